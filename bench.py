@@ -3,6 +3,7 @@
 all-reduce + Adam) of Hydra-GNN's room classifier on an MP3D-like hetero batch, on N MI355X of one node.
 
     python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--batch B] [--no-graph] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -13,8 +14,10 @@ per rank, hidden 256, fp32) are the other BASELINE configs; they are parity-test
 Weak scaling: every rank steps its own batch; ONE RCCL all-reduce of the flat gradient (+loss,count) per step makes the
 update the count-weighted global-batch update.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel family, HIP-event timed on
-the executor's streams) and `cpu_baseline` (the oracle = op-for-op PyG restatement, on the host cores).
+Prints ONE JSON line on rank 0 incl. `ms_per_step` (mean of exactly K timed steps), `roofline` (dominant kernel family, HIP-event
+timed on the executor's streams) and `cpu_baseline` (the oracle = op-for-op PyG restatement, on the host cores).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs); the inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -70,9 +73,12 @@ def parse():
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="launcher / rendezvous / timing-protocol rehearsal WITHOUT a GPU: gloo ranks, the step is the flat "
                          "all-reduce of a config-2-sized gradient buffer only; prints the JSON line with value null")
-    ap.add_argument("--min-timed-s", type=float, default=0.2,
-                    help="the K-step timed region is repeated (each repeat bracketed by barrier + synchronize) until this much "
-                         "time has been timed; `steps` stays K, `timed_regions` says how many")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="opt-in: the K-step timed region is repeated (each repeat bracketed by barrier + synchronize) until this "
+                         "much time has been timed; `timed_regions` says how many (default 0: exactly K timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returns to its caller (loss, updated parameters, "
+                         "Adam moments) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
     ap.add_argument("--fresh-batches", action="store_true",
                     help="extra leg (config 2 / 3): every step takes a DIFFERENT batch, collated on the device from a resident "
                          "dataset of min(64 x batch, max(2048, 4 x batch)) graphs (store.BatchStream: one host call + one kernel) and described afresh -- "
@@ -279,6 +285,40 @@ def emit_json(obj) -> None:
         os.write(_JSON_FD, line)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, step) -> dict:
+    """Write what the training step hands its caller after its last call: `loss` (float64 [1], mean masked CE), `params` (the
+    updated parameters) and `adam_m` / `adam_v` (the optimiser moments), each flat float32 in the model's named_parameters()
+    order -- independent of the executor's flat-buffer layout.  Above DUMP_MAX_BYTES in all, every array longer than its share
+    is cut to a fixed sample of its elements (seed 0, ascending order; the same sizes give the same indices).  Returns
+    {name: [elements written, elements computed]}."""
+    torch.cuda.synchronize()
+    nat = model.native()
+    named = [(n, p) for n, p in model.named_parameters() if id(p) in nat.param_offsets]
+    offs = [nat.param_offsets[id(p)] for _, p in named]
+
+    def gather(buf):
+        return torch.cat([buf[o:o + p.numel()] for o, (_, p) in zip(offs, named)]).cpu().numpy()
+
+    arrays = {"loss": np.array([step.loss()], dtype=np.float64), "params": gather(step.flat), "adam_m": gather(step.m),
+              "adam_v": gather(step.v)}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_MAX_BYTES - 1024 * len(arrays)  # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        full = a.size
+        if total > budget:
+            keep = max(1, int(a.size * budget / total))
+            if keep < a.size:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = [int(a.size), int(full)]
+    return written
+
+
 def free_port():
     import socket
 
@@ -475,6 +515,8 @@ def main():
         regions.append(timed_region())
     elapsed = float(sum(regions))
     timed_steps = args.steps * len(regions)
+    # before the untimed steps below move the parameters on
+    dumped = dump_outputs(args.dump_outputs, net, step) if (args.dump_outputs and rank == 0) else None
     # host cost of a step = time to ENQUEUE a few steps from an idle stream (no queue back-pressure); untimed extra steps
     host_us, extra_steps = 1e9, 0
     for _ in range(3):  # best of 3: the first launches after an idle period pay a wake-up that is not host work
@@ -530,6 +572,8 @@ def main():
             "host_enqueue_us_per_step": round(host_us, 1),
         },
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # ---- fresh-batch leg: the loop a trainer runs -- a new batch every step (base_training_job.py:202-216) --------------------
     if args.fresh_batches and args.config in (2, 3) and world == 1:

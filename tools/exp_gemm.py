@@ -1,5 +1,5 @@
-import sys, time, torch
-sys.path[:0] = ['/root/repo/hydra-gnn_amd']
+import os, sys, time, torch
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hydra-gnn_amd')]
 from hydra_gnn_amd import _lib
 lib = _lib.require_device()
 dev = 'cuda:0'

@@ -1,7 +1,7 @@
 """fp32 GEMM at the shapes of the GAT configuration (config 3) and of wide SAGE layers: us per launch and TFLOP/s.
     python tools/exp_gemm_big.py        (HMP_GEMM_BIG=0 / HMP_GEMM_BK=64 select kernel variants)"""
-import sys, torch
-sys.path[:0] = ['/root/repo/hydra-gnn_amd']
+import os, sys, torch
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hydra-gnn_amd')]
 from hydra_gnn_amd import _lib
 lib = _lib.require_device()
 dev = 'cuda:0'

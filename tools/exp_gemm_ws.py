@@ -1,7 +1,7 @@
 """bf16-A NT GEMM at the shape of config 5's projections: weight-stationary kernel vs the tiled kernel (HMP_GEMM_WS=0).
     python tools/exp_gemm_ws.py"""
-import sys, torch
-sys.path[:0] = ['/root/repo/hydra-gnn_amd']
+import os, sys, torch
+sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hydra-gnn_amd')]
 from hydra_gnn_amd import _lib
 lib = _lib.require_device()
 dev = 'cuda:0'
