@@ -19,8 +19,6 @@ KT_DEFINE(agg)
 KT_BLOCKS_DEFINE(agg)
 
 __device__ __forceinline__ int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
-[[maybe_unused]] constexpr int WIN_THREADS_CHAIN = 512;   // graph-local chain kernel: CHAIN_GROUPS groups of 256 threads (1024 threads would cap the
-[[maybe_unused]] constexpr int CHAIN_GROUPS = WIN_THREADS_CHAIN / 256;  // tile routines at 128 VGPRs: measured 1 201 spilled registers, 0.49 ms)
 
 // raw buffer descriptor over [base, base + bytes): loads past the end return 0 without touching memory
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, unsigned bytes) {
@@ -221,32 +219,6 @@ __global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const float* __re
   }
 }
 
-// ----- neighbour ids from the ELL table (kernels.h: ELL_W) ---------------------------------------------
-// The first 8 (PRE: 16) ids of `row`, requested by address arithmetic on the row alone: they travel in the same round trip as the
-// row extent.  Slots past the degree n were never written: they are replaced by the first id (a line the gather touches anyway;
-// the adds are masked by the callers exactly as for the clamped CSR loads), so every later load has a valid address.
-template <bool PRE>
-struct EllRow {
-  int4 h[PRE ? 4 : 2];
-  __device__ __forceinline__ void fetch(const int* __restrict__ ell, int row) {
-    const int4* p = reinterpret_cast<const int4*>(ell) + (int64_t)row * (ELL_W / 4);
-#pragma unroll
-    for (int q = 0; q < (PRE ? 4 : 2); ++q) h[q] = p[q];
-  }
-  __device__ __forceinline__ int word(int u) const {
-    const int4& v = h[u >> 2];
-    return (u & 3) == 0 ? v.x : (u & 3) == 1 ? v.y : (u & 3) == 2 ? v.z : v.w;
-  }
-  __device__ __forceinline__ void ids(int n, int (&j)[8], int (&jt)[PRE ? 8 : 1]) const {
-    const int first = n > 0 ? h[0].x : 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      j[u] = u < n ? word(u) : first;
-      if constexpr (PRE) jt[u] = 8 + u < n ? word(8 + u) : first;
-    }
-  }
-};
-
 // ----- fused SAGE layer aggregation -----------------------------------------------------------------
 // out[t][i] = dropout(act( zroot[i] + bias + sum_e mean_{k in N_e(i)} z_e[col_k] ))   (one row group, result also in `tot`)
 template <int GS, int NV, bool ZB = false, bool HB = false>
@@ -254,7 +226,7 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
   constexpr int VEC = 4;
   // Everything whose address depends on the row alone is requested here, and nothing of it is consumed before the gathers
   // (a use inside one of these branches would put an s_waitcnt in it): the device step counter of the dropout coordinates, the
-  // root row and the bias, the row extents of every incoming edge type, the ELL ids of the first pair -- ONE round trip.
+  // root row and the bias, the row extents of every incoming edge type -- ONE round trip.
   KT(3);
   DropCfg dcfg = D.drop;
   uint32_t step_add = 0;
@@ -275,18 +247,6 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
   for (int ii = 0; ii < AGG_MAX_IN; ++ii) {
     rb[ii] = re[ii] = 0;
     if (ii < D.n_in) { rb[ii] = D.in[ii].rowptr[row]; re[ii] = D.in[ii].rowptr[row + 1]; }
-  }
-  constexpr bool ELLP = NV == 1 && GS < 64;  // the pair path below
-  EllRow<GS <= 16> hA, hB;
-  bool ell0 = false;
-  if constexpr (ELLP) {
-    const AggIn& A0 = D.in[0];
-    const AggIn& A1 = D.in[D.n_in > 1 ? 1 : 0];
-    ell0 = D.n_in > 0 && A0.ell && A1.ell;  // block-uniform
-    if (ell0) {
-      hA.fetch(A0.ell, row);
-      hB.fetch(A1.ell, row);
-    }
   }
   KTW(4);
 #pragma unroll
@@ -358,14 +318,6 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
       // per SIMD (config 4: 0.140 -> 0.151 ms).
       constexpr bool PRE = GS <= 16;
       int j0[UB], j1[UB], j0t[PRE ? UB : 1], j1t[PRE ? UB : 1];
-      if (ii == 0 ? ell0 : (I0.ell && I1.ell)) {  // block-uniform: ids by row address, no dependence on the extents
-        if (ii != 0) {
-          hA.fetch(I0.ell, row);
-          hB.fetch(I1.ell, row);
-        }
-        hA.ids(e0 - b0, j0, j0t);
-        hB.ids(e1 - b1, j1, j1t);
-      } else {
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         j0[u] = I0.col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
@@ -374,7 +326,6 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
           j0t[u] = I0.col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
           j1t[u] = I1.col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
         }
-      }
       }
       Acc<VEC> v0[UB], v1[UB];
       const bool cin = c0 < D.F;
@@ -677,18 +628,6 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
     rb[oi] = re[oi] = 0;
     if (oi < S.n_out) { rb[oi] = S.out[oi].t_rowptr[row]; re[oi] = S.out[oi].t_rowptr[row + 1]; }
   }
-  // ELL ids of the first pair in the round trip of the extents (see agg_row)
-  EllRow<GS <= 16> hA, hB;
-  bool ell0 = false;
-  if constexpr (NV == 1) {
-    const TAggOut& A0 = S.out[0];
-    const TAggOut& A1 = S.out[S.n_out > 1 ? 1 : 0];
-    ell0 = S.n_out > 0 && A0.t_ell && A1.t_ell;  // block-uniform
-    if (ell0) {
-      hA.fetch(A0.t_ell, row);
-      hB.fetch(A1.t_ell, row);
-    }
-  }
   // (the 16-wide scalar-id form of agg_row was measured here too: 6.94 -> 7.02 ms at config 5, not kept)
   if constexpr (NV == 1) {
     // outgoing edge types in PAIRS (see agg_row): ids of both, then 1/deg + gradient rows of both
@@ -704,14 +643,6 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
       // GS <= 16: the ids of out-edges 8..15 travel with those of 0..7 (see agg_row): one round trip less for rows of 9..16 edges
       constexpr bool PRE = GS <= 16;
       int i0[UB], i1[UB], i0t[PRE ? UB : 1], i1t[PRE ? UB : 1];
-      if (oi == 0 ? ell0 : (O0.t_ell && O1.t_ell)) {  // block-uniform: ids by row address (see agg_row)
-        if (oi != 0) {
-          hA.fetch(O0.t_ell, row);
-          hB.fetch(O1.t_ell, row);
-        }
-        hA.ids(e0 - b0, i0, i0t);
-        hB.ids(e1 - b1, i1, i1t);
-      } else {
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         i0[u] = O0.t_col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
@@ -720,7 +651,6 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
           i0t[u] = O0.t_col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
           i1t[u] = O1.t_col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
         }
-      }
       }
       float d0[UB], d1[UB];
       Acc<VEC> v0[UB], v1[UB];
@@ -861,19 +791,6 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
       rb[oi] = re[oi] = 0;
       if (live && oi < S.n_out) { rb[oi] = S.out[oi].t_rowptr[row]; re[oi] = S.out[oi].t_rowptr[row + 1]; }
     }
-    // ELL ids of the first pair in the round trip of the extents (see agg_row); a row past the end reads the tile's first row
-    const int erow = live ? row : row0;
-    EllRow<GS <= 16> hA, hB;
-    bool ell0 = false;
-    {
-      const TAggOut& A0 = S.out[0];
-      const TAggOut& A1 = S.out[S.n_out > 1 ? 1 : 0];
-      ell0 = S.n_out > 0 && A0.t_ell && A1.t_ell;  // block-uniform
-      if (ell0) {
-        hA.fetch(A0.t_ell, erow);
-        hB.fetch(A1.t_ell, erow);
-      }
-    }
     // outgoing edge types in PAIRS (see agg_row): ids of both, then 1/deg + gradient rows of both
     constexpr int UB = 8;
 #pragma unroll
@@ -887,14 +804,6 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
       // GS <= 16: the ids of out-edges 8..15 travel with those of 0..7 (see agg_row): one round trip less for rows of 9..16 edges
       constexpr bool PRE = GS <= 16;
       int i0[UB], i1[UB], i0t[PRE ? UB : 1], i1t[PRE ? UB : 1];
-      if (oi == 0 ? ell0 : (O0.t_ell && O1.t_ell)) {  // block-uniform: ids by row address (see agg_row)
-        if (oi != 0) {
-          hA.fetch(O0.t_ell, erow);
-          hB.fetch(O1.t_ell, erow);
-        }
-        hA.ids(e0 - b0, i0, i0t);
-        hB.ids(e1 - b1, i1, i1t);
-      } else {
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         i0[u] = O0.t_col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
@@ -903,7 +812,6 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
           i0t[u] = O0.t_col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
           i1t[u] = O1.t_col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
         }
-      }
       }
       float d0[UB], d1[UB];
       Acc<VEC> v0[UB], v1[UB];
@@ -1052,160 +960,6 @@ __global__ __launch_bounds__(256) void agg_bwd_dx_kernel(const TAggArgs a) {
   agg_bwd_dx_tile<GS>(a, S, row0, min(row0 + S.tile_rows, S.n_rows), true, Hs);
   KT_SPAN_END(48, si);
 }
-
-#ifdef HMP_EXPERIMENTS  // measured 5x slower than the multi-launch sequence (profiles/r02_c_graph_local_chain.md): kept out of the product library
-// ----- graph-local chain: every launch between the front kernel and the weight-gradient GEMM, in ONE launch ------------------
-// A batch is a disjoint union of scene graphs: no edge crosses graphs, so from the first aggregation to the last transposed
-// aggregation a graph depends on nothing but itself.  One 1024-thread workgroup owns one graph for ALL of those phases
-// (aggregation + next projection per hidden layer, last aggregation + masked cross entropy, transposed aggregation +
-// input-gradient GEMM per layer): what were 2L launches with a cold L2 behind every boundary become phases separated by a
-// workgroup barrier, their operands written moments earlier by the same CU.  The phases ARE the tile / row routines of the
-// kernels above (four groups of 256 threads take the graph's 16-row tiles in turn), so results are bit-identical to the
-// multi-launch sequence (HMP_CHAIN=0).  The last workgroup to finish (an atomic ticket, no spinning) sums the per-row losses.
-// locate tile k of a phase: entries in order, ceil(rows / 16) tiles each
-template <class ARGS, class ENTRY>
-__device__ __forceinline__ bool chain_tile(const ChainArgs& A, const ARGS& a, const ENTRY* ents, const int* types, int g, int k, int& ei,
-                                           int& row0, int& row_end) {
-  for (int i = 0; i < a.n; ++i) {
-    const int64_t* pt = A.ptr[types[i]];
-    const int r0 = (int)pt[g], r1 = (int)pt[g + 1];
-    const int nt = (r1 - r0 + 15) >> 4;
-    if (k < nt) { ei = i; row0 = r0 + 16 * k; row_end = r1; return true; }
-    k -= nt;
-  }
-  ei = 0; row0 = 0; row_end = 0;
-  return false;
-}
-template <class ARGS>
-__device__ __forceinline__ int chain_tiles(const ChainArgs& A, const ARGS& a, const int* types, int g) {
-  int n = 0;
-  for (int i = 0; i < a.n; ++i) {
-    const int64_t* pt = A.ptr[types[i]];
-    n += ((int)pt[g + 1] - (int)pt[g] + 15) >> 4;
-  }
-  return n;
-}
-
-template <int GS>
-__device__ __forceinline__ void chain_ce_rows(const ChainArgs& A, const AggArgs& a, const int* types, int g) {
-  for (int i = 0; i < a.n; ++i) {
-    const AggDst& D = a.d[i];
-    const int64_t* pt = A.ptr[types[i]];
-    const int r0 = (int)pt[g], r1 = (int)pt[g + 1];
-    const int c0 = (threadIdx.x % GS) * 4;
-    for (int row = r0 + (int)threadIdx.x / GS; row < r1; row += WIN_THREADS_CHAIN / GS) {
-      Acc<4> tot[1];
-      int64_t y = 0;
-      if (D.ce_labels) y = D.ce_labels[row];
-      agg_row<GS, 1>(D, a.mean, row, c0, tot);
-      if (D.ce_labels) ce_rowgroup<GS>(D, a.state, row, c0, tot[0], y);
-    }
-  }
-}
-template <int GS>
-__device__ __forceinline__ void chain_bwd_rows(const ChainArgs& A, const TAggArgs& a, const int* types, int g) {
-  for (int i = 0; i < a.n; ++i) {
-    const TAggSrc& S = a.s[i];
-    const int64_t* pt = A.ptr[types[i]];
-    const int r0 = (int)pt[g], r1 = (int)pt[g + 1];
-    const int c0 = (threadIdx.x % GS) * 4;
-    for (int row = r0 + (int)threadIdx.x / GS; row < r1; row += WIN_THREADS_CHAIN / GS) agg_bwd_row<GS, 1>(a, S, row, c0);
-  }
-}
-
-template <int GS>
-__global__ __launch_bounds__(WIN_THREADS_CHAIN) void chain_kernel(const ChainArgs* __restrict__ Ap, int n_graphs, int fin_rows) {
-  extern __shared__ __attribute__((aligned(16))) float clds[];
-  __shared__ int s_last;
-  // the argument block (28 KB: the descriptors of every phase) is copied into LDS once -- read through the global pointer, every
-  // descriptor field an aggregation routine touches would be a dependent memory round trip of its own (measured: 0.51 ms
-  // for what five launches did in 0.05 ms); in the multi-launch kernels these fields sit in scalar registers
-  constexpr int ARG_F = (int)((sizeof(ChainArgs) + 15) / 16) * 4;  // floats
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(Ap);
-    uint4* dst = reinterpret_cast<uint4*>(clds);
-    for (int i = threadIdx.x; i < ARG_F / 4; i += WIN_THREADS_CHAIN) dst[i] = src[i];
-  }
-  __syncthreads();
-  const ChainArgs& A = *reinterpret_cast<const ChainArgs*>(clds);
-  const int g = blockIdx.x;
-  const int grp = threadIdx.x >> 8;
-  float* Hs = clds + ARG_F + (size_t)grp * A.lds_stride;
-  const int L = A.L;
-  // ---- forward
-  for (int l = 0; l < L; ++l) {
-    const AggArgs& a = A.fwd[l];
-    if (l < L - 1) {
-      const int T = chain_tiles(A, a, A.fwd_type[l], g);
-      for (int k0 = 0; k0 < T; k0 += CHAIN_GROUPS) {
-        int ei, row0, row_end;
-        const bool valid = chain_tile(A, a, a.d, A.fwd_type[l], g, k0 + grp, ei, row0, row_end);
-        agg_proj_tile<GS>(a, a.d[ei], row0, row_end, valid, Hs);
-        __syncthreads();  // the group's LDS image is rewritten by its next tile
-      }
-    } else {
-      if (A.gs_last == 8) chain_ce_rows<8>(A, a, A.fwd_type[l], g);
-      else if (A.gs_last == 16) chain_ce_rows<16>(A, a, A.fwd_type[l], g);
-      else chain_ce_rows<32>(A, a, A.fwd_type[l], g);
-    }
-    __syncthreads();  // phase boundary: this graph's rows of the layer are complete and visible to the whole workgroup
-  }
-  // ---- backward
-  for (int l = L - 1; l >= 0; --l) {
-    const TAggArgs& a = A.bwd[l];
-    if (l > 0) {
-      const int T = chain_tiles(A, a, A.bwd_type[l], g);
-      for (int k0 = 0; k0 < T; k0 += CHAIN_GROUPS) {
-        int ei, row0, row_end;
-        const bool valid = chain_tile(A, a, a.s, A.bwd_type[l], g, k0 + grp, ei, row0, row_end);
-        agg_bwd_dx_tile<GS>(a, a.s[ei], row0, row_end, valid, Hs);
-        __syncthreads();
-      }
-    } else {
-      if (A.gs_first == 8) chain_bwd_rows<8>(A, a, A.bwd_type[l], g);
-      else if (A.gs_first == 16) chain_bwd_rows<16>(A, a, A.bwd_type[l], g);
-      else chain_bwd_rows<32>(A, a, A.bwd_type[l], g);
-    }
-    __syncthreads();
-  }
-  // ---- the last workgroup to arrive sums the per-row {loss, valid} pairs of ALL graphs (fixed order: run-to-run identical)
-  if (A.fin_row_lv) {
-    if (threadIdx.x == 0) {
-      __threadfence();  // this workgroup's row_lv stores are out before the ticket
-      const unsigned t = atomicAdd(A.ticket, 1u);
-      s_last = (t == (unsigned)n_graphs - 1u) ? 1 : 0;
-      if (s_last) { *A.ticket = 0u; __threadfence(); }  // re-armed for the next step; acquire side of the hand-off
-    }
-    __syncthreads();
-    if (s_last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      // the summation order of finalize_loss (256 strided partial sums, then a tree): the same bits as the multi-launch path
-      float l = 0.f, v = 0.f;
-      const float* lv = A.fin_row_lv;
-      if (threadIdx.x < 256) {
-        for (int r = threadIdx.x; r < fin_rows; r += 256) {
-          l += __hip_atomic_load(lv + 2 * r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          v += __hip_atomic_load(lv + 2 * r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      float* sl = clds + ARG_F;
-      float* sv = clds + ARG_F + 256;
-      if (threadIdx.x < 256) { sl[threadIdx.x] = l; sv[threadIdx.x] = v; }
-      __syncthreads();
-      for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sl[threadIdx.x] += sl[threadIdx.x + o]; sv[threadIdx.x] += sv[threadIdx.x + o]; }
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) {
-        A.fin_out2[0] = sl[0];
-        A.fin_out2[1] = sv[0];
-        if (A.fin_state) { A.fin_state->loss_sum = sl[0]; A.fin_state->count = sv[0]; }
-      }
-    }
-  }
-}
-#endif  // HMP_EXPERIMENTS
-
 
 // ----- LDS sliding-window aggregation for the 10^6-row regime (bf16 rows of 256 elements = 512 bytes) ------------------------
 // Scene graphs are local: an object's neighbours are objects of the same room, and a graph builder numbers the objects of a
@@ -1638,328 +1392,6 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
   }
 }
 
-#ifdef HMP_EXPERIMENTS
-// ---------------------------------------------------------------------------------------------------------------------------
-// EXPERIMENT (make EXPERIMENTS=1, HMP_AGG_W4=1; correct -- tests/test_gpu_fusion.py, test_gpu_config5.py pass with it -- and SLOWER than
-// the per-edge kernel: 1.8 against 1.12 ms per launch; stamps and the two earlier forms: profiles/r03_n_matrix_pipe_window_sum.md).
-// Round 3, third form of the matrix-pipe window sum (agg_fwd_w4_kernel): the per-edge kernel's ROW-PER-WAVE layout for everything per
-// row, the product only for the in-window sum -- without any hand-over between waves.  v_mfma_f32_4x4x4_16b_bf16 multiplies 16
-// independent 4 x 4 x 4 blocks per wave; with the SAME A block in all of them (the count-matrix rows of the wave's 4 destination
-// rows: lane 4 b + i supplies row i) and B block b = 4 ring slots x features 4 b .. 4 b + 3 (one ds_read_b64_tr_b16 per lane from the
-// ring's natural [slot][feature] image), one instruction adds 4 slots into 4 rows x 64 features: lane l = feature 64 c + l of call c,
-// register i = row i (tools/microbench/mfma4_layout.hip checks this layout on the hardware).  48 k steps x 4 calls per chunk and
-// wave cover the window; only k steps in which one of the wave's rows has an edge are executed (a 48-bit mask built with the counts).
-// A lane then owns features l, 64 + l, 128 + l, 192 + l of each row: every row access is a 128-byte run per 64-feature slice.
-// Out-of-window edges (a per-row far table built with the counts) and the other edge types are requested per slice for all 4 rows.
-// LDS: ring 96 KB (192 slots = the window; the next chunk's rows wait in registers) + counts 25 KB + ids / extents / far table.
-// Sums: slot order + far edges in edge order (fp32; another association).
-constexpr int W4S = 192, W4_SUB = W4S * 256, W4_RING = 2 * W4_SUB, W4_CP = 400, W4_CBYTES = WR * W4_CP, W4_FARCAP = 8;
-constexpr int W4_LDS_FAR = WR * W4_FARCAP * 4 + WR * 4 + WIN_WAVES * 8;  // far ids, far counts, k-step masks
-constexpr int W4_LDS = W4_RING + W4_CBYTES + WIN_LDS_IDS + W4_LDS_FAR + WIN_LDS_RP;
-static_assert(W4_LDS <= 160 * 1024 && WM + WR + WM == W4S && WG == 4 && (W4_RING + W4_CBYTES + WIN_LDS_IDS) % 16 == 0, "LDS budget / window = ring / 4 rows per wave");
-typedef short w4_s16x4 __attribute__((ext_vector_type(4)));
-typedef float w4_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) unsigned char* w4_lds_ptr_t;
-__device__ __forceinline__ uint32_t w4_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(w4_lds_ptr_t)p; }
-__device__ __forceinline__ int w4_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-__device__ __forceinline__ w4_s16x4 w4_read_tr(uint32_t addr) {
-  w4_s16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-__device__ __forceinline__ void w4_barrier() {  // LDS operations done, then the barrier; vector-memory requests stay in flight
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ int w4_slot(int r) {
-  int s = r % W4S;
-  return s < 0 ? s + W4S : s;
-}
-__device__ __forceinline__ unsigned char* w4_ring_at(unsigned char* ring, int slot, int piece) {  // 16-byte piece (0..31) of a ring row
-  return ring + (piece >> 4) * W4_SUB + w4_off(slot, piece & 15);
-}
-template <bool HB>
-__global__ __launch_bounds__(WIN_THREADS) void agg_fwd_w4_kernel(const WinFwd a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wlds[];
-  unsigned char* ring = wlds;
-  unsigned char* cmat = wlds + W4_RING;
-  int* idbuf = reinterpret_cast<int*>(wlds + W4_RING + W4_CBYTES);                 // [2][WIDCAP]
-  int* farid = reinterpret_cast<int*>(wlds + W4_RING + W4_CBYTES + WIN_LDS_IDS);   // [WR][W4_FARCAP]
-  int* farcnt = farid + WR * W4_FARCAP;                                            // [WR]
-  unsigned long long* kmask = reinterpret_cast<unsigned long long*>(farcnt + WR);  // [WIN_WAVES]: k steps (of 4 slots) with an edge into the wave's rows
-  int* rpbuf = reinterpret_cast<int*>(kmask + WIN_WAVES);                          // [3][AGG_MAX_IN][WRP]
-  const AggDst& D = a.d;
-  const int n_rows = D.n_rows, nq = D.n_in;
-  const int c_begin = (int)blockIdx.x * a.chunks_per_block;
-  const int c_end = min(c_begin + a.chunks_per_block, a.n_chunks);
-  if (c_begin >= c_end) return;  // block-uniform
-  const int wave = uni((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int WQ = D.win_in;
-  const AggIn& IW = D.in[WQ];
-  const uint16_t* zwin = reinterpret_cast<const uint16_t*>(IW.z) + IW.coff;
-  DropCfg dcfg = D.drop;
-  if (D.drop_on) dcfg = drop_resolve(D.drop);
-  const uint32_t t16 = dcfg.thresh >> 16;
-  float biasv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (D.bias) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) biasv[c] = D.bias[64 * c + lane];
-  }
-  auto zero_c = [&]() {
-    for (int p = threadIdx.x; p < W4_CBYTES / 16; p += WIN_THREADS) *reinterpret_cast<uint4*>(cmat + p * 16) = make_uint4(0u, 0u, 0u, 0u);
-    if ((int)threadIdx.x < WIN_WAVES) kmask[threadIdx.x] = 0ull;
-  };
-  // ---- prologue ------------------------------------------------------------------------------------------------------------------------
-  {
-    const int r0 = win_load_rp(D, c_begin, a.n_chunks), r1 = win_load_rp(D, c_begin + 1, a.n_chunks);
-    if ((int)threadIdx.x < nq * WRP) {
-      rpbuf[(c_begin % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r0;
-      rpbuf[((c_begin + 1) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r1;
-    }
-    const int lo = c_begin * WR - WM;
-    for (int p = threadIdx.x; p < W4S * 32; p += WIN_THREADS) {  // the whole first window; rows outside the matrix: zeros (every slot is multiplied)
-      const int r = lo + (p >> 5), piece = p & 31;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (r >= 0 && r < n_rows) v = *reinterpret_cast<const uint4*>(zwin + (int64_t)r * IW.ldz + piece * 8);
-      *reinterpret_cast<uint4*>(w4_ring_at(ring, w4_slot(r), piece)) = v;
-    }
-    zero_c();
-    __syncthreads();
-    int ids[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS];
-    win_load_ids(D, rpbuf + (c_begin % 3) * AGG_MAX_IN * WRP, true, ids);
-#pragma unroll
-    for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-      const int p = (int)threadIdx.x + it * WIN_THREADS;
-      if (p < WIDCAP) idbuf[(c_begin & 1) * WIDCAP + p] = ids[it];
-    }
-    __syncthreads();
-  }
-
-  for (int i = 20; i < 31; ++i) KT_ZERO(i);
-  for (int ch = c_begin; ch < c_end; ++ch) {
-    [[maybe_unused]] const unsigned long long kt_0 = KT_NOW();
-    const int r_c = ch * WR;
-    const int* rp = rpbuf + (ch % 3) * AGG_MAX_IN * WRP;
-    const int* idc = idbuf + (ch & 1) * WIDCAP;
-    const bool next = ch + 1 < c_end;
-    // ---- requests for the chunks ahead --------------------------------------------------------------------------------------------------
-    WinStage stg;
-    {
-      const int nlo = r_c + WR + WM;  // new ring rows of chunk ch + 1: [nlo, nlo + WR)
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        stg.rows[it] = make_uint4(0u, 0u, 0u, 0u);
-        if (next && r < n_rows) stg.rows[it] = *reinterpret_cast<const uint4*>(zwin + (int64_t)r * IW.ldz + piece * 8);
-      }
-      win_load_ids(D, rpbuf + ((ch + 1) % 3) * AGG_MAX_IN * WRP, next, stg.ids);
-      stg.rp = (ch + 2 < c_end) ? win_load_rp(D, ch + 2, a.n_chunks) : 0;
-    }
-    int off[AGG_MAX_IN], eb[AGG_MAX_IN];
-    const bool fits = win_offsets(rp, nq, off, eb);
-    const int wlo = max(r_c - WM, 0), whi = min(r_c + WR + WM, n_rows);  // rows the ring holds now
-    const int offW = sel_q(off, WQ) - sel_q(eb, WQ);
-    // ---- counts + far table + k-step masks: the 16 threads (i, k) of row i take its edges k, k + 16, .. -------------------------------
-    {
-      const int i = (int)threadIdx.x >> 4, k0 = threadIdx.x & 15;
-      const int b = rp[WQ * WRP + i], e = rp[WQ * WRP + i + 1];
-      int nfar = 0;
-      unsigned long long km = 0ull;
-      for (int base = b;; base += 16) {
-        if (!__any(base < e)) break;  // wave-uniform (the four rows of a wave may differ in length)
-        const int p = base + k0;
-        const bool act = p < e;
-        const int id = act ? (fits ? idc[offW + p] : IW.col[p]) : 0;
-        const bool inw = act && id >= wlo && id < whi;
-        const bool far = act && !inw;
-        if (inw) {
-          const int sl = id % W4S;
-          asm volatile("ds_pk_add_bf16 %0, %1" ::"v"(w4_lds_addr(cmat + i * W4_CP + (sl >> 1) * 4)), "v"((sl & 1) ? 0x3f800000u : 0x00003f80u) : "memory");
-          km |= 1ull << (sl >> 2);
-        }
-        const unsigned long long fb = __ballot(far);
-        const unsigned grp = (unsigned)(fb >> (lane & 48)) & 0xffffu;  // the far flags of this row's 16 threads
-        const int pos = nfar + __popc(grp & ((1u << k0) - 1u));
-        if (far && pos < W4_FARCAP) farid[i * W4_FARCAP + pos] = id;
-        nfar += __popc(grp);
-      }
-      if (k0 == 0) farcnt[i] = nfar;
-      if (km) atomicOr(&kmask[i >> 2], km);  // rows 4 w .. 4 w + 3 belong to wave w (an OR of flags: order-independent)
-    }
-    w4_barrier();  // counts, far table and masks complete
-    KT_ADD(20, kt_0);
-    [[maybe_unused]] const unsigned long long kt_4 = KT_NOW();
-    // ---- the product for the wave's rows 4 w .. 4 w + 3 ---------------------------------------------------------------------------------------
-    w4_f32x4 accm[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) accm[c] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
-    {
-      unsigned long long km = kmask[wave];
-      km = ((unsigned long long)(uint32_t)uni((int)(km >> 32)) << 32) | (uint32_t)uni((int)km);
-      const unsigned char* Ai = cmat + (4 * wave + (lane & 3)) * W4_CP;
-      const int q = (lane & 15) >> 2;
-      uint32_t boff[4];  // byte offset of this lane's transposed-read address inside a ring row group, per call c (without the row term)
-      int bch[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int fo = 64 * (c & 1) + 16 * (lane >> 4) + 4 * (lane & 3);  // feature offset inside the sub-image
-        bch[c] = fo >> 3;
-        boff[c] = (c >> 1) * W4_SUB + 8 * ((fo >> 2) & 1);
-      }
-      while (km) {  // wave-uniform
-        const int k4 = __builtin_ctzll(km);
-        km &= km - 1ull;
-        const int row = 4 * k4 + q;
-        const uint2 araw = *reinterpret_cast<const uint2*>(Ai + 8 * k4);
-        w4_s16x4 bv[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) bv[c] = w4_read_tr(w4_lds_addr(ring + boff[c] + w4_off(row, bch[c])));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        union { uint2 u; w4_s16x4 v; } ua;
-        ua.u = araw;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) accm[c] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ua.v, bv[c], accm[c], 0, 0, 0);
-      }
-    }
-    w4_barrier();  // every wave has left the ring and C
-    KT_ADD(24, kt_4);
-    [[maybe_unused]] const unsigned long long kt_7 = KT_NOW();
-    // ---- the wave's 4 rows x 256 features, one 64-feature slice (MFMA call c) at a time: per slice ALL the rows' requests -- root, the
-    // first three far edges, the first edge of the other edge type -- are issued together (20 loads of 128 contiguous bytes), then
-    // summed, finished and stored.  (Row by row -- the per-edge kernel's order -- every row waited for its own far row and then for its
-    // rooms -> objects row with nothing else to do: 13 us of a 22 us chunk.) -----------------------------------------------------------------
-    const int DQ = (nq > 1) ? (WQ == 0 ? 1 : 0) : -1;  // first other edge type; further types (and further edges of this one) are walked
-    const AggIn& ID = D.in[DQ >= 0 ? DQ : WQ];
-    const uint16_t* zoth = reinterpret_cast<const uint16_t*>(ID.z) + ID.coff;
-    const __amdgpu_buffer_rsrc_t rsW = win_rsrc(zwin, (unsigned)IW.n_src * (unsigned)(IW.ldz * 2) - (unsigned)(IW.coff * 2));
-    const __amdgpu_buffer_rsrc_t rsD = win_rsrc(zoth, (unsigned)ID.n_src * (unsigned)(ID.ldz * 2) - (unsigned)(ID.coff * 2));
-    const int offD = DQ >= 0 ? sel_q(off, DQ) - sel_q(eb, DQ) : 0;
-    int rowg[4], nfg[4], dWg[4], bDg[4], dDg[4], f0g[4], f1g[4], f2g[4], d0g[4];  // wave-uniform per row
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int il = 4 * wave + g;
-      rowg[g] = r_c + il;
-      const bool live = rowg[g] < n_rows;
-      dWg[g] = live ? uni(rp[WQ * WRP + il + 1]) - uni(rp[WQ * WRP + il]) : 0;
-      nfg[g] = live ? uni(farcnt[il]) : 0;
-      f0g[g] = uni(farid[il * W4_FARCAP + 0]);
-      f1g[g] = uni(farid[il * W4_FARCAP + 1]);
-      f2g[g] = uni(farid[il * W4_FARCAP + 2]);
-      bDg[g] = DQ >= 0 ? uni(rp[DQ * WRP + il]) : 0;
-      dDg[g] = (live && DQ >= 0) ? uni(rp[DQ * WRP + il + 1]) - bDg[g] : 0;
-      d0g[g] = dDg[g] > 0 ? uni(fits ? idc[offD + bDg[g]] : ID.col[bDg[g]]) : 0;
-    }
-    const int ldW2 = IW.ldz * 2, ldD2 = ID.ldz * 2;
-    auto bf = [](uint32_t v) { return __uint_as_float(v << 16); };
-    auto slice = [&](auto cc) {
-      constexpr int c = decltype(cc)::value;
-      const unsigned vo = (unsigned)(lane * 2 + 128 * c);
-      uint32_t rootv[4], farv[4][3], othv[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int rowc = min(rowg[g], n_rows - 1);
-        rootv[g] = reinterpret_cast<const uint16_t*>(D.zroot)[(int64_t)rowc * D.ldzr + D.roff + 64 * c + lane];
-        farv[g][0] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsW, nfg[g] > 0 ? vo : WIN_SKIP_OFF, f0g[g] * ldW2, 0);
-        farv[g][1] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsW, nfg[g] > 1 ? vo : WIN_SKIP_OFF, f1g[g] * ldW2, 0);
-        farv[g][2] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsW, nfg[g] > 2 ? vo : WIN_SKIP_OFF, f2g[g] * ldW2, 0);
-        othv[g] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsD, dDg[g] > 0 ? vo : WIN_SKIP_OFF, d0g[g] * ldD2, 0);
-      }
-      // dropout decisions of quad 16 c + (lane >> 2) of the four rows: quad lane j computes row j's pair, the four lanes exchange them
-      uint32_t ha = 0u, hb = 0u;
-      if (D.drop_on) {
-        const int rsel = (lane & 3) == 0 ? rowg[0] : ((lane & 3) == 1 ? rowg[1] : ((lane & 3) == 2 ? rowg[2] : rowg[3]));
-        drop_pair(dcfg, (uint32_t)min(rsel, n_rows - 1) * (uint32_t)(D.ldo >> 2) + (uint32_t)(16 * c + (lane >> 2)), ha, hb);
-      }
-      uint32_t pa[4], pb[4];
-      pa[0] = __builtin_amdgcn_mov_dpp((int)ha, 0x00, 0xf, 0xf, true); pb[0] = __builtin_amdgcn_mov_dpp((int)hb, 0x00, 0xf, 0xf, true);
-      pa[1] = __builtin_amdgcn_mov_dpp((int)ha, 0x55, 0xf, 0xf, true); pb[1] = __builtin_amdgcn_mov_dpp((int)hb, 0x55, 0xf, 0xf, true);
-      pa[2] = __builtin_amdgcn_mov_dpp((int)ha, 0xaa, 0xf, 0xf, true); pb[2] = __builtin_amdgcn_mov_dpp((int)hb, 0xaa, 0xf, 0xf, true);
-      pa[3] = __builtin_amdgcn_mov_dpp((int)ha, 0xff, 0xf, 0xf, true); pb[3] = __builtin_amdgcn_mov_dpp((int)hb, 0xff, 0xf, 0xf, true);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (rowg[g] >= n_rows) continue;  // wave-uniform
-        const int il = 4 * wave + g;
-        float sw = accm[c][g] + bf(farv[g][0]);
-        sw += bf(farv[g][1]);
-        sw += bf(farv[g][2]);
-        if (nfg[g] > 3) {  // further far edges: table entries 3 .. 7, then (a graph without locality) the rest of the row's list
-          for (int jf = 3; jf < min(nfg[g], W4_FARCAP); ++jf)
-            sw += bf((uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsW, vo, uni(farid[il * W4_FARCAP + jf]) * ldW2, 0));
-          if (nfg[g] > W4_FARCAP) {
-            const int b = uni(rp[WQ * WRP + il]);
-            int seen = 0;
-            for (int p = 0; p < dWg[g]; ++p) {
-              const int id = uni(fits ? idc[offW + b + p] : IW.col[b + p]);
-              if (id >= wlo && id < whi) continue;
-              if (seen++ < W4_FARCAP) continue;
-              sw += bf((uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsW, vo, id * ldW2, 0));
-            }
-          }
-        }
-        float v = biasv[c] + bf(rootv[g]);
-        if (dWg[g] > 0) v = fmaf(sw, a.mean ? 1.0f / (float)dWg[g] : 1.f, v);
-        if (dDg[g] > 0) {
-          float sd = bf(othv[g]);
-          for (int p = 1; p < dDg[g]; ++p)  // (further edges of the other type: one waited-for row at a time)
-            sd += bf((uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rsD, vo, uni(fits ? idc[offD + bDg[g] + p] : ID.col[bDg[g] + p]) * ldD2, 0));
-          v = fmaf(sd, a.mean ? 1.0f / (float)dDg[g] : 1.f, v);
-        }
-        for (int q = 0; q < nq; ++q) {  // a third, fourth .. edge type: walked
-          if (q == WQ || q == DQ) continue;
-          const AggIn& I = D.in[q];
-          const int b = uni(rp[q * WRP + il]), e = uni(rp[q * WRP + il + 1]);
-          if (e == b) continue;
-          const uint16_t* zq = reinterpret_cast<const uint16_t*>(I.z) + I.coff;
-          const int offq = sel_q(off, q) - sel_q(eb, q);
-          float sq = 0.f;
-          for (int p = b; p < e; ++p) sq += bf((uint32_t)zq[(int64_t)uni(fits ? idc[offq + p] : I.col[p]) * I.ldz + 64 * c + lane]);
-          v = fmaf(sq, a.mean ? 1.0f / (float)(e - b) : 1.f, v);
-        }
-        if (D.act == HMP_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (D.act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-        if (D.drop_on) {
-          const uint32_t word = (lane & 2) ? pb[g] : pa[g];
-          const uint32_t draw = (lane & 1) ? (word >> 16) : (word & 0xffffu);
-          v = draw >= t16 ? (v * D.drop.scale + 0.0f) : -0.0f;
-        }
-        if constexpr (HB) reinterpret_cast<__bf16*>(D.out)[(int64_t)rowg[g] * D.ldo + 64 * c + lane] = (__bf16)v;
-        else D.out[(int64_t)rowg[g] * D.ldo + 64 * c + lane] = v;
-      }
-    };
-    slice(std::integral_constant<int, 0>());
-    slice(std::integral_constant<int, 1>());
-    slice(std::integral_constant<int, 2>());
-    slice(std::integral_constant<int, 3>());
-    KT_ADD(27, kt_7);
-    [[maybe_unused]] const unsigned long long kt_5 = KT_NOW();
-    // ---- what the requests brought goes to LDS; the counts are cleared for the next chunk -----------------------------------------------
-    if (next) {
-      const int nlo = r_c + WR + WM;
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        *reinterpret_cast<uint4*>(w4_ring_at(ring, w4_slot(r), piece)) = stg.rows[it];  // (rows past the matrix: zeros)
-      }
-#pragma unroll
-      for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        if (p < WIDCAP) idbuf[((ch + 1) & 1) * WIDCAP + p] = stg.ids[it];
-      }
-      if (ch + 2 < c_end && (int)threadIdx.x < nq * WRP) rpbuf[((ch + 2) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = stg.rp;
-      zero_c();
-    }
-    KT_ADD(25, kt_5);
-    [[maybe_unused]] const unsigned long long kt_8 = KT_NOW();
-    w4_barrier();
-    KT_ADD(28, kt_8);
-    KT_ADD(29, kt_0);
-  }
-}
-#endif  // HMP_EXPERIMENTS
-
 // transposed counterpart: source rows in chunks, ring over the gradient rows G of the destination type (same index space) and
 // their reciprocal in-degrees; one accumulator and one output segment per outgoing edge type
 template <bool DZB>
@@ -2141,25 +1573,6 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
   }
 }
 
-#ifdef HMP_EXPERIMENTS
-int chain_launch(const ChainArgs* d_args, int n_graphs, int fin_rows, int gs, size_t lds_bytes, hipStream_t st) {
-  lds_bytes += ((sizeof(ChainArgs) + 15) / 16) * 16;  // + the LDS copy of the argument block
-  HMP_CHECK_ARG(d_args && n_graphs > 0 && (gs == 16 || gs == 32) && lds_bytes <= 150 * 1024, "chain: bad launch (%d graphs, gs %d, %zu LDS bytes)", n_graphs, gs, lds_bytes);
-  static bool attr_done = false;
-  if (!attr_done) {
-    HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_done = true;
-  }
-  if (gs == 16) hipLaunchKernelGGL((chain_kernel<16>), dim3(n_graphs), dim3(WIN_THREADS_CHAIN), lds_bytes, st, d_args, n_graphs, fin_rows);
-  else hipLaunchKernelGGL((chain_kernel<32>), dim3(n_graphs), dim3(WIN_THREADS_CHAIN), lds_bytes, st, d_args, n_graphs, fin_rows);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
-#else
-int chain_launch(const ChainArgs*, int, int, int, size_t, hipStream_t) { HMP_FAIL(HMP_E_UNSUPPORTED, "chain_launch: experiment build only (make EXPERIMENTS=1)"); }
-#endif
-
 // ----- dispatch ---------------------------------------------------------------------------------------
 // lanes needed = ceil(F / VEC); GS = next pow2 in [8, 64]; NV = ceil(lanes / GS) <= 4
 // Measured at config 5 (10^6 rows of 256 floats, rocprofv3 --pmc): 152 M L2 requests per forward launch (= the 128-byte lines
@@ -2201,13 +1614,6 @@ static bool agg_win_enabled() {
   const char* v = getenv("HMP_AGG_WIN");
   return !(v && v[0] == '0');
 }
-#ifdef HMP_EXPERIMENTS
-// experiment builds, HMP_AGG_W4=1: the forward in-window sum by 4x4x4 MFMAs over a count matrix (agg_fwd_w4_kernel) instead of edge by edge
-static bool agg_w4_enabled() {
-  const char* v = getenv("HMP_AGG_W4");
-  return v && v[0] == '1';
-}
-#endif
 constexpr int AGG_WIN_MIN_ROWS = 16384;  // below: a persistent grid would leave CUs idle, the plain kernels do as well
 static int agg_win_grid(int n_chunks, int& per_block) {
   static int cus = 0;
@@ -2300,18 +1706,6 @@ int agg_fwd_launch(AggArgs& a, hipStream_t st) {
         }
 #endif
         const int grid = agg_win_grid(w.n_chunks, w.chunks_per_block);
-#ifdef HMP_EXPERIMENTS
-        if (agg_w4_enabled()) {  // the in-window sum on the matrix pipe, row-per-wave layout
-          static bool w4_attr_done = false;
-          if (!w4_attr_done) {
-            HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_fwd_w4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS));
-            HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_fwd_w4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS));
-            w4_attr_done = true;
-          }
-          if (a.hb16) hipLaunchKernelGGL((agg_fwd_w4_kernel<true>), dim3(grid), dim3(WIN_THREADS), W4_LDS, st, w);
-          else hipLaunchKernelGGL((agg_fwd_w4_kernel<false>), dim3(grid), dim3(WIN_THREADS), W4_LDS, st, w);
-        } else
-#endif
         if (a.hb16) hipLaunchKernelGGL((agg_fwd_win_kernel<true>), dim3(grid), dim3(WIN_THREADS), WIN_LDS_FWD, st, w);
         else hipLaunchKernelGGL((agg_fwd_win_kernel<false>), dim3(grid), dim3(WIN_THREADS), WIN_LDS_FWD, st, w);
         HMP_LAUNCH_CHECK();

@@ -94,7 +94,6 @@ struct FrontJob {    // one edge type of the plan; arrays as 4-byte-word offsets
   const int64_t* ei;
   int E, n_src, n_dst;
   uint32_t rowptr, col, eid, t_rowptr, t_col, t_eid, tmp_in, tmp_out, pos_of_eid, degf;
-  uint32_t ell, t_ell;  // 0: none
   const int64_t *gp_dst, *gp_src, *gp_edge;  // as PlanJob
   int n_graphs;
 };
@@ -148,7 +147,6 @@ struct PlanJob {
   int n_src, n_dst;
   int *rowptr, *col, *eid, *t_rowptr, *t_col, *t_pos;
   float* degf;  // optional [n_dst]: 1 / max(in-degree, 1) as float
-  int *ell, *t_ell;  // optional [n_dst][ELL_W] / [n_src][ELL_W]: first ids of every row; written by the single-launch build only
   // optional (all three or none; single-launch build only): the batch is a union of n_graphs graphs whose edges are listed graph
   // by graph -- int64 [n_graphs + 1] row offsets of the destination / source node type and edge offsets (hmp_batch::d_edge_ptr)
   const int64_t *gp_dst, *gp_src, *gp_edge;
@@ -165,7 +163,6 @@ struct PlanBatch {
   int n;
   int need_tpos;   // build t_pos (only GAT's source-major backward reads it)
   int clear_first; // memset the counters before the launch (caller-provided scratch of unknown content)
-  int built_small; // out: plan_launch took the single-launch build (the one that also writes PlanJob::ell / t_ell)
   int build_id;    // multi-launch build: stamp of this build (see PlanJob::flags)
   int* flags_all;  // [2 * n] = job 0's flag block used for ALL jobs: entry 2 j + dir (one pointer in the batch header: reading a
                    // per-job pointer through a per-lane job index made the compiler copy the 4 KB argument block to scratch)
@@ -183,10 +180,6 @@ int plan_link_launch(PlanBatch& pb, hipStream_t st);  // t_pos only, after a sin
 // K1 + fused SAGE aggregation
 // ---------------------------------------------------------------------------------------------
 constexpr int AGG_MAX_IN = 6;
-// Neighbour-id table in ELL form next to the CSR arrays: row r's first ELL_W ids at ell[r * ELL_W ..] (slots past the row's degree
-// are NOT written).  Its address depends on the row alone, so the small-batch aggregation kernels request it together with the
-// row extent -- extents+ids, rows: two dependent round trips where the CSR form needs three (extents, ids, rows).
-constexpr int ELL_W = 16;
 struct AggIn {
   const int* rowptr;
   const int* col;
@@ -194,11 +187,9 @@ struct AggIn {
   int ldz, coff;
   int same_type;   // source node type == destination node type (one index space): candidate for the LDS-windowed gather
   int n_src;       // rows of z
-  const int* ell;  // [n_dst][ELL_W] first neighbour ids of every row (single-launch plan by-product, see plan_small.h), or null
 };
 struct AggDst {
   int n_rows, F;
-  int type;  // node type index (graph-local chain: which row-offset vector positions this entry)
   float* out;
   int ldo;
   const float* zroot;  // may be null
@@ -252,11 +243,9 @@ struct TAggOut {
   int ldg, coff, F;
   int same_type;      // destination node type == source node type: candidate for the LDS-windowed gather
   int n_dst;          // rows of g
-  const int* t_ell;   // [n_src][ELL_W] first out-neighbour ids of every row, or null (see AggIn::ell)
 };
 struct TAggSrc {
   int n_rows;
-  int type;  // node type index
   float* dz;
   int lddz, ncols;     // ncols (padded): columns not covered by a segment are zeroed
   const float* groot;  // may be null
@@ -299,24 +288,6 @@ int seg_mean_rows_launch(const void* x, int ldx, int x_bf16, int F, const int* r
                          hipStream_t st);
 int seg_mean_rows_t_launch(const float* dm, int lddm, int F, const int* t_rowptr, const int* t_col, const float* degf, int n_rows,
                            const void* h, int ldh, int h_bf16, int act, int drop_on, float dscale, void* g, int ldg, int g_bf16, hipStream_t st);
-
-// graph-local chain (aggregate.hip: chain_kernel): all launches between the front kernel and the weight-gradient GEMM as phases
-// of ONE launch, one workgroup per graph.  The argument block lives in device memory (several KB).
-constexpr int CHAIN_MAX_LAYERS = 4;
-struct ChainArgs {
-  int L, lds_stride;
-  int gs_last, gs_first;  // row-group widths of the last forward layer / the layer-0 transposed aggregation
-  const int64_t* ptr[HMP_MAX_NODE_TYPES];  // [n_graphs + 1] row offsets of every node type (null: type without rows here)
-  AggArgs fwd[CHAIN_MAX_LAYERS];
-  int fwd_type[CHAIN_MAX_LAYERS][HMP_MAX_NODE_TYPES];  // node type of fwd[l].d[i]
-  TAggArgs bwd[CHAIN_MAX_LAYERS];                       // bwd[l] = layer l
-  int bwd_type[CHAIN_MAX_LAYERS][HMP_MAX_NODE_TYPES];
-  unsigned* ticket;
-  const float* fin_row_lv;
-  float* fin_out2;
-  NetState* fin_state;
-};
-int chain_launch(const ChainArgs* d_args, int n_graphs, int fin_rows, int gs, size_t lds_bytes, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // parameter packing / gradient un-packing (tables live in device memory, built at bind time)

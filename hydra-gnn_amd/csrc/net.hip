@@ -79,7 +79,6 @@ struct ProfRec {
 struct EnvSwitches {
   bool plan_sliced = true;  // HMP_PLAN_SLICED=0: plan parts read the whole edge list (tests compare both builds)
   bool front = true;        // HMP_FRONT=0: separate pack / projection / plan launches
-  bool ell = false;         // HMP_ELL=1 (experiment builds only): neighbour ids from the plan's ELL tables
   bool z16 = true;          // HMP_Z16=0: keep fp32 projected rows / gradients in bf16 compute mode
   bool h16 = true;          // HMP_H16=0: keep fp32 activations in bf16 compute mode
   bool rootcopy = false;    // HMP_ROOTCOPY=1: the transposed aggregation copies the root block of dZ
@@ -114,10 +113,6 @@ struct hmp_net {
   char* ws_base = nullptr;
   size_t ws_bytes = 0;
   float* degf[HMP_MAX_EDGE_TYPES];  // 1 / max(in-degree,1) per destination node, by-product of the plan
-  int* ell[HMP_MAX_EDGE_TYPES];     // [n_dst][ELL_W] / [n_src][ELL_W] first neighbour ids per row (kernels.h), by-product of
-  int* t_ell[HMP_MAX_EDGE_TYPES];   // the single-launch plan build only: valid while ell_ok
-  bool ell_ok = false;
-  bool ell_on = false;              // this call: HMP_ELL=1
   bool any_agg_first = false;       // some conv is evaluated aggregate-first (large batches only: never with the small-batch sequence)
   int* d_iota = nullptr;            // 0, 1, 2, ..: row extents AND ids of the identity lists that hand an aggregate-first block to
   float* d_ones = nullptr;          // the aggregation kernels (in-degree 1, weight 1)
@@ -175,22 +170,6 @@ struct hmp_net {
   hipEvent_t evs[32];
   int n_evs = 0, ev_i = 0;
 
-  // graph-local chain (aggregate.hip: chain_kernel): the aggregation launches of a fused training step are DEFERRED while they
-  // qualify; at the weight-gradient point they run as one launch (or, if anything in between did not qualify, in order as before)
-  struct Deferred {
-    int kind;  // 0 agg_proj_fwd, 1 agg_fwd, 2 agg_bwd_dx, 3 agg_bwd
-    AggArgs fa;
-    TAggArgs ba;
-  };
-  bool chain_try = false;        // this step: defer
-  std::vector<Deferred> deferred;
-  int chain_mode = -1;           // HMP_CHAIN override (0 / 1), -1 = automatic
-  ChainArgs* chain_h = nullptr;  // host copy of what the device holds (pinned)
-  ChainArgs* chain_stage = nullptr;
-  ChainArgs* d_chain = nullptr;
-  hipEvent_t chain_copied = nullptr;
-  bool chain_valid = false;
-
   // profiling
   bool prof = false;
   std::vector<ProfRec> recs;
@@ -203,9 +182,6 @@ void read_env(hmp_net* n) {
   EnvSwitches e;
   e.plan_sliced = !is("HMP_PLAN_SLICED", '0');
   e.front = !is("HMP_FRONT", '0');
-#ifdef HMP_EXPERIMENTS
-  e.ell = is("HMP_ELL", '1');
-#endif
   e.z16 = !is("HMP_Z16", '0');
   e.h16 = !is("HMP_H16", '0');
   e.rootcopy = is("HMP_ROOTCOPY", '1');
@@ -597,8 +573,6 @@ size_t carve(hmp_net* n, char* base, const int32_t* cn, const int64_t* ce) {
     P.d_t_pos = (int32_t*)take((size_t)ce[e] * 4);
     n->plan_scratch[e] = (int*)take(plan_scratch_ints(ce[e], ns, nd) * 4);
     n->degf[e] = (float*)take((size_t)nd * 4);
-    n->ell[e] = (int*)take((size_t)nd * ELL_W * 4);
-    n->t_ell[e] = (int*)take((size_t)ns * ELL_W * 4);
   }
   n->d_packed = (float*)take((size_t)n->packed_floats * 4);
   n->d_slabs = (float*)take((size_t)n->slab_floats * 4);
@@ -751,14 +725,6 @@ struct Scope {
     n->recs.push_back(r);
     idx = (int)n->recs.size() - 1;
   }
-  void cancel() {  // nothing was launched inside (the launch was deferred): drop the record
-    if (idx >= 0 && idx == (int)n->recs.size() - 1) {
-      (void)hipEventDestroy(n->recs[idx].a);
-      (void)hipEventDestroy(n->recs[idx].b);
-      n->recs.pop_back();
-    }
-    idx = -1;
-  }
   ~Scope() {
     if (idx >= 0) (void)hipEventRecord(n->recs[idx].b, st);
   }
@@ -773,7 +739,8 @@ int fork_to(hmp_net* n, hipStream_t from, hipStream_t to) {
   return HMP_OK;
 }
 
-enum { KC_PLAN = 0, KC_PACK, KC_GEMM_FWD, KC_AGG_FWD, KC_LOSS, KC_AGG_BWD, KC_GEMM_BWD, KC_GRAD_REDUCE, KC_ADAM, KC_GAT_FWD, KC_GAT_BWD, KC_POOL, KC_FRONT, KC_CHAIN };
+// profile classes (hmp_net_profile_read); slot 13 (chain) is retired and always 0
+enum { KC_PLAN = 0, KC_PACK, KC_GEMM_FWD, KC_AGG_FWD, KC_LOSS, KC_AGG_BWD, KC_GEMM_BWD, KC_GRAD_REDUCE, KC_ADAM, KC_GAT_FWD, KC_GAT_BWD, KC_POOL, KC_FRONT };
 
 DropCfg make_drop(const hmp_net* n, float p, uint32_t stream) {
   DropCfg d;
@@ -823,8 +790,6 @@ int check_batch(const hmp_net* n, const hmp_batch* b) {
 }
 
 // ---- forward -------------------------------------------------------------------------------------------
-// the ELL id tables of the current plan may be read (HMP_ELL=0: never -- the CSR-only gathers, for tests and A/B runs)
-bool ell_use(const hmp_net* n) { return n->ell_on && n->ell_ok; }
 void fill_plan_batch(hmp_net* n, const hmp_batch* b, PlanBatch& pb) {
   memset(&pb, 0, sizeof(pb));
   pb.n = n->ET;
@@ -848,8 +813,6 @@ void fill_plan_batch(hmp_net* n, const hmp_batch* b, PlanBatch& pb) {
         J.gp_edge = b->d_edge_ptr[e]; J.gp_src = b->d_node_ptr[ts]; J.gp_dst = b->d_node_ptr[td]; J.n_graphs = b->n_graphs;
       }
     }
-    J.ell = n->ell_on ? n->ell[e] : nullptr;
-    J.t_ell = n->ell_on ? n->t_ell[e] : nullptr;
     plan_carve(J, n->plan_scratch[e]);
   }
 }
@@ -858,9 +821,7 @@ int run_plan(hmp_net* n, const hmp_batch* b, hipStream_t st) {
   Scope sc(n, KC_PLAN, st);
   PlanBatch pb;
   fill_plan_batch(n, b, pb);
-  const int rc = plan_launch(pb, &n->d_state->status, st);
-  n->ell_ok = rc == HMP_OK && pb.built_small != 0 && n->ell_on;
-  return rc;
+  return plan_launch(pb, &n->d_state->status, st);
 }
 
 // Small (launch-latency-bound) batches (<= 65 536 nodes): the row-local GEMM that follows an aggregation (next layer's projection in the
@@ -997,8 +958,6 @@ bool build_front(hmp_net* n, const hmp_batch* b, const float* d_params, FrontArg
     F.t_rowptr = woff(J.t_rowptr); F.t_col = woff(J.t_col); F.t_eid = woff(J.t_eid);
     F.tmp_in = woff(J.tmp_in); F.tmp_out = woff(J.tmp_out); F.pos_of_eid = woff(J.pos_of_eid); F.degf = woff(J.degf);
     F.gp_dst = J.gp_dst; F.gp_src = J.gp_src; F.gp_edge = J.gp_edge; F.n_graphs = J.n_graphs;
-    F.ell = J.ell ? woff(J.ell) : 0u;
-    F.t_ell = J.t_ell ? woff(J.t_ell) : 0u;
   }
   fa.status = &n->d_state->status;
   // ---- pack blocks
@@ -1012,115 +971,6 @@ bool build_front(hmp_net* n, const hmp_batch* b, const float* d_params, FrontArg
   return true;
 }
 
-// launches what was deferred, in order, as the multi-launch sequence would have
-int chain_flush(hmp_net* n, hipStream_t st) {
-  n->chain_try = false;
-  for (auto& d : n->deferred) {
-    if (d.kind <= 1) {
-      Scope sc(n, KC_AGG_FWD, st);
-      HMP_TRY(d.kind == 0 ? agg_proj_fwd_launch(d.fa, st) : agg_fwd_launch(d.fa, st));
-    } else {
-      Scope sc(n, KC_AGG_BWD, st);
-      HMP_TRY(d.kind == 2 ? agg_bwd_dx_launch(d.ba, st) : agg_bwd_launch(d.ba, st));
-    }
-  }
-  n->deferred.clear();
-  return HMP_OK;
-}
-
-inline int gs_of(int fmax) {  // pick_shape of aggregate.hip for NV == 1 shapes
-  int gs = 8;
-  const int lanes = (fmax + 3) / 4;
-  while (gs < 64 && gs < lanes) gs <<= 1;
-  return gs;
-}
-inline int gs_tile(int fmax) {  // agg_proj_fwd_launch / agg_bwd_dx_launch
-  int gs = 16;
-  while (gs < 64 && gs * 4 < fmax) gs <<= 1;
-  return gs;
-}
-
-// everything deferred -> ONE chain launch, if the recorded sequence is exactly {L-1 x agg+proj, agg+CE, L-1 x aggT+dX, aggT} of one
-// tile shape; else the multi-launch sequence
-int chain_run(hmp_net* n, hipStream_t st) {
-  if (!n->chain_try) return HMP_OK;
-  const hmp_batch* b = &n->batch;
-  const int L = n->L;
-  bool ok = (int)n->deferred.size() == 2 * L && L >= 1 && L <= CHAIN_MAX_LAYERS && b->n_graphs > 0;
-  int gs = 0, gs_last = 0, gs_first = 0, kmax = 0;
-  for (int i = 0; ok && i < 2 * L; ++i) {
-    const hmp_net::Deferred& d = n->deferred[i];
-    const int want = i < L - 1 ? 0 : (i == L - 1 ? 1 : (i < 2 * L - 1 ? 2 : 3));
-    if (d.kind != want) { ok = false; break; }
-    int fmax = 0;
-    if (d.kind <= 1) {
-      for (int q = 0; q < d.fa.n; ++q) fmax = d.fa.d[q].F > fmax ? d.fa.d[q].F : fmax;
-      if (d.kind == 0) { const int g = gs_tile(fmax); if (gs && g != gs) ok = false; gs = g; }
-      else {
-        gs_last = gs_of(fmax);
-        for (int q = 0; q < d.fa.n; ++q) if (!d.fa.d[q].ce_labels) ok = false;  // the readout rows carry the loss
-        if (d.fa.zb16 || d.fa.hb16) ok = false;
-      }
-    } else {
-      for (int q = 0; q < d.ba.n; ++q) {
-        for (int o = 0; o < d.ba.s[q].n_out; ++o) fmax = d.ba.s[q].out[o].F > fmax ? d.ba.s[q].out[o].F : fmax;
-        if (d.ba.s[q].groot) fmax = d.ba.s[q].Froot > fmax ? d.ba.s[q].Froot : fmax;
-        kmax = d.ba.s[q].ncols > kmax ? d.ba.s[q].ncols : kmax;
-      }
-      if (d.kind == 2) { const int g = gs_tile(fmax); if (gs && g != gs) ok = false; gs = g; }
-      else { gs_first = gs_of(fmax); if (d.ba.gb16 || d.ba.dzb16) ok = false; }
-    }
-  }
-  if (L == 1) gs = 16;
-  const int stride = (256 * 17 > kmax * 17) ? 256 * 17 : kmax * 17;
-  const size_t lds = (size_t)2 * stride * sizeof(float);  // CHAIN_GROUPS = 2 groups of 256 threads
-  if (ok) ok = (gs == 16 || gs == 32) && gs_last <= 32 && gs_first <= 32 && lds + sizeof(ChainArgs) + 16 <= 150 * 1024;
-  if (!ok) return chain_flush(n, st);
-  // ---- argument block
-  if (!n->chain_h) {
-    HMP_HIP(hipHostMalloc((void**)&n->chain_h, sizeof(ChainArgs), hipHostMallocDefault));
-    HMP_HIP(hipHostMalloc((void**)&n->chain_stage, sizeof(ChainArgs), hipHostMallocDefault));
-    HMP_HIP(hipMalloc((void**)&n->d_chain, sizeof(ChainArgs)));
-    HMP_HIP(hipEventCreateWithFlags(&n->chain_copied, hipEventDisableTiming));
-    n->chain_valid = false;
-  }
-  ChainArgs& C = *n->chain_stage;
-  HMP_HIP(hipEventSynchronize(n->chain_copied));  // the previous upload has left the staging buffer (no-op when none is pending)
-  memset(&C, 0, sizeof(C));
-  C.L = L; C.lds_stride = stride; C.gs_last = gs_last; C.gs_first = gs_first;
-  for (int t = 0; t < n->T; ++t) C.ptr[t] = b->d_node_ptr[t];
-  for (int l = 0; l < L; ++l) {
-    C.fwd[l] = n->deferred[l].fa;
-    for (int q = 0; q < C.fwd[l].n; ++q) { C.fwd_type[l][q] = C.fwd[l].d[q].type; C.fwd[l].d[q].n_rows = 0; C.fwd[l].d[q].block_start = 0; }
-    C.fwd[l].total_blocks = 0;
-    TAggArgs& B = C.bwd[L - 1 - (l)];  // deferred[L + j] is layer L - 1 - j
-    B = n->deferred[L + l].ba;
-    for (int q = 0; q < B.n; ++q) { C.bwd_type[L - 1 - l][q] = B.s[q].type; B.s[q].n_rows = 0; B.s[q].block_start = 0; }
-    B.total_blocks = 0;
-    if (B.fin_row_lv) { C.fin_row_lv = B.fin_row_lv; C.fin_out2 = B.fin_out2; C.fin_state = B.fin_state; }
-    B.fin_row_lv = nullptr; B.fin_rows = 0; B.fin_out2 = nullptr; B.fin_state = nullptr;
-  }
-  C.ticket = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(n->d_state) + 128);
-  for (int t = 0; t < n->T; ++t) {  // every node type an entry works on needs its row offsets
-    bool used = false;
-    for (int l = 0; l < L; ++l) {
-      for (int q = 0; q < C.fwd[l].n; ++q) used = used || C.fwd_type[l][q] == t;
-      for (int q = 0; q < C.bwd[l].n; ++q) used = used || C.bwd_type[l][q] == t;
-    }
-    if (used && !C.ptr[t]) return chain_flush(n, st);
-  }
-  if (!n->chain_valid || memcmp(&C, n->chain_h, sizeof(ChainArgs)) != 0) {
-    memcpy(n->chain_h, &C, sizeof(ChainArgs));
-    HMP_HIP(hipMemcpyAsync(n->d_chain, n->chain_stage, sizeof(ChainArgs), hipMemcpyHostToDevice, st));
-    HMP_HIP(hipEventRecord(n->chain_copied, st));
-    n->chain_valid = true;
-  }
-  n->deferred.clear();
-  n->chain_try = false;
-  Scope sc(n, KC_CHAIN, st);
-  return chain_launch(n->d_chain, b->n_graphs, b->n_out, gs, lds, st);
-}
-
 int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStream_t st) {
   HMP_TRY(check_batch(n, b));
   n->batch = *b;
@@ -1132,7 +982,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
   hipStream_t side = (n->use_branches && (n->branch_mask & 1)) ? n->side[0] : main_st;
   if (side != main_st) HMP_TRY(fork_to(n, main_st, side));
   n->fuse_now = fuse_small(n, b);
-  n->ell_on = n->env.ell;  // (experiment builds: neighbour ids from the plan's ELL tables; measured slower, see kernels.h)
   memset(n->h16, 0, sizeof(n->h16));
   n->reuse_plan = false;
   if (b->plan_valid) {
@@ -1150,7 +999,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
   if (front) {
     Scope sc(n, KC_FRONT, main_st);
     HMP_TRY(front_launch(fa, main_st));
-    if (fa.plan_blocks > 0) n->ell_ok = n->ell_on;  // the front kernel's plan role is the single-launch build
     if (fa.need_tpos && fa.plan_blocks > 0) {
       PlanBatch pb;
       fill_plan_batch(n, b, pb);
@@ -1177,7 +1025,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
     if (l == 0 && front && fa.n_prob > 0) {
       // projection, plan and pack already ran in the front kernel
     } else if (!z_done) {  // grouped projection (skipped when the previous layer's aggregation kernel already produced Z[l])
-      HMP_TRY(chain_flush(n, st));
       Scope sc(n, KC_GEMM_FWD, st);
       std::vector<GemmProblem> ps;
       for (int s = 0; s < n->T; ++s) {
@@ -1252,7 +1099,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       st = main_st;
     }
     if (Y.kind == HMP_CONV_GAT) {
-      HMP_TRY(chain_flush(n, st));
       Scope sc(n, KC_GAT_FWD, st);
       GatDyn dyn = make_gat_dyn(n, b);
       HMP_TRY(gat_fwd_launch(Y.d_gat, Y.h_gat, dyn, st));
@@ -1274,7 +1120,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           n->ce_done = true;
         }
         D.n_rows = b->n_nodes[t];
-        D.type = t;
         D.F = fpad(Ls.out_dim[t]);
         D.out = n->H[l + 1][t]; D.ldo = n->ld[l + 1][t];
         D.zroot = n->Z[l][t]; D.ldzr = Y.ncols[t]; D.roff = Y.roff[t];
@@ -1291,7 +1136,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           if (Y.conv[c].agg_first) {  // the conv's block of this type's own Z, through identity lists (in-degree 1)
             I.rowptr = n->d_iota; I.col = n->d_iota;
             I.z = n->Z[l][t]; I.ldz = Y.ncols[t]; I.coff = Y.conv[c].aoff;
-            I.same_type = 0; I.n_src = b->n_nodes[t]; I.ell = nullptr;
+            I.same_type = 0; I.n_src = b->n_nodes[t];
             continue;
           }
           I.rowptr = n->plan[C.edge_type].d_rowptr;
@@ -1299,7 +1144,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           I.z = n->Z[l][C.src]; I.ldz = Y.ncols[C.src]; I.coff = Y.conv[c].coff;
           I.same_type = C.src == C.dst ? 1 : 0;
           I.n_src = b->n_nodes[C.src];
-          I.ell = ell_use(n) ? n->ell[C.edge_type] : nullptr;
           if (n->fuse_now && b->n_edges[C.edge_type] > (int64_t)8 * b->n_nodes[C.dst]) D.tile_rows = 8;  // average in-degree > 8
         }
       }
@@ -1325,14 +1169,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           D.pw = n->d_packed + Yn.wp_off[t]; D.pldw = Yn.ldw[t]; D.pncols = Yn.ncols[t]; D.pK = n->dim[l + 1][t];
           D.pz = n->Z[l + 1][t]; D.pldz = Yn.ncols[t];
         }
-        if (n->chain_try) {
-          hmp_net::Deferred d;
-          d.kind = 0; d.fa = a;
-          n->deferred.push_back(d);
-          sc.cancel();
-        } else {
-          HMP_TRY(agg_proj_fwd_launch(a, st));
-        }
+        HMP_TRY(agg_proj_fwd_launch(a, st));
         z_done = true;
       } else {
         a.zb16 = z16 ? 1 : 0;
@@ -1363,20 +1200,11 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           for (int t = 0; t < n->T; ++t)
             if (Y.roff[t] >= 0 && b->n_nodes[t] > 0) n->h16[l + 1][t] = true;
         }
-        if (n->chain_try && n->fuse_now && !z16) {
-          hmp_net::Deferred d;
-          d.kind = 1; d.fa = a;
-          n->deferred.push_back(d);
-          sc.cancel();
-        } else {
-          HMP_TRY(chain_flush(n, st));
-          HMP_TRY(agg_fwd_launch(a, st));
-        }
+        HMP_TRY(agg_fwd_launch(a, st));
       }
     }
   }
   if (S.pool_edge_type >= 0) {
-    HMP_TRY(chain_flush(n, st));
     Scope sc(n, KC_POOL, st);
     const int rt = S.readout_type;
     HMP_TRY(hmp_segment_mean_fwd(n->H[n->L][rt], n->ld[n->L][rt], n->out_ld, n->plan[S.pool_edge_type], n->d_out, n->out_ld, st));
@@ -1414,7 +1242,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
   const float* gtop = d_gout;
   int ld_gtop = ld_gout;
   if (S.pool_edge_type >= 0) {
-    HMP_TRY(chain_flush(n, st));
     Scope sc(n, KC_POOL, st);
     HMP_TRY(hmp_segment_mean_bwd(d_gout, ld_gout, n->out_ld, n->plan[S.pool_edge_type], n->G[n->L][rt], n->ld[n->L][rt], st));
     gtop = n->G[n->L][rt];
@@ -1447,7 +1274,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     bool rootless = false;  // this layer's GEMMs take the root block of dZ from the output gradient
     dz16 = false;
     if (Y.kind == HMP_CONV_GAT) {
-      HMP_TRY(chain_flush(n, st));
       Scope sc(n, KC_GAT_BWD, st);
       GatDyn dyn = make_gat_dyn(n, b);
       dyn.g_top = gtop; dyn.ld_gtop = ld_gtop;
@@ -1467,7 +1293,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         if (Y.ncols[s] == 0 || b->n_nodes[s] == 0) continue;
         TAggSrc& T = a.s[a.n++];
         T.n_rows = b->n_nodes[s];
-        T.type = s;
         T.dz = n->dZ[l][s]; T.lddz = Y.ncols[s]; T.ncols = Y.ncols[s];
         if (Y.roff[s] >= 0) {
           int ldg;
@@ -1484,7 +1309,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
             int ldg;
             O.g = g_of(s, ldg);
             O.ldg = ldg; O.coff = Y.conv[c].aoff; O.F = fpad(C.f_out);
-            O.same_type = 0; O.n_dst = b->n_nodes[s]; O.t_ell = nullptr;
+            O.same_type = 0; O.n_dst = b->n_nodes[s];
             continue;
           }
           if (C.src != s) continue;
@@ -1496,7 +1321,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           O.ldg = ldg; O.coff = Y.conv[c].coff; O.F = fpad(C.f_out);
           O.same_type = C.src == C.dst ? 1 : 0;
           O.n_dst = b->n_nodes[C.dst];
-          O.t_ell = ell_use(n) ? n->t_ell[C.edge_type] : nullptr;
           if (n->fuse_now && b->n_edges[C.edge_type] > (int64_t)8 * b->n_nodes[C.src]) T.tile_rows = 8;  // average out-degree > 8
         }
       }
@@ -1524,14 +1348,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           T.xh = (T.xact != HMP_ACT_NONE || T.xdrop_on) ? n->H[l][s] : nullptr;
           T.xldh = n->ld[l][s];
         }
-        if (n->chain_try) {
-          hmp_net::Deferred d;
-          d.kind = 2; d.ba = a;
-          n->deferred.push_back(d);
-          sc.cancel();
-        } else {
-          HMP_TRY(agg_bwd_dx_launch(a, st));
-        }
+        HMP_TRY(agg_bwd_dx_launch(a, st));
       } else {
         a.gb16 = g16[l + 1] ? 1 : 0;
         // dZ as bf16 too (it is only read back as the A operand of the two backward GEMMs): needs the bf16-reading kernel
@@ -1550,15 +1367,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         if (n->env.rootcopy) rootless = false;
         if (rootless)
           for (int i = 0; i < a.n; ++i) a.s[i].groot = nullptr;
-        if (n->chain_try && n->fuse_now && l == 0 && !a.gb16) {
-          hmp_net::Deferred d;
-          d.kind = 3; d.ba = a;
-          n->deferred.push_back(d);
-          sc.cancel();
-        } else {
-          HMP_TRY(chain_flush(n, st));
-          HMP_TRY(agg_bwd_launch(a, st));
-        }
+        HMP_TRY(agg_bwd_launch(a, st));
       }
     }
     // dZ[l] is complete.  Weight-gradient GEMMs: either ALL layers in one grouped split-K launch after the loop
@@ -1598,7 +1407,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         pp.push_back(p);
       }
       if (!pp.empty()) {
-        HMP_TRY(chain_flush(n, st));
         Scope sp(n, KC_GEMM_BWD, st);
         HMP_TRY(gemm_many(pp, false, st, nullptr, n->compute_bf16 != 0));
       }
@@ -1612,7 +1420,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       return true;
     };
     if (need_dx) {  // input gradient, masked by the previous layer's activation/dropout derivative
-      HMP_TRY(chain_flush(n, st));
       Scope sc(n, KC_GEMM_BWD, st);
       std::vector<GemmProblem> ps;
       std::vector<int> ps_type;
@@ -1787,7 +1594,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         }
       }
       if (n->dw_branch) {
-        HMP_TRY(chain_flush(n, st));
         Scope sc(n, KC_GEMM_BWD, wst);
         std::vector<int> ks;
         HMP_TRY(gemm_many(ps, true, wst, &ks, n->compute_bf16 != 0));
@@ -1795,7 +1601,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       }
     }
   }
-  HMP_TRY(chain_run(n, st));  // the deferred aggregation launches: as one graph-local launch, or in order
   if (n->dw_branch) {
     if (n->use_branches) HMP_TRY(fork_to(n, n->side[1], st));  // join the weight-gradient branch
   } else {
@@ -1881,12 +1686,6 @@ extern "C" int hmp_net_create(const hmp_net_spec* spec, hmp_net** out) {
     n->dw_mode = db ? (db[0] == '1' ? 1 : 0) : -1;  // -1: decide per batch (see backward_impl)
     const char* fz = getenv("HMP_FUSE");
     n->fuse_mode = fz ? (fz[0] == '1' ? 1 : 0) : -1;
-#ifdef HMP_EXPERIMENTS
-    const char* cz = getenv("HMP_CHAIN");  // graph-local chain launch: measured 5x slower (profiles/r02_c_graph_local_chain.md)
-    n->chain_mode = cz ? (cz[0] == '1' ? 1 : 0) : -1;
-#else
-    n->chain_mode = 0;
-#endif
   }
   if (r != HMP_OK) {
     hmp_net_destroy(n);
@@ -1903,10 +1702,6 @@ extern "C" void hmp_net_destroy(hmp_net* n) {
   for (int i = 0; i < 2; ++i)
     if (n->side[i]) (void)hipStreamDestroy(n->side[i]);
   if (n->d_state) (void)hipFree(n->d_state);
-  if (n->chain_h) (void)hipHostFree(n->chain_h);
-  if (n->chain_stage) (void)hipHostFree(n->chain_stage);
-  if (n->d_chain) (void)hipFree(n->d_chain);
-  if (n->chain_copied) (void)hipEventDestroy(n->chain_copied);
   if (n->d_pack_segs) (void)hipFree(n->d_pack_segs);
   if (n->d_pack_map) (void)hipFree(n->d_pack_map);
   if (n->d_grad_segs) (void)hipFree(n->d_grad_segs);
@@ -1944,7 +1739,6 @@ extern "C" int hmp_net_bind_workspace(hmp_net* n, void* d_workspace, size_t byte
   n->bound = true;
   n->have_fwd = false;
   n->plan_ok = false;
-  n->ell_ok = false;
   return HMP_OK;
 }
 
@@ -1954,8 +1748,6 @@ extern "C" int hmp_net_forward(hmp_net* n, const hmp_batch* batch, const float* 
   read_env(n);
   g_bf16_all = n->env.bf16_all;
   n->training = training; n->seed = seed; n->rng_step = rng_step; n->step_dev = false;
-  n->chain_try = false;
-  n->deferred.clear();
   HMP_TRY(forward_impl(n, batch, d_params, (hipStream_t)stream));
   *d_out = out_ptr(n);
   *ld_out = n->out_ld;
@@ -2019,19 +1811,10 @@ extern "C" int hmp_net_step_fwd_bwd(hmp_net* n, const hmp_batch* batch, const fl
   n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
   n->d_step = args->d_step ? args->d_step : &n->d_state->step;
   n->ce_labels = batch->d_labels; n->ce_ignored = args->ignored_label; n->ce_done = false;
-  // graph-local chain: a batch that says where its graphs begin (Batch.ptr), SAGE stacks, no pooled readout.
-  n->deferred.clear();
-  // MEASURED SLOWER than the multi-launch sequence (profiles/r02_c_graph_local_chain.md: 0.239 ms against 0.048 ms for the five launches
-  // it replaces on config 2): a graph's 7 tiles take 4 rounds of 2 per phase and a round is one full dependent-load chain, whereas the
-  // multi-launch sequence runs every tile of every graph at once.  Opt-in only (HMP_CHAIN=1), kept for its test and as the record.
-  n->chain_try = n->chain_mode == 1 && !n->any_gat && n->spec.pool_edge_type < 0 && n->L <= CHAIN_MAX_LAYERS && batch->n_graphs > 0 &&
-                 batch->max_graph_nodes > 0 && batch->max_graph_nodes <= 4096 && !n->use_branches;
   const int rf = forward_impl(n, batch, d_params, st);
   n->ce_labels = nullptr;
-  if (rf != HMP_OK) { n->chain_try = false; n->deferred.clear(); }
   HMP_TRY(rf);
   if (!n->ce_done) {
-    HMP_TRY(chain_flush(n, st));
     Scope sc(n, KC_LOSS, st);
     HMP_TRY(masked_ce_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, args->ignored_label, n->d_gout,
                                   n->out_ld, n->d_row_lv, n->d_state, st));
@@ -2039,7 +1822,6 @@ extern "C" int hmp_net_step_fwd_bwd(hmp_net* n, const hmp_batch* batch, const fl
   // {loss_sum, count} -> d_grads[na], d_grads[na + 1]: by the first transposed aggregation, else by the gradient un-pack
   n->fin_loss = true;
   const int rb = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
-  if (rb != HMP_OK) { n->chain_try = false; n->deferred.clear(); }
   n->d_step = &n->d_state->step;  // the optimiser's counter belongs to the caller: not kept beyond this call
   n->step_dev = false;
   return rb;

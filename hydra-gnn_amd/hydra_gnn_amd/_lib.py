@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("HMP_LIB") or os.path.join(HERE, "libhydra_mp.so")
 
 MAX_NODE_TYPES, MAX_EDGE_TYPES, MAX_LAYERS, MAX_CONVS = 8, 16, 8, 16
 N_KCLASS = 14
+# slot 13 ("chain", the removed graph-local launch) is retired and always 0
 KCLASS_NAMES = ["plan", "pack", "gemm_fwd", "aggregate_fwd", "loss", "aggregate_bwd", "gemm_bwd", "grad_reduce",
                 "adam", "gat_fwd", "gat_bwd", "pool", "front", "chain"]
 CONV_SAGE, CONV_GAT = 0, 1

@@ -205,7 +205,7 @@ class BatchStream:
         self._dst = (C.c_void_p * n_items)(*[b.data_ptr() for b in self._bufs])
         self._caps = (C.c_int64 * n_items)(*[self.cap[it.slot] for it in items])
         self._totals = (C.c_int64 * len(slots))()
-        # Batch.ptr of every slot, written by the collation kernel (the executor's graph-local launch reads the node types' rows)
+        # Batch.ptr of every slot, written by the collation kernel (the sliced plan build reads the node types' rows)
         self._off_stride = self.B + 1
         self._offsets = torch.zeros(len(slots) * self._off_stride, dtype=torch.int64, device=dev)
         self._slots, self._slot_of = slots, slot_of

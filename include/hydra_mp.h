@@ -255,11 +255,11 @@ typedef struct hmp_batch {
                               * consecutive frames of the inference server, bin/room_classification_server:273-299): the CSR /
                               * CSC plan in the workspace is reused instead of rebuilt.  Counts must match the previous call. */
   /* optional: the batch as a disjoint union of graphs ([PyG] Batch.ptr per node type; base_training_job.py:164-168 collates
-   * that way).  With it the small-batch training step runs everything between the first aggregation and the weight gradients
-   * as ONE launch, one workgroup per graph.  n_graphs = 0: unknown (any edge structure is accepted, multi-launch sequence). */
+   * that way); read with d_edge_ptr below.  n_graphs = 0: unknown (any edge structure is accepted). */
   const int64_t* d_node_ptr[HMP_MAX_NODE_TYPES]; /* [n_graphs + 1] int64 row offsets of the node type, or NULL */
   int32_t n_graphs;
-  int32_t max_graph_nodes;   /* largest per-graph node count over all types (host knowledge of the collation), 0 = unknown */
+  int32_t max_graph_nodes;   /* largest per-graph node count over all types, 0 = unknown: accepted and not read (its reader,
+                              * the graph-local launch, was removed) */
   /* optional, with d_node_ptr of both endpoint types: [n_graphs + 1] int64 edge offsets of the edge type -- the caller vouches
    * that the edges of graph g are entries [ptr[g], ptr[g+1]) of the edge list and join nodes of graph g only (what every
    * collation of a list of graphs produces: [PyG] Batch.from_data_list, base_training_job.py:164-168).  The single-launch plan
@@ -349,8 +349,8 @@ void hmp_timer_destroy(hmp_timer* t);
 /* per-kernel-class device time accumulated by the executor when profiling is on (HIP events around
  * every launch of that class on the executor's stream).  classes: 0 plan, 1 pack, 2 gemm_fwd,
  * 3 aggregate_fwd, 4 loss, 5 aggregate_bwd, 6 gemm_bwd, 7 grad_reduce, 8 adam, 9 gat_fwd, 10 gat_bwd, 11 pool,
- * 12 front (layer-0 projection + plan + pack in one launch, small batches), 13 chain (graph-local launch: every aggregation
- * phase of the step, one workgroup per graph) */
+ * 12 front (layer-0 projection + plan + pack in one launch, small batches), 13 chain (retired with the graph-local launch,
+ * measured slower and removed -- profiles/r02_c_graph_local_chain.md: always 0, kept so that the class count stays 14) */
 #define HMP_N_KCLASS 14
 int hmp_net_profile(hmp_net* net, int32_t enable);
 int hmp_net_profile_read(hmp_net* net, float* ms_sum /*[HMP_N_KCLASS]*/, int32_t* launches /*[HMP_N_KCLASS]*/);
