@@ -414,7 +414,7 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
 // with mask = label != ignored; writes the gradient of the SUM loss and the row's {loss, valid} pair.  The group
 // reductions are xor butterflies below GS, i.e. inside the (GS-aligned) row group.
 template <int GS>
-__device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, int row, int c0, Acc<4>& t, int64_t y) {
+__device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, int row, int c0, Acc<4>& t, int64_t y, bool in_mask) {
   const int nc = D.ce_classes;
   float v[4];
   bool in[4];
@@ -433,7 +433,7 @@ __device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, in
 #pragma unroll
   for (int o = GS / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float lse = m + logf(s);
-  const bool valid = (y != D.ce_ignored);
+  const bool valid = in_mask && (y != D.ce_ignored);
   const bool bad = valid && (y < 0 || y >= nc);
   const bool use = valid && !bad;
   float ly = 0.f;
@@ -443,6 +443,10 @@ __device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, in
     const bool hit = use && (int64_t)(c0 + i) == y;
     if (hit) ly = v[i];
     if (use && in[i]) (&g.x)[i] = expf(v[i] - lse) - (hit ? 1.f : 0.f);
+  }
+  if (D.ce_tail) {  // y = dropout(act(z)) is what the CE read: chain back to z (act' from y, as the hidden layers' backward does)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) (&g.x)[i] *= tail_dydz(t.at(i), D.act, D.drop_on != 0, D.drop.scale);
   }
 #pragma unroll
   for (int o = GS / 2; o > 0; o >>= 1) ly += __shfl_xor(ly, o);
@@ -476,10 +480,14 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a) {
   const int c0 = (threadIdx.x % GS) * 4;
   // the label is requested before the aggregation (it depends on nothing): one round trip less behind the last gather
   int64_t y = 0;
-  if (NV == 1 && D.ce_labels) y = D.ce_labels[row];
+  bool in_mask = true;
+  if (NV == 1 && D.ce_labels) {
+    y = D.ce_labels[row];
+    if (D.ce_mask) in_mask = D.ce_mask[row] != 0;
+  }
   agg_row<GS, NV, ZB, HB>(D, a.mean, row, c0, tot);
   if constexpr (NV == 1) {
-    if (D.ce_labels) ce_rowgroup<GS>(D, a.state, row, c0, tot[0], y);
+    if (D.ce_labels) ce_rowgroup<GS>(D, a.state, row, c0, tot[0], y, in_mask);
   }
 }
 

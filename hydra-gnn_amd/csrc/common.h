@@ -232,4 +232,14 @@ __host__ __device__ inline void drop_keep4(const DropCfg& cfg, uint32_t q, bool 
   keep[3] = (b >> 16) >= t16;
 }
 
+// d y / d z of y = dropout(act(z)) read off the stored y (scale = 1/(1-p), ignored without dropout): a dropped element (-0.0 under
+// dropout) -> 0;  none: scale;  relu: y > 0 ? scale : 0;  elu: y > 0 ? scale : y + scale  [y = scale * elu(z), elu' = elu + 1 for z <= 0]
+__device__ __forceinline__ float tail_dydz(float y, int act, bool drop_on, float scale) {
+  const float s = drop_on ? scale : 1.f;
+  if (drop_on && y == 0.f && signbit(y)) return 0.f;
+  if (act == HMP_ACT_RELU) return y > 0.f ? s : 0.f;
+  if (act == HMP_ACT_ELU) return y > 0.f ? s : y + s;
+  return s;
+}
+
 }  // namespace hmp

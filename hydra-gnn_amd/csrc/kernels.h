@@ -211,6 +211,10 @@ struct AggDst {
   int ce_classes, ce_ldg;
   float* ce_grad;
   float* ce_row_lv;
+  // two-headed step (hmp_net_step2_*): rows whose mask byte is 0 do not count (null: every row), and with ce_tail set the entry's
+  // act / dropout are the model's tail, so the gradient written is d loss / d (pre-activation): . keep/(1-p) . act', read off y
+  const uint8_t* ce_mask;
+  int ce_tail;
   int win_in, win_src_rows;  // filled by agg_fwd_launch: in-conv served from the LDS window (-1: none), rows of its source
   int tile_rows;             // agg_proj_fwd_launch: rows per workgroup, 16 or 8.  A launch is as long as its slowest tile and a tile of
                              // high-degree rows (rooms: ~12 objects each) requests twice the lines of the others (tools/ktime_blocks.py:
@@ -453,6 +457,32 @@ int masked_ce_launch(const float* logits, int ldl, int n_rows, int n_classes, co
                      float* grad, int ldg, float* out2, NetState* state_or_null, hipStream_t st);
 int masked_ce_rows_launch(const float* logits, int ldl, int n_rows, int n_classes, const int64_t* labels, int64_t ignored,
                           float* grad, int ldg, float* row_lv, NetState* state, hipStream_t st);
+// Tail of the two-headed task (semisup.hip): y = dropout(act(z)) on a final state, then the masked CE on y with the gradient written
+// as d loss / d z (fused step), or the first-maximum argmax of act(z) compared with the labels (accuracy count).  One launch covers
+// the rows of both heads.
+struct HeadTail {
+  const float* z;           // final state [n_rows][ldz] (output of the last conv, no activation)
+  int ldz, n_rows, classes;
+  const int64_t* labels;
+  const uint8_t* mask;      // null: every row
+  float* grad;              // d loss / d z [n_rows][ldg] (CE only; columns >= classes are written 0)
+  int ldg;
+  float* row_lv;            // per row {loss, valid} (CE only)
+  int slot;                 // 0 readout, 1 aux: counts[2 * slot], counts[2 * slot + 1] (accuracy count)
+  int drop_on;
+  DropCfg drop;             // quad numbering row * ceil(classes / 4) + col / 4
+  int block_start;
+};
+struct TailArgs {
+  int n;
+  int act;
+  int64_t ignored;
+  NetState* state;
+  HeadTail h[2];
+};
+int tail_ce_launch(TailArgs& a, hipStream_t st);
+int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st);
+
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                 int step_host, const int* step_dev, const float* d_count, hipStream_t st);

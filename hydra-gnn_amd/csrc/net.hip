@@ -166,6 +166,12 @@ struct hmp_net {
   bool ce_done = false;
   AdamFuse adam_fuse = {};
   bool adam_done = false;
+  // two-headed step (hmp_net_step2_*): its targets, the heads whose tail + CE rode in the last aggregation's epilogue, G[L][aux]
+  // already written by the tail (backward_impl does not stage it), rows of d_row_lv the loss finalisation sums (0: b->n_out)
+  const hmp_head_targets* tgt = nullptr;
+  bool tail_done[2] = {false, false};
+  bool aux_g_ready = false;
+  int fin_rows = 0;
   hipStream_t side[2] = {nullptr, nullptr};
   hipEvent_t evs[32];
   int n_evs = 0, ev_i = 0;
@@ -622,7 +628,8 @@ size_t carve(hmp_net* n, char* base, const int32_t* cn, const int64_t* ce) {
   n->cap_out = cap_out;
   n->d_out = (float*)take((size_t)cap_out * n->out_ld * 4);
   n->d_gout = (float*)take((size_t)cap_out * n->out_ld * 4);
-  n->d_row_lv = (float*)take((size_t)cap_out * 2 * 4);
+  const int cap_aux = S.aux_readout_type >= 0 ? cn[S.aux_readout_type] : 0;  // the aux rows follow the readout rows
+  n->d_row_lv = (float*)take((size_t)(cap_out + cap_aux) * 2 * 4);
   n->d_iota = nullptr; n->d_ones = nullptr; n->d_sadd = nullptr;
   if (n->any_agg_first) {
     int mx = 1;
@@ -1110,6 +1117,9 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       memset(&a, 0, sizeof(a));
       a.mean = 1;
       a.state = n->d_state;
+      // two-headed step: both heads' tail (act, dropout) and masked CE in this epilogue when it can hold both rows' widths
+      const bool tail_epi = l == n->L - 1 && n->tgt && n->fuse_now && fpad(Ls.out_dim[S.readout_type]) <= 256 &&
+                            fpad(Ls.out_dim[S.aux_readout_type]) <= 256;
       for (int t = 0; t < n->T; ++t) {
         if (Y.roff[t] < 0 || b->n_nodes[t] == 0) continue;
         AggDst& D = a.d[a.n++];
@@ -1127,6 +1137,20 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
         D.act = Ls.act;
         D.drop_on = (n->training && Ls.dropout > 0.f) ? 1 : 0;
         if (D.drop_on) D.drop = make_drop(n, Ls.dropout, (uint32_t)(l * HMP_MAX_NODE_TYPES + t));
+        const int head = t == S.readout_type ? 0 : (t == S.aux_readout_type ? 1 : -1);
+        if (tail_epi && head >= 0) {
+          // the layer runs with the model's tail: its pitch numbering of the keep-mask, row * (ldo / 4) + col / 4, is the tail's
+          // row * ceil(out_dim / 4) + col / 4 (ldo = fpad(out_dim)), on the tail's tensor id 8 * (L - 1) + t
+          D.act = S.tail_act;
+          D.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+          if (D.drop_on) D.drop = make_drop(n, S.tail_dropout, (uint32_t)(l * HMP_MAX_NODE_TYPES + t));
+          D.ce_labels = n->tgt->d_labels[head]; D.ce_mask = n->tgt->d_mask[head]; D.ce_tail = 1;
+          D.ce_ignored = n->ce_ignored; D.ce_classes = Ls.out_dim[t];
+          D.ce_grad = head == 0 ? n->d_gout : n->G[n->L][t];
+          D.ce_ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
+          D.ce_row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
+          n->tail_done[head] = true;
+        }
         for (int i = 0; i < Y.n_live; ++i) {
           const int c = Y.live[i];
           const hmp_conv_spec& C = Ls.convs[c];
@@ -1226,7 +1250,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     // second readout: stage its gradient in G[L][aux] (zero where the caller passed none, and in the padding columns)
     const int rows = n->batch.n_nodes[at], ld = n->ld[n->L][at], w = n->dim[n->L][at];
     HMP_CHECK_ARG(!d_gaux || ld_gaux >= w, "net: second output gradient narrower than the output (%d < %d)", ld_gaux, w);
-    if (rows > 0) {
+    if (rows > 0 && !n->aux_g_ready) {
       HMP_HIP(hipMemsetAsync(n->G[n->L][at], 0, (size_t)rows * ld * 4, st));
       if (d_gaux)
         HMP_HIP(hipMemcpy2DAsync(n->G[n->L][at], (size_t)ld * 4, d_gaux, (size_t)ld_gaux * 4, (size_t)w * 4, rows, hipMemcpyDeviceToDevice, st));
@@ -1285,7 +1309,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       memset(&a, 0, sizeof(a));
       a.mean = 1;
       if (n->fin_loss) {  // first backward kernel of the step: one extra block finalises {loss_sum, count}
-        a.fin_row_lv = n->d_row_lv; a.fin_rows = b->n_out; a.fin_out2 = d_grads + n->spec.n_active_params; a.fin_state = n->d_state;
+        a.fin_row_lv = n->d_row_lv; a.fin_rows = n->fin_rows > 0 ? n->fin_rows : b->n_out; a.fin_out2 = d_grads + n->spec.n_active_params; a.fin_state = n->d_state;
         n->fin_loss = false;
         fin_early = true;
       }
@@ -1642,7 +1666,8 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     af.on = (af.on && fin_early && !n->any_gat) ? 1 : 0;
     n->adam_done = af.on != 0;
     HMP_TRY(grad_reduce_launch(n->d_grad_segs, n->grad_sb, n->dyn, n->d_slabs, d_params, d_grads,
-                               n->fin_loss ? n->d_row_lv : nullptr, b->n_out, d_grads + na, n->d_state, af, st));
+                               n->fin_loss ? n->d_row_lv : nullptr, n->fin_rows > 0 ? n->fin_rows : b->n_out, d_grads + na, n->d_state,
+                               af, st));
     n->fin_loss = false;
   }
   return HMP_OK;
@@ -1843,6 +1868,116 @@ extern "C" int hmp_net_step_fused(hmp_net* n, const hmp_batch* batch, float* d_p
   HMP_TRY(r);
   if (n->adam_done) return HMP_OK;
   return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
+}
+
+namespace {
+
+// the rows of one head for the stand-alone tail kernel (semisup.hip)
+void add_tail(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
+  const hmp_net_spec& S = n->spec;
+  const int t = head == 0 ? S.readout_type : S.aux_readout_type;
+  if (b->n_nodes[t] == 0) return;
+  HeadTail& T = ta.h[ta.n++];
+  memset(&T, 0, sizeof(T));
+  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
+  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
+  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
+  T.slot = head;
+  if (!ce) return;
+  T.grad = head == 0 ? n->d_gout : n->G[n->L][t];
+  T.ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
+  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
+  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
+}
+
+int check_targets(const hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, const char* who) {
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(S.aux_readout_type >= 0, "%s: the net has one output (aux_readout_type < 0): use the single-head entry", who);
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
+                "%s: spec tail_act %d / tail_dropout %g", who, S.tail_act, (double)S.tail_dropout);
+  const int ts[2] = {S.readout_type, S.aux_readout_type};
+  for (int h = 0; h < 2; ++h)
+    HMP_CHECK_ARG(b->n_nodes[ts[h]] == 0 || tg->d_labels[h] != nullptr, "%s: labels of head %d required", who, h);
+  return HMP_OK;
+}
+
+}  // namespace
+
+extern "C" int hmp_net_step2_fwd_bwd(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                                     float* d_grads, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && args, "hmp_net_step2_fwd_bwd: null argument");
+  HMP_TRY(check_targets(n, batch, targets, "hmp_net_step2_fwd_bwd"));
+  hipStream_t st = (hipStream_t)stream;
+  read_env(n);
+  g_bf16_all = n->env.bf16_all;
+  n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
+  n->d_step = args->d_step ? args->d_step : &n->d_state->step;
+  n->ce_ignored = args->ignored_label;
+  n->tgt = targets;
+  n->tail_done[0] = n->tail_done[1] = false;
+  const int rf = forward_impl(n, batch, d_params, st);
+  n->tgt = nullptr;
+  int r = rf;
+  if (r == HMP_OK) {  // the heads the last epilogue did not serve: one stand-alone launch over their rows
+    TailArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.act = n->spec.tail_act; ta.ignored = args->ignored_label; ta.state = n->d_state;
+    for (int h = 0; h < 2; ++h)
+      if (!n->tail_done[h]) add_tail(n, batch, targets, h, true, ta);
+    if (ta.n > 0) {
+      Scope sc(n, KC_LOSS, st);
+      r = tail_ce_launch(ta, st);
+    }
+  }
+  if (r == HMP_OK) {
+    // {loss_sum, count} over the readout rows then the aux rows -> d_grads[na], d_grads[na + 1] (one count for both heads)
+    n->fin_loss = true;
+    n->fin_rows = batch->n_out + batch->n_nodes[n->spec.aux_readout_type];
+    n->aux_g_ready = true;
+    r = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
+    n->aux_g_ready = false;
+    n->fin_rows = 0;
+    n->fin_loss = false;
+  }
+  n->d_step = &n->d_state->step;
+  n->step_dev = false;
+  return r;
+}
+
+extern "C" int hmp_net_step2_fused(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, float* d_params,
+                                   float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && d_m && d_v && args, "hmp_net_step2_fused: null argument");
+  AdamFuse& af = n->adam_fuse;
+  af.on = n->fuse_mode == 0 ? 0 : 1;
+  af.p = d_params; af.m = d_m; af.v = d_v;
+  af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
+  af.step_dev = args->d_step ? args->d_step : &n->d_state->step;
+  af.count = d_grads + n->spec.n_active_params + 1;
+  n->adam_done = false;
+  const int r = hmp_net_step2_fwd_bwd(n, batch, targets, d_params, d_grads, args, stream);
+  af.on = 0;
+  HMP_TRY(r);
+  if (n->adam_done) return HMP_OK;
+  return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
+}
+
+extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                                      int64_t* d_counts, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct2: null argument");
+  HMP_TRY(check_targets(n, batch, targets, "hmp_net_count_correct2"));
+  hipStream_t st = (hipStream_t)stream;
+  read_env(n);
+  g_bf16_all = n->env.bf16_all;
+  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
+  HMP_TRY(forward_impl(n, batch, d_params, st));
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = n->spec.tail_act; ta.state = n->d_state;
+  for (int h = 0; h < 2; ++h) add_tail(n, batch, targets, h, false, ta);
+  if (ta.n == 0) return HMP_OK;
+  Scope sc(n, KC_LOSS, st);
+  return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
 }
 
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,

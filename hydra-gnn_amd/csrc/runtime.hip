@@ -33,6 +33,7 @@ size_t hmp_sizeof(int which) {
     case 4: return sizeof(hmp_net_spec);
     case 5: return sizeof(hmp_batch);
     case 6: return sizeof(hmp_train_args);
+    case 7: return sizeof(hmp_head_targets);
     default: return 0;
   }
 }

@@ -66,6 +66,7 @@ class NetSpec(C.Structure):
         ("readout_type", C.c_int32), ("pool_edge_type", C.c_int32), ("aux_readout_type", C.c_int32),
         ("n_params", C.c_int64), ("n_active_params", C.c_int64),
         ("layers", LayerSpec * MAX_LAYERS),
+        ("tail_act", C.c_int32), ("tail_dropout", C.c_float),
     ]
 
 
@@ -94,12 +95,16 @@ class TrainArgs(C.Structure):
     ]
 
 
+class HeadTargets(C.Structure):
+    _fields_ = [("d_labels", C.c_void_p * 2), ("d_mask", C.c_void_p * 2)]
+
+
 class CollateItem(C.Structure):
     _fields_ = [("d_src", C.c_void_p), ("d_ptr", C.c_void_p), ("src_total", C.c_int64), ("row_bytes", C.c_int64),
                 ("slot", C.c_int32), ("slot_src", C.c_int32), ("slot_dst", C.c_int32)]
 
 
-_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs]
+_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -138,6 +143,9 @@ SIGNATURES = {
     "hmp_net_step_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_step_adam": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_step_fused": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _VP, _VP, C.POINTER(TrainArgs), _VP]),
+    "hmp_net_step2_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, C.POINTER(TrainArgs), _VP]),
+    "hmp_net_step2_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP, _VP, C.POINTER(TrainArgs), _VP]),
+    "hmp_net_count_correct2": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP]),
     "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),
@@ -178,7 +186,7 @@ SIGNATURES = {
     "hmp_comm_broadcast_f32": (C.c_int, [_VP, _VP, _I64, _I32, _VP]),
 }
 
-ABI_VERSION = 3  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
+ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
 
 _lib: Optional[C.CDLL] = None
 

@@ -69,7 +69,7 @@ class _BatchHolder:
 class NativeNet:
     def __init__(self, node_types: Sequence[str], in_dims: Dict[str, int], edge_types: Sequence[EdgeType],
                  layers: List[LayerDesc], readout: str, pool_edge_type: Optional[EdgeType] = None,
-                 count_types: Sequence[str] = (), aux_readout: Optional[str] = None):
+                 count_types: Sequence[str] = (), aux_readout: Optional[str] = None, tail: Optional[Tuple[int, float]] = None):
         self.node_types = list(node_types)
         self.edge_types = [tuple(e) for e in edge_types]
         self.in_dims = dict(in_dims)
@@ -78,6 +78,9 @@ class NativeNet:
         # second output node type of the two-headed task (heterogeneous_network.py:123-135): forward returns (readout, aux)
         self.aux_readout = aux_readout
         assert aux_readout is None or (aux_readout != readout and pool_edge_type is None)
+        # (activation, dropout) the two-headed model applies to both final states after the program (heterogeneous_network.py:
+        # 124-134); only the fused two-head step (TwoHeadTrainStep) and count_correct run it natively
+        self.tail = (int(tail[0]), float(tail[1])) if tail is not None else (ACT_NONE, 0.0)
         self.pool_edge_type = tuple(pool_edge_type) if pool_edge_type is not None else None
         # node types without features whose node COUNT matters (virtual pool targets)
         self.count_types = list(count_types)
@@ -184,6 +187,7 @@ class NativeNet:
         sp.pool_edge_type = et[self.pool_edge_type] if self.pool_edge_type is not None else -1
         sp.aux_readout_type = nt[self.aux_readout] if self.aux_readout is not None else -1
         sp.n_params, sp.n_active_params = self.n_params, self.n_active
+        sp.tail_act, sp.tail_dropout = self.tail
         for l, layer in enumerate(self.layers):
             ls = sp.layers[l]
             ls.n_convs, ls.act, ls.dropout, ls.group_mean = len(layer.convs), layer.act, float(layer.dropout), int(layer.group_mean)
@@ -456,6 +460,23 @@ class NativeNet:
             self._pred_done.synchronize()
         return self._pred_host[:n]
 
+    def count_correct(self, data, labels, masks, counts: torch.Tensor) -> torch.Tensor:
+        """Two-headed nets: ADD this batch's {correct, total} of both heads to the device int64[4] ``counts`` (``hmp_net_count_correct2``:
+        eval-mode forward, argmax of act(final state), comparison under the masks).  Nothing synchronises."""
+        flat = self.flat_params(full_check=False)
+        h = self.make_batch(data)
+        dev = flat.device
+        if counts.dtype != torch.int64 or counts.numel() < 4 or not counts.is_contiguous() or counts.device != dev:
+            raise _lib.HydraMPError("counts must be a contiguous int64[4] tensor on the model's device")
+        tg = _head_targets(self, h, labels, masks)
+        with torch.cuda.device(dev):
+            self._ensure_workspace(h, dev)
+            _lib.check(self._lib.hmp_net_count_correct2(self._handle, C.byref(h.c), C.byref(tg), flat.data_ptr(), counts.data_ptr(),
+                                                        _lib.stream_ptr()))
+            self._fwd_token += 1
+            self._plan_key = self._plan_tensors = None
+        return counts
+
     def _forward_raw(self, h: _BatchHolder, training: bool, seed: int, rng_step: int) -> torch.Tensor:
         out_p, ld = C.c_void_p(), C.c_int32()
         _lib.check(self._lib.hmp_net_forward(self._handle, C.byref(h.c), self._flat.data_ptr(), int(training), seed, rng_step,
@@ -509,6 +530,40 @@ class NativeNet:
         step, status = C.c_int32(), C.c_int32()
         _lib.check(self._lib.hmp_net_read_state(self._handle, C.byref(step), C.byref(status), _lib.stream_ptr()))
         return step.value, status.value
+
+
+def _head_targets(net: NativeNet, h: _BatchHolder, labels, masks) -> _lib.HeadTargets:
+    """hmp_head_targets for (readout labels, aux labels) and optional (readout mask, aux mask); the tensors it points at are
+    appended to ``h.keep`` (kept alive with the descriptor, and part of a captured graph's key)."""
+    if net.aux_readout is None:
+        raise _lib.HydraMPError("the two-head entries need a two-headed net (aux_readout)")
+    if len(labels) != 2 or (masks is not None and len(masks) != 2):
+        raise _lib.HydraMPError("labels / masks: one tensor per head, (readout, aux)")
+    tg = _lib.HeadTargets()
+    for i, t in enumerate((net.readout, net.aux_readout)):
+        n = h.n_nodes[net.node_types.index(t)]
+        lab = labels[i]
+        _require_cuda(lab, f"labels[{i}]")
+        lab = lab.to(torch.int64).contiguous()
+        if lab is not labels[i]:
+            h.converted = True
+        if lab.numel() != n:
+            raise _lib.HydraMPError(f"labels[{i}]: {lab.numel()} labels for {n} '{t}' rows")
+        h.keep.append(lab)
+        tg.d_labels[i] = lab.data_ptr() if n > 0 else None
+        m = None if masks is None else masks[i]
+        if m is not None:
+            _require_cuda(m, f"masks[{i}]")
+            if m.dtype != torch.bool:
+                raise _lib.HydraMPError(f"masks[{i}] must be a bool tensor")
+            m = m.contiguous()
+            if m is not masks[i]:
+                h.converted = True
+            if m.numel() != n:
+                raise _lib.HydraMPError(f"masks[{i}]: {m.numel()} entries for {n} '{t}' rows")
+            h.keep.append(m)
+            tg.d_mask[i] = m.data_ptr() if n > 0 else None
+    return tg
 
 
 class _NetFunction(torch.autograd.Function):
@@ -751,3 +806,78 @@ class TrainStep:
         t = self.grads[self.net.n_active: self.net.n_active + 2].tolist()
         self.net.check_status()
         return t[0] / max(t[1], 1.0)
+
+
+class TwoHeadTrainStep(TrainStep):
+    """The loop body of ``SemiSupervisedTrainingJob.train`` (semisupervised_training_job.py:117-147) as native code: phase A =
+    plan + forward + the model's tail (act, dropout) + masked CE of BOTH heads + backward (``hmp_net_step2_fwd_bwd``), [all-reduce],
+    phase B = Adam -- the :class:`TrainStep` contract with ``hmp_head_targets`` in place of the batch's labels.
+
+    ``step(data, labels=(y_readout, y_aux), masks=(m_readout, m_aux) | None)``; :meth:`loss` is the summed CE of both heads
+    divided by the total count, the reference's ``loss.item()``.  The dropout masks are the autograd path's (same seed, draw number
+    = the step counter), so a step equals ``net(batch)`` -> ``net.loss`` -> ``backward`` -> ``torch.optim.Adam``."""
+
+    def __init__(self, net: NativeNet, lr: float, weight_decay: float = 0.0, ignored_label: int = -100, **kw):
+        if net.aux_readout is None:
+            raise _lib.HydraMPError("TwoHeadTrainStep needs a two-headed net (aux_readout); use TrainStep")
+        super().__init__(net, lr, weight_decay=weight_decay, ignored_label=ignored_label, **kw)
+        self._targets = None
+
+    def _phase_a(self, h, st):
+        net = self.net
+        _lib.check(net._lib.hmp_net_step2_fwd_bwd(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
+                                                  self.grads.data_ptr(), C.byref(self.args), st))
+
+    def _phase_ab(self, h, st):
+        net = self.net
+        _lib.check(net._lib.hmp_net_step2_fused(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
+                                                self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), C.byref(self.args), st))
+
+    def __call__(self, data, labels, masks=None) -> None:
+        net = self.net
+        if net.flat_params(full_check=False) is not self.flat:
+            raise _lib.HydraMPError("model parameters were moved after TwoHeadTrainStep was created")
+        stamp = getattr(data, "_mutation_stamp", None)
+        tensors = tuple(labels) + (tuple(masks) if masks is not None else ())
+        key = None
+        if stamp is not None:
+            key = (id(data), stamp(), masks is None) + tuple((id(t), t._version) if t is not None else None for t in tensors)
+        if key is not None and key == self._batch_key:
+            h = self._holder
+        else:
+            h = net.make_batch(self.view(data) if self.view is not None else data)
+            self._targets = _head_targets(net, h, labels, masks)
+            self._batch_key = key if not h.converted else None
+            self._data_ref = (data, tensors)  # keeps id() unique while the key is live
+        self._holder = h
+        dev = self.flat.device
+        with torch.cuda.device(dev):
+            net._ensure_workspace(h, dev)
+            net._fwd_token += 1
+            net._plan_key = net._plan_tensors = None
+            if not self.use_graph:
+                st = _lib.stream_ptr()
+                if self._world() == 1 and not self.force_collective:
+                    self._phase_ab(h, st)
+                else:
+                    self._phase_a(h, st)
+                    self._all_reduce()
+                    self._phase_b(st)
+                return
+            # the captured graph holds the descriptor's pointers (labels and masks among them: h.keep)
+            gkey = (tuple(h.n_nodes), tuple(h.n_edges), tuple(t.data_ptr() for t in h.keep), id(net._ws))
+            if self._graphs is None or gkey != self._key:
+                self._capture(h, gkey)
+            ga, gb = self._graphs
+            cur = torch.cuda.current_stream()
+            self._stream.wait_stream(cur)
+            with torch.cuda.stream(self._stream):
+                st = _lib.stream_ptr()
+                _lib.check(net._lib.hmp_graph_launch(ga, st))
+                if gb is not None:
+                    self._all_reduce()
+                    _lib.check(net._lib.hmp_graph_launch(gb, st))
+            cur.wait_stream(self._stream)
+
+    def run(self, holder) -> None:
+        raise _lib.HydraMPError("TwoHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from ..data import EDGE_TYPES
 from ..engine import LayerDesc, NativeNet
+from .. import _lib
 from .._lib import ACT_ELU, ACT_NONE, ACT_RELU
 from .utils import build_GAT_hetero_conv, build_hetero_conv, cross_entropy_loss
 
@@ -59,7 +60,7 @@ class _NativeModule(nn.Module):
 
         if getattr(self, "classification_task", "room") != "room":
             raise NotImplementedError("the fused training step computes ONE masked cross entropy (room labels); the two-headed "
-                                      "task trains through loss.backward() like the reference's SemiSupervisedTrainingJob")
+                                      "task has its own fused step: semisupervised_step()")
         return TrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=getattr(self, "_view", None), **kw)
 
     def predict(self, data):
@@ -140,8 +141,10 @@ class HeterogeneousNetwork(_NativeModule):
 
     def _build_native(self) -> NativeNet:
         node_types = ["objects", "rooms"]
+        two = self.classification_task == "all"
+        tail = ((ACT_ELU if self.conv_block[:3] == "GAT" else ACT_RELU), float(self.dropout)) if two else None
         return NativeNet(node_types, self.input_dim_dict, EDGE_TYPES, _hetero_layers(self, node_types), readout="rooms",
-                         aux_readout="objects" if self.classification_task == "all" else None)
+                         aux_readout="objects" if two else None, tail=tail)
 
     def forward(self, data):
         out = self._run(data)
@@ -152,3 +155,29 @@ class HeterogeneousNetwork(_NativeModule):
         last = self.num_layers - 1
         return (self._tail_act_drop(rooms[:, : dims["rooms"]], self._drop_stream(last, "rooms")),
                 self._tail_act_drop(objects[:, : dims["objects"]], self._drop_stream(last, "objects")))
+
+    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
+        """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body), see
+        engine.TwoHeadTrainStep: ``step(data, labels=(y_rooms, y_objects), masks=(m_rooms, m_objects))``.  The dropout seed is
+        the module's, so the masks are the ones ``forward()`` draws at the same step number."""
+        from ..engine import TwoHeadTrainStep
+
+        if getattr(self, "classification_task", "room") != "all":
+            raise _lib.HydraMPError("semisupervised_step: the model has one output (build it with output_dim_dict for the "
+                                    "two-headed task); use train_step()")
+        kw.setdefault("seed", self._seed)
+        return TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
+
+    def count_correct(self, data, labels, masks=None, counts=None):
+        """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
+        forward, argmax of both heads, compared with ``labels = (y_rooms, y_objects)`` under ``masks``.  With ``counts`` (device
+        int64[4]) the batch's {correct_rooms, total_rooms, correct_objects, total_objects} are ADDED to it on the device and the
+        tensor is returned without a sync (a loader loop reads it once per pass); without, returns the four ints of this batch."""
+        net = self.native()
+        if net.aux_readout is None:
+            raise _lib.HydraMPError("count_correct: the model has one output (build it with output_dim_dict)")
+        acc = counts
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+        net.count_correct(data, labels, masks, acc)
+        return acc if counts is not None else [int(v) for v in acc.tolist()]

@@ -107,6 +107,24 @@ def mp3d_like_batch(batch_size: int, seed: int, relative_pos: bool = False, sem_
     return collate(graphs)
 
 
+def semisupervised_batch(n_graphs: int, seed: int, relative_pos: bool = False) -> HeteroData:
+    """Batch of the two-headed (room + object) task, ``SemiSupervisedTrainingJob`` (semisupervised_training_job.py:117-147):
+    ``mp3d_like_graph`` graphs (room labels 0..25, object labels 0..27; no label is ignored) with a seeded per-node split of
+    BOTH node types into disjoint ``train_mask`` (60 %), ``val_mask`` (20 %) and ``test_mask`` (20 %) bool tensors."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    graphs = [mp3d_like_graph(rng) for _ in range(n_graphs)]
+    if relative_pos:
+        for g in graphs:
+            compute_relative_pos(g)
+    batch = collate(graphs)
+    for t in ("rooms", "objects"):
+        u = torch.from_numpy(rng.random(int(batch[t].y.numel())))
+        batch[t].train_mask = u < 0.6
+        batch[t].val_mask = (u >= 0.6) & (u < 0.8)
+        batch[t].test_mask = u >= 0.8
+    return batch
+
+
 def config2_batch(batch_size: int = 32, rank: int = 0) -> HeteroData:
     return mp3d_like_batch(batch_size, BASE_SEED + 2 + 1000 * rank)
 

@@ -26,8 +26,10 @@ extern "C" {
 
 /* 2: round 2 -- hmp_batch grew (plan_valid, d_node_ptr, n_graphs, max_graph_nodes, d_edge_ptr), hmp_train_args::d_step; sections 10-12
  * 3: round 3 -- hmp_comm_query; hmp_net_read_state reports the counter of the last step from the net's own state;
- *    hmp_conv_spec::agg_first; hmp_gemm_bf16_dx / hmp_gemm_bf16_dw */
-#define HMP_ABI_VERSION 3
+ *    hmp_conv_spec::agg_first; hmp_gemm_bf16_dx / hmp_gemm_bf16_dw
+ * 4: hmp_net_spec::tail_act / tail_dropout, hmp_head_targets (hmp_sizeof 7), hmp_net_step2_fwd_bwd / hmp_net_step2_fused /
+ *    hmp_net_count_correct2: the fused step of the two-headed task */
+#define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
 #define HMP_E_ARG 1      /* bad argument (shape / alignment / capacity) */
@@ -47,7 +49,7 @@ extern "C" {
 int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
- * 5 hmp_batch, 6 hmp_train_args (lets a foreign-language binding verify its struct mirror) */
+ * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets (lets a foreign-language binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -240,6 +242,11 @@ typedef struct hmp_net_spec {
   int64_t n_params;        /* total floats in the flat parameter buffer */
   int64_t n_active_params; /* parameters [0, n_active) receive gradients; the tail is dead weights */
   hmp_layer_spec layers[HMP_MAX_LAYERS];
+  /* two-headed task only: the activation (HMP_ACT_*) and feature dropout the model applies to BOTH final states after the last
+   * layer (heterogeneous_network.py:124-134).  The program itself ends at the last conv (its layer has act NONE, dropout 0);
+   * only the step2 / count_correct2 entries below read these */
+  int32_t tail_act;
+  float tail_dropout;
 } hmp_net_spec;
 
 typedef struct hmp_batch {
@@ -315,6 +322,36 @@ int hmp_net_step_adam(hmp_net* net, float* d_params, const float* d_grads, float
  * gradient un-pack kernel where the network allows it (SAGE stacks); the result equals A followed by B. */
 int hmp_net_step_fused(hmp_net* net, const hmp_batch* batch, float* d_params, float* d_grads, float* d_m, float* d_v,
                        const hmp_train_args* args, void* stream);
+/* Two-headed task (spec.aux_readout_type >= 0): the loop body of SemiSupervisedTrainingJob.train
+ * (semisupervised_training_job.py:117-147) and the per-batch arithmetic of its test() (:198-257).
+ *   Targets: d_labels[0] / d_mask[0] belong to the readout type, [1] to the aux type ([n_nodes[t]] int64 labels, one byte per
+ *   node as mask, mask NULL = every row).  A row counts iff (mask == NULL || mask[row]) && label != ignored_label; an in-mask
+ *   label outside [0, classes) sets status bit 2 (hmp_net_read_state).
+ *   Tail of each type t with final state z (the output of the last conv): y = dropout(act(z)), act = spec.tail_act,
+ *   p = spec.tail_dropout (training only), then the masked CE on y; the step writes dL/dz = (softmax(y) - onehot) . keep/(1-p) .
+ *   act'(z) where the backward reads the gradient of that type.
+ *   Dropout numbering: the keep-mask of type t is tensor 8 * (n_layers - 1) + t of the step's draw number (the device counter
+ *   the step bumps at its head, hmp_train_args::d_step), element (row, col) in quad row * ceil(out_dim / 4) + col / 4 -- i.e.
+ *   exactly hmp_dropout_mask(seed, step, 8 * (n_layers - 1) + t, p, n_rows, out_dim) and hmp_bias_act_drop_fwd on the same
+ *   coordinates.  (The final state is stored at pitch 4 * ceil(out_dim / 4), so the layer epilogues' pitch numbering coincides.)
+ *   Loss: {loss_sum, count} are summed over the readout rows, then the aux rows, in a fixed order: one count over both heads,
+ *   the normalisation of the reference's list-form cross_entropy_loss.  The flat-gradient contract is the single-head step's:
+ *   SUM-loss gradient in d_grads[0 : n_active), {loss_sum, count} in d_grads[n_active], d_grads[n_active + 1]; phase B is
+ *   hmp_net_step_adam.  Both phases are capturable.  Nets without aux_readout_type are refused. */
+typedef struct hmp_head_targets {
+  const int64_t* d_labels[2]; /* [0] readout type, [1] aux type; [n_nodes[t]] int64 */
+  const uint8_t* d_mask[2];   /* bool per node, or NULL = every row */
+} hmp_head_targets;
+
+int hmp_net_step2_fwd_bwd(hmp_net* net, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                          float* d_grads, const hmp_train_args* args, void* stream);
+int hmp_net_step2_fused(hmp_net* net, const hmp_batch* batch, const hmp_head_targets* targets, float* d_params, float* d_grads,
+                        float* d_m, float* d_v, const hmp_train_args* args, void* stream);
+/* eval-mode forward, y = act(z) on both final states (no dropout), first-maximum row argmax, compared with the labels under the
+ * masks (ignored_label plays no part: the reference's test() counts every masked row).  ACCUMULATES into d_counts (device int64[4])
+ * {correct_readout, total_readout, correct_aux, total_aux}; one launch beyond the forward, nothing synchronises. */
+int hmp_net_count_correct2(hmp_net* net, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                           int64_t* d_counts, void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
