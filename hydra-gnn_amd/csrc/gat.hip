@@ -488,6 +488,8 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
           continue;
         }
         if (!B.live[u]) continue;
+        // original edge id for dlogit_orig: fetch_batch loads it only for convs with edge attributes
+        const int eo = (I.dlogit_orig && !B.loop[u]) ? (ea ? B.eid[u] : glob(I.eid)[k]) : 0;
         bool keep[HM];
 #pragma unroll
         for (int h = 0; h < HM; ++h) keep[h] = true;
@@ -509,7 +511,7 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
           if (gl == 0) {
             globw(I.alpha_drop)[pos * GAT_HMAX + h] = alpha * dscale;
             globw(I.dlogit)[pos * GAT_HMAX + h] = dl;
-            if (I.dlogit_orig && !B.loop[u]) globw(I.dlogit_orig)[(int64_t)B.eid[u] * GAT_HMAX + h] = dl;
+            if (I.dlogit_orig && !B.loop[u]) globw(I.dlogit_orig)[(int64_t)eo * GAT_HMAX + h] = dl;
           }
         }
       }
