@@ -1,0 +1,269 @@
+// Two learned linear heads over one final state (HomogeneousNetwork / HomogeneousNeuralTreeNetwork with output_dim_dict): the
+// loop body of SemiSupervisedTrainingJob.train (semisupervised_training_job.py:117-147, homogeneous branches) from the program's
+// output z on, and the per-batch arithmetic of its test() (:198-257).
+//
+//   y = dropout(act(z))  over every row;  logits_h = y @ W_h^T + b_h  for the rows of head h;  masked CE of both heads.
+//
+// One workgroup owns tiles of HL_RB rows (tile b, b + grid, ...: a fixed assignment, so the result does not depend on timing).
+// Per tile:
+//   pass 1  logits of BOTH heads for every row of the tile, exact fp32 on the VALU (4 rows x 4 classes per thread), the
+//           F axis streamed through LDS in chunks of HL_FC columns (y chunk recomputed from z, W chunk of both heads);
+//   CE      one thread per (row, head): log-sum-exp, {loss, valid}, dlogits in place of the logits (0 outside the head);
+//   pass 2  per F chunk: dz = dlogits @ W . keep/(1-p) . act'  -> the output gradient, and dW += dlogits^T y into the
+//           workgroup's own slab (db once per tile).  No float atomics: the slabs are summed in a fixed order by the
+//           gradient un-pack (grad_reduce_kernel), which sees the heads as four more parameter segments.
+#include "kernels.h"
+
+namespace hmp {
+
+namespace {
+
+constexpr int HL_RB = 32;             // rows per tile
+constexpr int HL_FC = 64;             // F columns per LDS chunk
+constexpr int HL_KP = 2 * HEAD_MAX_CLASSES;  // logits per row, both heads
+constexpr int HL_PAD = HL_FC + 1;     // LDS row pitch of the chunks (conflict-free column walks)
+
+struct HeadSmem {
+  float lg[HL_RB][HL_KP + 1];  // logits, then dlogits
+  float ys[HL_RB][HL_PAD];     // y chunk
+  float ws[HL_KP][HL_PAD];     // W chunk of both heads (room rows first)
+  float hl[2][HL_RB], hv[2][HL_RB];
+  int cnt[4];
+};
+
+__device__ __forceinline__ bool head_member(const LinHeadArgs& a, int h, int row) {
+  if (h == 0) return a.member[0] ? a.member[0][row] != 0 : true;
+  if (a.member[1]) return a.member[1][row] != 0;
+  return a.member[0] ? a.member[0][row] == 0 : false;  // NULL: complement of head 0
+}
+
+// y = dropout(act(z)) of columns c0 .. c0 + HL_FC - 1 of the tile's rows into s.ys (0 outside the rows / columns); the arithmetic
+// and keep-mask numbering of bias_act_drop_kernel: quad row * ceil(F / 4) + col / 4
+__device__ void stage_y(const LinHeadArgs& a, const DropCfg& cfg, int row0, int c0, HeadSmem& s) {
+  const int qpr = (a.F + 3) >> 2;
+  for (int q = threadIdx.x; q < HL_RB * (HL_FC / 4); q += 256) {
+    const int r = q / (HL_FC / 4), cq = q % (HL_FC / 4);
+    const int row = row0 + r, c = c0 + 4 * cq;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (row < a.n_rows && c < a.F) {
+      const float4 z4 = *reinterpret_cast<const float4*>(a.z + (int64_t)row * a.ldz + c);  // ldz % 4 == 0, c + 3 < ldz
+      bool keep[4] = {true, true, true, true};
+      if (a.drop_on) drop_keep4(cfg, (uint32_t)row * (uint32_t)qpr + (uint32_t)(c >> 2), keep);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float x = (&z4.x)[i];
+        if (a.act == HMP_ACT_RELU) x = fmaxf(x, 0.f);
+        else if (a.act == HMP_ACT_ELU) x = x > 0.f ? x : expm1f(x);
+        if (a.drop_on) x = keep[i] ? (x * cfg.scale + 0.0f) : -0.0f;
+        else if (a.act != HMP_ACT_NONE) x = x + 0.0f;
+        v[i] = c + i < a.F ? x : 0.f;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s.ys[r][4 * cq + i] = v[i];
+  }
+}
+
+// W rows of both heads (k < classes[0]: room, then object), columns c0 .. c0 + HL_FC - 1, into s.ws (0 past F)
+__device__ void stage_w(const LinHeadArgs& a, int c0, HeadSmem& s) {
+  for (int q = threadIdx.x; q < a.K * HL_FC; q += 256) {
+    const int k = q / HL_FC, f = q % HL_FC, c = c0 + f;
+    const float* w = k < a.classes[0] ? a.W[0] + (int64_t)k * a.F : a.W[1] + (int64_t)(k - a.classes[0]) * a.F;
+    s.ws[k][f] = c < a.F ? w[c] : 0.f;
+  }
+}
+
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) {
+  __shared__ HeadSmem s;
+  const int t = threadIdx.x;
+  const DropCfg cfg = a.drop_on ? drop_resolve(a.drop) : a.drop;
+  if (!TRAIN && t < 4) s.cnt[t] = 0;
+  bool first = true;
+  for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x, first = false) {
+    const int row0 = tile * HL_RB;
+    // ---- pass 1: logits ----------------------------------------------------------------------------------------------
+    const int rg = t & 7, cg = t >> 3;  // rows rg + 8 i, classes 4 cg + j
+    const bool live = 4 * cg < a.K;     // whole wavefronts drop out past the classes
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    for (int c0 = 0; c0 < a.F; c0 += HL_FC) {
+      __syncthreads();  // the previous chunk / tile is consumed
+      stage_y(a, cfg, row0, c0, s);
+      stage_w(a, c0, s);
+      __syncthreads();
+      if (live) {
+        const int fe = min(HL_FC, a.F - c0);
+        for (int f = 0; f < fe; ++f) {
+          float yv[4], wv[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) yv[i] = s.ys[rg + 8 * i][f];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) wv[j] = s.ws[min(4 * cg + j, HL_KP - 1)][f];
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(yv[i], wv[j], acc[i][j]);
+        }
+      }
+    }
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = 4 * cg + j;
+        if (k >= a.K) continue;
+        const float bk = k < a.classes[0] ? a.bias[0][k] : a.bias[1][k - a.classes[0]];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s.lg[rg + 8 * i][k] = acc[i][j] + bk;
+      }
+    }
+    __syncthreads();
+    // ---- CE / argmax: one thread per (row, head) -----------------------------------------------------------------------
+    if (t < 2 * HL_RB) {
+      const int r = t % HL_RB, h = t / HL_RB, row = row0 + r;
+      const int C = a.classes[h], koff = h == 0 ? 0 : a.classes[0];
+      float* lg = &s.lg[r][koff];
+      const bool in_rows = row < a.n_rows;
+      const bool member = in_rows && head_member(a, h, row);
+      const bool in_mask = in_rows && (a.mask ? a.mask[row] != 0 : true);
+      const int64_t y = in_rows ? a.labels[row] : 0;
+      if (TRAIN) {
+        const bool valid = member && in_mask && y != a.ignored;
+        const bool bad = valid && (y < 0 || y >= C);
+        const bool use = valid && !bad;
+        float loss = 0.f;
+        if (use) {
+          float m = -INFINITY;
+          for (int k = 0; k < C; ++k) m = fmaxf(m, lg[k]);
+          float sum = 0.f;
+          for (int k = 0; k < C; ++k) sum += expf(lg[k] - m);
+          const float lse = m + logf(sum);
+          loss = lse - lg[y];
+          for (int k = 0; k < C; ++k) lg[k] = expf(lg[k] - lse) - (k == (int)y ? 1.f : 0.f);
+        } else {
+          for (int k = 0; k < C; ++k) lg[k] = 0.f;
+        }
+        s.hl[h][r] = loss;
+        s.hv[h][r] = use ? 1.f : 0.f;
+        if (bad) atomicOr(&a.state->status, 2);
+      } else if (member && in_mask) {
+        // first maximum (torch.argmax's rule)
+        int arg = 0;
+        float best = lg[0];
+        for (int k = 1; k < C; ++k)
+          if (lg[k] > best) { best = lg[k]; arg = k; }
+        atomicAdd(&s.cnt[2 * h + 1], 1);
+        if ((int64_t)arg == y) atomicAdd(&s.cnt[2 * h], 1);
+      }
+    }
+    if (!TRAIN) continue;
+    __syncthreads();
+    if (t < HL_RB && row0 + t < a.n_rows) {  // {loss, valid} of the row: room head + object head
+      a.row_lv[2 * (int64_t)(row0 + t)] = s.hl[0][t] + s.hl[1][t];
+      a.row_lv[2 * (int64_t)(row0 + t) + 1] = s.hv[0][t] + s.hv[1][t];
+    }
+    float* slab = a.slabs + (int64_t)blockIdx.x * a.slab_stride;
+    if (t < a.K) {  // db: column sums of dlogits, rows ascending
+      float db = 0.f;
+      for (int r = 0; r < HL_RB; ++r) db += s.lg[r][t];
+      float* d = slab + (int64_t)a.K * a.ld_slab + t;
+      *d = first ? db : *d + db;
+    }
+    // ---- pass 2: dz and dW per F chunk ---------------------------------------------------------------------------------
+    const int f = t & (HL_FC - 1), q = t >> 6;  // column f; rows / classes q + 4 i
+    for (int c0 = 0; c0 < a.F; c0 += HL_FC) {
+      __syncthreads();
+      stage_y(a, cfg, row0, c0, s);
+      stage_w(a, c0, s);
+      __syncthreads();
+      const int c = c0 + f;
+      float dz[HL_RB / 4];
+#pragma unroll
+      for (int i = 0; i < HL_RB / 4; ++i) dz[i] = 0.f;
+      for (int k = 0; k < a.K; ++k) {
+        const float w = s.ws[k][f];
+#pragma unroll
+        for (int i = 0; i < HL_RB / 4; ++i) dz[i] = fmaf(s.lg[q + 4 * i][k], w, dz[i]);
+      }
+      if (c < a.ldg) {
+#pragma unroll
+        for (int i = 0; i < HL_RB / 4; ++i) {
+          const int row = row0 + q + 4 * i;
+          if (row >= a.n_rows) continue;
+          const float g = c < a.F ? dz[i] * tail_dydz(s.ys[q + 4 * i][f], a.act, a.drop_on != 0, cfg.scale) : 0.f;
+          a.grad[(int64_t)row * a.ldg + c] = g;
+        }
+      }
+      if (c < a.F) {
+        for (int k0 = 0; k0 < a.K; k0 += 4 * 8) {  // classes q + 4 i of this group of 32
+          float dw[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) dw[i] = 0.f;
+          for (int r = 0; r < HL_RB; ++r) {
+            const float yv = s.ys[r][f];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dw[i] = fmaf(s.lg[r][min(k0 + q + 4 * i, HL_KP - 1)], yv, dw[i]);
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int k = k0 + q + 4 * i;
+            if (k >= a.K) continue;
+            float* d = slab + (int64_t)k * a.ld_slab + c;
+            *d = first ? dw[i] : *d + dw[i];
+          }
+        }
+      }
+    }
+  }
+  if (!TRAIN) {
+    __syncthreads();
+    if (t < 4 && s.cnt[t]) atomicAdd(&a.counts[t], (unsigned long long)s.cnt[t]);
+  }
+}
+
+int heads_check(const LinHeadArgs& a) {
+  HMP_CHECK_ARG(a.F >= 1 && a.F <= HEAD_MAX_F, "linear heads: F = %d (1 .. %d)", a.F, HEAD_MAX_F);
+  HMP_CHECK_ARG(a.classes[0] >= 1 && a.classes[0] <= HEAD_MAX_CLASSES && a.classes[1] >= 1 && a.classes[1] <= HEAD_MAX_CLASSES &&
+                    a.K == a.classes[0] + a.classes[1],
+                "linear heads: classes %d / %d (1 .. %d each)", a.classes[0], a.classes[1], HEAD_MAX_CLASSES);
+  HMP_CHECK_ARG((a.ldz & 3) == 0 && a.ldz >= a.F && (reinterpret_cast<uintptr_t>(a.z) & 15) == 0,
+                "linear heads: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", a.F);
+  HMP_CHECK_ARG(a.labels != nullptr || a.n_rows == 0, "linear heads: labels required");
+  return HMP_OK;
+}
+
+}  // namespace
+
+int heads_blocks(int n_rows) {
+  const int tiles = cdiv(n_rows, HL_RB);
+  return tiles < HEAD_MAX_BLOCKS ? tiles : HEAD_MAX_BLOCKS;
+}
+
+int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st) {
+  HMP_TRY(heads_check(a));
+  HMP_CHECK_ARG(a.ldg >= a.F && (a.ldg & 3) == 0 && a.ld_slab >= a.F && a.slab_stride >= (int64_t)a.K * (a.ld_slab + 1),
+                "linear heads: gradient / slab layout");
+  a.n_tiles = cdiv(a.n_rows, HL_RB);
+  const int blocks = heads_blocks(a.n_rows);
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(linear_heads_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st) {
+  HMP_TRY(heads_check(a));
+  a.n_tiles = cdiv(a.n_rows, HL_RB);
+  a.counts = reinterpret_cast<unsigned long long*>(counts);
+  a.drop_on = 0;
+  const int blocks = heads_blocks(a.n_rows);
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(linear_heads_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+}  // namespace hmp

@@ -350,9 +350,11 @@ struct GradSeg {
 // node type t (GAT) | 16 + c: V_edge of conv c (GAT_edge)}
 constexpr int SLAB_IDS_PER_LAYER = 2 * HMP_MAX_NODE_TYPES + HMP_MAX_CONVS;
 constexpr int GRAD_MAX_SLAB_IDS = HMP_MAX_LAYERS * SLAB_IDS_PER_LAYER;
+// one more id after the layers': the per-workgroup slabs of the linear heads (heads.hip, hmp_net_set_linear_heads)
+constexpr int HEAD_SLAB_ID = GRAD_MAX_SLAB_IDS;
 struct GradReduceDyn {  // passed by value: keep it small
-  unsigned char n_slabs[GRAD_MAX_SLAB_IDS];
-  int slab_stride[GRAD_MAX_SLAB_IDS];
+  unsigned char n_slabs[GRAD_MAX_SLAB_IDS + 1];
+  int slab_stride[GRAD_MAX_SLAB_IDS + 1];
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -482,6 +484,37 @@ struct TailArgs {
 };
 int tail_ce_launch(TailArgs& a, hipStream_t st);
 int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st);
+// Two learned linear heads over one final state (heads.hip): y = dropout(act(z)), logits_h = y W_h^T + b_h on the rows of head h,
+// masked CE of both heads with d loss / d z written to `grad` and per-workgroup partial dW / db slabs (fused step), or the
+// first-maximum argmax of both heads compared with the labels (accuracy count, eval mode).
+constexpr int HEAD_MAX_CLASSES = 64;
+constexpr int HEAD_MAX_F = 1024;
+constexpr int HEAD_MAX_BLOCKS = 240;  // workgroups = slabs per element (GradReduceDyn::n_slabs is a byte); one per CU
+struct LinHeadArgs {
+  const float* z;               // final state [n_rows][ldz]
+  int ldz, n_rows, F, K;        // K = classes[0] + classes[1]
+  int classes[2];
+  const float* W[2];            // [classes[h]][F] inside the flat parameters
+  const float* bias[2];
+  const int64_t* labels;        // one per row
+  const uint8_t* mask;          // null: every row
+  const uint8_t* member[2];     // rows of head h; member[1] null: complement of member[0]
+  int64_t ignored;
+  int act, drop_on;
+  DropCfg drop;                 // quad numbering row * ceil(F / 4) + col / 4
+  float* grad;                  // d loss / d z [n_rows][ldg] (columns F .. ldg written 0)
+  int ldg;
+  float* row_lv;                // per row {loss, valid} (both heads summed)
+  NetState* state;
+  float* slabs;                 // workgroup b: slabs + b * slab_stride = dW [K][ld_slab], then db [K]
+  int ld_slab;
+  int64_t slab_stride;
+  unsigned long long* counts;   // accuracy count: {correct_0, total_0, correct_1, total_1}
+  int n_tiles;
+};
+int heads_blocks(int n_rows);
+int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st);
+int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st);
 
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

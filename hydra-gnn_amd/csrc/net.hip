@@ -172,6 +172,13 @@ struct hmp_net {
   bool tail_done[2] = {false, false};
   bool aux_g_ready = false;
   int fin_rows = 0;
+  // linear heads (hmp_net_set_linear_heads): their description, where their per-workgroup slabs start in d_slabs, and the
+  // workgroups of the running step's head kernel (backward_impl hands that many slabs to the gradient un-pack; 0: none)
+  bool has_heads = false;
+  hmp_linear_heads heads = {};
+  int64_t head_slab_off = 0, head_slab_stride = 0;
+  int head_ld_slab = 0;
+  int head_blocks_now = 0;
   hipStream_t side[2] = {nullptr, nullptr};
   hipEvent_t evs[32];
   int n_evs = 0, ev_i = 0;
@@ -1272,6 +1279,10 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     ld_gtop = n->ld[n->L][rt];
   }
   memset(&n->dyn, 0, sizeof(n->dyn));
+  if (n->head_blocks_now > 0) {  // linear heads: the head kernel's workgroup slabs (rows past the heads' write nothing: 0)
+    n->dyn.n_slabs[HEAD_SLAB_ID] = (unsigned char)n->head_blocks_now;
+    n->dyn.slab_stride[HEAD_SLAB_ID] = (int)n->head_slab_stride;
+  }
   {
     // measured on MI355X (bench.py configs 2/3/4): below ~4k nodes per batch every kernel is launch-bound and one merged
     // weight-gradient launch wins (+2.5 %); above, overlapping the per-layer launches with the backward chain wins
@@ -1978,6 +1989,163 @@ extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const 
   if (ta.n == 0) return HMP_OK;
   Scope sc(n, KC_LOSS, st);
   return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
+}
+
+extern "C" int hmp_net_set_linear_heads(hmp_net* n, const hmp_linear_heads* h) {
+  HMP_CHECK_ARG(n && h, "hmp_net_set_linear_heads: null argument");
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(!n->has_heads, "hmp_net_set_linear_heads: the heads are already set");
+  HMP_CHECK_ARG(!n->bound, "hmp_net_set_linear_heads: call before the first workspace bind");
+  HMP_CHECK_ARG(S.aux_readout_type < 0, "hmp_net_set_linear_heads: a net with a second readout type has its own two-head step");
+  HMP_CHECK_ARG(h->F == n->out_dim, "hmp_net_set_linear_heads: F = %d, the program's output width is %d", h->F, n->out_dim);
+  HMP_CHECK_ARG(h->F <= HEAD_MAX_F, "hmp_net_set_linear_heads: F = %d > %d", h->F, HEAD_MAX_F);
+  for (int k = 0; k < 2; ++k) {
+    const int c = h->classes[k];
+    HMP_CHECK_ARG(c >= 1 && c <= HEAD_MAX_CLASSES, "hmp_net_set_linear_heads: classes[%d] = %d (1 .. %d)", k, c, HEAD_MAX_CLASSES);
+    HMP_CHECK_ARG(h->w_off[k] >= 0 && h->w_off[k] + (int64_t)c * h->F <= S.n_active_params && h->b_off[k] >= 0 &&
+                      h->b_off[k] + c <= S.n_active_params,
+                  "hmp_net_set_linear_heads: head %d parameters must lie in [0, n_active_params = %lld)", k,
+                  (long long)S.n_active_params);
+  }
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
+                "hmp_net_set_linear_heads: spec tail_act %d / tail_dropout %g", S.tail_act, (double)S.tail_dropout);
+  const int K = h->classes[0] + h->classes[1];
+  const int ld = fpad(h->F);
+  const int64_t stride = align4((int64_t)K * ld + K);
+  HMP_CHECK_ARG(n->n_grad + 4 <= SEG_MAX, "hmp_net_set_linear_heads: too many parameter segments");
+  // four more gradient segments (W_room, W_object, b_room, b_object), each the sum of the head kernel's workgroup slabs
+  std::vector<GradSeg> gs((size_t)n->n_grad + 4);
+  if (n->n_grad > 0) HMP_HIP(hipMemcpy(gs.data(), n->d_grad_segs, (size_t)n->n_grad * sizeof(GradSeg), hipMemcpyDeviceToHost));
+  const int64_t base = n->slab_floats;
+  for (int k = 0; k < 2; ++k) {
+    const int c = h->classes[k];
+    const int64_t row0 = k == 0 ? 0 : h->classes[0];
+    GradSeg& w = gs[(size_t)n->n_grad + k];
+    memset(&w, 0, sizeof(w));
+    w.dst = h->w_off[k]; w.rows = c; w.cols = h->F; w.n_terms = 1;
+    w.t[0] = term(GT_COPY, HEAD_SLAB_ID, base + row0 * ld, ld, c, c);
+    GradSeg& b = gs[(size_t)n->n_grad + 2 + k];
+    memset(&b, 0, sizeof(b));
+    b.dst = h->b_off[k]; b.rows = c; b.cols = 1; b.n_terms = 1;
+    b.t[0] = term(GT_COPY, HEAD_SLAB_ID, base + (int64_t)K * ld + row0, 1, c, c);
+  }
+  GradSeg* d = nullptr;
+  HMP_HIP(hipMalloc(&d, gs.size() * sizeof(GradSeg)));
+  if (hipMemcpy(d, gs.data(), gs.size() * sizeof(GradSeg), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    snprintf(err_buf(), 512, "hmp_net_set_linear_heads: copy of the gradient table failed");
+    return HMP_E_HIP;
+  }
+  if (n->d_grad_segs) (void)hipFree(n->d_grad_segs);
+  n->d_grad_segs = d;
+  for (int i = n->n_grad; i < (int)gs.size(); ++i) {
+    const int64_t el = (int64_t)gs[i].rows * gs[i].cols;
+    n->grad_sb.start[i + 1] = n->grad_sb.start[i] + (int)cdiv(el, 256);
+    n->grad_elems += el;
+    if (el > n->max_grad_elems) n->max_grad_elems = el;
+  }
+  n->n_grad = (int)gs.size();
+  n->grad_sb.n = n->n_grad;
+  n->slab_floats = base + (int64_t)HEAD_MAX_BLOCKS * stride;
+  n->head_slab_off = base; n->head_slab_stride = stride; n->head_ld_slab = ld;
+  n->heads = *h;
+  n->has_heads = true;
+  return HMP_OK;
+}
+
+namespace {
+
+int check_heads(const hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const char* who) {
+  HMP_CHECK_ARG(n->has_heads, "%s: the net has no linear heads (hmp_net_set_linear_heads)", who);
+  HMP_CHECK_ARG(!n->compute_bf16, "%s: the linear-head step computes in fp32 (bf16 compute mode is not supported)", who);
+  HMP_CHECK_ARG(b->n_out == 0 || tg->d_labels != nullptr, "%s: labels required", who);
+  return HMP_OK;
+}
+
+LinHeadArgs heads_args(hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const float* d_params, bool train,
+                       int64_t ignored) {
+  const hmp_net_spec& S = n->spec;
+  LinHeadArgs a;
+  memset(&a, 0, sizeof(a));
+  a.z = out_ptr(n); a.ldz = n->out_ld; a.n_rows = b->n_out; a.F = n->heads.F;
+  a.classes[0] = n->heads.classes[0]; a.classes[1] = n->heads.classes[1]; a.K = a.classes[0] + a.classes[1];
+  for (int k = 0; k < 2; ++k) {
+    a.W[k] = d_params + n->heads.w_off[k];
+    a.bias[k] = d_params + n->heads.b_off[k];
+    a.member[k] = tg->d_member[k];
+  }
+  a.labels = tg->d_labels; a.mask = tg->d_mask; a.ignored = ignored;
+  a.act = S.tail_act;
+  a.state = n->d_state;
+  if (!train) return a;
+  a.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+  if (a.drop_on) a.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + S.readout_type));
+  a.grad = n->d_gout; a.ldg = n->out_ld;
+  a.row_lv = n->d_row_lv;
+  a.slabs = n->d_slabs + n->head_slab_off; a.ld_slab = n->head_ld_slab; a.slab_stride = n->head_slab_stride;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int hmp_net_step_heads_fwd_bwd(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets,
+                                          const float* d_params, float* d_grads, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && args, "hmp_net_step_heads_fwd_bwd: null argument");
+  HMP_TRY(check_heads(n, batch, targets, "hmp_net_step_heads_fwd_bwd"));
+  hipStream_t st = (hipStream_t)stream;
+  read_env(n);
+  g_bf16_all = n->env.bf16_all;
+  n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
+  n->d_step = args->d_step ? args->d_step : &n->d_state->step;
+  n->ce_labels = nullptr; n->tgt = nullptr;
+  int r = forward_impl(n, batch, d_params, st);
+  if (r == HMP_OK) {  // the heads in place of the loss kernel: d loss / d z -> d_gout, {loss, valid} per row, dW / db slabs
+    LinHeadArgs a = heads_args(n, batch, targets, d_params, true, args->ignored_label);
+    Scope sc(n, KC_LOSS, st);
+    r = linear_heads_ce_launch(a, st);
+  }
+  if (r == HMP_OK) {
+    n->fin_loss = true;
+    n->head_blocks_now = heads_blocks(batch->n_out);
+    r = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
+    n->head_blocks_now = 0;
+    n->fin_loss = false;
+  }
+  n->d_step = &n->d_state->step;
+  n->step_dev = false;
+  return r;
+}
+
+extern "C" int hmp_net_step_heads_fused(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets, float* d_params,
+                                        float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && d_m && d_v && args, "hmp_net_step_heads_fused: null argument");
+  AdamFuse& af = n->adam_fuse;
+  af.on = n->fuse_mode == 0 ? 0 : 1;
+  af.p = d_params; af.m = d_m; af.v = d_v;
+  af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
+  af.step_dev = args->d_step ? args->d_step : &n->d_state->step;
+  af.count = d_grads + n->spec.n_active_params + 1;
+  n->adam_done = false;
+  const int r = hmp_net_step_heads_fwd_bwd(n, batch, targets, d_params, d_grads, args, stream);
+  af.on = 0;
+  HMP_TRY(r);
+  if (n->adam_done) return HMP_OK;
+  return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
+}
+
+extern "C" int hmp_net_count_correct_heads(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets,
+                                           const float* d_params, int64_t* d_counts, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct_heads: null argument");
+  HMP_TRY(check_heads(n, batch, targets, "hmp_net_count_correct_heads"));
+  hipStream_t st = (hipStream_t)stream;
+  read_env(n);
+  g_bf16_all = n->env.bf16_all;
+  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
+  n->ce_labels = nullptr; n->tgt = nullptr;
+  HMP_TRY(forward_impl(n, batch, d_params, st));
+  LinHeadArgs a = heads_args(n, batch, targets, d_params, false, 0);
+  Scope sc(n, KC_LOSS, st);
+  return linear_heads_count_launch(a, reinterpret_cast<long long*>(d_counts), st);
 }
 
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,

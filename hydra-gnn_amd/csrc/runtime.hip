@@ -34,6 +34,8 @@ size_t hmp_sizeof(int which) {
     case 5: return sizeof(hmp_batch);
     case 6: return sizeof(hmp_train_args);
     case 7: return sizeof(hmp_head_targets);
+    case 8: return sizeof(hmp_linear_heads);
+    case 9: return sizeof(hmp_linear_head_targets);
     default: return 0;
   }
 }

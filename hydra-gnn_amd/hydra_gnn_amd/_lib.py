@@ -99,12 +99,20 @@ class HeadTargets(C.Structure):
     _fields_ = [("d_labels", C.c_void_p * 2), ("d_mask", C.c_void_p * 2)]
 
 
+class LinearHeads(C.Structure):
+    _fields_ = [("F", C.c_int32), ("classes", C.c_int32 * 2), ("w_off", C.c_int64 * 2), ("b_off", C.c_int64 * 2)]
+
+
+class LinearHeadTargets(C.Structure):
+    _fields_ = [("d_labels", C.c_void_p), ("d_mask", C.c_void_p), ("d_member", C.c_void_p * 2)]
+
+
 class CollateItem(C.Structure):
     _fields_ = [("d_src", C.c_void_p), ("d_ptr", C.c_void_p), ("src_total", C.c_int64), ("row_bytes", C.c_int64),
                 ("slot", C.c_int32), ("slot_src", C.c_int32), ("slot_dst", C.c_int32)]
 
 
-_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets]
+_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -146,6 +154,11 @@ SIGNATURES = {
     "hmp_net_step2_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_step2_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_count_correct2": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP]),
+    "hmp_net_set_linear_heads": (C.c_int, [_VP, C.POINTER(LinearHeads)]),
+    "hmp_net_step_heads_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, C.POINTER(TrainArgs), _VP]),
+    "hmp_net_step_heads_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP, _VP,
+                                           C.POINTER(TrainArgs), _VP]),
+    "hmp_net_count_correct_heads": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP]),
     "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),

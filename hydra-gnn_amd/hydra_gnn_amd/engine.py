@@ -69,7 +69,8 @@ class _BatchHolder:
 class NativeNet:
     def __init__(self, node_types: Sequence[str], in_dims: Dict[str, int], edge_types: Sequence[EdgeType],
                  layers: List[LayerDesc], readout: str, pool_edge_type: Optional[EdgeType] = None,
-                 count_types: Sequence[str] = (), aux_readout: Optional[str] = None, tail: Optional[Tuple[int, float]] = None):
+                 count_types: Sequence[str] = (), aux_readout: Optional[str] = None, tail: Optional[Tuple[int, float]] = None,
+                 heads: Optional[Sequence[nn.Linear]] = None):
         self.node_types = list(node_types)
         self.edge_types = [tuple(e) for e in edge_types]
         self.in_dims = dict(in_dims)
@@ -81,6 +82,12 @@ class NativeNet:
         # (activation, dropout) the two-headed model applies to both final states after the program (heterogeneous_network.py:
         # 124-134); only the fused two-head step (TwoHeadTrainStep) and count_correct run it natively
         self.tail = (int(tail[0]), float(tail[1])) if tail is not None else (ACT_NONE, 0.0)
+        # two LEARNED linear heads (room, object) over the readout's final state (homogeneous_network.py:138-147): their
+        # parameters live in the flat buffer inside [0, n_active) so one all-reduce and Adam cover them, but they are not part of
+        # `params` (the autograd path of forward() computes the heads in torch and never returns their gradients)
+        self.heads = list(heads) if heads is not None else None
+        assert self.heads is None or (len(self.heads) == 2 and aux_readout is None)
+        self.head_params: List[nn.Parameter] = []
         self.pool_edge_type = tuple(pool_edge_type) if pool_edge_type is not None else None
         # node types without features whose node COUNT matters (virtual pool targets)
         self.count_types = list(count_types)
@@ -147,6 +154,11 @@ class NativeNet:
                             continue
                         seen[id(p)] = len(order)
                         order.append((p, live))
+            if active_pass and self.heads is not None:  # after the live conv parameters, in front of the dead ones
+                for lin in self.heads:
+                    for p in (lin.weight, lin.bias):
+                        seen[id(p)] = len(order)
+                        order.append((p, None))
         # a parameter shared by several convs (GAT lin_src == lin_dst) is active if any user is
         off = 0
         self.param_offsets: Dict[int, int] = {}
@@ -154,8 +166,12 @@ class NativeNet:
         self.param_active: List[bool] = []
         for p, live in order:
             self.param_offsets[id(p)] = off
-            self.params.append(p)
-            self.param_active.append(live)
+            if live is None:
+                self.head_params.append(p)
+                live = True
+            else:
+                self.params.append(p)
+                self.param_active.append(live)
             off += ((p.numel() + 3) // 4) * 4  # keep every tensor 16-byte aligned in the flat buffer
             if live:
                 self.n_active = off
@@ -248,7 +264,18 @@ class NativeNet:
             self._handle = h
             if self._compute_bf16:
                 _lib.check(self._lib.hmp_net_set_compute(h, 1))
+            if self.heads is not None:
+                _lib.check(self._lib.hmp_net_set_linear_heads(h, C.byref(self._linear_heads())))
         return self._handle
+
+    def _linear_heads(self) -> _lib.LinearHeads:
+        hd = _lib.LinearHeads()
+        hd.F = int(self.heads[0].in_features)
+        for k, lin in enumerate(self.heads):
+            hd.classes[k] = int(lin.out_features)
+            hd.w_off[k] = self.param_offsets[id(lin.weight)]
+            hd.b_off[k] = self.param_offsets[id(lin.bias)]
+        return hd
 
     def __del__(self):
         try:
@@ -267,14 +294,14 @@ class NativeNet:
             base = self._flat.data_ptr()
             # `.to()` / `.float()` re-home every parameter; the first and the last one are checked on the hot path (one call
             # per step), all of them when the check is forced
-            probe = self.params if full_check else (self.params[0], self.params[-1])
+            probe = self.params + self.head_params if full_check else (self.params[0], self.params[-1])
             for p in probe:
                 if p.data.data_ptr() != base + 4 * self.param_offsets[id(p)] or p.dtype != torch.float32:
                     ok = False
                     break
         if not ok:
             flat = torch.zeros(self.n_params + 4, dtype=torch.float32, device=p0.device)
-            for p in self.params:
+            for p in self.params + self.head_params:
                 if p.dtype != torch.float32:
                     raise _lib.HydraMPError("hydra_gnn_amd computes in fp32: parameter dtype must be float32")
                 off = self.param_offsets[id(p)]
@@ -473,6 +500,24 @@ class NativeNet:
             self._ensure_workspace(h, dev)
             _lib.check(self._lib.hmp_net_count_correct2(self._handle, C.byref(h.c), C.byref(tg), flat.data_ptr(), counts.data_ptr(),
                                                         _lib.stream_ptr()))
+            self._fwd_token += 1
+            self._plan_key = self._plan_tensors = None
+        return counts
+
+    def count_correct_heads(self, data, labels, mask, members, counts: torch.Tensor) -> torch.Tensor:
+        """Nets with linear heads: ADD this batch's {correct, total} of both heads to the device int64[4] ``counts``
+        (``hmp_net_count_correct_heads``: eval-mode forward, argmax of both heads on act(final state), comparison under ``mask``
+        on the member rows).  Nothing synchronises."""
+        flat = self.flat_params(full_check=False)
+        h = self.make_batch(data)
+        dev = flat.device
+        if counts.dtype != torch.int64 or counts.numel() < 4 or not counts.is_contiguous() or counts.device != dev:
+            raise _lib.HydraMPError("counts must be a contiguous int64[4] tensor on the model's device")
+        tg = _linear_head_targets(self, h, labels, mask, members)
+        with torch.cuda.device(dev):
+            self._ensure_workspace(h, dev)
+            _lib.check(self._lib.hmp_net_count_correct_heads(self._handle, C.byref(h.c), C.byref(tg), flat.data_ptr(),
+                                                             counts.data_ptr(), _lib.stream_ptr()))
             self._fwd_token += 1
             self._plan_key = self._plan_tensors = None
         return counts
@@ -834,19 +879,24 @@ class TwoHeadTrainStep(TrainStep):
                                                 self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), C.byref(self.args), st))
 
     def __call__(self, data, labels, masks=None) -> None:
+        tensors = tuple(labels) + (tuple(masks) if masks is not None else ())
+        self._step(data, masks is None, tensors, lambda h: _head_targets(self.net, h, labels, masks))
+
+    def _step(self, data, tag, tensors, make_targets) -> None:
+        """one step on ``data`` with the targets ``make_targets(holder)`` builds from ``tensors`` (reused, with the descriptor, while
+        ``data`` and every tensor are unchanged)"""
         net = self.net
         if net.flat_params(full_check=False) is not self.flat:
-            raise _lib.HydraMPError("model parameters were moved after TwoHeadTrainStep was created")
+            raise _lib.HydraMPError(f"model parameters were moved after {type(self).__name__} was created")
         stamp = getattr(data, "_mutation_stamp", None)
-        tensors = tuple(labels) + (tuple(masks) if masks is not None else ())
         key = None
         if stamp is not None:
-            key = (id(data), stamp(), masks is None) + tuple((id(t), t._version) if t is not None else None for t in tensors)
+            key = (id(data), stamp(), tag) + tuple((id(t), t._version) if t is not None else None for t in tensors)
         if key is not None and key == self._batch_key:
             h = self._holder
         else:
             h = net.make_batch(self.view(data) if self.view is not None else data)
-            self._targets = _head_targets(net, h, labels, masks)
+            self._targets = make_targets(h)
             self._batch_key = key if not h.converted else None
             self._data_ref = (data, tensors)  # keeps id() unique while the key is live
         self._holder = h
@@ -881,3 +931,83 @@ class TwoHeadTrainStep(TrainStep):
 
     def run(self, holder) -> None:
         raise _lib.HydraMPError("TwoHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")
+
+
+def _linear_head_targets(net: NativeNet, h: _BatchHolder, labels, mask, members) -> _lib.LinearHeadTargets:
+    """hmp_linear_head_targets for per-row ``labels``, an optional bool ``mask`` and the bool ``members`` (room rows, object rows
+    or None = the complement of the room rows); the tensors it points at join ``h.keep`` (alive with the descriptor, part of a
+    captured graph's key)."""
+    if net.heads is None:
+        raise _lib.HydraMPError("the linear-head entries need a net with linear heads")
+    n = int(h.c.n_out)
+    tg = _lib.LinearHeadTargets()
+    _require_cuda(labels, "labels")
+    lab = labels.to(torch.int64).contiguous()
+    if lab is not labels:
+        h.converted = True
+    if lab.numel() != n:
+        raise _lib.HydraMPError(f"labels: {lab.numel()} labels for {n} output rows")
+    h.keep.append(lab)
+    tg.d_labels = lab.data_ptr() if n > 0 else None
+
+    def rows(m, what):
+        _require_cuda(m, what)
+        if m.dtype != torch.bool:
+            raise _lib.HydraMPError(f"{what} must be a bool tensor")
+        c = m.contiguous()
+        if c is not m:
+            h.converted = True
+        if c.numel() != n:
+            raise _lib.HydraMPError(f"{what}: {c.numel()} entries for {n} output rows")
+        h.keep.append(c)
+        return c.data_ptr() if n > 0 else None
+
+    if mask is not None:
+        tg.d_mask = rows(mask, "mask")
+    if members[0] is None:
+        raise _lib.HydraMPError("the room head's rows (room_mask) are required")
+    tg.d_member[0] = rows(members[0], "room_mask")
+    if members[1] is not None:
+        tg.d_member[1] = rows(members[1], "object_mask")
+    return tg
+
+
+class LinearHeadTrainStep(TwoHeadTrainStep):
+    """The loop body of ``SemiSupervisedTrainingJob.train`` for the homogeneous two-headed models (HomogeneousNetwork /
+    HomogeneousNeuralTreeNetwork with ``output_dim_dict``): phase A = plan + forward + the model's tail (act, dropout) + the two
+    learned linear heads + masked CE of both + backward (``hmp_net_step_heads_fwd_bwd``), [all-reduce], phase B = Adam over
+    [0, n_active), the heads included -- :class:`TwoHeadTrainStep`'s eager / graph / collective machinery with
+    ``hmp_linear_head_targets``.
+
+    ``step(data, labels=None, mask=None)``: labels default to ``data.y``, the mask to ``data.train_mask``; the room head's rows are
+    ``data.room_mask``, the object head's ``data.<object_attr>`` (H-tree: ``object_mask``) or, with ``object_attr`` None, the
+    complement of the room rows (the baseline's ``~room_mask``, computed on the device by the head kernel)."""
+
+    def __init__(self, net: NativeNet, lr: float, weight_decay: float = 0.0, ignored_label: int = -100,
+                 object_attr: Optional[str] = None, **kw):
+        if net.heads is None:
+            raise _lib.HydraMPError("LinearHeadTrainStep needs a net with linear heads")
+        TrainStep.__init__(self, net, lr, weight_decay=weight_decay, ignored_label=ignored_label, **kw)
+        self._targets = None
+        self.object_attr = object_attr
+
+    def _phase_a(self, h, st):
+        net = self.net
+        _lib.check(net._lib.hmp_net_step_heads_fwd_bwd(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
+                                                       self.grads.data_ptr(), C.byref(self.args), st))
+
+    def _phase_ab(self, h, st):
+        net = self.net
+        _lib.check(net._lib.hmp_net_step_heads_fused(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
+                                                     self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                     C.byref(self.args), st))
+
+    def __call__(self, data, labels=None, mask=None) -> None:
+        labels = data.y if labels is None else labels
+        mask = data.train_mask if mask is None else mask
+        members = (data.room_mask, getattr(data, self.object_attr) if self.object_attr is not None else None)
+        tensors = (labels, mask) + members
+        self._step(data, None, tensors, lambda h: _linear_head_targets(self.net, h, labels, mask, members))
+
+    def run(self, holder) -> None:
+        raise _lib.HydraMPError("LinearHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")

@@ -105,7 +105,49 @@ class HomogeneousNetwork(_NativeModule):
             last = l == self.num_layers - 1
             act = ACT_NONE if last else (ACT_ELU if gat else ACT_RELU)
             layers.append(LayerDesc([cd], {_NODE: width}, act, 0.0 if last else self.dropout))
-        return NativeNet([_NODE], {_NODE: self.input_dim}, [_EDGE], layers, readout=_NODE)
+        return NativeNet([_NODE], {_NODE: self.input_dim}, [_EDGE], layers, readout=_NODE, **self._head_kw())
+
+    def _head_kw(self):
+        """two-headed task: the tail (act, dropout) and the learned heads the fused step runs natively (reference :138-146)"""
+        if self.classification_task != "all":
+            return {}
+        gat = self.conv_block[:3] == "GAT"
+        return dict(tail=(ACT_ELU if gat else ACT_RELU, float(self.dropout)), heads=[self.post_mp_room, self.post_mp_object])
+
+    _OBJECT_ATTR = None  # rows of the object head: None = ~room_mask (reference :147)
+
+    def _check_two_head(self, what):
+        if self.classification_task != "all":
+            raise HydraMPError(f"{what}: the model has one output (build it with output_dim_dict for the two-headed task); use "
+                               "train_step()")
+        if self.op_path:
+            raise HydraMPError(f"{what}: {self.conv_block} runs op by op; the fused two-head step covers GraphSAGE / GAT / GAT_edge")
+
+    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
+        """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body, homogeneous branch), see
+        engine.LinearHeadTrainStep: ``step(data, labels=None, mask=None)`` with ``data.y`` / ``data.train_mask`` as defaults and
+        the head rows from ``data.room_mask``.  The dropout seed is the module's, so the masks are the ones ``forward()`` draws at
+        the same step number."""
+        from ..engine import LinearHeadTrainStep
+
+        self._check_two_head("semisupervised_step")
+        kw.setdefault("seed", self._seed)
+        return LinearHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=self._view, object_attr=self._OBJECT_ATTR,
+                                   **kw)
+
+    def count_correct(self, data, mask_name="test_mask", counts=None):
+        """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
+        forward, argmax of both heads, compared with ``data.y`` on the rows of ``data.<mask_name>``.  With ``counts`` (device
+        int64[4]) {correct_room, total_room, correct_object, total_object} are ADDED to it without a sync; without, returns the
+        four ints of this batch."""
+        self._check_two_head("count_correct")
+        net = self.native()
+        acc = counts
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+        members = (data.room_mask, getattr(data, self._OBJECT_ATTR) if self._OBJECT_ATTR is not None else None)
+        net.count_correct_heads(self._view(data), data.y, getattr(data, mask_name), members, acc)
+        return acc if counts is not None else [int(v) for v in acc.tolist()]
 
     def _view(self, data):
         return _HomoView(data)

@@ -114,7 +114,10 @@ class HomogeneousNeuralTreeNetwork(HomogeneousNetwork):
             init = LayerDesc([self.pre_mp.desc(_INIT)], {_NODE: self.input_dim}, ACT_NONE, 0.0)
             layers = [init] + layers
             edge_types.append(_INIT)
-        return NativeNet([_NODE], {_NODE: self.input_dim}, edge_types, layers, readout=_NODE, pool_edge_type=_POOL)
+        return NativeNet([_NODE], {_NODE: self.input_dim}, edge_types, layers, readout=_NODE, pool_edge_type=_POOL,
+                         **self._head_kw())
+
+    _OBJECT_ATTR = "object_mask"  # reference :109
 
     def _drop_stream(self, l: int) -> int:
         # with pre_mp inside the native program (SAGE / GAT) the convs are its layers 1..L

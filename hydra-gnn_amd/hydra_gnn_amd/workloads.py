@@ -125,6 +125,21 @@ def semisupervised_batch(n_graphs: int, seed: int, relative_pos: bool = False) -
     return batch
 
 
+def stanford_semisupervised_batch(n_graphs: int, seed: int) -> Data:
+    """Batch of the homogeneous two-headed task (Stanford3DSG, ``SemiSupervisedTrainingJob`` with ``HomogeneousNetwork``):
+    ``stanford_like_graph``s (room node 0 with a label in 0..14, objects 0..34), collated like PyG, with a seeded per-node split
+    into disjoint ``train_mask`` (60 %), ``val_mask`` (20 %) and ``test_mask`` (20 %) bool tensors."""
+    from .data import collate_homogeneous
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    batch = collate_homogeneous([stanford_like_graph(rng) for _ in range(n_graphs)])
+    u = torch.from_numpy(rng.random(int(batch.y.numel())))
+    batch.train_mask = u < 0.6
+    batch.val_mask = (u >= 0.6) & (u < 0.8)
+    batch.test_mask = u >= 0.8
+    return batch
+
+
 def config2_batch(batch_size: int = 32, rank: int = 0) -> HeteroData:
     return mp3d_like_batch(batch_size, BASE_SEED + 2 + 1000 * rank)
 

@@ -28,7 +28,10 @@ extern "C" {
  * 3: round 3 -- hmp_comm_query; hmp_net_read_state reports the counter of the last step from the net's own state;
  *    hmp_conv_spec::agg_first; hmp_gemm_bf16_dx / hmp_gemm_bf16_dw
  * 4: hmp_net_spec::tail_act / tail_dropout, hmp_head_targets (hmp_sizeof 7), hmp_net_step2_fwd_bwd / hmp_net_step2_fused /
- *    hmp_net_count_correct2: the fused step of the two-headed task */
+ *    hmp_net_count_correct2: the fused step of the two-headed task
+ *    ABI-4-compatible additions (nothing above changed layout): hmp_linear_heads (hmp_sizeof 8), hmp_linear_head_targets
+ *    (hmp_sizeof 9), hmp_net_set_linear_heads / hmp_net_step_heads_fwd_bwd / hmp_net_step_heads_fused /
+ *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -49,7 +52,7 @@ extern "C" {
 int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
- * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets (lets a foreign-language binding verify its struct mirror) */
+ * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets (lets a foreign-language binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -352,6 +355,40 @@ int hmp_net_step2_fused(hmp_net* net, const hmp_batch* batch, const hmp_head_tar
  * {correct_readout, total_readout, correct_aux, total_aux}; one launch beyond the forward, nothing synchronises. */
 int hmp_net_count_correct2(hmp_net* net, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
                            int64_t* d_counts, void* stream);
+/* Two LEARNED linear heads over one final state (HomogeneousNetwork / HomogeneousNeuralTreeNetwork with output_dim_dict,
+ * homogeneous_network.py:122-147, homogeneous_neural_tree_network.py:96-109): the loop body of SemiSupervisedTrainingJob.train
+ * (semisupervised_training_job.py:117-147, homogeneous branches) and the per-batch arithmetic of its test() (:198-257).
+ *   z = the program's output [n_out][F] (the last conv, or the pooled output with pool_edge_type); y = dropout(act(z)) over EVERY
+ *   row, act = spec.tail_act, p = spec.tail_dropout (training only), keep-mask = tensor 8 * (n_layers - 1) of the step's draw
+ *   number in quad row * ceil(F / 4) + col / 4 (the hmp_net_step2_* rule above); logits_h = y[rows_h] W_h^T + b_h, with W_h
+ *   [classes[h]][F] and b_h [classes[h]] read from the flat parameters at w_off[h] / b_off[h].  A row may be in no head, one or
+ *   both.  Loss: the summed CE of both heads over rows_h AND mask AND label != ignored_label, over one total count (the
+ *   reference's list-form cross_entropy_loss); an in-mask member label outside [0, classes[h]) sets status bit 2.
+ *   The head parameters must lie in [0, n_active): their gradients join the flat gradient (summed per workgroup slab by the
+ *   gradient un-pack, no float atomics: bitwise reproducible) and phase B's Adam.  The flat-gradient contract, the two phases and
+ *   capturability are hmp_net_step2_*'s.  set_linear_heads is called once, before the first workspace bind; F must equal the
+ *   program's output width, 1 <= classes[h] <= 64. */
+typedef struct hmp_linear_heads {
+  int32_t F;
+  int32_t classes[2];         /* [0] room head, [1] object head */
+  int64_t w_off[2], b_off[2]; /* float offsets of W_h / b_h in the flat parameter buffer */
+} hmp_linear_heads;
+typedef struct hmp_linear_head_targets {
+  const int64_t* d_labels;    /* [n_out] int64, one label per row */
+  const uint8_t* d_mask;      /* bool per row (train / val / test mask), NULL = every row */
+  const uint8_t* d_member[2]; /* bool per row: rows of the room / object head; d_member[1] NULL = NOT d_member[0] */
+} hmp_linear_head_targets;
+
+int hmp_net_set_linear_heads(hmp_net* net, const hmp_linear_heads* heads);
+int hmp_net_step_heads_fwd_bwd(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, const float* d_params,
+                               float* d_grads, const hmp_train_args* args, void* stream);
+int hmp_net_step_heads_fused(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, float* d_params,
+                             float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream);
+/* eval-mode forward, logits of both heads on act(z) (no dropout), first-maximum argmax, compared with the labels of the member
+ * rows under the mask (every masked row counts).  ACCUMULATES {correct_room, total_room, correct_object, total_object} into
+ * d_counts (device int64[4]); nothing synchronises. */
+int hmp_net_count_correct_heads(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, const float* d_params,
+                                int64_t* d_counts, void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
