@@ -89,9 +89,11 @@ extern "C" int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const in
 // =============================================================================================================================
 namespace hmp {
 
-constexpr int CB_MAX_ITEMS = 20;
-constexpr int CB_MAX_SLOTS = 12;
-constexpr int CB_INLINE_WORDS = 356;  // int64 words of per-batch tables carried by value in the kernel argument block (whole block < 4 KB)
+// 24 / 24: room for an H-tree dataset (6 node types, 15 edge types: 21 slots, 22 items); slots cost nothing in the
+// argument block, items 56 bytes each
+constexpr int CB_MAX_ITEMS = 24;
+constexpr int CB_MAX_SLOTS = 24;
+constexpr int CB_INLINE_WORDS = 336;  // int64 words of per-batch tables carried by value in the kernel argument block (whole block < 4 KB)
 
 struct CbItem {
   const uint32_t* src;    // rows: packed rows (4-byte units); edges: int64 edge_index [2][src_total] viewed as units

@@ -516,6 +516,12 @@ int heads_blocks(int n_rows);
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st);
 int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st);
 
+// Room-task validation count (evaluate.hip): first-maximum row argmax compared with the labels of the counted rows
+// ((members == null || members[row]) && label != ignored); ACCUMULATES {correct, total} into counts and, with confusion != null,
+// confusion[label][pred] for labels in [0, n_classes).  n_rows == 0 launches nothing.
+int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
+                      int64_t ignored, long long* counts, long long* confusion, hipStream_t st);
+
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
                 int step_host, const int* step_dev, const float* d_count, hipStream_t st);

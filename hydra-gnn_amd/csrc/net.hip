@@ -2148,6 +2148,23 @@ extern "C" int hmp_net_count_correct_heads(hmp_net* n, const hmp_batch* batch, c
   return linear_heads_count_launch(a, reinterpret_cast<long long*>(d_counts), st);
 }
 
+extern "C" int hmp_net_count_correct_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
+                                           int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_counts, "hmp_net_count_correct_rooms: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
+                "hmp_net_count_correct_rooms: a two-headed net counts with hmp_net_count_correct2 / hmp_net_count_correct_heads");
+  HMP_CHECK_ARG(batch->n_out == 0 || batch->d_labels, "hmp_net_count_correct_rooms: the batch has no labels");
+  hipStream_t st = (hipStream_t)stream;
+  read_env(n);
+  g_bf16_all = n->env.bf16_all;
+  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
+  n->ce_labels = nullptr; n->tgt = nullptr;  // no fused CE inside an eval forward
+  HMP_TRY(forward_impl(n, batch, d_params, st));
+  Scope sc(n, KC_LOSS, st);
+  return count_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
+                           reinterpret_cast<long long*>(d_counts), reinterpret_cast<long long*>(d_confusion), st);
+}
+
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,
                                  const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && d_params && d_grads && d_m && d_v && args, "hmp_net_step_adam: null argument");

@@ -138,6 +138,7 @@ SIGNATURES = {
                               _VP, _I32, _VP, _I32, _VP, _I32, _VP]),
     "hmp_masked_ce": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_argmax_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
+    "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
     "hmp_net_create": (C.c_int, [C.POINTER(NetSpec), C.POINTER(_VP)]),
@@ -159,6 +160,7 @@ SIGNATURES = {
     "hmp_net_step_heads_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP, _VP,
                                            C.POINTER(TrainArgs), _VP]),
     "hmp_net_count_correct_heads": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP]),
+    "hmp_net_count_correct_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I64, _VP, _VP, _VP]),
     "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),

@@ -522,6 +522,45 @@ class NativeNet:
             self._plan_key = self._plan_tensors = None
         return counts
 
+    def count_correct_rooms(self, batch, labels, counts: torch.Tensor, ignored_label: int = 25,
+                            members: Optional[torch.Tensor] = None, confusion: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Room task: ADD this batch's {correct, total} to the device int64[2] ``counts`` and, when given, its confusion matrix to
+        the device int64[C * C] ``confusion`` (``hmp_net_count_correct_rooms``: eval-mode forward, first-maximum argmax of the
+        output, comparison with ``labels`` on the rows of ``members`` whose label is not ``ignored_label``).  ``batch`` is a data
+        object or a descriptor from ``store.BatchStream.next``, which brings its own labels (pass ``labels=None``).  Nothing
+        synchronises."""
+        if self.aux_readout is not None or self.heads is not None:
+            raise _lib.HydraMPError("count_correct_rooms: a two-headed net counts with count_correct / count_correct_heads")
+        flat = self.flat_params(full_check=False)
+        dev = flat.device
+        if isinstance(batch, _BatchHolder):
+            if labels is not None:
+                raise _lib.HydraMPError("count_correct_rooms: a stream batch brings its own labels (pass labels=None)")
+            h = batch
+        else:
+            if labels is None:
+                raise _lib.HydraMPError("count_correct_rooms: labels are required for a data batch")
+            h = self.make_batch(batch, labels)
+        if not h.c.d_labels and int(h.c.n_out) > 0:
+            raise _lib.HydraMPError("count_correct_rooms: the batch has no labels")
+        from .ops import check_count_buffers, row_members
+
+        check_count_buffers(counts, confusion, self.n_classes, dev)
+        members = row_members(members, int(h.c.n_out), dev)
+        with torch.cuda.device(dev):
+            self._ensure_workspace(h, dev)
+            _lib.check(self._lib.hmp_net_count_correct_rooms(
+                self._handle, C.byref(h.c), flat.data_ptr(), members.data_ptr() if members is not None else None, int(ignored_label),
+                counts.data_ptr(), confusion.data_ptr() if confusion is not None else None, _lib.stream_ptr()))
+            self._fwd_token += 1
+            self._plan_key = self._plan_tensors = None
+        return counts
+
+    @property
+    def n_classes(self) -> int:
+        """width of the program's output (the class count of the room task)"""
+        return int(self.layers[-1].out_dims[self.readout])
+
     def _forward_raw(self, h: _BatchHolder, training: bool, seed: int, rng_step: int) -> torch.Tensor:
         out_p, ld = C.c_void_p(), C.c_int32()
         _lib.check(self._lib.hmp_net_forward(self._handle, C.byref(h.c), self._flat.data_ptr(), int(training), seed, rng_step,

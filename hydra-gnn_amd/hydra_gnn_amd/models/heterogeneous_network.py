@@ -75,6 +75,31 @@ class _NativeModule(nn.Module):
     def loss(self, pred, label, mask=None):
         return cross_entropy_loss(pred, label, mask)
 
+    _ROOM_LABELS = "rooms"  # node type whose `y` BaseTrainingJob.test compares with (base_training_job.py:283-291)
+
+    def _room_task(self, what):
+        if getattr(self, "classification_task", "room") != "room":
+            raise _lib.HydraMPError(f"{what}: the model is two-headed (built with output_dim_dict); count its accuracy with "
+                                    "count_correct()")
+
+    def count_correct_rooms(self, data, counts=None, confusion=None, ignored_label=25):
+        """The per-batch arithmetic of ``BaseTrainingJob.test`` (base_training_job.py:269-313) for the room task: eval-mode native
+        forward, ``argmax(dim=1)``, compared with the room labels (``data["rooms"].y``, H-tree: ``data["room_virtual"].y``) on
+        the rows whose label is not ``ignored_label`` (``hmp_net_count_correct_rooms``).  ``data`` is a batch or a descriptor from
+        ``store.BatchStream.next`` (its labels come from the stream's ``label_type``).  With ``counts`` (device int64[2]) the
+        batch's {correct, total} are ADDED to it on the device and the tensor is returned without a sync; without, returns the two
+        ints of this batch.  ``confusion`` (device int64 [C, C]) receives ``[label, pred] += 1`` of the counted rows."""
+        from ..engine import _BatchHolder
+
+        self._room_task("count_correct_rooms")
+        net = self.native()
+        acc = counts
+        if acc is None:
+            acc = torch.zeros(2, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+        labels = None if isinstance(data, _BatchHolder) else data[self._ROOM_LABELS].y
+        net.count_correct_rooms(data, labels, acc, ignored_label, confusion=confusion)
+        return acc if counts is not None else [int(v) for v in acc.tolist()]
+
 
 def _hetero_layers(module, node_types):
     """LayerDesc list from ``module.convs`` (a ModuleList of HeteroConv containers)."""

@@ -92,6 +92,8 @@ class HeterogeneousNeuralTreeNetwork(_NativeModule):
         self.post_mp = LeafPool(aggr="mean")
         self._init_native()
 
+    _ROOM_LABELS = "room_virtual"  # BaseTrainingJob.test reads the labels of the pooled nodes (base_training_job.py:283-291)
+
     def _build_native(self) -> NativeNet:
         layers = _hetero_layers(self, HTREE_NODE_TYPES)
         two = self.classification_task == "all"

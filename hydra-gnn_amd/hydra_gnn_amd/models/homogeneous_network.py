@@ -199,6 +199,36 @@ class HomogeneousNetwork(_NativeModule):
         head = lambda lin, rows: ops.bias_act_drop(ops.project(rows, lin.weight), lin.bias)
         return head(self.post_mp_room, x[room_mask, :]), head(self.post_mp_object, x[object_mask, :])
 
+    def _op_states(self, data):
+        """final states of every node on the op path (GCN / GIN), before the readout"""
+        return self._op_layers(data.x, ops.GraphPlan(data.edge_index, data.x.size(0)))
+
+    def count_correct_rooms(self, data, counts=None, confusion=None, ignored_label=25):
+        """The per-batch arithmetic of ``BaseTrainingJob.test`` (base_training_job.py:269-313) for the room task: eval-mode
+        forward, ``argmax(dim=1)`` of the room rows, compared with ``data.y[data.room_mask]`` where the label is not
+        ``ignored_label``.  The native output has a row per node, so ``data.room_mask`` is the kernel's row filter (no
+        compaction).  SAGE / GAT: ``hmp_net_count_correct_rooms``; GCN / GIN: the op-by-op forward, then
+        ``ops.count_correct_rows``.  With ``counts`` (device int64[2]) {correct, total} are ADDED to it without a sync; without,
+        returns the two ints of this batch.  ``confusion`` (device int64 [C, C]) receives ``[label, pred] += 1``."""
+        self._room_task("count_correct_rooms")
+        acc = counts
+        if acc is None:
+            acc = torch.zeros(2, dtype=torch.int64, device=data.x.device)
+        if not self.op_path:
+            self.native().count_correct_rooms(self._view(data), data.y, acc, ignored_label, members=data.room_mask,
+                                              confusion=confusion)
+        else:
+            was = self.training
+            self.train(False)
+            try:
+                with torch.no_grad():
+                    x = self._op_states(data)
+            finally:
+                if was:
+                    self.train(True)
+            ops.count_correct_rows(x, data.y, acc, ignored_label, members=data.room_mask, confusion=confusion)
+        return acc if counts is not None else [int(v) for v in acc.tolist()]
+
     def predict(self, data):
         if self.classification_task != "room":
             raise NotImplementedError("predict() returns room labels (the server's task)")
@@ -209,9 +239,7 @@ class HomogeneousNetwork(_NativeModule):
 
     def forward(self, data):
         if self.op_path:
-            plan = ops.GraphPlan(data.edge_index, data.x.size(0))
-            x = self._op_layers(data.x, plan)
-            return self._op_heads(x, data.room_mask, ~data.room_mask)
+            return self._op_heads(self._op_states(data), data.room_mask, ~data.room_mask)
         out = self._run(_HomoView(data))
         out = out[:, : self.native().layers[-1].out_dims[_NODE]]
         return self._op_heads(out, data.room_mask, ~data.room_mask)

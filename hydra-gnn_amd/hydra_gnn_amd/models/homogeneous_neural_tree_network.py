@@ -126,15 +126,17 @@ class HomogeneousNeuralTreeNetwork(HomogeneousNetwork):
     def _view(self, data):
         return _HtreeView(data, self.pre_mp is not None)
 
+    def _op_states(self, data):
+        x = data.x
+        if self.pre_mp is not None:
+            x = self.native().forward(_InitView(data), self.training, self._seed, 0)[:, : self.input_dim]
+        n = data.x.size(0)
+        x = self._op_layers(x, ops.GraphPlan(data.edge_index, n), batch_norm=False)
+        return ops.segment_mean(x, ops.GraphPlan(data.pool_edge_index, n))
+
     def forward(self, data):
         if self.op_path:
-            x = data.x
-            if self.pre_mp is not None:
-                x = self.native().forward(_InitView(data), self.training, self._seed, 0)[:, : self.input_dim]
-            n = data.x.size(0)
-            x = self._op_layers(x, ops.GraphPlan(data.edge_index, n), batch_norm=False)
-            x = ops.segment_mean(x, ops.GraphPlan(data.pool_edge_index, n))
-            return self._op_heads(x, data.room_mask, getattr(data, "object_mask", None))
+            return self._op_heads(self._op_states(data), data.room_mask, getattr(data, "object_mask", None))
         out = self._run(_HtreeView(data, self.pre_mp is not None))
         out = out[:, : self.native().layers[-1].out_dims[_NODE]]
         return self._op_heads(out, data.room_mask, getattr(data, "object_mask", None))  # reference :96-109

@@ -274,3 +274,53 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().hmp_argmax_rows(x.data_ptr(), x.stride(0), x.size(0), x.size(1), out.data_ptr(), _lib.stream_ptr()))
     return out
+
+
+def check_count_buffers(counts: torch.Tensor, confusion: Optional[torch.Tensor], n_classes: int, device) -> None:
+    """the accumulators of the room-task validation count: ``counts`` contiguous int64[>= 2], ``confusion`` (optional) contiguous
+    int64 with ``n_classes ** 2`` elements, both on ``device``"""
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.numel() < 2 or not counts.is_contiguous()
+            or counts.device != device):
+        raise _lib.HydraMPError(f"counts must be a contiguous int64[2] tensor on {device}")
+    if confusion is not None and (confusion.dtype != torch.int64 or confusion.numel() != n_classes * n_classes
+                                  or not confusion.is_contiguous() or confusion.device != device):
+        raise _lib.HydraMPError(f"confusion must be a contiguous int64[{n_classes} * {n_classes}] tensor on {device}")
+
+
+def row_members(members: Optional[torch.Tensor], n_rows: int, device) -> Optional[torch.Tensor]:
+    """``members`` as the kernels read it: a contiguous bool tensor of ``n_rows`` entries on ``device`` (one byte per row)"""
+    if members is None:
+        return None
+    if not isinstance(members, torch.Tensor) or members.dtype != torch.bool:
+        raise _lib.HydraMPError("members must be a bool tensor (one entry per row)")
+    if members.device != device:
+        raise _lib.HydraMPError(f"members is on {members.device}, the rows are on {device}")
+    if members.numel() != n_rows:
+        raise _lib.HydraMPError(f"members: {members.numel()} entries for {n_rows} rows")
+    return members.contiguous()
+
+
+def count_correct_rows(logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, ignored_label: int = 25,
+                       members: Optional[torch.Tensor] = None, confusion: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-batch arithmetic of ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) on the device
+    (``hmp_count_correct_rows``): ``pred = logits.argmax(dim=1)`` (first maximum); a row counts iff ``members[row]`` (all rows
+    when None) and ``labels[row] != ignored_label``.  ADDS {correct, total} to ``counts`` (int64[2]) and, when given,
+    ``confusion[label, pred] += 1`` to ``confusion`` (int64 [C, C] or [C * C]).  Returns ``counts``; nothing synchronises."""
+    _dev(logits, "logits")
+    logits = _rows(logits)
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise _lib.HydraMPError(f"logits must be [rows, classes >= 1], got {tuple(logits.shape)}")
+    n, n_classes = logits.size(0), logits.size(1)
+    dev = logits.device
+    if not isinstance(labels, torch.Tensor) or labels.device != dev or labels.numel() != n:
+        raise _lib.HydraMPError(f"labels must hold {n} entries on {dev}")
+    labels = labels.to(torch.int64).contiguous()
+    check_count_buffers(counts, confusion, n_classes, dev)
+    members = row_members(members, n, dev)
+    if n:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hmp_count_correct_rows(
+                logits.data_ptr(), logits.stride(0) if n > 1 else n_classes, n, n_classes, labels.data_ptr(),
+                members.data_ptr() if members is not None else None, int(ignored_label), counts.data_ptr(),
+                confusion.data_ptr() if confusion is not None else None, _lib.stream_ptr()))
+    return counts

@@ -31,7 +31,8 @@ extern "C" {
  *    hmp_net_count_correct2: the fused step of the two-headed task
  *    ABI-4-compatible additions (nothing above changed layout): hmp_linear_heads (hmp_sizeof 8), hmp_linear_head_targets
  *    (hmp_sizeof 9), hmp_net_set_linear_heads / hmp_net_step_heads_fwd_bwd / hmp_net_step_heads_fused /
- *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state */
+ *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state;
+ *    hmp_count_correct_rows / hmp_net_count_correct_rooms: the device-side validation count of the room task */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -178,6 +179,14 @@ int hmp_masked_ce(const float* d_logits, int32_t ldl, int32_t n_rows, int32_t n_
 /* out[r] = argmax_c x[r, c] (first maximum): the `.argmax(dim=1)` of the inference loop
  * (bin/room_classification_server:286) on the executor's output, so only the labels cross PCIe */
 int hmp_argmax_rows(const float* d_x, int32_t ldx, int32_t n_rows, int32_t n_cols, int64_t* d_out, void* stream);
+/* validation count of the room task: the per-batch arithmetic of BaseTrainingJob.test (base_training_job.py:269-313) without a
+ * sync or a D2H.  pred[r] = first-maximum argmax of d_logits[r, 0:n_classes) (hmp_argmax_rows's rule); row r counts iff
+ * (d_members == NULL || d_members[r]) && d_labels[r] != ignored_label (d_members: one byte per row, a torch bool tensor).
+ * ACCUMULATES {correct, total} into d_counts (device int64[2]) and, if d_confusion != NULL, confusion[label][pred] += 1 into the
+ * device int64 [n_classes][n_classes] matrix.  A counted label outside [0, n_classes) adds to total only (pred.eq(label) is
+ * false) and never to the matrix.  One launch; n_rows == 0 launches nothing; nothing synchronises. */
+int hmp_count_correct_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
+                           const uint8_t* d_members, int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream);
 /* d_count: device float holding the valid-label count (grad_scale = 1/max(count,1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
@@ -389,6 +398,14 @@ int hmp_net_step_heads_fused(hmp_net* net, const hmp_batch* batch, const hmp_lin
  * d_counts (device int64[4]); nothing synchronises. */
 int hmp_net_count_correct_heads(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, const float* d_params,
                                 int64_t* d_counts, void* stream);
+/* Room task (one output, no aux readout, no linear heads): the per-batch arithmetic of BaseTrainingJob.test
+ * (base_training_job.py:269-313).  Eval-mode forward (no dropout, no fused CE), then ONE hmp_count_correct_rows launch on the
+ * program's output with the labels batch->d_labels over batch->n_out rows, the classes = the output width, the optional row
+ * filter d_members [n_out] and ignored_label.  ACCUMULATES {correct, total} into d_counts (device int64[2]) and, if d_confusion !=
+ * NULL, the [classes][classes] confusion matrix.  A batch without labels and two-headed nets (hmp_net_count_correct2 /
+ * hmp_net_count_correct_heads) are refused.  The activations of the last forward are overwritten; nothing synchronises. */
+int hmp_net_count_correct_rooms(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
+                                int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
@@ -448,7 +465,8 @@ int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const int64_t* d_ed
  *           (row_bytes == 0: int64 [2][src_total], positioned by `slot`, endpoints shifted by `slot_src` / `slot_dst`).
  * hmp_collator_run: h_sel [B] graph ids (host), d_dst[i] / dst_capacity[i] per item (rows resp. edges), h_totals[slot] receives
  * the batch's node / edge totals (the shapes of the outputs).  No allocation or synchronisation in the steady state.
- * (<= 356 words of offsets + selection travel in the kernel's argument block, larger batches through a pinned ring.) */
+ * (<= 336 words of offsets + selection travel in the kernel's argument block, larger batches through a pinned ring;
+ * at most 24 slots and 24 items.) */
 typedef struct hmp_collate_item {
   const void* d_src;
   const int64_t* d_ptr;      /* device copy of the item's [G + 1] offsets */
