@@ -474,6 +474,17 @@ struct HeadTail {
   int drop_on;
   DropCfg drop;             // quad numbering row * ceil(classes / 4) + col / 4
   int block_start;
+  // pooled heads (pool_tail_*_launch, hmp_net_set_head_pools): the CE / count rows are the n_pool rows of the pool edge type's
+  // destination, each the mean of dropout(act(z)) over its leaves.  rowptr / col: the pool plan's CSR (by destination), t_rowptr /
+  // t_col: its CSC (by leaf); rowptr null = identity (an unpooled head: row v's only leaf is v).  labels, mask and row_lv are per
+  // pooled row; dpool [n_pool][ldp] is d loss / d pooled * (1 / deg), read back by the leaf-gradient launch.
+  const int* rowptr;
+  const int* col;
+  const int* t_rowptr;
+  const int* t_col;
+  int n_pool;
+  float* dpool;
+  int ldp;
 };
 struct TailArgs {
   int n;
@@ -484,6 +495,10 @@ struct TailArgs {
 };
 int tail_ce_launch(TailArgs& a, hipStream_t st);
 int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st);
+constexpr int POOL_TAIL_MAX_CLASSES = 256;  // pooled rows are held in registers: at most 4 quads per lane
+int pool_tail_ce_launch(TailArgs& a, hipStream_t st);
+int pool_tail_grad_launch(TailArgs& a, hipStream_t st);
+int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st);
 // Two learned linear heads over one final state (heads.hip): y = dropout(act(z)), logits_h = y W_h^T + b_h on the rows of head h,
 // masked CE of both heads with d loss / d z written to `grad` and per-workgroup partial dW / db slabs (fused step), or the
 // first-maximum argmax of both heads compared with the labels (accuracy count, eval mode).

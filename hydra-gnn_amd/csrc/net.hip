@@ -179,6 +179,11 @@ struct hmp_net {
   int64_t head_slab_off = 0, head_slab_stride = 0;
   int head_ld_slab = 0;
   int head_blocks_now = 0;
+  // pooled heads (hmp_net_set_head_pools): the pool edge type of each head (-1: unpooled), d loss / d pooled per head (the
+  // workspace's [cap rows of the pool destination][fpad(classes)] scratch of the pooled CE launch)
+  bool has_pools = false;
+  int head_pool[2] = {-1, -1};
+  float* d_dpool[2] = {nullptr, nullptr};
   hipStream_t side[2] = {nullptr, nullptr};
   hipEvent_t evs[32];
   int n_evs = 0, ev_i = 0;
@@ -204,6 +209,12 @@ void read_env(hmp_net* n) {
 }
 
 inline int fpad(int f) { return align4(f); }
+
+// the node type of head h's final state, and the type whose rows carry its labels (the pool destination of a pooled head)
+inline int head_type(const hmp_net* n, int h) { return h == 0 ? n->spec.readout_type : n->spec.aux_readout_type; }
+inline int label_type(const hmp_net* n, int h) {
+  return n->head_pool[h] >= 0 ? n->spec.edge_dst[n->head_pool[h]] : head_type(n, h);
+}
 
 int build_layout(hmp_net* n) {
   const hmp_net_spec& S = n->spec;
@@ -636,7 +647,15 @@ size_t carve(hmp_net* n, char* base, const int32_t* cn, const int64_t* ce) {
   n->d_out = (float*)take((size_t)cap_out * n->out_ld * 4);
   n->d_gout = (float*)take((size_t)cap_out * n->out_ld * 4);
   const int cap_aux = S.aux_readout_type >= 0 ? cn[S.aux_readout_type] : 0;  // the aux rows follow the readout rows
-  n->d_row_lv = (float*)take((size_t)(cap_out + cap_aux) * 2 * 4);
+  int64_t lv_rows = cap_out + cap_aux;
+  n->d_dpool[0] = n->d_dpool[1] = nullptr;
+  if (n->has_pools) {  // pooled heads: one {loss, valid} per label row, the aux head's after the readout head's
+    const int64_t pr = (int64_t)cn[label_type(n, 0)] + cn[label_type(n, 1)];
+    lv_rows = pr > lv_rows ? pr : lv_rows;
+    for (int h = 0; h < 2; ++h)
+      n->d_dpool[h] = (float*)take((size_t)cn[label_type(n, h)] * n->ld[n->L][head_type(n, h)] * 4);
+  }
+  n->d_row_lv = (float*)take((size_t)lv_rows * 2 * 4);
   n->d_iota = nullptr; n->d_ones = nullptr; n->d_sadd = nullptr;
   if (n->any_agg_first) {
     int mx = 1;
@@ -1125,7 +1144,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       a.mean = 1;
       a.state = n->d_state;
       // two-headed step: both heads' tail (act, dropout) and masked CE in this epilogue when it can hold both rows' widths
-      const bool tail_epi = l == n->L - 1 && n->tgt && n->fuse_now && fpad(Ls.out_dim[S.readout_type]) <= 256 &&
+      const bool tail_epi = l == n->L - 1 && n->tgt && !n->has_pools && n->fuse_now && fpad(Ls.out_dim[S.readout_type]) <= 256 &&
                             fpad(Ls.out_dim[S.aux_readout_type]) <= 256;
       for (int t = 0; t < n->T; ++t) {
         if (Y.roff[t] < 0 || b->n_nodes[t] == 0) continue;
@@ -1907,10 +1926,49 @@ int check_targets(const hmp_net* n, const hmp_batch* b, const hmp_head_targets* 
   HMP_CHECK_ARG(S.aux_readout_type >= 0, "%s: the net has one output (aux_readout_type < 0): use the single-head entry", who);
   HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
                 "%s: spec tail_act %d / tail_dropout %g", who, S.tail_act, (double)S.tail_dropout);
-  const int ts[2] = {S.readout_type, S.aux_readout_type};
-  for (int h = 0; h < 2; ++h)
-    HMP_CHECK_ARG(b->n_nodes[ts[h]] == 0 || tg->d_labels[h] != nullptr, "%s: labels of head %d required", who, h);
+  for (int h = 0; h < 2; ++h)  // one label per row of the head's label type (the pool destination of a pooled head)
+    HMP_CHECK_ARG(b->n_nodes[label_type(n, h)] == 0 || tg->d_labels[h] != nullptr, "%s: labels of head %d required", who, h);
   return HMP_OK;
+}
+
+// the rows of one head for the pooled tail launches (semisup.hip): final state of the head's type, its pool plan (none: identity),
+// labels / mask / {loss, valid} per pooled row
+void add_pool(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
+  const hmp_net_spec& S = n->spec;
+  const int t = head_type(n, head), lt = label_type(n, head);
+  if (b->n_nodes[t] == 0 && b->n_nodes[lt] == 0) return;
+  HeadTail& T = ta.h[ta.n++];
+  memset(&T, 0, sizeof(T));
+  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
+  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
+  T.n_pool = b->n_nodes[lt];
+  if (n->head_pool[head] >= 0) {
+    const hmp_plan& P = n->plan[n->head_pool[head]];
+    T.rowptr = P.d_rowptr; T.col = P.d_col; T.t_rowptr = P.d_t_rowptr; T.t_col = P.d_t_col;
+  }
+  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
+  T.slot = head;
+  if (!ce) return;
+  T.grad = n->G[n->L][t]; T.ldg = n->ld[n->L][t];
+  T.dpool = n->d_dpool[head]; T.ldp = n->ld[n->L][t];
+  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_nodes[label_type(n, 0)]);
+  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
+}
+
+// pooled heads: the CE over the pooled rows of both heads (one launch), then d loss / d z of every leaf row (one launch) -> G[L][t]
+int pool_tail_ce(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int64_t ignored, hipStream_t st) {
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = n->spec.tail_act; ta.ignored = ignored; ta.state = n->d_state;
+  for (int h = 0; h < 2; ++h) add_pool(n, b, tg, h, true, ta);
+  if (ta.n == 0) return HMP_OK;
+  {
+    Scope sc(n, KC_LOSS, st);
+    HMP_TRY(pool_tail_ce_launch(ta, st));
+  }
+  Scope sc(n, KC_LOSS, st);
+  return pool_tail_grad_launch(ta, st);
 }
 
 }  // namespace
@@ -1930,6 +1988,23 @@ extern "C" int hmp_net_step2_fwd_bwd(hmp_net* n, const hmp_batch* batch, const h
   const int rf = forward_impl(n, batch, d_params, st);
   n->tgt = nullptr;
   int r = rf;
+  if (r == HMP_OK && n->has_pools) {
+    // pooled heads: both gradients land in G[L][*] (the readout's is handed to the backward as its output gradient)
+    r = pool_tail_ce(n, batch, targets, args->ignored_label, st);
+    if (r == HMP_OK) {
+      n->fin_loss = true;
+      n->fin_rows = batch->n_nodes[label_type(n, 0)] + batch->n_nodes[label_type(n, 1)];
+      n->aux_g_ready = true;
+      const int rt = n->spec.readout_type;
+      r = backward_impl(n, n->G[n->L][rt], n->ld[n->L][rt], d_grads, d_params, nullptr, st);
+      n->aux_g_ready = false;
+      n->fin_rows = 0;
+      n->fin_loss = false;
+    }
+    n->d_step = &n->d_state->step;
+    n->step_dev = false;
+    return r;
+  }
   if (r == HMP_OK) {  // the heads the last epilogue did not serve: one stand-alone launch over their rows
     TailArgs ta;
     memset(&ta, 0, sizeof(ta));
@@ -1985,10 +2060,45 @@ extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const 
   TailArgs ta;
   memset(&ta, 0, sizeof(ta));
   ta.act = n->spec.tail_act; ta.state = n->d_state;
-  for (int h = 0; h < 2; ++h) add_tail(n, batch, targets, h, false, ta);
+  for (int h = 0; h < 2; ++h) {
+    if (n->has_pools) add_pool(n, batch, targets, h, false, ta);
+    else add_tail(n, batch, targets, h, false, ta);
+  }
   if (ta.n == 0) return HMP_OK;
   Scope sc(n, KC_LOSS, st);
+  if (n->has_pools) return pool_tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
   return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
+}
+
+extern "C" int hmp_net_set_head_pools(hmp_net* n, int32_t pool_edge_type_readout, int32_t pool_edge_type_aux) {
+  HMP_CHECK_ARG(n, "hmp_net_set_head_pools: null net");
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(!n->has_pools, "hmp_net_set_head_pools: the head pools are already set");
+  HMP_CHECK_ARG(!n->bound, "hmp_net_set_head_pools: call before the first workspace bind");
+  HMP_CHECK_ARG(S.aux_readout_type >= 0 && S.pool_edge_type < 0 && !n->has_heads,
+                "hmp_net_set_head_pools: needs a two-headed net (aux_readout_type, no pool_edge_type, no linear heads)");
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
+                "hmp_net_set_head_pools: spec tail_act %d / tail_dropout %g", S.tail_act, (double)S.tail_dropout);
+  const int ets[2] = {pool_edge_type_readout, pool_edge_type_aux};
+  for (int h = 0; h < 2; ++h) {
+    const int e = ets[h], t = head_type(n, h);
+    HMP_CHECK_ARG(e >= -1 && e < n->ET, "hmp_net_set_head_pools: head %d: edge type %d (-1 = unpooled, < %d)", h, e, n->ET);
+    HMP_CHECK_ARG(n->dim[n->L][t] >= 1 && n->dim[n->L][t] <= POOL_TAIL_MAX_CLASSES,
+                  "hmp_net_set_head_pools: head %d has %d classes (1 .. %d)", h, n->dim[n->L][t], POOL_TAIL_MAX_CLASSES);
+    if (e < 0) continue;
+    const int d = S.edge_dst[e];
+    HMP_CHECK_ARG(S.edge_src[e] == t, "hmp_net_set_head_pools: head %d: edge type %d starts at node type %d, not the head's %d", h,
+                  e, S.edge_src[e], t);
+    HMP_CHECK_ARG(d != S.readout_type && d != S.aux_readout_type, "hmp_net_set_head_pools: head %d pools into a readout type", h);
+    const hmp_layer_spec& Ls = S.layers[n->L - 1];
+    for (int c = 0; c < Ls.n_convs; ++c)
+      HMP_CHECK_ARG(Ls.convs[c].dst != d, "hmp_net_set_head_pools: head %d: node type %d receives a conv in the last layer", h, d);
+  }
+  if (ets[0] < 0 && ets[1] < 0) return HMP_OK;  // nothing pooled: the ordinary two-head step
+  n->head_pool[0] = ets[0];
+  n->head_pool[1] = ets[1];
+  n->has_pools = true;
+  return HMP_OK;
 }
 
 extern "C" int hmp_net_set_linear_heads(hmp_net* n, const hmp_linear_heads* h) {

@@ -156,6 +156,7 @@ SIGNATURES = {
     "hmp_net_step2_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_count_correct2": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP]),
     "hmp_net_set_linear_heads": (C.c_int, [_VP, C.POINTER(LinearHeads)]),
+    "hmp_net_set_head_pools": (C.c_int, [_VP, _I32, _I32]),
     "hmp_net_step_heads_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_step_heads_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP, _VP,
                                            C.POINTER(TrainArgs), _VP]),

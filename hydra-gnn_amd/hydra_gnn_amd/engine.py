@@ -70,7 +70,7 @@ class NativeNet:
     def __init__(self, node_types: Sequence[str], in_dims: Dict[str, int], edge_types: Sequence[EdgeType],
                  layers: List[LayerDesc], readout: str, pool_edge_type: Optional[EdgeType] = None,
                  count_types: Sequence[str] = (), aux_readout: Optional[str] = None, tail: Optional[Tuple[int, float]] = None,
-                 heads: Optional[Sequence[nn.Linear]] = None):
+                 heads: Optional[Sequence[nn.Linear]] = None, head_pools: Optional[Sequence[Optional[EdgeType]]] = None):
         self.node_types = list(node_types)
         self.edge_types = [tuple(e) for e in edge_types]
         self.in_dims = dict(in_dims)
@@ -89,6 +89,14 @@ class NativeNet:
         assert self.heads is None or (len(self.heads) == 2 and aux_readout is None)
         self.head_params: List[nn.Parameter] = []
         self.pool_edge_type = tuple(pool_edge_type) if pool_edge_type is not None else None
+        # two-headed nets whose heads read a LeafPool of their final state (heterogeneous_neural_tree_network.py:186-205): the pool
+        # edge type of (readout, aux), None = unpooled; labels and masks then have one row per node of the edge type's destination
+        self.head_pools = None
+        if head_pools is not None:
+            assert aux_readout is not None and len(head_pools) == 2
+            self.head_pools = tuple(tuple(e) if e is not None else None for e in head_pools)
+            for e, t in zip(self.head_pools, (readout, aux_readout)):
+                assert e is None or (e in [tuple(x) for x in edge_types] and e[0] == t)
         # node types without features whose node COUNT matters (virtual pool targets)
         self.count_types = list(count_types)
         assert len(self.node_types) <= _lib.MAX_NODE_TYPES and len(self.edge_types) <= _lib.MAX_EDGE_TYPES
@@ -266,7 +274,15 @@ class NativeNet:
                 _lib.check(self._lib.hmp_net_set_compute(h, 1))
             if self.heads is not None:
                 _lib.check(self._lib.hmp_net_set_linear_heads(h, C.byref(self._linear_heads())))
+            if self.head_pools is not None:
+                ets = [self.edge_types.index(e) if e is not None else -1 for e in self.head_pools]
+                _lib.check(self._lib.hmp_net_set_head_pools(h, *ets))
         return self._handle
+
+    def head_label_types(self) -> Tuple[str, str]:
+        """node types whose rows carry the labels of the (readout, aux) heads: the pool destination of a pooled head"""
+        pools = self.head_pools or (None, None)
+        return tuple(e[2] if e is not None else t for e, t in zip(pools, (self.readout, self.aux_readout)))
 
     def _linear_heads(self) -> _lib.LinearHeads:
         hd = _lib.LinearHeads()
@@ -624,7 +640,7 @@ def _head_targets(net: NativeNet, h: _BatchHolder, labels, masks) -> _lib.HeadTa
     if len(labels) != 2 or (masks is not None and len(masks) != 2):
         raise _lib.HydraMPError("labels / masks: one tensor per head, (readout, aux)")
     tg = _lib.HeadTargets()
-    for i, t in enumerate((net.readout, net.aux_readout)):
+    for i, t in enumerate(net.head_label_types()):
         n = h.n_nodes[net.node_types.index(t)]
         lab = labels[i]
         _require_cuda(lab, f"labels[{i}]")

@@ -119,7 +119,40 @@ def _hetero_layers(module, node_types):
     return layers
 
 
-class HeterogeneousNetwork(_NativeModule):
+class _HeteroTwoHead(_NativeModule):
+    """The two-headed task's native entries, shared by the heterogeneous models built with ``output_dim_dict``
+    (HeterogeneousNetwork: the final states; HeterogeneousNeuralTreeNetwork: their LeafPool, ``NativeNet.head_pools``)."""
+
+    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
+        """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body), see
+        engine.TwoHeadTrainStep: ``step(data, labels=(y_rooms, y_objects), masks=(m_rooms, m_objects))``.  The dropout seed is
+        the module's, so the masks are the ones ``forward()`` draws at the same step number.  HeterogeneousNeuralTreeNetwork:
+        labels and masks of the pooled rows, ``(room_virtual, object_virtual)``."""
+        from ..engine import TwoHeadTrainStep
+
+        if getattr(self, "classification_task", "room") != "all":
+            raise _lib.HydraMPError("semisupervised_step: the model has one output (build it with output_dim_dict for the "
+                                    "two-headed task); use train_step()")
+        kw.setdefault("seed", self._seed)
+        return TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
+
+    def count_correct(self, data, labels, masks=None, counts=None):
+        """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
+        forward, argmax of both heads, compared with ``labels = (y_rooms, y_objects)`` under ``masks``.  With ``counts`` (device
+        int64[4]) the batch's {correct_rooms, total_rooms, correct_objects, total_objects} are ADDED to it on the device and the
+        tensor is returned without a sync (a loader loop reads it once per pass); without, returns the four ints of this batch.
+        The H-tree model's heads are its pooled rows: labels and masks of ``room_virtual`` / ``object_virtual``."""
+        net = self.native()
+        if net.aux_readout is None:
+            raise _lib.HydraMPError("count_correct: the model has one output (build it with output_dim_dict)")
+        acc = counts
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+        net.count_correct(data, labels, masks, acc)
+        return acc if counts is not None else [int(v) for v in acc.tolist()]
+
+
+class HeterogeneousNetwork(_HeteroTwoHead):
     def __init__(
         self,
         input_dim_dict,
@@ -180,29 +213,3 @@ class HeterogeneousNetwork(_NativeModule):
         last = self.num_layers - 1
         return (self._tail_act_drop(rooms[:, : dims["rooms"]], self._drop_stream(last, "rooms")),
                 self._tail_act_drop(objects[:, : dims["objects"]], self._drop_stream(last, "objects")))
-
-    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
-        """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body), see
-        engine.TwoHeadTrainStep: ``step(data, labels=(y_rooms, y_objects), masks=(m_rooms, m_objects))``.  The dropout seed is
-        the module's, so the masks are the ones ``forward()`` draws at the same step number."""
-        from ..engine import TwoHeadTrainStep
-
-        if getattr(self, "classification_task", "room") != "all":
-            raise _lib.HydraMPError("semisupervised_step: the model has one output (build it with output_dim_dict for the "
-                                    "two-headed task); use train_step()")
-        kw.setdefault("seed", self._seed)
-        return TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
-
-    def count_correct(self, data, labels, masks=None, counts=None):
-        """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
-        forward, argmax of both heads, compared with ``labels = (y_rooms, y_objects)`` under ``masks``.  With ``counts`` (device
-        int64[4]) the batch's {correct_rooms, total_rooms, correct_objects, total_objects} are ADDED to it on the device and the
-        tensor is returned without a sync (a loader loop reads it once per pass); without, returns the four ints of this batch."""
-        net = self.native()
-        if net.aux_readout is None:
-            raise _lib.HydraMPError("count_correct: the model has one output (build it with output_dim_dict)")
-        acc = counts
-        if acc is None:
-            acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
-        net.count_correct(data, labels, masks, acc)
-        return acc if counts is not None else [int(v) for v in acc.tolist()]

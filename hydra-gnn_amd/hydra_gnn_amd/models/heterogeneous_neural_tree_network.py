@@ -14,11 +14,14 @@ import torch.nn as nn
 
 from ..data import HTREE_EDGE_TYPES, HTREE_INIT_EDGE_TYPES, HTREE_NODE_TYPES
 from ..engine import LayerDesc, NativeNet
-from .._lib import ACT_NONE
-from .heterogeneous_network import _NativeModule, _hetero_layers
+from .._lib import ACT_ELU, ACT_NONE, ACT_RELU
+from .heterogeneous_network import _HeteroTwoHead, _hetero_layers
 from .utils import GATConv, HeteroConv, build_GAT_hetero_conv, build_hetero_conv
 
 POOL_EDGE_TYPE = ("room", "r_to_rv", "room_virtual")
+# two-headed task: the LeafPool of each head (room, object), reference :186-205
+HEAD_POOL_EDGE_TYPES = [POOL_EDGE_TYPE, ("object", "o_to_ov", "object_virtual")]
+VIRTUAL_TYPES = ["room_virtual", "object_virtual"]
 
 
 class LeafPool(nn.Module):
@@ -29,7 +32,7 @@ class LeafPool(nn.Module):
         assert aggr == "mean"
 
 
-class HeterogeneousNeuralTreeNetwork(_NativeModule):
+class HeterogeneousNeuralTreeNetwork(_HeteroTwoHead):
     def __init__(
         self,
         input_dim_dict,
@@ -54,7 +57,7 @@ class HeterogeneousNeuralTreeNetwork(_NativeModule):
             output_dim_dict = {node_type: output_dim for node_type in HTREE_NODE_TYPES}
         else:
             assert output_dim_dict is not None
-            self.classification_task = "all"  # two outputs (reference :186-205): second readout + LeafPool per head on the operators
+            self.classification_task = "all"  # two outputs (reference :186-205): second readout + a LeafPool per head
         self.num_layers = num_layers if conv_block[:3] != "GAT" else len(GAT_heads)
         self.dropout = dropout
 
@@ -97,12 +100,19 @@ class HeterogeneousNeuralTreeNetwork(_NativeModule):
     def _build_native(self) -> NativeNet:
         layers = _hetero_layers(self, HTREE_NODE_TYPES)
         two = self.classification_task == "all"
-        pool = dict(readout="room", aux_readout="object") if two else dict(readout="room", pool_edge_type=POOL_EDGE_TYPE)
-        pool_et = [] if two else [POOL_EDGE_TYPE]
+        if two:
+            # both heads' LeafPool is the executor's (head_pools: pooled CE / count of the fused step); the pool edges carry no conv,
+            # the virtual node types only their node count (without pre_mp) -- message passing stays on HTREE_EDGE_TYPES
+            tail = (ACT_ELU if self.conv_block[:3] == "GAT" else ACT_RELU, float(self.dropout))
+            pool = dict(readout="room", aux_readout="object", tail=tail, head_pools=HEAD_POOL_EDGE_TYPES)
+            pool_et = list(HEAD_POOL_EDGE_TYPES)
+        else:
+            pool = dict(readout="room", pool_edge_type=POOL_EDGE_TYPE)
+            pool_et = [POOL_EDGE_TYPE]
         if self.pre_mp is None:
             if two:
-                return NativeNet(list(HTREE_NODE_TYPES), {t: self.input_dim_dict[t] for t in HTREE_NODE_TYPES},
-                                 list(HTREE_EDGE_TYPES), layers, **pool)
+                return NativeNet(list(HTREE_NODE_TYPES) + VIRTUAL_TYPES, {t: self.input_dim_dict[t] for t in HTREE_NODE_TYPES},
+                                 list(HTREE_EDGE_TYPES) + pool_et, layers, count_types=VIRTUAL_TYPES, **pool)
             node_types = list(HTREE_NODE_TYPES) + ["room_virtual"]
             in_dims = {t: self.input_dim_dict[t] for t in HTREE_NODE_TYPES}
             return NativeNet(node_types, in_dims, list(HTREE_EDGE_TYPES) + [POOL_EDGE_TYPE], layers,
@@ -114,7 +124,7 @@ class HeterogeneousNeuralTreeNetwork(_NativeModule):
         leaves = [t for t in HTREE_NODE_TYPES if t not in out_dims]
         out_dims.update({t: self.input_dim_dict[t] for t in leaves})
         init = LayerDesc(convs, out_dims, ACT_NONE, 0.0, group_mean=(self.pre_mp.aggr == "mean"), passthrough=leaves)
-        node_types = list(HTREE_NODE_TYPES) + ["room_virtual", "object_virtual"]
+        node_types = list(HTREE_NODE_TYPES) + VIRTUAL_TYPES
         in_dims = {t: self.input_dim_dict[t] for t in node_types}
         return NativeNet(node_types, in_dims, list(HTREE_EDGE_TYPES) + pool_et + list(HTREE_INIT_EDGE_TYPES),
                          [init] + layers, **pool)

@@ -255,6 +255,32 @@ def htree_batch(batch_size: int = 128, seed: int = BASE_SEED + 4, fixture: Optio
     return collate([htree_graph(npz, i % n, rng) for i in range(batch_size)])
 
 
+def semisupervised_htree_batch(n_graphs: int, seed: int, relative_pos: bool = False) -> HeteroData:
+    """Batch of the two-headed task on H-trees (``HeterogeneousNeuralTreeNetwork(output_dim_dict=...)``,
+    ``SemiSupervisedTrainingJob`` on Stanford3DSG): the committed fixture's topologies as in ``htree_batch``, ``room_virtual.y`` in
+    0..14 and ``object_virtual.y`` in 0..34, and a seeded per-node split of BOTH virtual types into disjoint ``train_mask`` (60 %),
+    ``val_mask`` (20 %) and ``test_mask`` (20 %).  ``relative_pos``: 3-d ``edge_attr`` (destination minus source xyz, the leading
+    columns of ``x``) on the message-passing edge types, for GAT_edge; the pool edges carry none."""
+    npz = np.load(HTREE_FIXTURE)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = int(npz["n_graphs"])
+    graphs = [htree_graph(npz, i % n, rng) for i in range(n_graphs)]
+    for g in graphs:
+        for t, classes in (("room_virtual", 15), ("object_virtual", 35)):
+            g[t].y = torch.from_numpy(rng.integers(0, classes, size=int(g[t].num_nodes)).astype(np.int64))
+        if relative_pos:
+            for src, rel, dst in HTREE_EDGE_TYPES:
+                ei = g[src, rel, dst].edge_index
+                g[src, rel, dst].edge_attr = (g[dst].x[ei[1], :3] - g[src].x[ei[0], :3]).contiguous()
+    batch = collate(graphs)
+    for t in ("room_virtual", "object_virtual"):
+        u = torch.from_numpy(rng.random(int(batch[t].y.numel())))
+        batch[t].train_mask = u < 0.6
+        batch[t].val_mask = (u >= 0.6) & (u < 0.8)
+        batch[t].test_mask = u >= 0.8
+    return batch
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # config 2, second input (SURVEY 8(d)): the reference's real scene graph replicated x B
 # ---------------------------------------------------------------------------------------------------------------------

@@ -32,7 +32,8 @@ extern "C" {
  *    ABI-4-compatible additions (nothing above changed layout): hmp_linear_heads (hmp_sizeof 8), hmp_linear_head_targets
  *    (hmp_sizeof 9), hmp_net_set_linear_heads / hmp_net_step_heads_fwd_bwd / hmp_net_step_heads_fused /
  *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state;
- *    hmp_count_correct_rows / hmp_net_count_correct_rooms: the device-side validation count of the room task */
+ *    hmp_count_correct_rows / hmp_net_count_correct_rooms: the device-side validation count of the room task;
+ *    hmp_net_set_head_pools: the two-headed step / count with each head's CE on the mean over a pool edge type (LeafPool) */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -364,6 +365,14 @@ int hmp_net_step2_fused(hmp_net* net, const hmp_batch* batch, const hmp_head_tar
  * {correct_readout, total_readout, correct_aux, total_aux}; one launch beyond the forward, nothing synchronises. */
 int hmp_net_count_correct2(hmp_net* net, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
                            int64_t* d_counts, void* stream);
+/* Pooled heads (HeterogeneousNeuralTreeNetwork with output_dim_dict, heterogeneous_neural_tree_network.py:186-205): head h's CE
+ * and count read pooled[v] = mean over the edges (leaf -> v) of pool_edge_type_h of dropout(act(z[leaf])) (0 for a v with no
+ * edge), one row per node of the edge type's destination, instead of the final state's rows.  The keep-mask stays the one of the
+ * leaf rows (the rule above); hmp_head_targets then hold one label / mask byte per DESTINATION row.  -1 = an unpooled head.  The
+ * edge type must start at the head's readout type and end at a node type that no last-layer conv writes.  Called once, before the
+ * first workspace bind; the two-head entries above change their loss and count launches, nothing else changes.  Both step phases
+ * stay capturable, and the gradient is summed without float atomics (bitwise reproducible). */
+int hmp_net_set_head_pools(hmp_net* net, int32_t pool_edge_type_readout, int32_t pool_edge_type_aux);
 /* Two LEARNED linear heads over one final state (HomogeneousNetwork / HomogeneousNeuralTreeNetwork with output_dim_dict,
  * homogeneous_network.py:122-147, homogeneous_neural_tree_network.py:96-109): the loop body of SemiSupervisedTrainingJob.train
  * (semisupervised_training_job.py:117-147, homogeneous branches) and the per-batch arithmetic of its test() (:198-257).

@@ -5,7 +5,10 @@
 * the six homogeneous Stanford3DSG shapes of ``train_Stanford.py`` (B = 128, dropout 0.25, 15 room / 35 object classes, 6-d
   features; learned linear heads): ``HomogeneousNetwork`` on ``workloads.stanford_semisupervised_batch`` and
   ``HomogeneousNeuralTreeNetwork`` on H-tree batches from the committed fixture (built like
-  tests/test_gpu_htree.py::homogeneous_htree_batch):
+  tests/test_gpu_htree.py::homogeneous_htree_batch);
+* the two heterogeneous H-tree Stanford3DSG shapes (``htree_hetero_GAT`` / ``htree_hetero_GAT_edge``: GAT hidden [64, 64, 64],
+  heads 6, concats [T, T, T, F], no pre_mp, B = 128, 6-d features): ``HeterogeneousNeuralTreeNetwork`` on
+  ``workloads.semisupervised_htree_batch``, each head's CE on the LeafPool of its final state:
 
 * ``autograd``: the reference's loop body -- ``net(batch)`` -> ``net.loss`` -> ``backward`` -> ``torch.optim.Adam``;
 * ``fused_eager`` / ``fused_graph``: ``semisupervised_step`` without / with hipGraph replay;
@@ -26,7 +29,8 @@ for p in (ROOT, os.path.join(ROOT, "hydra-gnn_amd")):
 import torch  # noqa: E402
 
 from hydra_gnn_amd import workloads  # noqa: E402
-from hydra_gnn_amd.models import HeterogeneousNetwork, HomogeneousNetwork, HomogeneousNeuralTreeNetwork  # noqa: E402
+from hydra_gnn_amd.models import (HeterogeneousNetwork, HeterogeneousNeuralTreeNetwork, HomogeneousNetwork,  # noqa: E402
+                                   HomogeneousNeuralTreeNetwork)
 
 DEV = "cuda:0"
 SHAPES = {
@@ -46,6 +50,11 @@ STANFORD = {  # name: (H-tree, model kwargs)
     "htree_GAT_edge": (True, dict(conv_block="GAT_edge", **_G6x4)),
 }
 STANFORD_OUT = {"room": 15, "object": 35}
+_G64 = dict(GAT_hidden_dims=[64, 64, 64], GAT_heads=[6, 6, 6, 6], GAT_concats=[True, True, True, False])
+HETERO_HTREE = {  # config/Stanford3D/htree_hetero_GAT{,_edge}.yaml
+    "htree_hetero_GAT": dict(conv_block="GAT", **_G64),
+    "htree_hetero_GAT_edge": dict(conv_block="GAT_edge", **_G64),
+}
 
 
 def stanford_htree_batch(n_graphs, seed):
@@ -110,6 +119,41 @@ def measure_stanford(name, steps, warmup, n_graphs=128):
     return res
 
 
+def measure_hetero_htree(name, steps, warmup, n_graphs=128):
+    kw = HETERO_HTREE[name]
+    gb = workloads.semisupervised_htree_batch(n_graphs, workloads.BASE_SEED + 7, relative_pos=kw["conv_block"] == "GAT_edge")
+    for t in gb.node_types:  # 6-d features on every node type
+        if "x" in gb[t]:
+            gb[t].x = gb[t].x[:, :6].contiguous()
+    gb = gb.to(DEV)
+    dims = {t: 6 for t in ("object", "room", "object-room", "room-room", "object_virtual", "room_virtual")}
+    base = dict(input_dim_dict=dims, dropout=0.25, disable_initialization=True, **kw)
+    labels = (gb["room_virtual"].y, gb["object_virtual"].y)
+    masks = (gb["room_virtual"].train_mask, gb["object_virtual"].train_mask)
+    res = {"batch": n_graphs, "rows": {t: int(gb[t].num_nodes) for t in gb.node_types}}
+    torch.manual_seed(0)
+    out = dict(STANFORD_OUT, **{"object-room": 1, "room-room": 1})
+    net = HeterogeneousNeuralTreeNetwork(output_dim_dict=out, **base).to(DEV).train()
+    opt = torch.optim.Adam(net.parameters(), lr=1e-4, weight_decay=1e-3)
+
+    def autograd_step():
+        opt.zero_grad()
+        net.loss(net(gb), labels, masks).backward()
+        opt.step()
+
+    res["autograd"] = timed(autograd_step, steps, warmup)
+    for use_graph, key in ((False, "fused_eager"), (True, "fused_graph")):
+        step = net.semisupervised_step(lr=1e-4, weight_decay=1e-3, use_graph=use_graph)
+        res[key] = timed(lambda: step(gb, labels, masks), steps, warmup)
+    torch.manual_seed(0)
+    one = HeterogeneousNeuralTreeNetwork(output_dim=15, **base).to(DEV)
+    s1 = one.train_step(lr=1e-4, weight_decay=1e-3, ignored_label=-100, use_graph=True)
+    yr = gb["room_virtual"].y
+    res["single_graph"] = timed(lambda: s1(gb, yr), steps, warmup)
+    res["speedup_graph_vs_autograd"] = res["autograd"] / res["fused_graph"]
+    return res
+
+
 def timed(fn, steps, warmup):
     for _ in range(warmup):
         fn()
@@ -157,10 +201,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--shapes", default=",".join(list(SHAPES) + list(STANFORD)))
+    ap.add_argument("--shapes", default=",".join(list(SHAPES) + list(STANFORD) + list(HETERO_HTREE)))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = {name: (measure_stanford if name in STANFORD else measure)(name, a.steps, a.warmup) for name in a.shapes.split(",")}
+    def measure_any(name):
+        if name in HETERO_HTREE:
+            return measure_hetero_htree(name, a.steps, a.warmup)
+        return (measure_stanford if name in STANFORD else measure)(name, a.steps, a.warmup)
+
+    out = {name: measure_any(name) for name in a.shapes.split(",")}
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
