@@ -145,23 +145,18 @@ def test_config5_fp32_mode_matches_the_float64_oracle(graph):
           f"its scale; ReLU units within 1e-5 of zero: {stats['ambiguous']}, of which the two sides disagreed on {stats['flipped']}")
 
 
-def test_config5_bf16_mode_matches_the_bf16_contract_oracle(graph, monkeypatch):
-    monkeypatch.setenv("HMP_BF16_ALL", "1")  # the 10^6-object regime's decisions at a size the oracle can hold
-    monkeypatch.setenv("HMP_FUSE", "0")      # ... incl. its launch sequence (stand-alone GEMMs: the ones that run in bf16)
-    ora, net = build(seed=1)
-    net.native().set_compute("bf16")
-    g = graph.to(DEV)
-    pred, loss, grads = engine_fwd_bwd(net, g)
-    assert net.native().read_state()[1] == 0
-    replay = make_replay(net)
-    # the convs the engine evaluated aggregate-first (objects -> rooms at this size): the contract rounds where the engine rounds
-    nat = net.native()
-    af = {(l, tuple(nat.layers[l].convs[c].edge_type)) for (l, c), on in nat._agg_first.items() if on}
-    assert af == {(l, ("objects", "objects_to_rooms", "rooms")) for l in range(3)}, af
-    # the bf16 contract, accumulated in float64 and in float32, and the exact function (no rounding)
-    l64, s64, g64 = bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float64, rounding=True, dropout_fn=replay, training=True, agg_first=af)
-    l32, s32, g32 = bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float32, rounding=True, dropout_fn=replay, training=True, agg_first=af)
-    lex, sex, gex = bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float64, rounding=False, dropout_fn=replay, training=True)
+def bf16_contract(ora, graph, replay, af):
+    """the bf16 contract (oracle/bf16_emul.py) with the engine's replayed dropout masks and aggregate-first convs `af`,
+    accumulated in float64 and in float32, and the exact function (no rounding): three (logits, loss, grads) triples"""
+    return (bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float64, rounding=True, dropout_fn=replay, training=True, agg_first=af),
+            bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float32, rounding=True, dropout_fn=replay, training=True, agg_first=af),
+            bf16_emul.sage_hetero_bf16(ora, graph, dtype=torch.float64, rounding=False, dropout_fn=replay, training=True))
+
+
+def check_against_bf16_contract(contract, pred, loss, grads, n_live=30):
+    """the engine's training-mode logits / loss / gradients (bf16 mode) against bf16_contract(): inside the derived spread, and
+    far inside the distance to the exact function (the comparison has power).  Returns the per-tensor report."""
+    (l64, s64, g64), (l32, s32, g32), (lex, sex, gex) = contract
     report = []
 
     def check(what, eng, a64, a32, aex):
@@ -187,9 +182,26 @@ def test_config5_bf16_mode_matches_the_bf16_contract_oracle(graph, monkeypatch):
         e, d = check(name, grads[name], g64[name], g32[name], gex[name])
         n += 1
         tight += int(e < d / 2)
-    assert n == 30  # (4 + 4 + 2) live convs x (lin_l.weight, lin_l.bias, lin_r.weight)
+    assert n == n_live  # config 5: (4 + 4 + 2) live convs x (lin_l.weight, lin_l.bias, lin_r.weight)
     # ... and for (nearly) every tensor far inside the distance to the exact function: the comparison has power
     assert tight >= n - 2, report
+    return report
+
+
+def test_config5_bf16_mode_matches_the_bf16_contract_oracle(graph, monkeypatch):
+    monkeypatch.setenv("HMP_BF16_ALL", "1")  # the 10^6-object regime's decisions at a size the oracle can hold
+    monkeypatch.setenv("HMP_FUSE", "0")      # ... incl. its launch sequence (stand-alone GEMMs: the ones that run in bf16)
+    ora, net = build(seed=1)
+    net.native().set_compute("bf16")
+    g = graph.to(DEV)
+    pred, loss, grads = engine_fwd_bwd(net, g)
+    assert net.native().read_state()[1] == 0
+    replay = make_replay(net)
+    # the convs the engine evaluated aggregate-first (objects -> rooms at this size): the contract rounds where the engine rounds
+    nat = net.native()
+    af = {(l, tuple(nat.layers[l].convs[c].edge_type)) for (l, c), on in nat._agg_first.items() if on}
+    assert af == {(l, ("objects", "objects_to_rooms", "rooms")) for l in range(3)}, af
+    report = check_against_bf16_contract(bf16_contract(ora, graph, replay, af), pred, loss, grads)
     for r in report:
         print("bf16 contract: %-60s engine-vs-contract %.2e   f32-vs-f64 spread %.2e   contract-vs-exact %.2e" % r)
     # dead convs get no gradient
