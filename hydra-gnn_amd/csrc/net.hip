@@ -86,6 +86,34 @@ struct EnvSwitches {
   bool bf16_all = false;    // HMP_BF16_ALL=1: every GEMM of a bf16-mode net takes the bf16 kernel whatever its size
 };
 
+// State of the entry call in progress.  StepGuard sets it up on entry and puts it back to these defaults -- what a plain forward
+// and backward see -- on every exit, error returns included; the step driver (run_step) and its loss stages set the rest of the
+// inputs.  forward_impl / backward_impl read the inputs and write only the result flags (and consume fin_loss).
+struct StepCall {
+  // the dropout draw of this call's forward: forward_impl makes it the last forward's once it has accepted the batch
+  int training = 0;
+  uint64_t seed = 0;
+  uint32_t rng_step = 0;
+  int* d_step = nullptr;  // training step: its counter (hmp_train_args::d_step or &d_state->step), added to the draw number
+  // single-head step: labels for the cross entropy riding in the last aggregation; two-headed step (hmp_net_step2_*): its
+  // targets, whose tail + CE ride in that epilogue when it can hold both heads' rows
+  const int64_t* ce_labels = nullptr;
+  const hmp_head_targets* tgt = nullptr;
+  int64_t ce_ignored = 0;
+  AdamFuse adam = {};  // fused step: Adam riding in the gradient un-pack
+  // backward of a step: the first backward kernel finalises {loss_sum, count} over fin_rows rows of d_row_lv (0: b->n_out);
+  // G[L][aux] already written by the loss stage (backward_impl does not stage it); linear heads: workgroup slabs of the
+  // head kernel for the gradient un-pack (0: none)
+  bool fin_loss = false;
+  int fin_rows = 0;
+  bool aux_g_ready = false;
+  int head_blocks = 0;
+  // results: the CE / the heads whose tail + CE rode in the last aggregation's epilogue, Adam ran in the un-pack
+  bool ce_done = false;
+  bool tail_done[2] = {false, false};
+  bool adam_done = false;
+};
+
 struct hmp_net {
   hmp_net_spec spec;
   EnvSwitches env;
@@ -120,14 +148,12 @@ struct hmp_net {
   int iota_cap = 0;
   int64_t sadd_floats = 0;
   float* d_row_lv = nullptr;        // per output row {loss, valid} of the fused step's loss kernel
-  bool fin_loss = false;            // the next gradient un-pack also finalises {loss_sum, count}
 
   // workspace binding
   bool bound = false;
   int cap_nodes[HMP_MAX_NODE_TYPES];
   int64_t cap_edges[HMP_MAX_EDGE_TYPES];
   NetState* d_state = nullptr;  // owned by the net (NOT part of the re-bindable workspace): status bits and the net's own step counter
-  int* d_step = nullptr;        // the step counter of the running step: the optimiser's (hmp_train_args::d_step) or &d_state->step
   hmp_plan plan[HMP_MAX_EDGE_TYPES];
   int* plan_scratch[HMP_MAX_EDGE_TYPES];
   float* d_packed = nullptr;
@@ -148,8 +174,8 @@ struct hmp_net {
   int training = 0;
   uint64_t seed = 0;
   uint32_t rng_step = 0;
-  bool step_dev = false;  // dropout step offset read from *d_step
   GradReduceDyn dyn;
+  StepCall call;  // the entry call in progress (StepGuard)
 
   // parallel branches (side streams; under capture they become branches of the hipGraph)
   bool use_branches = false;
@@ -160,25 +186,11 @@ struct hmp_net {
   int fuse_mode = -1;      // HMP_FUSE override (0 / 1), -1 = automatic: row-local GEMMs ride in the aggregation kernels
   bool fuse_now = false;   // decision for the current batch
   bool reuse_plan = false; // this call: hmp_batch::plan_valid accepted
-  // fused training step: labels for the cross entropy riding in the last aggregation, Adam riding in the gradient un-pack
-  const int64_t* ce_labels = nullptr;
-  int64_t ce_ignored = 0;
-  bool ce_done = false;
-  AdamFuse adam_fuse = {};
-  bool adam_done = false;
-  // two-headed step (hmp_net_step2_*): its targets, the heads whose tail + CE rode in the last aggregation's epilogue, G[L][aux]
-  // already written by the tail (backward_impl does not stage it), rows of d_row_lv the loss finalisation sums (0: b->n_out)
-  const hmp_head_targets* tgt = nullptr;
-  bool tail_done[2] = {false, false};
-  bool aux_g_ready = false;
-  int fin_rows = 0;
-  // linear heads (hmp_net_set_linear_heads): their description, where their per-workgroup slabs start in d_slabs, and the
-  // workgroups of the running step's head kernel (backward_impl hands that many slabs to the gradient un-pack; 0: none)
+  // linear heads (hmp_net_set_linear_heads): their description and where their per-workgroup slabs start in d_slabs
   bool has_heads = false;
   hmp_linear_heads heads = {};
   int64_t head_slab_off = 0, head_slab_stride = 0;
   int head_ld_slab = 0;
-  int head_blocks_now = 0;
   // pooled heads (hmp_net_set_head_pools): the pool edge type of each head (-1: unpooled), d loss / d pooled per head (the
   // workspace's [cap rows of the pool destination][fpad(classes)] scratch of the pooled CE launch)
   bool has_pools = false;
@@ -780,7 +792,7 @@ DropCfg make_drop(const hmp_net* n, float p, uint32_t stream) {
   d.k0 = (uint32_t)n->seed; d.k1 = (uint32_t)(n->seed >> 32);
   d.step = n->rng_step; d.stream = stream;
   d.thresh = drop_thresh(p); d.scale = 1.f / (1.f - p);
-  d.step_dev = n->step_dev ? n->d_step : nullptr;
+  d.step_dev = n->call.d_step;
   return d;
 }
 
@@ -792,7 +804,7 @@ GatDyn make_gat_dyn(const hmp_net* n, const hmp_batch* b) {
   d.training = n->training;
   d.k0 = (uint32_t)n->seed; d.k1 = (uint32_t)(n->seed >> 32);
   d.step = n->rng_step;
-  d.step_dev = n->step_dev ? n->d_step : nullptr;
+  d.step_dev = n->call.d_step;
   return d;
 }
 
@@ -999,15 +1011,24 @@ bool build_front(hmp_net* n, const hmp_batch* b, const float* d_params, FrontArg
   fa.pack_map = n->d_pack_map;
   fa.pack_blocks = n->n_pack_blocks16;
   fa.packed = n->d_packed;
-  fa.step_ctr = n->step_dev ? n->d_step : nullptr;
+  fa.step_ctr = n->call.d_step;
   fa.step_mirror = &n->d_state->last_step;
   return true;
 }
 
 int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStream_t st) {
   HMP_TRY(check_batch(n, b));
-  n->batch = *b;
   const hmp_net_spec& S = n->spec;
+  if (b->plan_valid) {
+    HMP_CHECK_ARG(n->plan_ok, "batch: plan_valid without a plan from a previous call (first call, or the workspace was re-bound)");
+    for (int e = 0; e < n->ET; ++e)
+      HMP_CHECK_ARG(n->plan[e].n_edges == b->n_edges[e] && n->plan[e].n_src == b->n_nodes[S.edge_src[e]] && n->plan[e].n_dst == b->n_nodes[S.edge_dst[e]],
+                    "batch: plan_valid but edge type %d changed shape since the previous call", e);
+  }
+  // the batch is accepted: from here on this is the last forward (a refused batch leaves the previous one's state to its backward)
+  n->batch = *b;
+  n->training = n->call.training; n->seed = n->call.seed; n->rng_step = n->call.rng_step;
+  n->reuse_plan = b->plan_valid != 0;
   // The parameter pack and the layer-0 projection do not depend on the plan: they run on a side stream next to the
   // (4-5 dependent launches of the) plan build and join before the first aggregation.  Under capture this becomes
   // two parallel branches of the hipGraph.
@@ -1016,14 +1037,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
   if (side != main_st) HMP_TRY(fork_to(n, main_st, side));
   n->fuse_now = fuse_small(n, b);
   memset(n->h16, 0, sizeof(n->h16));
-  n->reuse_plan = false;
-  if (b->plan_valid) {
-    HMP_CHECK_ARG(n->plan_ok, "batch: plan_valid without a plan from a previous call (first call, or the workspace was re-bound)");
-    for (int e = 0; e < n->ET; ++e)
-      HMP_CHECK_ARG(n->plan[e].n_edges == b->n_edges[e] && n->plan[e].n_src == b->n_nodes[S.edge_src[e]] && n->plan[e].n_dst == b->n_nodes[S.edge_dst[e]],
-                    "batch: plan_valid but edge type %d changed shape since the previous call", e);
-    n->reuse_plan = true;
-  }
   // Small batches, SAGE layer 0: projection (reading the stacked weights straight from the flat parameters), plan and pack
   // are roles of ONE launch (front.hip) -- the plan, which has to read whole edge lists through single CUs, hides behind
   // the projection tiles.
@@ -1043,7 +1056,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
     }
   } else {
     Scope sc(n, KC_PACK, side);
-    HMP_TRY(pack_launch(n->d_pack_segs, n->pack_sb, d_params, n->d_packed, n->step_dev ? n->d_step : nullptr, &n->d_state->last_step, side));
+    HMP_TRY(pack_launch(n->d_pack_segs, n->pack_sb, d_params, n->d_packed, n->call.d_step, &n->d_state->last_step, side));
   }
   bool z_done = false;
   for (int l = 0; l < n->L; ++l) {
@@ -1144,16 +1157,16 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       a.mean = 1;
       a.state = n->d_state;
       // two-headed step: both heads' tail (act, dropout) and masked CE in this epilogue when it can hold both rows' widths
-      const bool tail_epi = l == n->L - 1 && n->tgt && !n->has_pools && n->fuse_now && fpad(Ls.out_dim[S.readout_type]) <= 256 &&
+      const bool tail_epi = l == n->L - 1 && n->call.tgt && !n->has_pools && n->fuse_now && fpad(Ls.out_dim[S.readout_type]) <= 256 &&
                             fpad(Ls.out_dim[S.aux_readout_type]) <= 256;
       for (int t = 0; t < n->T; ++t) {
         if (Y.roff[t] < 0 || b->n_nodes[t] == 0) continue;
         AggDst& D = a.d[a.n++];
-        if (l == n->L - 1 && t == S.readout_type && n->ce_labels && S.pool_edge_type < 0 && n->fuse_now && fpad(Ls.out_dim[t]) <= 256) {
+        if (l == n->L - 1 && t == S.readout_type && n->call.ce_labels && S.pool_edge_type < 0 && n->fuse_now && fpad(Ls.out_dim[t]) <= 256) {
           // masked cross entropy in the epilogue of the last aggregation (one kernel less on the step's critical path)
-          D.ce_labels = n->ce_labels; D.ce_ignored = n->ce_ignored; D.ce_classes = n->out_dim;
+          D.ce_labels = n->call.ce_labels; D.ce_ignored = n->call.ce_ignored; D.ce_classes = n->out_dim;
           D.ce_grad = n->d_gout; D.ce_ldg = n->out_ld; D.ce_row_lv = n->d_row_lv;
-          n->ce_done = true;
+          n->call.ce_done = true;
         }
         D.n_rows = b->n_nodes[t];
         D.F = fpad(Ls.out_dim[t]);
@@ -1170,12 +1183,12 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           D.act = S.tail_act;
           D.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
           if (D.drop_on) D.drop = make_drop(n, S.tail_dropout, (uint32_t)(l * HMP_MAX_NODE_TYPES + t));
-          D.ce_labels = n->tgt->d_labels[head]; D.ce_mask = n->tgt->d_mask[head]; D.ce_tail = 1;
-          D.ce_ignored = n->ce_ignored; D.ce_classes = Ls.out_dim[t];
+          D.ce_labels = n->call.tgt->d_labels[head]; D.ce_mask = n->call.tgt->d_mask[head]; D.ce_tail = 1;
+          D.ce_ignored = n->call.ce_ignored; D.ce_classes = Ls.out_dim[t];
           D.ce_grad = head == 0 ? n->d_gout : n->G[n->L][t];
           D.ce_ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
           D.ce_row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
-          n->tail_done[head] = true;
+          n->call.tail_done[head] = true;
         }
         for (int i = 0; i < Y.n_live; ++i) {
           const int c = Y.live[i];
@@ -1276,7 +1289,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     // second readout: stage its gradient in G[L][aux] (zero where the caller passed none, and in the padding columns)
     const int rows = n->batch.n_nodes[at], ld = n->ld[n->L][at], w = n->dim[n->L][at];
     HMP_CHECK_ARG(!d_gaux || ld_gaux >= w, "net: second output gradient narrower than the output (%d < %d)", ld_gaux, w);
-    if (rows > 0 && !n->aux_g_ready) {
+    if (rows > 0 && !n->call.aux_g_ready) {
       HMP_HIP(hipMemsetAsync(n->G[n->L][at], 0, (size_t)rows * ld * 4, st));
       if (d_gaux)
         HMP_HIP(hipMemcpy2DAsync(n->G[n->L][at], (size_t)ld * 4, d_gaux, (size_t)ld_gaux * 4, (size_t)w * 4, rows, hipMemcpyDeviceToDevice, st));
@@ -1298,8 +1311,8 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     ld_gtop = n->ld[n->L][rt];
   }
   memset(&n->dyn, 0, sizeof(n->dyn));
-  if (n->head_blocks_now > 0) {  // linear heads: the head kernel's workgroup slabs (rows past the heads' write nothing: 0)
-    n->dyn.n_slabs[HEAD_SLAB_ID] = (unsigned char)n->head_blocks_now;
+  if (n->call.head_blocks > 0) {  // linear heads: the head kernel's workgroup slabs (rows past the heads' write nothing: 0)
+    n->dyn.n_slabs[HEAD_SLAB_ID] = (unsigned char)n->call.head_blocks;
     n->dyn.slab_stride[HEAD_SLAB_ID] = (int)n->head_slab_stride;
   }
   {
@@ -1338,9 +1351,9 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       TAggArgs a;
       memset(&a, 0, sizeof(a));
       a.mean = 1;
-      if (n->fin_loss) {  // first backward kernel of the step: one extra block finalises {loss_sum, count}
-        a.fin_row_lv = n->d_row_lv; a.fin_rows = n->fin_rows > 0 ? n->fin_rows : b->n_out; a.fin_out2 = d_grads + n->spec.n_active_params; a.fin_state = n->d_state;
-        n->fin_loss = false;
+      if (n->call.fin_loss) {  // first backward kernel of the step: one extra block finalises {loss_sum, count}
+        a.fin_row_lv = n->d_row_lv; a.fin_rows = n->call.fin_rows > 0 ? n->call.fin_rows : b->n_out; a.fin_out2 = d_grads + n->spec.n_active_params; a.fin_state = n->d_state;
+        n->call.fin_loss = false;
         fin_early = true;
       }
       for (int s = 0; s < n->T; ++s) {
@@ -1692,15 +1705,37 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     const int64_t na = n->spec.n_active_params;
     // Adam inside the un-pack: needs the valid-label count before the kernel starts (finalised by the first backward
     // kernel) and gradient terms that read no parameters (no GAT layer)
-    AdamFuse af = n->adam_fuse;
+    AdamFuse af = n->call.adam;
     af.on = (af.on && fin_early && !n->any_gat) ? 1 : 0;
-    n->adam_done = af.on != 0;
+    n->call.adam_done = af.on != 0;
     HMP_TRY(grad_reduce_launch(n->d_grad_segs, n->grad_sb, n->dyn, n->d_slabs, d_params, d_grads,
-                               n->fin_loss ? n->d_row_lv : nullptr, n->fin_rows > 0 ? n->fin_rows : b->n_out, d_grads + na, n->d_state,
+                               n->call.fin_loss ? n->d_row_lv : nullptr, n->call.fin_rows > 0 ? n->call.fin_rows : b->n_out, d_grads + na, n->d_state,
                                af, st));
-    n->fin_loss = false;
+    n->call.fin_loss = false;
   }
   return HMP_OK;
+}
+
+// Sets up n->call for one entry call (the environment switches, the forward's dropout draw, a training step's counter) and puts
+// it back to the defaults on every exit
+struct StepGuard {
+  hmp_net* n;
+  StepGuard(hmp_net* net, int training = 0, uint64_t seed = 0, uint32_t rng_step = 0, int* d_step = nullptr) : n(net) {
+    read_env(n);
+    g_bf16_all = n->env.bf16_all;
+    n->call.training = training; n->call.seed = seed; n->call.rng_step = rng_step;
+    n->call.d_step = d_step;
+  }
+  ~StepGuard() { n->call = StepCall(); }
+  StepGuard(const StepGuard&) = delete;
+  StepGuard& operator=(const StepGuard&) = delete;
+};
+
+// a forward without a loss: hmp_net_forward, and the eval-mode forward of the count entries
+int plain_forward(hmp_net* n, const hmp_batch* b, const float* d_params, hipStream_t st, int training = 0, uint64_t seed = 0,
+                  uint32_t rng_step = 0) {
+  StepGuard guard(n, training, seed, rng_step);
+  return forward_impl(n, b, d_params, st);
 }
 
 }  // namespace
@@ -1722,7 +1757,6 @@ extern "C" int hmp_net_create(const hmp_net_spec* spec, hmp_net** out) {
       snprintf(err_buf(), 512, "hmp_net_create: device allocation of the net state failed");
       r = HMP_E_HIP;
     }
-    n->d_step = n->d_state ? &n->d_state->step : nullptr;
   }
   if (r == HMP_OK) {
     // side-stream branches (pack + layer-0 projection next to the plan, weight gradients next to the backward chain) only
@@ -1800,10 +1834,7 @@ extern "C" int hmp_net_bind_workspace(hmp_net* n, void* d_workspace, size_t byte
 extern "C" int hmp_net_forward(hmp_net* n, const hmp_batch* batch, const float* d_params, int32_t training, uint64_t seed,
                                uint32_t rng_step, const float** d_out, int32_t* ld_out, void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_out && ld_out, "hmp_net_forward: null argument");
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = training; n->seed = seed; n->rng_step = rng_step; n->step_dev = false;
-  HMP_TRY(forward_impl(n, batch, d_params, (hipStream_t)stream));
+  HMP_TRY(plain_forward(n, batch, d_params, (hipStream_t)stream, training, seed, rng_step));
   *d_out = out_ptr(n);
   *ld_out = n->out_ld;
   return HMP_OK;
@@ -1853,221 +1884,6 @@ extern "C" int hmp_net_backward2(hmp_net* n, const float* d_gout, int32_t ld_gou
     ld_gout = n->ld[n->L][rt];
   }
   return backward_impl(n, d_gout, ld_gout, d_grads, d_params, d_gx, (hipStream_t)stream, d_gout_aux, ld_aux);
-}
-
-extern "C" int hmp_net_step_fwd_bwd(hmp_net* n, const hmp_batch* batch, const float* d_params, float* d_grads,
-                                    const hmp_train_args* args, void* stream) {
-  HMP_CHECK_ARG(n && batch && d_params && d_grads && args, "hmp_net_step_fwd_bwd: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0, "hmp_net_step_fwd_bwd: the fused step computes one cross entropy (single-output nets)");
-  HMP_CHECK_ARG(batch->d_labels != nullptr, "hmp_net_step_fwd_bwd: labels required");
-  hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
-  n->d_step = args->d_step ? args->d_step : &n->d_state->step;
-  n->ce_labels = batch->d_labels; n->ce_ignored = args->ignored_label; n->ce_done = false;
-  const int rf = forward_impl(n, batch, d_params, st);
-  n->ce_labels = nullptr;
-  HMP_TRY(rf);
-  if (!n->ce_done) {
-    Scope sc(n, KC_LOSS, st);
-    HMP_TRY(masked_ce_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, args->ignored_label, n->d_gout,
-                                  n->out_ld, n->d_row_lv, n->d_state, st));
-  }
-  // {loss_sum, count} -> d_grads[na], d_grads[na + 1]: by the first transposed aggregation, else by the gradient un-pack
-  n->fin_loss = true;
-  const int rb = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
-  n->d_step = &n->d_state->step;  // the optimiser's counter belongs to the caller: not kept beyond this call
-  n->step_dev = false;
-  return rb;
-}
-
-extern "C" int hmp_net_step_fused(hmp_net* n, const hmp_batch* batch, float* d_params, float* d_grads, float* d_m, float* d_v,
-                                  const hmp_train_args* args, void* stream) {
-  HMP_CHECK_ARG(n && batch && d_params && d_grads && d_m && d_v && args, "hmp_net_step_fused: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0, "hmp_net_step_fused: the fused step computes one cross entropy (single-output nets)");
-  AdamFuse& af = n->adam_fuse;
-  af.on = n->fuse_mode == 0 ? 0 : 1;
-  af.p = d_params; af.m = d_m; af.v = d_v;
-  af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
-  af.step_dev = args->d_step ? args->d_step : &n->d_state->step;
-  af.count = d_grads + n->spec.n_active_params + 1;
-  n->adam_done = false;
-  const int r = hmp_net_step_fwd_bwd(n, batch, d_params, d_grads, args, stream);
-  af.on = 0;
-  HMP_TRY(r);
-  if (n->adam_done) return HMP_OK;
-  return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
-}
-
-namespace {
-
-// the rows of one head for the stand-alone tail kernel (semisup.hip)
-void add_tail(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
-  const hmp_net_spec& S = n->spec;
-  const int t = head == 0 ? S.readout_type : S.aux_readout_type;
-  if (b->n_nodes[t] == 0) return;
-  HeadTail& T = ta.h[ta.n++];
-  memset(&T, 0, sizeof(T));
-  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
-  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
-  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
-  T.slot = head;
-  if (!ce) return;
-  T.grad = head == 0 ? n->d_gout : n->G[n->L][t];
-  T.ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
-  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
-  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
-  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
-}
-
-int check_targets(const hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, const char* who) {
-  const hmp_net_spec& S = n->spec;
-  HMP_CHECK_ARG(S.aux_readout_type >= 0, "%s: the net has one output (aux_readout_type < 0): use the single-head entry", who);
-  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
-                "%s: spec tail_act %d / tail_dropout %g", who, S.tail_act, (double)S.tail_dropout);
-  for (int h = 0; h < 2; ++h)  // one label per row of the head's label type (the pool destination of a pooled head)
-    HMP_CHECK_ARG(b->n_nodes[label_type(n, h)] == 0 || tg->d_labels[h] != nullptr, "%s: labels of head %d required", who, h);
-  return HMP_OK;
-}
-
-// the rows of one head for the pooled tail launches (semisup.hip): final state of the head's type, its pool plan (none: identity),
-// labels / mask / {loss, valid} per pooled row
-void add_pool(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
-  const hmp_net_spec& S = n->spec;
-  const int t = head_type(n, head), lt = label_type(n, head);
-  if (b->n_nodes[t] == 0 && b->n_nodes[lt] == 0) return;
-  HeadTail& T = ta.h[ta.n++];
-  memset(&T, 0, sizeof(T));
-  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
-  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
-  T.n_pool = b->n_nodes[lt];
-  if (n->head_pool[head] >= 0) {
-    const hmp_plan& P = n->plan[n->head_pool[head]];
-    T.rowptr = P.d_rowptr; T.col = P.d_col; T.t_rowptr = P.d_t_rowptr; T.t_col = P.d_t_col;
-  }
-  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
-  T.slot = head;
-  if (!ce) return;
-  T.grad = n->G[n->L][t]; T.ldg = n->ld[n->L][t];
-  T.dpool = n->d_dpool[head]; T.ldp = n->ld[n->L][t];
-  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_nodes[label_type(n, 0)]);
-  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
-  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
-}
-
-// pooled heads: the CE over the pooled rows of both heads (one launch), then d loss / d z of every leaf row (one launch) -> G[L][t]
-int pool_tail_ce(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int64_t ignored, hipStream_t st) {
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = n->spec.tail_act; ta.ignored = ignored; ta.state = n->d_state;
-  for (int h = 0; h < 2; ++h) add_pool(n, b, tg, h, true, ta);
-  if (ta.n == 0) return HMP_OK;
-  {
-    Scope sc(n, KC_LOSS, st);
-    HMP_TRY(pool_tail_ce_launch(ta, st));
-  }
-  Scope sc(n, KC_LOSS, st);
-  return pool_tail_grad_launch(ta, st);
-}
-
-}  // namespace
-
-extern "C" int hmp_net_step2_fwd_bwd(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
-                                     float* d_grads, const hmp_train_args* args, void* stream) {
-  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && args, "hmp_net_step2_fwd_bwd: null argument");
-  HMP_TRY(check_targets(n, batch, targets, "hmp_net_step2_fwd_bwd"));
-  hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
-  n->d_step = args->d_step ? args->d_step : &n->d_state->step;
-  n->ce_ignored = args->ignored_label;
-  n->tgt = targets;
-  n->tail_done[0] = n->tail_done[1] = false;
-  const int rf = forward_impl(n, batch, d_params, st);
-  n->tgt = nullptr;
-  int r = rf;
-  if (r == HMP_OK && n->has_pools) {
-    // pooled heads: both gradients land in G[L][*] (the readout's is handed to the backward as its output gradient)
-    r = pool_tail_ce(n, batch, targets, args->ignored_label, st);
-    if (r == HMP_OK) {
-      n->fin_loss = true;
-      n->fin_rows = batch->n_nodes[label_type(n, 0)] + batch->n_nodes[label_type(n, 1)];
-      n->aux_g_ready = true;
-      const int rt = n->spec.readout_type;
-      r = backward_impl(n, n->G[n->L][rt], n->ld[n->L][rt], d_grads, d_params, nullptr, st);
-      n->aux_g_ready = false;
-      n->fin_rows = 0;
-      n->fin_loss = false;
-    }
-    n->d_step = &n->d_state->step;
-    n->step_dev = false;
-    return r;
-  }
-  if (r == HMP_OK) {  // the heads the last epilogue did not serve: one stand-alone launch over their rows
-    TailArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.act = n->spec.tail_act; ta.ignored = args->ignored_label; ta.state = n->d_state;
-    for (int h = 0; h < 2; ++h)
-      if (!n->tail_done[h]) add_tail(n, batch, targets, h, true, ta);
-    if (ta.n > 0) {
-      Scope sc(n, KC_LOSS, st);
-      r = tail_ce_launch(ta, st);
-    }
-  }
-  if (r == HMP_OK) {
-    // {loss_sum, count} over the readout rows then the aux rows -> d_grads[na], d_grads[na + 1] (one count for both heads)
-    n->fin_loss = true;
-    n->fin_rows = batch->n_out + batch->n_nodes[n->spec.aux_readout_type];
-    n->aux_g_ready = true;
-    r = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
-    n->aux_g_ready = false;
-    n->fin_rows = 0;
-    n->fin_loss = false;
-  }
-  n->d_step = &n->d_state->step;
-  n->step_dev = false;
-  return r;
-}
-
-extern "C" int hmp_net_step2_fused(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, float* d_params,
-                                   float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream) {
-  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && d_m && d_v && args, "hmp_net_step2_fused: null argument");
-  AdamFuse& af = n->adam_fuse;
-  af.on = n->fuse_mode == 0 ? 0 : 1;
-  af.p = d_params; af.m = d_m; af.v = d_v;
-  af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
-  af.step_dev = args->d_step ? args->d_step : &n->d_state->step;
-  af.count = d_grads + n->spec.n_active_params + 1;
-  n->adam_done = false;
-  const int r = hmp_net_step2_fwd_bwd(n, batch, targets, d_params, d_grads, args, stream);
-  af.on = 0;
-  HMP_TRY(r);
-  if (n->adam_done) return HMP_OK;
-  return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
-}
-
-extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
-                                      int64_t* d_counts, void* stream) {
-  HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct2: null argument");
-  HMP_TRY(check_targets(n, batch, targets, "hmp_net_count_correct2"));
-  hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
-  HMP_TRY(forward_impl(n, batch, d_params, st));
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = n->spec.tail_act; ta.state = n->d_state;
-  for (int h = 0; h < 2; ++h) {
-    if (n->has_pools) add_pool(n, batch, targets, h, false, ta);
-    else add_tail(n, batch, targets, h, false, ta);
-  }
-  if (ta.n == 0) return HMP_OK;
-  Scope sc(n, KC_LOSS, st);
-  if (n->has_pools) return pool_tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
-  return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
 }
 
 extern "C" int hmp_net_set_head_pools(hmp_net* n, int32_t pool_edge_type_readout, int32_t pool_edge_type_aux) {
@@ -2165,11 +1981,65 @@ extern "C" int hmp_net_set_linear_heads(hmp_net* n, const hmp_linear_heads* h) {
 
 namespace {
 
+int check_targets(const hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, const char* who) {
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(S.aux_readout_type >= 0, "%s: the net has one output (aux_readout_type < 0): use the single-head entry", who);
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU && S.tail_dropout >= 0.f && S.tail_dropout < 1.f,
+                "%s: spec tail_act %d / tail_dropout %g", who, S.tail_act, (double)S.tail_dropout);
+  for (int h = 0; h < 2; ++h)  // one label per row of the head's label type (the pool destination of a pooled head)
+    HMP_CHECK_ARG(b->n_nodes[label_type(n, h)] == 0 || tg->d_labels[h] != nullptr, "%s: labels of head %d required", who, h);
+  return HMP_OK;
+}
+
 int check_heads(const hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const char* who) {
   HMP_CHECK_ARG(n->has_heads, "%s: the net has no linear heads (hmp_net_set_linear_heads)", who);
   HMP_CHECK_ARG(!n->compute_bf16, "%s: the linear-head step computes in fp32 (bf16 compute mode is not supported)", who);
   HMP_CHECK_ARG(b->n_out == 0 || tg->d_labels != nullptr, "%s: labels required", who);
   return HMP_OK;
+}
+
+// the rows of one head for the stand-alone tail kernel (semisup.hip)
+void add_tail(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
+  const hmp_net_spec& S = n->spec;
+  const int t = head == 0 ? S.readout_type : S.aux_readout_type;
+  if (b->n_nodes[t] == 0) return;
+  HeadTail& T = ta.h[ta.n++];
+  memset(&T, 0, sizeof(T));
+  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
+  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
+  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
+  T.slot = head;
+  if (!ce) return;
+  T.grad = head == 0 ? n->d_gout : n->G[n->L][t];
+  T.ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
+  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
+  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
+}
+
+// the rows of one head for the pooled tail launches (semisup.hip): final state of the head's type, its pool plan (none: identity),
+// labels / mask / {loss, valid} per pooled row
+void add_pool(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int head, bool ce, TailArgs& ta) {
+  const hmp_net_spec& S = n->spec;
+  const int t = head_type(n, head), lt = label_type(n, head);
+  if (b->n_nodes[t] == 0 && b->n_nodes[lt] == 0) return;
+  HeadTail& T = ta.h[ta.n++];
+  memset(&T, 0, sizeof(T));
+  T.z = n->H[n->L][t]; T.ldz = n->ld[n->L][t];
+  T.n_rows = b->n_nodes[t]; T.classes = n->dim[n->L][t];
+  T.n_pool = b->n_nodes[lt];
+  if (n->head_pool[head] >= 0) {
+    const hmp_plan& P = n->plan[n->head_pool[head]];
+    T.rowptr = P.d_rowptr; T.col = P.d_col; T.t_rowptr = P.d_t_rowptr; T.t_col = P.d_t_col;
+  }
+  T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
+  T.slot = head;
+  if (!ce) return;
+  T.grad = n->G[n->L][t]; T.ldg = n->ld[n->L][t];
+  T.dpool = n->d_dpool[head]; T.ldp = n->ld[n->L][t];
+  T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_nodes[label_type(n, 0)]);
+  T.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
+  if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
 }
 
 LinHeadArgs heads_args(hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const float* d_params, bool train,
@@ -2196,51 +2066,159 @@ LinHeadArgs heads_args(hmp_net* n, const hmp_batch* b, const hmp_linear_head_tar
   return a;
 }
 
+// ---- the loss stages of the training step.  After the forward, each writes d loss / d output (handed back with its ld to the
+// backward), {loss, valid} per row, and the backward inputs of n->call that differ from the single head's
+// single head: the masked CE over the output rows, unless it rode in the last aggregation's epilogue
+int ce_loss(hmp_net* n, const hmp_batch* b, int64_t ignored, hipStream_t st, const float*& g, int& ldg) {
+  g = n->d_gout; ldg = n->out_ld;
+  if (n->call.ce_done) return HMP_OK;
+  Scope sc(n, KC_LOSS, st);
+  return masked_ce_rows_launch(out_ptr(n), n->out_ld, b->n_out, n->out_dim, b->d_labels, ignored, n->d_gout, n->out_ld, n->d_row_lv,
+                               n->d_state, st);
+}
+
+// two heads: the tail + CE of the heads the last epilogue did not serve, in one stand-alone launch over their rows; pooled heads:
+// the CE over the pooled rows of both heads (one launch), then d loss / d z of every leaf row (one launch) -> G[L][t].  Both
+// gradients are written; {loss_sum, count} sums the readout's rows then the aux rows (one count for both heads).
+int two_head_loss(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int64_t ignored, hipStream_t st, const float*& g,
+                  int& ldg) {
+  StepCall& c = n->call;
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = n->spec.tail_act; ta.ignored = ignored; ta.state = n->d_state;
+  c.aux_g_ready = true;
+  if (!n->has_pools) {
+    for (int h = 0; h < 2; ++h)
+      if (!c.tail_done[h]) add_tail(n, b, tg, h, true, ta);
+    g = n->d_gout; ldg = n->out_ld;
+    c.fin_rows = b->n_out + b->n_nodes[n->spec.aux_readout_type];
+    if (ta.n == 0) return HMP_OK;
+    Scope sc(n, KC_LOSS, st);
+    return tail_ce_launch(ta, st);
+  }
+  for (int h = 0; h < 2; ++h) add_pool(n, b, tg, h, true, ta);
+  const int rt = n->spec.readout_type;
+  g = n->G[n->L][rt]; ldg = n->ld[n->L][rt];
+  c.fin_rows = b->n_nodes[label_type(n, 0)] + b->n_nodes[label_type(n, 1)];
+  if (ta.n == 0) return HMP_OK;
+  {
+    Scope sc(n, KC_LOSS, st);
+    HMP_TRY(pool_tail_ce_launch(ta, st));
+  }
+  Scope sc(n, KC_LOSS, st);
+  return pool_tail_grad_launch(ta, st);
+}
+
+// linear heads in place of the loss kernel: d loss / d z -> d_gout, {loss, valid} per row, dW / db slabs
+int heads_loss(hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const float* d_params, int64_t ignored,
+               hipStream_t st, const float*& g, int& ldg) {
+  LinHeadArgs a = heads_args(n, b, tg, d_params, true, ignored);
+  g = n->d_gout; ldg = n->out_ld;
+  n->call.head_blocks = heads_blocks(b->n_out);
+  Scope sc(n, KC_LOSS, st);
+  return linear_heads_ce_launch(a, st);
+}
+
+// The targets of a step: the two heads', the linear heads', or neither (the single-head CE over hmp_batch::d_labels)
+struct StepTargets {
+  const hmp_head_targets* two = nullptr;
+  const hmp_linear_head_targets* lin = nullptr;
+};
+
+// One training step: forward (the single-head CE or the two heads' tail + CE riding in its last aggregation where they fit), the
+// loss stage, backward with the loss finalisation ({loss_sum, count} -> d_grads[na], d_grads[na + 1]), and, with moments d_m / d_v
+// (the *_fused entries, whose parameters are writable), Adam -- in the gradient un-pack where it can ride, else on its own.
+int run_step(hmp_net* n, const hmp_batch* b, const StepTargets& tg, const float* d_params, float* d_grads, float* d_m, float* d_v,
+             const hmp_train_args* args, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  StepGuard guard(n, args->training, args->seed, 0, args->d_step ? args->d_step : &n->d_state->step);
+  StepCall& c = n->call;
+  c.ce_labels = tg.two || tg.lin ? nullptr : b->d_labels;
+  c.tgt = tg.two;
+  c.ce_ignored = args->ignored_label;
+  if (d_m) {
+    AdamFuse& af = c.adam;
+    af.on = n->fuse_mode == 0 ? 0 : 1;
+    af.p = const_cast<float*>(d_params); af.m = d_m; af.v = d_v;
+    af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
+    af.step_dev = c.d_step;
+    af.count = d_grads + n->spec.n_active_params + 1;
+  }
+  HMP_TRY(forward_impl(n, b, d_params, st));
+  const float* g = nullptr;
+  int ldg = 0;
+  if (tg.lin) HMP_TRY(heads_loss(n, b, tg.lin, d_params, args->ignored_label, st, g, ldg));
+  else if (tg.two) HMP_TRY(two_head_loss(n, b, tg.two, args->ignored_label, st, g, ldg));
+  else HMP_TRY(ce_loss(n, b, args->ignored_label, st, g, ldg));
+  c.fin_loss = true;
+  HMP_TRY(backward_impl(n, g, ldg, d_grads, d_params, nullptr, st));
+  if (!d_m || c.adam_done) return HMP_OK;
+  return hmp_net_step_adam(n, const_cast<float*>(d_params), d_grads, d_m, d_v, args, stream);
+}
+
 }  // namespace
+
+extern "C" int hmp_net_step_fwd_bwd(hmp_net* n, const hmp_batch* batch, const float* d_params, float* d_grads,
+                                    const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_grads && args, "hmp_net_step_fwd_bwd: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0, "hmp_net_step_fwd_bwd: the fused step computes one cross entropy (single-output nets)");
+  HMP_CHECK_ARG(batch->d_labels != nullptr, "hmp_net_step_fwd_bwd: labels required");
+  return run_step(n, batch, {}, d_params, d_grads, nullptr, nullptr, args, stream);
+}
+
+extern "C" int hmp_net_step_fused(hmp_net* n, const hmp_batch* batch, float* d_params, float* d_grads, float* d_m, float* d_v,
+                                  const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_grads && d_m && d_v && args, "hmp_net_step_fused: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0, "hmp_net_step_fused: the fused step computes one cross entropy (single-output nets)");
+  HMP_CHECK_ARG(batch->d_labels != nullptr, "hmp_net_step_fused: labels required");
+  return run_step(n, batch, {}, d_params, d_grads, d_m, d_v, args, stream);
+}
+
+extern "C" int hmp_net_step2_fwd_bwd(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                                     float* d_grads, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && args, "hmp_net_step2_fwd_bwd: null argument");
+  HMP_TRY(check_targets(n, batch, targets, "hmp_net_step2_fwd_bwd"));
+  return run_step(n, batch, {targets, nullptr}, d_params, d_grads, nullptr, nullptr, args, stream);
+}
+
+extern "C" int hmp_net_step2_fused(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, float* d_params,
+                                   float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && d_m && d_v && args, "hmp_net_step2_fused: null argument");
+  HMP_TRY(check_targets(n, batch, targets, "hmp_net_step2_fused"));
+  return run_step(n, batch, {targets, nullptr}, d_params, d_grads, d_m, d_v, args, stream);
+}
 
 extern "C" int hmp_net_step_heads_fwd_bwd(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets,
                                           const float* d_params, float* d_grads, const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && args, "hmp_net_step_heads_fwd_bwd: null argument");
   HMP_TRY(check_heads(n, batch, targets, "hmp_net_step_heads_fwd_bwd"));
-  hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = args->training; n->seed = args->seed; n->rng_step = 0; n->step_dev = true;
-  n->d_step = args->d_step ? args->d_step : &n->d_state->step;
-  n->ce_labels = nullptr; n->tgt = nullptr;
-  int r = forward_impl(n, batch, d_params, st);
-  if (r == HMP_OK) {  // the heads in place of the loss kernel: d loss / d z -> d_gout, {loss, valid} per row, dW / db slabs
-    LinHeadArgs a = heads_args(n, batch, targets, d_params, true, args->ignored_label);
-    Scope sc(n, KC_LOSS, st);
-    r = linear_heads_ce_launch(a, st);
-  }
-  if (r == HMP_OK) {
-    n->fin_loss = true;
-    n->head_blocks_now = heads_blocks(batch->n_out);
-    r = backward_impl(n, n->d_gout, n->out_ld, d_grads, d_params, nullptr, st);
-    n->head_blocks_now = 0;
-    n->fin_loss = false;
-  }
-  n->d_step = &n->d_state->step;
-  n->step_dev = false;
-  return r;
+  return run_step(n, batch, {nullptr, targets}, d_params, d_grads, nullptr, nullptr, args, stream);
 }
 
 extern "C" int hmp_net_step_heads_fused(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets, float* d_params,
                                         float* d_grads, float* d_m, float* d_v, const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && batch && targets && d_params && d_grads && d_m && d_v && args, "hmp_net_step_heads_fused: null argument");
-  AdamFuse& af = n->adam_fuse;
-  af.on = n->fuse_mode == 0 ? 0 : 1;
-  af.p = d_params; af.m = d_m; af.v = d_v;
-  af.lr = args->lr; af.b1 = args->beta1; af.b2 = args->beta2; af.eps = args->eps; af.wd = args->weight_decay;
-  af.step_dev = args->d_step ? args->d_step : &n->d_state->step;
-  af.count = d_grads + n->spec.n_active_params + 1;
-  n->adam_done = false;
-  const int r = hmp_net_step_heads_fwd_bwd(n, batch, targets, d_params, d_grads, args, stream);
-  af.on = 0;
-  HMP_TRY(r);
-  if (n->adam_done) return HMP_OK;
-  return hmp_net_step_adam(n, d_params, d_grads, d_m, d_v, args, stream);
+  HMP_TRY(check_heads(n, batch, targets, "hmp_net_step_heads_fused"));
+  return run_step(n, batch, {nullptr, targets}, d_params, d_grads, d_m, d_v, args, stream);
+}
+
+extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
+                                      int64_t* d_counts, void* stream) {
+  HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct2: null argument");
+  HMP_TRY(check_targets(n, batch, targets, "hmp_net_count_correct2"));
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = n->spec.tail_act; ta.state = n->d_state;
+  for (int h = 0; h < 2; ++h) {
+    if (n->has_pools) add_pool(n, batch, targets, h, false, ta);
+    else add_tail(n, batch, targets, h, false, ta);
+  }
+  if (ta.n == 0) return HMP_OK;
+  Scope sc(n, KC_LOSS, st);
+  if (n->has_pools) return pool_tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
+  return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
 }
 
 extern "C" int hmp_net_count_correct_heads(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets,
@@ -2248,11 +2226,7 @@ extern "C" int hmp_net_count_correct_heads(hmp_net* n, const hmp_batch* batch, c
   HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct_heads: null argument");
   HMP_TRY(check_heads(n, batch, targets, "hmp_net_count_correct_heads"));
   hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
-  n->ce_labels = nullptr; n->tgt = nullptr;
-  HMP_TRY(forward_impl(n, batch, d_params, st));
+  HMP_TRY(plain_forward(n, batch, d_params, st));
   LinHeadArgs a = heads_args(n, batch, targets, d_params, false, 0);
   Scope sc(n, KC_LOSS, st);
   return linear_heads_count_launch(a, reinterpret_cast<long long*>(d_counts), st);
@@ -2265,11 +2239,7 @@ extern "C" int hmp_net_count_correct_rooms(hmp_net* n, const hmp_batch* batch, c
                 "hmp_net_count_correct_rooms: a two-headed net counts with hmp_net_count_correct2 / hmp_net_count_correct_heads");
   HMP_CHECK_ARG(batch->n_out == 0 || batch->d_labels, "hmp_net_count_correct_rooms: the batch has no labels");
   hipStream_t st = (hipStream_t)stream;
-  read_env(n);
-  g_bf16_all = n->env.bf16_all;
-  n->training = 0; n->seed = 0; n->rng_step = 0; n->step_dev = false;
-  n->ce_labels = nullptr; n->tgt = nullptr;  // no fused CE inside an eval forward
-  HMP_TRY(forward_impl(n, batch, d_params, st));
+  HMP_TRY(plain_forward(n, batch, d_params, st));
   Scope sc(n, KC_LOSS, st);
   return count_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
                            reinterpret_cast<long long*>(d_counts), reinterpret_cast<long long*>(d_confusion), st);

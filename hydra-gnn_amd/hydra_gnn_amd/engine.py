@@ -508,16 +508,9 @@ class NativeNet:
         eval-mode forward, argmax of act(final state), comparison under the masks).  Nothing synchronises."""
         flat = self.flat_params(full_check=False)
         h = self.make_batch(data)
-        dev = flat.device
-        if counts.dtype != torch.int64 or counts.numel() < 4 or not counts.is_contiguous() or counts.device != dev:
-            raise _lib.HydraMPError("counts must be a contiguous int64[4] tensor on the model's device")
+        _check_counts4(counts, flat.device)
         tg = _head_targets(self, h, labels, masks)
-        with torch.cuda.device(dev):
-            self._ensure_workspace(h, dev)
-            _lib.check(self._lib.hmp_net_count_correct2(self._handle, C.byref(h.c), C.byref(tg), flat.data_ptr(), counts.data_ptr(),
-                                                        _lib.stream_ptr()))
-            self._fwd_token += 1
-            self._plan_key = self._plan_tensors = None
+        self._count("hmp_net_count_correct2", h, flat.device, C.byref(tg), flat.data_ptr(), counts.data_ptr())
         return counts
 
     def count_correct_heads(self, data, labels, mask, members, counts: torch.Tensor) -> torch.Tensor:
@@ -526,16 +519,9 @@ class NativeNet:
         on the member rows).  Nothing synchronises."""
         flat = self.flat_params(full_check=False)
         h = self.make_batch(data)
-        dev = flat.device
-        if counts.dtype != torch.int64 or counts.numel() < 4 or not counts.is_contiguous() or counts.device != dev:
-            raise _lib.HydraMPError("counts must be a contiguous int64[4] tensor on the model's device")
+        _check_counts4(counts, flat.device)
         tg = _linear_head_targets(self, h, labels, mask, members)
-        with torch.cuda.device(dev):
-            self._ensure_workspace(h, dev)
-            _lib.check(self._lib.hmp_net_count_correct_heads(self._handle, C.byref(h.c), C.byref(tg), flat.data_ptr(),
-                                                             counts.data_ptr(), _lib.stream_ptr()))
-            self._fwd_token += 1
-            self._plan_key = self._plan_tensors = None
+        self._count("hmp_net_count_correct_heads", h, flat.device, C.byref(tg), flat.data_ptr(), counts.data_ptr())
         return counts
 
     def count_correct_rooms(self, batch, labels, counts: torch.Tensor, ignored_label: int = 25,
@@ -563,14 +549,18 @@ class NativeNet:
 
         check_count_buffers(counts, confusion, self.n_classes, dev)
         members = row_members(members, int(h.c.n_out), dev)
+        self._count("hmp_net_count_correct_rooms", h, dev, flat.data_ptr(), members.data_ptr() if members is not None else None,
+                    int(ignored_label), counts.data_ptr(), confusion.data_ptr() if confusion is not None else None)
+        return counts
+
+    def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
+        """the count entries' common block: ``entry(handle, batch, *args, stream)`` (eval-mode forward + count on the device),
+        which overwrites the activations of any earlier forward()"""
         with torch.cuda.device(dev):
             self._ensure_workspace(h, dev)
-            _lib.check(self._lib.hmp_net_count_correct_rooms(
-                self._handle, C.byref(h.c), flat.data_ptr(), members.data_ptr() if members is not None else None, int(ignored_label),
-                counts.data_ptr(), confusion.data_ptr() if confusion is not None else None, _lib.stream_ptr()))
+            _lib.check(getattr(self._lib, entry)(self._handle, C.byref(h.c), *args, _lib.stream_ptr()))
             self._fwd_token += 1
             self._plan_key = self._plan_tensors = None
-        return counts
 
     @property
     def n_classes(self) -> int:
@@ -630,6 +620,11 @@ class NativeNet:
         step, status = C.c_int32(), C.c_int32()
         _lib.check(self._lib.hmp_net_read_state(self._handle, C.byref(step), C.byref(status), _lib.stream_ptr()))
         return step.value, status.value
+
+
+def _check_counts4(counts: torch.Tensor, dev) -> None:
+    if counts.dtype != torch.int64 or counts.numel() < 4 or not counts.is_contiguous() or counts.device != dev:
+        raise _lib.HydraMPError("counts must be a contiguous int64[4] tensor on the model's device")
 
 
 def _head_targets(net: NativeNet, h: _BatchHolder, labels, masks) -> _lib.HeadTargets:
@@ -709,7 +704,12 @@ class TrainStep:
     Gradients are SUMS over valid labels; ``{loss_sum, count}`` ride in the tail of the same flat
     buffer, so one all-reduce(sum) of ``n_active + 2`` floats makes the N-rank update equal to the
     single-process full-batch update (count-weighted mean), and every rank applies the identical Adam.
+
+    The step kinds below differ only in their native entries (phase A alone, phases A + B in one call) and the targets
+    they pass; this class runs every kind's step.
     """
+
+    ENTRIES = ("hmp_net_step_fwd_bwd", "hmp_net_step_fused")
 
     def __init__(self, net: NativeNet, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  ignored_label: int = 25, seed: int = 0, training: bool = True, use_graph: bool = True,
@@ -740,6 +740,7 @@ class TrainStep:
         self.step_ctr = torch.zeros(4, dtype=torch.int32, device=dev)
         self.args.d_step = self.step_ctr.data_ptr()
         self._holder = None
+        self._targets = ()  # the entries' arguments between the batch and the parameters: byref(targets) but for one head
         self._batch_key = None
         self._data_ref = None
         if broadcast_init and self._world() > 1:
@@ -773,49 +774,62 @@ class TrainStep:
 
     def _phase_a(self, h, st):
         net = self.net
-        _lib.check(net._lib.hmp_net_step_fwd_bwd(net._handle, C.byref(h.c), self.flat.data_ptr(), self.grads.data_ptr(),
-                                                 C.byref(self.args), st))
+        _lib.check(getattr(net._lib, self.ENTRIES[0])(net._handle, C.byref(h.c), *self._targets, self.flat.data_ptr(),
+                                                      self.grads.data_ptr(), C.byref(self.args), st))
 
     def _phase_ab(self, h, st):
         """single rank: both phases in one native call (Adam may ride in the gradient un-pack kernel)"""
         net = self.net
-        _lib.check(net._lib.hmp_net_step_fused(net._handle, C.byref(h.c), self.flat.data_ptr(), self.grads.data_ptr(),
-                                               self.m.data_ptr(), self.v.data_ptr(), C.byref(self.args), st))
+        _lib.check(getattr(net._lib, self.ENTRIES[1])(net._handle, C.byref(h.c), *self._targets, self.flat.data_ptr(),
+                                                      self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                      C.byref(self.args), st))
 
     def _phase_b(self, st):
         net = self.net
         _lib.check(net._lib.hmp_net_step_adam(net._handle, self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
                                               self.v.data_ptr(), C.byref(self.args), st))
 
+    def _eager(self, h) -> None:
+        st = _lib.stream_ptr()
+        if self._world() == 1 and not self.force_collective:
+            self._phase_ab(h, st)
+        else:
+            self._phase_a(h, st)
+            self._all_reduce()
+            self._phase_b(st)
+
     def __call__(self, data, labels: torch.Tensor) -> None:
+        self._step(data, None, (labels,), labels, None)
+
+    def _step(self, data, tag, tensors, labels, make_targets) -> None:
+        """one step on ``data`` with the batch's ``labels`` or the targets ``make_targets(holder)`` builds; ``tensors`` (labels,
+        masks ...) and ``tag`` key the descriptor cache"""
         net = self.net
         if net.flat_params(full_check=False) is not self.flat:
-            raise _lib.HydraMPError("model parameters were moved after TrainStep was created")
-        # the batch descriptor of an unchanged batch object is reused (hydra_gnn_amd.data.HeteroData stamps every mutation;
-        # foreign containers are described afresh every step)
+            raise _lib.HydraMPError(f"model parameters were moved after {type(self).__name__} was created")
+        # the descriptor (and targets) of an unchanged batch object is reused (hydra_gnn_amd.data.HeteroData stamps every
+        # mutation; foreign containers are described afresh every step)
         stamp = getattr(data, "_mutation_stamp", None)
-        key = (id(data), stamp(), id(labels), labels._version) if stamp is not None else None
+        key = None
+        if stamp is not None:
+            key = (id(data), stamp(), tag) + tuple([(id(t), t._version) if t is not None else None for t in tensors])
         if key is not None and key == self._batch_key:
             h = self._holder
         else:
             h = net.make_batch(self.view(data) if self.view is not None else data, labels)
+            self._targets = () if make_targets is None else (C.byref(make_targets(h)),)
             self._batch_key = key if not h.converted else None
-            self._data_ref = (data, labels)  # keeps id() unique while the key is live
+            self._data_ref = (data, tensors)  # keeps id() unique while the key is live
+        self._holder = h
         dev = self.flat.device
         with torch.cuda.device(dev):
             net._ensure_workspace(h, dev)
             net._fwd_token += 1  # the step overwrites the activations of any earlier forward()
             net._plan_key = net._plan_tensors = None
             if not self.use_graph:
-                st = _lib.stream_ptr()
-                if self._world() == 1 and not self.force_collective:
-                    self._phase_ab(h, st)
-                else:
-                    self._phase_a(h, st)
-                    self._all_reduce()
-                    self._phase_b(st)
-                self._holder = h
+                self._eager(h)
                 return
+            # the captured graph holds the descriptor's pointers (labels and masks among them: h.keep)
             key = (tuple(h.n_nodes), tuple(h.n_edges), tuple(t.data_ptr() for t in h.keep), id(net._ws))
             if self._graphs is None or key != self._key:
                 self._capture(h, key)
@@ -881,13 +895,7 @@ class TrainStep:
         net._plan_key = net._plan_tensors = None
         self._batch_key = None
         self._holder = holder
-        st = _lib.stream_ptr()
-        if self._world() == 1 and not self.force_collective:
-            self._phase_ab(holder, st)
-        else:
-            self._phase_a(holder, st)
-            self._all_reduce()
-            self._phase_b(st)
+        self._eager(holder)
 
     def set_lr(self, lr: float) -> None:
         """Follow a learning-rate scheduler (``StepLR`` in ``base_training_job.py:186-188``): takes effect with the next
@@ -917,72 +925,16 @@ class TwoHeadTrainStep(TrainStep):
     divided by the total count, the reference's ``loss.item()``.  The dropout masks are the autograd path's (same seed, draw number
     = the step counter), so a step equals ``net(batch)`` -> ``net.loss`` -> ``backward`` -> ``torch.optim.Adam``."""
 
+    ENTRIES = ("hmp_net_step2_fwd_bwd", "hmp_net_step2_fused")
+
     def __init__(self, net: NativeNet, lr: float, weight_decay: float = 0.0, ignored_label: int = -100, **kw):
         if net.aux_readout is None:
             raise _lib.HydraMPError("TwoHeadTrainStep needs a two-headed net (aux_readout); use TrainStep")
         super().__init__(net, lr, weight_decay=weight_decay, ignored_label=ignored_label, **kw)
-        self._targets = None
-
-    def _phase_a(self, h, st):
-        net = self.net
-        _lib.check(net._lib.hmp_net_step2_fwd_bwd(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
-                                                  self.grads.data_ptr(), C.byref(self.args), st))
-
-    def _phase_ab(self, h, st):
-        net = self.net
-        _lib.check(net._lib.hmp_net_step2_fused(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
-                                                self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), C.byref(self.args), st))
 
     def __call__(self, data, labels, masks=None) -> None:
         tensors = tuple(labels) + (tuple(masks) if masks is not None else ())
-        self._step(data, masks is None, tensors, lambda h: _head_targets(self.net, h, labels, masks))
-
-    def _step(self, data, tag, tensors, make_targets) -> None:
-        """one step on ``data`` with the targets ``make_targets(holder)`` builds from ``tensors`` (reused, with the descriptor, while
-        ``data`` and every tensor are unchanged)"""
-        net = self.net
-        if net.flat_params(full_check=False) is not self.flat:
-            raise _lib.HydraMPError(f"model parameters were moved after {type(self).__name__} was created")
-        stamp = getattr(data, "_mutation_stamp", None)
-        key = None
-        if stamp is not None:
-            key = (id(data), stamp(), tag) + tuple((id(t), t._version) if t is not None else None for t in tensors)
-        if key is not None and key == self._batch_key:
-            h = self._holder
-        else:
-            h = net.make_batch(self.view(data) if self.view is not None else data)
-            self._targets = make_targets(h)
-            self._batch_key = key if not h.converted else None
-            self._data_ref = (data, tensors)  # keeps id() unique while the key is live
-        self._holder = h
-        dev = self.flat.device
-        with torch.cuda.device(dev):
-            net._ensure_workspace(h, dev)
-            net._fwd_token += 1
-            net._plan_key = net._plan_tensors = None
-            if not self.use_graph:
-                st = _lib.stream_ptr()
-                if self._world() == 1 and not self.force_collective:
-                    self._phase_ab(h, st)
-                else:
-                    self._phase_a(h, st)
-                    self._all_reduce()
-                    self._phase_b(st)
-                return
-            # the captured graph holds the descriptor's pointers (labels and masks among them: h.keep)
-            gkey = (tuple(h.n_nodes), tuple(h.n_edges), tuple(t.data_ptr() for t in h.keep), id(net._ws))
-            if self._graphs is None or gkey != self._key:
-                self._capture(h, gkey)
-            ga, gb = self._graphs
-            cur = torch.cuda.current_stream()
-            self._stream.wait_stream(cur)
-            with torch.cuda.stream(self._stream):
-                st = _lib.stream_ptr()
-                _lib.check(net._lib.hmp_graph_launch(ga, st))
-                if gb is not None:
-                    self._all_reduce()
-                    _lib.check(net._lib.hmp_graph_launch(gb, st))
-            cur.wait_stream(self._stream)
+        self._step(data, masks is None, tensors, None, lambda h: _head_targets(self.net, h, labels, masks))
 
     def run(self, holder) -> None:
         raise _lib.HydraMPError("TwoHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")
@@ -1031,38 +983,28 @@ class LinearHeadTrainStep(TwoHeadTrainStep):
     """The loop body of ``SemiSupervisedTrainingJob.train`` for the homogeneous two-headed models (HomogeneousNetwork /
     HomogeneousNeuralTreeNetwork with ``output_dim_dict``): phase A = plan + forward + the model's tail (act, dropout) + the two
     learned linear heads + masked CE of both + backward (``hmp_net_step_heads_fwd_bwd``), [all-reduce], phase B = Adam over
-    [0, n_active), the heads included -- :class:`TwoHeadTrainStep`'s eager / graph / collective machinery with
+    [0, n_active), the heads included -- :class:`TrainStep`'s eager / graph / collective machinery with
     ``hmp_linear_head_targets``.
 
     ``step(data, labels=None, mask=None)``: labels default to ``data.y``, the mask to ``data.train_mask``; the room head's rows are
     ``data.room_mask``, the object head's ``data.<object_attr>`` (H-tree: ``object_mask``) or, with ``object_attr`` None, the
     complement of the room rows (the baseline's ``~room_mask``, computed on the device by the head kernel)."""
 
+    ENTRIES = ("hmp_net_step_heads_fwd_bwd", "hmp_net_step_heads_fused")
+
     def __init__(self, net: NativeNet, lr: float, weight_decay: float = 0.0, ignored_label: int = -100,
                  object_attr: Optional[str] = None, **kw):
         if net.heads is None:
             raise _lib.HydraMPError("LinearHeadTrainStep needs a net with linear heads")
         TrainStep.__init__(self, net, lr, weight_decay=weight_decay, ignored_label=ignored_label, **kw)
-        self._targets = None
         self.object_attr = object_attr
-
-    def _phase_a(self, h, st):
-        net = self.net
-        _lib.check(net._lib.hmp_net_step_heads_fwd_bwd(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
-                                                       self.grads.data_ptr(), C.byref(self.args), st))
-
-    def _phase_ab(self, h, st):
-        net = self.net
-        _lib.check(net._lib.hmp_net_step_heads_fused(net._handle, C.byref(h.c), C.byref(self._targets), self.flat.data_ptr(),
-                                                     self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                     C.byref(self.args), st))
 
     def __call__(self, data, labels=None, mask=None) -> None:
         labels = data.y if labels is None else labels
         mask = data.train_mask if mask is None else mask
         members = (data.room_mask, getattr(data, self.object_attr) if self.object_attr is not None else None)
         tensors = (labels, mask) + members
-        self._step(data, None, tensors, lambda h: _linear_head_targets(self.net, h, labels, mask, members))
+        self._step(data, None, tensors, None, lambda h: _linear_head_targets(self.net, h, labels, mask, members))
 
     def run(self, holder) -> None:
         raise _lib.HydraMPError("LinearHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")

@@ -4,9 +4,11 @@
   draw number and the status bits must not restart (``base_training_job.py:202-216`` + ``torch.optim.Adam`` semantics);
 * Adam's ``t`` belongs to the optimiser (``state['step']``), not to the network: a second ``TrainStep`` starts at ``t = 1``;
 * ``StepLR`` (``base_training_job.py:186-188``) changes the rate between epochs: ``TrainStep.set_lr``;
-* stale-descriptor and stale-activation hazards of the host side fail loudly / are not there.
+* stale-descriptor and stale-activation hazards of the host side fail loudly / are not there;
+* a step the executor refuses leaves no step state behind for the next backward.
 """
 import copy
+import ctypes as C
 
 import numpy as np
 import pytest
@@ -217,3 +219,40 @@ def test_converted_inputs_are_not_cached_across_steps():
     assert abs(sa.loss() - sb.loss()) < 1e-6
     for (n, a), (_, b) in zip(net_a.named_parameters(), net_b.named_parameters()):
         assert torch.equal(a, b), n
+
+
+def test_refused_step_leaves_the_forwards_dropout_to_its_backward():
+    """A training step the executor refuses (here: n_out off by one) must leave no state of its own behind: the autograd backward
+    of the training-mode forward before it draws that forward's dropout masks, not masks numbered by the refused step's
+    optimiser counter.  GAT: its backward replays the attention-dropout draw (feature dropout reads its keep bits back from the
+    stored activations)."""
+    batch = workloads.config2_batch(4)
+    gb = batch.to(DEV)
+    y = gb["rooms"].y
+
+    def grads(refused_step):
+        torch.manual_seed(7)
+        net = HeterogeneousNetwork(input_dim_dict={"objects": 306, "rooms": 6}, output_dim=26, dropout=0.25, conv_block="GAT",
+                                   GAT_hidden_dims=[32, 32], GAT_heads=[2, 2, 2], GAT_concats=[True, True, False]).to(DEV)
+        net.train()
+        out = net(gb)
+        if refused_step:
+            nat = net.native()
+            h = nat.make_batch(gb, y)
+            bad = type(h.c).from_buffer_copy(h.c)
+            bad.n_out += 1
+            ctr = torch.full((4,), 1000, dtype=torch.int32, device=DEV)  # far from the forward's draw number (1)
+            g = torch.zeros(nat.n_params + 4, dtype=torch.float32, device=DEV)
+            args = _lib.TrainArgs(0.002, 0.9, 0.999, 1e-8, 0.0, 25, net._seed, 1)
+            args.d_step = ctr.data_ptr()
+            rc = nat._lib.hmp_net_step_fwd_bwd(nat._handle, C.byref(bad), nat.flat_params(full_check=False).data_ptr(),
+                                               g.data_ptr(), C.byref(args), _lib.stream_ptr())
+            assert rc != 0, "the step must refuse a batch whose n_out is off by one"
+        net.loss(out, y, y != 25).backward()
+        torch.cuda.synchronize()
+        return {n: p.grad.detach().cpu() for n, p in net.named_parameters() if p.grad is not None}
+
+    ref, got = grads(False), grads(True)
+    assert ref.keys() == got.keys() and ref
+    for n in ref:
+        assert torch.equal(ref[n], got[n]), n
