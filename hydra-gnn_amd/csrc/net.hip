@@ -177,11 +177,6 @@ struct hmp_net {
   GradReduceDyn dyn;
   StepCall call;  // the entry call in progress (StepGuard)
 
-  // parallel branches (side streams; under capture they become branches of the hipGraph)
-  bool use_branches = false;
-  int branch_mask = 0;     // HMP_BRANCH bits: 1 = pack + layer-0 projection next to the plan, 2 = weight gradients next to the backward chain
-  bool dw_branch = false;  // weight-gradient GEMMs per layer on a side stream instead of one merged launch
-  int dw_mode = -1;        // HMP_DW_BRANCH override (0 / 1), -1 = automatic
   int compute_bf16 = 0;    // hmp_net_set_compute: large grouped GEMMs on the bf16 matrix pipe (fp32 storage and accumulation)
   int fuse_mode = -1;      // HMP_FUSE override (0 / 1), -1 = automatic: row-local GEMMs ride in the aggregation kernels
   bool fuse_now = false;   // decision for the current batch
@@ -196,9 +191,6 @@ struct hmp_net {
   bool has_pools = false;
   int head_pool[2] = {-1, -1};
   float* d_dpool[2] = {nullptr, nullptr};
-  hipStream_t side[2] = {nullptr, nullptr};
-  hipEvent_t evs[32];
-  int n_evs = 0, ev_i = 0;
 
   // profiling
   bool prof = false;
@@ -775,15 +767,6 @@ struct Scope {
   }
 };
 
-// `to` waits for everything enqueued on `from` so far (fork when to is a side stream, join when to is the main stream)
-int fork_to(hmp_net* n, hipStream_t from, hipStream_t to) {
-  hipEvent_t e = n->evs[n->ev_i];
-  n->ev_i = (n->ev_i + 1) % n->n_evs;
-  HMP_HIP(hipEventRecord(e, from));
-  HMP_HIP(hipStreamWaitEvent(to, e, 0));
-  return HMP_OK;
-}
-
 // profile classes (hmp_net_profile_read); slot 13 (chain) is retired and always 0
 enum { KC_PLAN = 0, KC_PACK, KC_GEMM_FWD, KC_AGG_FWD, KC_LOSS, KC_AGG_BWD, KC_GEMM_BWD, KC_GRAD_REDUCE, KC_ADAM, KC_GAT_FWD, KC_GAT_BWD, KC_POOL, KC_FRONT };
 
@@ -898,11 +881,9 @@ int h_ld(const hmp_net* n, int l, int t) { return is_input(n, l, t) ? n->batch.l
 // bf16 compute mode: only the throughput-bound regime (>= 1024 64x64 tiles in the call) leaves the exact fp32 kernel
 // HMP_BF16_ALL=1 (tests): every GEMM call of a bf16-mode net takes the bf16 kernel whatever its size, so that a graph the
 // float64 oracle can hold (4 x 10^4 objects) runs exactly the decisions of the 10^6-object regime (BASELINE config 5)
-static thread_local bool g_bf16_all = false;  // EnvSwitches::bf16_all of the call in progress (set by read_env's callers)
-inline bool bf16_all() { return g_bf16_all; }
-
-bool gemm_takes_bf16(const std::vector<GemmProblem>& ps, bool allow_bf16) {
-  if (allow_bf16 && bf16_all()) return true;
+bool gemm_takes_bf16(const hmp_net* n, const std::vector<GemmProblem>& ps) {
+  const bool allow_bf16 = n->compute_bf16 != 0;
+  if (allow_bf16 && n->env.bf16_all) return true;
   int64_t tiles64 = 0;
   double work = 0.0;
   for (const GemmProblem& p : ps) {
@@ -913,11 +894,11 @@ bool gemm_takes_bf16(const std::vector<GemmProblem>& ps, bool allow_bf16) {
 }
 
 // launches a list of GEMM problems in groups of GEMM_MAX_PROB; ksplit_out receives the split of each problem
-int gemm_many(std::vector<GemmProblem>& ps, bool want_split, hipStream_t st, std::vector<int>* ksplit_out, bool allow_bf16 = false) {
-  bool bf16 = gemm_takes_bf16(ps, allow_bf16);
+int gemm_many(const hmp_net* n, std::vector<GemmProblem>& ps, bool want_split, hipStream_t st, std::vector<int>* ksplit_out) {
+  bool bf16 = gemm_takes_bf16(n, ps);
   for (const GemmProblem& p : ps)
     if (p.a_bf16 || p.c_bf16 || p.b_bf16 || p.h_bf16) {  // bf16-stored operands exist only for the bf16 kernel
-      HMP_CHECK_ARG(allow_bf16, "net: bf16-stored GEMM operand outside bf16 compute mode");
+      HMP_CHECK_ARG(n->compute_bf16 != 0, "net: bf16-stored GEMM operand outside bf16 compute mode");
       bf16 = true;
     }
   for (size_t base = 0; base < ps.size(); base += GEMM_MAX_PROB) {
@@ -933,6 +914,19 @@ int gemm_many(std::vector<GemmProblem>& ps, bool want_split, hipStream_t st, std
   return HMP_OK;
 }
 
+// bf16 compute mode: layer j's aggregation (forward) and transposed aggregation (backward) take the one-wavefront-per-row shape
+// that reads bf16 rows -- a SAGE layer outside the small-batch sequence whose every written node type is (128, 256] wide
+bool rows_kernel_bf16(const hmp_net* n, const hmp_batch* b, int j) {
+  const LayerLayout& Y = n->lay[j];
+  if (Y.kind == HMP_CONV_GAT || n->fuse_now || !n->env.z16) return false;
+  for (int t = 0; t < n->T; ++t) {
+    if (Y.roff[t] < 0 || b->n_nodes[t] == 0) continue;
+    const int f = fpad(n->spec.layers[j].out_dim[t]);
+    if (f <= 128 || f > 256) return false;
+  }
+  return true;
+}
+
 void fill_plan_batch(hmp_net* n, const hmp_batch* b, PlanBatch& pb);
 
 // Front kernel arguments (layer-0 projection + plan + pack in one launch); false when the batch / network does not fit its
@@ -945,9 +939,6 @@ bool build_front(hmp_net* n, const hmp_batch* b, const float* d_params, FrontArg
   // GAT layers: the projection's operand is the pack's OUTPUT (att . W rows), so only plan and pack share the launch (the plan,
   // 19 us at config 3, runs behind the 46 us pack); the link pass (t_pos) follows as its own launch
   const bool proj = Y.kind == HMP_CONV_SAGE && !n->any_gat;
-  // HMP_BRANCH bit 0 forks a side stream for pack + layer-0 projection BEFORE this launch: a front launch on the main stream that
-  // holds the pack (GAT: the projection's operand) would race with the projection on the side stream -> separate launches there
-  if (!proj && n->use_branches && (n->branch_mask & 1)) return false;
   memset(&fa, 0, sizeof(fa));
   // ---- projection problems
   for (int s = 0; s < n->T && proj; ++s) {
@@ -1029,12 +1020,6 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
   n->batch = *b;
   n->training = n->call.training; n->seed = n->call.seed; n->rng_step = n->call.rng_step;
   n->reuse_plan = b->plan_valid != 0;
-  // The parameter pack and the layer-0 projection do not depend on the plan: they run on a side stream next to the
-  // (4-5 dependent launches of the) plan build and join before the first aggregation.  Under capture this becomes
-  // two parallel branches of the hipGraph.
-  hipStream_t main_st = st;
-  hipStream_t side = (n->use_branches && (n->branch_mask & 1)) ? n->side[0] : main_st;
-  if (side != main_st) HMP_TRY(fork_to(n, main_st, side));
   n->fuse_now = fuse_small(n, b);
   memset(n->h16, 0, sizeof(n->h16));
   // Small batches, SAGE layer 0: projection (reading the stacked weights straight from the flat parameters), plan and pack
@@ -1043,31 +1028,27 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
   FrontArgs fa;
   const bool front = n->fuse_now && build_front(n, b, d_params, fa);
   if (front) {
-    Scope sc(n, KC_FRONT, main_st);
-    HMP_TRY(front_launch(fa, main_st));
+    Scope sc(n, KC_FRONT, st);
+    HMP_TRY(front_launch(fa, st));
     if (fa.need_tpos && fa.plan_blocks > 0) {
       PlanBatch pb;
       fill_plan_batch(n, b, pb);
-      HMP_TRY(plan_link_launch(pb, main_st));
+      HMP_TRY(plan_link_launch(pb, st));
     }
     for (int e = 0; e < n->ET; ++e) {  // what run_plan records on the host
       hmp_plan& P = n->plan[e];
       P.n_src = b->n_nodes[S.edge_src[e]]; P.n_dst = b->n_nodes[S.edge_dst[e]]; P.n_edges = b->n_edges[e];
     }
   } else {
-    Scope sc(n, KC_PACK, side);
-    HMP_TRY(pack_launch(n->d_pack_segs, n->pack_sb, d_params, n->d_packed, n->call.d_step, &n->d_state->last_step, side));
+    Scope sc(n, KC_PACK, st);
+    HMP_TRY(pack_launch(n->d_pack_segs, n->pack_sb, d_params, n->d_packed, n->call.d_step, &n->d_state->last_step, st));
   }
   bool z_done = false;
   for (int l = 0; l < n->L; ++l) {
     const hmp_layer_spec& Ls = S.layers[l];
     LayerLayout& Y = n->lay[l];
-    st = (l == 0) ? side : main_st;
     bool z16 = false;  // this layer's projected rows are stored as bf16 (decided with the projection, read by the aggregation)
-    if (l == 0 && !front && n->any_agg_first) {  // the segment means of layer 0 read the plan: build it first (no side stream here)
-      if (!n->reuse_plan) HMP_TRY(run_plan(n, b, main_st));
-      if (side != main_st) HMP_TRY(fork_to(n, main_st, side));
-    }
+    if (l == 0 && !front && n->any_agg_first && !n->reuse_plan) HMP_TRY(run_plan(n, b, st));  // the segment means of layer 0 read the plan
     if (l == 0 && front && fa.n_prob > 0) {
       // projection, plan and pack already ran in the front kernel
     } else if (!z_done) {  // grouped projection (skipped when the previous layer's aggregation kernel already produced Z[l])
@@ -1088,22 +1069,14 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       }
       // bf16 compute mode, 10^6-row regime: the projected rows are only ever gathered by this layer's aggregation, so they are
       // stored as bf16 (half the projection's write and half the gather's read traffic) -- when the bf16 GEMM runs AND the
-      // aggregation takes its one-wavefront-per-row shape (every output width in (128, 256]), the one that reads bf16 rows
-      if (Y.kind != HMP_CONV_GAT && !n->fuse_now && gemm_takes_bf16(ps, n->compute_bf16 != 0)) {
-        int fmin = 1 << 30, fmax = 0;
-        for (int t = 0; t < n->T; ++t) {
-          if (Y.roff[t] < 0 || b->n_nodes[t] == 0) continue;
-          const int f = fpad(Ls.out_dim[t]);
-          fmin = f < fmin ? f : fmin;
-          fmax = f > fmax ? f : fmax;
-        }
-        z16 = fmax <= 256 && fmin > 128;
+      // aggregation reads bf16 rows
+      if (rows_kernel_bf16(n, b, l) && gemm_takes_bf16(n, ps)) {
+        z16 = true;
         for (GemmProblem& p : ps) z16 = z16 && (p.ldc & 3) == 0;
-        if (!n->env.z16) z16 = false;
         if (z16)
           for (GemmProblem& p : ps) p.c_bf16 = 1;
       }
-      HMP_TRY(gemm_many(ps, false, st, nullptr, n->compute_bf16 != 0));
+      HMP_TRY(gemm_many(n, ps, false, st, nullptr));
     }
     if (n->any_agg_first && !z_done) {
       // aggregate-first convs: mean of the SOURCE rows per destination row, then the destination-sized projection into the conv's
@@ -1135,15 +1108,11 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
       }
       if (!pa.empty()) {
         Scope sg(n, KC_GEMM_FWD, st);
-        HMP_TRY(gemm_many(pa, false, st, nullptr, n->compute_bf16 != 0));
+        HMP_TRY(gemm_many(n, pa, false, st, nullptr));
       }
     }
     z_done = false;
-    if (l == 0 && !front) {
-      if (!n->reuse_plan && !n->any_agg_first) HMP_TRY(run_plan(n, b, main_st));
-      if (side != main_st) HMP_TRY(fork_to(n, side, main_st));  // join
-      st = main_st;
-    }
+    if (l == 0 && !front && !n->reuse_plan && !n->any_agg_first) HMP_TRY(run_plan(n, b, st));
     if (Y.kind == HMP_CONV_GAT) {
       Scope sc(n, KC_GAT_FWD, st);
       GatDyn dyn = make_gat_dyn(n, b);
@@ -1255,7 +1224,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
             const hmp_conv_spec& C = S.layers[l + 1].convs[c];
             work += (double)b->n_nodes[C.src] * fpad(C.f_out) * n->dim[l + 1][C.src];
           }
-          hb = work >= 1e9 || bf16_all();  // gemm_takes_bf16's work criterion
+          hb = work >= 1e9 || n->env.bf16_all;  // gemm_takes_bf16's work criterion
         }
         if (!n->env.h16) hb = false;
         if (hb) {
@@ -1315,15 +1284,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     n->dyn.n_slabs[HEAD_SLAB_ID] = (unsigned char)n->call.head_blocks;
     n->dyn.slab_stride[HEAD_SLAB_ID] = (int)n->head_slab_stride;
   }
-  {
-    // measured on MI355X (bench.py configs 2/3/4): below ~4k nodes per batch every kernel is launch-bound and one merged
-    // weight-gradient launch wins (+2.5 %); above, overlapping the per-layer launches with the backward chain wins
-    // (+4 % at 6k nodes, +10 % at 12k)
-    int total_nodes = 0;
-    for (int t = 0; t < n->T; ++t) total_nodes += b->n_nodes[t];
-    n->dw_branch = n->use_branches && (n->branch_mask & 2) && (n->dw_mode >= 0 ? n->dw_mode == 1 : total_nodes > 4096);
-  }
-  std::vector<GemmProblem> wps;  // weight-gradient problems of all layers (merged mode)
+  std::vector<GemmProblem> wps;  // weight-gradient problems of all layers (one launch after the loop)
   std::vector<int> wids;
   bool fin_early = false;
   bool g16[HMP_MAX_LAYERS + 2];  // g16[l]: the input gradients G[l][*] were stored as bf16 by layer l's input-gradient GEMM
@@ -1437,14 +1398,6 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         HMP_TRY(agg_bwd_launch(a, st));
       }
     }
-    // dZ[l] is complete.  Weight-gradient GEMMs: either ALL layers in one grouped split-K launch after the loop
-    // (default: one launch with ~1k workgroups instead of L launches, and no cross-queue fork per layer -- each fork
-    // costs ~5 us of dependency latency under graph replay), or per layer on a side stream (HMP_DW_BRANCH=1).
-    hipStream_t wst = st;
-    if (n->use_branches && n->dw_branch) {
-      wst = n->side[1];
-      HMP_TRY(fork_to(n, st, wst));
-    }
     const bool need_dx = !dx_fused && ((l > 0) || (d_gx != nullptr));
     // aggregate-first convs: dM = dZ_block * W_l (destination-sized), ahead of the launch whose epilogue scatters it
     auto dz_at = [&](int t, int col) -> const float* {
@@ -1475,7 +1428,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       }
       if (!pp.empty()) {
         Scope sp(n, KC_GEMM_BWD, st);
-        HMP_TRY(gemm_many(pp, false, st, nullptr, n->compute_bf16 != 0));
+        HMP_TRY(gemm_many(n, pp, false, st, nullptr));
       }
     }
     // the gradient the source rows of aggregate-first conv c receive: the segment mean's transpose of dM
@@ -1523,19 +1476,9 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         SrcTerm T;
         if (Y.ncols[s] == 0 && b->n_nodes[s] >= 32768 && src_term(s, T)) big_alone = true;
       }
-      if (l > 0 && !n->fuse_now && n->lay[l - 1].kind != HMP_CONV_GAT &&
-          (gemm_takes_bf16(ps, n->compute_bf16 != 0) || (n->compute_bf16 != 0 && big_alone))) {
-        const hmp_layer_spec& Lp = S.layers[l - 1];
-        int fmin = 1 << 30, fmax = 0;
-        for (int t = 0; t < n->T; ++t) {
-          if (n->lay[l - 1].roff[t] < 0 || b->n_nodes[t] == 0) continue;
-          const int f = fpad(Lp.out_dim[t]);
-          fmin = f < fmin ? f : fmin;
-          fmax = f > fmax ? f : fmax;
-        }
-        bool ok = fmax <= 256 && fmin > 128;
+      if (l > 0 && rows_kernel_bf16(n, b, l - 1) && (gemm_takes_bf16(n, ps) || (n->compute_bf16 != 0 && big_alone))) {
+        bool ok = true;
         for (GemmProblem& p : ps) ok = ok && (p.ldc & 3) == 0;
-        if (!n->env.z16) ok = false;
         if (ok) {
           for (GemmProblem& p : ps) p.c_bf16 = 1;
           g16[l] = true;
@@ -1558,7 +1501,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         HMP_TRY(seg_mean_rows_t_launch(Q.dmrows, Q.ld_m, Q.ld_m, T.P->d_t_rowptr, T.P->d_t_col, T.degf, p.M, nullptr, 0, 0, 0, 0, 1.f, sm, Q.ld_m, 0, st));
         p.Cadd = sm; p.ldadd = Q.ld_m;
       }
-      if (!ps.empty()) HMP_TRY(gemm_many(ps, false, st, nullptr, n->compute_bf16 != 0));
+      if (!ps.empty()) HMP_TRY(gemm_many(n, ps, false, st, nullptr));
       // source types with NO stacked columns in this layer (their only live conv is the aggregate-first one): no GEMM -- the
       // masked transpose directly
       for (int s = 0; s < n->T; ++s) {
@@ -1572,33 +1515,20 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         const int act = Lp ? Lp->act : HMP_ACT_NONE;
         const bool masked = Lp && (act != HMP_ACT_NONE || drop_on);
         bool gb = false;
-        if (l > 0 && ps.empty()) {  // no GEMM decided the storage of G[l]: the same rule (see above)
-          const hmp_layer_spec& Lq = S.layers[l - 1];
-          int fmin = 1 << 30, fmax = 0;
-          for (int t = 0; t < n->T; ++t) {
-            if (n->lay[l - 1].roff[t] < 0 || b->n_nodes[t] == 0) continue;
-            const int f = fpad(Lq.out_dim[t]);
-            fmin = f < fmin ? f : fmin;
-            fmax = f > fmax ? f : fmax;
-          }
-          g16[l] = n->compute_bf16 != 0 && !n->fuse_now && n->lay[l - 1].kind != HMP_CONV_GAT && fmax <= 256 && fmin > 128 &&
-                   (n->ld[l][s] & 3) == 0 && n->env.z16 && (b->n_nodes[s] >= 32768 || bf16_all());
-        }
+        if (l > 0 && ps.empty())  // no GEMM decided the storage of G[l]: the same rule (see above)
+          g16[l] = n->compute_bf16 != 0 && rows_kernel_bf16(n, b, l - 1) && (n->ld[l][s] & 3) == 0 &&
+                   (b->n_nodes[s] >= 32768 || n->env.bf16_all);
         gb = l > 0 && g16[l];
         HMP_TRY(seg_mean_rows_t_launch(Q.dmrows, Q.ld_m, fpad(n->dim[l][s]), T.P->d_t_rowptr, T.P->d_t_col, T.degf, b->n_nodes[s],
                                        masked ? (const void*)n->H[l][s] : nullptr, n->ld[l][s], n->h16[l][s] ? 1 : 0, act, drop_on ? 1 : 0,
                                        drop_on ? 1.f / (1.f - Lp->dropout) : 1.f, dst, l > 0 ? n->ld[l][s] : b->ldx[s], gb ? 1 : 0, st));
       }
     }
-    {  // weight + bias gradient: dWp = dZ^T * [H | 1], split over node chunks (+ GAT: bias column sums, d V_edge)
-      std::vector<GemmProblem> local_ps;
-      std::vector<int> local_ids;
-      std::vector<GemmProblem>& ps = n->dw_branch ? local_ps : wps;
-      std::vector<int>& ids = n->dw_branch ? local_ids : wids;
+    {  // weight + bias gradient: dWp = dZ^T * [H | 1], split over node chunks (+ GAT: bias column sums, d V_edge), launched after the loop
       auto add = [&](int sid, const GemmProblem& p) {
         n->dyn.slab_stride[sid] = (int)p.slab_stride;
-        ids.push_back(sid);
-        ps.push_back(p);
+        wids.push_back(sid);
+        wps.push_back(p);
       };
       for (int s = 0; s < n->T; ++s) {
         if (Y.ncols[s] == 0 || b->n_nodes[s] == 0) continue;  // no nodes: zero gradient (n_slabs stays 0)
@@ -1660,17 +1590,9 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           add(slab_id_v(l, c), p);
         }
       }
-      if (n->dw_branch) {
-        Scope sc(n, KC_GEMM_BWD, wst);
-        std::vector<int> ks;
-        HMP_TRY(gemm_many(ps, true, wst, &ks, n->compute_bf16 != 0));
-        for (size_t i = 0; i < ids.size(); ++i) n->dyn.n_slabs[ids[i]] = (unsigned char)ks[i];
-      }
     }
   }
-  if (n->dw_branch) {
-    if (n->use_branches) HMP_TRY(fork_to(n, n->side[1], st));  // join the weight-gradient branch
-  } else {
+  {  // the weight gradients of all layers: one launch with ~1k workgroups instead of L launches
     Scope sc(n, KC_GEMM_BWD, st);
     std::vector<int> ks;
     bool direct = n->fuse_now;
@@ -1697,7 +1619,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         for (size_t i = 0; i < cnt; ++i) ks.push_back(tb.p[i].ksplit);
       }
     }
-    if (!direct) HMP_TRY(gemm_many(wps, true, st, &ks, n->compute_bf16 != 0));
+    if (!direct) HMP_TRY(gemm_many(n, wps, true, st, &ks));
     for (size_t i = 0; i < wids.size(); ++i) n->dyn.n_slabs[wids[i]] = (unsigned char)ks[i];
   }
   {
@@ -1722,7 +1644,6 @@ struct StepGuard {
   hmp_net* n;
   StepGuard(hmp_net* net, int training = 0, uint64_t seed = 0, uint32_t rng_step = 0, int* d_step = nullptr) : n(net) {
     read_env(n);
-    g_bf16_all = n->env.bf16_all;
     n->call.training = training; n->call.seed = seed; n->call.rng_step = rng_step;
     n->call.d_step = d_step;
   }
@@ -1759,20 +1680,6 @@ extern "C" int hmp_net_create(const hmp_net_spec* spec, hmp_net** out) {
     }
   }
   if (r == HMP_OK) {
-    // side-stream branches (pack + layer-0 projection next to the plan, weight gradients next to the backward chain) only
-    // on request: measured on MI355X, every fork/join costs ~10 us of dependency latency, more than the overlap buys once
-    // the plan is a single launch
-    const char* nb = getenv("HMP_BRANCH");
-    n->branch_mask = nb ? atoi(nb) : 0;
-    bool ok = n->branch_mask != 0;
-    for (int i = 0; i < 2 && ok; ++i) ok = hipStreamCreateWithFlags(&n->side[i], hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 32 && ok; ++i) {
-      ok = hipEventCreateWithFlags(&n->evs[i], hipEventDisableTiming) == hipSuccess;
-      if (ok) n->n_evs = i + 1;
-    }
-    n->use_branches = ok && n->n_evs == 32;
-    const char* db = getenv("HMP_DW_BRANCH");
-    n->dw_mode = db ? (db[0] == '1' ? 1 : 0) : -1;  // -1: decide per batch (see backward_impl)
     const char* fz = getenv("HMP_FUSE");
     n->fuse_mode = fz ? (fz[0] == '1' ? 1 : 0) : -1;
   }
@@ -1787,9 +1694,6 @@ extern "C" int hmp_net_create(const hmp_net_spec* spec, hmp_net** out) {
 extern "C" void hmp_net_destroy(hmp_net* n) {
   if (!n) return;
   for (auto& r : n->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (int i = 0; i < n->n_evs; ++i) (void)hipEventDestroy(n->evs[i]);
-  for (int i = 0; i < 2; ++i)
-    if (n->side[i]) (void)hipStreamDestroy(n->side[i]);
   if (n->d_state) (void)hipFree(n->d_state);
   if (n->d_pack_segs) (void)hipFree(n->d_pack_segs);
   if (n->d_pack_map) (void)hipFree(n->d_pack_map);
@@ -1843,7 +1747,6 @@ extern "C" int hmp_net_forward(hmp_net* n, const hmp_batch* batch, const float* 
 extern "C" int hmp_net_backward(hmp_net* n, const float* d_gout, int32_t ld_gout, const float* d_params, float* d_grads,
                                 float* const* d_gx, void* stream) {
   HMP_CHECK_ARG(n && d_gout && d_grads && d_params, "hmp_net_backward: null argument");
-  g_bf16_all = n->env.bf16_all;  // (the switches of the forward this backward belongs to)
   return backward_impl(n, d_gout, ld_gout, d_grads, d_params, d_gx, (hipStream_t)stream);
 }
 
@@ -1875,7 +1778,6 @@ extern "C" int hmp_net_backward2(hmp_net* n, const float* d_gout, int32_t ld_gou
                                  const float* d_params, float* d_grads, float* const* d_gx, void* stream) {
   HMP_CHECK_ARG(n && d_grads && d_params && (d_gout || d_gout_aux), "hmp_net_backward2: null argument");
   HMP_CHECK_ARG(n->spec.aux_readout_type >= 0, "hmp_net_backward2: the net has one output (use hmp_net_backward)");
-  g_bf16_all = n->env.bf16_all;
   if (!d_gout) {  // no gradient for the first output: a zero block of its shape (G[L][readout] is free in the last layer)
     HMP_CHECK_ARG(n->have_fwd, "net: backward without a forward");
     const int rt = n->spec.readout_type, rows = n->batch.n_nodes[rt];

@@ -229,23 +229,6 @@ def test_gat_training_mode_parity_at_the_bench_size(block):
     training_mode_parity(block, [128, 128], [4, 4, 4], [True, True, False], batch)
 
 
-def test_gat_with_side_stream_branches_orders_pack_before_the_projection(monkeypatch):
-    """HMP_BRANCH=1 forks a side stream for pack + layer-0 projection; a GAT front launch (plan + pack on the main
-    stream) must not run next to it.  Same results as the single-stream sequence, bit for bit."""
-    batch = workloads.config3_batch(6)
-    res = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("HMP_BRANCH", mode)
-        _, net = gat_pair("GAT", [16, 16], [2, 2, 2], [True, True, False], seed=3)
-        net.eval()
-        gb = batch.to(DEV)
-        outs = [net(gb).detach().clone() for _ in range(4)]
-        assert all(torch.equal(o, outs[0]) for o in outs)
-        res[mode] = outs[0]
-    monkeypatch.delenv("HMP_BRANCH")
-    assert torch.equal(res["0"], res["1"])
-
-
 def training_mode_parity(block, hidden, heads, concats, batch):
     p = 0.25
     ora, net = gat_pair(block, hidden, heads, concats, dropout=p)
@@ -332,7 +315,7 @@ def test_homogeneous_gat_parity():
 def test_gat_front_launch_of_plan_and_pack_is_bit_identical(monkeypatch, block):
     """GAT nets: plan parts and pack blocks share one front launch (no projection role -- its operand is the pack's output), the
     link pass follows; HMP_FRONT=0 keeps pack, plan and link as separate launches.  Same plan, same packed operands: predictions,
-    gradients and three optimiser steps agree to the last bit."""
+    gradients and three optimiser steps agree to the last bit, and repeated eval forwards of one net give the same bits."""
     batch = workloads.config3_batch(6, edge=(block == "GAT_edge"))
     res = {}
     for mode in ("0", "1"):
@@ -345,6 +328,7 @@ def test_gat_front_launch_of_plan_and_pack_is_bit_identical(monkeypatch, block):
         net.loss(pred, y, y != 25).backward()
         grads = {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
         assert net.native().read_state()[1] == 0
+        assert all(torch.equal(net(gb), pred) for _ in range(3))  # repeated eval forwards: the same bits
         net.train()
         step = net.train_step(lr=0.002, weight_decay=0.001, ignored_label=25, use_graph=False)
         for _ in range(3):
