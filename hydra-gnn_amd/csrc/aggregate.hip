@@ -1613,24 +1613,14 @@ static inline void pick_shape(int F, int vec, int& gs, int& nv) {
 
 constexpr int64_t AGG_XCD_ROWS = 65536;  // from here on the launch is several waves of blocks deep and L2 locality pays
 static bool agg_xcd_enabled() {  // HMP_AGG_XCD=0: plain block order (tests compare both orders bit for bit)
-  const char* v = getenv("HMP_AGG_XCD");
-  return !(v && v[0] == '0');
+  return env_switch("HMP_AGG_XCD") != '0';
 }
 
 // HMP_AGG_WIN=0 turns the LDS sliding-window kernels off (tests compare both forms bit for bit)
-static bool agg_win_enabled() {
-  const char* v = getenv("HMP_AGG_WIN");
-  return !(v && v[0] == '0');
-}
+static bool agg_win_enabled() { return env_switch("HMP_AGG_WIN") != '0'; }
 constexpr int AGG_WIN_MIN_ROWS = 16384;  // below: a persistent grid would leave CUs idle, the plain kernels do as well
 static int agg_win_grid(int n_chunks, int& per_block) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cus = v;
-  }
-  per_block = cdiv(n_chunks, cus);
+  per_block = cdiv(n_chunks, device_cu_count());
   return cdiv(n_chunks, per_block);
 }
 

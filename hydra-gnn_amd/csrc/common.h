@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/hydra_mp.h"
@@ -46,6 +47,23 @@ char* err_buf();  // thread-local, 512 bytes (runtime.hip)
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int align4(int x) { return (x + 3) & ~3; }
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Test / A-B switches (HMP_* environment variables): the first character of the variable, -1 when it is unset and 0 when it is
+// set but empty (the tri-state switches tell those two apart)
+static inline int env_switch(const char* name) {
+  const char* v = getenv(name);
+  return v ? (unsigned char)v[0] : -1;
+}
+
+// compute units of the current device, queried once (256 when the query fails)
+inline int device_cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
+    return v;
+  }();
+  return n;
+}
 
 // ---- kernel-argument warm-up ---------------------------------------------------------------------------------------
 // Kernel arguments are read through the scalar cache one 64-byte line at a time, and the compiler waits for every field where

@@ -17,7 +17,7 @@
 //
 // Forms: NT (x * W^T, nn.Linear), NN (dZ * W, input gradient, optional activation-derivative epilogue),
 // TN with split-K over node chunks (dZ^T * [x | 1], weight + bias gradient; slabs are reduced later).
-#include <cstdlib>
+#include <algorithm>
 
 #include "kernels.h"
 
@@ -172,11 +172,11 @@ __device__ __forceinline__ void tile_load(TileRegs<ROWS, BK>& t, const float* __
 // consecutive k of one row): written plainly, 32 lanes (k = 0,4,8,..) would hit 2 banks (4*LD = 16 mod 32: 16-way
 // conflict), so row r of k-row k is ROTATED to column (r + k/4) mod ROWS: the 32 lanes then land on 32 different banks
 // (bank = 17*(k/4) + r + const), and the MFMA operand fetch (32 consecutive r of one k) stays conflict-free.
-// column of the rotated image: x in [0, 2 ROWS); ROWS need not be a power of two (192-column tiles)
+// column of the rotated image: x in [0, 2 ROWS)
 template <int ROWS>
 __device__ __forceinline__ int wrap_rows(int x) {
-  if constexpr ((ROWS & (ROWS - 1)) == 0) return x & (ROWS - 1);
-  else return x >= ROWS ? x - ROWS : x;
+  static_assert((ROWS & (ROWS - 1)) == 0, "the rotated LDS image wraps by a mask: ROWS must be a power of two");
+  return x & (ROWS - 1);
 }
 template <int ROWS, int BK>
 __device__ __forceinline__ void tile_store(const TileRegs<ROWS, BK>& t, float* __restrict__ s, int kcontig) {
@@ -401,42 +401,15 @@ __global__ __launch_bounds__(256, (MI * NI > 1) ? 2 : 3) void gemm_kernel(const 
 template <int WM, int WN, int BK, int MI = 1, int NI = 1>
 static int launch_cfg(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   constexpr int BM = 32 * WM * MI, BN = 32 * WN * NI;
-  int start = 0;
-  int all_tiles = 0;
-  for (int i = 0; i < gb.n; ++i) all_tiles += cdiv(gb.p[i].M, BM) * cdiv(gb.p[i].N, BN);
-  for (int i = 0; i < gb.n; ++i) {
-    GemmProblem& p = gb.p[i];
-    p.tiles_m = cdiv(p.M, BM);
-    p.tiles_n = cdiv(p.N, BN);
-    int tiles = p.tiles_m * p.tiles_n;
-    int ks = 1;
-    if (want_split && tiles > 0) {
-      // aim at ~1024 workgroups over the whole launch; every slab gets >= 1 full K stage
-      ks = 1024 / (all_tiles > 0 ? all_tiles : 1);
-      int max_by_k = cdiv(p.K, BK);
-      if (ks > max_by_k) ks = max_by_k;
-      if (ks > max_slabs) ks = max_slabs;
-      if (ks < 1) ks = 1;
-      while (ks & (ks - 1)) ks &= ks - 1;  // power of two (XCD affinity of the K chunks, see the kernel)
-    }
-    int kchunk = cdiv(cdiv(p.K, ks), BK) * BK;
-    if (kchunk < BK) kchunk = BK;
-    ks = p.K > 0 ? cdiv(p.K, kchunk) : 1;
-    p.ksplit = ks;
-    p.kchunk = kchunk;
-    p.tile_start = start;
-    start += tiles * ks;
-  }
-  gb.total_tiles = start;
+  // aim at ~1024 workgroups over the whole launch; every slab gets >= 1 full K stage; a power of two (XCD affinity of the K
+  // chunks, see the kernel)
+  const int start = gemm_plan_tiles(gb, BM, BN, BK, false, want_split, [&](const GemmProblem& p, int all_tiles, double) {
+    int ks = std::max(1, std::min({1024 / all_tiles, cdiv(p.K, BK), max_slabs}));
+    while (ks & (ks - 1)) ks &= ks - 1;
+    return ks;
+  });
   if (start == 0) return HMP_OK;
-  // operand form shared by every problem of the launch (the executor's launches are uniform), else the run-time variant
-  int form = -1;
-  for (int i = 0; i < gb.n; ++i) {
-    const GemmProblem& p = gb.p[i];
-    const int f = (!p.trans_a && p.trans_b) ? 0 : (!p.trans_a && !p.trans_b) ? 1 : (p.trans_a && !p.trans_b) ? 2 : 3;
-    form = (form == -1 || form == f) ? f : 3;
-  }
-  switch (form) {
+  switch (launch_form(gb)) {
     case 0: hipLaunchKernelGGL((gemm_kernel<WM, WN, BK, 0, MI, NI>), dim3(start), dim3(256), 0, st, gb); break;
     case 1: hipLaunchKernelGGL((gemm_kernel<WM, WN, BK, 1, MI, NI>), dim3(start), dim3(256), 0, st, gb); break;
     case 2: hipLaunchKernelGGL((gemm_kernel<WM, WN, BK, 2, MI, NI>), dim3(start), dim3(256), 0, st, gb); break;
@@ -582,11 +555,44 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tall_kernel(const TallBatch tb
 
 // problems of a split-K launch the tall kernel takes
 static bool tall_takes(const GemmProblem& p) {
-  const char* v = getenv("HMP_GEMM_TALL");  // 0: the tiled split-K kernel for every weight gradient (tests compare the two)
-  if (v && v[0] == '0') return false;
+  if (env_switch("HMP_GEMM_TALL") == '0') return false;  // the tiled split-K kernel for every weight gradient (tests compare the two)
   return p.trans_a && !p.trans_b && p.M > 0 && p.M <= TT_M && (p.M & 3) == 0 && p.N > 0 && p.K >= 32768 && (p.lda & 3) == 0 && (p.ldb & 1) == 0 &&
          (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 7) == 0 && p.epi == EPI_NONE &&
          (p.n_real & 1) == 0;
+}
+
+// one launch of the tall kernel for the problems of gb that s.taken names; their split goes back into gb
+static int tall_launch(GemmBatch& gb, const GemmPeel& s, hipStream_t st) {
+  TallBatch tb;
+  memset(&tb, 0, sizeof(tb));
+  tb.n = s.n_taken;
+  double work_total = 0.0;
+  for (int i = 0; i < tb.n; ++i) work_total += (double)gb.p[s.taken[i]].K * cdiv(gb.p[s.taken[i]].N, TT_NS);
+  int start = 0;
+  for (int i = 0; i < tb.n; ++i) {
+    GemmProblem& g = gb.p[s.taken[i]];
+    TallProblem& P = tb.p[i];
+    P.A = g.A; P.B = g.B; P.C = g.C; P.slab_stride = g.slab_stride;
+    P.M = g.M; P.N = g.N; P.K = g.K; P.lda = g.lda; P.ldb = g.ldb; P.ldc = g.ldc; P.n_real = g.n_real; P.aug_ones = g.aug_ones;
+    P.nslices = cdiv(g.N, TT_NS);
+    // ~2 workgroups per CU over the whole launch, shared out in proportion to chunks x slices; <= GEMM_TALL_SLABS slabs
+    // (measured at batch 2048: 256 / 512 / 768 / 1024 workgroups -> 0.80 / 0.51 / 0.58 / 0.52 ms for the backward GEMMs)
+    int ks = (int)(512.0 * ((double)g.K * P.nslices / work_total) / P.nslices + 0.5);
+    if (ks > GEMM_TALL_SLABS) ks = GEMM_TALL_SLABS;
+    if (ks < 1) ks = 1;
+    P.kchunk = g.kchunk = cdiv(cdiv(g.K, ks), TT_BK) * TT_BK;
+    P.ksplit = g.ksplit = cdiv(g.K, P.kchunk);
+    P.block_start = start;
+    start += P.ksplit * P.nslices;
+  }
+  static const int rc = [] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               2 * TT_STAGE * (int)sizeof(float)) == hipSuccess ? 0 : 1;
+  }();
+  HMP_CHECK_ARG(rc == 0, "gemm: could not raise the dynamic LDS limit of the tall weight-gradient kernel");
+  hipLaunchKernelGGL(gemm_tn_tall_kernel, dim3(start), dim3(256), 2 * TT_STAGE * sizeof(float), st, tb);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
 }
 
 int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
@@ -594,57 +600,12 @@ int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   // launches of >= 10^9 multiply-adds: fp32 accuracy from six bf16 piece products per element product (gemm_x3.hip)
   if (gemm_x3_takes(gb, want_split)) return gemm_x3_launch(gb, want_split, max_slabs, st);
   if (want_split) {  // weight gradients over >= 32768 nodes with <= 192 stacked columns: the tall kernel (one launch for all of them)
-    TallBatch tb;
-    memset(&tb, 0, sizeof(tb));
-    GemmBatch rest;
-    memset(&rest, 0, sizeof(rest));
-    int idx_t[GEMM_MAX_PROB], idx_r[GEMM_MAX_PROB];
-    double work_total = 0.0;
-    for (int i = 0; i < gb.n; ++i)
-      if (tall_takes(gb.p[i])) work_total += (double)gb.p[i].K * cdiv(gb.p[i].N, TT_NS);
-    for (int i = 0; i < gb.n; ++i) {
-      const GemmProblem& g = gb.p[i];
-      if (!tall_takes(g)) {
-        idx_r[rest.n] = i;
-        rest.p[rest.n++] = g;
-        continue;
-      }
-      TallProblem& P = tb.p[tb.n];
-      idx_t[tb.n++] = i;
-      P.A = g.A; P.B = g.B; P.C = g.C; P.slab_stride = g.slab_stride;
-      P.M = g.M; P.N = g.N; P.K = g.K; P.lda = g.lda; P.ldb = g.ldb; P.ldc = g.ldc; P.n_real = g.n_real; P.aug_ones = g.aug_ones;
-      P.nslices = cdiv(g.N, TT_NS);
-      // ~2 workgroups per CU over the whole launch, shared out in proportion to chunks x slices; <= GEMM_TALL_SLABS slabs
-      // (measured at batch 2048: 256 / 512 / 768 / 1024 workgroups -> 0.80 / 0.51 / 0.58 / 0.52 ms for the backward GEMMs)
-      int ks = (int)(512.0 * ((double)g.K * P.nslices / work_total) / P.nslices + 0.5);
-      if (ks > GEMM_TALL_SLABS) ks = GEMM_TALL_SLABS;
-      if (ks < 1) ks = 1;
-      int kchunk = cdiv(cdiv(g.K, ks), TT_BK) * TT_BK;
-      ks = cdiv(g.K, kchunk);
-      P.ksplit = ks; P.kchunk = kchunk;
-    }
-    if (tb.n > 0) {
-      int start = 0;
-      for (int i = 0; i < tb.n; ++i) {
-        tb.p[i].block_start = start;
-        start += tb.p[i].ksplit * tb.p[i].nslices;
-        gb.p[idx_t[i]].ksplit = tb.p[i].ksplit;
-        gb.p[idx_t[i]].kchunk = tb.p[i].kchunk;
-      }
-      static const int rc = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   2 * TT_STAGE * (int)sizeof(float)) == hipSuccess ? 0 : 1;
-      }();
-      HMP_CHECK_ARG(rc == 0, "gemm: could not raise the dynamic LDS limit of the tall weight-gradient kernel");
-      hipLaunchKernelGGL(gemm_tn_tall_kernel, dim3(start), dim3(256), 2 * TT_STAGE * sizeof(float), st, tb);
-      HMP_LAUNCH_CHECK();
-      if (rest.n == 0) return HMP_OK;
-      const int rc2 = gemm_launch(rest, want_split, max_slabs, st);  // (tall_takes is false for every problem of `rest`)
-      for (int i = 0; i < rest.n; ++i) {
-        gb.p[idx_r[i]].ksplit = rest.p[i].ksplit;
-        gb.p[idx_r[i]].kchunk = rest.p[i].kchunk;
-      }
-      return rc2;
+    GemmPeel tall;
+    gemm_peel(gb, tall_takes, tall);
+    if (tall.n_taken > 0) {
+      HMP_TRY(tall_launch(gb, tall, st));
+      // (tall_takes is false for every problem of the rest)
+      return gemm_launch_rest(gb, tall, [&](GemmBatch& rest) { return gemm_launch(rest, want_split, max_slabs, st); });
     }
   }
   int64_t tiles64 = 0;
@@ -664,8 +625,7 @@ int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   if (tiles64 >= 1024 || work >= 1e9) {
     int64_t tiles128 = 0;
     for (int i = 0; i < gb.n; ++i) tiles128 += (int64_t)cdiv(gb.p[i].M, 128) * cdiv(gb.p[i].N, 128);
-    const char* gv = getenv("HMP_GEMM_BIG");
-    const bool big_ok = !(gv && gv[0] == '0');
+    const bool big_ok = env_switch("HMP_GEMM_BIG") != '0';
     // ... and only for wide outputs (every N >= 256): measured on MI355X, the GAT backward GEMMs (N = 512 .. 1100) gain 18 %
     // (0.448 -> 0.366 ms per step, config 3), but at N = 192 / 65 (config 2 at batch 2048) the half-empty second column tile and
     // two workgroups per CU instead of three LOSE 20 % (gemm 1.33 -> 1.67 ms)
@@ -673,15 +633,6 @@ int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
     for (int i = 0; i < gb.n; ++i) min_n = gb.p[i].N < min_n ? gb.p[i].N : min_n;
     if (big_ok && min_n >= 256 && work >= 1e9 && (tiles128 >= 256 || (want_split && max_k >= 8192)))
       return launch_cfg<2, 2, 32, 2, 2>(gb, want_split, max_slabs, st);
-    // round 3: outputs of 129 .. 192 columns (the three stacked 64-column blocks of an MP3D layer at the reference's batch size:
-    // 190 k rows x 192) take the WHOLE width in one workgroup -- 64 x 192 tiles, 1 x 3 accumulator tiles per wave: the node rows
-    // are read once instead of three times and an A fragment feeds three MFMAs (246 VGPRs, no spill; the 128 x 192 form with
-    // 2 x 3 tiles per wave spills 96 registers at two workgroups per CU and was not kept).  HMP_GEMM_WIDE=0: the 64x64 form
-    int max_n = 0;
-    for (int i = 0; i < gb.n; ++i) max_n = gb.p[i].N > max_n ? gb.p[i].N : max_n;
-    const char* wv = getenv("HMP_GEMM_WIDE");
-    if (!(wv && wv[0] == '0') && !want_split && min_n > 128 && max_n <= 192 && work >= 1e9)
-      return launch_cfg<2, 2, 32, 1, 3>(gb, want_split, max_slabs, st);
     return launch_cfg<2, 2, 32>(gb, want_split, max_slabs, st);
   }
   if (max_k <= 64) return launch_cfg<1, 1, 64>(gb, want_split, max_slabs, st);

@@ -19,6 +19,8 @@
 //
 // Forms: NT (x * W^T), NN (dZ * W, optional activation-derivative epilogue), TN with split-K over node chunks
 // (dZ^T * [x | 1]) -- the same GemmProblem contract as gemm.hip.
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace hmp {
@@ -655,8 +657,7 @@ __global__ __launch_bounds__(WS_THREADS, WS_PER_CU) void gemm_bf16_ws_kernel(con
 
 // problems of a launch the weight-stationary kernel takes (one launch each); false: the tiled kernel
 static bool ws_takes(const GemmProblem& p, bool want_split) {
-  const char* v = getenv("HMP_GEMM_WS");  // 0: the tiled kernel for every problem (tests compare the two)
-  const bool on = !(v && v[0] == '0');
+  const bool on = env_switch("HMP_GEMM_WS") != '0';  // 0: the tiled kernel for every problem (tests compare the two)
   // an fp32 A only at K = 256 (the run-time-K form of that variant does not fit the register file: 75 spilled registers)
   if (!p.a_bf16 && p.K != 256) return false;
   return on && !want_split && !p.trans_a && p.trans_b && p.a_split == 0 && !p.b_bf16 && p.epi == EPI_NONE && !p.aug_ones &&
@@ -677,18 +678,9 @@ static int ws_launch(const GemmProblem& p, hipStream_t st) {
     a.dbg = dv ? atoi(dv) : 0;
   }
 #endif
-  static const int n_cu = [] {  // (queried once: the property call is not cheap)
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) return prop.multiProcessorCount;
-    return 256;
-  }();
-  // groups in sets of 8 (one per XCD); as many sets as fit the chip, at least one
-  int sets = WS_PER_CU * n_cu / (8 * a.n_slices);
-  if (sets < 1) sets = 1;
-  a.groups = 8 * sets;
-  if (a.groups > a.n_tiles) a.groups = ((a.n_tiles + 7) / 8) * 8;
-  a.tiles_per_group = cdiv(a.n_tiles, a.groups);
+  const XcdGrid g = xcd_set_grid(WS_PER_CU, a.n_slices, a.n_tiles);
+  a.groups = g.groups;
+  a.tiles_per_group = g.tiles_per_group;
   const dim3 grid(a.groups * a.n_slices), block(WS_THREADS);
   const size_t lds = 2 * WS_ROWS * 512;  // 64 KB: the default dynamic limit
   if (p.a_bf16) {
@@ -717,50 +709,29 @@ static int ws_launch(const GemmProblem& p, hipStream_t st) {
 // form (the 256 x 256 bf16 weight tile fits LDS).
 int gemm_bf16_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   HMP_CHECK_ARG(gb.n >= 0 && gb.n <= GEMM_MAX_PROB, "gemm_bf16: %d problems", gb.n);
-  {  // backward products of the 10^6-node regime: operand-stationary kernels (gemm_bf16_bwd.hip), one launch per problem
-    GemmBatch rest;
-    memset(&rest, 0, sizeof(rest));
-    int where[GEMM_MAX_PROB];
-    int taken = 0;
-    for (int i = 0; i < gb.n; ++i) {
-      if (gemm_bf16_dx_takes(gb.p[i], want_split)) {
-        HMP_TRY(gemm_bf16_dx_launch(gb.p[i], st));
-        gb.p[i].ksplit = 1;
-        ++taken;
-      } else if (gemm_bf16_dw_takes(gb.p[i], want_split)) {
-        int ns = 1;
-        HMP_TRY(gemm_bf16_dw_launch(gb.p[i], max_slabs, &ns, st));
-        gb.p[i].ksplit = ns;
-        ++taken;
+  auto rest_launch = [&](GemmBatch& rest) { return gemm_bf16_launch(rest, want_split, max_slabs, st); };
+  GemmPeel s;
+  // backward products of the 10^6-node regime: operand-stationary kernels (gemm_bf16_bwd.hip), one launch per problem
+  gemm_peel(gb, [&](const GemmProblem& p) { return gemm_bf16_dx_takes(p, want_split) || gemm_bf16_dw_takes(p, want_split); }, s);
+  if (s.n_taken > 0) {
+    for (int t = 0; t < s.n_taken; ++t) {
+      GemmProblem& p = gb.p[s.taken[t]];
+      if (gemm_bf16_dx_takes(p, want_split)) {
+        HMP_TRY(gemm_bf16_dx_launch(p, st));
+        p.ksplit = 1;
       } else {
-        where[rest.n] = i;
-        rest.p[rest.n++] = gb.p[i];
+        HMP_TRY(gemm_bf16_dw_launch(p, max_slabs, &p.ksplit, st));
       }
     }
-    if (taken) {
-      if (rest.n == 0) return HMP_OK;
-      HMP_TRY(gemm_bf16_launch(rest, want_split, max_slabs, st));  // (no problem of `rest` is taken here again)
-      for (int i = 0; i < rest.n; ++i) gb.p[where[i]].ksplit = rest.p[i].ksplit;
-      return HMP_OK;
-    }
+    return gemm_launch_rest(gb, s, rest_launch);  // (no problem of the rest is taken here again)
   }
-  {  // tall NT products over a bf16 A: the weight-stationary kernel, one launch per problem; the rest stays with the tiled kernel
-    GemmBatch rest;
-    memset(&rest, 0, sizeof(rest));
-    int taken = 0;
-    for (int i = 0; i < gb.n; ++i) {
-      if (ws_takes(gb.p[i], want_split)) {
-        HMP_TRY(ws_launch(gb.p[i], st));
-        ++taken;
-      } else {
-        rest.p[rest.n++] = gb.p[i];
-      }
-    }
-    if (taken) {
-      for (int i = 0; i < gb.n; ++i) gb.p[i].ksplit = 1;  // (no split-K in this branch: want_split is false)
-      if (rest.n == 0) return HMP_OK;
-      return gemm_bf16_launch(rest, want_split, max_slabs, st);  // (no problem of `rest` is taken again)
-    }
+  // tall NT products over a bf16 A: the weight-stationary kernel, one launch per problem; the rest stays with the tiled kernel
+  gemm_peel(gb, [&](const GemmProblem& p) { return ws_takes(p, want_split); }, s);
+  if (s.n_taken > 0) {
+    for (int t = 0; t < s.n_taken; ++t) HMP_TRY(ws_launch(gb.p[s.taken[t]], st));
+    const int rc = gemm_launch_rest(gb, s, rest_launch);  // (no problem of the rest is taken again)
+    for (int i = 0; i < gb.n; ++i) gb.p[i].ksplit = 1;  // (no split-K in this branch: want_split is false)
+    return rc;
   }
   // 256x256 tiles when every problem is a product with at least 4096 x 192 outputs (plain) / 192 x 192 outputs over >= 2^17
   // nodes in one problem (split-K weight gradients; narrow companions such as the 28-row last layer ride along on one tile)
@@ -788,46 +759,14 @@ int gemm_bf16_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t 
   }
   const int BT = big ? 256 : 128;
   const int BKB = big ? 32 : 64;
-  int start = 0, all_tiles = 0;
-  double work_total = 0.0;  // tiles x nodes
-  for (int i = 0; i < gb.n; ++i) {
-    const int t = cdiv(gb.p[i].M, BT) * cdiv(gb.p[i].aug_ones ? (gb.p[i].n_real > 0 ? gb.p[i].n_real : 1) : gb.p[i].N, BT);
-    all_tiles += t;
-    work_total += (double)t * gb.p[i].K;
-  }
-  for (int i = 0; i < gb.n; ++i) {
-    GemmProblem& p = gb.p[i];
-    p.tiles_m = cdiv(p.M, BT);
-    p.tiles_n = cdiv(p.aug_ones ? (p.n_real > 0 ? p.n_real : 1) : p.N, BT);  // the ones column rides in the first column tile
-    const int tiles = p.tiles_m * p.tiles_n;
-    int ks = 1;
-    if (want_split && tiles > 0) {
-      // aim at 4 workgroups per CU; big tile (1 block per CU): 2 x 256 blocks shared out in proportion to the nodes each
-      // problem reduces over (the 10^4-room problems of config 5 take one block per tile, the 10^6-object ones the rest)
-      if (big) ks = (int)(512.0 * (double)p.K / (work_total > 0 ? work_total : 1.0));
-      else ks = 1024 / (all_tiles > 0 ? all_tiles : 1);
-      const int max_by_k = cdiv(p.K, BKB);
-      if (ks > max_by_k) ks = max_by_k;
-      if (ks > (big ? max_slabs : 64)) ks = big ? max_slabs : 64;
-      if (ks < 1) ks = 1;
-    }
-    int kchunk = cdiv(cdiv(p.K, ks), BKB) * BKB;
-    if (kchunk < BKB) kchunk = BKB;
-    ks = p.K > 0 ? cdiv(p.K, kchunk) : 1;
-    p.ksplit = ks;
-    p.kchunk = kchunk;
-    p.tile_start = start;
-    start += tiles * ks;
-  }
-  gb.total_tiles = start;
+  // aim at 4 workgroups per CU; big tile (1 block per CU): 2 x 256 blocks shared out in proportion to the nodes each problem reduces
+  // over (the 10^4-room problems of config 5 take one block per tile, the 10^6-object ones the rest)
+  const int start = gemm_plan_tiles(gb, BT, BT, BKB, true, want_split, [&](const GemmProblem& p, int all_tiles, double tiles_k) {
+    const int ks = big ? (int)(512.0 * (double)p.K / (tiles_k > 0 ? tiles_k : 1.0)) : 1024 / all_tiles;
+    return std::max(1, std::min({ks, cdiv(p.K, BKB), big ? max_slabs : 64}));
+  });
   if (start == 0) return HMP_OK;
-  // operand form shared by every problem of the launch (the executor's launches are uniform), else the run-time variant
-  int form = -1;
-  for (int i = 0; i < gb.n; ++i) {
-    const GemmProblem& p = gb.p[i];
-    const int f = (!p.trans_a && p.trans_b) ? 0 : (!p.trans_a && !p.trans_b) ? 1 : (p.trans_a && !p.trans_b) ? 2 : 3;
-    form = (form == -1 || form == f) ? f : 3;
-  }
+  const int form = launch_form(gb);
 #define BF_LAUNCH(ONES_, NT_, ROWS_, WM_, WN_, BK_, FORM_) \
   hipLaunchKernelGGL((gemm_bf16_kernel<ONES_, NT_, ROWS_, WM_, WN_, BK_, FORM_>), dim3(start), dim3(NT_), 0, st, gb)
 #define BF_FORMS(ONES_, NT_, ROWS_, WM_, WN_, BK_)          \

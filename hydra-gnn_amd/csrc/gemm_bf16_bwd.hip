@@ -274,20 +274,13 @@ __global__ __launch_bounds__(DX_THREADS, (NBUF > 4 ? 1 : 2)) void gemm_bf16_dx_k
   }
 }
 
-static bool env_off(const char* name) {
-  const char* v = getenv(name);
-  return v && v[0] == '0';
-}
-
 bool gemm_bf16_dx_takes(const GemmProblem& p, bool want_split) {
-  if (env_off("HMP_GEMM_DX")) return false;  // 0: the tiled kernel (tests compare the two)
+  const int v = env_switch("HMP_GEMM_DX");
+  if (v == '0') return false;  // the tiled kernel (tests compare the two)
   // K = 768 (one workgroup per CU, one wave per SIMD, every LDS read waited for in front of its MFMA) measured 903 us against the
   // tiled kernel's 796 us at 10^6 rows: only on request (HMP_GEMM_DX=2, the unit test); with the objects -> rooms conv evaluated
   // aggregate-first the stacked operand of config 5 is 512 columns
-  if (p.K > 512) {
-    const char* v = getenv("HMP_GEMM_DX");
-    if (!(v && v[0] == '2')) return false;
-  }
+  if (p.K > 512 && v != '2') return false;
   return !want_split && !p.trans_a && !p.trans_b && p.a_bf16 && p.c_bf16 && !p.b_bf16 && !p.aug_ones &&
          (p.epi == EPI_NONE || p.h_bf16) && (p.K == 256 || p.K == 512 || p.K == 768) && (p.N % DX_COLS) == 0 && p.N >= DX_COLS &&
          p.M >= 32768 && (p.lda & 7) == 0 && (p.a_split == 0 || ((p.a_split & 255) == 0 && (p.lda2 & 7) == 0 && p.A2 &&
@@ -295,16 +288,6 @@ bool gemm_bf16_dx_takes(const GemmProblem& p, bool want_split) {
          (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0 &&
          (p.epi == EPI_NONE || (reinterpret_cast<uintptr_t>(p.H) & 15) == 0) &&
          (!p.g_rowptr || ((p.g_ld & 3) == 0 && (reinterpret_cast<uintptr_t>(p.g_rows) & 15) == 0));
-}
-
-static int n_cus() {
-  static const int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) return prop.multiProcessorCount;
-    return 256;
-  }();
-  return n;
 }
 
 int gemm_bf16_dx_launch(const GemmProblem& p, hipStream_t st) {
@@ -321,12 +304,9 @@ int gemm_bf16_dx_launch(const GemmProblem& p, hipStream_t st) {
   a.M = p.M; a.N = p.N; a.K = p.K;
   a.n_slices = p.N / DX_COLS;
   a.n_tiles = cdiv(p.M, DX_ROWS);
-  const int per_cu = p.K > 512 ? 1 : 2;
-  int sets = per_cu * n_cus() / (8 * a.n_slices);
-  if (sets < 1) sets = 1;
-  a.groups = 8 * sets;
-  if (a.groups > a.n_tiles) a.groups = ((a.n_tiles + 7) / 8) * 8;
-  a.tiles_per_group = cdiv(a.n_tiles, a.groups);
+  const XcdGrid g = xcd_set_grid(p.K > 512 ? 1 : 2, a.n_slices, a.n_tiles);
+  a.groups = g.groups;
+  a.tiles_per_group = g.tiles_per_group;
   const dim3 grid(a.groups * a.n_slices), block(DX_THREADS);
   static const int attr_rc = [] {
     int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dx_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, dx_lds_bytes(4));
@@ -552,7 +532,7 @@ __global__ __launch_bounds__(DW_THREADS, 2) void gemm_bf16_dw_kernel(const DwArg
 }
 
 bool gemm_bf16_dw_takes(const GemmProblem& p, bool want_split) {
-  if (env_off("HMP_GEMM_DW")) return false;  // 0: the tiled kernel (tests compare the two)
+  if (env_switch("HMP_GEMM_DW") == '0') return false;  // the tiled kernel (tests compare the two)
   return want_split && p.trans_a && !p.trans_b && p.a_bf16 && (p.M % DW_TILE) == 0 && p.M >= DW_TILE && p.n_real == 256 &&
          p.N == p.n_real + (p.aug_ones ? 1 : 0) && p.K >= 65536 && (p.lda & 7) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
          (p.a_split == 0 || ((p.a_split & 255) == 0 && (p.lda2 & 7) == 0 && p.A2 && (reinterpret_cast<uintptr_t>(p.A2) & 15) == 0)) &&
@@ -569,7 +549,7 @@ int gemm_bf16_dw_launch(const GemmProblem& p, int max_slabs, int* n_slabs, hipSt
   a.C = p.C; a.ldc = p.ldc; a.n_real = p.n_real; a.aug_ones = p.aug_ones; a.slab_stride = p.slab_stride;
   a.K = p.K;
   a.tiles_m = p.M / DW_TILE;
-  int groups = 8 * (n_cus() / (8 * a.tiles_m));  // one workgroup per CU, node ranges in sets of 8 (one per XCD)
+  int groups = 8 * (device_cu_count() / (8 * a.tiles_m));  // one workgroup per CU, node ranges in sets of 8 (one per XCD)
   if (groups < 8) groups = 8;
   while (groups > 8 && groups > max_slabs) groups -= 8;
   HMP_CHECK_ARG(groups <= max_slabs, "gemm_bf16_dw: %d slabs needed, %d available", groups, max_slabs);

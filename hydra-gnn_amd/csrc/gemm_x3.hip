@@ -18,6 +18,8 @@
 // gemm.hip: NT (x W^T), NN (dZ W, optional activation-derivative epilogue, optional addend), TN split-K over node chunks with the
 // virtual ones column (bias gradient) as one more product per row tile against an all-ones fragment.  Rows that are only 8-byte
 // aligned (MP3D object features: pitch 306) load as float2 pairs.
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace hmp {
@@ -376,44 +378,14 @@ __global__ __launch_bounds__(C::NT, C::PER_CU) void gemm_x3_kernel(const GemmBat
 template <class C>
 int x3_launch_cfg(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   bool any_ones = false;
-  int start = 0, all_tiles = 0;
-  for (int i = 0; i < gb.n; ++i) {
-    const GemmProblem& p = gb.p[i];
-    any_ones = any_ones || p.aug_ones != 0;
-    all_tiles += cdiv(p.M, C::RM) * cdiv(p.aug_ones ? (p.n_real > 0 ? p.n_real : 1) : p.N, C::RN);
-  }
+  for (int i = 0; i < gb.n; ++i) any_ones = any_ones || gb.p[i].aug_ones != 0;
   // workgroups over the whole launch when split-K supplies them: one per CU and resident slot -- the kernel time is flat from 256 to 2048
-  // at config 3, and every slab is written here and read again by the gradient un-pack
-  const int target = 256 * C::PER_CU;
-  for (int i = 0; i < gb.n; ++i) {
-    GemmProblem& p = gb.p[i];
-    p.tiles_m = cdiv(p.M, C::RM);
-    p.tiles_n = cdiv(p.aug_ones ? (p.n_real > 0 ? p.n_real : 1) : p.N, C::RN);  // the ones column rides in the first column tile
-    const int tiles = p.tiles_m * p.tiles_n;
-    int ks = 1;
-    if (want_split && tiles > 0) {  // every slab gets at least one K stage
-      ks = target / (all_tiles > 0 ? all_tiles : 1);
-      const int max_by_k = cdiv(p.K, X3_BK);
-      if (ks > max_by_k) ks = max_by_k;
-      if (ks > max_slabs) ks = max_slabs;
-      if (ks < 1) ks = 1;
-    }
-    int kchunk = cdiv(cdiv(p.K, ks), X3_BK) * X3_BK;
-    if (kchunk < X3_BK) kchunk = X3_BK;
-    ks = p.K > 0 ? cdiv(p.K, kchunk) : 1;
-    p.ksplit = ks;
-    p.kchunk = kchunk;
-    p.tile_start = start;
-    start += tiles * ks;
-  }
-  gb.total_tiles = start;
+  // at config 3, and every slab is written here and read again by the gradient un-pack; every slab gets at least one K stage
+  const int start = gemm_plan_tiles(gb, C::RM, C::RN, X3_BK, true, want_split, [&](const GemmProblem& p, int all_tiles, double) {
+    return std::max(1, std::min({256 * C::PER_CU / all_tiles, cdiv(p.K, X3_BK), max_slabs}));
+  });
   if (start == 0) return HMP_OK;
-  int form = -1;
-  for (int i = 0; i < gb.n; ++i) {
-    const GemmProblem& p = gb.p[i];
-    const int f = (!p.trans_a && p.trans_b) ? 0 : (!p.trans_a && !p.trans_b) ? 1 : (p.trans_a && !p.trans_b) ? 2 : 3;
-    form = (form == -1 || form == f) ? f : 3;
-  }
+  const int form = launch_form(gb);
   static bool attr_done = false;  // (per configuration: one static per template instance)
   if (!attr_done) {
 #define X3_ATTR(ONES_, FORM_) \
@@ -449,10 +421,10 @@ int x3_launch_cfg(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st)
 // over more nodes the outputs are at most 192 columns wide and the tall fp32 kernel of gemm.hip is faster (0.52 against 0.65 ms at
 // batch 2048).  HMP_GEMM_X3=0: never; =2: every split-K launch.
 static bool x3_takes_problems(const GemmProblem* ps, int n, bool want_split) {
-  const char* v = getenv("HMP_GEMM_X3");
-  if (v && v[0] == '0') return false;
+  const int v = env_switch("HMP_GEMM_X3");
+  if (v == '0') return false;
   if (n <= 0) return false;
-  const bool all_split = v && v[0] == '2';
+  const bool all_split = v == '2';
   double work = 0.0;
   for (int i = 0; i < n; ++i) {
     const GemmProblem& p = ps[i];
@@ -491,8 +463,8 @@ int gemm_x3_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st
       pad_sq += (double)gb.p[i].M * (cdiv(gb.p[i].N, 128) * 128);
       pad_nr += (double)gb.p[i].M * (cdiv(gb.p[i].N, 64) * 64);
     }
-    const char* tv = getenv("HMP_GEMM_X3_TILE");  // 128 / 64: pin the square / the narrow tile (tests, measurements)
-    const bool narrow = tv ? (tv[0] == '6') : (t_sq < 410 || pad_nr <= 0.8 * pad_sq);
+    const int tv = env_switch("HMP_GEMM_X3_TILE");  // 128 / 64: pin the square / the narrow tile (tests, measurements)
+    const bool narrow = tv >= 0 ? (tv == '6') : (t_sq < 410 || pad_nr <= 0.8 * pad_sq);
     if (narrow) return x3_launch_cfg<X3Narrow>(gb, want_split, max_slabs, st);
   }
   return x3_launch_cfg<X3Small>(gb, want_split, max_slabs, st);

@@ -57,6 +57,95 @@ struct GemmBatch {
   GemmProblem p[GEMM_MAX_PROB];
 };
 
+// Tile grid and split-K layout of a tiled launch with BM x BN tiles and K stages of BK: fills tiles_m, tiles_n, ksplit, kchunk and
+// tile_start of every problem and gb.total_tiles (returned).  fold_ones: the virtual ones column rides in the first column tile
+// (tiles_n counts the n_real columns).  want(p, all_tiles, tiles_k) is the launcher's wanted split of a problem with tiles, asked
+// only for a split-K launch (all_tiles: tiles of the launch; tiles_k: their sum of tiles x K); the K chunk is that split rounded
+// up to whole K stages, so the split used is cdiv(K, kchunk) (1 when K == 0).
+template <class Want>
+int gemm_plan_tiles(GemmBatch& gb, int BM, int BN, int BK, bool fold_ones, bool want_split, Want want) {
+  int all_tiles = 0;
+  double tiles_k = 0.0;
+  for (int i = 0; i < gb.n; ++i) {
+    GemmProblem& p = gb.p[i];
+    p.tiles_m = cdiv(p.M, BM);
+    p.tiles_n = cdiv(fold_ones && p.aug_ones ? (p.n_real > 0 ? p.n_real : 1) : p.N, BN);
+    all_tiles += p.tiles_m * p.tiles_n;
+    tiles_k += (double)(p.tiles_m * p.tiles_n) * p.K;
+  }
+  int start = 0;
+  for (int i = 0; i < gb.n; ++i) {
+    GemmProblem& p = gb.p[i];
+    const int tiles = p.tiles_m * p.tiles_n;
+    const int ks = (want_split && tiles > 0) ? want(p, all_tiles, tiles_k) : 1;
+    int kchunk = cdiv(cdiv(p.K, ks), BK) * BK;
+    if (kchunk < BK) kchunk = BK;
+    p.ksplit = p.K > 0 ? cdiv(p.K, kchunk) : 1;
+    p.kchunk = kchunk;
+    p.tile_start = start;
+    start += tiles * p.ksplit;
+  }
+  gb.total_tiles = start;
+  return start;
+}
+
+// operand form shared by every problem of the launch (the executor's launches are uniform): 0 = NT, 1 = NN, 2 = TN, else 3 (the
+// kernels' run-time variant)
+inline int launch_form(const GemmBatch& gb) {
+  int form = -1;
+  for (int i = 0; i < gb.n; ++i) {
+    const GemmProblem& p = gb.p[i];
+    const int f = (!p.trans_a && p.trans_b) ? 0 : (!p.trans_a && !p.trans_b) ? 1 : (p.trans_a && !p.trans_b) ? 2 : 3;
+    form = (form == -1 || form == f) ? f : 3;
+  }
+  return form;
+}
+
+// A batch split between a specialist kernel and the launcher that goes on with the rest: taken[] are the indices of the problems
+// the specialist takes, rest holds the others in order and rest_idx[] their indices in the batch
+struct GemmPeel {
+  int n_taken;
+  int taken[GEMM_MAX_PROB];
+  int rest_idx[GEMM_MAX_PROB];
+  GemmBatch rest;
+};
+template <class Pred>
+void gemm_peel(const GemmBatch& gb, Pred takes, GemmPeel& s) {
+  memset(&s, 0, sizeof(s));
+  for (int i = 0; i < gb.n; ++i) {
+    if (takes(gb.p[i])) {
+      s.taken[s.n_taken++] = i;
+    } else {
+      s.rest_idx[s.rest.n] = i;
+      s.rest.p[s.rest.n++] = gb.p[i];
+    }
+  }
+}
+// launch(s.rest) for the rest of a peeled batch (nothing when it is empty); the split that launch chose goes back into gb
+template <class Launch>
+int gemm_launch_rest(GemmBatch& gb, GemmPeel& s, Launch launch) {
+  if (s.rest.n == 0) return HMP_OK;
+  const int rc = launch(s.rest);
+  for (int i = 0; i < s.rest.n; ++i) {
+    gb.p[s.rest_idx[i]].ksplit = s.rest.p[i].ksplit;
+    gb.p[s.rest_idx[i]].kchunk = s.rest.p[i].kchunk;
+  }
+  return rc;
+}
+
+// Persistent grid of the operand-stationary kernels: row-tile groups in sets of 8 (one per XCD), as many sets as per_cu
+// workgroups per CU allow next to n_slices column slices (at least one set), no more groups than the n_tiles row tiles fill
+struct XcdGrid {
+  int groups, tiles_per_group;
+};
+inline XcdGrid xcd_set_grid(int per_cu, int n_slices, int n_tiles) {
+  int sets = per_cu * device_cu_count() / (8 * n_slices);
+  if (sets < 1) sets = 1;
+  int groups = 8 * sets;
+  if (groups > n_tiles) groups = ((n_tiles + 7) / 8) * 8;
+  return {groups, cdiv(n_tiles, groups)};
+}
+
 // chooses tile shape + split-K (only when want_split: C is then a stack of slabs) and launches
 int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st);
 // same contract on the bf16 matrix pipe (operands rounded to bf16 on their way into LDS, fp32 accumulate): gemm_bf16.hip

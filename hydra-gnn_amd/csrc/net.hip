@@ -200,15 +200,14 @@ struct hmp_net {
 namespace {
 
 void read_env(hmp_net* n) {
-  auto is = [](const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; };
   EnvSwitches e;
-  e.plan_sliced = !is("HMP_PLAN_SLICED", '0');
-  e.front = !is("HMP_FRONT", '0');
-  e.z16 = !is("HMP_Z16", '0');
-  e.h16 = !is("HMP_H16", '0');
-  e.rootcopy = is("HMP_ROOTCOPY", '1');
-  e.tn_direct = !is("HMP_TN", '0');
-  e.bf16_all = is("HMP_BF16_ALL", '1');
+  e.plan_sliced = env_switch("HMP_PLAN_SLICED") != '0';
+  e.front = env_switch("HMP_FRONT") != '0';
+  e.z16 = env_switch("HMP_Z16") != '0';
+  e.h16 = env_switch("HMP_H16") != '0';
+  e.rootcopy = env_switch("HMP_ROOTCOPY") == '1';
+  e.tn_direct = env_switch("HMP_TN") != '0';
+  e.bf16_all = env_switch("HMP_BF16_ALL") == '1';
   n->env = e;
 }
 
@@ -1680,8 +1679,8 @@ extern "C" int hmp_net_create(const hmp_net_spec* spec, hmp_net** out) {
     }
   }
   if (r == HMP_OK) {
-    const char* fz = getenv("HMP_FUSE");
-    n->fuse_mode = fz ? (fz[0] == '1' ? 1 : 0) : -1;
+    const int fz = env_switch("HMP_FUSE");
+    n->fuse_mode = fz < 0 ? -1 : fz == '1' ? 1 : 0;
   }
   if (r != HMP_OK) {
     hmp_net_destroy(n);

@@ -404,8 +404,8 @@ int plan_launch(PlanBatch& pb, int* d_status, hipStream_t st) {
   }
   const int64_t E = pb.edge_start[pb.n];
   const int64_t rows = pb.row_start[2 * pb.n];
-  const char* sm = getenv("HMP_PLAN_SMALL");  // 0 / 1 pins the multi-launch / single-launch build (tests); unset: by size
-  const int small_mode = sm ? (sm[0] == '1' ? 1 : 0) : -1;
+  const int sm = env_switch("HMP_PLAN_SMALL");  // 0 / 1 pins the multi-launch / single-launch build (tests); unset: by size
+  const int small_mode = sm < 0 ? -1 : sm == '1' ? 1 : 0;
   if (small_mode == 1 || (small_mode < 0 && E <= PS_MAX_EDGES)) {
     PlanSmallArgs a;
     a.pb = pb;
