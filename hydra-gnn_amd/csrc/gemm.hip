@@ -555,7 +555,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_tall_kernel(const TallBatch tb
 
 // problems of a split-K launch the tall kernel takes
 static bool tall_takes(const GemmProblem& p) {
-  if (env_switch("HMP_GEMM_TALL") == '0') return false;  // the tiled split-K kernel for every weight gradient (tests compare the two)
+  if (env_switch("HMP_GEMM_TALL") == '0') return false;  // the tiled split-K kernel for every weight gradient (tests/test_gpu_gemm_launch.py compares the two)
   return p.trans_a && !p.trans_b && p.M > 0 && p.M <= TT_M && (p.M & 3) == 0 && p.N > 0 && p.K >= 32768 && (p.lda & 3) == 0 && (p.ldb & 1) == 0 &&
          (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 7) == 0 && p.epi == EPI_NONE &&
          (p.n_real & 1) == 0;
@@ -621,7 +621,7 @@ int gemm_launch(GemmBatch& gb, bool want_split, int max_slabs, hipStream_t st) {
   // big problems (many tiles, or few tiles over a very deep K: the weight gradients of a 10^6-node graph): 64x64 tiles;
   // small ones: 32x32 tiles with in-block K split and deep K stages
   // 128x128 tiles (2x2 accumulator tiles per wave) once they still fill the chip: >= 256 of them, or a split-K launch (the
-  // K chunks supply the workgroups); HMP_GEMM_BIG=0 keeps the 64x64 form (tests compare the two)
+  // K chunks supply the workgroups); HMP_GEMM_BIG=0 keeps the 64x64 form (tests/test_gpu_gemm_launch.py compares the two)
   if (tiles64 >= 1024 || work >= 1e9) {
     int64_t tiles128 = 0;
     for (int i = 0; i < gb.n; ++i) tiles128 += (int64_t)cdiv(gb.p[i].M, 128) * cdiv(gb.p[i].N, 128);
@@ -659,4 +659,70 @@ extern "C" int hmp_gemm_f32(const float* d_a, int32_t lda, int32_t trans_a, cons
   p.epi = EPI_NONE;
   if (M == 0 || N == 0) return HMP_OK;
   return gemm_launch(gb, false, 1, (hipStream_t)stream);
+}
+
+// unit-test entry of the three grouped launchers: a plain copy of the descriptors into the launcher's table, no choice of its own
+extern "C" int hmp_gemm_grouped(const hmp_gemm_desc* d, int32_t n, int32_t route, int32_t want_split, int32_t max_slabs,
+                                int32_t* ksplit_out, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_gemm_grouped: no gfx950 device visible");
+  HMP_CHECK_ARG((d || n == 0) && n >= 0 && n <= GEMM_MAX_PROB, "hmp_gemm_grouped: %d problems (at most %d)", n, GEMM_MAX_PROB);
+  HMP_CHECK_ARG(route >= 0 && route <= 2 && max_slabs >= 1, "hmp_gemm_grouped: route %d, max_slabs %d", route, max_slabs);
+  for (int i = 0; i < n; ++i) {
+    const hmp_gemm_desc& q = d[i];
+    HMP_CHECK_ARG(q.A && q.B && q.C, "hmp_gemm_grouped: null pointer (problem %d)", i);
+    HMP_CHECK_ARG(q.M >= 0 && q.N >= 0 && q.K >= 0, "hmp_gemm_grouped: negative size (problem %d)", i);
+    HMP_CHECK_ARG(q.n_real == q.N - (q.aug_ones ? 1 : 0) && q.n_real >= 0, "hmp_gemm_grouped: n_real %d, N %d, aug_ones %d (problem %d)",
+                  q.n_real, q.N, q.aug_ones, i);
+    HMP_CHECK_ARG(q.lda >= (q.trans_a ? q.M : q.K) && q.ldb >= (q.trans_b ? q.K : q.n_real) && q.ldc >= q.N,
+                  "hmp_gemm_grouped: leading dimension too small (problem %d)", i);
+    HMP_CHECK_ARG(q.epi == EPI_NONE || (q.epi == EPI_ACTMASK && q.H && q.ldh >= q.N), "hmp_gemm_grouped: epilogue (problem %d)", i);
+    HMP_CHECK_ARG(!q.Cadd || q.ldadd >= q.N, "hmp_gemm_grouped: ldadd too small (problem %d)", i);
+    HMP_CHECK_ARG(q.drop_p >= 0.f && q.drop_p < 1.f, "hmp_gemm_grouped: drop_p %g (problem %d)", (double)q.drop_p, i);
+    HMP_CHECK_ARG(!want_split || q.M == 0 || q.slab_stride >= (int64_t)q.M * q.ldc, "hmp_gemm_grouped: slab_stride (problem %d)", i);
+    HMP_CHECK_ARG(route == 1 || !(q.a_bf16 || q.b_bf16 || q.c_bf16 || q.h_bf16), "hmp_gemm_grouped: bf16 operands on route %d", route);
+    HMP_CHECK_ARG(route != 2 || (q.trans_a && !q.trans_b && q.epi == EPI_NONE && !q.Cadd),
+                  "hmp_gemm_grouped: the direct kernel takes the plain TN form only (problem %d)", i);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (route == 2) {
+    TnBatch tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.n = n;
+    for (int i = 0; i < n; ++i) {
+      const hmp_gemm_desc& q = d[i];
+      TnProblem& P = tb.p[i];
+      P.A = (const float*)q.A; P.B = (const float*)q.B; P.C = (float*)q.C; P.slab_stride = q.slab_stride;
+      P.M = q.M; P.N = q.N; P.K = q.K; P.lda = q.lda; P.ldb = q.ldb; P.ldc = q.ldc;
+      P.n_real = q.n_real; P.aug_ones = q.aug_ones;
+    }
+    int ok = 0;
+    HMP_TRY(gemm_tn_direct_launch(tb, max_slabs, &ok, st));
+    if (ksplit_out)
+      for (int i = 0; i < n; ++i) ksplit_out[i] = ok ? tb.p[i].ksplit : 0;
+    return HMP_OK;
+  }
+  GemmBatch gb;
+  memset(&gb, 0, sizeof(gb));
+  gb.n = n;
+  for (int i = 0; i < n; ++i) {
+    const hmp_gemm_desc& q = d[i];
+    GemmProblem& p = gb.p[i];
+    p.A = (const float*)q.A; p.B = (const float*)q.B; p.C = (float*)q.C; p.H = (const float*)q.H;
+    p.a_bf16 = q.a_bf16; p.b_bf16 = q.b_bf16; p.c_bf16 = q.c_bf16; p.h_bf16 = q.h_bf16;
+    p.slab_stride = q.slab_stride;
+    p.M = q.M; p.N = q.N; p.K = q.K;
+    p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc; p.ldh = q.ldh;
+    p.trans_a = q.trans_a; p.trans_b = q.trans_b;
+    p.n_real = q.n_real; p.aug_ones = q.aug_ones;
+    p.epi = q.epi; p.act = q.act;
+    p.drop_on = q.drop_p > 0.f ? 1 : 0;
+    p.drop.thresh = drop_thresh(q.drop_p); p.drop.scale = 1.f / (1.f - q.drop_p);  // (as net.hip: make_drop)
+    p.Cadd = q.Cadd; p.ldadd = q.ldadd;
+  }
+  const int rc = route == 0 ? gemm_launch(gb, want_split != 0, max_slabs, st) : gemm_bf16_launch(gb, want_split != 0, max_slabs, st);
+  if (ksplit_out)
+    for (int i = 0; i < n; ++i) ksplit_out[i] = gb.p[i].ksplit;
+  return rc;
 }

@@ -36,6 +36,7 @@ size_t hmp_sizeof(int which) {
     case 7: return sizeof(hmp_head_targets);
     case 8: return sizeof(hmp_linear_heads);
     case 9: return sizeof(hmp_linear_head_targets);
+    case 10: return sizeof(hmp_gemm_desc);
     default: return 0;
   }
 }

@@ -112,7 +112,18 @@ class CollateItem(C.Structure):
                 ("slot", C.c_int32), ("slot_src", C.c_int32), ("slot_dst", C.c_int32)]
 
 
-_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets]
+class GemmDesc(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("H", C.c_void_p), ("Cadd", C.c_void_p),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32),
+        ("ldh", C.c_int32), ("ldadd", C.c_int32), ("trans_a", C.c_int32), ("trans_b", C.c_int32),
+        ("n_real", C.c_int32), ("aug_ones", C.c_int32), ("slab_stride", C.c_int64),
+        ("epi", C.c_int32), ("act", C.c_int32), ("drop_p", C.c_float),
+        ("a_bf16", C.c_int32), ("b_bf16", C.c_int32), ("c_bf16", C.c_int32), ("h_bf16", C.c_int32),
+    ]
+
+
+_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -194,6 +205,7 @@ SIGNATURES = {
     "hmp_htree_destroy": (None, [_VP]),
     "hmp_gemm_bf16_dx": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _I32, _I32, _VP]),
     "hmp_gemm_bf16_dw": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _I64, _I32, C.POINTER(_I32), _I32, _I32, _I32, _VP]),
+    "hmp_gemm_grouped": (C.c_int, [C.POINTER(GemmDesc), _I32, _I32, _I32, _I32, C.POINTER(_I32), _VP]),
     "hmp_comm_unique_id": (C.c_int, [_VP]),
     "hmp_comm_create": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP)]),
     "hmp_comm_destroy": (None, [_VP]),

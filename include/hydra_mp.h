@@ -33,7 +33,8 @@ extern "C" {
  *    (hmp_sizeof 9), hmp_net_set_linear_heads / hmp_net_step_heads_fwd_bwd / hmp_net_step_heads_fused /
  *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state;
  *    hmp_count_correct_rows / hmp_net_count_correct_rooms: the device-side validation count of the room task;
- *    hmp_net_set_head_pools: the two-headed step / count with each head's CE on the mean over a pool edge type (LeafPool) */
+ *    hmp_net_set_head_pools: the two-headed step / count with each head's CE on the mean over a pool edge type (LeafPool);
+ *    hmp_gemm_desc (hmp_sizeof 10), hmp_gemm_grouped: unit-test entry of the grouped GEMM launchers */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -54,7 +55,8 @@ extern "C" {
 int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
- * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets (lets a foreign-language binding verify its struct mirror) */
+ * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets, 10 hmp_gemm_desc (lets a
+ * foreign-language binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -127,6 +129,30 @@ int hmp_gemm_bf16_dx(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, 
 int hmp_gemm_bf16_dw(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const void* d_h,
                      int32_t ldh, int32_t h_bf16, float* d_slabs, int32_t ldc, int64_t slab_stride, int32_t max_slabs,
                      int32_t* n_slabs, int32_t Mw, int32_t F, int32_t nodes, void* stream);
+/* Unit-test entry of the grouped launchers as the executor calls them: n <= 8 problems in one launch, each copied as it stands
+ * into the launcher's problem table (csrc/gemm.hip); the launcher alone chooses the kernels.  One problem: C[M, N] = op(A) *
+ * op([B | 1]) (+ Cadd) (. act'(H) / (1 - drop_p) under epi = 1), fp32 unless a *_bf16 flag says otherwise (route 1 only, ld* then
+ * count elements).  B has n_real columns in memory, N = n_real + 1 with the virtual ones column (aug_ones), N = n_real without.
+ * Split-K (want_split): slab z of C lies at C + z * slab_stride, the caller sums the slabs.  epi = 1 (EPI_ACTMASK): the result is
+ * multiplied by act' (HMP_ACT_*) of the stored activations H [M][ldh]; drop_p > 0: an element of H stored as -0.0 is a dropped
+ * one (factor 0), kept ones are scaled by 1 / (1 - drop_p).  Cadd: fp32 [M][ldadd] added to the product before the mask. */
+typedef struct hmp_gemm_desc {
+  const void *A, *B;
+  void* C;
+  const void* H;
+  const float* Cadd;
+  int32_t M, N, K, lda, ldb, ldc, ldh, ldadd, trans_a, trans_b;
+  int32_t n_real, aug_ones;
+  int64_t slab_stride;
+  int32_t epi, act;
+  float drop_p;
+  int32_t a_bf16, b_bf16, c_bf16, h_bf16;
+} hmp_gemm_desc;
+/* route 0: the fp32 launcher (tiled, tall TN and x3 kernels), 1: the bf16 launcher (tiled 128 / 256, dx, dw, weight-stationary),
+ * 2: the register-direct TN kernel (trans_a = 1, trans_b = 0, fp32, no epilogue, no Cadd).  ksplit_out[i] (may be NULL): the
+ * slabs written for problem i; route 2: all 0 when the kernel declined (a problem would need more than max_slabs) and nothing ran */
+int hmp_gemm_grouped(const hmp_gemm_desc* d, int32_t n, int32_t route, int32_t want_split, int32_t max_slabs, int32_t* ksplit_out,
+                     void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 4. K3 -- GAT edge softmax + weighted aggregation, one row group of lanes per destination row.

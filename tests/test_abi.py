@@ -71,6 +71,10 @@ def test_no_cpu_fallback():
     h = C.c_void_p()
     assert lib.hmp_net_create(C.byref(spec), C.byref(h)) != 0
     assert b"gfx950" in lib.hmp_last_error()
+    buf = (C.c_float * 64)()
+    d = _lib.GemmDesc(A=C.addressof(buf), B=C.addressof(buf), C=C.addressof(buf), M=4, N=4, K=4, lda=4, ldb=4, ldc=4, n_real=4)
+    assert lib.hmp_gemm_grouped(C.byref(d), 1, 0, 0, 1, None, None) != 0
+    assert b"gfx950" in lib.hmp_last_error()
     from hydra_gnn_amd import workloads
     from hydra_gnn_amd.models import HeterogeneousNetwork
 

@@ -206,24 +206,35 @@ def test_front_kernel_and_direct_weight_gradient_agree_with_separate_launches(mo
         assert float((d > 2e-5).double().mean()) < 0.01, k
 
 
-def test_front_kernel_odd_shapes():
-    """rooms-only tiles, a node type with K = 6 (one ragged stage), hidden 40 (segments that straddle 64-column tiles)"""
+def test_front_kernel_odd_shapes(monkeypatch):
+    """rooms-only tiles, a node type with K = 6 (one ragged stage), hidden 40 (segments that straddle 64-column tiles); the weight
+    gradients on the register-direct TN kernel (HMP_TN unset) and on the LDS-staged split-K kernel (HMP_TN=0), both against the
+    oracle, and bitwise different from each other (the staged kernel really ran)"""
     kw = dict(SAGE_KW, hidden_dim=40)
     batch = workloads.config2_batch(3)
-    with fuse_env("1"):
-        ora, net = build(kw, HeterogeneousNetwork, omodels.HeterogeneousNetwork)
-        pred, loss, grads = run_fwd_bwd(net, batch, "rooms")
-    o64 = copy.deepcopy(ora).double()
-    b64 = batch.to("cpu")
-    for t in b64.node_types:
-        b64[t].x = b64[t].x.double()
-    pred_ref = o64(b64)
-    y = batch["rooms"].y
-    o64.loss(pred_ref, y, y != 25).backward()
-    torch.testing.assert_close(pred.cpu().double(), pred_ref.detach(), atol=ATOL, rtol=RTOL)
-    for name, p in o64.named_parameters():
-        if p.grad is not None:
-            torch.testing.assert_close(grads[name].cpu().double(), p.grad, atol=ATOL, rtol=RTOL, msg=lambda m: f"{name}: {m}")
+    weight_grads = {}
+    for tn in (None, "0"):
+        if tn is None:
+            monkeypatch.delenv("HMP_TN", raising=False)
+        else:
+            monkeypatch.setenv("HMP_TN", tn)
+        with fuse_env("1"):
+            ora, net = build(kw, HeterogeneousNetwork, omodels.HeterogeneousNetwork)
+            pred, loss, grads = run_fwd_bwd(net, batch, "rooms")
+        o64 = copy.deepcopy(ora).double()
+        b64 = batch.to("cpu")
+        for t in b64.node_types:
+            b64[t].x = b64[t].x.double()
+        pred_ref = o64(b64)
+        y = batch["rooms"].y
+        o64.loss(pred_ref, y, y != 25).backward()
+        torch.testing.assert_close(pred.cpu().double(), pred_ref.detach(), atol=ATOL, rtol=RTOL)
+        for name, p in o64.named_parameters():
+            if p.grad is not None:
+                torch.testing.assert_close(grads[name].cpu().double(), p.grad, atol=ATOL, rtol=RTOL, msg=lambda m: f"{tn} {name}: {m}")
+        weight_grads[tn] = {k: g for k, g in grads.items() if g is not None and g.dim() == 2}
+    monkeypatch.delenv("HMP_TN", raising=False)
+    assert any(not torch.equal(g, weight_grads["0"][k]) for k, g in weight_grads[None].items()), "HMP_TN=0 changed no weight gradient"
 
 
 def test_bf16_compute_mode_on_a_large_graph():
