@@ -91,18 +91,45 @@ __device__ __forceinline__ void store_z(const Acc<4>& a, float* base, int64_t id
   }
 }
 
-// sum_{k in [b,e)} x[col[k]][c .. c+VEC)   in edge order; NV column chunks per lane (stride GS*VEC).
+// Per-edge weight of a gather, a compile-time policy.  NoW: none -- plain adds.  MeanW: the backward of the mean, every edge carries
+// 1 / max(deg(dst), 1).  `degf` (the reciprocal per destination, written by the plan) removes the two dependent rowptr loads per
+// edge AND the per-edge fp32 divisions (4 per lane and edge: ~1 ms of the config-5 transposed aggregation); without it (unit entry
+// point, unit-test path) the reciprocal is derived from rowptr.  Table or derived, and mean = 0 (a plain sum after all), are
+// launch-uniform run-time cases of the one policy: the kernels are not instantiated per case.
+struct NoW {
+  static constexpr bool weighted = false;
+};
+struct MeanW {
+  static constexpr bool weighted = true;
+  const int* rowptr;
+  const float* degf;
+  int mean;
+  __device__ __forceinline__ float derived(int i) const {
+    const int deg = rowptr[i + 1] - rowptr[i];
+    return 1.f / (float)(deg > 1 ? deg : 1);
+  }
+};
+
+// sum_{k in [b,e)} w(col[k]) * x[col[k]][c .. c+VEC)   in edge order; NV column chunks per lane (stride GS*VEC).
 // Neighbours are processed in batches of UB = 8 (4 for wide rows) with NO tail loop: ids beyond the row are clamped to the
 // last valid entry (same address => cache hit) and masked at the add.  A row of degree <= 8 therefore costs three
 // dependent memory round trips (extent, ids, rows) instead of one per tail neighbour.
-template <int GS, int NV, int VEC, bool ZB = false>
+template <int GS, int NV, int VEC, bool ZB = false, class W = NoW>
 __device__ __forceinline__ void gather_sum(Acc<VEC> (&acc)[NV], const float* __restrict__ x, int ld, const int* __restrict__ col,
-                                           int b, int e, int c0, int F) {
+                                           int b, int e, int c0, int F, const W w = W()) {
   constexpr int UB = (NV == 1) ? 8 : 4;
   for (int k = b; k < e; k += UB) {
     int j[UB];
 #pragma unroll
     for (int u = 0; u < UB; ++u) j[u] = col[min(k + u, e - 1)];
+    [[maybe_unused]] float d[UB];
+    if constexpr (W::weighted) {
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        d[u] = 1.f;
+        if (w.mean) d[u] = w.degf ? w.degf[j[u]] : w.derived(j[u]);
+      }
+    }
     Acc<VEC> v[UB][NV];
 #pragma unroll
     for (int u = 0; u < UB; ++u)
@@ -121,62 +148,102 @@ __device__ __forceinline__ void gather_sum(Acc<VEC> (&acc)[NV], const float* __r
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
           const int c = c0 + q * GS * VEC;
-          if (c < F) acc[q].add(v[u][q]);
+          if (c < F) {
+            if constexpr (W::weighted) {
+              if (w.mean) acc[q].add_mul(v[u][q], d[u]); else acc[q].add(v[u][q]);
+            } else {
+              acc[q].add(v[u][q]);
+            }
+          }
         }
       }
   }
 }
 
-// sum_k g[tcol[k]][c..] * rdeg(tcol[k])  (backward of the mean: every edge carries 1 / max(deg(dst), 1)).
-// `rdeg` (the reciprocal per destination, written by the plan) removes the two dependent rowptr loads per edge AND the
-// per-edge fp32 divisions (4 per lane and edge: ~1 ms of the config-5 transposed aggregation); without it (unit entry
-// point) the reciprocal is derived from rowptr.  Same clamped batches as gather_sum.
-template <int GS, int NV, int VEC, bool GB = false>
-__device__ __forceinline__ void gather_sum_w(Acc<VEC> (&acc)[NV], const float* __restrict__ g, int ld, const int* __restrict__ tcol,
-                                             const int* __restrict__ rowptr, const float* __restrict__ rdeg, int mean, int b, int e,
-                                             int c0, int F) {
-  constexpr int UB = (NV == 1) ? 8 : 4;
-  for (int k = b; k < e; k += UB) {
-    int i[UB];
+// One side of a paired gather: rows x[col[k]] (pitch ld, in elements; a column offset is part of x), k in [b, e), the lane's
+// 4 columns valid while c0 < F.
+struct GatherSide {
+  const float* x;
+  int ld;
+  const int* col;
+  int b, e, F;
+};
+
+// Two edge types at a time: the neighbour ids of both types travel together, then the 16 neighbour rows -- three dependent
+// round trips (extents, ids, rows) for two edge types instead of five.  A missing partner aliases the first type with an
+// empty extent (loads hit the same lines, adds are masked).  a0 / a1 = the two sums, each in the edge order of its type.
+// ZB: the rows hold bf16 elements (load_z).  kt: this call stamps the KTIME phases 5 (ids here) and 6 (first rows here).
+template <int GS, bool ZB, class W>
+__device__ __forceinline__ void gather_pair(const GatherSide& s0, const GatherSide& s1, const W& w0, const W& w1, int c0,
+                                            Acc<4> (&a0)[1], Acc<4> (&a1)[1], [[maybe_unused]] bool kt) {
+  constexpr int UB = 8;
+  const int b0 = s0.b, e0 = s0.e, b1 = s1.b, e1 = s1.e;
+  // GS <= 16 (rows of <= 64 floats, the MP3D hidden width): ids of neighbours 0..7 AND 8..15 of both types in the same round
+  // trip -- a row of 9..16 neighbours (most 16-row blocks of a scene-graph batch hold one) then needs one more round trip
+  // for its second batch of rows instead of two.  Wider rows keep the plain tail: the 16 extra registers cost them a wave
+  // per SIMD (config 4: 0.140 -> 0.151 ms).
+  constexpr bool PRE = GS <= 16;
+  int j0[UB], j1[UB], j0t[PRE ? UB : 1], j1t[PRE ? UB : 1];
 #pragma unroll
-    for (int u = 0; u < UB; ++u) i[u] = tcol[min(k + u, e - 1)];
-    float d[UB];
+  for (int u = 0; u < UB; ++u) {
+    j0[u] = s0.col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
+    j1[u] = s1.col[e1 > b1 ? min(b1 + u, e1 - 1) : 0];
+    if constexpr (PRE) {
+      j0t[u] = s0.col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
+      j1t[u] = s1.col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
+    }
+  }
+  [[maybe_unused]] float d0[UB], d1[UB];
+  Acc<4> v0[UB], v1[UB];
+  const int cc0 = c0 < s0.F ? c0 : 0, cc1 = c0 < s1.F ? c0 : 0;
+  [[maybe_unused]] bool mean = false, dg = false;  // block-uniform
+  if constexpr (W::weighted) {
+    mean = w0.mean;
+    dg = mean && w0.degf && w1.degf;
+  }
+  a0[0].zero();
+  a1[0].zero();
+  // 8 rows of each side at ids i0 / i1 (edges off .. off + 7 of the extents), through the same registers every time
+  auto batch = [&](const int (&i0)[UB], const int (&i1)[UB], int off, [[maybe_unused]] bool stamp) {
 #pragma unroll
     for (int u = 0; u < UB; ++u) {
-      d[u] = 1.f;
-      if (mean) {
-        if (rdeg) {
-          d[u] = rdeg[i[u]];
-        } else {
-          const int deg = rowptr[i[u] + 1] - rowptr[i[u]];
-          d[u] = 1.f / (float)(deg > 1 ? deg : 1);
+      if constexpr (W::weighted) {
+        d0[u] = dg ? w0.degf[i0[u]] : 1.f;
+        d1[u] = dg ? w1.degf[i1[u]] : 1.f;
+      }
+      load_z<ZB>(v0[u], s0.x, (int64_t)i0[u] * s0.ld + cc0);
+      load_z<ZB>(v1[u], s1.x, (int64_t)i1[u] * s1.ld + cc1);
+    }
+    if (stamp) KTW(6);
+    if constexpr (W::weighted) {
+      if (mean && !dg) {
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {
+          d0[u] = w0.derived(i0[u]);
+          d1[u] = w1.derived(i1[u]);
         }
       }
     }
-    Acc<VEC> v[UB][NV];
 #pragma unroll
     for (int u = 0; u < UB; ++u)
-#pragma unroll
-      for (int q = 0; q < NV; ++q) {
-        const int c = c0 + q * GS * VEC;
-        if (c < F) {
-          if constexpr (GB && VEC == 4) load_z<true>(v[u][q], g, (int64_t)i[u] * ld + c);
-          else v[u][q].load(g + (int64_t)i[u] * ld + c);
-        }
+      if (b0 + off + u < e0) {
+        if constexpr (W::weighted) a0[0].add_mul(v0[u], d0[u]); else a0[0].add(v0[u]);
       }
-    const int cnt = e - k;
 #pragma unroll
     for (int u = 0; u < UB; ++u)
-      if (u < cnt) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) {
-          const int c = c0 + q * GS * VEC;
-          if (c < F) {
-            if (mean) acc[q].add_mul(v[u][q], d[u]); else acc[q].add(v[u][q]);
-          }
-        }
+      if (b1 + off + u < e1) {
+        if constexpr (W::weighted) a1[0].add_mul(v1[u], d1[u]); else a1[0].add(v1[u]);
       }
+  };
+  if (kt) KTW(5);
+  batch(j0, j1, 0, kt);
+  int done = UB;
+  if constexpr (PRE) {
+    if (e0 - b0 > UB || e1 - b1 > UB) batch(j0t, j1t, UB, false);  // second batch (ids already here)
+    done = 2 * UB;
   }
+  if (e0 - b0 > done) gather_sum<GS, 1, 4, ZB, W>(a0, s0.x, s0.ld, s0.col, b0 + done, e0, c0, s0.F, w0);
+  if (e1 - b1 > done) gather_sum<GS, 1, 4, ZB, W>(a1, s1.x, s1.ld, s1.col, b1 + done, e1, c0, s1.F, w1);
 }
 
 // ----- K1 unit kernels ----------------------------------------------------------------------------
@@ -211,7 +278,7 @@ __global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const float* __re
   Acc<VEC> acc[NV];
 #pragma unroll
   for (int q = 0; q < NV; ++q) acc[q].zero();
-  gather_sum_w<GS, NV, VEC>(acc, g, ldg, t_col, rowptr, nullptr, 1, t_rowptr[row], t_rowptr[row + 1], c0, F);
+  gather_sum<GS, NV, VEC, false, MeanW>(acc, g, ldg, t_col, t_rowptr[row], t_rowptr[row + 1], c0, F, MeanW{rowptr, nullptr, 1});
 #pragma unroll
   for (int q = 0; q < NV; ++q) {
     const int c = c0 + q * GS * VEC;
@@ -220,6 +287,22 @@ __global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const float* __re
 }
 
 // ----- fused SAGE layer aggregation -----------------------------------------------------------------
+// t = dropout(act(t)) for the lane's columns [c, c + 4) of row `row` of entry D (dcfg: D.drop with the step resolved)
+__device__ __forceinline__ void act_drop4(const AggDst& D, const DropCfg& dcfg, int row, int c, Acc<4>& t) {
+  bool keep[4] = {true, true, true, true};
+  if (D.drop_on) drop_keep4(dcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(c >> 2), keep);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float v = t.at(i);
+    if (D.act == HMP_ACT_RELU) v = v > 0.f ? v : 0.f;
+    else if (D.act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
+    // a dropped element is stored as -0.0f (a kept one that happens to be zero as +0.0f): numerically both are 0 for
+    // every consumer, and the backward pass reads the keep bit off the sign instead of regenerating the draws
+    if (D.drop_on) v = keep[i] ? (v * D.drop.scale + 0.0f) : -0.0f;  // "+ 0.0f": a kept -0.0 becomes +0.0
+    t.at(i) = v;
+  }
+}
+
 // out[t][i] = dropout(act( zroot[i] + bias + sum_e mean_{k in N_e(i)} z_e[col_k] ))   (one row group, result also in `tot`)
 template <int GS, int NV, bool ZB = false, bool HB = false>
 __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int c0, Acc<4> (&tot)[NV]) {
@@ -299,11 +382,8 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
       }
     }
   } else if constexpr (NV == 1) {
-    // Incoming edge types in PAIRS: the neighbour ids of both types travel together, then the 16 neighbour rows -- three
-    // dependent round trips (extents, ids, rows) for two edge types instead of five.  A missing partner aliases the
-    // first type with an empty extent (loads hit the same lines, adds are masked).  Sums keep the edge order per type
-    // and the type order of the sequential code.
-    constexpr int UB = 8;
+    // incoming edge types in PAIRS (gather_pair); sums keep the edge order per type and the type order of the sequential code
+    static_assert(!ZB, "bf16 rows take their column offset in the element index: the one-wavefront shape only");
 #pragma unroll
     for (int ii = 0; ii < AGG_MAX_IN; ii += 2) {
       if (ii >= D.n_in) break;
@@ -312,60 +392,10 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
       const AggIn& I1 = D.in[has2 ? ii + 1 : ii];
       const int b0 = rb[ii], e0 = re[ii];
       const int b1 = has2 ? rb[ii + 1] : b0, e1 = has2 ? re[ii + 1] : b0;
-      // GS <= 16 (rows of <= 64 floats, the MP3D hidden width): ids of neighbours 0..7 AND 8..15 of both types in the same round
-      // trip -- a row of 9..16 neighbours (most 16-row blocks of a scene-graph batch hold one) then needs one more round trip
-      // for its second batch of rows instead of two.  Wider rows keep the plain tail: the 16 extra registers cost them a wave
-      // per SIMD (config 4: 0.140 -> 0.151 ms).
-      constexpr bool PRE = GS <= 16;
-      int j0[UB], j1[UB], j0t[PRE ? UB : 1], j1t[PRE ? UB : 1];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        j0[u] = I0.col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
-        j1[u] = I1.col[e1 > b1 ? min(b1 + u, e1 - 1) : 0];
-        if constexpr (PRE) {
-          j0t[u] = I0.col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
-          j1t[u] = I1.col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
-        }
-      }
-      Acc<VEC> v0[UB], v1[UB];
-      const bool cin = c0 < D.F;
-      const int cc = cin ? c0 : 0;
-      if (ii == 0) KTW(5);
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        v0[u].load(I0.z + I0.coff + (int64_t)j0[u] * I0.ldz + cc);
-        v1[u].load(I1.z + I1.coff + (int64_t)j1[u] * I1.ldz + cc);
-      }
-      if (ii == 0) KTW(6);
       Acc<VEC> a0[1], a1[1];
-      a0[0].zero();
-      a1[0].zero();
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b0 + u < e0) a0[0].add(v0[u]);
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b1 + u < e1) a1[0].add(v1[u]);
-      int done = UB;
-      if constexpr (PRE) {
-        if (e0 - b0 > UB || e1 - b1 > UB) {  // second batch through the same registers (ids already here)
-#pragma unroll
-          for (int u = 0; u < UB; ++u) {
-            v0[u].load(I0.z + I0.coff + (int64_t)j0t[u] * I0.ldz + cc);
-            v1[u].load(I1.z + I1.coff + (int64_t)j1t[u] * I1.ldz + cc);
-          }
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b0 + UB + u < e0) a0[0].add(v0[u]);
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b1 + UB + u < e1) a1[0].add(v1[u]);
-        }
-        done = 2 * UB;
-      }
-      if (e0 - b0 > done) gather_sum<GS, 1, VEC>(a0, I0.z + I0.coff, I0.ldz, I0.col, b0 + done, e0, c0, D.F);
-      if (e1 - b1 > done) gather_sum<GS, 1, VEC>(a1, I1.z + I1.coff, I1.ldz, I1.col, b1 + done, e1, c0, D.F);
-      if (cin) {
+      gather_pair<GS, false>(GatherSide{I0.z + I0.coff, I0.ldz, I0.col, b0, e0, D.F}, GatherSide{I1.z + I1.coff, I1.ldz, I1.col, b1, e1, D.F},
+                             NoW(), NoW(), c0, a0, a1, ii == 0);
+      if (c0 < D.F) {
         if (e0 > b0) tot[0].add_div(a0[0], mean ? (float)(e0 - b0) : 1.f);
         if (e1 > b1) tot[0].add_div(a1[0], mean ? (float)(e1 - b1) : 1.f);
       }
@@ -393,18 +423,7 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
   for (int q = 0; q < NV; ++q) {
     const int c = c0 + q * GS * VEC;
     if (c >= D.F) continue;
-    bool keep[4] = {true, true, true, true};
-    if (D.drop_on) drop_keep4(dcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(c >> 2), keep);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float v = tot[q].at(i);
-      if (D.act == HMP_ACT_RELU) v = v > 0.f ? v : 0.f;
-      else if (D.act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-      // a dropped element is stored as -0.0f (a kept one that happens to be zero as +0.0f): numerically both are 0 for
-      // every consumer, and the backward pass reads the keep bit off the sign instead of regenerating the draws
-      if (D.drop_on) v = keep[i] ? (v * D.drop.scale + 0.0f) : -0.0f;  // "+ 0.0f": a kept -0.0 becomes +0.0
-      tot[q].at(i) = v;
-    }
+    act_drop4(D, dcfg, row, c, tot[q]);
     if constexpr (HB && VEC == 4) store_z<true>(tot[q], D.out, (int64_t)row * D.ldo + c);
     else tot[q].store(D.out + (int64_t)row * D.ldo + c);
   }
@@ -503,14 +522,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // (32-row tiles -- half the per-row weight traffic, two MFMA row halves sharing each B load -- were measured SLOWER on the
 // H-tree config 4: 0.585 against 0.474 ms/step; half as many blocks, twice the gather passes per block.)
-// GS >= 32 (H-tree, hidden 128: ~1000 blocks of 16 rows): 4 waves per SIMD = 4 blocks per CU keeps the whole launch resident in
-// one round (measured 0.152 -> 0.140 ms over the 4 layers of config 4 despite 148 bytes of spill; the same bound made the
-// backward kernel slower and is not applied there)
-// One 16-row tile [row0, row0 + 16) of destination entry D, rows below row_end, by ONE group of 256 threads (tid = thread inside
-// the group) with its own LDS image Hs [256][17].  Every group of the workgroup must call this the same number of times: the
-// barrier between the aggregation and the projection is workgroup-wide (`valid` = false: a group without a tile only joins it).
+// one 16-row tile [row0, row0 + 16) of destination entry D, rows below row_end, by the workgroup's 256 threads; LDS image Hs [256][17]
 template <int GS>
-__device__ __forceinline__ void agg_proj_tile(const AggArgs& a, const AggDst& D, int row0, int row_end, bool valid, float* Hs) {
+__device__ __forceinline__ void agg_proj_tile(const AggArgs& a, const AggDst& D, int row0, int row_end, float* Hs) {
   constexpr int TM = 16, LDH = 17;
   constexpr int RPP = 256 / GS;            // rows aggregated per pass
   constexpr int NP = TM / RPP;             // passes (GS = 16: 1, 32: 2, 64: 4)
@@ -524,8 +538,8 @@ __device__ __forceinline__ void agg_proj_tile(const AggArgs& a, const AggDst& D,
   // overlaps the three round trips of the gather instead of following them.
   constexpr int PT = 3;
   float4 pre[PT][4];
-  const int n_ct = (valid && D.pw) ? (D.pncols + 15) >> 4 : 0;
-  if (valid && D.pw) {  // group-uniform
+  const int n_ct = D.pw ? (D.pncols + 15) >> 4 : 0;
+  if (D.pw) {  // block-uniform
 #pragma unroll
     for (int it = 0; it < PT; ++it) {
       const int col = min((w + 4 * it) * 16 + n, D.pncols - 1);  // clamped: tiles past n_ct are never used
@@ -534,22 +548,20 @@ __device__ __forceinline__ void agg_proj_tile(const AggArgs& a, const AggDst& D,
       for (int u = 0; u < 4; ++u) pre[it][u] = *reinterpret_cast<const float4*>(wrow + min(16 * u, D.pK - 16) + 4 * kq);
     }
   }
-  if (valid) {
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int m = p * RPP + tid / GS;
-      const int row = row0 + m;
-      Acc<4> tot[1];
-      tot[0].zero();
-      if (row < row_end) agg_row<GS, 1>(D, a.mean, row, c0, tot);
-      if (c0 < D.pK) {
+  for (int p = 0; p < NP; ++p) {
+    const int m = p * RPP + tid / GS;
+    const int row = row0 + m;
+    Acc<4> tot[1];
+    tot[0].zero();
+    if (row < row_end) agg_row<GS, 1>(D, a.mean, row, c0, tot);
+    if (c0 < D.pK) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) Hs[(c0 + i) * LDH + m] = (c0 < D.F && row < row_end) ? tot[0].at(i) : 0.f;
-      }
+      for (int i = 0; i < 4; ++i) Hs[(c0 + i) * LDH + m] = (c0 < D.F && row < row_end) ? tot[0].at(i) : 0.f;
     }
   }
   __syncthreads();
-  if (!valid || D.pw == nullptr) return;  // group-uniform: no tile / this node type is not read by the next layer
+  if (D.pw == nullptr) return;  // block-uniform: this node type is not read by the next layer
   KT(1);
   // one 16-column tile: bv0 = prefetched weights of the first k trip (null: load them here)
   auto tile = [&](int ct, const float4* bv0) {
@@ -588,6 +600,9 @@ __device__ __forceinline__ void agg_proj_tile(const AggArgs& a, const AggDst& D,
   KT(2);
 }
 
+// GS >= 32 (H-tree, hidden 128: ~1000 blocks of 16 rows): 4 waves per SIMD = 4 blocks per CU keeps the whole launch resident in
+// one round (measured 0.152 -> 0.140 ms over the 4 layers of config 4; the same bound made the backward kernel slower and is
+// not applied there)
 template <int GS>
 __global__ __launch_bounds__(256, GS == 32 ? 3 : (GS == 64 ? 2 : 1)) void agg_proj_fwd_kernel(const AggArgs a) {
   __shared__ float Hs[256 * 17];
@@ -599,7 +614,7 @@ __global__ __launch_bounds__(256, GS == 32 ? 3 : (GS == 64 ? 2 : 1)) void agg_pr
   const AggDst& D = a.d[ti];
   // (an entry of heavy rows is cut into tiles of 8: see AggDst::tile_rows)
   const int row0 = ((int)blockIdx.x - D.block_start) * D.tile_rows;
-  agg_proj_tile<GS>(a, D, row0, min(row0 + D.tile_rows, D.n_rows), true, Hs);
+  agg_proj_tile<GS>(a, D, row0, min(row0 + D.tile_rows, D.n_rows), Hs);
   KT_SPAN_END(40, ti);
   KT_BLOCK_END();
 }
@@ -626,20 +641,22 @@ __device__ __forceinline__ void finalize_loss(const float* __restrict__ row_lv, 
 // dz[s][j, seg_e] = sum_{k in out_e(j)} g'[dst_k] / deg(dst_k);   dz[s][j, root] = g'[s][j]
 // GB: the gradient rows (TAggOut::g, TAggSrc::groot) hold bf16 elements (bf16 compute mode at 10^6 rows, see load_z);
 // DZB: so does the output dz (read back by the bf16 GEMMs as their A operand)
-// one row of source entry S by its row group of GS lanes (c0 = first column of the lane); `row` must be < S.n_rows
-template <int GS, int NV, bool GB = false, bool DZB = false>
-__device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S, int row, int c0) {
+// One row of source entry S by its row group of GS lanes (c0 = first column of the lane).  put(v, seg, c) receives every finished
+// piece -- a segment sum or the root copy: the lane's 4 elements at column c of the segment that starts at column `seg` of dz --
+// and decides where it goes.
+// live = false (a row past the entry's end inside a tile): extents read as 0 and the root as zeros, nothing is loaded for the row.
+template <int GS, int NV, bool GB, class Sink>
+__device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S, int row, bool live, int c0, const Sink& put) {
   constexpr int VEC = 4;
   int rb[AGG_MAX_IN], re[AGG_MAX_IN];
 #pragma unroll
   for (int oi = 0; oi < AGG_MAX_IN; ++oi) {
     rb[oi] = re[oi] = 0;
-    if (oi < S.n_out) { rb[oi] = S.out[oi].t_rowptr[row]; re[oi] = S.out[oi].t_rowptr[row + 1]; }
+    if (live && oi < S.n_out) { rb[oi] = S.out[oi].t_rowptr[row]; re[oi] = S.out[oi].t_rowptr[row + 1]; }
   }
   // (the 16-wide scalar-id form of agg_row was measured here too: 6.94 -> 7.02 ms at config 5, not kept)
   if constexpr (NV == 1) {
-    // outgoing edge types in PAIRS (see agg_row): ids of both, then 1/deg + gradient rows of both
-    constexpr int UB = 8;
+    // outgoing edge types in PAIRS (gather_pair): ids of both, then 1/deg + gradient rows of both
 #pragma unroll
     for (int oi = 0; oi < AGG_MAX_IN; oi += 2) {
       if (oi >= S.n_out) break;
@@ -648,77 +665,11 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
       const TAggOut& O1 = S.out[has2 ? oi + 1 : oi];
       const int b0 = rb[oi], e0 = re[oi];
       const int b1 = has2 ? rb[oi + 1] : b0, e1 = has2 ? re[oi + 1] : b0;
-      // GS <= 16: the ids of out-edges 8..15 travel with those of 0..7 (see agg_row): one round trip less for rows of 9..16 edges
-      constexpr bool PRE = GS <= 16;
-      int i0[UB], i1[UB], i0t[PRE ? UB : 1], i1t[PRE ? UB : 1];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        i0[u] = O0.t_col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
-        i1[u] = O1.t_col[e1 > b1 ? min(b1 + u, e1 - 1) : 0];
-        if constexpr (PRE) {
-          i0t[u] = O0.t_col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
-          i1t[u] = O1.t_col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
-        }
-      }
-      float d0[UB], d1[UB];
-      Acc<VEC> v0[UB], v1[UB];
-      const int cc0 = c0 < O0.F ? c0 : 0, cc1 = c0 < O1.F ? c0 : 0;
-      const bool dg = a.mean && O0.degf && O1.degf;  // block-uniform
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        d0[u] = dg ? O0.degf[i0[u]] : 1.f;
-        d1[u] = dg ? O1.degf[i1[u]] : 1.f;
-        load_z<GB>(v0[u], O0.g, (int64_t)i0[u] * O0.ldg + cc0);
-        load_z<GB>(v1[u], O1.g, (int64_t)i1[u] * O1.ldg + cc1);
-      }
-      if (a.mean && !dg) {
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int g0 = O0.rowptr[i0[u] + 1] - O0.rowptr[i0[u]], g1 = O1.rowptr[i1[u] + 1] - O1.rowptr[i1[u]];
-          d0[u] = 1.f / (float)(g0 > 1 ? g0 : 1);
-          d1[u] = 1.f / (float)(g1 > 1 ? g1 : 1);
-        }
-      }
       Acc<VEC> a0[1], a1[1];
-      a0[0].zero();
-      a1[0].zero();
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b0 + u < e0) a0[0].add_mul(v0[u], d0[u]);
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b1 + u < e1) a1[0].add_mul(v1[u], d1[u]);
-      int done = UB;
-      if constexpr (PRE) {
-        if (e0 - b0 > UB || e1 - b1 > UB) {  // second batch through the same registers (ids already here)
-#pragma unroll
-          for (int u = 0; u < UB; ++u) {
-            d0[u] = dg ? O0.degf[i0t[u]] : 1.f;
-            d1[u] = dg ? O1.degf[i1t[u]] : 1.f;
-            load_z<GB>(v0[u], O0.g, (int64_t)i0t[u] * O0.ldg + cc0);
-            load_z<GB>(v1[u], O1.g, (int64_t)i1t[u] * O1.ldg + cc1);
-          }
-          if (a.mean && !dg) {
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-              const int g0 = O0.rowptr[i0t[u] + 1] - O0.rowptr[i0t[u]], g1 = O1.rowptr[i1t[u] + 1] - O1.rowptr[i1t[u]];
-              d0[u] = 1.f / (float)(g0 > 1 ? g0 : 1);
-              d1[u] = 1.f / (float)(g1 > 1 ? g1 : 1);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b0 + UB + u < e0) a0[0].add_mul(v0[u], d0[u]);
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b1 + UB + u < e1) a1[0].add_mul(v1[u], d1[u]);
-        }
-        done = 2 * UB;
-      }
-      if (e0 - b0 > done) gather_sum_w<GS, 1, VEC, GB>(a0, O0.g, O0.ldg, O0.t_col, O0.rowptr, O0.degf, a.mean, b0 + done, e0, c0, O0.F);
-      if (e1 - b1 > done) gather_sum_w<GS, 1, VEC, GB>(a1, O1.g, O1.ldg, O1.t_col, O1.rowptr, O1.degf, a.mean, b1 + done, e1, c0, O1.F);
-      if (c0 < O0.F) store_z<DZB>(a0[0], S.dz, (int64_t)row * S.lddz + O0.coff + c0);
-      if (has2 && c0 < O1.F) store_z<DZB>(a1[0], S.dz, (int64_t)row * S.lddz + O1.coff + c0);
+      gather_pair<GS, GB>(GatherSide{O0.g, O0.ldg, O0.t_col, b0, e0, O0.F}, GatherSide{O1.g, O1.ldg, O1.t_col, b1, e1, O1.F},
+                          MeanW{O0.rowptr, O0.degf, a.mean}, MeanW{O1.rowptr, O1.degf, a.mean}, c0, a0, a1, false);
+      if (c0 < O0.F) put(a0[0], O0.coff, c0);
+      if (has2 && c0 < O1.F) put(a1[0], O1.coff, c0);
     }
   } else {
 #pragma unroll
@@ -728,11 +679,11 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
     Acc<VEC> acc[NV];
 #pragma unroll
     for (int q = 0; q < NV; ++q) acc[q].zero();
-    gather_sum_w<GS, NV, VEC, GB>(acc, O.g, O.ldg, O.t_col, O.rowptr, O.degf, a.mean, rb[oi], re[oi], c0, O.F);
+    gather_sum<GS, NV, VEC, GB>(acc, O.g, O.ldg, O.t_col, rb[oi], re[oi], c0, O.F, MeanW{O.rowptr, O.degf, a.mean});
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
       const int c = c0 + q * GS * VEC;
-      if (c < O.F) store_z<DZB>(acc[q], S.dz, (int64_t)row * S.lddz + O.coff + c);
+      if (c < O.F) put(acc[q], O.coff, c);
     }
   }
   }
@@ -742,8 +693,9 @@ __device__ __forceinline__ void agg_bwd_row(const TAggArgs& a, const TAggSrc& S,
       const int c = c0 + q * GS * VEC;
       if (c < S.Froot) {
         Acc<VEC> v;
-        load_z<GB>(v, S.groot, (int64_t)row * S.ldgr + c);
-        store_z<DZB>(v, S.dz, (int64_t)row * S.lddz + S.roff + c);
+        v.zero();
+        if (live) load_z<GB>(v, S.groot, (int64_t)row * S.ldgr + c);
+        put(v, S.roff, c);
       }
     }
   }
@@ -766,7 +718,8 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const TAggArgs a) {
   int row = local * rpb + threadIdx.x / GS;
   if (GS == 64) row = __builtin_amdgcn_readfirstlane(row);  // wave-uniform, see agg_fwd_kernel
   if (row >= S.n_rows) return;
-  agg_bwd_row<GS, NV, GB, DZB>(a, S, row, (int)(threadIdx.x % GS) * 4);
+  agg_bwd_row<GS, NV, GB>(a, S, row, true, (int)(threadIdx.x % GS) * 4,
+                          [&](Acc<4> v, int seg, int c) { store_z<DZB>(v, S.dz, (int64_t)row * S.lddz + seg + c); });
 }
 
 // ----- transposed aggregation of layer l FUSED with its input-gradient GEMM ------------------------------------------
@@ -774,9 +727,9 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const TAggArgs a) {
 // them in LDS ([k][row] image, LD 17) and multiplies them on the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32): one
 // kernel and one hand-off of dZ through L2 less per layer.  dZ is still written to HBM (the weight-gradient GEMM reads it).
 // Wp [ncols][ldw] is read from L2: lane (n, kq) loads Wp[kb + kq][n0 + n] (16 lanes = one 64-byte segment).
-// one 16-row tile of source entry S by one group of 256 threads, LDS image Hs [ncols][17]; see agg_proj_tile for `valid`
+// one 16-row tile [row0, row0 + 16) of source entry S, rows below row_end, by the workgroup's 256 threads; LDS image Hs [ncols][17]
 template <int GS>
-__device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc& S, int row0, int row_end, bool valid, float* Hs) {
+__device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc& S, int row0, int row_end, float* Hs) {
   constexpr int TM = 16, LDH = 17, VEC = 4;
   constexpr int RPP = 256 / GS;  // rows gathered per pass
   constexpr int NP = TM / RPP;   // passes (GS = 16: 1, 32: 2, 64: 4)
@@ -787,122 +740,20 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
   const int K = S.ncols;
   KT(8);
   constexpr int WB = 48;
-  if (valid) {
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     const int m = p * RPP + tid / GS;
     const int row = row0 + m;
     const bool live = row < row_end;
-    int rb[AGG_MAX_IN], re[AGG_MAX_IN];
+    // every piece goes to the LDS image (zeros for a row past the end), and to dz if the row exists
+    agg_bwd_row<GS, 1, false>(a, S, row, live, c0, [&](Acc<VEC> v, int seg, int c) {
+      if (live) v.store(S.dz + (int64_t)row * S.lddz + seg + c);
 #pragma unroll
-    for (int oi = 0; oi < AGG_MAX_IN; ++oi) {
-      rb[oi] = re[oi] = 0;
-      if (live && oi < S.n_out) { rb[oi] = S.out[oi].t_rowptr[row]; re[oi] = S.out[oi].t_rowptr[row + 1]; }
-    }
-    // outgoing edge types in PAIRS (see agg_row): ids of both, then 1/deg + gradient rows of both
-    constexpr int UB = 8;
-#pragma unroll
-    for (int oi = 0; oi < AGG_MAX_IN; oi += 2) {
-      if (oi >= S.n_out) break;
-      const bool has2 = oi + 1 < S.n_out;
-      const TAggOut& O0 = S.out[oi];
-      const TAggOut& O1 = S.out[has2 ? oi + 1 : oi];
-      const int b0 = rb[oi], e0 = re[oi];
-      const int b1 = has2 ? rb[oi + 1] : b0, e1 = has2 ? re[oi + 1] : b0;
-      // GS <= 16: the ids of out-edges 8..15 travel with those of 0..7 (see agg_row): one round trip less for rows of 9..16 edges
-      constexpr bool PRE = GS <= 16;
-      int i0[UB], i1[UB], i0t[PRE ? UB : 1], i1t[PRE ? UB : 1];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        i0[u] = O0.t_col[e0 > b0 ? min(b0 + u, e0 - 1) : 0];
-        i1[u] = O1.t_col[e1 > b1 ? min(b1 + u, e1 - 1) : 0];
-        if constexpr (PRE) {
-          i0t[u] = O0.t_col[e0 > b0 ? min(b0 + UB + u, e0 - 1) : 0];
-          i1t[u] = O1.t_col[e1 > b1 ? min(b1 + UB + u, e1 - 1) : 0];
-        }
-      }
-      float d0[UB], d1[UB];
-      Acc<VEC> v0[UB], v1[UB];
-      const int cc0 = c0 < O0.F ? c0 : 0, cc1 = c0 < O1.F ? c0 : 0;
-      const bool dg = a.mean && O0.degf && O1.degf;  // block-uniform
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        d0[u] = dg ? O0.degf[i0[u]] : 1.f;
-        d1[u] = dg ? O1.degf[i1[u]] : 1.f;
-        v0[u].load(O0.g + (int64_t)i0[u] * O0.ldg + cc0);
-        v1[u].load(O1.g + (int64_t)i1[u] * O1.ldg + cc1);
-      }
-      if (a.mean && !dg) {  // unit-test path without the plan's degree table
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int g0 = O0.rowptr[i0[u] + 1] - O0.rowptr[i0[u]], g1 = O1.rowptr[i1[u] + 1] - O1.rowptr[i1[u]];
-          d0[u] = 1.f / (float)(g0 > 1 ? g0 : 1);
-          d1[u] = 1.f / (float)(g1 > 1 ? g1 : 1);
-        }
-      }
-      Acc<VEC> a0[1], a1[1];
-      a0[0].zero();
-      a1[0].zero();
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b0 + u < e0) a0[0].add_mul(v0[u], d0[u]);
-#pragma unroll
-      for (int u = 0; u < UB; ++u)
-        if (b1 + u < e1) a1[0].add_mul(v1[u], d1[u]);
-      int done = UB;
-      if constexpr (PRE) {
-        if (e0 - b0 > UB || e1 - b1 > UB) {  // second batch through the same registers (ids already here)
-#pragma unroll
-          for (int u = 0; u < UB; ++u) {
-            d0[u] = dg ? O0.degf[i0t[u]] : 1.f;
-            d1[u] = dg ? O1.degf[i1t[u]] : 1.f;
-            v0[u].load(O0.g + (int64_t)i0t[u] * O0.ldg + cc0);
-            v1[u].load(O1.g + (int64_t)i1t[u] * O1.ldg + cc1);
-          }
-          if (a.mean && !dg) {
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-              const int g0 = O0.rowptr[i0t[u] + 1] - O0.rowptr[i0t[u]], g1 = O1.rowptr[i1t[u] + 1] - O1.rowptr[i1t[u]];
-              d0[u] = 1.f / (float)(g0 > 1 ? g0 : 1);
-              d1[u] = 1.f / (float)(g1 > 1 ? g1 : 1);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b0 + UB + u < e0) a0[0].add_mul(v0[u], d0[u]);
-#pragma unroll
-          for (int u = 0; u < UB; ++u)
-            if (b1 + UB + u < e1) a1[0].add_mul(v1[u], d1[u]);
-        }
-        done = 2 * UB;
-      }
-      if (e0 - b0 > done) gather_sum_w<GS, 1, VEC>(a0, O0.g, O0.ldg, O0.t_col, O0.rowptr, O0.degf, a.mean, b0 + done, e0, c0, O0.F);
-      if (e1 - b1 > done) gather_sum_w<GS, 1, VEC>(a1, O1.g, O1.ldg, O1.t_col, O1.rowptr, O1.degf, a.mean, b1 + done, e1, c0, O1.F);
-      if (c0 < O0.F) {
-        if (live) a0[0].store(S.dz + (int64_t)row * S.lddz + O0.coff + c0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Hs[(O0.coff + c0 + i) * LDH + m] = a0[0].at(i);
-      }
-      if (has2 && c0 < O1.F) {
-        if (live) a1[0].store(S.dz + (int64_t)row * S.lddz + O1.coff + c0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Hs[(O1.coff + c0 + i) * LDH + m] = a1[0].at(i);
-      }
-    }
-    if (S.groot && c0 < S.Froot) {
-      Acc<VEC> v;
-      v.zero();
-      if (live) {
-        v.load(S.groot + (int64_t)row * S.ldgr + c0);
-        v.store(S.dz + (int64_t)row * S.lddz + S.roff + c0);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Hs[(S.roff + c0 + i) * LDH + m] = v.at(i);
-    }
-  }
+      for (int i = 0; i < 4; ++i) Hs[(seg + c + i) * LDH + m] = v.at(i);
+    });
   }
   __syncthreads();
-  if (!valid || S.xw == nullptr) return;  // group-uniform
+  if (S.xw == nullptr) return;  // block-uniform
   KT(9);
   const int n_ct = (S.xN + 15) >> 4;
   for (int ct = w; ct < n_ct; ct += 4) {
@@ -965,7 +816,7 @@ __global__ __launch_bounds__(256) void agg_bwd_dx_kernel(const TAggArgs a) {
   karg_warm<10>((int)offsetof(TAggArgs, s) + si * (int)sizeof(TAggSrc), (int)sizeof(TAggSrc));
   const TAggSrc& S = a.s[si];
   const int row0 = ((int)blockIdx.x - S.block_start) * S.tile_rows;  // (tiles of 8 for entries of heavy rows: AggDst::tile_rows)
-  agg_bwd_dx_tile<GS>(a, S, row0, min(row0 + S.tile_rows, S.n_rows), true, Hs);
+  agg_bwd_dx_tile<GS>(a, S, row0, min(row0 + S.tile_rows, S.n_rows), Hs);
   KT_SPAN_END(48, si);
 }
 
@@ -1007,11 +858,10 @@ constexpr int WIN_LDS_BWD = WIN_LDS_FWD + WIN_LDS_DEG;
 static_assert(WIN_LDS_BWD <= 160 * 1024, "LDS budget");
 constexpr unsigned WIN_SKIP_OFF = 0xFFFFF000u;  // buffer offset beyond any record: the load returns 0 without touching memory
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-// raw buffer over [base, base + bytes): an out-of-range offset reads as zero (no memory access) -- lets a batch of edges issue BOTH
-// an LDS read and a global read per edge without a branch: the one that does not apply is aimed at the zero row / out of range
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t win_rsrc(const void* base, unsigned bytes) { return buf_rsrc(base, bytes); }
+// (raw buffers, buf_rsrc: an out-of-range offset reads as zero without a memory access -- lets a batch of edges issue BOTH an LDS
+// read and a global read per edge without a branch: the one that does not apply is aimed at the zero row / out of range)
 
-static_assert(AGG_MAX_IN == 6 && WG == 4, "sel_q / sel_root are written for 6 / 4 entries");
+static_assert(AGG_MAX_IN == 6, "sel_q is written for 6 entries");
 struct WinFwd {
   AggDst d;  // ONE destination entry, win_in >= 0
   int mean;
@@ -1020,7 +870,7 @@ struct WinFwd {
 };
 struct WinBwd {
   TAggSrc s;  // ONE source entry, win_out >= 0
-  int mean, dzb16;
+  int mean;
   int n_chunks, chunks_per_block;
 };
 
@@ -1029,25 +879,6 @@ __device__ __forceinline__ void widen_bf16x4(Acc<4>& a, const uint2 b) {
                     __uint_as_float(b.y & 0xffff0000u));
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint2 sel_root(const uint2 (&s)[WG], int g) {  // g wave-uniform: a scalar branch tree
-  switch (g) {
-    case 0: return s[0];
-    case 1: return s[1];
-    case 2: return s[2];
-    default: return s[3];
-  }
-}
-__device__ __forceinline__ int sel_st(const int (&s)[AGG_MAX_IN + 1], int q) {  // q wave-uniform
-  switch (q) {
-    case 0: return s[0];
-    case 1: return s[1];
-    case 2: return s[2];
-    case 3: return s[3];
-    case 4: return s[4];
-    case 5: return s[5];
-    default: return s[6];
-  }
-}
 __device__ __forceinline__ int sel_q(const int (&s)[AGG_MAX_IN], int q) {  // q wave-uniform
   switch (q) {
     case 0: return s[0];
@@ -1058,9 +889,20 @@ __device__ __forceinline__ int sel_q(const int (&s)[AGG_MAX_IN], int q) {  // q 
     default: return s[5];
   }
 }
-// Shared chunk pipeline of the forward and the transposed kernel.  `Side` supplies, per edge type q of the entry: the extent
-// array (rowptr), the id array (col), the gathered matrix (base pointer as bf16 elements, column offset, pitch) and, for the
-// transposed side, the per-row weights.
+// Shared chunk pipeline of the forward and the transposed kernel.  WinTopo<E> supplies, per edge type q of the entry, the extent
+// array (rowptr) and the id array (col); WinRing the matrix whose rows the ring holds and, for the transposed side, the per-row
+// weights staged beside them.
+struct WinLds {
+  unsigned char* ring;  // [WRING + 1] rows of WIN_ROW_BYTES (slot WRING: the all-zero row)
+  int* idbuf;           // [2][WIDCAP]
+  int* rpbuf;           // [3][AGG_MAX_IN][WRP]
+  float* wdeg;          // [WRING] weights of the ring rows (transposed kernel only)
+};
+struct WinRing {
+  const uint16_t* x;  // rows as bf16 elements (column offset included)
+  int ld;
+  const float* degf;  // per-row weights travelling with the rows, null: none
+};
 struct WinStage {  // registers holding what phase A requested for the chunks ahead
   uint4 rows[(WR * 32) / WIN_THREADS];          // 2: the WR new ring rows of chunk c + 1
   int ids[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS];  // 3: ids of chunk c + 1
@@ -1094,7 +936,7 @@ __device__ __forceinline__ int win_load_rp(const E& X, int ch, int n_chunks) {
   const int r = min(ch * WR + i, WinTopo<E>::rows(X));
   return WinTopo<E>::rowptr(X, q)[r];
 }
-// ids of chunk `ch` (extents already in LDS buffer rp) -> registers; returns the id total of the chunk through *total
+// ids of one chunk (its extents already in LDS buffer rp; live = false: no such chunk) -> registers, zeros if they exceed WIDCAP
 template <class E>
 __device__ __forceinline__ void win_load_ids(const E& X, const int* rp, bool live, int (&ids)[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS]) {
   const int nq = WinTopo<E>::n(X);
@@ -1134,12 +976,139 @@ __device__ __forceinline__ bool win_offsets(const int* rp, int nq, int (&off)[AG
   return acc <= WIDCAP;
 }
 
+// ids in registers -> one half of the LDS id buffer
+__device__ __forceinline__ void win_store_ids(int* dst, const int (&ids)[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS]) {
+#pragma unroll
+  for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
+    const int p = (int)threadIdx.x + it * WIN_THREADS;
+    if (p < WIDCAP) dst[p] = ids[it];
+  }
+}
+// prologue: extents of chunks c_begin, c_begin + 1; the zero row; the first window; ids of c_begin
+template <class E>
+__device__ __forceinline__ void win_prologue(const E& X, const WinRing& R, const WinLds& L, int c_begin, int n_chunks) {
+  const int n_rows = WinTopo<E>::rows(X), nq = WinTopo<E>::n(X);
+  const int r0 = win_load_rp(X, c_begin, n_chunks), r1 = win_load_rp(X, c_begin + 1, n_chunks);
+  if ((int)threadIdx.x < nq * WRP) {
+    L.rpbuf[(c_begin % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r0;
+    L.rpbuf[((c_begin + 1) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r1;
+  }
+  if ((int)threadIdx.x < 32) *reinterpret_cast<uint4*>(L.ring + (size_t)WRING * WIN_ROW_BYTES + threadIdx.x * 16) = make_uint4(0u, 0u, 0u, 0u);
+  // rows [lo, hi) of the first window (everything the ring will hold for chunk c_begin)
+  const int lo = max(c_begin * WR - WM, 0), hi = min(c_begin * WR + WR + WM, n_rows);
+  for (int p = threadIdx.x; p < (hi - lo) * 32; p += WIN_THREADS) {
+    const int r = lo + (p >> 5), piece = p & 31;
+    const uint4 v = *reinterpret_cast<const uint4*>(R.x + (int64_t)r * R.ld + piece * 8);
+    *reinterpret_cast<uint4*>(L.ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = v;
+  }
+  if (R.degf && (int)threadIdx.x < hi - lo) L.wdeg[(lo + threadIdx.x) & (WRING - 1)] = R.degf[lo + threadIdx.x];
+  __syncthreads();
+  int ids[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS];
+  win_load_ids(X, L.rpbuf + (c_begin % 3) * AGG_MAX_IN * WRP, true, ids);
+  win_store_ids(L.idbuf + (c_begin & 1) * WIDCAP, ids);
+  __syncthreads();
+}
+// phase A of chunk ch: request what the NEXT chunks need (lands while this chunk computes)
+template <class E>
+__device__ __forceinline__ void win_request(const E& X, const WinRing& R, const WinLds& L, int ch, int c_end, int n_chunks, WinStage& stg) {
+  const int n_rows = WinTopo<E>::rows(X);
+  const bool next = ch + 1 < c_end;
+  const int nlo = ch * WR + WR + WM;  // new ring rows of chunk ch + 1: [nlo, nlo + WR)
+#pragma unroll
+  for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
+    const int p = (int)threadIdx.x + it * WIN_THREADS;
+    const int r = nlo + (p >> 5), piece = p & 31;
+    stg.rows[it] = make_uint4(0u, 0u, 0u, 0u);
+    if (next && r < n_rows) stg.rows[it] = *reinterpret_cast<const uint4*>(R.x + (int64_t)r * R.ld + piece * 8);
+  }
+  stg.deg = 0.f;
+  if (next && R.degf && (int)threadIdx.x < WR && nlo + (int)threadIdx.x < n_rows) stg.deg = R.degf[nlo + threadIdx.x];
+  win_load_ids(X, L.rpbuf + ((ch + 1) % 3) * AGG_MAX_IN * WRP, next, stg.ids);
+  stg.rp = (ch + 2 < c_end) ? win_load_rp(X, ch + 2, n_chunks) : 0;
+}
+// phase D of chunk ch: what phase A requested goes to LDS (ring slots / buffers this chunk did not read)
+template <class E>
+__device__ __forceinline__ void win_commit(const E& X, const WinRing& R, const WinLds& L, int ch, int c_end, const WinStage& stg) {
+  if (ch + 1 >= c_end) return;
+  const int n_rows = WinTopo<E>::rows(X), nq = WinTopo<E>::n(X);
+  const int nlo = ch * WR + WR + WM;
+#pragma unroll
+  for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
+    const int p = (int)threadIdx.x + it * WIN_THREADS;
+    const int r = nlo + (p >> 5), piece = p & 31;
+    if (r < n_rows) *reinterpret_cast<uint4*>(L.ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = stg.rows[it];
+  }
+  if (R.degf && (int)threadIdx.x < WR && nlo + (int)threadIdx.x < n_rows) L.wdeg[(nlo + threadIdx.x) & (WRING - 1)] = stg.deg;
+  win_store_ids(L.idbuf + ((ch + 1) & 1) * WIDCAP, stg.ids);
+  if (ch + 2 < c_end && (int)threadIdx.x < nq * WRP) L.rpbuf[((ch + 2) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = stg.rp;
+}
+
+// The rows of one list of <= 64 edges (lane u = edge u), summed into acc.  WT = false (forward): plain adds.  WT = true
+// (transposed): every row times the weight of its edge, which lives in lane u of a register and is read by readlane -- add_mul if
+// `mean`, else a plain add.
+// Far rows (outside the window, or of a list without one): the set bits of fm, up to four in flight.
+template <bool WT>
+struct WinFar {
+  u32x2 fv[4];
+  int fu[4];
+  // request the next (up to) four set bits of fm: row of edge u at byte offset readlane(gov, u) + voff of the buffer rs
+  __device__ __forceinline__ void issue(unsigned long long& fm, __amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rs_null, int voff, int gov) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      fu[t] = fm ? __builtin_ctzll(fm) : 0;
+      fv[t] = __builtin_amdgcn_raw_buffer_load_b64(fm ? rs : rs_null, voff, __builtin_amdgcn_readlane(gov, fu[t]), 0);
+      fm &= fm - 1ull;  // (0 stays 0)
+    }
+  }
+  __device__ __forceinline__ void add(Acc<4>& acc, int mean, int wv) const {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      Acc<4> w;
+      widen_bf16x4(w, make_uint2(fv[t][0], fv[t][1]));
+      if (WT && mean) acc.add_mul(w, __int_as_float(__builtin_amdgcn_readlane(wv, fu[t]))); else acc.add(w);  // (a null read: 0 x a finite weight)
+    }
+  }
+};
+// NB in-window rows (edges u0 .. u0 + NB - 1) from the ring: LDS reads at scalar-computed slots (lane u of lov = byte offset of edge u's row)
+template <int NB, bool WT>
+__device__ __forceinline__ void win_batch(Acc<4>& acc, const unsigned char* ring, int lov, int lane, int u0, int mean, int wv) {
+  uint2 va[NB];
+#pragma unroll
+  for (int t = 0; t < NB; ++t) va[t] = *reinterpret_cast<const uint2*>(ring + __builtin_amdgcn_readlane(lov, u0 + t) + lane * 8);
+#pragma unroll
+  for (int t = 0; t < NB; ++t) {
+    Acc<4> w;
+    widen_bf16x4(w, va[t]);
+    if (WT && mean) acc.add_mul(w, __int_as_float(__builtin_amdgcn_readlane(wv, u0 + t))); else acc.add(w);
+  }
+}
+// one list: far rows requested FIRST, the in-window edges (wq: the list has a window) follow in batches of eight LDS reads, the
+// requested rows are added LAST; more than four far rows: further rounds, each waited for
+template <bool WT>
+__device__ __forceinline__ void win_sum_list(Acc<4>& acc, unsigned long long fm, bool wq, int cnt, const unsigned char* ring, int lov, int lane,
+                                             __amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rs_null, int voff, int gov, int mean, int wv_ring,
+                                             int wv_far) {
+  WinFar<WT> far;
+  const bool any_far = fm != 0ull;
+  if (any_far) far.issue(fm, rs, rs_null, voff, gov);
+  if (wq) {
+    int u0 = 0;
+    for (; cnt - u0 > 2; u0 += 8) win_batch<8, WT>(acc, ring, lov, lane, u0, mean, wv_ring);
+    if (u0 < cnt) win_batch<2, WT>(acc, ring, lov, lane, u0, mean, wv_ring);
+  }
+  if (any_far) {
+    far.add(acc, mean, wv_far);
+    while (fm) {
+      far.issue(fm, rs, rs_null, voff, gov);
+      far.add(acc, mean, wv_far);
+    }
+  }
+}
+
 template <bool HB>
 __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wlds[];
-  unsigned char* ring = wlds;
-  int* idbuf = reinterpret_cast<int*>(wlds + WIN_LDS_RING);                 // [2][WIDCAP]
-  int* rpbuf = reinterpret_cast<int*>(wlds + WIN_LDS_RING + WIN_LDS_IDS);   // [3][AGG_MAX_IN][WRP]
+  const WinLds L = {wlds, reinterpret_cast<int*>(wlds + WIN_LDS_RING), reinterpret_cast<int*>(wlds + WIN_LDS_RING + WIN_LDS_IDS), nullptr};
   const AggDst& D = a.d;
   const int n_rows = D.n_rows, nq = D.n_in;
   const int c_begin = (int)blockIdx.x * a.chunks_per_block;
@@ -1147,7 +1116,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
   if (c_begin >= c_end) return;  // block-uniform
   const int wave = uni((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
   const AggIn& IW = D.in[D.win_in];
-  const uint16_t* zwin = reinterpret_cast<const uint16_t*>(IW.z) + IW.coff;
+  const WinRing R = {reinterpret_cast<const uint16_t*>(IW.z) + IW.coff, IW.ldz, nullptr};
   const int c0 = lane * 4;
   DropCfg dcfg = D.drop;
   if (D.drop_on) dcfg = drop_resolve(D.drop);
@@ -1155,53 +1124,16 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
   biasv.zero();
   if (D.bias) biasv.load(D.bias + c0);
 
-  // ---- prologue: extents of chunks c_begin, c_begin + 1; ids of c_begin; the first window -------------------------------
-  {
-    const int r0 = win_load_rp(D, c_begin, a.n_chunks), r1 = win_load_rp(D, c_begin + 1, a.n_chunks);
-    if ((int)threadIdx.x < nq * WRP) {
-      rpbuf[(c_begin % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r0;
-      rpbuf[((c_begin + 1) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r1;
-    }
-    if ((int)threadIdx.x < 32) *reinterpret_cast<uint4*>(ring + (size_t)WRING * WIN_ROW_BYTES + threadIdx.x * 16) = make_uint4(0u, 0u, 0u, 0u);
-    // rows [lo, hi) of the first window (everything the ring will hold for chunk c_begin)
-    const int lo = max(c_begin * WR - WM, 0), hi = min(c_begin * WR + WR + WM, n_rows);
-    for (int p = threadIdx.x; p < (hi - lo) * 32; p += WIN_THREADS) {
-      const int r = lo + (p >> 5), piece = p & 31;
-      const uint4 v = *reinterpret_cast<const uint4*>(zwin + (int64_t)r * IW.ldz + piece * 8);
-      *reinterpret_cast<uint4*>(ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = v;
-    }
-    __syncthreads();
-    int ids[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS];
-    win_load_ids(D, rpbuf + (c_begin % 3) * AGG_MAX_IN * WRP, true, ids);
-#pragma unroll
-    for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-      const int p = (int)threadIdx.x + it * WIN_THREADS;
-      if (p < WIDCAP) idbuf[(c_begin & 1) * WIDCAP + p] = ids[it];
-    }
-    __syncthreads();
-  }
+  win_prologue(D, R, L, c_begin, a.n_chunks);
 
   for (int i = 20; i < 31; ++i) KT_ZERO(i);
   for (int ch = c_begin; ch < c_end; ++ch) {
     const int r_c = ch * WR;
-    const int* rp = rpbuf + (ch % 3) * AGG_MAX_IN * WRP;
-    const int* idc = idbuf + (ch & 1) * WIDCAP;
+    const int* rp = L.rpbuf + (ch % 3) * AGG_MAX_IN * WRP;
+    const int* idc = L.idbuf + (ch & 1) * WIDCAP;
     [[maybe_unused]] const unsigned long long kt_a = KT_NOW();
-    // ---- phase A: request what the NEXT chunks need (lands while this chunk computes) ------------------------------------
     WinStage stg;
-    const bool next = ch + 1 < c_end;
-    {
-      const int nlo = r_c + WR + WM;  // new ring rows of chunk ch + 1: [nlo, nlo + WR)
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        stg.rows[it] = make_uint4(0u, 0u, 0u, 0u);
-        if (next && r < n_rows) stg.rows[it] = *reinterpret_cast<const uint4*>(zwin + (int64_t)r * IW.ldz + piece * 8);
-      }
-      win_load_ids(D, rpbuf + ((ch + 1) % 3) * AGG_MAX_IN * WRP, next, stg.ids);
-      stg.rp = (ch + 2 < c_end) ? win_load_rp(D, ch + 2, a.n_chunks) : 0;
-    }
+    win_request(D, R, L, ch, c_end, a.n_chunks, stg);
     KT_ADD(20, kt_a);
     [[maybe_unused]] const unsigned long long kt_c = KT_NOW();
     // ---- this chunk ----------------------------------------------------------------------------------------------------------
@@ -1261,8 +1193,8 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
             cntD = eD - bD;
             const AggIn& I = D.in[DQ];
             const uint16_t* zq = reinterpret_cast<const uint16_t*>(I.z) + I.coff;
-            const __amdgpu_buffer_rsrc_t rs = win_rsrc(zq, (unsigned)I.n_src * (unsigned)(I.ldz * 2) - (unsigned)(I.coff * 2));
-            const __amdgpu_buffer_rsrc_t rs_null = win_rsrc(zq, 0u);
+            const __amdgpu_buffer_rsrc_t rs = buf_rsrc(zq, (unsigned)I.n_src * (unsigned)(I.ldz * 2) - (unsigned)(I.coff * 2));
+            const __amdgpu_buffer_rsrc_t rs_null = buf_rsrc(zq, 0u);
             const int gov = lane < cntD ? idd * (I.ldz * 2) : 0;
             vd[0] = __builtin_amdgcn_raw_buffer_load_b64(rs, lane * 8, __builtin_amdgcn_readlane(gov, 0), 0);
             vd[1] = __builtin_amdgcn_raw_buffer_load_b64(cntD > 1 ? rs : rs_null, lane * 8, __builtin_amdgcn_readlane(gov, 1), 0);
@@ -1290,8 +1222,8 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
           if (e == b) continue;
           const uint16_t* zq = reinterpret_cast<const uint16_t*>(I.z) + I.coff;
           const int ldq = I.ldz;
-          const __amdgpu_buffer_rsrc_t rs = win_rsrc(zq, (unsigned)I.n_src * (unsigned)(ldq * 2) - (unsigned)(I.coff * 2));
-          const __amdgpu_buffer_rsrc_t rs_null = win_rsrc(zq, 0u);
+          const __amdgpu_buffer_rsrc_t rs = buf_rsrc(zq, (unsigned)I.n_src * (unsigned)(ldq * 2) - (unsigned)(I.coff * 2));
+          const __amdgpu_buffer_rsrc_t rs_null = buf_rsrc(zq, 0u);
           const int offq = fits ? sel_q(off, q) + (b - sel_q(eb, q)) : 0;
           const bool wq = fits && q == WQ;
           Acc<4> acc;
@@ -1309,64 +1241,13 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
             const bool inw = lane < cnt && wq && idv >= wlo && idv < whi;
             const int lov = inw ? (idv & (WRING - 1)) * WIN_ROW_BYTES : WRING * WIN_ROW_BYTES;
             const int gov = idv * (ldq * 2);
-            unsigned long long fm = __ballot(lane < cnt && !inw) & (a.dbg ? 0ull : ~0ull);  // (dbg: measurement only -- no global reads)
-            u32x2 fv[4];
-            auto far_issue = [&]() {  // the next (up to) four set bits of fm
-#pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const int u = fm ? __builtin_ctzll(fm) : 0;
-                fv[t] = __builtin_amdgcn_raw_buffer_load_b64(fm ? rs : rs_null, lane * 8, __builtin_amdgcn_readlane(gov, u), 0);
-                fm &= fm - 1ull;  // (0 stays 0)
-              }
-            };
-            auto far_add = [&]() {
-#pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                Acc<4> w;
-                widen_bf16x4(w, make_uint2(fv[t][0], fv[t][1]));
-                acc.add(w);
-              }
-            };
-            const bool any_far = fm != 0ull;
-            if (any_far) far_issue();
-            if (wq) {
-              auto batch = [&](int u0, auto nb) {
-                constexpr int NB = decltype(nb)::value;
-                uint2 va[NB];
-#pragma unroll
-                for (int t = 0; t < NB; ++t) va[t] = *reinterpret_cast<const uint2*>(ring + __builtin_amdgcn_readlane(lov, u0 + t) + lane * 8);
-#pragma unroll
-                for (int t = 0; t < NB; ++t) {
-                  Acc<4> w;
-                  widen_bf16x4(w, va[t]);
-                  acc.add(w);
-                }
-              };
-              int u0 = 0;
-              for (; cnt - u0 > 2; u0 += 8) batch(u0, std::integral_constant<int, 8>());
-              if (u0 < cnt) batch(u0, std::integral_constant<int, 2>());
-            }
-            if (any_far) {
-              far_add();
-              while (fm) {  // more than four: further rounds, each waited for
-                far_issue();
-                far_add();
-              }
-            }
+            const unsigned long long fm = __ballot(lane < cnt && !inw) & (a.dbg ? 0ull : ~0ull);  // (dbg: measurement only -- no global reads)
+            win_sum_list<false>(acc, fm, wq, cnt, L.ring, lov, lane, rs, rs_null, lane * 8, gov, 0, 0, 0);
           }
           tot.add_div(acc, a.mean ? (float)(e - b) : 1.f);
         }
         KT_ADD(29, kt_r);
-        bool keep[4] = {true, true, true, true};
-        if (D.drop_on) drop_keep4(dcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(c0 >> 2), keep);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {  // as agg_row's epilogue
-          float v = tot.at(i);
-          if (D.act == HMP_ACT_RELU) v = v > 0.f ? v : 0.f;
-          else if (D.act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-          if (D.drop_on) v = keep[i] ? (v * D.drop.scale + 0.0f) : -0.0f;
-          tot.at(i) = v;
-        }
+        act_drop4(D, dcfg, row, c0, tot);
         store_z<HB>(tot, D.out, (int64_t)row * D.ldo + c0);
         KT_ADD(30, kt_r);
         idw = idw_n;
@@ -1376,22 +1257,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
     }
     KT_ADD(21, kt_c);
     [[maybe_unused]] const unsigned long long kt_d = KT_NOW();
-    // ---- phase D: what phase A requested goes to LDS (ring slots / buffers this chunk did not read) -------------------------
-    if (next) {
-      const int nlo = r_c + WR + WM;
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        if (r < n_rows) *reinterpret_cast<uint4*>(ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = stg.rows[it];
-      }
-#pragma unroll
-      for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        if (p < WIDCAP) idbuf[((ch + 1) & 1) * WIDCAP + p] = stg.ids[it];
-      }
-      if (ch + 2 < c_end && (int)threadIdx.x < nq * WRP) rpbuf[((ch + 2) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = stg.rp;
-    }
+    win_commit(D, R, L, ch, c_end, stg);
     KT_ADD(22, kt_d);
     [[maybe_unused]] const unsigned long long kt_b = KT_NOW();
     __syncthreads();
@@ -1405,10 +1271,8 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
 template <bool DZB>
 __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wlds[];
-  unsigned char* ring = wlds;
-  int* idbuf = reinterpret_cast<int*>(wlds + WIN_LDS_RING);
-  int* rpbuf = reinterpret_cast<int*>(wlds + WIN_LDS_RING + WIN_LDS_IDS);
-  float* wdeg = reinterpret_cast<float*>(wlds + WIN_LDS_FWD);
+  const WinLds L = {wlds, reinterpret_cast<int*>(wlds + WIN_LDS_RING), reinterpret_cast<int*>(wlds + WIN_LDS_RING + WIN_LDS_IDS),
+                    reinterpret_cast<float*>(wlds + WIN_LDS_FWD)};
   const TAggSrc& S = a.s;
   const int n_rows = S.n_rows, nq = S.n_out;
   const int c_begin = (int)blockIdx.x * a.chunks_per_block;
@@ -1416,53 +1280,16 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
   if (c_begin >= c_end) return;
   const int wave = uni((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
   const TAggOut& OW = S.out[S.win_out];
-  const uint16_t* gwin = reinterpret_cast<const uint16_t*>(OW.g);
-  const bool wdg = a.mean && OW.degf != nullptr;
+  // (the weights of the ring rows are staged beside them when the plan's table is there)
+  const WinRing R = {reinterpret_cast<const uint16_t*>(OW.g), OW.ldg, a.mean ? OW.degf : nullptr};
   const int c0 = lane * 4;
-  {
-    const int r0 = win_load_rp(S, c_begin, a.n_chunks), r1 = win_load_rp(S, c_begin + 1, a.n_chunks);
-    if ((int)threadIdx.x < nq * WRP) {
-      rpbuf[(c_begin % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r0;
-      rpbuf[((c_begin + 1) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = r1;
-    }
-    if ((int)threadIdx.x < 32) *reinterpret_cast<uint4*>(ring + (size_t)WRING * WIN_ROW_BYTES + threadIdx.x * 16) = make_uint4(0u, 0u, 0u, 0u);
-    const int lo = max(c_begin * WR - WM, 0), hi = min(c_begin * WR + WR + WM, n_rows);
-    for (int p = threadIdx.x; p < (hi - lo) * 32; p += WIN_THREADS) {
-      const int r = lo + (p >> 5), piece = p & 31;
-      const uint4 v = *reinterpret_cast<const uint4*>(gwin + (int64_t)r * OW.ldg + piece * 8);
-      *reinterpret_cast<uint4*>(ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = v;
-    }
-    if (wdg && (int)threadIdx.x < hi - lo) wdeg[(lo + threadIdx.x) & (WRING - 1)] = OW.degf[lo + threadIdx.x];
-    __syncthreads();
-    int ids[(WIDCAP + WIN_THREADS - 1) / WIN_THREADS];
-    win_load_ids(S, rpbuf + (c_begin % 3) * AGG_MAX_IN * WRP, true, ids);
-#pragma unroll
-    for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-      const int p = (int)threadIdx.x + it * WIN_THREADS;
-      if (p < WIDCAP) idbuf[(c_begin & 1) * WIDCAP + p] = ids[it];
-    }
-    __syncthreads();
-  }
+  win_prologue(S, R, L, c_begin, a.n_chunks);
   for (int ch = c_begin; ch < c_end; ++ch) {
     const int r_c = ch * WR;
-    const int* rp = rpbuf + (ch % 3) * AGG_MAX_IN * WRP;
-    const int* idc = idbuf + (ch & 1) * WIDCAP;
+    const int* rp = L.rpbuf + (ch % 3) * AGG_MAX_IN * WRP;
+    const int* idc = L.idbuf + (ch & 1) * WIDCAP;
     WinStage stg;
-    const bool next = ch + 1 < c_end;
-    {
-      const int nlo = r_c + WR + WM;
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        stg.rows[it] = make_uint4(0u, 0u, 0u, 0u);
-        if (next && r < n_rows) stg.rows[it] = *reinterpret_cast<const uint4*>(gwin + (int64_t)r * OW.ldg + piece * 8);
-      }
-      stg.deg = 0.f;
-      if (next && wdg && (int)threadIdx.x < WR && nlo + (int)threadIdx.x < n_rows) stg.deg = OW.degf[nlo + threadIdx.x];
-      win_load_ids(S, rpbuf + ((ch + 1) % 3) * AGG_MAX_IN * WRP, next, stg.ids);
-      stg.rp = (ch + 2 < c_end) ? win_load_rp(S, ch + 2, a.n_chunks) : 0;
-    }
+    win_request(S, R, L, ch, c_end, a.n_chunks, stg);
     int off[AGG_MAX_IN], eb[AGG_MAX_IN];
     const bool fits = win_offsets(rp, nq, off, eb);
     const int wlo = max(r_c - WM, 0), whi = min(r_c + WR + WM, n_rows);
@@ -1480,8 +1307,8 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
         const bool dg = a.mean && O.degf != nullptr;
         const uint16_t* gq = reinterpret_cast<const uint16_t*>(O.g);
         const int ldq = O.ldg;
-        const __amdgpu_buffer_rsrc_t rs = win_rsrc(gq, (unsigned)O.n_dst * (unsigned)(ldq * 2));
-        const __amdgpu_buffer_rsrc_t rs_null = win_rsrc(gq, 0u);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(gq, (unsigned)O.n_dst * (unsigned)(ldq * 2));
+        const __amdgpu_buffer_rsrc_t rs_null = buf_rsrc(gq, 0u);
         const int offq = fits ? sel_q(off, q) + (b - sel_q(eb, q)) : 0;
         const bool wq = fits && q == S.win_out;
         Acc<4> acc;
@@ -1497,7 +1324,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
           float dvl = 1.f, dvg = 1.f;
           if (a.mean) {
             if (dg) {
-              if (inw) dvl = wdeg[idv & (WRING - 1)];
+              if (inw) dvl = L.wdeg[idv & (WRING - 1)];
               if (farl) dvg = O.degf[idv];
             } else if (lane < cnt) {
               const int g0 = O.rowptr[idv + 1] - O.rowptr[idv];
@@ -1507,51 +1334,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
           const int dvli = __float_as_int(dvl), dvgi = __float_as_int(dvg);
           const int lov = inw ? (idv & (WRING - 1)) * WIN_ROW_BYTES : WRING * WIN_ROW_BYTES;  // see agg_fwd_win_kernel
           const int gov = idv * (ldq * 2);
-          unsigned long long fm = __ballot(farl);
-          u32x2 fv[4];
-          int fu[4];
-          auto far_issue = [&]() {  // the next (up to) four set bits of fm
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              fu[t] = fm ? __builtin_ctzll(fm) : 0;
-              fv[t] = __builtin_amdgcn_raw_buffer_load_b64(fm ? rs : rs_null, cc * 2, __builtin_amdgcn_readlane(gov, fu[t]), 0);
-              fm &= fm - 1ull;  // (0 stays 0)
-            }
-          };
-          auto far_add = [&]() {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              Acc<4> w;
-              widen_bf16x4(w, make_uint2(fv[t][0], fv[t][1]));
-              if (a.mean) acc.add_mul(w, __int_as_float(__builtin_amdgcn_readlane(dvgi, fu[t]))); else acc.add(w);  // (a null read: 0 x a finite weight)
-            }
-          };
-          const bool any_far = fm != 0ull;
-          if (any_far) far_issue();
-          if (wq) {
-            auto batch = [&](int u0, auto nb) {
-              constexpr int NB = decltype(nb)::value;
-              uint2 va[NB];
-#pragma unroll
-              for (int t = 0; t < NB; ++t) va[t] = *reinterpret_cast<const uint2*>(ring + __builtin_amdgcn_readlane(lov, u0 + t) + lane * 8);
-#pragma unroll
-              for (int t = 0; t < NB; ++t) {
-                Acc<4> w;
-                widen_bf16x4(w, va[t]);
-                if (a.mean) acc.add_mul(w, __int_as_float(__builtin_amdgcn_readlane(dvli, u0 + t))); else acc.add(w);
-              }
-            };
-            int u0 = 0;
-            for (; cnt - u0 > 2; u0 += 8) batch(u0, std::integral_constant<int, 8>());
-            if (u0 < cnt) batch(u0, std::integral_constant<int, 2>());
-          }
-          if (any_far) {
-            far_add();
-            while (fm) {  // more than four: further rounds, each waited for
-              far_issue();
-              far_add();
-            }
-          }
+          win_sum_list<true>(acc, __ballot(farl), wq, cnt, L.ring, lov, lane, rs, rs_null, cc * 2, gov, a.mean, dvli, dvgi);
         }
         if (cin) store_z<DZB>(acc, S.dz, (int64_t)row * S.lddz + O.coff + c0);
       }
@@ -1561,22 +1344,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_bwd_win_kernel(const WinBwd a
         store_z<DZB>(v, S.dz, (int64_t)row * S.lddz + S.roff + c0);
       }
     }
-    if (next) {
-      const int nlo = r_c + WR + WM;
-#pragma unroll
-      for (int it = 0; it < (WR * 32) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        const int r = nlo + (p >> 5), piece = p & 31;
-        if (r < n_rows) *reinterpret_cast<uint4*>(ring + (size_t)(r & (WRING - 1)) * WIN_ROW_BYTES + piece * 16) = stg.rows[it];
-      }
-      if (wdg && (int)threadIdx.x < WR && nlo + (int)threadIdx.x < n_rows) wdeg[(nlo + threadIdx.x) & (WRING - 1)] = stg.deg;
-#pragma unroll
-      for (int it = 0; it < (WIDCAP + WIN_THREADS - 1) / WIN_THREADS; ++it) {
-        const int p = (int)threadIdx.x + it * WIN_THREADS;
-        if (p < WIDCAP) idbuf[((ch + 1) & 1) * WIDCAP + p] = stg.ids[it];
-      }
-      if (ch + 2 < c_end && (int)threadIdx.x < nq * WRP) rpbuf[((ch + 2) % 3) * AGG_MAX_IN * WRP + threadIdx.x] = stg.rp;
-    }
+    win_commit(S, R, L, ch, c_end, stg);
     __syncthreads();
   }
 }
@@ -1646,15 +1414,103 @@ static int agg_win_out(const TAggSrc& S) {
 }
 
 constexpr int AGG_SMALL_TILES = 224;  // 16-row tiles of a launch up to which heavy entries are cut into tiles of 8 (AggDst::tile_rows)
+// the entries of either argument block (they differ in the member name only)
+static inline AggDst* agg_entries(AggArgs& a) { return a.d; }
+static inline TAggSrc* agg_entries(TAggArgs& a) { return a.s; }
 // the compact copy of the entries' first blocks that the kernels search (AggArgs::bstart)
-static inline void sync_bstart(AggArgs& a) {
-  for (int i = 0; i < a.n; ++i) a.bstart[i] = a.d[i].block_start;
+template <class Args>
+static inline void sync_bstart(Args& a) {
+  for (int i = 0; i < a.n; ++i) a.bstart[i] = agg_entries(a)[i].block_start;
 }
-static inline void sync_bstart(TAggArgs& a) {
-  for (int i = 0; i < a.n; ++i) a.bstart[i] = a.s[i].block_start;
+// Block layout of a row-group launch (agg_fwd_kernel / agg_bwd_kernel): an entry owns ceil(n_rows / rpb) blocks, rpb = 256 / gs rows
+// or 8 for an entry of heavy rows (tile_rows == 8).  xcd: every entry starts at a multiple of 8 and owns whole groups of 8 blocks.
+template <class Args>
+static int agg_layout_rows(Args& a, int gs) {
+  int blocks = 0;
+  for (int i = 0; i < a.n; ++i) {
+    auto& X = agg_entries(a)[i];
+    X.block_start = blocks;
+    const int nb = cdiv(X.n_rows, (X.tile_rows == 8 && 256 / gs > 8) ? 8 : 256 / gs);
+    blocks += a.xcd ? ((nb + 7) & ~7) : nb;
+  }
+  a.total_blocks = blocks;
+  return blocks;
 }
+// Tile layout of a fused launch (agg_proj_fwd_kernel / agg_bwd_dx_kernel): one block per tile of 16 rows; tiles of 8 rows for heavy
+// entries only while the launch leaves CUs idle (more workgroups in a launch of several rounds only add rounds)
+template <class Args>
+static int agg_layout_tiles(Args& a) {
+  int tiles16 = 0, blocks = 0;
+  for (int i = 0; i < a.n; ++i) tiles16 += cdiv(agg_entries(a)[i].n_rows, 16);
+  const bool small_launch = tiles16 <= AGG_SMALL_TILES;
+  for (int i = 0; i < a.n; ++i) {
+    auto& X = agg_entries(a)[i];
+    if (X.tile_rows != 8 || !small_launch) X.tile_rows = 16;
+    X.block_start = blocks;
+    blocks += cdiv(X.n_rows, X.tile_rows);
+  }
+  a.total_blocks = blocks;
+  return blocks;
+}
+static int agg_tile_gs(int Fmax) {  // row group of the fused kernels: 16, 32 or 64 lanes
+  int gs = 16;
+  while (gs < 64 && gs * 4 < Fmax) gs <<= 1;
+  return gs;
+}
+
+static void win_fill(WinFwd& w, const AggDst& D) {
+  w.d = D;
+  w.d.win_in = agg_win_in(D);
+#ifdef HMP_KTIME  // measurement-only switch (wrong results): profiling build only
+  const char* dv = getenv("HMP_WIN_DBG");
+  w.dbg = dv ? atoi(dv) : 0;
+#endif
+}
+static void win_fill(WinBwd& w, const TAggSrc& S) {
+  w.s = S;
+  w.s.win_out = agg_win_out(S);
+}
+// bf16 launches: entries with a same-type edge type over >= 16384 rows go to the sliding-window kernel (one launch each, in entry
+// order, persistent grid of one workgroup per CU); the others stay in `a` for the plain launch.  *any: at least one entry went.
+template <class Args>
+static int agg_win_peel(Args& a, hipStream_t st, bool* any) {
+  constexpr bool FWD = std::is_same<Args, AggArgs>::value;
+  using Win = typename std::conditional<FWD, WinFwd, WinBwd>::type;
+  constexpr int LDS = FWD ? WIN_LDS_FWD : WIN_LDS_BWD;
+  void (*k16)(const Win), (*k32)(const Win);  // output written as bf16 / fp32
+  bool out16;
+  if constexpr (FWD) { k16 = &agg_fwd_win_kernel<true>; k32 = &agg_fwd_win_kernel<false>; out16 = a.hb16; }
+  else { k16 = &agg_bwd_win_kernel<true>; k32 = &agg_bwd_win_kernel<false>; out16 = a.dzb16; }
+  Args rest = a;
+  rest.n = 0;
+  *any = false;
+  for (int i = 0; i < a.n; ++i) {
+    const auto& X = agg_entries(a)[i];
+    Win w;
+    memset(&w, 0, sizeof(w));
+    win_fill(w, X);
+    bool win;
+    if constexpr (FWD) win = w.d.win_in >= 0; else win = w.s.win_out >= 0;
+    if (!win) { agg_entries(rest)[rest.n++] = X; continue; }
+    static bool attr_done = false;
+    if (!attr_done) {
+      HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k32), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+      attr_done = true;
+    }
+    w.mean = a.mean;
+    w.n_chunks = cdiv(X.n_rows, WR);
+    const int grid = agg_win_grid(w.n_chunks, w.chunks_per_block);
+    hipLaunchKernelGGL(out16 ? k16 : k32, dim3(grid), dim3(WIN_THREADS), LDS, st, w);
+    HMP_LAUNCH_CHECK();
+    *any = true;
+  }
+  if (*any) a = rest;
+  return HMP_OK;
+}
+
 int agg_fwd_launch(AggArgs& a, hipStream_t st) {
-  int Fmax = 0, blocks = 0;
+  int Fmax = 0;
   const int vec = 4;
   for (int i = 0; i < a.n; ++i) Fmax = a.d[i].F > Fmax ? a.d[i].F : Fmax;
   if (a.n == 0 || Fmax == 0) return HMP_OK;
@@ -1666,59 +1522,18 @@ int agg_fwd_launch(AggArgs& a, hipStream_t st) {
   for (int i = 0; i < a.n; ++i) {
     AggDst& D = a.d[i];
     HMP_CHECK_ARG((D.ldo & 3) == 0 && (D.F & 3) == 0, "agg_fwd: widths must be padded to 4");
-    D.block_start = blocks;
     if (a.xcd || a.zb16 || rows_total > 16 * AGG_SMALL_TILES) D.tile_rows = 0;  // (tiles of 8 rows are a small-launch device)
-    const int nb = cdiv(D.n_rows, (D.tile_rows == 8 && 256 / gs > 8) ? 8 : 256 / gs);
-    blocks += a.xcd ? ((nb + 7) & ~7) : nb;  // xcd: every entry starts at a multiple of 8 and owns whole groups of 8 blocks
   }
-  a.total_blocks = blocks;
+  int blocks = agg_layout_rows(a, gs);
   if (blocks == 0) return HMP_OK;
   if (a.zb16) {  // bf16 projected rows: only the one-wavefront-per-row shape reads them
     HMP_CHECK_ARG(gs == 64 && nv == 1, "agg_fwd: bf16 projected rows need row widths in (128, 256], got %d", Fmax);
     if (agg_win_enabled()) {
-      // entries with a same-type edge type over >= 16384 rows go to the sliding-window kernel (one launch each, persistent
-      // grid of one workgroup per CU); the others stay in the plain launch below
-      AggArgs rest = a;
-      rest.n = 0;
-      bool any = false;
-      for (int i = 0; i < a.n; ++i) {
-        const int wi = agg_win_in(a.d[i]);
-        if (wi < 0) { rest.d[rest.n++] = a.d[i]; continue; }
-        static bool attr_done = false;
-        if (!attr_done) {
-          HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_fwd_win_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WIN_LDS_FWD));
-          HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_fwd_win_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WIN_LDS_FWD));
-          attr_done = true;
-        }
-        WinFwd w;
-        memset(&w, 0, sizeof(w));
-        w.d = a.d[i];
-        w.d.win_in = wi;
-        w.mean = a.mean;
-        w.n_chunks = cdiv(w.d.n_rows, WR);
-        w.dbg = 0;
-#ifdef HMP_KTIME  // measurement-only switch (wrong results): profiling build only
-        {
-          const char* dv = getenv("HMP_WIN_DBG");
-          w.dbg = dv ? atoi(dv) : 0;
-        }
-#endif
-        const int grid = agg_win_grid(w.n_chunks, w.chunks_per_block);
-        if (a.hb16) hipLaunchKernelGGL((agg_fwd_win_kernel<true>), dim3(grid), dim3(WIN_THREADS), WIN_LDS_FWD, st, w);
-        else hipLaunchKernelGGL((agg_fwd_win_kernel<false>), dim3(grid), dim3(WIN_THREADS), WIN_LDS_FWD, st, w);
-        HMP_LAUNCH_CHECK();
-        any = true;
-      }
+      bool any;
+      HMP_TRY(agg_win_peel(a, st, &any));
       if (any) {
-        if (rest.n == 0) return HMP_OK;
-        a = rest;
-        blocks = 0;
-        for (int i = 0; i < a.n; ++i) {
-          a.d[i].block_start = blocks;
-          const int nb = cdiv(a.d[i].n_rows, 256 / gs);
-          blocks += a.xcd ? ((nb + 7) & ~7) : nb;
-        }
-        a.total_blocks = blocks;
+        if (a.n == 0) return HMP_OK;
+        blocks = agg_layout_rows(a, gs);
       }
     }
     sync_bstart(a);
@@ -1737,30 +1552,21 @@ int agg_fwd_launch(AggArgs& a, hipStream_t st) {
 }
 
 int agg_proj_fwd_launch(AggArgs& a, hipStream_t st) {
-  int Fmax = 0, blocks = 0;
+  int Fmax = 0;
   for (int i = 0; i < a.n; ++i) Fmax = a.d[i].F > Fmax ? a.d[i].F : Fmax;
-  // tiles of 8 rows for heavy entries only while the launch leaves CUs idle (more workgroups in a launch of several rounds only add rounds)
-  int tiles16 = 0;
-  for (int i = 0; i < a.n; ++i) tiles16 += cdiv(a.d[i].n_rows, 16);
-  const bool small_launch = tiles16 <= AGG_SMALL_TILES;
   if (a.n == 0 || Fmax == 0) return HMP_OK;
   HMP_CHECK_ARG(Fmax <= 256, "agg_proj_fwd: row width %d > 256", Fmax);
-  int gs = 16;
-  while (gs < 64 && gs * 4 < Fmax) gs <<= 1;
   for (int i = 0; i < a.n; ++i) {
-    AggDst& D = a.d[i];
+    const AggDst& D = a.d[i];
     HMP_CHECK_ARG((D.ldo & 3) == 0 && (D.F & 3) == 0, "agg_proj_fwd: widths must be padded to 4");
     if (D.pw)
       HMP_CHECK_ARG((D.pK & 15) == 0 && D.pK <= 256 && D.pK <= D.F && (D.pldw & 3) == 0 && D.pncols > 0,
                     "agg_proj_fwd: projection K %d / ld %d not supported", D.pK, D.pldw);
-    if (D.tile_rows != 8 || !small_launch) D.tile_rows = 16;
-    D.block_start = blocks;
-    blocks += cdiv(D.n_rows, D.tile_rows);
   }
-  a.total_blocks = blocks;
+  const int blocks = agg_layout_tiles(a);
   if (blocks == 0) return HMP_OK;
   sync_bstart(a);
-  switch (gs) {
+  switch (agg_tile_gs(Fmax)) {
     case 16: hipLaunchKernelGGL((agg_proj_fwd_kernel<16>), dim3(blocks), dim3(256), 0, st, a); break;
     case 32: hipLaunchKernelGGL((agg_proj_fwd_kernel<32>), dim3(blocks), dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL((agg_proj_fwd_kernel<64>), dim3(blocks), dim3(256), 0, st, a); break;
@@ -1769,13 +1575,19 @@ int agg_proj_fwd_launch(AggArgs& a, hipStream_t st) {
   return HMP_OK;
 }
 
-int agg_bwd_launch(TAggArgs& a, hipStream_t st) {
-  int Fmax = 0, blocks = 0;
-  const int vec = 4;
+// widest segment or root width of a transposed launch
+static int tagg_fmax(const TAggArgs& a) {
+  int Fmax = 0;
   for (int i = 0; i < a.n; ++i) {
     for (int o = 0; o < a.s[i].n_out; ++o) Fmax = a.s[i].out[o].F > Fmax ? a.s[i].out[o].F : Fmax;
     if (a.s[i].groot) Fmax = a.s[i].Froot > Fmax ? a.s[i].Froot : Fmax;
   }
+  return Fmax;
+}
+
+int agg_bwd_launch(TAggArgs& a, hipStream_t st) {
+  const int vec = 4;
+  int Fmax = tagg_fmax(a);
   if (a.n == 0 || Fmax == 0) {
     if (!a.fin_row_lv) return HMP_OK;
     Fmax = 4;  // nothing to gather, but the loss still has to be finalised
@@ -1785,55 +1597,21 @@ int agg_bwd_launch(TAggArgs& a, hipStream_t st) {
   int64_t rows_total = 0;
   for (int i = 0; i < a.n; ++i) rows_total += a.s[i].n_rows;
   a.xcd = (rows_total >= AGG_XCD_ROWS && agg_xcd_enabled()) ? 1 : 0;
-  for (int i = 0; i < a.n; ++i) {
-    a.s[i].block_start = blocks;
+  for (int i = 0; i < a.n; ++i)
     if (a.xcd || a.gb16 || rows_total > 16 * AGG_SMALL_TILES) a.s[i].tile_rows = 0;  // (tiles of 8 rows are a small-launch device)
-    const int nb = cdiv(a.s[i].n_rows, (a.s[i].tile_rows == 8 && 256 / gs > 8) ? 8 : 256 / gs);
-    blocks += a.xcd ? ((nb + 7) & ~7) : nb;
-  }
-  a.total_blocks = blocks;
+  int blocks = agg_layout_rows(a, gs);
   if (blocks == 0 && !a.fin_row_lv) return HMP_OK;
-  int grid = blocks + (a.fin_row_lv ? 1 : 0);
   if (a.gb16) {  // bf16 gradient rows: only the one-wavefront-per-row shape reads them
     HMP_CHECK_ARG(gs == 64 && nv == 1, "agg_bwd: bf16 gradient rows need row widths in (128, 256], got %d", Fmax);
     if (agg_win_enabled()) {
-      TAggArgs rest = a;
-      rest.n = 0;
-      bool any = false;
-      for (int i = 0; i < a.n; ++i) {
-        const int wo = agg_win_out(a.s[i]);
-        if (wo < 0) { rest.s[rest.n++] = a.s[i]; continue; }
-        static bool attr_done = false;
-        if (!attr_done) {
-          HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_bwd_win_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, WIN_LDS_BWD));
-          HMP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&agg_bwd_win_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, WIN_LDS_BWD));
-          attr_done = true;
-        }
-        WinBwd w;
-        memset(&w, 0, sizeof(w));
-        w.s = a.s[i];
-        w.s.win_out = wo;
-        w.mean = a.mean;
-        w.n_chunks = cdiv(w.s.n_rows, WR);
-        const int wgrid = agg_win_grid(w.n_chunks, w.chunks_per_block);
-        if (a.dzb16) hipLaunchKernelGGL((agg_bwd_win_kernel<true>), dim3(wgrid), dim3(WIN_THREADS), WIN_LDS_BWD, st, w);
-        else hipLaunchKernelGGL((agg_bwd_win_kernel<false>), dim3(wgrid), dim3(WIN_THREADS), WIN_LDS_BWD, st, w);
-        HMP_LAUNCH_CHECK();
-        any = true;
-      }
+      bool any;
+      HMP_TRY(agg_win_peel(a, st, &any));
       if (any) {
-        a = rest;
-        blocks = 0;
-        for (int i = 0; i < a.n; ++i) {
-          a.s[i].block_start = blocks;
-          const int nb = cdiv(a.s[i].n_rows, 256 / gs);
-          blocks += a.xcd ? ((nb + 7) & ~7) : nb;
-        }
-        a.total_blocks = blocks;
+        blocks = agg_layout_rows(a, gs);
         if (blocks == 0 && !a.fin_row_lv) return HMP_OK;
-        grid = blocks + (a.fin_row_lv ? 1 : 0);
       }
     }
+    const int grid = blocks + (a.fin_row_lv ? 1 : 0);
     sync_bstart(a);
     if (a.dzb16) hipLaunchKernelGGL((agg_bwd_kernel<64, 1, true, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((agg_bwd_kernel<64, 1, true, false>), dim3(grid), dim3(256), 0, st, a);
@@ -1841,6 +1619,7 @@ int agg_bwd_launch(TAggArgs& a, hipStream_t st) {
     return HMP_OK;
   }
   HMP_CHECK_ARG(!a.dzb16, "agg_bwd: a bf16 dz needs bf16 gradient rows (the one-wavefront-per-row kernel)");
+  const int grid = blocks + (a.fin_row_lv ? 1 : 0);
   sync_bstart(a);
 #define LAUNCH_BWD(GS_, NV_) hipLaunchKernelGGL((agg_bwd_kernel<GS_, NV_>), dim3(grid), dim3(256), 0, st, a)
   HMP_DISPATCH_GS_NV(gs, nv, LAUNCH_BWD)
@@ -1850,10 +1629,8 @@ int agg_bwd_launch(TAggArgs& a, hipStream_t st) {
 }
 
 int agg_bwd_dx_launch(TAggArgs& a, hipStream_t st) {
-  int Fmax = 0, blocks = 0, kmax = 0;
+  int Fmax = tagg_fmax(a), kmax = 0;
   for (int i = 0; i < a.n; ++i) {
-    for (int o = 0; o < a.s[i].n_out; ++o) Fmax = a.s[i].out[o].F > Fmax ? a.s[i].out[o].F : Fmax;
-    if (a.s[i].groot) Fmax = a.s[i].Froot > Fmax ? a.s[i].Froot : Fmax;
     kmax = a.s[i].ncols > kmax ? a.s[i].ncols : kmax;
     HMP_CHECK_ARG((a.s[i].ncols & 3) == 0, "agg_bwd_dx: ncols must be padded to 4");
   }
@@ -1862,22 +1639,12 @@ int agg_bwd_dx_launch(TAggArgs& a, hipStream_t st) {
     Fmax = 4;
   }
   HMP_CHECK_ARG(Fmax <= 256 && kmax <= 896, "agg_bwd_dx: segment width %d / stacked width %d not supported", Fmax, kmax);
-  int gs = 16;
-  while (gs < 64 && gs * 4 < Fmax) gs <<= 1;
-  int tiles16 = 0;
-  for (int i = 0; i < a.n; ++i) tiles16 += cdiv(a.s[i].n_rows, 16);
-  const bool small_launch = tiles16 <= AGG_SMALL_TILES;  // see agg_proj_fwd_launch
-  for (int i = 0; i < a.n; ++i) {
-    if (a.s[i].tile_rows != 8 || !small_launch) a.s[i].tile_rows = 16;
-    a.s[i].block_start = blocks;
-    blocks += cdiv(a.s[i].n_rows, a.s[i].tile_rows);
-  }
-  a.total_blocks = blocks;
+  const int blocks = agg_layout_tiles(a);
   if (blocks == 0 && !a.fin_row_lv) return HMP_OK;
   const int grid = blocks + (a.fin_row_lv ? 1 : 0);
   const size_t smem = (size_t)kmax * 17 * sizeof(float);
   sync_bstart(a);
-  switch (gs) {
+  switch (agg_tile_gs(Fmax)) {
     case 16: hipLaunchKernelGGL((agg_bwd_dx_kernel<16>), dim3(grid), dim3(256), smem, st, a); break;
     case 32: hipLaunchKernelGGL((agg_bwd_dx_kernel<32>), dim3(grid), dim3(256), smem, st, a); break;
     default: hipLaunchKernelGGL((agg_bwd_dx_kernel<64>), dim3(grid), dim3(256), smem, st, a); break;

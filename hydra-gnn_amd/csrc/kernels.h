@@ -304,7 +304,7 @@ struct AggDst {
   // act / dropout are the model's tail, so the gradient written is d loss / d (pre-activation): . keep/(1-p) . act', read off y
   const uint8_t* ce_mask;
   int ce_tail;
-  int win_in, win_src_rows;  // filled by agg_fwd_launch: in-conv served from the LDS window (-1: none), rows of its source
+  int win_in;                // filled by agg_fwd_launch: in-conv served from the LDS window (-1: none)
   int tile_rows;             // agg_proj_fwd_launch: rows per workgroup, 16 or 8.  A launch is as long as its slowest tile and a tile of
                              // high-degree rows (rooms: ~12 objects each) requests twice the lines of the others (tools/ktime_blocks.py:
                              // 7.3 us against 5.8 us): such entries are cut into twice as many tiles of 8 rows (there are idle CUs)
@@ -317,7 +317,6 @@ struct AggArgs {
   int xcd;   // large launches: consecutive row ranges stay on one XCD (block counts padded to 8 per entry), see agg_fwd_launch
   int zb16;  // the projected rows (AggIn::z, AggDst::zroot) hold bf16 elements (bf16 compute mode, 256-wide rows)
   int hb16;  // with zb16: the outputs (AggDst::out) are WRITTEN as bf16 elements too (activations of a hidden layer, read only by GEMMs)
-  int win_R, win_W;  // LDS-windowed launch (agg_fwd_win_kernel): destination rows per workgroup / source rows staged
   NetState* state;  // status bits (fused cross entropy: label out of range)
   int bstart[HMP_MAX_NODE_TYPES];  // d[i].block_start again, in the struct's first lines (filled by the launchers): a workgroup
                                    // finds its entry without touching one argument line per entry, see karg_warm (common.h)
@@ -351,7 +350,7 @@ struct TAggSrc {
   const float* xh;  // activations whose derivative masks xg (null: none)
   int xldw, xN, xldg, xldh, xact, xdrop_on;
   float xscale;
-  int win_out, win_dst_rows;  // filled by agg_bwd_launch (see AggDst::win_in)
+  int win_out;                // filled by agg_bwd_launch (see AggDst::win_in)
   int tile_rows;              // agg_bwd_dx_launch: rows per workgroup, 16 or 8 (see AggDst::tile_rows)
   TAggOut out[AGG_MAX_IN];
 };
@@ -362,7 +361,6 @@ struct TAggArgs {
   int xcd;  // as AggArgs::xcd
   int gb16; // the gradient rows (TAggOut::g, TAggSrc::groot) hold bf16 elements
   int dzb16; // dz is written as bf16 (requires gb16)
-  int win_R, win_W;  // LDS-windowed launch (agg_bwd_win_kernel)
   // one extra block sums the per-row {loss, valid} pairs of the loss in fixed order -> fin_out2 / fin_state (null: off)
   const float* fin_row_lv;
   int fin_rows;
