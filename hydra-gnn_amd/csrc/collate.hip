@@ -4,7 +4,7 @@
 // copies the batch to the device every step; at MP3D sizes that costs as much as the GPU step itself.  Here the DATASET is
 // resident in HBM as packed per-type arrays (all graphs' node rows back to back, all edge lists back to back with
 // graph-local indices, plus [G+1] offset vectors), and a batch is assembled by two gather kernels:
-//   rows   out[dst_off[b] + i]        = src[src_ptr[sel[b]] + i]                                  (x, y, pos, edge_attr)
+//   rows   out[dst_off[b] + i]        = src[src_ptr[sel[b]] + i]                                  (x, y, pos, edge_attr, masks)
 //   edges  out[r][dst_off[b] + j]     = src[r][edge_ptr[sel[b]] + j] + node_off_{r}[b]            (edge_index, r = 0 / 1)
 // which is exactly PyG's collation rule: node stores concatenated in batch order, edge indices
 // shifted by the cumulative node counts of their endpoint types.  Byte work, HBM-bound, no GEMM.
@@ -37,6 +37,19 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(const uint32_t* __res
   }
 }
 
+// rows whose size is not a multiple of 4 bytes (bool / int8 masks: 1 byte): one thread per output byte
+__global__ __launch_bounds__(256) void collate_rows_bytes_kernel(const uint8_t* __restrict__ src, int row_bytes, const int64_t* __restrict__ src_ptr,
+                                                                 const int32_t* __restrict__ sel, const int64_t* __restrict__ dst_off, int B,
+                                                                 uint8_t* __restrict__ dst) {
+  const int64_t total = dst_off[B] * row_bytes;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = g / row_bytes;
+    const int b = find_seg(dst_off, B, row);
+    const int64_t srow = src_ptr[sel[b]] + (row - dst_off[b]);
+    dst[g] = src[srow * row_bytes + (g - row * row_bytes)];
+  }
+}
+
 __global__ __launch_bounds__(256) void collate_edges_kernel(const int64_t* __restrict__ src, int64_t e_total, const int64_t* __restrict__ edge_ptr,
                                                             const int32_t* __restrict__ sel, const int64_t* __restrict__ dst_off,
                                                             const int64_t* __restrict__ off_src, const int64_t* __restrict__ off_dst, int B,
@@ -55,9 +68,16 @@ __global__ __launch_bounds__(256) void collate_edges_kernel(const int64_t* __res
 extern "C" int hmp_collate_rows(const void* d_src, int64_t row_bytes, const int64_t* d_src_ptr, const int32_t* d_sel,
                                 const int64_t* d_dst_off, int32_t B, int64_t n_out_rows, void* d_dst, void* stream) {
   using namespace hmp;
-  HMP_CHECK_ARG(B >= 0 && n_out_rows >= 0 && row_bytes > 0 && (row_bytes & 3) == 0, "hmp_collate_rows: row_bytes must be a positive multiple of 4");
+  HMP_CHECK_ARG(B >= 0 && n_out_rows >= 0 && row_bytes > 0 && row_bytes <= INT32_MAX, "hmp_collate_rows: row_bytes must be positive");
   if (B == 0 || n_out_rows == 0) return HMP_OK;
   HMP_CHECK_ARG(d_src && d_src_ptr && d_sel && d_dst_off && d_dst, "hmp_collate_rows: null pointer");
+  if (row_bytes & 3) {  // byte-wide rows (masks)
+    const int64_t want = cdiv(n_out_rows * row_bytes, 256);
+    hipLaunchKernelGGL(collate_rows_bytes_kernel, dim3((int)(want > 4096 ? 4096 : want)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)d_src,
+                       (int)row_bytes, d_src_ptr, d_sel, d_dst_off, B, (uint8_t*)d_dst);
+    HMP_LAUNCH_CHECK();
+    return HMP_OK;
+  }
   const int64_t units = n_out_rows * (row_bytes / 4);
   const int64_t want = cdiv(units, 256);
   hipLaunchKernelGGL(collate_rows_kernel, dim3((int)(want > 4096 ? 4096 : want)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_src,
@@ -89,21 +109,23 @@ extern "C" int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const in
 // =============================================================================================================================
 namespace hmp {
 
-// 24 / 24: room for an H-tree dataset (6 node types, 15 edge types: 21 slots, 22 items); slots cost nothing in the
-// argument block, items 56 bytes each
-constexpr int CB_MAX_ITEMS = 24;
+// 40 / 24: room for the two-headed H-tree dataset with edge attributes (6 node types, 15 edge types: 21 slots; 6 x, 2 y, 6 masks,
+// 15 edge lists, 10 edge_attr: 39 items).  Slots cost nothing in the argument block, items 48 bytes each; what the items leave of
+// the 4 KB block carries the per-batch tables (a config-2 batch of 32 graphs needs 6 * 33 + 32 = 230 words)
+constexpr int CB_MAX_ITEMS = 40;
 constexpr int CB_MAX_SLOTS = 24;
-constexpr int CB_INLINE_WORDS = 336;  // int64 words of per-batch tables carried by value in the kernel argument block (whole block < 4 KB)
+constexpr int CB_INLINE_WORDS = 264;  // int64 words of per-batch tables carried by value in the kernel argument block (whole block < 4 KB)
 
 struct CbItem {
-  const uint32_t* src;    // rows: packed rows (4-byte units); edges: int64 edge_index [2][src_total] viewed as units
+  const uint32_t* src;    // rows: packed rows; edges: int64 edge_index [2][src_total]
   uint32_t* dst;
   const int64_t* ptr;     // [G + 1] per-graph offsets into src (device)
   int64_t src_total;      // edges: E_total
-  int row_units;          // rows: 4-byte units per row; edges: 0
-  int slot, slot_src, slot_dst;
+  int row_bytes;          // rows: bytes per row (a multiple of 4: moved as 4-byte units; otherwise byte by byte); edges: 0
+  uint8_t slot, slot_src, slot_dst;
   int block_start;
 };
+static_assert(CB_MAX_SLOTS <= 256 && sizeof(CbItem) == 48, "CbItem packing");
 struct CbArgs {
   int n_items, B, total_blocks, n_slots;
   const int64_t* tables;  // device tables (large batches), null: inline
@@ -127,7 +149,20 @@ __global__ __launch_bounds__(256) void collate_batch_kernel(const CbArgs a) {
   const int64_t n_out = off[B];
   if (a.off_out && blockIdx.x == 0)
     for (int q = threadIdx.x; q < a.n_slots * (B + 1); q += 256) a.off_out[(int64_t)(q / (B + 1)) * a.off_stride + q % (B + 1)] = tab[q];
-  if (I.row_units >= 32) {
+  const int row_units = I.row_bytes >> 2;
+  if (I.row_bytes & 3) {
+    // byte-wide rows (bool / int8 masks of the two-headed task): one thread per output byte
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(I.src);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(I.dst);
+    const int rb = I.row_bytes;
+    const int64_t total = n_out * rb;
+    for (int64_t g = (int64_t)((int)blockIdx.x - I.block_start) * 256 + threadIdx.x; g < total; g += (int64_t)nb * 256) {
+      const int64_t row = g / rb;
+      const int b = find_seg(off, B, row);
+      const int64_t srow = I.ptr[sel[b]] + (row - off[b]);
+      dst[g] = src[srow * rb + (g - row * rb)];
+    }
+  } else if (row_units >= 32) {
     // wide rows (features): one wavefront per row -- the batch position of the row is found ONCE (wave-uniform search in the
     // offset table), then 64 lanes copy the row with coalesced 8-byte (even widths) or 4-byte accesses
     const int lane = threadIdx.x & 63;
@@ -135,20 +170,20 @@ __global__ __launch_bounds__(256) void collate_batch_kernel(const CbArgs a) {
     for (int64_t row = w0; row < n_out; row += (int64_t)nb * 4) {
       const int b = __builtin_amdgcn_readfirstlane(find_seg(off, B, row));
       const int64_t srow = I.ptr[sel[b]] + (row - off[b]);
-      const uint32_t* sp = I.src + srow * I.row_units;
-      uint32_t* dp = I.dst + row * I.row_units;
-      if ((I.row_units & 1) == 0 && ((reinterpret_cast<uintptr_t>(sp) | reinterpret_cast<uintptr_t>(dp)) & 7) == 0) {
-        for (int u = lane; u < (I.row_units >> 1); u += 64) reinterpret_cast<uint2*>(dp)[u] = reinterpret_cast<const uint2*>(sp)[u];
+      const uint32_t* sp = I.src + srow * row_units;
+      uint32_t* dp = I.dst + row * row_units;
+      if ((row_units & 1) == 0 && ((reinterpret_cast<uintptr_t>(sp) | reinterpret_cast<uintptr_t>(dp)) & 7) == 0) {
+        for (int u = lane; u < (row_units >> 1); u += 64) reinterpret_cast<uint2*>(dp)[u] = reinterpret_cast<const uint2*>(sp)[u];
       } else {
-        for (int u = lane; u < I.row_units; u += 64) dp[u] = sp[u];
+        for (int u = lane; u < row_units; u += 64) dp[u] = sp[u];
       }
     }
-  } else if (I.row_units > 0) {
+  } else if (row_units > 0) {
     // narrow rows (labels, positions, edge attributes): one thread per row
     for (int64_t row = (int64_t)((int)blockIdx.x - I.block_start) * 256 + threadIdx.x; row < n_out; row += (int64_t)nb * 256) {
       const int b = find_seg(off, B, row);
       const int64_t srow = I.ptr[sel[b]] + (row - off[b]);
-      for (int u = 0; u < I.row_units; ++u) I.dst[row * I.row_units + u] = I.src[srow * I.row_units + u];
+      for (int u = 0; u < row_units; ++u) I.dst[row * row_units + u] = I.src[srow * row_units + u];
     }
   } else {
     const int64_t* src = reinterpret_cast<const int64_t*>(I.src);
@@ -191,14 +226,15 @@ extern "C" int hmp_collator_create(int32_t n_slots, const int64_t* const* h_slot
   for (int s = 0; s < n_slots; ++s) c->slot_ptr.emplace_back(h_slot_ptr[s], h_slot_ptr[s] + n_graphs + 1);
   for (int i = 0; i < n_items; ++i) {
     const hmp_collate_item& it = items[i];
-    if (!(it.d_src && it.d_ptr && it.slot >= 0 && it.slot < n_slots && it.row_bytes >= 0 && (it.row_bytes & 3) == 0 &&
+    if (!(it.d_src && it.d_ptr && it.slot >= 0 && it.slot < n_slots && it.row_bytes >= 0 && it.row_bytes <= INT32_MAX &&
           (it.row_bytes > 0 || (it.slot_src >= 0 && it.slot_src < n_slots && it.slot_dst >= 0 && it.slot_dst < n_slots)))) {
       delete c;
       HMP_FAIL(HMP_E_ARG, "hmp_collator_create: item %d is malformed", i);
     }
     CbItem& I = c->item[i];
     I.src = (const uint32_t*)it.d_src; I.dst = nullptr; I.ptr = it.d_ptr; I.src_total = it.src_total;
-    I.row_units = (int)(it.row_bytes / 4); I.slot = it.slot; I.slot_src = it.slot_src; I.slot_dst = it.slot_dst; I.block_start = 0;
+    I.row_bytes = (int)it.row_bytes; I.slot = (uint8_t)it.slot; I.block_start = 0;
+    I.slot_src = it.row_bytes ? 0 : (uint8_t)it.slot_src; I.slot_dst = it.row_bytes ? 0 : (uint8_t)it.slot_dst;
   }
   *out = c;
   return HMP_OK;
@@ -267,8 +303,10 @@ extern "C" int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B
     const int64_t n_out = h_totals[a.item[i].slot];
     HMP_CHECK_ARG(n_out <= dst_capacity[i], "hmp_collator_run: item %d needs %lld rows, buffer holds %lld", i, (long long)n_out, (long long)dst_capacity[i]);
     HMP_CHECK_ARG(n_out == 0 || d_dst[i], "hmp_collator_run: item %d has no output buffer", i);
-    // wide rows: a wavefront per row, 2 rows per wavefront and pass; narrow rows / edges: a thread per row / edge
-    int64_t nb = a.item[i].row_units >= 32 ? (n_out + 7) / 8 : (n_out + 255) / 256;
+    // wide rows: a wavefront per row, 2 rows per wavefront and pass; narrow rows / edges: a thread per row / edge; byte rows: a
+    // thread per byte
+    const int rb = a.item[i].row_bytes;
+    int64_t nb = (rb & 3) ? (n_out * rb + 255) / 256 : rb >= 128 ? (n_out + 7) / 8 : (n_out + 255) / 256;
     if (nb > 2048) nb = 2048;
     a.item[i].block_start = blocks;
     blocks += (int)nb;

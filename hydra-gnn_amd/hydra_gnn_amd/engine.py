@@ -64,6 +64,8 @@ class _BatchHolder:
         # an input had to be copied (dtype / layout conversion): the descriptor points at a private copy, so it must not be
         # reused for a later step (in-place edits of the caller's tensor would be missed)
         self.converted = False
+        # store.BatchStream that owns the descriptor (device-collated batches): it holds the targets of a two-headed stream
+        self.stream = None
 
 
 class NativeNet:
@@ -513,6 +515,18 @@ class NativeNet:
         self._count("hmp_net_count_correct2", h, flat.device, C.byref(tg), flat.data_ptr(), counts.data_ptr())
         return counts
 
+    def count_correct_stream(self, holder: "_BatchHolder", mask: Optional[str], counts: torch.Tensor) -> torch.Tensor:
+        """:meth:`count_correct` / :meth:`count_correct_heads` on a device-collated batch of a two-headed stream
+        (``store.BatchStream.next``): labels, head rows and the mask called ``mask`` are the stream's own.  Nothing synchronises."""
+        stream = getattr(holder, "stream", None)
+        if stream is None or stream.nat is not self:
+            raise _lib.HydraMPError("count_correct: the batch descriptor does not come from a stream created for this model")
+        flat = self.flat_params(full_check=False)
+        _check_counts4(counts, flat.device)
+        entry = "hmp_net_count_correct_heads" if self.heads is not None else "hmp_net_count_correct2"
+        self._count(entry, holder, flat.device, stream.targets(mask), flat.data_ptr(), counts.data_ptr())
+        return counts
+
     def count_correct_heads(self, data, labels, mask, members, counts: torch.Tensor) -> torch.Tensor:
         """Nets with linear heads: ADD this batch's {correct, total} of both heads to the device int64[4] ``counts``
         (``hmp_net_count_correct_heads``: eval-mode forward, argmax of both heads on act(final state), comparison under ``mask``
@@ -888,6 +902,12 @@ class TrainStep:
     def run(self, holder: _BatchHolder) -> None:
         """One training step on a batch that is already described (``store.BatchStream.next``): no per-tensor Python, no
         descriptor cache -- the path a data loader that lives on the device drives.  Eager launches."""
+        if getattr(getattr(holder, "stream", None), "two_headed", False):
+            raise _lib.HydraMPError("TrainStep.run: the batch comes from a two-headed stream (labels and masks of two heads); step it "
+                                    "with the model's semisupervised_step().run")
+        self._run(holder)
+
+    def _run(self, holder: _BatchHolder) -> None:
         net = self.net
         if self.use_graph:
             raise _lib.HydraMPError("TrainStep.run steps a NEW batch every call: create the step with use_graph=False")
@@ -936,8 +956,18 @@ class TwoHeadTrainStep(TrainStep):
         tensors = tuple(labels) + (tuple(masks) if masks is not None else ())
         self._step(data, masks is None, tensors, None, lambda h: _head_targets(self.net, h, labels, masks))
 
-    def run(self, holder) -> None:
-        raise _lib.HydraMPError("TwoHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")
+    def run(self, holder, mask: Optional[str] = "train_mask") -> None:
+        """One step on a device-collated batch of a two-headed stream (``store.stream(model, batch_size).next(ids)``): what
+        :meth:`TrainStep.run` does, with the stream's own targets under the mask called ``mask`` (None = every row).  The stream's
+        buffers never move, so its ``hmp_head_targets`` / ``hmp_linear_head_targets`` are built once per mask name."""
+        stream = getattr(holder, "stream", None)
+        if stream is None:
+            raise _lib.HydraMPError(f"{type(self).__name__}.run takes a batch from store.BatchStream.next; step a data batch with "
+                                    "step(data, ...)")
+        if stream.nat is not self.net:
+            raise _lib.HydraMPError(f"{type(self).__name__}.run: the batch comes from a stream created for another model")
+        self._targets = (stream.targets(mask),)
+        self._run(holder)
 
 
 def _linear_head_targets(net: NativeNet, h: _BatchHolder, labels, mask, members) -> _lib.LinearHeadTargets:
@@ -1005,6 +1035,3 @@ class LinearHeadTrainStep(TwoHeadTrainStep):
         members = (data.room_mask, getattr(data, self.object_attr) if self.object_attr is not None else None)
         tensors = (labels, mask) + members
         self._step(data, None, tensors, None, lambda h: _linear_head_targets(self.net, h, labels, mask, members))
-
-    def run(self, holder) -> None:
-        raise _lib.HydraMPError("LinearHeadTrainStep has no run(): device-collated batches of the two-headed task are not supported")

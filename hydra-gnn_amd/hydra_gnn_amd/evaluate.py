@@ -1,4 +1,4 @@
-"""Validation accuracy of the room task on the device: ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
+"""Validation accuracy on the device (room task: :func:`accuracy`; two-headed task: :func:`semisupervised_accuracy`): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
 per batch.
 
 The reference's ``test()`` runs an eval-mode forward per batch, takes ``argmax(dim=1)``, drops the rows whose label is the
@@ -70,3 +70,40 @@ def accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], ignored_l
     correct, total = int(host[0]), int(host[1])
     acc = correct / total  # the reference's division (a pass without labelled rows raises ZeroDivisionError there too)
     return (acc, accuracy_matrix(host[2:], ignored_label)) if per_label else acc
+
+
+def semisupervised_accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], mask_name: str = "test_mask",
+                            type_separated: bool = False):
+    """The arithmetic of ``SemiSupervisedTrainingJob.test`` (``semisupervised_training_job.py:198-258``) for the two-headed
+    (room + object) task with ONE synchronisation per pass: ``model.count_correct`` per batch adds {correct_room, total_room,
+    correct_object, total_object} to one device int64[4] tensor, which is copied to the host after the last batch.
+
+    ``batches``: an iterable of batches on the model's device (``HeteroData`` for the heterogeneous models, their labels and
+    masks read from the node types of ``net.head_label_types()``; ``Data`` for the homogeneous ones), or a ``(BatchStream,
+    iterable of graph-id lists)`` pair of a two-headed stream.  Returns ``(correct_room + correct_object) / (total_room +
+    total_object)``, or with ``type_separated=True`` the pair ``(correct_room / total_room, correct_object / total_object)``."""
+    from .store import BatchStream
+
+    if mask_name not in ("train_mask", "val_mask", "test_mask"):  # the reference's assert (:201)
+        raise ValueError(f"mask_name must be train_mask, val_mask or test_mask, got {mask_name!r}")
+    dev = next(model.parameters()).device
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    hetero = model.native().aux_readout is not None
+    if isinstance(batches, tuple) and len(batches) == 2 and isinstance(batches[0], BatchStream):
+        stream, id_lists = batches
+        for ids in id_lists:
+            if hetero:
+                model.count_correct(stream.next(ids), None, mask_name, counts)
+            else:
+                model.count_correct(stream.next(ids), mask_name, counts)
+    else:
+        types = model.native().head_label_types() if hetero else None
+        for batch in batches:
+            if hetero:
+                model.count_correct(batch, tuple(batch[t].y for t in types), tuple(getattr(batch[t], mask_name) for t in types), counts)
+            else:
+                model.count_correct(batch, mask_name, counts)
+    correct_room, total_room, correct_object, total_object = (int(v) for v in counts.cpu())  # the one synchronisation of the pass
+    if type_separated:
+        return correct_room / total_room, correct_object / total_object
+    return (correct_room + correct_object) / (total_room + total_object)

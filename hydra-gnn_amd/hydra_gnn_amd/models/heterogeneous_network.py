@@ -136,19 +136,31 @@ class _HeteroTwoHead(_NativeModule):
         kw.setdefault("seed", self._seed)
         return TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
 
-    def count_correct(self, data, labels, masks=None, counts=None):
+    def count_correct(self, data, labels=None, masks=None, counts=None):
         """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
         forward, argmax of both heads, compared with ``labels = (y_rooms, y_objects)`` under ``masks``.  With ``counts`` (device
         int64[4]) the batch's {correct_rooms, total_rooms, correct_objects, total_objects} are ADDED to it on the device and the
         tensor is returned without a sync (a loader loop reads it once per pass); without, returns the four ints of this batch.
-        The H-tree model's heads are its pooled rows: labels and masks of ``room_virtual`` / ``object_virtual``."""
+        The H-tree model's heads are its pooled rows: labels and masks of ``room_virtual`` / ``object_virtual``.
+        ``data`` may be a descriptor from a two-headed ``store.BatchStream.next``: the labels are the stream's (pass none) and
+        ``masks`` is the NAME of the mask (``"train_mask"`` / ``"val_mask"`` / ``"test_mask"``; None = every row)."""
+        from ..engine import _BatchHolder
+
         net = self.native()
         if net.aux_readout is None:
             raise _lib.HydraMPError("count_correct: the model has one output (build it with output_dim_dict)")
         acc = counts
         if acc is None:
             acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
-        net.count_correct(data, labels, masks, acc)
+        if isinstance(data, _BatchHolder):
+            if labels is not None or not (masks is None or isinstance(masks, str)):
+                raise _lib.HydraMPError("count_correct: a stream batch brings its own labels (pass labels=None) and takes the mask by "
+                                        "name (masks='val_mask')")
+            net.count_correct_stream(data, masks, acc)
+        else:
+            if labels is None:
+                raise _lib.HydraMPError("count_correct: labels are required for a data batch")
+            net.count_correct(data, labels, masks, acc)
         return acc if counts is not None else [int(v) for v in acc.tolist()]
 
 

@@ -139,12 +139,18 @@ class HomogeneousNetwork(_NativeModule):
         """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode
         forward, argmax of both heads, compared with ``data.y`` on the rows of ``data.<mask_name>``.  With ``counts`` (device
         int64[4]) {correct_room, total_room, correct_object, total_object} are ADDED to it without a sync; without, returns the
-        four ints of this batch."""
+        four ints of this batch.  ``data`` may be a descriptor from a two-headed ``store.BatchStream.next``: labels, head rows and
+        the mask called ``mask_name`` are then the stream's own."""
+        from ..engine import _BatchHolder
+
         self._check_two_head("count_correct")
         net = self.native()
         acc = counts
         if acc is None:
             acc = torch.zeros(4, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+        if isinstance(data, _BatchHolder):
+            net.count_correct_stream(data, mask_name, acc)
+            return acc if counts is not None else [int(v) for v in acc.tolist()]
         members = (data.room_mask, getattr(data, self._OBJECT_ATTR) if self._OBJECT_ATTR is not None else None)
         net.count_correct_heads(self._view(data), data.y, getattr(data, mask_name), members, acc)
         return acc if counts is not None else [int(v) for v in acc.tolist()]

@@ -11,16 +11,35 @@ cumsums over per-graph counts it keeps) and ships them in ONE small pinned H2D c
 The result is a :class:`hydra_gnn_amd.data.HeteroData` on the device with the same content, order and dtypes as
 ``data.collate(graphs).to(device)`` (bit-identical: ``tests/test_gpu_collate.py``), incl. ``batch`` / ``ptr`` vectors and
 ``num_graphs``.
+
+The two-headed (room + object) task of ``SemiSupervisedTrainingJob`` (``semisupervised_training_job.py:89-160``) is served the
+same way: bool / int8 rows (``train_mask`` / ``val_mask`` / ``test_mask`` / ``room_mask`` / ``object_mask``) are stored as they
+are and move through the byte branch of the same kernels, and a list of homogeneous :class:`hydra_gnn_amd.data.Data` graphs is
+stored under the names the homogeneous models present to the executor (node type ``node``; ``edge_index`` -> ``to``,
+``pool_edge_index`` -> ``pool``, ``init_edge_index`` -> ``init``).  A stream created for a two-headed model carries the labels and
+masks of both heads in its own buffers (``tests/test_gpu_semisupervised_stream.py``).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .data import EdgeType, HeteroData
+from .data import Data, EdgeType, HeteroData
+
+# homogeneous graphs: the names of the models' views (models/homogeneous_network.py, homogeneous_neural_tree_network.py)
+HOMO_NODE = "node"
+_HOMO_REL = {"edge_index": "to", "pool_edge_index": "pool", "init_edge_index": "init"}
+_HOMO_EDGE_ROWS = ("edge_attr", "edge_type")  # per-edge rows that follow `edge_index`
+DEFAULT_MASKS = ("train_mask", "val_mask", "test_mask")
+
+
+def homo_edge_type(name: str) -> EdgeType:
+    """edge type under which a homogeneous ``*index*`` attribute is stored"""
+    rel = _HOMO_REL.get(name) or name.replace("_edge_index", "").replace("_index", "")
+    return (HOMO_NODE, rel, HOMO_NODE)
 
 
 class _Packed:
@@ -32,19 +51,28 @@ class _Packed:
         self.data = torch.cat(parts, dim=0).contiguous().to(device)
         self.ptr = torch.from_numpy(self.ptr_host).to(device)
         self.row_shape = tuple(self.data.shape[1:])
+        # any size: multiples of 4 move as 4-byte units, bool / int8 rows byte by byte (csrc/collate.hip)
         self.row_bytes = int(self.data.element_size()) * (int(np.prod(self.row_shape, dtype=np.int64)) if self.row_shape else 1)
-        if self.row_bytes % 4 != 0:
-            raise _lib.HydraMPError(f"attribute rows of {self.row_bytes} bytes: the collate kernels move 4-byte units "
-                                    "(store bool / int8 masks as int32)")
 
 
 class GraphStore:
-    def __init__(self, graphs: Sequence[HeteroData], device="cuda:0"):
+    def __init__(self, graphs: Sequence, device="cuda:0"):
+        """``graphs``: a list of ``HeteroData``, or a list of homogeneous ``Data`` (classified by name as PyG and
+        ``data.collate_homogeneous`` do: ``*index*`` = an edge list shifted by the node offsets, ``edge_attr`` / ``edge_type`` = rows
+        per edge of ``edge_index``, every other tensor = rows per node)."""
         assert len(graphs) > 0
         self.device = torch.device(device)
         self.lib = _lib.require_device()
         self.n_graphs = len(graphs)
         g0 = graphs[0]
+        self.homogeneous = not hasattr(g0, "node_types")
+        self._stage = None
+        self._stage_dev = None
+        self._copied = None  # event: the previous batch's offset copy has left the pinned buffer
+        self.edge_rows: Dict[EdgeType, Dict[str, _Packed]] = {}  # per-edge rows by attribute name (edge_attr, edge_type)
+        if self.homogeneous:
+            self._init_homogeneous(graphs)
+            return
         self.node_types = list(g0.node_types)
         self.edge_types: List[EdgeType] = list(g0.edge_types)
         # node attributes (tensors whose first dimension is the node count)
@@ -72,14 +100,56 @@ class GraphStore:
             self.edge_index[e] = torch.cat(eis, dim=1).contiguous().to(self.device)
             if "edge_attr" in g0[e]:
                 self.edge_attr[e] = _Packed([g[e].edge_attr for g in graphs], self.device)
-        # staging buffer for the per-batch offset vectors (pinned: the H2D copy is asynchronous)
-        self._stage = None
-        self._stage_dev = None
-        self._copied = None  # event: the previous batch's offset copy has left the pinned buffer
+                self.edge_rows[e] = {"edge_attr": self.edge_attr[e]}
+
+    def _init_homogeneous(self, graphs: Sequence[Data]) -> None:
+        g0 = graphs[0]
+        keys = [k for k, v in g0.__dict__.items() if k != "_plan_cache" and isinstance(v, torch.Tensor)]
+        self.homo_keys = keys  # collate_homogeneous's attribute order
+        if "x" not in keys:
+            raise _lib.HydraMPError("homogeneous graphs need the node features 'x' (they give the node count)")
+        self.node_types = [HOMO_NODE]
+        self.node_counts = {HOMO_NODE: np.array([int(g.num_nodes) for g in graphs], dtype=np.int64)}
+        self.count_only = {HOMO_NODE: False}
+        self.node_attrs = {HOMO_NODE: {}}
+        self.edge_types, self.edge_name = [], {}
+        self.edge_index, self.edge_ptr, self.edge_ptr_host, self.edge_attr = {}, {}, {}, {}
+        for k in keys:
+            parts = [getattr(g, k) for g in graphs]
+            if "index" in k:
+                e = homo_edge_type(k)
+                if e in self.edge_name:
+                    raise _lib.HydraMPError(f"attributes '{self.edge_name[e]}' and '{k}' map to the same edge type {e}")
+                counts = np.array([int(ei.size(1)) for ei in parts], dtype=np.int64)
+                ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                self.edge_types.append(e)
+                self.edge_name[e] = k
+                self.edge_ptr_host[e] = ptr
+                self.edge_ptr[e] = torch.from_numpy(ptr).to(self.device)
+                if parts[0].dtype != torch.int64:
+                    raise _lib.HydraMPError(f"'{k}' must be int64, got {parts[0].dtype}")
+                self.edge_index[e] = torch.cat(parts, dim=1).contiguous().to(self.device)
+            elif k not in _HOMO_EDGE_ROWS:
+                pk = _Packed(parts, self.device)
+                if not np.array_equal(pk.counts, self.node_counts[HOMO_NODE]):
+                    raise _lib.HydraMPError(f"'{k}' is stored per node but its first dimension is not the node count of every graph")
+                self.node_attrs[HOMO_NODE][k] = pk
+        for k in keys:
+            if k in _HOMO_EDGE_ROWS:
+                e = homo_edge_type("edge_index")
+                if e not in self.edge_name:
+                    raise _lib.HydraMPError(f"'{k}' without 'edge_index'")
+                pk = _Packed([getattr(g, k) for g in graphs], self.device)
+                if not np.array_equal(pk.counts, np.diff(self.edge_ptr_host[e])):
+                    raise _lib.HydraMPError(f"'{k}' must have one row per edge of 'edge_index' in every graph")
+                self.edge_rows.setdefault(e, {})[k] = pk
+                if k == "edge_attr":
+                    self.edge_attr[e] = pk
 
     # ---------------------------------------------------------------------------------------------------------------
-    def collate(self, ids: Sequence[int]) -> HeteroData:
-        """Batch of graphs ``ids`` (in that order) on the device; equals ``data.collate([graphs[i] for i in ids]).to(device)``."""
+    def collate(self, ids: Sequence[int]):
+        """Batch of graphs ``ids`` (in that order) on the device; equals ``data.collate([graphs[i] for i in ids]).to(device)``
+        (a store of homogeneous graphs: ``data.collate_homogeneous(...).to(device)``, a ``Data``)."""
         sel_host = np.asarray(ids, dtype=np.int64)
         B = int(sel_host.size)
         assert B > 0 and sel_host.min() >= 0 and sel_host.max() < self.n_graphs
@@ -127,6 +197,8 @@ class GraphStore:
                 setattr(out[t], k, dst)
             if self.count_only[t]:
                 out[t].num_nodes = n_out
+            if self.homogeneous:  # collate_homogeneous keeps no batch / ptr vectors
+                continue
             ptr = dev[where[t]:where[t] + B + 1].clone()
             out[t].ptr = ptr
             out[t].batch = torch.repeat_interleave(torch.arange(B, dtype=torch.int64, device=self.device), ptr[1:] - ptr[:-1],
@@ -138,13 +210,24 @@ class GraphStore:
             _lib.check(lib.hmp_collate_edges(src.data_ptr(), int(src.size(1)), self.edge_ptr[e].data_ptr(), sel_ptr, off_ptr(e),
                                              off_ptr(e[0]), off_ptr(e[2]), B, e_out, dst.data_ptr(), st))
             out[e].edge_index = dst
-            if e in self.edge_attr:
-                pk = self.edge_attr[e]
+            for k, pk in self.edge_rows.get(e, {}).items():
                 ea = torch.empty((e_out,) + pk.row_shape, dtype=pk.data.dtype, device=self.device)
                 _lib.check(lib.hmp_collate_rows(pk.data.data_ptr(), pk.row_bytes, self.edge_ptr[e].data_ptr(), sel_ptr, off_ptr(e), B, e_out,
                                                 ea.data_ptr(), st))
-                out[e].edge_attr = ea
-        return out
+                setattr(out[e], k, ea)
+        if not self.homogeneous:
+            return out
+        flat = Data()
+        e0 = homo_edge_type("edge_index")
+        for k in self.homo_keys:
+            if "index" in k:
+                flat.__dict__[k] = out[homo_edge_type(k)].edge_index
+            elif k in _HOMO_EDGE_ROWS:
+                flat.__dict__[k] = getattr(out[e0], k)
+            else:
+                flat.__dict__[k] = getattr(out[HOMO_NODE], k)
+        flat.num_graphs = B
+        return flat
 
 
 class BatchStream:
@@ -157,40 +240,104 @@ class BatchStream:
         for ids in sampler:                  # e.g. a shuffled permutation cut into batches
             step.run(stream.next(ids))       # TrainStep.run: fwd + loss + bwd + Adam on that batch
 
+    Two-headed task (a model built with ``output_dim_dict``; no ``label_type``): the stream collates, in the same launch, the
+    features and edges the net reads plus ``y`` and the ``masks`` of both heads (homogeneous models: ``room_mask`` and, for
+    H-trees, ``object_mask`` too), and nothing else the store holds:
+
+        stream = store.stream(model, batch_size=64)
+        step = model.semisupervised_step(lr, use_graph=False)
+        for ids in sampler:
+            step.run(stream.next(ids), mask="train_mask")
+        acc = evaluate.semisupervised_accuracy(model, (stream, id_lists), "val_mask")
+
     The buffers are reused by the next call: a batch is valid until then (same-stream ordering makes that safe for everything
     already enqueued).  ``stream.data()`` presents the current batch as a ``HeteroData`` of views for code that wants one."""
 
-    def __init__(self, store: "GraphStore", net, batch_size: int, label_type: str, label_key: str = "y"):
+    def __init__(self, store: "GraphStore", net, batch_size: int, label_type: Optional[str] = None, label_key: str = "y",
+                 masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True):
         import ctypes as C
 
         self.store, self.B = store, int(batch_size)
         self.net = net
         lib = store.lib
         dev = store.device
-        slots: List[object] = list(store.node_types) + list(store.edge_types)
+        nat = net.native() if hasattr(net, "native") else net
+        self.nat = nat
+        # two-headed task: the stream carries what the net reads plus the targets of both heads (labels, the named masks, the
+        # head rows of the homogeneous models) and nothing else the store holds; room task: every attribute, as before
+        self.two_headed = nat.aux_readout is not None or nat.heads is not None
+        if self.two_headed and label_type is not None:
+            raise _lib.HydraMPError("a two-headed model's stream carries the targets of both heads: pass no label_type")
+        if not self.two_headed and label_type is None:
+            raise _lib.HydraMPError("label_type is required: the node type whose labels the model's single output is trained on")
+        if not self.two_headed and store.homogeneous:
+            raise _lib.HydraMPError("a store of homogeneous graphs streams the two-headed task (a model built with output_dim_dict)")
+        self.mask_names = tuple(masks) if (self.two_headed and targets) else ()
+        self._target_kind = None
+        target_attrs: Dict[str, List[str]] = {}
+        if self.two_headed and targets:
+            if nat.heads is not None:  # learned linear heads over the rows of one node set
+                self._target_kind = "linear"
+                self._object_attr = getattr(net, "_OBJECT_ATTR", None)
+                rows = ["room_mask"] + ([self._object_attr] if self._object_attr is not None else [])
+                self._label_types = (nat.pool_edge_type[2] if nat.pool_edge_type is not None else nat.readout,)
+                target_attrs[self._label_types[0]] = [label_key] + list(self.mask_names) + rows
+            else:
+                self._target_kind = "heads"
+                self._label_types = tuple(nat.head_label_types())
+                for t in self._label_types:
+                    target_attrs[t] = [label_key] + list(self.mask_names)
+        self._label_key = label_key
+        if self.two_headed:
+            used_nodes = set(nat.node_types) | set(target_attrs)
+            node_types = [t for t in store.node_types if t in used_nodes]
+            edge_types = [e for e in store.edge_types if e in nat.edge_types]
+        else:
+            node_types, edge_types = list(store.node_types), list(store.edge_types)
+        for t in list(nat.node_types) + list(target_attrs):
+            if t not in node_types:
+                raise _lib.HydraMPError(f"the store holds no node type '{t}'")
+        for e in nat.edge_types:
+            if e not in edge_types:
+                raise _lib.HydraMPError(f"the store holds no edge type {e}")
+        slots: List[object] = node_types + edge_types
         slot_of = {k: i for i, k in enumerate(slots)}
         host_ptrs = []
-        for t in store.node_types:
+        for t in node_types:
             host_ptrs.append(np.concatenate([[0], np.cumsum(store.node_counts[t])]).astype(np.int64))
-        for e in store.edge_types:
+        for e in edge_types:
             host_ptrs.append(np.ascontiguousarray(store.edge_ptr_host[e], dtype=np.int64))
         self._host_ptrs = host_ptrs
-        self._node_ptr_dev = {t: torch.from_numpy(host_ptrs[slot_of[t]]).to(dev) for t in store.node_types}
+        self._node_ptr_dev = {t: torch.from_numpy(host_ptrs[slot_of[t]]).to(dev) for t in node_types}
         # capacity of a batch per slot: B times the largest graph (ids may repeat)
         self.cap = [int(np.diff(p).max()) * self.B for p in host_ptrs]
         items, self._bufs, self._what = [], [], []
-        for t in store.node_types:
-            for k, pk in store.node_attrs[t].items():
-                it = _lib.CollateItem(pk.data.data_ptr(), self._node_ptr_dev[t].data_ptr(), 0, pk.row_bytes, slot_of[t], 0, 0)
-                items.append(it)
-                self._bufs.append(torch.empty((max(self.cap[slot_of[t]], 1),) + pk.row_shape, dtype=pk.data.dtype, device=dev))
-                self._what.append(("node", t, k))
-        for e in store.edge_types:
+
+        def node_item(t, k):
+            pk = store.node_attrs[t].get(k)
+            if pk is None:
+                raise _lib.HydraMPError(f"the store holds no attribute '{k}' of node type '{t}'")
+            items.append(_lib.CollateItem(pk.data.data_ptr(), self._node_ptr_dev[t].data_ptr(), 0, pk.row_bytes, slot_of[t], 0, 0))
+            self._bufs.append(torch.empty((max(self.cap[slot_of[t]], 1),) + pk.row_shape, dtype=pk.data.dtype, device=dev))
+            self._what.append(("node", t, k))
+
+        for t in node_types:
+            if self.two_headed:
+                keys = (["x"] if nat.in_dims.get(t, 0) > 0 and t in nat.node_types else []) + target_attrs.get(t, [])
+            else:
+                keys = list(store.node_attrs[t])
+            for k in keys:
+                node_item(t, k)
+        for e in edge_types:
             src = store.edge_index[e]
             it = _lib.CollateItem(src.data_ptr(), store.edge_ptr[e].data_ptr(), int(src.size(1)), 0, slot_of[e], slot_of[e[0]], slot_of[e[2]])
             items.append(it)
             self._bufs.append(torch.empty(2 * max(self.cap[slot_of[e]], 1), dtype=torch.int64, device=dev))
             self._what.append(("edge", e, "edge_index"))
+            if self.two_headed and not nat.edge_dims.get(e, 0):
+                continue
+            if self.two_headed and e not in store.edge_attr:
+                raise _lib.HydraMPError(f"the store holds no 'edge_attr' of edge type {e} (read by the model's GAT_edge convs)")
             if e in store.edge_attr:
                 pk = store.edge_attr[e]
                 items.append(_lib.CollateItem(pk.data.data_ptr(), store.edge_ptr[e].data_ptr(), 0, pk.row_bytes, slot_of[e], 0, 0))
@@ -200,6 +347,7 @@ class BatchStream:
         self._items = (_lib.CollateItem * n_items)(*items)
         self._slot_ptr = (C.c_void_p * len(slots))(*[p.ctypes.data for p in host_ptrs])
         h = C.c_void_p()
+        self._h = None
         _lib.check(lib.hmp_collator_create(len(slots), self._slot_ptr, store.n_graphs, n_items, self._items, C.byref(h)))
         self._h = h
         self._dst = (C.c_void_p * n_items)(*[b.data_ptr() for b in self._bufs])
@@ -212,46 +360,61 @@ class BatchStream:
         # ---- the executor's descriptor, filled once; per batch only the counts change
         from .engine import _BatchHolder
 
-        nat = net.native() if hasattr(net, "native") else net
-        self.nat = nat
         hd = _BatchHolder()
         buf_of = {w: b for w, b in zip(self._what, self._bufs)}
+        self._buf_of = buf_of
         self._node_slot, self._edge_slot = [], []
         for i, t in enumerate(nat.node_types):
-            if t not in slot_of:
-                raise _lib.HydraMPError(f"the store holds no node type '{t}'")
             self._node_slot.append(slot_of[t])
             if nat.in_dims.get(t, 0) > 0:
+                if ("node", t, "x") not in buf_of:
+                    raise _lib.HydraMPError(f"the store holds no attribute 'x' of node type '{t}'")
                 x = buf_of[("node", t, "x")]
-                if x.dtype != torch.float32 or x.size(1) != nat.in_dims[t]:
+                if x.dtype != torch.float32 or x.dim() != 2 or x.size(1) != nat.in_dims[t]:
                     raise _lib.HydraMPError(f"store features of '{t}' are {tuple(x.shape[1:])} {x.dtype}, model expects {nat.in_dims[t]} float32")
                 hd.c.d_x[i] = x.data_ptr()
                 hd.c.ldx[i] = x.size(1)
         for i, e in enumerate(nat.edge_types):
-            if e not in slot_of:
-                raise _lib.HydraMPError(f"the store holds no edge type {e}")
             self._edge_slot.append(slot_of[e])
             hd.c.d_edge_index[i] = buf_of[("edge", e, "edge_index")].data_ptr()
             if nat.edge_dims.get(e, 0):
-                hd.c.d_edge_attr[i] = buf_of[("edge", e, "edge_attr")].data_ptr()
-        lab = buf_of[("node", label_type, label_key)]
-        if lab.dtype != torch.int64:
-            raise _lib.HydraMPError("labels in the store must be int64")
-        hd.c.d_labels = lab.data_ptr()
+                if ("edge", e, "edge_attr") not in buf_of:
+                    raise _lib.HydraMPError(f"the store holds no 'edge_attr' of edge type {e} (read by the model's GAT_edge convs)")
+                ea = buf_of[("edge", e, "edge_attr")]
+                if ea.dtype != torch.float32 or ea.dim() != 2 or ea.size(1) != nat.edge_dims[e]:
+                    raise _lib.HydraMPError(f"store 'edge_attr' of {e} is {tuple(ea.shape[1:])} {ea.dtype}, model expects {nat.edge_dims[e]} float32")
+                hd.c.d_edge_attr[i] = ea.data_ptr()
+        out_type = nat.pool_edge_type[2] if nat.pool_edge_type is not None else nat.readout
+        if not self.two_headed:
+            if ("node", label_type, label_key) not in buf_of:
+                raise _lib.HydraMPError(f"the store holds no attribute '{label_key}' of node type '{label_type}'")
+            lab = buf_of[("node", label_type, label_key)]
+            if lab.dtype != torch.int64:
+                raise _lib.HydraMPError("labels in the store must be int64")
+            hd.c.d_labels = lab.data_ptr()
+            if out_type != label_type:
+                raise _lib.HydraMPError(f"labels of '{label_type}' for a model that reads out '{out_type}'")
+            self.label_buf = lab
+        else:
+            for t, keys in target_attrs.items():
+                for k in keys:
+                    v = buf_of[("node", t, k)]
+                    want = torch.int64 if k == label_key else torch.bool
+                    if v.dtype != want or v.dim() != 1:
+                        raise _lib.HydraMPError(f"'{k}' of node type '{t}' must be a {str(want).replace('torch.', '')} vector (one entry per "
+                                                f"node), the store holds {tuple(v.shape[1:])} {v.dtype}")
         hd.keep = list(self._bufs) + [self._offsets]
         for i, t in enumerate(nat.node_types):
             hd.c.d_node_ptr[i] = self._offsets.data_ptr() + 8 * slot_of[t] * self._off_stride
         for i, e in enumerate(nat.edge_types):  # the collator's edge offsets: edges arrive graph by graph
             hd.c.d_edge_ptr[i] = self._offsets.data_ptr() + 8 * slot_of[e] * self._off_stride
-        hd.c.max_graph_nodes = int(max(int(np.diff(host_ptrs[slot_of[t]]).max()) for t in store.node_types))
+        hd.c.max_graph_nodes = int(max(int(np.diff(host_ptrs[slot_of[t]]).max()) for t in node_types))
         hd.n_nodes = [0] * len(nat.node_types)
         hd.n_edges = [0] * len(nat.edge_types)
-        out_type = nat.pool_edge_type[2] if nat.pool_edge_type is not None else nat.readout
-        if out_type != label_type:
-            raise _lib.HydraMPError(f"labels of '{label_type}' for a model that reads out '{out_type}'")
         self._out_slot = slot_of[out_type]
+        hd.stream = self  # TwoHeadTrainStep.run / count_correct find the targets through the descriptor
         self.holder = hd
-        self.label_buf = lab
+        self._targets: Dict[Optional[str], Tuple[object, object]] = {}
         # workspace sized once for the largest batch this stream can produce
         cap_h = _BatchHolder()
         cap_h.n_nodes = [self.cap[s] for s in self._node_slot]
@@ -259,6 +422,38 @@ class BatchStream:
         flat = nat.flat_params()
         with torch.cuda.device(flat.device):
             nat._ensure_workspace(cap_h, flat.device)
+
+    def targets(self, mask: Optional[str]):
+        """``byref`` of the stream's ``hmp_head_targets`` / ``hmp_linear_head_targets`` under the mask called ``mask`` (None = every
+        row).  The buffers never move, so each is built once per mask name."""
+        import ctypes as C
+
+        hit = self._targets.get(mask)
+        if hit is not None:
+            return hit[1]
+        if self._target_kind is None:
+            raise _lib.HydraMPError("the stream carries no targets" + (" (it was created with targets=False)" if self.two_headed else
+                                                                        ": it feeds a single-output model (TrainStep.run)"))
+        if mask is not None and mask not in self.mask_names:
+            raise _lib.HydraMPError(f"the stream carries no mask '{mask}' (it was created with masks={self.mask_names})")
+        buf = lambda t, k: self._buf_of[("node", t, k)].data_ptr()
+        if self._target_kind == "heads":
+            tg = _lib.HeadTargets()
+            for i, t in enumerate(self._label_types):
+                tg.d_labels[i] = buf(t, self._label_key)
+                if mask is not None:
+                    tg.d_mask[i] = buf(t, mask)
+        else:
+            t = self._label_types[0]
+            tg = _lib.LinearHeadTargets()
+            tg.d_labels = buf(t, self._label_key)
+            if mask is not None:
+                tg.d_mask = buf(t, mask)
+            tg.d_member[0] = buf(t, "room_mask")
+            if self._object_attr is not None:  # None: the object head's rows are the complement of the room rows
+                tg.d_member[1] = buf(t, self._object_attr)
+        self._targets[mask] = (tg, C.byref(tg))
+        return self._targets[mask][1]
 
     def next(self, ids) -> "object":
         """collate graphs ``ids`` (len == batch_size or fewer) into the stream's buffers; returns the descriptor for TrainStep.run"""
@@ -295,7 +490,7 @@ class BatchStream:
         return out
 
     def close(self):
-        if self._h is not None:
+        if getattr(self, "_h", None) is not None:
             self.store.lib.hmp_collator_destroy(self._h)
             self._h = None
 
@@ -306,8 +501,9 @@ class BatchStream:
             pass
 
 
-def _graphstore_stream(self, net, batch_size: int, label_type: str, label_key: str = "y") -> BatchStream:
-    return BatchStream(self, net, batch_size, label_type, label_key)
+def _graphstore_stream(self, net, batch_size: int, label_type: Optional[str] = None, label_key: str = "y",
+                       masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True) -> BatchStream:
+    return BatchStream(self, net, batch_size, label_type, label_key, masks, targets)
 
 
 GraphStore.stream = _graphstore_stream

@@ -306,3 +306,84 @@ def real_fixture_frame(fixture: Optional[str] = None, seed: int = BASE_SEED) -> 
 
 def real_fixture_batch(batch_size: int = 32, fixture: Optional[str] = None) -> HeteroData:
     return collate([real_fixture_frame(fixture)] * batch_size)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# two-headed task, per-graph form: what SemiSupervisedTrainingJob's DataLoader iterates over (a dataset is a LIST of graphs,
+# each carrying its own train / val / test split) and what store.GraphStore keeps on the device.  Four data shapes.
+# ---------------------------------------------------------------------------------------------------------------------
+def _split_masks(rng: np.random.Generator, n: int):
+    """seeded disjoint 60 / 20 / 20 split of n rows: (train_mask, val_mask, test_mask) bool tensors"""
+    u = torch.from_numpy(rng.random(n))
+    return u < 0.6, (u >= 0.6) & (u < 0.8), u >= 0.8
+
+
+def semisupervised_graphs(n_graphs: int, seed: int, relative_pos: bool = False) -> List[HeteroData]:
+    """``mp3d_like_graph`` graphs of the two-headed task (``HeterogeneousNetwork(output_dim_dict=...)``): room labels 0..25, object
+    labels 0..27, ``train_mask`` / ``val_mask`` / ``test_mask`` on BOTH node types of every graph."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    graphs = [mp3d_like_graph(rng) for _ in range(n_graphs)]
+    for g in graphs:
+        if relative_pos:
+            compute_relative_pos(g)
+        for t in ("rooms", "objects"):
+            g[t].train_mask, g[t].val_mask, g[t].test_mask = _split_masks(rng, int(g[t].y.numel()))
+    return graphs
+
+
+def semisupervised_htree_graphs(n_graphs: int, seed: int, relative_pos: bool = False) -> List[HeteroData]:
+    """H-tree graphs of the two-headed task (``HeterogeneousNeuralTreeNetwork(output_dim_dict=...)``), per graph what
+    ``semisupervised_htree_batch`` is per batch: the committed fixture's topologies, ``room_virtual.y`` in 0..14,
+    ``object_virtual.y`` in 0..34, the three masks on both virtual types; ``relative_pos``: 3-d ``edge_attr`` on the
+    message-passing edge types."""
+    npz = np.load(HTREE_FIXTURE)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = int(npz["n_graphs"])
+    graphs = [htree_graph(npz, i % n, rng) for i in range(n_graphs)]
+    for g in graphs:
+        for t, classes in (("room_virtual", 15), ("object_virtual", 35)):
+            g[t].y = torch.from_numpy(rng.integers(0, classes, size=int(g[t].num_nodes)).astype(np.int64))
+            g[t].train_mask, g[t].val_mask, g[t].test_mask = _split_masks(rng, int(g[t].num_nodes))
+        if relative_pos:
+            for src, rel, dst in HTREE_EDGE_TYPES:
+                ei = g[src, rel, dst].edge_index
+                g[src, rel, dst].edge_attr = (g[dst].x[ei[1], :3] - g[src].x[ei[0], :3]).contiguous()
+    return graphs
+
+
+def stanford_semisupervised_graphs(n_graphs: int, seed: int, edge_attr: bool = False) -> List[Data]:
+    """``stanford_like_graph``s of the homogeneous two-headed task (``HomogeneousNetwork(output_dim_dict=...)``): ``x``, ``y``,
+    ``edge_index``, ``room_mask`` and the three masks per graph; ``edge_attr``: 3-d relative positions for GAT_edge."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    graphs = [stanford_like_graph(rng) for _ in range(n_graphs)]
+    for g in graphs:
+        g.train_mask, g.val_mask, g.test_mask = _split_masks(rng, g.num_nodes)
+        if edge_attr:
+            g.edge_attr = (g.x[g.edge_index[1], :3] - g.x[g.edge_index[0], :3]).contiguous()
+    return graphs
+
+
+def stanford_htree_semisupervised_graphs(n_graphs: int, seed: int, edge_attr: bool = False) -> List[Data]:
+    """Homogeneous H-tree graphs of the two-headed task (``HomogeneousNeuralTreeNetwork(output_dim_dict=...)``): the fixture's
+    H-trees through ``heterogeneous_htree_to_homogeneous`` with 6-d features -- ``x``, ``y`` (rooms 0..14 on the ``room_mask`` rows,
+    objects 0..34 elsewhere), ``edge_index`` / ``init_edge_index`` / ``pool_edge_index``, ``node_type``, ``room_mask``,
+    ``object_mask`` and the three masks per graph."""
+    from .data import heterogeneous_htree_to_homogeneous
+
+    npz = np.load(HTREE_FIXTURE)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = int(npz["n_graphs"])
+    graphs = []
+    for i in range(n_graphs):
+        d = heterogeneous_htree_to_homogeneous(htree_graph(npz, i % n, rng))
+        del d.__dict__["edge_type"]
+        d.x = d.x[:, :6].contiguous()
+        N = d.num_nodes
+        y = torch.from_numpy(rng.integers(0, 35, size=N).astype(np.int64))
+        y[d.room_mask] = torch.from_numpy(rng.integers(0, 15, size=int(d.room_mask.sum())).astype(np.int64))
+        d.y = y
+        d.train_mask, d.val_mask, d.test_mask = _split_masks(rng, N)
+        if edge_attr:
+            d.edge_attr = (d.x[d.edge_index[1], :3] - d.x[d.edge_index[0], :3]).contiguous()
+        graphs.append(d)
+    return graphs

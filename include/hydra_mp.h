@@ -34,7 +34,10 @@ extern "C" {
  *    hmp_net_count_correct_heads: the fused step of two learned linear heads over one final state;
  *    hmp_count_correct_rows / hmp_net_count_correct_rooms: the device-side validation count of the room task;
  *    hmp_net_set_head_pools: the two-headed step / count with each head's CE on the mean over a pool edge type (LeafPool);
- *    hmp_gemm_desc (hmp_sizeof 10), hmp_gemm_grouped: unit-test entry of the grouped GEMM launchers */
+ *    hmp_gemm_desc (hmp_sizeof 10), hmp_gemm_grouped: unit-test entry of the grouped GEMM launchers;
+ *    section 8: hmp_collate_rows / hmp_collate_item::row_bytes accept any positive row size (byte-wide bool / int8 masks of the
+ *    two-headed task ride in the same launch); the one-launch collator holds 40 items (was 24) and carries 264 table words in the
+ *    argument block (was 336).  No struct changed layout, no entry was added */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -484,7 +487,8 @@ int hmp_net_profile_read(hmp_net* net, float* ms_sum /*[HMP_N_KCLASS]*/, int32_t
 /* ---------------------------------------------------------------------------------------------
  * 8. Device-side collation: replaces [PyG] DataLoader -> Batch.from_data_list + the per-step H2D copy
  *    (base_training_job.py:164-178, :205).  The dataset lives in HBM as packed arrays; a batch = the graphs sel[0..B).
- *    rows:  d_dst[d_dst_off[b] + i] = d_src[d_src_ptr[sel[b]] + i]            (row_bytes per row, multiple of 4)
+ *    rows:  d_dst[d_dst_off[b] + i] = d_src[d_src_ptr[sel[b]] + i]            (row_bytes per row, any positive size: multiples
+ *           of 4 move as 4-byte units and need 4-byte aligned arrays, other sizes -- bool / int8 masks -- move byte by byte)
  *    edges: d_dst[r][d_dst_off[b] + j] = d_src[r][d_edge_ptr[sel[b]] + j] + (r ? d_off_dst : d_off_src)[b]
  *           (d_src is [2][e_total] int64 with graph-local indices, d_dst is [2][e_out])
  * ------------------------------------------------------------------------------------------- */
@@ -496,17 +500,18 @@ int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const int64_t* d_ed
 
 /* One-launch form: the dataset description is fixed at creation, a batch costs ONE host call and ONE kernel.
  *   slots   the distinct [G + 1] per-graph offset vectors (one per node type and per edge type; host copies are kept);
- *   items   the output arrays: rows (row_bytes > 0: x / y / pos / edge_attr, positioned by `slot`) or an edge_index
+ *   items   the output arrays: rows (row_bytes > 0: x / y / pos / edge_attr / masks, positioned by `slot`) or an edge_index
  *           (row_bytes == 0: int64 [2][src_total], positioned by `slot`, endpoints shifted by `slot_src` / `slot_dst`).
  * hmp_collator_run: h_sel [B] graph ids (host), d_dst[i] / dst_capacity[i] per item (rows resp. edges), h_totals[slot] receives
  * the batch's node / edge totals (the shapes of the outputs).  No allocation or synchronisation in the steady state.
- * (<= 336 words of offsets + selection travel in the kernel's argument block, larger batches through a pinned ring;
- * at most 24 slots and 24 items.) */
+ * (<= 264 words of offsets + selection travel in the kernel's argument block, larger batches through a pinned ring;
+ * at most 24 slots and 40 items: the two-headed H-tree dataset with edge attributes has 21 and 39.  Byte-wide rows are a branch
+ * of the same kernel: a batch of the two-headed task, labels and masks of both heads included, is still ONE launch.) */
 typedef struct hmp_collate_item {
   const void* d_src;
   const int64_t* d_ptr;      /* device copy of the item's [G + 1] offsets */
   int64_t src_total;         /* edges: E_total of the packed edge_index */
-  int64_t row_bytes;         /* rows: bytes per row (multiple of 4); edges: 0 */
+  int64_t row_bytes;         /* rows: bytes per row (> 0; not a multiple of 4: copied byte by byte); edges: 0 */
   int32_t slot, slot_src, slot_dst;
 } hmp_collate_item;
 typedef struct hmp_collator hmp_collator; /* opaque */
