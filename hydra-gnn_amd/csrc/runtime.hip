@@ -37,6 +37,9 @@ size_t hmp_sizeof(int which) {
     case 8: return sizeof(hmp_linear_heads);
     case 9: return sizeof(hmp_linear_head_targets);
     case 10: return sizeof(hmp_gemm_desc);
+    case 11: return sizeof(hmp_epoch_ctl);
+    case 12: return sizeof(hmp_epoch_row);
+    case 13: return sizeof(hmp_epoch_seg);
     default: return 0;
   }
 }

@@ -123,7 +123,25 @@ class GemmDesc(C.Structure):
     ]
 
 
-_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc]
+EPOCH_STOP, EPOCH_EMPTY_VAL, EPOCH_MAX_SEGS = 1, 2, 64
+
+
+class EpochCtl(C.Structure):
+    _fields_ = [("loss_acc", C.c_double), ("weight_acc", C.c_double), ("max_val_acc", C.c_double),
+                ("epoch", C.c_int32), ("best_epoch", C.c_int32), ("early_stop_step", C.c_int32), ("status", C.c_int32)]
+
+
+class EpochRow(C.Structure):
+    _fields_ = [("loss", C.c_double), ("val_acc", C.c_double), ("correct", C.c_int64), ("total", C.c_int64),
+                ("improved", C.c_int32), ("pad_", C.c_int32)]
+
+
+class EpochSeg(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bytes", C.c_int64)]
+
+
+_STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc,
+            EpochCtl, EpochRow, EpochSeg]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -212,6 +230,11 @@ SIGNATURES = {
     "hmp_comm_query": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_comm_allreduce_sum_f32": (C.c_int, [_VP, _VP, _I64, _VP]),
     "hmp_comm_broadcast_f32": (C.c_int, [_VP, _VP, _I64, _I32, _VP]),
+    "hmp_epoch_accumulate": (C.c_int, [_VP, _VP, _VP, _VP, C.c_double, _VP]),
+    "hmp_epoch_close": (C.c_int, [_VP, _VP, _I32, _VP, _I32, C.c_double, _I32, _I32, _VP, _I32, _I32, _VP]),
+    "hmp_epoch_restore": (C.c_int, [_VP, _I32, _I32, _VP]),
+    "hmp_epoch_read": (C.c_int, [_VP, _VP, _I32, C.POINTER(EpochCtl), C.POINTER(EpochRow), C.POINTER(_I32), _VP]),
+    "hmp_epoch_read_status": (C.c_int, [_VP, C.POINTER(_I32), _VP]),
 }
 
 ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)

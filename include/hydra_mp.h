@@ -605,6 +605,63 @@ int hmp_htree_sizes(const hmp_htree* t, int32_t* counts4, int64_t* n_edges10, in
 int hmp_htree_fill(const hmp_htree* t, int32_t* object_orig, int32_t* room_orig, int32_t* const* edges10, int32_t* const* init3);
 void hmp_htree_destroy(hmp_htree* t);
 
+/* ---------------------------------------------------------------------------------------------
+ * 13. Epoch bookkeeping of a training job on the device (csrc/epoch.hip; hydra_gnn_amd/jobs.py).  What BaseTrainingJob.train /
+ *     SemiSupervisedTrainingJob.train keep on the host between two steps and two epochs (base_training_job.py:196-246,
+ *     semisupervised_training_job.py:112-175): the weighted loss sum, the best validation accuracy, the copy of the best state and
+ *     the early-stop counter.  ABI-4-compatible addition (hmp_sizeof 11..13).  accumulate / close / restore only enqueue kernels
+ *     (no allocation, no synchronisation, capturable); hmp_epoch_read and hmp_epoch_read_status synchronise.
+ *
+ *     The record starts zeroed (hipMemset): max_val_acc = 0 and epoch = 0 are the reference's initial values.
+ * ------------------------------------------------------------------------------------------- */
+#define HMP_EPOCH_STOP 1       /* status bit: early_stop_step == early_stop_window && epoch > early_stop_window */
+#define HMP_EPOCH_EMPTY_VAL 2  /* status bit: a validation pass counted no row (the reference divides by zero there) */
+#define HMP_EPOCH_MAX_SEGS 64
+
+typedef struct hmp_epoch_ctl {
+  double loss_acc;   /* sum over the epoch's steps of loss * weight */
+  double weight_acc; /* sum of the weights */
+  double max_val_acc;
+  int32_t epoch; /* epochs closed so far = index of the next log row */
+  int32_t best_epoch;
+  int32_t early_stop_step;
+  int32_t status;
+} hmp_epoch_ctl;
+
+typedef struct hmp_epoch_row {
+  double loss;
+  double val_acc;
+  int64_t correct, total;
+  int32_t improved;
+  int32_t pad_;
+} hmp_epoch_row;
+
+typedef struct hmp_epoch_seg { /* one tensor of the model state and its place in the best-state snapshot (any alignment) */
+  const void* src;
+  void* dst;
+  int64_t bytes;
+} hmp_epoch_seg;
+
+/* After a step: loss = d_loss_count ? (double)d_loss[0] / max((double)d_loss_count[0], 1.0) : (double)d_loss[0] -- with the
+ * step's flat-gradient tail (d_grads + n_active, d_grads + n_active + 1) that is TrainStep.loss(); w = d_weight ? *d_weight :
+ * weight >= 0 ? weight : d_loss_count[0].  loss_acc += loss * w (a rounded product, then a rounded sum); weight_acc += w. */
+int hmp_epoch_accumulate(hmp_epoch_ctl* d_ctl, const float* d_loss, const float* d_loss_count, const int64_t* d_weight,
+                         double weight, void* stream);
+/* After the validation pass: correct / total = the sums of d_counts[0], [2] / [1], [3] (n_counts = 2 or 4).  Writes log row
+ * `epoch` (when epoch < log_cap) with loss = loss_acc / (loss_div > 0 ? loss_div : weight_acc); on a strict improvement at
+ * epoch >= min_log_epoch copies every segment src -> dst; updates the record; zeroes the accumulators and d_counts.  Two launches:
+ * the copy (grid_blocks workgroups, 0 = one) reads the record, the update that follows in stream order writes it. */
+int hmp_epoch_close(hmp_epoch_ctl* d_ctl, hmp_epoch_row* d_log, int32_t log_cap, int64_t* d_counts, int32_t n_counts,
+                    double loss_div, int32_t min_log_epoch, int32_t early_stop_window, const hmp_epoch_seg* d_segs,
+                    int32_t n_segs, int32_t grid_blocks, void* stream);
+/* the snapshot back into the model state: every segment dst -> src */
+int hmp_epoch_restore(const hmp_epoch_seg* d_segs, int32_t n_segs, int32_t grid_blocks, void* stream);
+/* the record and the first min(epoch, log_cap) log rows to the host; *n_rows = that row count.  Synchronises the stream. */
+int hmp_epoch_read(const hmp_epoch_ctl* d_ctl, const hmp_epoch_row* d_log, int32_t log_cap, hmp_epoch_ctl* h_ctl,
+                   hmp_epoch_row* h_rows, int32_t* n_rows, void* stream);
+/* the 4-byte status word alone (the per-epoch read of a job with early stopping).  Synchronises the stream. */
+int hmp_epoch_read_status(const hmp_epoch_ctl* d_ctl, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
