@@ -10,19 +10,9 @@
 // shifted by the cumulative node counts of their endpoint types.  Byte work, HBM-bound, no GEMM.
 #include <vector>
 
-#include "kernels.h"
+#include "device_fns.h"  // find_seg
 
 namespace hmp {
-
-// segment of flat output element g: last b with dst_off[b] <= g  (dst_off has B + 1 entries, B <= 10^4: ~14 steps)
-__device__ __forceinline__ int find_seg(const int64_t* __restrict__ off, int B, int64_t g) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // unit = 4 bytes; rows are `row_units` units long
 __global__ __launch_bounds__(256) void collate_rows_kernel(const uint32_t* __restrict__ src, int row_units, const int64_t* __restrict__ src_ptr,
@@ -131,6 +121,12 @@ struct CbArgs {
   const int64_t* tables;  // device tables (large batches), null: inline
   int64_t* off_out;       // optional: the offset vectors are also written here, [n_slots][off_stride] (Batch.ptr of every slot)
   int off_stride;
+  // label filter (hmp_collator_set_label_filter): item `label_item` (8-byte rows, int64 labels) is written as
+  // member_src[source row] ? label : ignored -- the one label vector per output row the fused room step reads.  -1: no filter.
+  // A collator setting and not a CbItem field: one item per collator at most, and 16 bytes here instead of 16 * CB_MAX_ITEMS
+  int label_item;
+  const uint8_t* member_src;  // packed one-byte rows, indexed like the label item's source rows
+  int64_t ignored;
   CbItem item[CB_MAX_ITEMS];
   int64_t inl[CB_INLINE_WORDS];  // [n_slots][B + 1] offsets, then sel packed as int64
 };
@@ -180,9 +176,14 @@ __global__ __launch_bounds__(256) void collate_batch_kernel(const CbArgs a) {
     }
   } else if (row_units > 0) {
     // narrow rows (labels, positions, edge attributes): one thread per row
+    const bool filtered = ii == a.label_item;  // workgroup-uniform: the room-masked labels (row_units == 2, int64)
     for (int64_t row = (int64_t)((int)blockIdx.x - I.block_start) * 256 + threadIdx.x; row < n_out; row += (int64_t)nb * 256) {
       const int b = find_seg(off, B, row);
       const int64_t srow = I.ptr[sel[b]] + (row - off[b]);
+      if (filtered) {
+        reinterpret_cast<int64_t*>(I.dst)[row] = a.member_src[srow] != 0 ? reinterpret_cast<const int64_t*>(I.src)[srow] : a.ignored;
+        continue;
+      }
       for (int u = 0; u < row_units; ++u) I.dst[row * row_units + u] = I.src[srow * row_units + u];
     }
   } else {
@@ -213,6 +214,10 @@ struct hmp_collator {
   hipEvent_t done[RING] = {nullptr};
   size_t cap_words = 0;
   int cur = 0;
+  // label filter: see CbArgs
+  int label_item = -1;
+  const uint8_t* member_src = nullptr;
+  int64_t ignored = 0;
 };
 
 extern "C" int hmp_collator_create(int32_t n_slots, const int64_t* const* h_slot_ptr, int64_t n_graphs, int32_t n_items,
@@ -240,6 +245,21 @@ extern "C" int hmp_collator_create(int32_t n_slots, const int64_t* const* h_slot
   return HMP_OK;
 }
 
+extern "C" int hmp_collator_set_label_filter(hmp_collator* c, int32_t label_item, const uint8_t* d_member_src, int64_t ignored_label) {
+  HMP_CHECK_ARG(c, "hmp_collator_set_label_filter: null collator");
+  if (label_item < 0) {
+    c->label_item = -1; c->member_src = nullptr; c->ignored = 0;
+    return HMP_OK;
+  }
+  HMP_CHECK_ARG(label_item < c->n_items, "hmp_collator_set_label_filter: item %d of %d", label_item, c->n_items);
+  HMP_CHECK_ARG(c->item[label_item].row_bytes == 8, "hmp_collator_set_label_filter: item %d has rows of %d bytes, labels are int64 (8)",
+                label_item, c->item[label_item].row_bytes);
+  HMP_CHECK_ARG((reinterpret_cast<uintptr_t>(c->item[label_item].src) & 7) == 0, "hmp_collator_set_label_filter: item %d is not 8-byte aligned", label_item);
+  HMP_CHECK_ARG(d_member_src, "hmp_collator_set_label_filter: null member mask");
+  c->label_item = label_item; c->member_src = d_member_src; c->ignored = ignored_label;
+  return HMP_OK;
+}
+
 extern "C" void hmp_collator_destroy(hmp_collator* c) {
   if (!c) return;
   for (int i = 0; i < hmp_collator::RING; ++i) {
@@ -259,6 +279,7 @@ extern "C" int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B
   a.n_items = c->n_items; a.B = B; a.n_slots = c->n_slots; a.tables = nullptr;
   HMP_CHECK_ARG(!d_offsets_out || offsets_stride >= B + 1, "hmp_collator_run: offsets_stride %d < B + 1", offsets_stride);
   a.off_out = d_offsets_out; a.off_stride = offsets_stride;
+  a.label_item = c->label_item; a.member_src = c->member_src; a.ignored = c->ignored;
   const size_t words = (size_t)c->n_slots * (B + 1) + (size_t)B;
   int64_t* tab = a.inl;
   int slot_i = -1;
@@ -303,6 +324,7 @@ extern "C" int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B
     const int64_t n_out = h_totals[a.item[i].slot];
     HMP_CHECK_ARG(n_out <= dst_capacity[i], "hmp_collator_run: item %d needs %lld rows, buffer holds %lld", i, (long long)n_out, (long long)dst_capacity[i]);
     HMP_CHECK_ARG(n_out == 0 || d_dst[i], "hmp_collator_run: item %d has no output buffer", i);
+    HMP_CHECK_ARG(i != c->label_item || (reinterpret_cast<uintptr_t>(d_dst[i]) & 7) == 0, "hmp_collator_run: filtered label buffer (item %d) is not 8-byte aligned", i);
     // wide rows: a wavefront per row, 2 rows per wavefront and pass; narrow rows / edges: a thread per row / edge; byte rows: a
     // thread per byte
     const int rb = a.item[i].row_bytes;

@@ -4,6 +4,17 @@
 
 namespace hmp {
 
+// segment of flat output element g: last b with dst_off[b] <= g  (dst_off has B + 1 entries, B <= 10^4: ~14 steps)
+__device__ __forceinline__ int find_seg(const int64_t* __restrict__ off, int B, int64_t g) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+
 // One packed element per lane: item = (packed row, 64-column chunk) of segment S, one wavefront per item.
 __device__ __forceinline__ void pack_item(const PackSeg& S, int item, const float* __restrict__ params, float* __restrict__ packed) {
   const int chunks = (S.ld_dst + 63) >> 6;

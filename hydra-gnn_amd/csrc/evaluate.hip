@@ -11,7 +11,13 @@
 // Per-workgroup counters live in LDS; each workgroup adds its non-zero counters to the int64 outputs with one 64-bit atomic each.
 // For n_classes <= EV_HIST_MAX the confusion matrix is an LDS histogram too (<= 16 KB of int32), above that rows add to the global
 // matrix directly.  Everything is ACCUMULATED (+=): a validation pass sums its batches on the device and reads the totals once.
-#include "kernels.h"
+//
+// Per-graph form (BaseTrainingJob.test_individual_graph, base_training_job.py:315-339, for a whole batch in one launch):
+// count_rows_by_graph_kernel applies the same rule per row and adds to counts[g] = {correct, total} of the graph g that owns the
+// row, found in the batch's [n_graphs + 1] row offsets of the output node type (find_seg: rows of a graph are contiguous).  The
+// 16 rows of a workgroup pass are consecutive, so they span few graphs: rows are staged in LDS and the first row of each run of
+// equal graphs adds the run's sums with two 64-bit atomics.
+#include "device_fns.h"  // find_seg
 
 namespace hmp {
 
@@ -25,6 +31,31 @@ constexpr int EV_NONE = 0x7fffffff;
 
 __device__ __forceinline__ void ev_take(float v, int c, float& best, int& arg) {
   if (v > best || arg == EV_NONE) { best = v; arg = c; }
+}
+
+// the row's prediction by its 16 lanes (both column walks keep the first maximum, the reduction breaks ties by the lower index)
+template <bool VEC>
+__device__ __forceinline__ int ev_argmax(const float* __restrict__ xr, int n_classes, int lane) {
+  float best = -INFINITY;
+  int arg = EV_NONE;
+  if (VEC) {
+    for (int c = lane * 4; c < n_classes; c += EV_GS * 4) {
+      const float4 v = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
+      ev_take(v.x, c, best, arg);
+      if (c + 1 < n_classes) ev_take(v.y, c + 1, best, arg);
+      if (c + 2 < n_classes) ev_take(v.z, c + 2, best, arg);
+      if (c + 3 < n_classes) ev_take(v.w, c + 3, best, arg);
+    }
+  } else {
+    for (int c = lane; c < n_classes; c += EV_GS) ev_take(xr[c], c, best, arg);
+  }
+#pragma unroll
+  for (int o = EV_GS / 2; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, EV_GS);
+    const int oa = __shfl_xor(arg, o, EV_GS);
+    if (oa != EV_NONE && (arg == EV_NONE || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
+  }
+  return arg == EV_NONE ? 0 : arg;
 }
 
 template <bool VEC, bool HIST>
@@ -43,28 +74,8 @@ __global__ __launch_bounds__(256) void count_rows_kernel(const float* __restrict
     // the whole group of 16 lanes takes the same branch: the shuffles below stay inside active groups
     const int64_t y = labels[row];
     if ((members && !members[row]) || y == ignored) continue;
-    float best = -INFINITY;
-    int arg = EV_NONE;
-    const float* xr = x + (int64_t)row * ld;
-    if (VEC) {
-      for (int c = lane * 4; c < n_classes; c += EV_GS * 4) {
-        const float4 v = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
-        ev_take(v.x, c, best, arg);
-        if (c + 1 < n_classes) ev_take(v.y, c + 1, best, arg);
-        if (c + 2 < n_classes) ev_take(v.z, c + 2, best, arg);
-        if (c + 3 < n_classes) ev_take(v.w, c + 3, best, arg);
-      }
-    } else {
-      for (int c = lane; c < n_classes; c += EV_GS) ev_take(xr[c], c, best, arg);
-    }
-#pragma unroll
-    for (int o = EV_GS / 2; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, EV_GS);
-      const int oa = __shfl_xor(arg, o, EV_GS);
-      if (oa != EV_NONE && (arg == EV_NONE || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-    }
+    const int pred = ev_argmax<VEC>(x + (int64_t)row * ld, n_classes, lane);
     if (lane == 0) {
-      const int pred = arg == EV_NONE ? 0 : arg;
       atomicAdd(&s_cnt[1], 1);
       // a label outside [0, n_classes) is never predicted: it counts in the total only (pred.eq(label) is false)
       if (y >= 0 && y < n_classes) {
@@ -80,7 +91,65 @@ __global__ __launch_bounds__(256) void count_rows_kernel(const float* __restrict
     if (s_hist[i]) atomicAdd(&confusion[i], (unsigned long long)s_hist[i]);
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void count_rows_by_graph_kernel(const float* __restrict__ x, int ld, int n_rows, int n_classes,
+                                                                  const int64_t* __restrict__ labels, const uint8_t* __restrict__ members,
+                                                                  int64_t ignored, const int64_t* __restrict__ graph_ptr, int n_graphs,
+                                                                  unsigned long long* __restrict__ counts) {
+  __shared__ int s_graph[EV_RPB];  // graph of the pass's row, -1: the row does not count
+  __shared__ int s_hit[EV_RPB];
+  const int lane = threadIdx.x % EV_GS, slot = (int)threadIdx.x / EV_GS;
+  // every workgroup runs the same number of passes (the barriers below): the row bound is checked inside
+  for (int base = blockIdx.x * EV_RPB; base < n_rows; base += gridDim.x * EV_RPB) {
+    const int row = base + slot;
+    int g = -1, hit = 0;
+    if (row < n_rows) {
+      const int64_t y = labels[row];
+      if (!(members && !members[row]) && y != ignored) {  // the whole group of 16 lanes takes the same branch
+        const int pred = ev_argmax<VEC>(x + (int64_t)row * ld, n_classes, lane);
+        g = find_seg(graph_ptr, n_graphs, row);  // always inside [0, n_graphs)
+        hit = (y >= 0 && y < n_classes && pred == (int)y) ? 1 : 0;  // a label outside [0, n_classes) counts in the total only
+      }
+    }
+    if (lane == 0) { s_graph[slot] = g; s_hit[slot] = hit; }
+    __syncthreads();
+    // graphs are non-decreasing along the rows: the first counted row of each graph in this pass adds the graph's sums
+    if (lane == 0 && g >= 0) {
+      bool first = true;
+      for (int q = 0; q < slot; ++q) first = first && s_graph[q] != g;
+      if (first) {
+        int correct = 0, total = 0;
+        for (int q = slot; q < EV_RPB; ++q)
+          if (s_graph[q] == g) { correct += s_hit[q]; ++total; }
+        if (correct) atomicAdd(&counts[2 * (int64_t)g], (unsigned long long)correct);
+        atomicAdd(&counts[2 * (int64_t)g + 1], (unsigned long long)total);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
+
+int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
+                               int64_t ignored, const int64_t* graph_ptr, int n_graphs, long long* counts, hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes && n_graphs >= 0, "count_rows_by_graph: n_rows %d, n_classes %d, ld %d, n_graphs %d",
+                n_rows, n_classes, ld, n_graphs);
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(n_graphs >= 1, "count_rows_by_graph: %d rows and no graph", n_rows);
+  HMP_CHECK_ARG(x && labels && counts && graph_ptr, "count_rows_by_graph: null logits, labels, offsets or counts");
+  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
+  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  auto* c = reinterpret_cast<unsigned long long*>(counts);
+  if (vec)
+    hipLaunchKernelGGL((count_rows_by_graph_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored,
+                       graph_ptr, n_graphs, c);
+  else
+    hipLaunchKernelGGL((count_rows_by_graph_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored,
+                       graph_ptr, n_graphs, c);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
 
 int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
                       int64_t ignored, long long* counts, long long* confusion, hipStream_t st) {
@@ -112,4 +181,12 @@ extern "C" int hmp_count_correct_rows(const float* d_logits, int32_t ld, int32_t
   using namespace hmp;
   return count_rows_launch(d_logits, ld, n_rows, n_classes, d_labels, d_members, ignored_label, reinterpret_cast<long long*>(d_counts),
                            reinterpret_cast<long long*>(d_confusion), (hipStream_t)stream);
+}
+
+extern "C" int hmp_count_correct_rows_by_graph(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
+                                               const uint8_t* d_members, int64_t ignored_label, const int64_t* d_graph_ptr,
+                                               int32_t n_graphs, int64_t* d_counts, void* stream) {
+  using namespace hmp;
+  return count_rows_by_graph_launch(d_logits, ld, n_rows, n_classes, d_labels, d_members, ignored_label, d_graph_ptr, n_graphs,
+                                    reinterpret_cast<long long*>(d_counts), (hipStream_t)stream);
 }

@@ -623,6 +623,9 @@ int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st)
 // confusion[label][pred] for labels in [0, n_classes).  n_rows == 0 launches nothing.
 int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
                       int64_t ignored, long long* counts, long long* confusion, hipStream_t st);
+// the same rule per graph: counts[g] += {correct, total} over the rows [graph_ptr[g], graph_ptr[g + 1]) (int64 [n_graphs + 1])
+int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
+                               int64_t ignored, const int64_t* graph_ptr, int n_graphs, long long* counts, hipStream_t st);
 
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

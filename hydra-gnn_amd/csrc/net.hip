@@ -2146,6 +2146,23 @@ extern "C" int hmp_net_count_correct_rooms(hmp_net* n, const hmp_batch* batch, c
                            reinterpret_cast<long long*>(d_counts), reinterpret_cast<long long*>(d_confusion), st);
 }
 
+extern "C" int hmp_net_count_correct_rooms_by_graph(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
+                                                    int64_t ignored_label, int64_t* d_counts, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_counts, "hmp_net_count_correct_rooms_by_graph: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
+                "hmp_net_count_correct_rooms_by_graph: a two-headed net counts with hmp_net_count_correct2 / hmp_net_count_correct_heads");
+  HMP_CHECK_ARG(batch->n_out == 0 || batch->d_labels, "hmp_net_count_correct_rooms_by_graph: the batch has no labels");
+  const hmp_net_spec& S = n->spec;
+  const int ot = S.pool_edge_type >= 0 ? S.edge_dst[S.pool_edge_type] : S.readout_type;  // the node type of the output rows
+  HMP_CHECK_ARG(batch->n_out == 0 || (batch->n_graphs > 0 && batch->d_node_ptr[ot]),
+                "hmp_net_count_correct_rooms_by_graph: the batch carries no graph offsets of the output node type (n_graphs, d_node_ptr[%d])", ot);
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  Scope sc(n, KC_LOSS, st);
+  return count_rows_by_graph_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
+                                    batch->d_node_ptr[ot], batch->n_graphs, reinterpret_cast<long long*>(d_counts), st);
+}
+
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,
                                  const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && d_params && d_grads && d_m && d_v && args, "hmp_net_step_adam: null argument");

@@ -168,6 +168,7 @@ SIGNATURES = {
     "hmp_masked_ce": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_argmax_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
+    "hmp_count_correct_rows_by_graph": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
     "hmp_net_create": (C.c_int, [C.POINTER(NetSpec), C.POINTER(_VP)]),
@@ -191,6 +192,7 @@ SIGNATURES = {
                                            C.POINTER(TrainArgs), _VP]),
     "hmp_net_count_correct_heads": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP]),
     "hmp_net_count_correct_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I64, _VP, _VP, _VP]),
+    "hmp_net_count_correct_rooms_by_graph": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I64, _VP, _VP]),
     "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),
@@ -216,6 +218,7 @@ SIGNATURES = {
     "hmp_batchnorm_bwd": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP]),
     "hmp_collator_create": (C.c_int, [_I32, C.POINTER(_VP), _I64, _I32, C.POINTER(CollateItem), C.POINTER(_VP)]),
     "hmp_collator_run": (C.c_int, [_VP, _VP, _I32, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I64), _VP, _I32, _VP]),
+    "hmp_collator_set_label_filter": (C.c_int, [_VP, _I32, _VP, _I64]),
     "hmp_collator_destroy": (None, [_VP]),
     "hmp_htree_build": (C.c_int, [_I32, _I32, _VP, _I64, _VP, _I64, _VP, _I64, C.POINTER(_VP)]),
     "hmp_htree_sizes": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I64), C.POINTER(_I64)]),

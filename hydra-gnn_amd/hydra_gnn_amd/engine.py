@@ -549,22 +549,69 @@ class NativeNet:
             raise _lib.HydraMPError("count_correct_rooms: a two-headed net counts with count_correct / count_correct_heads")
         flat = self.flat_params(full_check=False)
         dev = flat.device
-        if isinstance(batch, _BatchHolder):
-            if labels is not None:
-                raise _lib.HydraMPError("count_correct_rooms: a stream batch brings its own labels (pass labels=None)")
-            h = batch
-        else:
-            if labels is None:
-                raise _lib.HydraMPError("count_correct_rooms: labels are required for a data batch")
-            h = self.make_batch(batch, labels)
-        if not h.c.d_labels and int(h.c.n_out) > 0:
-            raise _lib.HydraMPError("count_correct_rooms: the batch has no labels")
-        from .ops import check_count_buffers, row_members
+        h, members_ptr = self._room_batch("count_correct_rooms", batch, labels, members, ignored_label, dev)
+        from .ops import check_count_buffers
 
         check_count_buffers(counts, confusion, self.n_classes, dev)
+        self._count("hmp_net_count_correct_rooms", h, dev, flat.data_ptr(), members_ptr, int(ignored_label), counts.data_ptr(),
+                    confusion.data_ptr() if confusion is not None else None)
+        return counts
+
+    def _room_batch(self, what: str, batch, labels, members, ignored_label: int, dev):
+        """(descriptor, address of the row filter or None) of a room-task count on a data object with ``labels`` or on a stream
+        descriptor, which brings its labels and -- a stream of homogeneous graphs -- its ``room_mask`` rows and ignored label"""
+        if isinstance(batch, _BatchHolder):
+            if labels is not None:
+                raise _lib.HydraMPError(f"{what}: a stream batch brings its own labels (pass labels=None)")
+            h = batch
+            stream = h.stream
+            if stream is not None and getattr(stream, "homog_room", False):
+                if stream.nat is not self:
+                    raise _lib.HydraMPError(f"{what}: the batch comes from a stream created for another model")
+                if int(ignored_label) != stream.ignored_label:
+                    raise _lib.HydraMPError(f"{what}: ignored_label {ignored_label}, but the stream wrote its labels with ignored_label "
+                                            f"{stream.ignored_label} outside room_mask")
+                if members is None:
+                    return h, stream.members.data_ptr()
+        else:
+            if labels is None:
+                raise _lib.HydraMPError(f"{what}: labels are required for a data batch")
+            h = self.make_batch(batch, labels)
+        if not h.c.d_labels and int(h.c.n_out) > 0:
+            raise _lib.HydraMPError(f"{what}: the batch has no labels")
+        from .ops import row_members
+
         members = row_members(members, int(h.c.n_out), dev)
-        self._count("hmp_net_count_correct_rooms", h, dev, flat.data_ptr(), members.data_ptr() if members is not None else None,
-                    int(ignored_label), counts.data_ptr(), confusion.data_ptr() if confusion is not None else None)
+        return h, (members.data_ptr() if members is not None else None)
+
+    def count_correct_rooms_by_graph(self, batch, labels, counts: torch.Tensor, ignored_label: int = 25,
+                                     members: Optional[torch.Tensor] = None, graph_ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """:meth:`count_correct_rooms` per graph (``hmp_net_count_correct_rooms_by_graph``: one eval-mode forward, one count
+        launch): ADD {correct, total} of graph ``g`` of the batch to ``counts[g]`` (device int64 ``[n_graphs, 2]``).  A stream
+        descriptor brings the graphs' row offsets; a data batch needs ``graph_ptr``, the device int64 ``[n_graphs + 1]`` offsets of
+        the output rows (``Batch.ptr`` of their node type).  Nothing synchronises."""
+        if self.aux_readout is not None or self.heads is not None:
+            raise _lib.HydraMPError("count_correct_rooms_by_graph: a two-headed net counts with count_correct / count_correct_heads")
+        flat = self.flat_params(full_check=False)
+        dev = flat.device
+        h, members_ptr = self._room_batch("count_correct_rooms_by_graph", batch, labels, members, ignored_label, dev)
+        if not isinstance(batch, _BatchHolder):
+            from .ops import check_graph_ptr
+
+            check_graph_ptr(graph_ptr, int(h.c.n_out), dev)
+            ng = graph_ptr.numel() - 1
+            out_type = self.pool_edge_type[2] if self.pool_edge_type is not None else self.readout
+            if int(h.c.n_graphs) not in (0, ng):
+                raise _lib.HydraMPError(f"count_correct_rooms_by_graph: graph_ptr describes {ng} graphs, the batch {int(h.c.n_graphs)}")
+            # the offsets of the output rows alone: without edge offsets the plan build reads the batch as before
+            h.keep.append(graph_ptr)
+            h.c.d_node_ptr[self.node_types.index(out_type)] = graph_ptr.data_ptr()
+            h.c.n_graphs = ng
+        from .ops import check_graph_counts
+
+        check_graph_counts(counts, int(h.c.n_graphs), dev)
+        self._count("hmp_net_count_correct_rooms_by_graph", h, dev, flat.data_ptr(), members_ptr, int(ignored_label),
+                    counts.data_ptr())
         return counts
 
     def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
@@ -905,6 +952,10 @@ class TrainStep:
         if getattr(getattr(holder, "stream", None), "two_headed", False):
             raise _lib.HydraMPError("TrainStep.run: the batch comes from a two-headed stream (labels and masks of two heads); step it "
                                     "with the model's semisupervised_step().run")
+        want = getattr(getattr(holder, "stream", None), "ignored_label", None)  # a stream of homogeneous graphs wrote it into the labels
+        if want is not None and want != self.args.ignored_label:
+            raise _lib.HydraMPError(f"TrainStep.run: the step's ignored_label is {self.args.ignored_label}, the stream wrote its labels "
+                                    f"with ignored_label {want} outside room_mask")
         self._run(holder)
 
     def _run(self, holder: _BatchHolder) -> None:

@@ -15,10 +15,11 @@ Host reads per ``train()``: one after the loop plus the test pass's one; with ``
 per epoch on top.  ``verbose=True`` adds the reads its printing needs (a training-accuracy pass per epoch, a record read every ten
 epochs).  The executor's sticky input-data status word is not read inside ``train()``; ``net.native().check_status()`` reads it.
 
-Models the fused step does not cover keep a loop body of their own on ``store.collate`` batches, with the same bookkeeping:
-GCN / GIN run the reference's body (``net(batch)``, ``net.loss``, ``backward``, ``torch.optim.Adam``; their forward compacts rows
-with boolean masks and therefore synchronises inside torch); homogeneous GraphSAGE / GAT room classifiers run
-``train_step(...)(batch, labels)`` with the labels outside ``room_mask`` set to ``ignored_label``.
+Homogeneous room classifiers stream like the others: their stream writes the labels outside ``room_mask`` as ``ignored_label`` in
+the collation launch and carries ``room_mask`` as the row filter of the counts.  GCN / GIN, which the fused step does not cover,
+keep a loop body of their own on ``store.collate`` batches with the same bookkeeping: the reference's body (``net(batch)``,
+``net.loss``, ``backward``, ``torch.optim.Adam``; their forward compacts rows with boolean masks and therefore synchronises inside
+torch).
 
 Shuffling.  Epoch ``e``'s training order is what ``torch.utils.data.DataLoader(range(n), batch_size, shuffle=True)`` yields in its
 ``e``-th iteration, and that loader is the only consumer of torch's global generator inside ``train()``.  The validation and test
@@ -201,10 +202,14 @@ class BaseTrainingJob:
         return bool(getattr(self._net, "op_path", False))
 
     def _streams_batches(self) -> bool:
-        """the fused step runs on BatchStream batches: every heterogeneous model and every two-headed GraphSAGE / GAT model"""
-        return not self._op_path() and self._graph_type != "homogeneous"
+        """the fused step runs on BatchStream batches: every GraphSAGE / GAT / GAT_edge model, both tasks"""
+        return not self._op_path()
 
     def _label_type(self) -> str:
+        if self._graph_type == "homogeneous":
+            from .store import HOMO_NODE
+
+            return HOMO_NODE
         return "rooms" if self._network_type == "baseline" else "room_virtual"
 
     def _store(self, name, dataset, device):
@@ -226,7 +231,7 @@ class BaseTrainingJob:
         return cache[key]
 
     def _new_stream(self, store, batch_size):
-        return store.stream(self._net, batch_size, self._label_type())
+        return store.stream(self._net, batch_size, self._label_type(), ignored_label=self.ignored_label())
 
     def _state_tensors(self) -> List[torch.Tensor]:
         """what ``deepcopy(net.state_dict())`` holds: the flat parameter buffer of a native net (its named parameters are views of
@@ -238,7 +243,7 @@ class BaseTrainingJob:
             net.native().flat_params()  # re-homes pre_mp's parameters into their flat buffer before addresses are taken
         return [t for t in net.state_dict().values()]
 
-    # ---- the three loop bodies ---------------------------------------------------------------------------------------------
+    # ---- the loop bodies ---------------------------------------------------------------------------------------------------
     def _room_labels(self, batch) -> torch.Tensor:
         if self._graph_type == "homogeneous":
             return batch.y[batch.room_mask]
@@ -267,19 +272,9 @@ class BaseTrainingJob:
         def count_batch(split, ids, counts, confusion=None):
             net.count_correct_rooms(stores[split].collate(ids), counts, confusion, ignored)
 
-        if not self._op_path():
-            step = net.train_step(lr=lr, weight_decay=wd, ignored_label=ignored, use_graph=False)
-            tail = step.grads[net.native().n_active:]
-
-            def train_batch(ids, book):
-                b = stores["train"].collate(ids)
-                step(b, torch.where(b.room_mask, b.y, torch.full_like(b.y, ignored)))  # one label per row; non-room rows ignored
-                book.accumulate(tail, tail[1:])
-
-            return train_batch, count_batch, step.set_lr
         opt = torch.optim.Adam(net.parameters(), lr=lr, weight_decay=wd)
 
-        def train_batch(ids, book):
+        def train_batch(ids, book):  # GCN / GIN: the reference's body
             b = stores["train"].collate(ids)
             opt.zero_grad()
             pred = net(b)
@@ -420,17 +415,34 @@ class BaseTrainingJob:
         return evaluate.accuracy(net, (b.to(device) for b in data_loader), self.ignored_label(), get_per_label_accuracy)
 
     def test_individual_graph(self, dataset, model=None):
-        """``(correct, total)`` of every graph of ``dataset`` (:315-339), counted on the device and read once"""
+        """``(correct, total)`` of every graph of ``dataset`` (:315-339): the dataset is uploaded once (and kept, like the splits),
+        counted in ``batch_size`` batches with one forward and one per-graph count launch each
+        (``count_correct_rooms_per_graph``), and read once"""
         if model is not None:
             self._net = model
         net = self._net
         net.eval()
         device = next(net.parameters()).device
-        graphs = list(dataset)
-        counts = torch.zeros(max(len(graphs), 1), 2, dtype=torch.int64, device=device)
-        for i, data in enumerate(graphs):
-            net.count_correct_rooms(data.to(device), counts[i], None, self.ignored_label())
-        return [(int(c), int(t)) for c, t in counts[:len(graphs)].cpu().tolist()]
+        if not hasattr(dataset, "__getitem__"):
+            dataset = list(dataset)
+        n = len(dataset)
+        if n == 0:
+            return []
+        B = self._training_params["optimization_params"]["batch_size"]
+        ignored = self.ignored_label()
+        with torch.cuda.device(device):
+            counts = torch.zeros(n, 2, dtype=torch.int64, device=device)
+            if self._streams_batches():
+                stream = self._stream("individual", dataset, device, B)
+                for ids in id_chunks(n, B):
+                    net.count_correct_rooms_per_graph(stream.next(ids), counts[ids[0]:ids[-1] + 1], ignored)
+            else:  # GCN / GIN (homogeneous): a collated Data keeps no ptr, the node offsets come from the store's counts
+                store = self._store("individual", dataset, device)
+                nodes = torch.from_numpy(store.node_counts[store.node_types[0]])
+                for ids in id_chunks(n, B):
+                    ptr = torch.cat([torch.zeros(1, dtype=torch.int64), nodes[ids[0]:ids[-1] + 1].cumsum(0)]).to(device)
+                    net.count_correct_rooms_per_graph(store.collate(ids), counts[ids[0]:ids[-1] + 1], ignored, graph_ptr=ptr)
+            return [(int(c), int(t)) for c, t in counts.cpu().tolist()]  # the one synchronisation
 
 
 class SemiSupervisedTrainingJob(BaseTrainingJob):
@@ -461,9 +473,6 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
 
     def _loss_div(self) -> float:
         return float(len(self._dataset))  # total_loss /= len(data_loader.dataset) (:149)
-
-    def _streams_batches(self) -> bool:
-        return not self._op_path()
 
     def _new_stream(self, store, batch_size):
         return store.stream(self._net, batch_size)

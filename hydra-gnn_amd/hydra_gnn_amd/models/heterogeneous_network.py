@@ -100,6 +100,26 @@ class _NativeModule(nn.Module):
         net.count_correct_rooms(data, labels, acc, ignored_label, confusion=confusion)
         return acc if counts is not None else [int(v) for v in acc.tolist()]
 
+    def count_correct_rooms_per_graph(self, data, counts, ignored_label=25, graph_ptr=None):
+        """:meth:`count_correct_rooms` per graph (``BaseTrainingJob.test_individual_graph``, base_training_job.py:315-339, for a
+        whole batch): one eval-mode forward and one count launch (``hmp_net_count_correct_rooms_by_graph``) ADD {correct, total}
+        of the batch's graph ``g`` to ``counts[g]`` (device int64 ``[num_graphs, 2]``), which is returned without a sync.  A stream
+        descriptor brings labels and row offsets; a collated batch is read through ``ptr`` of the room labels' node type unless
+        ``graph_ptr`` (device int64 ``[num_graphs + 1]``) is given."""
+        from ..engine import _BatchHolder
+
+        self._room_task("count_correct_rooms_per_graph")
+        net = self.native()
+        if isinstance(data, _BatchHolder):
+            return net.count_correct_rooms_by_graph(data, None, counts, ignored_label)
+        store = data[self._ROOM_LABELS]
+        if graph_ptr is None:
+            graph_ptr = getattr(store, "ptr", None)
+            if graph_ptr is None:
+                raise _lib.HydraMPError(f"count_correct_rooms_per_graph: the batch has no '{self._ROOM_LABELS}'.ptr (collate it, or pass "
+                                        "graph_ptr=)")
+        return net.count_correct_rooms_by_graph(data, store.y, counts, ignored_label, graph_ptr=graph_ptr)
+
 
 def _hetero_layers(module, node_types):
     """LayerDesc list from ``module.convs`` (a ModuleList of HeteroConv containers)."""

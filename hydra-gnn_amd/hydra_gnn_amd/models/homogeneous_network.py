@@ -215,25 +215,59 @@ class HomogeneousNetwork(_NativeModule):
         ``ignored_label``.  The native output has a row per node, so ``data.room_mask`` is the kernel's row filter (no
         compaction).  SAGE / GAT: ``hmp_net_count_correct_rooms``; GCN / GIN: the op-by-op forward, then
         ``ops.count_correct_rows``.  With ``counts`` (device int64[2]) {correct, total} are ADDED to it without a sync; without,
-        returns the two ints of this batch.  ``confusion`` (device int64 [C, C]) receives ``[label, pred] += 1``."""
+        returns the two ints of this batch.  ``confusion`` (device int64 [C, C]) receives ``[label, pred] += 1``.  ``data`` may be
+        a descriptor from ``store.stream(model, B, label_type="node").next(ids)``, which brings the labels and the ``room_mask``
+        rows."""
+        from ..engine import _BatchHolder
+
         self._room_task("count_correct_rooms")
         acc = counts
+        if isinstance(data, _BatchHolder):  # store.BatchStream.next: labels and room_mask rows are the stream's
+            net = self.native()
+            if acc is None:
+                acc = torch.zeros(2, dtype=torch.int64, device=net.flat_params(full_check=False).device)
+            net.count_correct_rooms(data, None, acc, ignored_label, confusion=confusion)
+            return acc if counts is not None else [int(v) for v in acc.tolist()]
         if acc is None:
             acc = torch.zeros(2, dtype=torch.int64, device=data.x.device)
         if not self.op_path:
             self.native().count_correct_rooms(self._view(data), data.y, acc, ignored_label, members=data.room_mask,
                                               confusion=confusion)
         else:
-            was = self.training
-            self.train(False)
-            try:
-                with torch.no_grad():
-                    x = self._op_states(data)
-            finally:
-                if was:
-                    self.train(True)
-            ops.count_correct_rows(x, data.y, acc, ignored_label, members=data.room_mask, confusion=confusion)
+            ops.count_correct_rows(self._eval_states(data), data.y, acc, ignored_label, members=data.room_mask, confusion=confusion)
         return acc if counts is not None else [int(v) for v in acc.tolist()]
+
+    def _eval_states(self, data):
+        """GCN / GIN: the final states of an eval-mode op-by-op forward (the training flag is put back)"""
+        was = self.training
+        self.train(False)
+        try:
+            with torch.no_grad():
+                return self._op_states(data)
+        finally:
+            if was:
+                self.train(True)
+
+    def count_correct_rooms_per_graph(self, data, counts, ignored_label=25, graph_ptr=None):
+        """:meth:`count_correct_rooms` per graph (``BaseTrainingJob.test_individual_graph``, base_training_job.py:315-339, for a
+        whole batch): ADDS {correct, total} of the batch's graph ``g`` to ``counts[g]`` (device int64 ``[num_graphs, 2]``) with one
+        forward and one count launch, and returns it without a sync.  A stream descriptor brings labels, ``room_mask`` rows and
+        row offsets; a collated ``Data`` keeps no ``ptr``, so it needs ``graph_ptr`` (device int64 ``[num_graphs + 1]`` node
+        offsets).  SAGE / GAT: ``hmp_net_count_correct_rooms_by_graph``; GCN / GIN: the op-by-op forward, then
+        ``ops.count_correct_rows_by_graph``."""
+        from ..engine import _BatchHolder
+
+        self._room_task("count_correct_rooms_per_graph")
+        if isinstance(data, _BatchHolder):
+            return self.native().count_correct_rooms_by_graph(data, None, counts, ignored_label)
+        if graph_ptr is None:
+            raise HydraMPError("count_correct_rooms_per_graph: a homogeneous Data batch keeps no ptr: pass graph_ptr= (device int64 "
+                               "[num_graphs + 1] node offsets)")
+        if not self.op_path:
+            return self.native().count_correct_rooms_by_graph(self._view(data), data.y, counts, ignored_label, members=data.room_mask,
+                                                              graph_ptr=graph_ptr)
+        return ops.count_correct_rows_by_graph(self._eval_states(data), data.y, counts, graph_ptr, ignored_label,
+                                               members=data.room_mask)
 
     def predict(self, data):
         if self.classification_task != "room":

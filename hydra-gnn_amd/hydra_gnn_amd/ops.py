@@ -324,3 +324,46 @@ def count_correct_rows(logits: torch.Tensor, labels: torch.Tensor, counts: torch
                 members.data_ptr() if members is not None else None, int(ignored_label), counts.data_ptr(),
                 confusion.data_ptr() if confusion is not None else None, _lib.stream_ptr()))
     return counts
+
+
+def check_graph_ptr(graph_ptr, n_rows: int, device) -> None:
+    """the row offsets of a batch's graphs: a contiguous int64 ``[n_graphs + 1]`` tensor on ``device`` (``Batch.ptr``)"""
+    if (not isinstance(graph_ptr, torch.Tensor) or graph_ptr.dtype != torch.int64 or graph_ptr.dim() != 1 or graph_ptr.numel() < 1
+            or not graph_ptr.is_contiguous() or graph_ptr.device != device):
+        raise _lib.HydraMPError(f"graph_ptr must be a contiguous int64 [n_graphs + 1] tensor on {device} (the row offsets of the "
+                                "batch's graphs; a homogeneous Data batch carries none: pass graph_ptr=)")
+    if graph_ptr.numel() < 2 and n_rows > 0:
+        raise _lib.HydraMPError(f"graph_ptr describes no graph, the batch has {n_rows} rows")
+
+
+def check_graph_counts(counts, n_graphs: int, device) -> None:
+    if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.numel() != 2 * n_graphs or not counts.is_contiguous()
+            or counts.device != device):
+        raise _lib.HydraMPError(f"counts must be a contiguous int64 [{n_graphs}, 2] tensor on {device} ({{correct, total}} per graph)")
+
+
+def count_correct_rows_by_graph(logits: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, graph_ptr: torch.Tensor,
+                                ignored_label: int = 25, members: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`count_correct_rows` per graph (``hmp_count_correct_rows_by_graph``): the rows of graph ``g`` are
+    ``[graph_ptr[g], graph_ptr[g + 1])`` (device int64 ``[n_graphs + 1]``, ``graph_ptr[-1] == rows``); ADDS {correct, total} of
+    graph ``g`` to ``counts[g]`` (int64 ``[n_graphs, 2]``).  Returns ``counts``; nothing synchronises."""
+    _dev(logits, "logits")
+    logits = _rows(logits)
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise _lib.HydraMPError(f"logits must be [rows, classes >= 1], got {tuple(logits.shape)}")
+    n, n_classes = logits.size(0), logits.size(1)
+    dev = logits.device
+    if not isinstance(labels, torch.Tensor) or labels.device != dev or labels.numel() != n:
+        raise _lib.HydraMPError(f"labels must hold {n} entries on {dev}")
+    labels = labels.to(torch.int64).contiguous()
+    check_graph_ptr(graph_ptr, n, dev)
+    n_graphs = graph_ptr.numel() - 1
+    check_graph_counts(counts, n_graphs, dev)
+    members = row_members(members, n, dev)
+    if n:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hmp_count_correct_rows_by_graph(
+                logits.data_ptr(), logits.stride(0) if n > 1 else n_classes, n, n_classes, labels.data_ptr(),
+                members.data_ptr() if members is not None else None, int(ignored_label), graph_ptr.data_ptr(), n_graphs,
+                counts.data_ptr(), _lib.stream_ptr()))
+    return counts

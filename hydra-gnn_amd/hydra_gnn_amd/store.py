@@ -17,7 +17,8 @@ same way: bool / int8 rows (``train_mask`` / ``val_mask`` / ``test_mask`` / ``ro
 are and move through the byte branch of the same kernels, and a list of homogeneous :class:`hydra_gnn_amd.data.Data` graphs is
 stored under the names the homogeneous models present to the executor (node type ``node``; ``edge_index`` -> ``to``,
 ``pool_edge_index`` -> ``pool``, ``init_edge_index`` -> ``init``).  A stream created for a two-headed model carries the labels and
-masks of both heads in its own buffers (``tests/test_gpu_semisupervised_stream.py``).
+masks of both heads in its own buffers (``tests/test_gpu_semisupervised_stream.py``); a stream created for a homogeneous room
+classifier carries ``room_mask`` and the room-masked labels (``tests/test_gpu_homog_room_stream.py``).
 """
 from __future__ import annotations
 
@@ -250,11 +251,21 @@ class BatchStream:
             step.run(stream.next(ids), mask="train_mask")
         acc = evaluate.semisupervised_accuracy(model, (stream, id_lists), "val_mask")
 
+    Room task on a store of homogeneous graphs (a ``HomogeneousNetwork`` / ``HomogeneousNeuralTreeNetwork`` built with
+    ``output_dim``; ``label_type="node"``): the stream collates ``x``, the edge lists (and ``edge_attr``) the net reads, ``room_mask``
+    and ``y``, the latter as the labels the fused step reads -- ``room_mask ? y : ignored_label``, written by the same launch
+    (``hmp_collator_set_label_filter``).  ``stream.members`` is the collated ``room_mask``: the row filter of the counts.  A step or
+    a count with another ``ignored_label`` than the stream's is refused.
+
+        stream = store.stream(model, batch_size=64, label_type="node", ignored_label=25)
+        step = model.train_step(lr, ignored_label=25, use_graph=False)
+        step.run(stream.next(ids)); model.count_correct_rooms(stream.next(ids), counts)
+
     The buffers are reused by the next call: a batch is valid until then (same-stream ordering makes that safe for everything
     already enqueued).  ``stream.data()`` presents the current batch as a ``HeteroData`` of views for code that wants one."""
 
     def __init__(self, store: "GraphStore", net, batch_size: int, label_type: Optional[str] = None, label_key: str = "y",
-                 masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True):
+                 masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True, ignored_label: int = 25):
         import ctypes as C
 
         self.store, self.B = store, int(batch_size)
@@ -270,11 +281,31 @@ class BatchStream:
             raise _lib.HydraMPError("a two-headed model's stream carries the targets of both heads: pass no label_type")
         if not self.two_headed and label_type is None:
             raise _lib.HydraMPError("label_type is required: the node type whose labels the model's single output is trained on")
-        if not self.two_headed and store.homogeneous:
-            raise _lib.HydraMPError("a store of homogeneous graphs streams the two-headed task (a model built with output_dim_dict)")
+        # room task on homogeneous graphs: the net has an output row per node, so the stream carries `room_mask` (the rows that count)
+        # and the labels the fused step reads, room_mask ? y : ignored_label, written by the collation launch (the label filter)
+        self.homog_room = not self.two_headed and store.homogeneous
+        self.ignored_label = int(ignored_label) if self.homog_room else None
+        self.members = None
         self.mask_names = tuple(masks) if (self.two_headed and targets) else ()
         self._target_kind = None
         target_attrs: Dict[str, List[str]] = {}
+        if self.homog_room:
+            if getattr(net, "op_path", False):
+                raise _lib.HydraMPError(f"{net.conv_block} runs op by op: there is no fused step to stream batches to")
+            attrs = store.node_attrs[HOMO_NODE]
+            if "room_mask" not in attrs:
+                raise _lib.HydraMPError("the store holds no attribute 'room_mask' (the rows of the room task on homogeneous graphs)")
+            if attrs["room_mask"].data.dtype != torch.bool or attrs["room_mask"].row_shape != ():
+                raise _lib.HydraMPError(f"'room_mask' must be a bool vector (one entry per node), the store holds "
+                                        f"{attrs['room_mask'].row_shape} {attrs['room_mask'].data.dtype}")
+            if label_key not in attrs:
+                raise _lib.HydraMPError(f"the store holds no attribute '{label_key}' of node type '{HOMO_NODE}'")
+            if attrs[label_key].data.dtype != torch.int64 or attrs[label_key].row_shape != ():
+                raise _lib.HydraMPError(f"'{label_key}' must be an int64 vector (one label per node), the store holds "
+                                        f"{attrs[label_key].row_shape} {attrs[label_key].data.dtype}")
+            target_attrs[HOMO_NODE] = [label_key, "room_mask"]
+        # selective: the stream carries what the net reads plus its targets; otherwise every attribute the store holds
+        selective = self.two_headed or self.homog_room
         if self.two_headed and targets:
             if nat.heads is not None:  # learned linear heads over the rows of one node set
                 self._target_kind = "linear"
@@ -288,7 +319,7 @@ class BatchStream:
                 for t in self._label_types:
                     target_attrs[t] = [label_key] + list(self.mask_names)
         self._label_key = label_key
-        if self.two_headed:
+        if selective:
             used_nodes = set(nat.node_types) | set(target_attrs)
             node_types = [t for t in store.node_types if t in used_nodes]
             edge_types = [e for e in store.edge_types if e in nat.edge_types]
@@ -322,7 +353,7 @@ class BatchStream:
             self._what.append(("node", t, k))
 
         for t in node_types:
-            if self.two_headed:
+            if selective:
                 keys = (["x"] if nat.in_dims.get(t, 0) > 0 and t in nat.node_types else []) + target_attrs.get(t, [])
             else:
                 keys = list(store.node_attrs[t])
@@ -334,9 +365,9 @@ class BatchStream:
             items.append(it)
             self._bufs.append(torch.empty(2 * max(self.cap[slot_of[e]], 1), dtype=torch.int64, device=dev))
             self._what.append(("edge", e, "edge_index"))
-            if self.two_headed and not nat.edge_dims.get(e, 0):
+            if selective and not nat.edge_dims.get(e, 0):
                 continue
-            if self.two_headed and e not in store.edge_attr:
+            if selective and e not in store.edge_attr:
                 raise _lib.HydraMPError(f"the store holds no 'edge_attr' of edge type {e} (read by the model's GAT_edge convs)")
             if e in store.edge_attr:
                 pk = store.edge_attr[e]
@@ -350,6 +381,9 @@ class BatchStream:
         self._h = None
         _lib.check(lib.hmp_collator_create(len(slots), self._slot_ptr, store.n_graphs, n_items, self._items, C.byref(h)))
         self._h = h
+        if self.homog_room:  # the label item comes out as room_mask ? y : ignored_label
+            _lib.check(lib.hmp_collator_set_label_filter(h, self._what.index(("node", HOMO_NODE, label_key)),
+                                                         store.node_attrs[HOMO_NODE]["room_mask"].data.data_ptr(), self.ignored_label))
         self._dst = (C.c_void_p * n_items)(*[b.data_ptr() for b in self._bufs])
         self._caps = (C.c_int64 * n_items)(*[self.cap[it.slot] for it in items])
         self._totals = (C.c_int64 * len(slots))()
@@ -395,6 +429,8 @@ class BatchStream:
             if out_type != label_type:
                 raise _lib.HydraMPError(f"labels of '{label_type}' for a model that reads out '{out_type}'")
             self.label_buf = lab
+            if self.homog_room:  # the row filter of the counts: the collated room_mask (H-tree model included, reference :96-109)
+                self.members = buf_of[("node", HOMO_NODE, "room_mask")]
         else:
             for t, keys in target_attrs.items():
                 for k in keys:
@@ -502,8 +538,8 @@ class BatchStream:
 
 
 def _graphstore_stream(self, net, batch_size: int, label_type: Optional[str] = None, label_key: str = "y",
-                       masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True) -> BatchStream:
-    return BatchStream(self, net, batch_size, label_type, label_key, masks, targets)
+                       masks: Sequence[str] = DEFAULT_MASKS, targets: bool = True, ignored_label: int = 25) -> BatchStream:
+    return BatchStream(self, net, batch_size, label_type, label_key, masks, targets, ignored_label)
 
 
 GraphStore.stream = _graphstore_stream

@@ -37,7 +37,9 @@ extern "C" {
  *    hmp_gemm_desc (hmp_sizeof 10), hmp_gemm_grouped: unit-test entry of the grouped GEMM launchers;
  *    section 8: hmp_collate_rows / hmp_collate_item::row_bytes accept any positive row size (byte-wide bool / int8 masks of the
  *    two-headed task ride in the same launch); the one-launch collator holds 40 items (was 24) and carries 264 table words in the
- *    argument block (was 336).  No struct changed layout, no entry was added */
+ *    argument block (was 336).  No struct changed layout, no entry was added;
+ *    hmp_collator_set_label_filter (room-masked labels in the collation launch), hmp_count_correct_rows_by_graph /
+ *    hmp_net_count_correct_rooms_by_graph (per-graph validation counts): new entries, no struct changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -217,6 +219,15 @@ int hmp_argmax_rows(const float* d_x, int32_t ldx, int32_t n_rows, int32_t n_col
  * false) and never to the matrix.  One launch; n_rows == 0 launches nothing; nothing synchronises. */
 int hmp_count_correct_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
                            const uint8_t* d_members, int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream);
+/* the same count per graph (BaseTrainingJob.test_individual_graph, base_training_job.py:315-339, for a whole batch): the rows of
+ * graph g are [d_graph_ptr[g], d_graph_ptr[g + 1]) (device int64 [n_graphs + 1], non-decreasing, d_graph_ptr[n_graphs] == n_rows:
+ * [PyG] Batch.ptr of the rows' node type); a row counts under hmp_count_correct_rows's rule and ACCUMULATES into
+ * d_counts[g] = {correct, total} (device int64 [n_graphs][2]).  A graph without counted rows (empty, or every label ignored)
+ * receives nothing.  No confusion matrix.  One launch; n_rows == 0 launches nothing; nothing synchronises.  (ABI-4-compatible
+ * addition, like the two entries marked so below.) */
+int hmp_count_correct_rows_by_graph(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
+                                    const uint8_t* d_members, int64_t ignored_label, const int64_t* d_graph_ptr, int32_t n_graphs,
+                                    int64_t* d_counts, void* stream);
 /* d_count: device float holding the valid-label count (grad_scale = 1/max(count,1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
@@ -444,6 +455,13 @@ int hmp_net_count_correct_heads(hmp_net* net, const hmp_batch* batch, const hmp_
  * hmp_net_count_correct_heads) are refused.  The activations of the last forward are overwritten; nothing synchronises. */
 int hmp_net_count_correct_rooms(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
                                 int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream);
+/* The same per graph: ONE eval-mode forward, then ONE hmp_count_correct_rows_by_graph launch on the program's output.  The graph of
+ * an output row comes from the batch itself: batch->n_graphs and batch->d_node_ptr[t] of the output node type t (the pool edge
+ * type's destination, else the readout type), which must be set (HMP_E_ARG otherwise; d_edge_ptr is not needed).  ACCUMULATES
+ * into d_counts (device int64 [n_graphs][2] = {correct, total} per graph).  Refusals and side effects as
+ * hmp_net_count_correct_rooms.  (ABI-4-compatible addition.) */
+int hmp_net_count_correct_rooms_by_graph(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
+                                         int64_t ignored_label, int64_t* d_counts, void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
@@ -520,6 +538,14 @@ int hmp_collator_create(int32_t n_slots, const int64_t* const* h_slot_ptr, int64
 int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B, void* const* d_dst, const int64_t* dst_capacity,
                      int64_t* h_totals, int64_t* d_offsets_out /* NULL or [n_slots][offsets_stride]: Batch.ptr of every slot */,
                      int32_t offsets_stride, void* stream);
+/* Label filter of the room task on homogeneous graphs (ABI-4-compatible addition: hmp_collate_item keeps its layout).  The fused
+ * step reads one int64 label per output row and a homogeneous net has a row per node, so the labels it needs are
+ * room_mask[row] ? y[row] : ignored_label.  After this call, item `label_item` (row_bytes == 8: int64 labels) is written by the
+ * same launch as  d_member_src[r] != 0 ? src[r] : ignored_label,  r = the row's position in the packed source: d_member_src
+ * is the dataset's packed one-byte mask (device), indexed by the per-graph offsets of the label item.  Holds for every later
+ * hmp_collator_run, whichever way its tables travel; label_item < 0 clears it.  Host-only: no device call.  HMP_E_ARG for an index
+ * outside the items, an item whose rows are not 8 bytes (or not 8-byte aligned) and a null mask. */
+int hmp_collator_set_label_filter(hmp_collator* c, int32_t label_item, const uint8_t* d_member_src, int64_t ignored_label);
 void hmp_collator_destroy(hmp_collator* c);
 
 /* ---------------------------------------------------------------------------------------------

@@ -6,12 +6,15 @@
   job   hydra_gnn_amd.jobs: BaseTrainingJob.train / SemiSupervisedTrainingJob.train (bookkeeping on the device, csrc/epoch.hip);
         the module is imported in this mode only, so `--mode hand` runs on commits that do not have it
 
-on two shapes:
+on three shapes:
 
   room  MP3D-like room task at config-2 shapes: 384 train / 96 val / 32 test graphs, batch 32, 3 x HeteroConv(SAGE), hidden 64
   semi  the Stanford-like two-headed task of tools/semisup_epoch.py: 384 homogeneous graphs, batch 32, GraphSAGE, hidden 64
+  homog_room  (job mode only) the room task on Stanford-like homogeneous graphs, BASELINE config 1's model family: 384 train / 96
+        val / 32 test graphs, batch 32, GraphSAGE, hidden 64; followed by one line for `job.test_individual_graph` on 64 graphs
+        (ms per call, `--repeats` calls after one untimed call)
 
-    python tools/train_job.py [--mode hand|job|both] [--shape room|semi|both] [--epochs 50] [--warmup 5] [--repeats 5]
+    python tools/train_job.py [--mode hand|job|both] [--shape room|semi|homog_room|both] [--epochs 50] [--warmup 5] [--repeats 5]
 
 Each repeat trains `warmup` epochs untimed, then times `epochs` epochs (wall clock around the loop, device synchronised at both
 ends).  One JSON line per (shape, mode): ms per epoch of every repeat, their median, minimum and spread.  Under
@@ -52,6 +55,16 @@ def semi_graphs():
         u = torch.from_numpy(rng.random(g.num_nodes))
         g.train_mask, g.val_mask, g.test_mask = u < 0.6, (u >= 0.6) & (u < 0.8), u >= 0.8
     return gs
+
+
+def homog_room_graphs():
+    """Stanford-like graphs (one room each) whose room label follows the room's size feature, three of the 15 classes: random labels
+    can leave every validation room wrong, and a run without an improvement has no best state"""
+    rng = np.random.Generator(np.random.PCG64(workloads.BASE_SEED + 91))
+    gs = [workloads.stanford_like_graph(rng) for _ in range(384 + 96 + 32)]
+    for g in gs:
+        g.y[0] = min(int((float(g.x[0, 3]) - 0.1) / 2.9 * 3), 2)
+    return {"train": gs[:384], "val": gs[384:480], "test": gs[480:]}
 
 
 def chunks(n):
@@ -162,6 +175,9 @@ def job_loop(shape, args, dev):
     if shape == "room":
         info = _Info({"objects": 306, "rooms": 6}, 26)
         job = jobs.BaseTrainingJob({s: _Dataset("heterogeneous", g, info) for s, g in room_graphs().items()}, params)
+    elif shape == "homog_room":
+        split = homog_room_graphs()
+        job = jobs.BaseTrainingJob({s: _Dataset("homogeneous", g, _Info(6, 15)) for s, g in split.items()}, params)
     else:
         job = jobs.SemiSupervisedTrainingJob(_Dataset("homogeneous", semi_graphs(), _Info(6, 15, 35)), params)
     opt = {"lr": LR, "weight_decay": WD, "batch_size": B, "shuffle": True}
@@ -171,20 +187,32 @@ def job_loop(shape, args, dev):
             job.train(log_folder, dict(opt, num_epochs=max(args.warmup, 1)))
             _, _, info = job.train(log_folder, dict(opt, num_epochs=args.epochs))
             times.append(1e3 * info["training_time"] / info["num_epochs"])
+    if shape == "homog_room":
+        dataset = _Dataset("homogeneous", (split["val"] + split["test"])[:64], _Info(6, 15))
+        job.test_individual_graph(dataset)
+        calls = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            job.test_individual_graph(dataset)
+            calls.append(1e3 * (time.perf_counter() - t0))
+        print(json.dumps({"shape": shape, "what": "test_individual_graph", "graphs": len(dataset), "batch_size": B,
+                          "ms_per_call": [round(t, 3) for t in calls], "median_ms": round(float(np.median(calls)), 3),
+                          "min_ms": round(min(calls), 3), "spread_ms": round(max(calls) - min(calls), 3)}), flush=True)
     return times
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="both", choices=["hand", "job", "both"])
-    ap.add_argument("--shape", default="both", choices=["room", "semi", "both"])
+    ap.add_argument("--shape", default="both", choices=["room", "semi", "homog_room", "both"])
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     for shape in (("room", "semi") if args.shape == "both" else (args.shape,)):
-        for mode in (("hand", "job") if args.mode == "both" else (args.mode,)):
+        for mode in (("hand", "job") if args.mode == "both" and shape != "homog_room" else ("job",) if shape == "homog_room" else (args.mode,)):
             times = (hand_loop if mode == "hand" else job_loop)(shape, args, dev)
             print(json.dumps({"shape": shape, "mode": mode, "epochs": args.epochs, "batch_size": B,
                               "ms_per_epoch": [round(t, 3) for t in times], "median_ms": round(float(np.median(times)), 3),
