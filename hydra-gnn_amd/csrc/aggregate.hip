@@ -11,7 +11,7 @@
 // HBM/L2 traffic per row: deg * F * 4 bytes of source rows + 4*deg + 8 bytes of indices + F*4 out.
 #include <type_traits>
 
-#include "kernels.h"
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -287,20 +287,12 @@ __global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const float* __re
 }
 
 // ----- fused SAGE layer aggregation -----------------------------------------------------------------
-// t = dropout(act(t)) for the lane's columns [c, c + 4) of row `row` of entry D (dcfg: D.drop with the step resolved)
-__device__ __forceinline__ void act_drop4(const AggDst& D, const DropCfg& dcfg, int row, int c, Acc<4>& t) {
+// t = dropout(act(t)) for the lane's columns [c, c + 4) of row `row` of entry D (dcfg: D.drop with the step resolved); keep-mask
+// quad row * (ldo / 4) + c / 4
+__device__ __forceinline__ void agg_act_drop4(const AggDst& D, const DropCfg& dcfg, int row, int c, Acc<4>& t) {
   bool keep[4] = {true, true, true, true};
   if (D.drop_on) drop_keep4(dcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(c >> 2), keep);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float v = t.at(i);
-    if (D.act == HMP_ACT_RELU) v = v > 0.f ? v : 0.f;
-    else if (D.act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-    // a dropped element is stored as -0.0f (a kept one that happens to be zero as +0.0f): numerically both are 0 for
-    // every consumer, and the backward pass reads the keep bit off the sign instead of regenerating the draws
-    if (D.drop_on) v = keep[i] ? (v * D.drop.scale + 0.0f) : -0.0f;  // "+ 0.0f": a kept -0.0 becomes +0.0
-    t.at(i) = v;
-  }
+  act_drop4(&t.at(0), D.act, D.drop_on != 0, keep, D.drop.scale);
 }
 
 // out[t][i] = dropout(act( zroot[i] + bias + sum_e mean_{k in N_e(i)} z_e[col_k] ))   (one row group, result also in `tot`)
@@ -423,58 +415,30 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
   for (int q = 0; q < NV; ++q) {
     const int c = c0 + q * GS * VEC;
     if (c >= D.F) continue;
-    act_drop4(D, dcfg, row, c, tot[q]);
+    agg_act_drop4(D, dcfg, row, c, tot[q]);
     if constexpr (HB && VEC == 4) store_z<true>(tot[q], D.out, (int64_t)row * D.ldo + c);
     else tot[q].store(D.out + (int64_t)row * D.ldo + c);
   }
 }
 
-// Masked cross entropy of one output row held by its row group (lane = 4 consecutive logits): models/utils.py:143-148
-// with mask = label != ignored; writes the gradient of the SUM loss and the row's {loss, valid} pair.  The group
-// reductions are xor butterflies below GS, i.e. inside the (GS-aligned) row group.
+// Masked cross entropy of the output row its row group has just computed (lane = 4 consecutive logits in `t`): ce_group over
+// the registers, the gradient chained back to z where the CE read y = dropout(act(z)).
 template <int GS>
 __device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, int row, int c0, Acc<4>& t, int64_t y, bool in_mask) {
-  const int nc = D.ce_classes;
-  float v[4];
-  bool in[4];
-  float m = -INFINITY;
+  ce_group<GS, 1>(
+      c0 >> 2, D.ce_classes, D.ce_ldg, y, D.ce_ignored, in_mask,
+      [&](int, int, float (&v)[4]) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    in[i] = c0 + i < nc;
-    v[i] = in[i] ? t.at(i) : -INFINITY;
-    m = fmaxf(m, v[i]);
-  }
+        for (int i = 0; i < 4; ++i) v[i] = t.at(i);
+      },
+      [&](int c, float (&g)[4], const float (&)[4]) {
+        if (D.ce_tail) {  // act' from y, as the hidden layers' backward does
 #pragma unroll
-  for (int o = GS / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) s += in[i] ? expf(v[i] - m) : 0.f;
-#pragma unroll
-  for (int o = GS / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float lse = m + logf(s);
-  const bool valid = in_mask && (y != D.ce_ignored);
-  const bool bad = valid && (y < 0 || y >= nc);
-  const bool use = valid && !bad;
-  float ly = 0.f;
-  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bool hit = use && (int64_t)(c0 + i) == y;
-    if (hit) ly = v[i];
-    if (use && in[i]) (&g.x)[i] = expf(v[i] - lse) - (hit ? 1.f : 0.f);
-  }
-  if (D.ce_tail) {  // y = dropout(act(z)) is what the CE read: chain back to z (act' from y, as the hidden layers' backward does)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) (&g.x)[i] *= tail_dydz(t.at(i), D.act, D.drop_on != 0, D.drop.scale);
-  }
-#pragma unroll
-  for (int o = GS / 2; o > 0; o >>= 1) ly += __shfl_xor(ly, o);
-  if (c0 < D.ce_ldg) *reinterpret_cast<float4*>(D.ce_grad + (int64_t)row * D.ce_ldg + c0) = g;
-  if ((threadIdx.x % GS) == 0) {
-    D.ce_row_lv[2 * row] = use ? (lse - ly) : 0.f;
-    D.ce_row_lv[2 * row + 1] = use ? 1.f : 0.f;
-    if (bad && state) atomicOr(&state->status, 2);
-  }
+          for (int i = 0; i < 4; ++i) g[i] *= tail_dydz(t.at(i), D.act, D.drop_on != 0, D.drop.scale);
+        }
+        *reinterpret_cast<float4*>(D.ce_grad + (int64_t)row * D.ce_ldg + c) = make_float4(g[0], g[1], g[2], g[3]);
+      },
+      D.ce_row_lv, row, state);
 }
 
 template <int GS, int NV, bool ZB = false, bool HB = false>
@@ -1247,7 +1211,7 @@ __global__ __launch_bounds__(WIN_THREADS) void agg_fwd_win_kernel(const WinFwd a
           tot.add_div(acc, a.mean ? (float)(e - b) : 1.f);
         }
         KT_ADD(29, kt_r);
-        act_drop4(D, dcfg, row, c0, tot);
+        agg_act_drop4(D, dcfg, row, c0, tot);
         store_z<HB>(tot, D.out, (int64_t)row * D.ldo + c0);
         KT_ADD(30, kt_r);
         idw = idw_n;

@@ -4,11 +4,11 @@
 //   counts += {#(pred == label), #rows};  confusion[label][pred] += 1 for counted rows with label in [0, n_classes).
 //
 // A row belongs to a group of 16 lanes (argmax_rows_kernel's grouping, optim.hip).  With ld % 4 == 0 and a 16-byte aligned base,
-// lane i owns the quads i, i + 16, ... of the row (16-byte loads); otherwise lane i owns the columns i, i + 16, ...  Both walk
-// their columns in ascending order and keep the first maximum, and the group reduction breaks ties by the lower index, so the
-// prediction is argmax_rows_kernel's (and torch.argmax's on finite logits) whatever the layout.
+// lane i owns the quads i, i + 16, ... of the row (16-byte loads); otherwise lane i owns the columns i, i + 16, ...  Both are
+// walks of the one first-maximum argmax (tail_fns.h), so the prediction is argmax_rows_kernel's (and torch.argmax's on finite
+// logits) whatever the layout.
 //
-// Per-workgroup counters live in LDS; each workgroup adds its non-zero counters to the int64 outputs with one 64-bit atomic each.
+// Per-workgroup counters live in LDS (tail_fns.h: count_begin / count_row / count_flush).
 // For n_classes <= EV_HIST_MAX the confusion matrix is an LDS histogram too (<= 16 KB of int32), above that rows add to the global
 // matrix directly.  Everything is ACCUMULATED (+=): a validation pass sums its batches on the device and reads the totals once.
 //
@@ -18,6 +18,7 @@
 // 16 rows of a workgroup pass are consecutive, so they span few graphs: rows are staged in LDS and the first row of each run of
 // equal graphs adds the run's sums with two 64-bit atomics.
 #include "device_fns.h"  // find_seg
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -27,35 +28,20 @@ constexpr int EV_GS = 16;               // lanes per row
 constexpr int EV_RPB = 256 / EV_GS;     // rows per workgroup and pass
 constexpr int EV_HIST_MAX = 64;         // largest class count with an LDS confusion histogram
 constexpr int EV_MAX_BLOCKS = 1024;     // grid cap: larger inputs stride over rows (fewer histogram flushes)
-constexpr int EV_NONE = 0x7fffffff;
 
-__device__ __forceinline__ void ev_take(float v, int c, float& best, int& arg) {
-  if (v > best || arg == EV_NONE) { best = v; arg = c; }
-}
-
-// the row's prediction by its 16 lanes (both column walks keep the first maximum, the reduction breaks ties by the lower index)
+// the row's prediction by its 16 lanes
 template <bool VEC>
 __device__ __forceinline__ int ev_argmax(const float* __restrict__ xr, int n_classes, int lane) {
-  float best = -INFINITY;
-  int arg = EV_NONE;
-  if (VEC) {
-    for (int c = lane * 4; c < n_classes; c += EV_GS * 4) {
-      const float4 v = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
-      ev_take(v.x, c, best, arg);
-      if (c + 1 < n_classes) ev_take(v.y, c + 1, best, arg);
-      if (c + 2 < n_classes) ev_take(v.z, c + 2, best, arg);
-      if (c + 3 < n_classes) ev_take(v.w, c + 3, best, arg);
-    }
-  } else {
-    for (int c = lane; c < n_classes; c += EV_GS) ev_take(xr[c], c, best, arg);
+  if (!VEC) {  // lane i owns the columns i, i + 16, ...
+    float best = -INFINITY;
+    int arg = ARGMAX_NONE;
+    for (int c = lane; c < n_classes; c += EV_GS) argmax_take(xr[c], c, best, arg);
+    return argmax_reduce<EV_GS>(best, arg);
   }
-#pragma unroll
-  for (int o = EV_GS / 2; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, EV_GS);
-    const int oa = __shfl_xor(arg, o, EV_GS);
-    if (oa != EV_NONE && (arg == EV_NONE || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-  }
-  return arg == EV_NONE ? 0 : arg;
+  return argmax_group<EV_GS, 0>(lane, n_classes, [&](int, int c, float (&v)[4]) {
+    const float4 x4 = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
+    v[0] = x4.x; v[1] = x4.y; v[2] = x4.z; v[3] = x4.w;
+  });
 }
 
 template <bool VEC, bool HIST>
@@ -67,8 +53,7 @@ __global__ __launch_bounds__(256) void count_rows_kernel(const float* __restrict
   __shared__ int s_hist[HIST ? EV_HIST_MAX * EV_HIST_MAX : 1];
   const int cc = HIST ? n_classes * n_classes : 0;
   for (int i = threadIdx.x; i < cc; i += 256) s_hist[i] = 0;
-  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-  __syncthreads();
+  count_begin(s_cnt);
   const int lane = threadIdx.x % EV_GS;
   for (int row = blockIdx.x * EV_RPB + (int)threadIdx.x / EV_GS; row < n_rows; row += gridDim.x * EV_RPB) {
     // the whole group of 16 lanes takes the same branch: the shuffles below stay inside active groups
@@ -76,17 +61,15 @@ __global__ __launch_bounds__(256) void count_rows_kernel(const float* __restrict
     if ((members && !members[row]) || y == ignored) continue;
     const int pred = ev_argmax<VEC>(x + (int64_t)row * ld, n_classes, lane);
     if (lane == 0) {
-      atomicAdd(&s_cnt[1], 1);
-      // a label outside [0, n_classes) is never predicted: it counts in the total only (pred.eq(label) is false)
+      // pred is always inside [0, n_classes), so a label outside it never equals pred: it counts in the total only
+      count_row(s_cnt, (int64_t)pred == y);
       if (y >= 0 && y < n_classes) {
-        if (pred == (int)y) atomicAdd(&s_cnt[0], 1);
         if (HIST) atomicAdd(&s_hist[(int)y * n_classes + pred], 1);
         else if (confusion) atomicAdd(&confusion[y * n_classes + pred], 1ull);
       }
     }
   }
-  __syncthreads();
-  if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+  count_flush(s_cnt, counts);
   for (int i = threadIdx.x; i < cc; i += 256)
     if (s_hist[i]) atomicAdd(&confusion[i], (unsigned long long)s_hist[i]);
 }

@@ -19,7 +19,7 @@
 //
 // No atomics: backward pass 1 runs destination-major (d logits, d a_dst), pass 2 source-major over the CSC lists
 // (d h_s, d a_src) reading what pass 1 stored per edge.
-#include "kernels.h"
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -81,12 +81,6 @@ __device__ __forceinline__ void alpha_keep(const DropCfg& cfg, int64_t pos, bool
 #pragma unroll
     for (int h = 4; h < HM; ++h) keep[h] = k4[h - 4];
   }
-}
-
-__device__ __forceinline__ float act_apply(float v, int act) {
-  if (act == HMP_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == HMP_ACT_ELU) return v > 0.f ? v : expm1f(v);
-  return v;
 }
 
 // raw (pre-leaky) logits of one neighbour for all heads.  `ea` is uniform (null: the conv has no edge attributes); `use`
@@ -268,17 +262,13 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
   if (!cact) return;
 
   const bool fdrop = dyn.training && D.drop_p > 0.f;
-  DropCfg fcfg;
+  DropCfg fcfg = {};
   if (fdrop) fcfg = make_cfg(dyn, D.drop_p, D.drop_stream);
   auto finish = [&](float v, int col) -> float {
     v = (v + (D.bias ? glob(D.bias)[col] : 0.f)) * D.group_scale;
-    v = act_apply(v, D.act);
-    if (fdrop) {
-      bool k4[4];
-      drop_keep4(fcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(col >> 2), k4);
-      v = k4[col & 3] ? (v * fcfg.scale + 0.0f) : -0.0f;  // dropped: -0.0f (sign bit = "dropped", see gemm.hip epilogue)
-    }
-    return v;
+    bool k4[4] = {true, true, true, true};
+    if (fdrop) drop_keep4(fcfg, (uint32_t)row * (uint32_t)(D.ldo >> 2) + (uint32_t)(col >> 2), k4);
+    return act_drop(v, D.act, fdrop, k4[col & 3], fcfg.scale);
   };
   auto orow = globw(D.out) + (int64_t)row * D.ldo;
   if (D.concat) {

@@ -12,7 +12,7 @@
 //   pass 2  per F chunk: dz = dlogits @ W . keep/(1-p) . act'  -> the output gradient, and dW += dlogits^T y into the
 //           workgroup's own slab (db once per tile).  No float atomics: the slabs are summed in a fixed order by the
 //           gradient un-pack (grad_reduce_kernel), which sees the heads as four more parameter segments.
-#include "kernels.h"
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -50,14 +50,7 @@ __device__ void stage_y(const LinHeadArgs& a, const DropCfg& cfg, int row0, int 
       bool keep[4] = {true, true, true, true};
       if (a.drop_on) drop_keep4(cfg, (uint32_t)row * (uint32_t)qpr + (uint32_t)(c >> 2), keep);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float x = (&z4.x)[i];
-        if (a.act == HMP_ACT_RELU) x = fmaxf(x, 0.f);
-        else if (a.act == HMP_ACT_ELU) x = x > 0.f ? x : expm1f(x);
-        if (a.drop_on) x = keep[i] ? (x * cfg.scale + 0.0f) : -0.0f;
-        else if (a.act != HMP_ACT_NONE) x = x + 0.0f;
-        v[i] = c + i < a.F ? x : 0.f;
-      }
+      for (int i = 0; i < 4; ++i) v[i] = c + i < a.F ? act_drop((&z4.x)[i], a.act, a.drop_on != 0, keep[i], cfg.scale) : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) s.ys[r][4 * cq + i] = v[i];

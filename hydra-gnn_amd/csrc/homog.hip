@@ -12,7 +12,7 @@
 //         ([PyG] gcn_norm with add_remaining_self_loops: existing loops are replaced by exactly one loop of weight 1)
 //   GIN:  out_i = sum_{j->i} z_j + (1 + eps) z_i
 // The transposed operator (gradient w.r.t. z) has the same form on the CSC lists, so one kernel serves both directions.
-#include "common.h"
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -66,8 +66,8 @@ __global__ __launch_bounds__(256) void gcn_norm_kernel(const int* __restrict__ r
 }
 
 // y = dropout(act(x + bias)), act = HMP_ACT_NONE / RELU / ELU; the keep-mask is the engine's (hmp_dropout_mask replays it: element
-// (row, col) of an [n, F] tensor).  A dropped element is stored as -0.0f, a kept zero as +0.0f (the engine's convention), so the
-// backward reads everything it needs off y.
+// (row, col) of an [n, F] tensor), the arithmetic and the sign-of-zero rule act_drop's (tail_fns.h), so the backward reads
+// everything it needs off y.
 __global__ __launch_bounds__(256) void bias_act_drop_kernel(const float* __restrict__ x, int ldx, int n, int F,
                                                             const float* __restrict__ bias, int act, int drop_on, DropCfg cfg,
                                                             float* __restrict__ y, int ldy) {
@@ -80,12 +80,8 @@ __global__ __launch_bounds__(256) void bias_act_drop_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (c + i >= F) continue;
-      float v = x[(int64_t)row * ldx + c + i] + (bias ? bias[c + i] : 0.f);
-      if (act == HMP_ACT_RELU) v = fmaxf(v, 0.f);
-      else if (act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-      if (drop_on) v = keep[i] ? (v * cfg.scale + 0.0f) : -0.0f;
-      else if (act != HMP_ACT_NONE) v = v + 0.0f;  // a kept -0.0 becomes +0.0: the sign of zero is reserved for "dropped"
-      y[(int64_t)row * ldy + c + i] = v;
+      const float v = x[(int64_t)row * ldx + c + i] + (bias ? bias[c + i] : 0.f);
+      y[(int64_t)row * ldy + c + i] = act_drop(v, act, drop_on != 0, keep[i], cfg.scale);
     }
   }
 }

@@ -1,5 +1,6 @@
 // Loss, optimiser and the parameter <-> packed-operand shuffles around the layer kernels.
 #include "device_fns.h"
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -93,27 +94,19 @@ int masked_ce_rows_launch(const float* logits, int ldl, int n_rows, int n_classe
 }
 
 // ---------------------------------------------------------------------------------------------
-// row argmax: the `.argmax(dim=1)` of the inference server (bin/room_classification_server:286); 16 lanes per row, first
-// maximum wins (torch's tie rule for distinct positions), labels as int64 so the buffer can be handed to the caller as is
+// row argmax: the `.argmax(dim=1)` of the inference server (bin/room_classification_server:286); 16 lanes per row, the
+// first-maximum rule of tail_fns.h, labels as int64 so the buffer can be handed to the caller as is
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int ld, int n_rows, int n_cols,
                                                           int64_t* __restrict__ out) {
   const int row = blockIdx.x * 16 + ((int)threadIdx.x >> 4);
   const int lane = threadIdx.x & 15;
   float best = -INFINITY;
-  int arg = 0x7fffffff;
-  if (row < n_rows)
-    for (int c = lane; c < n_cols; c += 16) {
-      const float v = x[(int64_t)row * ld + c];
-      if (v > best || arg == 0x7fffffff) { best = v; arg = c; }
-    }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 16);
-    const int oa = __shfl_xor(arg, o, 16);
-    if (oa != 0x7fffffff && (arg == 0x7fffffff || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-  }
-  if (row < n_rows && lane == 0) out[row] = arg == 0x7fffffff ? 0 : arg;
+  int arg = ARGMAX_NONE;
+  if (row < n_rows)  // rows past the end walk no column: every lane of the wavefront reaches the group's shuffles
+    for (int c = lane; c < n_cols; c += 16) argmax_take(x[(int64_t)row * ld + c], c, best, arg);
+  arg = argmax_reduce<16>(best, arg);
+  if (row < n_rows && lane == 0) out[row] = arg;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,8 +1,11 @@
 // Tail of the two-headed (room + object) task: SemiSupervisedTrainingJob's loss (semisupervised_training_job.py:117-147) and
 // the per-batch arithmetic of its test() (:198-257), for the node types whose last aggregation epilogue did not already serve them
 // (GAT layers, wide outputs, the large-batch launch sequence).  Both heads are rows of ONE launch; a row belongs to a group of 16
-// lanes, lane i owns the quads i, i + 16, ... of the row (classes <= 64: one quad per lane).
-#include "kernels.h"
+// lanes, lane i owns the quads i, i + 16, ... of the row (classes <= 64: one quad per lane).  The arithmetic of a row -- the
+// activation and dropout, the masked CE and its association, the first-maximum argmax, the workgroup counters -- is tail_fns.h's;
+// this file owns the row sources (a leaf row of the final state, a LeafPool mean of leaf rows), their keep-mask numbering and
+// the launches.
+#include "tail_fns.h"
 
 namespace hmp {
 
@@ -11,120 +14,36 @@ namespace {
 constexpr int TL_GS = 16;
 constexpr int TL_RPB = 256 / TL_GS;
 
-// y = dropout(act(z)) of elements c .. c+3 (c % 4 == 0, c < classes) of `row`; the same arithmetic and keep-mask numbering as
-// bias_act_drop_kernel (homog.hip): quad row * ceil(classes / 4) + c / 4
-__device__ __forceinline__ void tail_quad(const HeadTail& T, const DropCfg& cfg, int act, int row, int c, float (&y)[4], bool (&in)[4]) {
+// y = dropout(act(z)) of elements c .. c+3 (c % 4 == 0, c < classes) of `row`; the keep-mask numbering of bias_act_drop_kernel
+// (homog.hip): quad row * ceil(classes / 4) + c / 4.  Elements at or past `classes` hold padding: callers skip them.
+__device__ __forceinline__ void tail_quad(const HeadTail& T, const DropCfg& cfg, int act, int row, int c, float (&y)[4]) {
   const float4 z4 = *reinterpret_cast<const float4*>(T.z + (int64_t)row * T.ldz + c);  // ldz % 4 == 0 and c + 3 < ldz
   bool keep[4] = {true, true, true, true};
   if (T.drop_on) drop_keep4(cfg, (uint32_t)row * (uint32_t)((T.classes + 3) >> 2) + (uint32_t)(c >> 2), keep);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    in[i] = c + i < T.classes;
-    float v = (&z4.x)[i];
-    if (act == HMP_ACT_RELU) v = fmaxf(v, 0.f);
-    else if (act == HMP_ACT_ELU) v = v > 0.f ? v : expm1f(v);
-    if (T.drop_on) v = keep[i] ? (v * cfg.scale + 0.0f) : -0.0f;
-    else if (act != HMP_ACT_NONE) v = v + 0.0f;
-    y[i] = in[i] ? v : -INFINITY;
-  }
+  y[0] = z4.x; y[1] = z4.y; y[2] = z4.z; y[3] = z4.w;
+  act_drop4(y, act, T.drop_on != 0, keep, cfg.scale);
 }
 
 __device__ __forceinline__ int tail_entry(const TailArgs& a) { return (a.n > 1 && (int)blockIdx.x >= a.h[1].block_start) ? 1 : 0; }
+// the row of this thread's row group in entry T's launch range (whole row groups leave together: shuffles stay inside a group)
+__device__ __forceinline__ int tail_row(const HeadTail& T) { return ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS; }
 
 __global__ __launch_bounds__(256) void tail_ce_kernel(const TailArgs a) {
   const HeadTail& T = a.h[tail_entry(a)];
-  const int row = ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS;
-  if (row >= T.n_rows) return;  // whole row groups leave together: the shuffles below stay inside a group
-  const int lane = threadIdx.x % TL_GS;
+  const int row = tail_row(T);
+  if (row >= T.n_rows) return;
   const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
-  const int64_t y = T.labels[row];
-  const bool in_mask = T.mask ? T.mask[row] != 0 : true;
-  float m = -INFINITY;
-  for (int c = lane * 4; c < T.classes; c += TL_GS * 4) {
-    float v[4];
-    bool in[4];
-    tail_quad(T, cfg, a.act, row, c, v, in);
+  // any width: the row's quads are recomputed from z in each of the CE's passes
+  ce_group<TL_GS, 0>(
+      threadIdx.x % TL_GS, T.classes, T.ldg, T.labels[row], a.ignored, T.mask ? T.mask[row] != 0 : true,
+      [&](int, int c, float (&v)[4]) { tail_quad(T, cfg, a.act, row, c, v); },
+      [&](int c, float (&g)[4], const float (&v)[4]) {  // y is what the CE read: chain back to z
 #pragma unroll
-    for (int i = 0; i < 4; ++i) m = fmaxf(m, v[i]);
-  }
-#pragma unroll
-  for (int o = TL_GS / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f, ly = 0.f;
-  for (int c = lane * 4; c < T.classes; c += TL_GS * 4) {
-    float v[4];
-    bool in[4];
-    tail_quad(T, cfg, a.act, row, c, v, in);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (!in[i]) continue;
-      s += expf(v[i] - m);
-      if ((int64_t)(c + i) == y) ly = v[i];
-    }
-  }
-#pragma unroll
-  for (int o = TL_GS / 2; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o);
-    ly += __shfl_xor(ly, o);
-  }
-  const float lse = m + logf(s);
-  const bool valid = in_mask && y != a.ignored;
-  const bool bad = valid && (y < 0 || y >= T.classes);
-  const bool use = valid && !bad;
-  for (int c = lane * 4; c < T.ldg; c += TL_GS * 4) {
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use && c < T.classes) {
-      float v[4];
-      bool in[4];
-      tail_quad(T, cfg, a.act, row, c, v, in);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (in[i]) (&g.x)[i] = (expf(v[i] - lse) - ((int64_t)(c + i) == y ? 1.f : 0.f)) * tail_dydz(v[i], a.act, T.drop_on != 0, cfg.scale);
-    }
-    *reinterpret_cast<float4*>(T.grad + (int64_t)row * T.ldg + c) = g;
-  }
-  if (lane == 0) {
-    T.row_lv[2 * row] = use ? (lse - ly) : 0.f;
-    T.row_lv[2 * row + 1] = use ? 1.f : 0.f;
-    if (bad) atomicOr(&a.state->status, 2);
-  }
-}
-
-__global__ __launch_bounds__(256) void tail_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) {
-  __shared__ int s_correct, s_total;
-  if (threadIdx.x == 0) { s_correct = 0; s_total = 0; }
-  __syncthreads();
-  const HeadTail& T = a.h[tail_entry(a)];
-  const int row = ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS;
-  const int lane = threadIdx.x % TL_GS;
-  if (row < T.n_rows) {
-    // first maximum of act(z) (torch.argmax's rule; ReLU makes ties at 0): in-lane ascending, then the lowest index on equality
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int c = lane * 4; c < T.classes; c += TL_GS * 4) {
-      float v[4];
-      bool in[4];
-      tail_quad(T, T.drop, a.act, row, c, v, in);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (in[i] && (v[i] > best || arg == 0x7fffffff)) { best = v[i]; arg = c + i; }
-    }
-#pragma unroll
-    for (int o = TL_GS / 2; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o);
-      const int oa = __shfl_xor(arg, o);
-      if (oa != 0x7fffffff && (arg == 0x7fffffff || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
-    }
-    const bool in_mask = T.mask ? T.mask[row] != 0 : true;
-    if (lane == 0 && in_mask) {
-      atomicAdd(&s_total, 1);
-      if ((int64_t)(arg == 0x7fffffff ? 0 : arg) == T.labels[row]) atomicAdd(&s_correct, 1);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_correct) atomicAdd(&counts[2 * T.slot], (unsigned long long)s_correct);
-    if (s_total) atomicAdd(&counts[2 * T.slot + 1], (unsigned long long)s_total);
-  }
+        for (int i = 0; i < 4; ++i)
+          if (c + i < T.classes) g[i] *= tail_dydz(v[i], a.act, T.drop_on != 0, cfg.scale);
+        *reinterpret_cast<float4*>(T.grad + (int64_t)row * T.ldg + c) = make_float4(g[0], g[1], g[2], g[3]);
+      },
+      T.row_lv, row, a.state);
 }
 
 // ---- pooled heads (HeterogeneousNeuralTreeNetwork, reference heterogeneous_neural_tree_network.py:186-205) ------------------
@@ -146,17 +65,13 @@ __device__ __forceinline__ int pool_row(const HeadTail& T, const DropCfg& cfg, i
     for (int i = 0; i < 4; ++i) p[q][i] = 0.f;
   for (int k = b; k < e; ++k) {
     const int leaf = T.rowptr ? T.col[k] : k;
-#pragma unroll
-    for (int q = 0; q < PT_Q; ++q) {
-      const int c = lane * 4 + q * TL_GS * 4;
-      if (c >= T.classes) continue;
+    lane_quads<TL_GS, PT_Q>(lane, T.classes, [&](int q, int c) {
       float y[4];
-      bool in[4];
-      tail_quad(T, cfg, act, leaf, c, y, in);
+      tail_quad(T, cfg, act, leaf, c, y);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (in[i]) p[q][i] += y[i];
-    }
+        if (c + i < T.classes) p[q][i] += y[i];
+    });
   }
   const int deg = e - b;
   const float d = (float)(deg > 1 ? deg : 1);
@@ -169,64 +84,30 @@ __device__ __forceinline__ int pool_row(const HeadTail& T, const DropCfg& cfg, i
 
 __global__ __launch_bounds__(256) void pool_ce_kernel(const TailArgs a) {
   const HeadTail& T = a.h[tail_entry(a)];
-  const int v = ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS;
-  if (v >= T.n_pool) return;  // whole row groups leave together
+  const int v = tail_row(T);
+  if (v >= T.n_pool) return;
   const int lane = threadIdx.x % TL_GS;
   const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
   const int64_t y = T.labels[v];
   const bool in_mask = T.mask ? T.mask[v] != 0 : true;
   float p[PT_Q][4];
   const int deg = pool_row(T, cfg, a.act, v, lane, p);
-  float m = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < PT_Q; ++q)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (lane * 4 + q * TL_GS * 4 + i < T.classes) m = fmaxf(m, p[q][i]);
-#pragma unroll
-  for (int o = TL_GS / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f, ly = 0.f;
-#pragma unroll
-  for (int q = 0; q < PT_Q; ++q)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = lane * 4 + q * TL_GS * 4 + i;
-      if (c >= T.classes) continue;
-      s += expf(p[q][i] - m);
-      if ((int64_t)c == y) ly = p[q][i];
-    }
-#pragma unroll
-  for (int o = TL_GS / 2; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o);
-    ly += __shfl_xor(ly, o);
-  }
-  const float lse = m + logf(s);
-  const bool valid = in_mask && y != a.ignored;
-  const bool bad = valid && (y < 0 || y >= T.classes);
-  const bool use = valid && !bad;
   const float r = 1.0f / (float)(deg > 1 ? deg : 1);  // the mean's backward: every leaf edge carries 1 / max(deg, 1)
+  ce_group<TL_GS, PT_Q>(
+      lane, T.classes, T.ldp, y, a.ignored, in_mask,
+      [&](int q, int, float (&l)[4]) {
 #pragma unroll
-  for (int q = 0; q < PT_Q; ++q) {
-    const int c = lane * 4 + q * TL_GS * 4;
-    if (c >= T.ldp) continue;
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (use) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (c + i < T.classes) (&g.x)[i] = (expf(p[q][i] - lse) - ((int64_t)(c + i) == y ? 1.f : 0.f)) * r;
-    }
-    *reinterpret_cast<float4*>(T.dpool + (int64_t)v * T.ldp + c) = g;
-  }
-  if (lane == 0) {
-    T.row_lv[2 * v] = use ? (lse - ly) : 0.f;
-    T.row_lv[2 * v + 1] = use ? 1.f : 0.f;
-    if (bad) atomicOr(&a.state->status, 2);
-  }
+        for (int i = 0; i < 4; ++i) l[i] = p[q][i];
+      },
+      [&](int c, float (&g)[4], const float (&)[4]) {
+        *reinterpret_cast<float4*>(T.dpool + (int64_t)v * T.ldp + c) = make_float4(g[0] * r, g[1] * r, g[2] * r, g[3] * r);
+      },
+      T.row_lv, v, a.state);
 }
 
 __global__ __launch_bounds__(256) void pool_grad_kernel(const TailArgs a) {
   const HeadTail& T = a.h[tail_entry(a)];
-  const int row = ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS;
+  const int row = tail_row(T);
   if (row >= T.n_rows) return;
   const int lane = threadIdx.x % TL_GS;
   const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
@@ -242,138 +123,87 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(const TailArgs a) {
         acc.x += d.x; acc.y += d.y; acc.z += d.z; acc.w += d.w;
       }
       float y[4];
-      bool in[4];
-      tail_quad(T, cfg, a.act, row, c, y, in);
+      tail_quad(T, cfg, a.act, row, c, y);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (in[i]) (&g.x)[i] = (&acc.x)[i] * tail_dydz(y[i], a.act, T.drop_on != 0, cfg.scale);
+        if (c + i < T.classes) (&g.x)[i] = (&acc.x)[i] * tail_dydz(y[i], a.act, T.drop_on != 0, cfg.scale);
     }
     *reinterpret_cast<float4*>(T.grad + (int64_t)row * T.ldg + c) = g;
   }
 }
 
-__global__ __launch_bounds__(256) void pool_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) {
-  __shared__ int s_correct, s_total;
-  if (threadIdx.x == 0) { s_correct = 0; s_total = 0; }
-  __syncthreads();
+// counts[2 * slot] += {#(argmax == label), #rows} over the masked rows of both entries; POOL: the rows are LeafPool means (an empty
+// row is all 0 and predicts 0), else leaf rows of any width
+template <bool POOL>
+__device__ __forceinline__ void tail_count(const TailArgs& a, unsigned long long* __restrict__ counts) {
+  __shared__ int s_cnt[2];
+  count_begin(s_cnt);
   const HeadTail& T = a.h[tail_entry(a)];
-  const int v = ((int)blockIdx.x - T.block_start) * TL_RPB + (int)threadIdx.x / TL_GS;
+  const int row = tail_row(T);
   const int lane = threadIdx.x % TL_GS;
-  if (v < T.n_pool) {
-    float p[PT_Q][4];
-    pool_row(T, T.drop, a.act, v, lane, p);
-    // first maximum (tail_count_kernel's rule): in-lane ascending, then the lowest index on equality; an empty row is all 0 -> 0
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
+  if (row < (POOL ? T.n_pool : T.n_rows)) {
+    int pred;
+    if constexpr (POOL) {
+      float p[PT_Q][4];
+      pool_row(T, T.drop, a.act, row, lane, p);
+      pred = argmax_group<TL_GS, PT_Q>(lane, T.classes, [&](int q, int, float (&v)[4]) {
 #pragma unroll
-    for (int q = 0; q < PT_Q; ++q)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = lane * 4 + q * TL_GS * 4 + i;
-        if (c < T.classes && (p[q][i] > best || arg == 0x7fffffff)) { best = p[q][i]; arg = c; }
-      }
-#pragma unroll
-    for (int o = TL_GS / 2; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o);
-      const int oa = __shfl_xor(arg, o);
-      if (oa != 0x7fffffff && (arg == 0x7fffffff || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
+        for (int i = 0; i < 4; ++i) v[i] = p[q][i];
+      });
+    } else {
+      pred = argmax_group<TL_GS, 0>(lane, T.classes, [&](int, int c, float (&v)[4]) { tail_quad(T, T.drop, a.act, row, c, v); });
     }
-    const bool in_mask = T.mask ? T.mask[v] != 0 : true;
-    if (lane == 0 && in_mask) {
-      atomicAdd(&s_total, 1);
-      if ((int64_t)(arg == 0x7fffffff ? 0 : arg) == T.labels[v]) atomicAdd(&s_correct, 1);
-    }
+    const bool in_mask = T.mask ? T.mask[row] != 0 : true;
+    if (lane == 0 && in_mask) count_row(s_cnt, (int64_t)pred == T.labels[row]);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_correct) atomicAdd(&counts[2 * T.slot], (unsigned long long)s_correct);
-    if (s_total) atomicAdd(&counts[2 * T.slot + 1], (unsigned long long)s_total);
-  }
+  count_flush(s_cnt, counts + 2 * T.slot);
 }
 
-// leaf = true: one row group per leaf row (gradient launch), else per pooled row
-int pool_layout(TailArgs& a, bool leaf, bool ce, int& blocks) {
+__global__ __launch_bounds__(256) void tail_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) { tail_count<false>(a, counts); }
+__global__ __launch_bounds__(256) void pool_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) { tail_count<true>(a, counts); }
+
+// Checks the entries for a launch and lays their row groups out over the grid.  pool: the heads go through a LeafPool (rows in
+// registers, CSR / CSC or the identity); leaf_rows: one row group per leaf row, else per pooled row; ce: the launch writes gradients.
+int tail_layout(TailArgs& a, bool pool, bool leaf_rows, bool ce, int& blocks) {
+  auto aligned = [](const float* p, int ld, int classes) { return (ld & 3) == 0 && ld >= classes && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const char* who = pool ? "pool tail" : "tail";
   blocks = 0;
   for (int i = 0; i < a.n; ++i) {
     HeadTail& T = a.h[i];
-    HMP_CHECK_ARG(T.classes >= 1 && T.classes <= POOL_TAIL_MAX_CLASSES, "pool tail: %d classes (1 .. %d)", T.classes,
-                  POOL_TAIL_MAX_CLASSES);
-    HMP_CHECK_ARG((T.ldz & 3) == 0 && T.ldz >= T.classes && (reinterpret_cast<uintptr_t>(T.z) & 15) == 0,
-                  "pool tail: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", T.classes);
-    HMP_CHECK_ARG(T.rowptr ? (T.col && T.t_rowptr && T.t_col) : T.n_pool == T.n_rows,
-                  "pool tail: a pooled head needs the plan's CSR and CSC, an unpooled one a row per leaf");
-    if (ce) {
-      HMP_CHECK_ARG(T.dpool && (T.ldp & 3) == 0 && T.ldp >= T.classes && (reinterpret_cast<uintptr_t>(T.dpool) & 15) == 0,
-                    "pool tail: pooled gradient must be 16-byte aligned with ld %% 4 == 0");
-      HMP_CHECK_ARG(T.grad && (T.ldg & 3) == 0 && T.ldg >= T.classes && T.ldg <= T.ldp &&
-                        (reinterpret_cast<uintptr_t>(T.grad) & 15) == 0,
-                    "pool tail: gradient must be 16-byte aligned with ld %% 4 == 0");
+    if (pool) HMP_CHECK_ARG(T.classes >= 1 && T.classes <= POOL_TAIL_MAX_CLASSES, "pool tail: %d classes (1 .. %d)", T.classes, POOL_TAIL_MAX_CLASSES);
+    HMP_CHECK_ARG(T.classes >= 1 && aligned(T.z, T.ldz, T.classes),
+                  "%s: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", who, T.classes);
+    HMP_CHECK_ARG(!ce || (T.grad && aligned(T.grad, T.ldg, T.classes)), "%s: gradient must be 16-byte aligned with ld %% 4 == 0", who);
+    if (pool) {
+      HMP_CHECK_ARG(T.rowptr ? (T.col && T.t_rowptr && T.t_col) : T.n_pool == T.n_rows,
+                    "pool tail: a pooled head needs the plan's CSR and CSC, an unpooled one a row per leaf");
+      HMP_CHECK_ARG(!ce || (T.dpool && aligned(T.dpool, T.ldp, T.classes) && T.ldg <= T.ldp),
+                    "pool tail: pooled gradient must be 16-byte aligned with ld %% 4 == 0 and no narrower than the gradient");
     }
     T.block_start = blocks;
-    blocks += cdiv(leaf ? T.n_rows : T.n_pool, TL_RPB);
+    blocks += cdiv(leaf_rows ? T.n_rows : T.n_pool, TL_RPB);
   }
   return HMP_OK;
 }
 
-int tail_layout(TailArgs& a, int& blocks) {
-  blocks = 0;
-  for (int i = 0; i < a.n; ++i) {
-    HeadTail& T = a.h[i];
-    HMP_CHECK_ARG(T.classes >= 1 && (T.ldz & 3) == 0 && T.ldz >= T.classes && (reinterpret_cast<uintptr_t>(T.z) & 15) == 0,
-                  "tail: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", T.classes);
-    HMP_CHECK_ARG(!T.grad || ((T.ldg & 3) == 0 && T.ldg >= T.classes && (reinterpret_cast<uintptr_t>(T.grad) & 15) == 0),
-                  "tail: gradient must be 16-byte aligned with ld %% 4 == 0");
-    T.block_start = blocks;
-    blocks += cdiv(T.n_rows, TL_RPB);
-  }
+template <class... Extra>
+int tail_launch(void (*kernel)(TailArgs, Extra...), TailArgs& a, bool pool, bool leaf_rows, bool ce, hipStream_t st, Extra... extra) {
+  int blocks;
+  HMP_TRY(tail_layout(a, pool, leaf_rows, ce, blocks));
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, a, extra...);
+  HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
+
+unsigned long long* u64(long long* p) { return reinterpret_cast<unsigned long long*>(p); }
 
 }  // namespace
 
-int tail_ce_launch(TailArgs& a, hipStream_t st) {
-  int blocks;
-  HMP_TRY(tail_layout(a, blocks));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(tail_ce_kernel, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
-
-int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) {
-  int blocks;
-  HMP_TRY(tail_layout(a, blocks));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(tail_count_kernel, dim3(blocks), dim3(256), 0, st, a, reinterpret_cast<unsigned long long*>(counts));
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
-
-int pool_tail_ce_launch(TailArgs& a, hipStream_t st) {
-  int blocks;
-  HMP_TRY(pool_layout(a, false, true, blocks));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(pool_ce_kernel, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
-
-int pool_tail_grad_launch(TailArgs& a, hipStream_t st) {
-  int blocks;
-  HMP_TRY(pool_layout(a, true, true, blocks));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(pool_grad_kernel, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
-
-int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) {
-  int blocks;
-  HMP_TRY(pool_layout(a, false, false, blocks));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(pool_count_kernel, dim3(blocks), dim3(256), 0, st, a, reinterpret_cast<unsigned long long*>(counts));
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
-}
+int tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(tail_ce_kernel, a, false, true, true, st); }
+int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(tail_count_kernel, a, false, true, false, st, u64(counts)); }
+int pool_tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_ce_kernel, a, true, false, true, st); }
+int pool_tail_grad_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_grad_kernel, a, true, true, true, st); }
+int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(pool_count_kernel, a, true, false, false, st, u64(counts)); }
 
 }  // namespace hmp

@@ -61,7 +61,7 @@ def tie_logits(n, C, ld, seed):
     return buf[:n, :C]
 
 
-@pytest.mark.parametrize("C", [1, 15, 26, 33, 64, 65, 130])
+@pytest.mark.parametrize("C", [1, 3, 4, 15, 17, 26, 33, 64, 65, 130])
 @pytest.mark.parametrize("n", [0, 1, 17, 5003])
 def test_operator_matches_torch_argmax_and_bincount(C, n):
     ignored = 25 if C > 25 else C // 2
@@ -101,6 +101,26 @@ def _padded(host, ld):
     buf = torch.full((n, ld), 7.0)  # padding larger than every logit: a read past the row would change the argmax
     buf[:, :C] = host
     return buf.reshape(-1).to(DEV)
+
+
+@pytest.mark.parametrize("C", [1, 3, 4, 17, 64, 65, 130])
+def test_one_tie_rule_across_entries(C):
+    """hmp_argmax_rows and hmp_count_correct_rows share one first-maximum rule on rows full of exact ties, whichever column walk
+    the buffer's pitch selects (16-byte quads or scalar columns): a count against the other entry's predictions is all correct"""
+    n = 37
+    aligned, odd = (C + 3) // 4 * 4, (C + 3) // 4 * 4 + 1
+    for ld in (aligned, odd):
+        host = tie_logits(n, C, ld, seed=C + ld)
+        logits = torch.as_strided(_padded(host, ld), (n, C), (ld, 1))
+        pred = ops.argmax_rows(logits)
+        assert np.array_equal(pred.cpu().numpy(), np.argmax(host.numpy(), axis=1)), ld
+        counts = torch.zeros(2, dtype=torch.int64, device=DEV)
+        conf = torch.zeros(C, C, dtype=torch.int64, device=DEV)
+        ops.count_correct_rows(logits, pred, counts, ignored_label=-1, confusion=conf)
+        assert counts.cpu().tolist() == [n, n], ld
+        conf = conf.cpu()
+        assert int(conf.sum()) == n and int(conf.diagonal().sum()) == n, ld
+        assert torch.equal(conf.diagonal(), torch.bincount(pred.cpu(), minlength=C)), ld
 
 
 def test_operator_strides_over_many_rows_and_flags_nothing_else():

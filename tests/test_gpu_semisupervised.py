@@ -16,6 +16,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from hydra_gnn_amd import _lib, workloads  # noqa: E402
+from hydra_gnn_amd.data import HeteroData, collate  # noqa: E402
 from hydra_gnn_amd.models import HeterogeneousNetwork  # noqa: E402
 from oracle import models as omodels  # noqa: E402
 
@@ -259,6 +260,76 @@ def test_count_correct_matches_reference_test(block):
             pr, _ = b(gb)
         assert bool((pr == 0).all())  # the tie case really was exercised
         assert reference_test_counts(b, gb, "train_mask")[0] == int((gb["rooms"].y[gb["rooms"].train_mask] == 0).sum())
+
+
+def tiny_graph(rng, n_rooms, n_obj, n_obj_classes):
+    """a hand-sized scene graph of the MP3D shape: an object ring, a room chain, object i in room i % n_rooms"""
+    ring = np.stack([np.arange(n_obj), (np.arange(n_obj) + 1) % n_obj])
+    chain = np.stack([np.arange(n_rooms - 1), np.arange(1, n_rooms)])
+    ro = np.stack([np.arange(n_obj) % n_rooms, np.arange(n_obj)])
+    both = lambda e: torch.from_numpy(np.concatenate([e, e[::-1]], 1).astype(np.int64))
+    g = HeteroData()
+    for t, n, d, c in (("objects", n_obj, 306, n_obj_classes), ("rooms", n_rooms, 6, 5)):
+        g[t].x = torch.from_numpy(rng.normal(0.0, 0.5, size=(n, d)).astype(np.float32))
+        g[t].pos = g[t].x[:, :3].clone()
+        g[t].y = torch.from_numpy(rng.integers(0, c, size=n).astype(np.int64))
+    g["objects", "objects_to_objects", "objects"].edge_index = both(ring)
+    g["rooms", "rooms_to_rooms", "rooms"].edge_index = both(chain)
+    g["objects", "objects_to_rooms", "rooms"].edge_index = torch.from_numpy(ro[::-1].copy().astype(np.int64))
+    g["rooms", "rooms_to_objects", "objects"].edge_index = torch.from_numpy(ro.astype(np.int64))
+    return g
+
+
+def test_seventy_object_classes():
+    """70 object classes on the UNPOOLED two-head tail: a second quad per lane (16 lanes x 4) and a ragged last quad in its CE
+    and its argmax; 3 graphs of <= 6 rooms and <= 12 objects.  One fused step == the autograd loop (loss and gradient sums at the
+    tolerances of the tests above), count_correct == numpy's first-maximum argmax, and rows whose logits all tie predict class 0."""
+    rng = np.random.Generator(np.random.PCG64(70))
+    gb = collate([tiny_graph(rng, r, o, 70) for r, o in ((2, 5), (6, 12), (4, 9))])
+    for t in ("rooms", "objects"):
+        gb[t].train_mask = torch.from_numpy(rng.random(int(gb[t].y.numel())) < 0.7)
+    gb = gb.to(DEV)
+    gb["objects"].y[::4] = 0  # class 0 is labelled: the all-tied prediction below has rows to be right about
+    labels, masks = targets(gb)
+    torch.manual_seed(70)
+    kw = dict(model_kw("GraphSAGE", 0.25, 16), output_dim_dict={"rooms": 5, "objects": 70})
+    a = HeterogeneousNetwork(**kw)
+    b, c = copy.deepcopy(a).to(DEV), copy.deepcopy(a).to(DEV)
+    a = a.to(DEV)
+
+    a.train()
+    loss = a.loss(a(gb), labels, masks)
+    loss.backward()
+    step = b.semisupervised_step(lr=0.0, use_graph=False, force_collective=True)
+    step(gb, labels, masks)
+    torch.cuda.synchronize()
+    count = float(step.grads[b.native().n_active + 1])
+    assert count == float(masks[0].sum() + masks[1].sum())
+    np.testing.assert_allclose(step.loss(), float(loss), rtol=2e-5, atol=2e-6)
+    assert b.native().read_state()[1] == 0
+    for p_ref, p in zip(a.parameters(), b.parameters()):
+        if p_ref.grad is None:
+            continue
+        off, n = flat_grad(b, p)
+        torch.testing.assert_close(step.grads[off:off + n].view(p.shape) / count, p_ref.grad, atol=1e-6, rtol=1e-4)
+
+    with torch.no_grad():  # every object logit negative: ReLU makes the whole row 0
+        for name, p in c.named_parameters():
+            if name.startswith(f"convs.{c.num_layers - 1}.") and name.endswith("objects.lin_l.bias"):
+                p.add_(-1e3)
+    for net in (a, c):
+        net.eval()
+        with torch.no_grad():
+            pred = [np.argmax(p.cpu().numpy(), axis=1) for p in net(gb)]  # numpy: the first maximum
+        want = []
+        for p, l, m in zip(pred, labels, masks):
+            l, m = l.cpu().numpy(), m.cpu().numpy()
+            want += [int((p[m] == l[m]).sum()), int(m.sum())]
+        assert net.count_correct(gb, labels, masks) == want
+    with torch.no_grad():
+        po = c(gb)[1]
+    assert po.shape[1] == 70 and bool((po == 0).all())  # the tie case really was exercised
+    assert want[2] == int((labels[1][masks[1]] == 0).sum()) > 0
 
 
 def free_port():
