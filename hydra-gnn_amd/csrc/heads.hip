@@ -237,8 +237,9 @@ int heads_blocks(int n_rows) {
 
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st) {
   HMP_TRY(heads_check(a));
-  HMP_CHECK_ARG(a.ldg >= a.F && (a.ldg & 3) == 0 && a.ld_slab >= a.F && a.slab_stride >= (int64_t)a.K * (a.ld_slab + 1),
-                "linear heads: gradient / slab layout");
+  // the kernel walks the gradient's columns by LDS chunk up to roundup(F, HL_FC): a wider ldg would leave columns unwritten
+  HMP_CHECK_ARG(a.ldg == align4(a.F), "linear heads: gradient ld %d (F = %d rounded up to 4: %d)", a.ldg, a.F, align4(a.F));
+  HMP_CHECK_ARG(a.ld_slab >= a.F && a.slab_stride >= (int64_t)a.K * (a.ld_slab + 1), "linear heads: slab layout");
   a.n_tiles = cdiv(a.n_rows, HL_RB);
   const int blocks = heads_blocks(a.n_rows);
   if (blocks == 0) return HMP_OK;
@@ -260,3 +261,37 @@ int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st)
 }
 
 }  // namespace hmp
+
+// test / diagnostic entry of the two linear-heads launchers: a plain copy of the descriptor into LinHeadArgs, no choice of its own
+extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts,
+                                    int32_t* n_blocks_out, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_linear_heads_run: no gfx950 device visible");
+  HMP_CHECK_ARG(d && d->z && d->W[0] && d->W[1] && d->bias[0] && d->bias[1], "hmp_linear_heads_run: null pointer");
+  HMP_CHECK_ARG(train ? (d_state && d->grad && d->row_lv && d->slabs) : d_counts != nullptr,
+                "hmp_linear_heads_run: %s", train ? "the CE needs d_state, grad, row_lv and slabs" : "the count needs d_counts");
+  LinHeadArgs a;
+  memset(&a, 0, sizeof(a));
+  a.z = d->z; a.ldz = d->ldz; a.n_rows = d->n_rows; a.F = d->F;
+  a.classes[0] = d->classes[0]; a.classes[1] = d->classes[1]; a.K = a.classes[0] + a.classes[1];
+  for (int k = 0; k < 2; ++k) {
+    a.W[k] = d->W[k];
+    a.bias[k] = d->bias[k];
+    a.member[k] = d->member[k];
+  }
+  a.labels = d->labels; a.mask = d->mask; a.ignored = d->ignored;
+  a.act = d->act;
+  a.state = reinterpret_cast<NetState*>(d_state);
+  a.drop_on = (train && d->p > 0.f) ? 1 : 0;
+  if (a.drop_on) {  // (as net.hip: make_drop)
+    a.drop.k0 = (uint32_t)d->seed; a.drop.k1 = (uint32_t)(d->seed >> 32);
+    a.drop.step = d->rng_step; a.drop.stream = d->rng_stream;
+    a.drop.thresh = drop_thresh(d->p); a.drop.scale = 1.f / (1.f - d->p);
+    a.drop.step_dev = nullptr;
+  }
+  a.grad = d->grad; a.ldg = d->ldg; a.row_lv = d->row_lv;
+  a.slabs = d->slabs; a.ld_slab = d->ld_slab; a.slab_stride = d->slab_stride;
+  if (n_blocks_out) *n_blocks_out = heads_blocks(d->n_rows);
+  return train ? linear_heads_ce_launch(a, (hipStream_t)stream) : linear_heads_count_launch(a, (long long*)d_counts, (hipStream_t)stream);
+}

@@ -605,7 +605,7 @@ struct LinHeadArgs {
   int act, drop_on;
   DropCfg drop;                 // quad numbering row * ceil(F / 4) + col / 4
   float* grad;                  // d loss / d z [n_rows][ldg] (columns F .. ldg written 0)
-  int ldg;
+  int ldg;                      // == align4(F): the launch refuses any other (its column walk ends at roundup(F, 64))
   float* row_lv;                // per row {loss, valid} (both heads summed)
   NetState* state;
   float* slabs;                 // workgroup b: slabs + b * slab_stride = dW [K][ld_slab], then db [K]

@@ -40,6 +40,8 @@ size_t hmp_sizeof(int which) {
     case 11: return sizeof(hmp_epoch_ctl);
     case 12: return sizeof(hmp_epoch_row);
     case 13: return sizeof(hmp_epoch_seg);
+    case 14: return sizeof(hmp_tail_desc);
+    case 15: return sizeof(hmp_linear_heads_desc);
     default: return 0;
   }
 }

@@ -207,3 +207,43 @@ int pool_tail_grad_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool
 int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(pool_count_kernel, a, true, false, false, st, u64(counts)); }
 
 }  // namespace hmp
+
+// test / diagnostic entry of the five tail launchers: a plain copy of the descriptors into TailArgs, no choice of its own
+extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
+                              int64_t* d_counts, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_head_tails: no gfx950 device visible");
+  HMP_CHECK_ARG(d && (n == 1 || n == 2) && mode >= 0 && mode <= 3, "hmp_head_tails: %d heads (1 or 2), mode %d (0 .. 3)", n, mode);
+  const bool ce = mode == 0 || mode == 2;
+  HMP_CHECK_ARG(ce ? d_state != nullptr : d_counts != nullptr, "hmp_head_tails: mode %d needs %s", mode, ce ? "d_state" : "d_counts");
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.n = n; ta.act = act; ta.ignored = ignored;
+  ta.state = reinterpret_cast<NetState*>(d_state);
+  for (int i = 0; i < n; ++i) {
+    const hmp_tail_desc& q = d[i];
+    HMP_CHECK_ARG(q.z && (q.labels || q.n_rows == 0) && (!ce || q.row_lv), "hmp_head_tails: null pointer (head %d)", i);
+    HeadTail& T = ta.h[i];
+    T.z = q.z; T.ldz = q.ldz; T.n_rows = q.n_rows; T.classes = q.classes;
+    T.labels = q.labels; T.mask = q.mask;
+    T.grad = q.grad; T.ldg = q.ldg; T.row_lv = q.row_lv;
+    T.slot = q.slot;
+    T.rowptr = q.rowptr; T.col = q.col; T.t_rowptr = q.t_rowptr; T.t_col = q.t_col;
+    T.n_pool = q.n_pool; T.dpool = q.dpool; T.ldp = q.ldp;
+    T.drop_on = (ce && q.p > 0.f) ? 1 : 0;  // the counts run in eval mode (as net.hip: add_tail / add_pool)
+    if (T.drop_on) {  // (as net.hip: make_drop)
+      T.drop.k0 = (uint32_t)q.seed; T.drop.k1 = (uint32_t)(q.seed >> 32);
+      T.drop.step = q.rng_step; T.drop.stream = q.rng_stream;
+      T.drop.thresh = drop_thresh(q.p); T.drop.scale = 1.f / (1.f - q.p);
+      T.drop.step_dev = nullptr;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  switch (mode) {
+    case 0: return tail_ce_launch(ta, st);
+    case 1: return tail_count_launch(ta, (long long*)d_counts, st);
+    case 2: HMP_TRY(pool_tail_ce_launch(ta, st)); return pool_tail_grad_launch(ta, st);
+    default: return pool_tail_count_launch(ta, (long long*)d_counts, st);
+  }
+}

@@ -140,8 +140,29 @@ class EpochSeg(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("bytes", C.c_int64)]
 
 
+class TailDesc(C.Structure):
+    _fields_ = [
+        ("z", C.c_void_p), ("labels", C.c_void_p), ("mask", C.c_void_p), ("grad", C.c_void_p), ("row_lv", C.c_void_p),
+        ("rowptr", C.c_void_p), ("col", C.c_void_p), ("t_rowptr", C.c_void_p), ("t_col", C.c_void_p), ("dpool", C.c_void_p),
+        ("ldz", C.c_int32), ("n_rows", C.c_int32), ("classes", C.c_int32), ("ldg", C.c_int32), ("slot", C.c_int32),
+        ("n_pool", C.c_int32), ("ldp", C.c_int32),
+        ("rng_step", C.c_uint32), ("rng_stream", C.c_uint32), ("p", C.c_float), ("seed", C.c_uint64),
+    ]
+
+
+class LinearHeadsDesc(C.Structure):
+    _fields_ = [
+        ("z", C.c_void_p), ("W", C.c_void_p * 2), ("bias", C.c_void_p * 2), ("labels", C.c_void_p), ("mask", C.c_void_p),
+        ("member", C.c_void_p * 2), ("grad", C.c_void_p), ("row_lv", C.c_void_p), ("slabs", C.c_void_p),
+        ("slab_stride", C.c_int64), ("ignored", C.c_int64), ("seed", C.c_uint64),
+        ("ldz", C.c_int32), ("n_rows", C.c_int32), ("F", C.c_int32), ("classes", C.c_int32 * 2), ("act", C.c_int32),
+        ("ldg", C.c_int32), ("ld_slab", C.c_int32),
+        ("rng_step", C.c_uint32), ("rng_stream", C.c_uint32), ("p", C.c_float),
+    ]
+
+
 _STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc,
-            EpochCtl, EpochRow, EpochSeg]
+            EpochCtl, EpochRow, EpochSeg, TailDesc, LinearHeadsDesc]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -171,6 +192,8 @@ SIGNATURES = {
     "hmp_count_correct_rows_by_graph": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
+    "hmp_head_tails": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I64, _VP, _VP, _VP]),
+    "hmp_linear_heads_run": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
     "hmp_net_create": (C.c_int, [C.POINTER(NetSpec), C.POINTER(_VP)]),
     "hmp_net_destroy": (None, [_VP]),
     "hmp_net_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(_I32), C.POINTER(_I64)]),

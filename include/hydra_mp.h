@@ -39,7 +39,9 @@ extern "C" {
  *    two-headed task ride in the same launch); the one-launch collator holds 40 items (was 24) and carries 264 table words in the
  *    argument block (was 336).  No struct changed layout, no entry was added;
  *    hmp_collator_set_label_filter (room-masked labels in the collation launch), hmp_count_correct_rows_by_graph /
- *    hmp_net_count_correct_rooms_by_graph (per-graph validation counts): new entries, no struct changed layout */
+ *    hmp_net_count_correct_rooms_by_graph (per-graph validation counts): new entries, no struct changed layout;
+ *    hmp_tail_desc (hmp_sizeof 14), hmp_linear_heads_desc (hmp_sizeof 15), hmp_head_tails / hmp_linear_heads_run: test and
+ *    diagnostic entries of the readout tail and linear-head launchers: new entries, no struct changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -60,8 +62,9 @@ extern "C" {
 int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
- * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets, 10 hmp_gemm_desc (lets a
- * foreign-language binding verify its struct mirror) */
+ * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets, 10 hmp_gemm_desc,
+ * 11 hmp_epoch_ctl, 12 hmp_epoch_row, 13 hmp_epoch_seg, 14 hmp_tail_desc, 15 hmp_linear_heads_desc (lets a foreign-language
+ * binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -236,6 +239,63 @@ int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t 
  * element (row, col) of a [n_rows, F] tensor is kept iff mask[row*F+col] != 0. */
 int hmp_dropout_mask(uint64_t seed, uint32_t rng_step, uint32_t rng_stream, float p, int32_t n_rows, int32_t F,
                      uint8_t* d_mask, void* stream);
+
+/* Test and diagnostic entries of the readout launchers (csrc/semisup.hip, csrc/heads.hip) as the fused steps call them: each
+ * descriptor is copied as it stands into the launcher's argument struct; the launchers' own argument checks apply and nothing
+ * else.  ABI-4-compatible additions (hmp_sizeof 14, 15).  d_state: device int32[5] with the layout of the executor's state
+ * block -- word 1 is the status (bit 1: a counted label outside [0, classes)); the other words are not touched.
+ * The dropout site (seed, rng_step, rng_stream, p) is the one hmp_dropout_mask(seed, rng_step, rng_stream, p, n_rows, classes or F)
+ * replays; p == 0: no dropout.
+ *
+ * One head's rows for the tail launches.  z [n_rows][ldz] final state, y = dropout(act(z)) over its first `classes` columns;
+ * grad [n_rows][ldg] receives d(SUM loss) / d z (columns classes .. ldg written 0), row_lv [rows][2] = {loss, valid} per CE row.
+ * Pooled modes: the CE / count rows are the n_pool pooled rows, each the mean of y over its leaves (divisor max(deg, 1)); rowptr /
+ * col: CSR by pooled row, t_rowptr / t_col: CSC by leaf (hmp_plan's d_rowptr, d_col, d_t_rowptr, d_t_col); rowptr NULL = identity
+ * pool (n_pool == n_rows).  labels, mask and row_lv are then per pooled row; dpool [n_pool][ldp] is scratch (d loss / d pooled / deg,
+ * ldp >= ldg). */
+typedef struct hmp_tail_desc {
+  const float* z;
+  const int64_t* labels;
+  const uint8_t* mask; /* NULL: every row */
+  float* grad;
+  float* row_lv;
+  const int32_t *rowptr, *col, *t_rowptr, *t_col;
+  float* dpool;
+  int32_t ldz, n_rows, classes, ldg, slot, n_pool, ldp; /* slot: d_counts[2 * slot] += {correct, total} */
+  uint32_t rng_step, rng_stream;
+  float p;
+  uint64_t seed;
+} hmp_tail_desc;
+/* n = 1 or 2 heads in one launch.  mode 0: the unpooled CE (any width); 1: the unpooled accuracy count (ACCUMULATES into d_counts,
+ * device int64[4]; eval mode: no dropout); 2: the pooled CE launch followed by the leaf-gradient launch (classes <= 256);
+ * 3: the pooled accuracy count.  act: HMP_ACT_*.  A count row counts iff its mask byte is set (or mask is NULL). */
+int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
+                   int64_t* d_counts, void* stream);
+/* Two linear heads over one final state z [n_rows][ldz]: logits_h = dropout(act(z)) W_h^T + b_h on the rows of head h (member[0]
+ * NULL: every row; member[1] NULL: the complement of member[0], empty when both are NULL), W_h [classes[h]][F] dense.
+ * grad [n_rows][ldg], ldg == F rounded up to 4 (columns F .. ldg written 0); row_lv [n_rows][2] = {loss_0 + loss_1, valid_0 + valid_1};
+ * workgroup b writes its partial dW [K][ld_slab] then db [K] (K = classes[0] + classes[1], head 0's rows first) at
+ * slabs + b * slab_stride; the caller sums the first *n_blocks_out slabs. */
+typedef struct hmp_linear_heads_desc {
+  const float* z;
+  const float* W[2];
+  const float* bias[2];
+  const int64_t* labels;
+  const uint8_t* mask;
+  const uint8_t* member[2];
+  float* grad;
+  float* row_lv;
+  float* slabs;
+  int64_t slab_stride, ignored;
+  uint64_t seed;
+  int32_t ldz, n_rows, F, classes[2], act, ldg, ld_slab;
+  uint32_t rng_step, rng_stream;
+  float p;
+} hmp_linear_heads_desc;
+/* train = 1: the CE launch; train = 0: the accuracy count (eval mode), ACCUMULATES {correct_0, total_0, correct_1, total_1} into
+ * d_counts (device int64[4]).  *n_blocks_out (may be NULL) = the workgroups launched = min(ceil(n_rows / 32), 240). */
+int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts, int32_t* n_blocks_out,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 6. network executor -- the whole HeteroConv layer stack as one native program.

@@ -332,6 +332,61 @@ def test_seventy_object_classes():
     assert want[2] == int((labels[1][masks[1]] == 0).sum()) > 0
 
 
+@pytest.mark.parametrize("width", [3, 130, 256, 260])
+def test_object_head_widths_against_the_oracle(width):
+    """Object-head widths around the tail's dispatch: 3 (one ragged quad), 130 and 256 (the last aggregation's fused ce_tail epilogue
+    above 70 classes and at its widest, a padded width of 256), 260 (past it: the stand-alone tail, more than four quads per lane).
+    Phase A of one fused step (SAGE two-head, dropout 0.25 on the hidden layers and the tail) against oracle.models in float64 with
+    the keep-masks replayed: the loss at test_fused_step_matches_oracle's tolerance, the gradient sums / count at the tolerance of
+    the autograd comparisons above."""
+    rng = np.random.Generator(np.random.PCG64(width))
+    gb = collate([tiny_graph(rng, r, o, width) for r, o in ((2, 5), (6, 12), (4, 9))])
+    for t in ("rooms", "objects"):
+        gb[t].train_mask = torch.from_numpy(rng.random(int(gb[t].y.numel())) < 0.7)
+    gb = gb.to(DEV)
+    labels, masks = targets(gb)
+    torch.manual_seed(width)
+    kw = dict(model_kw("GraphSAGE", 0.25, 16), output_dim_dict={"rooms": 5, "objects": width})
+    ora = omodels.HeterogeneousNetwork(**kw)
+    net = HeterogeneousNetwork(**kw)
+    net.load_state_dict(ora.state_dict(), strict=True)
+    net = net.to(DEV)
+    lib = _lib.require_device()
+
+    def replay(x, p, training, tag):
+        if not training or p == 0:
+            return x
+        layer, t = tag[1:].split(".", 1)
+        n, f = x.shape
+        m = torch.zeros(max(n * f, 1), dtype=torch.uint8, device=DEV)
+        if n * f:
+            _lib.check(lib.hmp_dropout_mask(net._seed, 1, net._drop_stream(int(layer), t), p, n, f, m.data_ptr(), _lib.stream_ptr()))
+        return x * m[: n * f].view(n, f).cpu().to(x.dtype) / (1.0 - p)
+
+    o64 = copy.deepcopy(ora).double().train()
+    o64.dropout_fn = replay
+    b64 = gb.to("cpu")
+    for t in b64.node_types:
+        b64[t].x = b64[t].x.double()
+    loss = o64.loss(o64(b64), tuple(y.cpu() for y in labels), tuple(m.cpu() for m in masks))
+    loss.backward()
+
+    step = net.semisupervised_step(lr=0.0, use_graph=False, force_collective=True)
+    step(gb, labels, masks)
+    torch.cuda.synchronize()
+    count = float(step.grads[net.native().n_active + 1])
+    assert count == float(masks[0].sum() + masks[1].sum())
+    assert net.native().read_state()[1] == 0
+    assert abs(step.loss() - float(loss)) <= 1e-5 * max(1.0, abs(float(loss)))
+    ref = dict(o64.named_parameters())
+    for name, p in net.named_parameters():
+        if ref[name].grad is None:
+            continue
+        off, n = flat_grad(net, p)
+        got = (step.grads[off:off + n].view(p.shape) / count).cpu().double()
+        torch.testing.assert_close(got, ref[name].grad, atol=1e-6, rtol=1e-4, msg=lambda m: f"{name} (width {width}): {m}")
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
