@@ -112,7 +112,34 @@ __global__ __launch_bounds__(256) void count_rows_by_graph_kernel(const float* _
   }
 }
 
+// pred[row] = the row's prediction, -1 for a row outside `members` (null: every row)
+template <bool VEC>
+__global__ __launch_bounds__(256) void predict_rows_kernel(const float* __restrict__ x, int ld, int n_rows, int n_classes,
+                                                           const uint8_t* __restrict__ members, int64_t* __restrict__ pred) {
+  const int lane = threadIdx.x % EV_GS;
+  for (int row = blockIdx.x * EV_RPB + (int)threadIdx.x / EV_GS; row < n_rows; row += gridDim.x * EV_RPB) {
+    // the member byte and the output address do not depend on the walk; the whole group of 16 lanes takes the same branch
+    const bool member = members ? members[row] != 0 : true;
+    int64_t* const out = pred + row;
+    int p = -1;
+    if (member) p = ev_argmax<VEC>(x + (int64_t)row * ld, n_classes, lane);
+    if (lane == 0) *out = (int64_t)p;
+  }
+}
+
 }  // namespace
+
+int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "predict_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(x && pred, "predict_rows: null logits or output");
+  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
+  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((predict_rows_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, pred);
+  else hipLaunchKernelGGL((predict_rows_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, pred);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
 
 int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
                                int64_t ignored, const int64_t* graph_ptr, int n_graphs, long long* counts, hipStream_t st) {
@@ -172,4 +199,10 @@ extern "C" int hmp_count_correct_rows_by_graph(const float* d_logits, int32_t ld
   using namespace hmp;
   return count_rows_by_graph_launch(d_logits, ld, n_rows, n_classes, d_labels, d_members, ignored_label, d_graph_ptr, n_graphs,
                                     reinterpret_cast<long long*>(d_counts), (hipStream_t)stream);
+}
+
+extern "C" int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members,
+                                int64_t* d_pred, void* stream) {
+  using namespace hmp;
+  return predict_rows_launch(d_logits, ld, n_rows, n_classes, d_members, d_pred, (hipStream_t)stream);
 }

@@ -66,12 +66,25 @@ __device__ void stage_w(const LinHeadArgs& a, int c0, HeadSmem& s) {
   }
 }
 
-template <bool TRAIN>
+// first maximum of lg[0 .. C) (torch.argmax's rule), sequential over the classes
+__device__ __forceinline__ int head_argmax(const float* lg, int C) {
+  int arg = 0;
+  float best = lg[0];
+  for (int k = 1; k < C; ++k)
+    if (lg[k] > best) { best = lg[k]; arg = k; }
+  return arg;
+}
+
+// what follows the logits of a tile: the CE and its backward (pass 2), the accuracy count, or the labels themselves
+enum HeadMode { HL_COUNT = 0, HL_TRAIN = 1, HL_PREDICT = 2 };
+
+template <HeadMode MODE>
 __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) {
+  constexpr bool TRAIN = MODE == HL_TRAIN;
   __shared__ HeadSmem s;
   const int t = threadIdx.x;
   const DropCfg cfg = a.drop_on ? drop_resolve(a.drop) : a.drop;
-  if (!TRAIN && t < 4) s.cnt[t] = 0;
+  if (MODE == HL_COUNT && t < 4) s.cnt[t] = 0;
   bool first = true;
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x, first = false) {
     const int row0 = tile * HL_RB;
@@ -121,6 +134,11 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
       float* lg = &s.lg[r][koff];
       const bool in_rows = row < a.n_rows;
       const bool member = in_rows && head_member(a, h, row);
+      if (MODE == HL_PREDICT) {  // no labels, no mask: every row of the tile gets its label, -1 outside the head's rows
+        int64_t* const out = a.pred[h];
+        if (in_rows && out) out[row] = member ? (int64_t)head_argmax(lg, C) : -1;
+        continue;
+      }
       const bool in_mask = in_rows && (a.mask ? a.mask[row] != 0 : true);
       const int64_t y = in_rows ? a.labels[row] : 0;
       if (TRAIN) {
@@ -143,11 +161,7 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
         s.hv[h][r] = use ? 1.f : 0.f;
         if (bad) atomicOr(&a.state->status, 2);
       } else if (member && in_mask) {
-        // first maximum (torch.argmax's rule)
-        int arg = 0;
-        float best = lg[0];
-        for (int k = 1; k < C; ++k)
-          if (lg[k] > best) { best = lg[k]; arg = k; }
+        const int arg = head_argmax(lg, C);
         atomicAdd(&s.cnt[2 * h + 1], 1);
         if ((int64_t)arg == y) atomicAdd(&s.cnt[2 * h], 1);
       }
@@ -211,20 +225,20 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
       }
     }
   }
-  if (!TRAIN) {
+  if (MODE == HL_COUNT) {
     __syncthreads();
     if (t < 4 && s.cnt[t]) atomicAdd(&a.counts[t], (unsigned long long)s.cnt[t]);
   }
 }
 
-int heads_check(const LinHeadArgs& a) {
+int heads_check(const LinHeadArgs& a, bool labels = true) {
   HMP_CHECK_ARG(a.F >= 1 && a.F <= HEAD_MAX_F, "linear heads: F = %d (1 .. %d)", a.F, HEAD_MAX_F);
   HMP_CHECK_ARG(a.classes[0] >= 1 && a.classes[0] <= HEAD_MAX_CLASSES && a.classes[1] >= 1 && a.classes[1] <= HEAD_MAX_CLASSES &&
                     a.K == a.classes[0] + a.classes[1],
                 "linear heads: classes %d / %d (1 .. %d each)", a.classes[0], a.classes[1], HEAD_MAX_CLASSES);
   HMP_CHECK_ARG((a.ldz & 3) == 0 && a.ldz >= a.F && (reinterpret_cast<uintptr_t>(a.z) & 15) == 0,
                 "linear heads: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", a.F);
-  HMP_CHECK_ARG(a.labels != nullptr || a.n_rows == 0, "linear heads: labels required");
+  HMP_CHECK_ARG(!labels || a.labels != nullptr || a.n_rows == 0, "linear heads: labels required");
   return HMP_OK;
 }
 
@@ -243,7 +257,7 @@ int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st) {
   a.n_tiles = cdiv(a.n_rows, HL_RB);
   const int blocks = heads_blocks(a.n_rows);
   if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<true>, dim3(blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(linear_heads_kernel<HL_TRAIN>, dim3(blocks), dim3(256), 0, st, a);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
@@ -255,7 +269,22 @@ int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st)
   a.drop_on = 0;
   const int blocks = heads_blocks(a.n_rows);
   if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<false>, dim3(blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(linear_heads_kernel<HL_COUNT>, dim3(blocks), dim3(256), 0, st, a);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+// pred[h][row] = argmax of head h's logits on act(z) for the head's rows, -1 elsewhere (eval mode; pred[h] null: head skipped).
+// Pass 1 and the tile assignment are the count's; no labels, mask, counters or pass 2.
+int linear_heads_predict_launch(LinHeadArgs& a, int64_t* const* pred, hipStream_t st) {
+  HMP_CHECK_ARG(pred != nullptr, "linear heads: null output array");
+  HMP_TRY(heads_check(a, false));
+  a.n_tiles = cdiv(a.n_rows, HL_RB);
+  a.pred[0] = pred[0]; a.pred[1] = pred[1];
+  a.drop_on = 0;
+  const int blocks = heads_blocks(a.n_rows);
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(linear_heads_kernel<HL_PREDICT>, dim3(blocks), dim3(256), 0, st, a);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
@@ -294,4 +323,24 @@ extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t trai
   a.slabs = d->slabs; a.ld_slab = d->ld_slab; a.slab_stride = d->slab_stride;
   if (n_blocks_out) *n_blocks_out = heads_blocks(d->n_rows);
   return train ? linear_heads_ce_launch(a, (hipStream_t)stream) : linear_heads_count_launch(a, (long long*)d_counts, (hipStream_t)stream);
+}
+
+// the predict launcher on the same descriptor (labels, mask, grad, row_lv and slabs may be NULL)
+extern "C" int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_linear_heads_predict: no gfx950 device visible");
+  HMP_CHECK_ARG(d && d_pred && d->z && d->W[0] && d->W[1] && d->bias[0] && d->bias[1], "hmp_linear_heads_predict: null pointer");
+  LinHeadArgs a;
+  memset(&a, 0, sizeof(a));
+  a.z = d->z; a.ldz = d->ldz; a.n_rows = d->n_rows; a.F = d->F;
+  a.classes[0] = d->classes[0]; a.classes[1] = d->classes[1]; a.K = a.classes[0] + a.classes[1];
+  for (int k = 0; k < 2; ++k) {
+    a.W[k] = d->W[k];
+    a.bias[k] = d->bias[k];
+    a.member[k] = d->member[k];
+  }
+  a.act = d->act;
+  if (n_blocks_out) *n_blocks_out = heads_blocks(d->n_rows);
+  return linear_heads_predict_launch(a, d_pred, (hipStream_t)stream);
 }

@@ -586,6 +586,9 @@ constexpr int POOL_TAIL_MAX_CLASSES = 256;  // pooled rows are held in registers
 int pool_tail_ce_launch(TailArgs& a, hipStream_t st);
 int pool_tail_grad_launch(TailArgs& a, hipStream_t st);
 int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st);
+// pred[i][row] = the prediction the count launches compare, for every row of entry i (pool: every pooled row; an empty one: 0);
+// the entries need no labels, mask or row_lv, and a pooled entry no CSC
+int tail_predict_launch(TailArgs& a, int64_t* const* pred, bool pool, hipStream_t st);
 // Two learned linear heads over one final state (heads.hip): y = dropout(act(z)), logits_h = y W_h^T + b_h on the rows of head h,
 // masked CE of both heads with d loss / d z written to `grad` and per-workgroup partial dW / db slabs (fused step), or the
 // first-maximum argmax of both heads compared with the labels (accuracy count, eval mode).
@@ -612,11 +615,13 @@ struct LinHeadArgs {
   int ld_slab;
   int64_t slab_stride;
   unsigned long long* counts;   // accuracy count: {correct_0, total_0, correct_1, total_1}
+  int64_t* pred[2];             // label output: pred[h][row], -1 outside head h's rows (null: head skipped)
   int n_tiles;
 };
 int heads_blocks(int n_rows);
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st);
 int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st);
+int linear_heads_predict_launch(LinHeadArgs& a, int64_t* const* pred, hipStream_t st);
 
 // Room-task validation count (evaluate.hip): first-maximum row argmax compared with the labels of the counted rows
 // ((members == null || members[row]) && label != ignored); ACCUMULATES {correct, total} into counts and, with confusion != null,
@@ -626,6 +631,9 @@ int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const i
 // the same rule per graph: counts[g] += {correct, total} over the rows [graph_ptr[g], graph_ptr[g + 1]) (int64 [n_graphs + 1])
 int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
                                int64_t ignored, const int64_t* graph_ptr, int n_graphs, long long* counts, hipStream_t st);
+
+// pred[row] = first-maximum argmax of x[row, 0:n_classes) (count_rows_launch's prediction), -1 where members[row] == 0
+int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st);
 
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

@@ -2163,6 +2163,58 @@ extern "C" int hmp_net_count_correct_rooms_by_graph(hmp_net* n, const hmp_batch*
                                     batch->d_node_ptr[ot], batch->n_graphs, reinterpret_cast<long long*>(d_counts), st);
 }
 
+// ---- label output: the eval-mode forward of the count entries, then ONE launch that stores the prediction they compare
+extern "C" int hmp_net_predict_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
+                                     int64_t* d_pred, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && (d_pred || batch->n_out == 0), "hmp_net_predict_rooms: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
+                "hmp_net_predict_rooms: a two-headed net predicts with hmp_net_predict2 / hmp_net_predict_heads");
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  Scope sc(n, KC_LOSS, st);
+  return predict_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, d_pred, st);
+}
+
+extern "C" int hmp_net_predict2(hmp_net* n, const hmp_batch* batch, const float* d_params, int64_t* const d_pred[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_pred, "hmp_net_predict2: null argument");
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(S.aux_readout_type >= 0, "hmp_net_predict2: the net has one output (aux_readout_type < 0): use hmp_net_predict_rooms");
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU, "hmp_net_predict2: spec tail_act %d", S.tail_act);
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  hmp_head_targets none;
+  memset(&none, 0, sizeof(none));
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = S.tail_act; ta.state = n->d_state;
+  int64_t* pred[2] = {nullptr, nullptr};
+  for (int h = 0; h < 2; ++h) {
+    if (!d_pred[h]) continue;  // head skipped
+    const int before = ta.n;
+    if (n->has_pools) add_pool(n, batch, &none, h, false, ta);
+    else add_tail(n, batch, &none, h, false, ta);
+    if (ta.n > before) pred[before] = d_pred[h];
+  }
+  if (ta.n == 0) return HMP_OK;
+  Scope sc(n, KC_LOSS, st);
+  return tail_predict_launch(ta, pred, n->has_pools, st);
+}
+
+extern "C" int hmp_net_predict_heads(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2],
+                                     int64_t* const d_pred[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_member && d_pred, "hmp_net_predict_heads: null argument");
+  HMP_CHECK_ARG(n->has_heads, "hmp_net_predict_heads: the net has no linear heads (hmp_net_set_linear_heads)");
+  HMP_CHECK_ARG(!n->compute_bf16, "hmp_net_predict_heads: the linear heads compute in fp32 (bf16 compute mode is not supported)");
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  hmp_linear_head_targets tg;
+  memset(&tg, 0, sizeof(tg));
+  tg.d_member[0] = d_member[0]; tg.d_member[1] = d_member[1];
+  LinHeadArgs a = heads_args(n, batch, &tg, d_params, false, 0);
+  Scope sc(n, KC_LOSS, st);
+  return linear_heads_predict_launch(a, d_pred, st);
+}
+
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,
                                  const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && d_params && d_grads && d_m && d_v && args, "hmp_net_step_adam: null argument");

@@ -132,8 +132,23 @@ __global__ __launch_bounds__(256) void pool_grad_kernel(const TailArgs a) {
   }
 }
 
-// counts[2 * slot] += {#(argmax == label), #rows} over the masked rows of both entries; POOL: the rows are LeafPool means (an empty
-// row is all 0 and predicts 0), else leaf rows of any width
+// The prediction of row `row` of entry T (eval mode: T.drop is off) by its 16 lanes, every lane returns it: the first-maximum argmax
+// of act(z) over a leaf row of any width, or POOL: over the LeafPool mean of the row's leaves (an empty row is all 0 and predicts 0)
+template <bool POOL>
+__device__ __forceinline__ int tail_pred(const HeadTail& T, int act, int row, int lane) {
+  if constexpr (POOL) {
+    float p[PT_Q][4];
+    pool_row(T, T.drop, act, row, lane, p);
+    return argmax_group<TL_GS, PT_Q>(lane, T.classes, [&](int q, int, float (&v)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = p[q][i];
+    });
+  } else {
+    return argmax_group<TL_GS, 0>(lane, T.classes, [&](int, int c, float (&v)[4]) { tail_quad(T, T.drop, act, row, c, v); });
+  }
+}
+
+// counts[2 * slot] += {#(argmax == label), #rows} over the masked rows of both entries
 template <bool POOL>
 __device__ __forceinline__ void tail_count(const TailArgs& a, unsigned long long* __restrict__ counts) {
   __shared__ int s_cnt[2];
@@ -142,17 +157,7 @@ __device__ __forceinline__ void tail_count(const TailArgs& a, unsigned long long
   const int row = tail_row(T);
   const int lane = threadIdx.x % TL_GS;
   if (row < (POOL ? T.n_pool : T.n_rows)) {
-    int pred;
-    if constexpr (POOL) {
-      float p[PT_Q][4];
-      pool_row(T, T.drop, a.act, row, lane, p);
-      pred = argmax_group<TL_GS, PT_Q>(lane, T.classes, [&](int q, int, float (&v)[4]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = p[q][i];
-      });
-    } else {
-      pred = argmax_group<TL_GS, 0>(lane, T.classes, [&](int, int c, float (&v)[4]) { tail_quad(T, T.drop, a.act, row, c, v); });
-    }
+    const int pred = tail_pred<POOL>(T, a.act, row, lane);
     const bool in_mask = T.mask ? T.mask[row] != 0 : true;
     if (lane == 0 && in_mask) count_row(s_cnt, (int64_t)pred == T.labels[row]);
   }
@@ -162,9 +167,30 @@ __device__ __forceinline__ void tail_count(const TailArgs& a, unsigned long long
 __global__ __launch_bounds__(256) void tail_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) { tail_count<false>(a, counts); }
 __global__ __launch_bounds__(256) void pool_count_kernel(const TailArgs a, unsigned long long* __restrict__ counts) { tail_count<true>(a, counts); }
 
+// pred[entry][row] = the row's prediction, for every row of both entries: the counts' arithmetic without labels, mask or counters
+struct TailPred {
+  int64_t* p[2];  // by entry of the launch
+};
+
+template <bool POOL>
+__device__ __forceinline__ void tail_predict(const TailArgs& a, const TailPred& o) {
+  const int e = tail_entry(a);
+  const HeadTail& T = a.h[e];
+  const int row = tail_row(T);
+  if (row >= (POOL ? T.n_pool : T.n_rows)) return;
+  int64_t* __restrict__ out = (e ? o.p[1] : o.p[0]) + row;  // independent of the walk below
+  const int lane = threadIdx.x % TL_GS;
+  const int pred = tail_pred<POOL>(T, a.act, row, lane);
+  if (lane == 0) *out = (int64_t)pred;
+}
+
+__global__ __launch_bounds__(256) void tail_predict_kernel(const TailArgs a, const TailPred o) { tail_predict<false>(a, o); }
+__global__ __launch_bounds__(256) void pool_predict_kernel(const TailArgs a, const TailPred o) { tail_predict<true>(a, o); }
+
 // Checks the entries for a launch and lays their row groups out over the grid.  pool: the heads go through a LeafPool (rows in
-// registers, CSR / CSC or the identity); leaf_rows: one row group per leaf row, else per pooled row; ce: the launch writes gradients.
-int tail_layout(TailArgs& a, bool pool, bool leaf_rows, bool ce, int& blocks) {
+// registers, CSR / CSC or the identity); leaf_rows: one row group per leaf row, else per pooled row; ce: the launch writes gradients;
+// csc: the launch (or its companion) walks the pool plan by leaf -- the predict launch reads the CSR alone.
+int tail_layout(TailArgs& a, bool pool, bool leaf_rows, bool ce, int& blocks, bool csc = true) {
   auto aligned = [](const float* p, int ld, int classes) { return (ld & 3) == 0 && ld >= classes && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const char* who = pool ? "pool tail" : "tail";
   blocks = 0;
@@ -175,7 +201,7 @@ int tail_layout(TailArgs& a, bool pool, bool leaf_rows, bool ce, int& blocks) {
                   "%s: final state must be 16-byte aligned with ld %% 4 == 0 and ld >= %d", who, T.classes);
     HMP_CHECK_ARG(!ce || (T.grad && aligned(T.grad, T.ldg, T.classes)), "%s: gradient must be 16-byte aligned with ld %% 4 == 0", who);
     if (pool) {
-      HMP_CHECK_ARG(T.rowptr ? (T.col && T.t_rowptr && T.t_col) : T.n_pool == T.n_rows,
+      HMP_CHECK_ARG(T.rowptr ? (T.col && (!csc || (T.t_rowptr && T.t_col))) : T.n_pool == T.n_rows,
                     "pool tail: a pooled head needs the plan's CSR and CSC, an unpooled one a row per leaf");
       HMP_CHECK_ARG(!ce || (T.dpool && aligned(T.dpool, T.ldp, T.classes) && T.ldg <= T.ldp),
                     "pool tail: pooled gradient must be 16-byte aligned with ld %% 4 == 0 and no narrower than the gradient");
@@ -205,6 +231,22 @@ int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return t
 int pool_tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_ce_kernel, a, true, false, true, st); }
 int pool_tail_grad_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_grad_kernel, a, true, true, true, st); }
 int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(pool_count_kernel, a, true, false, false, st, u64(counts)); }
+
+// labels of every row of the entries (leaf rows, or pool: pooled rows) into pred[entry]; the entries need no labels, mask or row_lv
+int tail_predict_launch(TailArgs& a, int64_t* const* pred, bool pool, hipStream_t st) {
+  HMP_CHECK_ARG(pred != nullptr, "tail predict: null output array");
+  TailPred o = {{nullptr, nullptr}};
+  for (int i = 0; i < a.n; ++i) {
+    o.p[i] = pred[i];
+    HMP_CHECK_ARG(o.p[i] || (pool ? a.h[i].n_pool : a.h[i].n_rows) == 0, "tail predict: null output of entry %d", i);
+  }
+  int blocks;
+  HMP_TRY(tail_layout(a, pool, !pool, false, blocks, false));
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(pool ? pool_predict_kernel : tail_predict_kernel, dim3(blocks), dim3(256), 0, st, a, o);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
 
 }  // namespace hmp
 
@@ -246,4 +288,26 @@ extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, i
     case 2: HMP_TRY(pool_tail_ce_launch(ta, st)); return pool_tail_grad_launch(ta, st);
     default: return pool_tail_count_launch(ta, (long long*)d_counts, st);
   }
+}
+
+// the predict launchers on the same descriptors (labels, mask, grad, row_lv and dpool may be NULL): d_pred[i] = int64 labels of
+// head i's rows (pooled: of its n_pool rows), eval mode
+extern "C" int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int64_t* const* d_pred, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_head_tails_predict: no gfx950 device visible");
+  HMP_CHECK_ARG(d && d_pred && (n == 1 || n == 2), "hmp_head_tails_predict: null argument or %d heads (1 or 2)", n);
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.n = n; ta.act = act;
+  for (int i = 0; i < n; ++i) {
+    const hmp_tail_desc& q = d[i];
+    HMP_CHECK_ARG(q.z && q.n_rows >= 0 && q.n_pool >= 0, "hmp_head_tails_predict: null state or negative rows (head %d)", i);
+    HeadTail& T = ta.h[i];
+    T.z = q.z; T.ldz = q.ldz; T.n_rows = q.n_rows; T.classes = q.classes;
+    T.slot = q.slot;
+    T.rowptr = q.rowptr; T.col = q.col; T.t_rowptr = q.t_rowptr; T.t_col = q.t_col;
+    T.n_pool = q.n_pool;
+  }
+  return tail_predict_launch(ta, d_pred, pooled != 0, (hipStream_t)stream);
 }

@@ -614,6 +614,94 @@ class NativeNet:
                     counts.data_ptr())
         return counts
 
+    def predict_labels(self, batch, out=None, members=None):
+        """The labels the count entries compare, on the device: eval-mode native forward plus ONE launch (``hmp_net_predict_rooms``
+        / ``hmp_net_predict2`` / ``hmp_net_predict_heads``, picked by the net's kind).  ``batch`` is a data object or a descriptor
+        from ``store.BatchStream.next``; no labels are needed.
+
+        * room task: an int64 tensor with a label per output row, ``-1`` where ``members`` (a bool row filter; a stream of
+          homogeneous graphs brings its ``room_mask`` rows) is False;
+        * two-headed net with an aux readout: a pair, one label per row of ``head_label_types()`` (pooled heads: per pooled row);
+        * linear heads: a pair of per-row vectors, ``-1`` outside each head's rows.  ``members = (room rows, object rows | None)``
+          for a data batch (None = the complement of the room rows); a two-headed stream brings its own.
+
+        ``out`` takes caller-owned contiguous device int64 buffers (one, or a pair) of at least the needed rows; the result is a
+        view of their leading rows.  Nothing synchronises."""
+        flat = self.flat_params(full_check=False)
+        dev = flat.device
+        stream = None
+        if isinstance(batch, _BatchHolder):
+            h = batch
+            stream = h.stream
+            if stream is not None and stream.nat is not self:
+                raise _lib.HydraMPError("predict_labels: the batch comes from a stream created for another model")
+        else:
+            h = self.make_batch(batch)
+        two = self.aux_readout is not None or self.heads is not None
+        if self.heads is not None:
+            rows = [int(h.c.n_out)] * 2
+        elif two:
+            rows = [h.n_nodes[self.node_types.index(t)] for t in self.head_label_types()]
+        else:
+            rows = [int(h.c.n_out)]
+        outs = _label_buffers(out, rows, two, dev)
+        if self.heads is not None:
+            if stream is not None and members is None:
+                m0, m1 = stream.member_rows()
+            else:
+                if members is None or len(members) != 2 or members[0] is None:
+                    raise _lib.HydraMPError("predict_labels: a net with linear heads needs members=(room rows, object rows | None)")
+                from .ops import row_members
+
+                keep = [row_members(m, rows[0], dev) if m is not None else None for m in members]
+                m0, m1 = (k.data_ptr() if k is not None and rows[0] > 0 else None for k in keep)
+            mem = (C.c_void_p * 2)(m0, m1)
+            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
+            self._count("hmp_net_predict_heads", h, dev, flat.data_ptr(), mem, prd)
+        elif two:
+            if members is not None:
+                raise _lib.HydraMPError("predict_labels: the heads of an aux-readout net are whole node types (no members)")
+            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
+            self._count("hmp_net_predict2", h, dev, flat.data_ptr(), prd)
+        else:
+            if members is None and stream is not None and getattr(stream, "homog_room", False):
+                members_ptr = stream.members.data_ptr()
+            else:
+                from .ops import row_members
+
+                members = row_members(members, rows[0], dev)
+                members_ptr = members.data_ptr() if members is not None else None
+            self._count("hmp_net_predict_rooms", h, dev, flat.data_ptr(), members_ptr, outs[0].data_ptr())
+        views = tuple(o[:n] for o, n in zip(outs, rows))
+        return views if two else views[0]
+
+    def predict_pair(self, batch, members=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`predict_labels` of a two-headed net on the host: both label vectors land in ONE device buffer and cross in one
+        D2H through one pinned buffer and one event, as :meth:`predict` does for the room task.  Returns host int64 views of that
+        buffer (valid until the next call)."""
+        if self.aux_readout is None and self.heads is None:
+            raise _lib.HydraMPError("predict_pair: the net has one output; use predict()")
+        flat = self.flat_params(full_check=False)
+        dev = flat.device
+        h = batch if isinstance(batch, _BatchHolder) else self.make_batch(batch)
+        if self.heads is not None:
+            rows = [int(h.c.n_out)] * 2
+        else:
+            rows = [h.n_nodes[self.node_types.index(t)] for t in self.head_label_types()]
+        n = rows[0] + rows[1]
+        with torch.cuda.device(dev):
+            if getattr(self, "_pred_dev", None) is None or self._pred_dev.numel() < n or self._pred_dev.device != dev:
+                cap = max(256, 2 * n)
+                self._pred_dev = torch.empty(cap, dtype=torch.int64, device=dev)
+                self._pred_host = torch.empty(cap, dtype=torch.int64).pin_memory()
+                self._pred_done = torch.cuda.Event()
+            self.predict_labels(h, out=(self._pred_dev[:rows[0]], self._pred_dev[rows[0]:n]), members=members)
+            if n > 0:
+                self._pred_host[:n].copy_(self._pred_dev[:n], non_blocking=True)
+            self._pred_done.record()
+            self._pred_done.synchronize()
+        return self._pred_host[:rows[0]], self._pred_host[rows[0]:n]
+
     def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
         """the count entries' common block: ``entry(handle, batch, *args, stream)`` (eval-mode forward + count on the device),
         which overwrites the activations of any earlier forward()"""
@@ -681,6 +769,20 @@ class NativeNet:
         step, status = C.c_int32(), C.c_int32()
         _lib.check(self._lib.hmp_net_read_state(self._handle, C.byref(step), C.byref(status), _lib.stream_ptr()))
         return step.value, status.value
+
+
+def _label_buffers(out, rows: Sequence[int], pair: bool, dev) -> List[torch.Tensor]:
+    """the int64 label outputs of ``predict_labels``: fresh ones, or the caller's ``out`` after its checks"""
+    if out is None:
+        return [torch.empty(max(n, 1), dtype=torch.int64, device=dev) for n in rows]
+    outs = list(out) if pair and isinstance(out, (tuple, list)) else [out]
+    if len(outs) != len(rows) or not all(isinstance(o, torch.Tensor) for o in outs):
+        raise _lib.HydraMPError(f"out: {'a pair of tensors (one per head)' if pair else 'one tensor'} expected")
+    for o, n in zip(outs, rows):
+        if o.dtype != torch.int64 or not o.is_contiguous() or o.device != dev or o.dim() != 1 or o.numel() < n:
+            raise _lib.HydraMPError(f"out must be contiguous 1-d int64 tensors on {dev} with at least {n} rows, got "
+                                    f"{tuple(o.shape)} {o.dtype} on {o.device}")
+    return outs
 
 
 def _check_counts4(counts: torch.Tensor, dev) -> None:

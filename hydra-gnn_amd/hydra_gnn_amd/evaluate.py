@@ -1,4 +1,5 @@
-"""Validation accuracy on the device (room task: :func:`accuracy`; two-headed task: :func:`semisupervised_accuracy`): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
+"""Validation accuracy on the device (room task: :func:`accuracy`; two-headed task: :func:`semisupervised_accuracy`) and the
+predicted labels themselves (:func:`predict`, every model and task): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
 per batch.
 
 The reference's ``test()`` runs an eval-mode forward per batch, takes ``argmax(dim=1)``, drops the rows whose label is the
@@ -107,3 +108,78 @@ def semisupervised_accuracy(model, batches: Union[Iterable, Tuple[object, Iterab
     if type_separated:
         return correct_room / total_room, correct_object / total_object
     return (correct_room + correct_object) / (total_room + total_object)
+
+
+def _label_types(model):
+    """node types whose rows the label vectors of ``model.predict_labels`` follow: one per head"""
+    nat = model.native()
+    if nat.aux_readout is not None:
+        return tuple(nat.head_label_types())
+    out_type = nat.pool_edge_type[2] if nat.pool_edge_type is not None else nat.readout
+    return (out_type, out_type) if nat.heads is not None else (out_type,)
+
+
+def _split_rows(host: np.ndarray, counts: np.ndarray):
+    """per-graph pieces of a label vector, the -1 rows (outside the head's rows) dropped"""
+    off = np.concatenate([[0], np.cumsum(counts)])
+    pieces = [host[off[g]:off[g + 1]] for g in range(len(counts))]
+    return [p[p >= 0] for p in pieces]
+
+
+def predict(model, batches: Union[Iterable, Tuple[object, Iterable]]):
+    """Predicted labels over ``batches`` with ONE device-to-host copy at the end of the pass (``model.predict_labels`` per batch:
+    eval-mode forward plus one launch, nothing synchronises in between).  ``batches`` takes the two forms :func:`accuracy` takes.
+
+    ``(BatchStream, iterable of graph-id lists)``: the label buffers of the whole pass are allocated once from the store's
+    per-graph node counts, every batch writes its slice, and the result is a list with one entry per graph in id order -- a numpy
+    int64 array (room task) or a ``(room, object)`` pair of arrays (two-headed), each what ``model.predict`` returns for that graph
+    alone (the ``-1`` rows outside a head's rows are dropped on the host; the labels are a few KB, so nothing is compacted on the
+    device).  An iterable of batches on the model's device: one entry per BATCH, the per-row vectors of ``predict_labels`` (``-1``
+    rows kept: a collated homogeneous batch carries no graph offsets to split by)."""
+    from . import _lib
+    from .store import BatchStream
+
+    streamed = isinstance(batches, tuple) and len(batches) >= 1 and isinstance(batches[0], BatchStream)
+    if streamed and len(batches) != 2:
+        raise _lib.HydraMPError("predict: a stream is passed as the pair (BatchStream, iterable of graph-id lists)")
+    if batches is None or isinstance(batches, (str, bytes)) or not hasattr(batches, "__iter__"):
+        raise _lib.HydraMPError("predict: batches must be an iterable of batches or a (BatchStream, iterable of graph-id lists) pair")
+    if streamed:
+        stream, id_lists = batches
+        if id_lists is None or isinstance(id_lists, (str, bytes)) or not hasattr(id_lists, "__iter__"):
+            raise _lib.HydraMPError("predict: the second element of the pair must be an iterable of graph-id lists")
+        id_lists = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
+        if any(ids.size == 0 for ids in id_lists):
+            raise _lib.HydraMPError("predict: an empty graph-id list")
+        if stream.nat is not model.native():
+            raise _lib.HydraMPError("predict: the stream was created for another model")
+    dev = next(model.parameters()).device
+    if not streamed:
+        outs = [model.predict_labels(b) for b in batches]
+        two = bool(outs) and isinstance(outs[0], tuple)
+        flat = [t for o in outs for t in (o if two else (o,))]
+        if not flat:
+            return []
+        host = torch.cat(flat).cpu().numpy()  # the one copy of the pass
+        sizes = np.cumsum([0] + [t.numel() for t in flat])
+        parts = [host[sizes[i]:sizes[i + 1]] for i in range(len(flat))]
+        return [(parts[2 * i], parts[2 * i + 1]) for i in range(len(outs))] if two else parts
+    types = _label_types(model)
+    two = len(types) == 2
+    all_ids = np.concatenate(id_lists) if id_lists else np.zeros(0, dtype=np.int64)
+    counts = [stream.store.node_counts[t][all_ids] for t in types]
+    totals = [int(c.sum()) for c in counts]
+    buf = torch.empty(max(sum(totals), 1), dtype=torch.int64, device=dev)  # head 0's rows of the whole pass, then head 1's
+    pos = [0, totals[0]]
+    for ids in id_lists:
+        rows = [int(stream.store.node_counts[t][ids].sum()) for t in types]
+        views = [buf[pos[k]:pos[k] + rows[k]] for k in range(len(types))]
+        model.predict_labels(stream.next(ids), out=tuple(views) if two else views[0])
+        for k in range(len(types)):
+            pos[k] += rows[k]
+    host = buf[:sum(totals)].cpu().numpy()  # the one copy (and synchronisation) of the pass
+    heads = [_split_rows(host[:totals[0]], counts[0])]
+    if two:
+        heads.append(_split_rows(host[totals[0]:], counts[1]))
+        return list(zip(heads[0], heads[1]))
+    return heads[0]

@@ -414,6 +414,31 @@ class BaseTrainingJob:
                 return evaluate.accuracy(net, batches, self.ignored_label(), get_per_label_accuracy)
         return evaluate.accuracy(net, (b.to(device) for b in data_loader), self.ignored_label(), get_per_label_accuracy)
 
+    def predict(self, split):
+        """Predicted labels of every graph of the split ``"train"`` / ``"val"`` / ``"test"``, from the job's own device-resident copy
+        in ``batch_size`` batches with one device-to-host copy per pass (``evaluate.predict``): a list with one numpy int64 array
+        per graph, the labels ``model.predict`` returns for that graph alone."""
+        return self._predict_pass(split, self.get_dataset(split))
+
+    def _predict_pass(self, name, dataset):
+        net = self._net
+        net.eval()
+        device = next(net.parameters()).device
+        B = self._training_params["optimization_params"]["batch_size"]
+        chunks = id_chunks(len(dataset), B)
+        with torch.cuda.device(device):
+            if self._streams_batches():
+                return evaluate.predict(net, (self._stream(name, dataset, device, B), chunks))
+            # GCN / GIN: collated batches keep no graph offsets; the per-node vectors are split by the store's node counts
+            store = self._store(name, dataset, device)
+            per_batch = evaluate.predict(net, (store.collate(ids) for ids in chunks))
+        nodes = store.node_counts[store.node_types[0]]
+        out = []
+        for ids, labels in zip(chunks, per_batch):
+            heads = [evaluate._split_rows(v, nodes[ids]) for v in (labels if isinstance(labels, tuple) else (labels,))]
+            out.extend(zip(*heads) if isinstance(labels, tuple) else heads[0])
+        return out
+
     def test_individual_graph(self, dataset, model=None):
         """``(correct, total)`` of every graph of ``dataset`` (:315-339): the dataset is uploaded once (and kept, like the splits),
         counted in ``batch_size`` batches with one forward and one per-graph count launch each
@@ -585,6 +610,12 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
             else:
                 batches = (b.to(device) for b in data_loader)
             return evaluate.semisupervised_accuracy(net, batches, mask_name, get_type_separated_accuracy)
+
+    def predict(self, split=None):
+        """Predicted ``(room_labels, object_labels)`` of every graph of the job's dataset (one pair of numpy int64 arrays per graph,
+        what ``model.predict`` returns for that graph alone), from its device-resident copy in ``batch_size`` batches with one
+        device-to-host copy per pass."""
+        return self._predict_pass("all", self._dataset)
 
     def test_individual_graph(self, dataset, model=None):
         return NotImplemented

@@ -65,12 +65,29 @@ class _NativeModule(nn.Module):
 
     def predict(self, data):
         """Room labels of ``data`` on the host: ``self(data).argmax(dim=1).cpu()`` as ``GnnModel.infer`` computes it
-        (bin/room_classification_server:285-286), through the native inference path (:meth:`NativeNet.predict`)."""
+        (bin/room_classification_server:285-286), through the native inference path (:meth:`NativeNet.predict`).
+        A two-headed model returns host int64 ``(room_labels, object_labels)`` =
+        ``tuple(p.argmax(dim=1).cpu() for p in self(data))`` in eval mode, with one D2H for both (:meth:`NativeNet.predict_pair`)."""
+        if getattr(self, "classification_task", "room") == "all":
+            return self._predict_two(data)
         net = self.native()
         view = getattr(self, "_view", None)
         labels = net.predict(view(data) if view is not None else data, net.layers[-1].out_dims[net.readout])
         mask = getattr(data, "room_mask", None) if view is not None else None
         return labels if mask is None else labels[mask.cpu()]
+
+    def _predict_two(self, data):
+        """heterogeneous two-headed models: one label per ``rooms`` / ``objects`` row (H-tree: per ``room_virtual`` /
+        ``object_virtual`` row)"""
+        return self.native().predict_pair(data)
+
+    def predict_labels(self, data, out=None):
+        """The labels :meth:`predict` returns, left on the device (int64; nothing synchronises): eval-mode native forward plus one
+        launch (:meth:`NativeNet.predict_labels`).  Room task: one label per output row; two-headed: a pair, one label per row of
+        each head's label type.  ``data`` is a batch or a descriptor from ``store.BatchStream.next``; ``out`` takes caller-owned
+        contiguous device int64 buffers (one, or a pair) of at least the needed rows."""
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        return self.native().predict_labels(data, out=out)
 
     def loss(self, pred, label, mask=None):
         return cross_entropy_loss(pred, label, mask)

@@ -269,9 +269,66 @@ class HomogeneousNetwork(_NativeModule):
         return ops.count_correct_rows_by_graph(self._eval_states(data), data.y, counts, graph_ptr, ignored_label,
                                                members=data.room_mask)
 
+    def _object_rows(self, data):
+        """rows of the object head, or None for the complement of ``room_mask`` (reference :147)"""
+        return getattr(data, self._OBJECT_ATTR) if self._OBJECT_ATTR is not None else None
+
+    def _eval_heads(self, data):
+        """GCN / GIN: both heads' logits of an eval-mode op-by-op forward (the training flag is put back)"""
+        was = self.training
+        self.train(False)
+        try:
+            with torch.no_grad():
+                return self(data)
+        finally:
+            if was:
+                self.train(True)
+
+    def predict_labels(self, data, out=None):
+        """Labels on the device, one int64 per NODE (the native output has a row per node; nothing is compacted): room task:
+        the room label on the rows of ``data.room_mask``, ``-1`` elsewhere; two-headed: a pair ``(room, object)`` of such vectors,
+        ``-1`` outside ``room_mask`` and outside the object head's rows (``~room_mask``; H-tree: ``object_mask``).  ``data`` may be
+        a descriptor from ``store.BatchStream.next``, which brings those rows.  SAGE / GAT: eval-mode native forward plus one launch
+        (:meth:`NativeNet.predict_labels`), nothing synchronises.  GCN / GIN: the op-by-op eval forward, then
+        ``hmp_predict_rows`` (room task) or ``hmp_argmax_rows`` per head scattered to the head's rows (two-headed) -- this path may
+        synchronise inside torch (boolean row selection), as its ``forward()`` does."""
+        from .._lib import require_device
+        from ..engine import _BatchHolder
+
+        require_device()  # no device: HydraMPError (there is no CPU fallback)
+        two = self.classification_task == "all"
+        if isinstance(data, _BatchHolder):
+            if self.op_path:
+                raise HydraMPError(f"predict_labels: {self.conv_block} runs op by op: pass a collated Data batch")
+            return self.native().predict_labels(data, out=out)
+        if not self.op_path:
+            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
+            return self.native().predict_labels(self._view(data), out=out, members=members)
+        if not two:
+            return ops.predict_rows(self._eval_states(data), data.room_mask, out)
+        from ..engine import _label_buffers
+
+        n = data.x.size(0)
+        outs = _label_buffers(out, [n, n], True, data.x.device)
+        obj = self._object_rows(data)
+        for o, logits, rows in zip(outs, self._eval_heads(data), (data.room_mask, ~data.room_mask if obj is None else obj)):
+            o[:n].fill_(-1)
+            o[:n][rows] = ops.argmax_rows(logits)
+        return outs[0][:n], outs[1][:n]
+
+    def _predict_two(self, data):
+        """host ``(room_labels, object_labels)``: the labels of the ``room_mask`` rows and of the object head's rows, in row order
+        (the -1 rows of :meth:`predict_labels` dropped on the host)"""
+        if self.op_path:
+            return tuple(ops.argmax_rows(p).cpu() for p in self._eval_heads(data))
+        pair = self.native().predict_pair(self._view(data), members=(data.room_mask, self._object_rows(data)))
+        return tuple(p[p >= 0] for p in pair)
+
     def predict(self, data):
+        """Room labels of ``data.room_mask``'s rows on the host (``GnnModel.infer``); a two-headed model returns host int64
+        ``(room_labels, object_labels)`` = ``tuple(p.argmax(dim=1).cpu() for p in self(data))`` in eval mode."""
         if self.classification_task != "room":
-            raise NotImplementedError("predict() returns room labels (the server's task)")
+            return self._predict_two(data)
         if not self.op_path:
             return super().predict(data)
         with torch.no_grad():

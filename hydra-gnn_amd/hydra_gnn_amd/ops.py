@@ -276,6 +276,29 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def predict_rows(logits: torch.Tensor, members: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``logits.argmax(dim=1)`` (first maximum) as int64 on the device, ``-1`` where the bool row filter ``members`` is False
+    (``hmp_predict_rows``: the prediction :func:`count_correct_rows` compares).  ``out``: a contiguous int64 tensor of at least
+    ``rows`` entries on the same device.  Nothing synchronises."""
+    _dev(logits, "logits")
+    logits = _rows(logits)
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise _lib.HydraMPError(f"logits must be [rows, classes >= 1], got {tuple(logits.shape)}")
+    n = logits.size(0)
+    members = row_members(members, n, logits.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=logits.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != logits.device
+          or out.dim() != 1 or out.numel() < n):
+        raise _lib.HydraMPError(f"out must be a contiguous 1-d int64 tensor on {logits.device} with at least {n} rows")
+    if n:
+        with torch.cuda.device(logits.device):
+            _lib.check(_lib.load().hmp_predict_rows(logits.data_ptr(), logits.stride(0), n, logits.size(1),
+                                                    members.data_ptr() if members is not None else None, out.data_ptr(),
+                                                    _lib.stream_ptr()))
+    return out[:n]
+
+
 def check_count_buffers(counts: torch.Tensor, confusion: Optional[torch.Tensor], n_classes: int, device) -> None:
     """the accumulators of the room-task validation count: ``counts`` contiguous int64[>= 2], ``confusion`` (optional) contiguous
     int64 with ``n_classes ** 2`` elements, both on ``device``"""

@@ -491,6 +491,15 @@ class BatchStream:
         self._targets[mask] = (tg, C.byref(tg))
         return self._targets[mask][1]
 
+    def member_rows(self):
+        """addresses of the collated head rows of a linear-head stream, (room rows, object rows or None = their complement): what
+        :meth:`targets` holds, for the entries that take no labels (``NativeNet.predict_labels``)"""
+        self.targets(None)
+        tg = self._targets[None][0]
+        if self._target_kind != "linear":
+            raise _lib.HydraMPError("member_rows: the stream's heads are whole node types (no member rows)")
+        return tg.d_member[0], tg.d_member[1]
+
     def next(self, ids) -> "object":
         """collate graphs ``ids`` (len == batch_size or fewer) into the stream's buffers; returns the descriptor for TrainStep.run"""
         sel = np.ascontiguousarray(ids, dtype=np.int32)

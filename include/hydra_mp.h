@@ -41,7 +41,9 @@ extern "C" {
  *    hmp_collator_set_label_filter (room-masked labels in the collation launch), hmp_count_correct_rows_by_graph /
  *    hmp_net_count_correct_rooms_by_graph (per-graph validation counts): new entries, no struct changed layout;
  *    hmp_tail_desc (hmp_sizeof 14), hmp_linear_heads_desc (hmp_sizeof 15), hmp_head_tails / hmp_linear_heads_run: test and
- *    diagnostic entries of the readout tail and linear-head launchers: new entries, no struct changed layout */
+ *    diagnostic entries of the readout tail and linear-head launchers: new entries, no struct changed layout;
+ *    hmp_predict_rows, hmp_net_predict_rooms / hmp_net_predict2 / hmp_net_predict_heads (labels instead of counts, for every net
+ *    kind), hmp_head_tails_predict / hmp_linear_heads_predict (their test entries): new entries, no struct changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -231,6 +233,11 @@ int hmp_count_correct_rows(const float* d_logits, int32_t ld, int32_t n_rows, in
 int hmp_count_correct_rows_by_graph(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
                                     const uint8_t* d_members, int64_t ignored_label, const int64_t* d_graph_ptr, int32_t n_graphs,
                                     int64_t* d_counts, void* stream);
+/* the prediction hmp_count_correct_rows compares, written out: d_pred[r] (device int64 [n_rows]) = first-maximum argmax of
+ * d_logits[r, 0:n_classes), or -1 where d_members[r] == 0 (d_members NULL: every row).  Every row in [0, n_rows) is written.  One
+ * launch; n_rows == 0 launches nothing; nothing synchronises.  (ABI-4-compatible addition.) */
+int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int64_t* d_pred,
+                     void* stream);
 /* d_count: device float holding the valid-label count (grad_scale = 1/max(count,1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
@@ -271,6 +278,11 @@ typedef struct hmp_tail_desc {
  * 3: the pooled accuracy count.  act: HMP_ACT_*.  A count row counts iff its mask byte is set (or mask is NULL). */
 int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
                    int64_t* d_counts, void* stream);
+/* The label launch of the same descriptors (eval mode): d_pred[i] (device int64) receives the prediction the count of mode 1
+ * (pooled != 0: mode 3) compares, for EVERY row of head i -- its n_rows leaf rows, or its n_pool pooled rows (an empty pooled row
+ * predicts 0).  labels, mask, grad, row_lv, dpool, t_rowptr and t_col may be NULL.  One launch for both heads.  (ABI-4-compatible
+ * addition, like hmp_linear_heads_predict below.) */
+int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int64_t* const* d_pred, void* stream);
 /* Two linear heads over one final state z [n_rows][ldz]: logits_h = dropout(act(z)) W_h^T + b_h on the rows of head h (member[0]
  * NULL: every row; member[1] NULL: the complement of member[0], empty when both are NULL), W_h [classes[h]][F] dense.
  * grad [n_rows][ldg], ldg == F rounded up to 4 (columns F .. ldg written 0); row_lv [n_rows][2] = {loss_0 + loss_1, valid_0 + valid_1};
@@ -296,6 +308,9 @@ typedef struct hmp_linear_heads_desc {
  * d_counts (device int64[4]).  *n_blocks_out (may be NULL) = the workgroups launched = min(ceil(n_rows / 32), 240). */
 int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts, int32_t* n_blocks_out,
                          void* stream);
+/* The label launch (eval mode): d_pred[h] (device int64 [n_rows], NULL: head skipped) = first-maximum argmax of head h's logits
+ * for the rows of member[h] (the rule above), -1 elsewhere.  labels, mask, grad, row_lv and slabs may be NULL. */
+int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 6. network executor -- the whole HeteroConv layer stack as one native program.
@@ -522,6 +537,22 @@ int hmp_net_count_correct_rooms(hmp_net* net, const hmp_batch* batch, const floa
  * hmp_net_count_correct_rooms.  (ABI-4-compatible addition.) */
 int hmp_net_count_correct_rooms_by_graph(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
                                          int64_t ignored_label, int64_t* d_counts, void* stream);
+/* Label output of every net kind: the eval-mode forward of the count entries, then exactly ONE launch that stores the prediction
+ * they compare (int64, first maximum).  No labels are needed in the batch; batch->plan_valid is honoured as hmp_net_forward honours
+ * it; the activations of the last forward are overwritten; nothing allocates or synchronises.  Refusals mirror the count entries
+ * (wrong net kind, null arguments, unbound workspace).  (ABI-4-compatible additions.)
+ * room task (one output): d_pred [n_out] = argmax of the program's output row, -1 where d_members[row] == 0 (d_members NULL: every
+ * row).  Two-headed nets are refused. */
+int hmp_net_predict_rooms(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, int64_t* d_pred,
+                          void* stream);
+/* two-headed nets with aux readout: d_pred[0] one label per readout row, d_pred[1] per aux row, argmax of act(z); with
+ * hmp_net_set_head_pools one label per DESTINATION row of each pooled head (empty row: 0).  Either pointer may be NULL (head
+ * skipped). */
+int hmp_net_predict2(hmp_net* net, const hmp_batch* batch, const float* d_params, int64_t* const d_pred[2], void* stream);
+/* linear heads: d_pred[h] [n_out] = argmax of head h's logits on act(z) for the rows of d_member[h] (hmp_linear_head_targets'
+ * member rule, d_member[1] NULL = complement of d_member[0]), -1 elsewhere.  Either d_pred pointer may be NULL (head skipped). */
+int hmp_net_predict_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2],
+                          int64_t* const d_pred[2], void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
