@@ -13,6 +13,10 @@
 // the backward recomputes alpha from the saved per-row (max, denominator).  Logits are computed redundantly by
 // every lane of the group (H exps per neighbour per lane: cheap next to the gather).
 //
+// Wide heads (256 < Cp <= 512, H <= 4): the same 64-lane group, every lane owning R = 2 slices per head, channels
+// 4g..4g+3 and 256+4g..256+4g+3.  Everything per row and per edge (logits, softmax state, the LDS parking of backward
+// pass 1, dropout numbering) is per head and does not change; only the channel loops run over the R slices.
+//
 // Self loops (add_self_loops=True for same-type edges): entries with col == row are skipped ("remove_self_loops")
 // and one loop i->i is appended after the row's edges for i < min(N_src, N_dst); its edge-attribute term is 0
 // (the reference's fill_value for GAT_edge is zeros(3): heterogeneous_network.py:77-78).
@@ -142,18 +146,18 @@ __device__ __forceinline__ void load_row_consts(const GatInS& I, int H, int row,
 // together (second round trip).  The per-edge arithmetic that follows is the sequential code's, edge by edge, in the same
 // order: results are bit-identical to the unbatched kernels, the dependent chain is 2 round trips per UB edges instead of
 // 2 per edge.  Slots outside the row are clamped to valid addresses and flagged dead.
-template <int HM, int UB>
+template <int HM, int UB, int R = 1>
 struct EdgeBatch {
   int j[UB], eid[UB];
   bool live[UB], loop[UB], removed[UB];  // removed: an explicit self loop that add_self_loops replaces (PyG remove_self_loops)
   float raw[UB][HM];
-  float4 v[UB][HM];
+  float4 v[UB][R][HM];
 };
 
-template <int HM, int UB>
+template <int HM, int UB, int R>
 __device__ __forceinline__ void fetch_batch(const GatInS& I, int Cp, const float* __restrict__ ea, int H, int row, int b, int e, int kend,
-                                            int k0, int cc, const float (&ad)[HM], const float (&ve)[GAT_MAX_EDIM][HM],
-                                            EdgeBatch<HM, UB>& B) {
+                                            int k0, const int (&cc)[R], const float (&ad)[HM], const float (&ve)[GAT_MAX_EDIM][HM],
+                                            EdgeBatch<HM, UB, R>& B) {
 #pragma unroll
   for (int u = 0; u < UB; ++u) {
     const int k = k0 + u;
@@ -172,16 +176,37 @@ __device__ __forceinline__ void fetch_batch(const GatInS& I, int Cp, const float
 #pragma unroll
   for (int u = 0; u < UB; ++u) {
     edge_logits<HM>(I, ea, H, I.za + (int64_t)B.j[u] * I.ldza, ad, ve, !B.loop[u] && B.live[u], B.eid[u], B.raw[u]);
-    const float* zj = I.z + (int64_t)B.j[u] * I.ldz + I.hoff + cc;
+    const float* zj = I.z + (int64_t)B.j[u] * I.ldz + I.hoff;
 #pragma unroll
-    for (int h = 0; h < HM; ++h) B.v[u][h] = ld4(zj + min(h, H - 1) * Cp);  // heads >= H: a duplicate nobody reads
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int h = 0; h < HM; ++h) B.v[u][r][h] = ld4(zj + min(h, H - 1) * Cp + cc[r]);  // heads >= H: a duplicate nobody reads
   }
 }
+
+// The R channel slices of lane gl: slice r starts at channel 4*gl + 256*r and is active below Cp.  Inactive slices load
+// from channel 0 (always there) and are masked afterwards, like the head index.
+template <int R>
+struct Slices {
+  int c0[R], cc[R];
+  bool act[R];
+  __device__ __forceinline__ Slices(int gl, int Cp) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      c0[r] = gl * 4 + r * 256;
+      act[r] = c0[r] < Cp;
+      cc[r] = act[r] ? c0[r] : 0;
+    }
+  }
+};
+// fetch-batch depth by register footprint: H*R slices of 4 floats per neighbour in flight
+template <int HM, int R>
+constexpr int batch_depth() { return (HM * R <= 4) ? 4 : 2; }
 
 // =================================================================================================
 // forward
 // =================================================================================================
-template <int HM, int GS>
+template <int HM, int GS, int R = 1>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restrict__ tab, const GatDyn dyn) {
   int di = 0;
   while (di + 1 < tab->n_dst && (int)blockIdx.x >= dyn.block_start[di + 1]) ++di;
@@ -189,13 +214,15 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
   const int rpb = 256 / GS;
   const int row = ((int)blockIdx.x - dyn.block_start[di]) * rpb + (int)threadIdx.x / GS;
   if (row >= dyn.n_nodes[D.t]) return;
-  const int gl = threadIdx.x % GS, c0 = gl * 4;
-  const bool cact = c0 < D.Cp;
+  const int gl = threadIdx.x % GS;
+  const Slices<R> sl(gl, D.Cp);
   const int H = D.H;
 
-  float4 tot[HM];
+  float4 tot[R][HM];
 #pragma unroll
-  for (int h = 0; h < HM; ++h) tot[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int h = 0; h < HM; ++h) tot[r][h] = make_float4(0.f, 0.f, 0.f, 0.f);
 
   for (int ii = 0; ii < D.n_in; ++ii) {
     const GatInS& I = D.in[ii];
@@ -209,17 +236,20 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
     if (adrop) acfg = make_cfg(dyn, I.adrop_p, I.adrop_stream);
 
     float m[HM], s[HM];
-    float4 acc[HM];
+    float4 acc[R][HM];
 #pragma unroll
-    for (int h = 0; h < HM; ++h) { m[h] = -INFINITY; s[h] = 0.f; acc[h] = make_float4(0.f, 0.f, 0.f, 0.f); }
+    for (int h = 0; h < HM; ++h) {
+      m[h] = -INFINITY; s[h] = 0.f;
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r][h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
 
     const int b = glob(I.rowptr)[row], e = glob(I.rowptr)[row + 1];
     const int kend = e + ((row < n_loop) ? 1 : 0);
-    constexpr int UB = (HM <= 4) ? 4 : 2;
-    const int cc = cact ? c0 : 0;
+    constexpr int UB = batch_depth<HM, R>();
     for (int k0 = b; k0 < kend; k0 += UB) {
-      EdgeBatch<HM, UB> B;
-      fetch_batch<HM, UB>(I, D.Cp, ea, H, row, b, e, kend, k0, cc, ad, ve, B);
+      EdgeBatch<HM, UB, R> B;
+      fetch_batch<HM, UB, R>(I, D.Cp, ea, H, row, b, e, kend, k0, sl.cc, ad, ve, B);
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         if (!B.live[u]) continue;
@@ -237,12 +267,14 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
           s[h] = s[h] * sc + p;
           float w = p;
           if (adrop) w = keep[h] ? p * acfg.scale : 0.f;
-          if (cact) {
-            const float4 v = B.v[u][h];
-            acc[h].x = acc[h].x * sc + w * v.x;
-            acc[h].y = acc[h].y * sc + w * v.y;
-            acc[h].z = acc[h].z * sc + w * v.z;
-            acc[h].w = acc[h].w * sc + w * v.w;
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            if (!sl.act[r]) continue;
+            const float4 v = B.v[u][r][h];
+            acc[r][h].x = acc[r][h].x * sc + w * v.x;
+            acc[r][h].y = acc[r][h].y * sc + w * v.y;
+            acc[r][h].z = acc[r][h].z * sc + w * v.z;
+            acc[r][h].w = acc[r][h].w * sc + w * v.w;
           }
           m[h] = mn;
         }
@@ -252,14 +284,18 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
     for (int h = 0; h < HM; ++h) {
       if (h >= H) continue;
       const float den = s[h] + 1e-16f;
-      tot[h].x += acc[h].x / den; tot[h].y += acc[h].y / den; tot[h].z += acc[h].z / den; tot[h].w += acc[h].w / den;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        tot[r][h].x += acc[r][h].x / den; tot[r][h].y += acc[r][h].y / den;
+        tot[r][h].z += acc[r][h].z / den; tot[r][h].w += acc[r][h].w / den;
+      }
       if (gl == 0) {
         globw(I.smax)[(int64_t)row * GAT_HMAX + h] = m[h];
         globw(I.sden)[(int64_t)row * GAT_HMAX + h] = den;
       }
     }
   }
-  if (!cact) return;
+  if (!sl.act[0]) return;  // slice 1 is never active without slice 0
 
   const bool fdrop = dyn.training && D.drop_p > 0.f;
   DropCfg fcfg = {};
@@ -271,28 +307,33 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const GatLayerS* __restric
     return act_drop(v, D.act, fdrop, k4[col & 3], fcfg.scale);
   };
   auto orow = globw(D.out) + (int64_t)row * D.ldo;
-  if (D.concat) {
 #pragma unroll
-    for (int h = 0; h < HM; ++h) {
-      if (h >= H) continue;
-      const float t4[4] = {tot[h].x, tot[h].y, tot[h].z, tot[h].w};
+  for (int r = 0; r < R; ++r) {
+    if (!sl.act[r]) continue;
+    const int c0 = sl.c0[r];
+    if (D.concat) {
+#pragma unroll
+      for (int h = 0; h < HM; ++h) {
+        if (h >= H) continue;
+        const float t4[4] = {tot[r][h].x, tot[r][h].y, tot[r][h].z, tot[r][h].w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int c = c0 + i;
+          if (c < D.C) orow[h * D.C + c] = finish(t4[i], h * D.C + c);
+        }
+      }
+    } else {
+      float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int h = 0; h < HM; ++h)
+        if (h < H) { sum.x += tot[r][h].x; sum.y += tot[r][h].y; sum.z += tot[r][h].z; sum.w += tot[r][h].w; }
+      const float inv = 1.f / (float)H;
+      const float t4[4] = {sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int c = c0 + i;
-        if (c < D.C) orow[h * D.C + c] = finish(t4[i], h * D.C + c);
+        if (c < D.C) orow[c] = finish(t4[i], c);
       }
-    }
-  } else {
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int h = 0; h < HM; ++h)
-      if (h < H) { sum.x += tot[h].x; sum.y += tot[h].y; sum.z += tot[h].z; sum.w += tot[h].w; }
-    const float inv = 1.f / (float)H;
-    const float t4[4] = {sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = c0 + i;
-      if (c < D.C) orow[c] = finish(t4[i], c);
     }
   }
 }
@@ -338,7 +379,7 @@ __device__ __forceinline__ void load_g(const GatDstS& D, const GatDyn& dyn, int 
   }
 }
 
-template <int HM, int GS>
+template <int HM, int GS, int R = 1>
 __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restrict__ tab, const GatDyn dyn) {
   constexpr int CAP = 32;  // edges per row whose sweep-0 scalars are parked in LDS (multiple of the batch size; 16 KB at 8 rows x 4 heads: rooms with 17..32 objects no longer take the recompute path)
   __shared__ float cache[256 / GS][CAP][HM][4];
@@ -348,12 +389,13 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
   const int rpb = 256 / GS;
   const int row = ((int)blockIdx.x - dyn.block_start[di]) * rpb + (int)threadIdx.x / GS;
   if (row >= dyn.n_nodes[D.t]) return;  // whole groups leave together: shuffles below stay inside a group
-  const int gl = threadIdx.x % GS, c0 = gl * 4;
-  const bool cact = c0 < D.Cp;
+  const int gl = threadIdx.x % GS;
+  const Slices<R> sl(gl, D.Cp);
   const int H = D.H;
-  float4 g[HM];
+  float4 g[R][HM];
   KT(0);
-  load_g<HM>(D, dyn, row, c0, cact, g);
+#pragma unroll
+  for (int r = 0; r < R; ++r) load_g<HM>(D, dyn, row, sl.c0[r], sl.act[r], g[r]);
 
   for (int ii = 0; ii < D.n_in; ++ii) {
     KT(1 + 4 * ii);
@@ -378,8 +420,7 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
 #pragma unroll
     for (int h = 0; h < HM; ++h) { tsum[h] = 0.f; dsum[h] = 0.f; }
 
-    constexpr int UB = (HM <= 4) ? 4 : 2;
-    const int cc = cact ? c0 : 0;
+    constexpr int UB = batch_depth<HM, R>();
     // Sweep 0 needs every neighbour row (d alpha' = <g, h_s[j]>) to form sum_k alpha_k d alpha_k; sweep 1 needs only the
     // per-(edge, head) scalars again.  The first CAP edges of a row park them in LDS {alpha, d alpha, leaky slope, dropout
     // scale} (alpha < 0 marks a removed self loop), so sweep 1 re-reads NO neighbour rows for them: one lane per edge
@@ -389,8 +430,8 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
     const int n_cached = n_all < CAP ? n_all : CAP;
     KT(2 + 4 * ii);
     for (int k0 = b; k0 < kend; k0 += UB) {  // ---- sweep 0
-      EdgeBatch<HM, UB> B;
-      fetch_batch<HM, UB>(I, D.Cp, ea, H, row, b, e, kend, k0, cc, ad, ve, B);
+      EdgeBatch<HM, UB, R> B;
+      fetch_batch<HM, UB, R>(I, D.Cp, ea, H, row, b, e, kend, k0, sl.cc, ad, ve, B);
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int k = k0 + u;
@@ -412,7 +453,10 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
         for (int h = 0; h < HM; ++h) {
           if (h >= H) continue;
           float part = 0.f;
-          if (cact) part = dot4(g[h], B.v[u][h]);
+          if (sl.act[0]) part = dot4(g[0][h], B.v[u][0][h]);
+#pragma unroll
+          for (int r = 1; r < R; ++r)
+            if (sl.act[r]) part += dot4(g[r][h], B.v[u][r][h]);
           const float dap = group_sum<GS>(part);  // d alpha'_k,h (identical in every lane of the group)
           const float rw = B.raw[u][h];
           const float ev = rw > 0.f ? rw : NEG_SLOPE * rw;
@@ -459,8 +503,8 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
       for (int h = 0; h < HM; ++h) dsum[h] = group_sum<GS>(dpart[h]);
     }
     for (int k0 = b + CAP; k0 < kend; k0 += UB) {  // ---- sweep 1, edges past the cache: recompute
-      EdgeBatch<HM, UB> B;
-      fetch_batch<HM, UB>(I, D.Cp, ea, H, row, b, e, kend, k0, cc, ad, ve, B);
+      EdgeBatch<HM, UB, R> B;
+      fetch_batch<HM, UB, R>(I, D.Cp, ea, H, row, b, e, kend, k0, sl.cc, ad, ve, B);
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int k = k0 + u;
@@ -488,7 +532,10 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
         for (int h = 0; h < HM; ++h) {
           if (h >= H) continue;
           float part = 0.f;
-          if (cact) part = dot4(g[h], B.v[u][h]);
+          if (sl.act[0]) part = dot4(g[0][h], B.v[u][0][h]);
+#pragma unroll
+          for (int r = 1; r < R; ++r)
+            if (sl.act[r]) part += dot4(g[r][h], B.v[u][r][h]);
           const float dap = group_sum<GS>(part);
           const float rw = B.raw[u][h];
           const float ev = rw > 0.f ? rw : NEG_SLOPE * rw;
@@ -519,7 +566,7 @@ __global__ __launch_bounds__(256) void gat_bwd1_kernel(const GatLayerS* __restri
 // backward pass 2: source major over the CSC lists.
 //   d h_s[j,h,:] = sum_{k in out(j)} alpha'_k,h * g[i_k,h,:],   d a_src[j,h] = sum_k d raw_k,h
 // =================================================================================================
-template <int HM, int GS>
+template <int HM, int GS, int R = 1>
 __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restrict__ tab, const GatDyn dyn) {
   int si = 0;
   while (si + 1 < tab->n_src && (int)blockIdx.x >= dyn.block_start[si + 1]) ++si;
@@ -527,29 +574,32 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
   const int rpb = 256 / GS;
   const int row = ((int)blockIdx.x - dyn.block_start[si]) * rpb + (int)threadIdx.x / GS;
   if (row >= dyn.n_nodes[S.t]) return;
-  const int gl = threadIdx.x % GS, c0 = gl * 4;
+  const int gl = threadIdx.x % GS;
 
   for (int oi = 0; oi < S.n_out; ++oi) {
     const GatDstS& D = tab->d[S.out[oi].d];
     const GatInS& I = D.in[S.out[oi].i];
-    const bool cact = c0 < D.Cp;
+    const Slices<R> sl(gl, D.Cp);
     const int H = D.H;
     const int64_t E = dyn.n_edges[I.et];
     const int n_loop = I.self_loops ? min(dyn.n_nodes[I.src_t], dyn.n_nodes[D.t]) : 0;
     const float* gp = D.g ? D.g : dyn.g_top;
     const int ldg = D.g ? D.ldg : dyn.ld_gtop;
-    float4 acc[HM];
+    float4 acc[R][HM];
     float das[HM];
 #pragma unroll
-    for (int h = 0; h < HM; ++h) { acc[h] = make_float4(0.f, 0.f, 0.f, 0.f); das[h] = 0.f; }
+    for (int h = 0; h < HM; ++h) {
+      das[h] = 0.f;
+#pragma unroll
+      for (int r = 0; r < R; ++r) acc[r][h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     const int b = glob(I.t_rowptr)[row], e = glob(I.t_rowptr)[row + 1];
     const int kend = e + ((row < n_loop) ? 1 : 0);
     // vector path for the gradient rows (C % 4 == 0, 16-byte aligned rows: the executor's buffers); uniform
     const bool vec = (D.C & 3) == 0 && (ldg & 3) == 0 && (reinterpret_cast<uintptr_t>(gp) & 15) == 0;
-    const int cc = cact ? c0 : 0;
-    // out-edges in batches of 4: destination ids + CSR positions first, then the per-edge scalars and gradient rows of the
+    // out-edges in batches of UB: destination ids + CSR positions first, then the per-edge scalars and gradient rows of the
     // whole batch in flight together (all loads unconditional: head index clamped, see edge_logits); the adds keep the edge order
-    constexpr int UB = (HM <= 4) ? 4 : 2;
+    constexpr int UB = batch_depth<HM, R>();
     for (int k0 = b; k0 < kend; k0 += UB) {
       int ii[UB];
       int64_t pp[UB];
@@ -567,7 +617,7 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
         pp[u] = lp ? (E + row) : (real ? (int64_t)tp : 0);
       }
       float ap[UB][HM], dl[UB][HM];
-      float4 gv[UB][HM];
+      float4 gv[UB][R][HM];
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const float* gr = gp + (int64_t)ii[u] * ldg;
@@ -579,20 +629,24 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
         }
         if (vec) {
 #pragma unroll
-          for (int h = 0; h < HM; ++h) gv[u][h] = ld4(gr + (D.concat ? min(h, H - 1) * D.C : 0) + cc);
+          for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int h = 0; h < HM; ++h) gv[u][r][h] = ld4(gr + (D.concat ? min(h, H - 1) * D.C : 0) + sl.cc[r]);
         } else {
 #pragma unroll
-          for (int h = 0; h < HM; ++h) {
-            float t4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (cact && h < H && (D.concat || h == 0)) {
+          for (int r = 0; r < R; ++r)
 #pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int c = c0 + q;
-                if (c < D.C) t4[q] = D.concat ? glob(gr)[h * D.C + c] : glob(gr)[c];
+            for (int h = 0; h < HM; ++h) {
+              float t4[4] = {0.f, 0.f, 0.f, 0.f};
+              if (sl.act[r] && h < H && (D.concat || h == 0)) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                  const int c = sl.c0[r] + q;
+                  if (c < D.C) t4[q] = D.concat ? glob(gr)[h * D.C + c] : glob(gr)[c];
+                }
               }
+              gv[u][r][h] = make_float4(t4[0], t4[1], t4[2], t4[3]);
             }
-            gv[u][h] = make_float4(t4[0], t4[1], t4[2], t4[3]);
-          }
         }
       }
 #pragma unroll
@@ -602,14 +656,17 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
         for (int h = 0; h < HM; ++h) {
           if (h >= H) continue;
           das[h] += dl[u][h];
-          if (cact) {
-            const float4 gq = D.concat ? gv[u][h] : gv[u][0];
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            if (!sl.act[r]) continue;
+            const float4 gq = D.concat ? gv[u][r][h] : gv[u][r][0];
             const float w = ap[u][h] * D.group_scale;
+            float4& a = acc[r][h];
             if (D.concat) {
-              acc[h].x += w * gq.x; acc[h].y += w * gq.y; acc[h].z += w * gq.z; acc[h].w += w * gq.w;
+              a.x += w * gq.x; a.y += w * gq.y; a.z += w * gq.z; a.w += w * gq.w;
             } else {
               const float fh = (float)H;
-              acc[h].x += w * (gq.x / fh); acc[h].y += w * (gq.y / fh); acc[h].z += w * (gq.z / fh); acc[h].w += w * (gq.w / fh);
+              a.x += w * (gq.x / fh); a.y += w * (gq.y / fh); a.z += w * (gq.z / fh); a.w += w * (gq.w / fh);
             }
           }
         }
@@ -619,7 +676,9 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
 #pragma unroll
     for (int h = 0; h < HM; ++h) {
       if (h >= H) continue;
-      if (cact) st4(dzr + I.hoff + h * D.Cp + c0, acc[h]);
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if (sl.act[r]) st4(dzr + I.hoff + h * D.Cp + sl.c0[r], acc[r][h]);
       if (gl == 0) globw(I.dza_src)[(int64_t)row * I.lddza_src + I.asoff + h] = das[h];
     }
   }
@@ -630,15 +689,17 @@ int dispatch(int H, int Cp, F&& f) {
   const int lanes = Cp / 4;
   int gs = 8;
   while (gs < 64 && gs < lanes) gs <<= 1;
-  HMP_CHECK_ARG(lanes <= 64, "gat: channels per head %d > 256 not supported", Cp);
   HMP_CHECK_ARG(H >= 1 && H <= GAT_HMAX, "gat: heads %d not in [1, %d]", H, GAT_HMAX);
+  HMP_CHECK_ARG(lanes <= 64 || (lanes <= 128 && H <= GAT_WIDE_HMAX),
+                "gat: %d heads of %d channels not supported (at most %d channels per head, at most %d heads above 256 channels)", H, Cp,
+                GAT_CMAX, GAT_WIDE_HMAX);
   const int hm = H <= 1 ? 1 : (H <= 2 ? 2 : (H <= 4 ? 4 : 8));
-  return f(hm, gs);
+  return f(hm, gs, lanes <= 64 ? 1 : 2);  // slices per lane
 }
 
-#define GAT_LAUNCH(KERNEL, hm, gs, blocks, st, d_tab, dyn)                                                   \
+#define GAT_LAUNCH(KERNEL, hm, gs, r, blocks, st, d_tab, dyn)                                                \
   do {                                                                                                       \
-    switch ((hm)*100 + (gs)) {                                                                               \
+    switch (((r)-1) * 1000 + (hm)*100 + (gs)) {                                                              \
       case 108: hipLaunchKernelGGL((KERNEL<1, 8>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;       \
       case 116: hipLaunchKernelGGL((KERNEL<1, 16>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;      \
       case 132: hipLaunchKernelGGL((KERNEL<1, 32>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;      \
@@ -655,13 +716,16 @@ int dispatch(int H, int Cp, F&& f) {
       case 816: hipLaunchKernelGGL((KERNEL<8, 16>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;      \
       case 832: hipLaunchKernelGGL((KERNEL<8, 32>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;      \
       case 864: hipLaunchKernelGGL((KERNEL<8, 64>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;      \
-      default: HMP_FAIL(HMP_E_ARG, "gat: no kernel for heads-class %d, group %d", hm, gs);                   \
+      case 1164: hipLaunchKernelGGL((KERNEL<1, 64, 2>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;  \
+      case 1264: hipLaunchKernelGGL((KERNEL<2, 64, 2>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;  \
+      case 1464: hipLaunchKernelGGL((KERNEL<4, 64, 2>), dim3(blocks), dim3(256), 0, st, d_tab, dyn); break;  \
+      default: HMP_FAIL(HMP_E_ARG, "gat: no kernel for heads-class %d, group %d, %d slices", hm, gs, r);     \
     }                                                                                                        \
   } while (0)
 
 // all destination entries of a layer share H (the reference builds every edge type of a layer alike); the channel count may
 // differ between destination types (last layer of the two-headed task: output_dim_dict): the kernels read Cp per destination
-// and mask their lanes with it, so the launch takes the row-group width of the widest one
+// and mask their lanes (and the second slice of a wide class) with it, so the launch takes the class of the widest one
 int layer_shape(const GatLayerS& h_tab, int& H, int& Cp) {
   HMP_CHECK_ARG(h_tab.n_dst > 0, "gat: empty layer table");
   H = h_tab.d[0].H; Cp = h_tab.d[0].Cp;
@@ -677,7 +741,7 @@ int layer_shape(const GatLayerS& h_tab, int& H, int& Cp) {
 int gat_fwd_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st) {
   int H, Cp;
   HMP_TRY(layer_shape(h_tab, H, Cp));
-  return dispatch(H, Cp, [&](int hm, int gs) -> int {
+  return dispatch(H, Cp, [&](int hm, int gs, int r) -> int {
     int blocks = 0;
     for (int i = 0; i < h_tab.n_dst; ++i) {
       dyn.block_start[i] = blocks;
@@ -685,7 +749,7 @@ int gat_fwd_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, 
     }
     dyn.block_start[h_tab.n_dst] = blocks;
     if (blocks == 0) return HMP_OK;
-    GAT_LAUNCH(gat_fwd_kernel, hm, gs, blocks, st, d_tab, dyn);
+    GAT_LAUNCH(gat_fwd_kernel, hm, gs, r, blocks, st, d_tab, dyn);
     HMP_LAUNCH_CHECK();
     return HMP_OK;
   });
@@ -694,7 +758,7 @@ int gat_fwd_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, 
 int gat_bwd1_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st) {
   int H, Cp;
   HMP_TRY(layer_shape(h_tab, H, Cp));
-  return dispatch(H, Cp, [&](int hm, int gs) -> int {
+  return dispatch(H, Cp, [&](int hm, int gs, int r) -> int {
     int blocks = 0;
     for (int i = 0; i < h_tab.n_dst; ++i) {
       dyn.block_start[i] = blocks;
@@ -702,7 +766,7 @@ int gat_bwd1_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn,
     }
     dyn.block_start[h_tab.n_dst] = blocks;
     if (blocks == 0) return HMP_OK;
-    GAT_LAUNCH(gat_bwd1_kernel, hm, gs, blocks, st, d_tab, dyn);
+    GAT_LAUNCH(gat_bwd1_kernel, hm, gs, r, blocks, st, d_tab, dyn);
     HMP_LAUNCH_CHECK();
     return HMP_OK;
   });
@@ -711,7 +775,7 @@ int gat_bwd1_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn,
 int gat_bwd2_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st) {
   int H, Cp;
   HMP_TRY(layer_shape(h_tab, H, Cp));
-  return dispatch(H, Cp, [&](int hm, int gs) -> int {
+  return dispatch(H, Cp, [&](int hm, int gs, int r) -> int {
     int blocks = 0;
     for (int i = 0; i < h_tab.n_src; ++i) {
       dyn.block_start[i] = blocks;
@@ -719,7 +783,7 @@ int gat_bwd2_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn,
     }
     dyn.block_start[h_tab.n_src] = blocks;
     if (blocks == 0) return HMP_OK;
-    GAT_LAUNCH(gat_bwd2_kernel, hm, gs, blocks, st, d_tab, dyn);
+    GAT_LAUNCH(gat_bwd2_kernel, hm, gs, r, blocks, st, d_tab, dyn);
     HMP_LAUNCH_CHECK();
     return HMP_OK;
   });
@@ -744,7 +808,8 @@ struct UnitTab {
 
 int unit_setup(UnitTab& u, GatDyn& dyn, const hmp_plan& plan, const hmp_gat_args& a, const float* h_src, int ldh, const float* a_src,
                int lda_s, const float* a_dst, int lda_d, const float* edge_attr, const float* v_edge) {
-  HMP_CHECK_ARG(a.heads >= 1 && a.heads <= GAT_HMAX && a.channels >= 1 && a.channels <= 256, "hmp_gat: heads/channels out of range");
+  HMP_CHECK_ARG(gat_shape_ok(a.heads, a.channels), "hmp_gat: %d heads of %d channels out of range (at most %d channels per head, at most %d heads above 256 channels)",
+                a.heads, a.channels, GAT_CMAX, GAT_WIDE_HMAX);
   HMP_CHECK_ARG(a.edge_dim >= 0 && a.edge_dim <= GAT_MAX_EDIM, "hmp_gat: edge_dim out of range");
   HMP_CHECK_ARG(a.edge_dim == 0 || (edge_attr && v_edge) || plan.n_edges == 0, "hmp_gat: edge_attr / v_edge missing");
   HMP_CHECK_ARG((ldh & 3) == 0 && ldh >= a.heads * align4(a.channels), "hmp_gat: ldh must be a multiple of 4 and >= H*Cp");

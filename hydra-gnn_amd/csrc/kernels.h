@@ -449,6 +449,13 @@ struct GradReduceDyn {  // passed by value: keep it small
 // ---------------------------------------------------------------------------------------------
 constexpr int GAT_HMAX = 8;
 constexpr int GAT_MAX_EDIM = 4;
+// channels per head: up to 256 a lane of the row group owns one 4-channel slice per head, up to GAT_CMAX two -- with at most
+// GAT_WIDE_HMAX heads, so that heads x slices stays within the register footprint of the 8-head class
+constexpr int GAT_CMAX = 512;
+constexpr int GAT_WIDE_HMAX = 4;
+inline bool gat_shape_ok(int heads, int channels) {
+  return heads >= 1 && heads <= GAT_HMAX && channels >= 1 && channels <= GAT_CMAX && (channels <= 256 || heads <= GAT_WIDE_HMAX);
+}
 
 // Static (per bound network) description of one GAT layer, resident in device memory: the by-value kernel
 // argument budget (4 KB) cannot hold it.  Everything that changes with the batch travels in GatDyn.

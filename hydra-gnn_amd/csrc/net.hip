@@ -272,7 +272,8 @@ int build_layout(hmp_net* n) {
       if (Y.kind == HMP_CONV_SAGE) {
         HMP_CHECK_ARG(C.f_out == Ls.out_dim[C.dst], "net: SAGE f_out must equal the layer's out_dim of the destination type");
       } else {
-        HMP_CHECK_ARG(C.heads >= 1 && C.heads <= GAT_HMAX && C.f_out >= 1 && C.f_out <= 256, "net: GAT heads %d / channels %d unsupported", C.heads, C.f_out);
+        HMP_CHECK_ARG(gat_shape_ok(C.heads, C.f_out), "net: GAT heads %d / channels %d unsupported (at most %d channels per head, at most %d heads above 256 channels)",
+                      C.heads, C.f_out, GAT_CMAX, GAT_WIDE_HMAX);
         HMP_CHECK_ARG(Ls.out_dim[C.dst] == (C.concat ? C.heads * C.f_out : C.f_out), "net: GAT out_dim mismatch on layer %d conv %d", l, c);
         HMP_CHECK_ARG(C.edge_dim >= 0 && C.edge_dim <= GAT_MAX_EDIM, "net: GAT edge_dim %d > %d", C.edge_dim, GAT_MAX_EDIM);
         HMP_CHECK_ARG(!(C.edge_dim > 0 && C.fill_mean && C.self_loops), "net: fill_value='mean' with edge attributes is not supported (the reference passes zeros)");

@@ -94,11 +94,10 @@ class HomogeneousNeuralTreeNetwork(HomogeneousNetwork):
             self.pre_mp = None
             print("diable initialization")
         else:
-            if input_dim > 256:
+            if input_dim > 512:
                 raise NotImplementedError(
-                    f"pre_mp over {input_dim}-wide features: the GAT kernels hold one 4-channel slice per lane (<= 256 channels per "
-                    "head).  Every shipped H-tree config sets disable_initialization: True; the 6-d Stanford / --remove_word2vec "
-                    "features are supported.")
+                    f"pre_mp over {input_dim}-wide features: the GAT kernels hold at most two 4-channel slices per lane "
+                    "(<= 512 channels per head).  Set disable_initialization=True or reduce the features.")
             self.pre_mp = GATConv(input_dim, input_dim, heads=1, concat=False, dropout=0.0, add_self_loops=False)
         self.post_mp_pool = LeafPool(aggr="mean")
         self._native = None  # the parent built no program yet (lazy), but make the rebuild explicit

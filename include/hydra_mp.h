@@ -180,7 +180,7 @@ int hmp_gemm_grouped(const hmp_gemm_desc* d, int32_t n, int32_t route, int32_t w
  *    the network executor below drives the same kernels without synchronising).
  * ------------------------------------------------------------------------------------------- */
 typedef struct hmp_gat_args {
-  int32_t heads, channels;   /* H <= 8, C <= 256 */
+  int32_t heads, channels;   /* H <= 8, C <= 256; or H <= 4, C <= 512 */
   int32_t self_loops;
   int32_t edge_dim;          /* 0..4 */
   float dropout_p;           /* attention dropout; 0 = off */
