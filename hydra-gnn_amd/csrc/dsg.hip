@@ -13,44 +13,9 @@
 // objects: both passes are launch-latency bound, which is the point (the host loop takes milliseconds).
 #include "common.h"
 
+#include "obj_edge.h"  // ObjGeom, obj_edge: shared with the host stage of frame.cpp; float64, no contraction from here on
+
 namespace hmp {
-
-struct ObjGeom {
-  const double* pos;   // [n][3]
-  const double* size;  // [n][3]  bounding_box.max - bounding_box.min
-  const int* room;     // [n]     room index, < 0: no room
-  int n;
-  double threshold_near, max_near, max_on;
-};
-
-#pragma clang fp contract(off)
-__device__ __forceinline__ bool obj_edge(const ObjGeom& g, int i, int j) {
-  if (g.room[i] < 0 || g.room[i] != g.room[j]) return false;
-  double p1[3], p2[3], s1[3], s2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    p1[k] = g.pos[3 * i + k]; p2[k] = g.pos[3 * j + k];
-    s1[k] = g.size[3 * i + k]; s2[k] = g.size[3 * j + k];
-  }
-  const double dx = fabs(p1[0] - p2[0]), dy = fabs(p1[1] - p2[1]), dz = fabs(p1[2] - p2[2]);
-  const bool in2 = dx <= s2[0] / 2 && dy <= s2[1] / 2;  // centre of 1 inside 2 on the xy plane
-  const bool in1 = dx <= s1[0] / 2 && dy <= s1[1] / 2;
-  // _is_on (:89-110)
-  const bool above = p1[2] > p2[2];
-  const double on_thresh = g.max_on + (s1[2] + s2[2]) / 2;
-  const bool is_on = (in2 && above && dz <= on_thresh) || (in1 && !above && dz <= on_thresh);
-  // _is_under (:139-158)
-  const bool is_under = (in1 || in2) && (p1[2] < p2[2] || p2[2] < p1[2]);
-  // _is_near (:161-180)
-  bool is_near = true;
-  const double d[3] = {dx, dy, dz};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double avg = (s1[k] + s2[k]) / 2.0;
-    is_near = is_near && d[k] <= avg * g.threshold_near && d[k] - avg <= g.max_near;
-  }
-  return is_on || is_under || is_near;
-}
 
 __global__ __launch_bounds__(256) void object_edge_count_kernel(const ObjGeom g, int* __restrict__ count) {
   __shared__ int ws[4];

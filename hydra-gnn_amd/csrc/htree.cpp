@@ -23,7 +23,7 @@
 #include <set>
 #include <vector>
 
-#include "../../include/hydra_mp.h"
+#include "htree_build.h"  // struct hmp_htree, hmp::htree_build_i32 (the frame pipeline calls the builder directly)
 
 namespace hmp {
 char* err_buf();
@@ -253,13 +253,6 @@ JthResult generate_jth(const std::vector<int>& verts, const Adj& G, bool origina
 
 }  // namespace
 
-struct hmp_htree {
-  int32_t counts[4] = {0, 0, 0, 0};
-  std::vector<int32_t> object_orig, room_orig;
-  std::vector<int32_t> edges[10];  // [2][n] each: row 0 sources, row 1 destinations (local indices inside the node types)
-  std::vector<int32_t> init[3];    // ov_to_or, rv_to_or, rv_to_rr: row 0 = virtual (original index inside its type), row 1 = clique
-};
-
 namespace {
 
 const int ET_SRC[10] = {NT_OBJECT, NT_OBJECT_ROOM, NT_ROOM, NT_OBJECT_ROOM, NT_ROOM, NT_ROOM_ROOM, NT_OBJECT_ROOM, NT_ROOM_ROOM, NT_OBJECT_ROOM, NT_ROOM_ROOM};
@@ -267,10 +260,10 @@ const int ET_DST[10] = {NT_OBJECT_ROOM, NT_OBJECT, NT_OBJECT_ROOM, NT_ROOM, NT_R
 
 void push2(std::vector<int32_t>& rows, std::vector<int32_t>& tmp_dst, int32_t s, int32_t d) { rows.push_back(s); tmp_dst.push_back(d); }
 
-}  // namespace
-
-extern "C" int hmp_htree_build(int32_t n_objects, int32_t n_rooms, const int64_t* oo, int64_t e_oo, const int64_t* rr, int64_t e_rr,
-                               const int64_t* ro, int64_t e_ro, hmp_htree** out) {
+// Index = int64_t: the C entry (edge_index tensors); int32_t: the lists the frame pipeline has just made (csrc/frame.cpp)
+template <class Index>
+int htree_build_impl(int32_t n_objects, int32_t n_rooms, const Index* oo, int64_t e_oo, const Index* rr, int64_t e_rr, const Index* ro,
+                     int64_t e_ro, hmp_htree** out) {
   auto fail = [](const char* m) { snprintf(hmp::err_buf(), 512, "hmp_htree_build: %s", m); return HMP_E_ARG; };
   if (!out || n_objects < 0 || n_rooms < 0 || e_oo < 0 || e_rr < 0 || e_ro < 0) return fail("bad argument");
   if ((e_oo && !oo) || (e_rr && !rr) || (e_ro && !ro)) return fail("null edge list");
@@ -416,6 +409,18 @@ extern "C" int hmp_htree_build(int32_t n_objects, int32_t n_rooms, const int64_t
   for (int k = 0; k < 3; ++k) T->init[k].insert(T->init[k].end(), idst[k].begin(), idst[k].end());
   *out = T;
   return HMP_OK;
+}
+
+}  // namespace
+
+extern "C" int hmp_htree_build(int32_t n_objects, int32_t n_rooms, const int64_t* oo, int64_t e_oo, const int64_t* rr, int64_t e_rr,
+                               const int64_t* ro, int64_t e_ro, hmp_htree** out) {
+  return htree_build_impl<int64_t>(n_objects, n_rooms, oo, e_oo, rr, e_rr, ro, e_ro, out);
+}
+
+int hmp::htree_build_i32(int32_t n_objects, int32_t n_rooms, const int32_t* oo, int64_t e_oo, const int32_t* rr, int64_t e_rr,
+                         const int32_t* ro, int64_t e_ro, hmp_htree** out) {
+  return htree_build_impl<int32_t>(n_objects, n_rooms, oo, e_oo, rr, e_rr, ro, e_ro, out);
 }
 
 extern "C" int hmp_htree_sizes(const hmp_htree* t, int32_t* counts4, int64_t* n_edges10, int64_t* n_init3) {

@@ -18,17 +18,22 @@ Pinned by ``tests/golden/dsg_x8F5xyUWy9e_expected.npz`` -- the reference's own f
 features (the reference downloads GoogleNews vectors; pass ``semantic`` rows yourself or use the 6-d ``--remove_word2vec``
 contract) and ``spark_dsg.add_bounding_boxes_to_layer`` (C++, absent): room boxes are taken as the AABB of the positions of
 the room's places, stated here as an assumption.
+
+``FramePipeline`` (below) is the same conversion as one native host stage, one upload and one launch (``csrc/frame.cpp``,
+``csrc/frame.hip``), for the baseline graph and for its H-tree; the functions above it stay as they are and are its parity oracle.
 """
 from __future__ import annotations
 
+import ctypes as C
 import json
+import struct
 from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import _lib
-from .data import HeteroData
+from .data import HTREE_EDGE_TYPES, HTREE_INIT_EDGE_TYPES, HTREE_POOL_EDGE_TYPES, HeteroData
 
 OBJECTS, PLACES, ROOMS, BUILDINGS = 2, 3, 4, 5
 _STATIC = ("ObjectNodeAttributes", "PlaceNodeAttributes", "RoomNodeAttributes", "SemanticNodeAttributes")
@@ -187,3 +192,216 @@ def frame_to_data(src: Union[str, dict], threshold_near: float = 1.5, max_near: 
     rog = RoomObjectGraph(load_dsg_json(src))
     oo = object_connectivity(rog, threshold_near, max_near, max_on, device)
     return to_hetero_data(rog, oo, semantic, device), rog
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Frame pipeline (include/hydra_mp.h section 14): flat arrays -> HeteroData, host stage + one copy + one launch
+# ---------------------------------------------------------------------------------------------------------------------------------
+_OO, _RR = ("objects", "objects_to_objects", "objects"), ("rooms", "rooms_to_rooms", "rooms")
+_RO, _OR = ("rooms", "rooms_to_objects", "objects"), ("objects", "objects_to_rooms", "rooms")
+# output tensor number (HMP_FI_TENSOR) -> (store key, attribute); store creation follows to_hetero_data / generate_htree
+_FRAME_TENSORS = (
+    [(t, a) for t in ("objects", "rooms") for a in ("x", "pos", "label", "node_ids")]
+    + [(e, "edge_index") for e in (_OO, _RR, _RO, _OR)] + [(e, "edge_attr") for e in (_OO, _RR, _RO, _OR)]
+    + [(t, a) for t in ("object", "room") for a in ("x", "pos", "label")] + [("object-room", "x"), ("room-room", "x")]
+    + [(t, a) for t in ("object_virtual", "room_virtual") for a in ("x", "pos", "label")]
+    + [(tuple(e), "edge_index") for e in list(HTREE_EDGE_TYPES) + list(HTREE_INIT_EDGE_TYPES) + list(HTREE_POOL_EDGE_TYPES)]
+)
+assert len(_FRAME_TENSORS) == _lib.FT_COUNT
+_HTREE_STORES = ["object", "room", "object-room", "room-room", "object_virtual", "room_virtual"]
+
+
+def scene_arrays(sg: SceneGraph):
+    """A ``SceneGraph`` as the flat arrays the frame pipeline reads: ``(ids, layer, pos, bb_min, bb_max, label, edges)`` with
+    ``edges`` uint64 ``[2, m]`` of node ids, every undirected edge of ``sg.adj`` once."""
+    pairs = [(i, j) for i, nb in enumerate(sg.adj) for j in nb if i < j]
+    idx = np.array(pairs, dtype=np.int64).reshape(-1, 2).T
+    return sg.ids, sg.layer, sg.pos, sg.bb_min, sg.bb_max, sg.label, np.asarray(sg.ids, dtype=np.uint64)[idx]
+
+
+def _frame_args(ids, layer, pos, bb_min, bb_max, label, edges):
+    """contiguous arrays of the C entry's types (kept alive by the caller for the duration of the call) and (n, m)"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    n = int(ids.size)
+    f3 = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(n, 3)
+    edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(2, -1)
+    arrays = (ids, np.ascontiguousarray(layer, dtype=np.int32).reshape(n), f3(pos), f3(bb_min), f3(bb_max),
+              np.ascontiguousarray(label, dtype=np.int64).reshape(n), edges)
+    return arrays, n, int(edges.shape[1])
+
+
+def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_labels, clique_dim) -> C.c_void_p:
+    ids, layer, pos, bb_min, bb_max, label, edges = arrays
+    h = C.c_void_p()
+    _lib.check(lib.hmp_frame_build(n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data,
+                                   label.ctypes.data, m, edges.ctypes.data, float(thresholds[0]), float(thresholds[1]),
+                                   float(thresholds[2]), int(bool(htree)), int(bool(relative_pos)), int(sem_dim), int(n_labels),
+                                   int(clique_dim or 0), C.byref(h)))
+    return h
+
+
+def frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
+                     max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
+                     clique_dim: Optional[int] = None) -> Dict[str, object]:
+    """The host stage of the frame pipeline on its own (no GPU involved; tests and diagnostics): ``hmp_frame_build`` and every
+    accessor.  ``kept`` / ``dropped`` / ``rooms`` index the input arrays; ``items`` is the staging block's table (int32
+    ``[n_items, 12]``), ``block`` the packed block (uint8); ``empty``: no room or no kept object, nothing was laid out."""
+    lib = _lib.load()
+    arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
+    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels, clique_dim)
+    try:
+        sz = np.zeros(_lib.FS_COUNT, dtype=np.int64)
+        _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
+        n_o, n_r = int(sz[_lib.FS_KEPT]), int(sz[_lib.FS_ROOMS])
+        out = {"sizes": sz, "kept": np.zeros(n_o, np.int32), "obj_room": np.zeros(n_o, np.int32),
+               "dropped": np.zeros(int(sz[_lib.FS_DROPPED]), np.int32), "rooms": np.zeros(n_r, np.int32),
+               "rr_edges": np.zeros((2, int(sz[_lib.FS_E_RR])), np.int32), "room_bb": np.zeros((n_r, 2, 3)),
+               "oo_edges": np.zeros((2, int(sz[_lib.FS_E_OO])), np.int32)}
+        p = lambda k: out[k].ctypes.data if out[k].size else None
+        _lib.check(lib.hmp_frame_host_arrays(h, p("kept"), p("obj_room"), p("dropped"), p("rooms"), p("rr_edges"), p("room_bb"), p("oo_edges")))
+        n_items = int(sz[_lib.FS_ITEMS])
+        out["empty"] = n_items == 0
+        block = np.zeros(int(sz[_lib.FS_STAGING_BYTES]), dtype=np.uint8)
+        if n_items:
+            _lib.check(lib.hmp_frame_pack(h, block.ctypes.data, block.size))
+        out["block"] = block
+        out["items"] = block[: n_items * _lib.FRAME_ITEM_WORDS * 4].view(np.int32).reshape(n_items, _lib.FRAME_ITEM_WORDS).copy()
+    finally:
+        lib.hmp_frame_destroy(h)
+    return out
+
+
+def save_frame_file(path: str, ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
+                    max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
+                    clique_dim: int = 0) -> None:
+    """Flat binary frame file of the stand-alone host-stage driver (``make -C csrc frame_check``; layout in csrc/frame_check.cpp)."""
+    arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
+    with open(path, "wb") as f:
+        f.write(b"HMPF" + struct.pack("<7iq3d", 1, n, int(htree), int(relative_pos), sem_dim, n_labels, clique_dim, m,
+                                      threshold_near, max_near, max_on))
+        for a in arrays:
+            f.write(a.tobytes())
+
+
+class FramePipeline:
+    """``GnnModel.convert_graph`` after the JSON step as ONE native host stage, ONE host-to-device copy and ONE launch.
+
+    ``convert(ids, layer, pos, bb_min, bb_max, label, edges)`` takes the static layers of a scene graph as flat arrays (node ids
+    uint64 ``[n]``, layer ``[n]``, float64 ``[n, 3]`` position and box corners, semantic label ``[n]``, undirected edges as node
+    ids ``[2, m]``) and returns ``(HeteroData, info)``: what ``frame_to_data`` returns (``relative_pos=True``: after
+    ``data.compute_relative_pos``), or with ``htree=True`` what ``htree.generate_htree(frame, clique_dim)`` makes of it.
+    ``semantic_table`` (float32 ``[n_labels, sem_dim]``, resident on the device) appends ``table[label]`` to the objects' rows;
+    rooms take no semantic block.  ``info`` = ``{"object_ids", "dropped_ids", "room_ids"}`` (numpy, the node ids the server maps
+    labels back to).  Returns ``None`` for a frame without a room or without a kept object (the server's ``_check_graph`` refuses
+    those) without touching the device.
+
+    Every tensor of the result is a view of one device arena that ``hmp_frame_expand`` filled from one uploaded block; nothing
+    synchronises (a pinned staging buffer is waited for only if the device is two frames behind).  The tensors are FRESH objects
+    on every call -- ``predict`` re-uses a plan for the same edge tensor objects at the same ``_version``, and the kernel's writes
+    do not bump ``_version`` -- and, like ``predict``'s pinned label buffer, a result is valid until the next ``convert`` of the
+    same pipeline.  ``convert`` runs on torch's current stream and refuses a pipeline whose device is not the current one.  A
+    pipeline has ONE device staging buffer and ONE arena, ordered by the stream alone: the stream of the first ``convert`` that
+    enqueues anything is the pipeline's, and a ``convert`` under another current stream is refused (keep a pipeline per stream).
+    Relative positions on H-tree edges are not produced (``generate_htree`` has none): ``relative_pos`` with ``htree`` is refused.
+    """
+
+    def __init__(self, device="cuda:0", semantic_table=None, htree: bool = False, relative_pos: bool = False,
+                 clique_dim: Optional[int] = None, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.HydraMPError(f"FramePipeline needs a gfx950 device, not {self.device}: hydra_gnn_amd has no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", 0)
+        if htree and relative_pos:
+            raise _lib.HydraMPError("FramePipeline: relative positions on H-tree edges are not produced (generate_htree has none)")
+        self.htree, self.relative_pos, self.clique_dim = bool(htree), bool(relative_pos), int(clique_dim or 0)
+        self.thresholds = (float(threshold_near), float(max_near), float(max_on))
+        self._lib = _lib.load()
+        self._table_host, self._table = None, None
+        self.sem_dim, self.n_labels = 0, 0
+        if semantic_table is not None:
+            t = torch.as_tensor(semantic_table).detach().to(torch.float32).contiguous()
+            if t.dim() != 2 or t.size(0) < 1 or t.size(1) < 1:
+                raise _lib.HydraMPError("FramePipeline: semantic_table must be a float32 [n_labels, sem_dim] array")
+            self._table_host, self.n_labels, self.sem_dim = t, int(t.size(0)), int(t.size(1))
+        self._sizes = np.zeros(_lib.FS_COUNT, dtype=np.int64)
+        # device buffers appear with the first frame that has something to convert (an empty frame never touches the device)
+        self._pinned, self._pinned_np, self._events, self._slot = [None, None], [None, None], [None, None], 0
+        self._d_staging = self._arena = self._arena_f32 = self._arena_i64 = None
+        self._stream = None  # hipStream_t of the first convert that enqueued work
+
+    def _ensure(self, staging_bytes: int, arena_bytes: int) -> None:
+        if self._table is None and self._table_host is not None:
+            self._lib = _lib.require_device()
+            self._table = self._table_host.to(self.device)
+        if self._d_staging is None or self._d_staging.numel() < staging_bytes:
+            cap = max(1 << 16, 2 * staging_bytes)
+            self._lib = _lib.require_device()
+            self._d_staging = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            for k in range(2):
+                self._pinned[k] = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                self._pinned_np[k] = self._pinned[k].numpy().view(np.int32)
+                self._events[k] = torch.cuda.Event()
+        if self._arena is None or self._arena.numel() < arena_bytes:
+            self._arena = torch.empty(max(1 << 18, 2 * arena_bytes), dtype=torch.uint8, device=self.device)
+            self._arena_f32, self._arena_i64 = self._arena.view(torch.float32), self._arena.view(torch.int64)
+
+    def convert_scene(self, sg: SceneGraph):
+        """``convert`` on a ``SceneGraph`` (``load_dsg_json``): ``sg.adj`` is flattened to an edge array first."""
+        return self.convert(*scene_arrays(sg))
+
+    def convert(self, ids, layer, pos, bb_min, bb_max, label, edges):
+        lib = self._lib
+        arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
+        h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels, self.clique_dim)
+        try:
+            sz = self._sizes
+            _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
+            n_items = int(sz[_lib.FS_ITEMS])
+            if n_items == 0:
+                return None
+            if torch.cuda.current_device() != self.device.index:
+                raise _lib.HydraMPError(f"FramePipeline.convert: the pipeline lives on {self.device}, the current device is "
+                                        f"cuda:{torch.cuda.current_device()}")
+            stream = _lib.stream_ptr()
+            if self._stream is None:
+                self._stream = stream
+            elif stream != self._stream:
+                raise _lib.HydraMPError("FramePipeline.convert: the current stream is not the stream of this pipeline's earlier frames; "
+                                        "its staging buffer and arena are ordered by one stream (keep a pipeline per stream)")
+            n_o, n_r, n_d = int(sz[_lib.FS_KEPT]), int(sz[_lib.FS_ROOMS]), int(sz[_lib.FS_DROPPED])
+            staging_bytes, arena_bytes = int(sz[_lib.FS_STAGING_BYTES]), int(sz[_lib.FS_ARENA_BYTES])
+            self._ensure(staging_bytes, arena_bytes)
+            lib = self._lib
+            slot = self._slot = self._slot ^ 1
+            if not self._events[slot].query():  # the upload that last read this pinned buffer has not run yet
+                self._events[slot].synchronize()
+            pin = self._pinned[slot]
+            _lib.check(lib.hmp_frame_pack(h, pin.data_ptr(), staging_bytes))
+            self._d_staging[:staging_bytes].copy_(pin[:staging_bytes], non_blocking=True)
+            self._events[slot].record()
+            _lib.check(lib.hmp_frame_expand(self._d_staging.data_ptr(), self._arena.data_ptr(),
+                                            self._table.data_ptr() if self._table is not None else None, self.sem_dim, n_items,
+                                            int(sz[_lib.FS_BLOCKS]), stream))
+            kept, dropped, rooms = np.empty(n_o, np.int32), np.empty(n_d, np.int32), np.empty(n_r, np.int32)
+            _lib.check(lib.hmp_frame_host_arrays(h, kept.ctypes.data, None, dropped.ctypes.data if n_d else None, rooms.ctypes.data,
+                                                 None, None, None))
+            items = self._pinned_np[slot][: n_items * _lib.FRAME_ITEM_WORDS].reshape(n_items, _lib.FRAME_ITEM_WORDS).tolist()
+        finally:
+            lib.hmp_frame_destroy(h)
+        g = HeteroData()
+        if self.htree:
+            for t in _HTREE_STORES:
+                g[t]
+        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
+        for kind, tensor, n_rows, width, dst, *_ in items:
+            key, attr = _FRAME_TENSORS[tensor]
+            if kind == _lib.FK_I64:
+                t = strided(i64, (n_rows,), (1,), dst >> 3)
+            elif kind == _lib.FK_EDGE:
+                t = strided(i64, (2, width), (width, 1), dst >> 3)
+            else:
+                t = strided(f32, (n_rows, width), (width, 1), dst >> 2)
+            setattr(g[key], attr, t)
+        ids = arrays[0]
+        return g, {"object_ids": ids[kept], "dropped_ids": ids[dropped], "room_ids": ids[rooms]}

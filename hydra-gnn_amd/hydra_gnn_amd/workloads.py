@@ -387,3 +387,42 @@ def stanford_htree_semisupervised_graphs(n_graphs: int, seed: int, edge_attr: bo
             d.edge_attr = (d.x[d.edge_index[1], :3] - d.x[d.edge_index[0], :3]).contiguous()
         graphs.append(d)
     return graphs
+
+
+def synthetic_scene(n_objects: int, n_rooms: int, seed: int = 0, n_labels: int = 41, places_per_room: int = 4):
+    """Static layers of a synthetic scene graph as the flat arrays ``dsg.FramePipeline.convert`` reads:
+    ``(ids, layer, pos, bb_min, bb_max, label, edges)``.  One building, ``n_rooms`` rooms in a chain, ``places_per_room`` places
+    per room in a chain, ``n_objects`` objects spread over the places; node ids are spark_dsg NodeSymbols (category letter in the
+    top byte), the arrays are in shuffled order (layers are visited in ascending id, not in array order)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sym = lambda c, i: (ord(c) << 56) + i
+    ids, layer, pos, half, label, edges = [], [], [], [], [], []
+
+    def node(i, lay, p, h, lab):
+        ids.append(i), layer.append(lay), pos.append(p), half.append(h), label.append(lab)
+        return i
+
+    b = node(sym("B", 0), 5, np.zeros(3), np.ones(3), 0)
+    places = []
+    for r in range(n_rooms):
+        centre = np.array([8.0 * r, 0.0, 1.5])
+        room = node(sym("R", r), 4, centre, np.ones(3), int(rng.integers(0, 25)))
+        edges.append((b, room))
+        if r:
+            edges.append((sym("R", r - 1), room))
+        for k in range(places_per_room):
+            p = node(sym("p", r * places_per_room + k), 3, centre + rng.normal(0, 1.5, 3), 0.5 * np.ones(3), 0)
+            edges.append((room, p))
+            if k:
+                edges.append((sym("p", r * places_per_room + k - 1), p))
+            places.append(p)
+    index = {v: i for i, v in enumerate(ids)}
+    for o in range(n_objects):
+        p = places[int(rng.integers(0, len(places)))]
+        obj = node(sym("O", o), 2, pos[index[p]] + rng.normal(0, 1.2, 3), rng.uniform(0.1, 0.8, 3), int(rng.integers(0, n_labels)))
+        edges.append((obj, p))
+    perm = rng.permutation(len(ids))
+    ids = np.array(ids, dtype=np.uint64)[perm]
+    pos, half = np.array(pos, dtype=np.float64)[perm], np.array(half, dtype=np.float64)[perm]
+    return (ids, np.array(layer, dtype=np.int32)[perm], pos, pos - half, pos + half, np.array(label, dtype=np.int64)[perm],
+            np.array(edges, dtype=np.uint64).reshape(-1, 2).T.copy())

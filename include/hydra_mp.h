@@ -43,7 +43,9 @@ extern "C" {
  *    hmp_tail_desc (hmp_sizeof 14), hmp_linear_heads_desc (hmp_sizeof 15), hmp_head_tails / hmp_linear_heads_run: test and
  *    diagnostic entries of the readout tail and linear-head launchers: new entries, no struct changed layout;
  *    hmp_predict_rows, hmp_net_predict_rooms / hmp_net_predict2 / hmp_net_predict_heads (labels instead of counts, for every net
- *    kind), hmp_head_tails_predict / hmp_linear_heads_predict (their test entries): new entries, no struct changed layout */
+ *    kind), hmp_head_tails_predict / hmp_linear_heads_predict (their test entries): new entries, no struct changed layout;
+ *    section 14: hmp_frame_build / hmp_frame_sizes / hmp_frame_host_arrays / hmp_frame_pack / hmp_frame_destroy (host) and
+ *    hmp_frame_expand (one launch): scene-graph arrays to model input.  New entries, no struct was added or changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -778,6 +780,97 @@ int hmp_epoch_read(const hmp_epoch_ctl* d_ctl, const hmp_epoch_row* d_log, int32
                    hmp_epoch_row* h_rows, int32_t* n_rows, void* stream);
 /* the 4-byte status word alone (the per-epoch read of a job with early stopping).  Synchronises the stream. */
 int hmp_epoch_read_status(const hmp_epoch_ctl* d_ctl, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * 14. Frame pipeline: the static layers of a scene graph as flat arrays -> every tensor of the HeteroData the models read, for the
+ *     baseline room-object graph and for its H-tree (csrc/frame.cpp, csrc/frame.hip; hydra_gnn_amd/dsg.py FramePipeline).  Replaces
+ *     GnnModel.convert_graph (bin/room_classification_server:235-271) after the JSON / spark_dsg step: get_room_object_dsg,
+ *     add_object_connectivity, to_torch + fill_missing_edge_index, compute_relative_pos and, for H-tree models, generate_htree +
+ *     add_virtual_nodes_to_htree + nx_htree_to_torch.
+ *
+ *     Host stage (host memory only, no GPU needed): hmp_frame_build does all bookkeeping -- the room-object graph in the
+ *     reference's visiting order, the object-object predicates in float64 (the function body of section 10), the H-tree topology
+ *     (the builder of section 12) -- and lays out ONE staging block and ONE arena.  hmp_frame_pack writes the staging block:
+ *       [item table: n_items x HMP_FRAME_ITEM_WORDS int32][sections, each 16-byte aligned: float64 positions and sizes of the
+ *        kept objects and the rooms; int32 labels, int64 node ids; int32 one-directional edge lists; for H-trees object_orig,
+ *        room_orig, the 10 + 3 edge lists, and the members of every clique]
+ *     Device stage: the caller copies the block to the device (one copy) and hmp_frame_expand fills the arena in ONE launch; item i
+ *     describes output tensor HMP_FI_TENSOR at byte HMP_FI_DST of the arena, HMP_FI_ROWS x HMP_FI_WIDTH elements.  Every output
+ *     element is a function of the staging block and the resident semantic table alone.
+ *
+ *     Nodes: ids uint64[n], layer int32[n] (2 objects, 3 places, 4 rooms, 5 buildings), pos / bb_min / bb_max float64[n][3],
+ *     label int64[n]; undirected edges uint64[2][m] as node ids (self edges and unknown ids are ignored).  Feature rows are
+ *     x = [pos | bb size | table[label]] in float32 ((float)double; the float32 table row as is; relative_pos drops the leading 3
+ *     columns and adds edge_attr = pos32[dst] - pos32[src], baseline only); rooms take no semantic block.  sem_dim = 0: no table.
+ *     With a table a label of a kept object outside [0, n_labels) is refused (HMP_E_ARG, the message names the node id).
+ *     clique_dim: width of the H-tree's clique rows (0 = the feature width of the objects / rooms).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct hmp_frame hmp_frame; /* opaque */
+int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                    const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
+                    double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
+                    int32_t clique_dim, hmp_frame** out);
+/* sizes[HMP_FS_COUNT] */
+#define HMP_FS_KEPT 0          /* kept objects */
+#define HMP_FS_DROPPED 1       /* objects with neither a place with a room nor a sibling place with one */
+#define HMP_FS_ROOMS 2
+#define HMP_FS_E_OO 3          /* object-object edges, one direction */
+#define HMP_FS_E_RR 4          /* room-room edges, one direction */
+#define HMP_FS_STAGING_BYTES 5 /* what hmp_frame_pack writes */
+#define HMP_FS_ARENA_BYTES 6   /* what hmp_frame_expand writes */
+#define HMP_FS_ITEMS 7
+#define HMP_FS_BLOCKS 8        /* workgroups of the launch */
+#define HMP_FS_HT_COUNTS 9     /* +0..3: H-tree nodes per type (object, room, object-room, room-room) */
+#define HMP_FS_HT_EDGES 13     /* +0..9: edges per HTREE_EDGE_TYPE */
+#define HMP_FS_HT_INIT 23      /* +0..2: init edges ov_to_or, rv_to_or, rv_to_rr */
+#define HMP_FS_COUNT 26
+/* a frame without a room or without a kept object has HMP_FS_ITEMS = 0: nothing to pack, nothing to launch */
+int hmp_frame_sizes(const hmp_frame* f, int64_t* sizes);
+/* every pointer may be null: kept / dropped / rooms = indices into the input arrays (visiting order), obj_room[kept],
+ * rr_edges [2][E_RR], room_bb [rooms][2][3] (min, max), oo_edges [2][E_OO] (object, earlier object) */
+int hmp_frame_host_arrays(const hmp_frame* f, int32_t* kept, int32_t* obj_room, int32_t* dropped, int32_t* rooms, int32_t* rr_edges,
+                          double* room_bb, int32_t* oo_edges);
+int hmp_frame_pack(const hmp_frame* f, void* staging, int64_t bytes);
+void hmp_frame_destroy(hmp_frame* f);
+
+/* words of an item of the staging block's table */
+#define HMP_FRAME_ITEM_WORDS 12
+#define HMP_FI_KIND 0
+#define HMP_FI_TENSOR 1 /* which output tensor (HMP_FT_*) */
+#define HMP_FI_ROWS 2
+#define HMP_FI_WIDTH 3
+#define HMP_FI_DST 4    /* byte offset in the arena, 16-byte aligned */
+#define HMP_FI_S0 5     /* byte offsets of source sections in the staging block (-1: none); meaning per kind, see csrc/frame.hip */
+#define HMP_FI_S1 6
+#define HMP_FI_S2 7
+#define HMP_FI_S3 8
+#define HMP_FI_P0 9     /* parameters per kind */
+#define HMP_FI_P1 10
+#define HMP_FI_BLOCK0 11 /* first workgroup of the item (the prefix table of the launch) */
+#define HMP_FRAME_MAX_ITEMS 64
+/* item kinds */
+#define HMP_FK_FEAT 0   /* float32 rows [pos | size | table[label]], optionally gathered through a row-index vector */
+#define HMP_FK_POS 1    /* float32 [rows][3] */
+#define HMP_FK_I64 2    /* int64 [rows] from an int32 (labels) or int64 (node ids) section */
+#define HMP_FK_EDGE 3   /* int64 [2][width] from an int32 list */
+#define HMP_FK_EATTR 4  /* float32 [rows][3] = pos32[dst] - pos32[src] */
+#define HMP_FK_CLIQUE 5 /* float32 rows [mean float32 position of the member rooms | zeros] */
+/* output tensors: baseline 0..15 = {objects, rooms} x {x, pos, label, node_ids}, then edge_index and edge_attr of
+ * objects_to_objects, rooms_to_rooms, rooms_to_objects, objects_to_rooms; H-tree 16.. = {object, room} x {x, pos, label},
+ * object-room.x, room-room.x, {object_virtual, room_virtual} x {x, pos, label}, the 10 HTREE_EDGE_TYPES, the 3 init edge types,
+ * o_to_ov, r_to_rv */
+#define HMP_FT_HTREE 16
+#define HMP_FT_COUNT 45
+/* One launch on `stream`: d_staging = the packed block on the device (16-byte aligned), d_arena >= HMP_FS_ARENA_BYTES (16-byte
+ * aligned), d_sem_table float32 [n_labels][sem_dim] (8-byte aligned; null when sem_dim = 0); n_items / n_blocks from hmp_frame_sizes.
+ * The item table lives on the device, so this entry cannot compare it with its arguments; the caller owes it three things:
+ *   - sem_dim and the table are those hmp_frame_build was given.  A feature item laid out for another sem_dim (its HMP_FI_P1), or a
+ *     launch without the table, does not read the table: the semantic columns of that item are written as zeros, nothing is refused;
+ *   - the table has at least the n_labels rows hmp_frame_build was given: the row count is not passed to the device, the labels
+ *     were checked against n_labels on the host and that check is the only bound of the table reads;
+ *   - every launch that uses the same staging block or arena runs on ONE stream (they are ordered by it alone). */
+int hmp_frame_expand(const void* d_staging, void* d_arena, const float* d_sem_table, int32_t sem_dim, int32_t n_items,
+                     int32_t n_blocks, void* stream);
 
 #ifdef __cplusplus
 }

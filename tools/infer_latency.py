@@ -2,11 +2,15 @@
 
   a) the reference's expression on this engine:  model(data).argmax(dim=1).cpu()   under torch.no_grad()
   b) model.predict(data): native eval forward + hmp_argmax_rows + one pinned D2H of the labels
+  c) the step in front of the model call, GnnModel.convert_graph: the existing stages of hydra_gnn_amd/dsg.py and htree.py next to
+     dsg.FramePipeline.convert, median and p90 of ``--reps`` calls (default 200); ``--convert-loop N`` runs only N converts per
+     pipeline, for a kernel trace
 
 One MP3D-like scene graph per call (a fresh graph object every call, as the server receives a new frame), 306-d objects,
 3-layer SAGE hidden 64 and the shipped GAT shape (3 layers, 3 heads, hidden 64, concat False).  Prints one JSON line.
 """
 import json
+import os
 import sys
 import time
 
@@ -14,7 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, "hydra-gnn_amd")
-from hydra_gnn_amd import workloads  # noqa: E402
+from hydra_gnn_amd import dsg, htree, workloads  # noqa: E402
 from hydra_gnn_amd.models import HeterogeneousNetwork  # noqa: E402
 
 DEV = "cuda:0"
@@ -54,34 +58,89 @@ def main():
         for f in frames[:4]:
             assert torch.equal(ref_expr(f), net.predict(f))
         out[name] = {"forward_argmax_cpu": a, "predict": b}
-    # ---- the step before the model: spark_dsg JSON frame -> HeteroData (hydra_gnn_amd/dsg.py), on the reference's test graph
-    import os
-
-    from hydra_gnn_amd import dsg
-
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "dsg_x8F5xyUWy9e.json")
-    raw = json.load(open(path))
-    net6 = HeterogeneousNetwork(input_dim_dict={"objects": 6, "rooms": 6}, output_dim=26, dropout=0.25, **nets["sage_h64_l3"]).to(DEV).eval()
-    stages = {}
-
-    def stage(name, fn, reps=50):
-        r = fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter_ns()
-        for _ in range(reps):
-            r = fn()
-        torch.cuda.synchronize()
-        stages[name] = round((time.perf_counter_ns() - t0) * 1e-3 / reps, 1)
-        return r
-
-    sg = stage("parse_static_layers_us", lambda: dsg.load_dsg_json(raw))
-    rog = stage("room_object_graph_us", lambda: dsg.RoomObjectGraph(sg))
-    oo = stage("object_connectivity_hip_us", lambda: dsg.object_connectivity(rog, 1.5, 2.0, 0.2, DEV))
-    data = stage("to_hetero_data_us", lambda: dsg.to_hetero_data(rog, oo, None, DEV))
-    stage("predict_us", lambda: net6.predict(data))
-    out["dsg_frame_62_objects"] = stages
+    # ---- the step before the model: scene graph -> HeteroData (hydra_gnn_amd/dsg.py), on the reference's test graph and on a
+    # 300-object synthetic frame: the existing stages (Python loops + torch glue, three launches and a read-back for the object
+    # edges, the H-tree through generate_htree) next to dsg.FramePipeline.convert (one host stage, one copy, one launch)
+    out["dsg_frame_62_objects"] = frame_stages(dsg.load_dsg_json(json.load(open(FIXTURE))), nets["sage_h64_l3"], raw=json.load(open(FIXTURE)))
+    if hasattr(workloads, "synthetic_scene"):
+        out["dsg_frame_300_objects"] = frame_stages(scene_graph(workloads.synthetic_scene(300, 3, seed=1)), nets["sage_h64_l3"])
     print(json.dumps(out))
 
 
+FIXTURE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "dsg_x8F5xyUWy9e.json")
+REPS = 200
+
+
+def scene_graph(arrays):
+    """dsg.SceneGraph of flat arrays (ids, layer, pos, bb_min, bb_max, label, edges as node ids)"""
+    ids, layer, pos, bb_min, bb_max, label, edges = arrays
+    index = {int(v): i for i, v in enumerate(ids)}
+    adj = [set() for _ in ids]
+    for a, b in zip(edges[0].tolist(), edges[1].tolist()):
+        a, b = index[a], index[b]
+        adj[a].add(b)
+        adj[b].add(a)
+    return dsg.SceneGraph(ids, layer.astype(np.int64), pos, bb_min, bb_max, label, adj)
+
+
+def flat_arrays(sg):
+    if hasattr(dsg, "scene_arrays"):
+        return dsg.scene_arrays(sg)
+    pairs = np.array([(i, j) for i, nb in enumerate(sg.adj) for j in nb if i < j], dtype=np.int64).reshape(-1, 2).T
+    return sg.ids, sg.layer, sg.pos, sg.bb_min, sg.bb_max, sg.label, sg.ids[pairs]
+
+
+def frame_stages(sg, sage_kw, raw=None):
+    """median and p90 over REPS calls of every stage, each call timed to completion (host call + torch.cuda.synchronize())"""
+    net6 = HeterogeneousNetwork(input_dim_dict={"objects": 6, "rooms": 6}, output_dim=26, dropout=0.25, **sage_kw).to(DEV).eval()
+    stages = {}
+
+    def stage(name, fn, reps=REPS):
+        for _ in range(5):
+            r = fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter_ns()
+            r = fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter_ns() - t0) * 1e-3)
+        stages[name + "_us"] = round(float(np.median(ts)), 1)
+        stages[name + "_p90_us"] = round(float(np.percentile(ts, 90)), 1)
+        return r
+
+    if raw is not None:  # the JSON step in front of everything (host only)
+        stage("parse_static_layers", lambda: dsg.load_dsg_json(raw))
+    rog = stage("room_object_graph", lambda: dsg.RoomObjectGraph(sg))
+    oo = stage("object_connectivity_hip", lambda: dsg.object_connectivity(rog, 1.5, 2.0, 0.2, DEV))
+    data = stage("to_hetero_data", lambda: dsg.to_hetero_data(rog, oo, None, DEV))
+    stage("predict", lambda: net6.predict(data))
+    stage("generate_htree", lambda: htree.generate_htree(data, clique_dim=6))
+    stages["objects"], stages["object_edges"] = int(rog.objects.size), int(oo.size(1))
+    if hasattr(dsg, "FramePipeline"):
+        flat = flat_arrays(sg)
+        pipe, pipe_h = dsg.FramePipeline(DEV), dsg.FramePipeline(DEV, htree=True, clique_dim=6)
+        stage("scene_arrays", lambda: flat_arrays(sg))
+        frame, _ = stage("pipeline_convert", lambda: pipe.convert(*flat))
+        stage("pipeline_convert_htree", lambda: pipe_h.convert(*flat))
+        assert torch.equal(net6.predict(frame).clone(), net6.predict(data))
+    return stages
+
+
+def convert_loop(n):
+    """only the pipeline's convert calls (baseline, then H-tree), for a kernel trace of the conversion on its own"""
+    flat = flat_arrays(dsg.load_dsg_json(json.load(open(FIXTURE))))
+    for pipe in (dsg.FramePipeline(DEV), dsg.FramePipeline(DEV, htree=True, clique_dim=6)):
+        for _ in range(n):
+            pipe.convert(*flat)
+    torch.cuda.synchronize()
+    print(json.dumps({"convert_loop": n, "pipelines": 2}))
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 2 and sys.argv[1] == "--convert-loop":
+        convert_loop(int(sys.argv[2]))
+    else:
+        if len(sys.argv) > 2 and sys.argv[1] == "--reps":  # the H-tree of the 300-object frame takes 0.45 s per call
+            REPS = int(sys.argv[2])
+        main()
