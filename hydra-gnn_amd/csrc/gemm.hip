@@ -19,99 +19,31 @@
 // TN with split-K over node chunks (dZ^T * [x | 1], weight + bias gradient; slabs are reduced later).
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemm_tile.h"
 
 namespace hmp {
 
 KT_DEFINE(gemm)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// A (ROWS x BK) tile in registers; logical element (r, k).
-//  kcontig = 1: memory is [r][k] (k contiguous)  -> per thread NV float4 along k
-//  kcontig = 0: memory is [k][r] (r contiguous)  -> per thread NV float4 along r
+// A (ROWS x BK) stage of one operand in the registers of the block's 256 threads; the fast loader and its mask are
+// tile_load_fast / tile_mask (gemm_tile.h), whose slot mapping the edge loader and the LDS store share
 template <int ROWS, int BK>
-struct TileRegs {
-  static constexpr int NV = ROWS * BK / 4 / 256;  // float4 per thread
-  float4 v[NV];
-};
-
-// Fast path: NO control flow between the loads (a branchy loader makes hipcc drain vmcnt between slots, i.e. one load in
-// flight at a time).  Out-of-range rows / k are CLAMPED to an in-range address and zeroed by selects afterwards, so any
-// K stage of a k-contiguous operand (also the tail stage) and any K stage of an r-contiguous operand whose tile width is
-// fully in range take this path.  A 16/8-byte vector never leaves the row: ld is a multiple of the vector width and the
-// vector starts below kend <= ld.
-template <int ROWS, int BK, int VEC>
-__device__ __forceinline__ void tile_load_fast(TileRegs<ROWS, BK>& t, const float* __restrict__ p, int ld, int kcontig, int r0,
-                                               int R, int k0, int kend) {
-  // ISSUES the loads only (clamped addresses); tile_mask zeroes what lies outside the operand when the stage is consumed, one
-  // iteration later -- a select on a loaded value right here makes the compiler wait for the load before the MFMAs it was
-  // meant to overlap with.
-  constexpr int NV = TileRegs<ROWS, BK>::NV;
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = tid + i * 256;
-    const float* src;
-    int o1 = 1, o2 = 2, o3 = 3;  // element offsets (VEC < 4: clamped so that no access leaves [.., kend))
-    if (kcontig) {
-      const int r = q / (BK / 4), k4 = (q % (BK / 4)) * 4;
-      const int gr = r0 + r, gk = k0 + k4;
-      // clamp: row to the last row; k to the start of the stage (always < kend) when the slot starts out of range
-      const int gkc = (gk < kend) ? gk : k0;
-      src = p + (int64_t)(gr < R ? gr : R - 1) * ld + gkc;
-      if (VEC == 1) { o1 = (gkc + 1 < kend) ? 1 : 0; o2 = (gkc + 2 < kend) ? 2 : 0; o3 = (gkc + 3 < kend) ? 3 : 0; }
-      if (VEC == 2) { o2 = (gkc + 2 < kend) ? 2 : 0; }  // the second pair may start at / after kend: re-read the first pair then
-    } else {
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
-      const int gk = k0 + k;
-      src = p + (int64_t)(gk < kend ? gk : k0) * ld + (r0 + r4);
-    }
-    if (VEC == 4) {
-      t.v[i] = *reinterpret_cast<const float4*>(src);
-    } else if (VEC == 2) {
-      const float2 a = *reinterpret_cast<const float2*>(src);
-      const float2 b = *reinterpret_cast<const float2*>(src + o2);
-      t.v[i] = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      t.v[i] = make_float4(src[0], src[o1], src[o2], src[o3]);
-    }
-  }
-}
-
+using TileSide = TileSlots<256, ROWS, BK>;
 template <int ROWS, int BK>
-__device__ __forceinline__ void tile_mask(TileRegs<ROWS, BK>& t, int kcontig, int r0, int R, int k0, int kend) {
-  constexpr int NV = TileRegs<ROWS, BK>::NV;
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = tid + i * 256;
-    if (kcontig) {
-      const int r = q / (BK / 4), k4 = (q % (BK / 4)) * 4;
-      const int gk = k0 + k4;
-      const bool rlive = r0 + r < R;
-      t.v[i] = make_float4(rlive && gk + 0 < kend ? t.v[i].x : 0.f, rlive && gk + 1 < kend ? t.v[i].y : 0.f,
-                           rlive && gk + 2 < kend ? t.v[i].z : 0.f, rlive && gk + 3 < kend ? t.v[i].w : 0.f);
-    } else {
-      const int k = q / (ROWS / 4);
-      if (k0 + k >= kend) t.v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-}
+using TileRegs = StageRegs<TileSide<ROWS, BK>::NV>;
 
 // Edge path (last K stage, last column tile, ones column): bounds-checked element by element.
 // vec: 4 = 16-byte loads, 2 = 8-byte loads (rows only 8-byte aligned, e.g. ld = 306), 1 = scalar
 template <int ROWS, int BK>
 __device__ __forceinline__ void tile_load_edge(TileRegs<ROWS, BK>& t, const float* __restrict__ p, int ld, int kcontig, int r0,
                                                int R, int n_real, int aug, int k0, int kend, int vec) {
-  constexpr int NV = TileRegs<ROWS, BK>::NV;
-  const int tid = threadIdx.x;
+  using S = TileSide<ROWS, BK>;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = tid + i * 256;
+  for (int i = 0; i < S::NV; ++i) {
     float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
     if (kcontig) {
-      const int r = q / (BK / 4), k4 = (q % (BK / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       const int gr = r0 + r, gk = k0 + k4;
       if (gr < R && gk < kend) {
         const float* src = p + (int64_t)gr * ld + gk;
@@ -129,7 +61,8 @@ __device__ __forceinline__ void tile_load_edge(TileRegs<ROWS, BK>& t, const floa
         }
       }
     } else {
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       const int gk = k0 + k, gr = r0 + r4;
       if (gk < kend) {
         const float* src = p + (int64_t)gk * ld + gr;
@@ -160,9 +93,9 @@ __device__ __forceinline__ void tile_load(TileRegs<ROWS, BK>& t, const float* __
   // all conditions are block-uniform
   const bool fast = kcontig || (r0 + ROWS <= n_real);
   if (fast) {
-    if (vec == 4) tile_load_fast<ROWS, BK, 4>(t, p, ld, kcontig, r0, R, k0, kend);
-    else if (vec == 2) tile_load_fast<ROWS, BK, 2>(t, p, ld, kcontig, r0, R, k0, kend);
-    else tile_load_fast<ROWS, BK, 1>(t, p, ld, kcontig, r0, R, k0, kend);
+    if (vec == 4) tile_load_fast<TileSide<ROWS, BK>, 4>(t, p, ld, kcontig, r0, R, k0, kend);
+    else if (vec == 2) tile_load_fast<TileSide<ROWS, BK>, 2>(t, p, ld, kcontig, r0, R, k0, kend);
+    else tile_load_fast<TileSide<ROWS, BK>, 1>(t, p, ld, kcontig, r0, R, k0, kend);
   } else {
     tile_load_edge<ROWS, BK>(t, p, ld, kcontig, r0, R, n_real, aug, k0, kend, vec);
   }
@@ -180,32 +113,24 @@ __device__ __forceinline__ int wrap_rows(int x) {
 }
 template <int ROWS, int BK>
 __device__ __forceinline__ void tile_store(const TileRegs<ROWS, BK>& t, float* __restrict__ s, int kcontig) {
-  constexpr int NV = TileRegs<ROWS, BK>::NV;
+  using S = TileSide<ROWS, BK>;
   constexpr int LD = ROWS + 4;
-  const int tid = threadIdx.x;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int q = tid + i * 256;
+  for (int i = 0; i < S::NV; ++i) {
     if (kcontig) {
-      const int r = q / (BK / 4), k4 = (q % (BK / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       const int rr = wrap_rows<ROWS>(r + (k4 >> 2));
       s[(k4 + 0) * LD + rr] = t.v[i].x;
       s[(k4 + 1) * LD + rr] = t.v[i].y;
       s[(k4 + 2) * LD + rr] = t.v[i].z;
       s[(k4 + 3) * LD + rr] = t.v[i].w;
     } else {
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       *reinterpret_cast<float4*>(&s[k * LD + r4]) = t.v[i];
     }
   }
-}
-
-__device__ __forceinline__ float act_mask_factor(float h, int act, bool keep, float scale) {
-  // d out / d pre for out = dropout(act(pre)) given the stored out value h
-  if (!keep) return 0.f;
-  if (act == HMP_ACT_RELU) return h > 0.f ? scale : 0.f;
-  if (act == HMP_ACT_ELU) return h > 0.f ? scale : (h + scale);  // elu'(pre) = elu(pre) + 1 for pre <= 0
-  return scale;
 }
 
 __device__ __forceinline__ int vec_mode(const float* p, int ld, bool k_ok) {
@@ -216,8 +141,7 @@ __device__ __forceinline__ int vec_mode(const float* p, int ld, bool k_ok) {
   return 1;
 }
 
-// FORM fixes the operand layouts at compile time (0: NT = x * W^T, 1: NN = dZ * W, 2: TN = dZ^T * [x | 1]; 3: per problem at run
-// time): with run-time layouts the layout branch sits inside the unrolled load loops and the loads stop overlapping.
+// FORM: the operand layouts, fixed at compile time or 3 = per problem at run time (gemm_tile.h, below gemm_tile_walk).
 // MI x NI 32x32 accumulator tiles per wave (round 2): <2,2,32,.,2,2> = a 128x128 tile, every operand fragment fetched from LDS
 // feeds two MFMAs instead of one and the tile re-reads A / B from L2 half as often -- the 64x64 form ran the big problems
 // (GAT projections, batch-2048 weight gradients) at 34-60 TFLOP/s, bound by L2 -> CU operand traffic at 16 flop per byte.
@@ -239,14 +163,11 @@ __global__ __launch_bounds__(256, (MI * NI > 1) ? 2 : 3) void gemm_kernel(const 
   while (pi + 1 < gb.n && (int)blockIdx.x >= gb.p[pi + 1].tile_start) ++pi;
   const GemmProblem& P = gb.p[pi];
   const int local = blockIdx.x - P.tile_start;
-  const int tiles_mn = P.tiles_m * P.tiles_n;
-  // XCD-aware order (blocks b and b+8 share an XCD and its 4 MB L2; speed only, never correctness):
-  //  * split-K: the K chunk index is the fastest-varying part of the block id, so with ksplit = 8 (or 16) all tiles
-  //    of one chunk run on one XCD and its A/B panels are fetched into that L2 once;
-  //  * otherwise row tiles are grouped by 8 and the column tiles of one row tile are 8 block ids apart, so the row
-  //    panel of A (the big operand: nodes x features) is fetched once per XCD instead of once per column tile.
+  // This kernel keeps its OWN copies of gemm_tile.h's walk (gemm_tile_walk), accumulator set-up (gemm_acc_init) and epilogue
+  // (gemm_epilogue<MI, NI, false, false, false>): on the shared ones its 32 x 32 classes lost registers and gained s_waitcnt vmcnt(0)
+  // drains (TN, K stage 128: 12 -> 14, 118 -> 98 VGPRs), and the plain TN product 192 x 307 x 2831 ran 15 % slower (BASELINE.md,
+  // "Shared GEMM tile code").  A change there belongs here too.  It shares the staging pair, the slot mapping and the factor.
   const int z = local % P.ksplit, t = local / P.ksplit;
-  (void)tiles_mn;
   const int grp = t / (8 * P.tiles_n), within = t % (8 * P.tiles_n);
   const int rows_in_grp = min(8, P.tiles_m - grp * 8);
   const int m0 = (grp * 8 + within % rows_in_grp) * BM, n0 = (within / rows_in_grp) * BN;
@@ -293,11 +214,12 @@ __global__ __launch_bounds__(256, (MI * NI > 1) ? 2 : 3) void gemm_kernel(const 
   tile_load<BM, BK>(ra, P.A, P.lda, a_kcontig, m0, P.M, P.M, 0, kbeg, kend, a_vec);
   tile_load<BN, BK>(rb, P.B, P.ldb, b_kcontig, n0, P.n_real, P.n_real, P.aug_ones, kbeg, kend, b_vec);
 
+#ifdef HMP_KTIME
   int kti = 0;
-  (void)kti;
+#endif
   for (int kt = kbeg; kt < kend; kt += BK) {
-    if (a_fast) tile_mask<BM, BK>(ra, a_kcontig, m0, P.M, kt, kend);
-    if (b_fast) tile_mask<BN, BK>(rb, b_kcontig, n0, P.n_real, kt, kend);
+    if (a_fast) tile_mask<TileSide<BM, BK>>(ra, a_kcontig, m0, P.M, kt, kend);
+    if (b_fast) tile_mask<TileSide<BN, BK>>(rb, b_kcontig, n0, P.n_real, kt, kend);
     tile_store<BM, BK>(ra, As, a_kcontig);
     tile_store<BN, BK>(rb, Bs, b_kcontig);
     __syncthreads();
@@ -357,10 +279,7 @@ __global__ __launch_bounds__(256, (MI * NI > 1) ? 2 : 3) void gemm_kernel(const 
   }
   if (kw != 0) return;
 
-  // A = [i][k] supplies the rows of C, B = [k][j] its columns;
-  // D layout: col j = lane & 31, row i = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
-  // No branch between memory operations: fields in registers, the 16 activation values requested together (clamped addresses),
-  // predicated stores.  (With a `continue` per element the compiler waited for every H load before issuing the next one.)
+  // gemm_epilogue of gemm_tile.h, kept here (see the walk above); its contract holds: no branch between memory operations
   float* C = P.C + (int64_t)z * P.slab_stride;
   const int Mrows = P.M, Ncols = P.N, ldc = P.ldc, ldh = P.ldh, act = P.act;
   const bool amask = P.epi == EPI_ACTMASK;
@@ -390,7 +309,7 @@ __global__ __launch_bounds__(256, (MI * NI > 1) ? 2 : 3) void gemm_kernel(const 
         if (amask) {
           // the forward stored dropped elements as -0.0f: the keep bit is the sign of a zero, no RNG replay needed
           const bool keep = !dropon || (__float_as_uint(hv[r]) != 0x80000000u);
-          v *= act_mask_factor(hv[r], act, keep, dscale);
+          v *= gemm_act_mask(hv[r], act, keep, dscale);
         }
         if (cok && row < Mrows) C[(int64_t)row * ldc + col] = v;
       }

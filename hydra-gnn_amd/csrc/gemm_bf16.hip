@@ -21,92 +21,36 @@
 // (dZ^T * [x | 1]) -- the same GemmProblem contract as gemm.hip.
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemm_tile.h"
 
 namespace hmp {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // K stage BK (64 for the 128x128 tile, 32 for the 256x256 tile: 8 / 4 float4 slots per thread, operand and stage);
 // [row][k] images have a pitch of BK + 8 bf16 elements (16-byte aligned rows)
-template <int NV>
-struct StageRegs {
-  float4 v[NV];
-};
-
 // Block shapes <NT threads, ROWS x ROWS tile>: <256, 128> (4 waves, 2x2, 64x64 per wave) and <512, 256> (8 waves, 4x2,
 // 64x128 per wave).  The big tile exists because these GEMMs are bound by L2 -> CU operand traffic (~4.7 TB/s aggregate
 // measured): a 128x128 tile re-reads A once per 128 output columns and B once per 128 output rows (12 GB for the config-5
 // layer-0 projection), a 256x256 tile halves both.
-//  kcontig: slot q covers row q / 16, k4 = (q % 16) * 4      rcontig: slot q covers k = q / (ROWS/4), r4 = (q % (ROWS/4)) * 4
-// bf_load_fast only ISSUES the stage's loads (clamped addresses, nothing reads the registers); bf_mask zeroes what lies outside
-// the operand when the stage is consumed, one iteration later.  With the masks applied in the loader the compiler had to wait
-// for every load right there -- before the MFMAs the prefetch was meant to overlap with (and, with the layout branch inside the
-// loop, even between one load and the next).
-template <int NT, int ROWS, int BKB>
-__device__ __forceinline__ void bf_load_fast(StageRegs<ROWS * BKB / 4 / NT>& t, const float* __restrict__ p, int ld, int kcontig, int r0, int R,
-                                             int k0, int kend) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
-  const int tid = threadIdx.x;
-  if (kcontig) {
-#pragma unroll
-    for (int i = 0; i < BNV; ++i) {
-      const int q = tid + i * NT;
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
-      const int gr = r0 + r, gk = k0 + k4;
-      t.v[i] = *reinterpret_cast<const float4*>(p + (int64_t)(gr < R ? gr : R - 1) * ld + (gk < kend ? gk : k0));
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < BNV; ++i) {
-      const int q = tid + i * NT;
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
-      const int gk = k0 + k;
-      t.v[i] = *reinterpret_cast<const float4*>(p + (int64_t)(gk < kend ? gk : k0) * ld + (r0 + r4));
-    }
-  }
-}
-
-template <int NT, int ROWS, int BKB>
-__device__ __forceinline__ void bf_mask(StageRegs<ROWS * BKB / 4 / NT>& t, int kcontig, int r0, int R, int k0, int kend) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
-    if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
-      const int gk = k0 + k4;
-      const bool rl = r0 + r < R;
-      t.v[i] = make_float4(rl && gk + 0 < kend ? t.v[i].x : 0.f, rl && gk + 1 < kend ? t.v[i].y : 0.f, rl && gk + 2 < kend ? t.v[i].z : 0.f,
-                           rl && gk + 3 < kend ? t.v[i].w : 0.f);
-    } else {
-      const int k = q / (ROWS / 4);
-      if (k0 + k >= kend) t.v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-}
-
+// fp32 operands are staged by tile_load_fast<.., 4> / tile_mask (gemm_tile.h: slot mapping, issue now / mask later); a partial tile
+// of a row-contiguous operand, or an unaligned one, goes through bf_load_edge.
 // Operand that already exists as bf16 (dZ written by the transposed aggregation in bf16 compute mode): 8 bytes per slot, no
-// conversion.  Same slot mapping and the same issue-now / mask-later split as bf_load_fast; the 4 bf16 travel as raw bits in
+// conversion.  Same slot mapping and the same issue-now / mask-later split as tile_load_fast (gemm_tile.h); the 4 bf16 travel as raw bits in
 // v[i].x / .y.
 template <int NT, int ROWS, int BKB>
 __device__ __forceinline__ void bf_load16(StageRegs<ROWS * BKB / 4 / NT>& t, const uint16_t* __restrict__ p, int ld, int kcontig, int r0, int R,
                                           int k0, int kend) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
-  const int tid = threadIdx.x;
+  using S = TileSlots<NT, ROWS, BKB>;
 #pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
+  for (int i = 0; i < S::NV; ++i) {
     uint2 bits;
     if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       const int gr = r0 + r, gk = k0 + k4;
       bits = *reinterpret_cast<const uint2*>(p + (int64_t)(gr < R ? gr : R - 1) * ld + (gk < kend ? gk : k0));
     } else {
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       const int gk = k0 + k;
       bits = *reinterpret_cast<const uint2*>(p + (int64_t)(gk < kend ? gk : k0) * ld + (r0 + r4));
     }
@@ -117,14 +61,13 @@ __device__ __forceinline__ void bf_load16(StageRegs<ROWS * BKB / 4 / NT>& t, con
 
 template <int NT, int ROWS, int BKB>
 __device__ __forceinline__ void bf_mask16(StageRegs<ROWS * BKB / 4 / NT>& t, int kcontig, int r0, int R, int k0, int kend) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
-  const int tid = threadIdx.x;
+  using S = TileSlots<NT, ROWS, BKB>;
 #pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
+  for (int i = 0; i < S::NV; ++i) {
     uint32_t x = __float_as_uint(t.v[i].x), y = __float_as_uint(t.v[i].y);
     if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       const int gk = k0 + k4;
       const bool rl = r0 + r < R;
       if (!(rl && gk + 0 < kend)) x &= 0xffff0000u;
@@ -132,7 +75,8 @@ __device__ __forceinline__ void bf_mask16(StageRegs<ROWS * BKB / 4 / NT>& t, int
       if (!(rl && gk + 2 < kend)) y &= 0xffff0000u;
       if (!(rl && gk + 3 < kend)) y &= 0x0000ffffu;
     } else {
-      const int k = q / (ROWS / 4);
+      int k, r4;
+      S::slot_kr(i, k, r4);
       if (k0 + k >= kend) x = y = 0u;
     }
     t.v[i].x = __uint_as_float(x);
@@ -142,19 +86,19 @@ __device__ __forceinline__ void bf_mask16(StageRegs<ROWS * BKB / 4 / NT>& t, int
 
 template <int NT, int ROWS, int BKB>
 __device__ __forceinline__ void bf_store16(const StageRegs<ROWS * BKB / 4 / NT>& t, __bf16* __restrict__ s, int kcontig) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
+  using S = TileSlots<NT, ROWS, BKB>;
   constexpr int BPITCH = BKB + 8;
   constexpr int RP = ROWS + 8;
-  const int tid = threadIdx.x;
 #pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
+  for (int i = 0; i < S::NV; ++i) {
     const uint2 bits = make_uint2(__float_as_uint(t.v[i].x), __float_as_uint(t.v[i].y));
     if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       *reinterpret_cast<uint2*>(s + r * BPITCH + k4) = bits;
     } else {
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       *reinterpret_cast<uint2*>(s + k * RP + r4) = bits;
     }
   }
@@ -164,14 +108,13 @@ __device__ __forceinline__ void bf_store16(const StageRegs<ROWS * BKB / 4 / NT>&
 template <int NT, int ROWS, int BKB>
 __device__ __forceinline__ void bf_load_edge(StageRegs<ROWS * BKB / 4 / NT>& t, const float* __restrict__ p, int ld, int kcontig, int r0, int R,
                                              int n_real, int aug, int k0, int kend) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
-  const int tid = threadIdx.x;
+  using S = TileSlots<NT, ROWS, BKB>;
 #pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
+  for (int i = 0; i < S::NV; ++i) {
     float e[4] = {0.f, 0.f, 0.f, 0.f};
     if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       const int gr = r0 + r;
       if (gr < R) {
 #pragma unroll
@@ -179,7 +122,8 @@ __device__ __forceinline__ void bf_load_edge(StageRegs<ROWS * BKB / 4 / NT>& t, 
           if (k0 + k4 + j < kend) e[j] = p[(int64_t)gr * ld + k0 + k4 + j];
       }
     } else {  // columns past n_real are zero, the ones column is virtual
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       const int gk = k0 + k;
       if (gk < kend) {
 #pragma unroll
@@ -195,76 +139,37 @@ __device__ __forceinline__ void bf_load_edge(StageRegs<ROWS * BKB / 4 / NT>& t, 
 
 template <int NT, int ROWS, int BKB>
 __device__ __forceinline__ void bf_store(const StageRegs<ROWS * BKB / 4 / NT>& t, __bf16* __restrict__ s, int kcontig) {
-  constexpr int BNV = ROWS * BKB / 4 / NT;
+  using S = TileSlots<NT, ROWS, BKB>;
   constexpr int BPITCH = BKB + 8;
   constexpr int RP = ROWS + 8;  // bf16 elements per k row of a [k][row] image (8-byte aligned rows)
-  const int tid = threadIdx.x;
 #pragma unroll
-  for (int i = 0; i < BNV; ++i) {
-    const int q = tid + i * NT;
+  for (int i = 0; i < S::NV; ++i) {
     bf16x4 b;
     b[0] = (__bf16)t.v[i].x; b[1] = (__bf16)t.v[i].y; b[2] = (__bf16)t.v[i].z; b[3] = (__bf16)t.v[i].w;
     if (kcontig) {
-      const int r = q / (BKB / 4), k4 = (q % (BKB / 4)) * 4;
+      int r, k4;
+      S::slot_rk(i, r, k4);
       *reinterpret_cast<bf16x4*>(s + r * BPITCH + k4) = b;
     } else {  // natural [k][row] image
-      const int k = q / (ROWS / 4), r4 = (q % (ROWS / 4)) * 4;
+      int k, r4;
+      S::slot_kr(i, k, r4);
       *reinterpret_cast<bf16x4*>(s + k * RP + r4) = b;
     }
   }
 }
 
-// MFMA operand (8 consecutive k of row `rowbase + lane % 32`, k half lane / 32) of k step ks
-//  [row][k] image: one 16-byte read.   [k][row] image: two hardware-transposed reads (ds_read_b64_tr_b16): inside a
-//  16-lane group, lane 4q+p supplies the address of k row q, columns 4p..4p+3 and receives column (lane % 16), 4 k rows.
-//  EXEC must be all ones here (no divergence in the main loop).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-template <int ROWS, int BKB>
-__device__ __forceinline__ bf16x8 bf_fetch(const __bf16* __restrict__ s, int kcontig, int rowbase, int ks, int lane) {
-  constexpr int BPITCH = BKB + 8;
-  constexpr int RP = ROWS + 8;
-  if (kcontig) return *reinterpret_cast<const bf16x8*>(s + (rowbase + (lane & 31)) * BPITCH + ks * 16 + 8 * (lane >> 5));
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-  const int k0 = ks * 16 + 8 * (g >> 1);
-  const __bf16* a0 = s + (k0 + q) * RP + rowbase + 16 * (g & 1) + 4 * p;
-  typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a0 + 4 * RP));
-  union { s16x4 h[2]; bf16x8 v; } u;
-  u.h[0] = lo;
-  u.h[1] = hi;
-  return u.v;
-}
-
-__device__ __forceinline__ float bf_act_mask(float h, int act, bool keep, float scale) {
-  if (!keep) return 0.f;
-  if (act == HMP_ACT_RELU) return h > 0.f ? scale : 0.f;
-  if (act == HMP_ACT_ELU) return h > 0.f ? scale : (h + scale);
-  return scale;
-}
-
 // NT threads, ROWS x ROWS tile, waves WMW (along M) x WNW (along N), every wave (ROWS/WMW) x (ROWS/WNW) = MI x NI MFMA tiles
-// FORM fixes the operand layouts at compile time (0: NT = x * W^T, 1: NN = dZ * W, 2: TN = dZ^T * [x | 1]; 3: per problem at run
-// time).  With run-time layouts the branches sit inside the unrolled load / LDS-read loops and every access waits for the one
-// before it.
+// FORM: the operand layouts, fixed at compile time or 3 = per problem at run time (the comment at gemm_tile_walk in gemm_tile.h).
 template <bool ONES, int NT, int ROWS, int WMW, int WNW, int BKB, int FORM>
 __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const GemmBatch gb) {
   constexpr int MI = ROWS / WMW / 32, NI = ROWS / WNW / 32;
-  constexpr int BPITCH = BKB + 8;
+  constexpr int BPITCH = BKB + 8, RP = ROWS + 8;  // pitches of the [row][k] / [k][row] LDS images
+  using S = TileSlots<NT, ROWS, BKB>;
   constexpr int LDSN = (ROWS * BPITCH > BKB * (ROWS + 8)) ? ROWS * BPITCH : BKB * (ROWS + 8);
   __shared__ __attribute__((aligned(16))) __bf16 As[LDSN];
   __shared__ __attribute__((aligned(16))) __bf16 Bs[LDSN];
-  int pi = 0;
-  while (pi + 1 < gb.n && (int)blockIdx.x >= gb.p[pi + 1].tile_start) ++pi;
-  const GemmProblem& P = gb.p[pi];
-  const int local = blockIdx.x - P.tile_start;
-  // XCD-aware order as in gemm.hip: K chunk fastest; row tiles grouped by 8 so that the column tiles of a row tile share an L2
-  const int z = local % P.ksplit, t = local / P.ksplit;
-  const int grp = t / (8 * P.tiles_n), within = t % (8 * P.tiles_n);
-  const int rows_in_grp = min(8, P.tiles_m - grp * 8);
-  const int m0 = (grp * 8 + within % rows_in_grp) * ROWS, n0 = (within / rows_in_grp) * ROWS;
-  const int kbeg = z * P.kchunk;
-  const int kend = min(P.K, kbeg + P.kchunk);
+  int z, m0, n0, kbeg, kend;
+  const GemmProblem& P = gb.p[gemm_tile_walk<ROWS, ROWS>(gb, z, m0, n0, kbeg, kend)];
   const int a_kc = FORM == 3 ? (P.trans_a ? 0 : 1) : (FORM == 2 ? 0 : 1);
   const int b_kc = FORM == 3 ? (P.trans_b ? 1 : 0) : (FORM == 0 ? 1 : 0);
   // block-uniform loader choice
@@ -281,25 +186,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const 
   const int wm = w % WMW, wn = w / WMW;
   const bool ones_here = ONES && P.aug_ones && n0 == 0 && wn == 0;  // wave-uniform
 
+  const int row0 = m0 + wm * (MI * 32), col0 = n0 + wn * (NI * 32);  // the wave's corner of C
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  if (P.Cadd && z == 0) {  // block-uniform: the product accumulates ON TOP of the addend (GemmProblem::Cadd)
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wm * (MI * 32) + i * 32 + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2);
-          const int col = n0 + wn * (NI * 32) + j * 32 + (lane & 31);
-          acc[i][j][r] = (row < P.M && col < P.N) ? P.Cadd[(int64_t)row * P.ldadd + col] : 0.f;
-        }
-  }
+  gemm_acc_init<MI, NI>(acc, P, z == 0, row0, col0, lane);
 
   f32x16 acc1[ONES ? MI : 1];
 #pragma unroll
@@ -310,7 +199,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const 
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
 
-  StageRegs<ROWS * BKB / 4 / NT> ra, rb;
+  StageRegs<S::NV> ra, rb;
   // A in two pieces (a_split): [k][row] images (weight gradient) pick the piece per row tile, [row][k] images (input
   // gradient) per K stage; the second base is moved back by a_split elements so that the loaders keep their global indices
   const uint16_t* A16 = reinterpret_cast<const uint16_t*>(P.A);
@@ -322,18 +211,18 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const 
       const bool second = a_tile2 || (a_two && a_kc && k0 >= P.a_split);
       bf_load16<NT, ROWS, BKB>(ra, second ? A16b : A16, second ? P.lda2 : P.lda, a_kc, m0, P.M, k0, kend);
     }
-    else if (a_fast) bf_load_fast<NT, ROWS, BKB>(ra, P.A, P.lda, a_kc, m0, P.M, k0, kend);
+    else if (a_fast) tile_load_fast<S, 4>(ra, P.A, P.lda, a_kc, m0, P.M, k0, kend);
     else bf_load_edge<NT, ROWS, BKB>(ra, P.A, P.lda, a_kc, m0, P.M, P.M, 0, k0, kend);
     if (b_16) bf_load16<NT, ROWS, BKB>(rb, reinterpret_cast<const uint16_t*>(P.B), P.ldb, b_kc, n0, P.n_real, k0, kend);
-    else if (b_fast) bf_load_fast<NT, ROWS, BKB>(rb, P.B, P.ldb, b_kc, n0, P.n_real, k0, kend);
+    else if (b_fast) tile_load_fast<S, 4>(rb, P.B, P.ldb, b_kc, n0, P.n_real, k0, kend);
     else bf_load_edge<NT, ROWS, BKB>(rb, P.B, P.ldb, b_kc, n0, P.n_real, P.n_real, P.aug_ones, k0, kend);
   };
   load(kbeg);
   for (int kt = kbeg; kt < kend; kt += BKB) {
     if (a_16) bf_mask16<NT, ROWS, BKB>(ra, a_kc, m0, P.M, kt, kend);
-    else if (a_fast) bf_mask<NT, ROWS, BKB>(ra, a_kc, m0, P.M, kt, kend);
+    else if (a_fast) tile_mask<S>(ra, a_kc, m0, P.M, kt, kend);
     if (b_16) bf_mask16<NT, ROWS, BKB>(rb, b_kc, n0, P.n_real, kt, kend);
-    else if (b_fast) bf_mask<NT, ROWS, BKB>(rb, b_kc, n0, P.n_real, kt, kend);
+    else if (b_fast) tile_mask<S>(rb, b_kc, n0, P.n_real, kt, kend);
     if (a_16) bf_store16<NT, ROWS, BKB>(ra, As, a_kc);
     else bf_store<NT, ROWS, BKB>(ra, As, a_kc);
     if (b_16) bf_store16<NT, ROWS, BKB>(rb, Bs, b_kc);
@@ -344,9 +233,9 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const 
     for (int ks = 0; ks < BKB / 16; ++ks) {
       bf16x8 av[MI], bv[NI];
 #pragma unroll
-      for (int i = 0; i < MI; ++i) av[i] = bf_fetch<ROWS, BKB>(As, a_kc, wm * (MI * 32) + i * 32, ks, lane);
+      for (int i = 0; i < MI; ++i) av[i] = mfma_fetch_bf16<BPITCH, RP>(As, a_kc, wm * (MI * 32) + i * 32, ks, lane);
 #pragma unroll
-      for (int j = 0; j < NI; ++j) bv[j] = bf_fetch<ROWS, BKB>(Bs, b_kc, wn * (NI * 32) + j * 32, ks, lane);
+      for (int j = 0; j < NI; ++j) bv[j] = mfma_fetch_bf16<BPITCH, RP>(Bs, b_kc, wn * (NI * 32) + j * 32, ks, lane);
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -361,78 +250,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void gemm_bf16_kernel(const 
     __syncthreads();
   }
 
-  // D layout of a 32x32 tile: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-  // Epilogue without branches between memory operations: the problem's fields live in registers, the 16 activation values of
-  // a 32x32 tile are requested together (clamped addresses), stores are predicated.  (Written element by element with
-  // `continue`s, every H load was waited for before the next one was issued: 128 dependent round trips per thread.)
-  float* C = P.C + (int64_t)z * P.slab_stride;
-  const int Mrows = P.M, Ncols = P.N, ldc = P.ldc, ldh = P.ldh, act = P.act;
-  const bool amask = P.epi == EPI_ACTMASK;
-  const bool dropon = P.drop_on != 0;
-  const bool c16 = P.c_bf16 != 0;
-  const float dscale = dropon ? P.drop.scale : 1.f;
-  const float* Hp = P.H;
-  const bool h16 = P.h_bf16 != 0;  // block-uniform: the activations were stored as bf16 (sign of zero = keep bit survives)
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int col = n0 + wn * (NI * 32) + j * 32 + (lane & 31);
-      const int rbase = m0 + wm * (MI * 32) + i * 32 + 4 * (lane >> 5);
-      const bool cok = col < Ncols;
-      const int colc = cok ? col : 0;
-      float hv[16];
-      if (amask && h16) {  // hoisted like c16 below: no branch between the 16 loads of either form
-        const uint16_t* Hb = reinterpret_cast<const uint16_t*>(Hp);
-        uint16_t hb[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          hb[r] = Hb[(int64_t)(row < Mrows ? row : Mrows - 1) * ldh + colc];
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hv[r] = __uint_as_float((uint32_t)hb[r] << 16);
-      } else if (amask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          hv[r] = Hp[(int64_t)(row < Mrows ? row : Mrows - 1) * ldh + colc];
-        }
-      }
-      float vv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float v = acc[i][j][r];
-        if (amask) {
-          const bool keep = !dropon || (__float_as_uint(hv[r]) != 0x80000000u);  // dropped elements were stored as -0.0f
-          v *= bf_act_mask(hv[r], act, keep, dscale);
-        }
-        vv[r] = v;
-      }
-      if (c16) {  // block-uniform: bf16 projected rows (ldc counts elements)
-        __bf16* C16 = reinterpret_cast<__bf16*>(C);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          if (cok && row < Mrows) C16[(int64_t)row * ldc + col] = (__bf16)vv[r];
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          if (cok && row < Mrows) C[(int64_t)row * ldc + col] = vv[r];
-        }
-      }
-    }
-  if (ONES && ones_here && (lane & 31) == 0) {  // column 0 of the ones product -> C[:, n_real]
-#pragma unroll
-    for (int i = 0; i < (ONES ? MI : 1); ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * (MI * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < P.M) C[(int64_t)row * P.ldc + P.n_real] = acc1[i][r];
-      }
-  }
+  gemm_epilogue<MI, NI, true, ONES, false>(P, z, acc, acc1, ones_here, row0, col0, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -701,7 +519,7 @@ static int ws_launch(const GemmProblem& p, hipStream_t st) {
 // Measured on top of this kernel and rejected (config 5, 28.7 ms/step): a bf16 image of the stacked weights as B operand (half
 // the bytes, the same number of requests per stage: forward 5.14 -> 5.19 ms, backward 8.25 -> 8.99 ms) and two stages of register
 // prefetch instead of one (256 VGPRs + scratch spills: forward 5.50 ms, backward 13.5 ms).  The cause was elsewhere (the ISA: every load
-// of a stage was waited for before the next, see bf_load_fast / the epilogue).  With that fixed the kernel moves ~7.5 TB/s through
+// of a stage was waited for before the next, see tile_load_fast / gemm_epilogue in gemm_tile.h).  With that fixed the kernel moves ~7.5 TB/s through
 // L2; two stages of prefetch were measured again on the clean loader (no spills for the plain products) and are still slower
 // (forward 2.72 -> 2.87 ms, backward 3.75 -> 4.04 ms), and so is the bf16 weight image (2.75 / 4.03 ms): neither bytes nor
 // requests explain the ~26 us per tile that remain (MFMA floor 3.4 us); LDS traffic / barriers are the untested suspects.  AGPRs are no extra budget here: 8

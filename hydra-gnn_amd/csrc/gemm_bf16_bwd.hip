@@ -21,21 +21,9 @@
 //                         conflict-free on that image.  The bias column (row sums of dZ^T) is one extra MFMA per wave and k step
 //                         against an all-ones operand.  An fp32 H (the input features of layer 0) is converted in registers and
 //                         written into the same image (8-byte ds_writes) one chunk ahead.
-#include "kernels.h"
+#include "gemm_tile.h"
 
 namespace hmp {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bwd_act_mask(float h, int act, bool keep, float scale) {
-  if (!keep) return 0.f;
-  if (act == HMP_ACT_RELU) return h > 0.f ? scale : 0.f;
-  if (act == HMP_ACT_ELU) return h > 0.f ? scale : (h + scale);
-  return scale;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // input gradient
@@ -247,7 +235,7 @@ __global__ __launch_bounds__(DX_THREADS, (NBUF > 4 ? 1 : 2)) void gemm_bf16_dx_k
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const bool keep = !a.drop_on || hw[e] != 0x80000000u;  // dropped elements were stored as -0
-            vv[4 * g + e] *= bwd_act_mask(__uint_as_float(hw[e]), a.act, keep, a.dscale);
+            vv[4 * g + e] *= gemm_act_mask(__uint_as_float(hw[e]), a.act, keep, a.dscale);
           }
         }
         union { bf16x4 b; uint2 u; } o;

@@ -20,16 +20,11 @@
 // aligned (MP3D object features: pitch 306) load as float2 pairs.
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemm_tile.h"
 
 namespace hmp {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int X3_BK = 32;  // K stage
 // Tile shape: <256 threads, 128 x 128, 2 x 2 waves of 64 x 64>, two workgroups per CU, 60 KB of LDS each.  These products are bound
@@ -39,9 +34,8 @@ constexpr int X3_BK = 32;  // K stage
 // every fragment + the staging registers spill 500-1000 registers at the 256 a wave gets with 8 waves per CU -- not built.
 // one operand's tile: ROWS rows x X3_BK k, staged by NT threads
 template <int NT_, int ROWS_>
-struct X3Side {
-  static constexpr int NT = NT_, ROWS = ROWS_;
-  static constexpr int NV = ROWS * X3_BK / 4 / NT;  // float4 slots per thread
+struct X3Side : TileSlots<NT_, ROWS_, X3_BK> {
+  static constexpr int ROWS = ROWS_;
   static constexpr int PITCH = X3_BK + 8;  // [row][k] image: 40 bf16 = 80 bytes per row (odd multiple of 16 bytes: 8 consecutive rows cover all banks)
   static constexpr int RP = ROWS + 8;      // [k][row] image: bf16 elements per k row
   static constexpr int PLANE = (ROWS * PITCH > X3_BK * RP) ? ROWS * PITCH : X3_BK * RP;
@@ -60,86 +54,16 @@ struct X3Cfg {
 using X3Small = X3Cfg<256, 128, 128, 2, 2, 2>;
 using X3Narrow = X3Cfg<256, 128, 64, 2, 2, 3>;
 
+// A (128 x 32) stage of one operand goes through tile_load_fast / tile_mask (gemm_tile.h) with CLAMP_COLS / MASK_COLS: VEC 1 also takes
+// the partial tiles of a row-contiguous operand, element by element.
 template <int NV>
-struct Regs {
-  float4 v[NV];
-};
-
-// A (128 x 32) stage of one operand in registers: slot q of a k-contiguous operand ([row][k] in memory) covers row q / 8, k = 4 (q % 8)
-// .. + 3; of a row-contiguous one ([k][row]) k = q / 32, rows 4 (q % 32) .. + 3.  VEC: 4 = one 16-byte load, 2 = two 8-byte loads (rows
-// only 8-byte aligned: MP3D features, pitch 306), 1 = four scalar loads (odd pitches; partial tiles of a row-contiguous operand).
-// The loader only ISSUES loads, all of them at clamped in-range addresses and without a branch in between; x3_mask zeroes what lies
-// outside the operand when the stage is consumed, one iteration later (a select right here would make the compiler wait for each load
-// before the MFMAs it is meant to overlap with: gemm.hip).
-template <class C, int VEC>
-__device__ __forceinline__ void x3_load(Regs<C::NV>& t, const float* __restrict__ p, int ld, int kcontig, int r0, int R, int k0, int kend) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < C::NV; ++i) {
-    const int q = tid + i * C::NT;
-    const float* src;
-    int o1 = 1, o2 = 2, o3 = 3;
-    if (kcontig) {
-      const int r = q / (X3_BK / 4), k4 = (q % (X3_BK / 4)) * 4;
-      const int gr = r0 + r, gk = k0 + k4;
-      const int gkc = (gk < kend) ? gk : k0;  // a slot past the operand re-reads the start of the stage
-      src = p + (int64_t)(gr < R ? gr : R - 1) * ld + gkc;
-      // VEC 4: ld is a multiple of 4 and gkc one too, so the vector ends inside the row.  VEC 2: the first pair ends at gkc + 1 <= ld - 1
-      // (ld even), the second may start at / after kend.  VEC 1: every element on its own
-      if (VEC == 2) o2 = (gkc + 2 < kend) ? 2 : 0;
-      if (VEC == 1) { o1 = (gkc + 1 < kend) ? 1 : 0; o2 = (gkc + 2 < kend) ? 2 : 0; o3 = (gkc + 3 < kend) ? 3 : 0; }
-    } else {
-      const int k = q / (C::ROWS / 4), r4 = (q % (C::ROWS / 4)) * 4;
-      const int gk = k0 + k, c = r0 + r4;
-      const float* row = p + (int64_t)(gk < kend ? gk : k0) * ld;
-      if (VEC == 1) {  // partial tile: every column clamped into the operand
-        src = row + (c < R ? c : R - 1);
-        o1 = (c + 1 < R) ? 1 : 0; o2 = (c + 2 < R) ? 2 : 0; o3 = (c + 3 < R) ? 3 : 0;
-        if (c >= R) o1 = o2 = o3 = 0;
-      } else {
-        src = row + c;  // whole tile inside the operand (the caller's choice of VEC)
-      }
-    }
-    if (VEC == 4) {
-      t.v[i] = *reinterpret_cast<const float4*>(src);
-    } else if (VEC == 2) {
-      const float2 a = *reinterpret_cast<const float2*>(src);
-      const float2 b = *reinterpret_cast<const float2*>(src + o2);
-      t.v[i] = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      t.v[i] = make_float4(src[0], src[o1], src[o2], src[o3]);
-    }
-  }
-}
-
-template <class C>
-__device__ __forceinline__ void x3_mask(Regs<C::NV>& t, int kcontig, int r0, int R, int k0, int kend) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < C::NV; ++i) {
-    const int q = tid + i * C::NT;
-    if (kcontig) {
-      const int r = q / (X3_BK / 4), k4 = (q % (X3_BK / 4)) * 4;
-      const int gk = k0 + k4;
-      const bool rl = r0 + r < R;
-      t.v[i] = make_float4(rl && gk + 0 < kend ? t.v[i].x : 0.f, rl && gk + 1 < kend ? t.v[i].y : 0.f, rl && gk + 2 < kend ? t.v[i].z : 0.f,
-                           rl && gk + 3 < kend ? t.v[i].w : 0.f);
-    } else {
-      const int k = q / (C::ROWS / 4), c = r0 + (q % (C::ROWS / 4)) * 4;
-      const bool kl = k0 + k < kend;
-      t.v[i] = make_float4(kl && c + 0 < R ? t.v[i].x : 0.f, kl && c + 1 < R ? t.v[i].y : 0.f, kl && c + 2 < R ? t.v[i].z : 0.f,
-                           kl && c + 3 < R ? t.v[i].w : 0.f);
-    }
-  }
-}
+using Regs = StageRegs<NV>;
 
 // the exact three-way split of four consecutive elements -> one 8-byte write per plane
 template <class C>
 __device__ __forceinline__ void x3_store(const Regs<C::NV>& t, __bf16* __restrict__ s, int kcontig) {
-  const int tid = threadIdx.x;
 #pragma unroll
   for (int i = 0; i < C::NV; ++i) {
-    const int q = tid + i * C::NT;
     const float x[4] = {t.v[i].x, t.v[i].y, t.v[i].z, t.v[i].w};
     bf16x4 p1, p2, p3;
 #pragma unroll
@@ -152,39 +76,18 @@ __device__ __forceinline__ void x3_store(const Regs<C::NV>& t, __bf16* __restric
     }
     int o;
     if (kcontig) {
-      const int r = q / (X3_BK / 4), k4 = (q % (X3_BK / 4)) * 4;
+      int r, k4;
+      C::slot_rk(i, r, k4);
       o = r * C::PITCH + k4;
     } else {  // natural [k][row] image
-      const int k = q / (C::ROWS / 4), r4 = (q % (C::ROWS / 4)) * 4;
+      int k, r4;
+      C::slot_kr(i, k, r4);
       o = k * C::RP + r4;
     }
     *reinterpret_cast<bf16x4*>(s + o) = p1;
     *reinterpret_cast<bf16x4*>(s + C::PLANE + o) = p2;
     *reinterpret_cast<bf16x4*>(s + 2 * C::PLANE + o) = p3;
   }
-}
-
-// MFMA operand (8 consecutive k of row `rowbase + lane % 32`, k half lane / 32) of k step ks from one plane (see gemm_bf16.hip: bf_fetch)
-template <class C>
-__device__ __forceinline__ bf16x8 x3_fetch(const __bf16* __restrict__ s, int kcontig, int rowbase, int ks, int lane) {
-  if (kcontig) return *reinterpret_cast<const bf16x8*>(s + (rowbase + (lane & 31)) * C::PITCH + ks * 16 + 8 * (lane >> 5));
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-  const int k0 = ks * 16 + 8 * (g >> 1);
-  const __bf16* a0 = s + (k0 + q) * C::RP + rowbase + 16 * (g & 1) + 4 * p;
-  typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(a0 + 4 * C::RP));
-  union { s16x4 h[2]; bf16x8 v; } u;
-  u.h[0] = lo;
-  u.h[1] = hi;
-  return u.v;
-}
-
-__device__ __forceinline__ float x3_act_mask(float h, int act, bool keep, float scale) {
-  if (!keep) return 0.f;
-  if (act == HMP_ACT_RELU) return h > 0.f ? scale : 0.f;
-  if (act == HMP_ACT_ELU) return h > 0.f ? scale : (h + scale);
-  return scale;
 }
 
 // The K loop of one output tile.  AV / BV (the loaders' vector widths) are TEMPLATE arguments: a run-time `if (vec == 4) .. else ..`
@@ -206,12 +109,12 @@ __device__ __forceinline__ void x3_loop(const GemmProblem& P, int a_kc, int b_kc
   Regs<SA::NV> ra0, ra1;
   Regs<SB::NV> rb0, rb1;
   auto load = [&](Regs<SA::NV>& ra, Regs<SB::NV>& rb, int k0) {
-    x3_load<SA, AV>(ra, P.A, P.lda, a_kc, m0, P.M, k0, kend);
-    x3_load<SB, BV>(rb, P.B, P.ldb, b_kc, n0, P.n_real, k0, kend);
+    tile_load_fast<SA, AV, true>(ra, P.A, P.lda, a_kc, m0, P.M, k0, kend);
+    tile_load_fast<SB, BV, true>(rb, P.B, P.ldb, b_kc, n0, P.n_real, k0, kend);
   };
   auto stage = [&](Regs<SA::NV>& ra, Regs<SB::NV>& rb, int kt) {
-    x3_mask<SA>(ra, a_kc, m0, P.M, kt, kend);
-    x3_mask<SB>(rb, b_kc, n0, P.n_real, kt, kend);
+    tile_mask<SA, true>(ra, a_kc, m0, P.M, kt, kend);
+    tile_mask<SB, true>(rb, b_kc, n0, P.n_real, kt, kend);
     x3_store<SA>(ra, As, a_kc);
     x3_store<SB>(rb, Bs, b_kc);
     __syncthreads();
@@ -223,12 +126,12 @@ __device__ __forceinline__ void x3_loop(const GemmProblem& P, int a_kc, int b_kc
 #pragma unroll
       for (int p = 0; p < 3; ++p)
 #pragma unroll
-        for (int i = 0; i < MI; ++i) av[p][i] = x3_fetch<SA>(As + p * SA::PLANE, a_kc, wm * (MI * 32) + i * 32, ks, lane);
+        for (int i = 0; i < MI; ++i) av[p][i] = mfma_fetch_bf16<SA::PITCH, SA::RP>(As + p * SA::PLANE, a_kc, wm * (MI * 32) + i * 32, ks, lane);
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         bf16x8 bv[3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) bv[p] = x3_fetch<SB>(Bs + p * SB::PLANE, b_kc, wn * (NI * 32) + j * 32, ks, lane);
+        for (int p = 0; p < 3; ++p) bv[p] = mfma_fetch_bf16<SB::PITCH, SB::RP>(Bs + p * SB::PLANE, b_kc, wn * (NI * 32) + j * 32, ks, lane);
         // smallest terms first: (3,1) (1,3) (2,2) (2,1) (1,2) (1,1)
         constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
@@ -266,17 +169,8 @@ __global__ __launch_bounds__(C::NT, C::PER_CU) void gemm_x3_kernel(const GemmBat
   extern __shared__ __attribute__((aligned(16))) unsigned char x3_lds[];
   __bf16* As = reinterpret_cast<__bf16*>(x3_lds);
   __bf16* Bs = As + 3 * C::SA::PLANE;
-  int pi = 0;
-  while (pi + 1 < gb.n && (int)blockIdx.x >= gb.p[pi + 1].tile_start) ++pi;
-  const GemmProblem& P = gb.p[pi];
-  const int local = blockIdx.x - P.tile_start;
-  // XCD-aware order as in gemm.hip: K chunk fastest; row tiles grouped by 8 so that the column tiles of a row tile share an L2
-  const int z = local % P.ksplit, t = local / P.ksplit;
-  const int grp = t / (8 * P.tiles_n), within = t % (8 * P.tiles_n);
-  const int rows_in_grp = min(8, P.tiles_m - grp * 8);
-  const int m0 = (grp * 8 + within % rows_in_grp) * C::RM, n0 = (within / rows_in_grp) * C::RN;
-  const int kbeg = z * P.kchunk;
-  const int kend = min(P.K, kbeg + P.kchunk);
+  int z, m0, n0, kbeg, kend;
+  const GemmProblem& P = gb.p[gemm_tile_walk<C::RM, C::RN>(gb, z, m0, n0, kbeg, kend)];
   const int a_kc = FORM == 3 ? (P.trans_a ? 0 : 1) : (FORM == 2 ? 0 : 1);
   const int b_kc = FORM == 3 ? (P.trans_b ? 1 : 0) : (FORM == 0 ? 1 : 0);
   // block-uniform loader choice: 16-byte rows, 8-byte rows, or element by element; a row-contiguous operand's vectors run ALONG its
@@ -291,6 +185,8 @@ __global__ __launch_bounds__(C::NT, C::PER_CU) void gemm_x3_kernel(const GemmBat
   const int wm = w % C::WMW, wn = w / C::WMW;
   const bool ones_here = ONES && P.aug_ones && n0 == 0 && wn == 0;  // wave-uniform
 
+  // gemm_acc_init's body, kept here: shared, it added 4-8 bytes per lane of scratch to seven of this kernel's twelve instantiations
+  // in every form tried ("Shared GEMM tile code").  A change there belongs here too.
   f32x16 acc[MI][NI];
 #pragma unroll
   for (int i = 0; i < MI; ++i)
@@ -329,50 +225,7 @@ __global__ __launch_bounds__(C::NT, C::PER_CU) void gemm_x3_kernel(const GemmBat
   }
 #undef X3_LOOP
 
-  // D layout of a 32x32 tile: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); epilogue as gemm.hip (no branch
-  // between memory operations)
-  float* Cp = P.C + (int64_t)z * P.slab_stride;
-  const int Mrows = P.M, Ncols = P.N, ldc = P.ldc, ldh = P.ldh, act = P.act;
-  const bool amask = P.epi == EPI_ACTMASK;
-  const bool dropon = P.drop_on != 0;
-  const float dscale = dropon ? P.drop.scale : 1.f;
-  const float* Hp = P.H;
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int col = n0 + wn * (NI * 32) + j * 32 + (lane & 31);
-      const int rbase = m0 + wm * (MI * 32) + i * 32 + 4 * (lane >> 5);
-      const bool cok = col < Ncols && !(ONES && P.aug_ones && col >= P.n_real);  // (the ones column comes from acc1)
-      const int colc = col < Ncols ? col : 0;
-      float hv[16];
-      if (amask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = rbase + (r & 3) + 8 * (r >> 2);
-          hv[r] = Hp[(int64_t)(row < Mrows ? row : Mrows - 1) * ldh + colc];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = rbase + (r & 3) + 8 * (r >> 2);
-        float v = acc[i][j][r];
-        if (amask) {
-          const bool keep = !dropon || (__float_as_uint(hv[r]) != 0x80000000u);  // dropped elements were stored as -0.0f
-          v *= x3_act_mask(hv[r], act, keep, dscale);
-        }
-        if (cok && row < Mrows) Cp[(int64_t)row * ldc + col] = v;
-      }
-    }
-  if (ONES && ones_here && (lane & 31) == 0) {  // column 0 of the ones product -> C[:, n_real]
-#pragma unroll
-    for (int i = 0; i < (ONES ? MI : 1); ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * (MI * 32) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < P.M) Cp[(int64_t)row * P.ldc + P.n_real] = acc1[i][r];
-      }
-  }
+  gemm_epilogue<MI, NI, false, ONES, true>(P, z, acc, acc1, ones_here, m0 + wm * (MI * 32), n0 + wn * (NI * 32), lane);
 }
 
 template <class C>

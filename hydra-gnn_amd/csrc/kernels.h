@@ -47,8 +47,6 @@ struct GemmProblem {
   int ldadd;
 };
 
-// sum over the CSC entries of `row` of g_rows[g_col[k], col] * g_deg[g_col[k]] (row < 0: nothing) -- the tiled kernels' form of
-// GemmProblem::g_rowptr (one element at a time: the regime that uses it in earnest runs gemm_bf16_dx_kernel)
 constexpr int GEMM_MAX_PROB = 8;
 constexpr int GEMM_TALL_SLABS = 192;  // split-K slabs the tall weight-gradient kernel may ask for (== net.hip: MAX_SLABS, the slab buffer's size)
 struct GemmBatch {

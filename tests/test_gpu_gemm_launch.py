@@ -229,6 +229,18 @@ def plan_bf16_128(probs, max_slabs):
     return out
 
 
+def plan_x3(probs, RM, RN, per_cu, max_slabs):
+    """gemm_x3.hip x3_launch_cfg: one workgroup per CU and resident slot, K stages of 32, the ones column folded"""
+    tiles = [cdiv(p.M, RM) * cdiv((p.n_real if p.n_real > 0 else 1) if p.aug else p.N, RN) for p in probs]
+    all_tiles = sum(tiles)
+    out = []
+    for p, t in zip(probs, tiles):
+        ks = max(1, min(256 * per_cu // all_tiles, cdiv(p.K, 32), max_slabs)) if t > 0 else 1
+        kchunk = max(32, cdiv(cdiv(p.K, ks), 32) * 32)
+        out.append(cdiv(p.K, kchunk) if p.K > 0 else 1)
+    return out
+
+
 def plan_direct(p, max_slabs):
     """gemm_direct.hip: None when the kernel declines"""
     tiles = cdiv(p.M, 32) * cdiv(p.N, 32)
@@ -292,13 +304,34 @@ def test_fp32_ragged_k_and_empty_problems(monkeypatch):
 @pytest.mark.parametrize("want_split", [True, False])
 def test_fp32_mixed_forms_in_one_launch(want_split, monkeypatch):
     """launch_form 3 (the run-time layout variant): NT, NN, TN, TT problems in one table, ones columns on the NN / TN problems, an
-    empty problem in the middle (the tile_start search walks past it)"""
+    empty problem in the middle (the tile_start search walks past it).  The same table on the bf16 route (128 x 128 tiles), and a
+    mixed NT / NN / TN table of just over 10^9 multiply-adds on the x3 kernel (square and narrow tile; its ones column belongs to
+    the TN problem only): the three kernels share the tile walk and the epilogue."""
     monkeypatch.setenv("HMP_GEMM_X3", "0")
+    monkeypatch.delenv("HMP_GEMM_X3_TILE", raising=False)
     probs = [Prob(70, 50, 300, 0, 1, seed=11), Prob(40, 32, 200, 0, 0, aug=1, seed=12), Prob(0, 20, 100, 0, 0, seed=13),
              Prob(90, 63, 333, 1, 0, aug=1, seed=14, ldc_pad=2), Prob(33, 65, 129, 1, 1, seed=15)]
     ks, _ = run_check(probs, 0, want_split, 64, "mixed")
     if want_split:
         assert ks == plan_tiled(probs, 32, 32, 128, 64)
+    bprobs = [Prob(70, 50, 300, 0, 1, seed=11, bf16_route=True), Prob(40, 32, 200, 0, 0, aug=1, seed=12, bf16_route=True),
+              Prob(0, 20, 100, 0, 0, seed=13, bf16_route=True), Prob(90, 63, 333, 1, 0, aug=1, seed=14, ldc_pad=2, bf16_route=True),
+              Prob(33, 65, 129, 1, 1, seed=15, bf16_route=True)]
+    ks, _ = run_check(bprobs, 1, want_split, 64, "mixed bf16")
+    if want_split:
+        assert ks == plan_bf16_128(bprobs, 64)
+    xprobs = [Prob(2047, 299, 602, 0, 1, seed=16), Prob(2048, 300, 600, 0, 0, seed=17, ldc_pad=1), Prob(2050, 301, 610, 1, 0, aug=1, seed=18)]
+    assert sum(p.M * p.N * p.K for p in xprobs) >= 1e9
+    monkeypatch.setenv("HMP_GEMM_X3", "0")
+    _, outs0 = run_check(xprobs, 0, want_split, 64, "mixed X3=0")
+    monkeypatch.delenv("HMP_GEMM_X3")
+    for tile in ("128",) if want_split else ("128", "64"):  # (a split-K launch takes the square tile under either setting)
+        monkeypatch.setenv("HMP_GEMM_X3_TILE", tile)
+        ks, outs = run_check(xprobs, 0, want_split, 64, f"mixed x3 tile {tile}")
+        if want_split:
+            assert ks == plan_x3(xprobs, 128, 128, 2, 64)
+        for o, o0 in zip(outs, outs0):
+            assert not torch.equal(o, o0), "the x3 kernel did not run"
 
 
 # ---- the virtual ones column ---------------------------------------------------------------------------------------------------
@@ -499,16 +532,31 @@ def test_actmask_epilogue_and_cadd(kernel, monkeypatch):
         assert ks == plan_tiled([p], 128, 128, 32, 64) and ks0 == plan_tiled([p], 64, 64, 32, 64) and ks != ks0
 
 
-@pytest.mark.parametrize("cls", ["32x32_bk128", "64x64", "128x128"])
+@pytest.mark.parametrize("cls", ["32x32_bk128", "64x64", "128x128", "bf16_128", "x3_128"])
 def test_cadd_with_split_k(cls, monkeypatch):
-    """Cadd is added once: by the first K group of the block (32x32: four waves split the stage) and the first slab only"""
-    monkeypatch.setenv("HMP_GEMM_X3", "0")
-    (M, N, K), _, plan = CLASSES[cls]
+    """Cadd is added once: by the first K group of the block (32x32: four waves split the stage) and the first slab only.  Every
+    tiled kernel whose launcher splits an NN problem: the three fp32 classes, the bf16 128 x 128 tile and the square x3 tile.  (The
+    bf16 256 x 256 tile splits TN problems only and the narrow x3 tile is chosen for plain launches only: neither ever splits an
+    NN problem.)"""
+    for k in ("HMP_GEMM_X3_TILE", "HMP_GEMM_BIG"):
+        monkeypatch.delenv(k, raising=False)
+    route = 1 if cls == "bf16_128" else 0
+    if cls == "x3_128":
+        monkeypatch.delenv("HMP_GEMM_X3", raising=False)
+    else:
+        monkeypatch.setenv("HMP_GEMM_X3", "0")
+    (M, N, K), _, plan = CLASSES["128x128" if cls in ("bf16_128", "x3_128") else cls]
     for want_split in (True, False):
-        p = Prob(M, N, K, 0, 0, seed=71, cadd=True, slabs=64)
-        ks, _ = run_check([p], 0, want_split, 64, f"cadd {cls}")
+        p = Prob(M, N, K, 0, 0, seed=71, cadd=True, slabs=64, bf16_route=route == 1)
+        ks, outs = run_check([p], route, want_split, 64, f"cadd {cls}")
         if want_split:
-            assert ks == plan_tiled([p], *plan, 64) and ks[0] > 1
+            want = plan_bf16_128([p], 64) if cls == "bf16_128" else plan_x3([p], 128, 128, 2, 64) if cls == "x3_128" else plan_tiled([p], *plan, 64)
+            assert ks == want and ks[0] > 1
+        if cls == "x3_128":  # the kernel really ran: the fp32-MFMA kernel's result differs bitwise
+            monkeypatch.setenv("HMP_GEMM_X3", "0")
+            _, outs0 = run_check([p], 0, want_split, 64, "cadd x3 other")
+            monkeypatch.delenv("HMP_GEMM_X3")
+            assert not torch.equal(outs[0], outs0[0])
 
 
 # ---- the register-direct TN kernel ---------------------------------------------------------------------------------------------
