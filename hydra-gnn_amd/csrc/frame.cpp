@@ -7,7 +7,9 @@
 //   * add_object_connectivity      :191-225 with _is_on / _is_under / _is_near  (obj_edge.h: the function body of the device kernel)
 //   * generate_htree + virtual nodes + typed extraction   construct.py:241-483 (the builder of htree.cpp, called directly)
 // and lays out what the device stage (frame.hip) needs: ONE staging block [item table | 16-byte aligned sections] and the offsets
-// of every output tensor in ONE arena (include/hydra_mp.h section 14).
+// of every output tensor in ONE arena (include/hydra_mp.h section 14).  hmp_frame_build_homogeneous lays the same bookkeeping out as
+// the homogeneous Data instead (convert_graph's closing to_homogeneous(): data.heterogeneous_data_to_homogeneous /
+// heterogeneous_htree_to_homogeneous are its parity oracle): one tensor per attribute, one item per node-type / edge-type segment.
 //
 // The object-object predicates run HERE and not on the device on purpose: a frame has 10^1..10^3 objects and only pairs inside a
 // room are tested (microseconds of float64 work), while the H-tree builder needs the edge list on the host -- computing it on the
@@ -59,19 +61,32 @@ struct Layout {
   }
   template <class T>
   int32_t section(const std::vector<T>& v) { return section(v.data(), v.size() * sizeof(T)); }
+  // a 16-byte aligned range of the arena: one output tensor
+  int64_t alloc(int64_t bytes) {
+    const int64_t off = F.arena_bytes;
+    F.arena_bytes = align16(off + bytes);
+    return off;
+  }
   // `units` = work items of the launch (elements, or rows of a wide feature item), `per_block` of them to a workgroup
+  void item_at(int kind, int tensor, int64_t rows, int64_t width, int64_t dst, int s0, int s1, int s2, int s3, int p0, int p1, int64_t units,
+               int per_block) {
+    const int32_t w[HMP_FRAME_ITEM_WORDS] = {kind, tensor, (int32_t)rows, (int32_t)width, (int32_t)dst, s0, s1, s2, s3, p0, p1, F.n_blocks};
+    F.items.insert(F.items.end(), w, w + HMP_FRAME_ITEM_WORDS);
+    F.n_blocks += (int32_t)((units + per_block - 1) / per_block);
+  }
+  // an item that is a whole tensor
   void item(int kind, int tensor, int64_t rows, int64_t width, int64_t out_bytes, int s0, int s1, int s2, int s3, int p0, int p1,
             int64_t units, int per_block) {
-    const int32_t w[HMP_FRAME_ITEM_WORDS] = {kind, tensor, (int32_t)rows, (int32_t)width, (int32_t)F.arena_bytes, s0, s1, s2, s3, p0, p1,
-                                             F.n_blocks};
-    F.items.insert(F.items.end(), w, w + HMP_FRAME_ITEM_WORDS);
-    F.arena_bytes = align16(F.arena_bytes + out_bytes);
-    F.n_blocks += (int32_t)((units + per_block - 1) / per_block);
+    item_at(kind, tensor, rows, width, alloc(out_bytes), s0, s1, s2, s3, p0, p1, units, per_block);
+  }
+  // feature rows of `width` floats at `dst`; the type's own npos + 3 + sem columns, zeros behind them
+  void feat_at(int tensor, int64_t rows, int64_t width, int64_t dst, int s_pos, int s_size, int s_label, int s_idx, int npos, int sem) {
+    if (width >= 32) item_at(HMP_FK_FEAT, tensor, rows, width, dst, s_pos, s_size, s_label, s_idx, npos, sem, rows, 4);
+    else item_at(HMP_FK_FEAT, tensor, rows, width, dst, s_pos, s_size, s_label, s_idx, npos, sem, rows * width, 256);
   }
   void feat(int tensor, int64_t rows, int s_pos, int s_size, int s_label, int s_idx, int npos, int sem) {
     const int64_t width = npos + 3 + sem;
-    if (width >= 32) item(HMP_FK_FEAT, tensor, rows, width, rows * width * 4, s_pos, s_size, s_label, s_idx, npos, sem, rows, 4);
-    else item(HMP_FK_FEAT, tensor, rows, width, rows * width * 4, s_pos, s_size, s_label, s_idx, npos, sem, rows * width, 256);
+    feat_at(tensor, rows, width, alloc(rows * width * 4), s_pos, s_size, s_label, s_idx, npos, sem);
   }
   void pos(int tensor, int64_t rows, int s_pos, int s_idx) {
     item(HMP_FK_POS, tensor, rows, 3, rows * 12, s_pos, -1, -1, s_idx, 0, 0, rows * 3, 256);
@@ -89,6 +104,9 @@ struct Layout {
   }
   // clique rows: members of clique q = the sources of the init edges whose destination is q, in ascending init-edge order
   void clique(int tensor, int64_t rows, int64_t width, const std::vector<int32_t>& init, int s_room_pos) {
+    clique_at(tensor, rows, width, alloc(rows * width * 4), init, s_room_pos);
+  }
+  void clique_at(int tensor, int64_t rows, int64_t width, int64_t dst, const std::vector<int32_t>& init, int s_room_pos) {
     const size_t e = init.size() / 2;
     std::vector<int32_t> ptr(rows + 1, 0), mem(e);
     for (size_t k = 0; k < e; ++k) ++ptr[init[e + k] + 1];
@@ -96,7 +114,22 @@ struct Layout {
     std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
     for (size_t k = 0; k < e; ++k) mem[fill[init[e + k]]++] = init[k];
     const int s_ptr = section(ptr), s_mem = section(mem);
-    item(HMP_FK_CLIQUE, tensor, rows, width, rows * width * 4, s_ptr, s_mem, s_room_pos, -1, 0, 0, rows * width, 256);
+    item_at(HMP_FK_CLIQUE, tensor, rows, width, dst, s_ptr, s_mem, s_room_pos, -1, 0, 0, rows * width, 256);
+  }
+
+  // ---- segments of a homogeneous tensor: one item per node type (rows) or edge type (columns), at its place inside the tensor
+  // columns [col0, col0 + eo) of an int64 [2][pitch] tensor at `base`; endpoints shifted by the row offsets of their node types
+  void edge_seg(int tensor, int64_t base, int64_t pitch, int64_t col0, int s_list, int variant, int64_t e, int64_t shift_src, int64_t shift_dst) {
+    const int64_t eo = variant == EV_BOTH ? 2 * e : e;
+    item_at(HMP_FK_EDGE_SEG, tensor, 2, eo, base + col0 * 8, s_list, (int)pitch, (int)shift_src, (int)shift_dst, variant, (int)e, 2 * eo, 256);
+  }
+  void eattr_seg(int tensor, int64_t base, int64_t col0, int s_list, int variant, int64_t e, int s_pos_src, int s_pos_dst) {
+    const int64_t eo = variant == EV_BOTH ? 2 * e : e;
+    item_at(HMP_FK_EATTR, tensor, eo, 3, base + col0 * 12, s_list, s_pos_src, s_pos_dst, -1, variant, (int)e, eo * 3, 256);
+  }
+  // `rows` elements of `elem` bytes (8: int64, 1: a bool mask), all `value`, from element `row0` of the tensor at `base`
+  void fill_seg(int tensor, int64_t base, int64_t row0, int64_t rows, int value, int elem) {
+    item_at(HMP_FK_CONST, tensor, rows, 1, base + row0 * elem, -1, -1, -1, -1, value, elem, rows, 256);
   }
 };
 
@@ -107,10 +140,11 @@ int fail(const char* m) {
 
 }  // namespace
 
-extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
-                               const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
-                               double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
-                               int32_t clique_dim, hmp_frame** out) {
+// both entries: the bookkeeping is the same, `homogeneous` picks the layout
+static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min, const double* bb_max,
+                       const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near, double max_near, double max_on,
+                       int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels, int32_t clique_dim, bool homogeneous,
+                       hmp_frame** out) {
   if (!out || n < 0 || m < 0 || sem_dim < 0 || n_labels < 0 || clique_dim < 0) return fail("bad argument");
   if (n > 0 && (!ids || !layer || !pos || !bb_min || !bb_max || !label)) return fail("null node array");
   if (m > 0 && !edges) return fail("null edge array");
@@ -269,7 +303,88 @@ extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* la
   const int s_opos = L.section(opos), s_osize = L.section(osize), s_rpos = L.section(rpos), s_rsize = L.section(rsize);
   const int s_olabel = L.section(olabel), s_rlabel = L.section(rlabel);
   const int s_osem = sem_dim > 0 ? s_olabel : -1;
-  if (!htree) {
+  if (htree) {  // the topology, for either layout
+    std::vector<int32_t> ro(F->obj_room);
+    for (int k = 0; k < n_obj; ++k) ro.push_back(k);
+    const int rc = hmp::htree_build_i32(n_obj, n_rooms, e_oo ? F->oo.data() : nullptr, e_oo, e_rr ? F->rr.data() : nullptr, e_rr, ro.data(),
+                                        n_obj, &F->tree);
+    if (rc != HMP_OK) { delete F; return rc; }
+  }
+  if (homogeneous) {
+    // What data.heterogeneous_data_to_homogeneous / heterogeneous_htree_to_homogeneous make of the typed frame: node types
+    // concatenated in store order into one x of the widest type's width, every edge type's columns shifted by the row offsets of
+    // its endpoint types.  Every count is known here, so each tensor is allocated once and written by one item per segment.
+    struct EdgeSeg { int s_list, variant; int64_t e; int src, dst, s_pos_src, s_pos_dst; };
+    const int wo = npos + 3 + sem_dim, wr = npos + 3, H0 = HMP_FT_HOMOG;
+    std::vector<int64_t> n_rows;                // rows per node type
+    std::vector<EdgeSeg> main_e, init_e, pool_e;  // edge_index (with edge_type), init_edge_index, pool_edge_index
+    int64_t W = std::max(wo, wr);
+    int object_type = -1, room_type = 1;  // the types the masks select
+    if (!htree) {
+      const int s_oo = L.section(F->oo), s_rr = L.section(F->rr), s_oroom = L.section(F->obj_room);
+      n_rows = {n_obj, n_rooms};
+      main_e = {{s_oo, EV_BOTH, e_oo, 0, 0, s_opos, s_opos}, {s_rr, EV_BOTH, e_rr, 1, 1, s_rpos, s_rpos},
+                {s_oroom, EV_VEC_ARANGE, n_obj, 1, 0, s_rpos, s_opos}, {s_oroom, EV_ARANGE_VEC, n_obj, 0, 1, s_opos, s_rpos}};
+    } else {
+      const hmp_htree& T = *F->tree;
+      n_rows = {T.counts[0], T.counts[1], T.counts[2], T.counts[3], n_obj, n_rooms};
+      W = std::max<int64_t>(W, clique_dim);  // clique rows are clique_dim wide, or as wide as the objects' / rooms' (clique_dim 0)
+      object_type = 4, room_type = 5;
+      // (source type, destination type) of the 10 HTREE_EDGE_TYPES, the 3 init and the 2 pool edge types
+      static const int ends[15][2] = {{0, 2}, {2, 0}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 3}, {3, 2}, {2, 2}, {3, 3},
+                                      {4, 2}, {5, 2}, {5, 3}, {0, 4}, {1, 5}};
+      for (int k = 0; k < 10; ++k) main_e.push_back({L.section(T.edges[k]), EV_AS_GIVEN, (int64_t)T.edges[k].size() / 2, ends[k][0], ends[k][1], -1, -1});
+      for (int k = 0; k < 3; ++k) init_e.push_back({L.section(T.init[k]), EV_AS_GIVEN, (int64_t)T.init[k].size() / 2, ends[10 + k][0], ends[10 + k][1], -1, -1});
+    }
+    const int n_types = (int)n_rows.size();
+    std::vector<int64_t> row0(n_types + 1, 0);
+    for (int t = 0; t < n_types; ++t) row0[t + 1] = row0[t] + n_rows[t];
+    const int64_t N = row0[n_types];
+
+    const int64_t x = L.alloc(N * W * 4);
+    auto xrow = [&](int t) { return x + row0[t] * W * 4; };
+    if (!htree) {
+      L.feat_at(H0 + 0, n_obj, W, xrow(0), s_opos, s_osize, s_osem, -1, npos, sem_dim);
+      L.feat_at(H0 + 0, n_rooms, W, xrow(1), s_rpos, s_rsize, -1, -1, npos, 0);
+    } else {
+      const hmp_htree& T = *F->tree;
+      const int s_oorig = L.section(T.object_orig), s_rorig = L.section(T.room_orig);
+      L.feat_at(H0 + 0, n_rows[0], W, xrow(0), s_opos, s_osize, s_osem, s_oorig, npos, sem_dim);
+      L.feat_at(H0 + 0, n_rows[1], W, xrow(1), s_rpos, s_rsize, -1, s_rorig, npos, 0);
+      L.clique_at(H0 + 0, n_rows[2], W, xrow(2), T.init[1], s_rpos);  // [mean | zeros] whatever clique_dim is: zeros up to W
+      L.clique_at(H0 + 0, n_rows[3], W, xrow(3), T.init[2], s_rpos);
+      L.feat_at(H0 + 0, n_obj, W, xrow(4), s_opos, s_osize, s_osem, -1, npos, sem_dim);
+      L.feat_at(H0 + 0, n_rooms, W, xrow(5), s_rpos, s_rsize, -1, -1, npos, 0);
+      pool_e = {{s_oorig, EV_ARANGE_VEC, n_rows[0], 0, 4, -1, -1}, {s_rorig, EV_ARANGE_VEC, n_rows[1], 1, 5, -1, -1}};
+    }
+    auto columns = [](const EdgeSeg& g) { return g.variant == EV_BOTH ? 2 * g.e : g.e; };
+    auto edge_tensor = [&](int tensor, const std::vector<EdgeSeg>& segs) {
+      int64_t E = 0, col = 0;
+      for (const EdgeSeg& g : segs) E += columns(g);
+      const int64_t base = L.alloc(2 * E * 8);
+      for (const EdgeSeg& g : segs) { L.edge_seg(tensor, base, E, col, g.s_list, g.variant, g.e, row0[g.src], row0[g.dst]); col += columns(g); }
+      return E;
+    };
+    const int64_t E = edge_tensor(H0 + 1, main_e);
+    const int64_t node_type = L.alloc(N * 8);
+    for (int t = 0; t < n_types; ++t) L.fill_seg(H0 + 2, node_type, row0[t], n_rows[t], t, 8);
+    const int64_t edge_type = L.alloc(E * 8);
+    int64_t col = 0;
+    for (size_t k = 0; k < main_e.size(); ++k) { L.fill_seg(H0 + 3, edge_type, col, columns(main_e[k]), (int)k, 8); col += columns(main_e[k]); }
+    const int64_t room_mask = L.alloc(N);  // one byte per node; alloc keeps the next tensor 16-byte aligned
+    for (int t = 0; t < n_types; ++t) L.fill_seg(H0 + 4, room_mask, row0[t], n_rows[t], t == room_type, 1);
+    if (relative_pos) {
+      const int64_t edge_attr = L.alloc(E * 12);
+      col = 0;
+      for (const EdgeSeg& g : main_e) { L.eattr_seg(H0 + 5, edge_attr, col, g.s_list, g.variant, g.e, g.s_pos_src, g.s_pos_dst); col += columns(g); }
+    }
+    if (htree) {
+      const int64_t object_mask = L.alloc(N);
+      for (int t = 0; t < n_types; ++t) L.fill_seg(H0 + 6, object_mask, row0[t], n_rows[t], t == object_type, 1);
+      edge_tensor(H0 + 7, init_e);
+      edge_tensor(H0 + 8, pool_e);
+    }
+  } else if (!htree) {
     const int s_oid = L.section(oid), s_rid = L.section(rid);
     const int s_oo = L.section(F->oo), s_rr = L.section(F->rr), s_oroom = L.section(F->obj_room);
     L.feat(0, n_obj, s_opos, s_osize, s_osem, -1, npos, sem_dim);
@@ -291,11 +406,6 @@ extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* la
       L.eattr(15, s_oroom, EV_ARANGE_VEC, n_obj, s_opos, s_rpos);
     }
   } else {
-    std::vector<int32_t> ro(F->obj_room);
-    for (int k = 0; k < n_obj; ++k) ro.push_back(k);
-    const int rc = hmp::htree_build_i32(n_obj, n_rooms, e_oo ? F->oo.data() : nullptr, e_oo, e_rr ? F->rr.data() : nullptr, e_rr, ro.data(),
-                                        n_obj, &F->tree);
-    if (rc != HMP_OK) { delete F; return rc; }
     const hmp_htree& T = *F->tree;
     const int s_oorig = L.section(T.object_orig), s_rorig = L.section(T.room_orig);
     const int T0 = HMP_FT_HTREE;
@@ -323,13 +433,31 @@ extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* la
   if (n_items > HMP_FRAME_MAX_ITEMS) return bail("internal: more items than the launch's prefix table holds");
   if (F->arena_bytes > INT32_MAX || table_bytes + (int64_t)F->sections.size() > INT32_MAX)
     return bail("frame too large: the arena or the staging block exceeds 2 GiB");
-  for (int64_t i = 0; i < n_items; ++i)
-    for (int w = HMP_FI_S0; w <= HMP_FI_S3; ++w) {
+  for (int64_t i = 0; i < n_items; ++i) {
+    const bool seg = F->items[i * HMP_FRAME_ITEM_WORDS + HMP_FI_KIND] == HMP_FK_EDGE_SEG;  // S1..S3 are numbers, not sections
+    for (int w = HMP_FI_S0; w <= (seg ? HMP_FI_S0 : HMP_FI_S3); ++w) {
       int32_t& s = F->items[i * HMP_FRAME_ITEM_WORDS + w];
       if (s >= 0) s += (int32_t)table_bytes;
     }
+  }
   *out = F;
   return HMP_OK;
+}
+
+extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                               const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
+                               double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
+                               int32_t clique_dim, hmp_frame** out) {
+  return frame_build(n, ids, layer, pos, bb_min, bb_max, label, m, edges, threshold_near, max_near, max_on, htree, relative_pos, sem_dim,
+                     n_labels, clique_dim, false, out);
+}
+
+extern "C" int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                                           const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges,
+                                           double threshold_near, double max_near, double max_on, int32_t htree, int32_t relative_pos,
+                                           int32_t sem_dim, int32_t n_labels, int32_t clique_dim, hmp_frame** out) {
+  return frame_build(n, ids, layer, pos, bb_min, bb_max, label, m, edges, threshold_near, max_near, max_on, htree, relative_pos, sem_dim,
+                     n_labels, clique_dim, true, out);
 }
 
 extern "C" int hmp_frame_sizes(const hmp_frame* f, int64_t* sizes) {

@@ -7,10 +7,17 @@
 // need no ordering, no atomics and no flags.  Workgroups map to items through the prefix word of the item table (HMP_FI_BLOCK0),
 // as in collate_batch_kernel; a frame is a few tens of KB, so the launch is latency bound and what counts is that it is one.
 //
+// A homogeneous frame (hmp_frame_build_homogeneous) is a re-addressing of the same elements: a tensor is written by one item per
+// segment (a node type's rows of x, an edge type's columns of edge_index), each at its place inside the tensor, so the rule above
+// holds unchanged.  FEAT and CLIQUE rows are `width` floats whatever the type's own width is (zeros behind it), EATTR segments are
+// plain sub-ranges, EDGE_SEG and CONST are the two kinds it adds.
+//
 // Item kinds (words S0..S3 are byte offsets of sections in the staging block, -1: none):
-//   FEAT    x = [pos (P0 = 3 or 0 columns) | size | table[label] (P1 columns)]   S0 pos f64, S1 size f64, S2 label i32, S3 row index
+//   FEAT    x = [pos (P0 = 3 or 0 columns) | size | table[label] (P1 columns) | zeros up to width]
+//           S0 pos f64, S1 size f64, S2 label i32, S3 row index
 //           (float)double for the float64 part, the float32 table row as is.  Rows of 32 floats or more: one wavefront per row,
-//           8-byte lanes when the head and the row are even (306 floats = 1224 bytes: 8-byte aligned, not 16); else one thread per element
+//           8-byte lanes when the head, the table part and the row are even (306 floats = 1224 bytes: 8-byte aligned, not 16; a
+//           303-float row of a relative_pos frame is 4-byte aligned: one float per lane); else one thread per element
 //   POS     float32 [rows][3]                                                    S0 pos f64, S3 row index
 //   I64     int64 [rows]                                                         S0 source (P0 = 4: int32, 8: int64), S3 row index
 //   EDGE    int64 [2][width] from an int32 list of P1 entries, form P0           S0 list
@@ -18,6 +25,9 @@
 //           source type, S2 pos of the destination type
 //   CLIQUE  [mean float32 position of the member rooms | zeros]: summed in ascending init-edge order by one thread per (clique,
 //           coordinate), divided by the count                                    S0 ptr i32 [rows + 1], S1 members, S2 room pos f64
+//   EDGE_SEG  `width` columns of an int64 [2][S1] tensor, as EDGE: row 1 lies S1 elements (the tensor's pitch) behind row 0, the
+//           sources are shifted by S2 and the destinations by S3 (the row offsets of their node types)   S0 list; S1..S3 numbers
+//   CONST   `rows` elements of P1 bytes, every one P0: the int64 node_type / edge_type segments and the one-byte masks
 #include "common.h"
 
 namespace hmp {
@@ -66,7 +76,7 @@ __global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restric
     const double* size = reinterpret_cast<const double*>(sec(HMP_FI_S1));
     // the table is read only when the launch was given the table the frame was laid out for
     const int* label = p1 > 0 && p1 == sem_dim && table ? reinterpret_cast<const int*>(sec(HMP_FI_S2)) : nullptr;
-    const int head = p0 + 3;
+    const int head = p0 + 3, own = head + p1;  // columns [own, width) of a wider destination row are zeros
     float* o = reinterpret_cast<float*>(out);
     if (width >= 32) {
       const int row = lb * 4 + (threadIdx.x >> 6);
@@ -74,21 +84,22 @@ __global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restric
       const int r = idx ? idx[row] : row;
       const float* trow = label ? table + (int64_t)label[r] * sem_dim : nullptr;
       float* orow = o + (int64_t)row * width;
-      if (((width | head | sem_dim) & 1) == 0) {
+      // a table row is read (trow) only with P1 = sem_dim, and never past column own - head = sem_dim of it
+      if (((width | head | p1) & 1) == 0) {
         for (int u = lane; u < (width >> 1); u += 64) {
           const int c = 2 * u;
-          float2 v;
+          float2 v = make_float2(0.f, 0.f);
           if (c < head) v = make_float2(feat_head(pos, size, p0, r, c), feat_head(pos, size, p0, r, c + 1));
-          else v = trow ? reinterpret_cast<const float2*>(trow)[(c - head) >> 1] : make_float2(0.f, 0.f);
+          else if (trow && c < own) v = reinterpret_cast<const float2*>(trow)[(c - head) >> 1];
           reinterpret_cast<float2*>(orow)[u] = v;
         }
       } else {
-        for (int c = lane; c < width; c += 64) orow[c] = c < head ? feat_head(pos, size, p0, r, c) : (trow ? trow[c - head] : 0.f);
+        for (int c = lane; c < width; c += 64) orow[c] = c < head ? feat_head(pos, size, p0, r, c) : (trow && c < own ? trow[c - head] : 0.f);
       }
     } else if (e < (int64_t)rows * width) {
       const int row = (int)(e / width), c = (int)(e % width);
       const int r = idx ? idx[row] : row;
-      o[e] = c < head ? feat_head(pos, size, p0, r, c) : (label ? table[(int64_t)label[r] * sem_dim + (c - head)] : 0.f);
+      o[e] = c < head ? feat_head(pos, size, p0, r, c) : (label && c < own ? table[(int64_t)label[r] * sem_dim + (c - head)] : 0.f);
     }
   } else if (kind == HMP_FK_POS) {
     if (e < (int64_t)rows * 3) {
@@ -102,12 +113,16 @@ __global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restric
       const char* src = sec(HMP_FI_S0);
       reinterpret_cast<int64_t*>(out)[e] = p0 == 4 ? (int64_t)reinterpret_cast<const int*>(src)[r] : reinterpret_cast<const int64_t*>(src)[r];
     }
-  } else if (kind == HMP_FK_EDGE) {
+  } else if (kind == HMP_FK_EDGE || kind == HMP_FK_EDGE_SEG) {
     if (e < 2 * (int64_t)width) {
       const int row = e >= width ? 1 : 0, col = (int)(e - (int64_t)row * width);
       int s, d;
       edge_ends(reinterpret_cast<const int*>(sec(HMP_FI_S0)), p0, p1, col, s, d);
-      reinterpret_cast<int64_t*>(out)[e] = row ? d : s;
+      // a segment's row 1 lies one pitch of the whole tensor behind its row 0, and its ends count rows of the concatenated x
+      const bool seg = kind == HMP_FK_EDGE_SEG;
+      const int64_t pitch = seg ? I[HMP_FI_S1] : width;
+      const int shift = seg ? I[row ? HMP_FI_S3 : HMP_FI_S2] : 0;
+      reinterpret_cast<int64_t*>(out)[row * pitch + col] = (int64_t)(row ? d : s) + shift;
     }
   } else if (kind == HMP_FK_EATTR) {
     if (e < (int64_t)rows * 3) {
@@ -131,6 +146,11 @@ __global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restric
         v = v / (float)max(t - b, 1);
       }
       reinterpret_cast<float*>(out)[e] = v;
+    }
+  } else if (kind == HMP_FK_CONST) {
+    if (e < rows) {
+      if (p1 == 8) reinterpret_cast<int64_t*>(out)[e] = p0;
+      else reinterpret_cast<unsigned char*>(out)[e] = (unsigned char)p0;
     }
   }
 }

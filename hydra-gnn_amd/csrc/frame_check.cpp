@@ -1,5 +1,6 @@
 // Stand-alone driver of the frame pipeline's host stage for `make frame_check` (AddressSanitizer + UBSan, CPU only): reads flat
 // binary frame files and runs hmp_frame_build, hmp_frame_sizes, hmp_frame_host_arrays, hmp_frame_pack and hmp_frame_destroy on each.
+// `--homogeneous` before a file builds it (and every file after it) with hmp_frame_build_homogeneous instead.
 //
 // File (little endian, dsg.save_frame_file): "HMPF", int32 version = 1, int32 n, int32 htree, int32 relative_pos, int32 sem_dim,
 // int32 n_labels, int32 clique_dim, int64 m, float64 threshold_near, max_near, max_on, then ids uint64[n], layer int32[n],
@@ -19,7 +20,7 @@ bool read_vec(FILE* f, std::vector<T>& v, size_t count) {
   return count == 0 || fread(v.data(), sizeof(T), count, f) == count;
 }
 
-int run(const char* path) {
+int run(const char* path, bool homogeneous) {
   FILE* f = fopen(path, "rb");
   if (!f) { fprintf(stderr, "%s: cannot open\n", path); return 2; }
   char magic[4];
@@ -38,8 +39,9 @@ int run(const char* path) {
   fclose(f);
   if (!ok) { fprintf(stderr, "%s: not a frame file\n", path); return 2; }
   hmp_frame* fr = nullptr;
-  if (hmp_frame_build((int32_t)n, ids.data(), layer.data(), pos.data(), bb_min.data(), bb_max.data(), label.data(), m, edges.data(), th[0], th[1],
-                      th[2], h[2], h[3], h[4], h[5], h[6], &fr) != HMP_OK) {
+  auto build = homogeneous ? hmp_frame_build_homogeneous : hmp_frame_build;
+  if (build((int32_t)n, ids.data(), layer.data(), pos.data(), bb_min.data(), bb_max.data(), label.data(), m, edges.data(), th[0], th[1], th[2],
+            h[2], h[3], h[4], h[5], h[6], &fr) != HMP_OK) {
     fprintf(stderr, "%s: %s\n", path, hmp_last_error());
     return 1;
   }
@@ -53,8 +55,8 @@ int run(const char* path) {
   if (sz[HMP_FS_ITEMS] > 0) rc = rc || hmp_frame_pack(fr, staging.data(), (int64_t)staging.size());
   hmp_frame_destroy(fr);
   if (rc) { fprintf(stderr, "%s: %s\n", path, hmp_last_error()); return 1; }
-  printf("%s: kept %lld dropped %lld rooms %lld oo %lld rr %lld items %lld blocks %lld staging %lld arena %lld\n", path, (long long)sz[HMP_FS_KEPT],
-         (long long)sz[HMP_FS_DROPPED], (long long)sz[HMP_FS_ROOMS], (long long)sz[HMP_FS_E_OO], (long long)sz[HMP_FS_E_RR],
+  printf("%s%s: kept %lld dropped %lld rooms %lld oo %lld rr %lld items %lld blocks %lld staging %lld arena %lld\n", path,
+         homogeneous ? " (homogeneous)" : "", (long long)sz[HMP_FS_KEPT], (long long)sz[HMP_FS_DROPPED], (long long)sz[HMP_FS_ROOMS], (long long)sz[HMP_FS_E_OO], (long long)sz[HMP_FS_E_RR],
          (long long)sz[HMP_FS_ITEMS], (long long)sz[HMP_FS_BLOCKS], (long long)sz[HMP_FS_STAGING_BYTES], (long long)sz[HMP_FS_ARENA_BYTES]);
   return 0;
 }
@@ -62,9 +64,11 @@ int run(const char* path) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: %s FRAME_FILE...\n", argv[0]); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: %s [--homogeneous] FRAME_FILE...\n", argv[0]); return 2; }
+  bool homogeneous = false;
   for (int i = 1; i < argc; ++i) {
-    const int rc = run(argv[i]);
+    if (strcmp(argv[i], "--homogeneous") == 0) { homogeneous = true; continue; }
+    const int rc = run(argv[i], homogeneous);
     if (rc) return rc;
   }
   printf("FRAME-CHECK-OK\n");

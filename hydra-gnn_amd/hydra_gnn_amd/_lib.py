@@ -269,6 +269,8 @@ SIGNATURES = {
     "hmp_epoch_read_status": (C.c_int, [_VP, C.POINTER(_I32), _VP]),
     "hmp_frame_build": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _I32, _I32,
                                   _I32, C.POINTER(_VP)]),
+    "hmp_frame_build_homogeneous": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _I32,
+                                              _I32, _I32, C.POINTER(_VP)]),
     "hmp_frame_sizes": (C.c_int, [_VP, _VP]),
     "hmp_frame_host_arrays": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "hmp_frame_pack": (C.c_int, [_VP, _VP, _I64]),
@@ -281,8 +283,9 @@ FS_KEPT, FS_DROPPED, FS_ROOMS, FS_E_OO, FS_E_RR, FS_STAGING_BYTES, FS_ARENA_BYTE
 FS_HT_COUNTS, FS_HT_EDGES, FS_HT_INIT, FS_COUNT = 9, 13, 23, 26
 FRAME_ITEM_WORDS = 12
 FI_KIND, FI_TENSOR, FI_ROWS, FI_WIDTH, FI_DST, FI_S0, FI_S1, FI_S2, FI_S3, FI_P0, FI_P1, FI_BLOCK0 = range(12)
-FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE = range(6)
+FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE, FK_EDGE_SEG, FK_CONST = range(8)
 FT_HTREE, FT_COUNT = 16, 45
+FT_HOMOG, FT_HOMOG_COUNT = 45, 9  # the tensors of a homogeneous frame (hmp_frame_build_homogeneous)
 
 ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
 

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .data import HTREE_EDGE_TYPES, HTREE_INIT_EDGE_TYPES, HTREE_POOL_EDGE_TYPES, HeteroData
+from .data import HTREE_EDGE_TYPES, HTREE_INIT_EDGE_TYPES, HTREE_POOL_EDGE_TYPES, Data, HeteroData
 
 OBJECTS, PLACES, ROOMS, BUILDINGS = 2, 3, 4, 5
 _STATIC = ("ObjectNodeAttributes", "PlaceNodeAttributes", "RoomNodeAttributes", "SemanticNodeAttributes")
@@ -209,6 +209,9 @@ _FRAME_TENSORS = (
 )
 assert len(_FRAME_TENSORS) == _lib.FT_COUNT
 _HTREE_STORES = ["object", "room", "object-room", "room-room", "object_virtual", "room_virtual"]
+# attributes of the homogeneous Data, by output tensor number - HMP_FT_HOMOG
+_HOMOG_TENSORS = ("x", "edge_index", "node_type", "edge_type", "room_mask", "edge_attr", "object_mask", "init_edge_index", "pool_edge_index")
+assert len(_HOMOG_TENSORS) == _lib.FT_HOMOG_COUNT
 
 
 def scene_arrays(sg: SceneGraph):
@@ -230,25 +233,27 @@ def _frame_args(ids, layer, pos, bb_min, bb_max, label, edges):
     return arrays, n, int(edges.shape[1])
 
 
-def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_labels, clique_dim) -> C.c_void_p:
+def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_labels, clique_dim, homogeneous=False) -> C.c_void_p:
     ids, layer, pos, bb_min, bb_max, label, edges = arrays
     h = C.c_void_p()
-    _lib.check(lib.hmp_frame_build(n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data,
-                                   label.ctypes.data, m, edges.ctypes.data, float(thresholds[0]), float(thresholds[1]),
-                                   float(thresholds[2]), int(bool(htree)), int(bool(relative_pos)), int(sem_dim), int(n_labels),
-                                   int(clique_dim or 0), C.byref(h)))
+    build = lib.hmp_frame_build_homogeneous if homogeneous else lib.hmp_frame_build
+    _lib.check(build(n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data,
+                     label.ctypes.data, m, edges.ctypes.data, float(thresholds[0]), float(thresholds[1]),
+                     float(thresholds[2]), int(bool(htree)), int(bool(relative_pos)), int(sem_dim), int(n_labels),
+                     int(clique_dim or 0), C.byref(h)))
     return h
 
 
 def frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
                      max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
-                     clique_dim: Optional[int] = None) -> Dict[str, object]:
-    """The host stage of the frame pipeline on its own (no GPU involved; tests and diagnostics): ``hmp_frame_build`` and every
-    accessor.  ``kept`` / ``dropped`` / ``rooms`` index the input arrays; ``items`` is the staging block's table (int32
-    ``[n_items, 12]``), ``block`` the packed block (uint8); ``empty``: no room or no kept object, nothing was laid out."""
+                     clique_dim: Optional[int] = None, homogeneous: bool = False) -> Dict[str, object]:
+    """The host stage of the frame pipeline on its own (no GPU involved; tests and diagnostics): ``hmp_frame_build``
+    (``homogeneous``: ``hmp_frame_build_homogeneous``) and every accessor.  ``kept`` / ``dropped`` / ``rooms`` index the input
+    arrays; ``items`` is the staging block's table (int32 ``[n_items, 12]``), ``block`` the packed block (uint8); ``empty``: no room
+    or no kept object, nothing was laid out."""
     lib = _lib.load()
     arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
-    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels, clique_dim)
+    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels, clique_dim, homogeneous)
     try:
         sz = np.zeros(_lib.FS_COUNT, dtype=np.int64)
         _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -303,10 +308,20 @@ class FramePipeline:
     pipeline has ONE device staging buffer and ONE arena, ordered by the stream alone: the stream of the first ``convert`` that
     enqueues anything is the pipeline's, and a ``convert`` under another current stream is refused (keep a pipeline per stream).
     Relative positions on H-tree edges are not produced (``generate_htree`` has none): ``relative_pos`` with ``htree`` is refused.
+
+    ``homogeneous=True`` is ``convert_graph``'s ``if self.model_info.homogeneous: data.to_homogeneous()`` in the same host stage,
+    copy and launch: ``convert`` returns ``(data.Data, info)`` with what ``HomogeneousNetwork`` / ``HomogeneousNeuralTreeNetwork``
+    read.  Baseline: ``data.heterogeneous_data_to_homogeneous`` of the frame above plus ``room_mask`` (``x`` zero-padded to the
+    widest type, ``edge_index``, ``node_type``, ``edge_type``, ``room_mask``, and ``edge_attr`` with ``relative_pos``); with
+    ``htree=True``: ``data.heterogeneous_htree_to_homogeneous`` of the H-tree above (``x``, ``node_type``, ``edge_index`` /
+    ``edge_type`` of the ten tree edge types, ``init_edge_index``, ``pool_edge_index``, ``room_mask``, ``object_mask``).  The masks
+    are ``torch.bool`` views of arena bytes; a frame carries no ``y``.  ``info["room_ids"]`` is in the order of the ``room_mask``
+    rows.  Everything said above about views, fresh objects, streams and ``None`` holds for it.
     """
 
     def __init__(self, device="cuda:0", semantic_table=None, htree: bool = False, relative_pos: bool = False,
-                 clique_dim: Optional[int] = None, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2):
+                 clique_dim: Optional[int] = None, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2,
+                 homogeneous: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.HydraMPError(f"FramePipeline needs a gfx950 device, not {self.device}: hydra_gnn_amd has no CPU fallback")
@@ -315,6 +330,7 @@ class FramePipeline:
         if htree and relative_pos:
             raise _lib.HydraMPError("FramePipeline: relative positions on H-tree edges are not produced (generate_htree has none)")
         self.htree, self.relative_pos, self.clique_dim = bool(htree), bool(relative_pos), int(clique_dim or 0)
+        self.homogeneous = bool(homogeneous)
         self.thresholds = (float(threshold_near), float(max_near), float(max_on))
         self._lib = _lib.load()
         self._table_host, self._table = None, None
@@ -327,7 +343,7 @@ class FramePipeline:
         self._sizes = np.zeros(_lib.FS_COUNT, dtype=np.int64)
         # device buffers appear with the first frame that has something to convert (an empty frame never touches the device)
         self._pinned, self._pinned_np, self._events, self._slot = [None, None], [None, None], [None, None], 0
-        self._d_staging = self._arena = self._arena_f32 = self._arena_i64 = None
+        self._d_staging = self._arena = self._arena_f32 = self._arena_i64 = self._arena_bool = None
         self._stream = None  # hipStream_t of the first convert that enqueued work
 
     def _ensure(self, staging_bytes: int, arena_bytes: int) -> None:
@@ -345,6 +361,7 @@ class FramePipeline:
         if self._arena is None or self._arena.numel() < arena_bytes:
             self._arena = torch.empty(max(1 << 18, 2 * arena_bytes), dtype=torch.uint8, device=self.device)
             self._arena_f32, self._arena_i64 = self._arena.view(torch.float32), self._arena.view(torch.int64)
+            self._arena_bool = self._arena.view(torch.bool)
 
     def convert_scene(self, sg: SceneGraph):
         """``convert`` on a ``SceneGraph`` (``load_dsg_json``): ``sg.adj`` is flattened to an edge array first."""
@@ -353,7 +370,8 @@ class FramePipeline:
     def convert(self, ids, layer, pos, bb_min, bb_max, label, edges):
         lib = self._lib
         arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
-        h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels, self.clique_dim)
+        h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels, self.clique_dim,
+                         self.homogeneous)
         try:
             sz = self._sizes
             _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -389,6 +407,10 @@ class FramePipeline:
             items = self._pinned_np[slot][: n_items * _lib.FRAME_ITEM_WORDS].reshape(n_items, _lib.FRAME_ITEM_WORDS).tolist()
         finally:
             lib.hmp_frame_destroy(h)
+        ids = arrays[0]
+        info = {"object_ids": ids[kept], "dropped_ids": ids[dropped], "room_ids": ids[rooms]}
+        if self.homogeneous:
+            return self._homogeneous_data(items), info
         g = HeteroData()
         if self.htree:
             for t in _HTREE_STORES:
@@ -403,5 +425,27 @@ class FramePipeline:
             else:
                 t = strided(f32, (n_rows, width), (width, 1), dst >> 2)
             setattr(g[key], attr, t)
-        ids = arrays[0]
-        return g, {"object_ids": ids[kept], "dropped_ids": ids[dropped], "room_ids": ids[rooms]}
+        return g, info
+
+    def _homogeneous_data(self, items) -> Data:
+        """Views of the arena for the tensors of a homogeneous frame.  A tensor is written by one item per segment: its first item
+        starts where the tensor does, its rows (edge tensors: the pitch every segment carries) add up to the tensor's."""
+        at, n_rows, pitch = {}, {}, {}
+        for kind, tensor, rows, width, dst, _, s1, *_ in items:
+            if tensor not in at:
+                at[tensor], n_rows[tensor], pitch[tensor] = dst, 0, s1 if kind == _lib.FK_EDGE_SEG else width
+            n_rows[tensor] += rows
+        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
+        d = Data()
+        for tensor in sorted(at):
+            attr, dst, n, w = _HOMOG_TENSORS[tensor - _lib.FT_HOMOG], at[tensor], n_rows[tensor], pitch[tensor]
+            if attr.endswith("edge_index"):
+                t = strided(i64, (2, w), (w, 1), dst >> 3)
+            elif attr.endswith("_type"):
+                t = strided(i64, (n,), (1,), dst >> 3)
+            elif attr.endswith("_mask"):
+                t = strided(self._arena_bool, (n,), (1,), dst)
+            else:  # x, edge_attr
+                t = strided(f32, (n, w), (w, 1), dst >> 2)
+            setattr(d, attr, t)
+        return d

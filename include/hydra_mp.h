@@ -45,7 +45,9 @@ extern "C" {
  *    hmp_predict_rows, hmp_net_predict_rooms / hmp_net_predict2 / hmp_net_predict_heads (labels instead of counts, for every net
  *    kind), hmp_head_tails_predict / hmp_linear_heads_predict (their test entries): new entries, no struct changed layout;
  *    section 14: hmp_frame_build / hmp_frame_sizes / hmp_frame_host_arrays / hmp_frame_pack / hmp_frame_destroy (host) and
- *    hmp_frame_expand (one launch): scene-graph arrays to model input.  New entries, no struct was added or changed layout */
+ *    hmp_frame_expand (one launch): scene-graph arrays to model input.  New entries, no struct was added or changed layout;
+ *    hmp_frame_build_homogeneous: the same frame laid out as the homogeneous Data (item kinds HMP_FK_EDGE_SEG / HMP_FK_CONST, output
+ *    tensors from HMP_FT_HOMOG on).  A new entry; the six entries above, HMP_FRAME_ITEM_WORDS and every earlier number are unchanged */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -804,12 +806,31 @@ int hmp_epoch_read_status(const hmp_epoch_ctl* d_ctl, int32_t* status, void* str
  *     columns and adds edge_attr = pos32[dst] - pos32[src], baseline only); rooms take no semantic block.  sem_dim = 0: no table.
  *     With a table a label of a kept object outside [0, n_labels) is refused (HMP_E_ARG, the message names the node id).
  *     clique_dim: width of the H-tree's clique rows (0 = the feature width of the objects / rooms).
+ *
+ *     Homogeneous models (HomogeneousNetwork, HomogeneousNeuralTreeNetwork) read the same frame as ONE graph: what
+ *     data.heterogeneous_data_to_homogeneous (+ room_mask) makes of the baseline frame, data.heterogeneous_htree_to_homogeneous of
+ *     the H-tree (convert_graph's `if homogeneous: to_homogeneous()`).  hmp_frame_build_homogeneous lays the frame out in that form
+ *     directly; sizes, host arrays, pack, expand and destroy are the same calls.  Node types are concatenated in store order
+ *     (objects, rooms; object, room, object-room, room-room, object_virtual, room_virtual) into one x, zero-padded to the widest
+ *     type; every edge type's columns are shifted by the row offsets of its endpoint types and concatenated in edge-type order
+ *     (H-tree: the 10 tree types into edge_index / edge_type, the 3 init types into init_edge_index, o_to_ov / r_to_rv into
+ *     pool_edge_index -- a split by edge type, so every count is known on the host).  A homogeneous tensor is allocated once
+ *     (16-byte aligned) and written by ONE ITEM PER SEGMENT: a node type's rows, or an edge type's columns.  HMP_FI_DST of such an
+ *     item is where its segment starts inside the tensor (the first segment's is the tensor's), a row of x is HMP_FI_WIDTH floats
+ *     for every segment, and the segments of a tensor follow one another in table order.  An empty segment keeps its item (no
+ *     workgroup, no bytes).  Worst case: an H-tree has 6 node and 15 edge types: x 6 + node_type 6 + room_mask 6 + object_mask 6 +
+ *     edge_index 10 + edge_type 10 + init 3 + pool 2 = 49 items of the 64 the launch's table holds (baseline: 18).
  * ------------------------------------------------------------------------------------------- */
 typedef struct hmp_frame hmp_frame; /* opaque */
 int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
                     const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
                     double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
                     int32_t clique_dim, hmp_frame** out);
+/* the same arguments and refusals; the layout is the homogeneous one (the frame's HMP_FS_* sizes have the same meaning) */
+int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                                const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
+                                double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim,
+                                int32_t n_labels, int32_t clique_dim, hmp_frame** out);
 /* sizes[HMP_FS_COUNT] */
 #define HMP_FS_KEPT 0          /* kept objects */
 #define HMP_FS_DROPPED 1       /* objects with neither a place with a room nor a sibling place with one */
@@ -838,8 +859,9 @@ void hmp_frame_destroy(hmp_frame* f);
 #define HMP_FI_KIND 0
 #define HMP_FI_TENSOR 1 /* which output tensor (HMP_FT_*) */
 #define HMP_FI_ROWS 2
-#define HMP_FI_WIDTH 3
-#define HMP_FI_DST 4    /* byte offset in the arena, 16-byte aligned */
+#define HMP_FI_WIDTH 3  /* FEAT / CLIQUE: floats per destination row (a FEAT row's own P0 + 3 + P1 columns, zeros behind them) */
+#define HMP_FI_DST 4    /* byte offset in the arena: 16-byte aligned for a whole tensor; a segment of a homogeneous tensor starts
+                           at a multiple of its element size (x rows: of the row size) inside a 16-byte aligned tensor */
 #define HMP_FI_S0 5     /* byte offsets of source sections in the staging block (-1: none); meaning per kind, see csrc/frame.hip */
 #define HMP_FI_S1 6
 #define HMP_FI_S2 7
@@ -855,12 +877,19 @@ void hmp_frame_destroy(hmp_frame* f);
 #define HMP_FK_EDGE 3   /* int64 [2][width] from an int32 list */
 #define HMP_FK_EATTR 4  /* float32 [rows][3] = pos32[dst] - pos32[src] */
 #define HMP_FK_CLIQUE 5 /* float32 rows [mean float32 position of the member rooms | zeros] */
+#define HMP_FK_EDGE_SEG 6 /* HMP_FI_WIDTH columns of an int64 [2][S1] tensor from an int32 list (P0, P1 as EDGE): row 1 lies S1
+                             elements behind row 0; S2 is added to every source, S3 to every destination (S1..S3: numbers) */
+#define HMP_FK_CONST 7  /* HMP_FI_ROWS elements of P1 bytes (8: int64, 1: a bool mask), every one P0 */
 /* output tensors: baseline 0..15 = {objects, rooms} x {x, pos, label, node_ids}, then edge_index and edge_attr of
  * objects_to_objects, rooms_to_rooms, rooms_to_objects, objects_to_rooms; H-tree 16.. = {object, room} x {x, pos, label},
  * object-room.x, room-room.x, {object_virtual, room_virtual} x {x, pos, label}, the 10 HTREE_EDGE_TYPES, the 3 init edge types,
  * o_to_ov, r_to_rv */
 #define HMP_FT_HTREE 16
 #define HMP_FT_COUNT 45
+/* homogeneous frames (hmp_frame_build_homogeneous) use only these: +0 x, +1 edge_index, +2 node_type, +3 edge_type, +4 room_mask
+ * (bytes), +5 edge_attr (relative_pos); H-tree: +6 object_mask (bytes), +7 init_edge_index, +8 pool_edge_index */
+#define HMP_FT_HOMOG 45
+#define HMP_FT_HOMOG_COUNT 9
 /* One launch on `stream`: d_staging = the packed block on the device (16-byte aligned), d_arena >= HMP_FS_ARENA_BYTES (16-byte
  * aligned), d_sem_table float32 [n_labels][sem_dim] (8-byte aligned; null when sem_dim = 0); n_items / n_blocks from hmp_frame_sizes.
  * The item table lives on the device, so this entry cannot compare it with its arguments; the caller owes it three things:

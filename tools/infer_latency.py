@@ -4,7 +4,11 @@
   b) model.predict(data): native eval forward + hmp_argmax_rows + one pinned D2H of the labels
   c) the step in front of the model call, GnnModel.convert_graph: the existing stages of hydra_gnn_amd/dsg.py and htree.py next to
      dsg.FramePipeline.convert, median and p90 of ``--reps`` calls (default 200); ``--convert-loop N`` runs only N converts per
-     pipeline, for a kernel trace
+     pipeline, for a kernel trace (``--convert-loop N --homogeneous``: of the two homogeneous pipelines)
+  d) ``--homogeneous-legs``: only the input of the HOMOGENEOUS models (HomogeneousNetwork / HomogeneousNeuralTreeNetwork), three
+     ways in alternation (plus the typed convert alone, for scale): the host conversion + ``data.heterogeneous_*_to_homogeneous`` + one ``.to(device)``; the typed pipeline
+     brought back to the host for the same conversion; ``FramePipeline(homogeneous=True).convert``.  The first two use only
+     interfaces older than the third, which is skipped where the package does not have it
 
 One MP3D-like scene graph per call (a fresh graph object every call, as the server receives a new frame), 306-d objects,
 3-layer SAGE hidden 64 and the shipped GAT shape (3 layers, 3 heads, hidden 64, concat False).  Prints one JSON line.
@@ -19,6 +23,7 @@ import torch
 
 sys.path.insert(0, "hydra-gnn_amd")
 from hydra_gnn_amd import dsg, htree, workloads  # noqa: E402
+from hydra_gnn_amd.data import heterogeneous_data_to_homogeneous, heterogeneous_htree_to_homogeneous  # noqa: E402
 from hydra_gnn_amd.models import HeterogeneousNetwork  # noqa: E402
 
 DEV = "cuda:0"
@@ -127,19 +132,96 @@ def frame_stages(sg, sage_kw, raw=None):
     return stages
 
 
-def convert_loop(n):
+def to_homogeneous(frame, htree_mode):
+    """the host conversion of a typed frame on the CPU (Hydra_mp3d_data.to_homogeneous / heterogeneous_htree_to_homogeneous)"""
+    if htree_mode:
+        return heterogeneous_htree_to_homogeneous(frame)
+    d, types = heterogeneous_data_to_homogeneous(frame)
+    d.room_mask = d.node_type == types.index("rooms")
+    return d
+
+
+def has_homogeneous_pipeline():
+    import inspect
+
+    return hasattr(dsg, "FramePipeline") and "homogeneous" in inspect.signature(dsg.FramePipeline.__init__).parameters
+
+
+def homogeneous_legs(sg, reps, htree_reps):
+    """The homogeneous models' input, each call timed to completion, the legs alternating call by call (one session, so drift hits
+    all of them alike): median and p90 in us per leg, for the baseline frame and for its H-tree"""
+    flat = flat_arrays(sg)
+    out = {}
+    for htree_mode in (False, True):
+        kw = dict(htree=True, clique_dim=6) if htree_mode else {}
+        typed = dsg.FramePipeline(DEV, **kw)
+
+        def host_route():  # everything on the host, then one .to(device) of the Data
+            rog = dsg.RoomObjectGraph(sg)
+            oo = torch.from_numpy(dsg.frame_host_stage(*flat)["oo_edges"].astype(np.int64))  # the native predicates, host memory only
+            frame = dsg.to_hetero_data(rog, oo, None, "cpu")
+            if htree_mode:
+                frame = htree.generate_htree(frame, clique_dim=6)
+            return to_homogeneous(frame, htree_mode).to(DEV)
+
+        def roundtrip_route():  # the typed pipeline, back to the host for the conversion, up again
+            return to_homogeneous(typed.convert(*flat)[0].to("cpu"), htree_mode).to(DEV)
+
+        # the typed convert on its own: not a way to the homogeneous Data, only the scale of the two pipeline legs
+        legs = {"host_to_homogeneous": host_route, "typed_pipeline_roundtrip": roundtrip_route,
+                "typed_pipeline_convert": lambda: typed.convert(*flat)[0]}
+        if has_homogeneous_pipeline():
+            pipe = dsg.FramePipeline(DEV, homogeneous=True, **kw)
+            legs["pipeline_convert_homogeneous"] = lambda: pipe.convert(*flat)[0]
+        results = {}
+        for name, fn in legs.items():
+            for _ in range(3):
+                results[name] = fn()
+        torch.cuda.synchronize()
+        ts = {name: [] for name in legs}
+        n = htree_reps if htree_mode else reps
+        for _ in range(n):
+            for name, fn in legs.items():
+                t0 = time.perf_counter_ns()
+                fn()
+                torch.cuda.synchronize()
+                ts[name].append((time.perf_counter_ns() - t0) * 1e-3)
+        if "pipeline_convert_homogeneous" in legs and not htree_mode:  # the three legs made the same Data
+            want = vars(results["typed_pipeline_roundtrip"])
+            got = vars(legs["pipeline_convert_homogeneous"]())
+            assert all(torch.equal(got[k], want[k]) for k in want if k != "_plan_cache")
+        tag = "htree" if htree_mode else "baseline"
+        for name, t in ts.items():
+            out[f"{tag}_{name}_us"] = round(float(np.median(t)), 1)
+            out[f"{tag}_{name}_p90_us"] = round(float(np.percentile(t, 90)), 1)
+        out[f"{tag}_reps"] = n
+    return out
+
+
+def homogeneous_main(reps):
+    out = {"homogeneous_legs": True, "has_homogeneous_pipeline": has_homogeneous_pipeline()}
+    out["dsg_frame_62_objects"] = homogeneous_legs(dsg.load_dsg_json(json.load(open(FIXTURE))), reps, max(5, reps // 4))
+    big = scene_graph(workloads.synthetic_scene(300, 3, seed=1))
+    out["dsg_frame_300_objects"] = homogeneous_legs(big, reps, max(5, reps // 20))  # its H-tree: 0.45 s per call and leg
+    print(json.dumps(out))
+
+
+def convert_loop(n, homogeneous=False):
     """only the pipeline's convert calls (baseline, then H-tree), for a kernel trace of the conversion on its own"""
     flat = flat_arrays(dsg.load_dsg_json(json.load(open(FIXTURE))))
-    for pipe in (dsg.FramePipeline(DEV), dsg.FramePipeline(DEV, htree=True, clique_dim=6)):
+    kw = dict(homogeneous=True) if homogeneous else {}
+    for pipe in (dsg.FramePipeline(DEV, **kw), dsg.FramePipeline(DEV, htree=True, clique_dim=6, **kw)):
         for _ in range(n):
             pipe.convert(*flat)
     torch.cuda.synchronize()
-    print(json.dumps({"convert_loop": n, "pipelines": 2}))
+    print(json.dumps({"convert_loop": n, "pipelines": 2, "homogeneous": homogeneous}))
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--convert-loop":
-        convert_loop(int(sys.argv[2]))
+        convert_loop(int(sys.argv[2]), homogeneous="--homogeneous" in sys.argv[3:])
+    elif len(sys.argv) > 1 and sys.argv[1] == "--homogeneous-legs":  # [--reps N]
+        homogeneous_main(int(sys.argv[3]) if len(sys.argv) > 3 and sys.argv[2] == "--reps" else REPS)
     else:
         if len(sys.argv) > 2 and sys.argv[1] == "--reps":  # the H-tree of the 300-object frame takes 0.45 s per call
             REPS = int(sys.argv[2])
