@@ -44,6 +44,8 @@ struct hmp_frame {
   std::vector<uint8_t> sections;  // the block behind the item table
   int64_t arena_bytes = 0;
   int32_t n_blocks = 0;
+  int32_t cfg[6] = {0, 0, 0, 0, 0, 0};  // homogeneous, htree, relative_pos, sem_dim, n_labels, clique_dim: what a batch must share
+  int32_t n_input = 0;                  // nodes of the input arrays (the length of a frame's label vector y)
   ~hmp_frame() { hmp_htree_destroy(tree); }
 };
 
@@ -184,6 +186,9 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
   };
 
   hmp_frame* F = new hmp_frame;
+  const int32_t cfg[6] = {homogeneous ? 1 : 0, htree ? 1 : 0, relative_pos ? 1 : 0, sem_dim, n_labels, clique_dim};
+  memcpy(F->cfg, cfg, sizeof cfg);
+  F->n_input = n;
   auto bail = [&](const char* msg) { delete F; return fail(msg); };
   std::vector<int> room_index(n, -1);
   for (int i : order) if (layer[i] == L_ROOMS) { room_index[i] = (int)F->rooms.size(); F->rooms.push_back(i); }
@@ -509,3 +514,368 @@ extern "C" int hmp_frame_pack(const hmp_frame* f, void* staging, int64_t bytes) 
 }
 
 extern "C" void hmp_frame_destroy(hmp_frame* f) { delete f; }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Batches of frames (include/hydra_mp.h section 14, "batches"): K built frames -> ONE block [group table | item table | sections]
+// and ONE arena holding either the collated batch the models read (HMP_FB_COLLATED: data.collate / data.collate_homogeneous of the
+// K single results) or the packed arrays of a GraphStore (HMP_FB_STORE: the same concatenations with graph-local endpoints).
+// A batched tensor is the frames' tensors back to back, so every item of every frame is kept and RE-ADDRESSED: its sections move to
+// the frame's place in the block, its destination to the frame's place inside the batched tensor, an edge list becomes an EDGE_SEG
+// with the batched tensor's pitch and the frame's two shifts.  Nothing is re-derived from the scene graph, and the frames' sections
+// are not copied before hmp_frame_batch_pack writes them to the caller's buffer.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct hmp_frame_batch {
+  std::vector<const hmp_frame*> frames;  // the frames with items, in graph order (they outlive the batch)
+  std::vector<int32_t> graph_of_frame;   // per input frame: its graph, -1 for a skipped one
+  std::vector<int64_t> frame_base;       // per graph: where its sections start, relative to the first section of the block
+  std::vector<int32_t> groups, items;
+  std::vector<uint8_t> sections;         // the batch's own sections (offset vectors, labels, label row indices), behind the frames'
+  int64_t own_base = 0;                  // relative to the first section, as frame_base
+  std::vector<int64_t> tensors;          // [n][4]: tensor number, byte offset in the arena, rows, width
+  std::vector<int64_t> node_ptr, edge_ptr;  // [types][graphs + 1]
+  int32_t n_node_types = 0, n_edge_types = 0, n_blocks = 0;
+  int64_t arena_bytes = 0, max_graph_nodes = 0;
+};
+
+namespace {
+
+int batch_fail(const char* m) {
+  snprintf(hmp::err_buf(), 512, "hmp_frame_batch_build: %s", m);
+  return HMP_E_ARG;
+}
+
+// rows per node type of a frame, in store order: typed {objects, rooms} / the six H-tree stores; the same types are the segments
+// of a homogeneous frame's x
+int node_rows(const hmp_frame& f, int64_t* rows) {
+  const int64_t n_obj = (int64_t)f.kept.size(), n_rooms = (int64_t)f.rooms.size();
+  if (!f.tree) { rows[0] = n_obj; rows[1] = n_rooms; return 2; }
+  for (int k = 0; k < 4; ++k) rows[k] = f.tree->counts[k];
+  rows[4] = n_obj; rows[5] = n_rooms;
+  return 6;
+}
+
+// node type of a typed node tensor, or (source, destination) types of a typed edge tensor (edge_index and edge_attr alike)
+void typed_ends(int tensor, int& src, int& dst) {
+  static const int base_ends[4][2] = {{0, 0}, {1, 1}, {1, 0}, {0, 1}};
+  static const int tree_ends[15][2] = {{0, 2}, {2, 0}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 3}, {3, 2}, {2, 2}, {3, 3},
+                                       {4, 2}, {5, 2}, {5, 3}, {0, 4}, {1, 5}};
+  if (tensor < HMP_FT_HTREE) { src = base_ends[(tensor - 8) & 3][0]; dst = base_ends[(tensor - 8) & 3][1]; }
+  else { src = tree_ends[tensor - HMP_FT_HTREE - 14][0]; dst = tree_ends[tensor - HMP_FT_HTREE - 14][1]; }
+}
+
+// bytes of one row of an item's output (edge lists excepted: they are counted in columns)
+int64_t row_bytes(const int32_t* w) {
+  switch (w[HMP_FI_KIND]) {
+    case HMP_FK_FEAT: case HMP_FK_CLIQUE: return (int64_t)w[HMP_FI_WIDTH] * 4;
+    case HMP_FK_POS: case HMP_FK_EATTR: return 12;
+    case HMP_FK_CONST: return w[HMP_FI_P1];
+    default: return 8;
+  }
+}
+
+}  // namespace
+
+extern "C" int hmp_frame_batch_items_needed(const hmp_frame* f, int32_t form, int32_t with_y, int32_t* per_frame, int32_t* per_batch) {
+  if (!f || !per_frame || !per_batch || (form != HMP_FB_COLLATED && form != HMP_FB_STORE)) return batch_fail("bad argument (items_needed)");
+  const bool homog = f->cfg[0], htree = f->cfg[1], rel = f->cfg[2];
+  const int n_types = htree ? 6 : 2;
+  // items of a frame of this configuration (a frame without items has none to count: the layouts' own counts, as frame_build emits them)
+  int frame_items, n_edge_types;
+  if (homog) { frame_items = htree ? 49 : (rel ? 18 : 14); n_edge_types = htree ? 3 : 1; }
+  else { frame_items = htree ? 29 : (rel ? 16 : 12); n_edge_types = htree ? 15 : 4; }
+  if (!f->items.empty()) frame_items = (int)(f->items.size() / HMP_FRAME_ITEM_WORDS);
+  *per_frame = frame_items + (!homog && form == HMP_FB_COLLATED ? n_types : 0) + (with_y ? (homog ? n_types : (htree ? 4 : 2)) : 0);
+  *per_batch = homog ? (form == HMP_FB_STORE ? 1 + n_edge_types : 0) : n_types + n_edge_types;
+  return HMP_OK;
+}
+
+extern "C" int hmp_frame_batch_build(int32_t n_frames, const hmp_frame* const* frames, int32_t form, const int64_t* const* y,
+                                     hmp_frame_batch** out) {
+  if (!out || n_frames < 0 || (n_frames > 0 && !frames)) return batch_fail("bad argument");
+  if (form != HMP_FB_COLLATED && form != HMP_FB_STORE) return batch_fail("form must be HMP_FB_COLLATED or HMP_FB_STORE");
+  for (int i = 0; i < n_frames; ++i) {
+    if (!frames[i]) return batch_fail("null frame");
+    if (memcmp(frames[i]->cfg, frames[0]->cfg, sizeof frames[0]->cfg) != 0)
+      return batch_fail("the frames were built with different configurations (typed / homogeneous, htree, relative_pos, sem_dim, n_labels, clique_dim)");
+    if (y && !y[i] && frames[i]->n_input > 0) return batch_fail("labels are given for every frame or for none: a frame's y is null");
+  }
+  hmp_frame_batch* B = new hmp_frame_batch;
+  auto bail = [&](const char* m) { delete B; return batch_fail(m); };
+  B->graph_of_frame.assign(n_frames, -1);
+  std::vector<int> input_of;  // graph -> input frame
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]->items.empty()) { B->graph_of_frame[i] = (int32_t)B->frames.size(); B->frames.push_back(frames[i]); input_of.push_back(i); }
+  const int G = (int)B->frames.size();
+  if (G == 0) { *out = B; return HMP_OK; }  // nothing to pack, nothing to launch
+
+  const hmp_frame& F0 = *B->frames[0];
+  const bool homog = F0.cfg[0] != 0, collated = form == HMP_FB_COLLATED;
+  const int W = HMP_FRAME_ITEM_WORDS;
+  const int ipf = (int)(F0.items.size() / W);
+  for (const hmp_frame* f : B->frames) {
+    if ((int)(f->items.size() / W) != ipf) return bail("internal: frames of one configuration differ in their item count");
+    for (int j = 0; j < ipf; ++j)
+      if (f->items[j * W + HMP_FI_TENSOR] != F0.items[j * W + HMP_FI_TENSOR]) return bail("internal: frames of one configuration differ in their item order");
+  }
+
+  // ---- rows of every node type per graph and their running sums; a homogeneous batch has ONE node set (all types of a graph)
+  int64_t rows[6];
+  const int n_types = node_rows(F0, rows);  // types of a frame: segments of a homogeneous x
+  B->n_node_types = homog ? 1 : n_types;
+  std::vector<int64_t> type_rows((size_t)G * n_types);
+  B->node_ptr.assign((size_t)B->n_node_types * (G + 1), 0);
+  for (int g = 0; g < G; ++g) {
+    node_rows(*B->frames[g], rows);
+    int64_t total = 0;
+    for (int t = 0; t < n_types; ++t) { type_rows[(size_t)g * n_types + t] = rows[t]; total += rows[t]; }
+    if (homog) {
+      B->node_ptr[g + 1] = B->node_ptr[g] + total;
+      B->max_graph_nodes = std::max(B->max_graph_nodes, total);
+    } else {
+      for (int t = 0; t < n_types; ++t) {
+        B->node_ptr[(size_t)t * (G + 1) + g + 1] = B->node_ptr[(size_t)t * (G + 1) + g] + rows[t];
+        B->max_graph_nodes = std::max(B->max_graph_nodes, rows[t]);
+      }
+    }
+  }
+  auto nptr = [&](int t, int g) { return B->node_ptr[(size_t)t * (G + 1) + g]; };
+
+  // ---- where every frame's sections go
+  int64_t sec_end = 0;
+  for (int g = 0; g < G; ++g) { B->frame_base.push_back(sec_end); sec_end = align16(sec_end + (int64_t)B->frames[g]->sections.size()); }
+  B->own_base = sec_end;
+  auto own_section = [&](const void* p, size_t bytes) {
+    const size_t off = (size_t)align16((int64_t)B->sections.size());
+    B->sections.resize(off + bytes);
+    if (bytes) memcpy(B->sections.data() + off, p, bytes);
+    return (int64_t)off;  // relative to own_base
+  };
+  auto alloc = [&](int64_t bytes) { const int64_t off = B->arena_bytes; B->arena_bytes = align16(off + bytes); return off; };
+  // offsets can pass 2^31 while the table is made; they are checked before they are narrowed
+  bool too_large = false;
+  auto put_item = [&](const int64_t* w, int64_t blocks) {
+    for (int k = 0; k < W - 1; ++k) { if (w[k] > INT32_MAX || w[k] < INT32_MIN) too_large = true; B->items.push_back((int32_t)w[k]); }
+    B->items.push_back(B->n_blocks);
+    if ((int64_t)B->n_blocks + blocks > INT32_MAX) too_large = true; else B->n_blocks += (int32_t)blocks;
+  };
+  auto blocks_of = [](int64_t units) { return (units + 255) / 256; };
+
+  // ---- the frames' tensors: a run of items of one tensor number (one item of a typed frame, the segments of a homogeneous one)
+  for (int a = 0; a < ipf;) {
+    int b = a + 1;
+    const int tensor = F0.items[a * W + HMP_FI_TENSOR];
+    while (b < ipf && F0.items[b * W + HMP_FI_TENSOR] == tensor) ++b;
+    const int kind0 = F0.items[a * W + HMP_FI_KIND];
+    const bool edge = kind0 == HMP_FK_EDGE || kind0 == HMP_FK_EDGE_SEG;
+    // extent of the tensor in every frame: columns of an edge list, bytes of everything else
+    std::vector<int64_t> off(G + 1, 0);
+    for (int g = 0; g < G; ++g) {
+      int64_t ext = 0;
+      for (int j = a; j < b; ++j) {
+        const int32_t* w = &B->frames[g]->items[j * W];
+        ext += edge ? (int64_t)w[HMP_FI_WIDTH] : (int64_t)w[HMP_FI_ROWS] * row_bytes(w);
+      }
+      off[g + 1] = off[g] + ext;
+    }
+    const int64_t base = alloc(edge ? 2 * off[G] * 8 : off[G]);
+    if (edge) {
+      B->edge_ptr.insert(B->edge_ptr.end(), off.begin(), off.end());
+      ++B->n_edge_types;
+      const int64_t t4[4] = {tensor, base, 2, off[G]};
+      B->tensors.insert(B->tensors.end(), t4, t4 + 4);
+    } else {
+      const int32_t* w0 = &F0.items[a * W];
+      const int64_t rb = row_bytes(w0), width = (kind0 == HMP_FK_FEAT || kind0 == HMP_FK_CLIQUE) ? w0[HMP_FI_WIDTH] : (rb == 12 ? 3 : 1);
+      const int64_t t4[4] = {tensor, base, off[G] / rb, width};
+      B->tensors.insert(B->tensors.end(), t4, t4 + 4);
+    }
+    for (int g = 0; g < G; ++g) {
+      const hmp_frame& f = *B->frames[g];
+      const int64_t tb = align16((int64_t)ipf * W * 4);  // the frame's section offsets count from its own block
+      const int64_t frame_dst = f.items[a * W + HMP_FI_DST];
+      for (int j = a; j < b; ++j) {
+        const int32_t* w = &f.items[j * W];
+        int64_t v[HMP_FRAME_ITEM_WORDS];
+        for (int k = 0; k < W; ++k) v[k] = w[k];
+        const int kind = w[HMP_FI_KIND];
+        const bool seg = kind == HMP_FK_EDGE_SEG, list = kind == HMP_FK_EDGE || seg;
+        for (int k = HMP_FI_S0; k <= (list ? HMP_FI_S0 : HMP_FI_S3); ++k)
+          if (v[k] >= 0) v[k] = v[k] - tb + B->frame_base[g];
+        v[HMP_FI_DST] = base + (edge ? off[g] * 8 : off[g]) + (w[HMP_FI_DST] - frame_dst);
+        if (list) {
+          int64_t s_src = seg ? w[HMP_FI_S2] : 0, s_dst = seg ? w[HMP_FI_S3] : 0;  // a homogeneous frame's type offsets stay
+          if (collated) {
+            if (homog) { s_src += nptr(0, g); s_dst += nptr(0, g); }
+            else { int ts, td; typed_ends(tensor, ts, td); s_src = nptr(ts, g); s_dst = nptr(td, g); }
+          }
+          v[HMP_FI_KIND] = HMP_FK_EDGE_SEG;
+          v[HMP_FI_S1] = off[G];
+          v[HMP_FI_S2] = s_src;
+          v[HMP_FI_S3] = s_dst;
+        }
+        const int64_t next = j + 1 < ipf ? f.items[(j + 1) * W + HMP_FI_BLOCK0] : f.n_blocks;
+        put_item(v, next - w[HMP_FI_BLOCK0]);
+      }
+    }
+    a = b;
+  }
+
+  // ---- what a batch adds: `batch` of every node type (collated, typed), the offset vectors, the labels
+  const int FB = HMP_FT_BATCH;
+  auto const_item = [&](int tensor, int64_t dst, int64_t n, int64_t value) {
+    const int64_t v[HMP_FRAME_ITEM_WORDS] = {HMP_FK_CONST, tensor, n, 1, dst, -1, -1, -1, -1, value, 8, 0};
+    put_item(v, blocks_of(n));
+  };
+  auto i64_item = [&](int tensor, int64_t dst, int64_t n, int64_t s_src, int64_t s_idx) {
+    const int64_t v[HMP_FRAME_ITEM_WORDS] = {HMP_FK_I64, tensor, n, 1, dst, B->own_base + s_src, -1, -1, s_idx < 0 ? -1 : B->own_base + s_idx, 8, 0, 0};
+    put_item(v, blocks_of(n));
+  };
+  auto tensor_row = [&](int tensor, int64_t base, int64_t n) {
+    const int64_t t4[4] = {tensor, base, n, 1};
+    B->tensors.insert(B->tensors.end(), t4, t4 + 4);
+  };
+  if (collated && !homog)
+    for (int t = 0; t < n_types; ++t) {
+      const int64_t base = alloc(nptr(t, G) * 8);
+      tensor_row(FB + HMP_FTB_BATCH + t, base, nptr(t, G));
+      for (int g = 0; g < G; ++g) const_item(FB + HMP_FTB_BATCH + t, base + nptr(t, g) * 8, nptr(t, g + 1) - nptr(t, g), g);
+    }
+  if (!homog || !collated) {  // data.collate_homogeneous keeps no offset vector
+    for (int t = 0; t < B->n_node_types; ++t) {
+      const int64_t base = alloc((int64_t)(G + 1) * 8);
+      tensor_row(FB + HMP_FTB_NODE_PTR + t, base, G + 1);
+      i64_item(FB + HMP_FTB_NODE_PTR + t, base, G + 1, own_section(&B->node_ptr[(size_t)t * (G + 1)], (size_t)(G + 1) * 8), -1);
+    }
+    int e = 0;
+    for (size_t q = 0; q < B->tensors.size() / 4 && e < B->n_edge_types; ++q) {
+      const int64_t tensor = B->tensors[q * 4];
+      if (tensor >= FB || B->tensors[q * 4 + 2] != 2) continue;
+      const bool is_edge = homog ? (tensor == HMP_FT_HOMOG + 1 || tensor >= HMP_FT_HOMOG + 7)
+                                 : ((tensor >= 8 && tensor < 12) || tensor >= HMP_FT_HTREE + 14);
+      if (!is_edge) continue;
+      const int64_t base = alloc((int64_t)(G + 1) * 8);
+      tensor_row(FB + HMP_FTB_EDGE_PTR + e, base, G + 1);
+      i64_item(FB + HMP_FTB_EDGE_PTR + e, base, G + 1, own_section(&B->edge_ptr[(size_t)e * (G + 1)], (size_t)(G + 1) * 8), -1);
+      ++e;
+    }
+  }
+  if (y) {
+    // labels: int64 [n] per frame, aligned with the frame's INPUT arrays; a row-index section per labelled node type takes the
+    // output row to its input node (kept / rooms, composed with object_orig / room_orig for the leaves of an H-tree)
+    std::vector<int64_t> s_y(G);
+    std::vector<std::vector<int64_t>> s_idx(G);
+    for (int g = 0; g < G; ++g) {
+      const hmp_frame& f = *B->frames[g];
+      s_y[g] = own_section(y[input_of[g]], (size_t)f.n_input * 8);
+      std::vector<int32_t> leaf_o, leaf_r;
+      if (f.tree) {
+        for (int32_t k : f.tree->object_orig) leaf_o.push_back(f.kept[k]);
+        for (int32_t k : f.tree->room_orig) leaf_r.push_back(f.rooms[k]);
+        s_idx[g] = {own_section(leaf_o.data(), leaf_o.size() * 4), own_section(leaf_r.data(), leaf_r.size() * 4), -1, -1,
+                    own_section(f.kept.data(), f.kept.size() * 4), own_section(f.rooms.data(), f.rooms.size() * 4)};
+      } else {
+        s_idx[g] = {own_section(f.kept.data(), f.kept.size() * 4), own_section(f.rooms.data(), f.rooms.size() * 4)};
+      }
+    }
+    if (homog) {  // one y over all nodes in store order, -1 on the clique rows
+      const int64_t base = alloc(nptr(0, G) * 8);
+      tensor_row(FB + HMP_FTB_Y, base, nptr(0, G));
+      for (int g = 0; g < G; ++g) {
+        int64_t row = nptr(0, g);
+        for (int t = 0; t < n_types; ++t) {
+          const int64_t n = type_rows[(size_t)g * n_types + t];
+          if (s_idx[g][t] < 0) const_item(FB + HMP_FTB_Y, base + row * 8, n, -1);
+          else i64_item(FB + HMP_FTB_Y, base + row * 8, n, s_y[g], s_idx[g][t]);
+          row += n;
+        }
+      }
+    } else {
+      for (int t = 0; t < n_types; ++t) {
+        if (s_idx[0][t] < 0) continue;  // clique nodes carry no label
+        const int64_t base = alloc(nptr(t, G) * 8);
+        tensor_row(FB + HMP_FTB_Y + t, base, nptr(t, G));
+        for (int g = 0; g < G; ++g) i64_item(FB + HMP_FTB_Y + t, base + nptr(t, g) * 8, nptr(t, g + 1) - nptr(t, g), s_y[g], s_idx[g][t]);
+      }
+    }
+  }
+
+  // ---- the block: [group table | item table | sections]; section offsets so far count from the first section
+  const int64_t n_items = (int64_t)B->items.size() / W;
+  if (n_items > HMP_FRAME_BATCH_MAX_ITEMS) {
+    snprintf(hmp::err_buf(), 512, "hmp_frame_batch_build: %lld items for %d graphs, the launch's tables hold %d (HMP_FRAME_BATCH_MAX_ITEMS): convert fewer frames at once",
+             (long long)n_items, G, HMP_FRAME_BATCH_MAX_ITEMS);
+    delete B;
+    return HMP_E_ARG;
+  }
+  const int64_t n_groups = (n_items + HMP_FRAME_MAX_ITEMS - 1) / HMP_FRAME_MAX_ITEMS;
+  const int64_t header = align16(n_groups * 4) + align16(n_items * W * 4);
+  const int64_t staging = header + B->own_base + (int64_t)B->sections.size();
+  if (too_large || B->arena_bytes > INT32_MAX || staging > INT32_MAX) return bail("batch too large: the arena or the staging block exceeds 2^31 - 1 bytes");
+  for (int64_t i = 0; i < n_items; ++i) {
+    const bool seg = B->items[i * W + HMP_FI_KIND] == HMP_FK_EDGE_SEG;
+    for (int k = HMP_FI_S0; k <= (seg ? HMP_FI_S0 : HMP_FI_S3); ++k) {
+      int32_t& s = B->items[i * W + k];
+      if (s >= 0) s += (int32_t)header;
+    }
+  }
+  for (int64_t g = 0; g < n_groups; ++g) B->groups.push_back(B->items[g * HMP_FRAME_MAX_ITEMS * W + HMP_FI_BLOCK0]);
+  *out = B;
+  return HMP_OK;
+}
+
+extern "C" int hmp_frame_batch_sizes(const hmp_frame_batch* b, int64_t* sizes) {
+  if (!b || !sizes) { snprintf(hmp::err_buf(), 512, "hmp_frame_batch_sizes: null argument"); return HMP_E_ARG; }
+  const int64_t n_items = (int64_t)b->items.size() / HMP_FRAME_ITEM_WORDS, n_groups = (int64_t)b->groups.size();
+  for (int k = 0; k < HMP_FBS_COUNT; ++k) sizes[k] = 0;
+  sizes[HMP_FBS_FRAMES] = (int64_t)b->graph_of_frame.size();
+  sizes[HMP_FBS_GRAPHS] = (int64_t)b->frames.size();
+  sizes[HMP_FBS_MAX_GRAPH_NODES] = b->max_graph_nodes;
+  sizes[HMP_FBS_STAGING_BYTES] = n_items ? align16(n_groups * 4) + align16(n_items * HMP_FRAME_ITEM_WORDS * 4) + b->own_base + (int64_t)b->sections.size() : 0;
+  sizes[HMP_FBS_ARENA_BYTES] = b->arena_bytes;
+  sizes[HMP_FBS_ITEMS] = n_items;
+  sizes[HMP_FBS_GROUPS] = n_groups;
+  sizes[HMP_FBS_BLOCKS] = b->n_blocks;
+  sizes[HMP_FBS_NODE_TYPES] = b->n_node_types;
+  sizes[HMP_FBS_EDGE_TYPES] = b->n_edge_types;
+  sizes[HMP_FBS_TENSORS] = (int64_t)b->tensors.size() / 4;
+  return HMP_OK;
+}
+
+extern "C" int hmp_frame_batch_host_arrays(const hmp_frame_batch* b, int32_t* graph_of_frame, int64_t* node_ptr, int64_t* edge_ptr,
+                                           int64_t* tensors) {
+  if (!b) { snprintf(hmp::err_buf(), 512, "hmp_frame_batch_host_arrays: null batch"); return HMP_E_ARG; }
+  auto put = [](void* dst, const void* src, size_t bytes) { if (dst && bytes) memcpy(dst, src, bytes); };
+  put(graph_of_frame, b->graph_of_frame.data(), b->graph_of_frame.size() * 4);
+  put(node_ptr, b->node_ptr.data(), b->node_ptr.size() * 8);
+  put(edge_ptr, b->edge_ptr.data(), b->edge_ptr.size() * 8);
+  put(tensors, b->tensors.data(), b->tensors.size() * 8);
+  return HMP_OK;
+}
+
+extern "C" int hmp_frame_batch_pack(const hmp_frame_batch* b, void* staging, int64_t bytes) {
+  auto bad = [](const char* m) { snprintf(hmp::err_buf(), 512, "hmp_frame_batch_pack: %s", m); return HMP_E_ARG; };
+  if (!b || !staging) return bad("null argument");
+  if (b->items.empty()) return bad("the batch has no frame with a room and a kept object: nothing to pack");
+  const size_t groups = b->groups.size() * 4, groups_al = (size_t)align16((int64_t)groups);
+  const size_t table = b->items.size() * 4, table_al = (size_t)align16((int64_t)table);
+  const size_t header = groups_al + table_al, total = header + (size_t)b->own_base + b->sections.size();
+  if (bytes < (int64_t)total) return bad("the staging buffer is smaller than HMP_FBS_STAGING_BYTES");
+  uint8_t* p = (uint8_t*)staging;
+  memcpy(p, b->groups.data(), groups);
+  memset(p + groups, 0, groups_al - groups);
+  memcpy(p + groups_al, b->items.data(), table);
+  memset(p + groups_al + table, 0, table_al - table);
+  size_t at = header;  // the gaps between sections are alignment padding: zeroed, so that a block is a function of its frames
+  for (size_t g = 0; g < b->frames.size(); ++g) {
+    const std::vector<uint8_t>& s = b->frames[g]->sections;
+    const size_t start = header + (size_t)b->frame_base[g];
+    memset(p + at, 0, start - at);
+    if (!s.empty()) memcpy(p + start, s.data(), s.size());
+    at = start + s.size();
+  }
+  memset(p + at, 0, header + (size_t)b->own_base - at);
+  if (!b->sections.empty()) memcpy(p + header + b->own_base, b->sections.data(), b->sections.size());
+  return HMP_OK;
+}
+
+extern "C" void hmp_frame_batch_destroy(hmp_frame_batch* b) { delete b; }

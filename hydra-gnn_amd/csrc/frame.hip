@@ -12,6 +12,11 @@
 // holds unchanged.  FEAT and CLIQUE rows are `width` floats whatever the type's own width is (zeros behind it), EATTR segments are
 // plain sub-ranges, EDGE_SEG and CONST are the two kinds it adds.
 //
+// A batch of frames (hmp_frame_batch_*, frame.cpp) is the same re-addressing once more, with the frame as one more segment level:
+// every batched tensor is written by one item per (graph, segment), `batch` segments are CONST, offset vectors and labels I64.  Up to
+// 4096 items come with a group table in front of the item table; frame_expand_batch_kernel finds its item through it and writes it
+// with the code of frame_expand_kernel (frame_expand_item), so the rule above holds for both launches.
+//
 // Item kinds (words S0..S3 are byte offsets of sections in the staging block, -1: none):
 //   FEAT    x = [pos (P0 = 3 or 0 columns) | size | table[label] (P1 columns) | zeros up to width]
 //           S0 pos f64, S1 size f64, S2 label i32, S3 row index
@@ -54,15 +59,10 @@ __device__ __forceinline__ float feat_head(const double* __restrict__ pos, const
   return (float)(c < npos ? pos[3 * r + c] : size[3 * r + (c - npos)]);
 }
 
-__global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restrict__ stg, char* __restrict__ arena,
-                                                           const float* __restrict__ table, int sem_dim, int n_items) {
+// What a workgroup writes of its item I (the words behind the item lookup): both kernels below call it, so every kind is written once.
+__device__ __forceinline__ void frame_expand_item(const char* __restrict__ stg, char* __restrict__ arena, const float* __restrict__ table,
+                                                  int sem_dim, const int* __restrict__ I) {
   const int lane = threadIdx.x & 63;
-  const int* items = reinterpret_cast<const int*>(stg);
-  // the item of this workgroup: the last one whose first workgroup is not behind it (empty items share their successor's word)
-  const int b0 = lane < n_items ? items[lane * HMP_FRAME_ITEM_WORDS + HMP_FI_BLOCK0] : 0x7fffffff;
-  const int ii = __popcll(__ballot(b0 <= (int)blockIdx.x)) - 1;
-  if (ii < 0) return;
-  const int* I = items + ii * HMP_FRAME_ITEM_WORDS;
   const int kind = I[HMP_FI_KIND], rows = I[HMP_FI_ROWS], width = I[HMP_FI_WIDTH];
   const int p0 = I[HMP_FI_P0], p1 = I[HMP_FI_P1];
   const int lb = (int)blockIdx.x - I[HMP_FI_BLOCK0];
@@ -155,6 +155,36 @@ __global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restric
   }
 }
 
+__global__ __launch_bounds__(256) void frame_expand_kernel(const char* __restrict__ stg, char* __restrict__ arena,
+                                                           const float* __restrict__ table, int sem_dim, int n_items) {
+  const int lane = threadIdx.x & 63;
+  const int* items = reinterpret_cast<const int*>(stg);
+  // the item of this workgroup: the last one whose first workgroup is not behind it (empty items share their successor's word)
+  const int b0 = lane < n_items ? items[lane * HMP_FRAME_ITEM_WORDS + HMP_FI_BLOCK0] : 0x7fffffff;
+  const int ii = __popcll(__ballot(b0 <= (int)blockIdx.x)) - 1;
+  if (ii < 0) return;
+  frame_expand_item(stg, arena, table, sem_dim, items + ii * HMP_FRAME_ITEM_WORDS);
+}
+
+// A batch block (hmp_frame_batch_pack): [group table | item table | sections], up to 64 groups of 64 items.  The same rule picks
+// the group and then the item inside it -- the last one whose first workgroup is not behind this one -- with one 64-lane load and
+// one ballot each: the table's prefix words never decrease, so the last such item lies in the last such group.  Both results are
+// wave-uniform; lanes past the tables read INT_MAX.
+__global__ __launch_bounds__(256) void frame_expand_batch_kernel(const char* __restrict__ stg, char* __restrict__ arena,
+                                                                 const float* __restrict__ table, int sem_dim, int n_items) {
+  const int lane = threadIdx.x & 63;
+  const int n_groups = (n_items + HMP_FRAME_MAX_ITEMS - 1) / HMP_FRAME_MAX_ITEMS;
+  const int* groups = reinterpret_cast<const int*>(stg);
+  const int* items = reinterpret_cast<const int*>(stg + ((n_groups * 4 + 15) & ~15));
+  const int g0 = lane < n_groups ? groups[lane] : 0x7fffffff;
+  const int gi = __popcll(__ballot(g0 <= (int)blockIdx.x)) - 1;
+  if (gi < 0) return;
+  const int it = gi * HMP_FRAME_MAX_ITEMS + lane;
+  const int b0 = it < n_items ? items[it * HMP_FRAME_ITEM_WORDS + HMP_FI_BLOCK0] : 0x7fffffff;
+  const int ii = gi * HMP_FRAME_MAX_ITEMS + __popcll(__ballot(b0 <= (int)blockIdx.x)) - 1;
+  frame_expand_item(stg, arena, table, sem_dim, items + ii * HMP_FRAME_ITEM_WORDS);
+}
+
 }  // namespace hmp
 
 using namespace hmp;
@@ -168,6 +198,20 @@ extern "C" int hmp_frame_expand(const void* d_staging, void* d_arena, const floa
   HMP_CHECK_ARG(sem_dim >= 0 && (sem_dim == 0 || (d_sem_table && ((uintptr_t)d_sem_table & 7) == 0)),
                 "hmp_frame_expand: sem_dim > 0 needs the resident float32 table, 8-byte aligned");
   hipLaunchKernelGGL(frame_expand_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, (const char*)d_staging, (char*)d_arena,
+                     d_sem_table, sem_dim, n_items);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+extern "C" int hmp_frame_expand_batch(const void* d_staging, void* d_arena, const float* d_sem_table, int32_t sem_dim, int32_t n_items,
+                                      int32_t n_blocks, void* stream) {
+  HMP_CHECK_ARG(d_staging && d_arena && (((uintptr_t)d_staging | (uintptr_t)d_arena) & 15) == 0,
+                "hmp_frame_expand_batch: the staging block and the arena must be 16-byte aligned device buffers");
+  HMP_CHECK_ARG(n_items >= 1 && n_items <= HMP_FRAME_BATCH_MAX_ITEMS && n_blocks >= 1,
+                "hmp_frame_expand_batch: n_items in [1, %d] and n_blocks >= 1 (hmp_frame_batch_sizes)", HMP_FRAME_BATCH_MAX_ITEMS);
+  HMP_CHECK_ARG(sem_dim >= 0 && (sem_dim == 0 || (d_sem_table && ((uintptr_t)d_sem_table & 7) == 0)),
+                "hmp_frame_expand_batch: sem_dim > 0 needs the resident float32 table, 8-byte aligned");
+  hipLaunchKernelGGL(frame_expand_batch_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream, (const char*)d_staging, (char*)d_arena,
                      d_sem_table, sem_dim, n_items);
   HMP_LAUNCH_CHECK();
   return HMP_OK;

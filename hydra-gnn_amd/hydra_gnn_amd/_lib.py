@@ -276,6 +276,13 @@ SIGNATURES = {
     "hmp_frame_pack": (C.c_int, [_VP, _VP, _I64]),
     "hmp_frame_destroy": (None, [_VP]),
     "hmp_frame_expand": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "hmp_frame_batch_build": (C.c_int, [_I32, _VP, _I32, _VP, C.POINTER(_VP)]),
+    "hmp_frame_batch_items_needed": (C.c_int, [_VP, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
+    "hmp_frame_batch_sizes": (C.c_int, [_VP, _VP]),
+    "hmp_frame_batch_host_arrays": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "hmp_frame_batch_pack": (C.c_int, [_VP, _VP, _I64]),
+    "hmp_frame_batch_destroy": (None, [_VP]),
+    "hmp_frame_expand_batch": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
 }
 
 # include/hydra_mp.h section 14: indices of hmp_frame_sizes, words of an item of the staging block's table
@@ -286,6 +293,12 @@ FI_KIND, FI_TENSOR, FI_ROWS, FI_WIDTH, FI_DST, FI_S0, FI_S1, FI_S2, FI_S3, FI_P0
 FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE, FK_EDGE_SEG, FK_CONST = range(8)
 FT_HTREE, FT_COUNT = 16, 45
 FT_HOMOG, FT_HOMOG_COUNT = 45, 9  # the tensors of a homogeneous frame (hmp_frame_build_homogeneous)
+# batches of frames (hmp_frame_batch_*): forms, limits, indices of hmp_frame_batch_sizes, the tensors a batch adds
+FB_COLLATED, FB_STORE = 0, 1
+FRAME_MAX_ITEMS, FRAME_BATCH_MAX_ITEMS = 64, 4096
+(FBS_FRAMES, FBS_GRAPHS, FBS_MAX_GRAPH_NODES, FBS_STAGING_BYTES, FBS_ARENA_BYTES, FBS_ITEMS, FBS_GROUPS, FBS_BLOCKS, FBS_NODE_TYPES,
+ FBS_EDGE_TYPES, FBS_TENSORS, FBS_COUNT) = range(12)
+FT_BATCH, FTB_BATCH, FTB_NODE_PTR, FTB_EDGE_PTR, FTB_Y, FT_BATCH_COUNT = 54, 0, 6, 12, 27, 33
 
 ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
 

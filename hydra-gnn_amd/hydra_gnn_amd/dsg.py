@@ -288,6 +288,101 @@ def save_frame_file(path: str, ids, layer, pos, bb_min, bb_max, label, edges, th
             f.write(a.tobytes())
 
 
+# ---- batches of frames (include/hydra_mp.h section 14, "batches of frames") ------------------------------------------------------
+def _node_type_names(htree: bool, homogeneous: bool):
+    return ["node"] if homogeneous else (list(_HTREE_STORES) if htree else ["objects", "rooms"])
+
+
+def _edge_type_names(htree: bool, homogeneous: bool, relative_pos: bool = False):
+    """edge types of a batch in the order of ``hmp_frame_batch_host_arrays``'s ``edge_ptr``"""
+    if homogeneous:
+        return ["edge_index", "init_edge_index", "pool_edge_index"] if htree else ["edge_index"]
+    return [k for k, a in _FRAME_TENSORS[_lib.FT_HTREE if htree else 0:_lib.FT_COUNT if htree else _lib.FT_HTREE] if a == "edge_index"]
+
+
+def _label_pointers(y, n_frames: int, arrays):
+    """(ctypes array of the frames' int64 label vectors or None, what keeps them alive)"""
+    if y is None:
+        return None, None
+    if len(y) != n_frames:
+        raise _lib.HydraMPError(f"y holds {len(y)} label vectors for {n_frames} frames")
+    keep = []
+    for i, v in enumerate(y):
+        v = np.ascontiguousarray(v, dtype=np.int64).reshape(-1)
+        if v.size != arrays[i][0].size:
+            raise _lib.HydraMPError(f"y[{i}] holds {v.size} labels for the {arrays[i][0].size} nodes of its frame")
+        keep.append(v)
+    return (C.c_void_p * n_frames)(*[v.ctypes.data if v.size else None for v in keep]), keep
+
+
+def _batch_build(lib, handles, form: int, y_ptrs) -> C.c_void_p:
+    hb = C.c_void_p()
+    _lib.check(lib.hmp_frame_batch_build(len(handles), (C.c_void_p * max(len(handles), 1))(*handles), int(form), y_ptrs, C.byref(hb)))
+    return hb
+
+
+def _batch_host_arrays(lib, hb) -> Dict[str, object]:
+    """``hmp_frame_batch_sizes`` and ``hmp_frame_batch_host_arrays`` of a built batch"""
+    sz = np.zeros(_lib.FBS_COUNT, dtype=np.int64)
+    _lib.check(lib.hmp_frame_batch_sizes(hb, sz.ctypes.data))
+    G = int(sz[_lib.FBS_GRAPHS])
+    out = {"sizes": sz, "num_graphs": G, "max_graph_nodes": int(sz[_lib.FBS_MAX_GRAPH_NODES]),
+           "graph_of_frame": np.zeros(int(sz[_lib.FBS_FRAMES]), np.int32),
+           "node_ptr": np.zeros((int(sz[_lib.FBS_NODE_TYPES]), G + 1), np.int64),
+           "edge_ptr": np.zeros((int(sz[_lib.FBS_EDGE_TYPES]), G + 1), np.int64),
+           "tensors": np.zeros((int(sz[_lib.FBS_TENSORS]), 4), np.int64)}
+    p = lambda k: out[k].ctypes.data if out[k].size else None
+    _lib.check(lib.hmp_frame_batch_host_arrays(hb, p("graph_of_frame"), p("node_ptr"), p("edge_ptr"), p("tensors")))
+    return out
+
+
+def frame_batch_host_stage(frames, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2, htree: bool = False,
+                           relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0, clique_dim: Optional[int] = None,
+                           homogeneous: bool = False, form: int = _lib.FB_COLLATED, y=None) -> Dict[str, object]:
+    """The host stage of ``FramePipeline.convert_batch`` / ``GraphStore.from_frames`` on its own (no GPU involved; the batch
+    counterpart of ``frame_host_stage``).  ``frames``: a sequence of the 7-tuples ``frame_host_stage`` takes; ``form``:
+    ``_lib.FB_COLLATED`` or ``_lib.FB_STORE``; ``y``: one int64 label vector per frame, aligned with its input arrays.  Returns
+    ``sizes`` (``hmp_frame_batch_sizes``), ``num_graphs``, ``max_graph_nodes``, ``graph_of_frame``, ``node_ptr`` / ``edge_ptr``
+    (int64 ``[types, graphs + 1]``), ``tensors`` (int64 ``[n, 4]``: number, arena offset, rows, width), ``frames`` (per frame
+    ``kept`` / ``dropped`` / ``rooms``), and the packed ``block`` (uint8) with its ``groups`` and ``items`` tables."""
+    lib = _lib.load()
+    built, handles = [], []
+    try:
+        for fr in frames:
+            arrays, n, m = _frame_args(*fr)
+            built.append(arrays)
+            handles.append(_frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels,
+                                        clique_dim, homogeneous))
+        y_ptrs, keep = _label_pointers(y, len(handles), built)
+        hb = _batch_build(lib, handles, form, y_ptrs)
+        try:
+            out = _batch_host_arrays(lib, hb)
+            sz = out["sizes"]
+            out["frames"] = []
+            fsz = np.zeros(_lib.FS_COUNT, dtype=np.int64)
+            for h in handles:
+                _lib.check(lib.hmp_frame_sizes(h, fsz.ctypes.data))
+                kept, dropped, rooms = (np.zeros(int(fsz[k]), np.int32) for k in (_lib.FS_KEPT, _lib.FS_DROPPED, _lib.FS_ROOMS))
+                q = lambda a: a.ctypes.data if a.size else None
+                _lib.check(lib.hmp_frame_host_arrays(h, q(kept), None, q(dropped), q(rooms), None, None, None))
+                out["frames"].append({"kept": kept, "dropped": dropped, "rooms": rooms, "items": int(fsz[_lib.FS_ITEMS])})
+            n_items, n_groups = int(sz[_lib.FBS_ITEMS]), int(sz[_lib.FBS_GROUPS])
+            block = np.zeros(int(sz[_lib.FBS_STAGING_BYTES]), dtype=np.uint8)
+            if n_items:
+                _lib.check(lib.hmp_frame_batch_pack(hb, block.ctypes.data, block.size))
+            at = (n_groups * 4 + 15) & ~15
+            out["block"] = block
+            out["groups"] = block[: n_groups * 4].view(np.int32).copy()
+            out["items"] = block[at: at + n_items * _lib.FRAME_ITEM_WORDS * 4].view(np.int32).reshape(n_items, _lib.FRAME_ITEM_WORDS).copy()
+            del keep
+        finally:
+            lib.hmp_frame_batch_destroy(hb)
+    finally:
+        for h in handles:
+            lib.hmp_frame_destroy(h)
+    return out
+
+
 class FramePipeline:
     """``GnnModel.convert_graph`` after the JSON step as ONE native host stage, ONE host-to-device copy and ONE launch.
 
@@ -317,6 +412,10 @@ class FramePipeline:
     ``edge_type`` of the ten tree edge types, ``init_edge_index``, ``pool_edge_index``, ``room_mask``, ``object_mask``).  The masks
     are ``torch.bool`` views of arena bytes; a frame carries no ``y``.  ``info["room_ids"]`` is in the order of the ``room_mask``
     rows.  Everything said above about views, fresh objects, streams and ``None`` holds for it.
+
+    ``convert_batch(frames, y=None)`` converts MANY frames with one host stage, one upload and one launch into the collated batch
+    (``data.collate`` / ``data.collate_homogeneous`` of the single results), in every mode above; ``store.GraphStore.from_frames``
+    builds a device-resident store the same way.
     """
 
     def __init__(self, device="cuda:0", semantic_table=None, htree: bool = False, relative_pos: bool = False,
@@ -345,6 +444,7 @@ class FramePipeline:
         self._pinned, self._pinned_np, self._events, self._slot = [None, None], [None, None], [None, None], 0
         self._d_staging = self._arena = self._arena_f32 = self._arena_i64 = self._arena_bool = None
         self._stream = None  # hipStream_t of the first convert that enqueued work
+        self._batch_max_items = _lib.FRAME_BATCH_MAX_ITEMS  # items of one convert_batch launch
 
     def _ensure(self, staging_bytes: int, arena_bytes: int) -> None:
         if self._table is None and self._table_host is not None:
@@ -363,6 +463,32 @@ class FramePipeline:
             self._arena_f32, self._arena_i64 = self._arena.view(torch.float32), self._arena.view(torch.int64)
             self._arena_bool = self._arena.view(torch.bool)
 
+    def _stage_and_expand(self, pack, expand: str, h, staging_bytes: int, arena_bytes: int, n_items: int, n_blocks: int) -> int:
+        """The device half of ``convert`` / ``convert_batch``: ``pack`` the block of ``h`` into the next pinned buffer, ONE upload, ONE
+        launch of ``expand`` on the pipeline's stream.  Returns the pinned slot that holds the block."""
+        if torch.cuda.current_device() != self.device.index:
+            raise _lib.HydraMPError(f"FramePipeline.convert: the pipeline lives on {self.device}, the current device is "
+                                    f"cuda:{torch.cuda.current_device()}")
+        stream = _lib.stream_ptr()
+        if self._stream is None:
+            self._stream = stream
+        elif stream != self._stream:
+            raise _lib.HydraMPError("FramePipeline.convert: the current stream is not the stream of this pipeline's earlier frames; "
+                                    "its staging buffer and arena are ordered by one stream (keep a pipeline per stream)")
+        self._ensure(staging_bytes, arena_bytes)
+        lib = self._lib
+        slot = self._slot = self._slot ^ 1
+        if not self._events[slot].query():  # the upload that last read this pinned buffer has not run yet
+            self._events[slot].synchronize()
+        pin = self._pinned[slot]
+        _lib.check(pack(h, pin.data_ptr(), staging_bytes))
+        self._d_staging[:staging_bytes].copy_(pin[:staging_bytes], non_blocking=True)
+        self._events[slot].record()
+        _lib.check(getattr(lib, expand)(self._d_staging.data_ptr(), self._arena.data_ptr(),
+                                        self._table.data_ptr() if self._table is not None else None, self.sem_dim, n_items, n_blocks,
+                                        stream))
+        return slot
+
     def convert_scene(self, sg: SceneGraph):
         """``convert`` on a ``SceneGraph`` (``load_dsg_json``): ``sg.adj`` is flattened to an edge array first."""
         return self.convert(*scene_arrays(sg))
@@ -378,29 +504,10 @@ class FramePipeline:
             n_items = int(sz[_lib.FS_ITEMS])
             if n_items == 0:
                 return None
-            if torch.cuda.current_device() != self.device.index:
-                raise _lib.HydraMPError(f"FramePipeline.convert: the pipeline lives on {self.device}, the current device is "
-                                        f"cuda:{torch.cuda.current_device()}")
-            stream = _lib.stream_ptr()
-            if self._stream is None:
-                self._stream = stream
-            elif stream != self._stream:
-                raise _lib.HydraMPError("FramePipeline.convert: the current stream is not the stream of this pipeline's earlier frames; "
-                                        "its staging buffer and arena are ordered by one stream (keep a pipeline per stream)")
             n_o, n_r, n_d = int(sz[_lib.FS_KEPT]), int(sz[_lib.FS_ROOMS]), int(sz[_lib.FS_DROPPED])
-            staging_bytes, arena_bytes = int(sz[_lib.FS_STAGING_BYTES]), int(sz[_lib.FS_ARENA_BYTES])
-            self._ensure(staging_bytes, arena_bytes)
+            slot = self._stage_and_expand(lib.hmp_frame_pack, "hmp_frame_expand", h, int(sz[_lib.FS_STAGING_BYTES]),
+                                          int(sz[_lib.FS_ARENA_BYTES]), n_items, int(sz[_lib.FS_BLOCKS]))
             lib = self._lib
-            slot = self._slot = self._slot ^ 1
-            if not self._events[slot].query():  # the upload that last read this pinned buffer has not run yet
-                self._events[slot].synchronize()
-            pin = self._pinned[slot]
-            _lib.check(lib.hmp_frame_pack(h, pin.data_ptr(), staging_bytes))
-            self._d_staging[:staging_bytes].copy_(pin[:staging_bytes], non_blocking=True)
-            self._events[slot].record()
-            _lib.check(lib.hmp_frame_expand(self._d_staging.data_ptr(), self._arena.data_ptr(),
-                                            self._table.data_ptr() if self._table is not None else None, self.sem_dim, n_items,
-                                            int(sz[_lib.FS_BLOCKS]), stream))
             kept, dropped, rooms = np.empty(n_o, np.int32), np.empty(n_d, np.int32), np.empty(n_r, np.int32)
             _lib.check(lib.hmp_frame_host_arrays(h, kept.ctypes.data, None, dropped.ctypes.data if n_d else None, rooms.ctypes.data,
                                                  None, None, None))
@@ -426,6 +533,129 @@ class FramePipeline:
                 t = strided(f32, (n_rows, width), (width, 1), dst >> 2)
             setattr(g[key], attr, t)
         return g, info
+
+    # ---- many frames per launch ----------------------------------------------------------------------------------------------------
+    def convert_batch(self, frames, y=None):
+        """``frames``: a sequence of the 7-tuples ``convert`` takes -> ``(batch, infos)`` with ONE host stage, ONE pinned block, ONE
+        upload and ONE launch for all of them.  ``batch`` is what ``data.collate([clone of convert(f)[0] for f in frames]).to(device)``
+        is (``homogeneous``: ``data.collate_homogeneous``), bit for bit and attribute for attribute: ``num_graphs``,
+        ``max_graph_nodes``, ``batch`` / ``ptr`` of every node type, ``ptr`` / ``ptr_version`` of every edge type.  ``y``: one int64
+        label vector per frame, aligned with the frame's input arrays; it becomes ``objects.y`` / ``rooms.y`` (H-tree: ``object.y``,
+        ``room.y``, ``object_virtual.y``, ``room_virtual.y``; homogeneous: one ``y``, -1 on clique rows).  ``infos[i]`` is ``convert``'s
+        info dict plus ``"graph"`` (the frame's position in the batch), or ``None`` for a frame without a room or a kept object, which
+        the batch skips; with no frame left the result is ``(None, infos)`` and the device is not touched.  Everything ``convert``
+        says about views of the arena, fresh tensor objects, the two pinned buffers, the one stream and the lifetime of a result
+        (until the next ``convert`` / ``convert_batch``) holds.  More items than one launch's tables hold
+        (``_lib.FRAME_BATCH_MAX_ITEMS``) is refused: convert fewer frames at once."""
+        built, infos = self._build_frames(frames)
+        try:
+            run = self._run_batch(built, y, _lib.FB_COLLATED, infos)
+        finally:
+            for h, _ in built:
+                self._lib.hmp_frame_destroy(h)
+        if run is None:
+            return None, infos
+        tensors, host = run
+        return self._collated(tensors, host), infos
+
+    def _build_frames(self, frames):
+        """host stage of every frame: ([(handle, arrays)], infos) -- the caller destroys the handles"""
+        lib, built, infos = self._lib, [], []
+        sz = self._sizes
+        try:
+            for fr in frames:
+                arrays, n, m = _frame_args(*fr)
+                h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels,
+                                 self.clique_dim, self.homogeneous)
+                built.append((h, arrays))
+                _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
+                if int(sz[_lib.FS_ITEMS]) == 0:
+                    infos.append(None)
+                    continue
+                n_o, n_r, n_d = int(sz[_lib.FS_KEPT]), int(sz[_lib.FS_ROOMS]), int(sz[_lib.FS_DROPPED])
+                kept, dropped, rooms = np.empty(n_o, np.int32), np.empty(n_d, np.int32), np.empty(n_r, np.int32)
+                _lib.check(lib.hmp_frame_host_arrays(h, kept.ctypes.data, None, dropped.ctypes.data if n_d else None, rooms.ctypes.data,
+                                                     None, None, None))
+                ids = arrays[0]
+                infos.append({"object_ids": ids[kept], "dropped_ids": ids[dropped], "room_ids": ids[rooms]})
+        except Exception:
+            for h, _ in built:
+                lib.hmp_frame_destroy(h)
+            raise
+        return built, infos
+
+    def _batch_capacity(self, handle, form: int, with_y: bool) -> int:
+        """frames with items that fit one launch's tables (``_batch_max_items``: a test hook, at most the library's limit)"""
+        per_frame, per_batch = C.c_int32(), C.c_int32()
+        _lib.check(self._lib.hmp_frame_batch_items_needed(handle, form, int(with_y), C.byref(per_frame), C.byref(per_batch)))
+        return (min(self._batch_max_items, _lib.FRAME_BATCH_MAX_ITEMS) - per_batch.value) // per_frame.value
+
+    def _run_batch(self, built, y, form: int, infos):
+        """batch host stage + upload + launch over built frames -> ({tensor number: view of the arena}, host arrays); None if no
+        frame has items.  Sets ``infos[i]["graph"]``."""
+        lib = self._lib
+        live = [i for i, info in enumerate(infos) if info is not None]
+        if not live:
+            return None
+        if len(live) > self._batch_capacity(built[live[0]][0], form, y is not None):
+            raise _lib.HydraMPError(f"FramePipeline.convert_batch: {len(live)} frames need more items than one launch's tables hold "
+                                    f"({min(self._batch_max_items, _lib.FRAME_BATCH_MAX_ITEMS)}, HMP_FRAME_BATCH_MAX_ITEMS): convert "
+                                    f"fewer frames at once")
+        y_ptrs, keep = _label_pointers(y, len(built), [a for _, a in built])
+        hb = _batch_build(lib, [h for h, _ in built], form, y_ptrs)
+        try:
+            host = _batch_host_arrays(lib, hb)
+            sz = host["sizes"]
+            self._stage_and_expand(lib.hmp_frame_batch_pack, "hmp_frame_expand_batch", hb, int(sz[_lib.FBS_STAGING_BYTES]),
+                                   int(sz[_lib.FBS_ARENA_BYTES]), int(sz[_lib.FBS_ITEMS]), int(sz[_lib.FBS_BLOCKS]))
+        finally:
+            self._lib.hmp_frame_batch_destroy(hb)
+        del keep
+        for i, g in enumerate(host["graph_of_frame"].tolist()):
+            if infos[i] is not None:
+                infos[i]["graph"] = g
+        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
+        tensors = {}
+        for t, dst, rows, width in host["tensors"].tolist():
+            name = (_FRAME_TENSORS[t][1] if t < _lib.FT_HOMOG else _HOMOG_TENSORS[t - _lib.FT_HOMOG]) if t < _lib.FT_BATCH else "ptr"
+            if name.endswith("edge_index"):
+                tensors[t] = strided(i64, (2, width), (width, 1), dst >> 3)
+            elif name.endswith("_mask"):
+                tensors[t] = strided(self._arena_bool, (rows,), (1,), dst)
+            elif name in ("x", "pos", "edge_attr"):
+                tensors[t] = strided(f32, (rows, width), (width, 1), dst >> 2)
+            else:  # label, node_ids, node_type, edge_type, batch, ptr, y
+                tensors[t] = strided(i64, (rows,), (1,), dst >> 3)
+        return tensors, host
+
+    def _collated(self, tensors, host):
+        """the views of a collated batch as the HeteroData / Data that data.collate / data.collate_homogeneous build"""
+        FB = _lib.FT_BATCH
+        if self.homogeneous:
+            d = Data()
+            for t in sorted(tensors):
+                setattr(d, "y" if t == FB + _lib.FTB_Y else _HOMOG_TENSORS[t - _lib.FT_HOMOG], tensors[t])
+            d.num_graphs = host["num_graphs"]
+            return d
+        g = HeteroData()
+        g.num_graphs = host["num_graphs"]
+        node_types = _node_type_names(self.htree, False)
+        edge_types = _edge_type_names(self.htree, False)
+        for t in node_types:
+            g[t]
+        for t in sorted(k for k in tensors if k < FB):
+            key, attr = _FRAME_TENSORS[t]
+            setattr(g[key], attr, tensors[t])
+            if attr == "edge_index":
+                g[key].ptr = tensors[FB + _lib.FTB_EDGE_PTR + edge_types.index(key)]
+                g[key].ptr_version = int(tensors[t]._version)
+        for k, t in enumerate(node_types):
+            if FB + _lib.FTB_Y + k in tensors:
+                g[t].y = tensors[FB + _lib.FTB_Y + k]
+            g[t].batch = tensors[FB + _lib.FTB_BATCH + k]
+            g[t].ptr = tensors[FB + _lib.FTB_NODE_PTR + k]
+        g.max_graph_nodes = host["max_graph_nodes"]
+        return g
 
     def _homogeneous_data(self, items) -> Data:
         """Views of the arena for the tensors of a homogeneous frame.  A tensor is written by one item per segment: its first item

@@ -56,6 +56,17 @@ class _Packed:
         self.row_bytes = int(self.data.element_size()) * (int(np.prod(self.row_shape, dtype=np.int64)) if self.row_shape else 1)
 
 
+def _packed(data: torch.Tensor, ptr: torch.Tensor, ptr_host: np.ndarray) -> _Packed:
+    """a ``_Packed`` over rows that are already back to back on the device, with their ``[G + 1]`` offsets (device and host)"""
+    pk = object.__new__(_Packed)
+    ptr_host = np.ascontiguousarray(ptr_host, dtype=np.int64)
+    pk.counts, pk.ptr_host = np.diff(ptr_host), ptr_host
+    pk.data, pk.ptr = data, ptr
+    pk.row_shape = tuple(data.shape[1:])
+    pk.row_bytes = int(data.element_size()) * (int(np.prod(pk.row_shape, dtype=np.int64)) if pk.row_shape else 1)
+    return pk
+
+
 class GraphStore:
     def __init__(self, graphs: Sequence, device="cuda:0"):
         """``graphs``: a list of ``HeteroData``, or a list of homogeneous ``Data`` (classified by name as PyG and
@@ -146,6 +157,103 @@ class GraphStore:
                 self.edge_rows.setdefault(e, {})[k] = pk
                 if k == "edge_attr":
                     self.edge_attr[e] = pk
+
+    @classmethod
+    def from_frames(cls, pipeline, frames, y=None):
+        """``(store, infos)``: a store over the frames that have a room and a kept object, straight from scene-graph arrays -- what
+        ``GraphStore([clone of pipeline.convert(*f)[0] (+ y) for f in frames])`` holds, packed array for packed array and offset
+        vector for offset vector, without the per-frame launches, clones and ``torch.cat``s: the frames go through the pipeline's
+        batch path in store form (``HMP_FB_STORE``: rows back to back, graph-LOCAL edge lists, ``[G + 1]`` offsets; one host stage,
+        one upload and one launch per chunk).  ``frames`` / ``y`` / ``infos`` as ``FramePipeline.convert_batch`` (``infos[i]["graph"]``
+        is the frame's index in the store).  Frames beyond the capacity of one launch's tables are converted in chunks, and the
+        chunks are joined with ``torch.cat`` here: once per dataset, at construction, not on a hot path.  The store owns COPIES:
+        nothing it holds is a view of the pipeline's arena, so the pipeline stays free for other frames."""
+        from . import dsg
+
+        lib = pipeline._lib
+        built, infos = pipeline._build_frames(frames)
+        try:
+            live = [i for i, info in enumerate(infos) if info is not None]
+            if not live:
+                raise _lib.HydraMPError("GraphStore.from_frames: no frame has a room and a kept object")
+            cap = pipeline._batch_capacity(built[live[0]][0], _lib.FB_STORE, y is not None)
+            if cap < 1:
+                raise _lib.HydraMPError("GraphStore.from_frames: one frame does not fit the launch's tables")
+            chunks = []
+            for c in range(0, len(live), cap):
+                idx = live[c:c + cap]
+                sub_infos = [infos[i] for i in idx]
+                tensors, host = pipeline._run_batch([built[i] for i in idx], None if y is None else [y[i] for i in idx], _lib.FB_STORE,
+                                                    sub_infos)
+                for info in sub_infos:
+                    info["graph"] += c
+                chunks.append(({t: v.clone() for t, v in tensors.items()}, host))  # the arena is rewritten by the next chunk
+        finally:
+            for h, _ in built:
+                lib.hmp_frame_destroy(h)
+        FB = _lib.FT_BATCH
+
+        def joined_ptr(t, host_key, k):
+            dev = torch.cat([ch[t] if i == 0 else ch[t][1:] + int(sum(c[1][host_key][k][-1] for c in chunks[:i]))
+                             for i, (ch, _) in enumerate(chunks)])
+            hst = np.concatenate([h[host_key][k] if i == 0 else h[host_key][k][1:] + sum(c[1][host_key][k][-1] for c in chunks[:i])
+                                  for i, (_, h) in enumerate(chunks)]).astype(np.int64)
+            return dev, hst
+
+        data = {t: torch.cat([ch[t] for ch, _ in chunks], dim=1 if v.dim() == 2 and v.dtype == torch.int64 else 0) if len(chunks) > 1 else v
+                for t, v in chunks[0][0].items() if not FB + _lib.FTB_NODE_PTR <= t < FB + _lib.FTB_Y}
+        ht, homog = pipeline.htree, pipeline.homogeneous
+        node_names, edge_names = dsg._node_type_names(ht, homog), dsg._edge_type_names(ht, homog)
+        node_ptr = [joined_ptr(FB + _lib.FTB_NODE_PTR + k, "node_ptr", k) for k in range(len(node_names))]
+        edge_ptr = [joined_ptr(FB + _lib.FTB_EDGE_PTR + k, "edge_ptr", k) for k in range(len(edge_names))]
+
+        self = object.__new__(cls)
+        self.device, self.lib = pipeline.device, _lib.require_device()
+        self.n_graphs, self.homogeneous = len(live), homog
+        self._stage = self._stage_dev = self._copied = None
+        self.edge_rows, self.edge_index, self.edge_ptr, self.edge_ptr_host, self.edge_attr = {}, {}, {}, {}, {}
+        self.count_only = {t: False for t in ([HOMO_NODE] if homog else node_names)}
+        if homog:
+            names = {t: ("y" if t == FB + _lib.FTB_Y else dsg._HOMOG_TENSORS[t - _lib.FT_HOMOG]) for t in data}
+            self.homo_keys = [names[t] for t in sorted(data)]  # the attribute order of the pipeline's Data, then y
+            self.node_types, self.node_counts = [HOMO_NODE], {HOMO_NODE: np.diff(node_ptr[0][1])}
+            self.node_attrs, self.edge_types, self.edge_name = {HOMO_NODE: {}}, [], {}
+            e0 = homo_edge_type("edge_index")
+            for t in sorted(data):
+                k = names[t]
+                if "index" in k:
+                    e = homo_edge_type(k)
+                    self.edge_types.append(e)
+                    self.edge_name[e] = k
+                    self.edge_index[e] = data[t]
+                    self.edge_ptr[e], self.edge_ptr_host[e] = edge_ptr[edge_names.index(k)]
+                elif k not in _HOMO_EDGE_ROWS:
+                    self.node_attrs[HOMO_NODE][k] = _packed(data[t], *node_ptr[0])
+            for t in sorted(data):
+                if names[t] in _HOMO_EDGE_ROWS:
+                    pk = _packed(data[t], self.edge_ptr[e0], self.edge_ptr_host[e0])
+                    self.edge_rows.setdefault(e0, {})[names[t]] = pk
+                    if names[t] == "edge_attr":
+                        self.edge_attr[e0] = pk
+            return self, infos
+        self.node_types, self.edge_types = list(node_names), list(edge_names)
+        self.node_attrs = {t: {} for t in node_names}
+        self.node_counts = {t: np.diff(node_ptr[k][1]) for k, t in enumerate(node_names)}
+        for t in sorted(data):
+            if t >= FB:
+                k = t - FB - _lib.FTB_Y
+                self.node_attrs[node_names[k]]["y"] = _packed(data[t], *node_ptr[k])
+                continue
+            key, attr = dsg._FRAME_TENSORS[t]
+            if attr == "edge_index":
+                self.edge_index[key] = data[t]
+                self.edge_ptr[key], self.edge_ptr_host[key] = edge_ptr[edge_names.index(key)]
+            elif attr == "edge_attr":
+                self.edge_attr[key] = _packed(data[t], self.edge_ptr[key], self.edge_ptr_host[key])
+                self.edge_rows[key] = {"edge_attr": self.edge_attr[key]}
+            else:
+                self.node_attrs[key][attr] = _packed(data[t], *node_ptr[node_names.index(key)])
+        return self, infos
 
     # ---------------------------------------------------------------------------------------------------------------
     def collate(self, ids: Sequence[int]):

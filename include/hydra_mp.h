@@ -47,7 +47,9 @@ extern "C" {
  *    section 14: hmp_frame_build / hmp_frame_sizes / hmp_frame_host_arrays / hmp_frame_pack / hmp_frame_destroy (host) and
  *    hmp_frame_expand (one launch): scene-graph arrays to model input.  New entries, no struct was added or changed layout;
  *    hmp_frame_build_homogeneous: the same frame laid out as the homogeneous Data (item kinds HMP_FK_EDGE_SEG / HMP_FK_CONST, output
- *    tensors from HMP_FT_HOMOG on).  A new entry; the six entries above, HMP_FRAME_ITEM_WORDS and every earlier number are unchanged */
+ *    tensors from HMP_FT_HOMOG on).  A new entry; the six entries above, HMP_FRAME_ITEM_WORDS and every earlier number are unchanged;
+ *    hmp_frame_batch_build / _items_needed / _sizes / _host_arrays / _pack / _destroy and hmp_frame_expand_batch: many frames per
+ *    block and launch (output tensors from HMP_FT_BATCH on).  New entries; a single frame packs what it packed, nothing above changed */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -900,6 +902,80 @@ void hmp_frame_destroy(hmp_frame* f);
  *   - every launch that uses the same staging block or arena runs on ONE stream (they are ordered by it alone). */
 int hmp_frame_expand(const void* d_staging, void* d_arena, const float* d_sem_table, int32_t sem_dim, int32_t n_items,
                      int32_t n_blocks, void* stream);
+
+/* ---- batches of frames: K frames -> ONE block, ONE upload, ONE launch -> the collated batch the models read, or the packed arrays
+ *      of a GraphStore, as views of one arena (csrc/frame.cpp, csrc/frame.hip; dsg.FramePipeline.convert_batch,
+ *      store.GraphStore.from_frames).
+ *
+ *     hmp_frame_batch_build takes frames that hmp_frame_build / hmp_frame_build_homogeneous made, all with the SAME configuration
+ *     (typed / homogeneous, htree, relative_pos, sem_dim, n_labels, clique_dim; anything else is HMP_E_ARG), and keeps pointers to
+ *     them: they must outlive the batch.  A frame with HMP_FS_ITEMS = 0 is skipped (graph_of_frame = -1); the others are the
+ *     graphs 0..G-1 in input order.  A batch without a graph has 0 items: nothing to pack, nothing to launch.
+ *
+ *     HMP_FB_COLLATED is data.collate (typed) / data.collate_homogeneous (homogeneous) of the G single results: every tensor of a
+ *     frame becomes the concatenation over the graphs, every edge list has its endpoints shifted by the graph's row offsets of the
+ *     endpoint types (homogeneous: the graph's node offset, for edge_index, init_edge_index and pool_edge_index alike).  Typed
+ *     batches add the int64 `batch` and `ptr` [G + 1] of every node type and the `ptr` of every edge type.  HMP_FB_STORE is the
+ *     same concatenations with graph-local endpoints (what GraphStore keeps): no `batch`, and the offset vectors of the node set(s)
+ *     and of every edge list for the homogeneous layout too.
+ *
+ *     Labels: y[i] = int64 [n] aligned with the INPUT arrays of frame i (y null: no labels; otherwise every frame has one).
+ *     Typed baseline: objects.y / rooms.y gathered through kept / rooms; H-tree: object.y / room.y through kept[object_orig] /
+ *     rooms[room_orig], object_virtual.y / room_virtual.y as the baseline's; homogeneous: ONE y over all nodes in store order, -1 on
+ *     the clique rows.  They are HMP_FK_I64 items with a row-index section (and HMP_FK_CONST -1); no kind is added.
+ *
+ *     The item table is the frames' items re-addressed, one item per (graph, segment), tensor by tensor and graph by graph inside a
+ *     tensor: sections rebased to the batch block, HMP_FI_DST = where the segment starts inside the batched tensor (the first
+ *     segment's is the tensor's, 16-byte aligned; segments follow one another), an edge list = HMP_FK_EDGE_SEG with the batched
+ *     tensor's pitch and the graph's two shifts, `batch` segments = HMP_FK_CONST with the graph number, offset vectors = HMP_FK_I64
+ *     from an int64 section.  An empty segment keeps its item and shares its successor's HMP_FI_BLOCK0 (trailing ones: the block
+ *     count).  Offsets are int32: a block or an arena beyond 2^31 - 1 bytes is refused.
+ *
+ *     Block: [group table: one int32 per HMP_FRAME_MAX_ITEMS items = HMP_FI_BLOCK0 of the group's first item, padded to 16 bytes]
+ *            [item table: n_items x HMP_FRAME_ITEM_WORDS int32, padded to 16 bytes][sections, each 16-byte aligned: the frames' own,
+ *            graph by graph, then the offset vectors, the label vectors and their row-index vectors].  At most
+ *     HMP_FRAME_MAX_ITEMS groups, so HMP_FRAME_BATCH_MAX_ITEMS items; more is refused (the message names the limit). */
+typedef struct hmp_frame_batch hmp_frame_batch; /* opaque */
+#define HMP_FB_COLLATED 0
+#define HMP_FB_STORE 1
+#define HMP_FRAME_BATCH_MAX_ITEMS 4096
+int hmp_frame_batch_build(int32_t n_frames, const hmp_frame* const* frames, int32_t form, const int64_t* const* y, hmp_frame_batch** out);
+/* items a frame of f's configuration adds to a batch, and the items of the batch itself: what a caller cuts chunks by */
+int hmp_frame_batch_items_needed(const hmp_frame* f, int32_t form, int32_t with_y, int32_t* per_frame, int32_t* per_batch);
+/* sizes[HMP_FBS_COUNT] */
+#define HMP_FBS_FRAMES 0          /* input frames */
+#define HMP_FBS_GRAPHS 1          /* frames with items: num_graphs */
+#define HMP_FBS_MAX_GRAPH_NODES 2 /* most rows of one node type (homogeneous: nodes) in one graph */
+#define HMP_FBS_STAGING_BYTES 3   /* what hmp_frame_batch_pack writes */
+#define HMP_FBS_ARENA_BYTES 4     /* what hmp_frame_expand_batch writes */
+#define HMP_FBS_ITEMS 5
+#define HMP_FBS_GROUPS 6
+#define HMP_FBS_BLOCKS 7          /* workgroups of the launch */
+#define HMP_FBS_NODE_TYPES 8      /* typed: 2 / 6 (store order); homogeneous: 1 */
+#define HMP_FBS_EDGE_TYPES 9      /* typed: 4 / 15 (tensor order); homogeneous: edge_index (, init_edge_index, pool_edge_index) */
+#define HMP_FBS_TENSORS 10
+#define HMP_FBS_COUNT 11
+int hmp_frame_batch_sizes(const hmp_frame_batch* b, int64_t* sizes);
+/* every pointer may be null: graph_of_frame [FRAMES]; node_ptr [NODE_TYPES][GRAPHS + 1] and edge_ptr [EDGE_TYPES][GRAPHS + 1], the
+ * row / column offsets of every graph (data.collate's `ptr`, GraphStore's ptr_host / edge_ptr_host); tensors [TENSORS][4] = tensor
+ * number, byte offset in the arena, rows, width (an edge list: 2, columns) of every batched tensor.  kept / dropped / rooms of a
+ * frame come from hmp_frame_host_arrays of that frame, as before. */
+int hmp_frame_batch_host_arrays(const hmp_frame_batch* b, int32_t* graph_of_frame, int64_t* node_ptr, int64_t* edge_ptr, int64_t* tensors);
+int hmp_frame_batch_pack(const hmp_frame_batch* b, void* staging, int64_t bytes);
+void hmp_frame_batch_destroy(hmp_frame_batch* b);
+/* tensors a batch adds, behind the frames' own: HMP_FT_BATCH + HMP_FTB_BATCH + k = `batch` of node type k, + HMP_FTB_NODE_PTR + k =
+ * its `ptr`, + HMP_FTB_EDGE_PTR + k = `ptr` of edge type k, + HMP_FTB_Y + k = y of node type k (homogeneous: k = 0 only) */
+#define HMP_FT_BATCH (HMP_FT_HOMOG + HMP_FT_HOMOG_COUNT)
+#define HMP_FTB_BATCH 0
+#define HMP_FTB_NODE_PTR 6
+#define HMP_FTB_EDGE_PTR 12
+#define HMP_FTB_Y 27
+#define HMP_FT_BATCH_COUNT 33
+/* hmp_frame_expand for a batch block: ONE launch of frame_expand_batch_kernel, which finds a workgroup's item through the group
+ * table (two dependent 64-lane loads, two ballots) and writes it with the same code as hmp_frame_expand.  The same arguments, the
+ * same three things owed by the caller, the same refusals with n_items in [1, HMP_FRAME_BATCH_MAX_ITEMS]. */
+int hmp_frame_expand_batch(const void* d_staging, void* d_arena, const float* d_sem_table, int32_t sem_dim, int32_t n_items,
+                           int32_t n_blocks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,331 @@
+"""Shared cases of the frame-batch tests (tests/test_frame_batch_host.py, tests/test_gpu_frame_batch.py,
+tests/test_gpu_frame_store.py): the frame list, label vectors, the per-frame results of the existing path on the CPU with the
+committed collation applied to them (the comparison), and a numpy execution of a packed batch block -- what the one launch of
+``hmp_frame_expand_batch`` is specified to write, item by item, including the two-level item lookup."""
+import numpy as np
+import torch
+
+import _frame_cases as fc
+from hydra_gnn_amd import _lib, data as hdata, dsg, htree
+
+INT_MAX = 0x7FFFFFFF
+CLIQUE_DIM = 6
+# 5 graphs and one skipped frame; edge types that are empty in some frames and not in others
+FRAME_NAMES = ["special", (1, 1), "no_room", (7, 2), "fixture", (65, 1)]
+# name -> (homogeneous, htree, relative_pos, sem)
+MODES = {"typed": (False, False, False, False), "typed_htree": (False, True, False, False), "homog": (True, False, False, False),
+         "homog_htree": (True, True, False, False), "typed_relative_pos": (False, False, True, False),
+         "typed_sem300": (False, False, False, True), "homog_htree_sem300": (True, True, False, True)}
+
+
+def frame(name):
+    if name == "no_room":  # the (7, 2) frame without its rooms: nothing a model can run on
+        ids, layer, pos, bb_min, bb_max, label, edges = fc.frame((7, 2))
+        keep = layer != dsg.ROOMS
+        return tuple(a[keep] for a in (ids, layer, pos, bb_min, bb_max, label)) + (edges,)
+    return fc.frame(name)
+
+
+def frames(names=FRAME_NAMES):
+    return [frame(n) for n in names]
+
+
+def labels(arrays, salt=0):
+    """an int64 label per INPUT node, different for every node so that a wrong gather shows"""
+    n = arrays[0].size
+    return (np.arange(n, dtype=np.int64) * 7 + 3 + salt) % 1009
+
+
+def host_kwargs(mode):
+    homog, ht, rel, sem = MODES[mode]
+    tn, mn, mo = fc.THRESHOLDS
+    return dict(threshold_near=tn, max_near=mn, max_on=mo, htree=ht, relative_pos=rel, sem_dim=300 if sem else 0,
+                n_labels=fc.N_LABELS if sem else 0, clique_dim=CLIQUE_DIM if ht else None, homogeneous=homog)
+
+
+def pipeline_kwargs(mode):
+    homog, ht, rel, sem = MODES[mode]
+    return dict(semantic_table=fc.semantic_table() if sem else None, htree=ht, relative_pos=rel, clique_dim=CLIQUE_DIM if ht else None,
+                homogeneous=homog)
+
+
+# ---- the comparison: the existing path per frame, then the committed collation -------------------------------------------------
+def attach_labels(typed, y, kept, rooms, htree_mode):
+    """``y`` (per input node) on a typed single-frame result, as the dataset code attaches it: the objects' and rooms' labels, and
+    for an H-tree what ``htree.generate_htree`` copies (leaves through object_orig / room_orig = the pool edges' second row)"""
+    yo, yr = torch.from_numpy(y[kept]), torch.from_numpy(y[rooms])
+    dev = typed["object_virtual" if htree_mode else "objects"].x.device
+    if not htree_mode:
+        typed["objects"].y, typed["rooms"].y = yo.to(dev), yr.to(dev)
+        return typed
+    typed["object"].y = yo.to(dev)[typed["object", "o_to_ov", "object_virtual"].edge_index[1]]
+    typed["object_virtual"].y = yo.to(dev)
+    typed["room"].y = yr.to(dev)[typed["room", "r_to_rv", "room_virtual"].edge_index[1]]
+    typed["room_virtual"].y = yr.to(dev)
+    return typed
+
+
+def to_homogeneous(typed, htree_mode):
+    """the committed host conversion of a typed frame (what the homogeneous models' datasets apply)"""
+    if htree_mode:
+        return hdata.heterogeneous_htree_to_homogeneous(typed)
+    d, types = hdata.heterogeneous_data_to_homogeneous(typed)
+    d.room_mask = d.node_type == types.index("rooms")
+    return d
+
+
+def kernel_clique_rows(tree, which):
+    """the clique rows in the kernel's summation order: float32 room positions added in ascending init-edge order, then divided"""
+    store = tree["object-room" if which == 2 else "room-room"]
+    rpos = tree["room_virtual"].pos.numpy()
+    x = np.zeros(tuple(store.x.shape), dtype=np.float32)
+    for q, mem in enumerate(fc.clique_members(tree, which)):
+        s = np.zeros(3, dtype=np.float32)
+        for k in mem:
+            s = s + rpos[k]
+        x[q, :3] = s / np.float32(max(len(mem), 1))
+    return torch.from_numpy(x)
+
+
+def cpu_graph(arrays, mode, y=None):
+    """One frame through the existing path on the CPU: ``fc.existing_frame`` (+ ``htree.generate_htree``, + the homogeneous
+    conversion), with ``y`` attached.  None for a frame without a room or a kept object.  Clique means of more than two rooms are
+    replaced by the numpy emulation of the kernel's summation order (index_add_ has none); the others are asserted equal to it."""
+    homog, ht, rel, sem = MODES[mode]
+    rog = dsg.RoomObjectGraph(fc.scene_graph(arrays))
+    if rog.objects.size == 0 or rog.rooms.size == 0:
+        return None
+    g, _ = fc.existing_frame(arrays, sem, relative_pos=rel)
+    if y is not None:
+        g["objects"].y, g["rooms"].y = torch.from_numpy(y[rog.objects]), torch.from_numpy(y[rog.rooms])
+    if ht:
+        g = htree.generate_htree(g, clique_dim=CLIQUE_DIM)
+        for which, t in ((2, "object-room"), (3, "room-room")):
+            rows = kernel_clique_rows(g, which)
+            small = torch.tensor([len(m) <= 2 for m in fc.clique_members(g, which)], dtype=torch.bool)
+            assert torch.equal(rows[small], g[t].x[small])
+            g[t].x = rows
+    return to_homogeneous(g, ht) if homog else g
+
+
+def collate(graphs, homogeneous):
+    return hdata.collate_homogeneous(graphs) if homogeneous else hdata.collate(graphs)
+
+
+def batch_tensor_name(t, mode):
+    """(store key or None, attribute) of batched tensor number ``t``"""
+    homog, ht = MODES[mode][:2]
+    FB = _lib.FT_BATCH
+    if t < _lib.FT_HOMOG:
+        return dsg._FRAME_TENSORS[t]
+    if t < FB:
+        return None, dsg._HOMOG_TENSORS[t - _lib.FT_HOMOG]
+    k = t - FB
+    nodes, edges = dsg._node_type_names(ht, homog), dsg._edge_type_names(ht, homog)
+    if k >= _lib.FTB_Y:
+        if homog and k > _lib.FTB_Y:  # one y over all nodes
+            raise IndexError(t)
+        return (None if homog else nodes[k - _lib.FTB_Y]), "y"
+    if k >= _lib.FTB_EDGE_PTR:
+        return edges[k - _lib.FTB_EDGE_PTR], "ptr"
+    if k >= _lib.FTB_NODE_PTR:
+        return nodes[k - _lib.FTB_NODE_PTR], "ptr"
+    return nodes[k], "batch"
+
+
+def _batch_tensor_numbers(mode):
+    homog = MODES[mode][0]
+    for t in range(_lib.FT_HOMOG if homog else 0, _lib.FT_BATCH + _lib.FT_BATCH_COUNT):
+        if not homog and _lib.FT_HOMOG <= t < _lib.FT_BATCH:
+            continue
+        try:
+            yield (t,) + tuple(batch_tensor_name(t, mode))
+        except IndexError:  # a node / edge type number this mode does not have
+            continue
+
+
+def tensors_of_batch(batch, mode):
+    """{tensor number: numpy array} of a collated HeteroData / Data: what an HMP_FB_COLLATED block writes"""
+    homog = MODES[mode][0]
+    out = {}
+    for t, key, attr in _batch_tensor_numbers(mode):
+        if homog:
+            if key is None and hasattr(batch, attr):  # collate_homogeneous keeps no offset vectors
+                out[t] = getattr(batch, attr).cpu().numpy()
+        elif (key in batch.node_types or key in batch.edge_types) and attr in batch[key]:
+            out[t] = getattr(batch[key], attr).cpu().numpy()
+    return out
+
+
+def store_tensors(graphs, mode):
+    """{tensor number: numpy array} of what ``GraphStore.__init__`` cats from a list of graphs (what an HMP_FB_STORE block writes):
+    rows back to back, graph-LOCAL edge lists side by side, the [G + 1] offset vectors; no ``batch``"""
+    homog = MODES[mode][0]
+    g0 = graphs[0]
+    cum = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    out = {}
+    for t, key, attr in _batch_tensor_numbers(mode):
+        if attr == "batch":
+            continue
+        if homog:
+            if attr == "ptr":
+                out[t] = cum([g.num_nodes if key == "node" else getattr(g, key).size(1) for g in graphs])
+            elif hasattr(g0, attr):
+                out[t] = torch.cat([getattr(g, attr) for g in graphs], dim=1 if "index" in attr else 0).cpu().numpy()
+        elif key in g0.node_types or key in g0.edge_types:
+            if attr == "ptr":
+                out[t] = cum([g[key].edge_index.size(1) if isinstance(key, tuple) else g[key].num_nodes for g in graphs])
+            elif attr in g0[key]:
+                out[t] = torch.cat([getattr(g[key], attr) for g in graphs], dim=1 if attr == "edge_index" else 0).cpu().numpy()
+    return out
+
+
+# ---- a numpy execution of a batch block ----------------------------------------------------------------------------------------
+def lookup(groups, items, n_items, block):
+    """the kernel's two-level item lookup for workgroup ``block``: two 64-lane loads, two ballots; tail lanes read INT_MAX"""
+    lanes = np.arange(64)
+    g0 = np.where(lanes < groups.size, groups[np.minimum(lanes, groups.size - 1)], INT_MAX)
+    gi = int((g0 <= block).sum()) - 1
+    assert gi >= 0 and bool(np.all((g0 <= block)[: gi + 1]))  # the ballot is a prefix: popcount - 1 is the last set lane
+    it = gi * 64 + lanes
+    b0 = np.where(it < n_items, items[np.minimum(it, n_items - 1), _lib.FI_BLOCK0], INT_MAX)
+    hit = b0 <= block
+    assert bool(np.all(hit[: int(hit.sum())]))
+    return gi * 64 + int(hit.sum()) - 1
+
+
+def item_blocks(item):
+    """workgroups of an item, from its own words (the rule of csrc/frame.cpp)"""
+    kind, rows, width = item[_lib.FI_KIND], item[_lib.FI_ROWS], item[_lib.FI_WIDTH]
+    if kind == _lib.FK_FEAT and width >= 32:
+        return -(-rows // 4)
+    if kind in (_lib.FK_EDGE, _lib.FK_EDGE_SEG):
+        return -(-2 * width // 256)
+    if kind in (_lib.FK_I64, _lib.FK_CONST):
+        return -(-rows // 256)
+    return -(-rows * (3 if kind in (_lib.FK_POS, _lib.FK_EATTR) else width) // 256)
+
+
+def expand_block(block, items, arena_bytes, table=None):
+    """The arena (uint8) a launch over this block is specified to write.  Every section read is checked to lie inside the block
+    (``fc.read_block``), every write to lie inside the arena, at a multiple of its element size, and no byte is written twice."""
+    arena = np.zeros(arena_bytes, dtype=np.uint8)
+    written = np.zeros(arena_bytes, dtype=bool)
+
+    def put(dst, values):
+        raw = np.ascontiguousarray(values).view(np.uint8).reshape(-1)
+        assert dst >= 0 and dst % values.dtype.itemsize == 0 and dst + raw.size <= arena_bytes, (dst, raw.size, arena_bytes)
+        assert not written[dst:dst + raw.size].any()
+        arena[dst:dst + raw.size] = raw
+        written[dst:dst + raw.size] = True
+
+    for item in items.tolist():
+        kind, tensor, rows, width, dst, s0, s1, s2, s3, p0, p1, _ = item
+        one = lambda it: fc.read_block(block, np.array([it], dtype=np.int64), table)[tensor]
+        if kind == _lib.FK_CONST:
+            assert p1 in (1, 8)
+            put(dst, np.full(rows, p0, dtype=np.int64 if p1 == 8 else np.uint8))
+        elif kind == _lib.FK_EDGE_SEG:
+            ends = one([_lib.FK_EDGE, tensor, 2, width, 0, s0, -1, -1, -1, p0, p1, 0])
+            assert 0 <= width <= s1
+            put(dst, ends[0] + s2)
+            put(dst + 8 * s1, ends[1] + s3)
+        elif kind == _lib.FK_FEAT:
+            own = p0 + 3 + p1
+            x = np.zeros((rows, width), dtype=np.float32)
+            x[:, :own] = one([kind, tensor, rows, own, 0, s0, s1, s2, s3, p0, p1, 0])
+            put(dst, x)
+        else:
+            assert kind in (_lib.FK_POS, _lib.FK_I64, _lib.FK_EATTR, _lib.FK_CLIQUE), kind  # a batch holds no plain EDGE item
+            put(dst, one(item))
+    return arena, written
+
+
+def views(arena, tensors, mode):
+    """{tensor number: array} of the batched tensors, read from an arena through the batch's tensor table"""
+    out = {}
+    for t, dst, rows, width in tensors.tolist():
+        assert dst % 16 == 0
+        attr = batch_tensor_name(t, mode)[1]
+        if attr.endswith("edge_index"):
+            out[t] = arena[dst:dst + 16 * width].view(np.int64).reshape(2, width)
+        elif attr.endswith("_mask"):
+            out[t] = arena[dst:dst + rows].view(np.bool_)
+        elif attr in ("x", "pos", "edge_attr"):
+            out[t] = arena[dst:dst + 4 * rows * width].view(np.float32).reshape(rows, width)
+        else:
+            out[t] = arena[dst:dst + 8 * rows].view(np.int64)
+    return out
+
+
+# ---- the pipeline's own single-frame path on the device: what the batched path must reproduce bit for bit ----------------------
+def class_labels(arrays, salt=0):
+    """labels in [0, 26): what a 26-class model trains on"""
+    return labels(arrays, salt) % 26
+
+
+def homogeneous_labels(d, y, info, ids):
+    """the one ``y`` of a homogeneous frame ``d``: the object and room rows (the masks' rows in a baseline frame: node types 0 and 1;
+    the virtual nodes of an H-tree) carry the labels of their input nodes, H-tree leaves those of the node they pool into, clique
+    rows -1 (``data.heterogeneous_htree_to_homogeneous``)"""
+    index = {int(v): i for i, v in enumerate(ids)}
+    yo = torch.from_numpy(y[[index[int(v)] for v in info["object_ids"]]])
+    yr = torch.from_numpy(y[[index[int(v)] for v in info["room_ids"]]])
+    out = torch.full((d.x.size(0),), -1, dtype=torch.int64)
+    node_type = d.node_type.cpu()
+    if hasattr(d, "pool_edge_index"):
+        out[node_type == 4], out[node_type == 5] = yo, yr
+        pool = d.pool_edge_index.cpu()
+        out[pool[0]] = out[pool[1]]
+    else:
+        out[node_type == 0], out[node_type == 1] = yo, yr
+    return out
+
+
+def single_frame_clones(pipe, frame_list, ys=None):
+    """``pipe.convert`` on every frame, each result copied to the CPU before the next convert (a result is valid until then), with
+    ``y`` attached; frames the pipeline returns None for are left out.  -> (graphs on the CPU, infos)"""
+    graphs, infos = [], []
+    for i, arrays in enumerate(frame_list):
+        r = pipe.convert(*arrays)
+        infos.append(None if r is None else r[1])
+        if r is None:
+            continue
+        g, info = r
+        g = g.to("cpu")
+        if ys is not None:
+            if pipe.homogeneous:
+                g.y = homogeneous_labels(g, ys[i], info, arrays[0])
+            else:
+                index = {int(v): k for k, v in enumerate(arrays[0])}
+                kept = np.array([index[int(v)] for v in info["object_ids"]], dtype=np.int64)
+                rooms = np.array([index[int(v)] for v in info["room_ids"]], dtype=np.int64)
+                attach_labels(g, ys[i], kept, rooms, pipe.htree)
+        graphs.append(g)
+    return graphs, infos
+
+
+def assert_same_batch(got, want):
+    """every store, attribute and tensor of two collated HeteroData / Data (both on the device), bit for bit"""
+    if not hasattr(want, "node_types"):
+        g = {k: v for k, v in vars(got).items() if k != "_plan_cache"}
+        w = {k: v for k, v in vars(want).items() if k != "_plan_cache"}
+        assert sorted(g) == sorted(w)
+        for k, t in w.items():
+            if isinstance(t, torch.Tensor):
+                assert g[k].dtype == t.dtype and g[k].shape == t.shape and g[k].is_contiguous() and g[k].device == t.device, k
+                assert torch.equal(g[k], t), k
+            else:
+                assert g[k] == t, k
+        return
+    assert got.node_types == want.node_types and got.edge_types == want.edge_types
+    assert got.num_graphs == want.num_graphs and got.max_graph_nodes == want.max_graph_nodes
+    for key in want.node_types + want.edge_types:
+        assert sorted(got[key].keys()) == sorted(want[key].keys()), key
+        for attr, w in want[key].items():
+            g = getattr(got[key], attr)
+            if attr == "ptr_version":  # vouches for the edge_index it was computed for, on either side
+                assert int(g) == int(got[key].edge_index._version) and int(w) == int(want[key].edge_index._version)
+                continue
+            assert g.dtype == w.dtype and g.shape == w.shape and g.is_contiguous() and g.device == w.device, (key, attr)
+            assert torch.equal(g, w), (key, attr)
