@@ -10,6 +10,9 @@
 // of every output tensor in ONE arena (include/hydra_mp.h section 14).  hmp_frame_build_homogeneous lays the same bookkeeping out as
 // the homogeneous Data instead (convert_graph's closing to_homogeneous(): data.heterogeneous_data_to_homogeneous /
 // heterogeneous_htree_to_homogeneous are its parity oracle): one tensor per attribute, one item per node-type / edge-type segment.
+// With relative_pos = HMP_FRAME_RELPOS_HTREE an H-tree frame is laid out as the server's compute_relative_pos leaves it
+// (mp3d_dataset.py:298-319 on Hydra_mp3d_htree_data; data.compute_relative_pos of htree.generate_htree(clique_pos=True) is the
+// parity oracle): every x without its three position columns, pos on the clique types, edge_attr on every edge type.
 //
 // The object-object predicates run HERE and not on the device on purpose: a frame has 10^1..10^3 objects and only pairs inside a
 // room are tested (microseconds of float64 work), while the H-tree builder needs the edge list on the host -- computing it on the
@@ -33,6 +36,8 @@ namespace {
 enum { L_OBJECTS = 2, L_PLACES = 3, L_ROOMS = 4 };
 enum { EV_AS_GIVEN = 0, EV_BOTH = 1, EV_FLIP = 2, EV_VEC_ARANGE = 3, EV_ARANGE_VEC = 4 };  // frame.hip: edge_ends
 inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+// (source, destination) node types, in store order, of the 10 HTREE_EDGE_TYPES, the 3 init and the 2 pool edge types
+const int kTreeEnds[15][2] = {{0, 2}, {2, 0}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 3}, {3, 2}, {2, 2}, {3, 3}, {4, 2}, {5, 2}, {5, 3}, {0, 4}, {1, 5}};
 }  // namespace
 
 struct hmp_frame {
@@ -104,19 +109,41 @@ struct Layout {
     const int64_t eo = variant == EV_BOTH ? 2 * e : e;
     item(HMP_FK_EATTR, tensor, eo, 3, eo * 12, s_list, s_pos_src, s_pos_dst, -1, variant, (int)e, eo * 3, 256);
   }
-  // clique rows: members of clique q = the sources of the init edges whose destination is q, in ascending init-edge order
-  void clique(int tensor, int64_t rows, int64_t width, const std::vector<int32_t>& init, int s_room_pos) {
-    clique_at(tensor, rows, width, alloc(rows * width * 4), init, s_room_pos);
+  // clique rows: members of clique q = the sources of the init edges whose destination is q, in ascending init-edge order.
+  // `drop`: leading columns of [mean | zeros] a row goes without.  Returns the (ptr, members) sections it made
+  struct Members { int s_ptr, s_mem; };
+  Members clique(int tensor, int64_t rows, int64_t width, const std::vector<int32_t>& init, int s_room_pos, int drop) {
+    return clique_at(tensor, rows, width, alloc(rows * width * 4), init, s_room_pos, drop);
   }
-  void clique_at(int tensor, int64_t rows, int64_t width, int64_t dst, const std::vector<int32_t>& init, int s_room_pos) {
+  Members clique_at(int tensor, int64_t rows, int64_t width, int64_t dst, const std::vector<int32_t>& init, int s_room_pos, int drop) {
     const size_t e = init.size() / 2;
     std::vector<int32_t> ptr(rows + 1, 0), mem(e);
     for (size_t k = 0; k < e; ++k) ++ptr[init[e + k] + 1];
     for (int64_t q = 0; q < rows; ++q) ptr[q + 1] += ptr[q];
     std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
     for (size_t k = 0; k < e; ++k) mem[fill[init[e + k]]++] = init[k];
-    const int s_ptr = section(ptr), s_mem = section(mem);
-    item_at(HMP_FK_CLIQUE, tensor, rows, width, dst, s_ptr, s_mem, s_room_pos, -1, 0, 0, rows * width, 256);
+    const Members m{section(ptr), section(mem)};
+    item_at(HMP_FK_CLIQUE, tensor, rows, width, dst, m.s_ptr, m.s_mem, s_room_pos, -1, drop, 0, rows * width, 256);
+    return m;
+  }
+  // `pos` of a clique type: the three columns, from sections a clique item already made
+  void clique_pos(int tensor, int64_t rows, const Members& m, int s_room_pos) {
+    item(HMP_FK_CLIQUE, tensor, rows, 3, rows * 12, m.s_ptr, m.s_mem, s_room_pos, -1, 0, 0, rows * 3, 256);
+  }
+
+  // ---- relative positions on H-tree edges: where an end of an edge type finds its position (HMP_FE_*)
+  struct End { int mode, s_pos, s_a, s_b; };
+  // the descriptor section of an HMP_FK_EATTR_HT item; its offsets count from the descriptor itself, so they hold wherever a batch
+  // puts the frame's sections
+  int32_t ends_section(const End& src, const End& dst) {
+    const int32_t at = (int32_t)align16((int64_t)F.sections.size());  // where section() puts it
+    auto rel = [&](int s) { return s >= 0 ? s - at : 0; };
+    const int32_t w[2 * HMP_FRAME_END_WORDS] = {src.mode, rel(src.s_pos), rel(src.s_a), rel(src.s_b),
+                                                dst.mode, rel(dst.s_pos), rel(dst.s_a), rel(dst.s_b)};
+    return section(w, sizeof w);
+  }
+  void eattr_ht_at(int tensor, int64_t dst, int s_list, int variant, int64_t e, int s_ends) {
+    item_at(HMP_FK_EATTR_HT, tensor, e, 3, dst, s_list, s_ends, -1, -1, variant, (int)e, e * 3, 256);
   }
 
   // ---- segments of a homogeneous tensor: one item per node type (rows) or edge type (columns), at its place inside the tensor
@@ -150,7 +177,12 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
   if (!out || n < 0 || m < 0 || sem_dim < 0 || n_labels < 0 || clique_dim < 0) return fail("bad argument");
   if (n > 0 && (!ids || !layer || !pos || !bb_min || !bb_max || !label)) return fail("null node array");
   if (m > 0 && !edges) return fail("null edge array");
-  if (htree && relative_pos) return fail("relative positions on H-tree edges are not produced (generate_htree has none): relative_pos with htree");
+  const bool rel_ht = relative_pos == HMP_FRAME_RELPOS_HTREE;
+  if (rel_ht && !htree) return fail("relative_pos = HMP_FRAME_RELPOS_HTREE (relative positions on H-tree edges) needs htree");
+  if (htree && relative_pos && !rel_ht)
+    return fail("relative_pos = 1 with htree is refused: relative positions on H-tree edges are relative_pos = HMP_FRAME_RELPOS_HTREE");
+  if (rel_ht && clique_dim > 0 && clique_dim <= 3)
+    return fail("clique_dim must be 0 or more than 3 with relative positions on H-tree edges (a clique row loses its 3 position columns)");
   if (htree && clique_dim > 0 && clique_dim < 3) return fail("clique_dim must be 0 or at least 3 (the mean room position)");
   if (sem_dim > 0 && n_labels < 1) return fail("a semantic table needs n_labels >= 1");
 
@@ -186,7 +218,7 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
   };
 
   hmp_frame* F = new hmp_frame;
-  const int32_t cfg[6] = {homogeneous ? 1 : 0, htree ? 1 : 0, relative_pos ? 1 : 0, sem_dim, n_labels, clique_dim};
+  const int32_t cfg[6] = {homogeneous ? 1 : 0, htree ? 1 : 0, rel_ht ? HMP_FRAME_RELPOS_HTREE : (relative_pos ? 1 : 0), sem_dim, n_labels, clique_dim};
   memcpy(F->cfg, cfg, sizeof cfg);
   F->n_input = n;
   auto bail = [&](const char* msg) { delete F; return fail(msg); };
@@ -304,10 +336,20 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
 
   // ---- layout: sections of the staging block, items, arena offsets, workgroups
   Layout L(*F);
-  const int npos = relative_pos ? 0 : 3;
+  const int npos = relative_pos ? 0 : 3, drop = rel_ht ? 3 : 0;  // leading columns every x / every clique row goes without
   const int s_opos = L.section(opos), s_osize = L.section(osize), s_rpos = L.section(rpos), s_rsize = L.section(rsize);
   const int s_olabel = L.section(olabel), s_rlabel = L.section(rlabel);
   const int s_osem = sem_dim > 0 ? s_olabel : -1;
+  // relative positions on H-tree edges: how a node of each H-tree type (store order) finds its position
+  Layout::End end_of[6];
+  auto tree_ends = [&](int s_oorig, int s_rorig, const Layout::Members& m_or, const Layout::Members& m_rr) {
+    end_of[0] = {HMP_FE_GATHER, s_opos, s_oorig, -1};
+    end_of[1] = {HMP_FE_GATHER, s_rpos, s_rorig, -1};
+    end_of[2] = {HMP_FE_CLIQUE, s_rpos, m_or.s_ptr, m_or.s_mem};
+    end_of[3] = {HMP_FE_CLIQUE, s_rpos, m_rr.s_ptr, m_rr.s_mem};
+    end_of[4] = {HMP_FE_DIRECT, s_opos, -1, -1};
+    end_of[5] = {HMP_FE_DIRECT, s_rpos, -1, -1};
+  };
   if (htree) {  // the topology, for either layout
     std::vector<int32_t> ro(F->obj_room);
     for (int k = 0; k < n_obj; ++k) ro.push_back(k);
@@ -333,11 +375,9 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
     } else {
       const hmp_htree& T = *F->tree;
       n_rows = {T.counts[0], T.counts[1], T.counts[2], T.counts[3], n_obj, n_rooms};
-      W = std::max<int64_t>(W, clique_dim);  // clique rows are clique_dim wide, or as wide as the objects' / rooms' (clique_dim 0)
+      W = std::max<int64_t>(W, clique_dim - drop);  // clique rows are clique_dim wide, or as wide as the objects' / rooms' (clique_dim 0)
       object_type = 4, room_type = 5;
-      // (source type, destination type) of the 10 HTREE_EDGE_TYPES, the 3 init and the 2 pool edge types
-      static const int ends[15][2] = {{0, 2}, {2, 0}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 3}, {3, 2}, {2, 2}, {3, 3},
-                                      {4, 2}, {5, 2}, {5, 3}, {0, 4}, {1, 5}};
+      const auto& ends = kTreeEnds;
       for (int k = 0; k < 10; ++k) main_e.push_back({L.section(T.edges[k]), EV_AS_GIVEN, (int64_t)T.edges[k].size() / 2, ends[k][0], ends[k][1], -1, -1});
       for (int k = 0; k < 3; ++k) init_e.push_back({L.section(T.init[k]), EV_AS_GIVEN, (int64_t)T.init[k].size() / 2, ends[10 + k][0], ends[10 + k][1], -1, -1});
     }
@@ -356,8 +396,9 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
       const int s_oorig = L.section(T.object_orig), s_rorig = L.section(T.room_orig);
       L.feat_at(H0 + 0, n_rows[0], W, xrow(0), s_opos, s_osize, s_osem, s_oorig, npos, sem_dim);
       L.feat_at(H0 + 0, n_rows[1], W, xrow(1), s_rpos, s_rsize, -1, s_rorig, npos, 0);
-      L.clique_at(H0 + 0, n_rows[2], W, xrow(2), T.init[1], s_rpos);  // [mean | zeros] whatever clique_dim is: zeros up to W
-      L.clique_at(H0 + 0, n_rows[3], W, xrow(3), T.init[2], s_rpos);
+      const Layout::Members m_or = L.clique_at(H0 + 0, n_rows[2], W, xrow(2), T.init[1], s_rpos, drop);  // [mean | zeros] whatever clique_dim is: zeros up to W
+      const Layout::Members m_rr = L.clique_at(H0 + 0, n_rows[3], W, xrow(3), T.init[2], s_rpos, drop);
+      tree_ends(s_oorig, s_rorig, m_or, m_rr);
       L.feat_at(H0 + 0, n_obj, W, xrow(4), s_opos, s_osize, s_osem, -1, npos, sem_dim);
       L.feat_at(H0 + 0, n_rooms, W, xrow(5), s_rpos, s_rsize, -1, -1, npos, 0);
       pool_e = {{s_oorig, EV_ARANGE_VEC, n_rows[0], 0, 4, -1, -1}, {s_rorig, EV_ARANGE_VEC, n_rows[1], 1, 5, -1, -1}};
@@ -381,7 +422,11 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
     if (relative_pos) {
       const int64_t edge_attr = L.alloc(E * 12);
       col = 0;
-      for (const EdgeSeg& g : main_e) { L.eattr_seg(H0 + 5, edge_attr, col, g.s_list, g.variant, g.e, g.s_pos_src, g.s_pos_dst); col += columns(g); }
+      for (const EdgeSeg& g : main_e) {
+        if (rel_ht) L.eattr_ht_at(H0 + 5, edge_attr + col * 12, g.s_list, g.variant, g.e, L.ends_section(end_of[g.src], end_of[g.dst]));
+        else L.eattr_seg(H0 + 5, edge_attr, col, g.s_list, g.variant, g.e, g.s_pos_src, g.s_pos_dst);
+        col += columns(g);
+      }
     }
     if (htree) {
       const int64_t object_mask = L.alloc(N);
@@ -420,18 +465,31 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
     L.feat(T0 + 3, T.counts[1], s_rpos, s_rsize, -1, s_rorig, npos, 0);
     L.pos(T0 + 4, T.counts[1], s_rpos, s_rorig);
     L.i64(T0 + 5, T.counts[1], s_rlabel, s_rorig, 4);
-    L.clique(T0 + 6, T.counts[2], clique_dim ? clique_dim : npos + 3 + sem_dim, T.init[1], s_rpos);
-    L.clique(T0 + 7, T.counts[3], clique_dim ? clique_dim : npos + 3, T.init[2], s_rpos);
+    const Layout::Members m_or = L.clique(T0 + 6, T.counts[2], clique_dim ? clique_dim - drop : npos + 3 + sem_dim, T.init[1], s_rpos, drop);
+    const Layout::Members m_rr = L.clique(T0 + 7, T.counts[3], clique_dim ? clique_dim - drop : npos + 3, T.init[2], s_rpos, drop);
     L.feat(T0 + 8, n_obj, s_opos, s_osize, s_osem, -1, npos, sem_dim);
     L.pos(T0 + 9, n_obj, s_opos, -1);
     L.i64(T0 + 10, n_obj, s_olabel, -1, 4);
     L.feat(T0 + 11, n_rooms, s_rpos, s_rsize, -1, -1, npos, 0);
     L.pos(T0 + 12, n_rooms, s_rpos, -1);
     L.i64(T0 + 13, n_rooms, s_rlabel, -1, 4);
-    for (int k = 0; k < 10; ++k) L.edge(T0 + 14 + k, L.section(T.edges[k]), EV_AS_GIVEN, (int64_t)T.edges[k].size() / 2);
-    for (int k = 0; k < 3; ++k) L.edge(T0 + 24 + k, L.section(T.init[k]), EV_AS_GIVEN, (int64_t)T.init[k].size() / 2);
-    L.edge(T0 + 27, s_oorig, EV_ARANGE_VEC, T.counts[0]);  // o_to_ov: (leaf, original object)
-    L.edge(T0 + 28, s_rorig, EV_ARANGE_VEC, T.counts[1]);
+    int s_list[15], variant[15];
+    int64_t n_e[15];
+    for (int k = 0; k < 13; ++k) {
+      const std::vector<int32_t>& e = k < 10 ? T.edges[k] : T.init[k - 10];
+      s_list[k] = L.section(e), variant[k] = EV_AS_GIVEN, n_e[k] = (int64_t)e.size() / 2;
+    }
+    s_list[13] = s_oorig, variant[13] = EV_ARANGE_VEC, n_e[13] = T.counts[0];  // o_to_ov: (leaf, original object)
+    s_list[14] = s_rorig, variant[14] = EV_ARANGE_VEC, n_e[14] = T.counts[1];
+    for (int k = 0; k < 15; ++k) L.edge(T0 + 14 + k, s_list[k], variant[k], n_e[k]);
+    if (rel_ht) {  // what compute_relative_pos adds to an H-tree: pos of the clique types, edge_attr of every edge type
+      const int R0 = HMP_FT_HTREL;
+      L.clique_pos(R0 + 0, T.counts[2], m_or, s_rpos);
+      L.clique_pos(R0 + 1, T.counts[3], m_rr, s_rpos);
+      tree_ends(s_oorig, s_rorig, m_or, m_rr);
+      for (int k = 0; k < 15; ++k)
+        L.eattr_ht_at(R0 + 2 + k, L.alloc(n_e[k] * 12), s_list[k], variant[k], n_e[k], L.ends_section(end_of[kTreeEnds[k][0]], end_of[kTreeEnds[k][1]]));
+    }
   }
   const int64_t n_items = (int64_t)F->items.size() / HMP_FRAME_ITEM_WORDS;
   const int64_t table_bytes = align16(n_items * HMP_FRAME_ITEM_WORDS * 4);
@@ -557,17 +615,15 @@ int node_rows(const hmp_frame& f, int64_t* rows) {
 // node type of a typed node tensor, or (source, destination) types of a typed edge tensor (edge_index and edge_attr alike)
 void typed_ends(int tensor, int& src, int& dst) {
   static const int base_ends[4][2] = {{0, 0}, {1, 1}, {1, 0}, {0, 1}};
-  static const int tree_ends[15][2] = {{0, 2}, {2, 0}, {1, 2}, {2, 1}, {1, 3}, {3, 1}, {2, 3}, {3, 2}, {2, 2}, {3, 3},
-                                       {4, 2}, {5, 2}, {5, 3}, {0, 4}, {1, 5}};
   if (tensor < HMP_FT_HTREE) { src = base_ends[(tensor - 8) & 3][0]; dst = base_ends[(tensor - 8) & 3][1]; }
-  else { src = tree_ends[tensor - HMP_FT_HTREE - 14][0]; dst = tree_ends[tensor - HMP_FT_HTREE - 14][1]; }
+  else { src = kTreeEnds[tensor - HMP_FT_HTREE - 14][0]; dst = kTreeEnds[tensor - HMP_FT_HTREE - 14][1]; }
 }
 
 // bytes of one row of an item's output (edge lists excepted: they are counted in columns)
 int64_t row_bytes(const int32_t* w) {
   switch (w[HMP_FI_KIND]) {
     case HMP_FK_FEAT: case HMP_FK_CLIQUE: return (int64_t)w[HMP_FI_WIDTH] * 4;
-    case HMP_FK_POS: case HMP_FK_EATTR: return 12;
+    case HMP_FK_POS: case HMP_FK_EATTR: case HMP_FK_EATTR_HT: return 12;
     case HMP_FK_CONST: return w[HMP_FI_P1];
     default: return 8;
   }
@@ -577,12 +633,12 @@ int64_t row_bytes(const int32_t* w) {
 
 extern "C" int hmp_frame_batch_items_needed(const hmp_frame* f, int32_t form, int32_t with_y, int32_t* per_frame, int32_t* per_batch) {
   if (!f || !per_frame || !per_batch || (form != HMP_FB_COLLATED && form != HMP_FB_STORE)) return batch_fail("bad argument (items_needed)");
-  const bool homog = f->cfg[0], htree = f->cfg[1], rel = f->cfg[2];
+  const bool homog = f->cfg[0], htree = f->cfg[1], rel = f->cfg[2], rel_ht = f->cfg[2] == HMP_FRAME_RELPOS_HTREE;
   const int n_types = htree ? 6 : 2;
   // items of a frame of this configuration (a frame without items has none to count: the layouts' own counts, as frame_build emits them)
   int frame_items, n_edge_types;
-  if (homog) { frame_items = htree ? 49 : (rel ? 18 : 14); n_edge_types = htree ? 3 : 1; }
-  else { frame_items = htree ? 29 : (rel ? 16 : 12); n_edge_types = htree ? 15 : 4; }
+  if (homog) { frame_items = htree ? (rel_ht ? 59 : 49) : (rel ? 18 : 14); n_edge_types = htree ? 3 : 1; }
+  else { frame_items = htree ? (rel_ht ? 46 : 29) : (rel ? 16 : 12); n_edge_types = htree ? 15 : 4; }
   if (!f->items.empty()) frame_items = (int)(f->items.size() / HMP_FRAME_ITEM_WORDS);
   *per_frame = frame_items + (!homog && form == HMP_FB_COLLATED ? n_types : 0) + (with_y ? (homog ? n_types : (htree ? 4 : 2)) : 0);
   *per_batch = homog ? (form == HMP_FB_STORE ? 1 + n_edge_types : 0) : n_types + n_edge_types;

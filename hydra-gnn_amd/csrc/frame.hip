@@ -28,11 +28,17 @@
 //   EDGE    int64 [2][width] from an int32 list of P1 entries, form P0           S0 list
 //   EATTR   pos32[dst] - pos32[src]: both rounded to float32, one float32 subtraction   S0 list (form P0, P1 entries), S1 pos of the
 //           source type, S2 pos of the destination type
-//   CLIQUE  [mean float32 position of the member rooms | zeros]: summed in ascending init-edge order by one thread per (clique,
-//           coordinate), divided by the count                                    S0 ptr i32 [rows + 1], S1 members, S2 room pos f64
+//   CLIQUE  [mean float32 position of the member rooms | zeros] without its first P0 columns: summed in ascending init-edge order by
+//           one thread per (clique, coordinate), divided by the count (clique_mean)   S0 ptr i32 [rows + 1], S1 members, S2 room pos f64
 //   EDGE_SEG  `width` columns of an int64 [2][S1] tensor, as EDGE: row 1 lies S1 elements (the tensor's pitch) behind row 0, the
 //           sources are shifted by S2 and the destinations by S3 (the row offsets of their node types)   S0 list; S1..S3 numbers
 //   CONST   `rows` elements of P1 bytes, every one P0: the int64 node_type / edge_type segments and the one-byte masks
+//   EATTR_HT  pos[dst] - pos[src] on an H-tree edge list (relative positions on an H-tree, HMP_FRAME_RELPOS_HTREE), one float32
+//           subtraction of what the same launch writes as `pos` of the two node types.  An end is a leaf (the float64 position of its
+//           scene-graph node through object_orig / room_orig), a virtual node (that position directly) or a clique, whose mean is
+//           RECOMPUTED here from the ptr / members / room-position sections with clique_mean -- the clique's `pos` item may not have
+//           run yet, and nothing the launch writes is read in it.  S0 list (form P0, P1 entries), S1 descriptor: per end
+//           {HMP_FE_* mode, position section, index or ptr section, member section} as byte offsets from the descriptor itself
 #include "common.h"
 
 namespace hmp {
@@ -57,6 +63,24 @@ __device__ __forceinline__ void edge_ends(const int* __restrict__ e, int variant
 // column c of the float64 head [pos (npos columns) | size] of source row r
 __device__ __forceinline__ float feat_head(const double* __restrict__ pos, const double* __restrict__ size, int npos, int r, int c) {
   return (float)(c < npos ? pos[3 * r + c] : size[3 * r + (c - npos)]);
+}
+
+// coordinate c of clique q: the float32 positions of its member rooms summed in ascending member order, one float32 division by
+// the count.  The one statement of this arithmetic: a clique's x / pos rows and every edge_attr that ends in it agree bit for bit.
+__device__ __forceinline__ float clique_mean(const int* __restrict__ ptr, const int* __restrict__ mem, const double* __restrict__ rpos, int q,
+                                             int c) {
+  const int b = ptr[q], t = ptr[q + 1];
+  float v = 0.f;
+  for (int k = b; k < t; ++k) v += (float)rpos[3 * mem[k] + c];
+  return v / (float)max(t - b, 1);
+}
+
+// float32 coordinate c of node i of an H-tree edge end; E = the end's HMP_FRAME_END_WORDS words of the descriptor at `desc`
+__device__ __forceinline__ float tree_end_pos(const char* __restrict__ desc, const int* __restrict__ E, int i, int c) {
+  const double* pos = reinterpret_cast<const double*>(desc + E[1]);
+  const int* a = reinterpret_cast<const int*>(desc + E[2]);
+  if (E[0] == HMP_FE_CLIQUE) return clique_mean(a, reinterpret_cast<const int*>(desc + E[3]), pos, i, c);
+  return (float)pos[3 * (E[0] == HMP_FE_GATHER ? a[i] : i) + c];
 }
 
 // What a workgroup writes of its item I (the words behind the item lookup): both kernels below call it, so every kind is written once.
@@ -137,15 +161,21 @@ __device__ __forceinline__ void frame_expand_item(const char* __restrict__ stg, 
     if (e < (int64_t)rows * width) {
       const int q = (int)(e / width), c = (int)(e % width);
       float v = 0.f;
-      if (c < 3) {
-        const int* ptr = reinterpret_cast<const int*>(sec(HMP_FI_S0));
-        const int* mem = reinterpret_cast<const int*>(sec(HMP_FI_S1));
-        const double* rpos = reinterpret_cast<const double*>(sec(HMP_FI_S2));
-        const int b = ptr[q], t = ptr[q + 1];
-        for (int k = b; k < t; ++k) v += (float)rpos[3 * mem[k] + c];
-        v = v / (float)max(t - b, 1);
-      }
+      if (c + p0 < 3)
+        v = clique_mean(reinterpret_cast<const int*>(sec(HMP_FI_S0)), reinterpret_cast<const int*>(sec(HMP_FI_S1)),
+                        reinterpret_cast<const double*>(sec(HMP_FI_S2)), q, c + p0);
       reinterpret_cast<float*>(out)[e] = v;
+    }
+  } else if (kind == HMP_FK_EATTR_HT) {
+    if (e < (int64_t)rows * 3) {
+      const int col = (int)(e / 3), c = (int)(e % 3);
+      int s, d;
+      edge_ends(reinterpret_cast<const int*>(sec(HMP_FI_S0)), p0, p1, col, s, d);
+      const char* desc = sec(HMP_FI_S1);
+      const int* E = reinterpret_cast<const int*>(desc);
+      const float ps = tree_end_pos(desc, E, s, c);
+      const float pd = tree_end_pos(desc, E + HMP_FRAME_END_WORDS, d, c);
+      reinterpret_cast<float*>(out)[e] = pd - ps;
     }
   } else if (kind == HMP_FK_CONST) {
     if (e < rows) {

@@ -290,7 +290,9 @@ FS_KEPT, FS_DROPPED, FS_ROOMS, FS_E_OO, FS_E_RR, FS_STAGING_BYTES, FS_ARENA_BYTE
 FS_HT_COUNTS, FS_HT_EDGES, FS_HT_INIT, FS_COUNT = 9, 13, 23, 26
 FRAME_ITEM_WORDS = 12
 FI_KIND, FI_TENSOR, FI_ROWS, FI_WIDTH, FI_DST, FI_S0, FI_S1, FI_S2, FI_S3, FI_P0, FI_P1, FI_BLOCK0 = range(12)
-FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE, FK_EDGE_SEG, FK_CONST = range(8)
+FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE, FK_EDGE_SEG, FK_CONST, FK_EATTR_HT = range(9)
+FRAME_RELPOS_HTREE = 2  # value of hmp_frame_build's relative_pos: relative positions on the edges of an H-tree
+FRAME_END_WORDS, FE_DIRECT, FE_GATHER, FE_CLIQUE = 4, 0, 1, 2  # an end of an FK_EATTR_HT item's descriptor section
 FT_HTREE, FT_COUNT = 16, 45
 FT_HOMOG, FT_HOMOG_COUNT = 45, 9  # the tensors of a homogeneous frame (hmp_frame_build_homogeneous)
 # batches of frames (hmp_frame_batch_*): forms, limits, indices of hmp_frame_batch_sizes, the tensors a batch adds
@@ -299,6 +301,9 @@ FRAME_MAX_ITEMS, FRAME_BATCH_MAX_ITEMS = 64, 4096
 (FBS_FRAMES, FBS_GRAPHS, FBS_MAX_GRAPH_NODES, FBS_STAGING_BYTES, FBS_ARENA_BYTES, FBS_ITEMS, FBS_GROUPS, FBS_BLOCKS, FBS_NODE_TYPES,
  FBS_EDGE_TYPES, FBS_TENSORS, FBS_COUNT) = range(12)
 FT_BATCH, FTB_BATCH, FTB_NODE_PTR, FTB_EDGE_PTR, FTB_Y, FT_BATCH_COUNT = 54, 0, 6, 12, 27, 33
+FT_HTREL, FT_HTREL_COUNT = 87, 17  # what FRAME_RELPOS_HTREE adds: pos of the two clique types, edge_attr of the 15 H-tree edge types
+
+COLLATE_MAX_ITEMS, COLLATE_MAX_SLOTS = 40, 24  # csrc/collate.hip CB_MAX_ITEMS / CB_MAX_SLOTS: arrays and types of one collation launch
 
 ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
 

@@ -209,6 +209,33 @@ _FRAME_TENSORS = (
 )
 assert len(_FRAME_TENSORS) == _lib.FT_COUNT
 _HTREE_STORES = ["object", "room", "object-room", "room-room", "object_virtual", "room_virtual"]
+# what relative positions on an H-tree add (``htree_relative_pos``), by output tensor number - HMP_FT_HTREL
+_HTREL_TENSORS = [("object-room", "pos"), ("room-room", "pos")] + [(k, "edge_attr") for k, a in _FRAME_TENSORS[_lib.FT_HTREE:] if a == "edge_index"]
+assert len(_HTREL_TENSORS) == _lib.FT_HTREL_COUNT
+
+
+def _typed_tensor(t: int):
+    """(store key, attribute) of output tensor number ``t`` of a typed frame"""
+    return _HTREL_TENSORS[t - _lib.FT_HTREL] if t >= _lib.FT_HTREL else _FRAME_TENSORS[t]
+
+
+def _relpos_mode(who: str, htree, relative_pos, htree_relative_pos, clique_dim) -> int:
+    """``hmp_frame_build``'s ``relative_pos`` argument: 0, 1 (the baseline graph's) or ``HMP_FRAME_RELPOS_HTREE``.  Every refusal of
+    the three keywords is made here, for the pipeline and the host-stage functions alike."""
+    if htree_relative_pos and relative_pos:
+        raise _lib.HydraMPError(f"{who}: htree_relative_pos and relative_pos exclude one another (relative_pos is the baseline "
+                                f"graph's mode and is refused with htree)")
+    if htree and relative_pos:
+        raise _lib.HydraMPError(f"{who}: relative_pos is the baseline graph's mode and is refused with htree; relative positions on "
+                                f"H-tree edges are htree_relative_pos=True")
+    if not htree_relative_pos:
+        return int(bool(relative_pos))
+    if not htree:
+        raise _lib.HydraMPError(f"{who}: htree_relative_pos is relative positions on H-tree edges: it needs htree=True")
+    if 0 < int(clique_dim or 0) <= 3:
+        raise _lib.HydraMPError(f"{who}: clique_dim {int(clique_dim)} leaves a clique no column once htree_relative_pos drops the three "
+                                f"position columns: pass 0 or more than 3")
+    return _lib.FRAME_RELPOS_HTREE
 # attributes of the homogeneous Data, by output tensor number - HMP_FT_HOMOG
 _HOMOG_TENSORS = ("x", "edge_index", "node_type", "edge_type", "room_mask", "edge_attr", "object_mask", "init_edge_index", "pool_edge_index")
 assert len(_HOMOG_TENSORS) == _lib.FT_HOMOG_COUNT
@@ -239,21 +266,22 @@ def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_
     build = lib.hmp_frame_build_homogeneous if homogeneous else lib.hmp_frame_build
     _lib.check(build(n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data,
                      label.ctypes.data, m, edges.ctypes.data, float(thresholds[0]), float(thresholds[1]),
-                     float(thresholds[2]), int(bool(htree)), int(bool(relative_pos)), int(sem_dim), int(n_labels),
+                     float(thresholds[2]), int(bool(htree)), int(relative_pos), int(sem_dim), int(n_labels),
                      int(clique_dim or 0), C.byref(h)))
     return h
 
 
 def frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
                      max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
-                     clique_dim: Optional[int] = None, homogeneous: bool = False) -> Dict[str, object]:
+                     clique_dim: Optional[int] = None, homogeneous: bool = False, htree_relative_pos: bool = False) -> Dict[str, object]:
     """The host stage of the frame pipeline on its own (no GPU involved; tests and diagnostics): ``hmp_frame_build``
     (``homogeneous``: ``hmp_frame_build_homogeneous``) and every accessor.  ``kept`` / ``dropped`` / ``rooms`` index the input
     arrays; ``items`` is the staging block's table (int32 ``[n_items, 12]``), ``block`` the packed block (uint8); ``empty``: no room
     or no kept object, nothing was laid out."""
     lib = _lib.load()
     arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
-    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels, clique_dim, homogeneous)
+    rel = _relpos_mode("frame_host_stage", htree, relative_pos, htree_relative_pos, clique_dim)
+    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, rel, sem_dim, n_labels, clique_dim, homogeneous)
     try:
         sz = np.zeros(_lib.FS_COUNT, dtype=np.int64)
         _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -278,9 +306,10 @@ def frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, threshold_ne
 
 def save_frame_file(path: str, ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
                     max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
-                    clique_dim: int = 0) -> None:
+                    clique_dim: int = 0, htree_relative_pos: bool = False) -> None:
     """Flat binary frame file of the stand-alone host-stage driver (``make -C csrc frame_check``; layout in csrc/frame_check.cpp)."""
     arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
+    relative_pos = _relpos_mode("save_frame_file", htree, relative_pos, htree_relative_pos, clique_dim)
     with open(path, "wb") as f:
         f.write(b"HMPF" + struct.pack("<7iq3d", 1, n, int(htree), int(relative_pos), sem_dim, n_labels, clique_dim, m,
                                       threshold_near, max_near, max_on))
@@ -338,7 +367,8 @@ def _batch_host_arrays(lib, hb) -> Dict[str, object]:
 
 def frame_batch_host_stage(frames, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2, htree: bool = False,
                            relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0, clique_dim: Optional[int] = None,
-                           homogeneous: bool = False, form: int = _lib.FB_COLLATED, y=None) -> Dict[str, object]:
+                           homogeneous: bool = False, form: int = _lib.FB_COLLATED, y=None,
+                           htree_relative_pos: bool = False) -> Dict[str, object]:
     """The host stage of ``FramePipeline.convert_batch`` / ``GraphStore.from_frames`` on its own (no GPU involved; the batch
     counterpart of ``frame_host_stage``).  ``frames``: a sequence of the 7-tuples ``frame_host_stage`` takes; ``form``:
     ``_lib.FB_COLLATED`` or ``_lib.FB_STORE``; ``y``: one int64 label vector per frame, aligned with its input arrays.  Returns
@@ -346,12 +376,13 @@ def frame_batch_host_stage(frames, threshold_near: float = 1.5, max_near: float 
     (int64 ``[types, graphs + 1]``), ``tensors`` (int64 ``[n, 4]``: number, arena offset, rows, width), ``frames`` (per frame
     ``kept`` / ``dropped`` / ``rooms``), and the packed ``block`` (uint8) with its ``groups`` and ``items`` tables."""
     lib = _lib.load()
+    rel = _relpos_mode("frame_batch_host_stage", htree, relative_pos, htree_relative_pos, clique_dim)
     built, handles = [], []
     try:
         for fr in frames:
             arrays, n, m = _frame_args(*fr)
             built.append(arrays)
-            handles.append(_frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, relative_pos, sem_dim, n_labels,
+            handles.append(_frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, rel, sem_dim, n_labels,
                                         clique_dim, homogeneous))
         y_ptrs, keep = _label_pointers(y, len(handles), built)
         hb = _batch_build(lib, handles, form, y_ptrs)
@@ -402,7 +433,15 @@ class FramePipeline:
     same pipeline.  ``convert`` runs on torch's current stream and refuses a pipeline whose device is not the current one.  A
     pipeline has ONE device staging buffer and ONE arena, ordered by the stream alone: the stream of the first ``convert`` that
     enqueues anything is the pipeline's, and a ``convert`` under another current stream is refused (keep a pipeline per stream).
-    Relative positions on H-tree edges are not produced (``generate_htree`` has none): ``relative_pos`` with ``htree`` is refused.
+
+    ``htree=True, htree_relative_pos=True`` is the H-tree of the reference's GAT_edge models (``Hydra_mp3d_htree_data`` after
+    ``compute_relative_pos``, which the server runs behind ``nx_htree_to_torch``): what ``data.compute_relative_pos`` makes of
+    ``htree.generate_htree(frame, clique_dim, clique_pos=True)``.  Every node type's ``x`` loses its three leading columns (a clique
+    row is ``clique_dim - 3`` zeros; ``clique_dim`` 1..3 is refused), the two clique types carry ``pos`` (the mean position of their
+    member rooms), and every one of the 15 edge types carries ``edge_attr = pos[dst] - pos[src]``, bit-equal to that difference of
+    the ``pos`` tensors of the same result (a pool edge's is ``+0.0``).  With ``homogeneous=True`` the ``edge_attr`` of the ten tree
+    edge types follows ``edge_index``, as ``data.heterogeneous_htree_to_homogeneous`` keeps it.  ``relative_pos`` is the baseline
+    graph's mode: with ``htree`` it stays refused, and ``htree_relative_pos`` without ``htree`` or together with it is refused too.
 
     ``homogeneous=True`` is ``convert_graph``'s ``if self.model_info.homogeneous: data.to_homogeneous()`` in the same host stage,
     copy and launch: ``convert`` returns ``(data.Data, info)`` with what ``HomogeneousNetwork`` / ``HomogeneousNeuralTreeNetwork``
@@ -420,15 +459,15 @@ class FramePipeline:
 
     def __init__(self, device="cuda:0", semantic_table=None, htree: bool = False, relative_pos: bool = False,
                  clique_dim: Optional[int] = None, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2,
-                 homogeneous: bool = False):
+                 homogeneous: bool = False, htree_relative_pos: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.HydraMPError(f"FramePipeline needs a gfx950 device, not {self.device}: hydra_gnn_amd has no CPU fallback")
         if self.device.index is None:
             self.device = torch.device("cuda", 0)
-        if htree and relative_pos:
-            raise _lib.HydraMPError("FramePipeline: relative positions on H-tree edges are not produced (generate_htree has none)")
+        self._relpos = _relpos_mode("FramePipeline", htree, relative_pos, htree_relative_pos, clique_dim)
         self.htree, self.relative_pos, self.clique_dim = bool(htree), bool(relative_pos), int(clique_dim or 0)
+        self.htree_relative_pos = bool(htree_relative_pos)
         self.homogeneous = bool(homogeneous)
         self.thresholds = (float(threshold_near), float(max_near), float(max_on))
         self._lib = _lib.load()
@@ -496,7 +535,7 @@ class FramePipeline:
     def convert(self, ids, layer, pos, bb_min, bb_max, label, edges):
         lib = self._lib
         arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
-        h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels, self.clique_dim,
+        h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self._relpos, self.sem_dim, self.n_labels, self.clique_dim,
                          self.homogeneous)
         try:
             sz = self._sizes
@@ -524,7 +563,7 @@ class FramePipeline:
                 g[t]
         f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
         for kind, tensor, n_rows, width, dst, *_ in items:
-            key, attr = _FRAME_TENSORS[tensor]
+            key, attr = _typed_tensor(tensor)
             if kind == _lib.FK_I64:
                 t = strided(i64, (n_rows,), (1,), dst >> 3)
             elif kind == _lib.FK_EDGE:
@@ -565,7 +604,7 @@ class FramePipeline:
         try:
             for fr in frames:
                 arrays, n, m = _frame_args(*fr)
-                h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self.relative_pos, self.sem_dim, self.n_labels,
+                h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self._relpos, self.sem_dim, self.n_labels,
                                  self.clique_dim, self.homogeneous)
                 built.append((h, arrays))
                 _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -617,7 +656,10 @@ class FramePipeline:
         f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
         tensors = {}
         for t, dst, rows, width in host["tensors"].tolist():
-            name = (_FRAME_TENSORS[t][1] if t < _lib.FT_HOMOG else _HOMOG_TENSORS[t - _lib.FT_HOMOG]) if t < _lib.FT_BATCH else "ptr"
+            if t < _lib.FT_HOMOG or t >= _lib.FT_HTREL:
+                name = _typed_tensor(t)[1]
+            else:
+                name = _HOMOG_TENSORS[t - _lib.FT_HOMOG] if t < _lib.FT_BATCH else "ptr"
             if name.endswith("edge_index"):
                 tensors[t] = strided(i64, (2, width), (width, 1), dst >> 3)
             elif name.endswith("_mask"):
@@ -643,8 +685,8 @@ class FramePipeline:
         edge_types = _edge_type_names(self.htree, False)
         for t in node_types:
             g[t]
-        for t in sorted(k for k in tensors if k < FB):
-            key, attr = _FRAME_TENSORS[t]
+        for t in sorted(k for k in tensors if k < FB or k >= _lib.FT_HTREL):
+            key, attr = _typed_tensor(t)
             setattr(g[key], attr, tensors[t])
             if attr == "edge_index":
                 g[key].ptr = tensors[FB + _lib.FTB_EDGE_PTR + edge_types.index(key)]

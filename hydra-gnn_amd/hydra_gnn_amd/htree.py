@@ -58,12 +58,14 @@ def htree_topology(n_objects: int, n_rooms: int, oo: torch.Tensor, rr: torch.Ten
     return {"counts": [int(c) for c in counts], "object_orig": obj, "room_orig": room, "edges": edges, "init": init}
 
 
-def generate_htree(dsg: HeteroData, clique_dim: int = None) -> HeteroData:
+def generate_htree(dsg: HeteroData, clique_dim: int = None, clique_pos: bool = False) -> HeteroData:
     """``nx_htree_to_torch(add_virtual_nodes_to_htree(generate_htree(dsg)))`` of the reference for a baseline scene graph with
     node types ``objects`` / ``rooms`` (construct.py:241-483): node types ``object, room, object-room, room-room`` (+ virtual),
     the 10 message-passing edge types, pool edges ``o_to_ov`` / ``r_to_rv`` and init edges.  ``clique_dim``: keep only the
     first ``clique_dim`` feature columns of the clique nodes (the dataset drops their trailing zero block before training,
-    ``mp3d_dataset.py:449-458``: 6 for MP3D)."""
+    ``mp3d_dataset.py:449-458``: 6 for MP3D).  ``clique_pos``: also give the clique types a ``pos`` -- the mean position their ``x``
+    starts with, as ``nx_htree_to_torch`` does for every node type (construct.py:403-436) -- so that ``data.compute_relative_pos``
+    runs on the result as ``Hydra_mp3d_htree_data.compute_relative_pos`` does on the reference's."""
     xo, xr = dsg["objects"].x, dsg["rooms"].x
     n_o, n_r = xo.size(0), xr.size(0)
     ei = dsg.edge_index_dict
@@ -92,6 +94,9 @@ def generate_htree(dsg: HeteroData, clique_dim: int = None) -> HeteroData:
 
     out["object-room"].x = clique_x(topo["counts"][2], topo["init"][1], clique_dim or xo.size(1))
     out["room-room"].x = clique_x(topo["counts"][3], topo["init"][2], clique_dim or xr.size(1))
+    if clique_pos:
+        out["object-room"].pos = out["object-room"].x[:, :3].clone()
+        out["room-room"].pos = out["room-room"].x[:, :3].clone()
     out["object_virtual"].x = xo
     out["room_virtual"].x = xr
     for t_src, t_dst, orig in (("objects", "object", oorig), ("rooms", "room", rorig)):

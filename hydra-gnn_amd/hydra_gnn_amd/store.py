@@ -201,7 +201,7 @@ class GraphStore:
             return dev, hst
 
         data = {t: torch.cat([ch[t] for ch, _ in chunks], dim=1 if v.dim() == 2 and v.dtype == torch.int64 else 0) if len(chunks) > 1 else v
-                for t, v in chunks[0][0].items() if not FB + _lib.FTB_NODE_PTR <= t < FB + _lib.FTB_Y}
+                for t, v in chunks[0][0].items() if not FB + _lib.FTB_NODE_PTR <= t < FB + _lib.FTB_Y}  # the offset vectors are joined below
         ht, homog = pipeline.htree, pipeline.homogeneous
         node_names, edge_names = dsg._node_type_names(ht, homog), dsg._edge_type_names(ht, homog)
         node_ptr = [joined_ptr(FB + _lib.FTB_NODE_PTR + k, "node_ptr", k) for k in range(len(node_names))]
@@ -240,11 +240,11 @@ class GraphStore:
         self.node_attrs = {t: {} for t in node_names}
         self.node_counts = {t: np.diff(node_ptr[k][1]) for k, t in enumerate(node_names)}
         for t in sorted(data):
-            if t >= FB:
+            if FB <= t < _lib.FT_HTREL:
                 k = t - FB - _lib.FTB_Y
                 self.node_attrs[node_names[k]]["y"] = _packed(data[t], *node_ptr[k])
                 continue
-            key, attr = dsg._FRAME_TENSORS[t]
+            key, attr = dsg._typed_tensor(t)  # sorted: an edge type's edge_index comes before its edge_attr
             if attr == "edge_index":
                 self.edge_index[key] = data[t]
                 self.edge_ptr[key], self.edge_ptr_host[key] = edge_ptr[edge_names.index(key)]
@@ -412,8 +412,15 @@ class BatchStream:
                 raise _lib.HydraMPError(f"'{label_key}' must be an int64 vector (one label per node), the store holds "
                                         f"{attrs[label_key].row_shape} {attrs[label_key].data.dtype}")
             target_attrs[HOMO_NODE] = [label_key, "room_mask"]
-        # selective: the stream carries what the net reads plus its targets; otherwise every attribute the store holds
+        # selective: the stream carries what the net reads plus its targets; otherwise every attribute the store holds -- as long
+        # as that fits the collator's table.  A typed H-tree store with relative positions holds 50 arrays (20 node attributes, 15
+        # edge lists, 15 edge_attr): its single-headed stream carries what the net reads and the labels, like the other two.
         selective = self.two_headed or self.homog_room
+        if not selective:
+            n_all = sum(len(a) for a in store.node_attrs.values()) + len(store.edge_types) + sum(e in store.edge_attr for e in store.edge_types)
+            if n_all > _lib.COLLATE_MAX_ITEMS or len(store.node_types) + len(store.edge_types) > _lib.COLLATE_MAX_SLOTS:
+                selective = True
+                target_attrs[label_type] = [label_key]
         if self.two_headed and targets:
             if nat.heads is not None:  # learned linear heads over the rows of one node set
                 self._target_kind = "linear"
@@ -483,6 +490,9 @@ class BatchStream:
                 self._bufs.append(torch.empty((max(self.cap[slot_of[e]], 1),) + pk.row_shape, dtype=pk.data.dtype, device=dev))
                 self._what.append(("edge", e, "edge_attr"))
         n_items = len(items)
+        if n_items > _lib.COLLATE_MAX_ITEMS or len(slots) > _lib.COLLATE_MAX_SLOTS:
+            raise _lib.HydraMPError(f"the stream would collate {n_items} arrays of {len(slots)} node and edge types per batch, one launch's "
+                                    f"table holds {_lib.COLLATE_MAX_ITEMS} of {_lib.COLLATE_MAX_SLOTS}: {[w[1:] for w in self._what]}")
         self._items = (_lib.CollateItem * n_items)(*items)
         self._slot_ptr = (C.c_void_p * len(slots))(*[p.ctypes.data for p in host_ptrs])
         h = C.c_void_p()

@@ -49,7 +49,9 @@ extern "C" {
  *    hmp_frame_build_homogeneous: the same frame laid out as the homogeneous Data (item kinds HMP_FK_EDGE_SEG / HMP_FK_CONST, output
  *    tensors from HMP_FT_HOMOG on).  A new entry; the six entries above, HMP_FRAME_ITEM_WORDS and every earlier number are unchanged;
  *    hmp_frame_batch_build / _items_needed / _sizes / _host_arrays / _pack / _destroy and hmp_frame_expand_batch: many frames per
- *    block and launch (output tensors from HMP_FT_BATCH on).  New entries; a single frame packs what it packed, nothing above changed */
+ *    block and launch (output tensors from HMP_FT_BATCH on).  New entries; a single frame packs what it packed, nothing above changed;
+ *    relative_pos = HMP_FRAME_RELPOS_HTREE (item kind HMP_FK_EATTR_HT, output tensors from HMP_FT_HTREL on): a new value of an argument
+ *    that was refused before; no entry, struct or earlier number changed, every earlier mode packs what it packed */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -809,6 +811,14 @@ int hmp_epoch_read_status(const hmp_epoch_ctl* d_ctl, int32_t* status, void* str
  *     With a table a label of a kept object outside [0, n_labels) is refused (HMP_E_ARG, the message names the node id).
  *     clique_dim: width of the H-tree's clique rows (0 = the feature width of the objects / rooms).
  *
+ *     Relative positions on an H-tree (the reference's Hydra_mp3d_htree_data.compute_relative_pos, which the server runs after
+ *     nx_htree_to_torch for its GAT_edge H-tree models): relative_pos = HMP_FRAME_RELPOS_HTREE with htree = 1.  Every node type's x
+ *     loses its three leading columns (a clique row [mean | zeros] becomes clique_dim - 3 zeros; clique_dim 1..3 is refused), the two
+ *     clique types get a `pos` (the float32 mean of the member rooms: the three columns their x lost), and every one of the 15 edge
+ *     types gets edge_attr = pos[dst] - pos[src] (HMP_FK_EATTR_HT).  The homogeneous layout keeps the edge_attr of the 10 tree edge
+ *     types, segment by segment behind edge_index.  relative_pos = 1 with htree stays refused (it never meant this), and
+ *     HMP_FRAME_RELPOS_HTREE without htree is refused.
+ *
  *     Homogeneous models (HomogeneousNetwork, HomogeneousNeuralTreeNetwork) read the same frame as ONE graph: what
  *     data.heterogeneous_data_to_homogeneous (+ room_mask) makes of the baseline frame, data.heterogeneous_htree_to_homogeneous of
  *     the H-tree (convert_graph's `if homogeneous: to_homogeneous()`).  hmp_frame_build_homogeneous lays the frame out in that form
@@ -833,6 +843,7 @@ int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const int32_t* l
                                 const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
                                 double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim,
                                 int32_t n_labels, int32_t clique_dim, hmp_frame** out);
+#define HMP_FRAME_RELPOS_HTREE 2 /* value of `relative_pos`: relative positions on the edges of an H-tree (htree = 1 only) */
 /* sizes[HMP_FS_COUNT] */
 #define HMP_FS_KEPT 0          /* kept objects */
 #define HMP_FS_DROPPED 1       /* objects with neither a place with a room nor a sibling place with one */
@@ -878,10 +889,19 @@ void hmp_frame_destroy(hmp_frame* f);
 #define HMP_FK_I64 2    /* int64 [rows] from an int32 (labels) or int64 (node ids) section */
 #define HMP_FK_EDGE 3   /* int64 [2][width] from an int32 list */
 #define HMP_FK_EATTR 4  /* float32 [rows][3] = pos32[dst] - pos32[src] */
-#define HMP_FK_CLIQUE 5 /* float32 rows [mean float32 position of the member rooms | zeros] */
+#define HMP_FK_CLIQUE 5 /* float32 rows [mean float32 position of the member rooms | zeros] without their first P0 columns (0, or
+                           3 for the all-zero clique x of an HMP_FRAME_RELPOS_HTREE frame) */
 #define HMP_FK_EDGE_SEG 6 /* HMP_FI_WIDTH columns of an int64 [2][S1] tensor from an int32 list (P0, P1 as EDGE): row 1 lies S1
                              elements behind row 0; S2 is added to every source, S3 to every destination (S1..S3: numbers) */
 #define HMP_FK_CONST 7  /* HMP_FI_ROWS elements of P1 bytes (8: int64, 1: a bool mask), every one P0 */
+#define HMP_FK_EATTR_HT 8 /* float32 [rows][3] = pos[dst] - pos[src] on an H-tree edge list (S0; P0, P1 as EDGE).  S1 is a descriptor
+                             section of 2 x HMP_FRAME_END_WORDS int32, source end then destination end: {mode, position section,
+                             index or ptr section, member section}.  The three sections are byte offsets RELATIVE TO THE DESCRIPTOR
+                             (so a batch moves a frame's sections without touching it; 0 where the mode has none) */
+#define HMP_FRAME_END_WORDS 4
+#define HMP_FE_DIRECT 0   /* pos32 of row i of a float64 position section */
+#define HMP_FE_GATHER 1   /* pos32 of row index[i]: a leaf, through object_orig / room_orig */
+#define HMP_FE_CLIQUE 2   /* the float32 mean of the member rooms of clique i (ptr, members): the arithmetic of HMP_FK_CLIQUE */
 /* output tensors: baseline 0..15 = {objects, rooms} x {x, pos, label, node_ids}, then edge_index and edge_attr of
  * objects_to_objects, rooms_to_rooms, rooms_to_objects, objects_to_rooms; H-tree 16.. = {object, room} x {x, pos, label},
  * object-room.x, room-room.x, {object_virtual, room_virtual} x {x, pos, label}, the 10 HTREE_EDGE_TYPES, the 3 init edge types,
@@ -971,6 +991,11 @@ void hmp_frame_batch_destroy(hmp_frame_batch* b);
 #define HMP_FTB_EDGE_PTR 12
 #define HMP_FTB_Y 27
 #define HMP_FT_BATCH_COUNT 33
+/* tensors of an HMP_FRAME_RELPOS_HTREE frame, behind everything above: +0 pos of object-room, +1 pos of room-room, +2 + k = edge_attr
+ * of H-tree edge type k in the order of the edge_index tensors (10 tree, 3 init, o_to_ov, r_to_rv).  Typed frames: 29 + 17 = 46 items;
+ * the homogeneous layout writes edge_attr (HMP_FT_HOMOG + 5) by 10 more segments: 59 items of the 64 the table holds */
+#define HMP_FT_HTREL (HMP_FT_BATCH + HMP_FT_BATCH_COUNT)
+#define HMP_FT_HTREL_COUNT 17
 /* hmp_frame_expand for a batch block: ONE launch of frame_expand_batch_kernel, which finds a workgroup's item through the group
  * table (two dependent 64-lane loads, two ballots) and writes it with the same code as hmp_frame_expand.  The same arguments, the
  * same three things owed by the caller, the same refusals with n_items in [1, HMP_FRAME_BATCH_MAX_ITEMS]. */
