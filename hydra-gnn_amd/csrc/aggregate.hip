@@ -690,20 +690,48 @@ __global__ __launch_bounds__(256) void agg_bwd_kernel(const TAggArgs a) {
 // dH[l][s] = (dZ[l][s] * Wp[l][s]) . act'(H[l][s]) is row-local, so the block that has just gathered 16 rows of dZ keeps
 // them in LDS ([k][row] image, LD 17) and multiplies them on the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32): one
 // kernel and one hand-off of dZ through L2 less per layer.  dZ is still written to HBM (the weight-gradient GEMM reads it).
-// Wp [ncols][ldw] is read from L2: lane (n, kq) loads Wp[kb + kq][n0 + n] (16 lanes = one 64-byte segment).
-// one 16-row tile [row0, row0 + 16) of source entry S, rows below row_end, by the workgroup's 256 threads; LDS image Hs [ncols][17]
+// The reduction index k is the stacked column, the ROW index of Wp [ncols][ldw], so the weights are read from the transposed
+// image WpT [fpad(xN)][xldt] that the pack writes next to Wp (PackSeg::dst_t; xldt = ncols rounded up to 16, padding zero):
+// lane (nn, kq) loads 16 bytes WpT[n0 + nn][16 i + 4 kq .. +3] -- the operand fetch of agg_proj_tile -- and feeds 4 MFMAs with
+// them.  The image's columns are interleaved inside every 16 (wpt_col, kernels.h) so that those 16 bytes are the stacked rows
+// 16 i + 4 u + kq, u = 0..3: step u multiplies rows 16 i + 4 u .. + 3, the walk down Wp that 4-byte loads from Wp itself make
+// (48 dependent-address loads per lane and column tile), and the sum over k comes out bit for bit the same.
+// one 16-row tile [row0, row0 + 16) of source entry S, rows below row_end, by the workgroup's 256 threads; LDS image Hs
+// [roundup16(ncols)][17], rows past ncols zero
 template <int GS>
 __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc& S, int row0, int row_end, float* Hs) {
   constexpr int TM = 16, LDH = 17, VEC = 4;
   constexpr int RPP = 256 / GS;  // rows gathered per pass
   constexpr int NP = TM / RPP;   // passes (GS = 16: 1, 32: 2, 64: 4)
+  constexpr int WB = 12;         // 16-deep k blocks per trip: 192 stacked columns, the whole operand at hidden width 64
   const int tid = threadIdx.x & 255;
   const int c0 = (tid % GS) * VEC;
   const int lane = threadIdx.x & 63, w = tid >> 6;
   const int nn = lane & 15, kq = lane >> 4;
-  const int K = S.ncols;
+  const int K = S.ncols, K16 = (K + 15) & ~15;
   KT(8);
-  constexpr int WB = 48;
+  // GS = 16 (one gather pass, a launch of one round of workgroups: latency): the operands of the wave's first column tile that do
+  // not depend on the gather are requested ahead of the barrier -- the activations (4 floats per lane) before the gather, the
+  // first trip of weights (WB float4 per lane) right behind it, so that they travel while the tile is written to LDS.  The weights
+  // BEFORE the gather, or behind its extent loads, were measured: the GEMM phase of workgroup 0 falls to 2.3 us, its gather grows
+  // by 1.5 us (loads return in order: the first dependent step of the gather waits for 48 KB of weights per workgroup) and the
+  // launch does not move (profiles/bwd_dx_transposed_weights.md).  GS >= 32 (several passes, several rounds of workgroups:
+  // throughput) requests nothing early: measured slower there.
+  constexpr bool EARLY = GS == 16;
+  const int n_ct = S.xwt ? (S.xN + 15) >> 4 : 0;
+  float4 pre[WB];
+  auto fetch_first = [&]() {
+    if (w >= n_ct) return;  // wave-uniform
+    const float* wrow = S.xwt + (int64_t)min(w * 16 + nn, S.xN - 1) * S.xldt + 4 * kq;
+#pragma unroll
+    for (int i = 0; i < WB; ++i) pre[i] = *reinterpret_cast<const float4*>(wrow + min(16 * i, K16 - 16));
+  };
+  float hv0[4] = {0.f, 0.f, 0.f, 0.f};
+  if (EARLY && S.xh && w < n_ct) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      hv0[r] = S.xh[(int64_t)min(row0 + kq * 4 + r, row_end - 1) * S.xldh + min(w * 16 + nn, S.xN - 1)];
+  }
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     const int m = p * RPP + tid / GS;
@@ -716,32 +744,52 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
       for (int i = 0; i < 4; ++i) Hs[(seg + c + i) * LDH + m] = v.at(i);
     });
   }
+  if constexpr (EARLY) fetch_first();
+  // rows K .. K16 of the image meet the zero padding of WpT in the last k block
+  for (int i = tid; i < (K16 - K) * TM; i += 256) Hs[(K + (i >> 4)) * LDH + (i & 15)] = 0.f;
   __syncthreads();
-  if (S.xw == nullptr) return;  // block-uniform
+  if (S.xwt == nullptr) return;  // block-uniform
   KT(9);
-  const int n_ct = (S.xN + 15) >> 4;
-  for (int ct = w; ct < n_ct; ct += 4) {
+  // one trip of WB k-blocks of 16 from k = kb on: the 16 bytes of weights the lane holds for a block are its rows k + 4 u + kq,
+  // one MFMA each; the steps of the last block past K add products of the zero rows of Hs and the zero padding of WpT
+  auto trip = [&](int kb, const float4 (&bv)[WB], f32x4& acc) {
+#pragma unroll
+    for (int i = 0; i < WB; ++i) {
+      const int k = kb + 16 * i;
+      if (k >= K) break;
+      const float* hp = Hs + (k + kq) * LDH + nn;  // A operand: row m = lane & 15 of the tile
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hp[0 * LDH], bv[i].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hp[4 * LDH], bv[i].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hp[8 * LDH], bv[i].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hp[12 * LDH], bv[i].w, acc, 0, 0, 0);
+    }
+  };
+  // one 16-column tile; first: its activations and the weights of its first trip are the ones requested early
+  auto tile = [&](int ct, auto first) {
     const int col = ct * 16 + nn;
-    const float* wp = S.xw + min(col, S.xN - 1) + (int64_t)kq * S.xldw;  // clamped: padded columns are never stored
-    const float* hp = Hs + kq * LDH + nn;                                  // A operand: row m = lane & 15 of the tile
+    const float* wrow = S.xwt + (int64_t)min(col, S.xN - 1) * S.xldt + 4 * kq;  // clamped: padded columns are never stored
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     // activations whose derivative masks this tile's output: requested before the weight loads / MFMA chain instead of after
     float hv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (S.xh) {
+    if constexpr (decltype(first)::value) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hv[r] = hv0[r];
+    } else if (S.xh) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         hv[r] = S.xh[(int64_t)min(row0 + kq * 4 + r, row_end - 1) * S.xldh + min(col, S.xN - 1)];
     }
-    // 48 k-steps (192 stacked columns) per trip: the (clamped) weight loads are all in flight together, then the MFMA
-    // chain runs -- one L2 round trip for the typical stacked width.  (Requesting them before the gather was measured
-    // SLOWER, +1 us: 48 scalar loads per lane queue in front of the gather's own loads.)
-    for (int kb = 0; kb < K; kb += 4 * WB) {
-      float bv[WB];
+    int kb = 0;
+    if constexpr (decltype(first)::value) {
+      trip(0, pre, acc);
+      kb = 16 * WB;
+    }
+    // the (clamped) 16-byte weight loads of a trip are all in flight together, then its MFMA chain runs
+    for (; kb < K; kb += 16 * WB) {
+      float4 bv[WB];
 #pragma unroll
-      for (int u = 0; u < WB; ++u) bv[u] = wp[(int64_t)min(kb + 4 * u, K - 4) * S.xldw];
-#pragma unroll
-      for (int u = 0; u < WB; ++u)
-        if (kb + 4 * u < K) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(hp[(kb + 4 * u) * LDH], bv[u], acc, 0, 0, 0);
+      for (int i = 0; i < WB; ++i) bv[i] = *reinterpret_cast<const float4*>(wrow + min(kb + 16 * i, K16 - 16));
+      trip(kb, bv, acc);
     }
     // D layout: column = lane & 15, row = (lane >> 4) * 4 + reg
     if (col < S.xN) {
@@ -763,13 +811,19 @@ __device__ __forceinline__ void agg_bwd_dx_tile(const TAggArgs& a, const TAggSrc
         S.xg[(int64_t)row * S.xldg + col] = v;
       }
     }
+  };
+  if constexpr (EARLY) {
+    if (w < n_ct) tile(w, std::true_type());
+    for (int ct = w + 4; ct < n_ct; ct += 4) tile(ct, std::false_type());
+  } else {
+    for (int ct = w; ct < n_ct; ct += 4) tile(ct, std::false_type());
   }
   KT(10);
 }
 
 template <int GS>
 __global__ __launch_bounds__(256) void agg_bwd_dx_kernel(const TAggArgs a) {
-  extern __shared__ float Hs[];  // [ncols][17]
+  extern __shared__ float Hs[];  // [roundup16(ncols)][17]
   if ((int)blockIdx.x == a.total_blocks) {
     finalize_loss(a.fin_row_lv, a.fin_rows, a.fin_out2, a.fin_state);
     return;
@@ -1597,6 +1651,8 @@ int agg_bwd_dx_launch(TAggArgs& a, hipStream_t st) {
   for (int i = 0; i < a.n; ++i) {
     kmax = a.s[i].ncols > kmax ? a.s[i].ncols : kmax;
     HMP_CHECK_ARG((a.s[i].ncols & 3) == 0, "agg_bwd_dx: ncols must be padded to 4");
+    HMP_CHECK_ARG(!a.s[i].xwt || (a.s[i].xldt == ((a.s[i].ncols + 15) & ~15) && a.s[i].xN > 0),
+                  "agg_bwd_dx: transposed weights of %d columns with leading dimension %d", a.s[i].ncols, a.s[i].xldt);
   }
   if (a.n == 0 || Fmax == 0) {
     if (!a.fin_row_lv) return HMP_OK;
@@ -1606,7 +1662,7 @@ int agg_bwd_dx_launch(TAggArgs& a, hipStream_t st) {
   const int blocks = agg_layout_tiles(a);
   if (blocks == 0 && !a.fin_row_lv) return HMP_OK;
   const int grid = blocks + (a.fin_row_lv ? 1 : 0);
-  const size_t smem = (size_t)kmax * 17 * sizeof(float);
+  const size_t smem = (size_t)((kmax + 15) & ~15) * 17 * sizeof(float);  // the last k block of 16 is whole (zero rows)
   sync_bstart(a);
   switch (agg_tile_gs(Fmax)) {
     case 16: hipLaunchKernelGGL((agg_bwd_dx_kernel<16>), dim3(grid), dim3(256), smem, st, a); break;

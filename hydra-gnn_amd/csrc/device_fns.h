@@ -15,13 +15,15 @@ __device__ __forceinline__ int find_seg(const int64_t* __restrict__ off, int B, 
 }
 
 
-// One packed element per lane: item = (packed row, 64-column chunk) of segment S, one wavefront per item.
-__device__ __forceinline__ void pack_item(const PackSeg& S, int item, const float* __restrict__ params, float* __restrict__ packed) {
+// One packed element: item = (packed row, 64-column chunk) of segment S, lane = column inside the chunk.  Callable on the host
+// too, where tools/pack_transpose_check.cpp walks the destinations of a segment table.
+__host__ __device__ __forceinline__ void pack_lane(const PackSeg& S, int item, int lane, const float* __restrict__ params,
+                                                   float* __restrict__ packed) {
   const int chunks = (S.ld_dst + 63) >> 6;
   const int r = item / chunks;
   if (r >= S.rows_pad) return;
   float* dst = packed + S.dst + (int64_t)r * S.ld_dst;
-  const int c = (item % chunks) * 64 + (threadIdx.x & 63);
+  const int c = (item % chunks) * 64 + lane;
   if (c >= S.ld_dst) return;
   float v = 0.f;
   if (S.kind == PACK_SUM) {
@@ -67,6 +69,16 @@ __device__ __forceinline__ void pack_item(const PackSeg& S, int item, const floa
     }
   }
   dst[c] = v;
+  if (S.ld_dst_t > 0) {  // transposed image: the same value in row c, and this row's share of the zero padding
+    float* dt = packed + S.dst_t + (int64_t)c * S.ld_dst_t;
+    dt[wpt_col(S.col_t + r)] = v;
+    for (int p = r; p < S.pad_t; p += S.rows_pad) dt[wpt_col(S.col_t + S.rows_pad + p)] = 0.f;
+  }
+}
+
+// One packed element per lane, one wavefront per item.
+__device__ __forceinline__ void pack_item(const PackSeg& S, int item, const float* __restrict__ params, float* __restrict__ packed) {
+  pack_lane(S, item, (int)(threadIdx.x & 63), params, packed);
 }
 
 // One pack block (256 threads): one wavefront per item; `blk` indexes the SegBlocks table (4 items per block).

@@ -342,11 +342,12 @@ struct TAggSrc {
   int ldgr, roff, Froot;
   int n_out;
   int block_start;
-  // fused input gradient (agg_bwd_dx_launch): xg = (dz * xw) . act'(xh), xw = Wp[l][s] [ncols][xldw]
-  const float* xw;  // null: no input gradient for this node type
+  // fused input gradient (agg_bwd_dx_launch): xg = (dz * Wp[l][s]) . act'(xh), the weights read from their transposed image
+  // xwt = WpT[l][s] [fpad(xN)][xldt] (PackSeg::dst_t, columns in the order of wpt_col): xldt = ncols rounded up to 16, padding zero
+  const float* xwt;  // null: no input gradient for this node type
   float* xg;
   const float* xh;  // activations whose derivative masks xg (null: none)
-  int xldw, xN, xldg, xldh, xact, xdrop_on;
+  int xldt, xN, xldg, xldh, xact, xdrop_on;
   float xscale;
   int win_out;                // filled by agg_bwd_launch (see AggDst::win_in)
   int tile_rows;              // agg_bwd_dx_launch: rows per workgroup, 16 or 8 (see AggDst::tile_rows)
@@ -395,7 +396,17 @@ struct PackSeg {
   int kind, H, C, Cp;
   int64_t att;      // PACK_ATTDOT*: float offset of the attention vector [H*C]
   int64_t src[AGG_MAX_IN];  // float offsets into the flat parameter buffer (summed)
+  // PACK_SUM, ld_dst_t > 0: the same element (r, c) is also stored at dst_t + c * ld_dst_t + wpt_col(col_t + r) -- the transposed
+  // image WpT of the stacked weights that the fused input gradient reads (TAggSrc::xwt); dst_t = start of the image, col_t = the
+  // segment's first row in the stack.  pad_t: stacked rows behind the segment's own rows_pad that it stores as zeros (the last
+  // segment of a stack pads the image to ld_dst_t)
+  int64_t dst_t;
+  int ld_dst_t, col_t, pad_t;
 };
+// Column of WpT that holds stacked row k = 16 b + 4 u + q: 16 b + 4 q + u.  The 16 bytes a lane of quarter q loads at column
+// 16 b + 4 q are then the rows 16 b + 4 u + q, u = 0..3: MFMA step 4 b + u multiplies rows 16 b + 4 u .. + 3, one per quarter, in
+// the order of a walk down Wp itself -- the sum over k is taken in the same order, bit for bit, as from the untransposed operand.
+__host__ __device__ inline int wpt_col(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
 // block -> segment map of the table-driven kernels: segment i owns blocks [start[i], start[i+1]); passed by value so the
 // lookup is a scan of scalar (kernarg) loads instead of a dependent chain of global loads
 constexpr int SEG_MAX = 400;

@@ -55,6 +55,10 @@ struct LayerLayout {
   int roff[HMP_MAX_NODE_TYPES];       // SAGE root segment column in Z[l][t], -1 if none
   int64_t wp_off[HMP_MAX_NODE_TYPES]; // packed weights [ncols][ldw]
   int ldw[HMP_MAX_NODE_TYPES];
+  // SAGE layers l >= 1: transposed image WpT [ldw][ldt] of the same weights (columns in the order of wpt_col, kernels.h), ldt =
+  // ncols rounded up to 16 with zero padding, written by the pack items that write Wp (PackSeg::dst_t) and read by the fused input gradient; ldt = 0: none
+  int64_t wpt_off[HMP_MAX_NODE_TYPES];
+  int ldt[HMP_MAX_NODE_TYPES];
   int64_t bias_off[HMP_MAX_NODE_TYPES];
   int64_t slab_off[HMP_MAX_NODE_TYPES];   // packed-gradient slabs [max_slabs][ncols][lddw]
   int lddw[HMP_MAX_NODE_TYPES];
@@ -342,6 +346,9 @@ int build_layout(hmp_net* n) {
       Y.lddw[t] = fpad(n->dim[l][t] + 1);
       Y.wp_off[t] = packed;
       packed += (int64_t)Y.ncols[t] * Y.ldw[t];
+      Y.wpt_off[t] = packed;
+      Y.ldt[t] = (l >= 1 && Y.kind == HMP_CONV_SAGE && Y.ncols[t] > 0) ? ((Y.ncols[t] + 15) & ~15) : 0;
+      packed += (int64_t)Y.ldw[t] * Y.ldt[t];
       Y.bias_off[t] = packed;
       packed += (Y.n_in[t] > 0) ? fpad(Ls.out_dim[t]) : 0;
       Y.slab_off[t] = slabs;
@@ -412,6 +419,15 @@ int build_tables(hmp_net* n) {
   std::vector<GradSeg> gs;
   std::vector<int64_t> ges;
   int64_t prow = 0, gel = 0;
+  // transposed destination of a PACK_SUM segment that fills rows [coff, coff + rows_pad) of Wp[l][t]: columns of WpT[l][t]; the
+  // segment that ends the stack also zeroes the padding columns up to ldt
+  auto with_wpt = [&](PackSeg& s, const LayerLayout& Y, int t, int coff) {
+    if (Y.ldt[t] == 0) return;
+    s.dst_t = Y.wpt_off[t];
+    s.col_t = coff;
+    s.ld_dst_t = Y.ldt[t];
+    s.pad_t = coff + s.rows_pad == Y.ncols[t] ? Y.ldt[t] - Y.ncols[t] : 0;
+  };
   auto push_pack = [&](const PackSeg& s) {
     ps.push_back(s); prs.push_back(prow); prow += s.rows_pad;
     if (s.rows_pad > n->max_pack_rows) n->max_pack_rows = s.rows_pad;
@@ -437,6 +453,7 @@ int build_tables(hmp_net* n) {
         s.dst = Q.agg_first ? Q.wc_off : Y.wp_off[C.src] + (int64_t)Q.coff * Y.ldw[C.src];
         s.rows = C.f_out; s.rows_pad = fpad(C.f_out); s.cols = fs; s.ld_dst = Y.ldw[C.src]; s.ld_src = fs;
         s.nsrc = 1; s.src[0] = C.w0;
+        if (!Q.agg_first) with_wpt(s, Y, C.src, Q.coff);
         push_pack(s);
         GradSeg g;
         memset(&g, 0, sizeof(g));
@@ -538,7 +555,10 @@ int build_tables(hmp_net* n) {
         g.t[0] = term(GT_COPY, slab_id_w(l, t), root + ft, Y.lddw[t], fo, fo);
         push_grad(g);
       }
-      if (Y.kind == HMP_CONV_SAGE) push_pack(s);
+      if (Y.kind == HMP_CONV_SAGE) {
+        with_wpt(s, Y, t, Y.roff[t] < 0 ? 0 : Y.roff[t]);
+        push_pack(s);
+      }
       push_pack(b);
     }
   }
@@ -1368,7 +1388,8 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           if (Y.ncols[s] == 0 || b->n_nodes[s] == 0) continue;
           TAggSrc& T = a.s[ai++];
           if (!n->G[l][s]) continue;  // passthrough input of layer 1: no gradient wanted
-          T.xw = n->d_packed + Y.wp_off[s]; T.xldw = Y.ldw[s]; T.xN = n->dim[l][s];
+          HMP_CHECK_ARG(Y.ldt[s] > 0, "net: layer %d type %d has no transposed weight image for the fused input gradient", l, s);
+          T.xwt = n->d_packed + Y.wpt_off[s]; T.xldt = Y.ldt[s]; T.xN = n->dim[l][s];
           T.xg = n->G[l][s]; T.xldg = n->ld[l][s];
           T.xdrop_on = (n->training && Lp.dropout > 0.f) ? 1 : 0;
           T.xact = Lp.act;
