@@ -283,6 +283,9 @@ SIGNATURES = {
     "hmp_frame_batch_pack": (C.c_int, [_VP, _VP, _I64]),
     "hmp_frame_batch_destroy": (None, [_VP]),
     "hmp_frame_expand_batch": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "hmp_store_derive": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
+    "hmp_store_node_split": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "hmp_store_member_counts": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),
 }
 
 # include/hydra_mp.h section 14: indices of hmp_frame_sizes, words of an item of the staging block's table
@@ -303,7 +306,13 @@ FRAME_MAX_ITEMS, FRAME_BATCH_MAX_ITEMS = 64, 4096
 FT_BATCH, FTB_BATCH, FTB_NODE_PTR, FTB_EDGE_PTR, FTB_Y, FT_BATCH_COUNT = 54, 0, 6, 12, 27, 33
 FT_HTREL, FT_HTREL_COUNT = 87, 17  # what FRAME_RELPOS_HTREE adds: pos of the two clique types, edge_attr of the 15 H-tree edge types
 
-COLLATE_MAX_ITEMS, COLLATE_MAX_SLOTS = 40, 24  # csrc/collate.hip CB_MAX_ITEMS / CB_MAX_SLOTS: arrays and types of one collation launch
+# include/hydra_mp.h section 15: words of an item of hmp_store_derive's table, item kinds
+SD_ITEM_WORDS, SD_MAX_ITEMS = 16, 4096
+(SD_KIND, SD_BLOCK0, SD_SRC, SD_DST, SD_SRC_PTR, SD_DST_OFF, SD_N, SD_SRC_W, SD_SKIP, SD_TAKE, SD_DST_W, SD_A0, SD_A1, SD_A2, SD_A3,
+ SD_UNIT) = range(16)
+SD_ROWS, SD_FILL, SD_EDGES, SD_RELPOS = range(4)
+
+COLLATE_MAX_ITEMS, COLLATE_MAX_SLOTS = 40, 24 # csrc/collate.hip CB_MAX_ITEMS / CB_MAX_SLOTS: arrays and types of one collation launch
 
 ABI_VERSION = 4  # the HMP_ABI_VERSION of include/hydra_mp.h this binding was written against (tests/test_abi.py compares them)
 

@@ -213,8 +213,14 @@ class BaseTrainingJob:
         return "rooms" if self._network_type == "baseline" else "room_virtual"
 
     def _store(self, name, dataset, device):
-        from .store import GraphStore
+        from .store import GraphStore, StoreDataset
 
+        if isinstance(dataset, StoreDataset):  # already resident: the dataset's own store, no host graphs in between
+            if dataset.store.device != device:
+                raise _lib.HydraMPError(f"the StoreDataset's store lives on {dataset.store.device}, the job runs on {device}")
+            if self._stores.get(name) is None or self._stores[name][1] is not dataset:
+                self._stores[name] = (dataset.store, dataset, {})
+            return dataset.store
         hit = self._stores.get(name)
         if hit is None or hit[0].device != device or hit[1] is not dataset:
             hit = (GraphStore([dataset[i] for i in range(len(dataset))], device), dataset, {})

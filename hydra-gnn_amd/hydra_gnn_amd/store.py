@@ -19,6 +19,10 @@ stored under the names the homogeneous models present to the executor (node type
 ``pool_edge_index`` -> ``pool``, ``init_edge_index`` -> ``init``).  A stream created for a two-headed model carries the labels and
 masks of both heads in its own buffers (``tests/test_gpu_semisupervised_stream.py``); a stream created for a homogeneous room
 classifier carries ``room_mask`` and the room-masked labels (``tests/test_gpu_homog_room_stream.py``).
+
+A resident store is also where the configurations come from: ``with_relative_pos`` / ``to_homogeneous`` / ``remove_last_features``
+return the store of the transformed graphs from one launch of ``csrc/store_derive.hip``, ``generate_node_split`` writes the Stanford
+protocol's per-run masks in place, and :class:`StoreDataset` hands a store to the training jobs (second half of this module).
 """
 from __future__ import annotations
 
@@ -670,3 +674,504 @@ def _graphstore_stream(self, net, batch_size: int, label_type: Optional[str] = N
 
 
 GraphStore.stream = _graphstore_stream
+
+
+# =====================================================================================================================
+# Derived stores: the reference derives every configuration from ONE loaded dataset in place (train_mp3d.py:130-137,
+# train_Stanford.py:87-99: compute_relative_pos for GAT_edge, to_homogeneous, remove_last_features for --remove_word2vec) and
+# draws a node split per run (train_Stanford.py:166-171).  A resident store does the same without host graphs: the host
+# plans destination offsets and an item table in numpy over the offset vectors the store keeps, uploads both in one block,
+# and ``hmp_store_derive`` (csrc/store_derive.hip) writes every output in ONE launch.
+# =====================================================================================================================
+def _derive_alloc(shape, dtype, device) -> torch.Tensor:
+    """every output of a derive launch and every mask row of a node split is allocated here (the tests patch it to pre-fill the
+    outputs, so that an element the launch never writes cannot pass by luck)"""
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def plan_concat(counts: Sequence[np.ndarray]):
+    """Per-graph concatenation of ``len(counts)`` parts (node types of a homogeneous graph, edge types of one edge list), part
+    after part inside a graph and graph after graph: ``counts[p][g]`` rows of part ``p`` in graph ``g``.  Returns
+    ``(ptr [G + 1], inside [P][G], dst [P][G])``: the row offsets of the graphs in the concatenation, where part ``p`` starts inside
+    graph ``g``'s range, and the same as an absolute row -- what ``torch.cat`` of every graph's parts, then of the graphs, lays out
+    (``data.heterogeneous_data_to_homogeneous`` followed by ``GraphStore``).  Pure numpy; no part: ``ptr`` needs ``n_graphs``."""
+    c = np.asarray(counts, dtype=np.int64)
+    assert c.ndim == 2 and c.shape[0] > 0
+    inside = np.cumsum(c, axis=0) - c
+    ptr = np.concatenate([[0], np.cumsum(c.sum(axis=0))]).astype(np.int64)
+    return ptr, inside, inside + ptr[:-1][None, :]
+
+
+def _unit_of(*byte_values: int) -> int:
+    """the widest unit (16 / 4 / 1 bytes) that divides every width, skip and base address of a rows item"""
+    for u in (16, 4):
+        if all(int(v) % u == 0 for v in byte_values):
+            return u
+    return 1
+
+
+class DerivePlan:
+    """The item table and the offset vectors of one ``hmp_store_derive`` launch, planned without a device: arrays enter by address
+    (plain ints), offset vectors as numpy arrays that :meth:`pack` lays out behind the item table.  An item is a list of
+    ``_lib.SD_ITEM_WORDS`` ints whose vector fields hold ``("vec", index)`` until :meth:`pack` resolves them."""
+
+    THREADS, MAX_BLOCKS = 256, 1024
+
+    def __init__(self, n_graphs: int):
+        self.G = int(n_graphs)
+        self.items: List[list] = []
+        self.work: List[int] = []  # threads' worth of work per item (destination units / rows / edges)
+        self.vectors: List[np.ndarray] = []
+        self._seen: Dict[bytes, int] = {}
+
+    def vector(self, v) -> Tuple[str, int]:
+        v = np.ascontiguousarray(v, dtype=np.int64)
+        key = v.tobytes()
+        if key not in self._seen:
+            self._seen[key] = len(self.vectors)
+            self.vectors.append(v)
+        return ("vec", self._seen[key])
+
+    def _item(self, kind, work, **f):
+        it = [0] * _lib.SD_ITEM_WORDS
+        it[_lib.SD_KIND] = kind
+        for k, v in f.items():
+            it[getattr(_lib, "SD_" + k)] = v
+        self.items.append(it)
+        self.work.append(int(work))
+
+    def rows(self, src: int, dst: int, src_ptr: int, dst_off, n: int, src_bytes: int, skip_bytes: int, take_bytes: int, dst_bytes: int):
+        """rows of ``src_bytes`` bytes -> rows of ``dst_bytes``: bytes ``[skip, skip + take)`` then zeros; ``dst_off`` [G] = where a
+        graph's rows start in the destination"""
+        assert 0 <= skip_bytes and 0 <= take_bytes <= dst_bytes and skip_bytes + take_bytes <= src_bytes
+        if n == 0 or dst_bytes == 0:
+            return
+        u = _unit_of(src_bytes, skip_bytes, take_bytes, dst_bytes, src, dst)
+        self._item(_lib.SD_ROWS, n * (dst_bytes // u), SRC=src, DST=dst, SRC_PTR=src_ptr, DST_OFF=self.vector(dst_off), N=n,
+                   SRC_W=src_bytes // u, SKIP=skip_bytes // u, TAKE=take_bytes // u, DST_W=dst_bytes // u, UNIT=u)
+
+    def fill(self, dst: int, count_ptr: int, dst_off, n: int, value: int, unit: int):
+        assert unit in (1, 8)
+        if n:
+            self._item(_lib.SD_FILL, n, DST=dst, SRC_PTR=count_ptr, DST_OFF=self.vector(dst_off), N=n, A0=int(value), UNIT=unit)
+
+    def edges(self, src: int, dst: int, edge_ptr: int, dst_off, n: int, shift_src, shift_dst, dst_total: int):
+        if n:
+            self._item(_lib.SD_EDGES, n, SRC=src, DST=dst, SRC_PTR=edge_ptr, DST_OFF=self.vector(dst_off), N=n, A0=self.vector(shift_src),
+                       A1=self.vector(shift_dst), A3=int(dst_total), UNIT=8)
+
+    def relpos(self, edge_index: int, dst: int, edge_ptr: int, n: int, pos_src: int, pos_dst: int, ptr_src: int, ptr_dst: int):
+        if n:
+            self._item(_lib.SD_RELPOS, n, SRC=edge_index, DST=dst, SRC_PTR=edge_ptr, N=n, A0=pos_src, A1=pos_dst, A2=ptr_src, A3=ptr_dst,
+                       UNIT=4)
+
+    def layout(self):
+        """``(words, item_word0, vector_word0 [n_vectors])`` of the block: group table (even count), items, vectors (16-byte aligned)"""
+        n = len(self.items)
+        n_groups = (n + 63) // 64
+        item0 = (n_groups + 1) & ~1
+        pos = item0 + n * _lib.SD_ITEM_WORDS
+        where = []
+        for v in self.vectors:
+            where.append(pos)
+            pos += (v.size + 1) & ~1
+        return pos, item0, where
+
+    def pack(self, base_addr: int):
+        """``(block int64 [words], n_blocks)`` for a block that will live at device address ``base_addr``"""
+        n = len(self.items)
+        if n > _lib.SD_MAX_ITEMS:
+            raise _lib.HydraMPError(f"the derive launch would run {n} items, its group table holds {_lib.SD_MAX_ITEMS}")
+        words, item0, where = self.layout()
+        block = np.zeros(max(words, 2), dtype=np.int64)
+        blocks = 0
+        for i, (it, w) in enumerate(zip(self.items, self.work)):
+            row = [base_addr + 8 * where[v[1]] if isinstance(v, tuple) else v for v in it]
+            row[_lib.SD_BLOCK0] = blocks
+            block[item0 + i * _lib.SD_ITEM_WORDS: item0 + (i + 1) * _lib.SD_ITEM_WORDS] = row
+            if i % 64 == 0:
+                block[i // 64] = blocks
+            blocks += min((w + self.THREADS - 1) // self.THREADS, self.MAX_BLOCKS)
+        for v, p in zip(self.vectors, where):
+            block[p:p + v.size] = v
+        return block, blocks
+
+
+def _run_plan(store: "GraphStore", plan: DerivePlan, keep: Sequence[np.ndarray] = ()):
+    """upload the plan's block (one copy) and launch; ``keep``: offset vectors the result needs on the device -- they travel in the
+    same block and come back as views of it"""
+    handles = [plan.vector(v) for v in keep]
+    words, _, where = plan.layout()
+    dev = torch.empty(max(words, 2), dtype=torch.int64, device=store.device)
+    block, n_blocks = plan.pack(dev.data_ptr())
+    dev.copy_(torch.from_numpy(block), non_blocking=False)
+    _lib.check(store.lib.hmp_store_derive(dev.data_ptr(), len(plan.items), n_blocks, store.n_graphs, _lib.stream_ptr()))
+    return [dev[where[h[1]]: where[h[1]] + plan.vectors[h[1]].size] for h in handles]
+
+
+def _derived(self: "GraphStore") -> "GraphStore":
+    """a store that shares every array with ``self`` (the containers are its own)"""
+    new = object.__new__(GraphStore)
+    new.device, new.lib, new.n_graphs, new.homogeneous = self.device, self.lib, self.n_graphs, self.homogeneous
+    new._stage = new._stage_dev = new._copied = None
+    new.node_types, new.edge_types = list(self.node_types), list(self.edge_types)
+    new.node_counts, new.count_only = dict(self.node_counts), dict(self.count_only)
+    new.node_attrs = {t: dict(a) for t, a in self.node_attrs.items()}
+    new.edge_index, new.edge_ptr, new.edge_ptr_host = dict(self.edge_index), dict(self.edge_ptr), dict(self.edge_ptr_host)
+    new.edge_rows = {e: dict(r) for e, r in self.edge_rows.items()}
+    new.edge_attr = {e: new.edge_rows[e]["edge_attr"] for e in self.edge_attr}
+    if self.homogeneous:
+        new.homo_keys, new.edge_name = list(self.homo_keys), dict(self.edge_name)
+    return new
+
+
+def _own_masks(new: "GraphStore", plan: DerivePlan) -> None:
+    """a derived store never shares mask rows with its parent (a later node split rewrites them in place): copy them in the launch"""
+    for t, attrs in new.node_attrs.items():
+        for k in DEFAULT_MASKS:
+            pk = attrs.get(k)
+            if pk is None:
+                continue
+            out = _derive_alloc(tuple(pk.data.shape), pk.data.dtype, new.device)
+            plan.rows(pk.data.data_ptr(), out.data_ptr(), pk.ptr.data_ptr(), pk.ptr_host[:-1], int(pk.ptr_host[-1]), pk.row_bytes, 0,
+                      pk.row_bytes, pk.row_bytes)
+            attrs[k] = _packed(out, pk.ptr, pk.ptr_host)
+
+
+def _features(self: "GraphStore", t: str, what: str) -> _Packed:
+    pk = self.node_attrs[t].get("x")
+    if pk is None:
+        raise _lib.HydraMPError(f"{what}: node type '{t}' has no features 'x'")
+    if pk.data.dtype != torch.float32 or pk.data.dim() != 2:
+        raise _lib.HydraMPError(f"{what}: 'x' of node type '{t}' must be a float32 matrix, the store holds {tuple(pk.data.shape[1:])} {pk.data.dtype}")
+    return pk
+
+
+def _narrow_x(self: "GraphStore", new: "GraphStore", plan: DerivePlan, t: str, pk: _Packed, skip: int, take: int) -> None:
+    n = int(pk.ptr_host[-1])
+    out = _derive_alloc((n, take), torch.float32, self.device)
+    plan.rows(pk.data.data_ptr(), out.data_ptr(), pk.ptr.data_ptr(), pk.ptr_host[:-1], n, pk.row_bytes, 4 * skip, 4 * take, 4 * take)
+    new.node_attrs[t]["x"] = _packed(out, pk.ptr, pk.ptr_host)
+
+
+def _with_relative_pos(self: "GraphStore") -> "GraphStore":
+    """The store of ``data.compute_relative_pos`` applied to every graph (reference ``mp3d_dataset.py:298-319``): every ``x`` loses its
+    three leading position columns and every edge type gains ``edge_attr = pos_dst[ei[1]] - pos_src[ei[0]]``.  A new store; the
+    receiver is unchanged and shares the arrays that do not change."""
+    what = "with_relative_pos"
+    if self.homogeneous:
+        raise _lib.HydraMPError(f"{what}: works on a typed store (derive the homogeneous one afterwards: .to_homogeneous())")
+    if self.edge_attr:
+        raise _lib.HydraMPError(f"{what}: the store already holds 'edge_attr' ({list(self.edge_attr)[0]})")
+    xs = {t: _features(self, t, what) for t in self.node_types}
+    for t, pk in xs.items():
+        if pk.data.size(1) < 3:
+            raise _lib.HydraMPError(f"{what}: 'x' of node type '{t}' is {pk.data.size(1)} wide, narrower than the 3 position columns")
+    pos = {}
+    for e in self.edge_types:
+        for t in (e[0], e[2]):
+            pk = self.node_attrs.get(t, {}).get("pos")
+            if pk is None:
+                raise _lib.HydraMPError(f"{what}: node type '{t}' (an end of {e}) has no positions 'pos'")
+            if pk.data.dtype != torch.float32 or pk.row_shape != (3,):
+                raise _lib.HydraMPError(f"{what}: 'pos' of node type '{t}' must be float32 [n, 3], the store holds {pk.row_shape} {pk.data.dtype}")
+            pos[t] = pk
+    new, plan = _derived(self), DerivePlan(self.n_graphs)
+    for t, pk in xs.items():
+        _narrow_x(self, new, plan, t, pk, 3, pk.data.size(1) - 3)
+    for e in self.edge_types:
+        ei = self.edge_index[e]
+        n = int(ei.size(1))
+        out = _derive_alloc((n, 3), torch.float32, self.device)
+        plan.relpos(ei.data_ptr(), out.data_ptr(), self.edge_ptr[e].data_ptr(), n, pos[e[0]].data.data_ptr(), pos[e[2]].data.data_ptr(),
+                    pos[e[0]].ptr.data_ptr(), pos[e[2]].ptr.data_ptr())
+        pk = _packed(out, self.edge_ptr[e], self.edge_ptr_host[e])
+        new.edge_attr[e] = pk
+        new.edge_rows[e] = {"edge_attr": pk}
+    _own_masks(new, plan)
+    _run_plan(self, plan)
+    return new
+
+
+def _remove_last_features(self: "GraphStore", dim: int) -> "GraphStore":
+    """The store of the reference's ``remove_last_features(dim)`` (``mp3d_dataset.py:286-296``): every ``x`` at least ``dim`` wide loses
+    its last ``dim`` columns, a narrower one is kept.  Typed and homogeneous stores."""
+    what = "remove_last_features"
+    dim = int(dim)
+    if dim <= 0:
+        raise _lib.HydraMPError(f"{what}: dim must be positive, got {dim}")
+    new, plan = _derived(self), DerivePlan(self.n_graphs)
+    for t in self.node_types:
+        if "x" not in self.node_attrs[t]:
+            continue
+        pk = _features(self, t, what)
+        if pk.data.size(1) >= dim:
+            _narrow_x(self, new, plan, t, pk, 0, pk.data.size(1) - dim)
+    _own_masks(new, plan)
+    _run_plan(self, plan)
+    return new
+
+
+def _to_homogeneous(self: "GraphStore") -> "GraphStore":
+    """The homogeneous store of the same graphs.  Without ``object_virtual`` / ``room_virtual`` node types:
+    ``data.heterogeneous_data_to_homogeneous`` per graph plus ``room_mask = node_type == index("rooms")``; with them:
+    ``data.heterogeneous_htree_to_homogeneous`` (reference ``mp3d_dataset.py:29-119``).  Node types with ``x`` take part, in store order;
+    features are zero-padded to the widest type."""
+    what = "to_homogeneous"
+    if self.homogeneous:
+        raise _lib.HydraMPError(f"{what}: the store is homogeneous already")
+    types = [t for t in self.node_types if "x" in self.node_attrs[t]]
+    if not types:
+        raise _lib.HydraMPError(f"{what}: no node type has features 'x'")
+    xs = {t: _features(self, t, what) for t in types}
+    htree = "object_virtual" in types and "room_virtual" in types
+    if not htree and "rooms" not in types:
+        raise _lib.HydraMPError(f"{what}: no node type 'rooms' with features 'x' (room_mask marks its rows)")
+    virtual = ("object_virtual", "room_virtual") if htree else ()
+    group_of = {}
+    for e in self.edge_types:
+        for t in (e[0], e[2]):
+            if t not in types:
+                raise _lib.HydraMPError(f"{what}: edge type {e} touches node type '{t}', which has no features 'x'")
+        if e[0] in virtual and e[2] in virtual:
+            raise _lib.HydraMPError(f"{what}: edge type {e} has a virtual node type at both ends (it would be an init and a pool edge)")
+        group_of[e] = "init_edge_index" if e[0] in virtual else "pool_edge_index" if e[2] in virtual else "edge_index"
+    G, dev = self.n_graphs, self.device
+    width = max(int(pk.data.size(1)) for pk in xs.values())
+    # labels: every type has them, or (H-tree) room_virtual has them and the others are filled with -1
+    ys = {t: self.node_attrs[t].get("y") for t in types}
+    if htree and ys["room_virtual"] is not None:
+        has_y = True
+    else:
+        has_y = all(v is not None for v in ys.values())
+    if has_y:
+        y0 = ys["room_virtual"] if htree else ys[types[0]]
+        for t, pk in ys.items():
+            if pk is not None and (pk.data.dtype != y0.data.dtype or pk.row_shape != ()):
+                raise _lib.HydraMPError(f"{what}: 'y' of node type '{t}' is {pk.row_shape} {pk.data.dtype}, expected a {y0.data.dtype} vector")
+        if any(v is None for v in ys.values()) and y0.data.dtype != torch.int64:
+            raise _lib.HydraMPError(f"{what}: 'y' must be int64 for the -1 rows of the node types without labels, the store holds {y0.data.dtype}")
+    has_ea = len(self.edge_types) > 0 and all(e in self.edge_attr for e in self.edge_types)
+    if has_ea:
+        ea0 = self.edge_attr[self.edge_types[0]]
+        for e in self.edge_types:
+            if self.edge_attr[e].row_shape != ea0.row_shape or self.edge_attr[e].data.dtype != ea0.data.dtype:
+                raise _lib.HydraMPError(f"{what}: 'edge_attr' of {e} is {self.edge_attr[e].row_shape}, of {self.edge_types[0]} {ea0.row_shape}")
+
+    plan = DerivePlan(G)
+    node_ptr, inside, node_dst = plan_concat([self.node_counts[t] for t in types])
+    N = int(node_ptr[-1])
+    x = _derive_alloc((N, width), torch.float32, dev)
+    node_type = _derive_alloc((N,), torch.int64, dev)
+    y = _derive_alloc((N,), y0.data.dtype, dev) if has_y else None
+    room_mask = _derive_alloc((N,), torch.bool, dev)
+    object_mask = _derive_alloc((N,), torch.bool, dev) if htree else None
+    room_type = "room_virtual" if htree else "rooms"
+    for i, t in enumerate(types):
+        pk = xs[t]
+        n = int(pk.ptr_host[-1])
+        assert np.array_equal(pk.counts, self.node_counts[t])
+        cp = pk.ptr.data_ptr()
+        plan.rows(pk.data.data_ptr(), x.data_ptr(), cp, node_dst[i], n, pk.row_bytes, 0, pk.row_bytes, 4 * width)
+        plan.fill(node_type.data_ptr(), cp, node_dst[i], n, i, 8)
+        if has_y and ys[t] is not None:
+            plan.rows(ys[t].data.data_ptr(), y.data_ptr(), ys[t].ptr.data_ptr(), node_dst[i], n, ys[t].row_bytes, 0, ys[t].row_bytes, ys[t].row_bytes)
+        elif has_y:
+            plan.fill(y.data_ptr(), cp, node_dst[i], n, -1, 8)
+        plan.fill(room_mask.data_ptr(), cp, node_dst[i], n, int(t == room_type), 1)
+        if htree:
+            plan.fill(object_mask.data_ptr(), cp, node_dst[i], n, int(t == "object_virtual"), 1)
+    groups = ["edge_index"] + (["init_edge_index", "pool_edge_index"] if htree else [])
+    edge_out, edge_ptr_host = {}, {}
+    edge_type = edge_attr = None
+    for name in groups:
+        members = [e for e in self.edge_types if group_of[e] == name]
+        if members:
+            eptr, _, edst = plan_concat([np.diff(self.edge_ptr_host[e]) for e in members])
+        else:
+            eptr, edst = np.zeros(G + 1, dtype=np.int64), None
+        E = int(eptr[-1])
+        out = _derive_alloc((2, E), torch.int64, dev)
+        edge_out[name], edge_ptr_host[name] = out, eptr
+        if name == "edge_index":
+            edge_type = _derive_alloc((E,), torch.int64, dev)
+            if has_ea:
+                edge_attr = _derive_alloc((E,) + ea0.row_shape, ea0.data.dtype, dev)
+        for j, e in enumerate(members):
+            n = int(self.edge_ptr_host[e][-1])
+            ep = self.edge_ptr[e].data_ptr()
+            plan.edges(self.edge_index[e].data_ptr(), out.data_ptr(), ep, edst[j], n, inside[types.index(e[0])], inside[types.index(e[2])], E)
+            if name == "edge_index":
+                plan.fill(edge_type.data_ptr(), ep, edst[j], n, self.edge_types.index(e), 8)
+                if has_ea:
+                    pk = self.edge_attr[e]
+                    plan.rows(pk.data.data_ptr(), edge_attr.data_ptr(), ep, edst[j], n, pk.row_bytes, 0, pk.row_bytes, pk.row_bytes)
+    dev_vecs = _run_plan(self, plan, keep=[node_ptr] + [edge_ptr_host[name] for name in groups])
+    node_ptr_dev, edge_ptr_dev = dev_vecs[0], dict(zip(groups, dev_vecs[1:]))
+
+    new = object.__new__(GraphStore)
+    new.device, new.lib, new.n_graphs, new.homogeneous = dev, self.lib, G, True
+    new._stage = new._stage_dev = new._copied = None
+    new.homo_keys = (["x", "node_type", "edge_index", "edge_type"] + (["y"] if has_y else []) + (["edge_attr"] if has_ea else [])
+                     + groups[1:] + ["room_mask"] + (["object_mask"] if htree else []))
+    new.node_types, new.node_counts, new.count_only = [HOMO_NODE], {HOMO_NODE: np.diff(node_ptr)}, {HOMO_NODE: False}
+    arrays = {"x": x, "node_type": node_type, "y": y, "room_mask": room_mask, "object_mask": object_mask}
+    new.node_attrs = {HOMO_NODE: {k: _packed(arrays[k], node_ptr_dev, node_ptr) for k in new.homo_keys if k in arrays}}
+    new.edge_types, new.edge_name = [], {}
+    new.edge_index, new.edge_ptr, new.edge_ptr_host, new.edge_attr, new.edge_rows = {}, {}, {}, {}, {}
+    for name in groups:
+        e = homo_edge_type(name)
+        new.edge_types.append(e)
+        new.edge_name[e] = name
+        new.edge_index[e], new.edge_ptr[e], new.edge_ptr_host[e] = edge_out[name], edge_ptr_dev[name], edge_ptr_host[name]
+    e0 = homo_edge_type("edge_index")
+    new.edge_rows[e0] = {"edge_type": _packed(edge_type, new.edge_ptr[e0], new.edge_ptr_host[e0])}
+    if has_ea:
+        new.edge_attr[e0] = new.edge_rows[e0]["edge_attr"] = _packed(edge_attr, new.edge_ptr[e0], new.edge_ptr_host[e0])
+    return new
+
+
+# ---- node split -----------------------------------------------------------------------------------------------------------
+def node_split_assignment(total: int, ratios, seed: int = 0) -> np.ndarray:
+    """The shuffled assignment list of the reference's ``generate_node_split`` (``Stanford3DSG_dataset.py:462-492``) as an int8
+    vector: 1 train, 2 val, 3 test, 0 unassigned (ratios that sum to less than 1).  ``ratios = (train, val, test)``, ``test`` may be
+    None (= the rest).  The stdlib ``random`` in the reference's order of calls: exact by construction."""
+    import random
+
+    train, val, test = ratios
+    random.seed(seed)
+    assert train > 0
+    assert val >= 0
+    if test is None:
+        test = 1 - train - val
+    assert test >= 0
+    assert train + val + test <= 1
+    total = int(total)
+    n_train, n_val = round(total * train), round(total * val)
+    if train + val + test == 1:
+        n_test = total - n_train - n_val
+        out = [1] * n_train + [2] * n_val + [3] * n_test
+    else:
+        n_test = round(total * test)
+        out = [1] * n_train + [2] * n_val + [3] * n_test + [0] * (total - n_train - n_val - n_test)
+    random.shuffle(out)
+    if len(out) != total:
+        raise _lib.HydraMPError(f"node split: the ratios {tuple(ratios)} assign {len(out)} of {total} nodes")
+    return np.array(out, dtype=np.int8)
+
+
+def _split_layout(self: "GraphStore"):
+    """``(data type, parts)`` of the reference's ``data_type()``: the node types whose rows a split assigns, in its order"""
+    if self.homogeneous:
+        attrs = self.node_attrs[HOMO_NODE]
+        return ("homogeneous_htree" if "object_mask" in attrs and "room_mask" in attrs else "homogeneous"), [HOMO_NODE]
+    if "object_virtual" in self.node_types and "room_virtual" in self.node_types:
+        return "heterogeneous_htree", ["object_virtual", "room_virtual"]
+    for t in ("objects", "rooms"):
+        if t not in self.node_types:
+            raise _lib.HydraMPError(f"generate_node_split: the store holds no node type '{t}'")
+    return "heterogeneous", ["objects", "rooms"]
+
+
+def _generate_node_split(self: "GraphStore", train_node_ratio, val_node_ratio, test_node_ratio, seed=0) -> None:
+    """``Stanford3DSG_dataset.generate_node_split`` (reference ``:459-578``) on the resident store: ``train_mask`` / ``val_mask`` /
+    ``test_mask`` of the node types the data type splits, written by one launch from one uploaded assignment vector.  The first call
+    allocates the mask rows; later calls rewrite them in place, so an open stream's next batch carries the new split."""
+    G, dev, lib = self.n_graphs, self.device, self.lib
+    kind, parts = _split_layout(self)
+    state = self.__dict__.setdefault("_split", {})
+    if "ptr" not in state:  # [G + 1] row offsets of the parts on the device, and the members per graph
+        state["ptr"] = {}
+        for t in parts:
+            any_pk = next(iter(self.node_attrs[t].values()), None)
+            host = np.concatenate([[0], np.cumsum(self.node_counts[t])]).astype(np.int64)
+            state["ptr"][t] = (any_pk.ptr if any_pk is not None else torch.from_numpy(host).to(dev), host)
+        if kind == "homogeneous_htree":
+            attrs = self.node_attrs[HOMO_NODE]
+            for k in ("object_mask", "room_mask"):
+                if attrs[k].data.dtype != torch.bool or attrs[k].row_shape != ():
+                    raise _lib.HydraMPError(f"generate_node_split: '{k}' must be a bool vector, the store holds {attrs[k].row_shape} {attrs[k].data.dtype}")
+            counts = torch.empty((2, G), dtype=torch.int64, device=dev)
+            _lib.check(lib.hmp_store_member_counts(attrs["object_mask"].data.data_ptr(), attrs["room_mask"].data.data_ptr(),
+                                                   state["ptr"][HOMO_NODE][0].data_ptr(), G, counts.data_ptr(), _lib.stream_ptr()))
+            state["members"] = counts.cpu().numpy().sum(axis=0)  # the one device-to-host read, on the first call
+        else:
+            state["members"] = np.sum([self.node_counts[t] for t in parts], axis=0).astype(np.int64)
+    members = state["members"]
+    assign = node_split_assignment(int(members.sum()), (train_node_ratio, val_node_ratio, test_node_ratio), seed)
+    off = np.concatenate([[0], np.cumsum(members)]).astype(np.int64)
+    buf = np.concatenate([off.view(np.uint8), assign.view(np.uint8), np.zeros(1, dtype=np.uint8)])
+    block = torch.from_numpy(buf).to(dev)  # one upload: [G + 1] offsets, then the assignments
+    rows = []
+    for t in parts:
+        attrs = self.node_attrs[t]
+        ptr_dev, ptr_host = state["ptr"][t]
+        for k in DEFAULT_MASKS:
+            pk = attrs.get(k)
+            if pk is None:
+                pk = attrs[k] = _packed(_derive_alloc((int(ptr_host[-1]),), torch.bool, dev), ptr_dev, ptr_host)
+                if self.homogeneous:
+                    self.homo_keys.append(k)
+            elif pk.data.dtype != torch.bool or pk.row_shape != ():
+                raise _lib.HydraMPError(f"generate_node_split: '{k}' of node type '{t}' must be a bool vector, the store holds "
+                                        f"{pk.row_shape} {pk.data.dtype}")
+            rows.append(pk.data.data_ptr())
+    rows += [None] * (6 - len(rows))
+    ranked = kind == "homogeneous_htree"
+    attrs = self.node_attrs[parts[0]]
+    _lib.check(lib.hmp_store_node_split(block.data_ptr() + 8 * (G + 1), block.data_ptr(), G, state["ptr"][parts[0]][0].data_ptr(),
+                                        state["ptr"][parts[1]][0].data_ptr() if len(parts) > 1 else None,
+                                        attrs["object_mask"].data.data_ptr() if ranked else None,
+                                        attrs["room_mask"].data.data_ptr() if ranked else None, *rows, _lib.stream_ptr()))
+
+
+GraphStore.with_relative_pos = _with_relative_pos
+GraphStore.to_homogeneous = _to_homogeneous
+GraphStore.remove_last_features = _remove_last_features
+GraphStore.generate_node_split = _generate_node_split
+GraphStore.__len__ = lambda self: self.n_graphs
+
+
+class _StoreDatasetInfo:
+    """what the jobs read from ``dataset.get_data(0)``"""
+
+    def __init__(self, num_node_features, num_room_labels, num_object_labels):
+        self._f, self._r, self._o = num_node_features, num_room_labels, num_object_labels
+
+    def num_node_features(self):
+        return self._f
+
+    def num_room_labels(self):
+        return self._r
+
+    def num_object_labels(self):
+        return self._o
+
+
+class StoreDataset:
+    """A resident :class:`GraphStore` under the interface of the reference's dataset containers as far as the training jobs read
+    them (``jobs.py``): ``len``, ``data_type()``, ``get_data(0)`` with the three dimension accessors, ``generate_node_split``.  The jobs
+    use the store as it is -- no host graphs in between.  ``num_node_features``: an int (homogeneous) or a dict per node type."""
+
+    def __init__(self, store: GraphStore, data_type: str, num_node_features, num_room_labels: int, num_object_labels: Optional[int] = None):
+        if data_type not in ("homogeneous", "heterogeneous", "homogeneous_htree", "heterogeneous_htree"):
+            raise _lib.HydraMPError(f"StoreDataset: unknown data type '{data_type}'")
+        if (data_type.split("_")[0] == "homogeneous") != store.homogeneous:
+            raise _lib.HydraMPError(f"StoreDataset: data type '{data_type}' for a {'homogeneous' if store.homogeneous else 'typed'} store")
+        self.store, self._data_type = store, data_type
+        self._info = _StoreDatasetInfo(num_node_features, num_room_labels, num_object_labels)
+
+    def __len__(self):
+        return self.store.n_graphs
+
+    def __getitem__(self, i):
+        raise _lib.HydraMPError("a StoreDataset holds no host graphs: batches come from its store (store.collate / store.stream)")
+
+    def data_type(self):
+        return self._data_type
+
+    def get_data(self, i):
+        return self._info
+
+    def generate_node_split(self, train_node_ratio, val_node_ratio, test_node_ratio, seed=0):
+        self.store.generate_node_split(train_node_ratio, val_node_ratio, test_node_ratio, seed=seed)

@@ -1002,6 +1002,62 @@ void hmp_frame_batch_destroy(hmp_frame_batch* b);
 int hmp_frame_expand_batch(const void* d_staging, void* d_arena, const float* d_sem_table, int32_t sem_dim, int32_t n_items,
                            int32_t n_blocks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * 15. Derived variants of a device-resident dataset and its node split (csrc/store_derive.hip).  Replaces what the reference's
+ *     training scripts do to a loaded dataset in place: compute_relative_pos / to_homogeneous / remove_last_features
+ *     (mp3d_dataset.py:29-119, :286-319) and generate_node_split (Stanford3DSG_dataset.py:459-578).  The dataset is the packed form
+ *     of section 8: rows of all graphs back to back, graph-LOCAL int64 [2][E] edge lists, [G + 1] offset vectors.
+ *
+ *     hmp_store_derive: ONE launch runs a table of items that lives in device memory (ABI-4-compatible addition: the table is
+ *     plain int64 words, no struct).  Block: [group table: one int64 per 64 items = HMP_SD_BLOCK0 of the group's first item,
+ *     padded to an even count][n_items x HMP_SD_ITEM_WORDS].  An item walks the rows of ONE source array; row r of graph g
+ *     (HMP_SD_SRC_PTR[g] <= r < HMP_SD_SRC_PTR[g + 1]) goes to destination row HMP_SD_DST_OFF[g] + r - HMP_SD_SRC_PTR[g]:
+ *       HMP_SD_ROWS    units of HMP_SD_UNIT bytes (16 / 4 / 1; every width, SKIP and both arrays aligned to it): the destination row
+ *                      is DST_W units = source units [SKIP, SKIP + TAKE) of a row of SRC_W units, then zeros
+ *       HMP_SD_FILL    the value A0 as int64 (UNIT 8) or one byte (UNIT 1); SRC is unused, SRC_PTR gives the row counts
+ *       HMP_SD_EDGES   SRC int64 [2][N] -> DST int64 [2][A3]: row 0 + A0[g], row 1 + A1[g]  (A0 / A1: device int64 [G])
+ *       HMP_SD_RELPOS  SRC int64 [2][N] -> DST float [N][3] = A1[(A3[g] + SRC[1][j]) * 3 + c] - A0[(A2[g] + SRC[0][j]) * 3 + c]
+ *                      (A0 / A1: float32 positions of the source / destination node type, A2 / A3 their [G + 1] row offsets)
+ *     HMP_SD_N = rows (edges) of the source (> 0: a plan leaves empty arrays out), HMP_SD_BLOCK0 = the item's first workgroup; its
+ *     workgroups end at the next item's, the last item's at n_blocks, and an item with more work than its workgroups cover in one
+ *     pass walks it with a grid stride.  Pointers travel as int64 words.  No atomics: the plan owes that the items tile the outputs.
+ *     At most HMP_SD_MAX_ITEMS items (64 groups).
+ *
+ *     hmp_store_node_split: one wave per graph writes train / val / test byte rows from d_assign (int8: 0 unassigned, 1 / 2 / 3),
+ *     graph g's members starting at d_assign_off[g].  d_member_* null: part a's rows [d_ptr_a[g], d_ptr_a[g + 1]) take the first
+ *     assignments, part b's (d_ptr_b, null: none) the following ones.  d_member_* given (one node set, d_ptr_b null): the rows
+ *     with d_member_a are ranked first, then those with d_member_b; every other row is written false.
+ *     hmp_store_member_counts: d_counts [2][G] = rows with d_member_a / d_member_b per graph.
+ * ------------------------------------------------------------------------------------------- */
+#define HMP_SD_ITEM_WORDS 16
+#define HMP_SD_MAX_ITEMS 4096
+#define HMP_SD_KIND 0
+#define HMP_SD_BLOCK0 1
+#define HMP_SD_SRC 2
+#define HMP_SD_DST 3
+#define HMP_SD_SRC_PTR 4
+#define HMP_SD_DST_OFF 5
+#define HMP_SD_N 6
+#define HMP_SD_SRC_W 7
+#define HMP_SD_SKIP 8
+#define HMP_SD_TAKE 9
+#define HMP_SD_DST_W 10
+#define HMP_SD_A0 11
+#define HMP_SD_A1 12
+#define HMP_SD_A2 13
+#define HMP_SD_A3 14
+#define HMP_SD_UNIT 15
+#define HMP_SD_ROWS 0
+#define HMP_SD_FILL 1
+#define HMP_SD_EDGES 2
+#define HMP_SD_RELPOS 3
+int hmp_store_derive(const int64_t* d_block, int32_t n_items, int32_t n_blocks, int32_t n_graphs, void* stream);
+int hmp_store_node_split(const int8_t* d_assign, const int64_t* d_assign_off, int32_t n_graphs, const int64_t* d_ptr_a,
+                         const int64_t* d_ptr_b, const uint8_t* d_member_a, const uint8_t* d_member_b, uint8_t* d_train_a,
+                         uint8_t* d_val_a, uint8_t* d_test_a, uint8_t* d_train_b, uint8_t* d_val_b, uint8_t* d_test_b, void* stream);
+int hmp_store_member_counts(const uint8_t* d_member_a, const uint8_t* d_member_b, const int64_t* d_ptr, int32_t n_graphs,
+                            int64_t* d_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
