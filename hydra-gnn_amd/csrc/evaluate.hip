@@ -127,7 +127,51 @@ __global__ __launch_bounds__(256) void predict_rows_kernel(const float* __restri
   }
 }
 
+// labels[row][0:k) / probs[row][0:k) = the row's k largest entries and their softmax probabilities (tail_fns.h: topk_group), -1 / 0
+// for a row outside `members`.  VEC: 16-byte loads; else the same quads by scalar loads (a pitch or base without the alignment):
+// the lanes own the same columns either way, so the probabilities of a row do not depend on its layout.
+template <bool VEC>
+__global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ x, int ld, int n_rows, int n_classes,
+                                                        const uint8_t* __restrict__ members, int k, int64_t* __restrict__ labels,
+                                                        float* __restrict__ probs) {
+  const int lane = threadIdx.x % EV_GS;
+  for (int row = blockIdx.x * EV_RPB + (int)threadIdx.x / EV_GS; row < n_rows; row += gridDim.x * EV_RPB) {
+    // the member byte and the output addresses do not depend on the walk; the whole group of 16 lanes takes the same branch
+    const bool member = members ? members[row] != 0 : true;
+    int64_t* const lo = labels ? labels + (int64_t)row * k : nullptr;
+    float* const po = probs ? probs + (int64_t)row * k : nullptr;
+    const float* __restrict__ xr = x + (int64_t)row * ld;
+    if (!member) {
+      topk_blank(lane, 0, k, lo, po);
+    } else if (VEC) {
+      topk_group<EV_GS, 0>(lane, n_classes, k, [&](int, int c, float (&v)[4]) {
+        const float4 x4 = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
+        v[0] = x4.x; v[1] = x4.y; v[2] = x4.z; v[3] = x4.w;
+      }, lo, po);
+    } else {
+      topk_group<EV_GS, 0>(lane, n_classes, k, [&](int, int c, float (&v)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = c + i < n_classes ? xr[c + i] : 0.f;  // nothing past the row's classes is read
+      }, lo, po);
+    }
+  }
+}
+
 }  // namespace
+
+int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int k, int64_t* labels, float* probs,
+                     hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "topk_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
+  HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_rows: k = %d (1 .. %d)", k, TOPK_MAX);
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(x && (labels || probs), "topk_rows: null logits or no output");
+  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
+  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((topk_rows_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
+  else hipLaunchKernelGGL((topk_rows_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
 
 int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st) {
   HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "predict_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
@@ -205,4 +249,10 @@ extern "C" int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_row
                                 int64_t* d_pred, void* stream) {
   using namespace hmp;
   return predict_rows_launch(d_logits, ld, n_rows, n_classes, d_members, d_pred, (hipStream_t)stream);
+}
+
+extern "C" int hmp_topk_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int32_t k,
+                             int64_t* d_labels, float* d_probs, void* stream) {
+  using namespace hmp;
+  return topk_rows_launch(d_logits, ld, n_rows, n_classes, d_members, k, d_labels, d_probs, (hipStream_t)stream);
 }

@@ -76,7 +76,34 @@ __device__ __forceinline__ int head_argmax(const float* lg, int C) {
 }
 
 // what follows the logits of a tile: the CE and its backward (pass 2), the accuracy count, or the labels themselves
-enum HeadMode { HL_COUNT = 0, HL_TRAIN = 1, HL_PREDICT = 2 };
+// (or, HL_TOPK, the k largest logits of each head with their softmax probabilities)
+enum HeadMode { HL_COUNT = 0, HL_TRAIN = 1, HL_PREDICT = 2, HL_TOPK = 3 };
+
+constexpr int HL_GS = 16;  // HL_TOPK: lanes per (row, head) of the tile
+
+// HL_TOPK: the tile's 2 * HL_RB (row, head) pairs go round the workgroup's groups of HL_GS lanes, each a topk_group walk (tail_fns.h)
+// over the head's logits in LDS -- comparisons alone pick the labels, so column 0 is head_argmax's; -1 / 0 outside the head's rows
+__device__ __forceinline__ void heads_topk(const LinHeadArgs& a, const HeadSmem& s, int row0) {
+  const int lane = threadIdx.x % HL_GS;
+  for (int p = (int)threadIdx.x / HL_GS; p < 2 * HL_RB; p += 256 / HL_GS) {  // whole groups take every branch below together
+    const int r = p % HL_RB, h = p / HL_RB, row = row0 + r;
+    if (row >= a.n_rows || !(a.tk_labels[h] || a.tk_probs[h])) continue;
+    // the member byte and the output addresses do not depend on the walk
+    const bool member = head_member(a, h, row);
+    int64_t* const lo = a.tk_labels[h] ? a.tk_labels[h] + (int64_t)row * a.topk : nullptr;
+    float* const po = a.tk_probs[h] ? a.tk_probs[h] + (int64_t)row * a.topk : nullptr;
+    const int C = a.classes[h];
+    const float* lg = &s.lg[r][h == 0 ? 0 : a.classes[0]];
+    if (!member) {
+      topk_blank(lane, 0, a.topk, lo, po);
+      continue;
+    }
+    topk_group<HL_GS, 0>(lane, C, a.topk, [&](int, int c, float (&v)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = c + i < C ? lg[c + i] : 0.f;
+    }, lo, po);
+  }
+}
 
 template <HeadMode MODE>
 __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) {
@@ -127,6 +154,10 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
       }
     }
     __syncthreads();
+    if constexpr (MODE == HL_TOPK) {
+      heads_topk(a, s, row0);
+      continue;
+    }
     // ---- CE / argmax: one thread per (row, head) -----------------------------------------------------------------------
     if (t < 2 * HL_RB) {
       const int r = t % HL_RB, h = t / HL_RB, row = row0 + r;
@@ -289,6 +320,26 @@ int linear_heads_predict_launch(LinHeadArgs& a, int64_t* const* pred, hipStream_
   return HMP_OK;
 }
 
+// labels[h][row][0:k) / probs[h][row][0:k) = the k largest logits of head h on act(z) and their softmax probabilities for the head's
+// rows, -1 / 0 elsewhere (eval mode; a head with both pointers null is skipped).  Pass 1 and the tile assignment are the count's.
+int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, float* const* probs, hipStream_t st) {
+  HMP_CHECK_ARG(labels != nullptr && probs != nullptr, "linear heads: null output array");
+  HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "linear heads: k = %d (1 .. %d)", k, TOPK_MAX);
+  HMP_TRY(heads_check(a, false));
+  a.n_tiles = cdiv(a.n_rows, HL_RB);
+  for (int h = 0; h < 2; ++h) {
+    a.tk_labels[h] = labels[h];
+    a.tk_probs[h] = probs[h];
+  }
+  a.topk = k;
+  a.drop_on = 0;
+  const int blocks = heads_blocks(a.n_rows);
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(linear_heads_kernel<HL_TOPK>, dim3(blocks), dim3(256), 0, st, a);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 }  // namespace hmp
 
 // test / diagnostic entry of the two linear-heads launchers: a plain copy of the descriptor into LinHeadArgs, no choice of its own
@@ -325,13 +376,12 @@ extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t trai
   return train ? linear_heads_ce_launch(a, (hipStream_t)stream) : linear_heads_count_launch(a, (long long*)d_counts, (hipStream_t)stream);
 }
 
-// the predict launcher on the same descriptor (labels, mask, grad, row_lv and slabs may be NULL)
-extern "C" int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream) {
+// the descriptor of a label / top-k launch (labels, mask, grad, row_lv and slabs may be NULL) as LinHeadArgs, eval mode
+static int label_heads_args(const char* who, const hmp_linear_heads_desc* d, int32_t* n_blocks_out, hmp::LinHeadArgs& a) {
   using namespace hmp;
   static const bool have_device = hmp_device_count() > 0;
-  HMP_CHECK_ARG(have_device, "hmp_linear_heads_predict: no gfx950 device visible");
-  HMP_CHECK_ARG(d && d_pred && d->z && d->W[0] && d->W[1] && d->bias[0] && d->bias[1], "hmp_linear_heads_predict: null pointer");
-  LinHeadArgs a;
+  HMP_CHECK_ARG(have_device, "%s: no gfx950 device visible", who);
+  HMP_CHECK_ARG(d && d->z && d->W[0] && d->W[1] && d->bias[0] && d->bias[1], "%s: null pointer", who);
   memset(&a, 0, sizeof(a));
   a.z = d->z; a.ldz = d->ldz; a.n_rows = d->n_rows; a.F = d->F;
   a.classes[0] = d->classes[0]; a.classes[1] = d->classes[1]; a.K = a.classes[0] + a.classes[1];
@@ -342,5 +392,24 @@ extern "C" int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t*
   }
   a.act = d->act;
   if (n_blocks_out) *n_blocks_out = heads_blocks(d->n_rows);
+  return HMP_OK;
+}
+
+// the predict launcher on the same descriptor
+extern "C" int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_pred, "hmp_linear_heads_predict: null pointer");
+  LinHeadArgs a;
+  HMP_TRY(label_heads_args("hmp_linear_heads_predict", d, n_blocks_out, a));
   return linear_heads_predict_launch(a, d_pred, (hipStream_t)stream);
+}
+
+// the top-k launcher on the same descriptor
+extern "C" int hmp_linear_heads_topk(const hmp_linear_heads_desc* d, int32_t k, int64_t* const* d_labels, float* const* d_probs,
+                                     int32_t* n_blocks_out, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_labels && d_probs, "hmp_linear_heads_topk: null pointer");
+  LinHeadArgs a;
+  HMP_TRY(label_heads_args("hmp_linear_heads_topk", d, n_blocks_out, a));
+  return linear_heads_topk_launch(a, k, d_labels, d_probs, (hipStream_t)stream);
 }

@@ -633,6 +633,9 @@ struct LinHeadArgs {
   unsigned long long* counts;   // accuracy count: {correct_0, total_0, correct_1, total_1}
   int64_t* pred[2];             // label output: pred[h][row], -1 outside head h's rows (null: head skipped)
   int n_tiles;
+  int64_t* tk_labels[2];        // top-k output: [row][topk] per head (a head with both null is skipped)
+  float* tk_probs[2];
+  int topk;
 };
 int heads_blocks(int n_rows);
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st);
@@ -650,6 +653,17 @@ int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes
 
 // pred[row] = first-maximum argmax of x[row, 0:n_classes) (count_rows_launch's prediction), -1 where members[row] == 0
 int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st);
+
+// Top-k labels with their softmax probabilities (tail_fns.h: topk_group), one launch next to each predict launch above: row-major
+// labels [rows][k] int64 and probs [rows][k] float (either may be null, not both), 1 <= k <= TOPK_MAX.  Column 0 is the predict
+// launch's label; columns at or past the class count, and every column of a row outside the head's rows, hold -1 / 0.
+constexpr int TOPK_MAX = 8;
+int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int k, int64_t* labels, float* probs,
+                     hipStream_t st);
+// by entry of the launch, as tail_predict_launch's pred; an entry with both pointers null must have no rows
+int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* probs, bool pool, hipStream_t st);
+// by head; a head with both pointers null is skipped
+int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, float* const* probs, hipStream_t st);
 
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

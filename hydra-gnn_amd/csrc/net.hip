@@ -2237,6 +2237,66 @@ extern "C" int hmp_net_predict_heads(hmp_net* n, const hmp_batch* batch, const f
   return linear_heads_predict_launch(a, d_pred, st);
 }
 
+// ---- top-k labels with softmax probabilities: the forward of the predict entries, then ONE launch (tail_fns.h: topk_group).  k is
+// checked before the forward, so a refused call leaves the activations alone.
+#define HMP_CHECK_TOPK(who, k) HMP_CHECK_ARG((k) >= 1 && (k) <= TOPK_MAX, who ": k = %d (1 .. %d)", (int)(k), TOPK_MAX)
+
+extern "C" int hmp_net_topk_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, int32_t k,
+                                  int64_t* d_labels, float* d_probs, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && (d_labels || d_probs || batch->n_out == 0), "hmp_net_topk_rooms: null argument");
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
+                "hmp_net_topk_rooms: a two-headed net takes hmp_net_topk2 / hmp_net_topk_heads");
+  HMP_CHECK_TOPK("hmp_net_topk_rooms", k);
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  Scope sc(n, KC_LOSS, st);
+  return topk_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, k, d_labels, d_probs, st);
+}
+
+extern "C" int hmp_net_topk2(hmp_net* n, const hmp_batch* batch, const float* d_params, int32_t k, int64_t* const d_labels[2],
+                             float* const d_probs[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_labels && d_probs, "hmp_net_topk2: null argument");
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(S.aux_readout_type >= 0, "hmp_net_topk2: the net has one output (aux_readout_type < 0): use hmp_net_topk_rooms");
+  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU, "hmp_net_topk2: spec tail_act %d", S.tail_act);
+  HMP_CHECK_TOPK("hmp_net_topk2", k);
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  hmp_head_targets none;
+  memset(&none, 0, sizeof(none));
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = S.tail_act; ta.state = n->d_state;
+  int64_t* labels[2] = {nullptr, nullptr};
+  float* probs[2] = {nullptr, nullptr};
+  for (int h = 0; h < 2; ++h) {
+    if (!d_labels[h] && !d_probs[h]) continue;  // head skipped
+    const int before = ta.n;
+    if (n->has_pools) add_pool(n, batch, &none, h, false, ta);
+    else add_tail(n, batch, &none, h, false, ta);
+    if (ta.n > before) { labels[before] = d_labels[h]; probs[before] = d_probs[h]; }
+  }
+  if (ta.n == 0) return HMP_OK;
+  Scope sc(n, KC_LOSS, st);
+  return tail_topk_launch(ta, k, labels, probs, n->has_pools, st);
+}
+
+extern "C" int hmp_net_topk_heads(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], int32_t k,
+                                  int64_t* const d_labels[2], float* const d_probs[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_member && d_labels && d_probs, "hmp_net_topk_heads: null argument");
+  HMP_CHECK_ARG(n->has_heads, "hmp_net_topk_heads: the net has no linear heads (hmp_net_set_linear_heads)");
+  HMP_CHECK_ARG(!n->compute_bf16, "hmp_net_topk_heads: the linear heads compute in fp32 (bf16 compute mode is not supported)");
+  HMP_CHECK_TOPK("hmp_net_topk_heads", k);
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  hmp_linear_head_targets tg;
+  memset(&tg, 0, sizeof(tg));
+  tg.d_member[0] = d_member[0]; tg.d_member[1] = d_member[1];
+  LinHeadArgs a = heads_args(n, batch, &tg, d_params, false, 0);
+  Scope sc(n, KC_LOSS, st);
+  return linear_heads_topk_launch(a, k, d_labels, d_probs, st);
+}
+
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,
                                  const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && d_params && d_grads && d_m && d_v && args, "hmp_net_step_adam: null argument");

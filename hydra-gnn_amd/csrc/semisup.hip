@@ -187,6 +187,42 @@ __device__ __forceinline__ void tail_predict(const TailArgs& a, const TailPred& 
 __global__ __launch_bounds__(256) void tail_predict_kernel(const TailArgs a, const TailPred o) { tail_predict<false>(a, o); }
 __global__ __launch_bounds__(256) void pool_predict_kernel(const TailArgs a, const TailPred o) { tail_predict<true>(a, o); }
 
+// labels[entry][row][0:k) / probs[entry][row][0:k) = the k largest entries of the row tail_pred walks and their softmax
+// probabilities (tail_fns.h: topk_group; column 0 is tail_pred's label), for every row of both entries.  A pooled row stays in
+// registers over the rounds; a leaf row is recomputed from z in each.  An empty pooled row is all 0: labels 0 .. k - 1, each 1 / C.
+struct TailTopk {
+  int64_t* l[2];  // by entry of the launch
+  float* p[2];
+  int k;
+};
+
+template <bool POOL>
+__device__ __forceinline__ void tail_topk(const TailArgs& a, const TailTopk& o) {
+  const int e = tail_entry(a);
+  const HeadTail& T = a.h[e];
+  const int row = tail_row(T);
+  if (row >= (POOL ? T.n_pool : T.n_rows)) return;
+  // independent of the walk below
+  int64_t* const lb = e ? o.l[1] : o.l[0];
+  float* const pb = e ? o.p[1] : o.p[0];
+  int64_t* const lo = lb ? lb + (int64_t)row * o.k : nullptr;
+  float* const po = pb ? pb + (int64_t)row * o.k : nullptr;
+  const int lane = threadIdx.x % TL_GS;
+  if constexpr (POOL) {
+    float p[PT_Q][4];
+    pool_row(T, T.drop, a.act, row, lane, p);
+    topk_group<TL_GS, PT_Q>(lane, T.classes, o.k, [&](int q, int, float (&v)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = p[q][i];
+    }, lo, po);
+  } else {
+    topk_group<TL_GS, 0>(lane, T.classes, o.k, [&](int, int c, float (&v)[4]) { tail_quad(T, T.drop, a.act, row, c, v); }, lo, po);
+  }
+}
+
+__global__ __launch_bounds__(256) void tail_topk_kernel(const TailArgs a, const TailTopk o) { tail_topk<false>(a, o); }
+__global__ __launch_bounds__(256) void pool_topk_kernel(const TailArgs a, const TailTopk o) { tail_topk<true>(a, o); }
+
 // Checks the entries for a launch and lays their row groups out over the grid.  pool: the heads go through a LeafPool (rows in
 // registers, CSR / CSC or the identity); leaf_rows: one row group per leaf row, else per pooled row; ce: the launch writes gradients;
 // csc: the launch (or its companion) walks the pool plan by leaf -- the predict launch reads the CSR alone.
@@ -248,6 +284,25 @@ int tail_predict_launch(TailArgs& a, int64_t* const* pred, bool pool, hipStream_
   return HMP_OK;
 }
 
+// top-k labels and probabilities of every row of the entries (leaf rows, or pool: pooled rows); the layout and checks of
+// tail_predict_launch
+int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* probs, bool pool, hipStream_t st) {
+  HMP_CHECK_ARG(labels != nullptr && probs != nullptr, "tail top-k: null output array");
+  HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "tail top-k: k = %d (1 .. %d)", k, TOPK_MAX);
+  TailTopk o = {{nullptr, nullptr}, {nullptr, nullptr}, k};
+  for (int i = 0; i < a.n; ++i) {
+    o.l[i] = labels[i];
+    o.p[i] = probs[i];
+    HMP_CHECK_ARG(o.l[i] || o.p[i] || (pool ? a.h[i].n_pool : a.h[i].n_rows) == 0, "tail top-k: no output of entry %d", i);
+  }
+  int blocks;
+  HMP_TRY(tail_layout(a, pool, !pool, false, blocks, false));
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(pool ? pool_topk_kernel : tail_topk_kernel, dim3(blocks), dim3(256), 0, st, a, o);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 }  // namespace hmp
 
 // test / diagnostic entry of the five tail launchers: a plain copy of the descriptors into TailArgs, no choice of its own
@@ -290,24 +345,41 @@ extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, i
   }
 }
 
-// the predict launchers on the same descriptors (labels, mask, grad, row_lv and dpool may be NULL): d_pred[i] = int64 labels of
-// head i's rows (pooled: of its n_pool rows), eval mode
-extern "C" int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int64_t* const* d_pred, void* stream) {
+// the descriptors of a label / top-k launch (labels, mask, grad, row_lv and dpool may be NULL) as TailArgs, eval mode
+static int label_tail_args(const char* who, const hmp_tail_desc* d, int32_t n, int32_t act, hmp::TailArgs& ta) {
   using namespace hmp;
   static const bool have_device = hmp_device_count() > 0;
-  HMP_CHECK_ARG(have_device, "hmp_head_tails_predict: no gfx950 device visible");
-  HMP_CHECK_ARG(d && d_pred && (n == 1 || n == 2), "hmp_head_tails_predict: null argument or %d heads (1 or 2)", n);
-  TailArgs ta;
+  HMP_CHECK_ARG(have_device, "%s: no gfx950 device visible", who);
+  HMP_CHECK_ARG(d && (n == 1 || n == 2), "%s: null argument or %d heads (1 or 2)", who, n);
   memset(&ta, 0, sizeof(ta));
   ta.n = n; ta.act = act;
   for (int i = 0; i < n; ++i) {
     const hmp_tail_desc& q = d[i];
-    HMP_CHECK_ARG(q.z && q.n_rows >= 0 && q.n_pool >= 0, "hmp_head_tails_predict: null state or negative rows (head %d)", i);
+    HMP_CHECK_ARG(q.z && q.n_rows >= 0 && q.n_pool >= 0, "%s: null state or negative rows (head %d)", who, i);
     HeadTail& T = ta.h[i];
     T.z = q.z; T.ldz = q.ldz; T.n_rows = q.n_rows; T.classes = q.classes;
     T.slot = q.slot;
     T.rowptr = q.rowptr; T.col = q.col; T.t_rowptr = q.t_rowptr; T.t_col = q.t_col;
     T.n_pool = q.n_pool;
   }
+  return HMP_OK;
+}
+
+// the predict launchers on the same descriptors: d_pred[i] = int64 labels of head i's rows (pooled: of its n_pool rows), eval mode
+extern "C" int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int64_t* const* d_pred, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_pred, "hmp_head_tails_predict: null output array");
+  TailArgs ta;
+  HMP_TRY(label_tail_args("hmp_head_tails_predict", d, n, act, ta));
   return tail_predict_launch(ta, d_pred, pooled != 0, (hipStream_t)stream);
+}
+
+// the top-k launchers on the same descriptors: d_labels[i] int64 [rows][k], d_probs[i] float [rows][k] of head i's rows
+extern "C" int hmp_head_tails_topk(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int32_t k, int64_t* const* d_labels,
+                                   float* const* d_probs, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_labels && d_probs, "hmp_head_tails_topk: null output array");
+  TailArgs ta;
+  HMP_TRY(label_tail_args("hmp_head_tails_topk", d, n, act, ta));
+  return tail_topk_launch(ta, k, d_labels, d_probs, pooled != 0, (hipStream_t)stream);
 }

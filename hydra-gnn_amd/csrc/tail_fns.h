@@ -5,6 +5,7 @@
 //   ce_group<GS, NQ>       masked softmax-CE of a row held by GS lanes       aggregate.hip (fused epilogue), semisup.hip (both CE kernels)
 //   argmax_group<GS, NQ>,  first-maximum argmax of a row by GS lanes         evaluate.hip, optim.hip (argmax_rows_kernel), semisup.hip
 //   argmax_take/_reduce
+//   topk_group<GS, NQ>     the k largest entries and their softmax probabilities  evaluate.hip, semisup.hip, heads.hip (top-k kernels)
 //   count_begin/row/flush  a workgroup's {correct, total} pair in LDS        semisup.hip, evaluate.hip (count_rows_kernel)
 //
 // The backward form of act_drop, tail_dydz, is in common.h.
@@ -119,14 +120,20 @@ __device__ __forceinline__ void argmax_take(float v, int c, float& best, int& ar
   if (v > best || arg == ARGMAX_NONE) { best = v; arg = c; }
 }
 
+// the group reduction in place: afterwards every lane holds the group's {best, arg} (arg ARGMAX_NONE: no lane saw a column)
 template <int GS>
-__device__ __forceinline__ int argmax_reduce(float best, int arg) {
+__device__ __forceinline__ void argmax_reduce_pair(float& best, int& arg) {
 #pragma unroll
   for (int o = GS / 2; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, GS);
     const int oa = __shfl_xor(arg, o, GS);
     if (oa != ARGMAX_NONE && (arg == ARGMAX_NONE || ob > best || (ob == best && oa < arg))) { best = ob; arg = oa; }
   }
+}
+
+template <int GS>
+__device__ __forceinline__ int argmax_reduce(float best, int arg) {
+  argmax_reduce_pair<GS>(best, arg);
   return arg == ARGMAX_NONE ? 0 : arg;
 }
 
@@ -147,6 +154,65 @@ __device__ __forceinline__ int argmax_group(int lane, int classes, Quad&& quad) 
 
 // (a row without the quads' alignment is walked by scalar columns i, i + GS, ... with argmax_take and reduced by argmax_reduce:
 // the same prediction -- evaluate.hip, optim.hip)
+
+// ---- top-k labels with their softmax probabilities ---------------------------------------------------------------------------------
+// The k largest entries of a row in the total order "score descending, equal scores by ascending class" (+0.0 == -0.0), with
+// probs[j] = expf(s[c_j] - m) / sum_c expf(s[c] - m).  Round j is the first-maximum argmax above (argmax_take, argmax_reduce_pair)
+// restricted to the candidates behind pick j - 1 in that order, v < last_v || (v == last_v && c > last_c): it only compares, so the
+// order is exact, it keeps no per-lane state that grows with k, and round 0 has no restriction -- column 0 IS argmax_group's
+// prediction.  m is round 0's score (the row maximum; the sign of a zero maximum does not reach expf's result), the sum of expf
+// accumulates with ce_group's association (per lane in ascending column order, then the xor butterfly below GS), so every caller
+// computes the same bits for the same row.  quad(q, c, v) as in ce_group: it runs once per round and once for the sum, so a caller
+// without the row in registers recomputes it.  Lane 0 stores columns [0, k) of `labels` / `probs` (the row's k entries; either may
+// be null): columns at or past `classes` hold -1 / 0.  1 <= k; NaN scores are unspecified (as for the argmax) but store in bounds.
+// columns [from, k) of a row hold -1 / 0 (lane 0 stores): the columns past the class count, or from = 0: a row outside the head's rows
+__device__ __forceinline__ void topk_blank(int lane, int from, int k, int64_t* __restrict__ labels, float* __restrict__ probs) {
+  if (lane != 0) return;
+  for (int j = from; j < k; ++j) {
+    if (labels) labels[j] = -1;
+    if (probs) probs[j] = 0.f;
+  }
+}
+
+template <int GS, int NQ, class Quad>
+__device__ __forceinline__ void topk_group(int lane, int classes, int k, Quad&& quad, int64_t* __restrict__ labels, float* __restrict__ probs) {
+  const int kk = k < classes ? k : classes;
+  float last_v = 0.f, m = 0.f, s = 1.f;
+  int last_c = -1;
+  for (int j = 0; j < kk; ++j) {
+    float best = -INFINITY;
+    int arg = ARGMAX_NONE;
+    lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
+      float v[4];
+      quad(q, c, v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (c + i < classes && (j == 0 || v[i] < last_v || (v[i] == last_v && c + i > last_c))) argmax_take(v[i], c + i, best, arg);
+    });
+    argmax_reduce_pair<GS>(best, arg);
+    if (arg == ARGMAX_NONE) arg = 0;  // NaN scores only: j < classes leaves a candidate in every round otherwise
+    if (j == 0) {
+      m = best;
+      s = 0.f;
+      lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
+        float v[4];
+        quad(q, c, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (c + i < classes) s += expf(v[i] - m);
+      });
+#pragma unroll
+      for (int o = GS / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    }
+    if (lane == 0) {
+      if (labels) labels[j] = (int64_t)arg;
+      if (probs) probs[j] = expf(best - m) / s;
+    }
+    last_v = best;
+    last_c = arg;
+  }
+  topk_blank(lane, kk, k, labels, probs);
+}
 
 // ---- a workgroup's {correct, total} pair ------------------------------------------------------------------------------------------
 // s lives in LDS.  count_begin zeroes it (and is a barrier), count_row adds one counted row, count_flush (a barrier first) adds the

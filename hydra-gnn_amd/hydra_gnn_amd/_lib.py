@@ -191,12 +191,15 @@ SIGNATURES = {
     "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
     "hmp_count_correct_rows_by_graph": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_predict_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
+    "hmp_topk_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
     "hmp_head_tails": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I64, _VP, _VP, _VP]),
     "hmp_head_tails_predict": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, C.POINTER(_VP), _VP]),
+    "hmp_head_tails_topk": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_linear_heads_run": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
     "hmp_linear_heads_predict": (C.c_int, [C.POINTER(LinearHeadsDesc), C.POINTER(_VP), C.POINTER(_I32), _VP]),
+    "hmp_linear_heads_topk": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I32), _VP]),
     "hmp_net_create": (C.c_int, [C.POINTER(NetSpec), C.POINTER(_VP)]),
     "hmp_net_destroy": (None, [_VP]),
     "hmp_net_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(_I32), C.POINTER(_I64)]),
@@ -222,6 +225,9 @@ SIGNATURES = {
     "hmp_net_predict_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _VP, _VP]),
     "hmp_net_predict2": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _VP]),
     "hmp_net_predict_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_net_topk_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I32, _VP, _VP, _VP]),
+    "hmp_net_topk2": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_net_topk_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),

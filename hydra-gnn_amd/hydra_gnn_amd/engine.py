@@ -627,53 +627,128 @@ class NativeNet:
 
         ``out`` takes caller-owned contiguous device int64 buffers (one, or a pair) of at least the needed rows; the result is a
         view of their leading rows.  Nothing synchronises."""
-        flat = self.flat_params(full_check=False)
+        h, stream, flat, rows = self._label_rows(batch, "predict_labels")
         dev = flat.device
+        two = len(rows) == 2
+        outs = _label_buffers(out, rows, two, dev)
+        mem, _alive = self._label_members(h, stream, members, rows, dev, "predict_labels")
+        if self.heads is not None:
+            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
+            self._count("hmp_net_predict_heads", h, dev, flat.data_ptr(), mem, prd)
+        elif two:
+            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
+            self._count("hmp_net_predict2", h, dev, flat.data_ptr(), prd)
+        else:
+            self._count("hmp_net_predict_rooms", h, dev, flat.data_ptr(), mem, outs[0].data_ptr())
+        views = tuple(o[:n] for o, n in zip(outs, rows))
+        return views if two else views[0]
+
+    def _label_rows(self, batch, who: str):
+        """(holder, its stream or None, flat parameters, rows per head) of a label call: one entry for the room task, two for a
+        two-headed net"""
+        flat = self.flat_params(full_check=False)
         stream = None
         if isinstance(batch, _BatchHolder):
             h = batch
             stream = h.stream
             if stream is not None and stream.nat is not self:
-                raise _lib.HydraMPError("predict_labels: the batch comes from a stream created for another model")
+                raise _lib.HydraMPError(f"{who}: the batch comes from a stream created for another model")
         else:
             h = self.make_batch(batch)
-        two = self.aux_readout is not None or self.heads is not None
         if self.heads is not None:
             rows = [int(h.c.n_out)] * 2
-        elif two:
+        elif self.aux_readout is not None:
             rows = [h.n_nodes[self.node_types.index(t)] for t in self.head_label_types()]
         else:
             rows = [int(h.c.n_out)]
-        outs = _label_buffers(out, rows, two, dev)
+        return h, stream, flat, rows
+
+    def _label_members(self, h, stream, members, rows, dev, who: str):
+        """the member argument of the net kind's label entry (a pair of row addresses for linear heads, one address or None for the
+        room task, None for an aux-readout net) and the tensors that must outlive the call"""
+        from .ops import row_members
+
         if self.heads is not None:
+            keep = None
             if stream is not None and members is None:
                 m0, m1 = stream.member_rows()
             else:
                 if members is None or len(members) != 2 or members[0] is None:
-                    raise _lib.HydraMPError("predict_labels: a net with linear heads needs members=(room rows, object rows | None)")
-                from .ops import row_members
-
+                    raise _lib.HydraMPError(f"{who}: a net with linear heads needs members=(room rows, object rows | None)")
                 keep = [row_members(m, rows[0], dev) if m is not None else None for m in members]
                 m0, m1 = (k.data_ptr() if k is not None and rows[0] > 0 else None for k in keep)
-            mem = (C.c_void_p * 2)(m0, m1)
-            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
-            self._count("hmp_net_predict_heads", h, dev, flat.data_ptr(), mem, prd)
-        elif two:
+            return (C.c_void_p * 2)(m0, m1), keep
+        if self.aux_readout is not None:
             if members is not None:
-                raise _lib.HydraMPError("predict_labels: the heads of an aux-readout net are whole node types (no members)")
-            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
-            self._count("hmp_net_predict2", h, dev, flat.data_ptr(), prd)
-        else:
-            if members is None and stream is not None and getattr(stream, "homog_room", False):
-                members_ptr = stream.members.data_ptr()
-            else:
-                from .ops import row_members
+                raise _lib.HydraMPError(f"{who}: the heads of an aux-readout net are whole node types (no members)")
+            return None, None
+        if members is None and stream is not None and getattr(stream, "homog_room", False):
+            return stream.members.data_ptr(), None
+        members = row_members(members, rows[0], dev)
+        return (members.data_ptr() if members is not None else None), members
 
-                members = row_members(members, rows[0], dev)
-                members_ptr = members.data_ptr() if members is not None else None
-            self._count("hmp_net_predict_rooms", h, dev, flat.data_ptr(), members_ptr, outs[0].data_ptr())
-        views = tuple(o[:n] for o, n in zip(outs, rows))
+    def predict_topk(self, batch, k: int, out=None, members=None):
+        """Top-k labels with their softmax probabilities, on the device: eval-mode native forward plus ONE launch
+        (``hmp_net_topk_rooms`` / ``hmp_net_topk2`` / ``hmp_net_topk_heads``, picked by the net's kind as :meth:`predict_labels`
+        picks, with its ``batch`` and ``members``).  ``1 <= k <= 8``.
+
+        Per head ``(labels [rows, k] int64, probs [rows, k] float32)``: ``labels[r, j]`` is the class with the j-th largest score
+        of what ``forward()`` returns for the row in eval mode (equal scores: the smaller class), ``probs[r, j]`` its softmax
+        probability; column 0 is :meth:`predict_labels`' label.  Columns past the class count, and every column of a row outside
+        the head's rows, hold ``-1`` / ``0``.  The room task returns one such pair, a two-headed net a pair of them.
+
+        ``out`` takes caller-owned buffers of that shape (``(labels, probs)``, or a pair of those): contiguous, on the model's
+        device, k columns, at least the needed rows; the result is a view of their leading rows.  Nothing synchronises."""
+        k = _check_k(k)
+        h, stream, flat, rows = self._label_rows(batch, "predict_topk")
+        dev = flat.device
+        two = len(rows) == 2
+        outs = _topk_buffers(out, rows, k, two, dev)
+        mem, _alive = self._label_members(h, stream, members, rows, dev, "predict_topk")
+        if two:
+            lab = (C.c_void_p * 2)(*[o[0].data_ptr() for o in outs])
+            prb = (C.c_void_p * 2)(*[o[1].data_ptr() for o in outs])
+            if self.heads is not None:
+                self._count("hmp_net_topk_heads", h, dev, flat.data_ptr(), mem, k, lab, prb)
+            else:
+                self._count("hmp_net_topk2", h, dev, flat.data_ptr(), k, lab, prb)
+        else:
+            self._count("hmp_net_topk_rooms", h, dev, flat.data_ptr(), mem, k, outs[0][0].data_ptr(), outs[0][1].data_ptr())
+        views = tuple((lb[:n], pb[:n]) for (lb, pb), n in zip(outs, rows))
         return views if two else views[0]
+
+    def predict_confidence(self, batch, members=None):
+        """:meth:`predict_topk` with ``k = 1`` on the host: the labels and their probabilities of every head land in ONE device
+        buffer (8 bytes per label, then 4 per probability) and cross in one D2H through one pinned buffer and one event, as
+        :meth:`predict_pair` moves its labels.  Returns host ``(labels int64 [rows], confidence float32 [rows])`` per head -- one
+        pair for the room task, a pair of pairs for a two-headed net -- as views of that buffer (valid until the next call)."""
+        h, _, flat, rows = self._label_rows(batch, "predict_confidence")
+        dev = flat.device
+        n = sum(rows)
+        with torch.cuda.device(dev):
+            if getattr(self, "_conf_dev", None) is None or self._conf_dev.numel() < 12 * n or self._conf_dev.device != dev:
+                cap = max(4096, 24 * n)
+                self._conf_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
+                self._conf_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                self._conf_done = torch.cuda.Event()
+                self._conf_views = None
+            if self._conf_views is None or self._conf_views[0] != rows:  # consecutive frames of one size reuse the views
+
+                def split(buf):
+                    lab = buf[:8 * n].view(torch.int64)
+                    prb = buf[8 * n:12 * n].view(torch.float32)
+                    return [(lab[o:o + r], prb[o:o + r]) for o, r in zip((0, rows[0]), rows)]
+
+                outs = [(lb.view(lb.numel(), 1), pb.view(pb.numel(), 1)) for lb, pb in split(self._conf_dev)]
+                host = split(self._conf_host)
+                self._conf_views = (list(rows), tuple(outs) if len(rows) == 2 else outs[0], tuple(host) if len(rows) == 2 else host[0])
+            _, outs, host = self._conf_views
+            self.predict_topk(h, 1, out=outs, members=members)
+            if n > 0:
+                self._conf_host[:12 * n].copy_(self._conf_dev[:12 * n], non_blocking=True)
+            self._conf_done.record()
+            self._conf_done.synchronize()
+        return host
 
     def predict_pair(self, batch, members=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """:meth:`predict_labels` of a two-headed net on the host: both label vectors land in ONE device buffer and cross in one
@@ -783,6 +858,34 @@ def _label_buffers(out, rows: Sequence[int], pair: bool, dev) -> List[torch.Tens
             raise _lib.HydraMPError(f"out must be contiguous 1-d int64 tensors on {dev} with at least {n} rows, got "
                                     f"{tuple(o.shape)} {o.dtype} on {o.device}")
     return outs
+
+
+TOPK_MAX = 8  # csrc/kernels.h
+
+
+def _check_k(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX:
+        raise _lib.HydraMPError(f"k must be an integer in [1, {TOPK_MAX}], got {k!r}")
+    return k
+
+
+def _topk_buffers(out, rows: Sequence[int], k: int, pair: bool, dev) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """the ``(labels int64 [rows, k], probs float32 [rows, k])`` outputs of ``predict_topk`` per head: fresh ones, or the caller's
+    ``out`` after the checks ``_label_buffers`` makes (dtype, rows, k columns, contiguity, device)"""
+    if out is None:
+        return [(torch.empty((max(n, 1), k), dtype=torch.int64, device=dev), torch.empty((max(n, 1), k), dtype=torch.float32, device=dev))
+                for n in rows]
+    outs = list(out) if pair else [out]
+    ok = len(outs) == len(rows) and all(isinstance(o, (tuple, list)) and len(o) == 2 and all(isinstance(t, torch.Tensor) for t in o)
+                                        for o in outs)
+    if not ok:
+        raise _lib.HydraMPError(f"out: {'a pair of (labels, probs) pairs (one per head)' if pair else 'one (labels, probs) pair'} expected")
+    for (lb, pb), n in zip(outs, rows):
+        for t, dtype in ((lb, torch.int64), (pb, torch.float32)):
+            if t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.dim() != 2 or t.size(1) != k or t.size(0) < n:
+                raise _lib.HydraMPError(f"out must be contiguous (int64, float32) tensors [rows >= {n}, {k}] on {dev}, got "
+                                        f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    return [(lb, pb) for lb, pb in outs]
 
 
 def _check_counts4(counts: torch.Tensor, dev) -> None:

@@ -1,5 +1,6 @@
 """Validation accuracy on the device (room task: :func:`accuracy`; two-headed task: :func:`semisupervised_accuracy`) and the
-predicted labels themselves (:func:`predict`, every model and task): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
+predicted labels themselves (:func:`predict`, every model and task; :func:`predict_topk` adds the next guesses and the softmax
+probability of each): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
 per batch.
 
 The reference's ``test()`` runs an eval-mode forward per batch, takes ``argmax(dim=1)``, drops the rows whose label is the
@@ -126,6 +127,30 @@ def _split_rows(host: np.ndarray, counts: np.ndarray):
     return [p[p >= 0] for p in pieces]
 
 
+def _pass_args(model, batches, who: str):
+    """the two forms of ``batches`` checked: ``(stream, graph-id arrays)`` of a streamed pass, ``(None, None)`` for an iterable of
+    batches"""
+    from . import _lib
+    from .store import BatchStream
+
+    streamed = isinstance(batches, tuple) and len(batches) >= 1 and isinstance(batches[0], BatchStream)
+    if streamed and len(batches) != 2:
+        raise _lib.HydraMPError(f"{who}: a stream is passed as the pair (BatchStream, iterable of graph-id lists)")
+    if batches is None or isinstance(batches, (str, bytes)) or not hasattr(batches, "__iter__"):
+        raise _lib.HydraMPError(f"{who}: batches must be an iterable of batches or a (BatchStream, iterable of graph-id lists) pair")
+    if not streamed:
+        return None, None
+    stream, id_lists = batches
+    if id_lists is None or isinstance(id_lists, (str, bytes)) or not hasattr(id_lists, "__iter__"):
+        raise _lib.HydraMPError(f"{who}: the second element of the pair must be an iterable of graph-id lists")
+    id_lists = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
+    if any(ids.size == 0 for ids in id_lists):
+        raise _lib.HydraMPError(f"{who}: an empty graph-id list")
+    if stream.nat is not model.native():
+        raise _lib.HydraMPError(f"{who}: the stream was created for another model")
+    return stream, id_lists
+
+
 def predict(model, batches: Union[Iterable, Tuple[object, Iterable]]):
     """Predicted labels over ``batches`` with ONE device-to-host copy at the end of the pass (``model.predict_labels`` per batch:
     eval-mode forward plus one launch, nothing synchronises in between).  ``batches`` takes the two forms :func:`accuracy` takes.
@@ -136,23 +161,8 @@ def predict(model, batches: Union[Iterable, Tuple[object, Iterable]]):
     alone (the ``-1`` rows outside a head's rows are dropped on the host; the labels are a few KB, so nothing is compacted on the
     device).  An iterable of batches on the model's device: one entry per BATCH, the per-row vectors of ``predict_labels`` (``-1``
     rows kept: a collated homogeneous batch carries no graph offsets to split by)."""
-    from . import _lib
-    from .store import BatchStream
-
-    streamed = isinstance(batches, tuple) and len(batches) >= 1 and isinstance(batches[0], BatchStream)
-    if streamed and len(batches) != 2:
-        raise _lib.HydraMPError("predict: a stream is passed as the pair (BatchStream, iterable of graph-id lists)")
-    if batches is None or isinstance(batches, (str, bytes)) or not hasattr(batches, "__iter__"):
-        raise _lib.HydraMPError("predict: batches must be an iterable of batches or a (BatchStream, iterable of graph-id lists) pair")
-    if streamed:
-        stream, id_lists = batches
-        if id_lists is None or isinstance(id_lists, (str, bytes)) or not hasattr(id_lists, "__iter__"):
-            raise _lib.HydraMPError("predict: the second element of the pair must be an iterable of graph-id lists")
-        id_lists = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
-        if any(ids.size == 0 for ids in id_lists):
-            raise _lib.HydraMPError("predict: an empty graph-id list")
-        if stream.nat is not model.native():
-            raise _lib.HydraMPError("predict: the stream was created for another model")
+    stream, id_lists = _pass_args(model, batches, "predict")
+    streamed = stream is not None
     dev = next(model.parameters()).device
     if not streamed:
         outs = [model.predict_labels(b) for b in batches]
@@ -181,5 +191,67 @@ def predict(model, batches: Union[Iterable, Tuple[object, Iterable]]):
     heads = [_split_rows(host[:totals[0]], counts[0])]
     if two:
         heads.append(_split_rows(host[totals[0]:], counts[1]))
+        return list(zip(heads[0], heads[1]))
+    return heads[0]
+
+
+def _split_topk(labels: np.ndarray, probs: np.ndarray, counts: np.ndarray):
+    """per-graph ``(labels [n, k], probs [n, k])`` pieces, the rows outside the head's rows (label -1 in column 0) dropped: one
+    compaction of the whole pass, then two slices per graph"""
+    keep = labels[:, 0] >= 0
+    off = np.concatenate([[0], np.cumsum(counts)])
+    if not keep.all():
+        off = np.concatenate([[0], np.cumsum(keep)])[off]  # the kept rows in front of every graph
+        labels, probs = labels[keep], probs[keep]
+    return [(labels[off[g]:off[g + 1]], probs[off[g]:off[g + 1]]) for g in range(len(counts))]
+
+
+def predict_topk(model, batches: Union[Iterable, Tuple[object, Iterable]], k: int):
+    """:func:`predict` with the top-k labels AND their softmax probabilities (``model.predict_topk`` per batch: eval-mode forward
+    plus one launch), one device-to-host copy and one synchronisation per pass.  ``batches`` takes the forms :func:`predict` takes.
+
+    ``(BatchStream, iterable of graph-id lists)``: one buffer for the whole pass, sized from the store's per-graph node counts
+    (all labels, then all probabilities; head 0's rows, then head 1's); every batch writes its slice through ``out=``.  The result
+    has one entry per graph in id order: ``(labels [n, k] int64, probs [n, k] float32)`` numpy arrays over the rows :func:`predict`
+    returns for that graph (``labels[:, 0]`` is its result), or a ``(room, object)`` pair of those.  An iterable of
+    batches: one entry per BATCH, the per-row arrays of ``model.predict_topk`` (``-1`` / ``0`` rows kept)."""
+    from .engine import _check_k
+
+    k = _check_k(k)
+    stream, id_lists = _pass_args(model, batches, "predict_topk")
+    dev = next(model.parameters()).device
+    if stream is None:
+        outs = [model.predict_topk(b, k) for b in batches]
+        two = bool(outs) and isinstance(outs[0][0], tuple)
+        flat = [t for o in outs for hd in (o if two else (o,)) for t in hd]  # labels, probs, labels, probs, ...
+        if not flat:
+            return []
+        host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()  # the one copy of the pass
+        sizes = np.cumsum([0] + [t.numel() * t.element_size() for t in flat])
+        parts = [host[sizes[i]:sizes[i + 1]].view(np.int64 if i % 2 == 0 else np.float32).reshape(-1, k) for i in range(len(flat))]
+        heads = [(parts[2 * i], parts[2 * i + 1]) for i in range(len(parts) // 2)]
+        return [(heads[2 * i], heads[2 * i + 1]) for i in range(len(outs))] if two else heads
+    types = _label_types(model)
+    two = len(types) == 2
+    all_ids = np.concatenate(id_lists) if id_lists else np.zeros(0, dtype=np.int64)
+    counts = [stream.store.node_counts[t][all_ids] for t in types]
+    totals = [int(c.sum()) for c in counts]
+    R = sum(totals)
+    buf = torch.empty(max(12 * R * k, 1), dtype=torch.uint8, device=dev)  # int64 labels [R, k], then float32 probabilities [R, k]
+    labels = buf[:8 * R * k].view(torch.int64).view(R, k)
+    probs = buf[8 * R * k:12 * R * k].view(torch.float32).view(R, k)
+    pos = [0, totals[0]]
+    for ids in id_lists:
+        rows = [int(stream.store.node_counts[t][ids].sum()) for t in types]
+        views = [(labels[pos[h]:pos[h] + rows[h]], probs[pos[h]:pos[h] + rows[h]]) for h in range(len(types))]
+        model.predict_topk(stream.next(ids), k, out=tuple(views) if two else views[0])
+        for h in range(len(types)):
+            pos[h] += rows[h]
+    host = buf[:12 * R * k].cpu().numpy()  # the one copy (and synchronisation) of the pass
+    hl = host[:8 * R * k].view(np.int64).reshape(R, k)
+    hp = host[8 * R * k:].view(np.float32).reshape(R, k)
+    heads = [_split_topk(hl[:totals[0]], hp[:totals[0]], counts[0])]
+    if two:
+        heads.append(_split_topk(hl[totals[0]:], hp[totals[0]:], counts[1]))
         return list(zip(heads[0], heads[1]))
     return heads[0]

@@ -426,23 +426,35 @@ class BaseTrainingJob:
         per graph, the labels ``model.predict`` returns for that graph alone."""
         return self._predict_pass(split, self.get_dataset(split))
 
-    def _predict_pass(self, name, dataset):
+    def predict_topk(self, split, k):
+        """:meth:`predict` with the top-k labels and their softmax probabilities (``evaluate.predict_topk``): per graph
+        ``(labels [n, k] int64, probs [n, k] float32)`` numpy arrays over the rows :meth:`predict` returns (``labels[:, 0]`` is its
+        result), or a ``(room, object)`` pair of those for a two-headed model; one device-to-host copy per pass."""
+        return self._predict_pass(split, self.get_dataset(split), k)
+
+    def _predict_pass(self, name, dataset, k=None):
+        """``k`` None: the labels of ``evaluate.predict``; else the top-k pairs of ``evaluate.predict_topk``"""
         net = self._net
         net.eval()
         device = next(net.parameters()).device
         B = self._training_params["optimization_params"]["batch_size"]
         chunks = id_chunks(len(dataset), B)
+        run = evaluate.predict if k is None else (lambda model, batches: evaluate.predict_topk(model, batches, k))
         with torch.cuda.device(device):
             if self._streams_batches():
-                return evaluate.predict(net, (self._stream(name, dataset, device, B), chunks))
+                return run(net, (self._stream(name, dataset, device, B), chunks))
             # GCN / GIN: collated batches keep no graph offsets; the per-node vectors are split by the store's node counts
             store = self._store(name, dataset, device)
-            per_batch = evaluate.predict(net, (store.collate(ids) for ids in chunks))
+            per_batch = run(net, (store.collate(ids) for ids in chunks))
         nodes = store.node_counts[store.node_types[0]]
         out = []
         for ids, labels in zip(chunks, per_batch):
-            heads = [evaluate._split_rows(v, nodes[ids]) for v in (labels if isinstance(labels, tuple) else (labels,))]
-            out.extend(zip(*heads) if isinstance(labels, tuple) else heads[0])
+            two = isinstance(labels if k is None else labels[0], tuple)
+            if k is None:
+                heads = [evaluate._split_rows(v, nodes[ids]) for v in (labels if two else (labels,))]
+            else:
+                heads = [evaluate._split_topk(lb, pb, nodes[ids]) for lb, pb in (labels if two else (labels,))]
+            out.extend(zip(*heads) if two else heads[0])
         return out
 
     def test_individual_graph(self, dataset, model=None):
@@ -622,6 +634,11 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
         what ``model.predict`` returns for that graph alone), from its device-resident copy in ``batch_size`` batches with one
         device-to-host copy per pass."""
         return self._predict_pass("all", self._dataset)
+
+    def predict_topk(self, k, split=None):
+        """:meth:`predict` with the top-k labels and their softmax probabilities: per graph
+        ``((room_labels [n, k], room_probs [n, k]), (object_labels, object_probs))`` numpy arrays (``evaluate.predict_topk``)."""
+        return self._predict_pass("all", self._dataset, k)
 
     def test_individual_graph(self, dataset, model=None):
         return NotImplemented

@@ -89,6 +89,23 @@ class _NativeModule(nn.Module):
         _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
         return self.native().predict_labels(data, out=out)
 
+    def predict_topk(self, data, k=1, out=None):
+        """Top-k labels with their softmax probabilities, left on the device (nothing synchronises): eval-mode native forward plus
+        one launch (:meth:`NativeNet.predict_topk`).  Per head ``(labels [rows, k] int64, probs [rows, k] float32)`` over the rows
+        of :meth:`predict_labels` -- ``labels[:, 0]`` is its result, ``probs`` the softmax of what ``forward()`` returns in eval
+        mode; columns past the class count hold ``-1`` / ``0``.  Room task: ``(labels, probs)``; two-headed:
+        ``((room_labels, room_probs), (object_labels, object_probs))``.  ``1 <= k <= 8``; ``out`` takes caller-owned buffers of
+        that structure (contiguous, k columns, at least the needed rows)."""
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        return self.native().predict_topk(data, k, out=out)
+
+    def predict_with_confidence(self, data):
+        """``(labels, confidence)`` of ``data`` on the host: :meth:`predict`'s labels and the softmax probability of each (column 0
+        of :meth:`predict_topk` with ``k = 1``), through one pinned buffer and one device-to-host copy.  A two-headed model returns
+        a pair of those, ``((room_labels, room_confidence), (object_labels, object_confidence))``."""
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        return self.native().predict_confidence(data)
+
     def loss(self, pred, label, mask=None):
         return cross_entropy_loss(pred, label, mask)
 

@@ -316,6 +316,57 @@ class HomogeneousNetwork(_NativeModule):
             o[:n][rows] = ops.argmax_rows(logits)
         return outs[0][:n], outs[1][:n]
 
+    def predict_topk(self, data, k=1, out=None):
+        """Top-k labels with their softmax probabilities on the device, one row per NODE as :meth:`predict_labels` lays them out:
+        per head ``(labels [nodes, k] int64, probs [nodes, k] float32)``, ``labels[:, 0]`` its result, ``-1`` / ``0`` in all k
+        columns outside the head's rows and in the columns past the class count.  Room task: ``(labels, probs)``; two-headed:
+        ``((room_labels, room_probs), (object_labels, object_probs))``.  ``1 <= k <= 8``; ``data`` and ``out`` as
+        :meth:`predict_labels` takes them (``out`` in that structure: contiguous, k columns).  SAGE / GAT: eval-mode native forward
+        plus one launch (:meth:`NativeNet.predict_topk`).  GCN / GIN: the op-by-op eval forward, then ``hmp_topk_rows`` (two-headed:
+        per head, scattered to the head's rows)."""
+        from .._lib import require_device
+        from ..engine import _BatchHolder, _check_k, _topk_buffers
+
+        require_device()  # no device: HydraMPError (there is no CPU fallback)
+        k = _check_k(k)
+        two = self.classification_task == "all"
+        if isinstance(data, _BatchHolder):
+            if self.op_path:
+                raise HydraMPError(f"predict_topk: {self.conv_block} runs op by op: pass a collated Data batch")
+            return self.native().predict_topk(data, k, out=out)
+        if not self.op_path:
+            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
+            return self.native().predict_topk(self._view(data), k, out=out, members=members)
+        if not two:
+            return ops.topk_rows(self._eval_states(data), k, data.room_mask, out)
+        n = data.x.size(0)
+        outs = _topk_buffers(out, [n, n], k, True, data.x.device)
+        obj = self._object_rows(data)
+        for (lb, pb), logits, rows in zip(outs, self._eval_heads(data), (data.room_mask, ~data.room_mask if obj is None else obj)):
+            top = ops.topk_rows(logits, k)
+            lb[:n].fill_(-1)
+            pb[:n].zero_()
+            lb[:n][rows], pb[:n][rows] = top
+        return tuple((lb[:n], pb[:n]) for lb, pb in outs)
+
+    def predict_with_confidence(self, data):
+        """``(labels, confidence)`` on the host: :meth:`predict`'s labels (the ``room_mask`` rows; two-headed: each head's rows, in
+        row order) and the softmax probability of each, column 0 of :meth:`predict_topk` with ``k = 1``, through one pinned buffer
+        and one device-to-host copy (GCN / GIN: one copy per output).  A two-headed model returns a pair of those."""
+        from .._lib import require_device
+
+        require_device()  # no device: HydraMPError (there is no CPU fallback)
+        two = self.classification_task == "all"
+        if self.op_path:
+            heads = self.predict_topk(data, 1)
+            heads = [tuple(t[:, 0].cpu() for t in hd) for hd in (heads if two else (heads,))]
+        else:
+            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
+            heads = self.native().predict_confidence(self._view(data), members=members)
+            heads = heads if two else (heads,)
+        heads = tuple((lb[lb >= 0], pb[lb >= 0]) for lb, pb in heads)  # the rows outside a head's rows dropped on the host
+        return heads if two else heads[0]
+
     def _predict_two(self, data):
         """host ``(room_labels, object_labels)``: the labels of the ``room_mask`` rows and of the object head's rows, in row order
         (the -1 rows of :meth:`predict_labels` dropped on the host)"""

@@ -8,7 +8,7 @@ stream and the autograd tape only.  There is no CPU path: CPU tensors raise.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -297,6 +297,30 @@ def predict_rows(logits: torch.Tensor, members: Optional[torch.Tensor] = None, o
                                                     members.data_ptr() if members is not None else None, out.data_ptr(),
                                                     _lib.stream_ptr()))
     return out[:n]
+
+
+def topk_rows(logits: torch.Tensor, k: int, members: Optional[torch.Tensor] = None, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(labels [rows, k] int64, probs [rows, k] float32)`` on the device (``hmp_topk_rows``): the k largest entries of every row
+    -- descending, equal entries by ascending class, so column 0 is :func:`predict_rows`' label -- and their softmax probabilities.
+    Columns past the class count, and rows where the bool filter ``members`` is False, hold ``-1`` / ``0``.  ``1 <= k <= 8``.
+    ``out``: a ``(labels, probs)`` pair of contiguous tensors with k columns and at least ``rows`` rows on the same device.
+    Nothing synchronises."""
+    from .engine import _check_k, _topk_buffers
+
+    k = _check_k(k)
+    _dev(logits, "logits")
+    logits = _rows(logits)
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise _lib.HydraMPError(f"logits must be [rows, classes >= 1], got {tuple(logits.shape)}")
+    n = logits.size(0)
+    members = row_members(members, n, logits.device)
+    labels, probs = _topk_buffers(out, [n], k, False, logits.device)[0]
+    if n:
+        with torch.cuda.device(logits.device):
+            _lib.check(_lib.load().hmp_topk_rows(logits.data_ptr(), logits.stride(0), n, logits.size(1),
+                                                 members.data_ptr() if members is not None else None, k, labels.data_ptr(),
+                                                 probs.data_ptr(), _lib.stream_ptr()))
+    return labels[:n], probs[:n]
 
 
 def check_count_buffers(counts: torch.Tensor, confusion: Optional[torch.Tensor], n_classes: int, device) -> None:

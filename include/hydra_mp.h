@@ -44,6 +44,8 @@ extern "C" {
  *    diagnostic entries of the readout tail and linear-head launchers: new entries, no struct changed layout;
  *    hmp_predict_rows, hmp_net_predict_rooms / hmp_net_predict2 / hmp_net_predict_heads (labels instead of counts, for every net
  *    kind), hmp_head_tails_predict / hmp_linear_heads_predict (their test entries): new entries, no struct changed layout;
+ *    hmp_topk_rows, hmp_net_topk_rooms / hmp_net_topk2 / hmp_net_topk_heads (top-k labels with their softmax probabilities, for
+ *    every net kind), hmp_head_tails_topk / hmp_linear_heads_topk (their test entries): new entries, no struct changed layout;
  *    section 14: hmp_frame_build / hmp_frame_sizes / hmp_frame_host_arrays / hmp_frame_pack / hmp_frame_destroy (host) and
  *    hmp_frame_expand (one launch): scene-graph arrays to model input.  New entries, no struct was added or changed layout;
  *    hmp_frame_build_homogeneous: the same frame laid out as the homogeneous Data (item kinds HMP_FK_EDGE_SEG / HMP_FK_CONST, output
@@ -246,6 +248,17 @@ int hmp_count_correct_rows_by_graph(const float* d_logits, int32_t ld, int32_t n
  * launch; n_rows == 0 launches nothing; nothing synchronises.  (ABI-4-compatible addition.) */
 int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int64_t* d_pred,
                      void* stream);
+/* Top-k labels with their softmax probabilities: for a row's scores s = d_logits[r, 0:n_classes) and 1 <= k <= 8,
+ * d_labels[r, j] (device int64 [n_rows][k], row-major) = the class with the j-th largest score -- scores descending, equal scores
+ * (+0.0 == -0.0) by ascending class, so column 0 is hmp_predict_rows' label bit for bit -- and d_probs[r, j] (device float
+ * [n_rows][k]) = expf(s[c] - m) / sum_c' expf(s[c'] - m) with c = d_labels[r, j], m the row maximum; m and the sum accumulate in
+ * the association of the fused cross entropy (per lane of the row's 16 in ascending column order, then an xor butterfly), whatever
+ * the pitch.  Columns j >= n_classes hold -1 / 0, and so does every column of a row with d_members[r] == 0 (d_members NULL: every
+ * row).  Every element of rows [0, n_rows) is written exactly once, nothing behind them; the outputs need no initialisation.
+ * Either output may be NULL (skipped), not both.  NaN scores are unspecified.  One launch; n_rows == 0 launches nothing; nothing
+ * synchronises.  (ABI-4-compatible addition.) */
+int hmp_topk_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int32_t k,
+                  int64_t* d_labels, float* d_probs, void* stream);
 /* d_count: device float holding the valid-label count (grad_scale = 1/max(count,1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
@@ -291,6 +304,12 @@ int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act,
  * predicts 0).  labels, mask, grad, row_lv, dpool, t_rowptr and t_col may be NULL.  One launch for both heads.  (ABI-4-compatible
  * addition, like hmp_linear_heads_predict below.) */
 int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int64_t* const* d_pred, void* stream);
+/* The top-k launch of the same descriptors (eval mode, the contract of hmp_topk_rows on the rows hmp_head_tails_predict walks):
+ * d_labels[i] int64 [rows][k] and d_probs[i] float [rows][k] for EVERY row of head i (an empty pooled row is all zeros: labels
+ * 0 .. k-1, each 1 / classes).  Of a head's two pointers either may be NULL, both only when the head has no rows.  1 <= k <= 8.
+ * One launch for both heads. */
+int hmp_head_tails_topk(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int32_t k, int64_t* const* d_labels,
+                        float* const* d_probs, void* stream);
 /* Two linear heads over one final state z [n_rows][ldz]: logits_h = dropout(act(z)) W_h^T + b_h on the rows of head h (member[0]
  * NULL: every row; member[1] NULL: the complement of member[0], empty when both are NULL), W_h [classes[h]][F] dense.
  * grad [n_rows][ldg], ldg == F rounded up to 4 (columns F .. ldg written 0); row_lv [n_rows][2] = {loss_0 + loss_1, valid_0 + valid_1};
@@ -319,6 +338,10 @@ int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t*
 /* The label launch (eval mode): d_pred[h] (device int64 [n_rows], NULL: head skipped) = first-maximum argmax of head h's logits
  * for the rows of member[h] (the rule above), -1 elsewhere.  labels, mask, grad, row_lv and slabs may be NULL. */
 int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream);
+/* The top-k launch (eval mode, the contract of hmp_topk_rows on head h's logits): d_labels[h] int64 [n_rows][k], d_probs[h] float
+ * [n_rows][k] for the rows of member[h], -1 / 0 elsewhere; a head whose two pointers are both NULL is skipped.  1 <= k <= 8. */
+int hmp_linear_heads_topk(const hmp_linear_heads_desc* d, int32_t k, int64_t* const* d_labels, float* const* d_probs,
+                          int32_t* n_blocks_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 6. network executor -- the whole HeteroConv layer stack as one native program.
@@ -561,6 +584,24 @@ int hmp_net_predict2(hmp_net* net, const hmp_batch* batch, const float* d_params
  * member rule, d_member[1] NULL = complement of d_member[0]), -1 elsewhere.  Either d_pred pointer may be NULL (head skipped). */
 int hmp_net_predict_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2],
                           int64_t* const d_pred[2], void* stream);
+/* Top-k labels with their softmax probabilities, for every net kind: the eval-mode forward of the predict entries above, then exactly
+ * ONE launch (the contract of hmp_topk_rows, on each net kind's score vector = what forward() returns for the row in eval mode).
+ * 1 <= k <= 8, else HMP_E_ARG before anything runs.  Outputs are row-major [rows][k]: labels int64, probs float; of each labels /
+ * probs pair either may be NULL (that output is skipped).  Column 0 equals the matching predict entry bit for bit.  Everything else
+ * -- plan_valid, the overwritten activations, no allocation or synchronisation, the refusals -- is the predict entry's.
+ * (ABI-4-compatible additions.)
+ * room task: rows = n_out; -1 / 0 in all k columns where d_members[row] == 0.  Not both outputs NULL unless n_out == 0. */
+int hmp_net_topk_rooms(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, int32_t k,
+                       int64_t* d_labels, float* d_probs, void* stream);
+/* two-headed nets with aux readout: head 0 per readout row, head 1 per aux row, scores act(z); with hmp_net_set_head_pools per
+ * DESTINATION row of each pooled head, scores the LeafPool mean of act(z) (a row without an edge: labels 0 .. k-1, each 1 / C).  A
+ * head whose two pointers are both NULL is skipped. */
+int hmp_net_topk2(hmp_net* net, const hmp_batch* batch, const float* d_params, int32_t k, int64_t* const d_labels[2],
+                  float* const d_probs[2], void* stream);
+/* linear heads: head h's logits on act(z) for the rows of d_member[h] (hmp_net_predict_heads' rule), -1 / 0 in all k columns
+ * elsewhere.  A head whose two pointers are both NULL is skipped. */
+int hmp_net_topk_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], int32_t k,
+                       int64_t* const d_labels[2], float* const d_probs[2], void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
