@@ -231,7 +231,10 @@ extern "C" int hmp_collator_create(int32_t n_slots, const int64_t* const* h_slot
   for (int s = 0; s < n_slots; ++s) c->slot_ptr.emplace_back(h_slot_ptr[s], h_slot_ptr[s] + n_graphs + 1);
   for (int i = 0; i < n_items; ++i) {
     const hmp_collate_item& it = items[i];
-    if (!(it.d_src && it.d_ptr && it.slot >= 0 && it.slot < n_slots && it.row_bytes >= 0 && it.row_bytes <= INT32_MAX &&
+    // a slot that is empty in every graph of the store (an edge type a derivation removed) has no source array: its item stays in the
+    // table, gets no workgroup and writes nothing
+    const bool empty_slot = it.slot >= 0 && it.slot < n_slots && c->slot_ptr[it.slot][n_graphs] == c->slot_ptr[it.slot][0];
+    if (!((it.d_src || empty_slot) && it.d_ptr && it.slot >= 0 && it.slot < n_slots && it.row_bytes >= 0 && it.row_bytes <= INT32_MAX &&
           (it.row_bytes > 0 || (it.slot_src >= 0 && it.slot_src < n_slots && it.slot_dst >= 0 && it.slot_dst < n_slots)))) {
       delete c;
       HMP_FAIL(HMP_E_ARG, "hmp_collator_create: item %d is malformed", i);

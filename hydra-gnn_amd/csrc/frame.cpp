@@ -49,7 +49,7 @@ struct hmp_frame {
   std::vector<uint8_t> sections;  // the block behind the item table
   int64_t arena_bytes = 0;
   int32_t n_blocks = 0;
-  int32_t cfg[6] = {0, 0, 0, 0, 0, 0};  // homogeneous, htree, relative_pos, sem_dim, n_labels, clique_dim: what a batch must share
+  int32_t cfg[7] = {0, 0, 0, 0, 0, 0, 0};  // homogeneous, htree, relative_pos, sem_dim, n_labels, clique_dim, flags: what a batch must share
   int32_t n_input = 0;                  // nodes of the input arrays (the length of a frame's label vector y)
   ~hmp_frame() { hmp_htree_destroy(tree); }
 };
@@ -173,7 +173,8 @@ int fail(const char* m) {
 static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min, const double* bb_max,
                        const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near, double max_near, double max_on,
                        int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels, int32_t clique_dim, bool homogeneous,
-                       hmp_frame** out) {
+                       int32_t flags, hmp_frame** out) {
+  if (flags & ~HMP_FRAME_NO_ROOM_EDGES) return fail("unknown flag (HMP_FRAME_NO_ROOM_EDGES is the only one)");
   if (!out || n < 0 || m < 0 || sem_dim < 0 || n_labels < 0 || clique_dim < 0) return fail("bad argument");
   if (n > 0 && (!ids || !layer || !pos || !bb_min || !bb_max || !label)) return fail("null node array");
   if (m > 0 && !edges) return fail("null edge array");
@@ -218,7 +219,8 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
   };
 
   hmp_frame* F = new hmp_frame;
-  const int32_t cfg[6] = {homogeneous ? 1 : 0, htree ? 1 : 0, rel_ht ? HMP_FRAME_RELPOS_HTREE : (relative_pos ? 1 : 0), sem_dim, n_labels, clique_dim};
+  const int32_t cfg[7] = {homogeneous ? 1 : 0, htree ? 1 : 0, rel_ht ? HMP_FRAME_RELPOS_HTREE : (relative_pos ? 1 : 0), sem_dim, n_labels, clique_dim,
+                          flags};
   memcpy(F->cfg, cfg, sizeof cfg);
   F->n_input = n;
   auto bail = [&](const char* msg) { delete F; return fail(msg); };
@@ -229,6 +231,8 @@ static int frame_build(int32_t n, const uint64_t* ids, const int32_t* layer, con
   // ---- room-room edges, de-duplicated in visiting order (preprocess_dsgs.py:236-246)
   std::vector<int32_t> rr_src, rr_dst;
   std::set<std::pair<int, int>> seen;
+  // HMP_FRAME_NO_ROOM_EDGES (remove_room_edges_in_dsg): the room layer loses its edges here, before the layouts and the H-tree read them
+  if (!(flags & HMP_FRAME_NO_ROOM_EDGES))
   for (int r : F->rooms)
     for (int s : adj[r]) {
       if (layer[s] != L_ROOMS) continue;
@@ -512,7 +516,7 @@ extern "C" int hmp_frame_build(int32_t n, const uint64_t* ids, const int32_t* la
                                double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
                                int32_t clique_dim, hmp_frame** out) {
   return frame_build(n, ids, layer, pos, bb_min, bb_max, label, m, edges, threshold_near, max_near, max_on, htree, relative_pos, sem_dim,
-                     n_labels, clique_dim, false, out);
+                     n_labels, clique_dim, false, 0, out);
 }
 
 extern "C" int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
@@ -520,7 +524,15 @@ extern "C" int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const
                                            double threshold_near, double max_near, double max_on, int32_t htree, int32_t relative_pos,
                                            int32_t sem_dim, int32_t n_labels, int32_t clique_dim, hmp_frame** out) {
   return frame_build(n, ids, layer, pos, bb_min, bb_max, label, m, edges, threshold_near, max_near, max_on, htree, relative_pos, sem_dim,
-                     n_labels, clique_dim, true, out);
+                     n_labels, clique_dim, true, 0, out);
+}
+
+extern "C" int hmp_frame_build_flags(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                                     const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
+                                     double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
+                                     int32_t clique_dim, int32_t homogeneous, int32_t flags, hmp_frame** out) {
+  return frame_build(n, ids, layer, pos, bb_min, bb_max, label, m, edges, threshold_near, max_near, max_on, htree, relative_pos, sem_dim,
+                     n_labels, clique_dim, homogeneous != 0, flags, out);
 }
 
 extern "C" int hmp_frame_sizes(const hmp_frame* f, int64_t* sizes) {

@@ -8,6 +8,8 @@
 //   fill    dst[dst_off[g] + i] = value,  i < src_ptr[g + 1] - src_ptr[g]                                   (int64 or one byte)
 //   edges   dst[r][dst_off[g] + j] = src[r][src_ptr[g] + j] + shift_r[g]                                    (graph-local int64 [2][E])
 //   relpos  dst[j][c] = pos_dst[ptr_dst[g] + src[1][j]][c] - pos_src[ptr_src[g] + src[0][j]][c],  c < 3     (a plain subtraction)
+//   compact   the rows of graph g whose key[row] is NOT in a 64-bit set, in order, from dst row dst_off[g] on  (one wave per graph)
+//   rows_zero dst[dst_off[g] + i] = key[row] in the set ? zeros : src[src_ptr[g] + i]                        (units of 16 / 4 / 1 bytes)
 // Every item walks its SOURCE rows, so every output element is written exactly once as long as the plan tiles the outputs (the
 // planner's job; tests run with outputs pre-filled).  No atomics.  Byte work, HBM-bound.
 #include "device_fns.h"  // find_seg
@@ -50,6 +52,62 @@ __device__ __forceinline__ void sd_fill(const int64_t* __restrict__ I, int G, in
   for (int64_t row = first; row < total; row += stride) {
     const int g = find_seg(sp, G, row);
     dst[dof[g] + (row - sp[g])] = value;
+  }
+}
+
+// a key outside [0, 64) is in no set
+__device__ __forceinline__ bool sd_in_set(uint64_t set, int64_t key) {
+  return (uint64_t)key < 64u && ((set >> (uint64_t)key) & 1ull) != 0;
+}
+
+// rows copied, zeroed where the row's key is in the set: thread per destination unit, as sd_rows (skip 0, take = the whole row)
+template <typename U>
+__device__ __forceinline__ void sd_rows_zero(const int64_t* __restrict__ I, int G, int64_t first, int64_t stride) {
+  const U* __restrict__ src = reinterpret_cast<const U*>(I[HMP_SD_SRC]);
+  U* __restrict__ dst = reinterpret_cast<U*>(I[HMP_SD_DST]);
+  const int64_t* __restrict__ sp = reinterpret_cast<const int64_t*>(I[HMP_SD_SRC_PTR]);
+  const int64_t* __restrict__ dof = reinterpret_cast<const int64_t*>(I[HMP_SD_DST_OFF]);
+  const int64_t* __restrict__ key = reinterpret_cast<const int64_t*>(I[HMP_SD_A0]);
+  const uint64_t set = (uint64_t)I[HMP_SD_A1];
+  const int64_t w = I[HMP_SD_DST_W];
+  const int64_t total = I[HMP_SD_N] * w;
+  for (int64_t idx = first; idx < total; idx += stride) {
+    const int64_t row = idx / w, u = idx - row * w;
+    const int g = find_seg(sp, G, row);
+    const int64_t drow = dof[g] + (row - sp[g]);
+    dst[drow * w + u] = sd_in_set(set, key[row]) ? sd_zero<U>() : src[row * w + u];
+  }
+}
+
+// rows compacted by a key vector: a wave per graph (waves stride over the graphs), 64 source rows per sweep; a kept row's rank
+// among the kept rows of its graph = kept rows of the earlier sweeps + popcount of the ballot below the lane, so the order is the
+// source's and every destination row of the graph is written once (the plan's dst_off comes from the same count, store_count_kept)
+template <typename U>
+__device__ __forceinline__ void sd_compact(const int64_t* __restrict__ I, int G, int nb) {
+  const U* __restrict__ src = reinterpret_cast<const U*>(I[HMP_SD_SRC]);
+  U* __restrict__ dst = reinterpret_cast<U*>(I[HMP_SD_DST]);
+  const int64_t* __restrict__ sp = reinterpret_cast<const int64_t*>(I[HMP_SD_SRC_PTR]);
+  const int64_t* __restrict__ dof = reinterpret_cast<const int64_t*>(I[HMP_SD_DST_OFF]);
+  const int64_t* __restrict__ key = reinterpret_cast<const int64_t*>(I[HMP_SD_A0]);
+  const uint64_t set = (uint64_t)I[HMP_SD_A1];
+  const int64_t w = I[HMP_SD_DST_W];
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const int64_t wave0 = ((int64_t)blockIdx.x - I[HMP_SD_BLOCK0]) * 4 + (threadIdx.x >> 6);
+  for (int64_t g = wave0; g < G; g += (int64_t)nb * 4) {
+    const int64_t r0 = sp[g], n = sp[g + 1] - r0;
+    int64_t out = dof[g];
+    for (int64_t base = 0; base < n; base += 64) {
+      const int64_t i = base + lane;
+      const bool keep = i < n && !sd_in_set(set, key[r0 + i]);
+      const unsigned long long b = __ballot(keep);
+      if (keep) {
+        const U* s = src + (r0 + i) * w;
+        U* d = dst + (out + __popcll(b & below)) * w;
+        for (int64_t u = 0; u < w; ++u) d[u] = s[u];
+      }
+      out += __popcll(b);
+    }
   }
 }
 
@@ -103,6 +161,15 @@ __device__ __forceinline__ void sd_item(const int64_t* __restrict__ I, int G, in
       }
       break;
     }
+    case HMP_SD_COMPACT:
+      if (unit == 8) sd_compact<uint64_t>(I, G, nb);
+      else sd_compact<uint32_t>(I, G, nb);
+      break;
+    case HMP_SD_ROWS_ZERO:
+      if (unit == 16) sd_rows_zero<uint4>(I, G, first, stride);
+      else if (unit == 4) sd_rows_zero<uint32_t>(I, G, first, stride);
+      else sd_rows_zero<uint8_t>(I, G, first, stride);
+      break;
     default:
       break;
   }
@@ -209,9 +276,35 @@ __global__ __launch_bounds__(256) void store_member_counts_kernel(const uint8_t*
   }
 }
 
+// counts [G]: the rows of a graph whose key is not in the set (what an HMP_SD_COMPACT item keeps)
+__global__ __launch_bounds__(256) void store_count_kept_kernel(const int64_t* __restrict__ key, const int64_t* __restrict__ ptr, int G,
+                                                               uint64_t set, int64_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = (int64_t)gridDim.x * 4;
+  for (int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); g < G; g += waves) {
+    const int64_t r0 = ptr[g], n = ptr[g + 1] - r0;
+    int64_t c = 0;
+    for (int64_t base = 0; base < n; base += 64) {
+      const int64_t i = base + lane;
+      c += __popcll(__ballot(i < n && !sd_in_set(set, key[r0 + i])));
+    }
+    if (lane == 0) counts[g] = c;
+  }
+}
+
 }  // namespace hmp
 
 using namespace hmp;
+
+extern "C" int hmp_store_count_kept(const int64_t* d_key, const int64_t* d_ptr, int32_t n_graphs, uint64_t set, int64_t* d_counts,
+                                    void* stream) {
+  HMP_CHECK_ARG(n_graphs >= 1 && d_ptr && d_counts, "hmp_store_count_kept: null / empty argument");
+  // d_key may be null only for a store without a single row (the kernel then reads none)
+  hipLaunchKernelGGL(store_count_kept_kernel, dim3(std::min(cdiv(n_graphs, 4), 1024)), dim3(256), 0, (hipStream_t)stream, d_key, d_ptr,
+                     n_graphs, set, d_counts);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
 
 extern "C" int hmp_store_derive(const int64_t* d_block, int32_t n_items, int32_t n_blocks, int32_t n_graphs, void* stream) {
   HMP_CHECK_ARG(n_items >= 0 && n_items <= HMP_SD_MAX_ITEMS, "hmp_store_derive: %d items, a launch's group table holds %d", n_items, HMP_SD_MAX_ITEMS);

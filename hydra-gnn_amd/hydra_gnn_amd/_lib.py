@@ -277,6 +277,8 @@ SIGNATURES = {
                                   _I32, C.POINTER(_VP)]),
     "hmp_frame_build_homogeneous": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _I32,
                                               _I32, _I32, C.POINTER(_VP)]),
+    "hmp_frame_build_flags": (C.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, C.c_double, C.c_double, C.c_double, _I32, _I32, _I32, _I32,
+                                        _I32, _I32, _I32, C.POINTER(_VP)]),
     "hmp_frame_sizes": (C.c_int, [_VP, _VP]),
     "hmp_frame_host_arrays": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "hmp_frame_pack": (C.c_int, [_VP, _VP, _I64]),
@@ -289,6 +291,7 @@ SIGNATURES = {
     "hmp_frame_batch_pack": (C.c_int, [_VP, _VP, _I64]),
     "hmp_frame_batch_destroy": (None, [_VP]),
     "hmp_frame_expand_batch": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "hmp_store_count_kept": (C.c_int, [_VP, _VP, _I32, C.c_uint64, _VP, _VP]),
     "hmp_store_derive": (C.c_int, [_VP, _I32, _I32, _I32, _VP]),
     "hmp_store_node_split": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "hmp_store_member_counts": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),
@@ -300,6 +303,7 @@ FS_HT_COUNTS, FS_HT_EDGES, FS_HT_INIT, FS_COUNT = 9, 13, 23, 26
 FRAME_ITEM_WORDS = 12
 FI_KIND, FI_TENSOR, FI_ROWS, FI_WIDTH, FI_DST, FI_S0, FI_S1, FI_S2, FI_S3, FI_P0, FI_P1, FI_BLOCK0 = range(12)
 FK_FEAT, FK_POS, FK_I64, FK_EDGE, FK_EATTR, FK_CLIQUE, FK_EDGE_SEG, FK_CONST, FK_EATTR_HT = range(9)
+FRAME_NO_ROOM_EDGES = 1  # hmp_frame_build_flags: the room layer loses its edges (remove_room_edges_in_dsg)
 FRAME_RELPOS_HTREE = 2  # value of hmp_frame_build's relative_pos: relative positions on the edges of an H-tree
 FRAME_END_WORDS, FE_DIRECT, FE_GATHER, FE_CLIQUE = 4, 0, 1, 2  # an end of an FK_EATTR_HT item's descriptor section
 FT_HTREE, FT_COUNT = 16, 45
@@ -316,7 +320,7 @@ FT_HTREL, FT_HTREL_COUNT = 87, 17  # what FRAME_RELPOS_HTREE adds: pos of the tw
 SD_ITEM_WORDS, SD_MAX_ITEMS = 16, 4096
 (SD_KIND, SD_BLOCK0, SD_SRC, SD_DST, SD_SRC_PTR, SD_DST_OFF, SD_N, SD_SRC_W, SD_SKIP, SD_TAKE, SD_DST_W, SD_A0, SD_A1, SD_A2, SD_A3,
  SD_UNIT) = range(16)
-SD_ROWS, SD_FILL, SD_EDGES, SD_RELPOS = range(4)
+SD_ROWS, SD_FILL, SD_EDGES, SD_RELPOS, SD_COMPACT, SD_ROWS_ZERO = range(6)
 
 COLLATE_MAX_ITEMS, COLLATE_MAX_SLOTS = 40, 24 # csrc/collate.hip CB_MAX_ITEMS / CB_MAX_SLOTS: arrays and types of one collation launch
 

@@ -294,9 +294,12 @@ def collate(graphs: Sequence[HeteroData]) -> HeteroData:
 # reference: heterogeneous_data_to_homogeneous / heterogeneous_htree_to_homogeneous, src/hydra_gnn/mp3d_dataset.py:29-119
 # ([PyG] HeteroData.to_homogeneous: node types concatenated in store order, every edge type's edge_index shifted by the
 # offsets of its endpoint types and concatenated in edge-type order; node_type / edge_type id vectors).
-def heterogeneous_data_to_homogeneous(torch_data: HeteroData):
+def heterogeneous_data_to_homogeneous(torch_data: HeteroData, removed_edge_type: Optional[EdgeType] = None):
     """-> (Data with x, edge_index, node_type, edge_type [, y, edge_attr], list of node type names).  Features are
-    zero-padded to the widest node type (reference :36-51)."""
+    zero-padded to the widest node type (reference :36-51).  ``removed_edge_type`` (reference :53-69; the Stanford3DSG baseline
+    configs pass ``("rooms", "rooms_to_objects", "objects")``): the edges of that type are dropped from ``edge_index`` /
+    ``edge_type`` / ``edge_attr``, in order; the other types keep their numbers (the position among the graph's edge types).  A
+    triple the graph does not hold raises ``ValueError``."""
     node_types = [t for t in torch_data.node_types if "x" in torch_data[t]]
     width = max(torch_data[t].num_node_features for t in node_types)
     xs, ys, nts, off = [], [], [], {}
@@ -329,7 +332,67 @@ def heterogeneous_data_to_homogeneous(torch_data: HeteroData):
         out.y = torch.cat(ys, 0)
     if has_ea:
         out.edge_attr = torch.cat(eas, 0)
+    if removed_edge_type is not None:
+        removed = tuple(removed_edge_type)
+        if removed not in edge_types:
+            raise ValueError(f"removed_edge_type {removed} is not an edge type of the graph: {edge_types}")
+        remove_edge_types(out, [edge_types.index(removed)])
     return out, node_types
+
+
+def remove_edge_types(g, edge_types):
+    """Edge-type ablation, in place (returns ``g``).  Typed graph (reference ``Hydra_mp3d_data.remove_room_edges_in_dsg`` +
+    ``fill_missing_edge_index``, ``mp3d_dataset.py:203-255``, for ``rooms_to_rooms``): ``edge_types`` are triples; each stays in the graph
+    with ``edge_index`` ``[2, 0]`` int64 and, if it has one, ``edge_attr`` ``[0, d]``.  Homogeneous ``Data``: ``edge_types`` are ints; the
+    columns of ``edge_index`` whose ``edge_type`` is one of them are dropped, ``edge_type`` and ``edge_attr`` follow (``init_edge_index`` /
+    ``pool_edge_index`` are untouched)."""
+    if hasattr(g, "node_types"):
+        present = g.edge_types
+        for e in edge_types:
+            e = tuple(e)
+            if e not in present:
+                raise ValueError(f"remove_edge_types: {e} is not an edge type of the graph: {present}")
+            old = g[e].edge_index
+            g[e].edge_index = torch.empty((2, 0), dtype=torch.int64, device=old.device)
+            if "edge_attr" in g[e]:
+                ea = g[e].edge_attr
+                g[e].edge_attr = torch.empty((0,) + tuple(ea.shape[1:]), dtype=ea.dtype, device=ea.device)
+        return g
+    ids = [int(t) for t in edge_types]
+    if not hasattr(g, "edge_type"):
+        raise ValueError("remove_edge_types: the homogeneous graph has no 'edge_type'")
+    keep = torch.ones_like(g.edge_type, dtype=torch.bool)
+    for t in ids:
+        keep &= g.edge_type != t
+    g.edge_index = g.edge_index[:, keep]
+    g.edge_type = g.edge_type[keep]
+    if hasattr(g, "edge_attr"):
+        g.edge_attr = g.edge_attr[keep]
+    return g
+
+
+HTREE_CLIQUE_NODE_TYPES = ["object-room", "room-room"]
+
+
+def zero_clique_features(g):
+    """Clique ablation of the Stanford H-tree scripts (reference ``train_Stanford.py:93-99``: ``x[clique_has == -1] = 0``), in place
+    (returns ``g``).  ``clique_has`` is -1 exactly on the two clique node types (``construct.py:428-430``), so no such attribute is
+    carried: a typed H-tree gets zero ``x`` on ``object-room`` and ``room-room``; a homogeneous H-tree ``Data`` on the rows whose
+    ``node_type`` is one of those two (their positions in ``HTREE_NODE_TYPES``)."""
+    if hasattr(g, "node_types"):
+        for t in HTREE_CLIQUE_NODE_TYPES:
+            if t not in g.node_types or "x" not in g[t]:
+                raise ValueError(f"zero_clique_features: the graph has no node type '{t}' with features (not an H-tree)")
+        for t in HTREE_CLIQUE_NODE_TYPES:
+            g[t].x = torch.zeros_like(g[t].x)
+        return g
+    if not (hasattr(g, "object_mask") and hasattr(g, "node_type")):
+        raise ValueError("zero_clique_features: the homogeneous graph is not an H-tree (no 'object_mask' / 'node_type')")
+    x = g.x.clone()
+    for t in HTREE_CLIQUE_NODE_TYPES:
+        x[g.node_type == HTREE_NODE_TYPES.index(t)] = 0
+    g.x = x
+    return g
 
 
 def heterogeneous_htree_to_homogeneous(torch_data: HeteroData) -> Data:

@@ -260,28 +260,33 @@ def _frame_args(ids, layer, pos, bb_min, bb_max, label, edges):
     return arrays, n, int(edges.shape[1])
 
 
-def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_labels, clique_dim, homogeneous=False) -> C.c_void_p:
+def _frame_build(lib, arrays, n, m, thresholds, htree, relative_pos, sem_dim, n_labels, clique_dim, homogeneous=False,
+                 remove_room_edges=False) -> C.c_void_p:
     ids, layer, pos, bb_min, bb_max, label, edges = arrays
     h = C.c_void_p()
-    build = lib.hmp_frame_build_homogeneous if homogeneous else lib.hmp_frame_build
-    _lib.check(build(n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data,
-                     label.ctypes.data, m, edges.ctypes.data, float(thresholds[0]), float(thresholds[1]),
-                     float(thresholds[2]), int(bool(htree)), int(relative_pos), int(sem_dim), int(n_labels),
-                     int(clique_dim or 0), C.byref(h)))
+    args = (n, ids.ctypes.data, layer.ctypes.data, pos.ctypes.data, bb_min.ctypes.data, bb_max.ctypes.data, label.ctypes.data, m,
+            edges.ctypes.data, float(thresholds[0]), float(thresholds[1]), float(thresholds[2]), int(bool(htree)), int(relative_pos),
+            int(sem_dim), int(n_labels), int(clique_dim or 0))
+    if remove_room_edges:  # the room layer loses its edges in the native host stage (hmp_frame_build_flags)
+        _lib.check(lib.hmp_frame_build_flags(*args, int(bool(homogeneous)), _lib.FRAME_NO_ROOM_EDGES, C.byref(h)))
+    else:
+        _lib.check((lib.hmp_frame_build_homogeneous if homogeneous else lib.hmp_frame_build)(*args, C.byref(h)))
     return h
 
 
 def frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, threshold_near: float = 1.5, max_near: float = 2.0,
                      max_on: float = 0.2, htree: bool = False, relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0,
-                     clique_dim: Optional[int] = None, homogeneous: bool = False, htree_relative_pos: bool = False) -> Dict[str, object]:
+                     clique_dim: Optional[int] = None, homogeneous: bool = False, htree_relative_pos: bool = False,
+                     remove_room_edges: bool = False) -> Dict[str, object]:
     """The host stage of the frame pipeline on its own (no GPU involved; tests and diagnostics): ``hmp_frame_build``
     (``homogeneous``: ``hmp_frame_build_homogeneous``) and every accessor.  ``kept`` / ``dropped`` / ``rooms`` index the input
     arrays; ``items`` is the staging block's table (int32 ``[n_items, 12]``), ``block`` the packed block (uint8); ``empty``: no room
-    or no kept object, nothing was laid out."""
+    or no kept object, nothing was laid out.  ``remove_room_edges``: as ``FramePipeline``'s."""
     lib = _lib.load()
     arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
     rel = _relpos_mode("frame_host_stage", htree, relative_pos, htree_relative_pos, clique_dim)
-    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, rel, sem_dim, n_labels, clique_dim, homogeneous)
+    h = _frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, rel, sem_dim, n_labels, clique_dim, homogeneous,
+                     remove_room_edges)
     try:
         sz = np.zeros(_lib.FS_COUNT, dtype=np.int64)
         _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -368,7 +373,7 @@ def _batch_host_arrays(lib, hb) -> Dict[str, object]:
 def frame_batch_host_stage(frames, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2, htree: bool = False,
                            relative_pos: bool = False, sem_dim: int = 0, n_labels: int = 0, clique_dim: Optional[int] = None,
                            homogeneous: bool = False, form: int = _lib.FB_COLLATED, y=None,
-                           htree_relative_pos: bool = False) -> Dict[str, object]:
+                           htree_relative_pos: bool = False, remove_room_edges: bool = False) -> Dict[str, object]:
     """The host stage of ``FramePipeline.convert_batch`` / ``GraphStore.from_frames`` on its own (no GPU involved; the batch
     counterpart of ``frame_host_stage``).  ``frames``: a sequence of the 7-tuples ``frame_host_stage`` takes; ``form``:
     ``_lib.FB_COLLATED`` or ``_lib.FB_STORE``; ``y``: one int64 label vector per frame, aligned with its input arrays.  Returns
@@ -383,7 +388,7 @@ def frame_batch_host_stage(frames, threshold_near: float = 1.5, max_near: float 
             arrays, n, m = _frame_args(*fr)
             built.append(arrays)
             handles.append(_frame_build(lib, arrays, n, m, (threshold_near, max_near, max_on), htree, rel, sem_dim, n_labels,
-                                        clique_dim, homogeneous))
+                                        clique_dim, homogeneous, remove_room_edges))
         y_ptrs, keep = _label_pointers(y, len(handles), built)
         hb = _batch_build(lib, handles, form, y_ptrs)
         try:
@@ -452,6 +457,11 @@ class FramePipeline:
     are ``torch.bool`` views of arena bytes; a frame carries no ``y``.  ``info["room_ids"]`` is in the order of the ``room_mask``
     rows.  Everything said above about views, fresh objects, streams and ``None`` holds for it.
 
+    ``remove_room_edges=True`` is the reference's ``Hydra_mp3d_data.remove_room_edges_in_dsg`` (``mp3d_dataset.py:203-208``, the ``noRE``
+    configurations) in the native host stage: the room-room edges are dropped before anything reads them, so ``rooms_to_rooms`` is
+    ``[2, 0]`` and an H-tree is built from the edgeless room layer (every room its own component, no ``room-room`` clique).  It holds in
+    every mode above, typed and homogeneous, for ``convert``, ``convert_batch`` and ``GraphStore.from_frames``.
+
     ``convert_batch(frames, y=None)`` converts MANY frames with one host stage, one upload and one launch into the collated batch
     (``data.collate`` / ``data.collate_homogeneous`` of the single results), in every mode above; ``store.GraphStore.from_frames``
     builds a device-resident store the same way.
@@ -459,7 +469,7 @@ class FramePipeline:
 
     def __init__(self, device="cuda:0", semantic_table=None, htree: bool = False, relative_pos: bool = False,
                  clique_dim: Optional[int] = None, threshold_near: float = 1.5, max_near: float = 2.0, max_on: float = 0.2,
-                 homogeneous: bool = False, htree_relative_pos: bool = False):
+                 homogeneous: bool = False, htree_relative_pos: bool = False, remove_room_edges: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.HydraMPError(f"FramePipeline needs a gfx950 device, not {self.device}: hydra_gnn_amd has no CPU fallback")
@@ -469,6 +479,7 @@ class FramePipeline:
         self.htree, self.relative_pos, self.clique_dim = bool(htree), bool(relative_pos), int(clique_dim or 0)
         self.htree_relative_pos = bool(htree_relative_pos)
         self.homogeneous = bool(homogeneous)
+        self.remove_room_edges = bool(remove_room_edges)
         self.thresholds = (float(threshold_near), float(max_near), float(max_on))
         self._lib = _lib.load()
         self._table_host, self._table = None, None
@@ -536,7 +547,7 @@ class FramePipeline:
         lib = self._lib
         arrays, n, m = _frame_args(ids, layer, pos, bb_min, bb_max, label, edges)
         h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self._relpos, self.sem_dim, self.n_labels, self.clique_dim,
-                         self.homogeneous)
+                         self.homogeneous, self.remove_room_edges)
         try:
             sz = self._sizes
             _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
@@ -605,7 +616,7 @@ class FramePipeline:
             for fr in frames:
                 arrays, n, m = _frame_args(*fr)
                 h = _frame_build(lib, arrays, n, m, self.thresholds, self.htree, self._relpos, self.sem_dim, self.n_labels,
-                                 self.clique_dim, self.homogeneous)
+                                 self.clique_dim, self.homogeneous, self.remove_room_edges)
                 built.append((h, arrays))
                 _lib.check(lib.hmp_frame_sizes(h, sz.ctypes.data))
                 if int(sz[_lib.FS_ITEMS]) == 0:

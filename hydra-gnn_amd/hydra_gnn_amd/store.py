@@ -20,9 +20,9 @@ stored under the names the homogeneous models present to the executor (node type
 masks of both heads in its own buffers (``tests/test_gpu_semisupervised_stream.py``); a stream created for a homogeneous room
 classifier carries ``room_mask`` and the room-masked labels (``tests/test_gpu_homog_room_stream.py``).
 
-A resident store is also where the configurations come from: ``with_relative_pos`` / ``to_homogeneous`` / ``remove_last_features``
-return the store of the transformed graphs from one launch of ``csrc/store_derive.hip``, ``generate_node_split`` writes the Stanford
-protocol's per-run masks in place, and :class:`StoreDataset` hands a store to the training jobs (second half of this module).
+A resident store is also where the configurations come from: ``with_relative_pos`` / ``to_homogeneous`` / ``remove_last_features`` /
+``without_edge_types`` / ``zero_clique_features`` return the store of the transformed graphs from one launch of
+``csrc/store_derive.hip``, ``generate_node_split`` writes the Stanford protocol's per-run masks in place, and :class:`StoreDataset` hands a store to the training jobs (second half of this module).
 """
 from __future__ import annotations
 
@@ -765,6 +765,28 @@ class DerivePlan:
             self._item(_lib.SD_RELPOS, n, SRC=edge_index, DST=dst, SRC_PTR=edge_ptr, N=n, A0=pos_src, A1=pos_dst, A2=ptr_src, A3=ptr_dst,
                        UNIT=4)
 
+    def compact(self, src: int, dst: int, src_ptr: int, dst_off, n: int, row_bytes: int, key: int, key_set: int):
+        """the rows of ``row_bytes`` bytes whose int64 ``key`` (one per source row) is not in the 64-bit ``key_set``, graph by graph in
+        source order from row ``dst_off[g]`` on: a wave per graph"""
+        assert 0 <= key_set < 1 << 64 and row_bytes > 0
+        if n == 0:
+            return
+        u = 8 if row_bytes % 8 == 0 and src % 8 == 0 and dst % 8 == 0 else 4
+        assert row_bytes % u == 0 and src % u == 0 and dst % u == 0
+        signed = key_set - (1 << 64) if key_set >> 63 else key_set  # the table is int64 words
+        self._item(_lib.SD_COMPACT, self.G * 64, SRC=src, DST=dst, SRC_PTR=src_ptr, DST_OFF=self.vector(dst_off), N=n, SRC_W=row_bytes // u,
+                   DST_W=row_bytes // u, A0=key, A1=signed, UNIT=u)
+
+    def rows_zero(self, src: int, dst: int, src_ptr: int, dst_off, n: int, row_bytes: int, key: int, key_set: int):
+        """rows copied, written as zeros where the row's int64 ``key`` is in the 64-bit ``key_set``"""
+        assert 0 <= key_set < 1 << 64
+        if n == 0 or row_bytes == 0:
+            return
+        u = _unit_of(row_bytes, src, dst)
+        signed = key_set - (1 << 64) if key_set >> 63 else key_set
+        self._item(_lib.SD_ROWS_ZERO, n * (row_bytes // u), SRC=src, DST=dst, SRC_PTR=src_ptr, DST_OFF=self.vector(dst_off), N=n,
+                   SRC_W=row_bytes // u, TAKE=row_bytes // u, DST_W=row_bytes // u, A0=key, A1=signed, UNIT=u)
+
     def layout(self):
         """``(words, item_word0, vector_word0 [n_vectors])`` of the block: group table (even count), items, vectors (16-byte aligned)"""
         n = len(self.items)
@@ -912,11 +934,19 @@ def _remove_last_features(self: "GraphStore", dim: int) -> "GraphStore":
     return new
 
 
-def _to_homogeneous(self: "GraphStore") -> "GraphStore":
+def _to_homogeneous(self: "GraphStore", removed_edge_type: Optional[EdgeType] = None) -> "GraphStore":
     """The homogeneous store of the same graphs.  Without ``object_virtual`` / ``room_virtual`` node types:
     ``data.heterogeneous_data_to_homogeneous`` per graph plus ``room_mask = node_type == index("rooms")``; with them:
     ``data.heterogeneous_htree_to_homogeneous`` (reference ``mp3d_dataset.py:29-119``).  Node types with ``x`` take part, in store order;
-    features are zero-padded to the widest type."""
+    features are zero-padded to the widest type.  ``removed_edge_type`` (a store without virtual node types only, as in the reference,
+    ``mp3d_dataset.py:53-69``): the edges of that type stay out of ``edge_index`` / ``edge_type`` / ``edge_attr`` -- a change to the plan
+    alone, the removed type contributes no item -- and the other types keep their numbers."""
+    plan, parts = _plan_to_homogeneous(self, removed_edge_type)
+    return _finish_to_homogeneous(self, plan, *parts)
+
+
+def _plan_to_homogeneous(self: "GraphStore", removed_edge_type: Optional[EdgeType] = None):
+    """the plan of ``to_homogeneous`` and what the new store is assembled from: every output is allocated, nothing is launched"""
     what = "to_homogeneous"
     if self.homogeneous:
         raise _lib.HydraMPError(f"{what}: the store is homogeneous already")
@@ -928,6 +958,13 @@ def _to_homogeneous(self: "GraphStore") -> "GraphStore":
     if not htree and "rooms" not in types:
         raise _lib.HydraMPError(f"{what}: no node type 'rooms' with features 'x' (room_mask marks its rows)")
     virtual = ("object_virtual", "room_virtual") if htree else ()
+    if removed_edge_type is not None:
+        removed_edge_type = tuple(removed_edge_type)
+        if htree:
+            raise _lib.HydraMPError(f"{what}: removed_edge_type is refused on an H-tree store (the reference's H-tree converter has no "
+                                    f"such argument); on the homogeneous store: .without_edge_types([ids])")
+        if removed_edge_type not in self.edge_types:
+            raise _lib.HydraMPError(f"{what}: removed_edge_type {removed_edge_type} is not an edge type of the store: {self.edge_types}")
     group_of = {}
     for e in self.edge_types:
         for t in (e[0], e[2]):
@@ -985,7 +1022,7 @@ def _to_homogeneous(self: "GraphStore") -> "GraphStore":
     edge_out, edge_ptr_host = {}, {}
     edge_type = edge_attr = None
     for name in groups:
-        members = [e for e in self.edge_types if group_of[e] == name]
+        members = [e for e in self.edge_types if group_of[e] == name and e != removed_edge_type]
         if members:
             eptr, _, edst = plan_concat([np.diff(self.edge_ptr_host[e]) for e in members])
         else:
@@ -1006,6 +1043,13 @@ def _to_homogeneous(self: "GraphStore") -> "GraphStore":
                 if has_ea:
                     pk = self.edge_attr[e]
                     plan.rows(pk.data.data_ptr(), edge_attr.data_ptr(), ep, edst[j], n, pk.row_bytes, 0, pk.row_bytes, pk.row_bytes)
+    return plan, (groups, node_ptr, edge_ptr_host, edge_out, edge_type, edge_attr, x, node_type, y, room_mask, object_mask, has_y, has_ea,
+                  htree)
+
+
+def _finish_to_homogeneous(self, plan, groups, node_ptr, edge_ptr_host, edge_out, edge_type, edge_attr, x, node_type, y, room_mask, object_mask,
+                           has_y, has_ea, htree) -> "GraphStore":
+    G, dev = self.n_graphs, self.device
     dev_vecs = _run_plan(self, plan, keep=[node_ptr] + [edge_ptr_host[name] for name in groups])
     node_ptr_dev, edge_ptr_dev = dev_vecs[0], dict(zip(groups, dev_vecs[1:]))
 
@@ -1028,6 +1072,122 @@ def _to_homogeneous(self: "GraphStore") -> "GraphStore":
     new.edge_rows[e0] = {"edge_type": _packed(edge_type, new.edge_ptr[e0], new.edge_ptr_host[e0])}
     if has_ea:
         new.edge_attr[e0] = new.edge_rows[e0]["edge_attr"] = _packed(edge_attr, new.edge_ptr[e0], new.edge_ptr_host[e0])
+    return new
+
+
+def _empty_packed(pk: _Packed, ptr: torch.Tensor, ptr_host: np.ndarray) -> _Packed:
+    return _packed(torch.empty((0,) + pk.row_shape, dtype=pk.data.dtype, device=pk.data.device), ptr, ptr_host)
+
+
+def _without_edge_types(self: "GraphStore", edge_types) -> "GraphStore":
+    """The store of ``data.remove_edge_types`` applied to every graph.  Typed store: ``edge_types`` are triples; each stays in the store
+    with no edge in any graph (the reference's ``noRE`` data, ``remove_room_edges_in_dsg``, for ``rooms_to_rooms``) -- nothing but the mask
+    rows is copied.  Homogeneous store: ``edge_types`` are ints below 64; the columns of ``edge_index`` with that ``edge_type`` are
+    dropped, ``edge_type`` and ``edge_attr`` follow, ``init_edge_index`` / ``pool_edge_index`` stay: a count launch
+    (``hmp_store_count_kept``), one read of ``G`` int64, and a stable compaction in the derive launch."""
+    what = "without_edge_types"
+    edge_types = list(edge_types)
+    new, plan = _derived(self), DerivePlan(self.n_graphs)
+    G, dev = self.n_graphs, self.device
+    if not self.homogeneous:
+        for e in edge_types:
+            if not isinstance(e, (tuple, list)) or tuple(e) not in self.edge_types:
+                raise _lib.HydraMPError(f"{what}: {e!r} is not an edge type of the store: {self.edge_types}")
+        zero_host = np.zeros(G + 1, dtype=np.int64)
+        zero_dev = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+        for e in dict.fromkeys(tuple(e) for e in edge_types):
+            new.edge_index[e] = torch.empty((2, 0), dtype=torch.int64, device=dev)
+            new.edge_ptr[e], new.edge_ptr_host[e] = zero_dev, zero_host
+            if e in new.edge_rows:
+                new.edge_rows[e] = {k: _empty_packed(pk, zero_dev, zero_host) for k, pk in self.edge_rows[e].items()}
+            if e in new.edge_attr:
+                new.edge_attr[e] = new.edge_rows[e]["edge_attr"]
+        _own_masks(new, plan)
+        if plan.items:
+            _run_plan(self, plan)
+        return new
+    ids = []
+    for t in edge_types:
+        if isinstance(t, (bool, tuple, list, str)) or int(t) != t:
+            raise _lib.HydraMPError(f"{what}: a homogeneous store takes edge type numbers (ints), got {t!r}")
+        if not 0 <= int(t) < 64:
+            raise _lib.HydraMPError(f"{what}: edge type number {int(t)} is outside [0, 64): the removed types travel as a 64-bit set")
+        ids.append(int(t))
+    e0 = homo_edge_type("edge_index")
+    rows = self.edge_rows.get(e0, {})
+    if e0 not in self.edge_index or "edge_type" not in rows:
+        raise _lib.HydraMPError(f"{what}: the store holds no 'edge_type' rows of 'edge_index'")
+    key = rows["edge_type"]
+    if key.data.dtype != torch.int64 or key.row_shape != ():
+        raise _lib.HydraMPError(f"{what}: 'edge_type' must be an int64 vector, the store holds {key.row_shape} {key.data.dtype}")
+    key_set = 0
+    for t in ids:
+        key_set |= 1 << t
+    ei, ep, ep_host = self.edge_index[e0], self.edge_ptr[e0], self.edge_ptr_host[e0]
+    E = int(ep_host[-1])
+    kept = torch.empty(G, dtype=torch.int64, device=dev)
+    _lib.check(self.lib.hmp_store_count_kept(key.data.data_ptr() if E else None, ep.data_ptr(), G, key_set, kept.data_ptr(), _lib.stream_ptr()))
+    counts = kept.cpu().numpy()  # the one device-to-host read: G int64
+    ptr_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    E_new = int(ptr_host[-1])
+    out_ei = _derive_alloc((2, E_new), torch.int64, dev)
+    kp, sp = key.data.data_ptr(), ep.data_ptr()
+    if E_new:
+        for r in range(2):
+            plan.compact(ei.data_ptr() + 8 * E * r, out_ei.data_ptr() + 8 * E_new * r, sp, ptr_host[:-1], E, 8, kp, key_set)
+    out_rows = {}
+    for k, pk in rows.items():
+        out_rows[k] = _derive_alloc((E_new,) + pk.row_shape, pk.data.dtype, dev)
+        if pk.row_bytes % 4:
+            raise _lib.HydraMPError(f"{what}: '{k}' rows of {pk.row_bytes} bytes (the compaction moves 4- or 8-byte units)")
+        if E_new:
+            plan.compact(pk.data.data_ptr(), out_rows[k].data_ptr(), sp, ptr_host[:-1], E, pk.row_bytes, kp, key_set)
+    _own_masks(new, plan)
+    (ptr_dev,) = _run_plan(self, plan, keep=[ptr_host])
+    new.edge_index[e0], new.edge_ptr[e0], new.edge_ptr_host[e0] = out_ei, ptr_dev, ptr_host
+    new.edge_rows[e0] = {k: _packed(v, ptr_dev, ptr_host) for k, v in out_rows.items()}
+    if e0 in self.edge_attr:
+        new.edge_attr[e0] = new.edge_rows[e0]["edge_attr"]
+    return new
+
+
+CLIQUE_NODE_TYPES = ("object-room", "room-room")
+
+
+def _zero_clique_features(self: "GraphStore") -> "GraphStore":
+    """The store of ``data.zero_clique_features`` applied to every graph (reference ``train_Stanford.py:93-99``): ``x`` of the two clique
+    node types of an H-tree is zero.  Typed store: the two types' ``x``; homogeneous H-tree store: the rows of ``x`` whose ``node_type`` is
+    one of the two.  A store that is not an H-tree is refused."""
+    what = "zero_clique_features"
+    new, plan = _derived(self), DerivePlan(self.n_graphs)
+    if not self.homogeneous:
+        for t in CLIQUE_NODE_TYPES:
+            if t not in self.node_types or "x" not in self.node_attrs[t]:
+                raise _lib.HydraMPError(f"{what}: the store holds no node type '{t}' with features 'x' (not an H-tree store)")
+        for t in CLIQUE_NODE_TYPES:
+            pk = _features(self, t, what)
+            n = int(pk.ptr_host[-1])
+            out = _derive_alloc(tuple(pk.data.shape), torch.float32, self.device)
+            plan.rows(pk.data.data_ptr(), out.data_ptr(), pk.ptr.data_ptr(), pk.ptr_host[:-1], n, pk.row_bytes, 0, 0, pk.row_bytes)
+            new.node_attrs[t]["x"] = _packed(out, pk.ptr, pk.ptr_host)
+    else:
+        attrs = self.node_attrs[HOMO_NODE]
+        if "object_mask" not in attrs or "node_type" not in attrs:
+            raise _lib.HydraMPError(f"{what}: the homogeneous store is not an H-tree store (no 'object_mask' / 'node_type')")
+        pk, key = _features(self, HOMO_NODE, what), attrs["node_type"]
+        if key.data.dtype != torch.int64 or key.row_shape != ():
+            raise _lib.HydraMPError(f"{what}: 'node_type' must be an int64 vector, the store holds {key.row_shape} {key.data.dtype}")
+        from .data import HTREE_NODE_TYPES
+        key_set = 0
+        for t in CLIQUE_NODE_TYPES:
+            key_set |= 1 << HTREE_NODE_TYPES.index(t)
+        n = int(pk.ptr_host[-1])
+        out = _derive_alloc(tuple(pk.data.shape), torch.float32, self.device)
+        plan.rows_zero(pk.data.data_ptr(), out.data_ptr(), pk.ptr.data_ptr(), pk.ptr_host[:-1], n, pk.row_bytes, key.data.data_ptr(), key_set)
+        new.node_attrs[HOMO_NODE]["x"] = _packed(out, pk.ptr, pk.ptr_host)
+    _own_masks(new, plan)
+    if plan.items:
+        _run_plan(self, plan)
     return new
 
 
@@ -1128,6 +1288,8 @@ def _generate_node_split(self: "GraphStore", train_node_ratio, val_node_ratio, t
 GraphStore.with_relative_pos = _with_relative_pos
 GraphStore.to_homogeneous = _to_homogeneous
 GraphStore.remove_last_features = _remove_last_features
+GraphStore.without_edge_types = _without_edge_types
+GraphStore.zero_clique_features = _zero_clique_features
 GraphStore.generate_node_split = _generate_node_split
 GraphStore.__len__ = lambda self: self.n_graphs
 

@@ -53,7 +53,11 @@ extern "C" {
  *    hmp_frame_batch_build / _items_needed / _sizes / _host_arrays / _pack / _destroy and hmp_frame_expand_batch: many frames per
  *    block and launch (output tensors from HMP_FT_BATCH on).  New entries; a single frame packs what it packed, nothing above changed;
  *    relative_pos = HMP_FRAME_RELPOS_HTREE (item kind HMP_FK_EATTR_HT, output tensors from HMP_FT_HTREL on): a new value of an argument
- *    that was refused before; no entry, struct or earlier number changed, every earlier mode packs what it packed */
+ *    that was refused before; no entry, struct or earlier number changed, every earlier mode packs what it packed;
+ *    hmp_frame_build_flags (HMP_FRAME_NO_ROOM_EDGES: the reference's remove_room_edges_in_dsg in the host stage), item kinds
+ *    HMP_SD_COMPACT / HMP_SD_ROWS_ZERO of hmp_store_derive's table and hmp_store_count_kept (the edge-type and clique ablations on a
+ *    resident store): new entries and new kinds behind the old ones; hmp_collator_create accepts a null d_src for an item whose
+ *    slot is empty in every graph (it was refused before) */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -666,7 +670,7 @@ int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const int64_t* d_ed
  * at most 24 slots and 40 items: the two-headed H-tree dataset with edge attributes has 21 and 39.  Byte-wide rows are a branch
  * of the same kernel: a batch of the two-headed task, labels and masks of both heads included, is still ONE launch.) */
 typedef struct hmp_collate_item {
-  const void* d_src;
+  const void* d_src;         /* null only for a slot that is empty in every graph (no workgroup, nothing written) */
   const int64_t* d_ptr;      /* device copy of the item's [G + 1] offsets */
   int64_t src_total;         /* edges: E_total of the packed edge_index */
   int64_t row_bytes;         /* rows: bytes per row (> 0; not a multiple of 4: copied byte by byte); edges: 0 */
@@ -884,6 +888,16 @@ int hmp_frame_build_homogeneous(int32_t n, const uint64_t* ids, const int32_t* l
                                 const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
                                 double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim,
                                 int32_t n_labels, int32_t clique_dim, hmp_frame** out);
+/* both layouts with `flags`: HMP_FRAME_NO_ROOM_EDGES drops the room-room edges before anything reads them (the reference's
+ * Hydra_mp3d_data.remove_room_edges_in_dsg, mp3d_dataset.py:203-208, the `noRE` configurations): rooms_to_rooms is empty and HMP_FS_E_RR
+ * is 0; an H-tree is built from the edgeless room layer (every room its own component, no room-room clique).  The result is what
+ * the same frame gives with its room-room pairs deleted from `edges`.  flags = 0: hmp_frame_build / hmp_frame_build_homogeneous.
+ * The frames of a batch share their flags.  Unknown bits are refused. */
+#define HMP_FRAME_NO_ROOM_EDGES 1
+int hmp_frame_build_flags(int32_t n, const uint64_t* ids, const int32_t* layer, const double* pos, const double* bb_min,
+                          const double* bb_max, const int64_t* label, int64_t m, const uint64_t* edges, double threshold_near,
+                          double max_near, double max_on, int32_t htree, int32_t relative_pos, int32_t sem_dim, int32_t n_labels,
+                          int32_t clique_dim, int32_t homogeneous, int32_t flags, hmp_frame** out);
 #define HMP_FRAME_RELPOS_HTREE 2 /* value of `relative_pos`: relative positions on the edges of an H-tree (htree = 1 only) */
 /* sizes[HMP_FS_COUNT] */
 #define HMP_FS_KEPT 0          /* kept objects */
@@ -1063,6 +1077,17 @@ int hmp_frame_expand_batch(const void* d_staging, void* d_arena, const float* d_
  *     workgroups end at the next item's, the last item's at n_blocks, and an item with more work than its workgroups cover in one
  *     pass walks it with a grid stride.  Pointers travel as int64 words.  No atomics: the plan owes that the items tile the outputs.
  *     At most HMP_SD_MAX_ITEMS items (64 groups).
+ *     Two kinds select rows by a KEY vector (A0: device int64, one key per source row) and a 64-bit SET (A1: bit k = key k is in
+ *     the set; a key outside [0, 64) is in no set) -- the edge-type and clique ablations of the reference (to_homogeneous's
+ *     removed_edge_type, mp3d_dataset.py:53-69; x[clique_has == -1] = 0, train_Stanford.py:93-99):
+ *       HMP_SD_COMPACT    the rows of graph g whose key is NOT in the set, in source order, back to back from destination row
+ *                         DST_OFF[g] (stable).  One wave per graph, 64 rows per sweep, rank = popcount of the ballot below the lane;
+ *                         waves stride over the graphs.  Rows of SRC_W = DST_W units of UNIT bytes (8 / 4).  The plan owes DST_OFF from
+ *                         the kept rows per graph, which hmp_store_count_kept writes (d_counts [G]; one wave per graph, ballot and
+ *                         popcount) and the host reads once.  Every array of one edge list is an item of its own with the same key
+ *                         vector: the two rows of edge_index (SRC / DST advanced by the row pitch), edge_type, edge_attr.
+ *       HMP_SD_ROWS_ZERO  HMP_SD_ROWS with SKIP 0 and TAKE = SRC_W = DST_W, except that a row whose key is in the set is written as
+ *                         zeros (its source is not read).
  *
  *     hmp_store_node_split: one wave per graph writes train / val / test byte rows from d_assign (int8: 0 unassigned, 1 / 2 / 3),
  *     graph g's members starting at d_assign_off[g].  d_member_* null: part a's rows [d_ptr_a[g], d_ptr_a[g + 1]) take the first
@@ -1092,6 +1117,9 @@ int hmp_frame_expand_batch(const void* d_staging, void* d_arena, const float* d_
 #define HMP_SD_FILL 1
 #define HMP_SD_EDGES 2
 #define HMP_SD_RELPOS 3
+#define HMP_SD_COMPACT 4
+#define HMP_SD_ROWS_ZERO 5
+int hmp_store_count_kept(const int64_t* d_key, const int64_t* d_ptr, int32_t n_graphs, uint64_t set, int64_t* d_counts, void* stream);
 int hmp_store_derive(const int64_t* d_block, int32_t n_items, int32_t n_blocks, int32_t n_graphs, void* stream);
 int hmp_store_node_split(const int8_t* d_assign, const int64_t* d_assign_off, int32_t n_graphs, const int64_t* d_ptr_a,
                          const int64_t* d_ptr_b, const uint8_t* d_member_a, const uint8_t* d_member_b, uint8_t* d_train_a,
