@@ -23,6 +23,11 @@
 //
 // No atomics: backward pass 1 runs destination-major (d logits, d a_dst), pass 2 source-major over the CSC lists
 // (d h_s, d a_src) reading what pass 1 stored per edge.
+//
+// Attention export (gat_attention_kernel, forward only): alpha per edge in the caller's edge order and the top-k sources per
+// row, recomputed from the saved (max, denominator) with the backward's expression -- see the block comment in front of it.
+#include <climits>
+
 #include "tail_fns.h"
 
 namespace hmp {
@@ -154,25 +159,30 @@ struct EdgeBatch {
   float4 v[UB][R][HM];
 };
 
+// Neighbour slot k of destination row `row`: real edges [b, e), then the virtual self loop at k == e when kend > e.  The loop
+// and removed-entry rules of every kernel here; want_eid (uniform): the original edge id is loaded (0 otherwise).
+__device__ __forceinline__ void edge_slot(const GatInS& I, bool want_eid, int row, int b, int e, int kend, int k, int& j, int& eid,
+                                          bool& live, bool& loop, bool& removed) {
+  const bool in = k < kend;
+  const bool lp = in && k >= e;
+  const int kc = (e > b) ? min(k, e - 1) : 0;
+  const int cj = glob(I.col)[kc];
+  const int ce = want_eid ? glob(I.eid)[kc] : 0;
+  const bool real = in && !lp;
+  loop = lp;
+  j = lp ? row : (real ? cj : 0);  // dead slots read row 0 (always allocated), never used
+  eid = real ? ce : 0;
+  removed = real && I.self_loops && cj == row;
+  live = in && !removed;
+}
+
 template <int HM, int UB, int R>
 __device__ __forceinline__ void fetch_batch(const GatInS& I, int Cp, const float* __restrict__ ea, int H, int row, int b, int e, int kend,
                                             int k0, const int (&cc)[R], const float (&ad)[HM], const float (&ve)[GAT_MAX_EDIM][HM],
                                             EdgeBatch<HM, UB, R>& B) {
 #pragma unroll
-  for (int u = 0; u < UB; ++u) {
-    const int k = k0 + u;
-    const bool in = k < kend;
-    const bool lp = in && k >= e;
-    const int kc = (e > b) ? min(k, e - 1) : 0;
-    const int cj = glob(I.col)[kc];
-    const int ce = ea ? glob(I.eid)[kc] : 0;
-    const bool real = in && !lp;
-    B.loop[u] = lp;
-    B.j[u] = lp ? row : (real ? cj : 0);  // dead slots read row 0 (always allocated), never used
-    B.eid[u] = real ? ce : 0;
-    B.removed[u] = real && I.self_loops && cj == row;
-    B.live[u] = in && !B.removed[u];
-  }
+  for (int u = 0; u < UB; ++u)
+    edge_slot(I, ea != nullptr, row, b, e, kend, k0 + u, B.j[u], B.eid[u], B.live[u], B.loop[u], B.removed[u]);
 #pragma unroll
   for (int u = 0; u < UB; ++u) {
     edge_logits<HM>(I, ea, H, I.za + (int64_t)B.j[u] * I.ldza, ad, ve, !B.loop[u] && B.live[u], B.eid[u], B.raw[u]);
@@ -684,6 +694,150 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
   }
 }
 
+// =================================================================================================
+// attention export: alpha of the last forward per edge (the caller's edge order) and / or the k most attended sources per row.
+//
+// Mapping: a group of ATT_GS = 16 lanes per destination row, four rows per wavefront; lane g takes the row's slots b + g,
+// b + g + 16, ...  There is no feature gather, so unlike the forward the lanes SPLIT the slots: an object row (a handful of
+// neighbours) is one trip, a room row with hundreds of objects ceil(deg / 16).  Per slot a lane reads col / eid (consecutive
+// lanes, consecutive words), the neighbour's a_s and the edge attributes (scattered, H and edim words), and stores its H
+// coefficients as one row of alpha at eid -- scattered by nature, 16 bytes per store when H is 4 or 8.  The row's softmax state
+// (32-byte rows of smax / sden) is two 16-byte loads, the same address in all 16 lanes.
+//
+// Top-k: every lane keeps the GAT_ATT_KMAX best (mean, slot) of its own slots, sorted (a strict > on insertion keeps the earlier
+// slot ahead among equal means: a lane meets its slots in ascending order); k rounds of a 16-lane butterfly then pick the group's
+// best head (larger mean, then smaller slot -- slots are unique, so every lane agrees) and its owner pops it.  Lane j keeps
+// result j and stores column j.
+//
+// Blocks past a request's row blocks are its sweep blocks: they walk the caller's edge list and zero the alpha rows of the edges
+// the plan dropped (no row group owns those).
+// =================================================================================================
+constexpr int ATT_GS = 16;
+constexpr int ATT_SWEEP_MAX = 64;  // sweep blocks per request (grid stride beyond)
+static_assert(GAT_ATT_KMAX <= ATT_GS, "lane j of a row group stores top-k column j");
+
+template <int HM>
+__global__ __launch_bounds__(256) void gat_attention_kernel(const GatLayerS* __restrict__ tab, const GatDyn dyn, const GatAttArgs a) {
+  int q = 0;
+  while (q + 1 < a.n && (int)blockIdx.x >= a.block_start[2 * (q + 1)]) ++q;
+  const GatAttReq& R = a.r[q];
+  const GatDstS& D = tab->d[R.d];
+  const GatInS& I = D.in[R.i];
+  const int H = D.H;
+  const int64_t E = dyn.n_edges[I.et];
+  const int n_dst = dyn.n_nodes[D.t], n_src = dyn.n_nodes[I.src_t];
+
+  if ((int)blockIdx.x >= a.block_start[2 * q + 1]) {  // ---- sweep role: rows of dropped edges
+    const int64_t nb = a.block_start[2 * q + 2] - a.block_start[2 * q + 1];
+    for (int64_t eo = ((int64_t)blockIdx.x - a.block_start[2 * q + 1]) * 256 + threadIdx.x; eo < E; eo += nb * 256) {
+      if (plan_edge_ok(glob(R.ei)[eo], glob(R.ei)[E + eo], n_src, n_dst)) continue;
+      for (int h = 0; h < H; ++h) globw(R.alpha)[eo * H + h] = 0.f;
+    }
+    return;
+  }
+
+  const int row = ((int)blockIdx.x - a.block_start[2 * q]) * (256 / ATT_GS) + (int)threadIdx.x / ATT_GS;
+  if (row >= n_dst) return;  // whole groups leave together: the shuffles below stay inside a group
+  const int gl = threadIdx.x % ATT_GS;
+  const int n_loop = I.self_loops ? min(n_src, n_dst) : 0;
+  const float* ea = (I.edim > 0 && E > 0) ? dyn.edge_attr[I.et] : nullptr;
+  float ad[HM], ve[GAT_MAX_EDIM][HM], m[HM], den[HM];
+  load_row_consts<HM>(I, H, row, ad, ve);
+  {  // the launcher checked the 16-byte alignment; heads >= H: values nobody reads
+    const float4 m0 = ld4(I.smax + (int64_t)row * GAT_HMAX), d0 = ld4(I.sden + (int64_t)row * GAT_HMAX);
+    const float mm[4] = {m0.x, m0.y, m0.z, m0.w}, dd[4] = {d0.x, d0.y, d0.z, d0.w};
+#pragma unroll
+    for (int h = 0; h < HM && h < 4; ++h) { m[h] = mm[h]; den[h] = dd[h]; }
+    if (HM > 4) {
+      const float4 m1 = ld4(I.smax + (int64_t)row * GAT_HMAX + 4), d1 = ld4(I.sden + (int64_t)row * GAT_HMAX + 4);
+      const float mm1[4] = {m1.x, m1.y, m1.z, m1.w}, dd1[4] = {d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+      for (int h = 4; h < HM; ++h) { m[h] = mm1[h - 4]; den[h] = dd1[h - 4]; }
+    }
+  }
+  const int b = glob(I.rowptr)[row], e = glob(I.rowptr)[row + 1];
+  const int kend = e + ((row < n_loop) ? 1 : 0);
+  const bool want_top = R.top_src || R.top_w;                                              // uniform
+  const bool vec = R.alpha && H == HM && HM >= 4 && (reinterpret_cast<uintptr_t>(R.alpha) & 15) == 0;  // uniform: H is 4 or 8
+
+  float tv[GAT_ATT_KMAX];  // this lane's best means, descending; -1 marks an empty place (a mean is >= 0)
+  int tp[GAT_ATT_KMAX];    // their slots
+#pragma unroll
+  for (int i = 0; i < GAT_ATT_KMAX; ++i) { tv[i] = -1.f; tp[i] = INT_MAX; }
+
+  for (int k = b + gl; k < kend; k += ATT_GS) {
+    int j, eid;
+    bool live, loop, removed;
+    edge_slot(I, true, row, b, e, kend, k, j, eid, live, loop, removed);
+    float raw[HM], al[HM];
+    edge_logits<HM>(I, ea, H, I.za + (int64_t)j * I.ldza, ad, ve, !loop && live, eid, raw);
+#pragma unroll
+    for (int h = 0; h < HM; ++h) {
+      const float ev = raw[h] > 0.f ? raw[h] : NEG_SLOPE * raw[h];
+      al[h] = (live && h < H) ? expf(ev - m[h]) / den[h] : 0.f;  // a removed loop's row is 0
+    }
+    if (R.alpha) {
+      float* ar = R.alpha + (loop ? E + row : (int64_t)eid) * H;
+      bool stored = false;
+      if constexpr (HM >= 4) {
+        if (vec) {
+#pragma unroll
+          for (int h = 0; h < HM; h += 4) st4(ar + h, make_float4(al[h], al[h + 1], al[h + 2], al[h + 3]));
+          stored = true;
+        }
+      }
+      if (!stored) {
+#pragma unroll
+        for (int h = 0; h < HM; ++h)
+          if (h < H) globw(ar)[h] = al[h];
+      }
+    }
+    if (want_top && live) {
+      float v = al[0];  // head mean in float32: heads added in ascending order, then one division
+#pragma unroll
+      for (int h = 1; h < HM; ++h)
+        if (h < H) v += al[h];
+      v = v / (float)H;
+      int p = k;
+#pragma unroll
+      for (int i = 0; i < GAT_ATT_KMAX; ++i) {
+        if (v > tv[i]) {
+          const float fv = tv[i];
+          const int fp = tp[i];
+          tv[i] = v; tp[i] = p;
+          v = fv; p = fp;
+        }
+      }
+    }
+  }
+  if (!want_top) return;
+
+  float rv = -1.f;
+  int rp = INT_MAX;
+  for (int r = 0; r < a.k; ++r) {
+    float v = tv[0];
+    int p = tp[0];
+#pragma unroll
+    for (int o = ATT_GS / 2; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(v, o);
+      const int op = __shfl_xor(p, o);
+      if (ov > v || (ov == v && op < p)) { v = ov; p = op; }
+    }
+    if (tp[0] == p) {  // the owner pops (groups with nothing left all hold the empty mark: popping it changes nothing)
+#pragma unroll
+      for (int i = 0; i + 1 < GAT_ATT_KMAX; ++i) { tv[i] = tv[i + 1]; tp[i] = tp[i + 1]; }
+      tv[GAT_ATT_KMAX - 1] = -1.f; tp[GAT_ATT_KMAX - 1] = INT_MAX;
+    }
+    if (gl == r) { rv = v; rp = p; }
+  }
+  if (gl < a.k) {
+    const bool have = rp != INT_MAX;
+    const int src = !have ? -1 : (rp >= e ? row : glob(I.col)[rp]);
+    if (R.top_src) R.top_src[(int64_t)row * a.k + gl] = src;
+    if (R.top_w) globw(R.top_w)[(int64_t)row * a.k + gl] = have ? rv : 0.f;
+  }
+}
+
 template <typename F>
 int dispatch(int H, int Cp, F&& f) {
   const int lanes = Cp / 4;
@@ -789,6 +943,37 @@ int gat_bwd2_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn,
   });
 }
 
+int gat_attention_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, GatAttArgs& a, hipStream_t st) {
+  int H, Cp;
+  HMP_TRY(layer_shape(h_tab, H, Cp));
+  HMP_CHECK_ARG(H >= 1 && H <= GAT_HMAX, "gat attention: heads %d not in [1, %d]", H, GAT_HMAX);
+  HMP_CHECK_ARG(a.n >= 0 && a.n <= HMP_MAX_EDGE_TYPES, "gat attention: %d requests", a.n);
+  HMP_CHECK_ARG(a.k >= 1 && a.k <= GAT_ATT_KMAX, "gat attention: k = %d (1 .. %d)", a.k, GAT_ATT_KMAX);
+  int blocks = 0;
+  for (int q = 0; q < a.n; ++q) {
+    const GatAttReq& R = a.r[q];
+    HMP_CHECK_ARG(R.d >= 0 && R.d < h_tab.n_dst && R.i >= 0 && R.i < h_tab.d[R.d].n_in, "gat attention: request %d names no conv of the layer", q);
+    const GatInS& I = h_tab.d[R.d].in[R.i];
+    HMP_CHECK_ARG(I.smax && I.sden && ((reinterpret_cast<uintptr_t>(I.smax) | reinterpret_cast<uintptr_t>(I.sden)) & 15) == 0,
+                  "gat attention: smax / sden must be 16-byte aligned");
+    const int64_t E = dyn.n_edges[I.et];
+    a.block_start[2 * q] = blocks;
+    blocks += cdiv(dyn.n_nodes[h_tab.d[R.d].t], 256 / ATT_GS);
+    a.block_start[2 * q + 1] = blocks;
+    if (R.alpha && R.ei && E > 0) blocks += E < (int64_t)ATT_SWEEP_MAX * 256 ? cdiv(E, 256) : ATT_SWEEP_MAX;
+  }
+  a.block_start[2 * a.n] = blocks;
+  if (blocks == 0) return HMP_OK;
+  switch (H <= 1 ? 1 : (H <= 2 ? 2 : (H <= 4 ? 4 : 8))) {
+    case 1: hipLaunchKernelGGL((gat_attention_kernel<1>), dim3(blocks), dim3(256), 0, st, d_tab, dyn, a); break;
+    case 2: hipLaunchKernelGGL((gat_attention_kernel<2>), dim3(blocks), dim3(256), 0, st, d_tab, dyn, a); break;
+    case 4: hipLaunchKernelGGL((gat_attention_kernel<4>), dim3(blocks), dim3(256), 0, st, d_tab, dyn, a); break;
+    default: hipLaunchKernelGGL((gat_attention_kernel<8>), dim3(blocks), dim3(256), 0, st, d_tab, dyn, a); break;
+  }
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 }  // namespace hmp
 
 // =================================================================================================
@@ -887,6 +1072,30 @@ extern "C" int hmp_gat_bwd(const float* d_gout, int32_t ldg, const float* d_h_sr
   HMP_TRY(unit_upload(u));
   HMP_TRY(gat_bwd1_launch(u.d, u.h, dyn, (hipStream_t)stream));
   HMP_TRY(gat_bwd2_launch(u.d, u.h, dyn, (hipStream_t)stream));
+  HMP_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return HMP_OK;
+}
+
+extern "C" int hmp_gat_attention(const float* d_a_src, int32_t lda_src, const float* d_a_dst, int32_t lda_dst, const float* d_edge_attr,
+                                 const float* d_v_edge, const int64_t* d_edge_index, hmp_plan plan, hmp_gat_args args,
+                                 const float* d_smax, const float* d_sden, float* d_alpha, int32_t k, int64_t* d_top_src, float* d_top_w,
+                                 void* stream) {
+  HMP_CHECK_ARG(d_a_src && d_a_dst && d_smax && d_sden, "hmp_gat_attention: null pointer");
+  HMP_CHECK_ARG(k >= 1 && k <= GAT_ATT_KMAX, "hmp_gat_attention: k = %d (1 .. %d)", (int)k, GAT_ATT_KMAX);
+  HMP_CHECK_ARG(hmp_device_count() > 0, "hmp_gat_attention: no gfx950 device visible");
+  UnitTab u;
+  GatDyn dyn;
+  args.dropout_p = 0.f;  // the coefficients are exported before dropout
+  HMP_TRY(unit_setup(u, dyn, plan, args, nullptr, args.heads * align4(args.channels), d_a_src, lda_src, d_a_dst, lda_dst, d_edge_attr, d_v_edge));
+  GatInS& I = u.h.d[0].in[0];
+  I.smax = const_cast<float*>(d_smax); I.sden = const_cast<float*>(d_sden);
+  if (!d_alpha && !d_top_src && !d_top_w) return HMP_OK;
+  GatAttArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = 1; a.k = k;
+  a.r[0].alpha = d_alpha; a.r[0].top_src = reinterpret_cast<long long*>(d_top_src); a.r[0].top_w = d_top_w; a.r[0].ei = d_edge_index;
+  HMP_TRY(unit_upload(u));
+  HMP_TRY(gat_attention_launch(u.d, u.h, dyn, a, (hipStream_t)stream));
   HMP_HIP(hipStreamSynchronize((hipStream_t)stream));
   return HMP_OK;
 }

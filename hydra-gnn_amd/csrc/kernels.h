@@ -257,6 +257,12 @@ struct PlanBatch {
   int64_t row_start[2 * HMP_MAX_EDGE_TYPES + 1];  // rows of (job, dir): dir 0 = by dst, 1 = by src
   PlanJob j[HMP_MAX_EDGE_TYPES];
 };
+// the plan keeps edge s -> d iff both endpoints exist; every other edge is dropped from the lists and sets status bit 0.  For
+// readers of a plan that must know which edges it dropped (the attention export); the plan builds state the same condition in
+// their own loops (plan_hist_kernel, plan_small_part), whose code is left as it is
+__host__ __device__ inline bool plan_edge_ok(int64_t s, int64_t d, int n_src, int n_dst) {
+  return s >= 0 && s < n_src && d >= 0 && d < n_dst;
+}
 size_t plan_scratch_ints(int64_t E, int n_src, int n_dst);
 // carve scratch for job (all int32); zero_begin/zero_ints return the region to memset
 void plan_carve(PlanJob& job, int* scratch);
@@ -531,6 +537,27 @@ struct GatDyn {
 int gat_fwd_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st);
 int gat_bwd1_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st);
 int gat_bwd2_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, hipStream_t st);
+
+// Attention export (gat_attention_kernel): the coefficients the backward differentiates, alpha = expf(leaky(raw) - smax) / sden
+// from the softmax state of the last forward, written out per conv in the CALLER's edge order, and / or the k entries of every
+// destination row with the largest head-mean coefficient.  One launch serves the n requested convs of one layer; a request names
+// its conv by (destination entry, in-conv index) of the layer table.  Passed by value next to GatDyn.
+constexpr int GAT_ATT_KMAX = 8;
+struct GatAttReq {
+  int d, i;
+  float* alpha;         // [E + n_loop][H] (no head padding): row e < E = edge e of the batch's edge_index, row E + r = the appended
+                        // loop of row r; an explicit loop the conv removes and an edge the plan dropped hold 0.  null: skipped
+  long long* top_src;   // [n_dst][k] source node of the k largest head means, descending, equal means by ascending CSR position
+  float* top_w;         // [n_dst][k] those means; columns past the row's live entries hold -1 / 0.  Either may be null
+  const int64_t* ei;    // the [2][E] list the plan was built from: its out-of-range edges (PlanJob's rule) get their alpha rows
+                        // zeroed by sweep blocks.  null: the caller vouches that the plan dropped nothing
+};
+struct GatAttArgs {
+  int n, k;
+  int block_start[2 * HMP_MAX_EDGE_TYPES + 1];  // request q: row blocks from [2q], sweep blocks from [2q + 1] (filled by the launcher)
+  GatAttReq r[HMP_MAX_EDGE_TYPES];
+};
+int gat_attention_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, GatAttArgs& a, hipStream_t st);
 
 // Adam riding in the gradient un-pack (single-rank step of networks whose gradient terms read no parameters, i.e. SAGE):
 // the thread that produced gradient element i updates parameter i right away.  count = valid labels (device), step = t.

@@ -2297,6 +2297,51 @@ extern "C" int hmp_net_topk_heads(hmp_net* n, const hmp_batch* batch, const floa
   return linear_heads_topk_launch(a, k, d_labels, d_probs, st);
 }
 
+// ---- attention export: the eval-mode forward, then ONE launch that writes the coefficients of the requested convs of one GAT
+// layer from the softmax state the forward left (gat.hip: gat_attention_kernel).  Everything is checked before the forward.
+extern "C" int hmp_net_attention(hmp_net* n, const hmp_batch* batch, const float* d_params, int32_t layer,
+                                 float* const d_alpha[HMP_MAX_EDGE_TYPES], int32_t k, int64_t* const d_top_src[HMP_MAX_EDGE_TYPES],
+                                 float* const d_top_w[HMP_MAX_EDGE_TYPES], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params, "hmp_net_attention: null argument");
+  HMP_CHECK_ARG(n->bound, "hmp_net_attention: workspace not bound (call hmp_net_bind_workspace)");
+  HMP_CHECK_ARG(layer >= 0 && layer < n->L, "hmp_net_attention: layer %d out of range (the program has %d layers)", (int)layer, n->L);
+  const LayerLayout& Y = n->lay[layer];
+  HMP_CHECK_ARG(Y.kind == HMP_CONV_GAT, "hmp_net_attention: layer %d is not a GAT layer: it has no attention coefficients", (int)layer);
+  HMP_CHECK_ARG(k >= 1 && k <= GAT_ATT_KMAX, "hmp_net_attention: k = %d (1 .. %d)", (int)k, GAT_ATT_KMAX);
+  const hmp_layer_spec& Ls = n->spec.layers[layer];
+  GatAttArgs a;
+  memset(&a, 0, sizeof(a));
+  a.k = k;
+  for (int et = 0; et < HMP_MAX_EDGE_TYPES; ++et) {
+    float* al = d_alpha ? d_alpha[et] : nullptr;
+    int64_t* ts = d_top_src ? d_top_src[et] : nullptr;
+    float* tw = d_top_w ? d_top_w[et] : nullptr;
+    if (!al && !ts && !tw) continue;
+    int c = -1;
+    for (int i = 0; i < Ls.n_convs && c < 0; ++i)
+      if (Ls.convs[i].edge_type == et) c = i;
+    HMP_CHECK_ARG(et < n->ET && c >= 0, "hmp_net_attention: layer %d has no conv on edge type %d", (int)layer, et);
+    HMP_CHECK_ARG(Ls.convs[c].active != 0,
+                  "hmp_net_attention: the conv of layer %d on edge type %d is inactive (its output never reaches the readout: nothing is computed)",
+                  (int)layer, et);
+    GatAttReq& R = a.r[a.n];
+    R.d = -1;
+    for (int d = 0; d < Y.h_gat.n_dst; ++d)
+      for (int i = 0; i < Y.h_gat.d[d].n_in; ++i)
+        if (Y.h_gat.d[d].in[i].et == et) { R.d = d; R.i = i; }
+    HMP_CHECK_ARG(R.d >= 0, "hmp_net_attention: the conv of layer %d on edge type %d is not in the layer table", (int)layer, et);
+    R.alpha = al; R.top_src = reinterpret_cast<long long*>(ts); R.top_w = tw;
+    R.ei = batch->d_edge_index[et];
+    ++a.n;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, batch, d_params, st));
+  if (a.n == 0) return HMP_OK;
+  Scope sc(n, KC_GAT_FWD, st);
+  GatDyn dyn = make_gat_dyn(n, batch);
+  return gat_attention_launch(Y.d_gat, Y.h_gat, dyn, a, st);
+}
+
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,
                                  const hmp_train_args* args, void* stream) {
   HMP_CHECK_ARG(n && d_params && d_grads && d_m && d_v && args, "hmp_net_step_adam: null argument");

@@ -186,6 +186,7 @@ SIGNATURES = {
     "hmp_gat_fwd": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, Plan, GatArgs, _VP, _VP, _VP, _I32, _VP]),
     "hmp_gat_bwd": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, Plan, GatArgs, _VP, _VP, _VP, _VP, _VP,
                               _VP, _I32, _VP, _I32, _VP, _I32, _VP]),
+    "hmp_gat_attention": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _VP, Plan, GatArgs, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     "hmp_masked_ce": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_argmax_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
@@ -228,7 +229,8 @@ SIGNATURES = {
     "hmp_net_topk_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I32, _VP, _VP, _VP]),
     "hmp_net_topk2": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_topk_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
-    "hmp_net_hidden": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "hmp_net_attention": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_net_hidden":(C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),
     "hmp_graph_end": (C.c_int, [_VP, C.POINTER(_VP)]),

@@ -242,6 +242,15 @@ def compute_relative_pos(torch_data: HeteroData) -> None:
         torch_data[src, rel, dst].edge_attr = torch_data[dst].pos[ei[1]] - torch_data[src].pos[ei[0]]
 
 
+def attention_edge_index(edge_index: torch.Tensor, n_loop: int) -> torch.Tensor:
+    """The ``[2, E + n_loop]`` index the rows of an exported ``alpha`` (``model.attention``) correspond to: the input edges as they
+    are, then the self loops ``i -> i``, ``i < n_loop``, a same-type GAT conv appends (``n_loop = alpha.size(0) - E``).  Unlike
+    [PyG] ``return_attention_weights`` the input self loops such a conv replaces keep their rows (their coefficient is 0).  A
+    convenience built with torch ops; not on any hot path."""
+    loops = torch.arange(int(n_loop), dtype=edge_index.dtype, device=edge_index.device)
+    return torch.cat([edge_index, torch.stack([loops, loops])], dim=1)
+
+
 # ---------------------------------------------------------------------------------------------
 # collate: PyG Batch.from_data_list semantics (SURVEY Appendix B.3; reference caller
 # src/hydra_gnn/base_training_job.py:164-178)

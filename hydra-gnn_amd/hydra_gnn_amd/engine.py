@@ -777,6 +777,132 @@ class NativeNet:
             self._pred_done.synchronize()
         return self._pred_host[:rows[0]], self._pred_host[rows[0]:n]
 
+    # ---- attention export ([PyG] GATConv.forward(return_attention_weights=True)) -------------------------------------
+    def _gat_layer(self, layer: int, who: str) -> List[ConvDesc]:
+        """the convs of program layer ``layer`` after the checks that it exists and is a GAT layer"""
+        if isinstance(layer, bool) or not isinstance(layer, int) or not 0 <= layer < len(self.layers):
+            raise _lib.HydraMPError(f"{who}: layer {layer!r} out of range (the program has {len(self.layers)} layers)")
+        convs = self.layers[layer].convs
+        if not convs or convs[0].kind != CONV_GAT:
+            raise _lib.HydraMPError(f"{who}: no attention coefficients: layer {layer} is not a GAT layer")
+        return convs
+
+    def _gat_conv(self, layer: int, edge_type, who: str) -> ConvDesc:
+        """the live GAT conv of program layer ``layer`` on ``edge_type``, or the refusal that names what is wrong"""
+        for conv in self._gat_layer(layer, who):
+            if conv.edge_type == tuple(edge_type):
+                if not conv.active:
+                    raise _lib.HydraMPError(f"{who}: the conv on edge type {conv.edge_type} of layer {layer} is inactive: its output "
+                                            "never reaches the readout, so nothing is computed for it")
+                return conv
+        raise _lib.HydraMPError(f"{who}: layer {layer} has no conv on edge type {tuple(edge_type)!r}")
+
+    def attention_edge_types(self, layer: int) -> List[EdgeType]:
+        """edge types of the live GAT convs of program layer ``layer`` (what :meth:`attention` exports by default)"""
+        return [c.edge_type for c in self._gat_layer(layer, "attention") if c.active]
+
+    def _attention_batch(self, batch, who: str):
+        flat = self.flat_params(full_check=False)
+        if isinstance(batch, _BatchHolder):
+            h = batch
+            if h.stream is not None and h.stream.nat is not self:
+                raise _lib.HydraMPError(f"{who}: the batch comes from a stream created for another model")
+        else:
+            h = self.make_batch(batch)
+        return h, flat
+
+    def attention_rows(self, h: _BatchHolder, conv: ConvDesc) -> Tuple[int, int, int]:
+        """(E, n_loop, n_dst) of ``conv`` on the batch ``h``: alpha has ``E + n_loop`` rows, the top-k outputs ``n_dst``"""
+        ns, nd = (h.n_nodes[self.node_types.index(t)] for t in (conv.edge_type[0], conv.edge_type[2]))
+        n_loop = min(ns, nd) if conv.gat.get("self_loops", 0) else 0
+        return h.n_edges[self.edge_types.index(conv.edge_type)], n_loop, nd
+
+    def attention(self, batch, layer: int, edge_types=None, out=None) -> Dict[EdgeType, torch.Tensor]:
+        """Attention coefficients of program layer ``layer``, on the device: eval-mode native forward plus ONE launch
+        (``hmp_net_attention``).  ``batch`` is a data object or a descriptor from ``store.BatchStream.next``.
+
+        Returns ``{edge_type: alpha}`` for ``edge_types`` (default: every live conv of the layer), ``alpha`` float32
+        ``[E + n_loop, heads]``: row ``e < E`` belongs to column ``e`` of the batch's ``edge_index``, row ``E + i`` to the self loop
+        ``i -> i`` the conv appends (``n_loop = min(n_src, n_dst)`` for a conv with self loops, else 0); an input edge ``i -> i``
+        such a conv removes, and an edge dropped for an out-of-range endpoint, hold 0.  The values are the pre-dropout softmax
+        weights the backward differentiates.
+
+        ``out`` takes caller-owned buffers ``{edge_type: tensor}``: contiguous float32 on the model's device, ``heads`` columns,
+        at least the needed rows; the result is a view of their leading rows.  Nothing synchronises."""
+        ets = [tuple(e) for e in edge_types] if edge_types is not None else self.attention_edge_types(layer)
+        convs = [self._gat_conv(layer, e, "attention") for e in ets]
+        h, flat = self._attention_batch(batch, "attention")
+        dev = flat.device
+        slots = (C.c_void_p * _lib.MAX_EDGE_TYPES)()
+        res = {}
+        for conv in convs:
+            E, n_loop, _ = self.attention_rows(h, conv)
+            H = int(conv.gat.get("heads", 1))
+            buf = _attention_buffer(out.get(conv.edge_type) if out is not None else None, E + n_loop, H, torch.float32, dev,
+                                    f"out[{conv.edge_type}]")
+            slots[self.edge_types.index(conv.edge_type)] = buf.data_ptr()
+            res[conv.edge_type] = buf[:E + n_loop]
+        self._count("hmp_net_attention", h, dev, flat.data_ptr(), int(layer), slots, 1, None, None)
+        return res
+
+    def top_attended(self, batch, layer: int, edge_type, k: int, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The ``k`` most attended sources of every destination row of the conv on ``edge_type`` in program layer ``layer``, on the
+        device: eval-mode native forward plus ONE launch (``hmp_net_attention``).  ``1 <= k <= 8``.
+
+        Returns ``(src int64 [n_dst, k], weight float32 [n_dst, k])``: the entries with the largest head-mean coefficient (heads
+        added in ascending order in float32, divided by the head count), descending; equal means by ascending original edge id,
+        the appended self loop last.  ``src`` is the source node index (the row itself for the loop).  Removed and dropped edges
+        are no candidates; columns past a row's live entries hold ``-1`` / ``0``.
+
+        ``out`` takes caller-owned ``(src, weight)`` buffers: contiguous, on the model's device, ``k`` columns, at least ``n_dst``
+        rows; the result is a view of their leading rows.  Nothing synchronises.
+
+        ``edge_type`` may also be a LIST of edge types: the same single launch serves them all and the result is
+        ``{edge_type: (src, weight)}`` (``out`` then a dict of pairs)."""
+        k = _check_k(k)
+        many = isinstance(edge_type, list)
+        convs = [self._gat_conv(layer, e, "top_attended") for e in (edge_type if many else [edge_type])]
+        h, flat = self._attention_batch(batch, "top_attended")
+        dev = flat.device
+        s_slots, w_slots = (C.c_void_p * _lib.MAX_EDGE_TYPES)(), (C.c_void_p * _lib.MAX_EDGE_TYPES)()
+        res = {}
+        for conv in convs:
+            o = (out.get(conv.edge_type) if out is not None else None) if many else out
+            if o is not None and (not isinstance(o, (tuple, list)) or len(o) != 2):
+                raise _lib.HydraMPError("top_attended: out must be a (src, weight) pair of tensors")
+            nd = self.attention_rows(h, conv)[2]
+            src = _attention_buffer(o[0] if o is not None else None, nd, k, torch.int64, dev, "out[0]")
+            wgt = _attention_buffer(o[1] if o is not None else None, nd, k, torch.float32, dev, "out[1]")
+            i = self.edge_types.index(conv.edge_type)
+            s_slots[i], w_slots[i] = src.data_ptr(), wgt.data_ptr()
+            res[conv.edge_type] = (src[:nd], wgt[:nd])
+        self._count("hmp_net_attention", h, dev, flat.data_ptr(), int(layer), None, k, s_slots, w_slots)
+        return res if many else res[convs[0].edge_type]
+
+    def explain(self, batch, layer: int, edge_type, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`top_attended` on the host: sources and weights land in ONE device buffer (8 bytes per source, then 4 per weight)
+        and cross in one D2H through one pinned buffer and one event, as :meth:`predict_confidence` moves its labels.  Returns host
+        ``(src int64 [n_dst, k], weight float32 [n_dst, k])`` as views of that buffer (valid until the next call)."""
+        k = _check_k(k)
+        conv = self._gat_conv(layer, edge_type, "explain")
+        h, flat = self._attention_batch(batch, "explain")
+        dev = flat.device
+        nd = self.attention_rows(h, conv)[2]
+        n = nd * k
+        with torch.cuda.device(dev):
+            if getattr(self, "_att_dev", None) is None or self._att_dev.numel() < 12 * n or self._att_dev.device != dev:
+                cap = max(4096, 24 * n)
+                self._att_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
+                self._att_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                self._att_done = torch.cuda.Event()
+            split = lambda buf: (buf[:8 * n].view(torch.int64).view(nd, k), buf[8 * n:12 * n].view(torch.float32).view(nd, k))  # noqa: E731
+            self.top_attended(h, layer, conv.edge_type, k, out=split(self._att_dev) if n > 0 else None)
+            if n > 0:
+                self._att_host[:12 * n].copy_(self._att_dev[:12 * n], non_blocking=True)
+            self._att_done.record()
+            self._att_done.synchronize()
+        return split(self._att_host)
+
     def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
         """the count entries' common block: ``entry(handle, batch, *args, stream)`` (eval-mode forward + count on the device),
         which overwrites the activations of any earlier forward()"""
@@ -886,6 +1012,17 @@ def _topk_buffers(out, rows: Sequence[int], k: int, pair: bool, dev) -> List[Tup
                 raise _lib.HydraMPError(f"out must be contiguous (int64, float32) tensors [rows >= {n}, {k}] on {dev}, got "
                                         f"{tuple(t.shape)} {t.dtype} on {t.device}")
     return [(lb, pb) for lb, pb in outs]
+
+
+def _attention_buffer(out, rows: int, cols: int, dtype, dev, what: str) -> torch.Tensor:
+    """one ``[rows, cols]`` output of the attention export: a fresh tensor, or the caller's after the checks of ``_topk_buffers``"""
+    if out is None:
+        return torch.empty((max(rows, 1), cols), dtype=dtype, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != dtype or not out.is_contiguous() or out.device != dev or out.dim() != 2
+            or out.size(1) != cols or out.size(0) < rows):
+        got = f"{tuple(out.shape)} {out.dtype} on {out.device}" if isinstance(out, torch.Tensor) else repr(type(out))
+        raise _lib.HydraMPError(f"{what} must be a contiguous {dtype} tensor [rows >= {rows}, {cols}] on {dev}, got {got}")
+    return out
 
 
 def _check_counts4(counts: torch.Tensor, dev) -> None:

@@ -106,6 +106,55 @@ class _NativeModule(nn.Module):
         _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
         return self.native().predict_confidence(data)
 
+    # ---- attention export ([PyG] GATConv(..., return_attention_weights=True)) ----------------------------------------
+    def _attention_layer(self, layer, who: str) -> int:
+        """program layer of the model's conv layer ``layer`` (an int counting ``self.convs``, negative from the end) or of
+        ``"pre_mp"``, the H-tree models' initialisation layer where it is a GAT layer of the native program"""
+        if self.conv_block[:3] != "GAT":
+            raise _lib.HydraMPError(f"{who}: no attention coefficients: conv_block {self.conv_block} has no attention (GAT and "
+                                    "GAT_edge models export them)")
+        first = len(self.native().layers) - self.num_layers  # 1 with pre_mp in front
+        if layer == "pre_mp":
+            if first == 0:
+                raise _lib.HydraMPError(f"{who}: the model has no pre_mp layer (disable_initialization)")
+            return 0
+        if isinstance(layer, bool) or not isinstance(layer, int) or not -self.num_layers <= layer < self.num_layers:
+            raise _lib.HydraMPError(f"{who}: layer must be 'pre_mp' or an int in [{-self.num_layers}, {self.num_layers}), got {layer!r}")
+        return first + layer % self.num_layers
+
+    def _attention_input(self, data):
+        from ..engine import _BatchHolder
+
+        view = getattr(self, "_view", None)
+        return data if view is None or isinstance(data, _BatchHolder) else view(data)
+
+    def attention(self, data, layer=-1):
+        """Attention coefficients of conv layer ``layer`` (``-1``: the last; ``"pre_mp"``: the H-tree initialisation layer), left on
+        the device (nothing synchronises): eval-mode native forward plus one launch (:meth:`NativeNet.attention`).  Heterogeneous
+        models return ``{edge_type: alpha}`` for every conv whose output reaches the model's output, homogeneous models the one
+        tensor.  ``alpha`` is float32 ``[E + n_loop, heads]`` in the order of ``hydra_gnn_amd.data.attention_edge_index(edge_index,
+        n_loop)``: the input edges, then the self loops a same-type conv appends; an input self loop such a conv removes holds 0.
+        ``data`` is a batch or a descriptor from ``store.BatchStream.next``."""
+        l = self._attention_layer(layer, "attention")
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        res = self.native().attention(self._attention_input(data), l)
+        return next(iter(res.values())) if len(self.native().node_types) == 1 else res  # one node type: one conv per layer
+
+    def top_attended(self, data, edge_type=None, k=3, layer=-1):
+        """``(src int64 [n_dst, k], weight float32 [n_dst, k])`` on the device: per destination row of the conv on ``edge_type``
+        in conv layer ``layer`` the ``k`` sources with the largest head-mean attention, descending (:meth:`NativeNet.top_attended`:
+        eval-mode native forward plus one launch, nothing synchronises; ``1 <= k <= 8``; ``-1`` / ``0`` past a row's entries).
+        Heterogeneous models: ``edge_type=None`` returns ``{edge_type: (src, weight)}`` for every conv :meth:`attention` exports;
+        homogeneous models have one edge type per layer and return its pair."""
+        l = self._attention_layer(layer, "top_attended")
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        net = self.native()
+        homog = len(net.node_types) == 1
+        if edge_type is None:
+            ets = net.attention_edge_types(l)
+            return net.top_attended(self._attention_input(data), l, ets[0] if homog else ets, k)
+        return net.top_attended(self._attention_input(data), l, tuple(edge_type), k)
+
     def loss(self, pred, label, mask=None):
         return cross_entropy_loss(pred, label, mask)
 
@@ -269,6 +318,17 @@ class HeterogeneousNetwork(_HeteroTwoHead):
         tail = ((ACT_ELU if self.conv_block[:3] == "GAT" else ACT_RELU), float(self.dropout)) if two else None
         return NativeNet(node_types, self.input_dim_dict, EDGE_TYPES, _hetero_layers(self, node_types), readout="rooms",
                          aux_readout="objects" if two else None, tail=tail)
+
+    def explain_rooms(self, data, k=3):
+        """Which objects a room's label rests on, on the host: for every room the ``k`` most attended objects of the last layer's
+        ``objects_to_rooms`` conv and their weights -- :meth:`top_attended` on that conv through one pinned buffer and one
+        device-to-host copy, as :meth:`predict_with_confidence` moves its labels.  Returns ``(objects int64 [rooms, k], weight
+        float32 [rooms, k])``, ``-1`` / ``0`` past a room's objects (views of that buffer: valid until the next call).  GAT /
+        GAT_edge models only."""
+        l = self._attention_layer(-1, "explain_rooms")
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        et = next(e for e in EDGE_TYPES if e[0] == "objects" and e[2] == "rooms")
+        return self.native().explain(data, l, et, k)
 
     def forward(self, data):
         out = self._run(data)

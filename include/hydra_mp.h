@@ -57,7 +57,9 @@ extern "C" {
  *    hmp_frame_build_flags (HMP_FRAME_NO_ROOM_EDGES: the reference's remove_room_edges_in_dsg in the host stage), item kinds
  *    HMP_SD_COMPACT / HMP_SD_ROWS_ZERO of hmp_store_derive's table and hmp_store_count_kept (the edge-type and clique ablations on a
  *    resident store): new entries and new kinds behind the old ones; hmp_collator_create accepts a null d_src for an item whose
- *    slot is empty in every graph (it was refused before) */
+ *    slot is empty in every graph (it was refused before);
+ *    hmp_gat_attention / hmp_net_attention (per-edge attention coefficients and the top-k sources per row, from the softmax state
+ *    of a forward): new entries, no struct was added or changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -214,6 +216,23 @@ int hmp_gat_bwd(const float* d_gout, int32_t ldg, const float* d_h_src, int32_t 
                 hmp_gat_args args, const float* d_smax, const float* d_sden, float* d_alpha_drop, float* d_dlogit,
                 float* d_dlogit_orig, float* d_g_h_src, int32_t ldgh, float* d_g_a_src, int32_t ldgas, float* d_g_a_dst,
                 int32_t ldgad, void* stream);
+/* Attention export: what [PyG] GATConv.forward(return_attention_weights=True) hands out, from the softmax state d_smax / d_sden
+ * [n_dst, 8] (16-byte aligned) a preceding hmp_gat_fwd with the same inputs left.  One launch; synchronises like the two entries
+ * above.  args.dropout_p plays no part: the coefficients are the ones before dropout.  (ABI-4-compatible addition.)
+ *   d_alpha [E + n_loop, H] float, exactly H columns: row e < E belongs to column e of the edge_index the plan was built from, row
+ *   E + i to the appended loop i -> i (n_loop = self_loops ? min(n_src, n_dst) : 0).  Value: expf(e_k - smax[i, h]) / sden[i, h],
+ *   the expression the backward differentiates.  An input edge i -> i the conv removes (self_loops != 0) holds 0, and so does an
+ *   edge the plan dropped (endpoint out of range, status bit 0) when d_edge_index -- that same int64 [2][E] list -- is given; with
+ *   d_edge_index NULL the caller vouches that nothing was dropped (such rows would be left unwritten).
+ *   d_top_src [n_dst, k] int64 / d_top_w [n_dst, k] float, 1 <= k <= 8: the k entries of the row with the largest head-mean
+ *   coefficient (a_0 + a_1 + ... + a_{H-1}) / H, computed in float32 with the heads added in ascending order; descending, equal means
+ *   by ascending CSR position (the plan is stable: ascending original edge id, the appended loop last).  d_top_src holds the source
+ *   node (the row itself for the loop); removed and dropped entries are no candidates; columns past the row's live entries hold
+ *   -1 / 0.  Every element of both arrays is written.
+ *   Any of the three outputs may be NULL (skipped); what one output holds does not depend on which others were requested. */
+int hmp_gat_attention(const float* d_a_src, int32_t lda_src, const float* d_a_dst, int32_t lda_dst, const float* d_edge_attr,
+                      const float* d_v_edge, const int64_t* d_edge_index, hmp_plan plan, hmp_gat_args args, const float* d_smax,
+                      const float* d_sden, float* d_alpha, int32_t k, int64_t* d_top_src, float* d_top_w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 5. loss + optimiser
@@ -606,6 +625,18 @@ int hmp_net_topk2(hmp_net* net, const hmp_batch* batch, const float* d_params, i
  * elsewhere.  A head whose two pointers are both NULL is skipped. */
 int hmp_net_topk_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], int32_t k,
                        int64_t* const d_labels[2], float* const d_probs[2], void* stream);
+/* Attention export of a bound net (any net kind with a GAT layer): the eval-mode forward of `batch` (the predict entries' forward:
+ * plan_valid, the overwritten activations, no allocation or synchronisation), then ONE launch -- recorded under profile class 9,
+ * gat_fwd -- that writes, for program layer `layer` (0 .. n_layers - 1) and every edge type e with a non-NULL slot, the outputs of
+ * hmp_gat_attention for the layer's conv on e: d_alpha[e] [n_edges[e] + n_loop, heads], d_top_src[e] / d_top_w[e]
+ * [n_nodes[dst], k], in the order of batch->d_edge_index[e] (whose dropped edges' rows hold 0).  Each of the three arrays of
+ * pointers may itself be NULL (= all slots NULL); NULL slots are skipped.  Refused with HMP_E_ARG before anything runs: a layer
+ * out of range, a layer that is not GAT, k outside 1 .. 8, a slot on an edge type the layer has no conv for, and a slot whose conv
+ * is inactive (hmp_conv_spec::active == 0: its output never reaches the readout, so nothing was computed).
+ * (ABI-4-compatible addition.) */
+int hmp_net_attention(hmp_net* net, const hmp_batch* batch, const float* d_params, int32_t layer,
+                      float* const d_alpha[HMP_MAX_EDGE_TYPES], int32_t k, int64_t* const d_top_src[HMP_MAX_EDGE_TYPES],
+                      float* const d_top_w[HMP_MAX_EDGE_TYPES], void* stream);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
