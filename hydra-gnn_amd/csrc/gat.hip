@@ -29,6 +29,7 @@
 #include <climits>
 
 #include "tail_fns.h"
+#include "topk_select.h"
 
 namespace hmp {
 
@@ -704,10 +705,9 @@ __global__ __launch_bounds__(256) void gat_bwd2_kernel(const GatLayerS* __restri
 // coefficients as one row of alpha at eid -- scattered by nature, 16 bytes per store when H is 4 or 8.  The row's softmax state
 // (32-byte rows of smax / sden) is two 16-byte loads, the same address in all 16 lanes.
 //
-// Top-k: every lane keeps the GAT_ATT_KMAX best (mean, slot) of its own slots, sorted (a strict > on insertion keeps the earlier
-// slot ahead among equal means: a lane meets its slots in ascending order); k rounds of a 16-lane butterfly then pick the group's
-// best head (larger mean, then smaller slot -- slots are unique, so every lane agrees) and its owner pops it.  Lane j keeps
-// result j and stores column j.
+// Top-k (topk_select.h, shared with the saliency export): every lane keeps the GAT_ATT_KMAX best (mean, slot) of its own slots,
+// sorted; k rounds of a 16-lane butterfly then pick the group's best head (larger mean, then smaller slot -- slots are unique, so
+// every lane agrees) and its owner pops it.  Lane j keeps result j and stores column j.
 //
 // Blocks past a request's row blocks are its sweep blocks: they walk the caller's edge list and zero the alpha rows of the edges
 // the plan dropped (no row group owns those).
@@ -762,8 +762,7 @@ __global__ __launch_bounds__(256) void gat_attention_kernel(const GatLayerS* __r
 
   float tv[GAT_ATT_KMAX];  // this lane's best means, descending; -1 marks an empty place (a mean is >= 0)
   int tp[GAT_ATT_KMAX];    // their slots
-#pragma unroll
-  for (int i = 0; i < GAT_ATT_KMAX; ++i) { tv[i] = -1.f; tp[i] = INT_MAX; }
+  topsel_init(tv, tp);
 
   for (int k = b + gl; k < kend; k += ATT_GS) {
     int j, eid;
@@ -798,38 +797,14 @@ __global__ __launch_bounds__(256) void gat_attention_kernel(const GatLayerS* __r
       for (int h = 1; h < HM; ++h)
         if (h < H) v += al[h];
       v = v / (float)H;
-      int p = k;
-#pragma unroll
-      for (int i = 0; i < GAT_ATT_KMAX; ++i) {
-        if (v > tv[i]) {
-          const float fv = tv[i];
-          const int fp = tp[i];
-          tv[i] = v; tp[i] = p;
-          v = fv; p = fp;
-        }
-      }
+      topsel_insert(tv, tp, v, k);
     }
   }
   if (!want_top) return;
 
-  float rv = -1.f;
-  int rp = INT_MAX;
-  for (int r = 0; r < a.k; ++r) {
-    float v = tv[0];
-    int p = tp[0];
-#pragma unroll
-    for (int o = ATT_GS / 2; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v, o);
-      const int op = __shfl_xor(p, o);
-      if (ov > v || (ov == v && op < p)) { v = ov; p = op; }
-    }
-    if (tp[0] == p) {  // the owner pops (groups with nothing left all hold the empty mark: popping it changes nothing)
-#pragma unroll
-      for (int i = 0; i + 1 < GAT_ATT_KMAX; ++i) { tv[i] = tv[i + 1]; tp[i] = tp[i + 1]; }
-      tv[GAT_ATT_KMAX - 1] = -1.f; tp[GAT_ATT_KMAX - 1] = INT_MAX;
-    }
-    if (gl == r) { rv = v; rp = p; }
-  }
+  float rv;
+  int rp;
+  topsel_rounds<ATT_GS>(tv, tp, a.k, gl, rv, rp);
   if (gl < a.k) {
     const bool have = rp != INT_MAX;
     const int src = !have ? -1 : (rp >= e ? row : glob(I.col)[rp]);

@@ -559,6 +559,33 @@ struct GatAttArgs {
 };
 int gat_attention_launch(const GatLayerS* d_tab, const GatLayerS& h_tab, GatDyn& dyn, GatAttArgs& a, hipStream_t st);
 
+// Gradient saliency (saliency.hip).  A row selection names the rows a launch serves: all, a byte per row, or -- ORDINAL -- row
+// ptr[g] + p of every graph g of the batch with more than p rows (int64 ptr[n_graphs + 1], [PyG] Batch.ptr of the row's node type):
+// rows of different graphs do not interact, so one pass per ordinal explains every graph's p-th row exactly.
+constexpr int SAL_SEL_ALL = 0, SAL_SEL_MASK = 1, SAL_SEL_ORDINAL = 2;
+constexpr int SAL_WRT_LOGIT = 0, SAL_WRT_LOGPROB = 1;
+constexpr int SAL_MAX_GROUPS = 4;
+constexpr int SAL_TOPK_MAX = 8;  // = GAT_ATT_KMAX: top_salient has top_attended's conventions
+struct SalSel {
+  int mode;
+  const uint8_t* mask;
+  int p;
+  const int64_t* ptr;
+  int n_graphs;
+};
+// gout[n_rows, ldg] (every element written, padding columns and unselected rows 0): onehot(c) or onehot(c) - softmax(z) per selected
+// row, c = target[row] where given and in [0, n_classes), else the first-maximum argmax (predict_rows_launch's prediction)
+// act != HMP_ACT_NONE: z is a pre-activation, the rule runs on y = act(z) and the row is multiplied by d y / d z (tail_dydz)
+int saliency_seed_launch(const float* z, int ld, int n_rows, int n_classes, const int64_t* target, const SalSel& sel, int wrt, float* gout,
+                         int ldg, hipStream_t st, int act = HMP_ACT_NONE);
+// per row: gxi = sum_f g*x, gnorm = sqrt(sum_f g^2), groups[row, i] = sum of g*x over columns [lo[i], hi[i]) clipped to F; any output
+// may be null.  lo / hi are HOST arrays
+int saliency_scores_launch(const float* g, int ldg, const float* x, int ldx, int n_rows, int F, int n_groups, const int* lo, const int* hi,
+                           float* gxi, float* gnorm, float* groups, hipStream_t st);
+// per selected destination row of plan P: the k sources with the largest |score|, descending, equal magnitudes by ascending source,
+// every source once; top_src / top_score [n_dst, k], -1 / 0 past the row's sources; unselected rows are left untouched
+int saliency_topk_launch(const hmp_plan& P, const float* score, int k, const SalSel& sel, int64_t* top_src, float* top_score, hipStream_t st);
+
 // Adam riding in the gradient un-pack (single-rank step of networks whose gradient terms read no parameters, i.e. SAGE):
 // the thread that produced gradient element i updates parameter i right away.  count = valid labels (device), step = t.
 struct AdamFuse {

@@ -1271,8 +1271,10 @@ const float* out_ptr(const hmp_net* n) {
 }
 
 // ---- backward ------------------------------------------------------------------------------------------
+// skip_w (the input-gradient entry): the weight-gradient problems, their launch and the gradient un-pack are left out -- only the
+// chain down to d_gx runs, d_grads is not touched and may be null.  Every other caller's launches are what they were.
 int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, const float* d_params, float* const* d_gx,
-                  hipStream_t st, const float* d_gaux = nullptr, int ld_gaux = 0) {
+                  hipStream_t st, const float* d_gaux = nullptr, int ld_gaux = 0, bool skip_w = false) {
   HMP_CHECK_ARG(n->have_fwd, "net: backward without a forward");
   if (const int at = n->spec.aux_readout_type; at >= 0) {
     // second readout: stage its gradient in G[L][aux] (zero where the caller passed none, and in the padding columns)
@@ -1310,6 +1312,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
   bool g16[HMP_MAX_LAYERS + 2];  // g16[l]: the input gradients G[l][*] were stored as bf16 by layer l's input-gradient GEMM
   for (int i = 0; i < HMP_MAX_LAYERS + 2; ++i) g16[i] = false;
   bool dz16 = false;  // this layer's dZ is written as bf16 by the transposed aggregation (read by both backward GEMMs)
+  bool pass_gx[HMP_MAX_NODE_TYPES] = {false};  // d_gx[t] already holds layer 1's share (passthrough types)
   for (int l = n->L - 1; l >= 0; --l) {
     const hmp_layer_spec& Ls = S.layers[l];
     LayerLayout& Y = n->lay[l];
@@ -1420,6 +1423,29 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       }
     }
     const bool need_dx = !dx_fused && ((l > 0) || (d_gx != nullptr));
+    // passthrough types (pre_mp): layer 1 reads their INPUT rows, so its share of d x goes to d_gx first -- layer 0 adds its own
+    // on top (GemmProblem::Cadd below).  Only with d_gx: no other caller wants a gradient there (G[1][t] is null)
+    if (l == 1 && d_gx) {
+      std::vector<GemmProblem> ps;
+      for (int s = 0; s < n->T; ++s) {
+        if (!n->pass0[s] || !d_gx[s] || Y.ncols[s] == 0 || b->n_nodes[s] == 0) continue;
+        GemmProblem p;
+        memset(&p, 0, sizeof(p));
+        p.A = n->dZ[l][s]; p.lda = Y.ncols[s]; p.trans_a = 0;
+        p.a_bf16 = dz16 ? 1 : 0;
+        p.B = n->d_packed + Y.wp_off[s]; p.ldb = Y.ldw[s]; p.trans_b = 0;
+        p.C = d_gx[s]; p.ldc = b->ldx[s];
+        p.M = b->n_nodes[s]; p.N = n->dim[l][s]; p.K = Y.ncols[s];
+        p.n_real = p.N;
+        p.epi = EPI_NONE;
+        ps.push_back(p);
+        pass_gx[s] = true;
+      }
+      if (!ps.empty()) {
+        Scope sp(n, KC_GEMM_BWD, st);
+        HMP_TRY(gemm_many(n, ps, false, st, nullptr));
+      }
+    }
     // aggregate-first convs: dM = dZ_block * W_l (destination-sized), ahead of the launch whose epilogue scatters it
     auto dz_at = [&](int t, int col) -> const float* {
       return dz16 ? reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(n->dZ[l][t]) + col) : n->dZ[l][t] + col;
@@ -1485,6 +1511,8 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           p.drop_on = (n->training && Lp.dropout > 0.f) ? 1 : 0;
           if (p.drop_on) p.drop = make_drop(n, Lp.dropout, (uint32_t)((l - 1) * HMP_MAX_NODE_TYPES + s));
           if (p.act == HMP_ACT_NONE && !p.drop_on) p.epi = EPI_NONE;
+        } else if (pass_gx[s]) {
+          p.Cadd = dst; p.ldadd = p.ldc;  // in place: a tile starts its sums from the elements it stores
         }
         ps.push_back(p);
         ps_type.push_back(s);
@@ -1545,7 +1573,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
                                        drop_on ? 1.f / (1.f - Lp->dropout) : 1.f, dst, l > 0 ? n->ld[l][s] : b->ldx[s], gb ? 1 : 0, st));
       }
     }
-    {  // weight + bias gradient: dWp = dZ^T * [H | 1], split over node chunks (+ GAT: bias column sums, d V_edge), launched after the loop
+    if (!skip_w) {  // weight + bias gradient: dWp = dZ^T * [H | 1], split over node chunks (+ GAT: bias column sums, d V_edge), launched after the loop
       auto add = [&](int sid, const GemmProblem& p) {
         n->dyn.slab_stride[sid] = (int)p.slab_stride;
         wids.push_back(sid);
@@ -1613,6 +1641,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
       }
     }
   }
+  if (skip_w) return HMP_OK;
   {  // the weight gradients of all layers: one launch with ~1k workgroups instead of L launches
     Scope sc(n, KC_GEMM_BWD, st);
     std::vector<int> ks;
@@ -1792,6 +1821,14 @@ extern "C" int hmp_net_hidden(hmp_net* n, int32_t layer, int32_t node_type, cons
   *n_rows = n->batch.n_nodes[node_type];
   *width = n->dim[layer][node_type];
   *is_bf16 = n->h16[layer][node_type] ? 1 : 0;
+  return HMP_OK;
+}
+
+extern "C" int hmp_net_plan(hmp_net* n, int32_t edge_type, hmp_plan* out) {
+  HMP_CHECK_ARG(n && out, "hmp_net_plan: null argument");
+  HMP_CHECK_ARG(n->have_fwd && n->plan_ok, "hmp_net_plan: needs a forward");
+  HMP_CHECK_ARG(edge_type >= 0 && edge_type < n->ET, "hmp_net_plan: edge type %d out of range (the net has %d)", (int)edge_type, n->ET);
+  *out = n->plan[edge_type];
   return HMP_OK;
 }
 
@@ -2340,6 +2377,57 @@ extern "C" int hmp_net_attention(hmp_net* n, const hmp_batch* batch, const float
   Scope sc(n, KC_GAT_FWD, st);
   GatDyn dyn = make_gat_dyn(n, batch);
   return gat_attention_launch(Y.d_gat, Y.h_gat, dyn, a, st);
+}
+
+// ---- input gradients: the eval-mode forward, ONE launch that writes the output gradient selecting what is explained
+// (saliency.hip: saliency_seed_kernel) into the workspace, then the backward chain down to d loss / d x[t] without the weight
+// gradients.  Everything is checked before the forward.
+extern "C" int hmp_net_input_gradient(hmp_net* n, const hmp_batch* batch, const float* d_params, int32_t head, const int64_t* d_target,
+                                      int32_t sel_mode, const uint8_t* d_mask, int32_t ordinal, const int64_t* d_graph_ptr,
+                                      int32_t n_graphs, int32_t wrt, float* const d_gx[HMP_MAX_NODE_TYPES], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_gx, "hmp_net_input_gradient: null argument");
+  HMP_CHECK_ARG(n->bound, "hmp_net_input_gradient: workspace not bound (call hmp_net_bind_workspace)");
+  HMP_CHECK_ARG(!n->compute_bf16, "hmp_net_input_gradient: bf16 compute mode is not supported (input gradients are computed in fp32)");
+  HMP_CHECK_ARG(!n->has_heads, "hmp_net_input_gradient: nets with learned linear heads are not supported (their outputs are not the "
+                               "program's: the homogeneous two-headed task)");
+  const hmp_net_spec& S = n->spec;
+  const int at = S.aux_readout_type;
+  HMP_CHECK_ARG(head == 0 || (head == 1 && at >= 0), "hmp_net_input_gradient: head %d (0: the readout%s)", (int)head,
+                at >= 0 ? ", 1: the second output" : "; the net has one output");
+  HMP_CHECK_ARG(!n->has_pools, "hmp_net_input_gradient: two-headed nets with pooled heads are not supported");
+  HMP_CHECK_ARG(wrt == SAL_WRT_LOGIT || wrt == SAL_WRT_LOGPROB, "hmp_net_input_gradient: wrt = %d (0 logit, 1 log-probability)", (int)wrt);
+  HMP_CHECK_ARG(sel_mode == SAL_SEL_ALL || sel_mode == SAL_SEL_MASK || sel_mode == SAL_SEL_ORDINAL,
+                "hmp_net_input_gradient: selection mode %d (0 all, 1 mask, 2 ordinal)", (int)sel_mode);
+  HMP_CHECK_ARG(sel_mode != SAL_SEL_MASK || d_mask || (head == 0 ? batch->n_out : batch->n_nodes[at]) == 0,
+                "hmp_net_input_gradient: the mask selection needs a byte per output row");
+  HMP_CHECK_ARG(sel_mode != SAL_SEL_ORDINAL || (d_graph_ptr && n_graphs >= 0 && ordinal >= 0),
+                "hmp_net_input_gradient: the ordinal selection needs graph_ptr, n_graphs >= 0 and ordinal >= 0");
+  HMP_CHECK_ARG(at < 0 || (S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU), "hmp_net_input_gradient: spec tail_act %d", S.tail_act);
+  for (int t = 0; t < n->T; ++t)
+    HMP_CHECK_ARG(!(n->pass0[t] && n->any_agg_first), "hmp_net_input_gradient: passthrough node types next to aggregate-first convs are not supported");
+  for (int t = 0; t < n->T; ++t)
+    HMP_CHECK_ARG(!d_gx[t] || (batch->d_x[t] && batch->ldx[t] >= n->dim[0][t]), "hmp_net_input_gradient: d_gx[%d] for a node type without input rows", t);
+  hipStream_t st = (hipStream_t)stream;
+  StepGuard guard(n);
+  HMP_TRY(forward_impl(n, batch, d_params, st));
+  SalSel sel;
+  sel.mode = sel_mode; sel.mask = d_mask; sel.p = ordinal; sel.ptr = d_graph_ptr; sel.n_graphs = n_graphs;
+  // two-headed nets: the model's outputs are act(final state) (hmp_net_spec::tail_act), so the seed chains through it
+  const int act = at >= 0 ? S.tail_act : HMP_ACT_NONE;
+  const float* gaux = nullptr;
+  int ld_gaux = 0;
+  {
+    Scope sc(n, KC_LOSS, st);
+    if (head == 0) {
+      HMP_TRY(saliency_seed_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_target, sel, wrt, n->d_gout, n->out_ld, st, act));
+    } else {  // the second output's gradient goes where the loss stages put it; the readout's is a zero block
+      if (batch->n_out > 0) HMP_HIP(hipMemsetAsync(n->d_gout, 0, (size_t)batch->n_out * n->out_ld * 4, st));
+      HMP_TRY(saliency_seed_launch(n->H[n->L][at], n->ld[n->L][at], batch->n_nodes[at], n->dim[n->L][at], d_target, sel, wrt,
+                                   n->G[n->L][at], n->ld[n->L][at], st, act));
+      n->call.aux_g_ready = true;
+    }
+  }
+  return backward_impl(n, n->d_gout, n->out_ld, nullptr, d_params, d_gx, st, gaux, ld_gaux, true);
 }
 
 extern "C" int hmp_net_step_adam(hmp_net* n, float* d_params, const float* d_grads, float* d_m, float* d_v,

@@ -187,6 +187,9 @@ SIGNATURES = {
     "hmp_gat_bwd": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _VP, _VP, Plan, GatArgs, _VP, _VP, _VP, _VP, _VP,
                               _VP, _I32, _VP, _I32, _VP, _I32, _VP]),
     "hmp_gat_attention": (C.c_int, [_VP, _I32, _VP, _I32, _VP, _VP, _VP, Plan, GatArgs, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "hmp_saliency_seed": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP]),
+    "hmp_saliency_scores": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), _VP, _VP, _VP, _VP]),
+    "hmp_saliency_topk": (C.c_int, [Plan, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP]),
     "hmp_masked_ce": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_argmax_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
@@ -230,6 +233,8 @@ SIGNATURES = {
     "hmp_net_topk2": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_topk_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_attention": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_net_input_gradient": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _I32, C.POINTER(_VP), _VP]),
+    "hmp_net_plan": (C.c_int, [_VP, _I32, C.POINTER(Plan)]),
     "hmp_net_hidden":(C.c_int, [_VP, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
     "hmp_net_read_state": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_graph_begin": (C.c_int, [_VP]),

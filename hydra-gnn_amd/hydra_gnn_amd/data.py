@@ -181,7 +181,7 @@ class HeteroData:
         out = type(self)()
         out._nodes = {k: s._map(lambda t: t.to(device)) for k, s in self._nodes.items()}
         out._edges = {k: s._map(lambda t: t.to(device)) for k, s in self._edges.items()}
-        for name in ("num_graphs", "max_graph_nodes"):
+        for name in ("num_graphs", "max_graph_nodes", "max_graph_rows"):
             if hasattr(self, name):
                 setattr(out, name, getattr(self, name))
         return out
@@ -262,6 +262,7 @@ def collate(graphs: Sequence[HeteroData]) -> HeteroData:
     node_types = graphs[0].node_types
     offsets: Dict[str, List[int]] = {}
     max_nodes = 0
+    max_rows: Dict[str, int] = {}
     for nt in node_types:
         counts = [g[nt].num_nodes for g in graphs]
         off = [0]
@@ -278,6 +279,7 @@ def collate(graphs: Sequence[HeteroData]) -> HeteroData:
         )
         out[nt].ptr = torch.tensor(off, dtype=torch.int64)
         max_nodes = max(max_nodes, max(counts))
+        max_rows[nt] = int(max(counts))
     for et in graphs[0].edge_types:
         src, _, dst = et
         parts = []
@@ -297,6 +299,8 @@ def collate(graphs: Sequence[HeteroData]) -> HeteroData:
             out[et].edge_attr = torch.cat([g[et].edge_attr for g in graphs], dim=0)
     # host knowledge of the collation: lets the engine run the per-graph phases of a training step as one launch (hmp_batch)
     out.max_graph_nodes = int(max_nodes)
+    # ... per node type: the pass count of exact per-row explanations (one pass per row ordinal of a graph)
+    out.max_graph_rows = max_rows
     return out
 
 

@@ -52,6 +52,22 @@ def _require_cuda(t: torch.Tensor, what: str) -> None:
         )
 
 
+SEL_ALL, SEL_MASK, SEL_ORDINAL = 0, 1, 2  # include/hydra_mp.h: HMP_SEL_*
+WRT_CODES = {"logit": 0, "logprob": 1}  # HMP_WRT_*
+SAL_MAX_GROUPS = 4  # csrc/kernels.h
+DEFAULT_GROUPS = ((0, 3), (3, 6), (6, None))  # position, box size, word2vec block of the 306-d object features
+
+
+class _PtrView:
+    """an int64 vector that lives inside a buffer someone else keeps alive (a stream's collated ``ptr``), known by address"""
+
+    def __init__(self, addr: int):
+        self.addr = addr
+
+    def data_ptr(self) -> int:
+        return self.addr
+
+
 class _BatchHolder:
     """ctypes batch descriptor + the tensors it points at (kept alive while kernels run)."""
 
@@ -66,6 +82,8 @@ class _BatchHolder:
         self.converted = False
         # store.BatchStream that owns the descriptor (device-collated batches): it holds the targets of a two-headed stream
         self.stream = None
+        # node type index -> largest row count of one graph of the batch, where the collation knows it on the host
+        self.max_rows: Dict[int, int] = {}
 
 
 class NativeNet:
@@ -410,6 +428,9 @@ class NativeNet:
                 h.c.d_node_ptr[i] = p.data_ptr()
         h.c.n_graphs = ng
         h.c.max_graph_nodes = mg if ng else 0
+        if ng:
+            rows = getattr(data, "max_graph_rows", None) or {}
+            h.max_rows = {i: int(rows[t]) for i, t in enumerate(self.node_types) if t in rows}
         if ng:  # graph-sorted edge lists (collate's per-edge-type ptr)
             for i, e in enumerate(self.edge_types):
                 st_ = data[e] if e in data.edge_types else None
@@ -462,9 +483,22 @@ class NativeNet:
     def forward(self, data, training: bool, seed: int = 0, rng_step: int = 0) -> torch.Tensor:
         flat = self.flat_params()
         h = self.make_batch(data)
+        # inputs that ask for a gradient ([PyG] idiom: x.requires_grad_(); model(data)[i, c].backward(); x.grad) become inputs of
+        # the autograd node, behind the parameters; without one the call is what it always was
+        h.grad_inputs = []
+        xs = []
+        if torch.is_grad_enabled():
+            x_dict = data.x_dict
+            for i, t in enumerate(self.node_types):
+                x = x_dict.get(t) if self.in_dims.get(t, 0) > 0 else None
+                if x is not None and x.requires_grad:
+                    if x.dtype != torch.float32:
+                        raise _lib.HydraMPError(f"x_dict['{t}'] requires a gradient: it must be float32 (hydra_gnn_amd computes in fp32)")
+                    h.grad_inputs.append(i)
+                    xs.append(x)
         with torch.cuda.device(flat.device):
             self._ensure_workspace(h, flat.device)
-            return _NetFunction.apply(self, h, bool(training), int(seed), int(rng_step), *self.params)
+            return _NetFunction.apply(self, h, bool(training), int(seed), int(rng_step), *self.params, *xs)
 
     # ---- inference hot loop (bin/room_classification_server:273-299) -------------------------------------------------
     def predict(self, data, n_classes: int) -> torch.Tensor:
@@ -903,6 +937,293 @@ class NativeNet:
             self._att_done.synchronize()
         return split(self._att_host)
 
+    # ---- gradient saliency ([PyG] idiom: x.requires_grad_(); model(data)[i, c].backward(); x.grad) --------------------
+    def _saliency_checks(self, who: str, wrt, head, rows, ordinal) -> Tuple[int, int]:
+        """the argument checks of the saliency calls that need no device: (wrt code, head)"""
+        if self.heads is not None:
+            raise _lib.HydraMPError(f"{who}: nets with learned linear heads are not supported: their outputs are computed behind the "
+                                    "native program (the homogeneous two-headed task)")
+        if self._compute_bf16:
+            raise _lib.HydraMPError(f"{who}: bf16 compute mode is not supported: input gradients are computed in fp32 "
+                                    "(set_compute('fp32'))")
+        if wrt not in WRT_CODES:
+            raise _lib.HydraMPError(f"{who}: wrt must be 'logit' or 'logprob', got {wrt!r}")
+        if isinstance(head, bool) or head not in (0, 1) or (head == 1 and self.aux_readout is None):
+            raise _lib.HydraMPError(f"{who}: head {head!r}: " + ("0 (the readout) or 1 (the second output)" if self.aux_readout is not None
+                                                                  else "the net has one output (head 0)"))
+        if self.head_pools is not None:
+            raise _lib.HydraMPError(f"{who}: two-headed nets with pooled heads are not supported")
+        if rows is not None and ordinal is not None:
+            raise _lib.HydraMPError(f"{who}: rows and ordinal overlap: pass one row selection")
+        if ordinal is not None:
+            p = ordinal[0] if isinstance(ordinal, (tuple, list)) and len(ordinal) == 2 else ordinal
+            if isinstance(p, bool) or not isinstance(p, int) or p < 0:
+                raise _lib.HydraMPError(f"{who}: ordinal must be an int >= 0 or (int >= 0, graph ptr), got {ordinal!r}")
+        return WRT_CODES[wrt], int(head)
+
+    def head_type(self, head: int = 0) -> str:
+        """node type whose rows are the output rows of ``head``"""
+        if head == 1:
+            return self.aux_readout
+        return self.pool_edge_type[2] if self.pool_edge_type is not None else self.readout
+
+    def _head_rows(self, h: _BatchHolder, head: int) -> int:
+        return int(h.c.n_out) if head == 0 else h.n_nodes[self.node_types.index(self.aux_readout)]
+
+    def graph_ptr(self, h: _BatchHolder, node_type: str, dev) -> Tuple[torch.Tensor, int]:
+        """(int64 ``ptr`` [G + 1] on the device, G) of ``node_type`` in the batch ``h``: the collation's, else one graph"""
+        i = self.node_types.index(node_type)
+        ng = int(h.c.n_graphs)
+        if ng > 0 and h.c.d_node_ptr[i]:
+            return _PtrView(int(h.c.d_node_ptr[i])), ng
+        n = h.n_nodes[i]
+        one = torch.arange(0, n + 1, n, dtype=torch.int64, device=dev) if n > 0 else torch.zeros(2, dtype=torch.int64, device=dev)
+        return one, 1
+
+    def _selection(self, h: _BatchHolder, head: int, rows, ordinal, dev, who: str):
+        """(mode, mask address, ordinal, ptr address, graphs, tensors to keep alive) of a row selection over the rows of ``head``"""
+        from .ops import row_members
+
+        n = self._head_rows(h, head)
+        if rows is not None:
+            m = row_members(rows, n, dev)
+            return SEL_MASK, (m.data_ptr() if n > 0 else None), 0, None, 0, m
+        if ordinal is not None:
+            if isinstance(ordinal, (tuple, list)):
+                p, ptr = ordinal
+                if (not isinstance(ptr, torch.Tensor) or ptr.dtype != torch.int64 or ptr.device != dev or ptr.dim() != 1 or ptr.numel() < 2
+                        or not ptr.is_contiguous()):
+                    raise _lib.HydraMPError(f"{who}: the graph ptr of ordinal must be a contiguous int64 vector [graphs + 1] on {dev}")
+                ng = ptr.numel() - 1
+            else:
+                p = ordinal
+                ptr, ng = self.graph_ptr(h, self.head_type(head), dev)
+            return SEL_ORDINAL, None, int(p), ptr.data_ptr(), ng, ptr
+        return SEL_ALL, None, 0, None, 0, None
+
+    def _gx_buffers(self, h: _BatchHolder, out, dev, who: str):
+        """per node type with input features: (index, gx storage [n, ldx], view [n, F]); ``out``: the caller's ``{type: tensor}``"""
+        res = []
+        for i, t in enumerate(self.node_types):
+            F = self.in_dims.get(t, 0)
+            if F <= 0 or not h.c.d_x[i]:
+                continue
+            n, ld = h.n_nodes[i], int(h.c.ldx[i])
+            o = out.get(t) if out is not None else None
+            if o is None:
+                buf = torch.zeros((max(n, 1), ld), dtype=torch.float32, device=dev)  # types the program never reads keep 0
+            else:
+                if (not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or o.device != dev or o.dim() != 2 or o.size(0) < n
+                        or o.size(1) < F or o.stride(1) != 1 or (o.size(0) > 1 and o.stride(0) != ld)):
+                    got = f"{tuple(o.shape)} {o.dtype} on {o.device}" if isinstance(o, torch.Tensor) else repr(type(o))
+                    raise _lib.HydraMPError(f"{who}: out['{t}'] must be a float32 tensor [rows >= {n}, >= {F}] on {dev} with the row "
+                                            f"pitch of x ({ld}), got {got}")
+                buf = o
+            res.append((i, t, buf, buf[:n, :F]))
+        return res
+
+    def input_gradients(self, batch, target=None, rows=None, ordinal=None, wrt: str = "logit", head: int = 0,
+                        out=None) -> Dict[str, torch.Tensor]:
+        """``{node_type: d s / d x[node_type]}`` on the device, float32 ``[n_t, F_t]``, where ``s`` is the sum over the selected
+        output rows of ``head`` of the chosen class's logit (``wrt="logit"``) or log-probability (``"logprob"``): eval-mode native
+        forward, one seed launch and the backward chain without the weight gradients (``hmp_net_input_gradient``).  Nothing
+        synchronises; the activations of any earlier ``forward()`` are overwritten.
+
+        ``target``: int64 class per output row on the device (a value outside ``[0, classes)`` falls back to the prediction);
+        None: every row's own prediction (:meth:`predict_labels`).  Row selection: ``rows`` (a bool tensor over the output rows)
+        or ``ordinal`` (``p``: the ``p``-th output row of every graph of the batch, by the collation's ``ptr``; ``(p, ptr)`` with
+        an explicit int64 ``[G + 1]``); neither: all rows.  ``batch`` is a data object or a ``store.BatchStream`` descriptor.
+        ``out``: caller-owned ``{node_type: tensor}`` with the row pitch of that type's ``x``, zeroed once by the caller (a node
+        type the program never reads is not written)."""
+        who = "input_gradients"
+        w, head = self._saliency_checks(who, wrt, head, rows, ordinal)
+        h, flat = self._attention_batch(batch, who)
+        dev = flat.device
+        n_out = self._head_rows(h, head)
+        tgt = None
+        if target is not None:
+            _require_cuda(target, "target")
+            if target.dtype != torch.int64 or target.numel() != n_out or target.device != dev:
+                raise _lib.HydraMPError(f"{who}: target must be an int64 tensor with {n_out} entries on {dev}")
+            tgt = target.contiguous()
+        mode, mptr, p, pptr, ng, keep = self._selection(h, head, rows, ordinal, dev, who)
+        bufs = self._gx_buffers(h, out, dev, who)
+        slots = (C.c_void_p * _lib.MAX_NODE_TYPES)()
+        for i, _, buf, _ in bufs:
+            slots[i] = buf.data_ptr()
+        self._count("hmp_net_input_gradient", h, dev, flat.data_ptr(), head, tgt.data_ptr() if tgt is not None and n_out > 0 else None,
+                    mode, mptr, p, pptr, ng, w, slots)
+        del keep
+        return {t: view for _, t, _, view in bufs}
+
+    def _score_ranges(self, groups, F: int, who: str):
+        groups = tuple(groups) if groups is not None else ()
+        if len(groups) > SAL_MAX_GROUPS:
+            raise _lib.HydraMPError(f"{who}: {len(groups)} column groups (at most {SAL_MAX_GROUPS})")
+        lo, hi = [], []
+        for g in groups:
+            if not isinstance(g, (tuple, list)) or len(g) != 2:
+                raise _lib.HydraMPError(f"{who}: a column group is (lo, hi) with hi None = the last column, got {g!r}")
+            lo.append(max(0, int(g[0])))
+            hi.append(F if g[1] is None else min(F, int(g[1])))
+        return lo, hi
+
+    def saliency_scores(self, gx: torch.Tensor, x_ptr: int, ldx: int, n: int, F: int, groups, dev, who: str = "saliency"):
+        """``(gxi [n], gnorm [n], groups [n, n_groups])`` of one node type: ``hmp_saliency_scores`` on a gradient view ``gx``
+        (``[n, F]``, any pitch) against the input rows at ``x_ptr`` / ``ldx``"""
+        lo, hi = self._score_ranges(groups, F, who)
+        ng = len(lo)
+        rows = max(n, 1)
+        buf = torch.empty(rows * (2 + ng), dtype=torch.float32, device=dev)  # one allocation: gxi, gnorm, then the groups
+        gxi, gnorm, grp = buf[:rows], buf[rows:2 * rows], buf[2 * rows:].view(rows, ng)
+        lo_c, hi_c = (C.c_int32 * max(ng, 1))(*lo), (C.c_int32 * max(ng, 1))(*hi)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hmp_saliency_scores(gx.data_ptr(), gx.stride(0) if gx.size(0) > 1 else max(gx.size(1), F), x_ptr, ldx, n, F, ng,
+                                                     lo_c, hi_c, gxi.data_ptr(), gnorm.data_ptr(), grp.data_ptr() if ng else None,
+                                                     _lib.stream_ptr()))
+        return gxi[:n], gnorm[:n], grp[:n]
+
+    def saliency(self, batch, groups=DEFAULT_GROUPS, **kw) -> Dict[str, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """``{node_type: (gxi [n], gnorm [n], groups [n, n_groups])}`` on the device: :meth:`input_gradients` (``**kw``) reduced
+        against the input per node row (``hmp_saliency_scores``, one launch per node type): ``gxi = sum_f g * x`` (signed gradient
+        x input), ``gnorm = sqrt(sum_f g^2)``, ``groups[:, i]`` = gradient x input over the columns ``[lo, hi)`` of
+        ``groups[i]`` (at most 4; ``hi`` None = the last column; clipped to the type's width).  The default groups are the blocks
+        of the 306-d object features: position, box size, word2vec.  Nothing synchronises."""
+        self._score_ranges(groups, 1, "saliency")
+        self._saliency_checks("saliency", kw.get("wrt", "logit"), kw.get("head", 0), kw.get("rows"), kw.get("ordinal"))
+        h, _ = self._attention_batch(batch, "saliency")
+        gx = self.input_gradients(h, **kw)
+        dev = next(iter(gx.values())).device if gx else None
+        res = {}
+        for t, g in gx.items():
+            i = self.node_types.index(t)
+            res[t] = self.saliency_scores(g, int(h.c.d_x[i]), int(h.c.ldx[i]), h.n_nodes[i], self.in_dims[t], groups, dev)
+        return res
+
+    def _salient_edge(self, edge_type, who: str) -> EdgeType:
+        et = tuple(edge_type)
+        if et not in self.edge_types:
+            raise _lib.HydraMPError(f"{who}: the net has no edge type {et!r}")
+        if self.in_dims.get(et[0], 0) <= 0:
+            raise _lib.HydraMPError(f"{who}: node type '{et[0]}' has no input features to attribute to")
+        return et
+
+    def salient_edge_types(self) -> List[EdgeType]:
+        """edge types of the live convs whose source type has input features (what the models' ``top_salient`` ranks by default)"""
+        live = {c.edge_type for layer in self.layers for c in layer.convs if c.active}
+        return [e for e in self.edge_types if e in live and self.in_dims.get(e[0], 0) > 0]
+
+    def top_salient(self, batch, edge_type, k: int, out=None, passes=None, **kw):
+        """``(src int64 [n_dst, k], score float32 [n_dst, k])`` on the device: for every destination row of ``edge_type`` the ``k``
+        sources with the largest ``|gradient x input|``, descending, with the signed score; lower source index first on equal
+        magnitude, a source reached by several edges once, ``-1`` / ``0`` past a row's sources (``top_attended``'s conventions;
+        ``1 <= k <= 8``).  The scores are :meth:`saliency`'s ``gxi`` of the edge type's source type under ``**kw``
+        (:meth:`input_gradients`' arguments): ONE gradient for all rows, i.e. what the selected outputs TOGETHER rest on.
+
+        ``passes=P`` instead runs exact per-row passes: pass ``p < P`` explains output row ``ptr[g] + p`` of every graph ``g`` on
+        its own (``ordinal=p``) and fills the destination rows of that ordinal only (the others keep what ``out`` held) -- the
+        destination type must then be the head's output type.  All passes are queued without a host synchronisation.
+        ``passes`` may also be a device int64 vector of output rows: one pass per listed row (a batch whose rows of interest are
+        not its graphs' leading rows: the room nodes of a homogeneous batch).
+
+        ``edge_type`` may also be a LIST of edge types: one gradient per pass serves them all and the result is
+        ``{edge_type: (src, score)}`` (``out`` then a dict of pairs)."""
+        who = "top_salient"
+        k = _check_k(k)
+        many = isinstance(edge_type, list)
+        ets = [self._salient_edge(e, who) for e in (edge_type if many else [edge_type])]
+        if passes is not None and (kw.get("rows") is not None or kw.get("ordinal") is not None):
+            raise _lib.HydraMPError(f"{who}: passes and rows / ordinal overlap: per-row passes select their own rows")
+        self._saliency_checks(who, kw.get("wrt", "logit"), kw.get("head", 0), kw.get("rows"), kw.get("ordinal"))
+        head_t = self.head_type(int(kw.get("head", 0)))
+        if passes is not None:
+            for et in ets:
+                if et[2] != head_t:
+                    raise _lib.HydraMPError(f"{who}: per-row passes rank the sources of the output rows: edge type {et!r} does not end "
+                                            f"in '{head_t}'")
+        h, flat = self._attention_batch(batch, who)
+        dev = flat.device
+        idx = lambda t: self.node_types.index(t)  # noqa: E731
+        res = {}
+        for et in ets:
+            if not h.c.d_x[idx(et[0])]:
+                raise _lib.HydraMPError(f"{who}: the batch has no input features of node type '{et[0]}'")
+            o = (out.get(et) if out is not None else None) if many else out
+            if o is not None and (not isinstance(o, (tuple, list)) or len(o) != 2):
+                raise _lib.HydraMPError(f"{who}: out must be a (src, score) pair of tensors")
+            nd = h.n_nodes[idx(et[2])]
+            res[et] = (_attention_buffer(o[0] if o is not None else None, nd, k, torch.int64, dev, "out[0]"),
+                       _attention_buffer(o[1] if o is not None else None, nd, k, torch.float32, dev, "out[1]"), nd)
+        gxi = {t: torch.empty(max(h.n_nodes[idx(t)], 1), dtype=torch.float32, device=dev) for t in {et[0] for et in ets}}
+        plan = _lib.Plan()
+        gbuf = {t: b for _, t, b, _ in self._gx_buffers(h, None, dev, who)}  # one set of gradient buffers for all passes
+        if passes is None:
+            todo = [(None, None, 0)]
+        elif isinstance(passes, torch.Tensor):  # one pass per listed row r: ordinal 0 of the one-graph ptr [r, r + 1]
+            if passes.dtype != torch.int64 or passes.dim() != 1 or passes.device != dev:
+                raise _lib.HydraMPError(f"{who}: passes must be a pass count or an int64 vector of output rows on {dev}")
+            ranges = torch.stack([passes, passes + 1], dim=1).contiguous()
+            todo = [(0, ranges[r], 1) for r in range(ranges.size(0))]
+        else:
+            ptr, ng = self.graph_ptr(h, head_t, dev)
+            todo = [(p, ptr, ng) for p in range(int(passes))]
+        for p, ptr, ng in todo:
+            g = self.input_gradients(h, out=gbuf, **(dict(kw, ordinal=(p, ptr) if isinstance(ptr, torch.Tensor) else p) if p is not None else kw))
+            with torch.cuda.device(dev):
+                for t, sc in gxi.items():
+                    i = idx(t)
+                    _lib.check(self._lib.hmp_saliency_scores(g[t].data_ptr(), int(h.c.ldx[i]), int(h.c.d_x[i]), int(h.c.ldx[i]),
+                                                             h.n_nodes[i], self.in_dims[t], 0, None, None, sc.data_ptr(), None, None,
+                                                             _lib.stream_ptr()))
+                for et in ets:
+                    _lib.check(self._lib.hmp_net_plan(self._handle, self.edge_types.index(et), C.byref(plan)))
+                    _lib.check(self._lib.hmp_saliency_topk(plan, gxi[et[0]].data_ptr(), k, SEL_ORDINAL if p is not None else SEL_ALL, None,
+                                                           p or 0, ptr.data_ptr() if p is not None else None, ng,
+                                                           res[et][0].data_ptr(), res[et][1].data_ptr(), _lib.stream_ptr()))
+        res = {et: (s_[:nd], w_[:nd]) for et, (s_, w_, nd) in res.items()}
+        return res if many else res[ets[0]]
+
+    def max_graph_rows(self, batch, node_type: str) -> int:
+        """an upper bound of the ``node_type`` rows in one graph of the batch (the pass count of exact per-row explanations), from
+        host-side numbers only: the collation's per-type maximum (``data.collate``, ``BatchStream.next``) or its largest graph where
+        the batch is a union of graphs, else all rows (one graph)"""
+        h, _ = self._attention_batch(batch, "max_graph_rows")
+        i = self.node_types.index(node_type)
+        if int(h.c.n_graphs) > 0 and h.c.d_node_ptr[i] and int(h.c.max_graph_nodes) > 0:
+            return min(h.n_nodes[i], h.max_rows.get(i, int(h.c.max_graph_nodes)))
+        return h.n_nodes[i]
+
+    def explain_salient(self, batch, edge_type, k: int, passes: Optional[int] = None, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+        """:meth:`top_salient` with exact per-row passes on the host: every pass lands in ONE device buffer (8 bytes per source,
+        then 4 per score) that crosses in one D2H through one pinned buffer and one event, as :meth:`explain` moves its result.
+        ``passes`` defaults to the largest output-row count of a graph of the batch.  Rows without a pass (none exist by default)
+        hold ``-1`` / ``0``.  Returns host ``(src int64 [n_dst, k], score float32 [n_dst, k])``, views of that buffer (valid until
+        the next call)."""
+        k = _check_k(k)
+        et = self._salient_edge(edge_type, "explain_salient")
+        h, flat = self._attention_batch(batch, "explain_salient")
+        dev = flat.device
+        if passes is None:
+            passes = self.max_graph_rows(h, et[2])
+        nd = h.n_nodes[self.node_types.index(et[2])]
+        n = nd * k
+        with torch.cuda.device(dev):
+            if getattr(self, "_att_dev", None) is None or self._att_dev.numel() < 12 * n or self._att_dev.device != dev:
+                cap = max(4096, 24 * n)
+                self._att_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
+                self._att_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+                self._att_done = torch.cuda.Event()
+            split = lambda buf: (buf[:8 * n].view(torch.int64).view(nd, k), buf[8 * n:12 * n].view(torch.float32).view(nd, k))  # noqa: E731
+            if n > 0:
+                s_dev, w_dev = split(self._att_dev)
+                s_dev.fill_(-1)
+                w_dev.zero_()
+                self.top_salient(h, et, k, out=(s_dev, w_dev), passes=passes, **kw)
+                self._att_host[:12 * n].copy_(self._att_dev[:12 * n], non_blocking=True)
+            self._att_done.record()
+            self._att_done.synchronize()
+        return split(self._att_host)
+
     def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
         """the count entries' common block: ``entry(handle, batch, *args, stream)`` (eval-mode forward + count on the device),
         which overwrites the activations of any earlier forward()"""
@@ -930,18 +1251,19 @@ class NativeNet:
         _lib.check(self._lib.hmp_net_aux_output(self._handle, C.byref(out_p), C.byref(ld), C.byref(rows)))
         return out, self._ws_view(out_p.value, rows.value, ld.value).clone()
 
-    def _backward_raw(self, gout: Optional[torch.Tensor], gaux: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _backward_raw(self, gout: Optional[torch.Tensor], gaux: Optional[torch.Tensor] = None, d_gx=None) -> torch.Tensor:
+        """``d_gx``: the executor's table of input-gradient buffers (one slot per node type, None = not wanted), else None"""
         dev = (gout if gout is not None else gaux).device
         grads = torch.zeros(self.n_params + 4, dtype=torch.float32, device=dev)
         if self.aux_readout is None:
             _lib.check(self._lib.hmp_net_backward(self._handle, gout.data_ptr(), gout.stride(0), self._flat.data_ptr(),
-                                                  grads.data_ptr(), None, _lib.stream_ptr()))
+                                                  grads.data_ptr(), d_gx, _lib.stream_ptr()))
         else:
             _lib.check(self._lib.hmp_net_backward2(self._handle, gout.data_ptr() if gout is not None else None,
                                                    gout.stride(0) if gout is not None else 0,
                                                    gaux.data_ptr() if gaux is not None else None,
                                                    gaux.stride(0) if gaux is not None else 0, self._flat.data_ptr(),
-                                                   grads.data_ptr(), None, _lib.stream_ptr()))
+                                                   grads.data_ptr(), d_gx, _lib.stream_ptr()))
         return grads
 
     def hidden(self, layer: int, node_type: str) -> torch.Tensor:
@@ -1087,9 +1409,23 @@ class _NetFunction(torch.autograd.Function):
                 gout = padded
         if gaux is not None:
             gaux = gaux.contiguous()  # staged by the executor (any row pitch)
+        want_x = getattr(ctx.holder, "grad_inputs", None) or []
         if gout is None and gaux is None:
-            return (None,) * (5 + len(net.params))
-        flat_g = net._backward_raw(gout, gaux)
+            return (None,) * (5 + len(net.params) + len(want_x))
+        d_gx, gx = None, []
+        if want_x:
+            if net.heads is not None or net._compute_bf16:
+                raise _lib.HydraMPError("an input of the batch requires a gradient: not supported for nets with learned linear heads or in "
+                                        "bf16 compute mode")
+            h = ctx.holder
+            dev = (gout if gout is not None else gaux).device
+            d_gx = (C.c_void_p * _lib.MAX_NODE_TYPES)()
+            for i in want_x:  # storage with the pitch of x; a node type the program never reads keeps 0
+                n, F = h.n_nodes[i], net.in_dims[net.node_types[i]]
+                buf = torch.zeros((max(n, 1), int(h.c.ldx[i])), dtype=torch.float32, device=dev)
+                d_gx[i] = buf.data_ptr()
+                gx.append(buf[:n, :F])
+        flat_g = net._backward_raw(gout, gaux, d_gx)
         grads = []
         for p, live in zip(net.params, net.param_active):
             if not live:
@@ -1097,7 +1433,7 @@ class _NetFunction(torch.autograd.Function):
                 continue
             off = net.param_offsets[id(p)]
             grads.append(flat_g[off:off + p.numel()].view(p.shape))
-        return (None, None, None, None, None, *grads)
+        return (None, None, None, None, None, *grads, *gx)
 
 
 class TrainStep:

@@ -255,3 +255,44 @@ def predict_topk(model, batches: Union[Iterable, Tuple[object, Iterable]], k: in
         heads.append(_split_topk(hl[totals[0]:], hp[totals[0]:], counts[1]))
         return list(zip(heads[0], heads[1]))
     return heads[0]
+
+
+def saliency(model, batches: Union[Iterable, Tuple[object, Iterable]], groups=((0, 3), (3, 6), (6, None)), **kw):
+    """Gradient saliency over ``batches`` with ONE device-to-host copy at the end of the pass (``model.saliency`` per batch: eval-mode
+    forward, one seed launch, the input-gradient chain and one reduction launch per node type; nothing synchronises in between).
+    ``batches`` takes the forms :func:`predict` takes; ``groups`` and ``**kw`` (``target``, ``wrt``, ``head``) go to
+    ``model.saliency``.  Every batch explains all its output rows together: the gradient of the sum of each row's own
+    predicted-class logit.
+
+    ``(BatchStream, iterable of graph-id lists)``: one entry per graph in id order, ``{node_type: (gxi [n], gnorm [n], groups [n,
+    n_groups])}`` of numpy float32 arrays over the graph's rows of that node type (homogeneous models: the one triple).  An
+    iterable of batches: one entry per BATCH in that structure."""
+    stream, id_lists = _pass_args(model, batches, "saliency")
+    per_batch = [model.saliency(stream.next(ids) if stream is not None else b, groups=groups, **kw)
+                 for ids, b in (zip(id_lists, id_lists) if stream is not None else ((None, b) for b in batches))]
+    if not per_batch:
+        return []
+    homog = isinstance(per_batch[0], tuple)
+    dicts = [{None: r} if homog else r for r in per_batch]
+    flat = [t.reshape(-1) for d in dicts for trip in d.values() for t in trip]
+    host = torch.cat(flat).cpu().numpy() if flat else np.zeros(0, dtype=np.float32)  # the one copy (and synchronisation) of the pass
+    pos = 0
+    out = []
+    for bi, d in enumerate(dicts):
+        arrays = {}
+        for t, trip in d.items():
+            parts = []
+            for v in trip:
+                parts.append(host[pos:pos + v.numel()].reshape(tuple(v.shape)))
+                pos += v.numel()
+            arrays[t] = tuple(parts)
+        if stream is None:
+            out.append(arrays[None] if homog else arrays)
+            continue
+        ids = id_lists[bi]
+        node_types = stream.store.node_types
+        offs = {t: np.concatenate([[0], np.cumsum(stream.store.node_counts[t if t is not None else node_types[0]][ids])]) for t in arrays}
+        for g in range(len(ids)):
+            piece = {t: tuple(a[offs[t][g]:offs[t][g + 1]] for a in trip) for t, trip in arrays.items()}
+            out.append(piece[None] if homog else piece)
+    return out

@@ -432,6 +432,22 @@ class BaseTrainingJob:
         result), or a ``(room, object)`` pair of those for a two-headed model; one device-to-host copy per pass."""
         return self._predict_pass(split, self.get_dataset(split), k)
 
+    def saliency(self, split, groups=((0, 3), (3, 6), (6, None)), **kw):
+        """Gradient saliency of every graph of the split ``"train"`` / ``"val"`` / ``"test"``, from the job's own device-resident copy
+        in ``batch_size`` batches with one device-to-host copy per pass (``evaluate.saliency``): per graph ``{node_type: (gxi [n],
+        gnorm [n], groups [n, n_groups])}`` numpy arrays (homogeneous models: the one triple) of the gradient of the rows' own
+        predicted-class logits.  GraphSAGE / GAT / GAT_edge models; GCN / GIN models are refused by name."""
+        net = self._net
+        if self._op_path():
+            raise _lib.HydraMPError(f"saliency: {net.conv_block} models run op by op (hydra_gnn_amd.ops), not the native program: they "
+                                    "have no input-gradient path (GraphSAGE, GAT and GAT_edge models do)")
+        net.eval()
+        dataset = self.get_dataset(split)
+        device = next(net.parameters()).device
+        B = self._training_params["optimization_params"]["batch_size"]
+        with torch.cuda.device(device):
+            return evaluate.saliency(net, (self._stream(split, dataset, device, B), id_chunks(len(dataset), B)), groups=groups, **kw)
+
     def _predict_pass(self, name, dataset, k=None):
         """``k`` None: the labels of ``evaluate.predict``; else the top-k pairs of ``evaluate.predict_topk``"""
         net = self._net

@@ -155,6 +155,81 @@ class _NativeModule(nn.Module):
             return net.top_attended(self._attention_input(data), l, ets[0] if homog else ets, k)
         return net.top_attended(self._attention_input(data), l, tuple(edge_type), k)
 
+    # ---- gradient saliency ([PyG] idiom: x.requires_grad_(); model(data)[i, c].backward(); x.grad) --------------------
+    def _saliency_net(self, who: str) -> NativeNet:
+        """the native net after the refusals that need no device, or HydraMPError without one"""
+        if getattr(self, "op_path", False):
+            raise _lib.HydraMPError(f"{who}: {self.conv_block} models run op by op (hydra_gnn_amd.ops), not the native program: they "
+                                    "have no input-gradient path (GraphSAGE, GAT and GAT_edge models do)")
+        net = self.native()
+        net._saliency_checks(who, "logit", 0, None, None)
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        return net
+
+    def _saliency_rows(self, data, rows):
+        """the default row selection: every output row; homogeneous room classifiers: the rows of ``room_mask`` (the native output
+        has a row per node, the model's output the room rows)"""
+        from ..engine import _BatchHolder
+
+        if rows is not None or getattr(self, "_view", None) is None:
+            return rows
+        if isinstance(data, _BatchHolder):
+            if data.stream is not None and getattr(data.stream, "homog_room", False):
+                return data.stream.members[:int(data.c.n_out)]  # the collated room_mask of the current batch
+            return None
+        return getattr(data, "room_mask", None)
+
+    def input_gradients(self, data, target=None, rows=None, wrt="logit", head=0, ordinal=None):
+        """Gradient of the chosen class's logit (``wrt="logit"``) or log-probability (``"logprob"``), summed over the selected
+        output rows, with respect to the input features, left on the device (nothing synchronises): eval-mode native forward, one
+        seed launch and the backward chain without the weight gradients (:meth:`NativeNet.input_gradients`).  Heterogeneous
+        models return ``{node_type: gx [n_t, F_t]}``, homogeneous models the one tensor.
+
+        ``target``: int64 class per native output row (None: the row's prediction, :meth:`predict_labels`); ``rows``: bool
+        selection of output rows (None: all; homogeneous models: ``data.room_mask``, and ``target`` / ``rows`` have one entry per
+        NODE); ``ordinal=p``: the ``p``-th output row of every graph of the batch instead.  ``head=1``: the object head of a
+        two-headed heterogeneous model.  ``data`` is a batch or a descriptor from ``store.BatchStream.next``."""
+        net = self._saliency_net("input_gradients")
+        res = net.input_gradients(self._attention_input(data), target=target, rows=self._saliency_rows(data, rows) if ordinal is None else None,
+                                  ordinal=ordinal, wrt=wrt, head=head)
+        return next(iter(res.values())) if len(net.node_types) == 1 else res
+
+    def saliency(self, data, groups=((0, 3), (3, 6), (6, None)), target=None, rows=None, wrt="logit", head=0, ordinal=None):
+        """Per node type ``(gxi [n], gnorm [n], groups [n, n_groups])`` on the device: :meth:`input_gradients` reduced against the
+        input per node row (:meth:`NativeNet.saliency`): signed gradient x input, gradient norm, and gradient x input per column
+        range of ``groups`` (at most 4 ``(lo, hi)``, ``hi`` None = the last column; the default splits the 306-d object features
+        into position, box size and the word2vec block).  Heterogeneous models return ``{node_type: triple}``, homogeneous
+        models the one triple.  Nothing synchronises."""
+        net = self._saliency_net("saliency")
+        res = net.saliency(self._attention_input(data), groups=groups, target=target,
+                           rows=self._saliency_rows(data, rows) if ordinal is None else None, ordinal=ordinal, wrt=wrt, head=head)
+        return next(iter(res.values())) if len(net.node_types) == 1 else res
+
+    def top_salient(self, data, edge_type=None, k=3, target=None, rows=None, wrt="logit", head=0):
+        """``(src int64 [n_dst, k], score float32 [n_dst, k])`` on the device: per destination row of ``edge_type`` the ``k``
+        sources with the largest ``|gradient x input|`` under ONE gradient for all selected rows (:meth:`NativeNet.top_salient`;
+        ``top_attended``'s conventions, the score signed).  Heterogeneous models: ``edge_type=None`` returns ``{edge_type: (src,
+        score)}`` for every live conv whose source type has input features; homogeneous models return their one pair."""
+        net = self._saliency_net("top_salient")
+        homog = len(net.node_types) == 1
+        kw = dict(target=target, rows=self._saliency_rows(data, rows), wrt=wrt, head=head)
+        if edge_type is None:
+            ets = net.salient_edge_types()
+            return net.top_salient(self._attention_input(data), ets[0] if homog else ets, k, **kw)
+        return net.top_salient(self._attention_input(data), tuple(edge_type), k, **kw)
+
+    _EXPLAIN_EDGE = None  # the edge type whose sources explain_rooms ranks for every output row (None: the model has none)
+
+    def _explain_by_gradient(self, data, k, target=None, wrt="logit"):
+        """exact per-room passes in ordinal mode over the readout's ``ptr``, all queued into one output, one copy at the end"""
+        if self._EXPLAIN_EDGE is None:
+            raise _lib.HydraMPError(f"explain_rooms: {type(self).__name__} has no edge type that ends in its output rows to rank over "
+                                    "(use top_salient / saliency)")
+        if getattr(self, "classification_task", "room") != "room":
+            raise _lib.HydraMPError("explain_rooms: the model is two-headed; use top_salient(head=...)")
+        net = self._saliency_net("explain_rooms")
+        return net.explain_salient(self._attention_input(data), self._EXPLAIN_EDGE, k, target=target, wrt=wrt)
+
     def loss(self, pred, label, mask=None):
         return cross_entropy_loss(pred, label, mask)
 
@@ -319,16 +394,29 @@ class HeterogeneousNetwork(_HeteroTwoHead):
         return NativeNet(node_types, self.input_dim_dict, EDGE_TYPES, _hetero_layers(self, node_types), readout="rooms",
                          aux_readout="objects" if two else None, tail=tail)
 
-    def explain_rooms(self, data, k=3):
-        """Which objects a room's label rests on, on the host: for every room the ``k`` most attended objects of the last layer's
-        ``objects_to_rooms`` conv and their weights -- :meth:`top_attended` on that conv through one pinned buffer and one
-        device-to-host copy, as :meth:`predict_with_confidence` moves its labels.  Returns ``(objects int64 [rooms, k], weight
-        float32 [rooms, k])``, ``-1`` / ``0`` past a room's objects (views of that buffer: valid until the next call).  GAT /
-        GAT_edge models only."""
+    _EXPLAIN_EDGE = ("objects", "objects_to_rooms", "rooms")
+
+    def explain_rooms(self, data, k=3, by="attention", target=None, wrt="logit"):
+        """Which objects a room's label rests on, on the host: ``(objects int64 [rooms, k], weight float32 [rooms, k])``, ``-1`` /
+        ``0`` past a room's objects (views of one pinned buffer: valid until the next call), moved by one device-to-host copy.
+
+        ``by="attention"`` (the default; GAT / GAT_edge models only, which keep returning what they returned): for every room
+        the ``k`` most attended objects of the last layer's ``objects_to_rooms`` conv and their weights (:meth:`top_attended`).
+        ``by="gradient"`` (GraphSAGE, GAT and GAT_edge models): the ``k`` objects with the largest ``|gradient x input|`` of the
+        room's own predicted-class logit (``target`` / ``wrt`` as :meth:`input_gradients` takes them) with the signed score --
+        exact per-room passes, one per room ordinal of the batch's graphs (a single frame is one graph), all queued without a
+        host synchronisation into one output."""
+        if by not in ("attention", "gradient"):
+            raise _lib.HydraMPError(f"explain_rooms: by must be 'attention' or 'gradient', got {by!r}")
+        if by == "gradient":
+            return self._explain_by_gradient(data, k, target=target, wrt=wrt)
+        if self.conv_block[:3] != "GAT":
+            raise _lib.HydraMPError(f"explain_rooms: no attention coefficients: conv_block {self.conv_block} has no attention (GAT and "
+                                    "GAT_edge models export them); explain_rooms(by='gradient') ranks the objects by gradient x "
+                                    "input on every model")
         l = self._attention_layer(-1, "explain_rooms")
         _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
-        et = next(e for e in EDGE_TYPES if e[0] == "objects" and e[2] == "rooms")
-        return self.native().explain(data, l, et, k)
+        return self.native().explain(data, l, self._EXPLAIN_EDGE, k)
 
     def forward(self, data):
         out = self._run(data)

@@ -129,6 +129,15 @@ class HeterogeneousNeuralTreeNetwork(_HeteroTwoHead):
         return NativeNet(node_types, in_dims, list(HTREE_EDGE_TYPES) + pool_et + list(HTREE_INIT_EDGE_TYPES),
                          [init] + layers, **pool)
 
+    _EXPLAIN_EDGE = POOL_EDGE_TYPE
+
+    def explain_rooms(self, data, k=3, target=None, wrt="logit"):
+        """Which room leaves of the H-tree a pooled room row's label rests on, on the host: per ``room_virtual`` row the ``k``
+        ``room`` nodes of its LeafPool with the largest ``|gradient x input|`` of the row's own predicted-class logit, with the
+        signed score (exact per-row passes, one device-to-host copy; see ``HeterogeneousNetwork.explain_rooms(by="gradient")``).
+        Room task only."""
+        return self._explain_by_gradient(data, k, target=target, wrt=wrt)
+
     def forward(self, data):
         out = self._run(data)
         dims = self.native().layers[-1].out_dims

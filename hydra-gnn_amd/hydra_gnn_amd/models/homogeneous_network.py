@@ -385,6 +385,24 @@ class HomogeneousNetwork(_NativeModule):
         with torch.no_grad():
             return ops.argmax_rows(self(data)).cpu()
 
+    _EXPLAIN_EDGE = _EDGE  # (H-tree: the LeafPool's edges, whose sources are the room's leaves)
+
+    def explain_rooms(self, data, k=3, target=None, wrt="logit"):
+        """Which nodes a room's label rests on, on the host: for every row of ``data.room_mask``, in row order, the ``k`` neighbours
+        (sources of the room's incoming edges; H-tree model: the leaves of its LeafPool) with the largest ``|gradient x input|`` of the room's own predicted-class logit and
+        their signed scores -- ``(nodes int64 [rooms, k], score float32 [rooms, k])``, ``-1`` / ``0`` past a room's neighbours.
+        One exact pass per room (:meth:`NativeNet.top_salient` with the room rows as ``passes``): a collated homogeneous batch
+        carries no graph offsets, and its rooms are not its graphs' leading rows.  The room rows are read from ``room_mask`` once
+        up front; the passes are then queued without a synchronisation and the result crosses in one copy.  Room task, GraphSAGE /
+        GAT / GAT_edge; ``target`` has one entry per NODE."""
+        if self.classification_task != "room":
+            raise HydraMPError("explain_rooms: the model is two-headed (learned linear heads): no input-gradient path")
+        net = self._saliency_net("explain_rooms")
+        rows = torch.nonzero(data.room_mask).flatten()  # (synchronises: the number of passes is a host number)
+        src, score = net.explain_salient(self._view(data), self._EXPLAIN_EDGE, k, passes=rows, target=target, wrt=wrt)
+        idx = rows.cpu()
+        return src[idx], score[idx]
+
     def forward(self, data):
         if self.op_path:
             return self._op_heads(self._op_states(data), data.room_mask, ~data.room_mask)

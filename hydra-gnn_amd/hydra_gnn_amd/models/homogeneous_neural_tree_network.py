@@ -117,6 +117,7 @@ class HomogeneousNeuralTreeNetwork(HomogeneousNetwork):
                          **self._head_kw())
 
     _OBJECT_ATTR = "object_mask"  # reference :109
+    _EXPLAIN_EDGE = _POOL
 
     def _drop_stream(self, l: int) -> int:
         # with pre_mp inside the native program (SAGE / GAT) the convs are its layers 1..L

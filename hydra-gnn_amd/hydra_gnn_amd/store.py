@@ -641,6 +641,8 @@ class BatchStream:
             hd.n_edges[i] = v
         hd.c.n_out = tot[self._out_slot]
         hd.c.n_graphs = B
+        hd.max_rows = {i: int(self.store.node_counts[t][sel].max()) for i, t in enumerate(self.nat.node_types)
+                       if t in self.store.node_counts}
         self.num_graphs = B
         return hd
 

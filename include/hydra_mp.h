@@ -59,7 +59,10 @@ extern "C" {
  *    resident store): new entries and new kinds behind the old ones; hmp_collator_create accepts a null d_src for an item whose
  *    slot is empty in every graph (it was refused before);
  *    hmp_gat_attention / hmp_net_attention (per-edge attention coefficients and the top-k sources per row, from the softmax state
- *    of a forward): new entries, no struct was added or changed layout */
+ *    of a forward): new entries, no struct was added or changed layout;
+ *    hmp_saliency_seed / hmp_saliency_scores / hmp_saliency_topk / hmp_net_input_gradient / hmp_net_plan (gradient saliency: the gradient of a
+ *    chosen class's logit or log-probability with respect to the input features, and its reductions): new entries, no struct was
+ *    added or changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -233,6 +236,42 @@ int hmp_gat_bwd(const float* d_gout, int32_t ldg, const float* d_h_src, int32_t 
 int hmp_gat_attention(const float* d_a_src, int32_t lda_src, const float* d_a_dst, int32_t lda_dst, const float* d_edge_attr,
                       const float* d_v_edge, const int64_t* d_edge_index, hmp_plan plan, hmp_gat_args args, const float* d_smax,
                       const float* d_sden, float* d_alpha, int32_t k, int64_t* d_top_src, float* d_top_w, void* stream);
+
+/* Gradient saliency, the three stand-alone launches (each is one launch on `stream`, nothing synchronises; ABI-4-compatible
+ * additions).  A ROW SELECTION (sel_mode, d_mask, ordinal, d_graph_ptr, n_graphs) names the rows a launch serves:
+ *   HMP_SEL_ALL      every row;
+ *   HMP_SEL_MASK     the rows whose byte of d_mask [n_rows] is not 0;
+ *   HMP_SEL_ORDINAL  row d_graph_ptr[g] + ordinal of every graph g with more than `ordinal` rows; d_graph_ptr is int64 [n_graphs + 1],
+ *                    ascending from 0 ([PyG] Batch.ptr of the rows' node type), empty graphs allowed.
+ * Arguments a mode does not use are ignored. */
+#define HMP_SEL_ALL 0
+#define HMP_SEL_MASK 1
+#define HMP_SEL_ORDINAL 2
+#define HMP_WRT_LOGIT 0
+#define HMP_WRT_LOGPROB 1
+/* The output gradient that selects what is explained.  Class c of a selected row is d_target[row] where d_target is given and the
+ * value lies in [0, n_classes), else the row's first-maximum argmax (bit-equal to hmp_predict_rows).  The row of d_gout is
+ * onehot(c) (HMP_WRT_LOGIT: the gradient of logit c) or onehot(c) - softmax(z) (HMP_WRT_LOGPROB: of log softmax(z)[c]; the softmax
+ * arithmetic of hmp_topk_rows).  EVERY element of d_gout [n_rows, ld_g] is written: columns at or past n_classes and rows outside
+ * the selection hold 0, so the buffer needs no memset.  ld >= n_classes, ld_g >= n_classes; no alignment is asked for. */
+int hmp_saliency_seed(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_target, int32_t sel_mode,
+                      const uint8_t* d_mask, int32_t ordinal, const int64_t* d_graph_ptr, int32_t n_graphs, int32_t wrt,
+                      float* d_gout, int32_t ld_g, void* stream);
+/* An input gradient d_g [n_rows, ld_g] reduced against its input d_x [n_rows, ld_x] over the n_features real columns, per row:
+ *   d_gxi [n_rows]              sum_f g * x          (signed gradient x input)
+ *   d_gnorm [n_rows]            sqrt(sum_f g^2)
+ *   d_groups [n_rows, n_groups] sum of g * x over the columns [lo[i], hi[i]) clipped to [0, n_features); lo >= hi: 0
+ * with 0 <= n_groups <= 4 and lo / hi HOST arrays.  Any output may be NULL; what one output holds does not depend on which others
+ * were requested.  One wavefront per row, fp32 sums in a fixed order: a rerun gives the same bits.  No alignment is asked for. */
+int hmp_saliency_scores(const float* d_g, int32_t ld_g, const float* d_x, int32_t ld_x, int32_t n_rows, int32_t n_features,
+                        int32_t n_groups, const int32_t* lo, const int32_t* hi, float* d_gxi, float* d_gnorm, float* d_groups,
+                        void* stream);
+/* For every selected destination row of `plan`, the k sources (1 <= k <= 8) with the largest |d_score[source]|, descending, equal
+ * magnitudes by ascending source index; a source reached by several edges is listed once.  d_top_src [n_dst, k] int64 and
+ * d_top_score [n_dst, k] float (the SIGNED score); columns past a row's sources hold -1 / 0; either may be NULL.  Rows outside the
+ * selection are left untouched, so repeated HMP_SEL_ORDINAL launches fill one output.  d_score has plan.n_src entries. */
+int hmp_saliency_topk(hmp_plan plan, const float* d_score, int32_t k, int32_t sel_mode, const uint8_t* d_mask, int32_t ordinal,
+                      const int64_t* d_graph_ptr, int32_t n_graphs, int64_t* d_top_src, float* d_top_score, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 5. loss + optimiser
@@ -637,6 +676,24 @@ int hmp_net_topk_heads(hmp_net* net, const hmp_batch* batch, const float* d_para
 int hmp_net_attention(hmp_net* net, const hmp_batch* batch, const float* d_params, int32_t layer,
                       float* const d_alpha[HMP_MAX_EDGE_TYPES], int32_t k, int64_t* const d_top_src[HMP_MAX_EDGE_TYPES],
                       float* const d_top_w[HMP_MAX_EDGE_TYPES], void* stream);
+/* Input gradients of a bound net: the eval-mode forward of `batch` (the predict entries' forward), hmp_saliency_seed over the output
+ * rows of `head` into the workspace, then the backward chain WITHOUT the weight gradients down to
+ *   d_gx[t] [n_nodes[t], batch->ldx[t]]  =  d (sum over the selected output rows of logit_c or log softmax_c) / d x[t]
+ * for every node type t with a non-NULL slot (the real in-dim columns are written; NULL slots are skipped).  head 0: the readout
+ * (the pooled rows of a net with pool_edge_type); head 1: the second output of a net with aux_readout_type.  The outputs of such a
+ * two-headed net are tail_act(final state), and the gradient chains through that activation.  d_target (NULL: the prediction),
+ * the row selection and wrt are hmp_saliency_seed's, over the head's output rows.  No allocation, no synchronisation; overwrites
+ * the activations of any earlier forward.  Refused with HMP_E_ARG before anything runs: bf16 compute mode, nets with learned
+ * linear heads (hmp_net_set_linear_heads), two-headed nets with pooled heads, a head the net does not have, a d_gx slot of a
+ * node type without input rows.  A program with aggregate-first convs (large batches) needs ldx[t] % 4 == 0 for a type whose
+ * only live layer-0 conv is aggregate-first.  (ABI-4-compatible addition.) */
+int hmp_net_input_gradient(hmp_net* net, const hmp_batch* batch, const float* d_params, int32_t head, const int64_t* d_target,
+                           int32_t sel_mode, const uint8_t* d_mask, int32_t ordinal, const int64_t* d_graph_ptr, int32_t n_graphs,
+                           int32_t wrt, float* const d_gx[HMP_MAX_NODE_TYPES], void* stream);
+/* The plan of `edge_type` as the last forward / step / predict / input-gradient call of the net built it from batch->d_edge_index
+ * (CSR by destination, CSC by source; hmp_saliency_topk ranks over it).  Valid until the next such call or workspace re-bind.
+ * (ABI-4-compatible addition.) */
+int hmp_net_plan(hmp_net* net, int32_t edge_type, hmp_plan* out);
 /* diagnosis / tests: where the last forward left the output of layer `layer` (1 .. n_layers) for `node_type`: rows [n_rows, width]
  * at pitch *ld elements, fp32 or (*is_bf16) bfloat16.  A dropped element (training-mode dropout) is stored as -0: its sign bit
  * is the keep-mask the backward reads.  Valid until the next forward / step / workspace re-bind. */
