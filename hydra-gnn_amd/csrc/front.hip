@@ -217,23 +217,28 @@ __global__ __launch_bounds__(1024) void front_kernel(const FrontArgs a) {
     const int pb = blk - a.gemm_blocks;
     int jd = 0;
     while (jd + 1 < 2 * a.n_jobs && pb >= a.part_start[jd + 1]) ++jd;
-    const FrontJob& F = a.job[jd >> 1];
     int* wsi = reinterpret_cast<int*>(a.ws);
-    PlanJob J;
-    J.ei = F.ei; J.E = F.E; J.n_src = F.n_src; J.n_dst = F.n_dst;
-    J.rowptr = wsi + F.rowptr; J.col = wsi + F.col; J.eid = wsi + F.eid;
-    J.t_rowptr = wsi + F.t_rowptr; J.t_col = wsi + F.t_col; J.t_pos = nullptr;
-    J.degf = reinterpret_cast<float*>(wsi + F.degf);
-    J.gp_dst = F.gp_dst; J.gp_src = F.gp_src; J.gp_edge = F.gp_edge; J.n_graphs = F.n_graphs;
-    J.cnt_in = J.cnt_out = J.cur_in = J.cur_out = nullptr;
-    J.tmpc_in = J.tmpc_out = nullptr;
-    J.tmp_in = wsi + F.tmp_in; J.tmp_out = wsi + F.tmp_out; J.t_eid = wsi + F.t_eid; J.pos_of_eid = wsi + F.pos_of_eid;
+    auto job = [&]() {
+      const FrontJob& F = a.job[jd >> 1];
+      PlanJob J;
+      J.ei = F.ei; J.E = F.E; J.n_src = F.n_src; J.n_dst = F.n_dst;
+      J.rowptr = wsi + F.rowptr; J.col = wsi + F.col; J.eid = wsi + F.eid;
+      J.t_rowptr = wsi + F.t_rowptr; J.t_col = wsi + F.t_col; J.t_pos = nullptr;
+      J.degf = reinterpret_cast<float*>(wsi + F.degf);
+      J.gp_dst = F.gp_dst; J.gp_src = F.gp_src; J.gp_edge = F.gp_edge; J.n_graphs = F.n_graphs;
+      J.cnt_in = J.cnt_out = J.cur_in = J.cur_out = nullptr;
+      J.tmpc_in = J.tmpc_out = nullptr;
+      J.flags = wsi + F.flags;
+      J.tmp_in = wsi + F.tmp_in; J.tmp_out = wsi + F.tmp_out; J.t_eid = wsi + F.t_eid; J.pos_of_eid = wsi + F.pos_of_eid;
+      return J;
+    };
 #ifdef HMP_KTIME
     if (threadIdx.x == 0 && pb == 0) front_kt_ei = a.job[0].ei;
 #endif
-    const bool last = pb + 1 == a.part_start[jd + 1];
-    if (a.plan_rc) plan_small_part<true>(J, jd & 1, pb - a.part_start[jd], a.rows_per_part[jd], last, a.need_tpos, a.status, lds);
-    else plan_small_part<false>(J, jd & 1, pb - a.part_start[jd], a.rows_per_part[jd], last, a.need_tpos, a.status, lds);
+    const int n_parts = a.part_start[jd + 1] - a.part_start[jd];
+    const bool again = a.plan_rc ? plan_small_part<true>(job(), jd & 1, pb - a.part_start[jd], a.rows_per_part[jd], n_parts, a.need_tpos, a.status, lds)
+                                 : plan_small_part<false>(job(), jd & 1, pb - a.part_start[jd], a.rows_per_part[jd], n_parts, a.need_tpos, a.status, lds);
+    if (again) plan_small_again(job(), jd & 1, a.need_tpos, lds);  // (the job is read from the argument block again: nothing of it lives across the part)
     return;
   }
   // pack role: 16 items per block; the block -> (segment, first item) map is a static device table

@@ -180,7 +180,7 @@ struct FrontProb {   // C[M, N] = A[M, K] * B^T
 struct FrontJob {    // one edge type of the plan; arrays as 4-byte-word offsets from the workspace base
   const int64_t* ei;
   int E, n_src, n_dst;
-  uint32_t rowptr, col, eid, t_rowptr, t_col, t_eid, tmp_in, tmp_out, pos_of_eid, degf;
+  uint32_t rowptr, col, eid, t_rowptr, t_col, t_eid, tmp_in, tmp_out, pos_of_eid, degf, flags;
   const int64_t *gp_dst, *gp_src, *gp_edge;  // as PlanJob
   int n_graphs;
 };
@@ -242,7 +242,9 @@ struct PlanJob {
   int *cnt_in, *cnt_out, *cur_in, *cur_out;  // must be zero on entry (one contiguous block); left zero on exit
   int* flags;  // multi-launch build: [0] / [1] = PlanBatch::build_id of the last build that found the list NOT ordered by destination /
                // source (or holding an invalid edge); part of the zeroed block.  An edge list that arrives ordered by destination --
-               // what graph builders emit -- IS its CSR (position = edge id): no scatter, no rank pass for that direction
+               // what graph builders emit -- IS its CSR (position = edge id): no scatter, no rank pass for that direction.
+               // Single-launch build of a graph-sorted list: [32 + 2 * dir] / [33 + 2 * dir] count the parts of a direction that
+               // have arrived / that dropped an edge (plan_small_part); zero on entry, left zero
   int *tmp_in, *tmp_out, *t_eid, *pos_of_eid;
   int *tmpc_in, *tmpc_out;  // multi-launch build: the other endpoint of every scratch slot
 };

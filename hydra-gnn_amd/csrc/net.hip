@@ -1012,7 +1012,7 @@ bool build_front(hmp_net* n, const hmp_batch* b, const float* d_params, FrontArg
     F.ei = J.ei; F.E = (int)J.E; F.n_src = J.n_src; F.n_dst = J.n_dst;
     F.rowptr = woff(J.rowptr); F.col = woff(J.col); F.eid = woff(J.eid);
     F.t_rowptr = woff(J.t_rowptr); F.t_col = woff(J.t_col); F.t_eid = woff(J.t_eid);
-    F.tmp_in = woff(J.tmp_in); F.tmp_out = woff(J.tmp_out); F.pos_of_eid = woff(J.pos_of_eid); F.degf = woff(J.degf);
+    F.tmp_in = woff(J.tmp_in); F.tmp_out = woff(J.tmp_out); F.pos_of_eid = woff(J.pos_of_eid); F.degf = woff(J.degf); F.flags = woff(J.flags);
     F.gp_dst = J.gp_dst; F.gp_src = J.gp_src; F.gp_edge = J.gp_edge; F.n_graphs = J.n_graphs;
   }
   fa.status = &n->d_state->status;

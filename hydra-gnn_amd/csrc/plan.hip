@@ -339,7 +339,11 @@ __global__ __launch_bounds__(256) void plan_link_kernel(const PlanBatch pb) {
     const int j = find_job(pb.edge_start, pb.n, g);
     const PlanJob& J = pb.j[j];
     const int64_t k = g - pb.edge_start[j];
-    if (k < J.t_rowptr[J.n_src]) J.t_pos[k] = J.pos_of_eid[J.t_eid[k]];
+    if (k >= J.t_rowptr[J.n_src]) continue;
+    // (a single-launch build of a list that is not graph-sorted as vouched for -- status bit 2 -- leaves CSC slots unwritten: what
+    // they hold is scratch content, never an index to follow)
+    const int64_t e = J.t_eid[k];
+    if (e >= 0 && e < J.E) J.t_pos[k] = J.pos_of_eid[e];
   }
 }
 
@@ -446,17 +450,21 @@ int plan_launch(PlanBatch& pb, int* d_status, hipStream_t st) {
     if (blocks > 0) hipLaunchKernelGGL(plan_scan_final_kernel, dim3(blocks), dim3(1024), 0, st, pb, sg);
     HMP_LAUNCH_CHECK();
   }
+  bool owes_degf = false;  // a call without a single edge still owes degf = 1 for every destination row: the rank pass writes it
+  for (int j = 0; j < pb.n; ++j) owes_degf = owes_degf || (pb.j[j].degf != nullptr && pb.j[j].n_dst > 0);
   if (E > 0) {
     hipLaunchKernelGGL(plan_fill_kernel, dim3(eg), dim3(256), 0, st, pb);
     HMP_LAUNCH_CHECK();
+  }
+  if (E > 0 || owes_degf) {
     const int64_t want = cdiv(rows, 16);  // 16 rows per block and trip
     const int rg = (int)(want < 1 ? 1 : (want > 8192 ? 8192 : want));
     hipLaunchKernelGGL(plan_rank_kernel, dim3(rg), dim3(256), 0, st, pb);
     HMP_LAUNCH_CHECK();
-    if (pb.need_tpos) {
-      hipLaunchKernelGGL(plan_link_kernel, dim3(eg), dim3(256), 0, st, pb);
-      HMP_LAUNCH_CHECK();
-    }
+  }
+  if (E > 0 && pb.need_tpos) {
+    hipLaunchKernelGGL(plan_link_kernel, dim3(eg), dim3(256), 0, st, pb);
+    HMP_LAUNCH_CHECK();
   }
   return HMP_OK;
 }
@@ -467,24 +475,47 @@ extern "C" size_t hmp_plan_scratch_bytes(int64_t n_edges, int32_t n_src, int32_t
   return hmp::plan_scratch_ints(n_edges, n_src, n_dst) * sizeof(int);
 }
 
-extern "C" int hmp_plan_build(const int64_t* d_edge_index, hmp_plan plan, void* d_scratch, int32_t* d_status, void* stream) {
+// the builder as the executor calls it: every job is copied as it stands into one PlanBatch and handed to plan_launch
+extern "C" int hmp_plan_build_many(const hmp_plan_job* jobs, int32_t n, int32_t need_tpos, int32_t clear_first, int32_t* d_status,
+                                   void* stream) {
   using namespace hmp;
-  HMP_CHECK_ARG(plan.d_rowptr && plan.d_t_rowptr, "hmp_plan_build: null rowptr");
-  HMP_CHECK_ARG(plan.n_edges == 0 || (plan.d_col && plan.d_eid && plan.d_t_col && plan.d_t_pos && d_scratch),
-                "hmp_plan_build: null output/scratch with E > 0");
+  HMP_CHECK_ARG(n >= 0 && n <= HMP_MAX_EDGE_TYPES, "hmp_plan_build_many: %d jobs", n);
+  HMP_CHECK_ARG(n == 0 || jobs != nullptr, "hmp_plan_build_many: null jobs");
   PlanBatch pb;
   memset(&pb, 0, sizeof(pb));
-  pb.n = 1;
-  pb.need_tpos = 1;
-  pb.clear_first = 1;
-  PlanJob& J = pb.j[0];
-  J.ei = d_edge_index;
-  J.E = plan.n_edges;
-  J.n_src = plan.n_src;
-  J.n_dst = plan.n_dst;
-  J.rowptr = plan.d_rowptr; J.col = plan.d_col; J.eid = plan.d_eid;
-  J.t_rowptr = plan.d_t_rowptr; J.t_col = plan.d_t_col; J.t_pos = plan.d_t_pos;
-  HMP_CHECK_ARG(d_scratch != nullptr, "hmp_plan_build: scratch required");
-  plan_carve(J, (int*)d_scratch);
+  pb.n = n;
+  pb.need_tpos = need_tpos != 0;
+  pb.clear_first = clear_first != 0;
+  for (int j = 0; j < n; ++j) {
+    const hmp_plan_job& in = jobs[j];
+    const hmp_plan& plan = in.plan;
+    HMP_CHECK_ARG(in.d_scratch != nullptr, "hmp_plan_build_many: job %d: scratch required", j);
+    HMP_CHECK_ARG(plan.d_rowptr && plan.d_t_rowptr, "hmp_plan_build_many: job %d: null rowptr", j);
+    HMP_CHECK_ARG(plan.n_edges <= 0 || (plan.d_col && plan.d_eid && plan.d_t_col && plan.d_t_pos),
+                  "hmp_plan_build_many: job %d: null output with E > 0", j);
+    const int given = (in.d_dst_ptr != nullptr) + (in.d_src_ptr != nullptr) + (in.d_edge_ptr != nullptr);
+    HMP_CHECK_ARG(given == 0 || given == 3, "hmp_plan_build_many: job %d: %d of the three graph offset arrays", j, given);
+    HMP_CHECK_ARG(given == 0 || in.n_graphs >= 0, "hmp_plan_build_many: job %d: n_graphs %d", j, in.n_graphs);
+    PlanJob& J = pb.j[j];
+    J.ei = in.d_edge_index;
+    J.E = plan.n_edges;
+    J.n_src = plan.n_src;
+    J.n_dst = plan.n_dst;
+    J.rowptr = plan.d_rowptr; J.col = plan.d_col; J.eid = plan.d_eid;
+    J.t_rowptr = plan.d_t_rowptr; J.t_col = plan.d_t_col; J.t_pos = plan.d_t_pos;
+    J.degf = in.d_degf;
+    J.gp_dst = in.d_dst_ptr; J.gp_src = in.d_src_ptr; J.gp_edge = in.d_edge_ptr;
+    J.n_graphs = given ? in.n_graphs : 0;
+    plan_carve(J, (int*)in.d_scratch);
+  }
   return plan_launch(pb, d_status, (hipStream_t)stream);
+}
+
+extern "C" int hmp_plan_build(const int64_t* d_edge_index, hmp_plan plan, void* d_scratch, int32_t* d_status, void* stream) {
+  hmp_plan_job job;
+  memset(&job, 0, sizeof(job));
+  job.d_edge_index = d_edge_index;
+  job.plan = plan;
+  job.d_scratch = d_scratch;
+  return hmp_plan_build_many(&job, 1, 1, 1, d_status, stream);
 }

@@ -42,6 +42,7 @@ size_t hmp_sizeof(int which) {
     case 13: return sizeof(hmp_epoch_seg);
     case 14: return sizeof(hmp_tail_desc);
     case 15: return sizeof(hmp_linear_heads_desc);
+    case 16: return sizeof(hmp_plan_job);
     default: return 0;
   }
 }

@@ -161,8 +161,16 @@ class LinearHeadsDesc(C.Structure):
     ]
 
 
+class PlanJob(C.Structure):
+    _fields_ = [
+        ("d_edge_index", C.c_void_p), ("plan", Plan), ("d_degf", C.c_void_p),
+        ("d_dst_ptr", C.c_void_p), ("d_src_ptr", C.c_void_p), ("d_edge_ptr", C.c_void_p),
+        ("n_graphs", C.c_int32), ("d_scratch", C.c_void_p),
+    ]
+
+
 _STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc,
-            EpochCtl, EpochRow, EpochSeg, TailDesc, LinearHeadsDesc]
+            EpochCtl, EpochRow, EpochSeg, TailDesc, LinearHeadsDesc, PlanJob]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -175,6 +183,7 @@ SIGNATURES = {
     "hmp_device_count": (C.c_int, []),
     "hmp_plan_scratch_bytes": (C.c_size_t, [_I64, _I32, _I32]),
     "hmp_plan_build": (C.c_int, [_VP, Plan, _VP, _VP, _VP]),
+    "hmp_plan_build_many": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "hmp_segment_mean_fwd": (C.c_int, [_VP, _I32, _I32, Plan, _VP, _I32, _VP]),
     "hmp_segment_mean_bwd": (C.c_int, [_VP, _I32, _I32, Plan, _VP, _I32, _VP]),
     "hmp_gemm_f32": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _I32, _I32, _I32, _VP]),

@@ -62,7 +62,10 @@ extern "C" {
  *    of a forward): new entries, no struct was added or changed layout;
  *    hmp_saliency_seed / hmp_saliency_scores / hmp_saliency_topk / hmp_net_input_gradient / hmp_net_plan (gradient saliency: the gradient of a
  *    chosen class's logit or log-probability with respect to the input features, and its reductions): new entries, no struct was
- *    added or changed layout */
+ *    added or changed layout;
+ *    hmp_plan_job (hmp_sizeof 16), hmp_plan_build_many: unit-test entry of the plan builder as the executor calls it (several edge
+ *    types per call, need_tpos, clear_first, degf, graph offsets); hmp_plan_build is its one-job call.  A new entry and a new
+ *    struct, nothing above changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -84,8 +87,8 @@ int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
  * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets, 10 hmp_gemm_desc,
- * 11 hmp_epoch_ctl, 12 hmp_epoch_row, 13 hmp_epoch_seg, 14 hmp_tail_desc, 15 hmp_linear_heads_desc (lets a foreign-language
- * binding verify its struct mirror) */
+ * 11 hmp_epoch_ctl, 12 hmp_epoch_row, 13 hmp_epoch_seg, 14 hmp_tail_desc, 15 hmp_linear_heads_desc, 16 hmp_plan_job (lets a
+ * foreign-language binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -111,8 +114,35 @@ typedef struct hmp_plan {
 /* bytes of scratch hmp_plan_build needs for E edges between n_src and n_dst nodes */
 size_t hmp_plan_scratch_bytes(int64_t n_edges, int32_t n_src, int32_t n_dst);
 /* d_edge_index: int64 [2][E] (row stride = E).  Out-of-range endpoints set bit 0 of *d_status
- * (int32, device, may be NULL) and the edge is dropped from the lists (its slot keeps eid = -1). */
+ * (int32, device, may be NULL) and the edge is dropped from the lists: rowptr[n_dst] = t_rowptr[n_src] = the number of edges kept,
+ * and the entries of col / eid / t_col / t_pos at and after that count are unspecified. */
 int hmp_plan_build(const int64_t* d_edge_index, hmp_plan plan, void* d_scratch, int32_t* d_status, void* stream);
+
+/* Unit-test entry of the builder as the network executor calls it (ABI-4-compatible addition, hmp_sizeof 16): n edge types in one
+ * call, each job copied as it stands; hmp_plan_build is the call with n = 1, need_tpos = 1, clear_first = 1.
+ *   d_degf       optional [n_dst] float: 1 / max(in-degree, 1)
+ *   d_dst_ptr, d_src_ptr, d_edge_ptr   optional, all three or none: int64 [n_graphs + 1] row offsets of the destination / source
+ *                node type and edge offsets of a batch whose edges are listed graph by graph (what hmp_batch::d_node_ptr and
+ *                d_edge_ptr vouch for).  Only the single-launch build reads them; offsets that do not describe the list (an edge
+ *                with an in-range endpoint outside its graph's rows, edges in a graph without rows for them, last offsets that are
+ *                not the row / edge counts) set status bit 2 (value 4) and leave the arrays unspecified, though every access of
+ *                the build stays inside the arrays.  An edge with an endpoint out of range breaks no vouching: it is dropped as
+ *                above, and the arrays are those of the same call without offsets.
+ *   d_scratch    hmp_plan_scratch_bytes(E, n_src, n_dst) bytes per job.  Its first 2 * a(n_dst) + 2 * a(n_src) ints (a rounds up to
+ *                64) are counters, zero on entry and left zero on exit; the 64 ints behind them are zero before the first build
+ *                and hold what builds leave there afterwards.  clear_first != 0 zeroes all of these before the build.
+ *   need_tpos    0: d_t_pos is left untouched.
+ * Refused (HMP_E_ARG): n outside 0..HMP_MAX_EDGE_TYPES, null jobs with n > 0, a null scratch, a null output array with E > 0, one
+ * or two of the three offset arrays without the rest. */
+typedef struct hmp_plan_job {
+  const int64_t* d_edge_index;   /* [2][E] */
+  hmp_plan plan;                 /* sizes + output arrays */
+  float* d_degf;                 /* optional [n_dst] */
+  const int64_t *d_dst_ptr, *d_src_ptr, *d_edge_ptr;  /* optional, all three or none: [n_graphs + 1] */
+  int32_t n_graphs;
+  void* d_scratch;               /* hmp_plan_scratch_bytes(E, n_src, n_dst) */
+} hmp_plan_job;
+int hmp_plan_build_many(const hmp_plan_job* jobs, int32_t n, int32_t need_tpos, int32_t clear_first, int32_t* d_status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 2. K1 -- segment mean over CSR rows (SAGE neighbour mean, LeafPool).
