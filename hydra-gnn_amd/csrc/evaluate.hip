@@ -157,6 +157,19 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   }
 }
 
+// ---- launch: one workgroup per EV_RPB rows up to the grid cap; VEC iff every row can be read by 16-byte loads
+int ev_blocks(int n_rows) { return cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS; }
+bool ev_vec(const float* x, int ld) { return (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
+
+// launch(grid, std::bool_constant<VEC>) starts the kernel's VEC instantiation
+template <class F>
+int ev_launch(const float* x, int ld, int n_rows, F&& launch) {
+  if (ev_vec(x, ld)) launch(dim3(ev_blocks(n_rows)), std::true_type());
+  else launch(dim3(ev_blocks(n_rows)), std::false_type());
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 }  // namespace
 
 int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int k, int64_t* labels, float* probs,
@@ -165,24 +178,18 @@ int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const ui
   HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "topk_rows: k = %d (1 .. %d)", k, TOPK_MAX);
   if (n_rows == 0) return HMP_OK;
   HMP_CHECK_ARG(x && (labels || probs), "topk_rows: null logits or no output");
-  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
-  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (vec) hipLaunchKernelGGL((topk_rows_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
-  else hipLaunchKernelGGL((topk_rows_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
+    hipLaunchKernelGGL((topk_rows_kernel<vec()>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
+  });
 }
 
 int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st) {
   HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "predict_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
   if (n_rows == 0) return HMP_OK;
   HMP_CHECK_ARG(x && pred, "predict_rows: null logits or output");
-  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
-  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (vec) hipLaunchKernelGGL((predict_rows_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, pred);
-  else hipLaunchKernelGGL((predict_rows_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, members, pred);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
+    hipLaunchKernelGGL((predict_rows_kernel<vec()>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, members, pred);
+  });
 }
 
 int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
@@ -192,17 +199,11 @@ int count_rows_by_graph_launch(const float* x, int ld, int n_rows, int n_classes
   if (n_rows == 0) return HMP_OK;
   HMP_CHECK_ARG(n_graphs >= 1, "count_rows_by_graph: %d rows and no graph", n_rows);
   HMP_CHECK_ARG(x && labels && counts && graph_ptr, "count_rows_by_graph: null logits, labels, offsets or counts");
-  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
-  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   auto* c = reinterpret_cast<unsigned long long*>(counts);
-  if (vec)
-    hipLaunchKernelGGL((count_rows_by_graph_kernel<true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored,
+  return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
+    hipLaunchKernelGGL((count_rows_by_graph_kernel<vec()>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored,
                        graph_ptr, n_graphs, c);
-  else
-    hipLaunchKernelGGL((count_rows_by_graph_kernel<false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored,
-                       graph_ptr, n_graphs, c);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  });
 }
 
 int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const int64_t* labels, const uint8_t* members,
@@ -210,21 +211,13 @@ int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const i
   HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "count_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
   if (n_rows == 0) return HMP_OK;
   HMP_CHECK_ARG(x && labels && counts, "count_rows: null logits, labels or counts");
-  const int blocks = cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS;
-  const bool vec = (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   const bool hist = confusion && n_classes <= EV_HIST_MAX;
   auto* c = reinterpret_cast<unsigned long long*>(counts);
   auto* m = reinterpret_cast<unsigned long long*>(confusion);
-  if (vec && hist)
-    hipLaunchKernelGGL((count_rows_kernel<true, true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
-  else if (vec)
-    hipLaunchKernelGGL((count_rows_kernel<true, false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
-  else if (hist)
-    hipLaunchKernelGGL((count_rows_kernel<false, true>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
-  else
-    hipLaunchKernelGGL((count_rows_kernel<false, false>), dim3(blocks), dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
+    if (hist) hipLaunchKernelGGL((count_rows_kernel<vec(), true>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
+    else hipLaunchKernelGGL((count_rows_kernel<vec(), false>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, labels, members, ignored, c, m);
+  });
 }
 
 }  // namespace hmp

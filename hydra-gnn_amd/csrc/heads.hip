@@ -280,29 +280,30 @@ int heads_blocks(int n_rows) {
   return tiles < HEAD_MAX_BLOCKS ? tiles : HEAD_MAX_BLOCKS;
 }
 
+// the launch of every mode: a workgroup per row tile up to the cap, walking n_tiles; only the training launch drops
+template <HeadMode MODE>
+static int heads_launch(LinHeadArgs& a, hipStream_t st) {
+  a.n_tiles = cdiv(a.n_rows, HL_RB);
+  if (MODE != HL_TRAIN) a.drop_on = 0;
+  const int blocks = heads_blocks(a.n_rows);
+  if (blocks == 0) return HMP_OK;
+  hipLaunchKernelGGL(linear_heads_kernel<MODE>, dim3(blocks), dim3(256), 0, st, a);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st) {
   HMP_TRY(heads_check(a));
   // the kernel walks the gradient's columns by LDS chunk up to roundup(F, HL_FC): a wider ldg would leave columns unwritten
   HMP_CHECK_ARG(a.ldg == align4(a.F), "linear heads: gradient ld %d (F = %d rounded up to 4: %d)", a.ldg, a.F, align4(a.F));
   HMP_CHECK_ARG(a.ld_slab >= a.F && a.slab_stride >= (int64_t)a.K * (a.ld_slab + 1), "linear heads: slab layout");
-  a.n_tiles = cdiv(a.n_rows, HL_RB);
-  const int blocks = heads_blocks(a.n_rows);
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<HL_TRAIN>, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return heads_launch<HL_TRAIN>(a, st);
 }
 
 int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st) {
   HMP_TRY(heads_check(a));
-  a.n_tiles = cdiv(a.n_rows, HL_RB);
   a.counts = reinterpret_cast<unsigned long long*>(counts);
-  a.drop_on = 0;
-  const int blocks = heads_blocks(a.n_rows);
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<HL_COUNT>, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return heads_launch<HL_COUNT>(a, st);
 }
 
 // pred[h][row] = argmax of head h's logits on act(z) for the head's rows, -1 elsewhere (eval mode; pred[h] null: head skipped).
@@ -310,14 +311,8 @@ int linear_heads_count_launch(LinHeadArgs& a, long long* counts, hipStream_t st)
 int linear_heads_predict_launch(LinHeadArgs& a, int64_t* const* pred, hipStream_t st) {
   HMP_CHECK_ARG(pred != nullptr, "linear heads: null output array");
   HMP_TRY(heads_check(a, false));
-  a.n_tiles = cdiv(a.n_rows, HL_RB);
   a.pred[0] = pred[0]; a.pred[1] = pred[1];
-  a.drop_on = 0;
-  const int blocks = heads_blocks(a.n_rows);
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<HL_PREDICT>, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return heads_launch<HL_PREDICT>(a, st);
 }
 
 // labels[h][row][0:k) / probs[h][row][0:k) = the k largest logits of head h on act(z) and their softmax probabilities for the head's
@@ -326,18 +321,12 @@ int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, floa
   HMP_CHECK_ARG(labels != nullptr && probs != nullptr, "linear heads: null output array");
   HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "linear heads: k = %d (1 .. %d)", k, TOPK_MAX);
   HMP_TRY(heads_check(a, false));
-  a.n_tiles = cdiv(a.n_rows, HL_RB);
   for (int h = 0; h < 2; ++h) {
     a.tk_labels[h] = labels[h];
     a.tk_probs[h] = probs[h];
   }
   a.topk = k;
-  a.drop_on = 0;
-  const int blocks = heads_blocks(a.n_rows);
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(linear_heads_kernel<HL_TOPK>, dim3(blocks), dim3(256), 0, st, a);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  return heads_launch<HL_TOPK>(a, st);
 }
 
 }  // namespace hmp

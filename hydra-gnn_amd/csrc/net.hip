@@ -2002,6 +2002,25 @@ void add_pool(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int he
   if (T.drop_on) T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + t));
 }
 
+// The two heads' rows for one tail launch (semisup.hip): an entry for every wanted head that has rows, pooled or not as the net is.
+// tg null: no labels and no masks (predict, top-k).  slot[h] = the entry of head h, -1 where it got none.
+TailArgs tail_rows(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, bool ce, int64_t ignored, const bool want[2],
+                   int slot[2]) {
+  static const hmp_head_targets none = {};
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.act = n->spec.tail_act; ta.ignored = ignored; ta.state = n->d_state;
+  for (int h = 0; h < 2; ++h) {
+    slot[h] = -1;
+    if (!want[h]) continue;
+    const int before = ta.n;
+    if (n->has_pools) add_pool(n, b, tg ? tg : &none, h, ce, ta);
+    else add_tail(n, b, tg ? tg : &none, h, ce, ta);
+    if (ta.n > before) slot[h] = before;
+  }
+  return ta;
+}
+
 LinHeadArgs heads_args(hmp_net* n, const hmp_batch* b, const hmp_linear_head_targets* tg, const float* d_params, bool train,
                        int64_t ignored) {
   const hmp_net_spec& S = n->spec;
@@ -2043,20 +2062,17 @@ int ce_loss(hmp_net* n, const hmp_batch* b, int64_t ignored, hipStream_t st, con
 int two_head_loss(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int64_t ignored, hipStream_t st, const float*& g,
                   int& ldg) {
   StepCall& c = n->call;
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = n->spec.tail_act; ta.ignored = ignored; ta.state = n->d_state;
+  const bool want[2] = {n->has_pools || !c.tail_done[0], n->has_pools || !c.tail_done[1]};
+  int slot[2];
+  TailArgs ta = tail_rows(n, b, tg, true, ignored, want, slot);
   c.aux_g_ready = true;
   if (!n->has_pools) {
-    for (int h = 0; h < 2; ++h)
-      if (!c.tail_done[h]) add_tail(n, b, tg, h, true, ta);
     g = n->d_gout; ldg = n->out_ld;
     c.fin_rows = b->n_out + b->n_nodes[n->spec.aux_readout_type];
     if (ta.n == 0) return HMP_OK;
     Scope sc(n, KC_LOSS, st);
     return tail_ce_launch(ta, st);
   }
-  for (int h = 0; h < 2; ++h) add_pool(n, b, tg, h, true, ta);
   const int rt = n->spec.readout_type;
   g = n->G[n->L][rt]; ldg = n->ld[n->L][rt];
   c.fin_rows = b->n_nodes[label_type(n, 0)] + b->n_nodes[label_type(n, 1)];
@@ -2162,176 +2178,184 @@ extern "C" int hmp_net_step_heads_fused(hmp_net* n, const hmp_batch* batch, cons
   return run_step(n, batch, {nullptr, targets}, d_params, d_grads, d_m, d_v, args, stream);
 }
 
+// ---- the readout entries (count, predict, top-k): the eval-mode forward, then ONE launch over the final state.  Every entry checks
+// its arguments first -- a refused call launches nothing and leaves the last forward as it was -- and then states its launch.
+namespace {
+
+// the targets of a readout call in the net's form; predict and top-k have no labels (two: null, lin: the members alone)
+struct ReadoutTargets {
+  const hmp_head_targets* two = nullptr;
+  const hmp_linear_head_targets* lin = nullptr;
+  bool want[2] = {true, true};  // two heads: the heads the launch serves
+};
+
+// the final state in the net's readout form: the linear heads' arguments, the two heads' tail rows, or (neither filled) the output
+// rows out_ptr(n)
+struct Readout {
+  LinHeadArgs lin;
+  TailArgs ta;
+  int slot[2];  // head -> entry of ta, -1: none
+};
+
+template <class Launch>
+int run_readout(hmp_net* n, const hmp_batch* b, const float* d_params, const ReadoutTargets& tg, void* stream, Launch&& launch) {
+  hipStream_t st = (hipStream_t)stream;
+  HMP_TRY(plain_forward(n, b, d_params, st));
+  Readout r;
+  if (n->has_heads) {
+    r.lin = heads_args(n, b, tg.lin, d_params, false, 0);
+  } else if (n->spec.aux_readout_type >= 0) {
+    r.ta = tail_rows(n, b, tg.two, false, 0, tg.want, r.slot);
+    if (r.ta.n == 0) return HMP_OK;  // no wanted head has rows
+  }
+  Scope sc(n, KC_LOSS, st);
+  return launch(r, st);
+}
+
+// the guards on the net's kind; `instead` names the entries that serve the other kinds
+int check_single_head(const hmp_net* n, const char* who, const char* instead) {
+  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads, "%s: a two-headed net %s", who, instead);
+  return HMP_OK;
+}
+
+int check_tail_act(const hmp_net* n, const char* who) {
+  const int act = n->spec.tail_act;
+  HMP_CHECK_ARG(act >= HMP_ACT_NONE && act <= HMP_ACT_ELU, "%s: spec tail_act %d", who, act);
+  return HMP_OK;
+}
+
+int check_two_heads(const hmp_net* n, const char* who, const char* instead) {
+  HMP_CHECK_ARG(n->spec.aux_readout_type >= 0, "%s: the net has one output (aux_readout_type < 0): use %s", who, instead);
+  return check_tail_act(n, who);
+}
+
+int check_label_heads(const hmp_net* n, const char* who) {
+  HMP_CHECK_ARG(n->has_heads, "%s: the net has no linear heads (hmp_net_set_linear_heads)", who);
+  HMP_CHECK_ARG(!n->compute_bf16, "%s: the linear heads compute in fp32 (bf16 compute mode is not supported)", who);
+  return HMP_OK;
+}
+
+// the linear heads' targets of a label entry: the members alone
+hmp_linear_head_targets members_only(const uint8_t* const d_member[2]) {
+  hmp_linear_head_targets tg = {};
+  tg.d_member[0] = d_member[0]; tg.d_member[1] = d_member[1];
+  return tg;
+}
+
+long long* i64(int64_t* p) { return reinterpret_cast<long long*>(p); }
+
+}  // namespace
+
 extern "C" int hmp_net_count_correct2(hmp_net* n, const hmp_batch* batch, const hmp_head_targets* targets, const float* d_params,
                                       int64_t* d_counts, void* stream) {
   HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct2: null argument");
   HMP_TRY(check_targets(n, batch, targets, "hmp_net_count_correct2"));
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = n->spec.tail_act; ta.state = n->d_state;
-  for (int h = 0; h < 2; ++h) {
-    if (n->has_pools) add_pool(n, batch, targets, h, false, ta);
-    else add_tail(n, batch, targets, h, false, ta);
-  }
-  if (ta.n == 0) return HMP_OK;
-  Scope sc(n, KC_LOSS, st);
-  if (n->has_pools) return pool_tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
-  return tail_count_launch(ta, reinterpret_cast<long long*>(d_counts), st);
+  return run_readout(n, batch, d_params, {targets}, stream, [&](Readout& r, hipStream_t st) {
+    return n->has_pools ? pool_tail_count_launch(r.ta, i64(d_counts), st) : tail_count_launch(r.ta, i64(d_counts), st);
+  });
 }
 
 extern "C" int hmp_net_count_correct_heads(hmp_net* n, const hmp_batch* batch, const hmp_linear_head_targets* targets,
                                            const float* d_params, int64_t* d_counts, void* stream) {
   HMP_CHECK_ARG(n && batch && targets && d_params && d_counts, "hmp_net_count_correct_heads: null argument");
   HMP_TRY(check_heads(n, batch, targets, "hmp_net_count_correct_heads"));
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  LinHeadArgs a = heads_args(n, batch, targets, d_params, false, 0);
-  Scope sc(n, KC_LOSS, st);
-  return linear_heads_count_launch(a, reinterpret_cast<long long*>(d_counts), st);
+  return run_readout(n, batch, d_params, {nullptr, targets}, stream,
+                     [&](Readout& r, hipStream_t st) { return linear_heads_count_launch(r.lin, i64(d_counts), st); });
 }
 
 extern "C" int hmp_net_count_correct_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
                                            int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion, void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_counts, "hmp_net_count_correct_rooms: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
-                "hmp_net_count_correct_rooms: a two-headed net counts with hmp_net_count_correct2 / hmp_net_count_correct_heads");
+  HMP_TRY(check_single_head(n, "hmp_net_count_correct_rooms", "counts with hmp_net_count_correct2 / hmp_net_count_correct_heads"));
   HMP_CHECK_ARG(batch->n_out == 0 || batch->d_labels, "hmp_net_count_correct_rooms: the batch has no labels");
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  Scope sc(n, KC_LOSS, st);
-  return count_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
-                           reinterpret_cast<long long*>(d_counts), reinterpret_cast<long long*>(d_confusion), st);
+  return run_readout(n, batch, d_params, {}, stream, [&](Readout&, hipStream_t st) {
+    return count_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label, i64(d_counts),
+                             i64(d_confusion), st);
+  });
 }
 
 extern "C" int hmp_net_count_correct_rooms_by_graph(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
                                                     int64_t ignored_label, int64_t* d_counts, void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_counts, "hmp_net_count_correct_rooms_by_graph: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
-                "hmp_net_count_correct_rooms_by_graph: a two-headed net counts with hmp_net_count_correct2 / hmp_net_count_correct_heads");
+  HMP_TRY(check_single_head(n, "hmp_net_count_correct_rooms_by_graph", "counts with hmp_net_count_correct2 / hmp_net_count_correct_heads"));
   HMP_CHECK_ARG(batch->n_out == 0 || batch->d_labels, "hmp_net_count_correct_rooms_by_graph: the batch has no labels");
   const hmp_net_spec& S = n->spec;
   const int ot = S.pool_edge_type >= 0 ? S.edge_dst[S.pool_edge_type] : S.readout_type;  // the node type of the output rows
   HMP_CHECK_ARG(batch->n_out == 0 || (batch->n_graphs > 0 && batch->d_node_ptr[ot]),
                 "hmp_net_count_correct_rooms_by_graph: the batch carries no graph offsets of the output node type (n_graphs, d_node_ptr[%d])", ot);
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  Scope sc(n, KC_LOSS, st);
-  return count_rows_by_graph_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
-                                    batch->d_node_ptr[ot], batch->n_graphs, reinterpret_cast<long long*>(d_counts), st);
+  return run_readout(n, batch, d_params, {}, stream, [&](Readout&, hipStream_t st) {
+    return count_rows_by_graph_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, batch->d_labels, d_members, ignored_label,
+                                      batch->d_node_ptr[ot], batch->n_graphs, i64(d_counts), st);
+  });
 }
 
-// ---- label output: the eval-mode forward of the count entries, then ONE launch that stores the prediction they compare
+// ---- label output: the launch stores the prediction the count entries compare
 extern "C" int hmp_net_predict_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members,
                                      int64_t* d_pred, void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && (d_pred || batch->n_out == 0), "hmp_net_predict_rooms: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
-                "hmp_net_predict_rooms: a two-headed net predicts with hmp_net_predict2 / hmp_net_predict_heads");
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  Scope sc(n, KC_LOSS, st);
-  return predict_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, d_pred, st);
+  HMP_TRY(check_single_head(n, "hmp_net_predict_rooms", "predicts with hmp_net_predict2 / hmp_net_predict_heads"));
+  return run_readout(n, batch, d_params, {}, stream, [&](Readout&, hipStream_t st) {
+    return predict_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, d_pred, st);
+  });
 }
 
 extern "C" int hmp_net_predict2(hmp_net* n, const hmp_batch* batch, const float* d_params, int64_t* const d_pred[2], void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_pred, "hmp_net_predict2: null argument");
-  const hmp_net_spec& S = n->spec;
-  HMP_CHECK_ARG(S.aux_readout_type >= 0, "hmp_net_predict2: the net has one output (aux_readout_type < 0): use hmp_net_predict_rooms");
-  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU, "hmp_net_predict2: spec tail_act %d", S.tail_act);
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  hmp_head_targets none;
-  memset(&none, 0, sizeof(none));
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = S.tail_act; ta.state = n->d_state;
-  int64_t* pred[2] = {nullptr, nullptr};
-  for (int h = 0; h < 2; ++h) {
-    if (!d_pred[h]) continue;  // head skipped
-    const int before = ta.n;
-    if (n->has_pools) add_pool(n, batch, &none, h, false, ta);
-    else add_tail(n, batch, &none, h, false, ta);
-    if (ta.n > before) pred[before] = d_pred[h];
-  }
-  if (ta.n == 0) return HMP_OK;
-  Scope sc(n, KC_LOSS, st);
-  return tail_predict_launch(ta, pred, n->has_pools, st);
+  HMP_TRY(check_two_heads(n, "hmp_net_predict2", "hmp_net_predict_rooms"));
+  const ReadoutTargets tg = {nullptr, nullptr, {d_pred[0] != nullptr, d_pred[1] != nullptr}};  // a null output skips the head
+  return run_readout(n, batch, d_params, tg, stream, [&](Readout& r, hipStream_t st) {
+    int64_t* pred[2] = {nullptr, nullptr};
+    for (int h = 0; h < 2; ++h)
+      if (r.slot[h] >= 0) pred[r.slot[h]] = d_pred[h];
+    return tail_predict_launch(r.ta, pred, n->has_pools, st);
+  });
 }
 
 extern "C" int hmp_net_predict_heads(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2],
                                      int64_t* const d_pred[2], void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_member && d_pred, "hmp_net_predict_heads: null argument");
-  HMP_CHECK_ARG(n->has_heads, "hmp_net_predict_heads: the net has no linear heads (hmp_net_set_linear_heads)");
-  HMP_CHECK_ARG(!n->compute_bf16, "hmp_net_predict_heads: the linear heads compute in fp32 (bf16 compute mode is not supported)");
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  hmp_linear_head_targets tg;
-  memset(&tg, 0, sizeof(tg));
-  tg.d_member[0] = d_member[0]; tg.d_member[1] = d_member[1];
-  LinHeadArgs a = heads_args(n, batch, &tg, d_params, false, 0);
-  Scope sc(n, KC_LOSS, st);
-  return linear_heads_predict_launch(a, d_pred, st);
+  HMP_TRY(check_label_heads(n, "hmp_net_predict_heads"));
+  const hmp_linear_head_targets tg = members_only(d_member);
+  return run_readout(n, batch, d_params, {nullptr, &tg}, stream,
+                     [&](Readout& r, hipStream_t st) { return linear_heads_predict_launch(r.lin, d_pred, st); });
 }
 
-// ---- top-k labels with softmax probabilities: the forward of the predict entries, then ONE launch (tail_fns.h: topk_group).  k is
-// checked before the forward, so a refused call leaves the activations alone.
+// ---- top-k labels with softmax probabilities (tail_fns.h: topk_group).  k is checked before the forward, like everything else.
 #define HMP_CHECK_TOPK(who, k) HMP_CHECK_ARG((k) >= 1 && (k) <= TOPK_MAX, who ": k = %d (1 .. %d)", (int)(k), TOPK_MAX)
 
 extern "C" int hmp_net_topk_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, int32_t k,
                                   int64_t* d_labels, float* d_probs, void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && (d_labels || d_probs || batch->n_out == 0), "hmp_net_topk_rooms: null argument");
-  HMP_CHECK_ARG(n->spec.aux_readout_type < 0 && !n->has_heads,
-                "hmp_net_topk_rooms: a two-headed net takes hmp_net_topk2 / hmp_net_topk_heads");
+  HMP_TRY(check_single_head(n, "hmp_net_topk_rooms", "takes hmp_net_topk2 / hmp_net_topk_heads"));
   HMP_CHECK_TOPK("hmp_net_topk_rooms", k);
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  Scope sc(n, KC_LOSS, st);
-  return topk_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, k, d_labels, d_probs, st);
+  return run_readout(n, batch, d_params, {}, stream, [&](Readout&, hipStream_t st) {
+    return topk_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, k, d_labels, d_probs, st);
+  });
 }
 
 extern "C" int hmp_net_topk2(hmp_net* n, const hmp_batch* batch, const float* d_params, int32_t k, int64_t* const d_labels[2],
                              float* const d_probs[2], void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_labels && d_probs, "hmp_net_topk2: null argument");
-  const hmp_net_spec& S = n->spec;
-  HMP_CHECK_ARG(S.aux_readout_type >= 0, "hmp_net_topk2: the net has one output (aux_readout_type < 0): use hmp_net_topk_rooms");
-  HMP_CHECK_ARG(S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU, "hmp_net_topk2: spec tail_act %d", S.tail_act);
+  HMP_TRY(check_two_heads(n, "hmp_net_topk2", "hmp_net_topk_rooms"));
   HMP_CHECK_TOPK("hmp_net_topk2", k);
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  hmp_head_targets none;
-  memset(&none, 0, sizeof(none));
-  TailArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  ta.act = S.tail_act; ta.state = n->d_state;
-  int64_t* labels[2] = {nullptr, nullptr};
-  float* probs[2] = {nullptr, nullptr};
-  for (int h = 0; h < 2; ++h) {
-    if (!d_labels[h] && !d_probs[h]) continue;  // head skipped
-    const int before = ta.n;
-    if (n->has_pools) add_pool(n, batch, &none, h, false, ta);
-    else add_tail(n, batch, &none, h, false, ta);
-    if (ta.n > before) { labels[before] = d_labels[h]; probs[before] = d_probs[h]; }
-  }
-  if (ta.n == 0) return HMP_OK;
-  Scope sc(n, KC_LOSS, st);
-  return tail_topk_launch(ta, k, labels, probs, n->has_pools, st);
+  const ReadoutTargets tg = {nullptr, nullptr, {d_labels[0] || d_probs[0], d_labels[1] || d_probs[1]}};  // no output skips the head
+  return run_readout(n, batch, d_params, tg, stream, [&](Readout& r, hipStream_t st) {
+    int64_t* labels[2] = {nullptr, nullptr};
+    float* probs[2] = {nullptr, nullptr};
+    for (int h = 0; h < 2; ++h)
+      if (r.slot[h] >= 0) { labels[r.slot[h]] = d_labels[h]; probs[r.slot[h]] = d_probs[h]; }
+    return tail_topk_launch(r.ta, k, labels, probs, n->has_pools, st);
+  });
 }
 
 extern "C" int hmp_net_topk_heads(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], int32_t k,
                                   int64_t* const d_labels[2], float* const d_probs[2], void* stream) {
   HMP_CHECK_ARG(n && batch && d_params && d_member && d_labels && d_probs, "hmp_net_topk_heads: null argument");
-  HMP_CHECK_ARG(n->has_heads, "hmp_net_topk_heads: the net has no linear heads (hmp_net_set_linear_heads)");
-  HMP_CHECK_ARG(!n->compute_bf16, "hmp_net_topk_heads: the linear heads compute in fp32 (bf16 compute mode is not supported)");
+  HMP_TRY(check_label_heads(n, "hmp_net_topk_heads"));
   HMP_CHECK_TOPK("hmp_net_topk_heads", k);
-  hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, batch, d_params, st));
-  hmp_linear_head_targets tg;
-  memset(&tg, 0, sizeof(tg));
-  tg.d_member[0] = d_member[0]; tg.d_member[1] = d_member[1];
-  LinHeadArgs a = heads_args(n, batch, &tg, d_params, false, 0);
-  Scope sc(n, KC_LOSS, st);
-  return linear_heads_topk_launch(a, k, d_labels, d_probs, st);
+  const hmp_linear_head_targets tg = members_only(d_member);
+  return run_readout(n, batch, d_params, {nullptr, &tg}, stream,
+                     [&](Readout& r, hipStream_t st) { return linear_heads_topk_launch(r.lin, k, d_labels, d_probs, st); });
 }
 
 // ---- attention export: the eval-mode forward, then ONE launch that writes the coefficients of the requested convs of one GAT
@@ -2402,7 +2426,7 @@ extern "C" int hmp_net_input_gradient(hmp_net* n, const hmp_batch* batch, const 
                 "hmp_net_input_gradient: the mask selection needs a byte per output row");
   HMP_CHECK_ARG(sel_mode != SAL_SEL_ORDINAL || (d_graph_ptr && n_graphs >= 0 && ordinal >= 0),
                 "hmp_net_input_gradient: the ordinal selection needs graph_ptr, n_graphs >= 0 and ordinal >= 0");
-  HMP_CHECK_ARG(at < 0 || (S.tail_act >= HMP_ACT_NONE && S.tail_act <= HMP_ACT_ELU), "hmp_net_input_gradient: spec tail_act %d", S.tail_act);
+  if (at >= 0) HMP_TRY(check_tail_act(n, "hmp_net_input_gradient"));
   for (int t = 0; t < n->T; ++t)
     HMP_CHECK_ARG(!(n->pass0[t] && n->any_agg_first), "hmp_net_input_gradient: passthrough node types next to aggregate-first convs are not supported");
   for (int t = 0; t < n->T; ++t)

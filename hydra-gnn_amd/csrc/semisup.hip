@@ -249,12 +249,21 @@ int tail_layout(TailArgs& a, bool pool, bool leaf_rows, bool ce, int& blocks, bo
 }
 
 template <class... Extra>
-int tail_launch(void (*kernel)(TailArgs, Extra...), TailArgs& a, bool pool, bool leaf_rows, bool ce, hipStream_t st, Extra... extra) {
+int tail_launch(void (*kernel)(TailArgs, Extra...), TailArgs& a, bool pool, bool leaf_rows, bool ce, bool csc, hipStream_t st,
+                Extra... extra) {
   int blocks;
-  HMP_TRY(tail_layout(a, pool, leaf_rows, ce, blocks));
+  HMP_TRY(tail_layout(a, pool, leaf_rows, ce, blocks, csc));
   if (blocks == 0) return HMP_OK;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, a, extra...);
   HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+// the label launches: every entry has an output (has(i)) or no row to write
+template <class Has>
+int check_outputs(const TailArgs& a, bool pool, const char* what, Has has) {
+  for (int i = 0; i < a.n; ++i)
+    HMP_CHECK_ARG(has(i) || (pool ? a.h[i].n_pool : a.h[i].n_rows) == 0, "%s of entry %d", what, i);
   return HMP_OK;
 }
 
@@ -262,26 +271,20 @@ unsigned long long* u64(long long* p) { return reinterpret_cast<unsigned long lo
 
 }  // namespace
 
-int tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(tail_ce_kernel, a, false, true, true, st); }
-int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(tail_count_kernel, a, false, true, false, st, u64(counts)); }
-int pool_tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_ce_kernel, a, true, false, true, st); }
-int pool_tail_grad_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_grad_kernel, a, true, true, true, st); }
-int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(pool_count_kernel, a, true, false, false, st, u64(counts)); }
+int tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(tail_ce_kernel, a, false, true, true, true, st); }
+int tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(tail_count_kernel, a, false, true, false, true, st, u64(counts)); }
+int pool_tail_ce_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_ce_kernel, a, true, false, true, true, st); }
+int pool_tail_grad_launch(TailArgs& a, hipStream_t st) { return tail_launch(pool_grad_kernel, a, true, true, true, true, st); }
+int pool_tail_count_launch(TailArgs& a, long long* counts, hipStream_t st) { return tail_launch(pool_count_kernel, a, true, false, false, true, st, u64(counts)); }
 
-// labels of every row of the entries (leaf rows, or pool: pooled rows) into pred[entry]; the entries need no labels, mask or row_lv
+// labels of every row of the entries (leaf rows, or pool: pooled rows) into pred[entry]; the entries need no labels, mask or row_lv,
+// and a pooled head no CSC (the launch reads the plan's CSR alone)
 int tail_predict_launch(TailArgs& a, int64_t* const* pred, bool pool, hipStream_t st) {
   HMP_CHECK_ARG(pred != nullptr, "tail predict: null output array");
   TailPred o = {{nullptr, nullptr}};
-  for (int i = 0; i < a.n; ++i) {
-    o.p[i] = pred[i];
-    HMP_CHECK_ARG(o.p[i] || (pool ? a.h[i].n_pool : a.h[i].n_rows) == 0, "tail predict: null output of entry %d", i);
-  }
-  int blocks;
-  HMP_TRY(tail_layout(a, pool, !pool, false, blocks, false));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(pool ? pool_predict_kernel : tail_predict_kernel, dim3(blocks), dim3(256), 0, st, a, o);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  for (int i = 0; i < a.n; ++i) o.p[i] = pred[i];
+  HMP_TRY(check_outputs(a, pool, "tail predict: null output", [&](int i) { return o.p[i] != nullptr; }));
+  return tail_launch(pool ? pool_predict_kernel : tail_predict_kernel, a, pool, !pool, false, false, st, o);
 }
 
 // top-k labels and probabilities of every row of the entries (leaf rows, or pool: pooled rows); the layout and checks of
@@ -290,17 +293,9 @@ int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* p
   HMP_CHECK_ARG(labels != nullptr && probs != nullptr, "tail top-k: null output array");
   HMP_CHECK_ARG(k >= 1 && k <= TOPK_MAX, "tail top-k: k = %d (1 .. %d)", k, TOPK_MAX);
   TailTopk o = {{nullptr, nullptr}, {nullptr, nullptr}, k};
-  for (int i = 0; i < a.n; ++i) {
-    o.l[i] = labels[i];
-    o.p[i] = probs[i];
-    HMP_CHECK_ARG(o.l[i] || o.p[i] || (pool ? a.h[i].n_pool : a.h[i].n_rows) == 0, "tail top-k: no output of entry %d", i);
-  }
-  int blocks;
-  HMP_TRY(tail_layout(a, pool, !pool, false, blocks, false));
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(pool ? pool_topk_kernel : tail_topk_kernel, dim3(blocks), dim3(256), 0, st, a, o);
-  HMP_LAUNCH_CHECK();
-  return HMP_OK;
+  for (int i = 0; i < a.n; ++i) { o.l[i] = labels[i]; o.p[i] = probs[i]; }
+  HMP_TRY(check_outputs(a, pool, "tail top-k: no output", [&](int i) { return o.l[i] || o.p[i]; }));
+  return tail_launch(pool ? pool_topk_kernel : tail_topk_kernel, a, pool, !pool, false, false, st, o);
 }
 
 }  // namespace hmp

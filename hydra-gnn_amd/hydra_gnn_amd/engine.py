@@ -68,6 +68,38 @@ class _PtrView:
         return self.addr
 
 
+class _HostMirror:
+    """A device byte buffer, its pinned host twin and one event: a call's results land in ``dev``, cross in ONE device-to-host copy
+    and are read through views of ``host``, which stay valid until the next call that uses the mirror."""
+
+    def __init__(self):
+        self.dev = self.host = self.done = None
+
+    def reserve(self, nbytes: int, device) -> bool:
+        """at least ``nbytes`` on ``device`` (a grown buffer takes twice the need, 4096 at the least); True: the buffers are new"""
+        if self.dev is not None and self.dev.numel() >= nbytes and self.dev.device == device:
+            return False
+        cap = max(4096, 2 * nbytes)
+        self.dev = torch.empty(cap, dtype=torch.uint8, device=device)
+        self.host = torch.empty(cap, dtype=torch.uint8).pin_memory()
+        self.done = torch.cuda.Event()
+        return True
+
+    def fetch(self, nbytes: int) -> torch.Tensor:
+        """the first ``nbytes`` bytes down in one copy, one event recorded and waited for; returns them (a view of ``host``)"""
+        host = self.host[:nbytes]
+        if nbytes > 0:
+            host.copy_(self.dev[:nbytes], non_blocking=True)
+        self.done.record()
+        self.done.synchronize()
+        return host
+
+
+def _pairs(buf: torch.Tensor, n: int):
+    """the int64 and float32 halves of a mirror buffer that holds ``n`` 8-byte entries, then ``n`` 4-byte ones"""
+    return buf[:8 * n].view(torch.int64), buf[8 * n:12 * n].view(torch.float32)
+
+
 class _BatchHolder:
     """ctypes batch descriptor + the tensors it points at (kept alive while kernels run)."""
 
@@ -139,6 +171,9 @@ class NativeNet:
         self._plan_key = None  # versions of the edge lists whose plan the workspace holds (predict() reuses it across frames)
         self._plan_tensors = None  # ... and the edge tensors themselves (identity is the test; holding them pins their addresses)
         self._agg_first: Dict[Tuple[int, int], bool] = {}  # (layer, conv) -> evaluated aggregate-first (decided with the first batch)
+        # the host results of predict / predict_pair, of predict_confidence, and of explain / explain_salient
+        self._pred, self._conf, self._att = _HostMirror(), _HostMirror(), _HostMirror()
+        self._conf_views = None  # predict_confidence: (rows per head, device views, host views) of the last call
 
     def set_compute(self, precision: str) -> None:
         """'fp32' (default): every projection on the exact fp32 MFMA path.  'bf16': GEMM calls in the throughput-bound regime
@@ -511,11 +546,7 @@ class NativeNet:
         n = int(h.c.n_out)
         with torch.cuda.device(dev):
             self._ensure_workspace(h, dev)
-            if getattr(self, "_pred_dev", None) is None or self._pred_dev.numel() < n or self._pred_dev.device != dev:
-                cap = max(256, 2 * n)
-                self._pred_dev = torch.empty(cap, dtype=torch.int64, device=dev)
-                self._pred_host = torch.empty(cap, dtype=torch.int64).pin_memory()
-                self._pred_done = torch.cuda.Event()
+            self._pred.reserve(8 * n, dev)
             out_p, ld = C.c_void_p(), C.c_int32()
             st = _lib.stream_ptr()
             # consecutive frames with the SAME edge tensors (unchanged in place): the plan of the previous call is reused
@@ -533,11 +564,8 @@ class NativeNet:
             self._plan_key = key
             self._plan_tensors = list(h.edge_tensors) if key is not None else None
             if n > 0:
-                _lib.check(self._lib.hmp_argmax_rows(out_p.value, ld.value, n, int(n_classes), self._pred_dev.data_ptr(), st))
-                self._pred_host[:n].copy_(self._pred_dev[:n], non_blocking=True)
-            self._pred_done.record()
-            self._pred_done.synchronize()
-        return self._pred_host[:n]
+                _lib.check(self._lib.hmp_argmax_rows(out_p.value, ld.value, n, int(n_classes), self._pred.dev.data_ptr(), st))
+            return self._pred.fetch(8 * n).view(torch.int64)
 
     def count_correct(self, data, labels, masks, counts: torch.Tensor) -> torch.Tensor:
         """Two-headed nets: ADD this batch's {correct, total} of both heads to the device int64[4] ``counts`` (``hmp_net_count_correct2``:
@@ -579,11 +607,8 @@ class NativeNet:
         output, comparison with ``labels`` on the rows of ``members`` whose label is not ``ignored_label``).  ``batch`` is a data
         object or a descriptor from ``store.BatchStream.next``, which brings its own labels (pass ``labels=None``).  Nothing
         synchronises."""
-        if self.aux_readout is not None or self.heads is not None:
-            raise _lib.HydraMPError("count_correct_rooms: a two-headed net counts with count_correct / count_correct_heads")
-        flat = self.flat_params(full_check=False)
+        h, members_ptr, flat = self._room_batch("count_correct_rooms", batch, labels, members, ignored_label)
         dev = flat.device
-        h, members_ptr = self._room_batch("count_correct_rooms", batch, labels, members, ignored_label, dev)
         from .ops import check_count_buffers
 
         check_count_buffers(counts, confusion, self.n_classes, dev)
@@ -591,9 +616,13 @@ class NativeNet:
                     confusion.data_ptr() if confusion is not None else None)
         return counts
 
-    def _room_batch(self, what: str, batch, labels, members, ignored_label: int, dev):
-        """(descriptor, address of the row filter or None) of a room-task count on a data object with ``labels`` or on a stream
-        descriptor, which brings its labels and -- a stream of homogeneous graphs -- its ``room_mask`` rows and ignored label"""
+    def _room_batch(self, what: str, batch, labels, members, ignored_label: int):
+        """(descriptor, address of the row filter or None, flat parameters) of a room-task count on a data object with ``labels``
+        or on a stream descriptor, which brings its labels and -- a stream of homogeneous graphs -- its ``room_mask`` rows and
+        ignored label"""
+        if self.aux_readout is not None or self.heads is not None:
+            raise _lib.HydraMPError(f"{what}: a two-headed net counts with count_correct / count_correct_heads")
+        flat = self.flat_params(full_check=False)
         if isinstance(batch, _BatchHolder):
             if labels is not None:
                 raise _lib.HydraMPError(f"{what}: a stream batch brings its own labels (pass labels=None)")
@@ -606,7 +635,7 @@ class NativeNet:
                     raise _lib.HydraMPError(f"{what}: ignored_label {ignored_label}, but the stream wrote its labels with ignored_label "
                                             f"{stream.ignored_label} outside room_mask")
                 if members is None:
-                    return h, stream.members.data_ptr()
+                    return h, stream.members.data_ptr(), flat
         else:
             if labels is None:
                 raise _lib.HydraMPError(f"{what}: labels are required for a data batch")
@@ -615,8 +644,8 @@ class NativeNet:
             raise _lib.HydraMPError(f"{what}: the batch has no labels")
         from .ops import row_members
 
-        members = row_members(members, int(h.c.n_out), dev)
-        return h, (members.data_ptr() if members is not None else None)
+        members = row_members(members, int(h.c.n_out), flat.device)
+        return h, (members.data_ptr() if members is not None else None), flat
 
     def count_correct_rooms_by_graph(self, batch, labels, counts: torch.Tensor, ignored_label: int = 25,
                                      members: Optional[torch.Tensor] = None, graph_ptr: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -624,11 +653,8 @@ class NativeNet:
         launch): ADD {correct, total} of graph ``g`` of the batch to ``counts[g]`` (device int64 ``[n_graphs, 2]``).  A stream
         descriptor brings the graphs' row offsets; a data batch needs ``graph_ptr``, the device int64 ``[n_graphs + 1]`` offsets of
         the output rows (``Batch.ptr`` of their node type).  Nothing synchronises."""
-        if self.aux_readout is not None or self.heads is not None:
-            raise _lib.HydraMPError("count_correct_rooms_by_graph: a two-headed net counts with count_correct / count_correct_heads")
-        flat = self.flat_params(full_check=False)
+        h, members_ptr, flat = self._room_batch("count_correct_rooms_by_graph", batch, labels, members, ignored_label)
         dev = flat.device
-        h, members_ptr = self._room_batch("count_correct_rooms_by_graph", batch, labels, members, ignored_label, dev)
         if not isinstance(batch, _BatchHolder):
             from .ops import check_graph_ptr
 
@@ -666,29 +692,22 @@ class NativeNet:
         two = len(rows) == 2
         outs = _label_buffers(out, rows, two, dev)
         mem, _alive = self._label_members(h, stream, members, rows, dev, "predict_labels")
-        if self.heads is not None:
-            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
-            self._count("hmp_net_predict_heads", h, dev, flat.data_ptr(), mem, prd)
-        elif two:
-            prd = (C.c_void_p * 2)(*[o.data_ptr() for o in outs])
-            self._count("hmp_net_predict2", h, dev, flat.data_ptr(), prd)
-        else:
-            self._count("hmp_net_predict_rooms", h, dev, flat.data_ptr(), mem, outs[0].data_ptr())
+        self._label_entry("predict", h, flat, mem, (), [outs])
         views = tuple(o[:n] for o, n in zip(outs, rows))
         return views if two else views[0]
+
+    def _label_entry(self, what: str, h, flat, mem, extra: tuple, outputs) -> None:
+        """``hmp_net_<what>_rooms`` / ``2`` / ``_heads`` by the net's kind: the parameters, the members (an aux-readout net has
+        none), ``extra``, then every output's address -- of a two-headed net, the pair of its heads' addresses"""
+        kind = "_heads" if self.heads is not None else "2" if self.aux_readout is not None else "_rooms"
+        outs = [ts[0].data_ptr() if kind == "_rooms" else (C.c_void_p * 2)(*[t.data_ptr() for t in ts]) for ts in outputs]
+        self._count(f"hmp_net_{what}{kind}", h, flat.device, flat.data_ptr(), *(() if kind == "2" else (mem,)), *extra, *outs)
 
     def _label_rows(self, batch, who: str):
         """(holder, its stream or None, flat parameters, rows per head) of a label call: one entry for the room task, two for a
         two-headed net"""
-        flat = self.flat_params(full_check=False)
-        stream = None
-        if isinstance(batch, _BatchHolder):
-            h = batch
-            stream = h.stream
-            if stream is not None and stream.nat is not self:
-                raise _lib.HydraMPError(f"{who}: the batch comes from a stream created for another model")
-        else:
-            h = self.make_batch(batch)
+        h, flat = self._readout_batch(batch, who)
+        stream = h.stream  # None for a data batch
         if self.heads is not None:
             rows = [int(h.c.n_out)] * 2
         elif self.aux_readout is not None:
@@ -739,15 +758,7 @@ class NativeNet:
         two = len(rows) == 2
         outs = _topk_buffers(out, rows, k, two, dev)
         mem, _alive = self._label_members(h, stream, members, rows, dev, "predict_topk")
-        if two:
-            lab = (C.c_void_p * 2)(*[o[0].data_ptr() for o in outs])
-            prb = (C.c_void_p * 2)(*[o[1].data_ptr() for o in outs])
-            if self.heads is not None:
-                self._count("hmp_net_topk_heads", h, dev, flat.data_ptr(), mem, k, lab, prb)
-            else:
-                self._count("hmp_net_topk2", h, dev, flat.data_ptr(), k, lab, prb)
-        else:
-            self._count("hmp_net_topk_rooms", h, dev, flat.data_ptr(), mem, k, outs[0][0].data_ptr(), outs[0][1].data_ptr())
+        self._label_entry("topk", h, flat, mem, (k,), [[o[0] for o in outs], [o[1] for o in outs]])
         views = tuple((lb[:n], pb[:n]) for (lb, pb), n in zip(outs, rows))
         return views if two else views[0]
 
@@ -760,28 +771,19 @@ class NativeNet:
         dev = flat.device
         n = sum(rows)
         with torch.cuda.device(dev):
-            if getattr(self, "_conf_dev", None) is None or self._conf_dev.numel() < 12 * n or self._conf_dev.device != dev:
-                cap = max(4096, 24 * n)
-                self._conf_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
-                self._conf_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
-                self._conf_done = torch.cuda.Event()
-                self._conf_views = None
-            if self._conf_views is None or self._conf_views[0] != rows:  # consecutive frames of one size reuse the views
+            fresh = self._conf.reserve(12 * n, dev)
+            if fresh or self._conf_views is None or self._conf_views[0] != rows:  # consecutive frames of one size reuse the views
 
                 def split(buf):
-                    lab = buf[:8 * n].view(torch.int64)
-                    prb = buf[8 * n:12 * n].view(torch.float32)
+                    lab, prb = _pairs(buf, n)
                     return [(lab[o:o + r], prb[o:o + r]) for o, r in zip((0, rows[0]), rows)]
 
-                outs = [(lb.view(lb.numel(), 1), pb.view(pb.numel(), 1)) for lb, pb in split(self._conf_dev)]
-                host = split(self._conf_host)
+                outs = [(lb.view(lb.numel(), 1), pb.view(pb.numel(), 1)) for lb, pb in split(self._conf.dev)]
+                host = split(self._conf.host)
                 self._conf_views = (list(rows), tuple(outs) if len(rows) == 2 else outs[0], tuple(host) if len(rows) == 2 else host[0])
             _, outs, host = self._conf_views
             self.predict_topk(h, 1, out=outs, members=members)
-            if n > 0:
-                self._conf_host[:12 * n].copy_(self._conf_dev[:12 * n], non_blocking=True)
-            self._conf_done.record()
-            self._conf_done.synchronize()
+            self._conf.fetch(12 * n)
         return host
 
     def predict_pair(self, batch, members=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -790,26 +792,15 @@ class NativeNet:
         buffer (valid until the next call)."""
         if self.aux_readout is None and self.heads is None:
             raise _lib.HydraMPError("predict_pair: the net has one output; use predict()")
-        flat = self.flat_params(full_check=False)
+        h, _, flat, rows = self._label_rows(batch, "predict_pair")
         dev = flat.device
-        h = batch if isinstance(batch, _BatchHolder) else self.make_batch(batch)
-        if self.heads is not None:
-            rows = [int(h.c.n_out)] * 2
-        else:
-            rows = [h.n_nodes[self.node_types.index(t)] for t in self.head_label_types()]
         n = rows[0] + rows[1]
         with torch.cuda.device(dev):
-            if getattr(self, "_pred_dev", None) is None or self._pred_dev.numel() < n or self._pred_dev.device != dev:
-                cap = max(256, 2 * n)
-                self._pred_dev = torch.empty(cap, dtype=torch.int64, device=dev)
-                self._pred_host = torch.empty(cap, dtype=torch.int64).pin_memory()
-                self._pred_done = torch.cuda.Event()
-            self.predict_labels(h, out=(self._pred_dev[:rows[0]], self._pred_dev[rows[0]:n]), members=members)
-            if n > 0:
-                self._pred_host[:n].copy_(self._pred_dev[:n], non_blocking=True)
-            self._pred_done.record()
-            self._pred_done.synchronize()
-        return self._pred_host[:rows[0]], self._pred_host[rows[0]:n]
+            self._pred.reserve(8 * n, dev)
+            pred = self._pred.dev[:8 * n].view(torch.int64)
+            self.predict_labels(h, out=(pred[:rows[0]], pred[rows[0]:]), members=members)
+            host = self._pred.fetch(8 * n).view(torch.int64)
+        return host[:rows[0]], host[rows[0]:]
 
     # ---- attention export ([PyG] GATConv.forward(return_attention_weights=True)) -------------------------------------
     def _gat_layer(self, layer: int, who: str) -> List[ConvDesc]:
@@ -835,7 +826,8 @@ class NativeNet:
         """edge types of the live GAT convs of program layer ``layer`` (what :meth:`attention` exports by default)"""
         return [c.edge_type for c in self._gat_layer(layer, "attention") if c.active]
 
-    def _attention_batch(self, batch, who: str):
+    def _readout_batch(self, batch, who: str):
+        """(descriptor, flat parameters) of a label, attention or saliency call on a data object or on a stream descriptor"""
         flat = self.flat_params(full_check=False)
         if isinstance(batch, _BatchHolder):
             h = batch
@@ -865,7 +857,7 @@ class NativeNet:
         at least the needed rows; the result is a view of their leading rows.  Nothing synchronises."""
         ets = [tuple(e) for e in edge_types] if edge_types is not None else self.attention_edge_types(layer)
         convs = [self._gat_conv(layer, e, "attention") for e in ets]
-        h, flat = self._attention_batch(batch, "attention")
+        h, flat = self._readout_batch(batch, "attention")
         dev = flat.device
         slots = (C.c_void_p * _lib.MAX_EDGE_TYPES)()
         res = {}
@@ -896,7 +888,7 @@ class NativeNet:
         k = _check_k(k)
         many = isinstance(edge_type, list)
         convs = [self._gat_conv(layer, e, "top_attended") for e in (edge_type if many else [edge_type])]
-        h, flat = self._attention_batch(batch, "top_attended")
+        h, flat = self._readout_batch(batch, "top_attended")
         dev = flat.device
         s_slots, w_slots = (C.c_void_p * _lib.MAX_EDGE_TYPES)(), (C.c_void_p * _lib.MAX_EDGE_TYPES)()
         res = {}
@@ -919,23 +911,15 @@ class NativeNet:
         ``(src int64 [n_dst, k], weight float32 [n_dst, k])`` as views of that buffer (valid until the next call)."""
         k = _check_k(k)
         conv = self._gat_conv(layer, edge_type, "explain")
-        h, flat = self._attention_batch(batch, "explain")
+        h, flat = self._readout_batch(batch, "explain")
         dev = flat.device
         nd = self.attention_rows(h, conv)[2]
         n = nd * k
         with torch.cuda.device(dev):
-            if getattr(self, "_att_dev", None) is None or self._att_dev.numel() < 12 * n or self._att_dev.device != dev:
-                cap = max(4096, 24 * n)
-                self._att_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
-                self._att_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
-                self._att_done = torch.cuda.Event()
-            split = lambda buf: (buf[:8 * n].view(torch.int64).view(nd, k), buf[8 * n:12 * n].view(torch.float32).view(nd, k))  # noqa: E731
-            self.top_attended(h, layer, conv.edge_type, k, out=split(self._att_dev) if n > 0 else None)
-            if n > 0:
-                self._att_host[:12 * n].copy_(self._att_dev[:12 * n], non_blocking=True)
-            self._att_done.record()
-            self._att_done.synchronize()
-        return split(self._att_host)
+            self._att.reserve(12 * n, dev)
+            split = lambda buf: tuple(v.view(nd, k) for v in _pairs(buf, n))  # noqa: E731
+            self.top_attended(h, layer, conv.edge_type, k, out=split(self._att.dev) if n > 0 else None)
+            return split(self._att.fetch(12 * n))
 
     # ---- gradient saliency ([PyG] idiom: x.requires_grad_(); model(data)[i, c].backward(); x.grad) --------------------
     def _saliency_checks(self, who: str, wrt, head, rows, ordinal) -> Tuple[int, int]:
@@ -1037,7 +1021,7 @@ class NativeNet:
         type the program never reads is not written)."""
         who = "input_gradients"
         w, head = self._saliency_checks(who, wrt, head, rows, ordinal)
-        h, flat = self._attention_batch(batch, who)
+        h, flat = self._readout_batch(batch, who)
         dev = flat.device
         n_out = self._head_rows(h, head)
         tgt = None
@@ -1091,7 +1075,7 @@ class NativeNet:
         of the 306-d object features: position, box size, word2vec.  Nothing synchronises."""
         self._score_ranges(groups, 1, "saliency")
         self._saliency_checks("saliency", kw.get("wrt", "logit"), kw.get("head", 0), kw.get("rows"), kw.get("ordinal"))
-        h, _ = self._attention_batch(batch, "saliency")
+        h, _ = self._readout_batch(batch, "saliency")
         gx = self.input_gradients(h, **kw)
         dev = next(iter(gx.values())).device if gx else None
         res = {}
@@ -1141,7 +1125,7 @@ class NativeNet:
                 if et[2] != head_t:
                     raise _lib.HydraMPError(f"{who}: per-row passes rank the sources of the output rows: edge type {et!r} does not end "
                                             f"in '{head_t}'")
-        h, flat = self._attention_batch(batch, who)
+        h, flat = self._readout_batch(batch, who)
         dev = flat.device
         idx = lambda t: self.node_types.index(t)  # noqa: E731
         res = {}
@@ -1187,7 +1171,7 @@ class NativeNet:
         """an upper bound of the ``node_type`` rows in one graph of the batch (the pass count of exact per-row explanations), from
         host-side numbers only: the collation's per-type maximum (``data.collate``, ``BatchStream.next``) or its largest graph where
         the batch is a union of graphs, else all rows (one graph)"""
-        h, _ = self._attention_batch(batch, "max_graph_rows")
+        h, _ = self._readout_batch(batch, "max_graph_rows")
         i = self.node_types.index(node_type)
         if int(h.c.n_graphs) > 0 and h.c.d_node_ptr[i] and int(h.c.max_graph_nodes) > 0:
             return min(h.n_nodes[i], h.max_rows.get(i, int(h.c.max_graph_nodes)))
@@ -1201,28 +1185,21 @@ class NativeNet:
         the next call)."""
         k = _check_k(k)
         et = self._salient_edge(edge_type, "explain_salient")
-        h, flat = self._attention_batch(batch, "explain_salient")
+        h, flat = self._readout_batch(batch, "explain_salient")
         dev = flat.device
         if passes is None:
             passes = self.max_graph_rows(h, et[2])
         nd = h.n_nodes[self.node_types.index(et[2])]
         n = nd * k
         with torch.cuda.device(dev):
-            if getattr(self, "_att_dev", None) is None or self._att_dev.numel() < 12 * n or self._att_dev.device != dev:
-                cap = max(4096, 24 * n)
-                self._att_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
-                self._att_host = torch.empty(cap, dtype=torch.uint8).pin_memory()
-                self._att_done = torch.cuda.Event()
-            split = lambda buf: (buf[:8 * n].view(torch.int64).view(nd, k), buf[8 * n:12 * n].view(torch.float32).view(nd, k))  # noqa: E731
+            self._att.reserve(12 * n, dev)
+            split = lambda buf: tuple(v.view(nd, k) for v in _pairs(buf, n))  # noqa: E731
             if n > 0:
-                s_dev, w_dev = split(self._att_dev)
+                s_dev, w_dev = split(self._att.dev)
                 s_dev.fill_(-1)
                 w_dev.zero_()
                 self.top_salient(h, et, k, out=(s_dev, w_dev), passes=passes, **kw)
-                self._att_host[:12 * n].copy_(self._att_dev[:12 * n], non_blocking=True)
-            self._att_done.record()
-            self._att_done.synchronize()
-        return split(self._att_host)
+            return split(self._att.fetch(12 * n))
 
     def _count(self, entry: str, h: _BatchHolder, dev, *args) -> None:
         """the count entries' common block: ``entry(handle, batch, *args, stream)`` (eval-mode forward + count on the device),

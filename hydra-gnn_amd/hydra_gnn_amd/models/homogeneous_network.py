@@ -8,6 +8,8 @@ of :mod:`hydra_gnn_amd.ops` (their graphs have 2..27 nodes; the per-layer launch
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -151,8 +153,7 @@ class HomogeneousNetwork(_NativeModule):
         if isinstance(data, _BatchHolder):
             net.count_correct_stream(data, mask_name, acc)
             return acc if counts is not None else [int(v) for v in acc.tolist()]
-        members = (data.room_mask, getattr(data, self._OBJECT_ATTR) if self._OBJECT_ATTR is not None else None)
-        net.count_correct_heads(self._view(data), data.y, getattr(data, mask_name), members, acc)
+        net.count_correct_heads(self._view(data), data.y, getattr(data, mask_name), self._members(data), acc)
         return acc if counts is not None else [int(v) for v in acc.tolist()]
 
     def _view(self, data):
@@ -237,16 +238,22 @@ class HomogeneousNetwork(_NativeModule):
             ops.count_correct_rows(self._eval_states(data), data.y, acc, ignored_label, members=data.room_mask, confusion=confusion)
         return acc if counts is not None else [int(v) for v in acc.tolist()]
 
-    def _eval_states(self, data):
-        """GCN / GIN: the final states of an eval-mode op-by-op forward (the training flag is put back)"""
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """eval mode without autograd; the training flag is put back"""
         was = self.training
         self.train(False)
         try:
             with torch.no_grad():
-                return self._op_states(data)
+                yield
         finally:
             if was:
                 self.train(True)
+
+    def _eval_states(self, data):
+        """GCN / GIN: the final states of an eval-mode op-by-op forward"""
+        with self._eval_mode():
+            return self._op_states(data)
 
     def count_correct_rooms_per_graph(self, data, counts, ignored_label=25, graph_ptr=None):
         """:meth:`count_correct_rooms` per graph (``BaseTrainingJob.test_individual_graph``, base_training_job.py:315-339, for a
@@ -273,16 +280,24 @@ class HomogeneousNetwork(_NativeModule):
         """rows of the object head, or None for the complement of ``room_mask`` (reference :147)"""
         return getattr(data, self._OBJECT_ATTR) if self._OBJECT_ATTR is not None else None
 
+    def _members(self, data):
+        """the row filter of the native label calls: ``room_mask``; two-headed: (room rows, object rows | None)"""
+        return (data.room_mask, self._object_rows(data)) if self.classification_task == "all" else data.room_mask
+
     def _eval_heads(self, data):
-        """GCN / GIN: both heads' logits of an eval-mode op-by-op forward (the training flag is put back)"""
-        was = self.training
-        self.train(False)
-        try:
-            with torch.no_grad():
-                return self(data)
-        finally:
-            if was:
-                self.train(True)
+        """GCN / GIN: both heads' logits of an eval-mode op-by-op forward"""
+        with self._eval_mode():
+            return self(data)
+
+    def _scatter_heads(self, data, outs, per_head):
+        """GCN / GIN, two-headed: the tensors ``per_head(logits)`` of each head scattered to the head's rows of its per-node buffers
+        ``outs[head]``, ``-1`` (labels) / ``0`` (probabilities) elsewhere"""
+        n = data.x.size(0)
+        obj = self._object_rows(data)
+        for bufs, logits, rows in zip(outs, self._eval_heads(data), (data.room_mask, ~data.room_mask if obj is None else obj)):
+            for buf, values in zip(bufs, per_head(logits)):
+                buf[:n].fill_(0 if buf.is_floating_point() else -1)
+                buf[:n][rows] = values
 
     def predict_labels(self, data, out=None):
         """Labels on the device, one int64 per NODE (the native output has a row per node; nothing is compacted): room task:
@@ -302,18 +317,14 @@ class HomogeneousNetwork(_NativeModule):
                 raise HydraMPError(f"predict_labels: {self.conv_block} runs op by op: pass a collated Data batch")
             return self.native().predict_labels(data, out=out)
         if not self.op_path:
-            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
-            return self.native().predict_labels(self._view(data), out=out, members=members)
+            return self.native().predict_labels(self._view(data), out=out, members=self._members(data))
         if not two:
             return ops.predict_rows(self._eval_states(data), data.room_mask, out)
         from ..engine import _label_buffers
 
         n = data.x.size(0)
         outs = _label_buffers(out, [n, n], True, data.x.device)
-        obj = self._object_rows(data)
-        for o, logits, rows in zip(outs, self._eval_heads(data), (data.room_mask, ~data.room_mask if obj is None else obj)):
-            o[:n].fill_(-1)
-            o[:n][rows] = ops.argmax_rows(logits)
+        self._scatter_heads(data, [(o,) for o in outs], lambda logits: (ops.argmax_rows(logits),))
         return outs[0][:n], outs[1][:n]
 
     def predict_topk(self, data, k=1, out=None):
@@ -335,18 +346,12 @@ class HomogeneousNetwork(_NativeModule):
                 raise HydraMPError(f"predict_topk: {self.conv_block} runs op by op: pass a collated Data batch")
             return self.native().predict_topk(data, k, out=out)
         if not self.op_path:
-            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
-            return self.native().predict_topk(self._view(data), k, out=out, members=members)
+            return self.native().predict_topk(self._view(data), k, out=out, members=self._members(data))
         if not two:
             return ops.topk_rows(self._eval_states(data), k, data.room_mask, out)
         n = data.x.size(0)
         outs = _topk_buffers(out, [n, n], k, True, data.x.device)
-        obj = self._object_rows(data)
-        for (lb, pb), logits, rows in zip(outs, self._eval_heads(data), (data.room_mask, ~data.room_mask if obj is None else obj)):
-            top = ops.topk_rows(logits, k)
-            lb[:n].fill_(-1)
-            pb[:n].zero_()
-            lb[:n][rows], pb[:n][rows] = top
+        self._scatter_heads(data, outs, lambda logits: ops.topk_rows(logits, k))
         return tuple((lb[:n], pb[:n]) for lb, pb in outs)
 
     def predict_with_confidence(self, data):
@@ -361,8 +366,7 @@ class HomogeneousNetwork(_NativeModule):
             heads = self.predict_topk(data, 1)
             heads = [tuple(t[:, 0].cpu() for t in hd) for hd in (heads if two else (heads,))]
         else:
-            members = (data.room_mask, self._object_rows(data)) if two else data.room_mask
-            heads = self.native().predict_confidence(self._view(data), members=members)
+            heads = self.native().predict_confidence(self._view(data), members=self._members(data))
             heads = heads if two else (heads,)
         heads = tuple((lb[lb >= 0], pb[lb >= 0]) for lb, pb in heads)  # the rows outside a head's rows dropped on the host
         return heads if two else heads[0]
@@ -372,7 +376,7 @@ class HomogeneousNetwork(_NativeModule):
         (the -1 rows of :meth:`predict_labels` dropped on the host)"""
         if self.op_path:
             return tuple(ops.argmax_rows(p).cpu() for p in self._eval_heads(data))
-        pair = self.native().predict_pair(self._view(data), members=(data.room_mask, self._object_rows(data)))
+        pair = self.native().predict_pair(self._view(data), members=self._members(data))
         return tuple(p[p >= 0] for p in pair)
 
     def predict(self, data):

@@ -511,3 +511,74 @@ def test_predict_leaves_parameters_optimiser_state_and_the_dropout_counter_alone
     one_step()  # and the step goes on
     torch.cuda.synchronize()
     assert step.steps_taken() == 2 and np.isfinite(step.loss())
+
+
+# ---- 9. refused readout calls -------------------------------------------------------------------------------------------------------
+READOUT_ENTRIES = ("hmp_net_count_correct2", "hmp_net_count_correct_heads", "hmp_net_count_correct_rooms",
+                   "hmp_net_count_correct_rooms_by_graph", "hmp_net_predict_rooms", "hmp_net_predict2", "hmp_net_predict_heads",
+                   "hmp_net_topk_rooms", "hmp_net_topk2", "hmp_net_topk_heads")
+
+
+def net_of_kind(kind):
+    """(training-mode model, batch of 2 graphs) of a net kind: "room" one output, "two" an aux readout, "heads" linear heads"""
+    if kind == "room":
+        net, gs, coll = room_case("hetero")
+        return net.to(DEV).train(), coll(gs[:2]).to(DEV)
+    shape = "hetero" if kind == "two" else "homog"
+    return two_head_model(shape, "GraphSAGE", seed=23).to(DEV).train(), host_batch(shape, graphs_of(shape, 2, 41), [0, 1])
+
+
+def readout_call(entry, net, batch, k):
+    """the raw library call of ``entry`` on the model's net with valid, roomy buffers: only the net's kind or ``k`` is wrong"""
+    nat = net.native()
+    h = nat.make_batch(net._view(batch) if isinstance(net, HomogeneousNetwork) else batch)
+    rows = sum(h.n_nodes) * 9 + 4
+    lab = torch.zeros(2, rows, dtype=torch.int64, device=DEV)
+    prb = torch.zeros(2, rows, dtype=torch.float32, device=DEV)
+    mem = torch.ones(rows, dtype=torch.uint8, device=DEV)
+    pair = lambda t: (C.c_void_p * 2)(t[0].data_ptr(), t[1].data_ptr())  # noqa: E731
+    P, one, members = nat.flat_params(full_check=False).data_ptr(), lab[0].data_ptr(), (C.c_void_p * 2)(mem.data_ptr(), None)
+    args = {"hmp_net_count_correct2": (C.byref(_lib.HeadTargets()), P, one),
+            "hmp_net_count_correct_heads": (C.byref(_lib.LinearHeadTargets()), P, one),
+            "hmp_net_count_correct_rooms": (P, None, 25, one, None),
+            "hmp_net_count_correct_rooms_by_graph": (P, None, 25, one),
+            "hmp_net_predict_rooms": (P, None, one),
+            "hmp_net_predict2": (P, pair(lab)),
+            "hmp_net_predict_heads": (P, members, pair(lab)),
+            "hmp_net_topk_rooms": (P, None, k, one, prb[0].data_ptr()),
+            "hmp_net_topk2": (P, k, pair(lab), pair(prb)),
+            "hmp_net_topk_heads": (P, members, k, pair(lab), pair(prb))}[entry]
+    keep = (h, lab, prb, mem)
+    return lambda: (keep, getattr(nat._lib, entry)(nat._handle, C.byref(h.c), *args, _lib.stream_ptr()))[1]
+
+
+@pytest.mark.parametrize("entry", READOUT_ENTRIES)
+def test_a_refused_readout_call_launches_nothing_and_leaves_the_forward_usable(entry):
+    """Every readout entry checks its arguments before its forward: on a net of a kind it does not serve (and, top-k, on its own
+    kind with k out of range) the call fails naming the entry, enqueues no launch of any kernel class, and the backward of the
+    training-mode forward before it gives the gradients, bit for bit, of a twin model that never made the call."""
+    right = "room" if entry.endswith("_rooms") or entry.endswith("_by_graph") else "two" if entry.endswith("2") else "heads"
+    scenarios = [("two" if right == "room" else "room", 1)]
+    if "topk" in entry:
+        scenarios += [(right, 0), (right, 9)]
+    total = lambda out: sum(o.sum() for o in out) if isinstance(out, tuple) else out.sum()  # noqa: E731
+    for kind, k in scenarios:
+        (net, batch), (twin, _) = net_of_kind(kind), net_of_kind(kind)
+        out, ref = net(batch), twin(batch)
+        call = readout_call(entry, net, batch, k)
+
+        def refused():
+            with pytest.raises(_lib.HydraMPError, match=entry + ":"):
+                _lib.check(call())
+
+        assert launches(net, refused) == [0] * _lib.N_KCLASS, (kind, k)
+        total(out).backward()
+        total(ref).backward()
+        torch.cuda.synchronize()
+        compared = 0
+        for (name, p), q in zip(net.named_parameters(), twin.parameters()):
+            assert (p.grad is None) == (q.grad is None), (kind, k, name)
+            if p.grad is not None:
+                assert torch.equal(p.grad, q.grad), (kind, k, name)
+                compared += int(bool((p.grad != 0).any()))
+        assert compared > 0, (kind, k)
