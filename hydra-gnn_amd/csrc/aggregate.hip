@@ -424,7 +424,8 @@ __device__ __forceinline__ void agg_row(const AggDst& D, int mean, int row, int 
 // Masked cross entropy of the output row its row group has just computed (lane = 4 consecutive logits in `t`): ce_group over
 // the registers, the gradient chained back to z where the CE read y = dropout(act(z)).
 template <int GS>
-__device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, int row, int c0, Acc<4>& t, int64_t y, bool in_mask) {
+__device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, int row, int c0, Acc<4>& t, int64_t y, bool in_mask,
+                                            float wy) {
   ce_group<GS, 1>(
       c0 >> 2, D.ce_classes, D.ce_ldg, y, D.ce_ignored, in_mask,
       [&](int, int, float (&v)[4]) {
@@ -438,7 +439,7 @@ __device__ __forceinline__ void ce_rowgroup(const AggDst& D, NetState* state, in
         }
         *reinterpret_cast<float4*>(D.ce_grad + (int64_t)row * D.ce_ldg + c) = make_float4(g[0], g[1], g[2], g[3]);
       },
-      D.ce_row_lv, row, state);
+      D.ce_row_lv, row, state, D.ce_weight, wy);
 }
 
 template <int GS, int NV, bool ZB = false, bool HB = false>
@@ -461,16 +462,19 @@ __global__ __launch_bounds__(256) void agg_fwd_kernel(const AggArgs a) {
   if (row >= D.n_rows) return;
   Acc<4> tot[NV];
   const int c0 = (threadIdx.x % GS) * 4;
-  // the label is requested before the aggregation (it depends on nothing): one round trip less behind the last gather
+  // the label is requested before the aggregation (it depends on nothing): one round trip less behind the last gather; so is
+  // its class weight, as soon as the label is there (weighted steps only: an unweighted launch issues no load for it)
   int64_t y = 0;
   bool in_mask = true;
+  float wy = 1.f;
   if (NV == 1 && D.ce_labels) {
     y = D.ce_labels[row];
     if (D.ce_mask) in_mask = D.ce_mask[row] != 0;
+    if (D.ce_weight) wy = ce_weight(D.ce_weight, y, D.ce_classes);
   }
   agg_row<GS, NV, ZB, HB>(D, a.mean, row, c0, tot);
   if constexpr (NV == 1) {
-    if (D.ce_labels) ce_rowgroup<GS>(D, a.state, row, c0, tot[0], y, in_mask);
+    if (D.ce_labels) ce_rowgroup<GS>(D, a.state, row, c0, tot[0], y, in_mask, wy);
   }
 }
 

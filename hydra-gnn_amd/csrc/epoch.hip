@@ -117,7 +117,7 @@ __global__ void epoch_accumulate_kernel(hmp_epoch_ctl* ctl, const float* loss, c
   double cnt = 0.0;
   if (loss_count) {
     cnt = (double)loss_count[0];
-    l = l / (cnt > 1.0 ? cnt : 1.0);  // TrainStep.loss(): loss_sum / max(count, 1) on the two floats, in double
+    l = l / (cnt > 0.0 ? cnt : 1.0);  // TrainStep.loss(): loss_sum / (count > 0 ? count : 1) on the two floats, in double
   }
   const double w = d_weight ? (double)d_weight[0] : (weight >= 0.0 ? weight : cnt);
   ctl->loss_acc = __dadd_rn(ctl->loss_acc, __dmul_rn(l, w));

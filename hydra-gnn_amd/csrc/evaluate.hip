@@ -157,6 +157,60 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   }
 }
 
+// ---- label histogram and balanced class weights (the class weights of the weighted cross entropy, computed where the labels live)
+// counts[c] += #rows with label c that count ((mask == null || mask[row]) && label != ignored), c in [0, n_classes);
+// counts[n_classes] += #counted rows whose label lies outside [0, n_classes).  HIST (n_classes <= LC_HIST_MAX): a per-workgroup
+// LDS histogram and one 64-bit atomic per non-zero bin; else every row adds to the global bins directly.
+constexpr int LC_HIST_MAX = 256;
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void label_count_kernel(const int64_t* __restrict__ labels, int64_t n_rows, const uint8_t* __restrict__ mask,
+                                                          int64_t ignored, int n_classes, unsigned long long* __restrict__ counts) {
+  __shared__ int s_hist[HIST ? LC_HIST_MAX + 1 : 1];
+  if (HIST) {
+    for (int i = threadIdx.x; i <= n_classes; i += 256) s_hist[i] = 0;
+    __syncthreads();
+  }
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
+    if (mask && !mask[r]) continue;
+    const int64_t y = labels[r];
+    if (y == ignored) continue;
+    const int bin = (y >= 0 && y < n_classes) ? (int)y : n_classes;
+    if (HIST) atomicAdd(&s_hist[bin], 1);
+    else atomicAdd(&counts[bin], 1ull);
+  }
+  if (HIST) {
+    __syncthreads();
+    for (int i = threadIdx.x; i <= n_classes; i += 256)
+      if (s_hist[i]) atomicAdd(&counts[i], (unsigned long long)s_hist[i]);
+  }
+}
+
+// scikit-learn's class_weight = "balanced" over the classes present: with K = #{c : n_c > 0} and N = sum n_c,
+// w[c] = (float)((double)N / ((double)K * n_c)) for n_c > 0 and 0 for an absent class.  ONE workgroup; reads counts[0 .. n_classes)
+// (the out-of-range slot is not part of N).
+__global__ __launch_bounds__(256) void balanced_weights_kernel(const unsigned long long* __restrict__ counts, int n_classes,
+                                                               float* __restrict__ w) {
+  __shared__ unsigned long long s_n;
+  __shared__ int s_k;
+  if (threadIdx.x == 0) { s_n = 0ull; s_k = 0; }
+  __syncthreads();
+  unsigned long long n = 0ull;
+  int k = 0;
+  for (int c = threadIdx.x; c < n_classes; c += 256) {
+    const unsigned long long nc = counts[c];
+    n += nc;
+    k += nc > 0 ? 1 : 0;
+  }
+  if (k) { atomicAdd(&s_n, n); atomicAdd(&s_k, k); }  // integer sums: any order gives the same totals
+  __syncthreads();
+  const double N = (double)s_n, K = (double)s_k;
+  for (int c = threadIdx.x; c < n_classes; c += 256) {
+    const unsigned long long nc = counts[c];
+    w[c] = nc > 0 ? (float)(N / (K * (double)nc)) : 0.f;
+  }
+}
+
 // ---- launch: one workgroup per EV_RPB rows up to the grid cap; VEC iff every row can be read by 16-byte loads
 int ev_blocks(int n_rows) { return cdiv(n_rows, EV_RPB) < EV_MAX_BLOCKS ? cdiv(n_rows, EV_RPB) : EV_MAX_BLOCKS; }
 bool ev_vec(const float* x, int ld) { return (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0; }
@@ -220,7 +274,39 @@ int count_rows_launch(const float* x, int ld, int n_rows, int n_classes, const i
   });
 }
 
+int label_counts_launch(const int64_t* labels, int64_t n_rows, const uint8_t* mask, int64_t ignored, int n_classes, long long* counts,
+                        hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1, "label_counts: n_rows %lld, n_classes %d", (long long)n_rows, n_classes);
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(labels && counts, "label_counts: null labels or counts");
+  const int64_t want = cdiv(n_rows, (int64_t)256);
+  const dim3 grid((unsigned)(want < EV_MAX_BLOCKS ? want : EV_MAX_BLOCKS));
+  auto* c = reinterpret_cast<unsigned long long*>(counts);
+  if (n_classes <= LC_HIST_MAX) hipLaunchKernelGGL(label_count_kernel<true>, grid, dim3(256), 0, st, labels, n_rows, mask, ignored, n_classes, c);
+  else hipLaunchKernelGGL(label_count_kernel<false>, grid, dim3(256), 0, st, labels, n_rows, mask, ignored, n_classes, c);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
+int balanced_weights_launch(const long long* counts, int n_classes, float* w, hipStream_t st) {
+  HMP_CHECK_ARG(counts && w && n_classes >= 1, "balanced_class_weights: null pointer or n_classes %d", n_classes);
+  hipLaunchKernelGGL(balanced_weights_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(counts), n_classes, w);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
+}
+
 }  // namespace hmp
+
+extern "C" int hmp_label_counts(const int64_t* d_labels, int64_t n_rows, const uint8_t* d_mask, int64_t ignored_label, int32_t n_classes,
+                                int64_t* d_counts, void* stream) {
+  using namespace hmp;
+  return label_counts_launch(d_labels, n_rows, d_mask, ignored_label, n_classes, reinterpret_cast<long long*>(d_counts), (hipStream_t)stream);
+}
+
+extern "C" int hmp_balanced_class_weights(const int64_t* d_counts, int32_t n_classes, float* d_w, void* stream) {
+  using namespace hmp;
+  return balanced_weights_launch(reinterpret_cast<const long long*>(d_counts), n_classes, d_w, (hipStream_t)stream);
+}
 
 extern "C" int hmp_count_correct_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
                                       const uint8_t* d_members, int64_t ignored_label, int64_t* d_counts, int64_t* d_confusion,

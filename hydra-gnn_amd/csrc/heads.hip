@@ -175,7 +175,10 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
       if (TRAIN) {
         const bool valid = member && in_mask && y != a.ignored;
         const bool bad = valid && (y < 0 || y >= C);
-        const bool use = valid && !bad;
+        // class weight of the row's label (tail_fns.h: ce_group's rule; never indexed by an unchecked label)
+        const float* const hw = a.weight[h];
+        const float wy = (hw && valid && !bad) ? hw[y] : 1.f;
+        const bool use = valid && !bad && !(hw && wy == 0.f);
         float loss = 0.f;
         if (use) {
           float m = -INFINITY;
@@ -184,12 +187,16 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
           for (int k = 0; k < C; ++k) sum += expf(lg[k] - m);
           const float lse = m + logf(sum);
           loss = lse - lg[y];
-          for (int k = 0; k < C; ++k) lg[k] = expf(lg[k] - lse) - (k == (int)y ? 1.f : 0.f);
+          if (hw) loss *= wy;
+          for (int k = 0; k < C; ++k) {
+            const float g = expf(lg[k] - lse) - (k == (int)y ? 1.f : 0.f);
+            lg[k] = hw ? g * wy : g;
+          }
         } else {
           for (int k = 0; k < C; ++k) lg[k] = 0.f;
         }
         s.hl[h][r] = loss;
-        s.hv[h][r] = use ? 1.f : 0.f;
+        s.hv[h][r] = use ? (hw ? wy : 1.f) : 0.f;
         if (bad) atomicOr(&a.state->status, 2);
       } else if (member && in_mask) {
         const int arg = head_argmax(lg, C);
@@ -332,8 +339,9 @@ int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, floa
 }  // namespace hmp
 
 // test / diagnostic entry of the two linear-heads launchers: a plain copy of the descriptor into LinHeadArgs, no choice of its own
-extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts,
-                                    int32_t* n_blocks_out, void* stream) {
+// (d_w: the class weights of each head for the CE launch, null: unweighted)
+static int linear_heads_run(const hmp_linear_heads_desc* d, const float* const* d_w, int32_t train, int32_t* d_state, int64_t* d_counts,
+                            int32_t* n_blocks_out, void* stream) {
   using namespace hmp;
   static const bool have_device = hmp_device_count() > 0;
   HMP_CHECK_ARG(have_device, "hmp_linear_heads_run: no gfx950 device visible");
@@ -348,6 +356,7 @@ extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t trai
     a.W[k] = d->W[k];
     a.bias[k] = d->bias[k];
     a.member[k] = d->member[k];
+    if (train && d_w) a.weight[k] = d_w[k];
   }
   a.labels = d->labels; a.mask = d->mask; a.ignored = d->ignored;
   a.act = d->act;
@@ -363,6 +372,16 @@ extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t trai
   a.slabs = d->slabs; a.ld_slab = d->ld_slab; a.slab_stride = d->slab_stride;
   if (n_blocks_out) *n_blocks_out = heads_blocks(d->n_rows);
   return train ? linear_heads_ce_launch(a, (hipStream_t)stream) : linear_heads_count_launch(a, (long long*)d_counts, (hipStream_t)stream);
+}
+
+extern "C" int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts,
+                                    int32_t* n_blocks_out, void* stream) {
+  return linear_heads_run(d, nullptr, train, d_state, d_counts, n_blocks_out, stream);
+}
+
+extern "C" int hmp_linear_heads_run_weighted(const hmp_linear_heads_desc* d, const float* const* d_w, int32_t train, int32_t* d_state,
+                                             int64_t* d_counts, int32_t* n_blocks_out, void* stream) {
+  return linear_heads_run(d, d_w, train, d_state, d_counts, n_blocks_out, stream);
 }
 
 // the descriptor of a label / top-k launch (labels, mask, grad, row_lv and slabs may be NULL) as LinHeadArgs, eval mode

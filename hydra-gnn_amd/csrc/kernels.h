@@ -309,6 +309,7 @@ struct AggDst {
   // two-headed step (hmp_net_step2_*): rows whose mask byte is 0 do not count (null: every row), and with ce_tail set the entry's
   // act / dropout are the model's tail, so the gradient written is d loss / d (pre-activation): . keep/(1-p) . act', read off y
   const uint8_t* ce_mask;
+  const float* ce_weight;    // class weights of the entry's head [ce_classes], null: unweighted (tail_fns.h: ce_group)
   int ce_tail;
   int win_in;                // filled by agg_fwd_launch: in-conv served from the LDS window (-1: none)
   int tile_rows;             // agg_proj_fwd_launch: rows per workgroup, 16 or 8.  A launch is as long as its slowest tile and a tile of
@@ -614,10 +615,11 @@ struct NetState {  // device resident
   float loss_sum, count;
   int last_step;   // value of the counter the last started step ran on (its optimiser's, or `step`): what hmp_net_read_state reports
 };
+// w: class weights [n_classes], null: unweighted.  Weighted, a row's pair is {w[y] * nll, w[y]} and its gradient is scaled by w[y]
 int masked_ce_launch(const float* logits, int ldl, int n_rows, int n_classes, const int64_t* labels, int64_t ignored,
-                     float* grad, int ldg, float* out2, NetState* state_or_null, hipStream_t st);
+                     float* grad, int ldg, float* out2, NetState* state_or_null, hipStream_t st, const float* w = nullptr);
 int masked_ce_rows_launch(const float* logits, int ldl, int n_rows, int n_classes, const int64_t* labels, int64_t ignored,
-                          float* grad, int ldg, float* row_lv, NetState* state, hipStream_t st);
+                          float* grad, int ldg, float* row_lv, NetState* state, hipStream_t st, const float* w = nullptr);
 // Tail of the two-headed task (semisup.hip): y = dropout(act(z)) on a final state, then the masked CE on y with the gradient written
 // as d loss / d z (fused step), or the first-maximum argmax of act(z) compared with the labels (accuracy count).  One launch covers
 // the rows of both heads.
@@ -626,6 +628,7 @@ struct HeadTail {
   int ldz, n_rows, classes;
   const int64_t* labels;
   const uint8_t* mask;      // null: every row
+  const float* weight;      // class weights [classes] (CE only), null: unweighted
   float* grad;              // d loss / d z [n_rows][ldg] (CE only; columns >= classes are written 0)
   int ldg;
   float* row_lv;            // per row {loss, valid} (CE only)
@@ -676,6 +679,7 @@ struct LinHeadArgs {
   const int64_t* labels;        // one per row
   const uint8_t* mask;          // null: every row
   const uint8_t* member[2];     // rows of head h; member[1] null: complement of member[0]
+  const float* weight[2];       // class weights of head h [classes[h]] (CE only), null: unweighted
   int64_t ignored;
   int act, drop_on;
   DropCfg drop;                 // quad numbering row * ceil(F / 4) + col / 4

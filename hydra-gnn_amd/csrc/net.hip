@@ -195,6 +195,9 @@ struct hmp_net {
   bool has_pools = false;
   int head_pool[2] = {-1, -1};
   float* d_dpool[2] = {nullptr, nullptr};
+  // class weights of the cross entropy (hmp_net_set_class_weights): borrowed device vectors, [0] readout / rooms, [1] aux / objects
+  // (null: unweighted).  They travel where the labels do: a field of the argument struct, or an argument, of every CE launch.
+  const float* class_w[2] = {nullptr, nullptr};
 
   // profiling
   bool prof = false;
@@ -1155,6 +1158,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           // masked cross entropy in the epilogue of the last aggregation (one kernel less on the step's critical path)
           D.ce_labels = n->call.ce_labels; D.ce_ignored = n->call.ce_ignored; D.ce_classes = n->out_dim;
           D.ce_grad = n->d_gout; D.ce_ldg = n->out_ld; D.ce_row_lv = n->d_row_lv;
+          D.ce_weight = n->class_w[0];
           n->call.ce_done = true;
         }
         D.n_rows = b->n_nodes[t];
@@ -1173,6 +1177,7 @@ int forward_impl(hmp_net* n, const hmp_batch* b, const float* d_params, hipStrea
           D.drop_on = (n->training && S.tail_dropout > 0.f) ? 1 : 0;
           if (D.drop_on) D.drop = make_drop(n, S.tail_dropout, (uint32_t)(l * HMP_MAX_NODE_TYPES + t));
           D.ce_labels = n->call.tgt->d_labels[head]; D.ce_mask = n->call.tgt->d_mask[head]; D.ce_tail = 1;
+          D.ce_weight = n->class_w[head];
           D.ce_ignored = n->call.ce_ignored; D.ce_classes = Ls.out_dim[t];
           D.ce_grad = head == 0 ? n->d_gout : n->G[n->L][t];
           D.ce_ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
@@ -1877,6 +1882,22 @@ extern "C" int hmp_net_set_head_pools(hmp_net* n, int32_t pool_edge_type_readout
   return HMP_OK;
 }
 
+extern "C" int hmp_net_set_class_weights(hmp_net* n, int32_t head, const float* d_w, int32_t n_w) {
+  HMP_CHECK_ARG(n, "hmp_net_set_class_weights: null net");
+  HMP_CHECK_ARG(head == 0 || head == 1, "hmp_net_set_class_weights: head %d (0 = readout / rooms, 1 = aux / objects)", head);
+  if (d_w == nullptr) {
+    n->class_w[head] = nullptr;
+    return HMP_OK;
+  }
+  const hmp_net_spec& S = n->spec;
+  HMP_CHECK_ARG(head == 0 || n->has_heads || S.aux_readout_type >= 0, "hmp_net_set_class_weights: the net has one head");
+  // the head's class count: a linear head's, or the width of the last layer on the head's node type
+  const int classes = n->has_heads ? n->heads.classes[head] : (S.aux_readout_type >= 0 ? n->dim[n->L][head_type(n, head)] : n->out_dim);
+  HMP_CHECK_ARG(n_w == classes, "hmp_net_set_class_weights: %d weights for head %d, which has %d classes", n_w, head, classes);
+  n->class_w[head] = d_w;
+  return HMP_OK;
+}
+
 extern "C" int hmp_net_set_linear_heads(hmp_net* n, const hmp_linear_heads* h) {
   HMP_CHECK_ARG(n && h, "hmp_net_set_linear_heads: null argument");
   const hmp_net_spec& S = n->spec;
@@ -1970,6 +1991,7 @@ void add_tail(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int he
   T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
   T.slot = head;
   if (!ce) return;
+  T.weight = n->class_w[head];
   T.grad = head == 0 ? n->d_gout : n->G[n->L][t];
   T.ldg = head == 0 ? n->out_ld : n->ld[n->L][t];
   T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_out);
@@ -1995,6 +2017,7 @@ void add_pool(hmp_net* n, const hmp_batch* b, const hmp_head_targets* tg, int he
   T.labels = tg->d_labels[head]; T.mask = tg->d_mask[head];
   T.slot = head;
   if (!ce) return;
+  T.weight = n->class_w[head];
   T.grad = n->G[n->L][t]; T.ldg = n->ld[n->L][t];
   T.dpool = n->d_dpool[head]; T.ldp = n->ld[n->L][t];
   T.row_lv = n->d_row_lv + (head == 0 ? 0 : 2 * (int64_t)b->n_nodes[label_type(n, 0)]);
@@ -2041,6 +2064,7 @@ LinHeadArgs heads_args(hmp_net* n, const hmp_batch* b, const hmp_linear_head_tar
   if (a.drop_on) a.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + S.readout_type));
   a.grad = n->d_gout; a.ldg = n->out_ld;
   a.row_lv = n->d_row_lv;
+  a.weight[0] = n->class_w[0]; a.weight[1] = n->class_w[1];
   a.slabs = n->d_slabs + n->head_slab_off; a.ld_slab = n->head_ld_slab; a.slab_stride = n->head_slab_stride;
   return a;
 }
@@ -2053,7 +2077,7 @@ int ce_loss(hmp_net* n, const hmp_batch* b, int64_t ignored, hipStream_t st, con
   if (n->call.ce_done) return HMP_OK;
   Scope sc(n, KC_LOSS, st);
   return masked_ce_rows_launch(out_ptr(n), n->out_ld, b->n_out, n->out_dim, b->d_labels, ignored, n->d_gout, n->out_ld, n->d_row_lv,
-                               n->d_state, st);
+                               n->d_state, st, n->class_w[0]);
 }
 
 // two heads: the tail + CE of the heads the last epilogue did not serve, in one stand-alone launch over their rows; pooled heads:

@@ -9,7 +9,11 @@ namespace hmp {
 // loss.  Unit entry point: one block, one wavefront per row, fixed-order reductions => deterministic.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ce_row(const float* __restrict__ lr, int n_classes, int64_t y, int64_t ignored, int lane,
-                                       float* __restrict__ grow, int ldg, float& loss, float& valid, int& bad) {
+                                       float* __restrict__ grow, int ldg, float& loss, float& valid, int& bad,
+                                       const float* __restrict__ w) {
+  // class weights (tail_fns.h: ce_group's rule): the pair is {w[y] * nll, w[y]}, the gradient is scaled by w[y], a row of weight
+  // 0 does not count; w == null: the unweighted bits.  Requested first: it depends on the label alone.
+  const float wy = ce_weight(w, y, n_classes);
   const bool is_valid = (y != ignored);
   if (is_valid && (y < 0 || y >= n_classes)) bad = 1;
   float m = -INFINITY;
@@ -21,21 +25,25 @@ __device__ __forceinline__ void ce_row(const float* __restrict__ lr, int n_class
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float lse = m + logf(s);
-  const bool use = is_valid && y >= 0 && y < n_classes;
+  const bool use = is_valid && y >= 0 && y < n_classes && !(w && wy == 0.f);
   if (grow) {
     for (int c = lane; c < ldg; c += 64) {
       float g = 0.f;
-      if (use && c < n_classes) g = expf(lr[c] - lse) - (c == (int)y ? 1.f : 0.f);
+      if (use && c < n_classes) {
+        g = expf(lr[c] - lse) - (c == (int)y ? 1.f : 0.f);
+        if (w) g *= wy;
+      }
       grow[c] = g;
     }
   }
-  loss = use ? (lse - lr[y]) : 0.f;
-  valid = use ? 1.f : 0.f;
+  loss = use ? (w ? wy * (lse - lr[y]) : (lse - lr[y])) : 0.f;
+  valid = use ? (w ? wy : 1.f) : 0.f;
 }
 
 __global__ __launch_bounds__(1024) void masked_ce_kernel(const float* __restrict__ logits, int ldl, int n_rows, int n_classes,
                                                          const int64_t* __restrict__ labels, int64_t ignored, float* __restrict__ grad,
-                                                         int ldg, float* __restrict__ out2, NetState* state) {
+                                                         int ldg, float* __restrict__ out2, NetState* state,
+                                                         const float* __restrict__ cw) {
   __shared__ float s_loss[16];
   __shared__ float s_cnt[16];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -43,7 +51,7 @@ __global__ __launch_bounds__(1024) void masked_ce_kernel(const float* __restrict
   int bad = 0;
   for (int row = w; row < n_rows; row += 16) {
     float l, v;
-    ce_row(logits + (int64_t)row * ldl, n_classes, labels[row], ignored, lane, grad ? grad + (int64_t)row * ldg : nullptr, ldg, l, v, bad);
+    ce_row(logits + (int64_t)row * ldl, n_classes, labels[row], ignored, lane, grad ? grad + (int64_t)row * ldg : nullptr, ldg, l, v, bad, cw);
     loss += l;
     cnt += v;
   }
@@ -60,8 +68,8 @@ __global__ __launch_bounds__(1024) void masked_ce_kernel(const float* __restrict
 }
 
 int masked_ce_launch(const float* logits, int ldl, int n_rows, int n_classes, const int64_t* labels, int64_t ignored, float* grad,
-                     int ldg, float* out2, NetState* state, hipStream_t st) {
-  hipLaunchKernelGGL(masked_ce_kernel, dim3(1), dim3(1024), 0, st, logits, ldl, n_rows, n_classes, labels, ignored, grad, ldg, out2, state);
+                     int ldg, float* out2, NetState* state, hipStream_t st, const float* w) {
+  hipLaunchKernelGGL(masked_ce_kernel, dim3(1), dim3(1024), 0, st, logits, ldl, n_rows, n_classes, labels, ignored, grad, ldg, out2, state, w);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
@@ -70,13 +78,14 @@ int masked_ce_launch(const float* logits, int ldl, int n_rows, int n_classes, co
 // fixed order by block (0,0) of the gradient un-pack kernel, which runs later in the same step anyway
 __global__ __launch_bounds__(256) void masked_ce_rows_kernel(const float* __restrict__ logits, int ldl, int n_rows, int n_classes,
                                                              const int64_t* __restrict__ labels, int64_t ignored, float* __restrict__ grad,
-                                                             int ldg, float* __restrict__ row_lv, NetState* state) {
+                                                             int ldg, float* __restrict__ row_lv, NetState* state,
+                                                             const float* __restrict__ cw) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;
   float l, v;
   int bad = 0;
-  ce_row(logits + (int64_t)row * ldl, n_classes, labels[row], ignored, lane, grad + (int64_t)row * ldg, ldg, l, v, bad);
+  ce_row(logits + (int64_t)row * ldl, n_classes, labels[row], ignored, lane, grad + (int64_t)row * ldg, ldg, l, v, bad, cw);
   if (lane == 0) {
     row_lv[2 * row] = l;
     row_lv[2 * row + 1] = v;
@@ -85,10 +94,10 @@ __global__ __launch_bounds__(256) void masked_ce_rows_kernel(const float* __rest
 }
 
 int masked_ce_rows_launch(const float* logits, int ldl, int n_rows, int n_classes, const int64_t* labels, int64_t ignored, float* grad,
-                          int ldg, float* row_lv, NetState* state, hipStream_t st) {
+                          int ldg, float* row_lv, NetState* state, hipStream_t st, const float* w) {
   if (n_rows == 0) return HMP_OK;
   hipLaunchKernelGGL(masked_ce_rows_kernel, dim3(cdiv(n_rows, 4)), dim3(256), 0, st, logits, ldl, n_rows, n_classes, labels, ignored,
-                     grad, ldg, row_lv, state);
+                     grad, ldg, row_lv, state, w);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
@@ -123,7 +132,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   float gscale = 1.f;
   if (d_count) {
     const float c = *d_count;
-    gscale = 1.f / (c > 1.f ? c : 1.f);
+    gscale = 1.f / (c > 0.f ? c : 1.f);  // a weight sum below 1 is a normaliser too; integer counts: the same bits
   }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float pi = p[i];
@@ -281,7 +290,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const GradSeg* __restr
       const float bc1 = 1.f - powf(adam.b1, (float)t);
       const float bc2 = 1.f - powf(adam.b2, (float)t);
       const float c = a_cnt;
-      const float gscale = 1.f / (c > 1.f ? c : 1.f);
+      const float gscale = 1.f / (c > 0.f ? c : 1.f);  // a weight sum below 1 is a normaliser too; integer counts: the same bits
       const int64_t e = S.dst + i;
       const float pi = a_p;
       const float gi = total * gscale + adam.wd * pi;
@@ -331,6 +340,14 @@ extern "C" int hmp_masked_ce(const float* d_logits, int32_t ldl, int32_t n_rows,
   HMP_CHECK_ARG(d_logits && d_labels && d_out2, "hmp_masked_ce: null pointer");
   HMP_CHECK_ARG(n_rows >= 0 && n_classes > 0 && ldl >= n_classes && (d_grad == nullptr || ldg >= n_classes), "hmp_masked_ce: bad shape");
   return masked_ce_launch(d_logits, ldl, n_rows, n_classes, d_labels, ignored_label, d_grad, ldg, d_out2, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int hmp_masked_ce_weighted(const float* d_logits, int32_t ldl, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
+                                      int64_t ignored_label, const float* d_w, float* d_grad, int32_t ldg, float* d_out2, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_logits && d_labels && d_out2, "hmp_masked_ce_weighted: null pointer");
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes > 0 && ldl >= n_classes && (d_grad == nullptr || ldg >= n_classes), "hmp_masked_ce_weighted: bad shape");
+  return masked_ce_launch(d_logits, ldl, n_rows, n_classes, d_labels, ignored_label, d_grad, ldg, d_out2, nullptr, (hipStream_t)stream, d_w);
 }
 
 extern "C" int hmp_argmax_rows(const float* d_x, int32_t ldx, int32_t n_rows, int32_t n_cols, int64_t* d_out, void* stream) {

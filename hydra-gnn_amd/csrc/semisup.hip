@@ -33,9 +33,11 @@ __global__ __launch_bounds__(256) void tail_ce_kernel(const TailArgs a) {
   const int row = tail_row(T);
   if (row >= T.n_rows) return;
   const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
+  const int64_t y = T.labels[row];
+  const float wy = ce_weight(T.weight, y, T.classes);
   // any width: the row's quads are recomputed from z in each of the CE's passes
   ce_group<TL_GS, 0>(
-      threadIdx.x % TL_GS, T.classes, T.ldg, T.labels[row], a.ignored, T.mask ? T.mask[row] != 0 : true,
+      threadIdx.x % TL_GS, T.classes, T.ldg, y, a.ignored, T.mask ? T.mask[row] != 0 : true,
       [&](int, int c, float (&v)[4]) { tail_quad(T, cfg, a.act, row, c, v); },
       [&](int c, float (&g)[4], const float (&v)[4]) {  // y is what the CE read: chain back to z
 #pragma unroll
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(256) void tail_ce_kernel(const TailArgs a) {
           if (c + i < T.classes) g[i] *= tail_dydz(v[i], a.act, T.drop_on != 0, cfg.scale);
         *reinterpret_cast<float4*>(T.grad + (int64_t)row * T.ldg + c) = make_float4(g[0], g[1], g[2], g[3]);
       },
-      T.row_lv, row, a.state);
+      T.row_lv, row, a.state, T.weight, wy);
 }
 
 // ---- pooled heads (HeterogeneousNeuralTreeNetwork, reference heterogeneous_neural_tree_network.py:186-205) ------------------
@@ -90,6 +92,7 @@ __global__ __launch_bounds__(256) void pool_ce_kernel(const TailArgs a) {
   const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
   const int64_t y = T.labels[v];
   const bool in_mask = T.mask ? T.mask[v] != 0 : true;
+  const float wy = ce_weight(T.weight, y, T.classes);  // requested before the pool's gather
   float p[PT_Q][4];
   const int deg = pool_row(T, cfg, a.act, v, lane, p);
   const float r = 1.0f / (float)(deg > 1 ? deg : 1);  // the mean's backward: every leaf edge carries 1 / max(deg, 1)
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256) void pool_ce_kernel(const TailArgs a) {
       [&](int c, float (&g)[4], const float (&)[4]) {
         *reinterpret_cast<float4*>(T.dpool + (int64_t)v * T.ldp + c) = make_float4(g[0] * r, g[1] * r, g[2] * r, g[3] * r);
       },
-      T.row_lv, v, a.state);
+      T.row_lv, v, a.state, T.weight, wy);
 }
 
 __global__ __launch_bounds__(256) void pool_grad_kernel(const TailArgs a) {
@@ -301,8 +304,9 @@ int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* p
 }  // namespace hmp
 
 // test / diagnostic entry of the five tail launchers: a plain copy of the descriptors into TailArgs, no choice of its own
-extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
-                              int64_t* d_counts, void* stream) {
+// (d_w: the class weights of each head for the CE modes, null: unweighted)
+static int head_tails_run(const hmp_tail_desc* d, int32_t n, const float* const* d_w, int32_t mode, int32_t act, int64_t ignored,
+                          int32_t* d_state, int64_t* d_counts, void* stream) {
   using namespace hmp;
   static const bool have_device = hmp_device_count() > 0;
   HMP_CHECK_ARG(have_device, "hmp_head_tails: no gfx950 device visible");
@@ -319,6 +323,7 @@ extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, i
     HeadTail& T = ta.h[i];
     T.z = q.z; T.ldz = q.ldz; T.n_rows = q.n_rows; T.classes = q.classes;
     T.labels = q.labels; T.mask = q.mask;
+    if (ce && d_w) T.weight = d_w[i];
     T.grad = q.grad; T.ldg = q.ldg; T.row_lv = q.row_lv;
     T.slot = q.slot;
     T.rowptr = q.rowptr; T.col = q.col; T.t_rowptr = q.t_rowptr; T.t_col = q.t_col;
@@ -338,6 +343,16 @@ extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, i
     case 2: HMP_TRY(pool_tail_ce_launch(ta, st)); return pool_tail_grad_launch(ta, st);
     default: return pool_tail_count_launch(ta, (long long*)d_counts, st);
   }
+}
+
+extern "C" int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
+                              int64_t* d_counts, void* stream) {
+  return head_tails_run(d, n, nullptr, mode, act, ignored, d_state, d_counts, stream);
+}
+
+extern "C" int hmp_head_tails_weighted(const hmp_tail_desc* d, int32_t n, const float* const* d_w, int32_t mode, int32_t act,
+                                       int64_t ignored, int32_t* d_state, int64_t* d_counts, void* stream) {
+  return head_tails_run(d, n, d_w, mode, act, ignored, d_state, d_counts, stream);
 }
 
 // the descriptors of a label / top-k launch (labels, mask, grad, row_lv and dpool may be NULL) as TailArgs, eval mode

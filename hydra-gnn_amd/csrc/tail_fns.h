@@ -59,11 +59,20 @@ __device__ __forceinline__ void lane_quads(int lane, int width, F&& f) {
 // registers recomputes it.  put(c, g, v) receives d(SUM loss) / d logits of every quad below `ldg` -- 0 for a row that does not
 // count and past `classes`, where v is 0 too -- and chains and stores it.  Lane 0 writes the row's {loss, valid} pair and raises
 // status bit 1 for a label outside [0, classes).
+// Class weights (F.cross_entropy(weight = w)): with w != null the caller hands in wy = ce_weight(w, y, classes), requested wherever
+// its label arrives; the gradient quads are multiplied by wy before put and the pair becomes {wy * (lse - ly), wy}, so every
+// consumer of {loss_sum, count} computes sum(w * nll) / sum(w).  A row of weight 0 does not count, exactly as an ignored one.
+// w == null: wy is not looked at and the bits are those of the unweighted loss.
 // Association: max, sum of expf and the label's logit accumulate per lane in ascending column order, then an xor butterfly below
 // GS (inside the GS-aligned row group) -- the same whatever NQ, so every caller computes the same bits for the same row.
+// w[y] of a label inside [0, classes) -- an unchecked label never indexes w (it has `classes` entries) -- and 1 without weights
+__device__ __forceinline__ float ce_weight(const float* __restrict__ w, int64_t y, int classes) {
+  return (w && y >= 0 && y < classes) ? w[y] : 1.f;
+}
+
 template <int GS, int NQ, class Quad, class Put>
 __device__ __forceinline__ void ce_group(int lane, int classes, int ldg, int64_t y, int64_t ignored, bool in_mask, Quad&& quad, Put&& put,
-                                         float* __restrict__ row_lv, int row, NetState* state) {
+                                         float* __restrict__ row_lv, int row, NetState* state, const float* w = nullptr, float wy = 1.f) {
   float m = -INFINITY;
   lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
     float v[4];
@@ -93,7 +102,7 @@ __device__ __forceinline__ void ce_group(int lane, int classes, int ldg, int64_t
   const float lse = m + logf(s);
   const bool valid = in_mask && y != ignored;
   const bool bad = valid && (y < 0 || y >= classes);
-  const bool use = valid && !bad;
+  const bool use = valid && !bad && !(w && wy == 0.f);
   lane_quads<GS, NQ>(lane, ldg, [&](int q, int c) {
     float g[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
     if (use && c < classes) {
@@ -101,12 +110,16 @@ __device__ __forceinline__ void ce_group(int lane, int classes, int ldg, int64_t
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (c + i < classes) g[i] = expf(v[i] - lse) - ((int64_t)(c + i) == y ? 1.f : 0.f);
+      if (w) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] *= wy;
+      }
     }
     put(c, g, v);
   });
   if (lane == 0) {
-    row_lv[2 * row] = use ? (lse - ly) : 0.f;
-    row_lv[2 * row + 1] = use ? 1.f : 0.f;
+    row_lv[2 * row] = use ? (w ? wy * (lse - ly) : (lse - ly)) : 0.f;
+    row_lv[2 * row + 1] = use ? (w ? wy : 1.f) : 0.f;
     if (bad && state) atomicOr(&state->status, 2);
   }
 }

@@ -200,6 +200,9 @@ SIGNATURES = {
     "hmp_saliency_scores": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), _VP, _VP, _VP, _VP]),
     "hmp_saliency_topk": (C.c_int, [Plan, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _VP, _VP, _VP]),
     "hmp_masked_ce": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _I32, _VP, _VP]),
+    "hmp_masked_ce_weighted": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I64, _VP, _VP, _I32, _VP, _VP]),
+    "hmp_label_counts": (C.c_int, [_VP, _I64, _VP, _I64, _I32, _VP, _VP]),
+    "hmp_balanced_class_weights": (C.c_int, [_VP, _I32, _VP, _VP]),
     "hmp_argmax_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "hmp_count_correct_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
     "hmp_count_correct_rows_by_graph": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _I32, _VP, _VP]),
@@ -208,9 +211,11 @@ SIGNATURES = {
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
     "hmp_head_tails": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I64, _VP, _VP, _VP]),
+    "hmp_head_tails_weighted": (C.c_int, [C.POINTER(TailDesc), _I32, C.POINTER(_VP), _I32, _I32, _I64, _VP, _VP, _VP]),
     "hmp_head_tails_predict": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, C.POINTER(_VP), _VP]),
     "hmp_head_tails_topk": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_linear_heads_run": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
+    "hmp_linear_heads_run_weighted": (C.c_int, [C.POINTER(LinearHeadsDesc), C.POINTER(_VP), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
     "hmp_linear_heads_predict": (C.c_int, [C.POINTER(LinearHeadsDesc), C.POINTER(_VP), C.POINTER(_I32), _VP]),
     "hmp_linear_heads_topk": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I32), _VP]),
     "hmp_net_create": (C.c_int, [C.POINTER(NetSpec), C.POINTER(_VP)]),
@@ -229,6 +234,7 @@ SIGNATURES = {
     "hmp_net_count_correct2": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(HeadTargets), _VP, _VP, _VP]),
     "hmp_net_set_linear_heads": (C.c_int, [_VP, C.POINTER(LinearHeads)]),
     "hmp_net_set_head_pools": (C.c_int, [_VP, _I32, _I32]),
+    "hmp_net_set_class_weights": (C.c_int, [_VP, _I32, _VP, _I32]),
     "hmp_net_step_heads_fwd_bwd": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, C.POINTER(TrainArgs), _VP]),
     "hmp_net_step_heads_fused": (C.c_int, [_VP, C.POINTER(Batch), C.POINTER(LinearHeadTargets), _VP, _VP, _VP, _VP,
                                            C.POINTER(TrainArgs), _VP]),

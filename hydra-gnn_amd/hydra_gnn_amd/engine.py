@@ -118,7 +118,12 @@ class _BatchHolder:
         self.max_rows: Dict[int, int] = {}
 
 
+_NO_CLASS_W = ()  # the unweighted step's (empty) class-weight tuple: compared by identity
+
+
 class NativeNet:
+    _class_w = _NO_CLASS_W  # set_class_weights: the vectors the library currently borrows (one per head)
+
     def __init__(self, node_types: Sequence[str], in_dims: Dict[str, int], edge_types: Sequence[EdgeType],
                  layers: List[LayerDesc], readout: str, pool_edge_type: Optional[EdgeType] = None,
                  count_types: Sequence[str] = (), aux_readout: Optional[str] = None, tail: Optional[Tuple[int, float]] = None,
@@ -332,7 +337,32 @@ class NativeNet:
             if self.head_pools is not None:
                 ets = [self.edge_types.index(e) if e is not None else -1 for e in self.head_pools]
                 _lib.check(self._lib.hmp_net_set_head_pools(h, *ets))
+            self._push_class_weights()
         return self._handle
+
+    # ---- class weights of the cross entropy ----------------------------------------------------------
+    def head_classes(self) -> Tuple[int, ...]:
+        """class count of every head: (readout,) or (readout / rooms, aux / objects)"""
+        if self.heads is not None:
+            return tuple(int(lin.out_features) for lin in self.heads)
+        out = self.layers[-1].out_dims
+        if self.aux_readout is not None:
+            return int(out[self.readout]), int(out[self.aux_readout])
+        return (int(out[self.readout]),)
+
+    def set_class_weights(self, weights) -> None:
+        """``weights``: one float32 device vector (or None) per head -- the class weights of every later training step of this
+        net (``hmp_net_set_class_weights``; the library borrows the pointers, this object keeps the tensors alive)."""
+        self._class_w = weights
+        if self._handle is not None:
+            self._push_class_weights()
+
+    def _push_class_weights(self) -> None:
+        ws = tuple(self._class_w)
+        for head in range(2):  # a head without an entry is cleared
+            w = ws[head] if head < len(ws) else None
+            _lib.check(self._lib.hmp_net_set_class_weights(self._handle, head, w.data_ptr() if w is not None else None,
+                                                           w.numel() if w is not None else 0))
 
     def head_label_types(self) -> Tuple[str, str]:
         """node types whose rows carry the labels of the (readout, aux) heads: the pool destination of a pooled head"""
@@ -1456,6 +1486,7 @@ class TrainStep:
         self.step_ctr = torch.zeros(4, dtype=torch.int32, device=dev)
         self.args.d_step = self.step_ctr.data_ptr()
         self._holder = None
+        self._class_w = _NO_CLASS_W  # set_class_weight: one device vector (or None) per head; the identity of the tuple is the key
         self._targets = ()  # the entries' arguments between the batch and the parameters: byref(targets) but for one head
         self._batch_key = None
         self._data_ref = None
@@ -1487,6 +1518,37 @@ class TrainStep:
 
             parallel.allreduce_flat(self.grads, self.net.n_active, group=None if self.pg is True else self.pg,
                                     force=self.force_collective)
+
+    def set_class_weight(self, weight) -> None:
+        """Class weights of the step's cross entropy, ``F.cross_entropy(..., weight=w)``: from the next step on the loss is
+        ``sum(w[y] * nll) / sum(w[y])`` over the valid labels, and Adam divides the summed gradients by that sum of weights.
+        ``weight``: a float32 device tensor or a sequence of floats with one entry per class; for a two-headed step a pair
+        ``(w_rooms, w_objects)`` or a dict ``{"rooms": w, "objects": w}`` (a missing or None entry leaves that head unweighted);
+        None restores the unweighted step bit for bit.  The step keeps the tensors alive.  No launch is added; captured graphs
+        hold the pointers as kernel arguments and are re-captured."""
+        from .models.utils import class_weight_tensor
+
+        classes = self.net.head_classes()
+        if weight is None:
+            per_head = [None] * len(classes)
+        elif isinstance(weight, dict):
+            unknown = set(weight) - {"rooms", "objects", "room", "object"}
+            if unknown or len(classes) != 2:
+                raise _lib.HydraMPError(f"class_weight: a dict names the heads 'rooms' and 'objects' of a two-headed step (got "
+                                        f"{sorted(weight)} for {len(classes)} head(s))")
+            per_head = [weight.get("rooms", weight.get("room")), weight.get("objects", weight.get("object"))]
+        elif len(classes) == 2:
+            if isinstance(weight, torch.Tensor) or len(weight) != 2:
+                raise _lib.HydraMPError("class_weight: a two-headed step takes a pair (w_rooms, w_objects) or a dict")
+            per_head = list(weight)
+        else:
+            per_head = [weight]
+        dev = self.flat.device
+        names = ("class_weight",) if len(classes) == 1 else ("class_weight[rooms]", "class_weight[objects]")
+        ws = tuple(None if w is None else class_weight_tensor(w, c, dev, nm) for w, c, nm in zip(per_head, classes, names))
+        self._class_w = _NO_CLASS_W if all(w is None for w in ws) else ws
+        self._destroy_graphs()
+        self._key = None
 
     def _phase_a(self, h, st):
         net = self.net
@@ -1537,6 +1599,8 @@ class TrainStep:
             self._batch_key = key if not h.converted else None
             self._data_ref = (data, tensors)  # keeps id() unique while the key is live
         self._holder = h
+        if net._class_w is not self._class_w:  # the weights are the net's (every step form reads them there): make them this step's
+            net.set_class_weights(self._class_w)
         dev = self.flat.device
         with torch.cuda.device(dev):
             net._ensure_workspace(h, dev)
@@ -1621,6 +1685,8 @@ class TrainStep:
         net._plan_key = net._plan_tensors = None
         self._batch_key = None
         self._holder = holder
+        if net._class_w is not self._class_w:
+            net.set_class_weights(self._class_w)
         self._eager(holder)
 
     def set_lr(self, lr: float) -> None:
@@ -1636,10 +1702,11 @@ class TrainStep:
         return int(self.step_ctr[0].item())
 
     def loss(self) -> float:
-        """mean CE over the valid labels of the last step (global when data parallel); synchronises."""
+        """mean CE over the valid labels of the last step (global when data parallel); with class weights the weight-normalised
+        mean ``sum(w * nll) / sum(w)``.  Synchronises."""
         t = self.grads[self.net.n_active: self.net.n_active + 2].tolist()
         self.net.check_status()
-        return t[0] / max(t[1], 1.0)
+        return t[0] / (t[1] if t[1] > 0.0 else 1.0)  # a sum of weights below 1 is a normaliser too; no valid label: 0
 
 
 class TwoHeadTrainStep(TrainStep):

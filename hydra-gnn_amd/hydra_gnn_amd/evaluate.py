@@ -12,6 +12,7 @@ ONCE at the end of the pass.
     acc = evaluate.accuracy(model, val_batches)                            # batches already on the device
     acc = evaluate.accuracy(model, (stream, id_lists))                     # store.BatchStream + graph ids per batch
     acc, matrix = evaluate.accuracy(model, val_batches, per_label=True)    # test(loader, get_per_label_accuracy=True)
+    acc, bal = evaluate.accuracy(model, val_batches, balanced=True)        # + mean per-class recall (balanced accuracy)
 
 The per-label matrix is the reference's ``(C - 1) x C`` int array (``accuracy_matrix[l, p]`` = rows of label ``l`` predicted
 as ``p``; the ``ignored_label`` row stays zero), summed over the pass.  The reference's loop ASSIGNS each batch's matrix, so
@@ -40,6 +41,23 @@ def accuracy_matrix(confusion, ignored_label: int = 25) -> np.ndarray:
     return out
 
 
+def balanced_accuracy(confusion) -> float:
+    """Mean per-class recall over the classes with support, from a ``[C, C]`` (or ``[C * C]``) confusion matrix
+    ``confusion[label, pred]``: ``mean_c conf[c, c] / sum_p conf[c, p]`` over the rows with a non-zero sum (scikit-learn's
+    ``balanced_accuracy_score``).  The measure that class-weighted training moves; a matrix without any counted row raises
+    ZeroDivisionError, as the plain accuracy of such a pass does."""
+    conf = confusion.detach().cpu().numpy() if isinstance(confusion, torch.Tensor) else np.asarray(confusion)
+    C = int(round(np.sqrt(conf.size)))
+    if C * C != conf.size:
+        raise ValueError(f"confusion matrix of {conf.size} entries is not square")
+    conf = conf.reshape(C, C).astype(np.int64)
+    support = conf.sum(axis=1)
+    have = support > 0
+    if not have.any():
+        raise ZeroDivisionError("balanced accuracy of a pass without labelled rows")
+    return float(np.mean(np.diag(conf)[have].astype(np.float64) / support[have].astype(np.float64)))
+
+
 def _n_classes(model) -> int:
     op_path = getattr(model, "op_path", False)
     if op_path:  # GCN / GIN: the width of the last conv
@@ -48,16 +66,19 @@ def _n_classes(model) -> int:
     return model.native().n_classes
 
 
-def accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], ignored_label: int = 25, per_label: bool = False):
+def accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], ignored_label: int = 25, per_label: bool = False,
+             balanced: bool = False):
     """``correct / total`` of the room task over ``batches`` (``BaseTrainingJob.test``), accumulated on the device with ONE
     synchronisation at the end.  ``batches``: an iterable of batches on the model's device, or a ``(BatchStream, iterable of
-    graph-id lists)`` pair.  With ``per_label=True`` returns ``(accuracy, accuracy_matrix)``."""
+    graph-id lists)`` pair.  With ``per_label=True`` returns ``(accuracy, accuracy_matrix)``.  ``balanced=True`` appends the
+    mean per-class recall over the classes with support (:func:`balanced_accuracy`) to the result, from the confusion counters
+    the count launches fill anyway: no launch and no synchronisation more."""
     from .store import BatchStream
 
     dev = next(model.parameters()).device
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     confusion = None
-    if per_label:
+    if per_label or balanced:
         C = _n_classes(model)
         confusion = torch.zeros(C * C, dtype=torch.int64, device=dev)
     if isinstance(batches, tuple) and len(batches) == 2 and isinstance(batches[0], BatchStream):
@@ -71,7 +92,8 @@ def accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], ignored_l
     host = (torch.cat([counts[:2], confusion]) if confusion is not None else counts[:2]).cpu()
     correct, total = int(host[0]), int(host[1])
     acc = correct / total  # the reference's division (a pass without labelled rows raises ZeroDivisionError there too)
-    return (acc, accuracy_matrix(host[2:], ignored_label)) if per_label else acc
+    out = (acc,) + ((accuracy_matrix(host[2:], ignored_label),) if per_label else ()) + ((balanced_accuracy(host[2:]),) if balanced else ())
+    return out if len(out) > 1 else acc
 
 
 def semisupervised_accuracy(model, batches: Union[Iterable, Tuple[object, Iterable]], mask_name: str = "test_mask",

@@ -27,6 +27,16 @@ passes are never shuffled: their integer counts do not depend on the order.  The
 too and so draws extra seeds from the global generator every epoch -- a run here and a run of the reference under the same
 ``torch.manual_seed`` see different training permutations from the second epoch on.
 
+Class weights.  ``optimization_params["class_weight"]``: None (the default: the unweighted loss), ``"balanced"`` or explicit
+weights (a tensor or a sequence with one entry per class); the semi-supervised job also takes a dict per head,
+``{"rooms": ..., "objects": ...}``.  ``"balanced"`` is computed on the device from the training split's resident store
+(``GraphStore.class_weights``; the semi-supervised job: the rows of ``train_mask``) at the start of ``train()``, after the node
+split of that run.  The weights reach the fused step (``train_step(class_weight=...)``) and the GCN / GIN body
+(``net.loss(..., weight=...)``) alike.  The loss is then ``sum(w[y] * nll) / sum(w[y])``, and the epoch's logged loss of the
+room job is that weight-normalised mean over the epoch (the steps' weighted sums over the steps' sums of weights); the
+semi-supervised job keeps ``sum(batch loss * num_graphs) / len(dataset)`` with the batch loss weight-normalised.  Validation and
+test accuracies do not depend on the weights; ``test(..., get_balanced_accuracy=True)`` adds the mean per-class recall.
+
 Scalars go to ``tensorboardX.SummaryWriter(log_folder)`` when that module is installed, else to ``log_folder/scalars.json``
 (``{"loss": [...], "validation result": [...]}``); both are written after the loop from the device log.
 """
@@ -255,19 +265,38 @@ class BaseTrainingJob:
             return batch.y[batch.room_mask]
         return batch[self._label_type()].y
 
+    def _class_weight(self, device, opt_params):
+        """``optimization_params["class_weight"]`` resolved for the room head: None, or a float32 device vector -- "balanced" from
+        the training split's resident store, explicit weights as they are"""
+        from .models.utils import class_weight_tensor
+
+        spec = opt_params.get("class_weight")
+        if spec is None:
+            return None
+        C = evaluate._n_classes(self._net)
+        if isinstance(spec, str):
+            from .store import check_weight_scheme
+
+            check_weight_scheme(spec)
+            store = self._store("train", self.get_dataset("train"), device)
+            label_type = "rooms" if store.homogeneous else self._label_type()
+            return store.class_weights(label_type, n_classes=C, ignored_label=self.ignored_label(), scheme=spec)
+        return class_weight_tensor(spec, C, device, 'optimization_params["class_weight"]')
+
     def _make_trainer(self, device, opt_params):
         """(train_batch(ids, book), count_batch(split, ids, counts, confusion), set_lr(lr)) for the room task"""
         net, ignored = self._net, self.ignored_label()
         B = opt_params["batch_size"]
         lr, wd = opt_params["lr"], opt_params["weight_decay"]
+        cw = self._class_weight(device, opt_params)
         if self._streams_batches():
             streams = {s: self._stream(s, self.get_dataset(s), device, B) for s in ("train", "val", "test")}
-            step = net.train_step(lr=lr, weight_decay=wd, ignored_label=ignored, use_graph=False)
+            step = net.train_step(lr=lr, weight_decay=wd, ignored_label=ignored, use_graph=False, class_weight=cw)
             tail = step.grads[net.native().n_active:]
 
             def train_batch(ids, book):
                 step.run(streams["train"].next(ids))
-                book.accumulate(tail, tail[1:])  # {loss_sum, count}: weight = the valid-label count
+                book.accumulate(tail, tail[1:])  # {loss_sum, count}: weight = the valid-label count (weighted: the sum of weights)
 
             def count_batch(split, ids, counts, confusion=None):
                 net.count_correct_rooms(streams[split].next(ids), counts, confusion, ignored)
@@ -286,10 +315,15 @@ class BaseTrainingJob:
             pred = net(b)
             label = self._room_labels(b)
             mask = label != ignored
-            loss = net.loss(pred, label, mask)
+            loss = net.loss(pred, label, mask, weight=cw)
             loss.backward()
             opt.step()
-            book.accumulate(loss.detach(), None, mask.sum())
+            if cw is None:
+                book.accumulate(loss.detach(), None, mask.sum())
+            else:  # {weighted sum, sum of weights}, as the fused step's tail: the epoch's loss is their ratio over the epoch
+                ws = (cw[label.clamp(0, cw.numel() - 1)] * (mask & (label >= 0) & (label < cw.numel()))).sum()
+                pair = torch.stack([loss.detach() * ws, ws])
+                book.accumulate(pair, pair[1:])
 
         def set_lr(value):
             for group in opt.param_groups:
@@ -402,9 +436,10 @@ class BaseTrainingJob:
         n = self._split_sizes()[self.TEST_SPLIT]
         return self._pass_accuracy(count_batch, self.TEST_SPLIT, id_chunks(n, batch_size), device)
 
-    def test(self, data_loader, get_per_label_accuracy=False):
+    def test(self, data_loader, get_per_label_accuracy=False, get_balanced_accuracy=False):
         """``BaseTrainingJob.test`` (:269-313) with one synchronisation per pass.  ``data_loader``: a split name (``"train"`` /
-        ``"val"`` / ``"test"``: the job's own device-resident copy, in ``batch_size`` batches) or an iterable of batches."""
+        ``"val"`` / ``"test"``: the job's own device-resident copy, in ``batch_size`` batches) or an iterable of batches.
+        ``get_balanced_accuracy=True`` appends the mean per-class recall (``evaluate.accuracy(..., balanced=True)``)."""
         net = self._net
         net.eval()
         device = next(net.parameters()).device
@@ -417,8 +452,9 @@ class BaseTrainingJob:
                 else:
                     store = self._store(data_loader, dataset, device)
                     batches = (store.collate(ids) for ids in id_chunks(len(dataset), B))
-                return evaluate.accuracy(net, batches, self.ignored_label(), get_per_label_accuracy)
-        return evaluate.accuracy(net, (b.to(device) for b in data_loader), self.ignored_label(), get_per_label_accuracy)
+                return evaluate.accuracy(net, batches, self.ignored_label(), get_per_label_accuracy, get_balanced_accuracy)
+        return evaluate.accuracy(net, (b.to(device) for b in data_loader), self.ignored_label(), get_per_label_accuracy,
+                                 get_balanced_accuracy)
 
     def predict(self, split):
         """Predicted labels of every graph of the split ``"train"`` / ``"val"`` / ``"test"``, from the job's own device-resident copy
@@ -554,14 +590,57 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
                 counts[2 * k] += p.argmax(dim=1)[m].eq(l[m]).sum()
                 counts[2 * k + 1] += m.sum()
 
+    def _head_classes(self) -> Tuple[int, int]:
+        net = self._net
+        if self._op_path():
+            return int(net.post_mp_room.out_features), int(net.post_mp_object.out_features)
+        return tuple(net.native().head_classes())
+
+    def _class_weight(self, device, opt_params):
+        """``optimization_params["class_weight"]`` resolved per head: None, or a pair (rooms, objects) of float32 device vectors
+        / None -- "balanced" from the rows of ``train_mask`` in the resident store, explicit weights as they are"""
+        from .models.utils import class_weight_tensor
+        from .store import check_weight_scheme
+
+        spec = opt_params.get("class_weight")
+        if spec is None:
+            return None
+        if isinstance(spec, dict):
+            unknown = set(spec) - {"rooms", "objects"}
+            if unknown:
+                raise _lib.HydraMPError(f'optimization_params["class_weight"]: the heads are "rooms" and "objects", got {sorted(unknown)}')
+            per_head = [spec.get("rooms"), spec.get("objects")]
+        elif isinstance(spec, str):
+            per_head = [spec, spec]
+        else:
+            if isinstance(spec, torch.Tensor) or len(spec) != 2:
+                raise _lib.HydraMPError('optimization_params["class_weight"]: the two-headed job takes "balanced", a pair or a dict '
+                                        '{"rooms": ..., "objects": ...}')
+            per_head = list(spec)
+        store = self._store("all", self._dataset, device)
+        if store.homogeneous:
+            types = ("rooms", "objects")
+        else:
+            types = ("rooms", "objects") if self._network_type == "baseline" else ("room_virtual", "object_virtual")
+        out = []
+        for name, w, t, C in zip(("rooms", "objects"), per_head, types, self._head_classes()):
+            if isinstance(w, str):
+                check_weight_scheme(w)
+                w = store.class_weights(t, mask="train_mask", n_classes=C, ignored_label=-100, scheme=w)
+            elif w is not None:
+                w = class_weight_tensor(w, C, device, f'optimization_params["class_weight"][{name}]')
+            out.append(w)
+        return None if all(w is None for w in out) else tuple(out)
+
     def _make_trainer(self, device, opt_params):
         net = self._net
         B, lr, wd = opt_params["batch_size"], opt_params["lr"], opt_params["weight_decay"]
         hetero = self._graph_type != "homogeneous"
         self._pass_mask = "val_mask"  # mask of the counting passes: val during the loop, train (verbose) / test around it
+        cw = self._class_weight(device, opt_params)
         if self._streams_batches():
             stream = self._stream("all", self._dataset, device, B)
-            step = net.semisupervised_step(lr=lr, weight_decay=wd, use_graph=False)
+            step = net.semisupervised_step(lr=lr, weight_decay=wd, use_graph=False, class_weight=cw)
             tail = step.grads[net.native().n_active:]
 
             def train_batch(ids, book):
@@ -583,7 +662,7 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
             opt.zero_grad()
             pred = net(b)
             label, mask = self._targets(b, "train_mask")
-            loss = net.loss(pred, label, mask)
+            loss = net.loss(pred, label, mask, weight=cw)
             loss.backward()
             opt.step()
             book.accumulate(loss.detach(), None, None, float(len(ids)))

@@ -54,14 +54,18 @@ class _NativeModule(nn.Module):
         return ops.bias_act_drop(x, None, relu=not gat, elu=gat, p=self.dropout if self.training else 0.0, seed=self._seed,
                                  rng_step=self._rng_step, rng_stream=stream)
 
-    def train_step(self, lr, weight_decay=0.0, **kw):
-        """Fused native training step (fwd + masked CE + bwd [+ all-reduce] + Adam), see engine.TrainStep."""
+    def train_step(self, lr, weight_decay=0.0, class_weight=None, **kw):
+        """Fused native training step (fwd + masked CE + bwd [+ all-reduce] + Adam), see engine.TrainStep.  ``class_weight``:
+        the class weights of the cross entropy (``TrainStep.set_class_weight``), None = unweighted."""
         from ..engine import TrainStep
 
         if getattr(self, "classification_task", "room") != "room":
             raise NotImplementedError("the fused training step computes ONE masked cross entropy (room labels); the two-headed "
                                       "task has its own fused step: semisupervised_step()")
-        return TrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=getattr(self, "_view", None), **kw)
+        step = TrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=getattr(self, "_view", None), **kw)
+        if class_weight is not None:
+            step.set_class_weight(class_weight)
+        return step
 
     def predict(self, data):
         """Room labels of ``data`` on the host: ``self(data).argmax(dim=1).cpu()`` as ``GnnModel.infer`` computes it
@@ -230,8 +234,8 @@ class _NativeModule(nn.Module):
         net = self._saliency_net("explain_rooms")
         return net.explain_salient(self._attention_input(data), self._EXPLAIN_EDGE, k, target=target, wrt=wrt)
 
-    def loss(self, pred, label, mask=None):
-        return cross_entropy_loss(pred, label, mask)
+    def loss(self, pred, label, mask=None, weight=None):
+        return cross_entropy_loss(pred, label, mask, weight)
 
     _ROOM_LABELS = "rooms"  # node type whose `y` BaseTrainingJob.test compares with (base_training_job.py:283-291)
 
@@ -301,7 +305,7 @@ class _HeteroTwoHead(_NativeModule):
     """The two-headed task's native entries, shared by the heterogeneous models built with ``output_dim_dict``
     (HeterogeneousNetwork: the final states; HeterogeneousNeuralTreeNetwork: their LeafPool, ``NativeNet.head_pools``)."""
 
-    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
+    def semisupervised_step(self, lr, weight_decay=0.0, class_weight=None, **kw):
         """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body), see
         engine.TwoHeadTrainStep: ``step(data, labels=(y_rooms, y_objects), masks=(m_rooms, m_objects))``.  The dropout seed is
         the module's, so the masks are the ones ``forward()`` draws at the same step number.  HeterogeneousNeuralTreeNetwork:
@@ -312,7 +316,10 @@ class _HeteroTwoHead(_NativeModule):
             raise _lib.HydraMPError("semisupervised_step: the model has one output (build it with output_dim_dict for the "
                                     "two-headed task); use train_step()")
         kw.setdefault("seed", self._seed)
-        return TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
+        step = TwoHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, **kw)
+        if class_weight is not None:  # a pair (w_rooms, w_objects) or a dict {"rooms": w, "objects": w}
+            step.set_class_weight(class_weight)
+        return step
 
     def count_correct(self, data, labels=None, masks=None, counts=None):
         """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode

@@ -125,7 +125,7 @@ class HomogeneousNetwork(_NativeModule):
         if self.op_path:
             raise HydraMPError(f"{what}: {self.conv_block} runs op by op; the fused two-head step covers GraphSAGE / GAT / GAT_edge")
 
-    def semisupervised_step(self, lr, weight_decay=0.0, **kw):
+    def semisupervised_step(self, lr, weight_decay=0.0, class_weight=None, **kw):
         """Fused native step of the two-headed task (``SemiSupervisedTrainingJob.train``'s loop body, homogeneous branch), see
         engine.LinearHeadTrainStep: ``step(data, labels=None, mask=None)`` with ``data.y`` / ``data.train_mask`` as defaults and
         the head rows from ``data.room_mask``.  The dropout seed is the module's, so the masks are the ones ``forward()`` draws at
@@ -134,8 +134,11 @@ class HomogeneousNetwork(_NativeModule):
 
         self._check_two_head("semisupervised_step")
         kw.setdefault("seed", self._seed)
-        return LinearHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=self._view, object_attr=self._OBJECT_ATTR,
+        step = LinearHeadTrainStep(self.native(), lr=lr, weight_decay=weight_decay, view=self._view, object_attr=self._OBJECT_ATTR,
                                    **kw)
+        if class_weight is not None:  # a pair (w_rooms, w_objects) or a dict {"rooms": w, "objects": w}
+            step.set_class_weight(class_weight)
+        return step
 
     def count_correct(self, data, mask_name="test_mask", counts=None):
         """The per-batch arithmetic of ``SemiSupervisedTrainingJob.test`` (semisupervised_training_job.py:198-257): eval-mode

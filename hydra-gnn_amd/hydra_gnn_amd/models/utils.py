@@ -249,9 +249,66 @@ class _MaskedCE(torch.autograd.Function):
         return grad * (g / out2[1]), None
 
 
-def cross_entropy_loss(pred, label, mask=None):
-    """reference models/utils.py:143-161 (tensor form = mean CE over ``mask``; list form = sum / count)."""
+class _WeightedCE(torch.autograd.Function):
+    """``F.cross_entropy(pred[mask], label[mask], weight=w, reduction="sum")`` and the sum of the rows' weights, one native
+    launch: ``(sum_i w[y_i] * nll_i, sum_i w[y_i])``.  Only the first output carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, label_eff, weight):
+        lib = _lib.require_device()
+        pred = pred.contiguous()
+        n, c = pred.shape
+        grad = torch.empty_like(pred)
+        out2 = torch.empty(2, dtype=torch.float32, device=pred.device)
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.hmp_masked_ce_weighted(pred.data_ptr(), pred.stride(0), n, c, label_eff.data_ptr(), -1, weight.data_ptr(),
+                                                  grad.data_ptr(), grad.stride(0), out2.data_ptr(), _lib.stream_ptr()))
+        ctx.save_for_backward(grad)
+        loss_sum, weight_sum = out2[0].clone(), out2[1].clone()
+        ctx.mark_non_differentiable(weight_sum)
+        return loss_sum, weight_sum
+
+    @staticmethod
+    def backward(ctx, g, _gw):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def class_weight_tensor(weight, n_classes: int, device, who: str = "class_weight") -> torch.Tensor:
+    """``weight`` (a tensor or a sequence of floats) as the contiguous float32 device vector the native entries read; refuses a
+    length that is not the class count and negative (or NaN) entries, by name."""
+    w = weight if isinstance(weight, torch.Tensor) else torch.as_tensor([float(x) for x in weight], dtype=torch.float32)
+    if w.dim() != 1 or w.numel() != int(n_classes):
+        raise _lib.HydraMPError(f"{who}: {tuple(w.shape)} weights for {int(n_classes)} classes (wrong length)")
+    if not w.is_floating_point():
+        raise _lib.HydraMPError(f"{who}: class weights must be floating point, got {w.dtype}")
+    if not bool((w >= 0).all()):
+        raise _lib.HydraMPError(f"{who}: negative weight (class weights must be >= 0)")
+    return w.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _weighted_pair(pred, label, mask, weight):
+    if not pred.is_cuda:
+        raise _lib.HydraMPError("cross_entropy_loss: pred is on the CPU; hydra_gnn_amd has no CPU fallback")
+    if pred.dtype != torch.float32:
+        raise _lib.HydraMPError("cross_entropy_loss computes in fp32")
+    label = label.to(torch.int64)
+    if mask is not None:
+        label = torch.where(mask, label, torch.full_like(label, -1))
+    w = class_weight_tensor(weight, pred.shape[1], pred.device, "cross_entropy_loss: weight")
+    return _WeightedCE.apply(pred, label.contiguous(), w)
+
+
+def cross_entropy_loss(pred, label, mask=None, weight=None):
+    """reference models/utils.py:143-161 (tensor form = mean CE over ``mask``; list form = sum / count).
+
+    ``weight``: class weights, ``F.cross_entropy(..., weight=w)``: the tensor form is ``sum(w[y] * nll) / sum(w[y])`` over the
+    masked rows; the list form takes one vector per head (None: that head's rows weigh 1) and divides ONE weighted sum over all
+    heads by ONE sum of weights, as the unweighted list form divides by one count."""
     if isinstance(pred, torch.Tensor):
+        if weight is not None:
+            ls, ws = _weighted_pair(pred, label, mask, weight)
+            return ls / ws
         if not pred.is_cuda:
             raise _lib.HydraMPError("cross_entropy_loss: pred is on the CPU; hydra_gnn_amd has no CPU fallback")
         if pred.dtype != torch.float32:
@@ -260,6 +317,13 @@ def cross_entropy_loss(pred, label, mask=None):
         if mask is not None:
             label = torch.where(mask, label, torch.full_like(label, -1))
         return _MaskedCE.apply(pred, label.contiguous())
+    if weight is not None:
+        if len(weight) != len(pred):
+            raise _lib.HydraMPError(f"cross_entropy_loss: {len(weight)} weight vectors for {len(pred)} heads")
+        masks = mask if mask is not None else [None] * len(pred)
+        pairs = [_weighted_pair(p, l, m, w if w is not None else torch.ones(p.shape[1], device=p.device))
+                 for p, l, m, w in zip(pred, label, masks, weight)]
+        return sum(ls for ls, _ in pairs) / sum(ws for _, ws in pairs)
     losses = [cross_entropy_loss(p, l, None if mask is None else m) for p, l, m in
               zip(pred, label, mask if mask is not None else [None] * len(pred))]
     counts = [torch.numel(l) if mask is None else m.sum() for l, m in zip(label, mask if mask is not None else label)]

@@ -10,6 +10,11 @@ after which every rank scales by 1/count and applies the identical Adam update. 
 count (instead of averaging per-rank means) makes the N-rank step equal to the single-process step on the whole batch
 even when ranks hold different numbers of valid labels.
 
+Class weights (``TrainStep.set_class_weight``) change nothing here: a weighted step writes ``sum(w[y] * nll)`` and ``sum(w[y])``
+into the same two tail slots and gradient sums already scaled by ``w[y]``, the sums of weights add up across ranks as the counts
+do, and every rank divides by the global sum of weights -- the single-process weighted step on the whole batch, provided every
+rank sets the same weights.
+
 Gradient buffers here are 0.5-13 MB: latency-bound on xGMI, so the buffer is never bucketed.
 """
 from __future__ import annotations

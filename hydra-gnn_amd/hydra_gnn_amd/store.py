@@ -679,6 +679,111 @@ GraphStore.stream = _graphstore_stream
 
 
 # =====================================================================================================================
+# Label statistics of a resident store: the class histogram of the labels a training run reads and the class weights of the
+# weighted cross entropy (``TrainStep.set_class_weight``), computed where the labels live -- two launches, no host read.
+# =====================================================================================================================
+CLASS_WEIGHT_SCHEMES = ("balanced",)
+_NO_IGNORED = -(1 << 63)  # ignored_label=None: no label is ignored (the kernel compares with a value no class index takes)
+
+
+def check_weight_scheme(scheme) -> str:
+    if scheme not in CLASS_WEIGHT_SCHEMES:
+        raise _lib.HydraMPError(f"class_weights: unknown scheme {scheme!r} (known: {', '.join(CLASS_WEIGHT_SCHEMES)})")
+    return scheme
+
+
+def balanced_weights_host(counts) -> np.ndarray:
+    """Host statement of ``hmp_balanced_class_weights`` (scikit-learn's ``class_weight="balanced"`` over the classes present):
+    ``w_c = N / (K * n_c)`` in float64 with ``N = sum n_c`` and ``K = #{c: n_c > 0}``, cast to float32; 0 for an absent class."""
+    n = np.asarray(counts, dtype=np.int64)
+    w = np.zeros(n.shape, dtype=np.float64)
+    present = n > 0
+    if present.any():
+        w[present] = float(n.sum()) / (float(present.sum()) * n[present].astype(np.float64))
+    return w.astype(np.float32)
+
+
+def _label_rows(self: "GraphStore", who: str, label_type, label_key: str, mask):
+    """(labels, row filter or None) of the rows a head trains on.  Typed stores: the rows of node type ``label_type``.  Homogeneous
+    stores: ``label_type`` "rooms" (the default) = the rows of ``room_mask``, "objects" = the rows of ``object_mask`` (H-tree
+    graphs) or the complement of ``room_mask`` -- the label filter of the stream and the member rows of the linear heads.
+    ``mask`` names a bool attribute of those rows (``"train_mask"``: the node-split protocol) that narrows them further."""
+    if self.homogeneous:
+        attrs = self.node_attrs[HOMO_NODE]
+        head = "rooms" if label_type is None else label_type
+        if head not in ("rooms", "objects"):
+            raise _lib.HydraMPError(f"{who}: label_type of a homogeneous store is 'rooms' or 'objects', got {label_type!r}")
+        if "room_mask" not in attrs:
+            raise _lib.HydraMPError(f"{who}: the store holds no attribute 'room_mask'")
+        if head == "rooms":
+            rows = attrs["room_mask"].data
+        else:
+            rows = attrs["object_mask"].data if "object_mask" in attrs else ~attrs["room_mask"].data
+    else:
+        if label_type is None:
+            raise _lib.HydraMPError(f"{who}: label_type (the node type that carries the labels) is required for a typed store")
+        if label_type not in self.node_attrs:
+            raise _lib.HydraMPError(f"{who}: the store has no node type {label_type!r}")
+        attrs, rows = self.node_attrs[label_type], None
+    if label_key not in attrs:
+        raise _lib.HydraMPError(f"{who}: the store holds no attribute {label_key!r} of those rows")
+    lab = attrs[label_key].data
+    if lab.dtype != torch.int64 or lab.dim() != 1:
+        raise _lib.HydraMPError(f"{who}: {label_key!r} must be an int64 vector (one label per row), the store holds {tuple(lab.shape)} {lab.dtype}")
+    if mask is not None:
+        if mask not in attrs:
+            raise _lib.HydraMPError(f"{who}: the store holds no mask {mask!r} of those rows (generate_node_split writes train_mask / val_mask / test_mask)")
+        m = attrs[mask].data
+        if m.dtype != torch.bool or m.shape != lab.shape:
+            raise _lib.HydraMPError(f"{who}: {mask!r} must be a bool vector with one entry per row")
+        rows = m if rows is None else (rows & m)
+    if rows is not None and (rows.dtype != torch.bool or rows.shape != lab.shape):
+        raise _lib.HydraMPError(f"{who}: the row filter must be a bool vector with one entry per row")
+    return lab, (rows.contiguous() if rows is not None else None)
+
+
+def _label_histogram(self: "GraphStore", who: str, label_type, label_key: str, mask, n_classes, ignored_label) -> torch.Tensor:
+    if n_classes is None or int(n_classes) < 1:
+        raise _lib.HydraMPError(f"{who}: n_classes (>= 1) is required")
+    n_classes = int(n_classes)
+    lab, rows = _label_rows(self, who, label_type, label_key, mask)
+    counts = torch.zeros(n_classes + 1, dtype=torch.int64, device=self.device)
+    ignored = _NO_IGNORED if ignored_label is None else int(ignored_label)
+    with torch.cuda.device(self.device):
+        _lib.check(self.lib.hmp_label_counts(lab.data_ptr(), lab.numel(), rows.data_ptr() if rows is not None else None, ignored,
+                                             n_classes, counts.data_ptr(), _lib.stream_ptr()))
+    return counts
+
+
+def _class_counts(self: "GraphStore", label_type: Optional[str] = None, label_key: str = "y", mask: Optional[str] = None,
+                  n_classes: Optional[int] = None, ignored_label: Optional[int] = None) -> torch.Tensor:
+    """Class histogram of the store's labels (``hmp_label_counts``, one launch, nothing synchronises): device int64 ``[n_classes]``,
+    entry ``c`` = the rows of label ``c`` among the rows :func:`_label_rows` describes whose label is not ``ignored_label``.  The
+    result's attribute ``out_of_range`` (a device int64 scalar) counts the labels outside ``[0, n_classes)``."""
+    counts = _label_histogram(self, "class_counts", label_type, label_key, mask, n_classes, ignored_label)
+    out = counts[:-1]
+    out.out_of_range = counts[-1]
+    return out
+
+
+def _class_weights(self: "GraphStore", label_type: Optional[str] = None, label_key: str = "y", mask: Optional[str] = None,
+                   n_classes: Optional[int] = None, ignored_label: Optional[int] = None, scheme: str = "balanced") -> torch.Tensor:
+    """Class weights from :meth:`class_counts`, device float32 ``[n_classes]``, ready for ``train_step(class_weight=...)``.
+    ``scheme="balanced"``: ``w_c = N / (K * n_c)`` over the K classes present (N their rows; scikit-learn's "balanced"), 0 for an
+    absent class (``hmp_balanced_class_weights``).  Two launches, no host read between them."""
+    check_weight_scheme(scheme)
+    counts = _label_histogram(self, "class_weights", label_type, label_key, mask, n_classes, ignored_label)
+    w = torch.empty(int(n_classes), dtype=torch.float32, device=self.device)
+    with torch.cuda.device(self.device):
+        _lib.check(self.lib.hmp_balanced_class_weights(counts.data_ptr(), int(n_classes), w.data_ptr(), _lib.stream_ptr()))
+    return w
+
+
+GraphStore.class_counts = _class_counts
+GraphStore.class_weights = _class_weights
+
+
+# =====================================================================================================================
 # Derived stores: the reference derives every configuration from ONE loaded dataset in place (train_mp3d.py:130-137,
 # train_Stanford.py:87-99: compute_relative_pos for GAT_edge, to_homogeneous, remove_last_features for --remove_word2vec) and
 # draws a node split per run (train_Stanford.py:166-171).  A resident store does the same without host graphs: the host

@@ -65,7 +65,12 @@ extern "C" {
  *    added or changed layout;
  *    hmp_plan_job (hmp_sizeof 16), hmp_plan_build_many: unit-test entry of the plan builder as the executor calls it (several edge
  *    types per call, need_tpos, clear_first, degf, graph offsets); hmp_plan_build is its one-job call.  A new entry and a new
- *    struct, nothing above changed layout */
+ *    struct, nothing above changed layout;
+ *    hmp_net_set_class_weights, hmp_masked_ce_weighted (class weights of the cross entropy for every step form and the standalone
+ *    loss), hmp_label_counts / hmp_balanced_class_weights (the label histogram and balanced weights on the device),
+ *    hmp_head_tails_weighted / hmp_linear_heads_run_weighted (their test entries): new entries, no struct was added or changed
+ *    layout.  The normaliser of the loss and of Adam's gradient scale is now used as it is when > 0 (it was clamped at 1): the
+ *    same bits for the integer-valued counts of unweighted steps */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -315,6 +320,23 @@ int hmp_saliency_topk(hmp_plan plan, const float* d_score, int32_t k, int32_t se
  * ------------------------------------------------------------------------------------------- */
 int hmp_masked_ce(const float* d_logits, int32_t ldl, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
                   int64_t ignored_label, float* d_grad, int32_t ldg, float* d_out2, void* stream);
+/* hmp_masked_ce with class weights, torch.nn.functional.cross_entropy(weight = w): d_w device float [n_classes] (NULL: hmp_masked_ce
+ * bit for bit).  d_out2 = {sum of w[label] * -log p[label], sum of w[label]} over the valid rows and d_grad holds w[label] *
+ * (softmax - onehot), so loss_sum / weight_sum is torch's weighted mean.  A row whose label has weight 0 does not count, exactly as
+ * an ignored one; w is indexed by labels inside [0, n_classes) only.  The sum of weights is the normaliser of every consumer
+ * (hmp_adam_flat's d_count, the fused steps): it is used as it is when > 0 -- a sum below 1 included -- and replaced by 1 when 0.
+ * (ABI-4-compatible addition, like the class-weight entries below.) */
+int hmp_masked_ce_weighted(const float* d_logits, int32_t ldl, int32_t n_rows, int32_t n_classes, const int64_t* d_labels,
+                           int64_t ignored_label, const float* d_w, float* d_grad, int32_t ldg, float* d_out2, void* stream);
+/* Label histogram: d_counts (device int64 [n_classes + 1]) ACCUMULATES, over the rows r with (d_mask == NULL || d_mask[r]) &&
+ * d_labels[r] != ignored_label, the number of rows of each label in [0, n_classes) and, in slot n_classes, the rows whose label
+ * lies outside that range.  One launch; n_rows == 0 launches nothing; nothing synchronises. */
+int hmp_label_counts(const int64_t* d_labels, int64_t n_rows, const uint8_t* d_mask, int64_t ignored_label, int32_t n_classes,
+                     int64_t* d_counts, void* stream);
+/* Balanced class weights from such a histogram (scikit-learn's class_weight = "balanced" over the classes present): with
+ * K = #{c : n_c > 0} and N = sum_c n_c over d_counts[0 .. n_classes), d_w[c] = (float)((double)N / ((double)K * n_c)) for n_c > 0 and
+ * 0 for an absent class (device float [n_classes]).  One launch behind hmp_label_counts on the same stream: no host read between. */
+int hmp_balanced_class_weights(const int64_t* d_counts, int32_t n_classes, float* d_w, void* stream);
 /* out[r] = argmax_c x[r, c] (first maximum): the `.argmax(dim=1)` of the inference loop
  * (bin/room_classification_server:286) on the executor's output, so only the labels cross PCIe */
 int hmp_argmax_rows(const float* d_x, int32_t ldx, int32_t n_rows, int32_t n_cols, int64_t* d_out, void* stream);
@@ -351,7 +373,7 @@ int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t 
  * synchronises.  (ABI-4-compatible addition.) */
 int hmp_topk_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int32_t k,
                   int64_t* d_labels, float* d_probs, void* stream);
-/* d_count: device float holding the valid-label count (grad_scale = 1/max(count,1)); NULL => grad_scale = 1 */
+/* d_count: device float holding the valid-label count or weight sum (grad_scale = 1 / (count > 0 ? count : 1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
 
@@ -391,6 +413,9 @@ typedef struct hmp_tail_desc {
  * 3: the pooled accuracy count.  act: HMP_ACT_*.  A count row counts iff its mask byte is set (or mask is NULL). */
 int hmp_head_tails(const hmp_tail_desc* d, int32_t n, int32_t mode, int32_t act, int64_t ignored, int32_t* d_state,
                    int64_t* d_counts, void* stream);
+/* the same with class weights for the CE modes: d_w[i] device float [d[i].classes] or NULL (d_w NULL: hmp_head_tails) */
+int hmp_head_tails_weighted(const hmp_tail_desc* d, int32_t n, const float* const* d_w, int32_t mode, int32_t act, int64_t ignored,
+                            int32_t* d_state, int64_t* d_counts, void* stream);
 /* The label launch of the same descriptors (eval mode): d_pred[i] (device int64) receives the prediction the count of mode 1
  * (pooled != 0: mode 3) compares, for EVERY row of head i -- its n_rows leaf rows, or its n_pool pooled rows (an empty pooled row
  * predicts 0).  labels, mask, grad, row_lv, dpool, t_rowptr and t_col may be NULL.  One launch for both heads.  (ABI-4-compatible
@@ -427,6 +452,9 @@ typedef struct hmp_linear_heads_desc {
  * d_counts (device int64[4]).  *n_blocks_out (may be NULL) = the workgroups launched = min(ceil(n_rows / 32), 240). */
 int hmp_linear_heads_run(const hmp_linear_heads_desc* d, int32_t train, int32_t* d_state, int64_t* d_counts, int32_t* n_blocks_out,
                          void* stream);
+/* the same with class weights for the CE launch: d_w[h] device float [classes[h]] or NULL (d_w NULL: hmp_linear_heads_run) */
+int hmp_linear_heads_run_weighted(const hmp_linear_heads_desc* d, const float* const* d_w, int32_t train, int32_t* d_state,
+                                  int64_t* d_counts, int32_t* n_blocks_out, void* stream);
 /* The label launch (eval mode): d_pred[h] (device int64 [n_rows], NULL: head skipped) = first-maximum argmax of head h's logits
  * for the rows of member[h] (the rule above), -1 elsewhere.  labels, mask, grad, row_lv and slabs may be NULL. */
 int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_pred, int32_t* n_blocks_out, void* stream);
@@ -636,6 +664,14 @@ typedef struct hmp_linear_head_targets {
 } hmp_linear_head_targets;
 
 int hmp_net_set_linear_heads(hmp_net* net, const hmp_linear_heads* heads);
+/* Class weights of the cross entropy of every later training step of `net`, whatever its form (hmp_net_step_*, hmp_net_step2_*,
+ * hmp_net_step_heads_*): head 0 = the readout (rooms), head 1 = the aux readout or the second linear head (objects).  d_w is a
+ * BORROWED device float vector of n entries that must outlive the steps; n must equal the head's class count (HMP_ERR_ARG names
+ * both numbers otherwise; set linear heads first).  d_w == NULL clears the head's weights: the unweighted step, bit for bit.
+ * Weighted, a row contributes {w[y] * nll, w[y]} and w[y] * (softmax - onehot): {loss_sum, count} hold the weighted sum and the
+ * sum of weights, and Adam divides by that sum.  No launch is added: the vector travels next to the label pointer of each CE
+ * launch and an unweighted step issues no load for it.  (ABI-4-compatible addition.) */
+int hmp_net_set_class_weights(hmp_net* net, int32_t head, const float* d_w, int32_t n);
 int hmp_net_step_heads_fwd_bwd(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, const float* d_params,
                                float* d_grads, const hmp_train_args* args, void* stream);
 int hmp_net_step_heads_fused(hmp_net* net, const hmp_batch* batch, const hmp_linear_head_targets* targets, float* d_params,
