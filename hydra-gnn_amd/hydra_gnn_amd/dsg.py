@@ -239,6 +239,12 @@ def _relpos_mode(who: str, htree, relative_pos, htree_relative_pos, clique_dim) 
 # attributes of the homogeneous Data, by output tensor number - HMP_FT_HOMOG
 _HOMOG_TENSORS = ("x", "edge_index", "node_type", "edge_type", "room_mask", "edge_attr", "object_mask", "init_edge_index", "pool_edge_index")
 assert len(_HOMOG_TENSORS) == _lib.FT_HOMOG_COUNT
+# element class of an output tensor: how its (arena byte, rows, width) is viewed - float32 [rows, width], int64 [2, width] (an edge
+# list), int64 [rows], bool [rows]
+_F32, _EDGE, _I64, _BOOL = range(4)
+_ELEMENT_CLASS = {"x": _F32, "pos": _F32, "edge_attr": _F32, "edge_index": _EDGE, "init_edge_index": _EDGE, "pool_edge_index": _EDGE,
+                  "label": _I64, "node_ids": _I64, "node_type": _I64, "edge_type": _I64, "batch": _I64, "ptr": _I64, "y": _I64,
+                  "room_mask": _BOOL, "object_mask": _BOOL}
 
 
 def scene_arrays(sg: SceneGraph):
@@ -332,6 +338,47 @@ def _edge_type_names(htree: bool, homogeneous: bool, relative_pos: bool = False)
     if homogeneous:
         return ["edge_index", "init_edge_index", "pool_edge_index"] if htree else ["edge_index"]
     return [k for k, a in _FRAME_TENSORS[_lib.FT_HTREE if htree else 0:_lib.FT_COUNT if htree else _lib.FT_HTREE] if a == "edge_index"]
+
+
+def _build_tensor_table(htree: bool, homogeneous: bool):
+    """THE tensor table of a mode: ``table[t] = (store key or None, attribute, element class)`` for every output tensor number the
+    library emits in it -- the mode's own range (typed baseline, typed H-tree with HMP_FT_HTREL, or HMP_FT_HOMOG) and HMP_FT_BATCH
+    (``batch``, node ``ptr``, edge ``ptr``, ``y`` of this mode's node and edge types).  Every other number, another mode's included,
+    holds ``(None, t, None)`` and is refused where a view is asked for."""
+    nodes, edges = _node_type_names(htree, homogeneous), _edge_type_names(htree, homogeneous)
+    FB = _lib.FT_BATCH
+    if homogeneous:
+        named = {_lib.FT_HOMOG + k: (None, a) for k, a in enumerate(_HOMOG_TENSORS)}
+    elif htree:
+        named = {t: _typed_tensor(t) for r in (range(_lib.FT_HTREE, _lib.FT_COUNT), range(_lib.FT_HTREL, _lib.FT_HTREL + _lib.FT_HTREL_COUNT)) for t in r}
+    else:
+        named = {t: _typed_tensor(t) for t in range(_lib.FT_HTREE)}
+    named.update((FB + _lib.FTB_BATCH + k, (t, "batch")) for k, t in enumerate(nodes))
+    named.update((FB + _lib.FTB_NODE_PTR + k, (t, "ptr")) for k, t in enumerate(nodes))
+    named.update((FB + _lib.FTB_EDGE_PTR + k, (e, "ptr")) for k, e in enumerate(edges))
+    named.update((FB + _lib.FTB_Y + k, (None if homogeneous else t, "y")) for k, t in enumerate(nodes))
+    return [(*named[t], _ELEMENT_CLASS[named[t][1]]) if t in named else (None, t, None) for t in range(_lib.FT_HTREL + _lib.FT_HTREL_COUNT)]
+
+
+_TENSOR_TABLES = {(ht, hg): _build_tensor_table(ht, hg) for ht in (False, True) for hg in (False, True)}
+
+
+def _resolve_views(table, f32, i64, as_bool):
+    """A tensor table resolved against one arena (its float32, int64 and bool views): ``resolved[t] = (store key, attribute, base
+    view, shift of the arena byte to the base's element, leading dimension)`` -- leading dimension 0: ``[rows, width]``, 2: an edge
+    list ``[2, width]``, None: ``[rows]`` -- or None for a number the mode does not define."""
+    layout = {_F32: (f32, 2, 0), _EDGE: (i64, 3, 2), _I64: (i64, 3, None), _BOOL: (as_bool, 0, None)}
+    return [None if cls is None else (key, attr) + layout[cls] for key, attr, cls in table]
+
+
+def _arena_view(resolved, t: int, dst: int, rows: int, width: int):
+    """The view of output tensor number ``t`` (``rows`` x ``width``) at arena byte ``dst``.  An undefined number is refused."""
+    if not 0 <= t < len(resolved) or resolved[t] is None:
+        raise _lib.HydraMPError(f"frame pipeline: output tensor number {t} is not a tensor of this mode")
+    _, _, base, shift, lead = resolved[t]
+    if lead is None:
+        return torch.as_strided(base, (rows,), (1,), dst >> shift)
+    return torch.as_strided(base, (lead or rows, width), (width, 1), dst >> shift)
 
 
 def _label_pointers(y, n_frames: int, arrays):
@@ -492,7 +539,8 @@ class FramePipeline:
         self._sizes = np.zeros(_lib.FS_COUNT, dtype=np.int64)
         # device buffers appear with the first frame that has something to convert (an empty frame never touches the device)
         self._pinned, self._pinned_np, self._events, self._slot = [None, None], [None, None], [None, None], 0
-        self._d_staging = self._arena = self._arena_f32 = self._arena_i64 = self._arena_bool = None
+        self._d_staging = self._arena = self._resolved = None  # _resolved: the table against the arena (_resolve_views)
+        self._tensors = _TENSOR_TABLES[self.htree, self.homogeneous]
         self._stream = None  # hipStream_t of the first convert that enqueued work
         self._batch_max_items = _lib.FRAME_BATCH_MAX_ITEMS  # items of one convert_batch launch
 
@@ -510,8 +558,8 @@ class FramePipeline:
                 self._events[k] = torch.cuda.Event()
         if self._arena is None or self._arena.numel() < arena_bytes:
             self._arena = torch.empty(max(1 << 18, 2 * arena_bytes), dtype=torch.uint8, device=self.device)
-            self._arena_f32, self._arena_i64 = self._arena.view(torch.float32), self._arena.view(torch.int64)
-            self._arena_bool = self._arena.view(torch.bool)
+            self._resolved = _resolve_views(self._tensors, self._arena.view(torch.float32), self._arena.view(torch.int64),
+                                            self._arena.view(torch.bool))
 
     def _stage_and_expand(self, pack, expand: str, h, staging_bytes: int, arena_bytes: int, n_items: int, n_blocks: int) -> int:
         """The device half of ``convert`` / ``convert_batch``: ``pack`` the block of ``h`` into the next pinned buffer, ONE upload, ONE
@@ -572,16 +620,18 @@ class FramePipeline:
         if self.htree:
             for t in _HTREE_STORES:
                 g[t]
-        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
-        for kind, tensor, n_rows, width, dst, *_ in items:
-            key, attr = _typed_tensor(tensor)
-            if kind == _lib.FK_I64:
-                t = strided(i64, (n_rows,), (1,), dst >> 3)
-            elif kind == _lib.FK_EDGE:
-                t = strided(i64, (2, width), (width, 1), dst >> 3)
-            else:
-                t = strided(f32, (n_rows, width), (width, 1), dst >> 2)
-            setattr(g[key], attr, t)
+        resolved, strided = self._resolved, torch.as_strided
+        try:
+            for _, tensor, n_rows, width, dst, *_ in items:  # the body of _arena_view inline: one lookup and one as_strided per item
+                key, attr, base, shift, lead = resolved[tensor]
+                if lead is None:
+                    t = strided(base, (n_rows,), (1,), dst >> shift)
+                else:
+                    t = strided(base, (lead or n_rows, width), (width, 1), dst >> shift)
+                setattr(g[key], attr, t)
+        except (TypeError, IndexError):
+            _arena_view(resolved, tensor, dst, n_rows, width)  # an undefined number is refused by name
+            raise
         return g, info
 
     # ---- many frames per launch ----------------------------------------------------------------------------------------------------
@@ -664,30 +714,18 @@ class FramePipeline:
         for i, g in enumerate(host["graph_of_frame"].tolist()):
             if infos[i] is not None:
                 infos[i]["graph"] = g
-        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
-        tensors = {}
-        for t, dst, rows, width in host["tensors"].tolist():
-            if t < _lib.FT_HOMOG or t >= _lib.FT_HTREL:
-                name = _typed_tensor(t)[1]
-            else:
-                name = _HOMOG_TENSORS[t - _lib.FT_HOMOG] if t < _lib.FT_BATCH else "ptr"
-            if name.endswith("edge_index"):
-                tensors[t] = strided(i64, (2, width), (width, 1), dst >> 3)
-            elif name.endswith("_mask"):
-                tensors[t] = strided(self._arena_bool, (rows,), (1,), dst)
-            elif name in ("x", "pos", "edge_attr"):
-                tensors[t] = strided(f32, (rows, width), (width, 1), dst >> 2)
-            else:  # label, node_ids, node_type, edge_type, batch, ptr, y
-                tensors[t] = strided(i64, (rows,), (1,), dst >> 3)
-        return tensors, host
+        resolved = self._resolved
+        return {t: _arena_view(resolved, t, dst, rows, width) for t, dst, rows, width in host["tensors"].tolist()}, host
 
     def _collated(self, tensors, host):
         """the views of a collated batch as the HeteroData / Data that data.collate / data.collate_homogeneous build"""
-        FB = _lib.FT_BATCH
+        FB, table = _lib.FT_BATCH, self._tensors
         if self.homogeneous:
             d = Data()
             for t in sorted(tensors):
-                setattr(d, "y" if t == FB + _lib.FTB_Y else _HOMOG_TENSORS[t - _lib.FT_HOMOG], tensors[t])
+                key, attr, _ = table[t]
+                assert key is None, (t, key, attr)  # a collated Data carries no offset vectors
+                setattr(d, attr, tensors[t])
             d.num_graphs = host["num_graphs"]
             return d
         g = HeteroData()
@@ -697,7 +735,7 @@ class FramePipeline:
         for t in node_types:
             g[t]
         for t in sorted(k for k in tensors if k < FB or k >= _lib.FT_HTREL):
-            key, attr = _typed_tensor(t)
+            key, attr, _ = table[t]
             setattr(g[key], attr, tensors[t])
             if attr == "edge_index":
                 g[key].ptr = tensors[FB + _lib.FTB_EDGE_PTR + edge_types.index(key)]
@@ -718,17 +756,8 @@ class FramePipeline:
             if tensor not in at:
                 at[tensor], n_rows[tensor], pitch[tensor] = dst, 0, s1 if kind == _lib.FK_EDGE_SEG else width
             n_rows[tensor] += rows
-        f32, i64, strided = self._arena_f32, self._arena_i64, torch.as_strided
+        resolved, table = self._resolved, self._tensors
         d = Data()
         for tensor in sorted(at):
-            attr, dst, n, w = _HOMOG_TENSORS[tensor - _lib.FT_HOMOG], at[tensor], n_rows[tensor], pitch[tensor]
-            if attr.endswith("edge_index"):
-                t = strided(i64, (2, w), (w, 1), dst >> 3)
-            elif attr.endswith("_type"):
-                t = strided(i64, (n,), (1,), dst >> 3)
-            elif attr.endswith("_mask"):
-                t = strided(self._arena_bool, (n,), (1,), dst)
-            else:  # x, edge_attr
-                t = strided(f32, (n, w), (w, 1), dst >> 2)
-            setattr(d, attr, t)
+            setattr(d, table[tensor][1], _arena_view(resolved, tensor, at[tensor], n_rows[tensor], pitch[tensor]))
         return d

@@ -195,7 +195,7 @@ class GraphStore:
         finally:
             for h, _ in built:
                 lib.hmp_frame_destroy(h)
-        FB = _lib.FT_BATCH
+        FB, table = _lib.FT_BATCH, pipeline._tensors
 
         def joined_ptr(t, host_key, k):
             dev = torch.cat([ch[t] if i == 0 else ch[t][1:] + int(sum(c[1][host_key][k][-1] for c in chunks[:i]))
@@ -204,8 +204,8 @@ class GraphStore:
                                   for i, (_, h) in enumerate(chunks)]).astype(np.int64)
             return dev, hst
 
-        data = {t: torch.cat([ch[t] for ch, _ in chunks], dim=1 if v.dim() == 2 and v.dtype == torch.int64 else 0) if len(chunks) > 1 else v
-                for t, v in chunks[0][0].items() if not FB + _lib.FTB_NODE_PTR <= t < FB + _lib.FTB_Y}  # the offset vectors are joined below
+        data = {t: torch.cat([ch[t] for ch, _ in chunks], dim=1 if table[t][2] == dsg._EDGE else 0) if len(chunks) > 1 else v
+                for t, v in chunks[0][0].items() if table[t][1] != "ptr"}  # the offset vectors are joined below
         ht, homog = pipeline.htree, pipeline.homogeneous
         node_names, edge_names = dsg._node_type_names(ht, homog), dsg._edge_type_names(ht, homog)
         node_ptr = [joined_ptr(FB + _lib.FTB_NODE_PTR + k, "node_ptr", k) for k in range(len(node_names))]
@@ -218,7 +218,7 @@ class GraphStore:
         self.edge_rows, self.edge_index, self.edge_ptr, self.edge_ptr_host, self.edge_attr = {}, {}, {}, {}, {}
         self.count_only = {t: False for t in ([HOMO_NODE] if homog else node_names)}
         if homog:
-            names = {t: ("y" if t == FB + _lib.FTB_Y else dsg._HOMOG_TENSORS[t - _lib.FT_HOMOG]) for t in data}
+            names = {t: table[t][1] for t in data}
             self.homo_keys = [names[t] for t in sorted(data)]  # the attribute order of the pipeline's Data, then y
             self.node_types, self.node_counts = [HOMO_NODE], {HOMO_NODE: np.diff(node_ptr[0][1])}
             self.node_attrs, self.edge_types, self.edge_name = {HOMO_NODE: {}}, [], {}
@@ -244,11 +244,7 @@ class GraphStore:
         self.node_attrs = {t: {} for t in node_names}
         self.node_counts = {t: np.diff(node_ptr[k][1]) for k, t in enumerate(node_names)}
         for t in sorted(data):
-            if FB <= t < _lib.FT_HTREL:
-                k = t - FB - _lib.FTB_Y
-                self.node_attrs[node_names[k]]["y"] = _packed(data[t], *node_ptr[k])
-                continue
-            key, attr = dsg._typed_tensor(t)  # sorted: an edge type's edge_index comes before its edge_attr
+            key, attr, _ = table[t]  # sorted: an edge type's edge_index comes before its edge_attr
             if attr == "edge_index":
                 self.edge_index[key] = data[t]
                 self.edge_ptr[key], self.edge_ptr_host[key] = edge_ptr[edge_names.index(key)]

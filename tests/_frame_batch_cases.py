@@ -1,14 +1,12 @@
 """Shared cases of the frame-batch tests (tests/test_frame_batch_host.py, tests/test_gpu_frame_batch.py,
 tests/test_gpu_frame_store.py): the frame list, label vectors, the per-frame results of the existing path on the CPU with the
-committed collation applied to them (the comparison), and a numpy execution of a packed batch block -- what the one launch of
-``hmp_frame_expand_batch`` is specified to write, item by item, including the two-level item lookup."""
+committed collation applied to them (the comparison).  The numpy execution of a packed batch block is tests/_frame_block.py."""
 import numpy as np
 import torch
 
 import _frame_cases as fc
-from hydra_gnn_amd import _lib, data as hdata, dsg, htree
+from hydra_gnn_amd import data as hdata, dsg, htree
 
-INT_MAX = 0x7FFFFFFF
 CLIQUE_DIM = 6
 # 5 graphs and one skipped frame; edge types that are empty in some frames and not in others
 FRAME_NAMES = ["special", (1, 1), "no_room", (7, 2), "fixture", (65, 1)]
@@ -112,149 +110,29 @@ def collate(graphs, homogeneous):
     return hdata.collate_homogeneous(graphs) if homogeneous else hdata.collate(graphs)
 
 
-def batch_tensor_name(t, mode):
-    """(store key or None, attribute) of batched tensor number ``t``"""
-    homog, ht = MODES[mode][:2]
-    FB = _lib.FT_BATCH
-    if t < _lib.FT_HOMOG:
-        return dsg._FRAME_TENSORS[t]
-    if t < FB:
-        return None, dsg._HOMOG_TENSORS[t - _lib.FT_HOMOG]
-    k = t - FB
-    nodes, edges = dsg._node_type_names(ht, homog), dsg._edge_type_names(ht, homog)
-    if k >= _lib.FTB_Y:
-        if homog and k > _lib.FTB_Y:  # one y over all nodes
-            raise IndexError(t)
-        return (None if homog else nodes[k - _lib.FTB_Y]), "y"
-    if k >= _lib.FTB_EDGE_PTR:
-        return edges[k - _lib.FTB_EDGE_PTR], "ptr"
-    if k >= _lib.FTB_NODE_PTR:
-        return nodes[k - _lib.FTB_NODE_PTR], "ptr"
-    return nodes[k], "batch"
+def collated_arrays(batch, homogeneous):
+    """{(key or None, attr): array} of a ``data.collate`` / ``data.collate_homogeneous`` result (an HMP_FB_COLLATED block)"""
+    return fc.data_arrays(batch) if homogeneous else fc.hetero_arrays(batch)
 
 
-def _batch_tensor_numbers(mode):
-    homog = MODES[mode][0]
-    for t in range(_lib.FT_HOMOG if homog else 0, _lib.FT_BATCH + _lib.FT_BATCH_COUNT):
-        if not homog and _lib.FT_HOMOG <= t < _lib.FT_BATCH:
-            continue
-        try:
-            yield (t,) + tuple(batch_tensor_name(t, mode))
-        except IndexError:  # a node / edge type number this mode does not have
-            continue
-
-
-def tensors_of_batch(batch, mode):
-    """{tensor number: numpy array} of a collated HeteroData / Data: what an HMP_FB_COLLATED block writes"""
-    homog = MODES[mode][0]
-    out = {}
-    for t, key, attr in _batch_tensor_numbers(mode):
-        if homog:
-            if key is None and hasattr(batch, attr):  # collate_homogeneous keeps no offset vectors
-                out[t] = getattr(batch, attr).cpu().numpy()
-        elif (key in batch.node_types or key in batch.edge_types) and attr in batch[key]:
-            out[t] = getattr(batch[key], attr).cpu().numpy()
-    return out
-
-
-def store_tensors(graphs, mode):
-    """{tensor number: numpy array} of what ``GraphStore.__init__`` cats from a list of graphs (what an HMP_FB_STORE block writes):
-    rows back to back, graph-LOCAL edge lists side by side, the [G + 1] offset vectors; no ``batch``"""
-    homog = MODES[mode][0]
-    g0 = graphs[0]
+def store_arrays(graphs, homogeneous):
+    """{(key or None, attr): array} of what ``GraphStore.__init__`` cats from a list of graphs (an HMP_FB_STORE block): rows back to
+    back, graph-LOCAL edge lists side by side, the [G + 1] offset vectors; no ``batch``"""
     cum = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    out = {}
-    for t, key, attr in _batch_tensor_numbers(mode):
-        if attr == "batch":
-            continue
-        if homog:
-            if attr == "ptr":
-                out[t] = cum([g.num_nodes if key == "node" else getattr(g, key).size(1) for g in graphs])
-            elif hasattr(g0, attr):
-                out[t] = torch.cat([getattr(g, attr) for g in graphs], dim=1 if "index" in attr else 0).cpu().numpy()
-        elif key in g0.node_types or key in g0.edge_types:
-            if attr == "ptr":
-                out[t] = cum([g[key].edge_index.size(1) if isinstance(key, tuple) else g[key].num_nodes for g in graphs])
-            elif attr in g0[key]:
-                out[t] = torch.cat([getattr(g[key], attr) for g in graphs], dim=1 if attr == "edge_index" else 0).cpu().numpy()
-    return out
-
-
-# ---- a numpy execution of a batch block ----------------------------------------------------------------------------------------
-def lookup(groups, items, n_items, block):
-    """the kernel's two-level item lookup for workgroup ``block``: two 64-lane loads, two ballots; tail lanes read INT_MAX"""
-    lanes = np.arange(64)
-    g0 = np.where(lanes < groups.size, groups[np.minimum(lanes, groups.size - 1)], INT_MAX)
-    gi = int((g0 <= block).sum()) - 1
-    assert gi >= 0 and bool(np.all((g0 <= block)[: gi + 1]))  # the ballot is a prefix: popcount - 1 is the last set lane
-    it = gi * 64 + lanes
-    b0 = np.where(it < n_items, items[np.minimum(it, n_items - 1), _lib.FI_BLOCK0], INT_MAX)
-    hit = b0 <= block
-    assert bool(np.all(hit[: int(hit.sum())]))
-    return gi * 64 + int(hit.sum()) - 1
-
-
-def item_blocks(item):
-    """workgroups of an item, from its own words (the rule of csrc/frame.cpp)"""
-    kind, rows, width = item[_lib.FI_KIND], item[_lib.FI_ROWS], item[_lib.FI_WIDTH]
-    if kind == _lib.FK_FEAT and width >= 32:
-        return -(-rows // 4)
-    if kind in (_lib.FK_EDGE, _lib.FK_EDGE_SEG):
-        return -(-2 * width // 256)
-    if kind in (_lib.FK_I64, _lib.FK_CONST):
-        return -(-rows // 256)
-    return -(-rows * (3 if kind in (_lib.FK_POS, _lib.FK_EATTR) else width) // 256)
-
-
-def expand_block(block, items, arena_bytes, table=None):
-    """The arena (uint8) a launch over this block is specified to write.  Every section read is checked to lie inside the block
-    (``fc.read_block``), every write to lie inside the arena, at a multiple of its element size, and no byte is written twice."""
-    arena = np.zeros(arena_bytes, dtype=np.uint8)
-    written = np.zeros(arena_bytes, dtype=bool)
-
-    def put(dst, values):
-        raw = np.ascontiguousarray(values).view(np.uint8).reshape(-1)
-        assert dst >= 0 and dst % values.dtype.itemsize == 0 and dst + raw.size <= arena_bytes, (dst, raw.size, arena_bytes)
-        assert not written[dst:dst + raw.size].any()
-        arena[dst:dst + raw.size] = raw
-        written[dst:dst + raw.size] = True
-
-    for item in items.tolist():
-        kind, tensor, rows, width, dst, s0, s1, s2, s3, p0, p1, _ = item
-        one = lambda it: fc.read_block(block, np.array([it], dtype=np.int64), table)[tensor]
-        if kind == _lib.FK_CONST:
-            assert p1 in (1, 8)
-            put(dst, np.full(rows, p0, dtype=np.int64 if p1 == 8 else np.uint8))
-        elif kind == _lib.FK_EDGE_SEG:
-            ends = one([_lib.FK_EDGE, tensor, 2, width, 0, s0, -1, -1, -1, p0, p1, 0])
-            assert 0 <= width <= s1
-            put(dst, ends[0] + s2)
-            put(dst + 8 * s1, ends[1] + s3)
-        elif kind == _lib.FK_FEAT:
-            own = p0 + 3 + p1
-            x = np.zeros((rows, width), dtype=np.float32)
-            x[:, :own] = one([kind, tensor, rows, own, 0, s0, s1, s2, s3, p0, p1, 0])
-            put(dst, x)
-        else:
-            assert kind in (_lib.FK_POS, _lib.FK_I64, _lib.FK_EATTR, _lib.FK_CLIQUE), kind  # a batch holds no plain EDGE item
-            put(dst, one(item))
-    return arena, written
-
-
-def views(arena, tensors, mode):
-    """{tensor number: array} of the batched tensors, read from an arena through the batch's tensor table"""
-    out = {}
-    for t, dst, rows, width in tensors.tolist():
-        assert dst % 16 == 0
-        attr = batch_tensor_name(t, mode)[1]
-        if attr.endswith("edge_index"):
-            out[t] = arena[dst:dst + 16 * width].view(np.int64).reshape(2, width)
-        elif attr.endswith("_mask"):
-            out[t] = arena[dst:dst + rows].view(np.bool_)
-        elif attr in ("x", "pos", "edge_attr"):
-            out[t] = arena[dst:dst + 4 * rows * width].view(np.float32).reshape(rows, width)
-        else:
-            out[t] = arena[dst:dst + 8 * rows].view(np.int64)
+    g0, out = graphs[0], {}
+    if homogeneous:
+        for attr, v in vars(g0).items():
+            if isinstance(v, torch.Tensor):
+                out[(None, attr)] = torch.cat([getattr(g, attr) for g in graphs], dim=1 if "index" in attr else 0).numpy()
+                if "index" in attr:
+                    out[(attr, "ptr")] = cum([getattr(g, attr).size(1) for g in graphs])
+        out[("node", "ptr")] = cum([g.num_nodes for g in graphs])
+        return out
+    for key in g0.node_types + g0.edge_types:
+        for attr, v in g0[key].items():
+            if isinstance(v, torch.Tensor):
+                out[(key, attr)] = torch.cat([getattr(g[key], attr) for g in graphs], dim=1 if attr == "edge_index" else 0).numpy()
+        out[(key, "ptr")] = cum([g[key].edge_index.size(1) if isinstance(key, tuple) else g[key].num_nodes for g in graphs])
     return out
 
 

@@ -1,12 +1,12 @@
 """Shared cases of the frame-pipeline tests (tests/test_frame_host.py, tests/test_gpu_frame_pipeline.py): scene graphs as flat
-arrays, the ``dsg.SceneGraph`` built from the same arrays (the comparison), the existing conversion path they are checked against,
-and a numpy reading of the staging block (what ``hmp_frame_expand`` is specified to write, item by item)."""
+arrays, the ``dsg.SceneGraph`` built from the same arrays (the comparison), and the existing conversion path they are checked
+against.  The numpy execution of a staging block is tests/_frame_block.py."""
 import os
 
 import numpy as np
 import torch
 
-from hydra_gnn_amd import _lib, dsg, workloads
+from hydra_gnn_amd import dsg, workloads
 from hydra_gnn_amd.data import compute_relative_pos
 from oracle import dsg_ref
 
@@ -107,77 +107,14 @@ def existing_frame(arrays, sem: bool, relative_pos: bool = False, device="cpu"):
     return data, rog
 
 
-# ---- a numpy reading of the staging block: what the launch is specified to write, item by item -------------------------------
-def _ends(e, variant, n, col):
-    if variant == 0:
-        return e[col], e[n + col]
-    if variant == 1:
-        return (e[col], e[n + col]) if col < n else (e[col], e[col - n])
-    if variant == 2:
-        return e[n + col], e[col]
-    return (e[col], col) if variant == 3 else (col, e[col])
+def hetero_arrays(g):
+    """{(store key, attribute): host array} of every tensor a HeteroData holds, by its OWN stores and attributes"""
+    return {(key, attr): v.cpu().numpy() for key in g.node_types + g.edge_types for attr, v in g[key].items() if isinstance(v, torch.Tensor)}
 
 
-def read_block(block: np.ndarray, items: np.ndarray, table=None):
-    """{tensor number: array} from a packed block; every source read is checked to lie inside the block"""
-
-    def sec(off, dtype, count):
-        nbytes = count * np.dtype(dtype).itemsize
-        assert off >= 0 and off % 16 == 0 and off + nbytes <= block.size, (off, count, block.size)
-        return block[off:off + nbytes].view(dtype)
-
-    out = {}
-    for kind, tensor, rows, width, dst, s0, s1, s2, s3, p0, p1, _ in items.tolist():
-        idx = sec(s3, np.int32, rows) if s3 >= 0 else np.arange(rows, dtype=np.int32)
-        n_src = int(idx.max()) + 1 if rows else 0
-        if kind == _lib.FK_FEAT:
-            cols = [sec(s0, np.float64, 3 * n_src).reshape(-1, 3)[idx]] if p0 else []
-            cols.append(sec(s1, np.float64, 3 * n_src).reshape(-1, 3)[idx])
-            x = np.concatenate(cols, 1).astype(np.float32)
-            if p1:
-                x = np.concatenate([x, table[sec(s2, np.int32, n_src)[idx]]], 1)
-            assert x.shape == (rows, width)
-            out[tensor] = x
-        elif kind == _lib.FK_POS:
-            out[tensor] = sec(s0, np.float64, 3 * n_src).reshape(-1, 3)[idx].astype(np.float32)
-        elif kind == _lib.FK_I64:
-            out[tensor] = sec(s0, np.int32 if p0 == 4 else np.int64, n_src)[idx].astype(np.int64)
-        elif kind in (_lib.FK_EDGE, _lib.FK_EATTR):
-            n_out = width if kind == _lib.FK_EDGE else rows
-            e = sec(s0, np.int32, (2 if p0 <= 2 else 1) * p1)
-            ends = np.array([_ends(e, p0, p1, c) for c in range(n_out)], dtype=np.int64).reshape(-1, 2)
-            if kind == _lib.FK_EDGE:
-                out[tensor] = ends.T.copy()
-            else:
-                ps = sec(s1, np.float64, 3 * (int(ends[:, 0].max()) + 1 if n_out else 0)).reshape(-1, 3).astype(np.float32)
-                pd = sec(s2, np.float64, 3 * (int(ends[:, 1].max()) + 1 if n_out else 0)).reshape(-1, 3).astype(np.float32)
-                out[tensor] = pd[ends[:, 1]] - ps[ends[:, 0]]
-        elif kind == _lib.FK_CLIQUE:
-            ptr = sec(s0, np.int32, rows + 1)
-            mem = sec(s1, np.int32, int(ptr[-1]))
-            rpos = sec(s2, np.float64, 3 * (int(mem.max()) + 1 if mem.size else 0)).reshape(-1, 3).astype(np.float32)
-            x = np.zeros((rows, width), dtype=np.float32)
-            for q in range(rows):
-                s = np.zeros(3, dtype=np.float32)
-                for k in mem[ptr[q]:ptr[q + 1]]:
-                    s = s + rpos[k]
-                x[q, :3] = s / np.float32(max(int(ptr[q + 1] - ptr[q]), 1))
-            out[tensor] = x
-        else:
-            raise AssertionError(f"unknown item kind {kind}")
-    return out
-
-
-def tensors_of(data, htree_mode: bool):
-    """{tensor number: host array} of a HeteroData of the existing path (only the tensors it holds)"""
-    out = {}
-    for t, (key, attr) in enumerate(dsg._FRAME_TENSORS):
-        if (t >= _lib.FT_HTREE) != htree_mode:
-            continue
-        store = data[key]
-        if attr in store:
-            out[t] = getattr(store, attr).cpu().numpy()
-    return out
+def data_arrays(d):
+    """{(None, attribute): host array} of every tensor a homogeneous Data holds"""
+    return {(None, k): v.cpu().numpy() for k, v in vars(d).items() if isinstance(v, torch.Tensor)}
 
 
 def clique_members(tree, which: int):

@@ -3,17 +3,14 @@ block [group table | item table | sections] is executed with numpy, item by item
 with ``data.collate`` / ``data.collate_homogeneous`` of the per-frame results of the existing path on the CPU (HMP_FB_COLLATED) and
 with the arrays ``GraphStore.__init__`` cats (HMP_FB_STORE).  The two-level item lookup of ``frame_expand_batch_kernel`` is emulated
 over the packed tables; capacity, refusals, empty batches and the stand-alone sanitizer program are covered as well."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import _frame_batch_cases as bc
+import _frame_block as fb
 import _frame_cases as fc
 from hydra_gnn_amd import _lib, dsg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAYOUT_MODES = ["typed", "typed_htree", "homog", "homog_htree", "typed_relative_pos", "typed_sem300", "homog_htree_sem300"]
 _GRAPHS = {}
 
@@ -33,14 +30,16 @@ def cpu_graphs(mode):
 
 
 def run_block(r, mode):
+    """({(store key or None, attribute): array}, written mask) of a batch block, executed with numpy"""
     sz = r["sizes"]
     table = fc.semantic_table().numpy() if bc.MODES[mode][3] else None
-    arena, written = bc.expand_block(r["block"], r["items"], int(sz[_lib.FBS_ARENA_BYTES]), table)
-    return bc.views(arena, r["tensors"], mode), written
+    fb.check_kinds(r["items"], fb.BATCH_KINDS)  # a batch holds no plain EDGE item
+    arena, written = fb.expand(r["block"], r["items"], int(sz[_lib.FBS_ARENA_BYTES]), table)
+    return fb.views(arena, r["tensors"], bc.MODES[mode][1], bc.MODES[mode][0]), written
 
 
 def assert_tensors(got, want):
-    assert sorted(got) == sorted(want)
+    assert sorted(map(str, got)) == sorted(map(str, want))
     for t, w in want.items():
         assert got[t].dtype == w.dtype and got[t].shape == w.shape and np.array_equal(got[t], w), t
 
@@ -53,12 +52,9 @@ def test_collated_block_equals_collate_of_the_single_frames(mode):
     assert [f["items"] == 0 for f in r["frames"]] == [g is None for g in graphs]
     want_batch = bc.collate([g for g in graphs if g is not None], bc.MODES[mode][0])
     got, written = run_block(r, mode)
-    assert_tensors(got, bc.tensors_of_batch(want_batch, mode))
-    # every byte of every tensor is written (exactly once: expand_block), and nothing outside the tensors
-    covered = np.zeros_like(written)
-    for t, dst, rows, width in r["tensors"].tolist():
-        covered[dst:dst + got[t].nbytes] = True
-    assert np.array_equal(covered, written)
+    assert_tensors(got, bc.collated_arrays(want_batch, bc.MODES[mode][0]))
+    # every byte of every tensor is written (exactly once: fb.expand), and nothing outside the tensors
+    assert np.array_equal(fb.covered(written.size, r["tensors"], bc.MODES[mode][1], bc.MODES[mode][0]), written)
     if not bc.MODES[mode][0]:
         assert r["max_graph_nodes"] == want_batch.max_graph_nodes
         nodes, edges = dsg._node_type_names(bc.MODES[mode][1], False), dsg._edge_type_names(bc.MODES[mode][1], False)
@@ -72,16 +68,15 @@ def test_collated_block_equals_collate_of_the_single_frames(mode):
 def test_store_block_equals_what_graphstore_cats(mode):
     r = host(bc.FRAME_NAMES, mode, form=_lib.FB_STORE)
     graphs = [g for g in cpu_graphs(mode) if g is not None]
-    want = bc.store_tensors(graphs, mode)
+    homog, ht = bc.MODES[mode][:2]
+    want = bc.store_arrays(graphs, homog)
     got, _ = run_block(r, mode)
     assert_tensors(got, want)
-    assert not any(bc.batch_tensor_name(t, mode)[1] == "batch" for t in got)
-    homog, ht = bc.MODES[mode][:2]
-    FB = _lib.FT_BATCH
-    for k in range(len(dsg._node_type_names(ht, homog))):
-        assert np.array_equal(r["node_ptr"][k], want[FB + _lib.FTB_NODE_PTR + k])
-    for k in range(len(dsg._edge_type_names(ht, homog))):
-        assert np.array_equal(r["edge_ptr"][k], want[FB + _lib.FTB_EDGE_PTR + k])
+    assert not any(attr == "batch" for _, attr in got)
+    for k, t in enumerate(dsg._node_type_names(ht, homog)):
+        assert np.array_equal(r["node_ptr"][k], want[(t, "ptr")])
+    for k, e in enumerate(dsg._edge_type_names(ht, homog)):
+        assert np.array_equal(r["edge_ptr"][k], want[(e, "ptr")])
 
 
 # name -> (frame names, mode, form, expected item count).  Item counts are K * (items of a frame) + (items of the batch), and no
@@ -112,12 +107,11 @@ def test_two_level_lookup(case):
     assert n_items == want_items
     assert groups.size == -(-n_items // 64) == sz[_lib.FBS_GROUPS] and np.array_equal(groups, items[::64, _lib.FI_BLOCK0])
     # the prefix words: an item's word is the sum of the workgroups of the items before it
-    blocks = np.array([bc.item_blocks(it) for it in items.tolist()])
-    assert np.array_equal(items[:, _lib.FI_BLOCK0], np.concatenate([[0], np.cumsum(blocks)[:-1]])) and blocks.sum() == n_blocks
+    blocks = fb.check_prefix(items, n_blocks)
     if case == "empty_tail_of_a_group":  # empty items at the end of a group, a non-empty one at the start of the next
         assert any(blocks[64 * g - 1] == 0 and blocks[64 * g] > 0 for g in range(1, groups.size)), blocks.reshape(-1)[:200]
     # every workgroup maps to a non-empty item; each item gets exactly its number of workgroups, in order
-    found = [bc.lookup(groups, items, n_items, b) for b in range(n_blocks)]
+    found = [fb.lookup(groups, items, n_items, b) for b in range(n_blocks)]
     assert found == sorted(found) and all(blocks[i] > 0 for i in found)
     assert np.array_equal(np.bincount(found, minlength=n_items), blocks)
     # every section read and arena write lies inside its buffer and is aligned (checked by the numpy execution)
@@ -137,7 +131,7 @@ def test_capacity():
     r = host([(1, 1)] * k, "typed", with_y=False)
     assert len(r["items"]) == k * per_frame + per_batch <= 4096 < (k + 1) * per_frame + per_batch
     assert r["groups"].size == 64 and r["num_graphs"] == k and r["block"].size == r["sizes"][_lib.FBS_STAGING_BYTES]
-    found = [bc.lookup(r["groups"], r["items"], len(r["items"]), b) for b in (0, int(r["sizes"][_lib.FBS_BLOCKS]) - 1)]
+    found = [fb.lookup(r["groups"], r["items"], len(r["items"]), b) for b in (0, int(r["sizes"][_lib.FBS_BLOCKS]) - 1)]
     assert found[0] == 0 and found[1] == len(r["items"]) - 1
     with pytest.raises(_lib.HydraMPError, match="4096"):
         host([(1, 1)] * (k + 1), "typed", with_y=False)
@@ -184,49 +178,32 @@ def test_a_batch_of_only_empty_frames_has_no_items(mode):
 @pytest.mark.parametrize("mode", LAYOUT_MODES)
 @pytest.mark.parametrize("name", ["fixture", (1, 1)], ids=str)
 def test_a_one_frame_batch_equals_the_frame(name, mode):
-    """the tensors of a one-frame batch, read from its block, are the single-frame block's (fc.read_block for typed frames; a
-    homogeneous frame's block is executed with the same numpy code, through its own item table)"""
+    """the tensors of a one-frame batch, read from its block, are the single-frame block's, executed with the same numpy code
+    through its own item table"""
+    homog, ht = bc.MODES[mode][:2]
     r = host([name], mode, with_y=False)
     got, _ = run_block(r, mode)
     single = dsg.frame_host_stage(*bc.frame(name), **bc.host_kwargs(mode))
     table = fc.semantic_table().numpy() if bc.MODES[mode][3] else None
-    FB = _lib.FT_BATCH
-    if not bc.MODES[mode][0]:
-        want = fc.read_block(single["block"], single["items"], table)
-    else:
-        arena, _ = bc.expand_block(single["block"], single["items"], int(single["sizes"][_lib.FS_ARENA_BYTES]), table)
-        tensors = r["tensors"][r["tensors"][:, 0] < FB].copy()  # one graph: the frame's own shapes, in the frame's tensor order
-        tensors[:, 1] = first_dst(single["items"])  # at the single frame's own arena offsets
-        want = bc.views(arena, tensors, mode)
-    frame_tensors = {t: v for t, v in got.items() if t < FB}
-    assert sorted(frame_tensors) == sorted(want)
-    for t, w in want.items():
-        assert frame_tensors[t].dtype == w.dtype and np.array_equal(frame_tensors[t], w), t
+    fb.check_kinds(single["items"], fb.HOMOG_KINDS) if homog else fb.check_typed_frame(single["items"])
+    arena, _ = fb.expand(single["block"], single["items"], int(single["sizes"][_lib.FS_ARENA_BYTES]), table)
+    want = fb.views(arena, fb.tensor_rows(single["items"]), ht, homog)
+    frame_tensors = {k: v for k, v in got.items() if k[1] not in ("batch", "ptr")}
+    assert sorted(map(str, frame_tensors)) == sorted(map(str, want))
+    for k, w in want.items():
+        assert frame_tensors[k].dtype == w.dtype and np.array_equal(frame_tensors[k], w), k
     # what the batch adds: one graph
-    for t, v in got.items():
-        attr = bc.batch_tensor_name(t, mode)[1]
+    for (_, attr), v in got.items():
         if attr == "batch":
             assert not v.any()
         elif attr == "ptr":
             assert v.size == 2 and v[0] == 0
 
 
-def first_dst(items):
-    """arena offset of every tensor of a single homogeneous frame, in table order (the first segment's is the tensor's)"""
-    seen, out = set(), []
-    for it in items.tolist():
-        if it[_lib.FI_TENSOR] not in seen:
-            seen.add(it[_lib.FI_TENSOR])
-            out.append(it[_lib.FI_DST])
-    return out
-
-
 def test_batch_host_stage_is_clean_under_asan_and_ubsan(tmp_path):
-    """`make frame_batch_check`: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only,
+    """`make frame_check`, run with --batch: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only,
     the runtimes linked statically, nothing preloaded, nothing loaded into Python), run on the frame list: frame build, batch build,
     sizes, host arrays, pack and destroy, in both forms and both layouts, baseline and H-tree"""
-    csrc = os.path.join(ROOT, "hydra-gnn_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "frame_batch_check"], check=True, capture_output=True)
     runs = []
     for ht in (False, True):
         files = []
@@ -235,9 +212,5 @@ def test_batch_host_stage_is_clean_under_asan_and_ubsan(tmp_path):
             dsg.save_frame_file(path, *arrays, htree=ht, sem_dim=0 if ht else 300, n_labels=0 if ht else fc.N_LABELS, clique_dim=6 if ht else 0)
             files.append(path)
         runs.append(files)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     for files in runs:
-        p = subprocess.run([os.path.join(csrc, "build", "frame_batch_check")] + files, env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0 and "FRAME-BATCH-CHECK-OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
-        assert p.stdout.count("frames 6 graphs 5") == 4  # typed / homogeneous x collated / store
-        assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
+        assert fb.run_frame_check(["--batch"] + files).count("frames 6 graphs 5") == 4  # typed / homogeneous x collated / store

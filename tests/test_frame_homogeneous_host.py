@@ -1,18 +1,18 @@
 """Host stage of the HOMOGENEOUS frame pipeline (csrc/frame.cpp ``hmp_frame_build_homogeneous``; include/hydra_mp.h section 14)
-without a device.  The packed block is read with numpy, item by item -- one item per segment of a tensor, what the one launch is
-specified to write -- and compared bit for bit with the committed host conversion run on the CPU:
+without a device.  The packed block is executed with numpy (tests/_frame_block.py), item by item -- one item per segment of a
+tensor, what the one launch is specified to write -- and compared bit for bit with the committed host conversion run on the CPU:
 ``data.heterogeneous_data_to_homogeneous`` (+ ``room_mask``) of the existing frame, ``data.heterogeneous_htree_to_homogeneous`` of
 its H-tree.  Also: the layout of the segments in the arena, the block of a NON-homogeneous frame (unchanged, pinned by hashes taken
 before the homogeneous layout existed), the refusals, and the stand-alone sanitizer program."""
 import ctypes as C
 import hashlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _frame_block as fb
 import _frame_cases as fc
 from hydra_gnn_amd import _lib, dsg, htree
 from hydra_gnn_amd.data import Data, heterogeneous_data_to_homogeneous, heterogeneous_htree_to_homogeneous
@@ -61,79 +61,33 @@ def attributes(d: Data):
 def tensor_geometry(items):
     """{tensor: (base byte, rows, pitch)}: a tensor starts where its first item does, its segments' rows add up, and every segment
     of an edge tensor carries the pitch of the whole (S1)"""
-    geo = {}
-    for kind, tensor, rows, width, dst, _, s1, *_ in items.tolist():
-        assert H0 <= tensor < H0 + _lib.FT_HOMOG_COUNT, tensor
-        pitch = s1 if kind == _lib.FK_EDGE_SEG else width
-        if tensor not in geo:
-            assert dst % 16 == 0, (tensor, dst)
-            geo[tensor] = [dst, 0, pitch]
-        assert geo[tensor][2] == pitch, "one pitch per tensor"
-        geo[tensor][1] += rows if kind != _lib.FK_EDGE_SEG else 0
-    return {t: tuple(g) for t, g in geo.items()}
+    rows = fb.tensor_rows(items)  # asserts one pitch per tensor
+    assert all(H0 <= t < H0 + _lib.FT_HOMOG_COUNT and dst % 16 == 0 for t, dst, _, _ in rows), rows
+    return {t: (dst, n, pitch) for t, dst, n, pitch in rows}
 
 
-def read_homogeneous(block, items, table):
-    """{attribute: array} from a packed homogeneous block.  Sources are read through ``_frame_cases.read_block`` (every read checked
-    to lie inside the block) for the kinds it knows, here for the new ones; every segment must lie inside its tensor, and the
-    segments of a tensor must cover it exactly once."""
-
-    def sec(off, dtype, count):
-        nbytes = count * np.dtype(dtype).itemsize
-        assert off >= 0 and off % 16 == 0 and off + nbytes <= block.size, (off, count, block.size)
-        return block[off:off + nbytes].view(dtype)
-
+def read_homogeneous(r, htree_mode, table):
+    """{attribute: array} of a homogeneous frame: its block executed with numpy (``fb.expand``: every read inside the block, every
+    write inside the arena, no byte twice) and viewed through its item table.  A homogeneous frame holds the five kinds of
+    ``fb.HOMOG_KINDS``; every segment starts at a whole row (an edge segment: column) of its tensor and an edge segment lies inside
+    the pitch; a CONST item reads no section and writes its tensor's element; and the segments of a tensor cover it exactly once,
+    with nothing written outside the tensors."""
+    items = r["items"]
+    fb.check_kinds(items, fb.HOMOG_KINDS)
     geo = tensor_geometry(items)
-    out, written = {}, {}
-    for t, (base, rows, pitch) in geo.items():
-        attr = dsg._HOMOG_TENSORS[t - H0]
-        if attr.endswith("edge_index"):
-            out[t] = np.full((2, pitch), -1, dtype=np.int64)
-        elif attr.endswith("_type"):
-            out[t] = np.full((rows,), -1, dtype=np.int64)
-        elif attr.endswith("_mask"):
-            out[t] = np.full((rows,), 255, dtype=np.uint8)
-        else:
-            out[t] = np.full((rows, pitch), np.nan, dtype=np.float32)
-        written[t] = np.zeros(out[t].shape[-1] if attr.endswith("edge_index") else out[t].shape[0], dtype=np.int32)
-    for it in items.tolist():
-        kind, tensor, rows, width, dst, s0, s1, s2, s3, p0, p1, _ = it
-        base = geo[tensor][0]
+    for kind, tensor, rows, width, dst, s0, s1, s2, s3, p0, p1, _ in items.tolist():
+        at, attr = dst - geo[tensor][0], dsg._HOMOG_TENSORS[tensor - H0]
         if kind == _lib.FK_EDGE_SEG:
-            assert (dst - base) % 8 == 0
-            col0 = (dst - base) // 8
-            assert rows == 2 and 0 <= col0 and col0 + width <= s1
-            e = sec(s0, np.int32, (2 if p0 <= 2 else 1) * p1)
-            ends = np.array([fc._ends(e, p0, p1, c) for c in range(width)], dtype=np.int64).reshape(-1, 2)
-            out[tensor][0, col0:col0 + width] = ends[:, 0] + s2
-            out[tensor][1, col0:col0 + width] = ends[:, 1] + s3
-            written[tensor][col0:col0 + width] += 1
-            continue
-        if kind == _lib.FK_CONST:
-            assert p1 in (1, 8) and out[tensor].dtype.itemsize == p1 and (dst - base) % p1 == 0 and s0 == s1 == s2 == s3 == -1
-            seg = np.full((rows,), p0, dtype=out[tensor].dtype)
-            row_bytes = p1
-        elif kind == _lib.FK_FEAT:
-            own = p0 + 3 + p1
-            assert own <= width  # the destination row is at least as wide as the type's own columns: zeros behind them
-            narrow = list(it)
-            narrow[_lib.FI_WIDTH] = own
-            seg = np.zeros((rows, width), dtype=np.float32)
-            seg[:, :own] = fc.read_block(block, np.array([narrow], dtype=np.int32), table)[tensor]
-            row_bytes = 4 * width
-        elif kind in (_lib.FK_CLIQUE, _lib.FK_EATTR):
-            seg = fc.read_block(block, np.array([it], dtype=np.int32), table)[tensor]
-            row_bytes = 4 * width
+            assert rows == 2 and at % 8 == 0 and 0 <= at // 8 and at // 8 + width <= s1
+        elif kind == _lib.FK_CONST:
+            assert attr.endswith(("_type", "_mask")) and p1 == (1 if attr.endswith("_mask") else 8) and at % p1 == 0 and s0 == s1 == s2 == s3 == -1
         else:
-            raise AssertionError(f"item kind {kind} in a homogeneous frame")
-        assert (dst - base) % row_bytes == 0
-        r0 = (dst - base) // row_bytes
-        assert 0 <= r0 and r0 + rows <= out[tensor].shape[0], (tensor, r0, rows)
-        out[tensor][r0:r0 + rows] = seg
-        written[tensor][r0:r0 + rows] += 1
-    for t, w in written.items():
-        assert (w == 1).all(), f"tensor {t}: every element is written by exactly one segment"
-    return {dsg._HOMOG_TENSORS[t - H0]: (a.view(np.bool_) if a.dtype == np.uint8 else a) for t, a in out.items()}
+            assert at >= 0 and at % (4 * width) == 0
+    arena, written = fb.expand(r["block"], items, int(r["sizes"][_lib.FS_ARENA_BYTES]), table)
+    tensors = fb.tensor_rows(items)
+    got = fb.views(arena, tensors, htree_mode, True)
+    assert np.array_equal(fb.covered(arena.size, tensors, htree_mode, True), written), "every element is written by exactly one segment"
+    return {attr: a for (_, attr), a in got.items()}
 
 
 def clique_rows(tree):
@@ -146,7 +100,7 @@ def clique_rows(tree):
 @pytest.mark.parametrize("name", FRAMES, ids=str)
 def test_packed_block_equals_the_host_conversion(name, mode):
     r = host(name, mode)
-    got = read_homogeneous(r["block"], r["items"], fc.semantic_table().numpy())
+    got = read_homogeneous(r, mode[1], fc.semantic_table().numpy())
     d, tree = oracle(name, mode)
     want = {k: v.numpy() for k, v in attributes(d).items()}
     assert sorted(got) == sorted(want)
@@ -168,14 +122,14 @@ def test_packed_block_equals_the_host_conversion(name, mode):
 
 def test_known_answers_of_the_fixture():
     r = host("fixture", MODES[2])  # baseline, 300-column table
-    got = read_homogeneous(r["block"], r["items"], fc.semantic_table().numpy())
+    got = read_homogeneous(r, False, fc.semantic_table().numpy())
     assert got["x"].shape == (67, 306) and got["edge_index"].shape == (2, 482)
     assert np.bincount(got["edge_type"]).tolist() == [356, 2, 62, 62]
     assert got["room_mask"].dtype == np.bool_ and got["room_mask"].sum() == 5 and got["room_mask"][-5:].all()
     assert not got["x"][62:, 6:].any()  # room rows: no semantic block
     assert len(r["items"]) == 14
     r = host("fixture", MODES[7])  # H-tree, clique_dim 6, 300-column table
-    got = read_homogeneous(r["block"], r["items"], fc.semantic_table().numpy())
+    got = read_homogeneous(r, True, fc.semantic_table().numpy())
     assert got["x"].shape == (268, 306)
     assert got["edge_index"].shape == (2, 394) and got["init_edge_index"].shape == (2, 195) and got["pool_edge_index"].shape == (2, 166)
     assert got["room_mask"].sum() == 5 and got["object_mask"].sum() == 62
@@ -339,8 +293,6 @@ def test_homogeneous_host_stage_is_clean_under_asan_and_ubsan(tmp_path):
     """`make frame_check`: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only, nothing
     preloaded), run with --homogeneous on the fixture frame and on the (300, 3) frame, baseline (with and without relative
     positions) and H-tree; a version-1 file written by dsg.save_frame_file in front of the flag still runs the existing layout"""
-    csrc = os.path.join(ROOT, "hydra-gnn_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "frame_check"], check=True, capture_output=True)
     files = []
     for name in ("fixture", (300, 3)):
         for kw in (dict(sem_dim=300, n_labels=fc.N_LABELS), dict(relative_pos=True, sem_dim=300, n_labels=fc.N_LABELS),
@@ -348,13 +300,8 @@ def test_homogeneous_host_stage_is_clean_under_asan_and_ubsan(tmp_path):
             path = str(tmp_path / f"frame_{len(files)}.bin")
             dsg.save_frame_file(path, *fc.frame(name), **kw)
             files.append(path)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    p = subprocess.run([os.path.join(csrc, "build", "frame_check"), files[0], "--homogeneous"] + files, env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0 and "FRAME-CHECK-OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
-    lines = p.stdout.splitlines()
+    lines = fb.run_frame_check([files[0], "--homogeneous"] + files).splitlines()
     assert "(homogeneous)" not in lines[0] and "items 12 " in lines[0]  # in front of the flag: the existing layout
     assert sum("(homogeneous): kept 62 dropped 3 rooms 5 oo 178 rr 1" in ln for ln in lines) == 4
     assert sum("(homogeneous): kept 300 dropped 0 rooms 3" in ln for ln in lines) == 4
     assert sum("items 49 " in ln for ln in lines) == 4 and sum("items 14 " in ln for ln in lines) == 2 and sum("items 18 " in ln for ln in lines) == 2
-    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]

@@ -3,24 +3,30 @@ against the reference's recorded result, against ``dsg.RoomObjectGraph`` / the o
 irregular case, the H-tree topology inside the packed block against ``htree.htree_topology``, the layout of the block and the arena,
 the refusals, and the stand-alone sanitizer program.  The block is also read with numpy, item by item (what the one launch is
 specified to write), and compared with the existing torch path on the CPU."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _frame_block as fb
 import _frame_cases as fc
 from hydra_gnn_amd import _lib, dsg, htree
 from oracle import dsg_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["fixture", "special"] + fc.SIZES
 
 
 def host(name, **kw):
     tn, mn, mo = fc.THRESHOLDS
     return dsg.frame_host_stage(*fc.frame(name), threshold_near=tn, max_near=mn, max_on=mo, **kw)
+
+
+def read_block(r, htree_mode, table=None):
+    """{(store key, attribute): array} of a typed frame: its block executed with numpy"""
+    items = r["items"]
+    fb.check_typed_frame(items)
+    arena, _ = fb.expand(r["block"], items, int(r["sizes"][_lib.FS_ARENA_BYTES]), table)
+    return fb.views(arena, fb.tensor_rows(items), htree_mode, False)
 
 
 def test_fixture_reproduces_the_reference():
@@ -77,14 +83,14 @@ def test_htree_topology_in_the_packed_block(name):
     assert [int(v) for v in sz[_lib.FS_HT_COUNTS:_lib.FS_HT_COUNTS + 4]] == want["counts"]
     assert [int(v) for v in sz[_lib.FS_HT_EDGES:_lib.FS_HT_EDGES + 10]] == [e.shape[1] for e in want["edges"]]
     assert [int(v) for v in sz[_lib.FS_HT_INIT:_lib.FS_HT_INIT + 3]] == [e.shape[1] for e in want["init"]]
-    got = fc.read_block(r["block"], r["items"])
+    got = read_block(r, True)
     T0 = _lib.FT_HTREE
     for k in range(10):
-        assert np.array_equal(got[T0 + 14 + k], want["edges"][k]), k
+        assert np.array_equal(got[dsg._FRAME_TENSORS[T0 + 14 + k]], want["edges"][k]), k
     for k in range(3):
-        assert np.array_equal(got[T0 + 24 + k], want["init"][k]), k
+        assert np.array_equal(got[dsg._FRAME_TENSORS[T0 + 24 + k]], want["init"][k]), k
     for t, orig in ((T0 + 27, want["object_orig"]), (T0 + 28, want["room_orig"])):  # the pool lists [arange | orig]
-        assert np.array_equal(got[t], np.stack([np.arange(orig.size), orig]))
+        assert np.array_equal(got[dsg._FRAME_TENSORS[t]], np.stack([np.arange(orig.size), orig]))
 
 
 @pytest.mark.parametrize("mode", ["baseline", "relative_pos", "sem300", "htree", "htree_sem300"])
@@ -110,19 +116,19 @@ def test_layout_and_block_contents(name, mode):
     spans.sort()
     assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))
     table = fc.semantic_table().numpy()
-    got = fc.read_block(r["block"], items, table)
+    got = read_block(r, ht, table)
     data, _ = fc.existing_frame(fc.frame(name), sem, relative_pos=mode == "relative_pos")
     if ht:
         data = htree.generate_htree(data, clique_dim=6)
-    want = fc.tensors_of(data, ht)
-    assert sorted(got) == sorted(want)
+    want = fc.hetero_arrays(data)  # the existing path's own stores and attributes, not the table's
+    assert sorted(map(str, got)) == sorted(map(str, want))
     for t, w in want.items():
-        if ht and t in (_lib.FT_HTREE + 6, _lib.FT_HTREE + 7):
-            members = fc.clique_members(data, 2 if t == _lib.FT_HTREE + 6 else 3)
+        if ht and t in (("object-room", "x"), ("room-room", "x")):
+            members = fc.clique_members(data, 2 if t[0] == "object-room" else 3)
             small = np.array([len(m) <= 2 for m in members], dtype=bool)
             assert not got[t][:, 3:].any() and np.array_equal(got[t][small], w[small])
             continue
-        assert got[t].dtype == w.dtype and got[t].shape == w.shape and np.array_equal(got[t], w), dsg._FRAME_TENSORS[t]
+        assert got[t].dtype == w.dtype and got[t].shape == w.shape and np.array_equal(got[t], w), t
 
 
 def test_refusals():
@@ -140,6 +146,20 @@ def test_refusals():
         dsg.frame_host_stage(ids, layer, pos, bb_min, bb_max, label, edges, htree=True, relative_pos=True)
     with pytest.raises(_lib.HydraMPError, match="relative"):
         dsg.FramePipeline("cuda:0", htree=True, relative_pos=True)
+    # an output tensor number that a mode does not define (another mode's included) is refused, never viewed as some default type
+    arena = torch.zeros(64, dtype=torch.uint8)
+    defined = {(False, False): 16 + 10, (True, False): 29 + 17 + 33, (False, True): 9 + 4, (True, True): 9 + 6}  # own range(s) + batch range
+    for mode, table in dsg._TENSOR_TABLES.items():
+        assert len(table) == _lib.FT_HTREL + _lib.FT_HTREL_COUNT and sum(e[2] is not None for e in table) == defined[mode]
+        resolved = dsg._resolve_views(table, arena.view(torch.float32), arena.view(torch.int64), arena.view(torch.bool))
+        for t, entry in enumerate(table):
+            if entry[2] is None:
+                with pytest.raises(_lib.HydraMPError, match=f"number {t} "):
+                    dsg._arena_view(resolved, t, 0, 1, 1)
+            else:
+                assert dsg._arena_view(resolved, t, 16, 2, 2).numel() in (2, 4)
+        with pytest.raises(_lib.HydraMPError, match="number 104 "):
+            dsg._arena_view(resolved, len(table), 0, 1, 1)
     with pytest.raises(_lib.HydraMPError, match="listed twice"):
         dsg.frame_host_stage(np.concatenate([ids, ids[:1]]), *[np.concatenate([a, a[:1]]) for a in (layer, pos, bb_min, bb_max, label)], edges)
 
@@ -162,16 +182,11 @@ def test_frames_without_a_room_or_without_kept_objects_return_none(htree_mode):
 def test_host_stage_is_clean_under_asan_and_ubsan(tmp_path):
     """`make frame_check`: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only, nothing
     preloaded), run on the fixture frame and on the (300, 3) frame, baseline and H-tree"""
-    csrc = os.path.join(ROOT, "hydra-gnn_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "frame_check"], check=True, capture_output=True)
     files = []
     for name in ("fixture", (300, 3)):
         for ht in (False, True):
             path = str(tmp_path / f"frame_{len(files)}.bin")
             dsg.save_frame_file(path, *fc.frame(name), htree=ht, sem_dim=0 if ht else 300, n_labels=0 if ht else fc.N_LABELS, clique_dim=6 if ht else 0)
             files.append(path)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")  # the sanitizer runtimes are linked statically: nothing is preloaded
-    p = subprocess.run([os.path.join(csrc, "build", "frame_check")] + files, env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "FRAME-CHECK-OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
-    assert "kept 62 dropped 3 rooms 5 oo 178 rr 1" in p.stdout and "kept 300 dropped 0 rooms 3" in p.stdout
-    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
+    out = fb.run_frame_check(files)
+    assert "kept 62 dropped 3 rooms 5 oo 178 rr 1" in out and "kept 300 dropped 0 rooms 3" in out

@@ -7,13 +7,13 @@ from the commit before this mode existed), and the stand-alone sanitizer program
 import ctypes as C
 import hashlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import _frame_batch_cases as bc
+import _frame_block as fb
 import _frame_cases as fc
 import _frame_htree_relpos_cases as hc
 from hydra_gnn_amd import _lib, data as hdata, dsg, htree
@@ -27,9 +27,11 @@ def single(name, homogeneous, sem=False):
     key = (str(name), homogeneous, sem)
     if key not in _SINGLE:
         r = dsg.frame_host_stage(*hc.frame(name), **hc.host_kwargs(homogeneous, sem))
-        arena, written = hc.expand(r["block"], r["items"], int(r["sizes"][_lib.FS_ARENA_BYTES]), fc.semantic_table().numpy())
+        fb.check_kinds(r["items"], fb.HTREL_KINDS)  # the mode has no plain EATTR item
+        arena, written = fb.expand(r["block"], r["items"], int(r["sizes"][_lib.FS_ARENA_BYTES]), fc.semantic_table().numpy())
         r["written"] = written
-        _SINGLE[key] = (r, (hc.homogeneous_views if homogeneous else hc.typed_views)(arena, r["items"]))
+        views = fb.views(arena, fb.tensor_rows(r["items"]), True, homogeneous)
+        _SINGLE[key] = (r, {attr: a for (_, attr), a in views.items()} if homogeneous else views)
     return _SINGLE[key]
 
 
@@ -91,7 +93,7 @@ def check_typed_block(name, sem):
     items, sz = r["items"], r["sizes"]
     assert len(items) == 46 == sz[_lib.FS_ITEMS] and set(items[:, _lib.FI_KIND].tolist()) == {_lib.FK_FEAT, _lib.FK_POS, _lib.FK_I64, _lib.FK_EDGE, _lib.FK_CLIQUE, _lib.FK_EATTR_HT}
     assert (items[:, _lib.FI_DST] % 16 == 0).all()
-    hc.check_prefix(items, int(sz[_lib.FS_BLOCKS]))
+    fb.check_prefix(items, int(sz[_lib.FS_BLOCKS]))
     tree, members, rpos = oracle(name, sem)
     bounds = {t: hc.clique_bound(members[t], rpos) for t in hc.CLIQUE_TYPES}
     want = {(k, a): v.numpy() for k in tree.node_types + tree.edge_types for a, v in tree[k].items()}
@@ -121,7 +123,7 @@ def test_homogeneous_block_equals_the_oracle(name):
     r, got = single(name, True)
     items, sz = r["items"], r["sizes"]
     assert len(items) == 59 == sz[_lib.FS_ITEMS]
-    hc.check_prefix(items, int(sz[_lib.FS_BLOCKS]))
+    fb.check_prefix(items, int(sz[_lib.FS_BLOCKS]))
     tree, members, rpos = hc.oracle_typed(hc.frame(name))  # heterogeneous_htree_to_homogeneous edits its argument: a fresh one
     bounds = {t: hc.clique_bound(members[t], rpos) for t in hc.CLIQUE_TYPES}
     eb = np.concatenate([hc.edge_bound(tuple(k), tree[tuple(k)].edge_index.numpy(), bounds) for k in hc.EDGE_KEYS[:10]])
@@ -136,7 +138,7 @@ def test_homogeneous_block_equals_the_oracle(name):
     # the same values as the typed block's, segment by segment, bit for bit
     typed = single(name, False)[1]
     assert np.array_equal(got["edge_attr"], np.concatenate([typed[(k, "edge_attr")] for k in hc.EDGE_KEYS[:10]]))
-    # every written byte once (hc.expand), and the segments of a tensor tile it: no gap inside the tensors either
+    # every written byte once (fb.expand), and the segments of a tensor tile it: no gap inside the tensors either
     x_bytes = got["x"].size * 4
     assert r["written"][:x_bytes].all()
 
@@ -170,19 +172,20 @@ def test_batch_block_equals_the_collation_of_the_single_frames(homogeneous, form
     n_items = int(sz[_lib.FBS_ITEMS])
     assert r["num_graphs"] == 6 and r["graph_of_frame"].tolist() == [0, 1, -1, 2, 3, 4, 5]
     assert groups.size == -(-n_items // 64) >= 3 and np.array_equal(groups, items[::64, _lib.FI_BLOCK0])  # several item groups
-    blocks = hc.check_prefix(items, int(sz[_lib.FBS_BLOCKS]))
+    blocks = fb.check_prefix(items, int(sz[_lib.FBS_BLOCKS]))
     if not homogeneous and form == _lib.FB_COLLATED:  # a group that ends in empty items, the next one starting with work
         assert any(blocks[64 * g - 1] == 0 and blocks[64 * g:].any() for g in range(1, groups.size)), blocks.tolist()
     for b in range(0, int(sz[_lib.FBS_BLOCKS]), 7):  # the two-level lookup lands on the item that owns the workgroup
-        i = bc.lookup(groups, items, n_items, b)
+        i = fb.lookup(groups, items, n_items, b)
         assert blocks[i] > 0 and items[i, _lib.FI_BLOCK0] <= b < items[i, _lib.FI_BLOCK0] + blocks[i]
-    arena, written = hc.expand(r["block"], items, int(sz[_lib.FBS_ARENA_BYTES]))
-    got = hc.batch_views(arena, r["tensors"], homogeneous)
+    fb.check_kinds(items, fb.HTREL_KINDS)
+    arena, written = fb.expand(r["block"], items, int(sz[_lib.FBS_ARENA_BYTES]))
+    got = fb.views(arena, r["tensors"], True, homogeneous)
     graphs = cpu_graphs(BATCH_NAMES, homogeneous, ys)
     if form == _lib.FB_COLLATED:
-        want = hc.collated_arrays(bc.collate(graphs, homogeneous), homogeneous)
+        want = bc.collated_arrays(bc.collate(graphs, homogeneous), homogeneous)
     else:
-        want = hc.store_arrays(graphs, homogeneous)
+        want = bc.store_arrays(graphs, homogeneous)
     assert sorted(map(str, got)) == sorted(map(str, want))
     for k, w in want.items():  # the per-frame results are the kernel's own arithmetic: exact everywhere
         assert got[k].dtype == w.dtype and got[k].shape == w.shape and np.array_equal(got[k], w), k
@@ -338,19 +341,14 @@ def test_the_numbers_of_the_mode_lie_behind_every_earlier_one():
 
 # ---- the stand-alone sanitizer program -------------------------------------------------------------------------------------------
 def test_host_and_batch_stage_are_clean_under_asan_and_ubsan(tmp_path):
-    """`make frame_htree_relpos_check`: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU
+    """`make frame_check`, run with --htree-relpos: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU
     only, the runtimes linked statically, nothing preloaded).  It builds every frame file in the new mode, typed and homogeneous,
     packs it into a buffer cut to size, and runs the batch stage over all of them in both forms."""
-    csrc = os.path.join(ROOT, "hydra-gnn_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "frame_htree_relpos_check"], check=True, capture_output=True)
     files = []
     for name in ("fixture", "triangle", (1, 1), "no_room", (300, 3)):
         path = str(tmp_path / f"frame_{len(files)}.bin")
         dsg.save_frame_file(path, *hc.frame(name), htree=True, htree_relative_pos=True, clique_dim=hc.CLIQUE_DIM)
         files.append(path)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    p = subprocess.run([os.path.join(csrc, "build", "frame_htree_relpos_check")] + files, env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "FRAME-HTREE-RELPOS-CHECK-OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
-    assert "typed frame 0: items 46" in p.stdout and "homogeneous frame 0: items 59" in p.stdout and "typed frame 3: items 0" in p.stdout
-    assert "typed collated: frames 5 graphs 4" in p.stdout and "homogeneous store: frames 5 graphs 4" in p.stdout
-    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
+    out = fb.run_frame_check(["--htree-relpos"] + files)
+    assert "typed frame 0: items 46" in out and "homogeneous frame 0: items 59" in out and "typed frame 3: items 0" in out
+    assert "typed collated: frames 5 graphs 4" in out and "homogeneous store: frames 5 graphs 4" in out

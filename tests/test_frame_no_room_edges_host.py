@@ -3,12 +3,10 @@
 ``_frame_cases`` the host stage equals, byte for byte, the host stage of the same frame with the room-room pairs deleted from
 ``edges`` by the test itself.  No GPU."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import _frame_block as fb
 import _frame_cases as fc
 from hydra_gnn_amd import _lib, dsg
 
@@ -100,19 +98,13 @@ def test_a_batch_shares_the_flag_and_unknown_flags_are_refused():
 
 @pytest.mark.parametrize("mode", ["typed_relpos", "htree_relpos"])
 def test_the_flag_is_clean_under_asan_and_ubsan(tmp_path, mode):
-    """`make frame_flags_check`: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only, the
+    """`make frame_check`, run with --flags: frame.cpp + htree.cpp + a program with its own main under -fsanitize=address,undefined (CPU only, the
     runtimes linked statically, nothing preloaded) on existing ``HMPF`` files, with the flag from the command line and without"""
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hydra-gnn_amd", "csrc")
-    subprocess.run(["make", "-C", csrc, "frame_flags_check"], check=True, capture_output=True)
     kw = {k: v for k, v in MODES[mode].items() if k != "homogeneous"}
     files = []
     for name in ("fixture", "special", (7, 2)):
         files.append(str(tmp_path / f"frame_{len(files)}.bin"))
         dsg.save_frame_file(files[-1], *fc.frame(name), **kw)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    p = subprocess.run([os.path.join(csrc, "build", "frame_flags_check")] + files + ["--no-room-edges"] + files, env=env, capture_output=True,
-                       text=True, timeout=300)
-    assert p.returncode == 0 and "FRAME-FLAGS-CHECK-OK" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
-    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-3000:]
-    assert "flags 0: kept 62 dropped 3 rooms 5 oo 178 rr 1 " in p.stdout and "flags 1: kept 62 dropped 3 rooms 5 oo 178 rr 0 " in p.stdout
-    assert p.stdout.count("batch no-room-edges") == 4 and "(homogeneous) flags 1" in p.stdout
+    out = fb.run_frame_check(["--flags"] + files + ["--no-room-edges"] + files)
+    assert "flags 0: kept 62 dropped 3 rooms 5 oo 178 rr 1 " in out and "flags 1: kept 62 dropped 3 rooms 5 oo 178 rr 0 " in out
+    assert out.count("batch no-room-edges") == 4 and "(homogeneous) flags 1" in out
