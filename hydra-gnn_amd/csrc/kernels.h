@@ -462,6 +462,75 @@ struct GradReduceDyn {  // passed by value: keep it small
   int slab_stride[GRAD_MAX_SLAB_IDS + 1];
 };
 
+// Static block -> work map of grad_reduce_kernel (FrontArgs::pack_map is the precedent): one line-aligned record per workgroup
+// of the launch, built once per bound network from the segment table and resident in device memory.  A workgroup reads its own
+// record with one wave-uniform request instead of searching a block table and walking a 216-byte GradSeg field by field.
+//  GR_COPY  every term is GT_COPY: the record holds all a thread needs; element `first + threadIdx.x` of the segment, stored at
+//           dst + threadIdx.x, threads >= n_live idle
+//  GR_SEG   some term reads parameters (GT_ATT_OUTER*, or a dot product among several terms): thread per element as above, the
+//           terms come from segs[seg]
+//  GR_WAVE  one GT_ATT_DOT* term: a wavefront per element, 4 elements per workgroup from `first` on, through segs[seg]
+enum { GR_COPY = 0, GR_SEG = 1, GR_WAVE = 2 };
+struct GradRecTerm {
+  int64_t src;  // GradTerm::src
+  int ld, C, Cp;
+  int slab_id;
+  float scale;
+  int pad_;
+};
+struct alignas(128) GradRec {
+  int64_t dst;   // flat offset (gradient and parameter buffers) of the workgroup's first element
+  int first;     // index of that element inside its segment
+  int n_live;    // elements of the workgroup: 1 .. 256 (GR_WAVE: 1 .. 4)
+  int cols;
+  int kind;      // GR_*
+  int seg;       // index into the GradSeg table
+  int n_terms;
+  GradRecTerm t[3];
+};
+static_assert(sizeof(GradRec) == 128 && sizeof(GradRecTerm) == 32, "a record is two 64-byte lines");
+
+inline int grad_seg_kind(const GradSeg& g) {
+  if (g.n_terms == 1 && (g.t[0].kind == GT_ATT_DOT || g.t[0].kind == GT_ATT_DOT_T)) return GR_WAVE;
+  for (int ti = 0; ti < g.n_terms; ++ti)
+    if (g.t[ti].kind != GT_COPY) return GR_SEG;
+  return GR_COPY;
+}
+// workgroups of segment g: 256 elements each, 4 in wavefront-per-element mode
+inline int64_t grad_seg_blocks(const GradSeg& g) {
+  const int64_t el = (int64_t)g.rows * g.cols;
+  const int per = grad_seg_kind(g) == GR_WAVE ? 4 : 256;
+  return (el + per - 1) / per;
+}
+// Records of segments gs[0 .. n) in launch order into out[] (room for the sum of grad_seg_blocks); returns how many were
+// written.  Host code without a HIP call: tools/grad_records_check.cpp runs it on the CPU.
+inline int64_t grad_records_build(const GradSeg* gs, int n, GradRec* out) {
+  int64_t nb = 0;
+  for (int si = 0; si < n; ++si) {
+    const GradSeg& g = gs[si];
+    const int64_t el = (int64_t)g.rows * g.cols;
+    const int kind = grad_seg_kind(g);
+    const int per = kind == GR_WAVE ? 4 : 256;
+    for (int64_t first = 0; first < el; first += per) {
+      GradRec& R = out[nb++];
+      memset(&R, 0, sizeof(R));
+      R.dst = g.dst + first;
+      R.first = (int)first;
+      R.n_live = (int)(el - first < per ? el - first : per);
+      R.cols = g.cols;
+      R.kind = kind;
+      R.seg = si;
+      R.n_terms = g.n_terms;
+      for (int ti = 0; ti < g.n_terms && kind == GR_COPY; ++ti) {
+        const GradTerm& T = g.t[ti];
+        GradRecTerm& Q = R.t[ti];
+        Q.src = T.src; Q.ld = T.ld; Q.C = T.C; Q.Cp = T.Cp; Q.slab_id = T.slab_id; Q.scale = T.scale;
+      }
+    }
+  }
+  return nb;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K3: GAT edge softmax + aggregation
 // ---------------------------------------------------------------------------------------------
@@ -600,8 +669,25 @@ struct AdamFuse {
   const int* step_dev;
   const float* count;
 };
+// grad_reduce_kernel's one by-value argument.  What a workgroup needs to REQUEST its record and Adam's uniform words (recs, adam)
+// fills the first two lines; the kernel warms all the others (karg_warm), dyn's among them, while the record is in flight
+struct GradReduceArgs {
+  const GradRec* recs;
+  AdamFuse adam;
+  const GradSeg* segs;
+  const float* slabs;
+  const float* params;
+  float* grads;
+  const float* row_lv;
+  float* out2;
+  NetState* state;
+  int n_lv_rows;
+  GradReduceDyn dyn;
+};
+static_assert(offsetof(GradReduceArgs, adam) + sizeof(AdamFuse) <= 128, "recs and adam: the two lines requested at entry");
+// d_recs: the n_recs workgroup records of d_segs (grad_records_build), one workgroup each.
 // row_lv != null: block (0,0) also sums the per-row {loss, valid} pairs (masked_ce_rows_launch) into out2 / state
-int grad_reduce_launch(const GradSeg* d_segs, const SegBlocks& sb, const GradReduceDyn& dyn, const float* d_slabs,
+int grad_reduce_launch(const GradSeg* d_segs, const GradRec* d_recs, int n_recs, const GradReduceDyn& dyn, const float* d_slabs,
                        const float* d_params, float* d_grads, const float* row_lv, int n_lv_rows, float* out2, NetState* state,
                        const AdamFuse& adam, hipStream_t st);
 

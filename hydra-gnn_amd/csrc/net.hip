@@ -139,7 +139,9 @@ struct hmp_net {
   int64_t grad_elems = 0;
   int max_pack_rows = 0;
   int64_t max_grad_elems = 0;
-  SegBlocks pack_sb, grad_sb;
+  SegBlocks pack_sb;
+  GradRec* d_grad_recs = nullptr;  // grad_reduce_kernel: one record per workgroup (grad_records_build over d_grad_segs)
+  int n_grad_recs = 0;
   int2* d_pack_map = nullptr;  // front kernel: pack block (16 items) -> {segment, first item}
   int n_pack_blocks16 = 0;
   char* ws_base = nullptr;
@@ -414,6 +416,29 @@ GradTerm term(int kind, int slab_id, int64_t src, int ld, int C, int Cp, int inn
   return t;
 }
 
+// the workgroup records of the gradient un-pack for segment table gs (kernels.h grad_records_build), replacing the net's
+int upload_grad_records(hmp_net* n, const std::vector<GradSeg>& gs) {
+  int64_t nb = 0;
+  for (const GradSeg& g : gs) nb += grad_seg_blocks(g);
+  HMP_CHECK_ARG(nb <= INT32_MAX, "net: %lld gradient un-pack workgroups", (long long)nb);
+  std::vector<GradRec> recs((size_t)nb);
+  const int64_t got = grad_records_build(gs.data(), (int)gs.size(), recs.data());
+  HMP_CHECK_ARG(got == nb, "net: gradient record table: %lld records for %lld workgroups", (long long)got, (long long)nb);
+  GradRec* d = nullptr;
+  if (nb > 0) {
+    HMP_HIP(hipMalloc(&d, recs.size() * sizeof(GradRec)));
+    if (hipMemcpy(d, recs.data(), recs.size() * sizeof(GradRec), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      snprintf(err_buf(), 512, "net: copy of the gradient record table failed");
+      return HMP_E_HIP;
+    }
+  }
+  if (n->d_grad_recs) (void)hipFree(n->d_grad_recs);
+  n->d_grad_recs = d;
+  n->n_grad_recs = (int)nb;
+  return HMP_OK;
+}
+
 // static pack / grad tables ------------------------------------------------------------------------
 int build_tables(hmp_net* n) {
   const hmp_net_spec& S = n->spec;
@@ -587,17 +612,11 @@ int build_tables(hmp_net* n) {
       HMP_HIP(hipMemcpy(n->d_pack_map, pm.data(), pm.size() * sizeof(int2), hipMemcpyHostToDevice));
     }
   }
-  n->grad_sb.n = (int)gs.size();
-  n->grad_sb.start[0] = 0;
-  for (size_t i = 0; i < gs.size(); ++i) {
-    const bool wave_mode = gs[i].n_terms == 1 && (gs[i].t[0].kind == GT_ATT_DOT || gs[i].t[0].kind == GT_ATT_DOT_T);
-    const int64_t el = (int64_t)gs[i].rows * gs[i].cols;
-    n->grad_sb.start[i + 1] = n->grad_sb.start[i] + cdiv(el, wave_mode ? 4 : 256);
-  }
   HMP_HIP(hipMalloc(&n->d_pack_segs, ps.size() * sizeof(PackSeg)));
   HMP_HIP(hipMalloc(&n->d_grad_segs, gs.size() * sizeof(GradSeg)));
   HMP_HIP(hipMemcpy(n->d_pack_segs, ps.data(), ps.size() * sizeof(PackSeg), hipMemcpyHostToDevice));
   HMP_HIP(hipMemcpy(n->d_grad_segs, gs.data(), gs.size() * sizeof(GradSeg), hipMemcpyHostToDevice));
+  HMP_TRY(upload_grad_records(n, gs));
   for (int l = 0; l < n->L; ++l)
     if (n->lay[l].kind == HMP_CONV_GAT) HMP_HIP(hipMalloc(&n->lay[l].d_gat, sizeof(GatLayerS)));
   return HMP_OK;
@@ -1685,7 +1704,7 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
     AdamFuse af = n->call.adam;
     af.on = (af.on && fin_early && !n->any_gat) ? 1 : 0;
     n->call.adam_done = af.on != 0;
-    HMP_TRY(grad_reduce_launch(n->d_grad_segs, n->grad_sb, n->dyn, n->d_slabs, d_params, d_grads,
+    HMP_TRY(grad_reduce_launch(n->d_grad_segs, n->d_grad_recs, n->n_grad_recs, n->dyn, n->d_slabs, d_params, d_grads,
                                n->call.fin_loss ? n->d_row_lv : nullptr, n->call.fin_rows > 0 ? n->call.fin_rows : b->n_out, d_grads + na, n->d_state,
                                af, st));
     n->call.fin_loss = false;
@@ -1753,6 +1772,7 @@ extern "C" void hmp_net_destroy(hmp_net* n) {
   if (n->d_pack_segs) (void)hipFree(n->d_pack_segs);
   if (n->d_pack_map) (void)hipFree(n->d_pack_map);
   if (n->d_grad_segs) (void)hipFree(n->d_grad_segs);
+  if (n->d_grad_recs) (void)hipFree(n->d_grad_recs);
   for (int l = 0; l < HMP_MAX_LAYERS; ++l)
     if (l < n->L && n->lay[l].d_gat) (void)hipFree(n->lay[l].d_gat);
   delete n;
@@ -1943,16 +1963,18 @@ extern "C" int hmp_net_set_linear_heads(hmp_net* n, const hmp_linear_heads* h) {
     snprintf(err_buf(), 512, "hmp_net_set_linear_heads: copy of the gradient table failed");
     return HMP_E_HIP;
   }
+  if (const int rc = upload_grad_records(n, gs); rc != HMP_OK) {
+    (void)hipFree(d);
+    return rc;
+  }
   if (n->d_grad_segs) (void)hipFree(n->d_grad_segs);
   n->d_grad_segs = d;
   for (int i = n->n_grad; i < (int)gs.size(); ++i) {
     const int64_t el = (int64_t)gs[i].rows * gs[i].cols;
-    n->grad_sb.start[i + 1] = n->grad_sb.start[i] + (int)cdiv(el, 256);
     n->grad_elems += el;
     if (el > n->max_grad_elems) n->max_grad_elems = el;
   }
   n->n_grad = (int)gs.size();
-  n->grad_sb.n = n->n_grad;
   n->slab_floats = base + (int64_t)HEAD_MAX_BLOCKS * stride;
   n->head_slab_off = base; n->head_slab_stride = stride; n->head_ld_slab = ld;
   n->heads = *h;

@@ -191,12 +191,50 @@ int pack_launch(const PackSeg* d_segs, const SegBlocks& sb, const float* d_param
 }
 
 // ---------------------------------------------------------------------------------------------
-// grad reduce: split-K slabs of the packed weight gradients -> flat gradient buffer (fixed slab order).
-// grid = (element chunks of 1024, segments).  Block (0,0) additionally sums the per-row {loss, valid} pairs of the
+// grad reduce: split-K slabs of the packed weight gradients -> flat gradient buffer (fixed slab order), one workgroup per
+// record of the bind-time table (kernels.h GradRec).  Block 0 additionally sums the per-row {loss, valid} pairs of the
 // loss kernel in fixed order into out2 = {loss_sum, count} (the tail of the flat gradient buffer).
+//
+// All workgroups of the launch are co-resident, so the launch is as long as its longest chain of dependent requests, and the
+// chain is kept short: [kernel arguments] -> [record; the lines of `dyn` and Adam's two uniform words ride the same trip] ->
+// [p, m, v and every slab value of the element, GR_BATCH per term] -> stores.  Nothing is consumed before all of it is
+// requested; the sums are then taken in the order they always were: slab 0 first, one running sum per term, terms in index order.
 // ---------------------------------------------------------------------------------------------
+KT_DEFINE(optim)
+#ifdef HMP_KTIME
+// stamps of thread 0: workgroup 0 into slots 0.., the selected workgroup into slots 8.. (tools/ktime_grad.py); the first
+// workgroups of a 16-slab and of an 8-slab segment leave their index in slots 20 / 21 for the selection
+#define GKT(i)                                                              \
+  do {                                                                      \
+    if (threadIdx.x == 0) {                                                 \
+      if (blockIdx.x == 0) kt_buf[i] = wall_clock64();                      \
+      else if ((int)blockIdx.x == kt_sel) kt_buf[8 + (i)] = wall_clock64(); \
+    }                                                                       \
+  } while (0)
+#define GKT_NOTE(first, ns)                                                          \
+  do {                                                                               \
+    if (threadIdx.x == 0 && (first) && ((ns) == 16 || (ns) == 8) && blockIdx.x != 0) \
+      atomicMin(&kt_buf[(ns) == 16 ? 20 : 21], (unsigned long long)blockIdx.x);      \
+  } while (0)
+#else
+#define GKT(i) \
+  do {         \
+  } while (0)
+#define GKT_NOTE(first, ns) \
+  do {                      \
+  } while (0)
+#endif
+
+// dyn.n_slabs[id], read as the 32-bit word around it: there is no scalar byte load, and a byte indexed by a loaded id would
+// come through the vector path -- a round trip of its own that also waits for every load requested before it
+__device__ __forceinline__ int dyn_n_slabs(const GradReduceDyn& dyn, int id) {
+  static_assert(offsetof(GradReduceDyn, slab_stride) >= ((GRAD_MAX_SLAB_IDS + 4) & ~3), "the last byte's word lies inside the struct");
+  const unsigned w = reinterpret_cast<const unsigned*>(dyn.n_slabs)[id >> 2];
+  return (int)((w >> ((id & 3) * 8)) & 0xffu);
+}
+
 // sum over the split-K slabs of one element, slab 0 first; 8 (clamped) loads in flight per trip instead of one dependent
-// load per slab
+// load per slab (the segments that go through the GradSeg table)
 __device__ __forceinline__ float slab_sum(const float* __restrict__ src, int ns, int64_t stride) {
   float v = 0.f;
   for (int z0 = 0; z0 < ns; z0 += 8) {
@@ -210,21 +248,82 @@ __device__ __forceinline__ float slab_sum(const float* __restrict__ src, int ns,
   return v;
 }
 
-__global__ __launch_bounds__(256) void grad_reduce_kernel(const GradSeg* __restrict__ segs, const SegBlocks sb, const GradReduceDyn dyn,
-                                                          const float* __restrict__ slabs, const float* params,
-                                                          float* __restrict__ grads, const float* __restrict__ row_lv, int n_lv_rows,
-                                                          float* __restrict__ out2, NetState* state, const AdamFuse adam) {
-  int si = 0;
-  while (si + 1 < sb.n && (int)blockIdx.x >= sb.start[si + 1]) ++si;
-  const GradSeg& S = segs[si];
-  const int64_t n_el = (int64_t)S.rows * S.cols;
-  if (S.n_terms == 1 && (S.t[0].kind == GT_ATT_DOT || S.t[0].kind == GT_ATT_DOT_T)) {
+// element (r, c) of a segment with parameter-reading terms, term by term from the segment table
+__device__ __forceinline__ float seg_terms(const GradSeg& S, const GradReduceDyn& dyn, const float* __restrict__ slabs,
+                                           const float* params, int r, int c) {
+  float total = 0.f;
+  for (int ti = 0; ti < S.n_terms; ++ti) {
+    const GradTerm& T = S.t[ti];
+    const int ns = dyn_n_slabs(dyn, T.slab_id);
+    const int64_t stride = dyn.slab_stride[T.slab_id];
+    const float* base = slabs + T.src;
+    float v = 0.f;
+    if (T.kind == GT_COPY) {
+      v = slab_sum(base + (int64_t)((r / T.C) * T.Cp + (r % T.C)) * T.ld + c, ns, stride);
+    } else if (T.kind == GT_ATT_OUTER) {
+      v = params[T.att + r] * slab_sum(base + (int64_t)(r / T.C) * T.ld + c, ns, stride);
+    } else if (T.kind == GT_ATT_DOT) {
+      const float* src = base + (int64_t)(r / T.C) * T.ld;
+      const float* w = params + T.w + (int64_t)r * T.ldw;
+      for (int f = 0; f < T.inner; ++f) {
+        float s = 0.f;
+        for (int z = 0; z < ns; ++z) s += src[z * stride + f];
+        v += s * w[f];
+      }
+    } else if (T.kind == GT_ATT_OUTER_T) {
+      v = params[T.att + r] * slab_sum(base + (int64_t)c * T.ld + (r / T.C), ns, stride);
+    } else {  // GT_ATT_DOT_T
+      const float* w = params + T.w + (int64_t)r * T.ldw;
+      for (int d = 0; d < T.inner; ++d) {
+        float s = 0.f;
+        for (int z = 0; z < ns; ++z) s += base[z * stride + (int64_t)d * T.ld + (r / T.C)];
+        v += s * w[d];
+      }
+    }
+    total += v * T.scale;
+  }
+  return total;
+}
+
+constexpr int GR_BATCH = 16;  // slab values of one term in flight per lane: what the small-batch launcher writes at most
+
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const GradReduceArgs a) {
+  GKT(0);
+  const GradReduceDyn& dyn = a.dyn;
+  const AdamFuse& adam = a.adam;
+  const GradSeg* __restrict__ segs = a.segs;
+  const float* __restrict__ slabs = a.slabs;
+  const float* params = a.params;
+  float* __restrict__ grads = a.grads;
+  // the record: two lines behind one wave-uniform pointer, every field requested here
+  const GradRec* __restrict__ Rp = a.recs + blockIdx.x;
+  const int64_t dst = Rp->dst;
+  const int first = Rp->first, n_live = Rp->n_live, cols = Rp->cols, kind = Rp->kind, seg = Rp->seg, n_terms = Rp->n_terms;
+  GradRecTerm Q[3];
+#pragma unroll
+  for (int ti = 0; ti < 3; ++ti) Q[ti] = Rp->t[ti];
+  // Adam's two uniform words travel with the record: requested without a branch (adam.on is kernel-uniform; off: a word of the
+  // record stands in for the load and is not used) ...
+  const float* cnt_p = adam.on ? adam.count : (const float*)Rp;
+  const int* step_p = adam.on ? adam.step_dev : (const int*)Rp;
+  const float cnt_w = *cnt_p;
+  const int step_w = *step_p;
+  // ... and so do the other lines of the argument struct: the pointers, and dyn, which the record's slab ids index next
+  constexpr int WARM_OFF = 128, WARM_BYTES = (int)sizeof(GradReduceArgs) - WARM_OFF;
+  karg_warm<(WARM_BYTES + 63) / 64 + 1>(WARM_OFF, WARM_BYTES);
+  const float a_cnt = adam.on ? cnt_w : 1.f;
+  const int a_t = adam.on ? step_w : 1;
+  asm volatile("" ::"s"(kind), "s"(n_live));
+  GKT(1);
+  if (kind == GR_WAVE) {
     // attention-vector gradients are long dot products: one WAVEFRONT per element, lanes over the reduction index
+    const GradSeg& S = segs[seg];
     const GradTerm& T = S.t[0];
-    const int64_t r = (int64_t)((int)blockIdx.x - sb.start[si]) * 4 + (threadIdx.x >> 6);
+    const int w4 = threadIdx.x >> 6;
+    const int64_t r = (int64_t)first + w4;
     const int lane = threadIdx.x & 63;
-    if (r < n_el) {
-      const int ns = dyn.n_slabs[T.slab_id];
+    if (w4 < n_live) {
+      const int ns = dyn_n_slabs(dyn, T.slab_id);
       const int64_t stride = dyn.slab_stride[T.slab_id];
       const float* w = params + T.w + r * T.ldw;
       float part = 0.f;
@@ -239,74 +338,105 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const GradSeg* __restr
       for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
       if (lane == 0) grads[S.dst + r] = part * T.scale;
     }
-  } else {
-    const int64_t i = (int64_t)((int)blockIdx.x - sb.start[si]) * 256 + threadIdx.x;
-    if (i < n_el) {
-    const int r = (int)(i / S.cols), c = (int)(i % S.cols);
-    // Adam state of this element, requested before the slab sums so that it travels with them (adam.on is kernel-uniform)
-    float a_p = 0.f, a_m = 0.f, a_v = 0.f, a_cnt = 1.f;
-    int a_t = 1;
+  } else if ((int)threadIdx.x < n_live) {
+    const int i = first + (int)threadIdx.x;  // element of the segment
+    const int r = i / cols, c = i - r * cols;
+    const int64_t e = dst + threadIdx.x;     // element of the flat buffers
+    // Adam state of this element, requested before the slab values so that it travels with them
+    float a_p = 0.f, a_m = 0.f, a_v = 0.f;
     if (adam.on) {
-      a_p = adam.p[S.dst + i]; a_m = adam.m[S.dst + i]; a_v = adam.v[S.dst + i];
-      a_cnt = *adam.count;
-      a_t = *adam.step_dev;
+      a_p = adam.p[e]; a_m = adam.m[e]; a_v = adam.v[e];
     }
-    float total = 0.f;
-    for (int ti = 0; ti < S.n_terms; ++ti) {
-      const GradTerm& T = S.t[ti];
-      const int ns = dyn.n_slabs[T.slab_id];
-      const int64_t stride = dyn.slab_stride[T.slab_id];
-      const float* base = slabs + T.src;
-      float v = 0.f;
-      if (T.kind == GT_COPY) {
-        v = slab_sum(base + (int64_t)((r / T.C) * T.Cp + (r % T.C)) * T.ld + c, ns, stride);
-      } else if (T.kind == GT_ATT_OUTER) {
-        v = params[T.att + r] * slab_sum(base + (int64_t)(r / T.C) * T.ld + c, ns, stride);
-      } else if (T.kind == GT_ATT_DOT) {
-        const float* src = base + (int64_t)(r / T.C) * T.ld;
-        const float* w = params + T.w + (int64_t)r * T.ldw;
-        for (int f = 0; f < T.inner; ++f) {
-          float s = 0.f;
-          for (int z = 0; z < ns; ++z) s += src[z * stride + f];
-          v += s * w[f];
-        }
-      } else if (T.kind == GT_ATT_OUTER_T) {
-        v = params[T.att + r] * slab_sum(base + (int64_t)c * T.ld + (r / T.C), ns, stride);
-      } else {  // GT_ATT_DOT_T
-        const float* w = params + T.w + (int64_t)r * T.ldw;
-        for (int d = 0; d < T.inner; ++d) {
-          float s = 0.f;
-          for (int z = 0; z < ns; ++z) s += base[z * stride + (int64_t)d * T.ld + (r / T.C)];
-          v += s * w[d];
+    // GR_COPY: the first GR_BATCH slab values of every term, all requested before any is used (clamped addresses: a term of
+    // fewer slabs re-reads its last one, the sums below skip it)
+    float tv[3][GR_BATCH];
+    const float* src[3];
+    int ns[3];
+    int64_t stride[3];
+    if (kind == GR_COPY) {
+#pragma unroll
+      for (int ti = 0; ti < 3; ++ti) {
+        ns[ti] = 0;
+        if (ti < n_terms) {
+          ns[ti] = dyn_n_slabs(dyn, Q[ti].slab_id);
+          stride[ti] = dyn.slab_stride[Q[ti].slab_id];
+          const int row = Q[ti].C == Q[ti].Cp ? r : (r / Q[ti].C) * Q[ti].Cp + (r % Q[ti].C);
+          src[ti] = slabs + Q[ti].src + (int64_t)row * Q[ti].ld + c;
+          if (ti == 0) {
+            asm volatile("" ::"v"(src[0]), "s"(ns[0]), "s"(stride[0]));
+            GKT(2);
+            GKT_NOTE(first == 0, ns[0]);
+          }
+          if (ns[ti] > 0) {
+#pragma unroll
+            for (int u = 0; u < GR_BATCH; ++u) tv[ti][u] = src[ti][(int64_t)min(u, ns[ti] - 1) * stride[ti]];
+          }
         }
       }
-      total += v * T.scale;
     }
-    grads[S.dst + i] = total;
+    // Adam's bias corrections are uniform and need the step alone: evaluated while the loads are in flight
+    float bc1 = 1.f, bc2 = 1.f, gscale = 1.f;
+    if (adam.on) {
+      bc1 = 1.f - powf(adam.b1, (float)a_t);
+      bc2 = 1.f - powf(adam.b2, (float)a_t);
+      gscale = 1.f / (a_cnt > 0.f ? a_cnt : 1.f);  // a weight sum below 1 is a normaliser too; integer counts: the same bits
+      asm volatile("" ::"v"(bc1), "v"(bc2), "v"(gscale));
+    }
+    float total = 0.f;
+    if (kind == GR_COPY) {
+#pragma unroll
+      for (int ti = 0; ti < 3; ++ti) {
+        if (ti < n_terms) {
+          float v = 0.f;
+          if (ns[ti] > 0) {
+            asm volatile("" : "+v"(tv[ti][0]));  // the first wait for a loaded value stands here, behind the bias corrections
+#pragma unroll
+            for (int u = 0; u < GR_BATCH; ++u)
+              if (u < ns[ti]) v += tv[ti][u];
+          }
+          for (int z0 = GR_BATCH; z0 < ns[ti]; z0 += GR_BATCH) {  // deeper split-K (staged launchers, linear heads)
+            float t[GR_BATCH];
+#pragma unroll
+            for (int u = 0; u < GR_BATCH; ++u) t[u] = src[ti][(int64_t)min(z0 + u, ns[ti] - 1) * stride[ti]];
+#pragma unroll
+            for (int u = 0; u < GR_BATCH; ++u)
+              if (z0 + u < ns[ti]) v += t[u];
+          }
+          total += v * Q[ti].scale;
+        }
+      }
+    } else {
+      total = seg_terms(segs[seg], dyn, slabs, params, r, c);
+    }
+#ifdef HMP_KTIME
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"(total) : "memory");
+    GKT(3);
+#endif
+    grads[e] = total;
     if (adam.on) {
       // torch.optim.Adam with coupled L2 on this element (same arithmetic as adam_kernel); only taken when no gradient
       // term of the network reads parameters (SAGE), so updating in place cannot race with another thread's reads
-      const int t = a_t;
-      const float bc1 = 1.f - powf(adam.b1, (float)t);
-      const float bc2 = 1.f - powf(adam.b2, (float)t);
-      const float c = a_cnt;
-      const float gscale = 1.f / (c > 0.f ? c : 1.f);  // a weight sum below 1 is a normaliser too; integer counts: the same bits
-      const int64_t e = S.dst + i;
+      // Which products are fused into their sums is written out, not left to the compiler (it changes with the code around
+      // the expressions): these are the operations this update has always been compiled to, so its bits stay what they were
+#pragma clang fp contract(off)
       const float pi = a_p;
-      const float gi = total * gscale + adam.wd * pi;
+      const float gi = __builtin_fmaf(adam.wd, pi, total * gscale);
       const float mi = adam.b1 * a_m + (1.f - adam.b1) * gi;
       const float vi = adam.b2 * a_v + (1.f - adam.b2) * gi * gi;
       adam.m[e] = mi;
       adam.v[e] = vi;
       const float denom = sqrtf(vi) / sqrtf(bc2) + adam.eps;
-      adam.p[e] = pi - (adam.lr / bc1) * (mi / denom);
+      adam.p[e] = __builtin_fmaf(-(adam.lr / bc1), mi / denom, pi);
     }
-    }
+    GKT(4);
   }
+  const float* __restrict__ row_lv = a.row_lv;
   if (row_lv != nullptr && blockIdx.x == 0) {
     __shared__ float sl[256], sv[256];
+    float* __restrict__ out2 = a.out2;
+    NetState* state = a.state;
     float l = 0.f, v = 0.f;
-    for (int r = threadIdx.x; r < n_lv_rows; r += 256) { l += row_lv[2 * r]; v += row_lv[2 * r + 1]; }
+    for (int r = threadIdx.x; r < a.n_lv_rows; r += 256) { l += row_lv[2 * r]; v += row_lv[2 * r + 1]; }
     sl[threadIdx.x] = l;
     sv[threadIdx.x] = v;
     __syncthreads();
@@ -322,12 +452,17 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const GradSeg* __restr
   }
 }
 
-int grad_reduce_launch(const GradSeg* d_segs, const SegBlocks& sb, const GradReduceDyn& dyn, const float* d_slabs,
+int grad_reduce_launch(const GradSeg* d_segs, const GradRec* d_recs, int n_recs, const GradReduceDyn& dyn, const float* d_slabs,
                        const float* d_params, float* d_grads, const float* row_lv, int n_lv_rows, float* out2, NetState* state,
                        const AdamFuse& adam, hipStream_t st) {
-  if (sb.n == 0 || sb.start[sb.n] == 0) return HMP_OK;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3(sb.start[sb.n]), dim3(256), 0, st, d_segs, sb, dyn, d_slabs, d_params, d_grads, row_lv,
-                     n_lv_rows, out2, state, adam);
+  if (n_recs == 0) return HMP_OK;
+  GradReduceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.dyn = dyn;
+  a.recs = d_recs; a.segs = d_segs; a.slabs = d_slabs; a.params = d_params; a.grads = d_grads;
+  a.row_lv = row_lv; a.out2 = out2; a.state = state; a.n_lv_rows = n_lv_rows;
+  a.adam = adam;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3(n_recs), dim3(256), 0, st, a);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }

@@ -54,6 +54,8 @@ def main():
     show("front gemm tile (blk0)", read(lib, "front"), [0, 2, 3, 5, 6, 7, 13, 14, 15, 4, 1])
     show("front plan part 0 (job 0)", read(lib, "front"), [0, 8, 9, 10, 11, 12])
     show("gemm_tn_direct dW (blk0)", read(lib, "gemmd"), [8, 9])
+    # entry, record in registers, first slab address known, all loads back, stores issued (tools/ktime_grad.py: other workgroups)
+    show("grad_reduce un-pack+Adam (blk0)", read(lib, "optim"), [0, 1, 2, 3, 4])
     # the layer-0 projection alone: x[2831, 306] * Wp[192, 306]^T
     x = torch.randn(2831, 306, device=dev)
     w = torch.randn(192, 308, device=dev)[:, :306]
