@@ -71,8 +71,10 @@ __device__ __forceinline__ float t_mask(float h, int act, bool keep, float scale
 // time with every row's chain (extent -> destination id -> reciprocal degree + dM row) and its H row requested together: a source row
 // has one or two such edges (the conv qualified by E <= 2 N_src), so a wave that owns a single row is a chain of four dependent round
 // trips with one 512-byte row in flight (measured 2.5 TB/s at config 5; TR rows per wave keep TR of them in flight).
+// GV: the rows of G are whole aligned 4-vectors; else (the caller's input-gradient rows: 306 floats at pitch 306) exactly F fp32
+// elements per row are stored one by one, the store-side twin of ld4_edge.
 constexpr int TR = 4;
-template <bool HB, bool GB>
+template <bool HB, bool GB, bool GV>
 __global__ __launch_bounds__(256) void seg_mean_rows_t_kernel(const float* __restrict__ dm, int lddm, int F, const int* __restrict__ t_rowptr,
                                                               const int* __restrict__ t_col, const float* __restrict__ degf, int n_rows,
                                                               const void* __restrict__ h, int ldh, int act, int drop_on, float dscale,
@@ -135,8 +137,14 @@ __global__ __launch_bounds__(256) void seg_mean_rows_t_kernel(const float* __res
         bf16x4 o;
         o[0] = (__bf16)a4.x; o[1] = (__bf16)a4.y; o[2] = (__bf16)a4.z; o[3] = (__bf16)a4.w;
         *reinterpret_cast<bf16x4*>(reinterpret_cast<uint16_t*>(g) + (int64_t)(row0 + u) * ldg + c0) = o;
-      } else {
+      } else if constexpr (GV) {
         *reinterpret_cast<float4*>(reinterpret_cast<float*>(g) + (int64_t)(row0 + u) * ldg + c0) = a4;
+      } else {
+        float* go = reinterpret_cast<float*>(g) + (int64_t)(row0 + u) * ldg + c0;
+        const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (c0 + q < F) go[q] = av[q];
       }
     }
   }
@@ -165,17 +173,61 @@ int seg_mean_rows_launch(const void* x, int ldx, int x_bf16, int F, const int* r
 int seg_mean_rows_t_launch(const float* dm, int lddm, int F, const int* t_rowptr, const int* t_col, const float* degf, int n_rows,
                            const void* h, int ldh, int h_bf16, int act, int drop_on, float dscale, void* g, int ldg, int g_bf16, hipStream_t st) {
   if (n_rows <= 0) return HMP_OK;
-  HMP_CHECK_ARG((F & 3) == 0 && (lddm & 3) == 0 && (ldg & 3) == 0 && (!h || (ldh & 3) == 0), "seg_mean_rows_t: rows must be whole 4-element vectors");
+  // fp32 rows of G at a pitch that is not whole 4-vectors take exactly F elements each, stored one by one; every other operand
+  // (and G at an aligned pitch, where the caller pads F itself) is read and written as whole 4-vectors
+  const bool g_elems = !g_bf16 && (ldg & 3) != 0;
+  HMP_CHECK_ARG(F > 0 && (lddm & 3) == 0 && lddm >= align4(F) && (!h || ((ldh & 3) == 0 && ldh >= align4(F))) &&
+                    (g_elems ? ldg >= F : ((F & 3) == 0 && (ldg & 3) == 0 && ldg >= F)),
+                "seg_mean_rows_t: rows must be whole 4-element vectors (F = %d, pitches dM %d, H %d, G %d)", F, lddm, h ? ldh : 0, ldg);
   const dim3 grid(cdiv(n_rows, 4 * TR)), block(256);
-#define HMP_T_LAUNCH(HB_, GB_) \
-  hipLaunchKernelGGL((seg_mean_rows_t_kernel<HB_, GB_>), grid, block, 0, st, dm, lddm, F, t_rowptr, t_col, degf, n_rows, h, ldh, act, drop_on, dscale, g, ldg)
-  if (h_bf16 && g_bf16) HMP_T_LAUNCH(true, true);
-  else if (h_bf16) HMP_T_LAUNCH(true, false);
-  else if (g_bf16) HMP_T_LAUNCH(false, true);
-  else HMP_T_LAUNCH(false, false);
+#define HMP_T_LAUNCH(HB_, GB_, GV_) \
+  hipLaunchKernelGGL((seg_mean_rows_t_kernel<HB_, GB_, GV_>), grid, block, 0, st, dm, lddm, F, t_rowptr, t_col, degf, n_rows, h, ldh, act, drop_on, dscale, g, ldg)
+  if (g_elems && h_bf16) HMP_T_LAUNCH(true, false, false);
+  else if (g_elems) HMP_T_LAUNCH(false, false, false);
+  else if (h_bf16 && g_bf16) HMP_T_LAUNCH(true, true, true);
+  else if (h_bf16) HMP_T_LAUNCH(true, false, true);
+  else if (g_bf16) HMP_T_LAUNCH(false, true, true);
+  else HMP_T_LAUNCH(false, false, true);
 #undef HMP_T_LAUNCH
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }
 
+// source types of aggregate-first convs: + transpose of the segment mean, before the mask.  Fused into the epilogue of the
+// weight-stationary kernel where that one runs the problem; else as an fp32 matrix the tiled kernels start their sums from
+int gemm_dx_gather_term(GemmProblem& p, bool bf16_mode, const int* t_rowptr, const int* t_col, const float* degf, const float* g_rows,
+                        int g_ld, float* scratch, int64_t scratch_floats, int64_t* scratch_used, hipStream_t st) {
+  p.g_rowptr = t_rowptr; p.g_col = t_col; p.g_deg = degf; p.g_rows = g_rows; p.g_ld = g_ld;
+  if (bf16_mode && gemm_bf16_dx_takes(p, false)) return HMP_OK;
+  p.g_rowptr = nullptr;
+  HMP_CHECK_ARG(scratch && *scratch_used + (int64_t)p.M * g_ld <= scratch_floats, "net: gather-add scratch too small");
+  float* sm = scratch + *scratch_used;
+  *scratch_used += (int64_t)p.M * g_ld;
+  HMP_TRY(seg_mean_rows_t_launch(g_rows, g_ld, g_ld, t_rowptr, t_col, degf, p.M, nullptr, 0, 0, 0, 0, 1.f, sm, g_ld, 0, st));
+  p.Cadd = sm; p.ldadd = g_ld;
+  return HMP_OK;
+}
+
 }  // namespace hmp
+
+// ---- unit-test entries (include/hydra_mp.h section 3): the two launchers as the executor calls them, on raw device CSR arrays
+extern "C" int hmp_seg_mean_rows(const void* d_x, int32_t ldx, int32_t x_bf16, int32_t F, const int32_t* d_rowptr, const int32_t* d_col,
+                                 int32_t n_rows, float* d_m, int32_t ldm, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_seg_mean_rows: no gfx950 device visible");
+  HMP_CHECK_ARG(d_x && d_rowptr && d_m && F > 0 && n_rows >= 0 && ldx >= F, "hmp_seg_mean_rows: bad argument");
+  return seg_mean_rows_launch(d_x, ldx, x_bf16 ? 1 : 0, F, d_rowptr, d_col, n_rows, d_m, ldm, (hipStream_t)stream);
+}
+
+extern "C" int hmp_seg_mean_rows_t(const float* d_dm, int32_t lddm, int32_t F, const int32_t* d_t_rowptr, const int32_t* d_t_col,
+                                   const float* d_degf, int32_t n_rows, const void* d_h, int32_t ldh, int32_t h_bf16, int32_t act,
+                                   int32_t drop_on, float dscale, void* d_g, int32_t ldg, int32_t g_bf16, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_seg_mean_rows_t: no gfx950 device visible");
+  HMP_CHECK_ARG(d_dm && d_t_rowptr && d_degf && d_g && F > 0 && n_rows >= 0, "hmp_seg_mean_rows_t: bad argument");
+  HMP_CHECK_ARG(act == HMP_ACT_NONE || act == HMP_ACT_RELU || act == HMP_ACT_ELU, "hmp_seg_mean_rows_t: act %d", (int)act);
+  return seg_mean_rows_t_launch(d_dm, lddm, F, d_t_rowptr, d_t_col, d_degf, n_rows, d_h, ldh, h_bf16 ? 1 : 0, act, drop_on ? 1 : 0, dscale,
+                                d_g, ldg, g_bf16 ? 1 : 0, (hipStream_t)stream);
+}

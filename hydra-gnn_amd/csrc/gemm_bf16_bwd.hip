@@ -188,8 +188,14 @@ __global__ __launch_bounds__(DX_THREADS, (NBUF > 4 ? 1 : 2)) void gemm_bf16_dx_k
       }
     }
     // ---- epilogue.  D^T: lane = output row m0 + i*32 + l31; registers 4 g .. 4 g + 3 = columns n0 + 32 w + 8 g + 4 half ..
-    // H was requested in front of this tile's first unit: younger than it are the KU - 1 unit requests issued since
-    if (a.H) HMP_VMCNT(4 * (KU - 1));
+    // H was requested in front of this tile's first unit: younger than it are the KU - 1 unit requests issued since -- while the
+    // pipeline still had units to request (block-uniform: the last of them is unit v - 1 + D).  Towards the end of the group's
+    // tiles fewer follow and H may be the youngest request: wait for everything.  (K = 512 reached a vmcnt(0) in the loop above
+    // in exactly those tiles; K = 256 and K = 768 did not, and masked a tile with whatever the H area held.)
+    if (a.H) {
+      if (v - 1 + D < total) HMP_VMCNT(4 * (KU - 1));
+      else HMP_VMCNT(0);
+    }
     const int m0 = t * DX_ROWS;
     // The wave's 4 KB of the H tile doubles as the staging area of its output: it is the one region no other wave touches (the
     // unit buffers are read as MFMA operands by every wave until the next barrier).  All H values are read into registers first;
@@ -561,9 +567,16 @@ int gemm_bf16_dw_launch(const GemmProblem& p, int max_slabs, int* n_slabs, hipSt
 
 // ---- unit-test entries (include/hydra_mp.h section 3): the same GemmProblem the executor builds, through gemm_bf16_launch, so
 // that HMP_GEMM_DX=0 / HMP_GEMM_DW=0 send the identical call to the tiled kernel
-extern "C" int hmp_gemm_bf16_dx(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const float* d_w,
-                                int32_t ldw, const uint16_t* d_h, int32_t ldh, int32_t act, int32_t drop_on, float drop_scale,
-                                uint16_t* d_g, int32_t ldg, int32_t M, int32_t N, int32_t K, void* stream) {
+namespace {
+struct DxGather {  // the gather-add term of hmp_gemm_bf16_dx_gather (t_rowptr == null: none)
+  const int32_t *t_rowptr, *t_col;
+  const float *degf, *rows;
+  int32_t ld;
+  float* scratch;
+};
+int dx_entry(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const float* d_w, int32_t ldw,
+             const uint16_t* d_h, int32_t ldh, int32_t act, int32_t drop_on, float drop_scale, uint16_t* d_g, int32_t ldg, int32_t M,
+             int32_t N, int32_t K, const DxGather& ga, void* stream) {
   using namespace hmp;
   HMP_CHECK_ARG(d_dz && d_w && d_g && M >= 0 && N > 0 && K > 0, "hmp_gemm_bf16_dx: bad argument");
   HMP_CHECK_ARG(split == 0 || (d_dz2 && split > 0 && split < K && (split & 255) == 0), "hmp_gemm_bf16_dx: split %d of K = %d", split, K);
@@ -583,7 +596,34 @@ extern "C" int hmp_gemm_bf16_dx(const uint16_t* d_dz, int32_t lddz, const uint16
     p.H = reinterpret_cast<const float*>(d_h); p.ldh = ldh; p.h_bf16 = 1; p.act = act; p.drop_on = drop_on; p.drop.scale = drop_scale;
   }
   if (M == 0) return HMP_OK;
+  if (ga.t_rowptr) {  // the executor's own decision: fused into the weight-stationary kernel's epilogue, or scratch + Cadd
+    int64_t used = 0;
+    HMP_TRY(gemm_dx_gather_term(p, true, ga.t_rowptr, ga.t_col, ga.degf, ga.rows, ga.ld, ga.scratch, (int64_t)M * ga.ld, &used,
+                                (hipStream_t)stream));
+  }
   return gemm_bf16_launch(gb, false, 1, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int hmp_gemm_bf16_dx(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const float* d_w,
+                                int32_t ldw, const uint16_t* d_h, int32_t ldh, int32_t act, int32_t drop_on, float drop_scale,
+                                uint16_t* d_g, int32_t ldg, int32_t M, int32_t N, int32_t K, void* stream) {
+  DxGather none;
+  memset(&none, 0, sizeof(none));
+  return dx_entry(d_dz, lddz, d_dz2, lddz2, split, d_w, ldw, d_h, ldh, act, drop_on, drop_scale, d_g, ldg, M, N, K, none, stream);
+}
+
+extern "C" int hmp_gemm_bf16_dx_gather(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split,
+                                       const float* d_w, int32_t ldw, const uint16_t* d_h, int32_t ldh, int32_t act, int32_t drop_on,
+                                       float drop_scale, uint16_t* d_g, int32_t ldg, int32_t M, int32_t N, int32_t K,
+                                       const int32_t* d_t_rowptr, const int32_t* d_t_col, const float* d_degf, const float* d_g_rows,
+                                       int32_t g_ld, float* d_scratch, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_gemm_bf16_dx_gather: no gfx950 device visible");
+  HMP_CHECK_ARG(d_t_rowptr && d_degf && d_g_rows && d_scratch && g_ld >= N, "hmp_gemm_bf16_dx_gather: bad gather argument");
+  const DxGather ga = {d_t_rowptr, d_t_col, d_degf, d_g_rows, g_ld, d_scratch};
+  return dx_entry(d_dz, lddz, d_dz2, lddz2, split, d_w, ldw, d_h, ldh, act, drop_on, drop_scale, d_g, ldg, M, N, K, ga, stream);
 }
 
 extern "C" int hmp_gemm_bf16_dw(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const void* d_h,

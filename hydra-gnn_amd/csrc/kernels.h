@@ -387,6 +387,11 @@ int seg_mean_rows_launch(const void* x, int ldx, int x_bf16, int F, const int* r
                          hipStream_t st);
 int seg_mean_rows_t_launch(const float* dm, int lddm, int F, const int* t_rowptr, const int* t_col, const float* degf, int n_rows,
                            const void* h, int ldh, int h_bf16, int act, int drop_on, float dscale, void* g, int ldg, int g_bf16, hipStream_t st);
+// The source rows' gradient term of an aggregate-first conv on the input-gradient problem p of its source type (rows of p = source
+// rows): p.g_* when the weight-stationary dx kernel takes p that way (bf16 compute mode only), else the term materialised as fp32
+// [p.M][g_ld] at scratch + *scratch_used (advanced by what it takes; scratch_floats: the scratch's size) and handed over as p.Cadd
+int gemm_dx_gather_term(GemmProblem& p, bool bf16_mode, const int* t_rowptr, const int* t_col, const float* degf, const float* g_rows,
+                        int g_ld, float* scratch, int64_t scratch_floats, int64_t* scratch_used, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // parameter packing / gradient un-packing (tables live in device memory, built at bind time)

@@ -1564,15 +1564,8 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
         SrcTerm T;
         if (!src_term(ps_type[i], T)) continue;
         const ConvLayout& Q = Y.conv[T.c];
-        GemmProblem& p = ps[i];
-        p.g_rowptr = T.P->d_t_rowptr; p.g_col = T.P->d_t_col; p.g_deg = T.degf; p.g_rows = Q.dmrows; p.g_ld = Q.ld_m;
-        if (n->compute_bf16 != 0 && gemm_bf16_dx_takes(p, false)) continue;
-        p.g_rowptr = nullptr;
-        HMP_CHECK_ARG(sadd_used + (int64_t)p.M * Q.ld_m <= n->sadd_floats, "net: gather-add scratch too small");
-        float* sm = n->d_sadd + sadd_used;
-        sadd_used += (int64_t)p.M * Q.ld_m;
-        HMP_TRY(seg_mean_rows_t_launch(Q.dmrows, Q.ld_m, Q.ld_m, T.P->d_t_rowptr, T.P->d_t_col, T.degf, p.M, nullptr, 0, 0, 0, 0, 1.f, sm, Q.ld_m, 0, st));
-        p.Cadd = sm; p.ldadd = Q.ld_m;
+        HMP_TRY(gemm_dx_gather_term(ps[i], n->compute_bf16 != 0, T.P->d_t_rowptr, T.P->d_t_col, T.degf, Q.dmrows, Q.ld_m, n->d_sadd,
+                                    n->sadd_floats, &sadd_used, st));
       }
       if (!ps.empty()) HMP_TRY(gemm_many(n, ps, false, st, nullptr));
       // source types with NO stacked columns in this layer (their only live conv is the aggregate-first one): no GEMM -- the
@@ -1592,9 +1585,12 @@ int backward_impl(hmp_net* n, const float* d_gout, int ld_gout, float* d_grads, 
           g16[l] = n->compute_bf16 != 0 && rows_kernel_bf16(n, b, l - 1) && (n->ld[l][s] & 3) == 0 &&
                    (b->n_nodes[s] >= 32768 || n->env.bf16_all);
         gb = l > 0 && g16[l];
-        HMP_TRY(seg_mean_rows_t_launch(Q.dmrows, Q.ld_m, fpad(n->dim[l][s]), T.P->d_t_rowptr, T.P->d_t_col, T.degf, b->n_nodes[s],
+        // the caller's input-gradient rows need not be whole 4-vectors (306 floats at pitch 306): exactly dim columns, element-wise
+        const int ldg = l > 0 ? n->ld[l][s] : b->ldx[s];
+        const int Fg = (ldg & 3) != 0 ? n->dim[l][s] : fpad(n->dim[l][s]);
+        HMP_TRY(seg_mean_rows_t_launch(Q.dmrows, Q.ld_m, Fg, T.P->d_t_rowptr, T.P->d_t_col, T.degf, b->n_nodes[s],
                                        masked ? (const void*)n->H[l][s] : nullptr, n->ld[l][s], n->h16[l][s] ? 1 : 0, act, drop_on ? 1 : 0,
-                                       drop_on ? 1.f / (1.f - Lp->dropout) : 1.f, dst, l > 0 ? n->ld[l][s] : b->ldx[s], gb ? 1 : 0, st));
+                                       drop_on ? 1.f / (1.f - Lp->dropout) : 1.f, dst, ldg, gb ? 1 : 0, st));
       }
     }
     if (!skip_w) {  // weight + bias gradient: dWp = dZ^T * [H | 1], split over node chunks (+ GAT: bias column sums, d V_edge), launched after the loop

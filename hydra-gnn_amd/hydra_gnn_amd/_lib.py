@@ -283,6 +283,10 @@ SIGNATURES = {
     "hmp_htree_destroy": (None, [_VP]),
     "hmp_gemm_bf16_dx": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _I32, _I32, _VP]),
     "hmp_gemm_bf16_dw": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _I32, _VP, _I32, _I64, _I32, C.POINTER(_I32), _I32, _I32, _I32, _VP]),
+    "hmp_seg_mean_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _I32, _VP]),
+    "hmp_seg_mean_rows_t": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _I32, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _VP]),
+    "hmp_gemm_bf16_dx_gather": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _I32, _I32,
+                                          _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "hmp_gemm_grouped": (C.c_int, [C.POINTER(GemmDesc), _I32, _I32, _I32, _I32, C.POINTER(_I32), _VP]),
     "hmp_comm_unique_id": (C.c_int, [_VP]),
     "hmp_comm_create": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP)]),

@@ -70,7 +70,9 @@ extern "C" {
  *    loss), hmp_label_counts / hmp_balanced_class_weights (the label histogram and balanced weights on the device),
  *    hmp_head_tails_weighted / hmp_linear_heads_run_weighted (their test entries): new entries, no struct was added or changed
  *    layout.  The normaliser of the loss and of Adam's gradient scale is now used as it is when > 0 (it was clamped at 1): the
- *    same bits for the integer-valued counts of unweighted steps */
+ *    same bits for the integer-valued counts of unweighted steps;
+ *    hmp_seg_mean_rows / hmp_seg_mean_rows_t / hmp_gemm_bf16_dx_gather (test entries of the aggregate-first convs' launchers and of
+ *    the gather-add term of the input-gradient GEMM): new entries, no struct was added or changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -193,6 +195,36 @@ int hmp_gemm_bf16_dx(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, 
 int hmp_gemm_bf16_dw(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const void* d_h,
                      int32_t ldh, int32_t h_bf16, float* d_slabs, int32_t ldc, int64_t slab_stride, int32_t max_slabs,
                      int32_t* n_slabs, int32_t Mw, int32_t F, int32_t nodes, void* stream);
+/* Unit-test entries of the aggregate-first SAGE convs (csrc/aggfirst.hip; ABI-4-compatible additions): the launchers as the
+ * executor calls them, on raw device int32 CSR arrays instead of an hmp_plan.  Reference: [PyG] SAGEConv evaluated in its own order,
+ * out = lin_l(mean_j x_j), and autograd of that mean.
+ *   hmp_seg_mean_rows    M[i, 0:F] = (1 / max(deg_i, 1)) * sum_{k in [rowptr[i], rowptr[i+1])} X[col[k], 0:F], fp32 [n_rows][ldm]
+ *                        written as whole 4-vectors (columns up to align4(F); ldm % 4 == 0, 16-byte aligned base: refused otherwise).
+ *                        X is fp32 or bf16 (x_bf16) [.][ldx]; rows that are not whole aligned 4-vectors (ldx % 4 != 0, ldx <
+ *                        align4(F), or an unaligned base) are read element by element.
+ *   hmp_seg_mean_rows_t  G[j, 0:F] = mask(H[j, :]) . sum_{k in [t_rowptr[j], t_rowptr[j+1])} dM[t_col[k], 0:F] * degf[t_col[k]]: the
+ *                        transpose of that mean (degf[i] = 1 / max(deg_i, 1)) times the activation / dropout factor of the source
+ *                        rows.  dM fp32 [.][lddm]; H fp32 or bf16 (h_bf16) [n_rows][ldh], NULL: no mask; with drop_on an element of H
+ *                        stored as -0.0 is a dropped one (factor 0); a kept one has the factor dscale (HMP_ACT_NONE), h > 0 ? dscale : 0
+ *                        (RELU) or h > 0 ? dscale : h + dscale (ELU: the stored h is dscale * elu(z)).  G fp32 or bf16 (g_bf16)
+ *                        [n_rows][ldg].  Everything moves as whole 4-vectors: F, lddm, ldh, ldg multiples of 4 (refused otherwise) --
+ *                        except fp32 G at a pitch that is no multiple of 4 (the caller's input-gradient rows: 306 floats at pitch
+ *                        306), which takes any F <= ldg and stores exactly F elements per row one by one.
+ *   hmp_gemm_bf16_dx_gather   hmp_gemm_bf16_dx with that transposed sum over d_g_rows (fp32 [.][g_ld], g_ld >= N) added to the product
+ *                        BEFORE the mask: G = mask . (dZ W + sum_k g_rows[t_col[k], 0:N] * degf[t_col[k]]).  It runs the executor's own
+ *                        decision: the term rides in the epilogue of the weight-stationary kernel where that kernel takes the
+ *                        problem (g_ld % 4 == 0, 16-byte aligned g_rows), else it is materialised into d_scratch (fp32, at least
+ *                        M * g_ld floats) by hmp_seg_mean_rows_t's launcher and added by the tiled kernel (HMP_GEMM_DX=0 forces this). */
+int hmp_seg_mean_rows(const void* d_x, int32_t ldx, int32_t x_bf16, int32_t F, const int32_t* d_rowptr, const int32_t* d_col,
+                      int32_t n_rows, float* d_m, int32_t ldm, void* stream);
+int hmp_seg_mean_rows_t(const float* d_dm, int32_t lddm, int32_t F, const int32_t* d_t_rowptr, const int32_t* d_t_col,
+                        const float* d_degf, int32_t n_rows, const void* d_h, int32_t ldh, int32_t h_bf16, int32_t act, int32_t drop_on,
+                        float dscale, void* d_g, int32_t ldg, int32_t g_bf16, void* stream);
+int hmp_gemm_bf16_dx_gather(const uint16_t* d_dz, int32_t lddz, const uint16_t* d_dz2, int32_t lddz2, int32_t split, const float* d_w,
+                            int32_t ldw, const uint16_t* d_h, int32_t ldh, int32_t act, int32_t drop_on, float drop_scale,
+                            uint16_t* d_g, int32_t ldg, int32_t M, int32_t N, int32_t K, const int32_t* d_t_rowptr,
+                            const int32_t* d_t_col, const float* d_degf, const float* d_g_rows, int32_t g_ld, float* d_scratch,
+                            void* stream);
 /* Unit-test entry of the grouped launchers as the executor calls them: n <= 8 problems in one launch, each copied as it stands
  * into the launcher's problem table (csrc/gemm.hip); the launcher alone chooses the kernels.  One problem: C[M, N] = op(A) *
  * op([B | 1]) (+ Cadd) (. act'(H) / (1 - drop_p) under epi = 1), fp32 unless a *_bf16 flag says otherwise (route 1 only, ld* then

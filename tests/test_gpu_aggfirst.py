@@ -133,6 +133,34 @@ def test_aggregate_first_fused_training_step_tracks_the_oracle(monkeypatch):
     assert {k for k, on in net.native()._agg_first.items() if on} == {(0, 2), (1, 2), (2, 2), (0, 3), (1, 3)}
 
 
+@pytest.mark.parametrize("layers,seed", [(1, 3), (3, 13)])  # (seeds whose oracle keeps every ReLU input 1e-4 away from 0)
+def test_input_gradients_through_aggregate_first_convs(monkeypatch, layers, seed):
+    """input_gradients (eval mode) against float64 autograd of the oracle with respect to x, MP3D contract (objects 306-d at pitch
+    306, rooms 6-d).  One layer: the objects' only live conv is objects -> rooms, so they have no input-gradient GEMM and their
+    gradient is the stand-alone transpose of the segment mean, written straight into rows of 306 floats at pitch 306 -- rows that
+    are not whole 4-vectors.  Three layers: the same term enters layer 0's input-gradient GEMM as its addend."""
+    from _saliency_reference import oracle_input_gradients
+
+    monkeypatch.setenv("HMP_AGG_FIRST", "1")
+    kw = dict(input_dim_dict={"objects": 306, "rooms": 6}, output_dim=26, conv_block="GraphSAGE", hidden_dim=32, num_layers=layers, dropout=0.0)
+    ora, net = pair(kw, seed=seed)
+    net.eval()
+    ref, margin, _ = oracle_input_gradients(ora, workloads.mp3d_like_batch(9, seed=41))
+    # the two sides take the same ReLU branch everywhere (tests/test_gpu_saliency_models.py: RELU_MARGIN)
+    assert margin >= 1e-4, f"smallest |ReLU input| of the oracle is {margin:.3e}: pick another seed"
+    batch = workloads.mp3d_like_batch(9, seed=41).to(DEV)
+    assert batch["objects"].x.shape[1] == 306 and batch["objects"].x.stride(0) == 306
+    got = net.input_gradients(batch)
+    nat = net.native()
+    on = {(l, tuple(nat.layers[l].convs[c].edge_type)) for (l, c), v in nat._agg_first.items() if v}
+    assert (0, OR) in on, on  # the layer-0 objects -> rooms conv did run aggregate-first
+    assert nat.read_state()[1] == 0
+    assert "objects" in got and set(got) <= set(ref)
+    for t, g in got.items():
+        assert tuple(g.shape) == tuple(ref[t].shape) and float(ref[t].abs().max()) > 0
+        torch.testing.assert_close(g.cpu().double(), ref[t], atol=ATOL, rtol=RTOL, msg=lambda m: f"{t}: {m}")
+
+
 def test_aggregate_first_on_the_htree_network(monkeypatch):
     """10 edge types, 4 node types, LeafPool: the forced choice takes one conv per source type and layer; parity at 1e-5"""
     monkeypatch.setenv("HMP_AGG_FIRST", "1")

@@ -398,7 +398,8 @@ def _act_factor(h, act, drop_on, scale):
 
 
 @pytest.mark.parametrize("M,K,split,mask", [(40037, 768, 512, "relu_drop"), (33000, 512, 256, "relu_drop"), (36000, 256, 0, "none"),
-                                            (40000, 768, 0, "relu"), (34567, 512, 0, "elu_drop")])
+                                            (40000, 768, 0, "relu"), (34567, 512, 0, "elu_drop"),
+                                            (33000, 256, 0, "relu_drop")])  # K = 256 with a mask: two tiles per group, H awaited at the tail
 def test_bf16_input_gradient_weight_stationary_kernel(monkeypatch, M, K, split, mask):
     """hmp_gemm_bf16_dx: G = act'(H) . (dZ * Wp) with dZ in one or two bf16 pieces, against float64 on the rounded operands and
     against the tiled kernel (HMP_GEMM_DX=0) on the same call: every K class, ragged M, padded leading dimensions, the
