@@ -28,6 +28,8 @@ __device__ void front_kt_slot(int i);
 #endif
 #include "plan_small.h"
 
+#include <vector>
+
 namespace hmp {
 
 KT_DEFINE(front)
@@ -287,4 +289,132 @@ int front_launch(FrontArgs& a, hipStream_t st) {
   return HMP_OK;
 }
 
+// ---- unit-test entries: hmp_front_run / hmp_pack_run ------------------------------------------------------------------------
+namespace {
+
+static_assert(HMP_FRONT_MAX_PROB == FR_MAX_PROB && HMP_FRONT_MAX_SEG == FR_MAX_SEG && HMP_FRONT_MAX_SRC == FR_MAX_SRC, "public limits");
+static_assert(HMP_PACK_SUM == PACK_SUM && HMP_PACK_HEADS == PACK_HEADS && HMP_PACK_ATTDOT == PACK_ATTDOT && HMP_PACK_ATTDOT_T == PACK_ATTDOT_T,
+              "public pack kinds");
+
+// what build_tables guarantees of a segment and pack_lane relies on, and that every access stays inside the two buffers
+int unit_pack_seg(const hmp_pack_seg& q, int i, int64_t n_params, int64_t n_packed, PackSeg& S) {
+  HMP_CHECK_ARG(q.kind >= PACK_SUM && q.kind <= PACK_ATTDOT_T, "pack: segment %d of kind %d", i, q.kind);
+  HMP_CHECK_ARG(q.rows >= 0 && q.rows_pad >= 1 && q.rows <= q.rows_pad && q.cols >= 0 && q.ld_dst >= 1 && q.cols <= q.ld_dst && q.ld_src >= 0 &&
+                    q.rows_pad <= (1 << 20) && q.ld_dst <= (1 << 20) && q.ld_src <= (1 << 20),
+                "pack: segment %d: rows %d / %d, cols %d, ld_dst %d, ld_src %d", i, q.rows, q.rows_pad, q.cols, q.ld_dst, q.ld_src);
+  HMP_CHECK_ARG(q.dst >= 0 && q.dst + (int64_t)q.rows_pad * q.ld_dst <= n_packed, "pack: segment %d writes outside the packed buffer", i);
+  auto reads = [&](int64_t off, int64_t rows, int64_t ld, int64_t cols) {  // a [rows][cols] block at pitch ld
+    return off >= 0 && (rows <= 0 || cols <= 0 || off + (rows - 1) * ld + cols <= n_params);
+  };
+  if (q.kind == PACK_SUM) {
+    HMP_CHECK_ARG(q.nsrc >= 0 && q.nsrc <= AGG_MAX_IN && q.ld_src >= q.cols, "pack: segment %d: %d sources, ld_src %d", i, q.nsrc, q.ld_src);
+    for (int s = 0; s < q.nsrc; ++s) HMP_CHECK_ARG(reads(q.src[s], q.rows, q.ld_src, q.cols), "pack: segment %d reads outside the parameters", i);
+  } else {
+    HMP_CHECK_ARG(q.H >= 1 && q.C >= 1 && q.H <= 4096 && q.C <= 4096, "pack: segment %d: H %d, C %d", i, q.H, q.C);
+    const int width = q.kind == PACK_ATTDOT_T ? q.rows : q.cols;
+    HMP_CHECK_ARG(q.ld_src >= width && reads(q.src[0], (int64_t)q.H * q.C, q.ld_src, width), "pack: segment %d reads outside the parameters", i);
+    if (q.kind == PACK_HEADS) HMP_CHECK_ARG(q.Cp >= q.C, "pack: segment %d: Cp %d < C %d", i, q.Cp, q.C);
+    else HMP_CHECK_ARG(reads(q.att, 1, 0, (int64_t)q.H * q.C), "pack: segment %d: attention vector outside the parameters", i);
+  }
+  if (q.ld_dst_t != 0) {
+    HMP_CHECK_ARG(q.kind == PACK_SUM && q.ld_dst_t > 0 && q.col_t >= 0 && q.pad_t >= 0 && q.pad_t <= (1 << 20) && q.col_t <= (1 << 20),
+                  "pack: segment %d: transposed image of kind %d, ld %d, col %d, pad %d", i, q.kind, q.ld_dst_t, q.col_t, q.pad_t);
+    const int64_t last = (((int64_t)q.col_t + q.rows_pad + q.pad_t + 15) / 16) * 16;  // wpt_col permutes inside blocks of 16
+    HMP_CHECK_ARG(last <= q.ld_dst_t && q.dst_t >= 0 && q.dst_t + (int64_t)q.ld_dst * q.ld_dst_t <= n_packed,
+                  "pack: segment %d: transposed image outside the packed buffer", i);
+  }
+  memset(&S, 0, sizeof(S));
+  S.dst = q.dst; S.rows = q.rows; S.rows_pad = q.rows_pad; S.cols = q.cols; S.ld_dst = q.ld_dst; S.ld_src = q.ld_src; S.nsrc = q.nsrc;
+  S.kind = q.kind; S.H = q.H; S.C = q.C; S.Cp = q.Cp; S.att = q.att;
+  for (int s = 0; s < AGG_MAX_IN; ++s) S.src[s] = q.src[s];
+  S.dst_t = q.dst_t; S.ld_dst_t = q.ld_dst_t; S.col_t = q.col_t; S.pad_t = q.pad_t;
+  return HMP_OK;
+}
+
+struct UnitTables {  // device copies of a pack table and its 16-item map, freed on every way out
+  PackSeg* d_segs = nullptr;
+  int2* d_map = nullptr;
+  ~UnitTables() {
+    if (d_segs) (void)hipFree(d_segs);
+    if (d_map) (void)hipFree(d_map);
+  }
+};
+
+// route 0: pack_launch; 1: the front launch (fa holds the projections, or none)
+int unit_run(FrontArgs* fa, const hmp_pack_seg* segs, int n_segs, int route, const float* d_params, int64_t n_params, float* d_packed,
+             int64_t n_packed, int32_t* d_step, int32_t* d_step_mirror, hipStream_t st) {
+  HMP_CHECK_ARG(n_segs >= 0 && n_segs <= SEG_MAX && (segs || n_segs == 0), "pack: %d segments (at most %d)", n_segs, SEG_MAX);
+  HMP_CHECK_ARG(d_params && n_params >= 0 && n_packed >= 0 && (d_packed || n_segs == 0), "front / pack: null buffer");
+  std::vector<PackSeg> ps(n_segs);
+  UnitTables T;
+  SegBlocks sb;
+  for (int i = 0; i < n_segs; ++i) HMP_TRY(unit_pack_seg(segs[i], i, n_params, n_packed, ps[i]));
+  pack_seg_blocks(ps.data(), n_segs, sb);
+  const int n_map = pack_block_map(ps.data(), n_segs, nullptr);
+  std::vector<int2> pm(n_map);
+  pack_block_map(ps.data(), n_segs, pm.data());
+  if (n_segs > 0) {
+    HMP_HIP(hipMalloc(&T.d_segs, n_segs * sizeof(PackSeg)));
+    HMP_HIP(hipMemcpy(T.d_segs, ps.data(), n_segs * sizeof(PackSeg), hipMemcpyHostToDevice));
+    if (n_map > 0) {
+      HMP_HIP(hipMalloc(&T.d_map, n_map * sizeof(int2)));
+      HMP_HIP(hipMemcpy(T.d_map, pm.data(), n_map * sizeof(int2), hipMemcpyHostToDevice));
+    }
+  }
+  if (route == 0) {
+    HMP_TRY(pack_launch(T.d_segs, sb, d_params, d_packed, d_step, d_step_mirror, st));
+  } else {
+    fa->params = d_params;
+    fa->segs = T.d_segs; fa->pack_map = T.d_map; fa->pack_blocks = n_map; fa->packed = d_packed;
+    fa->step_ctr = d_step; fa->step_mirror = d_step_mirror;
+    HMP_TRY(front_launch(*fa, st));
+  }
+  HMP_HIP(hipStreamSynchronize(st));
+  return HMP_OK;
+}
+
+}  // namespace
 }  // namespace hmp
+
+extern "C" int hmp_front_run(const hmp_front_prob* probs, int32_t n_prob, const float* d_params, int64_t n_params, const hmp_pack_seg* segs,
+                             int32_t n_segs, float* d_packed, int64_t n_packed, int32_t* d_step, int32_t* d_step_mirror, void* stream) {
+  using namespace hmp;
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_front_run: no gfx950 device visible");
+  HMP_CHECK_ARG(n_prob >= 0 && n_prob <= FR_MAX_PROB && (probs || n_prob == 0), "hmp_front_run: %d problems (at most %d)", n_prob, FR_MAX_PROB);
+  HMP_CHECK_ARG(d_params && n_params >= 0 && n_params < ((int64_t)1 << 31), "hmp_front_run: parameter buffer");
+  FrontArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.n_prob = n_prob;
+  for (int i = 0; i < n_prob; ++i) {
+    const hmp_front_prob& q = probs[i];
+    FrontProb& P = fa.prob[i];
+    HMP_CHECK_ARG(q.A && q.C && q.lda >= q.K && q.ldc >= q.N, "hmp_front_run: problem %d: null operand, lda %d < K %d or ldc %d < N %d", i,
+                  q.lda, q.K, q.ldc, q.N);
+    P.A = q.A; P.C = q.C; P.lda = q.lda; P.ldc = q.ldc; P.M = q.M; P.N = q.N; P.K = q.K; P.n_seg = q.n_seg;
+    int end = 0;
+    for (int s = 0; s < q.n_seg && s < FR_MAX_SEG; ++s) {  // (a count outside 1 .. FR_MAX_SEG is front_launch's to refuse)
+      const hmp_front_seg& g = q.seg[s];
+      HMP_CHECK_ARG(g.ld == q.K && g.rows >= 1 && g.col0 >= end && g.rows <= (1 << 24) && g.col0 <= (1 << 24),
+                    "hmp_front_run: problem %d, segment %d: ld %d (K %d), rows %d at column %d behind %d (sorted, no overlap)", i, s, g.ld, q.K,
+                    g.rows, g.col0, end);
+      end = g.col0 + g.rows;
+      for (int k = 0; k < g.nsrc && k < FR_MAX_SRC; ++k)
+        HMP_CHECK_ARG((int64_t)g.off[k] + (int64_t)g.rows * g.ld <= n_params, "hmp_front_run: problem %d, segment %d reads outside the parameters", i, s);
+      FrontSeg& G = P.seg[s];
+      G.col0 = g.col0; G.rows = g.rows; G.nsrc = g.nsrc; G.ld = g.ld;
+      for (int k = 0; k < FR_MAX_SRC; ++k) G.off[k] = g.off[k];
+    }
+  }
+  return unit_run(&fa, segs, n_segs, 1, d_params, n_params, d_packed, n_packed, d_step, d_step_mirror, (hipStream_t)stream);
+}
+
+extern "C" int hmp_pack_run(const hmp_pack_seg* segs, int32_t n_segs, int32_t route, const float* d_params, int64_t n_params, float* d_packed,
+                            int64_t n_packed, int32_t* d_step, int32_t* d_step_mirror, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(route == 0 || route == 1, "hmp_pack_run: route %d", route);
+  if (route == 1) return hmp_front_run(nullptr, 0, d_params, n_params, segs, n_segs, d_packed, n_packed, d_step, d_step_mirror, stream);
+  static const bool have_device = hmp_device_count() > 0;
+  HMP_CHECK_ARG(have_device, "hmp_pack_run: no gfx950 device visible");
+  return unit_run(nullptr, segs, n_segs, 0, d_params, n_params, d_packed, n_packed, d_step, d_step_mirror, (hipStream_t)stream);
+}

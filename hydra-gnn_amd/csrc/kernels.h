@@ -428,6 +428,10 @@ struct SegBlocks {
   int n;
   int start[SEG_MAX + 1];
 };
+// the two block maps of a pack table (net.hip; build_tables and the unit entry hmp_front_run call the same two): the SegBlocks
+// starts of pack_launch, and FrontArgs::pack_map (returns the number of blocks; pm == null: only counts them)
+void pack_seg_blocks(const PackSeg* ps, int n, SegBlocks& sb);
+int pack_block_map(const PackSeg* ps, int n, int2* pm);
 // step_ctr != null: block 0 increments *step_ctr (the fused step starts with the pack)
 int pack_launch(const PackSeg* d_segs, const SegBlocks& sb, const float* d_params, float* d_packed, int* step_ctr, int* step_mirror,
                 hipStream_t st);

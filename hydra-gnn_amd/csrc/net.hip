@@ -206,6 +206,22 @@ struct hmp_net {
   std::vector<ProfRec> recs;
 };
 
+// block maps of a pack table (n <= SEG_MAX): an item is a (packed row, 64-column chunk), one wave each
+void hmp::pack_seg_blocks(const PackSeg* ps, int n, SegBlocks& sb) {  // pack_launch: 4 waves per block
+  sb.n = n;
+  sb.start[0] = 0;
+  for (int i = 0; i < n; ++i) sb.start[i + 1] = sb.start[i] + cdiv((int64_t)ps[i].rows_pad * cdiv(ps[i].ld_dst, 64), 4);
+}
+int hmp::pack_block_map(const PackSeg* ps, int n, int2* pm) {  // front kernel: 16 waves per block; pm == null: only count
+  int nb = 0;
+  for (int i = 0; i < n; ++i) {
+    const int items = ps[i].rows_pad * cdiv(ps[i].ld_dst, 64);
+    for (int it = 0; it < items; it += 16, ++nb)
+      if (pm) pm[nb] = make_int2(i, it);
+  }
+  return nb;
+}
+
 namespace {
 
 void read_env(hmp_net* n) {
@@ -596,16 +612,10 @@ int build_tables(hmp_net* n) {
   n->n_grad = (int)gs.size(); n->grad_elems = gel;
   HMP_CHECK_ARG(ps.size() <= (size_t)SEG_MAX && gs.size() <= (size_t)SEG_MAX, "net: too many parameter segments (%zu / %zu > %d)",
                 ps.size(), gs.size(), SEG_MAX);
-  n->pack_sb.n = (int)ps.size();
-  n->pack_sb.start[0] = 0;
-  for (size_t i = 0; i < ps.size(); ++i)  // one wave per (row, 64-column chunk), 4 waves per block
-    n->pack_sb.start[i + 1] = n->pack_sb.start[i] + cdiv((int64_t)ps[i].rows_pad * cdiv(ps[i].ld_dst, 64), 4);
+  pack_seg_blocks(ps.data(), (int)ps.size(), n->pack_sb);
   {
-    std::vector<int2> pm;
-    for (size_t i = 0; i < ps.size(); ++i) {
-      const int items = ps[i].rows_pad * cdiv(ps[i].ld_dst, 64);
-      for (int it = 0; it < items; it += 16) pm.push_back(make_int2((int)i, it));
-    }
+    std::vector<int2> pm(pack_block_map(ps.data(), (int)ps.size(), nullptr));
+    pack_block_map(ps.data(), (int)ps.size(), pm.data());
     n->n_pack_blocks16 = (int)pm.size();
     if (!pm.empty()) {
       HMP_HIP(hipMalloc(&n->d_pack_map, pm.size() * sizeof(int2)));

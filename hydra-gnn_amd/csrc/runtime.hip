@@ -43,6 +43,9 @@ size_t hmp_sizeof(int which) {
     case 14: return sizeof(hmp_tail_desc);
     case 15: return sizeof(hmp_linear_heads_desc);
     case 16: return sizeof(hmp_plan_job);
+    case 17: return sizeof(hmp_front_seg);
+    case 18: return sizeof(hmp_front_prob);
+    case 19: return sizeof(hmp_pack_seg);
     default: return 0;
   }
 }

@@ -169,8 +169,34 @@ class PlanJob(C.Structure):
     ]
 
 
+FRONT_MAX_PROB, FRONT_MAX_SEG, FRONT_MAX_SRC = 4, 6, 6
+PACK_SUM, PACK_HEADS, PACK_ATTDOT, PACK_ATTDOT_T = range(4)
+
+
+class FrontSeg(C.Structure):
+    _fields_ = [("col0", C.c_int32), ("rows", C.c_int32), ("nsrc", C.c_int32), ("ld", C.c_int32), ("off", C.c_uint32 * FRONT_MAX_SRC)]
+
+
+class FrontProb(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("C", C.c_void_p),
+        ("lda", C.c_int32), ("ldc", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("n_seg", C.c_int32),
+        ("seg", FrontSeg * FRONT_MAX_SEG),
+    ]
+
+
+class PackSeg(C.Structure):
+    _fields_ = [
+        ("dst", C.c_int64),
+        ("rows", C.c_int32), ("rows_pad", C.c_int32), ("cols", C.c_int32), ("ld_dst", C.c_int32), ("ld_src", C.c_int32),
+        ("nsrc", C.c_int32), ("kind", C.c_int32), ("H", C.c_int32), ("C", C.c_int32), ("Cp", C.c_int32),
+        ("att", C.c_int64), ("src", C.c_int64 * 6), ("dst_t", C.c_int64),
+        ("ld_dst_t", C.c_int32), ("col_t", C.c_int32), ("pad_t", C.c_int32),
+    ]
+
+
 _STRUCTS = [Plan, GatArgs, ConvSpec, LayerSpec, NetSpec, Batch, TrainArgs, HeadTargets, LinearHeads, LinearHeadTargets, GemmDesc,
-            EpochCtl, EpochRow, EpochSeg, TailDesc, LinearHeadsDesc, PlanJob]
+            EpochCtl, EpochRow, EpochSeg, TailDesc, LinearHeadsDesc, PlanJob, FrontSeg, FrontProb, PackSeg]
 
 _VP, _I32, _I64, _F32, _U64, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
@@ -288,6 +314,8 @@ SIGNATURES = {
     "hmp_gemm_bf16_dx_gather": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _I32, _F32, _VP, _I32, _I32, _I32, _I32,
                                           _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     "hmp_gemm_grouped": (C.c_int, [C.POINTER(GemmDesc), _I32, _I32, _I32, _I32, C.POINTER(_I32), _VP]),
+    "hmp_front_run": (C.c_int, [_VP, _I32, _VP, _I64, _VP, _I32, _VP, _I64, _VP, _VP, _VP]),
+    "hmp_pack_run": (C.c_int, [_VP, _I32, _I32, _VP, _I64, _VP, _I64, _VP, _VP, _VP]),
     "hmp_comm_unique_id": (C.c_int, [_VP]),
     "hmp_comm_create": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP)]),
     "hmp_comm_destroy": (None, [_VP]),

@@ -72,7 +72,10 @@ extern "C" {
  *    layout.  The normaliser of the loss and of Adam's gradient scale is now used as it is when > 0 (it was clamped at 1): the
  *    same bits for the integer-valued counts of unweighted steps;
  *    hmp_seg_mean_rows / hmp_seg_mean_rows_t / hmp_gemm_bf16_dx_gather (test entries of the aggregate-first convs' launchers and of
- *    the gather-add term of the input-gradient GEMM): new entries, no struct was added or changed layout */
+ *    the gather-add term of the input-gradient GEMM): new entries, no struct was added or changed layout;
+ *    hmp_front_seg / hmp_front_prob / hmp_pack_seg (hmp_sizeof 17..19), hmp_front_run / hmp_pack_run: unit-test entries of the
+ *    front launch's projection and pack roles and of the stand-alone pack.  New entries and new structs, nothing above changed
+ *    layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -94,8 +97,8 @@ int hmp_abi_version(void);
 const char* hmp_last_error(void);
 /* sizeof() of the ABI structs: 0 hmp_plan, 1 hmp_gat_args, 2 hmp_conv_spec, 3 hmp_layer_spec, 4 hmp_net_spec,
  * 5 hmp_batch, 6 hmp_train_args, 7 hmp_head_targets, 8 hmp_linear_heads, 9 hmp_linear_head_targets, 10 hmp_gemm_desc,
- * 11 hmp_epoch_ctl, 12 hmp_epoch_row, 13 hmp_epoch_seg, 14 hmp_tail_desc, 15 hmp_linear_heads_desc, 16 hmp_plan_job (lets a
- * foreign-language binding verify its struct mirror) */
+ * 11 hmp_epoch_ctl, 12 hmp_epoch_row, 13 hmp_epoch_seg, 14 hmp_tail_desc, 15 hmp_linear_heads_desc, 16 hmp_plan_job, 17 hmp_front_seg,
+ * 18 hmp_front_prob, 19 hmp_pack_seg (lets a foreign-language binding verify its struct mirror) */
 size_t hmp_sizeof(int which);
 /* number of visible devices whose gcnArchName starts with "gfx950"; never raises */
 int hmp_device_count(void);
@@ -249,6 +252,61 @@ typedef struct hmp_gemm_desc {
  * slabs written for problem i; route 2: all 0 when the kernel declined (a problem would need more than max_slabs) and nothing ran */
 int hmp_gemm_grouped(const hmp_gemm_desc* d, int32_t n, int32_t route, int32_t want_split, int32_t max_slabs, int32_t* ksplit_out,
                      void* stream);
+
+/* Unit-test entries of the small-batch step's front launch (csrc/front.hip) and of the parameter pack (ABI-4-compatible
+ * additions, hmp_sizeof 17..19): the descriptors are copied as they stand into the structures the executor fills, the block maps
+ * are the executor's own (pack_seg_blocks / pack_block_map), the plan role is left out (hmp_plan_build_many has it).
+ *
+ * A projection is C[M, N] = A[M, K] * B^T with the stacked operand B read from the flat parameter buffer: row c of B, for
+ * col0 <= c < col0 + rows of a segment, is the sum over q < nsrc of the ld floats at d_params + off[q] + (c - col0) * ld; every
+ * other row below N is zero.  The launcher wants 4 <= K <= 384, K, lda, ld and every off even, A 8-byte and d_params 16-byte
+ * aligned, 1..6 segments of 1..6 sources.  The entry itself checks what the executor guarantees by construction: ld == K, lda >=
+ * K, ldc >= N, segments sorted by col0 without overlap, and every parameter block inside [0, n_params). */
+#define HMP_FRONT_MAX_PROB 4
+#define HMP_FRONT_MAX_SEG 6
+#define HMP_FRONT_MAX_SRC 6
+typedef struct hmp_front_seg {
+  int32_t col0, rows, nsrc, ld;
+  uint32_t off[HMP_FRONT_MAX_SRC];
+} hmp_front_seg;
+typedef struct hmp_front_prob {
+  const float* A;
+  float* C;
+  int32_t lda, ldc, M, N, K, n_seg;
+  hmp_front_seg seg[HMP_FRONT_MAX_SEG];
+} hmp_front_prob;
+/* One segment of a pack table; all offsets count floats.  Rows [0, rows_pad) x columns [0, ld_dst) at d_packed + dst are all
+ * written (what the kind does not define is zero):
+ *   HMP_PACK_SUM       row r = sum over q < nsrc, left to right, of the cols floats at d_params + src[q] + r * ld_src   (r < rows)
+ *   HMP_PACK_HEADS     row h * Cp + c = the cols floats at d_params + src[0] + (h * C + c) * ld_src                   (h < H, c < C)
+ *   HMP_PACK_ATTDOT    row h = sum over c < C of d_params[att + h * C + c] * (row h * C + c of src[0])                 (h < H)
+ *   HMP_PACK_ATTDOT_T  element (d, h) = sum over c < C of d_params[att + h * C + c] * d_params[src[0] + (h * C + c) * ld_src + d]
+ *                      (d < rows, h < H)
+ * ld_dst_t > 0 (HMP_PACK_SUM): element (r, c) of the whole [rows_pad][ld_dst] block is stored a second time at d_packed + dst_t +
+ * c * ld_dst_t + col(col_t + r), where col(16 b + 4 u + q) = 16 b + 4 q + u, and col(col_t + rows_pad + p) of the same ld_dst rows
+ * is set to zero for p < pad_t. */
+#define HMP_PACK_SUM 0
+#define HMP_PACK_HEADS 1
+#define HMP_PACK_ATTDOT 2
+#define HMP_PACK_ATTDOT_T 3
+typedef struct hmp_pack_seg {
+  int64_t dst;
+  int32_t rows, rows_pad, cols, ld_dst, ld_src, nsrc, kind, H, C, Cp;
+  int64_t att;
+  int64_t src[6];
+  int64_t dst_t;
+  int32_t ld_dst_t, col_t, pad_t;
+} hmp_pack_seg;
+/* One front launch: n_prob <= 4 projections (may be 0) and, when n_segs > 0, the pack role over segs (16 items per block through
+ * the executor's static map).  d_step (may be NULL): device int32 that the pack role raises by one, leaving the new value in
+ * d_step_mirror too (may be NULL).  n_params / n_packed: floats in the two buffers; a descriptor that reaches outside is refused.
+ * The table upload is synchronous and the call returns after the launch has finished. */
+int hmp_front_run(const hmp_front_prob* probs, int32_t n_prob, const float* d_params, int64_t n_params, const hmp_pack_seg* segs,
+                  int32_t n_segs, float* d_packed, int64_t n_packed, int32_t* d_step, int32_t* d_step_mirror, void* stream);
+/* The pack alone: route 0 through pack_launch (4 items per block, block -> segment scan), route 1 through the front launch's pack
+ * role (hmp_front_run without projections). */
+int hmp_pack_run(const hmp_pack_seg* segs, int32_t n_segs, int32_t route, const float* d_params, int64_t n_params, float* d_packed,
+                 int64_t n_packed, int32_t* d_step, int32_t* d_step_mirror, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 4. K3 -- GAT edge softmax + weighted aggregation, one row group of lanes per destination row.

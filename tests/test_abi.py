@@ -75,6 +75,14 @@ def test_no_cpu_fallback():
     d = _lib.GemmDesc(A=C.addressof(buf), B=C.addressof(buf), C=C.addressof(buf), M=4, N=4, K=4, lda=4, ldb=4, ldc=4, n_real=4)
     assert lib.hmp_gemm_grouped(C.byref(d), 1, 0, 0, 1, None, None) != 0
     assert b"gfx950" in lib.hmp_last_error()
+    prob = _lib.FrontProb(A=C.addressof(buf), C=C.addressof(buf), lda=4, ldc=4, M=4, N=4, K=4, n_seg=1)
+    prob.seg[0] = _lib.FrontSeg(col0=0, rows=4, nsrc=1, ld=4)
+    seg = _lib.PackSeg(dst=0, rows=4, rows_pad=4, cols=4, ld_dst=4, ld_src=4, nsrc=1)
+    for route in (0, 1):  # the unit entries of the front launch and the pack: no host stand-in either
+        assert lib.hmp_pack_run(C.byref(seg), 1, route, C.addressof(buf), 64, C.addressof(buf), 64, None, None, None) != 0
+        assert b"gfx950" in lib.hmp_last_error()
+    assert lib.hmp_front_run(C.byref(prob), 1, C.addressof(buf), 64, None, 0, None, 0, None, None, None) != 0
+    assert b"gfx950" in lib.hmp_last_error()
     from hydra_gnn_amd import workloads
     from hydra_gnn_amd.models import HeterogeneousNetwork
 

@@ -26,7 +26,8 @@ NEW_ENTRIES = {
 # hmp_sizeof(i) of the public structs before the label entries were added, in _lib._STRUCTS order
 STRUCT_BYTES = {"Plan": 64, "GatArgs": 40, "ConvSpec": 112, "LayerSpec": 1872, "NetSpec": 15184, "Batch": 736, "TrainArgs": 56,
                 "HeadTargets": 32, "LinearHeads": 48, "LinearHeadTargets": 32, "GemmDesc": 128, "EpochCtl": 40, "EpochRow": 40,
-                "EpochSeg": 24, "TailDesc": 128, "LinearHeadsDesc": 168, "PlanJob": 120}
+                "EpochSeg": 24, "TailDesc": 128, "LinearHeadsDesc": 168, "PlanJob": 120, "FrontSeg": 40,
+                "FrontProb": 280, "PackSeg": 128}
 
 
 def test_new_entries_are_exported_and_bound():
