@@ -104,6 +104,7 @@ namespace hmp {
 // the 4 KB block carries the per-batch tables (a config-2 batch of 32 graphs needs 6 * 33 + 32 = 230 words)
 constexpr int CB_MAX_ITEMS = 40;
 constexpr int CB_MAX_SLOTS = 24;
+constexpr int CB_WIDE_UNITS = 32;  // rows of this many 4-byte units or more go a wavefront per row: read by the kernel's branch AND the host's grid sizing
 constexpr int CB_INLINE_WORDS = 264;  // int64 words of per-batch tables carried by value in the kernel argument block (whole block < 4 KB)
 
 struct CbItem {
@@ -134,17 +135,20 @@ struct CbArgs {
 static_assert(sizeof(CbArgs) <= 4096, "kernel argument block");
 
 __global__ __launch_bounds__(256) void collate_batch_kernel(const CbArgs a) {
+  const int B = a.B;
+  const int64_t* tab = a.tables ? a.tables : a.inl;
+  if (a.off_out && blockIdx.x == 0)
+    for (int q = threadIdx.x; q < a.n_slots * (B + 1); q += 256) a.off_out[(int64_t)(q / (B + 1)) * a.off_stride + q % (B + 1)] = tab[q];
+  // a batch in which no item has a row is launched as one workgroup for the offsets alone: no item owns it, and the loops below
+  // would stride by nb == 0
+  if (a.total_blocks == 0) return;
   int ii = 0;
   while (ii + 1 < a.n_items && (int)blockIdx.x >= a.item[ii + 1].block_start) ++ii;
   const CbItem& I = a.item[ii];
-  const int B = a.B;
-  const int64_t* tab = a.tables ? a.tables : a.inl;
   const int64_t* off = tab + (int64_t)I.slot * (B + 1);
   const int64_t* sel = tab + (int64_t)a.n_slots * (B + 1);
   const int nb = (ii + 1 < a.n_items ? a.item[ii + 1].block_start : a.total_blocks) - I.block_start;
   const int64_t n_out = off[B];
-  if (a.off_out && blockIdx.x == 0)
-    for (int q = threadIdx.x; q < a.n_slots * (B + 1); q += 256) a.off_out[(int64_t)(q / (B + 1)) * a.off_stride + q % (B + 1)] = tab[q];
   const int row_units = I.row_bytes >> 2;
   if (I.row_bytes & 3) {
     // byte-wide rows (bool / int8 masks of the two-headed task): one thread per output byte
@@ -158,7 +162,7 @@ __global__ __launch_bounds__(256) void collate_batch_kernel(const CbArgs a) {
       const int64_t srow = I.ptr[sel[b]] + (row - off[b]);
       dst[g] = src[srow * rb + (g - row * rb)];
     }
-  } else if (row_units >= 32) {
+  } else if (row_units >= CB_WIDE_UNITS) {
     // wide rows (features): one wavefront per row -- the batch position of the row is found ONCE (wave-uniform search in the
     // offset table), then 64 lanes copy the row with coalesced 8-byte (even widths) or 4-byte accesses
     const int lane = threadIdx.x & 63;
@@ -331,7 +335,7 @@ extern "C" int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B
     // wide rows: a wavefront per row, 2 rows per wavefront and pass; narrow rows / edges: a thread per row / edge; byte rows: a
     // thread per byte
     const int rb = a.item[i].row_bytes;
-    int64_t nb = (rb & 3) ? (n_out * rb + 255) / 256 : rb >= 128 ? (n_out + 7) / 8 : (n_out + 255) / 256;
+    int64_t nb = (rb & 3) ? (n_out * rb + 255) / 256 : rb >= 4 * CB_WIDE_UNITS ? (n_out + 7) / 8 : (n_out + 255) / 256;
     if (nb > 2048) nb = 2048;
     a.item[i].block_start = blocks;
     blocks += (int)nb;
@@ -342,8 +346,9 @@ extern "C" int hmp_collator_run(hmp_collator* c, const int32_t* h_sel, int32_t B
     HMP_HIP(hipEventRecord(c->done[slot_i], st));
     a.tables = c->dev[slot_i];
   }
-  if (blocks == 0) return HMP_OK;
-  hipLaunchKernelGGL(collate_batch_kernel, dim3(blocks), dim3(256), 0, st, a);
+  // no item has a row: nothing to copy, but the caller's offset table (the plan build reads it) must not keep the previous batch's
+  if (blocks == 0 && !d_offsets_out) return HMP_OK;
+  hipLaunchKernelGGL(collate_batch_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, a);
   HMP_LAUNCH_CHECK();
   return HMP_OK;
 }

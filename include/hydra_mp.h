@@ -910,6 +910,7 @@ int hmp_collate_edges(const int64_t* d_src, int64_t e_total, const int64_t* d_ed
  *           (row_bytes == 0: int64 [2][src_total], positioned by `slot`, endpoints shifted by `slot_src` / `slot_dst`).
  * hmp_collator_run: h_sel [B] graph ids (host), d_dst[i] / dst_capacity[i] per item (rows resp. edges), h_totals[slot] receives
  * the batch's node / edge totals (the shapes of the outputs).  No allocation or synchronisation in the steady state.
+ * d_offsets_out, when given, is written by every run, a batch in which no item has a row included.
  * (<= 264 words of offsets + selection travel in the kernel's argument block, larger batches through a pinned ring;
  * at most 24 slots and 40 items: the two-headed H-tree dataset with edge attributes has 21 and 39.  Byte-wide rows are a branch
  * of the same kernel: a batch of the two-headed task, labels and masks of both heads included, is still ONE launch.) */
