@@ -232,10 +232,14 @@ __host__ __device__ inline uint32_t drop_thresh(float p) {
 }
 
 // the two hash words of quad q (elements 4*q .. 4*q+3 of the tensor numbered cfg.stream): element j draws the 16-bit half
-// (j & 1) of word (j >> 1) and is kept when the draw >= thresh >> 16
+// (j & 1) of word (j >> 1) and is kept when the draw >= thresh >> 16.  include/hydra_mp.h (hmp_dropout_mask) states the generator;
+// tests/_dropout_reference.py restates it in numpy and tools/drop_check.cpp prints this code's words for it to compare.
 __host__ __device__ inline void drop_pair(const DropCfg& cfg, uint32_t q, uint32_t& a, uint32_t& b) {
-  // (stream, step, seed) fold into a wave-uniform key; the quad index is the counter
-  const uint32_t key = cfg.k0 ^ (cfg.stream * 0x9E3779B1u) ^ (cfg.step * 0x85EBCA77u);
+  // (stream, step, both seed words) fold into a wave-uniform key; the quad index is the counter.  Without the k1 term the first
+  // word, i.e. elements 0 and 1 of every quad, would not depend on the seed's high word.  hash32(0) == 0: a seed below 2^32 draws
+  // what it drew before the term existed.  hash32 and not a multiply: seeds that differ in one high bit would move a multiplied
+  // term in its top bits only, where hash32's own avalanche is weakest; the hash is scalar work on a kernel argument either way.
+  const uint32_t key = cfg.k0 ^ (cfg.stream * 0x9E3779B1u) ^ (cfg.step * 0x85EBCA77u) ^ hash32(cfg.k1);
   a = hash32(q ^ key);
   b = hash32((a + 0x9E3779B9u) ^ cfg.k1 ^ (q * 0xC2B2AE3Du));
 }

@@ -468,7 +468,42 @@ int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t 
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
 
 /* keep-mask generator of the engine's feature dropout, exposed so tests can replay it in the oracle:
- * element (row, col) of a [n_rows, F] tensor is kept iff mask[row*F+col] != 0. */
+ * element (row, col) of a [n_rows, F] tensor is kept iff mask[row*F+col] != 0 (d_mask: device uint8 [n_rows * F], every element
+ * written 0 or 1, nothing behind them; n_rows == 0 or F == 0 writes nothing).
+ *
+ * The generator (csrc/common.h: hash32, drop_thresh, drop_pair, drop_keep4; every draw site of the library calls the same four).
+ * All arithmetic is on 32-bit unsigned words and wraps modulo 2^32; >> is a logical shift.
+ *
+ *   hash32(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16;  return x
+ *
+ *   seed words: k0 = seed mod 2^32 (low word), k1 = seed >> 32 (high word)
+ *   key  = k0 ^ (rng_stream * 0x9E3779B1) ^ (rng_step * 0x85EBCA77) ^ hash32(k1)
+ *          (one word per launch, the same for every element; hash32(0) == 0, so the k1 term vanishes for a seed below 2^32)
+ *
+ *   The counter is the quad number q, a 32-bit word (a tensor of more than 2^32 quads wraps).  Quad q draws two words
+ *     a = hash32(q ^ key)
+ *     b = hash32((a + 0x9E3779B9) ^ k1 ^ (q * 0xC2B2AE3D))
+ *   and its four elements j = 0 .. 3 draw the 16-bit halves
+ *     draw[0] = a & 0xFFFF,   draw[1] = a >> 16,   draw[2] = b & 0xFFFF,   draw[3] = b >> 16.
+ *
+ *   Keep rule: element j is kept iff draw[j] >= (thresh >> 16), with
+ *     thresh = (uint32) min(trunc((double)(float)p * 2^32), 2^32 - 1)
+ *   -- p is the C float of the call (a caller holding a double rounds it to float first); the product is exact in double.
+ *
+ *   Quad numbering of a [n_rows, F] tensor: a row is padded to qpr = (F + 3) >> 2 quads, and element (row, col) is element
+ *   j = col & 3 of quad q = row * qpr + (col >> 2), computed as a 32-bit word.  The elements col >= F of a row's last quad are drawn
+ *   and discarded: a row always starts a fresh quad, so masks of different F share no layout.
+ *   GAT attention dropout numbers the coefficient (pos, head) of edge position pos (CSR position of the edge, self loops at
+ *   E + node) as element (pos, head) of a [*, 8] tensor whatever the number of heads: quad q = 2 * pos + (head >> 2), element
+ *   j = head & 3; hmp_dropout_mask(seed, step, stream, p, P, 8, ...) replays it.
+ *
+ * What the 16-bit resolution means: the keep probability is 1 - floor((float)p * 65536) / 65536, not 1 - p, while kept values are
+ * scaled by 1.f / (1.f - p) (float arithmetic) at every draw site; the expectation is off by less than 2^-16 / (1 - p) relative.
+ * A p below 2^-16 (p == 0 included) drops nothing.  rng_step and rng_stream are full 32-bit words; all 64 bits of the seed count.
+ * What the key being one xor-ed word means: two sites whose keys differ by d draw the same first words at permuted quads
+ * (a of quad q at one is a of quad q ^ d at the other; the second words differ).  Stream, step and high seed word are spread over
+ * the word by their multipliers and the hash, so d exceeds any tensor's quad count in practice; seeds that differ in low bits of
+ * the low word only (s and s + 1) give a small d.  Choose seeds at random (the models draw 62 random bits), not consecutively. */
 int hmp_dropout_mask(uint64_t seed, uint32_t rng_step, uint32_t rng_stream, float p, int32_t n_rows, int32_t F,
                      uint8_t* d_mask, void* stream);
 

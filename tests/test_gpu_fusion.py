@@ -110,7 +110,7 @@ def test_both_sequences_match_the_oracle(mode):
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_fused_step_equals_two_phase_step(use_graph):
     """cross entropy in the last aggregation + Adam in the gradient un-pack == loss kernel + Adam kernel (5 steps, dropout on:
-    both draw the same Philox masks)"""
+    both draw the same dropout masks)"""
     kw = dict(SAGE_KW, dropout=0.25)
     batch = workloads.config2_batch(8).to(DEV)
     y = batch["rooms"].y

@@ -216,7 +216,7 @@ def make_gat_replay(net, batch):
 ])
 def test_gat_training_mode_parity_with_replayed_masks(block, hidden, heads, concats):
     """Training mode as train_mp3d.py runs it (dropout 0.25 on the attention coefficients AND on the ELU outputs): the oracle
-    replays the engine's Philox keep-masks; logits, loss and every gradient at 1e-5.  (models/utils.py:31-87)"""
+    replays the engine's keep-masks; logits, loss and every gradient at 1e-5.  (models/utils.py:31-87)"""
     training_mode_parity(block, hidden, heads, concats, workloads.mp3d_like_batch(6, seed=29, relative_pos=(block == "GAT_edge")))
 
 
@@ -289,7 +289,7 @@ def test_gat_training_mode_runs_and_is_deterministic():
     for _ in range(8):
         step2(batch, y)
         losses2.append(step2.loss())
-    assert losses == losses2  # same seed => same Philox masks, eager and graph replay agree bit for bit
+    assert losses == losses2  # same seed => same dropout masks, eager and graph replay agree bit for bit
 
 
 def test_homogeneous_gat_parity():

@@ -110,7 +110,7 @@ def test_empty_and_ragged_edge_types():
 
 
 def test_dropout_training_parity_with_replayed_masks():
-    """Training-mode parity: the oracle replays the engine's Philox keep-masks (hmp_dropout_mask)."""
+    """Training-mode parity: the oracle replays the engine's keep-masks (hmp_dropout_mask)."""
     import ctypes as C
 
     lib = _lib.require_device()

@@ -265,6 +265,79 @@ def test_adam_matches_torch():
     torch.testing.assert_close(p.cpu().double(), ref_p.detach(), atol=1e-6, rtol=1e-5)
 
 
+def adam_reference(p, g, m, v, lr, b1, b2, eps, wd, step, count):
+    """include/hydra_mp.h's Adam in float64 (numpy arrays in; the scalars are the C floats of the call): (p, m, v, extra), `extra`
+    the per-element allowance for p on top of the kernel's usual tolerance, derived below"""
+    lr, b1, b2, eps, wd = (float(np.float32(s)) for s in (lr, b1, b2, eps, wd))
+    p0, g, m0, v0 = (a.astype(np.float64) for a in (p, g, m, v))
+    gs = 1.0 if count is None else 1.0 / (float(np.float32(count)) if count > 0 else 1.0)
+    gi = g * gs + wd * p0
+    m = b1 * m0 + (1.0 - b1) * gi
+    v = b2 * v0 + (1.0 - b2) * gi * gi
+    s, d = lr / (1.0 - b1**step), np.sqrt(v) / np.sqrt(1.0 - b2**step) + eps
+    upd = s * m / d
+
+    # What float32 evaluation of the same formula can add to the error of p BEYOND 1e-6 + 1e-5 |p|, per element (u = 2^-24, the
+    # relative error of one rounding).  The two existing tolerances cover roundings that scale with |p| or stay below 1e-6; two
+    # things do not scale so, and both show where v is small, so that the update upd = s m / d is large against m:
+    #  (1) the error of m, amplified by s / d.  gi = g gs + wd p: gs, two products and a sum round, |dgi| <= 3u (|g gs| + |wd p|);
+    #      m = b1 m0 + (1 - b1) gi (1 - b1 is exact, Sterbenz): |dm| <= (1 - b1) |dgi| + 2u (|b1 m0| + |(1 - b1) gi|).
+    #  (2) the relative error of s / d, times |upd|.  A bias correction 1 - b^t is a difference: powf within 2 ulp (4u relative)
+    #      leaves it with the relative error e(b, t) = 4u b^t / (1 - b^t) + u -- 500 x 4u for b2 = 0.999 at t = 2, u at t = 1
+    #      (b^1 is exact) and for large t.  s carries e(b1, t) + u; d carries half of e(b2, t) (square root), half the relative
+    #      error of v -- |dv| <= 2 (1 - b2) |gi| |dgi| + 4u v, every term of v is >= 0 -- and 4u for the two square roots, the
+    #      division and the sum with eps; the product and the quotient of the update add 2u.
+    u = 2.0**-24
+    e1, e2 = (4 * u * b**step / (1.0 - b**step) + u for b in (b1, b2))
+    dgi = 3 * u * (np.abs(g * gs) + np.abs(wd * p0))
+    dm = (1.0 - b1) * dgi + 2 * u * (np.abs(b1 * m0) + np.abs((1.0 - b1) * gi))
+    dv_rel = np.divide(2 * (1.0 - b2) * np.abs(gi) * dgi, v, out=np.zeros_like(v), where=v > 0) + 4 * u
+    extra = s / d * dm + np.abs(upd) * (e1 + u + e2 / 2 + dv_rel / 2 + 4 * u + 2 * u)
+    return p0 - upd, m, v, extra
+
+
+@pytest.mark.parametrize("n,zero_at", [(1, None), (1, 0), (255, 17), (257, 256), (2048 * 256 + 3, 2048 * 256 + 2)])
+def test_adam_flat_matches_float64_formula(n, zero_at):
+    """One hmp_adam_flat step from random (p, g, m, v >= 0) against the header's formula in float64: one element, one short of and one
+    past a workgroup, and 2048 x 256 + 3 elements (the launch has at most 2048 workgroups: the last three elements are a second
+    trip of the grid-stride loop); d_count 0 (acts as 1), below 1 and above; with and without weight decay; steps 1, 2 (bias
+    corrections far from 1) and 100000 (both equal to 1 in float32).  Element zero_at has g = m = v = 0: without weight decay its
+    p keeps its bits and its moments stay 0 (m / (sqrt(v) + eps) = 0 / eps), with weight decay it follows the formula like any other.
+    Tolerances: the kernel's existing ones (p: 1e-6 + 1e-5 |ref|, as test_adam_matches_torch; m, v: this module's 1e-5 + 1e-5 |ref|),
+    for p plus adam_reference's per-element `extra`: with those two alone, 1 element of the 524 291 at step 2 (count 0, wd 1e-3) is
+    off by 3.8e-6 = 1.8e-5 |ref| -- a small v makes its update large, and at step 2 the float32 bias correction 1 - b2^2 is a
+    difference of nearly equal numbers (relative error up to 1.2e-4, half of it in the update)."""
+    lib = _lib.require_device()
+    rng = np.random.default_rng(n)
+    p0, g0, m0 = (rng.standard_normal(n).astype(np.float32) for _ in range(3))
+    v0 = (rng.standard_normal(n) ** 2).astype(np.float32)
+    if zero_at is not None:
+        g0[zero_at] = m0[zero_at] = v0[zero_at] = 0.0
+        p0[zero_at] = 0.7
+    lr, b1, b2, eps = 0.002, 0.9, 0.999, 1e-8
+    g_dev = torch.from_numpy(g0).to(dev())
+    for count in (0.0, 0.25, 37.0):
+        cnt = torch.tensor([count], dtype=torch.float32, device=dev())
+        for wd in (0.0, 1e-3):
+            for step in (1, 2, 100000):
+                p, m, v = (torch.from_numpy(a).to(dev()) for a in (p0, m0, v0))
+                _lib.check(lib.hmp_adam_flat(p.data_ptr(), g_dev.data_ptr(), m.data_ptr(), v.data_ptr(), n, lr, b1, b2, eps, wd, step,
+                                             cnt.data_ptr(), sp()))
+                torch.cuda.synchronize()
+                rp, rm, rv, extra = adam_reference(p0, g0, m0, v0, lr, b1, b2, eps, wd, step, count)
+                what = f"count {count} wd {wd} step {step}"
+                err, allowed = np.abs(p.cpu().double().numpy() - rp), 1e-6 + 1e-5 * np.abs(rp) + extra
+                worst = int(np.argmax(err / allowed))
+                print(f"n {n} {what}: p off by at most {err.max():.2e}; worst against its bound: {err[worst]:.2e} of {allowed[worst]:.2e} "
+                      f"(extra {extra[worst]:.2e}, largest extra {extra.max():.2e}, median {np.median(extra):.2e})")
+                assert err[worst] <= allowed[worst], f"p, {what}: element {worst} off by {err[worst]:.3e}, allowed {allowed[worst]:.3e}"
+                torch.testing.assert_close(m.cpu().double(), torch.from_numpy(rm), atol=ATOL, rtol=RTOL, msg=lambda s: f"m, {what}: {s}")
+                torch.testing.assert_close(v.cpu().double(), torch.from_numpy(rv), atol=ATOL, rtol=RTOL, msg=lambda s: f"v, {what}: {s}")
+                assert torch.equal(g_dev.cpu(), torch.from_numpy(g0))  # the gradient is read only
+                if zero_at is not None and wd == 0.0:
+                    assert p[zero_at].item() == float(p0[zero_at]) and m[zero_at].item() == 0.0 and v[zero_at].item() == 0.0, what
+
+
 def test_dropout_mask_rate_and_determinism():
     lib = _lib.require_device()
     n, F = 4000, 64

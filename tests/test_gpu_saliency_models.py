@@ -271,6 +271,10 @@ def test_training_mode_autograd_replays_the_dropout_masks():
     from test_gpu_models import hetero_replay
 
     ora, net, graphs, coll, head, relu = host_case("sage32x3", dropout=0.25)
+    # The dropout seed is part of this run's inputs: under the masks of the seed the model drew, the smallest |ReLU input| of the
+    # oracle is 9.5e-5, below the margin; under those of seed + 2 it is 4.8e-4 (found on the CPU by replaying the masks of
+    # tests/_dropout_reference.py in the oracle: seed + 1 gives 5.1e-5).
+    net._seed += 2
     net = net.to(DEV).train()
     batch = coll(graphs).to(DEV)
     for t in ("objects", "rooms"):

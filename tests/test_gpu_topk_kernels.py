@@ -276,9 +276,10 @@ def test_identity_pool_next_to_a_real_one(classes, act, k):
 HEAD_SHAPES = [((15, 35), 16), ((1, 64), 80), ((15, 35), 768), ((2, 3), 20)]
 HEAD_ROWS = [1, 31, 33, 7681]
 # activation and k per (shape, row count).  ELU keeps k <= 3.  F = 768 meets ELU at 31 rows, not at 7681: its logits reach |50|, where
-# the kernel's 768-term fmaf chain is further from float64 than the blocked sum of the host's float32 matmul, the yardstick.  Measured
-# at 7681 rows: probabilities off by 3.6e-5 against a tolerance of 4.1e-5 that moves with the host's BLAS -- a property of the logits
-# of pass 1 (unchanged by the top-k mode; tests/test_gpu_tail_kernels.py measures its cross entropy), not of the top-k behind them.
+# the kernel's logits -- when these cases were chosen, one 768-term fmaf chain; since then summed per 64-column chunk -- were further from
+# float64 than the blocked sum of the host's float32 matmul, the yardstick.  Measured at 7681 rows with the chain: probabilities off by
+# 3.6e-5 against a tolerance of 4.1e-5 that moves with the host's BLAS -- a property of the logits of pass 1 (unchanged by the top-k
+# mode; tests/test_gpu_tail_kernels.py measures its cross entropy), not of the top-k behind them.
 HEAD_ACTS = [[R, E, N, E], [E, N, E, R], [N, E, R, N], [E, R, E, N]]
 HEAD_KS = [[3, 1, 8, 3], [1, 8, 3, 2], [8, 3, 2, 1], [3, 2, 1, 8]]
 
