@@ -157,6 +157,76 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   }
 }
 
+// One Monte-Carlo dropout sample (tail_fns.h: mc_group): the row's softmax, its squares and its entropy are added to the row's
+// accumulators acc[row] (kernels.h: the layout), or stored with first != 0.  Rows outside `members` are not touched.  VEC / scalar
+// as topk_rows_kernel: the lanes own the same columns either way, so a row's probabilities are the top-k kernel's bit for bit.
+template <bool VEC>
+__global__ __launch_bounds__(256) void mc_rows_kernel(const float* __restrict__ x, int ld, int n_rows, int n_classes,
+                                                      const uint8_t* __restrict__ members, int first, float* __restrict__ acc, int ld_acc) {
+  const int lane = threadIdx.x % EV_GS;
+  for (int row = blockIdx.x * EV_RPB + (int)threadIdx.x / EV_GS; row < n_rows; row += gridDim.x * EV_RPB) {
+    // the member byte and the accumulator address do not depend on the walk; the whole group of 16 lanes takes the same branch
+    const bool member = members ? members[row] != 0 : true;
+    float* const ar = acc + (int64_t)row * ld_acc;
+    const float* __restrict__ xr = x + (int64_t)row * ld;
+    if (!member) continue;
+    if (VEC) {
+      mc_group<EV_GS, 0>(lane, n_classes, [&](int, int c, float (&v)[4]) {
+        const float4 x4 = *reinterpret_cast<const float4*>(xr + c);  // c + 3 < ld: ld % 4 == 0 and c < n_classes <= ld
+        v[0] = x4.x; v[1] = x4.y; v[2] = x4.z; v[3] = x4.w;
+      }, first != 0, ar);
+    } else {
+      mc_group<EV_GS, 0>(lane, n_classes, [&](int, int c, float (&v)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = c + i < n_classes ? xr[c + i] : 0.f;  // nothing past the row's classes is read
+      }, first != 0, ar);
+    }
+  }
+}
+
+// The statistics of `samples` accumulated samples, per row by its 16 lanes (lane i owns the quads i, i + 16, ... of the classes):
+//   mean[c] = A[c] / T;  label = first-maximum argmax of mean;  std = sqrt(max(0, B[label] / T - mean[label]^2));
+//   entropy = -sum_c mean[c] logf(mean[c]) (a zero term is 0; per lane in ascending column order, then the xor butterfly);
+//   mutual information = max(0, entropy - E / T).
+// Every requested output of every row in [0, n_rows) is written once: a row outside `members` holds -1 / 0; columns of `mean` at
+// or past the classes are not written.
+__global__ __launch_bounds__(256) void mc_finish_kernel(const float* __restrict__ acc, int ld_acc, int n_rows, int n_classes, int samples,
+                                                        const uint8_t* __restrict__ members, int64_t* __restrict__ labels,
+                                                        float* __restrict__ mean, int ld_mean, float* __restrict__ sd,
+                                                        float* __restrict__ entropy, float* __restrict__ mi) {
+  const int lane = threadIdx.x % EV_GS;
+  const float T = (float)samples;
+  for (int row = blockIdx.x * EV_RPB + (int)threadIdx.x / EV_GS; row < n_rows; row += gridDim.x * EV_RPB) {
+    // the member byte and the addresses do not depend on the walk; the whole group of 16 lanes takes the same branch
+    const bool member = members ? members[row] != 0 : true;
+    const float* __restrict__ ar = acc + (int64_t)row * ld_acc;
+    float* const mr = mean ? mean + (int64_t)row * ld_mean : nullptr;
+    float best = -INFINITY, h = 0.f;
+    int arg = ARGMAX_NONE;
+    lane_quads<EV_GS, 0>(lane, n_classes, [&](int, int c) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (c + i >= n_classes) continue;
+        const float p = member ? ar[c + i] / T : 0.f;
+        if (mr) mr[c + i] = p;
+        argmax_take(p, c + i, best, arg);
+        h += p > 0.f ? p * logf(p) : 0.f;
+      }
+    });
+    argmax_reduce_pair<EV_GS>(best, arg);
+#pragma unroll
+    for (int o = EV_GS / 2; o > 0; o >>= 1) h += __shfl_xor(h, o);
+    if (lane == 0) {
+      if (arg == ARGMAX_NONE) arg = 0;
+      const float ent = 0.f - h;
+      if (labels) labels[row] = member ? (int64_t)arg : -1;
+      if (sd) sd[row] = member ? sqrtf(fmaxf(0.f, ar[mc_off_b(n_classes) + arg] / T - best * best)) : 0.f;
+      if (entropy) entropy[row] = member ? ent : 0.f;
+      if (mi) mi[row] = member ? fmaxf(0.f, ent - ar[mc_off_e(n_classes)] / T) : 0.f;
+    }
+  }
+}
+
 // ---- label histogram and balanced class weights (the class weights of the weighted cross entropy, computed where the labels live)
 // counts[c] += #rows with label c that count ((mask == null || mask[row]) && label != ignored), c in [0, n_classes);
 // counts[n_classes] += #counted rows whose label lies outside [0, n_classes).  HIST (n_classes <= LC_HIST_MAX): a per-workgroup
@@ -235,6 +305,31 @@ int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const ui
   return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
     hipLaunchKernelGGL((topk_rows_kernel<vec()>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, members, k, labels, probs);
   });
+}
+
+int mc_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int first, float* acc, int ld_acc,
+                   hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1 && ld >= n_classes, "mc_accumulate_rows: n_rows %d, n_classes %d, ld %d", n_rows, n_classes, ld);
+  HMP_CHECK_ARG(ld_acc > mc_off_e(n_classes), "mc_accumulate_rows: ld_acc %d (%d classes need more than %d)", ld_acc, n_classes, mc_off_e(n_classes));
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(x && acc, "mc_accumulate_rows: null logits or accumulators");
+  return ev_launch(x, ld, n_rows, [&](dim3 grid, auto vec) {
+    hipLaunchKernelGGL((mc_rows_kernel<vec()>), grid, dim3(256), 0, st, x, ld, n_rows, n_classes, members, first, acc, ld_acc);
+  });
+}
+
+int mc_finish_launch(const float* acc, int ld_acc, int n_rows, int n_classes, int samples, const uint8_t* members, int64_t* labels,
+                     float* mean, int ld_mean, float* sd, float* entropy, float* mi, hipStream_t st) {
+  HMP_CHECK_ARG(n_rows >= 0 && n_classes >= 1, "mc_finish: n_rows %d, n_classes %d", n_rows, n_classes);
+  HMP_CHECK_ARG(ld_acc > mc_off_e(n_classes), "mc_finish: ld_acc %d (%d classes need more than %d)", ld_acc, n_classes, mc_off_e(n_classes));
+  HMP_CHECK_ARG(samples >= 1 && samples <= MC_MAX_SAMPLES, "mc_finish: samples = %d (1 .. %d)", samples, MC_MAX_SAMPLES);
+  HMP_CHECK_ARG(!mean || ld_mean >= n_classes, "mc_finish: ld_mean %d below the %d classes", ld_mean, n_classes);
+  if (n_rows == 0) return HMP_OK;
+  HMP_CHECK_ARG(acc && (labels || mean || sd || entropy || mi), "mc_finish: null accumulators or no output");
+  hipLaunchKernelGGL(mc_finish_kernel, dim3(ev_blocks(n_rows)), dim3(256), 0, st, acc, ld_acc, n_rows, n_classes, samples, members, labels,
+                     mean, ld_mean, sd, entropy, mi);
+  HMP_LAUNCH_CHECK();
+  return HMP_OK;
 }
 
 int predict_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int64_t* pred, hipStream_t st) {
@@ -334,4 +429,20 @@ extern "C" int hmp_topk_rows(const float* d_logits, int32_t ld, int32_t n_rows, 
                              int64_t* d_labels, float* d_probs, void* stream) {
   using namespace hmp;
   return topk_rows_launch(d_logits, ld, n_rows, n_classes, d_members, k, d_labels, d_probs, (hipStream_t)stream);
+}
+
+extern "C" int32_t hmp_mc_acc_ld(int32_t n_classes) { return n_classes >= 1 ? hmp::mc_acc_ld(n_classes) : 0; }
+
+extern "C" int hmp_mc_accumulate_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members,
+                                      int32_t first, float* d_acc, int32_t ld_acc, void* stream) {
+  using namespace hmp;
+  return mc_rows_launch(d_logits, ld, n_rows, n_classes, d_members, first, d_acc, ld_acc, (hipStream_t)stream);
+}
+
+extern "C" int hmp_mc_finish(const float* d_acc, int32_t ld_acc, int32_t n_rows, int32_t n_classes, int32_t samples,
+                             const uint8_t* d_members, int64_t* d_labels, float* d_mean, int32_t ld_mean, float* d_std, float* d_entropy,
+                             float* d_mi, void* stream) {
+  using namespace hmp;
+  return mc_finish_launch(d_acc, ld_acc, n_rows, n_classes, samples, d_members, d_labels, d_mean, ld_mean, d_std, d_entropy, d_mi,
+                          (hipStream_t)stream);
 }

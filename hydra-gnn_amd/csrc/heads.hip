@@ -77,10 +77,11 @@ __device__ __forceinline__ int head_argmax(const float* lg, int C) {
 }
 
 // what follows the logits of a tile: the CE and its backward (pass 2), the accuracy count, or the labels themselves
-// (or, HL_TOPK, the k largest logits of each head with their softmax probabilities)
-enum HeadMode { HL_COUNT = 0, HL_TRAIN = 1, HL_PREDICT = 2, HL_TOPK = 3 };
+// (or, HL_TOPK, the k largest logits of each head with their softmax probabilities; or, HL_MC, one Monte-Carlo dropout sample
+// of each head's softmax added to the row's accumulators -- the one label mode whose tail draws)
+enum HeadMode { HL_COUNT = 0, HL_TRAIN = 1, HL_PREDICT = 2, HL_TOPK = 3, HL_MC = 4 };
 
-constexpr int HL_GS = 16;  // HL_TOPK: lanes per (row, head) of the tile
+constexpr int HL_GS = 16;  // HL_TOPK, HL_MC: lanes per (row, head) of the tile
 
 // HL_TOPK: the tile's 2 * HL_RB (row, head) pairs go round the workgroup's groups of HL_GS lanes, each a topk_group walk (tail_fns.h)
 // over the head's logits in LDS -- comparisons alone pick the labels, so column 0 is head_argmax's; -1 / 0 outside the head's rows
@@ -103,6 +104,26 @@ __device__ __forceinline__ void heads_topk(const LinHeadArgs& a, const HeadSmem&
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = c + i < C ? lg[c + i] : 0.f;
     }, lo, po);
+  }
+}
+
+// HL_MC: the same round over the tile's (row, head) pairs, each a mc_group walk (tail_fns.h) over the head's logits in LDS into the
+// accumulators of the head's row; rows outside the head's rows are not touched
+__device__ __forceinline__ void heads_mc(const LinHeadArgs& a, const HeadSmem& s, int row0) {
+  const int lane = threadIdx.x % HL_GS;
+  for (int p = (int)threadIdx.x / HL_GS; p < 2 * HL_RB; p += 256 / HL_GS) {  // whole groups take every branch below together
+    const int r = p % HL_RB, h = p / HL_RB, row = row0 + r;
+    if (row >= a.n_rows || !a.mc_acc[h]) continue;
+    // the member byte and the accumulator address do not depend on the walk
+    const bool member = head_member(a, h, row);
+    float* const ar = a.mc_acc[h] + (int64_t)row * a.mc_ld[h];
+    const int C = a.classes[h];
+    const float* lg = &s.lg[r][h == 0 ? 0 : a.classes[0]];
+    if (!member) continue;
+    mc_group<HL_GS, 0>(lane, C, [&](int, int c, float (&v)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = c + i < C ? lg[c + i] : 0.f;
+    }, a.mc_first != 0, ar);
   }
 }
 
@@ -170,6 +191,10 @@ __global__ __launch_bounds__(256) void linear_heads_kernel(const LinHeadArgs a) 
     __syncthreads();
     if constexpr (MODE == HL_TOPK) {
       heads_topk(a, s, row0);
+      continue;
+    }
+    if constexpr (MODE == HL_MC) {
+      heads_mc(a, s, row0);
       continue;
     }
     // ---- CE / argmax: one thread per (row, head) -----------------------------------------------------------------------
@@ -301,11 +326,11 @@ int heads_blocks(int n_rows) {
   return tiles < HEAD_MAX_BLOCKS ? tiles : HEAD_MAX_BLOCKS;
 }
 
-// the launch of every mode: a workgroup per row tile up to the cap, walking n_tiles; only the training launch drops
+// the launch of every mode: a workgroup per row tile up to the cap, walking n_tiles; only the training and the Monte-Carlo launch drop
 template <HeadMode MODE>
 static int heads_launch(LinHeadArgs& a, hipStream_t st) {
   a.n_tiles = cdiv(a.n_rows, HL_RB);
-  if (MODE != HL_TRAIN) a.drop_on = 0;
+  if (MODE != HL_TRAIN && MODE != HL_MC) a.drop_on = 0;
   const int blocks = heads_blocks(a.n_rows);
   if (blocks == 0) return HMP_OK;
   hipLaunchKernelGGL(linear_heads_kernel<MODE>, dim3(blocks), dim3(256), 0, st, a);
@@ -348,6 +373,22 @@ int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, floa
   }
   a.topk = k;
   return heads_launch<HL_TOPK>(a, st);
+}
+
+// one Monte-Carlo dropout sample: the softmax of head h's logits on dropout(act(z)) (a.drop_on / a.drop: the caller's site) added to
+// acc[h][row] (kernels.h: the layout) for the head's rows; a head without accumulator is skipped.  Pass 1 and the tile assignment are
+// the count's.
+int linear_heads_mc_launch(LinHeadArgs& a, int first, float* const* acc, const int* ld_acc, hipStream_t st) {
+  HMP_CHECK_ARG(acc != nullptr && ld_acc != nullptr, "linear heads: null accumulator array");
+  HMP_TRY(heads_check(a, false));
+  for (int h = 0; h < 2; ++h) {
+    HMP_CHECK_ARG(!acc[h] || ld_acc[h] > mc_off_e(a.classes[h]), "linear heads: ld_acc %d of head %d (%d classes need more than %d)", ld_acc[h],
+                  h, a.classes[h], mc_off_e(a.classes[h]));
+    a.mc_acc[h] = acc[h];
+    a.mc_ld[h] = ld_acc[h];
+  }
+  a.mc_first = first;
+  return heads_launch<HL_MC>(a, st);
 }
 
 }  // namespace hmp
@@ -434,4 +475,22 @@ extern "C" int hmp_linear_heads_topk(const hmp_linear_heads_desc* d, int32_t k, 
   LinHeadArgs a;
   HMP_TRY(label_heads_args("hmp_linear_heads_topk", d, n_blocks_out, a));
   return linear_heads_topk_launch(a, k, d_labels, d_probs, (hipStream_t)stream);
+}
+
+// the Monte-Carlo launcher on the same descriptor, training mode: the tail draws at the descriptor's dropout site (p == 0: none)
+extern "C" int hmp_linear_heads_mc(const hmp_linear_heads_desc* d, int32_t first, float* const* d_acc, const int32_t* ld_acc,
+                                   int32_t* n_blocks_out, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_acc && ld_acc, "hmp_linear_heads_mc: null pointer");
+  LinHeadArgs a;
+  HMP_TRY(label_heads_args("hmp_linear_heads_mc", d, n_blocks_out, a));
+  HMP_CHECK_ARG(d->p >= 0.f && d->p < 1.f, "hmp_linear_heads_mc: p = %g", (double)d->p);
+  a.drop_on = d->p > 0.f ? 1 : 0;
+  if (a.drop_on) {  // (as net.hip: make_drop)
+    a.drop.k0 = (uint32_t)d->seed; a.drop.k1 = (uint32_t)(d->seed >> 32);
+    a.drop.step = d->rng_step; a.drop.stream = d->rng_stream;
+    a.drop.thresh = drop_thresh(d->p); a.drop.scale = 1.f / (1.f - d->p);
+    a.drop.step_dev = nullptr;
+  }
+  return linear_heads_mc_launch(a, first, d_acc, ld_acc, (hipStream_t)stream);
 }

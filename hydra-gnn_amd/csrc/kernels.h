@@ -791,6 +791,9 @@ struct LinHeadArgs {
   int64_t* tk_labels[2];        // top-k output: [row][topk] per head (a head with both null is skipped)
   float* tk_probs[2];
   int topk;
+  float* mc_acc[2];             // MC-dropout accumulators: [row][mc_ld[h]] per head (null: head skipped)
+  int mc_ld[2];
+  int mc_first;
 };
 int heads_blocks(int n_rows);
 int linear_heads_ce_launch(LinHeadArgs& a, hipStream_t st);
@@ -819,6 +822,26 @@ int topk_rows_launch(const float* x, int ld, int n_rows, int n_classes, const ui
 int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* probs, bool pool, hipStream_t st);
 // by head; a head with both pointers null is skipped
 int linear_heads_topk_launch(LinHeadArgs& a, int k, int64_t* const* labels, float* const* probs, hipStream_t st);
+
+// Monte-Carlo dropout accumulators (tail_fns.h: mc_group), one launch next to each top-k launch above, over the scores of ONE
+// stochastic sample.  A row of an accumulator buffer [rows][ld_acc] holds, with Cp = align4(classes),
+//   A[c] = sum_t p_t[c] at column c,  B[c] = sum_t p_t[c]^2 at column Cp + c  (c < classes),  E = sum_t h_t at column 2 * Cp;
+// the columns [classes, Cp), [Cp + classes, 2 * Cp) and past 2 * Cp are never touched.  first != 0 stores the sample instead of
+// adding it (the buffer needs no initialisation).  The row group that owns a row is its only writer: no atomics.
+constexpr int MC_MAX_SAMPLES = 4096;
+__host__ __device__ inline int mc_off_b(int classes) { return (classes + 3) & ~3; }
+__host__ __device__ inline int mc_off_e(int classes) { return 2 * ((classes + 3) & ~3); }
+inline int mc_acc_ld(int classes) { return mc_off_e(classes) + 4; }  // rows stay 16-byte aligned
+int mc_rows_launch(const float* x, int ld, int n_rows, int n_classes, const uint8_t* members, int first, float* acc, int ld_acc,
+                   hipStream_t st);
+// labels / mean / std / entropy / mutual information of `samples` accumulated samples (any may be null, not all); rows outside
+// `members` hold -1 / 0
+int mc_finish_launch(const float* acc, int ld_acc, int n_rows, int n_classes, int samples, const uint8_t* members, int64_t* labels,
+                     float* mean, int ld_mean, float* std, float* entropy, float* mi, hipStream_t st);
+// by entry of the launch (the entries' drop_on / drop say whether and how the tail draws); an entry without accumulator must have no rows
+int tail_mc_launch(TailArgs& a, int first, float* const* acc, const int* ld_acc, bool pool, hipStream_t st);
+// by head; a head without accumulator is skipped.  a.drop_on / a.drop are the caller's
+int linear_heads_mc_launch(LinHeadArgs& a, int first, float* const* acc, const int* ld_acc, hipStream_t st);
 
 // step_dev != null: t = *step_dev is read on the device (graph replay); else t = step_host
 int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

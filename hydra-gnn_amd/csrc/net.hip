@@ -2239,6 +2239,10 @@ struct ReadoutTargets {
   const hmp_head_targets* two = nullptr;
   const hmp_linear_head_targets* lin = nullptr;
   bool want[2] = {true, true};  // two heads: the heads the launch serves
+  // Monte-Carlo dropout: the forward runs in training mode at (seed, rng_step) and the readout's tail draws at the same site
+  int training = 0;
+  uint64_t seed = 0;
+  uint32_t rng_step = 0;
 };
 
 // the final state in the net's readout form: the linear heads' arguments, the two heads' tail rows, or (neither filled) the output
@@ -2252,13 +2256,22 @@ struct Readout {
 template <class Launch>
 int run_readout(hmp_net* n, const hmp_batch* b, const float* d_params, const ReadoutTargets& tg, void* stream, Launch&& launch) {
   hipStream_t st = (hipStream_t)stream;
-  HMP_TRY(plain_forward(n, b, d_params, st));
+  HMP_TRY(plain_forward(n, b, d_params, st, tg.training, tg.seed, tg.rng_step));
+  const hmp_net_spec& S = n->spec;
+  const bool drop = tg.training && S.tail_dropout > 0.f;  // the tail's site: what add_tail / add_pool / heads_args give the CE
   Readout r;
   if (n->has_heads) {
     r.lin = heads_args(n, b, tg.lin, d_params, false, 0);
-  } else if (n->spec.aux_readout_type >= 0) {
+    r.lin.drop_on = drop ? 1 : 0;
+    if (drop) r.lin.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + S.readout_type));
+  } else if (S.aux_readout_type >= 0) {
     r.ta = tail_rows(n, b, tg.two, false, 0, tg.want, r.slot);
     if (r.ta.n == 0) return HMP_OK;  // no wanted head has rows
+    for (int i = 0; i < r.ta.n && drop; ++i) {
+      HeadTail& T = r.ta.h[i];
+      T.drop_on = 1;
+      T.drop = make_drop(n, S.tail_dropout, (uint32_t)((n->L - 1) * HMP_MAX_NODE_TYPES + head_type(n, T.slot)));
+    }
   }
   Scope sc(n, KC_LOSS, st);
   return launch(r, st);
@@ -2408,6 +2421,73 @@ extern "C" int hmp_net_topk_heads(hmp_net* n, const hmp_batch* batch, const floa
   const hmp_linear_head_targets tg = members_only(d_member);
   return run_readout(n, batch, d_params, {nullptr, &tg}, stream,
                      [&](Readout& r, hipStream_t st) { return linear_heads_topk_launch(r.lin, k, d_labels, d_probs, st); });
+}
+
+// ---- Monte-Carlo dropout (tail_fns.h: mc_group): ONE stochastic sample -- the training-mode forward at (seed, rng_step), then ONE
+// launch that adds the softmax of the sample's scores to the caller's accumulators (first: stores it).  The refusals are the top-k
+// siblings', checked before the forward.
+namespace {
+
+int check_mc_tail(const hmp_net* n, const char* who) {
+  const float p = n->spec.tail_dropout;
+  HMP_CHECK_ARG(p >= 0.f && p < 1.f, "%s: spec tail_dropout %g", who, (double)p);
+  return HMP_OK;
+}
+
+ReadoutTargets mc_targets(const hmp_linear_head_targets* lin, bool want0, bool want1, uint64_t seed, uint32_t rng_step) {
+  ReadoutTargets tg;
+  tg.lin = lin;
+  tg.want[0] = want0; tg.want[1] = want1;
+  tg.training = 1; tg.seed = seed; tg.rng_step = rng_step;
+  return tg;
+}
+
+}  // namespace
+
+extern "C" int hmp_net_mc_rooms(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, uint64_t seed,
+                                uint32_t rng_step, int32_t first, float* d_acc, int32_t ld_acc, void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && (d_acc || batch->n_out == 0), "hmp_net_mc_rooms: null argument");
+  HMP_TRY(check_single_head(n, "hmp_net_mc_rooms", "takes hmp_net_mc2 / hmp_net_mc_heads"));
+  HMP_CHECK_ARG(ld_acc > mc_off_e(n->out_dim), "hmp_net_mc_rooms: ld_acc %d (%d classes need hmp_mc_acc_ld = %d)", (int)ld_acc, n->out_dim,
+                mc_acc_ld(n->out_dim));
+  return run_readout(n, batch, d_params, mc_targets(nullptr, true, true, seed, rng_step), stream, [&](Readout&, hipStream_t st) {
+    return mc_rows_launch(out_ptr(n), n->out_ld, batch->n_out, n->out_dim, d_members, first, d_acc, ld_acc, st);
+  });
+}
+
+extern "C" int hmp_net_mc2(hmp_net* n, const hmp_batch* batch, const float* d_params, uint64_t seed, uint32_t rng_step, int32_t first,
+                           float* const d_acc[2], const int32_t ld_acc[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_acc && ld_acc, "hmp_net_mc2: null argument");
+  HMP_TRY(check_two_heads(n, "hmp_net_mc2", "hmp_net_mc_rooms"));
+  HMP_TRY(check_mc_tail(n, "hmp_net_mc2"));
+  for (int h = 0; h < 2; ++h) {
+    const int C = n->dim[n->L][head_type(n, h)];
+    HMP_CHECK_ARG(!d_acc[h] || ld_acc[h] > mc_off_e(C), "hmp_net_mc2: ld_acc %d of head %d (%d classes need hmp_mc_acc_ld = %d)", (int)ld_acc[h],
+                  h, C, mc_acc_ld(C));
+  }
+  const ReadoutTargets tg = mc_targets(nullptr, d_acc[0] != nullptr, d_acc[1] != nullptr, seed, rng_step);  // no accumulator skips the head
+  return run_readout(n, batch, d_params, tg, stream, [&](Readout& r, hipStream_t st) {
+    float* acc[2] = {nullptr, nullptr};
+    int ld[2] = {0, 0};
+    for (int h = 0; h < 2; ++h)
+      if (r.slot[h] >= 0) { acc[r.slot[h]] = d_acc[h]; ld[r.slot[h]] = ld_acc[h]; }
+    return tail_mc_launch(r.ta, first, acc, ld, n->has_pools, st);
+  });
+}
+
+extern "C" int hmp_net_mc_heads(hmp_net* n, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], uint64_t seed,
+                                uint32_t rng_step, int32_t first, float* const d_acc[2], const int32_t ld_acc[2], void* stream) {
+  HMP_CHECK_ARG(n && batch && d_params && d_member && d_acc && ld_acc, "hmp_net_mc_heads: null argument");
+  HMP_TRY(check_label_heads(n, "hmp_net_mc_heads"));
+  HMP_TRY(check_mc_tail(n, "hmp_net_mc_heads"));
+  for (int h = 0; h < 2; ++h)
+    HMP_CHECK_ARG(!d_acc[h] || ld_acc[h] > mc_off_e(n->heads.classes[h]), "hmp_net_mc_heads: ld_acc %d of head %d (%d classes need hmp_mc_acc_ld = %d)",
+                  (int)ld_acc[h], h, n->heads.classes[h], mc_acc_ld(n->heads.classes[h]));
+  const hmp_linear_head_targets lt = members_only(d_member);
+  return run_readout(n, batch, d_params, mc_targets(&lt, true, true, seed, rng_step), stream, [&](Readout& r, hipStream_t st) {
+    const int ld[2] = {ld_acc[0], ld_acc[1]};
+    return linear_heads_mc_launch(r.lin, first, d_acc, ld, st);
+  });
 }
 
 // ---- attention export: the eval-mode forward, then ONE launch that writes the coefficients of the requested convs of one GAT

@@ -226,6 +226,40 @@ __device__ __forceinline__ void tail_topk(const TailArgs& a, const TailTopk& o) 
 __global__ __launch_bounds__(256) void tail_topk_kernel(const TailArgs a, const TailTopk o) { tail_topk<false>(a, o); }
 __global__ __launch_bounds__(256) void pool_topk_kernel(const TailArgs a, const TailTopk o) { tail_topk<true>(a, o); }
 
+// One Monte-Carlo dropout sample of the rows tail_topk walks (tail_fns.h: mc_group), for every row of both entries: the softmax of
+// dropout(act(z)) -- the tail draws as the CE kernels do, with the entry's drop -- or of its LeafPool mean is added to the row's
+// accumulators acc[entry][row] (kernels.h: the layout).  An empty pooled row is all 0: p = 1 / C.
+struct TailMc {
+  float* acc[2];  // by entry of the launch
+  int ld[2];
+  int first;
+};
+
+template <bool POOL>
+__device__ __forceinline__ void tail_mc(const TailArgs& a, const TailMc& o) {
+  const int e = tail_entry(a);
+  const HeadTail& T = a.h[e];
+  const int row = tail_row(T);
+  if (row >= (POOL ? T.n_pool : T.n_rows)) return;
+  // independent of the walk below
+  float* const ar = (e ? o.acc[1] : o.acc[0]) + (int64_t)row * (e ? o.ld[1] : o.ld[0]);
+  const int lane = threadIdx.x % TL_GS;
+  const DropCfg cfg = T.drop_on ? drop_resolve(T.drop) : T.drop;
+  if constexpr (POOL) {
+    float p[PT_Q][4];
+    pool_row(T, cfg, a.act, row, lane, p);
+    mc_group<TL_GS, PT_Q>(lane, T.classes, [&](int q, int, float (&v)[4]) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = p[q][i];
+    }, o.first != 0, ar);
+  } else {
+    mc_group<TL_GS, 0>(lane, T.classes, [&](int, int c, float (&v)[4]) { tail_quad(T, cfg, a.act, row, c, v); }, o.first != 0, ar);
+  }
+}
+
+__global__ __launch_bounds__(256) void tail_mc_kernel(const TailArgs a, const TailMc o) { tail_mc<false>(a, o); }
+__global__ __launch_bounds__(256) void pool_mc_kernel(const TailArgs a, const TailMc o) { tail_mc<true>(a, o); }
+
 // Checks the entries for a launch and lays their row groups out over the grid.  pool: the heads go through a LeafPool (rows in
 // registers, CSR / CSC or the identity); leaf_rows: one row group per leaf row, else per pooled row; ce: the launch writes gradients;
 // csc: the launch (or its companion) walks the pool plan by leaf -- the predict launch reads the CSR alone.
@@ -299,6 +333,19 @@ int tail_topk_launch(TailArgs& a, int k, int64_t* const* labels, float* const* p
   for (int i = 0; i < a.n; ++i) { o.l[i] = labels[i]; o.p[i] = probs[i]; }
   HMP_TRY(check_outputs(a, pool, "tail top-k: no output", [&](int i) { return o.l[i] || o.p[i]; }));
   return tail_launch(pool ? pool_topk_kernel : tail_topk_kernel, a, pool, !pool, false, false, st, o);
+}
+
+// one Monte-Carlo dropout sample of every row of the entries (leaf rows, or pool: pooled rows) into acc[entry]; the layout and checks
+// of tail_predict_launch
+int tail_mc_launch(TailArgs& a, int first, float* const* acc, const int* ld_acc, bool pool, hipStream_t st) {
+  HMP_CHECK_ARG(acc != nullptr && ld_acc != nullptr, "tail mc: null accumulator array");
+  TailMc o = {{nullptr, nullptr}, {0, 0}, first};
+  for (int i = 0; i < a.n; ++i) { o.acc[i] = acc[i]; o.ld[i] = ld_acc[i]; }
+  HMP_TRY(check_outputs(a, pool, "tail mc: no accumulator", [&](int i) { return o.acc[i] != nullptr; }));
+  for (int i = 0; i < a.n; ++i)
+    HMP_CHECK_ARG(!o.acc[i] || o.ld[i] > mc_off_e(a.h[i].classes), "tail mc: ld_acc %d of entry %d (%d classes need more than %d)", o.ld[i], i,
+                  a.h[i].classes, mc_off_e(a.h[i].classes));
+  return tail_launch(pool ? pool_mc_kernel : tail_mc_kernel, a, pool, !pool, false, false, st, o);
 }
 
 }  // namespace hmp
@@ -392,4 +439,26 @@ extern "C" int hmp_head_tails_topk(const hmp_tail_desc* d, int32_t n, int32_t po
   TailArgs ta;
   HMP_TRY(label_tail_args("hmp_head_tails_topk", d, n, act, ta));
   return tail_topk_launch(ta, k, d_labels, d_probs, pooled != 0, (hipStream_t)stream);
+}
+
+// the Monte-Carlo launchers on the same descriptors, training mode: the tail draws at the descriptors' dropout site (p == 0: none)
+extern "C" int hmp_head_tails_mc(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int32_t first, float* const* d_acc,
+                                 const int32_t* ld_acc, void* stream) {
+  using namespace hmp;
+  HMP_CHECK_ARG(d_acc && ld_acc, "hmp_head_tails_mc: null accumulator array");
+  TailArgs ta;
+  HMP_TRY(label_tail_args("hmp_head_tails_mc", d, n, act, ta));
+  for (int i = 0; i < n; ++i) {
+    const hmp_tail_desc& q = d[i];
+    HMP_CHECK_ARG(q.p >= 0.f && q.p < 1.f, "hmp_head_tails_mc: p = %g (head %d)", (double)q.p, i);
+    HeadTail& T = ta.h[i];
+    T.drop_on = q.p > 0.f ? 1 : 0;
+    if (T.drop_on) {  // (as net.hip: make_drop)
+      T.drop.k0 = (uint32_t)q.seed; T.drop.k1 = (uint32_t)(q.seed >> 32);
+      T.drop.step = q.rng_step; T.drop.stream = q.rng_stream;
+      T.drop.thresh = drop_thresh(q.p); T.drop.scale = 1.f / (1.f - q.p);
+      T.drop.step_dev = nullptr;
+    }
+  }
+  return tail_mc_launch(ta, first, d_acc, ld_acc, pooled != 0, (hipStream_t)stream);
 }

@@ -6,6 +6,7 @@
 //   argmax_group<GS, NQ>,  first-maximum argmax of a row by GS lanes         evaluate.hip, optim.hip (argmax_rows_kernel), semisup.hip
 //   argmax_take/_reduce
 //   topk_group<GS, NQ>     the k largest entries and their softmax probabilities  evaluate.hip, semisup.hip, heads.hip (top-k kernels)
+//   mc_group<GS, NQ>       one Monte-Carlo dropout sample: the row's softmax and entropy added to its accumulators  evaluate.hip, semisup.hip, heads.hip
 //   count_begin/row/flush  a workgroup's {correct, total} pair in LDS        semisup.hip, evaluate.hip (count_rows_kernel)
 //
 // The backward form of act_drop, tail_dydz, is in common.h.
@@ -225,6 +226,57 @@ __device__ __forceinline__ void topk_group(int lane, int classes, int k, Quad&& 
     last_c = arg;
   }
   topk_blank(lane, kk, k, labels, probs);
+}
+
+// ---- Monte-Carlo dropout: one stochastic sample of a row added to the row's accumulators ------------------------------------------
+// p[c] = expf(s[c] - m) / sum_c' expf(s[c'] - m) with topk_group's m (the row maximum) and its sum -- per lane in ascending column
+// order, then the xor butterfly below GS -- so p[c] has the bits topk_group stores for class c on the same scores;
+// h = -sum_c p[c] * logf(p[c]) (a term with p[c] == 0 is 0) in the same association.  The row's accumulators (kernels.h: the
+// layout, mc_off_b / mc_off_e) receive A[c] += p[c], B[c] += p[c] * p[c] from the lane that owns column c and E += h from lane 0;
+// first: the sample is stored instead (what the buffer held, NaN included, is not read).  quad(q, c, v) as in ce_group: it runs
+// once per pass (maximum, sum, probabilities), so a caller without the row in registers recomputes it.  NaN scores are
+// unspecified but store in bounds.
+template <int GS, int NQ, class Quad>
+__device__ __forceinline__ void mc_group(int lane, int classes, Quad&& quad, bool first, float* __restrict__ acc) {
+  float* const accb = acc + mc_off_b(classes);
+  float* const acce = acc + mc_off_e(classes);
+  float m = -INFINITY;
+  lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
+    float v[4];
+    quad(q, c, v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (c + i < classes) m = fmaxf(m, v[i]);
+  });
+#pragma unroll
+  for (int o = GS / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  float s = 0.f;
+  lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
+    float v[4];
+    quad(q, c, v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (c + i < classes) s += expf(v[i] - m);
+  });
+#pragma unroll
+  for (int o = GS / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  float h = 0.f;
+  lane_quads<GS, NQ>(lane, classes, [&](int q, int c) {
+    float v[4];
+    quad(q, c, v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (c + i >= classes) continue;
+      const float p = expf(v[i] - m) / s;
+      const float pp = p * p;
+      h += p > 0.f ? p * logf(p) : 0.f;
+      acc[c + i] = first ? p : acc[c + i] + p;
+      accb[c + i] = first ? pp : accb[c + i] + pp;
+    }
+  });
+#pragma unroll
+  for (int o = GS / 2; o > 0; o >>= 1) h += __shfl_xor(h, o);
+  if (lane == 0) *acce = first ? 0.f - h : *acce + (0.f - h);
 }
 
 // ---- a workgroup's {correct, total} pair ------------------------------------------------------------------------------------------

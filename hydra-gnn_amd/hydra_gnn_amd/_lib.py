@@ -234,12 +234,17 @@ SIGNATURES = {
     "hmp_count_correct_rows_by_graph": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _VP, _I32, _VP, _VP]),
     "hmp_predict_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "hmp_topk_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
+    "hmp_mc_acc_ld": (_I32, [_I32]),
+    "hmp_mc_accumulate_rows": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP]),
+    "hmp_mc_finish": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "hmp_adam_flat": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "hmp_dropout_mask": (C.c_int, [_U64, _U32, _U32, _F32, _I32, _I32, _VP, _VP]),
     "hmp_head_tails": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I64, _VP, _VP, _VP]),
     "hmp_head_tails_weighted": (C.c_int, [C.POINTER(TailDesc), _I32, C.POINTER(_VP), _I32, _I32, _I64, _VP, _VP, _VP]),
     "hmp_head_tails_predict": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, C.POINTER(_VP), _VP]),
     "hmp_head_tails_topk": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_head_tails_mc": (C.c_int, [C.POINTER(TailDesc), _I32, _I32, _I32, _I32, C.POINTER(_VP), C.POINTER(_I32), _VP]),
+    "hmp_linear_heads_mc": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, C.POINTER(_VP), C.POINTER(_I32), C.POINTER(_I32), _VP]),
     "hmp_linear_heads_run": (C.c_int, [C.POINTER(LinearHeadsDesc), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
     "hmp_linear_heads_run_weighted": (C.c_int, [C.POINTER(LinearHeadsDesc), C.POINTER(_VP), _I32, _VP, _VP, C.POINTER(_I32), _VP]),
     "hmp_linear_heads_predict": (C.c_int, [C.POINTER(LinearHeadsDesc), C.POINTER(_VP), C.POINTER(_I32), _VP]),
@@ -273,6 +278,9 @@ SIGNATURES = {
     "hmp_net_topk_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _I32, _VP, _VP, _VP]),
     "hmp_net_topk2": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_topk_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
+    "hmp_net_mc_rooms": (C.c_int, [_VP, C.POINTER(Batch), _VP, _VP, _U64, _U32, _I32, _VP, _I32, _VP]),
+    "hmp_net_mc2": (C.c_int, [_VP, C.POINTER(Batch), _VP, _U64, _U32, _I32, C.POINTER(_VP), C.POINTER(_I32), _VP]),
+    "hmp_net_mc_heads": (C.c_int, [_VP, C.POINTER(Batch), _VP, C.POINTER(_VP), _U64, _U32, _I32, C.POINTER(_VP), C.POINTER(_I32), _VP]),
     "hmp_net_attention": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, C.POINTER(_VP), _I32, C.POINTER(_VP), C.POINTER(_VP), _VP]),
     "hmp_net_input_gradient": (C.c_int, [_VP, C.POINTER(Batch), _VP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _I32, C.POINTER(_VP), _VP]),
     "hmp_net_plan": (C.c_int, [_VP, _I32, C.POINTER(Plan)]),

@@ -179,6 +179,9 @@ class NativeNet:
         # the host results of predict / predict_pair, of predict_confidence, and of explain / explain_salient
         self._pred, self._conf, self._att = _HostMirror(), _HostMirror(), _HostMirror()
         self._conf_views = None  # predict_confidence: (rows per head, device views, host views) of the last call
+        # predict_mc: the accumulators of each head (regrown on demand); predict_uncertainty: its host results
+        self._mc_cache: List[Optional[torch.Tensor]] = [None, None]
+        self._unc = _HostMirror()
 
     def set_compute(self, precision: str) -> None:
         """'fp32' (default): every projection on the exact fp32 MFMA path.  'bf16': GEMM calls in the throughput-bound regime
@@ -816,6 +819,106 @@ class NativeNet:
             self._conf.fetch(12 * n)
         return host
 
+    # ---- Monte-Carlo dropout uncertainty ---------------------------------------------------------------------------------
+    def _mc_accs(self, rows: Sequence[int], classes: Sequence[int], dev) -> List[torch.Tensor]:
+        """the cached accumulators of :meth:`predict_mc`, one ``[rows, hmp_mc_acc_ld(C)]`` view per head; a buffer is regrown when a
+        batch needs more floats than it holds"""
+        cache = self._mc_cache
+        views = []
+        for i, (n, c) in enumerate(zip(rows, classes)):
+            ld = int(self._lib.hmp_mc_acc_ld(c))
+            buf = cache[i]
+            if buf is None or buf.numel() < n * ld or buf.device != dev:
+                buf = cache[i] = torch.empty(max(2 * n * ld, 1024), dtype=torch.float32, device=dev)
+            views.append(buf[:n * ld].view(n, ld))
+        return views
+
+    def _mc_finish_members(self, h, stream, mem, keep, rows):
+        """the member address of every head's finishing launch (None: every row) and what must outlive it: the room task's row
+        filter, nothing for the whole node types of an aux-readout net, the member rows of linear heads -- the object head's being
+        the complement of the room rows where the net has no object rows of its own"""
+        if self.heads is None:
+            return ([mem] if self.aux_readout is None else [None, None]), None
+        m0, m1 = mem[0], mem[1]
+        alive = None
+        if m1 is None and rows[0] > 0:
+            room = stream.room_rows()[:rows[0]] if keep is None else keep[0]
+            alive = ~room
+            m1 = alive.data_ptr()
+        return [m0, m1], alive
+
+    def predict_mc(self, batch, samples: int, seed: int, first_step: int = 1, members=None, out=None):
+        """Monte-Carlo dropout on the device: ``samples`` = T stochastic passes, sample ``t`` being the training-mode forward at the
+        dropout site ``(seed, first_step + t)`` -- feature, attention and tail dropout all draw -- plus ONE launch that adds the
+        softmax of the sample's scores to per-row accumulators (``hmp_net_mc_rooms`` / ``hmp_net_mc2`` / ``hmp_net_mc_heads``, picked
+        by the net's kind as :meth:`predict_labels` picks, with its ``batch`` and ``members``), then one finishing launch per head
+        (``hmp_mc_finish``).  ``1 <= samples <= 4096``, ``0 <= first_step``, ``first_step + samples <= 2**32``.
+
+        Per head ``(labels int64 [rows], mean_probs float32 [rows, C], std, entropy, mutual_info float32 [rows])``: the mean
+        predictive distribution over the samples, its first-maximum argmax, the standard deviation of that label's probability, the
+        entropy of the mean and the mutual information between prediction and weights (entropy of the mean minus the mean entropy).
+        Rows outside the head's rows hold ``-1`` / ``0``.  The room task returns one such tuple, a two-headed net a pair of them.
+
+        ``out`` takes caller-owned buffers of that structure (contiguous, on the model's device, at least the needed rows); the result
+        is a view of their leading rows.  The accumulators are cached on the net.  Nothing synchronises; the parameters are read,
+        never written."""
+        samples = _check_samples(samples)
+        first_step = _check_first_step(first_step, samples)
+        seed = _check_seed(seed)
+        h, stream, flat, rows = self._label_rows(batch, "predict_mc")
+        dev = flat.device
+        two = len(rows) == 2
+        classes = self.head_classes()
+        outs = _mc_buffers(out, rows, classes, two, dev)
+        mem, keep = self._label_members(h, stream, members, rows, dev, "predict_mc")
+        self._ensure_handle(h)
+        with torch.cuda.device(dev):
+            accs = self._mc_accs(rows, classes, dev)
+            fin, _alive = self._mc_finish_members(h, stream, mem, keep, rows)
+        kind = "_heads" if self.heads is not None else "2" if self.aux_readout is not None else "_rooms"
+        if kind == "_rooms":
+            acc_args = (accs[0].data_ptr(), accs[0].size(1))
+        else:
+            acc_args = ((C.c_void_p * 2)(*[a.data_ptr() if a.numel() else None for a in accs]), (C.c_int32 * 2)(*[a.size(1) for a in accs]))
+        for t in range(samples):
+            self._count(f"hmp_net_mc{kind}", h, dev, flat.data_ptr(), *(() if kind == "2" else (mem,)), seed, first_step + t,
+                        1 if t == 0 else 0, *acc_args)
+        with torch.cuda.device(dev):
+            for a, c, n, m, o in zip(accs, classes, rows, fin, outs):
+                if n:
+                    _lib.check(self._lib.hmp_mc_finish(a.data_ptr(), a.size(1), n, c, samples, m, o[0].data_ptr(), o[1].data_ptr(), c,
+                                                       o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), _lib.stream_ptr()))
+        views = tuple(tuple(t[:n] for t in o) for o, n in zip(outs, rows))
+        return views if two else views[0]
+
+    def predict_uncertainty(self, batch, samples: int, seed: int, first_step: int = 1, members=None):
+        """:meth:`predict_mc` on the host: every output of every head lands in ONE device buffer (8 bytes per label, then the
+        floats) and crosses in one D2H through one pinned buffer and one event, as :meth:`predict_confidence` moves its pairs.
+        Returns host ``(labels int64 [rows], mean_probs float32 [rows, C], std, entropy, mutual_info float32 [rows])`` per head --
+        one tuple for the room task, a pair for a two-headed net -- as views of that buffer (valid until the next call)."""
+        h, _, flat, rows = self._label_rows(batch, "predict_uncertainty")
+        dev = flat.device
+        classes = self.head_classes()
+        n_lab = sum(rows)
+        nbytes = 8 * n_lab + 4 * sum(n * (c + 3) for n, c in zip(rows, classes))
+        mirror = self._unc
+
+        def split(buf):
+            heads, lo, fo = [], 0, 8 * n_lab
+            for n, c in zip(rows, classes):
+                lab = buf[lo:lo + 8 * n].view(torch.int64)
+                lo += 8 * n
+                fl = buf[fo:fo + 4 * n * (c + 3)].view(torch.float32)
+                fo += 4 * n * (c + 3)
+                heads.append((lab, fl[:n * c].view(n, c), fl[n * c:n * c + n], fl[n * c + n:n * c + 2 * n], fl[n * c + 2 * n:]))
+            return tuple(heads) if len(rows) == 2 else heads[0]
+
+        with torch.cuda.device(dev):
+            mirror.reserve(nbytes, dev)
+            self.predict_mc(h, samples, seed, first_step, members=members, out=split(mirror.dev))
+            mirror.fetch(nbytes)
+        return split(mirror.host)
+
     def predict_pair(self, batch, members=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """:meth:`predict_labels` of a two-headed net on the host: both label vectors land in ONE device buffer and cross in one
         D2H through one pinned buffer and one event, as :meth:`predict` does for the room task.  Returns host int64 views of that
@@ -1341,6 +1444,52 @@ def _topk_buffers(out, rows: Sequence[int], k: int, pair: bool, dev) -> List[Tup
                 raise _lib.HydraMPError(f"out must be contiguous (int64, float32) tensors [rows >= {n}, {k}] on {dev}, got "
                                         f"{tuple(t.shape)} {t.dtype} on {t.device}")
     return [(lb, pb) for lb, pb in outs]
+
+
+MC_MAX_SAMPLES = 4096  # csrc/kernels.h
+
+
+def _check_samples(samples) -> int:
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= MC_MAX_SAMPLES:
+        raise _lib.HydraMPError(f"samples must be an integer in [1, {MC_MAX_SAMPLES}], got {samples!r}")
+    return samples
+
+
+def _check_first_step(first_step, samples: int) -> int:
+    """the dropout step of sample 0: samples t = 0 .. samples - 1 draw at the 32-bit step ``first_step + t``"""
+    if isinstance(first_step, bool) or not isinstance(first_step, int) or first_step < 0 or first_step + samples > 2 ** 32:
+        raise _lib.HydraMPError(f"first_step must be an integer with 0 <= first_step and first_step + samples <= 2**32, got {first_step!r} "
+                                f"with samples = {samples}")
+    return first_step
+
+
+def _check_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise _lib.HydraMPError(f"seed must be an integer in [0, 2**64), got {seed!r}")
+    return seed
+
+
+def _mc_buffers(out, rows: Sequence[int], classes: Sequence[int], pair: bool, dev) -> List[Tuple[torch.Tensor, ...]]:
+    """the ``(labels int64 [rows], mean_probs float32 [rows, C], std, entropy, mutual_info float32 [rows])`` outputs of ``predict_mc``
+    per head: fresh ones, or the caller's ``out`` after the checks ``_topk_buffers`` makes (structure, dtype, rows, C columns,
+    contiguity, device)"""
+    if out is None:
+        return [(torch.empty(max(n, 1), dtype=torch.int64, device=dev), torch.empty((max(n, 1), c), dtype=torch.float32, device=dev))
+                + tuple(torch.empty(max(n, 1), dtype=torch.float32, device=dev) for _ in range(3)) for n, c in zip(rows, classes)]
+    outs = list(out) if pair and isinstance(out, (tuple, list)) else [out]
+    ok = len(outs) == len(rows) and all(isinstance(o, (tuple, list)) and len(o) == 5 and all(isinstance(t, torch.Tensor) for t in o)
+                                        for o in outs)
+    if not ok:
+        what = "(labels, mean_probs, std, entropy, mutual_info)"
+        raise _lib.HydraMPError(f"out: {'a pair of ' + what + ' tuples (one per head)' if pair else 'one ' + what + ' tuple'} expected")
+    for o, n, c in zip(outs, rows, classes):
+        for i, t in enumerate(o):
+            dtype, dim = (torch.int64 if i == 0 else torch.float32), (2 if i == 1 else 1)
+            if (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.dim() != dim or t.size(0) < n
+                    or (i == 1 and t.size(1) != c)):
+                raise _lib.HydraMPError(f"out must be contiguous tensors (int64 [rows], float32 [rows, {c}], 3 x float32 [rows]) with rows "
+                                        f">= {n} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device} at position {i}")
+    return [tuple(o) for o in outs]
 
 
 def _attention_buffer(out, rows: int, cols: int, dtype, dev, what: str) -> torch.Tensor:

@@ -1,6 +1,6 @@
 """Validation accuracy on the device (room task: :func:`accuracy`; two-headed task: :func:`semisupervised_accuracy`) and the
 predicted labels themselves (:func:`predict`, every model and task; :func:`predict_topk` adds the next guesses and the softmax
-probability of each): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
+probability of each, :func:`predict_mc` the Monte-Carlo dropout mean, entropy and mutual information): ``BaseTrainingJob.test`` (``base_training_job.py:269-313``) without a sync
 per batch.
 
 The reference's ``test()`` runs an eval-mode forward per batch, takes ``argmax(dim=1)``, drops the rows whose label is the
@@ -277,6 +277,79 @@ def predict_topk(model, batches: Union[Iterable, Tuple[object, Iterable]], k: in
         heads.append(_split_topk(hl[totals[0]:], hp[totals[0]:], counts[1]))
         return list(zip(heads[0], heads[1]))
     return heads[0]
+
+
+def _split_mc(arrays, counts: np.ndarray):
+    """per-graph ``(labels [n], mean_probs [n, C], std [n], entropy [n], mutual_info [n])`` pieces, the rows outside the head's rows
+    (label -1) dropped: one compaction of the whole pass, then a slice per array and graph"""
+    keep = arrays[0] >= 0
+    off = np.concatenate([[0], np.cumsum(counts)])
+    if not keep.all():
+        off = np.concatenate([[0], np.cumsum(keep)])[off]  # the kept rows in front of every graph
+        arrays = [a[keep] for a in arrays]
+    return [tuple(a[off[g]:off[g + 1]] for a in arrays) for g in range(len(counts))]
+
+
+def predict_mc(model, batches: Union[Iterable, Tuple[object, Iterable]], samples: int, seed=None, first_step: int = 1):
+    """:func:`predict` with Monte-Carlo dropout uncertainty (``model.predict_mc`` per batch: ``samples`` training-mode forwards plus
+    one launch each and one finishing launch per head), one device-to-host copy and one synchronisation per pass.  ``batches`` takes
+    the forms :func:`predict` takes; ``seed`` None is the model's dropout seed, and every batch draws at the steps ``first_step ..
+    first_step + samples - 1``.
+
+    ``(BatchStream, iterable of graph-id lists)``: one buffer for the whole pass, sized from the store's per-graph node counts (all
+    labels, then each head's floats); every batch writes its slice through ``out=``.  The result has one entry per graph in id
+    order: ``(labels [n] int64, mean_probs [n, C], std [n], entropy [n], mutual_info [n] float32)`` numpy arrays over the rows
+    :func:`predict` returns for that graph, or a ``(room, object)`` pair of those.  An iterable of batches: one entry per BATCH, the
+    per-row arrays of ``model.predict_mc`` (``-1`` / ``0`` rows kept)."""
+    from .engine import _check_first_step, _check_samples
+
+    samples = _check_samples(samples)
+    first_step = _check_first_step(first_step, samples)
+    stream, id_lists = _pass_args(model, batches, "predict_mc")
+    dev = next(model.parameters()).device
+    if stream is None:
+        outs = [model.predict_mc(b, samples, seed, first_step) for b in batches]
+        two = bool(outs) and isinstance(outs[0][0], tuple)
+        flat = [t for o in outs for hd in (o if two else (o,)) for t in hd]  # labels, mean, std, entropy, mi, labels, ...
+        if not flat:
+            return []
+        host = torch.cat([t.reshape(-1).view(torch.uint8) for t in flat]).cpu().numpy()  # the one copy of the pass
+        sizes = np.cumsum([0] + [t.numel() * t.element_size() for t in flat])
+        parts = [host[sizes[i]:sizes[i + 1]].view(np.int64 if i % 5 == 0 else np.float32).reshape(tuple(t.shape))
+                 for i, t in enumerate(flat)]
+        heads = [tuple(parts[5 * i:5 * i + 5]) for i in range(len(parts) // 5)]
+        return [(heads[2 * i], heads[2 * i + 1]) for i in range(len(outs))] if two else heads
+    types = _label_types(model)
+    two = len(types) == 2
+    classes = model.native().head_classes()
+    all_ids = np.concatenate(id_lists) if id_lists else np.zeros(0, dtype=np.int64)
+    counts = [stream.store.node_counts[t][all_ids] for t in types]
+    totals = [int(c.sum()) for c in counts]
+    nbytes = 8 * sum(totals) + 4 * sum(r * (c + 3) for r, c in zip(totals, classes))
+    buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)  # every head's int64 labels, then each head's float32 arrays
+
+    def carve(b, view):
+        """per head (labels [R], mean [R, C], std [R], entropy [R], mi [R]) inside the pass buffer `b`"""
+        heads, lo, fo = [], 0, 8 * sum(totals)
+        for r, c in zip(totals, classes):
+            lab = view(b[lo:lo + 8 * r], False)
+            fl = view(b[fo:fo + 4 * r * (c + 3)], True)
+            lo, fo = lo + 8 * r, fo + 4 * r * (c + 3)
+            heads.append((lab, fl[:r * c].reshape(r, c), fl[r * c:r * c + r], fl[r * c + r:r * c + 2 * r], fl[r * c + 2 * r:]))
+        return heads
+
+    dev_heads = carve(buf, lambda b, f32: b.view(torch.float32 if f32 else torch.int64))
+    pos = [0, 0]
+    for ids in id_lists:
+        rows = [int(stream.store.node_counts[t][ids].sum()) for t in types]
+        views = [tuple(a[pos[h]:pos[h] + rows[h]] for a in dev_heads[h]) for h in range(len(types))]
+        model.predict_mc(stream.next(ids), samples, seed, first_step, out=tuple(views) if two else views[0])
+        for h in range(len(types)):
+            pos[h] += rows[h]
+    host = buf[:nbytes].cpu().numpy()  # the one copy (and synchronisation) of the pass
+    host_heads = carve(host, lambda b, f32: b.view(np.float32 if f32 else np.int64))
+    heads = [_split_mc(list(hd), c) for hd, c in zip(host_heads, counts)]
+    return list(zip(heads[0], heads[1])) if two else heads[0]
 
 
 def saliency(model, batches: Union[Iterable, Tuple[object, Iterable]], groups=((0, 3), (3, 6), (6, None)), **kw):

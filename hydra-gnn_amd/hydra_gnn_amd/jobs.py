@@ -468,6 +468,13 @@ class BaseTrainingJob:
         result), or a ``(room, object)`` pair of those for a two-headed model; one device-to-host copy per pass."""
         return self._predict_pass(split, self.get_dataset(split), k)
 
+    def predict_mc(self, split, samples):
+        """:meth:`predict` with Monte-Carlo dropout uncertainty over ``samples`` stochastic passes (``evaluate.predict_mc``, the
+        model's dropout seed): per graph ``(labels [n] int64, mean_probs [n, C], std [n], entropy [n], mutual_info [n] float32)``
+        numpy arrays over the rows :meth:`predict` returns, or a ``(room, object)`` pair of those for a two-headed model; one
+        device-to-host copy per pass."""
+        return self._predict_pass(split, self.get_dataset(split), mc=samples)
+
     def saliency(self, split, groups=((0, 3), (3, 6), (6, None)), **kw):
         """Gradient saliency of every graph of the split ``"train"`` / ``"val"`` / ``"test"``, from the job's own device-resident copy
         in ``batch_size`` batches with one device-to-host copy per pass (``evaluate.saliency``): per graph ``{node_type: (gxi [n],
@@ -484,14 +491,17 @@ class BaseTrainingJob:
         with torch.cuda.device(device):
             return evaluate.saliency(net, (self._stream(split, dataset, device, B), id_chunks(len(dataset), B)), groups=groups, **kw)
 
-    def _predict_pass(self, name, dataset, k=None):
-        """``k`` None: the labels of ``evaluate.predict``; else the top-k pairs of ``evaluate.predict_topk``"""
+    def _predict_pass(self, name, dataset, k=None, mc=None):
+        """``k`` None: the labels of ``evaluate.predict``; else the top-k pairs of ``evaluate.predict_topk``.  ``mc``: the sample
+        count of ``evaluate.predict_mc`` instead"""
         net = self._net
         net.eval()
         device = next(net.parameters()).device
         B = self._training_params["optimization_params"]["batch_size"]
         chunks = id_chunks(len(dataset), B)
         run = evaluate.predict if k is None else (lambda model, batches: evaluate.predict_topk(model, batches, k))
+        if mc is not None:
+            run = lambda model, batches: evaluate.predict_mc(model, batches, mc)  # noqa: E731
         with torch.cuda.device(device):
             if self._streams_batches():
                 return run(net, (self._stream(name, dataset, device, B), chunks))
@@ -501,8 +511,10 @@ class BaseTrainingJob:
         nodes = store.node_counts[store.node_types[0]]
         out = []
         for ids, labels in zip(chunks, per_batch):
-            two = isinstance(labels if k is None else labels[0], tuple)
-            if k is None:
+            two = isinstance(labels if (k is None and mc is None) else labels[0], tuple)
+            if mc is not None:
+                heads = [evaluate._split_mc(list(hd), nodes[ids]) for hd in (labels if two else (labels,))]
+            elif k is None:
                 heads = [evaluate._split_rows(v, nodes[ids]) for v in (labels if two else (labels,))]
             else:
                 heads = [evaluate._split_topk(lb, pb, nodes[ids]) for lb, pb in (labels if two else (labels,))]
@@ -734,6 +746,11 @@ class SemiSupervisedTrainingJob(BaseTrainingJob):
         """:meth:`predict` with the top-k labels and their softmax probabilities: per graph
         ``((room_labels [n, k], room_probs [n, k]), (object_labels, object_probs))`` numpy arrays (``evaluate.predict_topk``)."""
         return self._predict_pass("all", self._dataset, k)
+
+    def predict_mc(self, samples, split=None):
+        """:meth:`predict` with Monte-Carlo dropout uncertainty over ``samples`` stochastic passes: per graph a ``(room, object)``
+        pair of ``(labels [n], mean_probs [n, C], std [n], entropy [n], mutual_info [n])`` numpy arrays (``evaluate.predict_mc``)."""
+        return self._predict_pass("all", self._dataset, mc=samples)
 
     def test_individual_graph(self, dataset, model=None):
         return NotImplemented

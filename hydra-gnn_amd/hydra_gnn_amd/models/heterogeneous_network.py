@@ -18,6 +18,19 @@ from .._lib import ACT_ELU, ACT_NONE, ACT_RELU
 from .utils import build_GAT_hetero_conv, build_hetero_conv, cross_entropy_loss
 
 
+def _uncertainty_rows(heads):
+    """host ``predict_mc`` tuples (one, or a pair) as ``(labels, confidence, std, entropy, mutual_info)`` on the head's rows only:
+    the rows outside a head's rows (label -1) dropped, ``confidence`` = the mean probability of the label"""
+    two = isinstance(heads[0], tuple)
+    out = []
+    for lab, mean, sd, ent, mi in (heads if two else (heads,)):
+        keep = lab >= 0
+        lab = lab[keep]
+        conf = mean[keep].gather(1, lab.view(-1, 1)).view(-1) if lab.numel() else mean.new_zeros(0)
+        out.append((lab, conf, sd[keep], ent[keep], mi[keep]))
+    return tuple(out) if two else out[0]
+
+
 class _NativeModule(nn.Module):
     """Shared plumbing: lazily built :class:`NativeNet`, dropout RNG bookkeeping."""
 
@@ -109,6 +122,39 @@ class _NativeModule(nn.Module):
         a pair of those, ``((room_labels, room_confidence), (object_labels, object_confidence))``."""
         _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
         return self.native().predict_confidence(data)
+
+    # ---- Monte-Carlo dropout uncertainty -------------------------------------------------------------------------------
+    def _mc_args(self, samples, seed, first_step):
+        """the checked ``(samples, seed, first_step)`` of a Monte-Carlo call; ``seed`` None: the module's dropout seed"""
+        from ..engine import _check_first_step, _check_samples, _check_seed
+
+        samples = _check_samples(samples)
+        return samples, _check_seed(self._seed if seed is None else seed), _check_first_step(first_step, samples)
+
+    def predict_mc(self, data, samples=16, seed=None, first_step=1, out=None):
+        """Monte-Carlo dropout uncertainty, left on the device (nothing synchronises): ``samples`` stochastic passes -- pass ``t`` is
+        the training-mode ``forward()`` with the dropout masks of ``(seed, first_step + t)`` -- reduced per row to
+        ``(labels int64 [rows], mean_probs float32 [rows, C], std, entropy, mutual_info float32 [rows])`` over the rows of
+        :meth:`predict_labels`: the mean softmax over the passes, its argmax, the standard deviation of that label's probability,
+        the entropy of the mean and the mutual information between prediction and weights (BALD).  Room task: one such tuple;
+        two-headed: a pair.  Each pass is the native training-mode forward plus one launch, one more launch per head finishes
+        (:meth:`NativeNet.predict_mc`).  ``seed`` None: the module's dropout seed.  The module is left as it was: ``_rng_step`` is
+        neither read nor advanced, the ``training`` flag, parameters and buffers are untouched.  ``1 <= samples <= 4096``; ``out``
+        takes caller-owned buffers of that structure."""
+        samples, seed, first_step = self._mc_args(samples, seed, first_step)
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        with torch.no_grad():
+            return self.native().predict_mc(data, samples, seed, first_step, out=out)
+
+    def predict_with_uncertainty(self, data, samples=16):
+        """``(labels, confidence, std, entropy, mutual_info)`` of ``data`` on the host: :meth:`predict_mc` with the module's seed,
+        ``confidence`` being the mean probability of the label, through one pinned buffer and one device-to-host copy.  A two-headed
+        model returns a pair of those."""
+        samples, seed, first_step = self._mc_args(samples, None, 1)
+        _lib.require_device()  # no device: HydraMPError (there is no CPU fallback)
+        with torch.no_grad():
+            heads = self.native().predict_uncertainty(data, samples, seed, first_step)
+        return _uncertainty_rows(heads)
 
     # ---- attention export ([PyG] GATConv(..., return_attention_weights=True)) ----------------------------------------
     def _attention_layer(self, layer, who: str) -> int:

@@ -167,17 +167,19 @@ class HomogeneousNetwork(_NativeModule):
         """RNG tensor id of the feature dropout after conv ``l`` (the native program numbers its layers from 0, node type 0)"""
         return 8 * l
 
-    def _act_drop(self, x, l, bias=None):
+    def _act_drop(self, x, l, bias=None, _mc=None):
         """activation (relu; elu for GAT) + dropout after layer ``l`` (reference :135-136,141-142); the keep-mask is tensor
-        ``_drop_stream(l)`` of this call's RNG step"""
-        p = self.dropout if self.training else 0.0
+        ``_drop_stream(l)`` of this call's RNG step.  ``_mc = (seed, rng_step)``: a Monte-Carlo dropout pass -- dropout draws at
+        that site whatever the ``training`` flag says, and the module's own seed and step are not looked at"""
+        p = self.dropout if (self.training or _mc is not None) else 0.0
+        seed, rng_step = (self._seed, self._rng_step) if _mc is None else _mc
         gat = self.conv_block[:3] == "GAT"
-        return ops.bias_act_drop(x, bias, relu=not gat, elu=gat, p=p, seed=self._seed, rng_step=self._rng_step,
-                                 rng_stream=self._drop_stream(l))
+        return ops.bias_act_drop(x, bias, relu=not gat, elu=gat, p=p, seed=seed, rng_step=rng_step, rng_stream=self._drop_stream(l))
 
-    def _op_layers(self, x, plan, batch_norm=True):
+    def _op_layers(self, x, plan, batch_norm=True, _mc=None):
         """reference :125-136 for conv_block GCN / GIN; ``batch_norm`` False = the H-tree variant's loop, which never
-        applies ``batch_norms`` (homogeneous_neural_tree_network.py:86-94)."""
+        applies ``batch_norms`` (homogeneous_neural_tree_network.py:86-94).  ``_mc``: as :meth:`_act_drop` takes it (the caller
+        holds the module in eval mode, so BatchNorm reads its running statistics and updates nothing)."""
         if self.training:
             self._rng_step += 1
         L = self.num_layers
@@ -185,7 +187,7 @@ class HomogeneousNetwork(_NativeModule):
             last = l == L - 1
             if self.conv_block == "GCN":
                 a = ops.gcn_propagate(ops.project(x, conv.lin.weight), plan)
-                x = ops.bias_act_drop(a, conv.bias) if last else self._act_drop(a, l, conv.bias)
+                x = ops.bias_act_drop(a, conv.bias) if last else self._act_drop(a, l, conv.bias, _mc=_mc)
             else:
                 a = ops.gin_propagate(ops.project(x, conv.nn[0].weight), plan, conv.eps)
                 h = ops.bias_act_drop(a, conv.nn[0].bias, relu=True)
@@ -198,20 +200,20 @@ class HomogeneousNetwork(_NativeModule):
                         y = ops.batch_norm(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, self.training)
                         if self.training:
                             bn.num_batches_tracked += 1
-                    x = self._act_drop(y, l)
+                    x = self._act_drop(y, l, _mc=_mc)
         return x
 
-    def _op_heads(self, x, room_mask, object_mask):
+    def _op_heads(self, x, room_mask, object_mask, _mc=None):
         """reference :138-146"""
         if self.classification_task == "room":
             return x[room_mask, :]
-        x = self._act_drop(x, self.num_layers - 1)
+        x = self._act_drop(x, self.num_layers - 1, _mc=_mc)
         head = lambda lin, rows: ops.bias_act_drop(ops.project(rows, lin.weight), lin.bias)
         return head(self.post_mp_room, x[room_mask, :]), head(self.post_mp_object, x[object_mask, :])
 
-    def _op_states(self, data):
+    def _op_states(self, data, _mc=None):
         """final states of every node on the op path (GCN / GIN), before the readout"""
-        return self._op_layers(data.x, ops.GraphPlan(data.edge_index, data.x.size(0)))
+        return self._op_layers(data.x, ops.GraphPlan(data.edge_index, data.x.size(0)), _mc=_mc)
 
     def count_correct_rooms(self, data, counts=None, confusion=None, ignored_label=25):
         """The per-batch arithmetic of ``BaseTrainingJob.test`` (base_training_job.py:269-313) for the room task: eval-mode
@@ -373,6 +375,78 @@ class HomogeneousNetwork(_NativeModule):
             heads = heads if two else (heads,)
         heads = tuple((lb[lb >= 0], pb[lb >= 0]) for lb, pb in heads)  # the rows outside a head's rows dropped on the host
         return heads if two else heads[0]
+
+    def predict_mc(self, data, samples=16, seed=None, first_step=1, out=None):
+        """Monte-Carlo dropout uncertainty on the device, one row per NODE as :meth:`predict_labels` lays them out: per head
+        ``(labels int64 [nodes], mean_probs float32 [nodes, C], std, entropy, mutual_info float32 [nodes])`` over ``samples``
+        stochastic passes, pass ``t`` drawing its dropout masks at ``(seed, first_step + t)`` (``seed`` None: the module's), ``-1`` /
+        ``0`` outside the head's rows.  Room task: one such tuple; two-headed: a pair.  ``data`` and ``out`` as :meth:`predict_topk`
+        takes them (``out`` in that structure).  SAGE / GAT: per pass the native training-mode forward plus one launch, then one
+        launch per head (:meth:`NativeNet.predict_mc`).  GCN / GIN: per pass the op-by-op forward with dropout drawing and
+        BatchNorm in eval mode (running statistics, nothing updated), then ``hmp_mc_accumulate_rows`` per head, and
+        ``hmp_mc_finish`` (two-headed: scattered to the head's rows).  ``_rng_step``, the ``training`` flag, parameters and buffers
+        are left as they were."""
+        from .._lib import require_device
+        from ..engine import _BatchHolder, _mc_buffers
+
+        samples, seed, first_step = self._mc_args(samples, seed, first_step)
+        require_device()  # no device: HydraMPError (there is no CPU fallback)
+        two = self.classification_task == "all"
+        if isinstance(data, _BatchHolder):
+            if self.op_path:
+                raise HydraMPError(f"predict_mc: {self.conv_block} runs op by op: pass a collated Data batch")
+            with torch.no_grad():
+                return self.native().predict_mc(data, samples, seed, first_step, out=out)
+        if not self.op_path:
+            with torch.no_grad():
+                return self.native().predict_mc(self._view(data), samples, seed, first_step, members=self._members(data), out=out)
+        n, dev = data.x.size(0), data.x.device
+        if not two:
+            classes = [int(self.convs[-1].lin.weight.size(0) if self.conv_block == "GCN" else self.convs[-1].nn[2].weight.size(0))]
+        else:
+            classes = [int(self.post_mp_room.out_features), int(self.post_mp_object.out_features)]
+        outs = _mc_buffers(out, [n] * len(classes), classes, two, dev)
+        obj = self._object_rows(data)
+        head_rows = (data.room_mask, ~data.room_mask if obj is None else obj)
+        accs = None
+        with self._eval_mode():
+            for t in range(samples):
+                mc = (seed, first_step + t)
+                states = self._op_states(data, _mc=mc)
+                if not two:
+                    accs = accs or [ops.mc_acc(n, classes[0], dev)]
+                    ops.mc_accumulate_rows(states, accs[0], t == 0, data.room_mask)
+                    continue
+                logits = self._op_heads(states, head_rows[0], head_rows[1], _mc=mc)
+                accs = accs or [ops.mc_acc(lg.size(0), c, dev) for lg, c in zip(logits, classes)]
+                for lg, acc in zip(logits, accs):
+                    ops.mc_accumulate_rows(lg, acc, t == 0)
+            if not two:
+                return ops.mc_finish(accs[0], classes[0], samples, data.room_mask, outs[0])
+            for bufs, acc, c, rows in zip(outs, accs, classes, head_rows):
+                for buf, values in zip(bufs, ops.mc_finish(acc, c, samples)):
+                    buf[:n].fill_(0 if buf.is_floating_point() else -1)
+                    buf[:n][rows] = values
+        return tuple(tuple(b[:n] for b in bufs) for bufs in outs)
+
+    def predict_with_uncertainty(self, data, samples=16):
+        """``(labels, confidence, std, entropy, mutual_info)`` on the host: :meth:`predict_mc` with the module's seed on the head's
+        rows (the ``room_mask`` rows; two-headed: each head's rows, in row order), ``confidence`` the mean probability of the label,
+        through one pinned buffer and one device-to-host copy (GCN / GIN: one copy per output).  A two-headed model returns a pair
+        of those."""
+        from .._lib import require_device
+        from .heterogeneous_network import _uncertainty_rows
+
+        samples, seed, first_step = self._mc_args(samples, None, 1)
+        require_device()  # no device: HydraMPError (there is no CPU fallback)
+        if self.op_path:
+            heads = self.predict_mc(data, samples)
+            two = self.classification_task == "all"
+            heads = tuple(tuple(t.cpu() for t in hd) for hd in (heads if two else (heads,)))
+            return _uncertainty_rows(heads if two else heads[0])
+        with torch.no_grad():
+            heads = self.native().predict_uncertainty(self._view(data), samples, seed, first_step, members=self._members(data))
+        return _uncertainty_rows(heads)
 
     def _predict_two(self, data):
         """host ``(room_labels, object_labels)``: the labels of the ``room_mask`` rows and of the object head's rows, in row order

@@ -126,12 +126,12 @@ class HomogeneousNeuralTreeNetwork(HomogeneousNetwork):
     def _view(self, data):
         return _HtreeView(data, self.pre_mp is not None)
 
-    def _op_states(self, data):
+    def _op_states(self, data, _mc=None):
         x = data.x
         if self.pre_mp is not None:
             x = self.native().forward(_InitView(data), self.training, self._seed, 0)[:, : self.input_dim]
         n = data.x.size(0)
-        x = self._op_layers(x, ops.GraphPlan(data.edge_index, n), batch_norm=False)
+        x = self._op_layers(x, ops.GraphPlan(data.edge_index, n), batch_norm=False, _mc=_mc)
         return ops.segment_mean(x, ops.GraphPlan(data.pool_edge_index, n))
 
     def forward(self, data):

@@ -323,6 +323,75 @@ def topk_rows(logits: torch.Tensor, k: int, members: Optional[torch.Tensor] = No
     return labels[:n], probs[:n]
 
 
+def mc_acc(rows: int, n_classes: int, device) -> torch.Tensor:
+    """Monte-Carlo dropout accumulators of ``rows`` rows with ``n_classes`` classes: an uninitialised float32 ``[rows, ld]`` tensor on
+    ``device`` with ``ld = hmp_mc_acc_ld(n_classes)`` (include/hydra_mp.h states the layout).  The first sample is stored
+    (``first=True``), so nothing needs zeroing."""
+    if isinstance(n_classes, bool) or not isinstance(n_classes, int) or n_classes < 1 or int(rows) < 0:
+        raise _lib.HydraMPError(f"mc_acc: rows {rows!r} (>= 0), n_classes {n_classes!r} (>= 1)")
+    return torch.empty((int(rows), int(_lib.load().hmp_mc_acc_ld(n_classes))), dtype=torch.float32, device=device)
+
+
+def _check_mc_acc(acc, n_classes: int, device, who: str) -> None:
+    if (not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32 or acc.dim() != 2 or acc.device != device
+            or (acc.size(0) > 1 and acc.stride(0) < acc.size(1)) or (acc.numel() and acc.stride(1) != 1)
+            or acc.size(1) < int(_lib.load().hmp_mc_acc_ld(n_classes))):
+        raise _lib.HydraMPError(f"{who}: acc must be a row-major float32 tensor [rows, >= hmp_mc_acc_ld({n_classes})] on {device} "
+                                "(ops.mc_acc makes one)")
+
+
+def _acc_ld(acc: torch.Tensor) -> int:
+    return acc.stride(0) if acc.size(0) > 1 else acc.size(1)
+
+
+def mc_accumulate_rows(logits: torch.Tensor, acc: torch.Tensor, first: bool, members: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One Monte-Carlo dropout sample (``hmp_mc_accumulate_rows``): the softmax of every row of ``logits`` -- bit-equal to
+    :func:`topk_rows`' probabilities --, its squares and its entropy are ADDED to the row's accumulators in ``acc`` (from
+    :func:`mc_acc`, one row per row of ``logits``), or STORED with ``first=True``.  Rows where the bool filter ``members`` is False
+    are not touched.  Returns ``acc``; nothing synchronises."""
+    _dev(logits, "logits")
+    logits = _rows(logits)
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise _lib.HydraMPError(f"logits must be [rows, classes >= 1], got {tuple(logits.shape)}")
+    n, n_classes = logits.size(0), logits.size(1)
+    _check_mc_acc(acc, n_classes, logits.device, "mc_accumulate_rows")
+    if acc.size(0) != n:
+        raise _lib.HydraMPError(f"mc_accumulate_rows: acc has {acc.size(0)} rows, logits {n}")
+    members = row_members(members, n, logits.device)
+    if n:
+        with torch.cuda.device(logits.device):
+            _lib.check(_lib.load().hmp_mc_accumulate_rows(logits.data_ptr(), logits.stride(0) if n > 1 else n_classes, n, n_classes,
+                                                          members.data_ptr() if members is not None else None, 1 if first else 0,
+                                                          acc.data_ptr(), _acc_ld(acc), _lib.stream_ptr()))
+    return acc
+
+
+def mc_finish(acc: torch.Tensor, n_classes: int, samples: int, members: Optional[torch.Tensor] = None, out=None):
+    """``(labels int64 [rows], mean_probs float32 [rows, n_classes], std, entropy, mutual_info float32 [rows])`` of ``samples``
+    accumulated samples on the device (``hmp_mc_finish``): the mean predictive distribution, its first-maximum argmax, the standard
+    deviation of the label's probability over the samples, the entropy of the mean and the mutual information between prediction
+    and weights (entropy of the mean minus mean entropy, clamped at 0).  Rows where ``members`` is False hold ``-1`` / ``0``.
+    ``out``: such a 5-tuple of contiguous tensors with at least ``rows`` rows on the same device.  Nothing synchronises."""
+    from .engine import _check_samples, _mc_buffers
+
+    samples = _check_samples(samples)
+    if isinstance(n_classes, bool) or not isinstance(n_classes, int) or n_classes < 1:
+        raise _lib.HydraMPError(f"mc_finish: n_classes {n_classes!r} (>= 1)")
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda:
+        raise _lib.HydraMPError("mc_finish: acc is not a device tensor; hydra_gnn_amd has no CPU fallback")
+    _check_mc_acc(acc, n_classes, acc.device, "mc_finish")
+    n = acc.size(0)
+    members = row_members(members, n, acc.device)
+    bufs = _mc_buffers(out, [n], [n_classes], False, acc.device)[0]
+    if n:
+        with torch.cuda.device(acc.device):
+            _lib.check(_lib.load().hmp_mc_finish(acc.data_ptr(), _acc_ld(acc), n, n_classes, samples,
+                                                 members.data_ptr() if members is not None else None, bufs[0].data_ptr(),
+                                                 bufs[1].data_ptr(), n_classes, bufs[2].data_ptr(), bufs[3].data_ptr(),
+                                                 bufs[4].data_ptr(), _lib.stream_ptr()))
+    return tuple(b[:n] for b in bufs)
+
+
 def check_count_buffers(counts: torch.Tensor, confusion: Optional[torch.Tensor], n_classes: int, device) -> None:
     """the accumulators of the room-task validation count: ``counts`` contiguous int64[>= 2], ``confusion`` (optional) contiguous
     int64 with ``n_classes ** 2`` elements, both on ``device``"""

@@ -618,6 +618,12 @@ class BatchStream:
             raise _lib.HydraMPError("member_rows: the stream's heads are whole node types (no member rows)")
         return tg.d_member[0], tg.d_member[1]
 
+    def room_rows(self) -> torch.Tensor:
+        """the collated ``room_mask`` buffer of a linear-head stream itself (capacity rows; the batch's rows lead), whose address
+        :meth:`member_rows` returns first"""
+        self.member_rows()
+        return self._buf_of[("node", self._label_types[0], "room_mask")]
+
     def next(self, ids) -> "object":
         """collate graphs ``ids`` (len == batch_size or fewer) into the stream's buffers; returns the descriptor for TrainStep.run"""
         sel = np.ascontiguousarray(ids, dtype=np.int32)

@@ -75,7 +75,11 @@ extern "C" {
  *    the gather-add term of the input-gradient GEMM): new entries, no struct was added or changed layout;
  *    hmp_front_seg / hmp_front_prob / hmp_pack_seg (hmp_sizeof 17..19), hmp_front_run / hmp_pack_run: unit-test entries of the
  *    front launch's projection and pack roles and of the stand-alone pack.  New entries and new structs, nothing above changed
- *    layout */
+ *    layout;
+ *    hmp_mc_acc_ld / hmp_mc_accumulate_rows / hmp_mc_finish, hmp_net_mc_rooms / hmp_net_mc2 / hmp_net_mc_heads (Monte-Carlo dropout
+ *    uncertainty for every net kind: per-row accumulators of the stochastic samples' softmax, and their mean, standard deviation,
+ *    entropy and mutual information), hmp_head_tails_mc / hmp_linear_heads_mc (their test entries): new entries, no struct was added
+ *    or changed layout */
 #define HMP_ABI_VERSION 4
 
 #define HMP_OK 0
@@ -463,6 +467,39 @@ int hmp_predict_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t 
  * synchronises.  (ABI-4-compatible addition.) */
 int hmp_topk_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int32_t k,
                   int64_t* d_labels, float* d_probs, void* stream);
+/* Monte-Carlo dropout uncertainty: T stochastic samples of a row's scores are reduced to the mean predictive distribution, its
+ * entropy and the mutual information between prediction and weights (BALD) through per-row accumulators.  (ABI-4-compatible
+ * additions.)
+ *
+ * Accumulators: one caller-owned device float buffer [rows][ld_acc] per head, ld_acc >= hmp_mc_acc_ld(n_classes) (= 2 * Cp + 4 with
+ * Cp = n_classes rounded up to 4; 0 for n_classes < 1).  A row holds
+ *   A[c] = sum_t p_t[c]   at column c,          c < n_classes
+ *   B[c] = sum_t p_t[c]^2 at column Cp + c,     c < n_classes
+ *   E    = sum_t h_t      at column 2 * Cp;
+ * every other column of the row (the padding behind A and B, everything past 2 * Cp) is never read or written.
+ *
+ * hmp_mc_accumulate_rows adds ONE sample: for a row's scores s = d_logits[r, 0:n_classes),
+ *   p[c] = expf(s[c] - m) / sum_c' expf(s[c'] - m), m the row maximum -- the arithmetic and association of hmp_topk_rows (per lane
+ *   of the row's 16 in ascending column order, then an xor butterfly, whatever the pitch): p[c] is bit-equal to the probability
+ *   hmp_topk_rows stores for class c on the same scores;
+ *   h = -sum_c p[c] * logf(p[c]) in the same association, a term with p[c] == 0 being 0;
+ *   A[c] += p[c], B[c] += p[c] * p[c], E += h.  first != 0 STORES the sample instead: the buffer needs no memset and may hold
+ *   anything, NaN included.  The row's 16 lanes are its only writer and samples are ordered by the stream: no atomics, results are
+ *   bit-reproducible.  Rows with d_members[r] == 0 (d_members NULL: every row) are not touched.  NaN scores are unspecified.  One
+ *   launch; n_rows == 0 launches nothing; nothing synchronises. */
+int32_t hmp_mc_acc_ld(int32_t n_classes);
+int hmp_mc_accumulate_rows(const float* d_logits, int32_t ld, int32_t n_rows, int32_t n_classes, const uint8_t* d_members, int32_t first,
+                           float* d_acc, int32_t ld_acc, void* stream);
+/* The statistics of `samples` = T accumulated samples (1 <= T <= 4096, else HMP_E_ARG), one launch over plain buffers:
+ *   mean[c] = A[c] / (float)T;   label = first-maximum argmax of mean (hmp_predict_rows' rule);
+ *   std = sqrtf(max(0, B[label] / T - mean[label]^2));   entropy = -sum_c mean[c] * logf(mean[c]) (a zero term is 0);
+ *   mutual_info = max(0, entropy - E / T).
+ * d_labels int64 [n_rows], d_mean float [n_rows][ld_mean] (ld_mean >= n_classes; columns >= n_classes are not written), d_std /
+ * d_entropy / d_mi float [n_rows]: each may be NULL (skipped), not all.  A row with d_members[r] == 0 holds -1 / 0 and its
+ * accumulators are not read.  Every requested element of rows [0, n_rows) is written exactly once, nothing behind them.  n_rows == 0
+ * launches nothing; nothing synchronises. */
+int hmp_mc_finish(const float* d_acc, int32_t ld_acc, int32_t n_rows, int32_t n_classes, int32_t samples, const uint8_t* d_members,
+                  int64_t* d_labels, float* d_mean, int32_t ld_mean, float* d_std, float* d_entropy, float* d_mi, void* stream);
 /* d_count: device float holding the valid-label count or weight sum (grad_scale = 1 / (count > 0 ? count : 1)); NULL => grad_scale = 1 */
 int hmp_adam_flat(float* d_p, const float* d_g, float* d_m, float* d_v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int32_t step, const float* d_count, void* stream);
@@ -552,6 +589,11 @@ int hmp_head_tails_predict(const hmp_tail_desc* d, int32_t n, int32_t pooled, in
  * One launch for both heads. */
 int hmp_head_tails_topk(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int32_t k, int64_t* const* d_labels,
                         float* const* d_probs, void* stream);
+/* The Monte-Carlo launch of the same descriptors (TRAINING mode: the tail draws at each descriptor's dropout site; the contract of
+ * hmp_mc_accumulate_rows on the rows hmp_head_tails_topk walks): d_acc[i] float [rows][ld_acc[i]] for EVERY row of head i (an empty
+ * pooled row is all zeros: p = 1 / classes).  d_acc[i] may be NULL only when the head has no rows.  One launch for both heads. */
+int hmp_head_tails_mc(const hmp_tail_desc* d, int32_t n, int32_t pooled, int32_t act, int32_t first, float* const* d_acc,
+                      const int32_t* ld_acc, void* stream);
 /* Two linear heads over one final state z [n_rows][ldz]: logits_h = dropout(act(z)) W_h^T + b_h on the rows of head h (member[0]
  * NULL: every row; member[1] NULL: the complement of member[0], empty when both are NULL), W_h [classes[h]][F] dense.
  * grad [n_rows][ldg], ldg == F rounded up to 4 (columns F .. ldg written 0); row_lv [n_rows][2] = {loss_0 + loss_1, valid_0 + valid_1};
@@ -587,6 +629,11 @@ int hmp_linear_heads_predict(const hmp_linear_heads_desc* d, int64_t* const* d_p
  * [n_rows][k] for the rows of member[h], -1 / 0 elsewhere; a head whose two pointers are both NULL is skipped.  1 <= k <= 8. */
 int hmp_linear_heads_topk(const hmp_linear_heads_desc* d, int32_t k, int64_t* const* d_labels, float* const* d_probs,
                           int32_t* n_blocks_out, void* stream);
+/* The Monte-Carlo launch (TRAINING mode: the tail draws at the descriptor's dropout site; the contract of hmp_mc_accumulate_rows on
+ * head h's logits): d_acc[h] float [n_rows][ld_acc[h]], touched on the rows of member[h] alone; a head with a NULL accumulator is
+ * skipped. */
+int hmp_linear_heads_mc(const hmp_linear_heads_desc* d, int32_t first, float* const* d_acc, const int32_t* ld_acc, int32_t* n_blocks_out,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 6. network executor -- the whole HeteroConv layer stack as one native program.
@@ -855,6 +902,25 @@ int hmp_net_topk2(hmp_net* net, const hmp_batch* batch, const float* d_params, i
  * elsewhere.  A head whose two pointers are both NULL is skipped. */
 int hmp_net_topk_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], int32_t k,
                        int64_t* const d_labels[2], float* const d_probs[2], void* stream);
+/* Monte-Carlo dropout, for every net kind: ONE stochastic sample per call -- hmp_net_forward(training = 1, seed, rng_step): feature
+ * dropout, GAT attention dropout and the readout's tail dropout all draw at (seed, rng_step) -- then exactly ONE launch (the
+ * contract of hmp_mc_accumulate_rows, on each net kind's score vector = what forward() returns for the row in training mode) that
+ * adds the sample to the caller's accumulators (first != 0: stores it).  A caller runs T calls with rng_step = first_step + t and
+ * then hmp_mc_finish per head.  Everything else -- plan_valid, the overwritten activations, no allocation or synchronisation, the
+ * refusals (checked before the forward, an ld_acc below hmp_mc_acc_ld among them) -- is the top-k entry's.  (ABI-4-compatible
+ * additions.)
+ * room task: rows = n_out; rows with d_members[row] == 0 are not touched. */
+int hmp_net_mc_rooms(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* d_members, uint64_t seed,
+                     uint32_t rng_step, int32_t first, float* d_acc, int32_t ld_acc, void* stream);
+/* two-headed nets with aux readout: head 0 per readout row, head 1 per aux row, scores dropout(act(z)); with hmp_net_set_head_pools
+ * per DESTINATION row of each pooled head, scores the LeafPool mean of dropout(act(z)) (a row without an edge: p = 1 / C).  A head
+ * with a NULL accumulator is skipped. */
+int hmp_net_mc2(hmp_net* net, const hmp_batch* batch, const float* d_params, uint64_t seed, uint32_t rng_step, int32_t first,
+                float* const d_acc[2], const int32_t ld_acc[2], void* stream);
+/* linear heads: head h's logits on dropout(act(z)) for the rows of d_member[h] (hmp_net_predict_heads' rule); other rows are not
+ * touched.  A head with a NULL accumulator is skipped. */
+int hmp_net_mc_heads(hmp_net* net, const hmp_batch* batch, const float* d_params, const uint8_t* const d_member[2], uint64_t seed,
+                     uint32_t rng_step, int32_t first, float* const d_acc[2], const int32_t ld_acc[2], void* stream);
 /* Attention export of a bound net (any net kind with a GAT layer): the eval-mode forward of `batch` (the predict entries' forward:
  * plan_valid, the overwritten activations, no allocation or synchronisation), then ONE launch -- recorded under profile class 9,
  * gat_fwd -- that writes, for program layer `layer` (0 .. n_layers - 1) and every edge type e with a non-NULL slot, the outputs of
